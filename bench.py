@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- Langevin think-iterations/sec of the HIP path (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -16,10 +16,18 @@ IS_FLUX, IS_FLOW)` builds it (reference lanpaint.py:8) -- rng="torch" (the refer
 in-kernel), graph="auto", the reference's fp32 mask (which the engine bit-packs by itself).  --rng / --graph / --mask-format
 select other configurations; `summary.philox_bits_it_s` carries the fastest one beside the headline.
 
-ONE JSON line (< 6 KB, the last line of stdout) carries metric/value/config, `parity_check` (the timed engine against the CPU
-oracle before anything is timed), `roofline` (the dominant kernel: algorithmic bytes per launch / mean launch duration from
-HIP events on the launch stream, THIS run), `cpu_baseline` (the CPU port of the reference on this box's host cores, bounded
-sample) and a few scalars; everything else goes to the side-car file `bench_extras.json` (benchkit/line.py).
+A plain run sets up, warms up, times the K steps and prints ONE JSON line (< 6 KB, the last line of stdout) with
+metric/value/config and `ms_per_step`; `parity_check`, `roofline`, `cpu_baseline` and `summary` are null.  --full adds the
+rest: `parity_check` (the timed engine against the CPU oracle before anything is timed), `roofline` (the
+dominant kernel: algorithmic bytes per launch / mean launch duration from HIP events on the launch stream, THIS run),
+`cpu_baseline` (the CPU port of the reference on this box's host cores, bounded sample), the run-to-run repeats and the summary
+scalars; everything else goes to the side-car file `bench_extras.json` (benchkit/line.py).
+
+--dump-outputs DIR writes, after the timed steps, the final latent of the LAST timed step (what `schedule_pass` hands its
+caller) as DIR/final_latent.npy (fp32; DIR/final_latent_rank<r>.npy at N > 1; a fixed, seeded sample of it past 64 MB in all).
+Inputs come from --seed, and torch's generator is reseeded from it right before the timed steps, so with the same arguments the
+dump is the same from run to run and can be compared between builds (--rng philox excepted: its launch counter also counts
+the time-bounded pre-warm passes).
 """
 from __future__ import annotations
 
@@ -80,13 +88,15 @@ def run_gpu(args):
     rng_name = args.rng or "torch"
     kernel_rng = "torch" if rng_name.startswith("torch") else "philox"
 
-    # Per-dispatch event timing of the dominant kernel, taken FIRST in the process (before graph captures and other streams
-    # exist) and by EVERY rank, before the process group exists: no rank ever waits in a collective for another's local work.
-    try:
-        steady = measure_steady_launch(_cabi, dev, workload=args.workload, launches=120, mask_kind=args.mask, rng=kernel_rng,
-                                       mask_format="bits")          # (a binary fp32 / u8 mask reaches the kernels bit-packed)
-    except Exception as e:
-        steady = {"error": repr(e)}
+    # --full: per-dispatch event timing of the dominant kernel, taken FIRST in the process (before graph captures and other
+    # streams exist) and by EVERY rank, before the process group exists: no rank ever waits in a collective for another's local work.
+    steady = None
+    if args.full:
+        try:
+            steady = measure_steady_launch(_cabi, dev, workload=args.workload, launches=120, mask_kind=args.mask, rng=kernel_rng,
+                                           mask_format="bits")          # (a binary fp32 / u8 mask reaches the kernels bit-packed)
+        except Exception as e:
+            steady = {"error": repr(e)}
 
     job = Job(args.workload, dev, seed=lpd.replica_seed(args.seed, rank), mask_kind=args.mask, mask_format="f32")
     def fail(what, e):
@@ -117,7 +127,7 @@ def run_gpu(args):
         job.mask, job.y = got["mask"], got["y"]
         cond = {k: v for k, v in got.items() if k not in ("mask", "y")}
         job.renoise()
-    if len(job.shape) == 5 and (args.mask or "temporal") == "temporal" and rank == 0:
+    if args.full and len(job.shape) == 5 and (args.mask or "temporal") == "temporal" and rank == 0:
         # job set-up as a workflow does it: the pixel-resolution video mask goes through reshape_mask's video path
         # (lp_reshape_mask: nearest-exact + 5-tap temporal union) and must give the latent mask used here
         from lanpaint_amd import nodes as lpn
@@ -145,7 +155,7 @@ def run_gpu(args):
     # pass against the CPU oracle on the same draws (bounded on the video-latent shapes and at N > 1, where every rank checks
     # its own replica).  No `value` is printed when the pass is off by more than the stated tolerance.
     parity = None
-    if not args.no_parity_check:
+    if args.full and not args.no_parity_check:
         n_par = args.parity_sigmas if args.parity_sigmas > 0 else (job.n_sig if (job.n_el <= 512 * 1024 and world == 1) else (8 if job.n_el <= 512 * 1024 else 2))
         try:
             parity = check_job(job, engine, max_sigmas=n_par)
@@ -161,6 +171,7 @@ def run_gpu(args):
     for _ in range(args.warmup):
         job.run(engine)
     t_setup = time.perf_counter() - t_proc0
+    torch.manual_seed(lpd.replica_seed(args.seed, rank))           # the timed steps' noise stream: independent of the pre-warm
     barrier()
     first_wait = waits[-1] if waits else None
     it0, cpu0, t0 = engine.iterations_run, time.process_time(), time.perf_counter()
@@ -173,6 +184,8 @@ def run_gpu(args):
     elapsed = time.perf_counter() - t0
     iters_local = engine.iterations_run - it0
     assert torch.isfinite(x_last).all(), "bench produced non-finite latents"
+    if args.dump_outputs:
+        bl.dump_outputs(args.dump_outputs, {"final_latent" + (f"_rank{rank}" if world > 1 else ""): x_last}, world)
 
     tmax, iters_total = lpd.reduce_throughput(elapsed, iters_local, dev)
     dist_info = lpd.gather_rank_reports({
@@ -202,7 +215,7 @@ def run_gpu(args):
     # run-to-run spread of the same measurement: further blocks of K steps, each bracketed like the timed region
     # (the headline `value` stays the first block -- exactly K steps, as the contract says)
     repeat_values = []
-    for _ in range(max(0, args.repeats)):
+    for _ in range(max(0, args.repeats) if args.full else 0):
         barrier()
         itr, tr = engine.iterations_run, time.perf_counter()
         for _ in range(args.steps):
@@ -220,8 +233,9 @@ def run_gpu(args):
 
     # ---- rank 0, outside every timed region: the secondary numbers (never at the cost of the line) ----
     sidecar = {"roofline": steady, "parity_check": parity, "dist": dist_info, "argv": sys.argv[1:]}
-    summary = {"repeats_median": float(np.median(repeat_values)) if repeat_values else None,
-               "repeats_min": min(repeat_values) if repeat_values else None, "repeats_max": max(repeat_values) if repeat_values else None}
+    summary = None if not args.full else {"repeats_median": float(np.median(repeat_values)) if repeat_values else None,
+                                          "repeats_min": min(repeat_values) if repeat_values else None,
+                                          "repeats_max": max(repeat_values) if repeat_values else None}
     live = None
     if world == 1 and args.pmc:
         try:
@@ -234,7 +248,7 @@ def run_gpu(args):
                                               traffic_source="live: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this launch in this run"))
         except Exception as e:
             sidecar["live_pmc"] = {"error": repr(e)}
-    if world == 1 and not args.no_summary:
+    if world == 1 and args.full and not args.no_summary:
         try:
             from benchkit.extras import summary_scalars
             s, detail = summary_scalars(args, dev, None if parity_failed else value, _cabi)
@@ -249,7 +263,7 @@ def run_gpu(args):
         except Exception as e:
             sidecar["extras"] = {"error": repr(e)}
     cpu = None
-    if not args.no_cpu_baseline:     # rank 0 only, after the process group is gone: host time nobody waits for
+    if args.full and not args.no_cpu_baseline:     # rank 0 only, after the process group is gone: host time nobody waits for
         try:
             try:
                 os.sched_setaffinity(0, affinity0)      # the baseline is the port on the BOX's host cores, not on one NUMA node's
@@ -261,7 +275,7 @@ def run_gpu(args):
     sidecar["cpu_baseline"] = cpu
     line = build_line(args, job.shape, job.n_sig, job.n_think, job.flow, value, tmax, parity, steady, cpu, summary, dist_info,
                       captured_calls=len(engine._graphs), mask_packed=getattr(job.mask, "_lp_bits", None) is not None)
-    line["extras_file"] = bl.write_sidecar(bl.sidecar_path(args.sidecar), dict(sidecar, line=line))
+    line["extras_file"] = bl.write_sidecar(bl.sidecar_path(args.sidecar), dict(sidecar, line=line)) if args.full else None
     bl.emit_line(line)
     if parity_failed:
         raise SystemExit(3)
@@ -296,7 +310,14 @@ def parse_args(argv=None):
     ap.add_argument("--extras", type=int, default=0, help="1: also run the secondary measurements (side-car file only)")
     ap.add_argument("--pmc", action="store_true", help="measure roofline.traffic live (re-runs the steady launch under rocprofv3 --pmc)")
     ap.add_argument("--sidecar", default=None, help="path of the side-car JSON (default: bench_extras.json next to bench.py)")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="write the last timed step's final latent as DIR/*.npy")
+    ap.add_argument("--full", action="store_true", help="also measure and check what the headline does not need: parity "
+                    "check, roofline, repeats, summary scalars, cpu_baseline, side-car file (the options above that tune those "
+                    "legs act only with --full)")
+    args = ap.parse_args(argv)
+    if (args.pmc or args.extras) and not args.full:
+        ap.error("--pmc / --extras measure beyond the headline: add --full")
+    return args
 
 
 def main():

@@ -75,6 +75,23 @@ def write_sidecar(path, payload):
         return f"not written ({type(e).__name__})"
 
 
+MAX_DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays, world=1):
+    """--dump-outputs: each tensor as `path`/<name>.npy in fp32.  This rank's share of MAX_DUMP_BYTES is 1 / world; a tensor past
+    it is written as a sample: the elements of the flattened tensor at sorted indices drawn without replacement from a
+    generator seeded with 0, so two runs (or two builds) write the same positions."""
+    os.makedirs(path, exist_ok=True)
+    budget = MAX_DUMP_BYTES // max(1, world) // max(1, len(arrays))
+    for name, t in arrays.items():
+        a = t.detach().float().cpu().numpy()
+        if a.nbytes > budget:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, size=budget // 4, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+
+
 def emit_line(line):
     """Serialise, bound and print the line as the LAST line of stdout."""
     out = bounded(line)

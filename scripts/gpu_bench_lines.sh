@@ -3,19 +3,19 @@
 # noise stream, a 2-rank rehearsal on the one GPU of the box); results under gpurun_out/bench/.
 set -u
 R=$PWD; OUT=$R/gpurun_out/bench; rm -rf $OUT; mkdir -p $OUT
-python bench.py > $OUT/bench_c2.json 2> $OUT/bench_c2.err
-python bench.py --workload c1_sd15 --no-cpu-baseline --extras 0 --no-large-shape > $OUT/bench_c1.json 2>/dev/null
-python bench.py --workload c3_sdxl_b4 --no-cpu-baseline --extras 0 --no-large-shape > $OUT/bench_c3.json 2>/dev/null
-python bench.py --workload c4_flux --no-cpu-baseline --extras 0 --no-large-shape > $OUT/bench_c4.json 2>/dev/null
-python bench.py --workload c5_wan --steps 100 --no-cpu-baseline --extras 0 > $OUT/bench_c5.json 2>/dev/null
-python bench.py --graph 0 --steps 100 --no-cpu-baseline --extras 0 --no-large-shape > $OUT/bench_c2_eager.json 2>/dev/null
-python bench.py --rng torch --no-cpu-baseline --extras 0 --no-large-shape > $OUT/bench_c2_torchrng.json 2>/dev/null
-python bench.py --rng torch --workload c5_wan --steps 100 --no-cpu-baseline --extras 0 --no-large-shape > $OUT/bench_c5_torchrng.json 2>/dev/null
+python bench.py --full > $OUT/bench_c2.json 2> $OUT/bench_c2.err
+python bench.py --full --workload c1_sd15 --no-cpu-baseline --extras 0 --no-large-shape > $OUT/bench_c1.json 2>/dev/null
+python bench.py --full --workload c3_sdxl_b4 --no-cpu-baseline --extras 0 --no-large-shape > $OUT/bench_c3.json 2>/dev/null
+python bench.py --full --workload c4_flux --no-cpu-baseline --extras 0 --no-large-shape > $OUT/bench_c4.json 2>/dev/null
+python bench.py --full --workload c5_wan --steps 100 --no-cpu-baseline --extras 0 > $OUT/bench_c5.json 2>/dev/null
+python bench.py --full --graph 0 --steps 100 --no-cpu-baseline --extras 0 --no-large-shape > $OUT/bench_c2_eager.json 2>/dev/null
+python bench.py --full --rng torch --no-cpu-baseline --extras 0 --no-large-shape > $OUT/bench_c2_torchrng.json 2>/dev/null
+python bench.py --full --rng torch --workload c5_wan --steps 100 --no-cpu-baseline --extras 0 --no-large-shape > $OUT/bench_c5_torchrng.json 2>/dev/null
 python scripts/host_vs_gpu.py c2_sdxl 1 > $OUT/host_vs_gpu_c2.log 2>&1
 python scripts/host_cost_probe.py > $OUT/host_cost_probe.log 2>&1
 for be in gloo nccl; do
   timeout 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29517 \
-    bench.py --gpus 2 --dist-backend $be --steps 100 --warmup 10 --repeats 0 > $OUT/bench_2rank_$be.log 2>&1
+    bench.py --full --gpus 2 --dist-backend $be --steps 100 --warmup 10 --repeats 0 > $OUT/bench_2rank_$be.log 2>&1
   echo "rc=$?" >> $OUT/bench_2rank_$be.log
 done
 for f in $OUT/bench_*.json; do python - "$f" <<'PY'

@@ -4,7 +4,7 @@ R=$PWD; O=$R/gpurun_out/r04_ab; mkdir -p $O
 for round in 1 2; do
   for tree in r03 r04; do
     if [ $tree = r03 ]; then cd $R/build/r03_tree; else cd $R; fi
-    timeout 250 python bench.py --no-cpu-baseline --no-large-shape --repeats 1 > $O/headline_$tree.json 2>/dev/null
+    timeout 250 python bench.py --full --no-cpu-baseline --no-large-shape --repeats 1 > $O/headline_$tree.json 2>/dev/null
     python - <<PY
 import json
 l = json.load(open("$O/headline_$tree.json"))
@@ -17,7 +17,7 @@ done | tee $O/ab_headline.log
 for tree in r03 r04; do
   if [ $tree = r03 ]; then cd $R/build/r03_tree; else cd $R; fi
   for wl in c3_sdxl_b4 c5_wan; do
-    timeout 200 python bench.py --workload $wl --steps 40 --warmup 5 --repeats 1 --extras 0 --no-large-shape --no-cpu-baseline > $O/headline_${tree}_$wl.json 2>/dev/null
+    timeout 200 python bench.py --full --workload $wl --steps 40 --warmup 5 --repeats 1 --extras 0 --no-large-shape --no-cpu-baseline > $O/headline_${tree}_$wl.json 2>/dev/null
     python -c "
 import json; l=json.load(open('$O/headline_${tree}_$wl.json')); print('$tree $wl value', round(l['value']))"
   done

@@ -3,7 +3,7 @@ timeout 600 python -m pytest tests -m gpu -q -x > $O/pytest5.log 2>&1; grep -n "
 for round in 1 2; do
   for lib in prev new; do
     if [ $lib = new ]; then unset LANPAINT_AMD_LIB; else export LANPAINT_AMD_LIB=$R/build/liblanpaint_hip_$lib.so; fi
-    timeout 200 python bench.py --no-cpu-baseline --no-large-shape --repeats 1 > $O/node_$lib.json 2>/dev/null
+    timeout 200 python bench.py --full --no-cpu-baseline --no-large-shape --repeats 1 > $O/node_$lib.json 2>/dev/null
     python -c "
 import json; l=json.load(open('$O/node_$lib.json')); print('round $round $lib value', round(l['value']), 'node_default_schedule', round(l['node_default_schedule']['value']), 'engine_defaults', round(l['engine_defaults']['value']))"
   done

@@ -2,12 +2,12 @@
 # round 4, final GPU session: the whole GPU suite, the default bench line, the other BASELINE workloads, the 8-rank rehearsals
 O=gpurun_out/r04_final; mkdir -p $O
 timeout 600 python -m pytest tests -m gpu -q --durations=8 > $O/pytest_gpu.log 2>&1; echo "pytest rc=$?" >> $O/pytest_gpu.log; tail -14 $O/pytest_gpu.log
-timeout 300 python bench.py > $O/bench_c2.json 2> $O/bench_c2.err; echo "bench rc=$?"
+timeout 300 python bench.py --full > $O/bench_c2.json 2> $O/bench_c2.err; echo "bench rc=$?"
 for wl in c1_sd15 c3_sdxl_b4 c4_flux c5_wan; do
-  timeout 200 python bench.py --workload $wl --steps 40 --warmup 5 --repeats 2 --extras 0 --no-large-shape --cpu-seconds 6 > $O/bench_$wl.json 2> $O/bench_$wl.err; echo "$wl rc=$?"
+  timeout 200 python bench.py --full --workload $wl --steps 40 --warmup 5 --repeats 2 --extras 0 --no-large-shape --cpu-seconds 6 > $O/bench_$wl.json 2> $O/bench_$wl.err; echo "$wl rc=$?"
 done
 for wl in c3_sdxl_b4 c5_wan; do
-  timeout 200 python bench.py --gpus 8 --dist-backend gloo --workload $wl --steps 20 --warmup 3 --repeats 1 --no-large-shape --extras 0 --cpu-seconds 4 > $O/bench_8rank_gloo_$wl.json 2> $O/bench_8rank_gloo_$wl.err; echo "8rank $wl rc=$?"
+  timeout 200 python bench.py --full --gpus 8 --dist-backend gloo --workload $wl --steps 20 --warmup 3 --repeats 1 --no-large-shape --extras 0 --cpu-seconds 4 > $O/bench_8rank_gloo_$wl.json 2> $O/bench_8rank_gloo_$wl.err; echo "8rank $wl rc=$?"
 done
 timeout 100 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -2
 python - <<'PY'

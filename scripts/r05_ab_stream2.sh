@@ -27,7 +27,7 @@ for round in 1 2; do
   for tree in r04 r05; do
     for wl in c5_wan c3_sdxl_b4; do
       inr $tree
-      timeout 200 python bench.py --workload $wl --steps 40 --warmup 5 --repeats 1 --extras 0 --no-large-shape --no-cpu-baseline > $O/line_${tree}_$wl.json 2>/dev/null
+      timeout 200 python bench.py --full --workload $wl --steps 40 --warmup 5 --repeats 1 --extras 0 --no-large-shape --no-cpu-baseline > $O/line_${tree}_$wl.json 2>/dev/null
       python -c "
 import json; l=json.load(open('$O/line_${tree}_$wl.json')); print('round $round $tree $wl value', round(l['value']), 'repeat', [round(v) for v in (l.get('repeats') or {}).get('values', [])], 'steady_launch_us', round(l['roofline']['mean_launch_us'],3))"
       cd $R

@@ -24,7 +24,7 @@ rm -rf /tmp/p_f_$$; cd $R
 for round in 1 2; do
   for tree in r04 r05; do
       inr $tree
-      timeout 200 python bench.py --workload c5_wan --rng torch --steps 40 --warmup 5 --repeats 1 --extras 0 --no-large-shape --no-cpu-baseline > $O/line_${tree}_c5_torch.json 2>/dev/null
+      timeout 200 python bench.py --full --workload c5_wan --rng torch --steps 40 --warmup 5 --repeats 1 --extras 0 --no-large-shape --no-cpu-baseline > $O/line_${tree}_c5_torch.json 2>/dev/null
       python -c "
 import json; l=json.load(open('$O/line_${tree}_c5_torch.json')); print('round $round $tree c5_wan rng=torch value', round(l['value']), 'repeat', [round(v) for v in (l.get('repeats') or {}).get('values', [])], 'parity', l['parity_check']['ok'])"
       cd $R

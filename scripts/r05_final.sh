@@ -4,14 +4,14 @@
 O=gpurun_out/r05_final; mkdir -p $O
 LANPAINT_AMD_LIB=$PWD/build/liblanpaint_hip_trace.so LANPAINT_AMD_TRACE_FILE=$PWD/$O/trace.txt timeout 700 python -m pytest tests -m gpu -q --durations=8 -p no:cacheprovider > $O/pytest_gpu_trace_build.log 2>&1; echo "pytest(trace build) rc=$?"; tail -4 $O/pytest_gpu_trace_build.log
 timeout 700 python -m pytest tests -m gpu -q -p no:cacheprovider > $O/pytest_gpu.log 2>&1; echo "pytest rc=$?" | tee -a $O/pytest_gpu.log; tail -4 $O/pytest_gpu.log
-timeout 400 python bench.py > $O/bench_c2.json 2> $O/bench_c2.err; echo "bench rc=$?"
-timeout 200 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_c2_driver_form.json 2> $O/bench_c2_driver_form.err; echo "driver-form rc=$?"
+timeout 400 python bench.py --full > $O/bench_c2.json 2> $O/bench_c2.err; echo "bench rc=$?"
+timeout 200 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/bench_c2_driver_form.json 2> $O/bench_c2_driver_form.err; echo "driver-form rc=$?"
 for wl in c1_sd15 c3_sdxl_b4 c4_flux c5_wan; do
-  timeout 250 python bench.py --workload $wl --steps 40 --warmup 5 --repeats 2 --extras 0 --no-large-shape --cpu-seconds 6 > $O/bench_$wl.json 2> $O/bench_$wl.err; echo "$wl rc=$?"
+  timeout 250 python bench.py --full --workload $wl --steps 40 --warmup 5 --repeats 2 --extras 0 --no-large-shape --cpu-seconds 6 > $O/bench_$wl.json 2> $O/bench_$wl.err; echo "$wl rc=$?"
 done
-timeout 250 python bench.py --workload c5_wan --rng torch --steps 40 --warmup 5 --repeats 2 --extras 0 --no-large-shape --no-cpu-baseline > $O/bench_c5_wan_torch.json 2>/dev/null; echo "c5 torch rc=$?"
+timeout 250 python bench.py --full --workload c5_wan --rng torch --steps 40 --warmup 5 --repeats 2 --extras 0 --no-large-shape --no-cpu-baseline > $O/bench_c5_wan_torch.json 2>/dev/null; echo "c5 torch rc=$?"
 for wl in c3_sdxl_b4 c5_wan; do
-  timeout 250 python bench.py --gpus 8 --dist-backend gloo --workload $wl --steps 20 --warmup 3 --repeats 1 --no-large-shape --extras 0 --cpu-seconds 4 --parity-sigmas 2 > $O/bench_8rank_gloo_$wl.json 2> $O/bench_8rank_gloo_$wl.err; echo "8rank $wl rc=$?"
+  timeout 250 python bench.py --full --gpus 8 --dist-backend gloo --workload $wl --steps 20 --warmup 3 --repeats 1 --no-large-shape --extras 0 --cpu-seconds 4 --parity-sigmas 2 > $O/bench_8rank_gloo_$wl.json 2> $O/bench_8rank_gloo_$wl.err; echo "8rank $wl rc=$?"
 done
 timeout 100 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -2
 python - <<'PY'

@@ -4,7 +4,7 @@
 set -u
 R=$PWD; O=$R/gpurun_out/r06_final; rm -rf $O; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp && cd $R
-run() { name=$1; shift; ( time timeout 600 python bench.py "$@" --sidecar $O/${name}_extras.json ) > $O/$name.out 2> $O/$name.err; echo "$name rc=$?"; tail -1 $O/$name.out > $O/$name.json; wc -c < $O/$name.json; grep real $O/$name.err; }
+run() { name=$1; shift; ( time timeout 600 python bench.py --full "$@" --sidecar $O/${name}_extras.json ) > $O/$name.out 2> $O/$name.err; echo "$name rc=$?"; tail -1 $O/$name.out > $O/$name.json; wc -c < $O/$name.json; grep real $O/$name.err; }
 run bench_c2_driver_form --gpus 1 --steps 20 --warmup 5
 run bench_c2
 run bench_c2_live_pmc --pmc --no-summary --steps 40

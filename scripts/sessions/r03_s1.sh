@@ -4,10 +4,10 @@ O=gpurun_out/r03_s1; mkdir -p $O
 timeout 120 build/graph_setparams 12 > $O/setparams.log 2>&1; echo "setparams rc=$?" >> $O/setparams.log
 timeout 900 python -m pytest tests -m gpu -x -q > $O/pytest_gpu.log 2>&1; echo "pytest rc=$?" >> $O/pytest_gpu.log
 tail -5 $O/pytest_gpu.log
-timeout 300 python bench.py --steps 200 > $O/bench_c2.json 2> $O/bench_c2.err
-LANPAINT_AMD_REPLACE_IN_GRAPH=0 timeout 300 python bench.py --steps 200 --no-large-shape --no-cpu-baseline > $O/bench_c2_round2layout.json 2> $O/bench_c2_round2layout.err
-timeout 300 python bench.py --steps 200 --no-large-shape --no-cpu-baseline --extras 0 > $O/bench_c2_b.json 2> $O/bench_c2_b.err
-timeout 600 python bench.py --gpus 2 --dist-backend gloo --steps 20 --warmup 5 --no-large-shape > $O/bench_2rank_selfspawn.json 2> $O/bench_2rank_selfspawn.err
+timeout 300 python bench.py --full --steps 200 > $O/bench_c2.json 2> $O/bench_c2.err
+LANPAINT_AMD_REPLACE_IN_GRAPH=0 timeout 300 python bench.py --full --steps 200 --no-large-shape --no-cpu-baseline > $O/bench_c2_round2layout.json 2> $O/bench_c2_round2layout.err
+timeout 300 python bench.py --full --steps 200 --no-large-shape --no-cpu-baseline --extras 0 > $O/bench_c2_b.json 2> $O/bench_c2_b.err
+timeout 600 python bench.py --full --gpus 2 --dist-backend gloo --steps 20 --warmup 5 --no-large-shape > $O/bench_2rank_selfspawn.json 2> $O/bench_2rank_selfspawn.err
 python - <<'PY'
 import json,glob
 for f in sorted(glob.glob('gpurun_out/r03_s1/bench*.json')):

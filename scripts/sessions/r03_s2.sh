@@ -7,7 +7,7 @@ grep -E "passed|failed|rc=" $O/pytest_gpu.log | tail -3
 rm -f $O/trace.txt
 LANPAINT_AMD_LIB=build/liblanpaint_hip_trace.so LANPAINT_AMD_TRACE_FILE=$PWD/$O/trace.txt timeout 900 python -m pytest tests -m gpu -q > $O/pytest_gpu_trace.log 2>&1
 echo "trace pytest rc=$? lines=$(sort -u $O/trace.txt | wc -l)"
-timeout 400 python bench.py > $O/bench_c2.json 2> $O/bench_c2.err; echo "bench rc=$?"
+timeout 400 python bench.py --full > $O/bench_c2.json 2> $O/bench_c2.err; echo "bench rc=$?"
 for knob in "NONE=0" "ROC_SYSTEM_SCOPE_SIGNAL=0" "DEBUG_CLR_MAX_BATCH_SIZE=4096" "DEBUG_CLR_MAX_BATCH_SIZE=1" "DEBUG_CLR_BATCH_CPU_SYNC_SIZE=4096" \
     "DEBUG_HIP_BLOCK_SYNC=0" "AMD_DIRECT_DISPATCH=0" "GPU_MAX_HW_QUEUES=1" "DEBUG_HIP_FORCE_GRAPH_QUEUES=1" "DEBUG_HIP_DYNAMIC_QUEUES=0" \
     "ROC_CPU_WAIT_FOR_SIGNAL=0" "ROC_USE_FGS_KERNARG=0" "ROC_SKIP_KERNEL_ARG_COPY=1" "DEBUG_HIP_KERNARG_COPY_OPT=0" "GPU_FORCE_QUEUE_PROFILING=1" \

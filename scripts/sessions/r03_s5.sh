@@ -14,7 +14,7 @@ cat $O/microbench_bf16.log
 LANPAINT_AMD_GRAPH=1 timeout 900 python -m pytest tests -m gpu -q > $O/pytest_gpu_graph1.log 2>&1; echo "graph=1 rc=$?"; grep -E "passed|failed" $O/pytest_gpu_graph1.log | tail -2
 LANPAINT_AMD_GRAPH=0 timeout 900 python -m pytest tests -m gpu -q > $O/pytest_gpu_graph0.log 2>&1; echo "graph=0 rc=$?"; grep -E "passed|failed" $O/pytest_gpu_graph0.log | tail -2
 timeout 600 bash scripts/gpu_profile_mfma.sh > $O/mfma.log 2>&1; echo "mfma rc=$?"
-timeout 300 python bench.py --workload c5_wan --no-large-shape --no-cpu-baseline > $O/bench_c5.json 2> $O/bench_c5.err
+timeout 300 python bench.py --full --workload c5_wan --no-large-shape --no-cpu-baseline > $O/bench_c5.json 2> $O/bench_c5.err
 python - <<'PY'
 import json
 d=json.load(open('gpurun_out/r03_s5/bench_c5.json'))

@@ -4,7 +4,7 @@ O=gpurun_out/r03_s7; mkdir -p $O
 timeout 900 python -m pytest tests -m gpu -x -q > $O/pytest_gpu.log 2>&1; echo "pytest rc=$?" >> $O/pytest_gpu.log
 grep -E "passed|failed|rc=" $O/pytest_gpu.log | tail -3
 for i in 1 2; do
-timeout 300 python bench.py --no-large-shape --no-cpu-baseline > $O/bench_c2_$i.json 2> $O/bench_c2_$i.err
+timeout 300 python bench.py --full --no-large-shape --no-cpu-baseline > $O/bench_c2_$i.json 2> $O/bench_c2_$i.err
 done
 timeout 120 python scripts/prof_node.py > $O/prof_node.log 2>&1
 python - <<'PY'

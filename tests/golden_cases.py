@@ -288,3 +288,72 @@ def build_schedule(name):
         mask[..., h // 4: 3 * h // 4, w // 4: 3 * w // 4] = 0.0
     return dict(name=name, shape=shape, flow=flow, sigmas=sig, x=x, y=y, noise=noise, mask=mask,
                 hyper=hyper, model="linear_tuple", model_options=c.get("model_options"))
+
+
+# ---------------------------------------------------------------- tests/golden/ref_random_calls.npz, ref_reshape_mask.npz
+# Random engine calls and random reshape_mask layouts answered by the reference (tests/golden/make_reference_calls.py writes
+# them; tests/test_oracle_vs_reference_live.py replays them against the oracle).
+class FormSampling:
+    def __init__(self, flow):
+        self.flow, self.noise_scale = flow, 1.0
+
+    def noise_scaling(self, sigma, noise, latent_image, max_denoise=False):
+        return sigma * noise + (1.0 - sigma) * latent_image if self.flow else latent_image + noise * sigma
+
+
+class FormModel:
+    """x -> heads in one of the forms lanpaint.py:34-43 accepts; arithmetic that works on numpy arrays and torch tensors alike."""
+
+    def __init__(self, flow, form):
+        self.inner_model, self.model_sampling, self.form, self.calls = self, FormSampling(flow), form, 0
+
+    def __call__(self, x, t, model_options=None, seed=None):
+        self.calls += 1
+        tb = t.reshape((-1,) + (1,) * (x.ndim - 1))
+        a, b = x * 0.9 - 0.05 * tb, x * 0.8 + 0.1
+        return {"tuple": (a, b), "list1": [a], "single": a, "triple": (a, b, b)}[self.form]
+
+
+def random_masks(version):
+    """The 400 (binary fp32 mask, latent shape, video flag) draws of the reshape_mask comparison, from the version's seed:
+    [H, W], [B, H, W], [F, H, W] / [F, 1, H, W] video masks and the audio forms [F] and [1, 1, F, 1]."""
+    rng = np.random.default_rng(7 if version == "0.6.0" else 8)
+    for _ in range(400):
+        video = bool(rng.integers(0, 2))
+        five_d = video or bool(rng.integers(0, 3) == 0)
+        b, c = int(rng.integers(1, 3)), int(rng.integers(1, 5))
+        h, w = int(rng.integers(2, 40)), int(rng.integers(2, 40))
+        H, W = int(rng.integers(2, 150)), int(rng.integers(2, 150))
+        if video:
+            f, F = int(rng.integers(1, 8)), int(rng.integers(1, 30))
+            out_shape = (b, c, f, h, w)
+            form = int(rng.integers(0, 3))
+            m = rng.random((F, H, W)) if form == 0 else (rng.random((F, 1, H, W)) if form == 1 else rng.random((H, W)))
+        elif five_d:
+            f = int(rng.integers(1, 6))
+            out_shape = (b, c, f, h, w)
+            m = rng.random((H, W)) if rng.integers(0, 2) else rng.random((int(rng.integers(1, 3)), H, W))
+        else:
+            out_shape = (b, c, h, w)
+            form = int(rng.integers(0, 4))
+            if form == 0:
+                m = rng.random((H, W))
+            elif form == 1:
+                m = rng.random((int(rng.integers(1, 3)), H, W))
+            elif form == 2:
+                m = rng.random((int(rng.integers(2, 200)),))                          # audio [F] at video frame rate
+            else:
+                m = rng.random((1, 1, int(rng.integers(2, 200)), 1))                  # ... as SetLatentNoiseMask reshapes it
+        yield (m > 0.5).astype(np.float32), out_shape, video
+
+
+def array_digest(a):
+    """SHA-256 of an array's shape and fp32 bytes: equal digests = bit-equal arrays."""
+    import hashlib
+    a = np.ascontiguousarray(np.asarray(a, dtype=np.float32))
+    return hashlib.sha256(repr(a.shape).encode() + a.tobytes()).hexdigest()
+
+
+def effective_steps_grid():
+    """(n, frac, MinStepFrac) of the dense grid the inner-step rule (nodes.py:134-144) is compared on."""
+    return [(n, float(frac), mf) for n in range(0, 12) for frac in np.linspace(0.0, 1.0, 41) for mf in (0.0, 0.05, 0.3, 1.0)]

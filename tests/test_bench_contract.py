@@ -243,3 +243,40 @@ def test_every_committed_round6_line_is_small_and_complete():
     assert default["summary"]["philox_bits_it_s"] > default["value"] and 0.9 < default["summary"]["value_over_launch_floor"] <= 1.05
     live = json.load(open(os.path.join(ROOT, "profiles", "r06_bench_c2_live_pmc.json")))["roofline"]
     assert "live" in live["traffic_source"] and abs(live["traffic"] - 2173952) < 0.03 * 2173952       # within 3 % of the committed passes
+
+
+def test_plain_run_measures_only_the_headline():
+    """Without --full a run sets up, warms up, times --steps steps and prints the line; what else the benchmark measures or
+    checks is asked for with --full, and the legs that only exist there refuse to run without it."""
+    import pytest
+    import bench
+    a = bench.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert not a.full and a.dump_outputs is None and a.steps == 7 and a.warmup == 2
+    f = bench.parse_args(["--full", "--dump-outputs", "d"])
+    assert f.full and f.dump_outputs == "d" and f.repeats == 5 and not f.no_cpu_baseline and not f.no_parity_check
+    assert bench.parse_args(["--full", "--pmc", "--extras", "1"]).pmc
+    for argv in (["--pmc"], ["--extras", "1"]):
+        with pytest.raises(SystemExit):
+            bench.parse_args(argv)
+    src = open(os.path.join(ROOT, "bench.py")).read()
+    for leg in ("measure_steady_launch(", "check_job(", "cpu_baseline(", "summary_scalars(", "write_sidecar("):
+        i = src.index(leg)
+        assert "args.full" in src[src.rindex("\n    if ", 0, i):i] or "if args.full" in src[src.rindex("\n", 0, i):i], leg
+
+
+def test_dump_outputs_writes_fp32_within_budget(tmp_path):
+    """--dump-outputs: fp32 .npy files; past the 64 MB budget a seeded sample at the same positions every time."""
+    import numpy as np
+    import torch
+    from benchkit import line as bl
+    x = torch.arange(24, dtype=torch.float64).reshape(2, 3, 4)
+    bl.dump_outputs(str(tmp_path / "a"), {"final_latent": x})
+    got = np.load(tmp_path / "a" / "final_latent.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, x.numpy().astype(np.float32))
+    big = torch.arange(bl.MAX_DUMP_BYTES // 4 + 1000, dtype=torch.float32)
+    for d in ("b", "c"):
+        bl.dump_outputs(str(tmp_path / d), {"final_latent": big})
+    s1, s2 = np.load(tmp_path / "b" / "final_latent.npy"), np.load(tmp_path / "c" / "final_latent.npy")
+    assert s1.nbytes <= bl.MAX_DUMP_BYTES and np.array_equal(s1, s2) and np.all(np.diff(s1) >= 0)   # (sorted positions)
+    bl.dump_outputs(str(tmp_path / "r"), {"final_latent_rank1": big}, world=2)
+    assert np.load(tmp_path / "r" / "final_latent_rank1.npy").nbytes <= bl.MAX_DUMP_BYTES // 2

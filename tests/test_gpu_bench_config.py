@@ -118,7 +118,7 @@ def test_bench_line_carries_the_parity_check():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     import tempfile
     with tempfile.TemporaryDirectory() as tmp:
-        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--repeats", "0",
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "3", "--warmup", "1", "--repeats", "0",
                "--prewarm-seconds", "0.05", "--no-cpu-baseline", "--no-summary", "--sidecar", os.path.join(tmp, "x.json")]
         p = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=500)
         assert p.returncode == 0, p.stderr[-3000:]
@@ -135,6 +135,37 @@ def test_bench_line_carries_the_parity_check():
     assert cfg["captured_calls"] == 1 and "drop-in" in cfg["engine"]
     assert "RNG" not in line["roofline"]["kernel"] and ", 1, false, 0>" in line["roofline"]["kernel"]      # the torch-stream instantiation
     assert side["parity_check"]["draws"] == 270 and side["roofline"]["launches_timed"] == 120 and abs(side["line"]["value"] - line["value"]) <= 1e-5 * line["value"]
+
+
+@pytest.mark.timeout(600)
+def test_plain_bench_run_times_exactly_its_steps_and_dumps_the_same_outputs_as_full():
+    """`python bench.py --steps K --warmup W --dump-outputs DIR`: only the headline (no parity check, roofline, cpu_baseline,
+    summary or side-car), ms_per_step = the K timed steps' time / K, and the last timed step's final latent in DIR --
+    bit-identical to what a --full run of the same arguments dumps, although that run consumed the generator before it."""
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
+    import tempfile
+    with tempfile.TemporaryDirectory() as tmp:
+        lines, dumps = [], []
+        for extra in ((), ("--full", "--repeats", "0", "--no-cpu-baseline", "--no-summary", "--parity-sigmas", "2",
+                           "--sidecar", os.path.join(tmp, "x.json"))):
+            out = os.path.join(tmp, "full" if extra else "plain")
+            cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--dump-outputs", out, *extra]
+            p = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=280)
+            assert p.returncode == 0, p.stderr[-3000:]
+            lines.append(json.loads(p.stdout.rstrip().splitlines()[-1]))
+            assert sorted(os.listdir(out)) == ["final_latent.npy"]
+            dumps.append(np.load(os.path.join(out, "final_latent.npy")))
+    plain, full = lines
+    for k in ("parity_check", "roofline", "cpu_baseline", "summary", "extras_file"):
+        assert plain[k] is None, k
+    assert full["parity_check"]["ok"] and full["roofline"]["frac"] > 0
+    assert plain["steps"] == 3 and plain["warmup"] == 1 and plain["metric"] == full["metric"] and plain["unit"] == full["unit"]
+    assert plain["higher_is_better"] is True and plain["dtype"] == "f32" and plain["value"] > 0 and plain["ms_per_step"] > 0
+    # value = think iterations / the timed steps' time: exactly 3 steps' worth of iterations were timed
+    assert abs(plain["value"] * plain["ms_per_step"] * 1e-3 * 3 - 3 * plain["config"]["iterations_per_step"]) < 1e-3 * 450
+    a, b = dumps
+    assert a.dtype == np.float32 and a.shape == (1, 4, 128, 128) and np.isfinite(a).all()
+    assert np.array_equal(a, b)
 
 
 @pytest.mark.parametrize("workload,max_sigmas", [("c2_sdxl", None), ("c5_wan", 2)])

@@ -15,7 +15,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def _cmd(backend, gpus=2, extra=(), sidecar=None):
-    return [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(gpus), "--dist-backend", backend, "--steps", "3",
+    return [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", str(gpus), "--dist-backend", backend, "--steps", "3",
             "--warmup", "1", "--repeats", "1", "--prewarm-seconds", "0.05", "--cpu-seconds", "1.0", "--no-large-shape",
             "--parity-sigmas", "4", *(("--sidecar", sidecar) if sidecar else ()), *extra]
             # (every rank checks its own replica: keep the numpy passes short here)
@@ -103,7 +103,7 @@ def test_bench_two_ranks_under_torch_distributed_run():
         port = s.getsockname()[1]
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dist-backend", "gloo", "--steps", "3",
+           "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--dist-backend", "gloo", "--steps", "3",
            "--warmup", "1", "--repeats", "0", "--prewarm-seconds", "0.05", "--no-cpu-baseline", "--no-large-shape",
            "--parity-sigmas", "3"]
     p = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=800)
