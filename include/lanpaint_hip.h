@@ -43,7 +43,7 @@
 extern "C" {
 #endif
 
-#define LP_ABI_VERSION 20
+#define LP_ABI_VERSION 21
 
 /* The library is built with -fvisibility=hidden: the entry points declared LP_API below are its ONLY dynamic symbols (the
  * dispatch functions, kernel handles and device stubs of the C++ side stay internal; tests/test_cabi_exports.py checks
@@ -649,6 +649,71 @@ typedef struct lp_blend_desc {
     int32_t reserved0;
 } lp_blend_desc;
 LP_API int lp_mask_blend(const lp_blend_desc* desc, void* stream);
+
+/* ---- video mask editor (reference src/LanPaint/videomask.py, nodes.py:890-995) ----------------------------
+ * The reference's LanPaint_VideoMaskEditor builds one mask per video frame on the host: binarise the painted keyframes, a
+ * signed distance field per keyframe (scipy's EDT), a translation-compensated SDF blend + sigmoid for the frames between two
+ * keyframes, then Pillow's 8-bit BILINEAR up to the video size.  Three jobs here; the host (lanpaint_amd/videomask.py)
+ * builds the per-frame plan and the resize coefficients, the device does every per-pixel pass.  Sides are 1..16384
+ * (int32 squared distances stay exact); larger sides are LP_E_INVALID.                                                   */
+#define LP_VMASK_MAX_SIDE 16384
+#define LP_VMASK_D2_NONE  (-1)    /* d2 of a pixel whose plane has no pixel of the wanted kind (empty / full keyframe) */
+#define LP_VMASK_ZERO     0       /* lp_vmask_frame.kind: all-zero frame (outside the keyframe window)                */
+#define LP_VMASK_KEY      1       /*   a keyframe: its original soft values                                            */
+#define LP_VMASK_INNER    2       /*   between keyframes key_lo < t < key_hi: the SDF morph                            */
+#define LP_VMASK_OUT_U8   1       /* lp_vmask_morph_desc.flags: write uint8 codes trunc(m * 255.0f) instead of fp32    */
+
+/* EDT + SDF + centroid of n_keys keyframes at once (videomask.py:105-170 _edt_2d / _signed_distance / _centroid).
+ *   keys  [n_keys, h, w] fp32; foreground = (v >= 0.5)
+ *   d2    out [n_keys, 2, h, w] int32: plane 0 = exact squared Euclidean distance to the nearest foreground pixel, plane 1 to
+ *         the nearest background pixel; LP_VMASK_D2_NONE where the keyframe has none
+ *   sdf   out [n_keys, h, w] fp64: sqrt(d2_bg) - sqrt(d2_fg); -max(h, w)/2 for an empty keyframe, +max(h, w)/2 for a full one
+ *   csum  out [n_keys, 3] uint64: foreground count, sum of its row indices, sum of its column indices (exact; the centroid is
+ *         (sum_y / n, sum_x / n)).  Zeroed by this call.                                                                */
+typedef struct lp_vmask_edt_desc {
+    int32_t n_keys, height, width, reserved0;
+    const float* keys;
+    int32_t*     d2;
+    double*      sdf;
+    uint64_t*    csum;
+} lp_vmask_edt_desc;
+LP_API int lp_vmask_edt(const lp_vmask_edt_desc* desc, void* stream);
+
+/* One output frame of lp_vmask_morph (videomask.py:173-240 interpolate_masks).  INNER: with S(f, dy, dx)(y, x) = f(y - dy,
+ * x - dx), 0 outside the frame,  d = omw * S(sdf[key_lo], sy1, sx1) + wf * S(sdf[key_hi], -sy2, -sx2)  in fp64, products and
+ * sum rounded separately, then float(1 / (1 + exp(-clip(d, -50, 50)))).  KEY: keys[key_lo].  key_* index the key stack. */
+typedef struct lp_vmask_frame {
+    int32_t kind, key_lo, key_hi, sx1, sy1, sx2, sy2, reserved0;
+    double  wf, omw;
+} lp_vmask_frame;
+
+/* The morph over [n_frames, h, w] in one launch (videomask.py:173-240).  frames: device [n_frames]; sdf may be NULL when no
+ * frame is INNER.  out: fp32, or uint8 codes with LP_VMASK_OUT_U8 (what resize_masks quantises, videomask.py:58-65).     */
+typedef struct lp_vmask_morph_desc {
+    int32_t n_frames, n_keys, height, width;
+    uint32_t flags;
+    int32_t  reserved0;
+    const lp_vmask_frame* frames;
+    const float*  keys;
+    const double* sdf;
+    void*         out;
+} lp_vmask_morph_desc;
+LP_API int lp_vmask_morph(const lp_vmask_morph_desc* desc, void* stream);
+
+/* Pillow's 8-bit BILINEAR resize of uint8 frames (resize_masks, videomask.py:58-65: Image.resize(size, BILINEAR)), output
+ * fp32 code / 255.  Horizontal then vertical pass, uint8 in between; per axis the caller's tables from Pillow's
+ * precompute_coeffs: bounds [out, 2] = (first source index, tap count), weights [out, ksize] 22-bit fixed point.  An axis
+ * whose size does not change takes the identity table (tap weights 1, 0), which equals skipping the pass.               */
+typedef struct lp_vmask_resize_desc {
+    int32_t n_frames, in_h, in_w, out_h, out_w, ksize_x, ksize_y, reserved0;
+    const uint8_t* src;          /* [n_frames, in_h, in_w]   */
+    const int32_t* bounds_x;
+    const int32_t* weights_x;
+    const int32_t* bounds_y;
+    const int32_t* weights_y;
+    float*         dst;          /* [n_frames, out_h, out_w] */
+} lp_vmask_resize_desc;
+LP_API int lp_vmask_resize(const lp_vmask_resize_desc* desc, void* stream);
 
 #ifdef __cplusplus
 }

@@ -13,7 +13,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_NAME = "liblanpaint_hip.so"
 LIB_PATH = os.path.join(_HERE, LIB_NAME)
-ABI_VERSION = 20
+ABI_VERSION = 21
 
 # --- constants mirrored from include/lanpaint_hip.h -------------------------------
 LP_OK, LP_E_INVALID, LP_E_UNSUPPORTED, LP_E_LAUNCH, LP_E_ALIGN = 0, -1, -2, -3, -4
@@ -135,6 +135,33 @@ class LpBlendDesc(C.Structure):
                 ("smooth_out", C.c_void_p), ("nn_rule", C.c_int32), ("reserved0", C.c_int32)]
 
 
+LP_VMASK_MAX_SIDE, LP_VMASK_D2_NONE = 16384, -1
+LP_VMASK_ZERO, LP_VMASK_KEY, LP_VMASK_INNER, LP_VMASK_OUT_U8 = 0, 1, 2, 1
+
+
+class LpVmaskEdtDesc(C.Structure):
+    _fields_ = [("n_keys", C.c_int32), ("height", C.c_int32), ("width", C.c_int32), ("reserved0", C.c_int32),
+                ("keys", C.c_void_p), ("d2", C.c_void_p), ("sdf", C.c_void_p), ("csum", C.c_void_p)]
+
+
+class LpVmaskFrame(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("key_lo", C.c_int32), ("key_hi", C.c_int32), ("sx1", C.c_int32), ("sy1", C.c_int32),
+                ("sx2", C.c_int32), ("sy2", C.c_int32), ("reserved0", C.c_int32), ("wf", C.c_double), ("omw", C.c_double)]
+
+
+class LpVmaskMorphDesc(C.Structure):
+    _fields_ = [("n_frames", C.c_int32), ("n_keys", C.c_int32), ("height", C.c_int32), ("width", C.c_int32),
+                ("flags", C.c_uint32), ("reserved0", C.c_int32), ("frames", C.c_void_p), ("keys", C.c_void_p),
+                ("sdf", C.c_void_p), ("out", C.c_void_p)]
+
+
+class LpVmaskResizeDesc(C.Structure):
+    _fields_ = [("n_frames", C.c_int32), ("in_h", C.c_int32), ("in_w", C.c_int32), ("out_h", C.c_int32),
+                ("out_w", C.c_int32), ("ksize_x", C.c_int32), ("ksize_y", C.c_int32), ("reserved0", C.c_int32),
+                ("src", C.c_void_p), ("bounds_x", C.c_void_p), ("weights_x", C.c_void_p), ("bounds_y", C.c_void_p),
+                ("weights_y", C.c_void_p), ("dst", C.c_void_p)]
+
+
 EXPORTS = {
     # name: (restype, argtypes)
     "lp_abi_version": (C.c_int, []),
@@ -169,6 +196,9 @@ EXPORTS = {
     "lp_pack_mask": (C.c_int, [C.c_void_p, C.c_int64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "lp_pack_mask_latent": (C.c_int, [C.c_void_p, C.c_int64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "lp_reshape_mask": (C.c_int, [C.c_void_p] + [C.c_int32] * 5 + [C.c_void_p] + [C.c_int32] * 7 + [C.c_void_p]),
+    "lp_vmask_edt": (C.c_int, [C.POINTER(LpVmaskEdtDesc), C.c_void_p]),
+    "lp_vmask_morph": (C.c_int, [C.POINTER(LpVmaskMorphDesc), C.c_void_p]),
+    "lp_vmask_resize": (C.c_int, [C.POINTER(LpVmaskResizeDesc), C.c_void_p]),
 }
 
 

@@ -31,6 +31,9 @@ int wmse_dispatch(const float* a, const float* b, const float* mask, const float
 int torch_normal_dispatch(float* out, int64_t n, uint64_t seed, uint64_t offset, uint32_t bg, hipStream_t stream);
 int pack_mask_dispatch(const float* mask, int64_t n_el, uint32_t flags, void* bits, int32_t* nonbinary, float* latent_out,
                        hipStream_t stream);
+int vmask_edt_dispatch(const lp_vmask_edt_desc* d, hipStream_t stream);
+int vmask_morph_dispatch(const lp_vmask_morph_desc* d, hipStream_t stream);
+int vmask_resize_dispatch(const lp_vmask_resize_desc* d, hipStream_t stream);
 int reshape_mask_dispatch(const float* src, int sb, int sc, int sf, int sh, int sw, float* dst, int db, int dc, int df,
                           int dh, int dw, int taps, int flags, hipStream_t stream);
 }  // namespace lp
@@ -83,6 +86,12 @@ int lp_step_timed(const lp_step_desc* desc, void* stream, void* timer) {
 int lp_timer_elapsed_ns(void* timer, double* ns) { return lp::timer_elapsed_ns(timer, ns); }
 
 int lp_mask_blend(const lp_blend_desc* desc, void* stream) { return lp::blend_dispatch(desc, as_stream(stream)); }
+
+int lp_vmask_edt(const lp_vmask_edt_desc* desc, void* stream) { return lp::vmask_edt_dispatch(desc, as_stream(stream)); }
+
+int lp_vmask_morph(const lp_vmask_morph_desc* desc, void* stream) { return lp::vmask_morph_dispatch(desc, as_stream(stream)); }
+
+int lp_vmask_resize(const lp_vmask_resize_desc* desc, void* stream) { return lp::vmask_resize_dispatch(desc, as_stream(stream)); }
 
 
 int lp_finalize(const lp_final_desc* desc, void* stream) { return lp::finalize_dispatch(desc, as_stream(stream)); }
