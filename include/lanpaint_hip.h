@@ -43,7 +43,7 @@
 extern "C" {
 #endif
 
-#define LP_ABI_VERSION 21
+#define LP_ABI_VERSION 22
 
 /* The library is built with -fvisibility=hidden: the entry points declared LP_API below are its ONLY dynamic symbols (the
  * dispatch functions, kernel handles and device stubs of the C++ side stay internal; tests/test_cabi_exports.py checks
@@ -714,6 +714,39 @@ typedef struct lp_vmask_resize_desc {
     float*         dst;          /* [n_frames, out_h, out_w] */
 } lp_vmask_resize_desc;
 LP_API int lp_vmask_resize(const lp_vmask_resize_desc* desc, void* stream);
+
+/* ---- AV decode: audio merge (reference nodes.py:1091-1136 merge_audio_with_mask, run by LanPaint_AVDecode,
+ * nodes.py:1139-1227) ----------------------------------------------------------------------------------------------------
+ * From the point where both waveforms are at the original sample rate (lanpaint_amd/audio.py resamples before the call):
+ *   w[i]  = mask[i]                          when mask_len == n (a per-sample mask, soft values allowed)
+ *         = mask[src(i)]                     otherwise; src = ATen's nearest-exact 1-D index, rule nn_rule (LP_NN_ATEN_*)
+ *   w'[i] = (1/cf) * sum_{k=0}^{cf-1} w[clamp(i - cf/2 + k, 0, n-1)]      when cf > 1 (integer cf/2; any cf >= 1 vs n);
+ *           the reference's replicate pad (cf/2, cf-1-cf/2) + conv1d(ones/cf).  Evaluated as float(S * double(1.0f / cf)):
+ *           S the exact window sum in fp64, times the reference's fp32 kernel tap, rounded once -- for a 0/1 mask
+ *           w' = fl(count * fl(1/cf)).  cf <= 1: w' = w.
+ *   out[b][c][i] = o * (1 - w') + p * w'     fp32, every product and the sum rounded on its own (no FMA), like torch's ops
+ * o = orig[b * orig_sb + c * orig_sc + i], p = inpainted[b * inp_sb + c * inp_sc + i] (element strides; 0 = broadcast: the
+ * reference's mono expand and batch broadcasting; orig[:, :Ci] is orig_sc with channels = Ci).  Samples are contiguous in
+ * every row; out is [batch, channels, n] contiguous.  The window sum is a difference of the prefix function of the
+ * piecewise-constant w, from a (mask_len + 1)-entry fp64 table the call builds in `workspace` (first launch, one workgroup)
+ * -- O(1) per sample whatever cf is; one launch then does the weight, the crossfade and the lerp, 4 samples per lane.
+ * workspace: LP_AUDIO_WS_BYTES(mask_len) bytes, 8-byte aligned, needed when cf > 1 (NULL allowed otherwise).           */
+#define LP_AUDIO_WS_BYTES(mask_len) (12 * ((int64_t)(mask_len) + 1))
+typedef struct lp_audio_desc {
+    int32_t n;                    /* samples per row, >= 1                                           */
+    int32_t mask_len;             /* Fm >= 1: mask values at frame rate (or n: per sample)           */
+    int32_t batch, channels;      /* output rows                                                     */
+    int32_t cf;                   /* crossfade window in samples; 0 or 1 = none                      */
+    int32_t nn_rule;              /* LP_NN_ATEN_* rule of the mask's up-sampling                    */
+    int64_t orig_sb, orig_sc;     /* element strides of orig per batch / channel (>= 0)              */
+    int64_t inp_sb, inp_sc;       /* element strides of inpainted per batch / channel (>= 0)         */
+    const float* mask;            /* [mask_len]                                                      */
+    const float* orig;
+    const float* inpainted;
+    float*       out;             /* [batch, channels, n]                                            */
+    void*        workspace;
+} lp_audio_desc;
+LP_API int lp_audio_merge(const lp_audio_desc* desc, void* stream);
 
 #ifdef __cplusplus
 }

@@ -13,7 +13,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_NAME = "liblanpaint_hip.so"
 LIB_PATH = os.path.join(_HERE, LIB_NAME)
-ABI_VERSION = 21
+ABI_VERSION = 22
 
 # --- constants mirrored from include/lanpaint_hip.h -------------------------------
 LP_OK, LP_E_INVALID, LP_E_UNSUPPORTED, LP_E_LAUNCH, LP_E_ALIGN = 0, -1, -2, -3, -4
@@ -162,6 +162,18 @@ class LpVmaskResizeDesc(C.Structure):
                 ("weights_y", C.c_void_p), ("dst", C.c_void_p)]
 
 
+class LpAudioDesc(C.Structure):
+    _fields_ = [("n", C.c_int32), ("mask_len", C.c_int32), ("batch", C.c_int32), ("channels", C.c_int32), ("cf", C.c_int32),
+                ("nn_rule", C.c_int32), ("orig_sb", C.c_int64), ("orig_sc", C.c_int64), ("inp_sb", C.c_int64),
+                ("inp_sc", C.c_int64), ("mask", C.c_void_p), ("orig", C.c_void_p), ("inpainted", C.c_void_p),
+                ("out", C.c_void_p), ("workspace", C.c_void_p)]
+
+
+def lp_audio_ws_bytes(mask_len):
+    """LP_AUDIO_WS_BYTES of include/lanpaint_hip.h."""
+    return 12 * (int(mask_len) + 1)
+
+
 EXPORTS = {
     # name: (restype, argtypes)
     "lp_abi_version": (C.c_int, []),
@@ -199,6 +211,7 @@ EXPORTS = {
     "lp_vmask_edt": (C.c_int, [C.POINTER(LpVmaskEdtDesc), C.c_void_p]),
     "lp_vmask_morph": (C.c_int, [C.POINTER(LpVmaskMorphDesc), C.c_void_p]),
     "lp_vmask_resize": (C.c_int, [C.POINTER(LpVmaskResizeDesc), C.c_void_p]),
+    "lp_audio_merge": (C.c_int, [C.POINTER(LpAudioDesc), C.c_void_p]),
 }
 
 

@@ -34,6 +34,7 @@ int pack_mask_dispatch(const float* mask, int64_t n_el, uint32_t flags, void* bi
 int vmask_edt_dispatch(const lp_vmask_edt_desc* d, hipStream_t stream);
 int vmask_morph_dispatch(const lp_vmask_morph_desc* d, hipStream_t stream);
 int vmask_resize_dispatch(const lp_vmask_resize_desc* d, hipStream_t stream);
+int audio_merge_dispatch(const lp_audio_desc* d, hipStream_t stream);
 int reshape_mask_dispatch(const float* src, int sb, int sc, int sf, int sh, int sw, float* dst, int db, int dc, int df,
                           int dh, int dw, int taps, int flags, hipStream_t stream);
 }  // namespace lp
@@ -92,6 +93,8 @@ int lp_vmask_edt(const lp_vmask_edt_desc* desc, void* stream) { return lp::vmask
 int lp_vmask_morph(const lp_vmask_morph_desc* desc, void* stream) { return lp::vmask_morph_dispatch(desc, as_stream(stream)); }
 
 int lp_vmask_resize(const lp_vmask_resize_desc* desc, void* stream) { return lp::vmask_resize_dispatch(desc, as_stream(stream)); }
+
+int lp_audio_merge(const lp_audio_desc* desc, void* stream) { return lp::audio_merge_dispatch(desc, as_stream(stream)); }
 
 
 int lp_finalize(const lp_final_desc* desc, void* stream) { return lp::finalize_dispatch(desc, as_stream(stream)); }
