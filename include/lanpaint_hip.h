@@ -43,7 +43,7 @@
 extern "C" {
 #endif
 
-#define LP_ABI_VERSION 22
+#define LP_ABI_VERSION 23
 
 /* The library is built with -fvisibility=hidden: the entry points declared LP_API below are its ONLY dynamic symbols (the
  * dispatch functions, kernel handles and device stubs of the C++ side stay internal; tests/test_cabi_exports.py checks
@@ -438,11 +438,9 @@ typedef struct lp_graph_binding {
     void*    func;                      /* its kernel                                                              */
     uint32_t grid[3], block[3];
     uint32_t shared_bytes;
-    uint32_t fingerprint;               /* of everything in the captured descriptor that selected this kernel instantiation
-                                           and its grid (phases, the flag bits the dispatcher reads, replace_kind, rng_kind,
-                                           sizes): a later argument rewrite with a descriptor that would have dispatched to
-                                           ANOTHER kernel is refused (LP_E_INVALID) instead of running the captured one on
-                                           arguments it does not understand                                              */
+    uint32_t reserved0;                 /* 0 (was a hash of the captured descriptor): a rewrite is checked against the kernel,
+                                           grid and block above instead -- the one the replace descriptor dispatches to must
+                                           be exactly this launch, or the rewrite is refused (LP_E_INVALID)              */
 } lp_graph_binding;
 LP_API int lp_graph_bind_replace(void* graph, const lp_step_desc* captured_replace, lp_graph_binding* out);
 LP_API int lp_graph_clone_tail(void* graph, void** tail_graph_out, void** tail_exec_out);
@@ -451,8 +449,9 @@ LP_API int lp_graph_release(void* tail_graph, void* tail_exec);
  * every sigma call: a copy of the captured call `graph` (root = the replace launch, LP_PH_REPLACE | LP_PH_EMIT | LP_PH_COEFFS)
  * whose root is the SAME launch with the sigma algebra folded in (`with_sigma`: the captured replace descriptor with
  * LP_PH_SIGMA and its sg_* fields set), instantiated.  `binding_out` names the new root for lp_node_call's per-call argument
- * refresh.  Briefly captures on a private stream to learn the launch geometry: not capture-safe.  Release with
- * lp_graph_release.                                                                                                   */
+ * refresh.  The captured root must run the launch `with_sigma` without LP_PH_SIGMA dispatches to (LP_E_UNSUPPORTED
+ * otherwise); a descriptor lp_step would refuse is refused with the same code before the graph is touched.  Host-side
+ * graph surgery only, no stream involved.  Release with lp_graph_release.                                        */
 LP_API int lp_graph_clone_sigma_root(void* graph, const lp_step_desc* with_sigma, void** graph_out, void** exec_out,
                                      lp_graph_binding* binding_out);
 

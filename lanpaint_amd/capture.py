@@ -185,17 +185,16 @@ class GraphReplay:
 
     def _sigma_root(self, cap, cap0, nd):
         """The copy of `cap`'s graph whose node 0 is the replace launch WITH the sigma algebra (LP_PH_SIGMA), made once per
-        capture, or None where the call does not qualify (lp_node_call's own conditions for folding the algebra: bit-packed
-        mask, a fused replace form, no correction tensor, no early-stop reset) or the runtime refuses."""
+        capture, or None.  The caller's node descriptor must ask for the fold (lp_node_call's own conditions, checked on every
+        call); whether the captured replace launch has a sigma form is lp_graph_clone_sigma_root's to say, and a refusal there,
+        like a capture without a bound root, is remembered."""
+        k0 = cap0.k0_desc
+        if k0 is None or not (nd.fold_sigma and nd.rows == k0.rows and bool(nd.is_flow) == bool(k0.flags & _cabi.LP_FL_FLOW)):
+            return None
         if cap.sigma_root is not None:
             return cap.sigma_root or None
         cap.sigma_root = False
-        k0 = cap0.k0_desc
-        ok = (cap.binding is not None and k0 is not None
-              and k0.phases == (_cabi.LP_PH_REPLACE | _cabi.LP_PH_EMIT | _cabi.LP_PH_COEFFS) and (k0.flags & _cabi.LP_FL_MASK_BITS)
-              and not k0.corr_el and not k0.es_reset and k0.replace_kind != _cabi.LP_REPLACE_KNOWN
-              and bool(nd.is_flow) == bool(k0.flags & _cabi.LP_FL_FLOW) and nd.rows == k0.rows and nd.fold_sigma)
-        if not ok:
+        if cap.binding is None:
             return None
         try:
             raw_graph = int(cap.graph.raw_cuda_graph())

@@ -10,7 +10,6 @@
 namespace lp {
 int step_dispatch(const lp_step_desc* d, hipStream_t stream, void* timer);
 int replace_node_update(const lp_step_desc* d, hipGraphExec_t exec, const lp_graph_binding* b);
-uint32_t replace_fingerprint(const lp_step_desc& d);
 int timer_create(void** out);
 int timer_destroy(void* h);
 int timer_elapsed_ns(void* h, double* ns);
@@ -142,17 +141,21 @@ int lp_graph_bind_replace(void* graph, const lp_step_desc* captured, lp_graph_bi
     if (hipGraphNodeGetType(root, &ty) != hipSuccess || ty != hipGraphNodeTypeKernel) return LP_E_UNSUPPORTED;
     hipKernelNodeParams p{};
     if (hipGraphKernelNodeGetParams(root, &p) != hipSuccess || !p.func || !p.kernelParams) return LP_E_UNSUPPORTED;
-    // the node must be the launch of `captured`: leading arguments x_t, C, x (LP_STEP_ARGS of a replace launch) and
-    // the descriptor it carries by value
+    // the node must be the launch of `captured`: leading arguments x_t, C, x (pack_step_args of a replace launch), the
+    // descriptor it carries by value, and the kernel and grid plan_step picks for that descriptor
     void* const* kp = p.kernelParams;
     const lp_step_desc* dn = static_cast<const lp_step_desc*>(kp[8]);
     if (*static_cast<void* const*>(kp[0]) != captured->x_t || *static_cast<const void* const*>(kp[2]) != captured->x ||
         !dn || dn->phases != captured->phases || !(dn->phases & LP_PH_REPLACE) || dn->n_el != captured->n_el)
         return LP_E_UNSUPPORTED;
+    lp::StepPlan plan;
+    const int rc = lp::plan_step(*captured, &plan);
+    if (rc != LP_OK) return rc;
+    if (!lp::plan_is_node(plan, p.func, p.gridDim, p.blockDim)) return LP_E_UNSUPPORTED;
     out->node = root; out->func = p.func;
     out->grid[0] = p.gridDim.x; out->grid[1] = p.gridDim.y; out->grid[2] = p.gridDim.z;
     out->block[0] = p.blockDim.x; out->block[1] = p.blockDim.y; out->block[2] = p.blockDim.z;
-    out->shared_bytes = p.sharedMemBytes; out->fingerprint = lp::replace_fingerprint(*captured);
+    out->shared_bytes = p.sharedMemBytes; out->reserved0 = 0;
     return LP_OK;
 }
 
@@ -177,51 +180,45 @@ int lp_graph_clone_sigma_root(void* graph, const lp_step_desc* with_sigma, void*
                               lp_graph_binding* binding_out) {
     if (!graph || !with_sigma || !graph_out || !exec_out || !binding_out) return LP_E_INVALID;
     if (with_sigma->phases != (LP_PH_REPLACE | LP_PH_EMIT | LP_PH_COEFFS | LP_PH_SIGMA)) return LP_E_INVALID;
-    // (1) the launch geometry and kernel of the sigma-folded replace launch: captured once on a private stream (the dispatcher
-    //     is the only place that knows which instantiation and grid a descriptor maps to)
-    hipStream_t tmp = nullptr;
-    if (hipStreamCreateWithFlags(&tmp, hipStreamNonBlocking) != hipSuccess) return LP_E_LAUNCH;
-    hipGraph_t probe = nullptr;
-    int rc = LP_E_UNSUPPORTED;
+    // the launch the new root makes, and the one the captured root must be making: the same descriptor without the algebra
+    lp::StepPlan sig, plain;
+    int rc = lp::plan_step(*with_sigma, &sig);
+    if (rc != LP_OK) return rc;
+    lp_step_desc without = *with_sigma;
+    without.phases &= ~LP_PH_SIGMA;
+    rc = lp::plan_step(without, &plain);
+    if (rc != LP_OK) return rc;
+    rc = LP_E_UNSUPPORTED;
     hipGraph_t clone = nullptr;
     hipGraphExec_t exec = nullptr;
     do {
-        if (hipStreamBeginCapture(tmp, hipStreamCaptureModeThreadLocal) != hipSuccess) break;
-        const int rc_launch = lp::step_dispatch(with_sigma, tmp, nullptr);
-        const hipError_t end = hipStreamEndCapture(tmp, &probe);
-        if (rc_launch != LP_OK) { rc = rc_launch; break; }
-        if (end != hipSuccess || !probe) break;
-        size_t n_root = 0;
-        hipGraphNode_t probe_root = nullptr;
-        if (hipGraphGetRootNodes(probe, nullptr, &n_root) != hipSuccess || n_root != 1 ||
-            hipGraphGetRootNodes(probe, &probe_root, &n_root) != hipSuccess || !probe_root) break;
-        hipGraphNodeType ty;
-        if (hipGraphNodeGetType(probe_root, &ty) != hipSuccess || ty != hipGraphNodeTypeKernel) break;
-        hipKernelNodeParams p{};
-        if (hipGraphKernelNodeGetParams(probe_root, &p) != hipSuccess || !p.func) break;
-        // (2) the captured call with its root exchanged for that launch
         if (hipGraphClone(&clone, static_cast<hipGraph_t>(graph)) != hipSuccess) { clone = nullptr; break; }
         hipGraphNode_t root = nullptr;
-        n_root = 0;
+        size_t n_root = 0;
         if (hipGraphGetRootNodes(clone, nullptr, &n_root) != hipSuccess || n_root != 1 ||
             hipGraphGetRootNodes(clone, &root, &n_root) != hipSuccess || !root) break;
+        hipGraphNodeType ty;
         if (hipGraphNodeGetType(root, &ty) != hipSuccess || ty != hipGraphNodeTypeKernel) break;
+        hipKernelNodeParams p{};
+        if (hipGraphKernelNodeGetParams(root, &p) != hipSuccess || !lp::plan_is_node(plain, p.func, p.gridDim, p.blockDim)) break;
         // the root keeps its place in the graph (same node, same edges, same insertion order: a node added afterwards and wired
         // in by hand made the runtime leave its pre-recorded-packet path -- every node of every launch then went through the
         // ordinary dispatch, 3.4 us of host time each); only what it launches changes
+        lp::StepArgs a;
+        lp::pack_step_args(sig, *with_sigma, &a);
+        p.func = const_cast<void*>(sig.kernel);
+        p.gridDim = sig.grid;
+        p.kernelParams = a.ptr;
+        p.extra = nullptr;
         if (hipGraphKernelNodeSetParams(root, &p) != hipSuccess) break;
-        hipGraphNode_t fresh = root;
         if (hipGraphInstantiate(&exec, clone, nullptr, nullptr, 0) != hipSuccess) { exec = nullptr; break; }
-        binding_out->node = fresh; binding_out->func = p.func;
+        binding_out->node = root; binding_out->func = p.func;
         binding_out->grid[0] = p.gridDim.x; binding_out->grid[1] = p.gridDim.y; binding_out->grid[2] = p.gridDim.z;
         binding_out->block[0] = p.blockDim.x; binding_out->block[1] = p.blockDim.y; binding_out->block[2] = p.blockDim.z;
-        binding_out->shared_bytes = p.sharedMemBytes;
-        binding_out->fingerprint = lp::replace_fingerprint(*with_sigma);
+        binding_out->shared_bytes = p.sharedMemBytes; binding_out->reserved0 = 0;
         *graph_out = clone; *exec_out = exec;
         rc = LP_OK;
     } while (false);
-    if (probe) (void)hipGraphDestroy(probe);
-    (void)hipStreamDestroy(tmp);
     if (rc != LP_OK) {
         if (exec) (void)hipGraphExecDestroy(exec);
         if (clone) (void)hipGraphDestroy(clone);
@@ -270,18 +267,22 @@ static int node_call_body(lp_node_call_desc* c, hipStream_t s, bool* queued_spec
     // On a speculated call the answer is only a confirmation, so its arriving a little later costs nothing: the sigma
     // algebra rides in the replace launch (LP_PH_SIGMA) instead of a launch of its own.  Otherwise the small kernel goes
     // first -- its answer is what the host is waiting for.
-    const bool fold_sigma = speculate && c->replace->phases == (LP_PH_REPLACE | LP_PH_EMIT | LP_PH_COEFFS) &&
-                            (c->replace->flags & LP_FL_MASK_BITS) && !c->replace->corr_el && !c->replace->es_reset &&
-                            c->replace->replace_kind != LP_REPLACE_KNOWN && c->is_flow == ((c->replace->flags & LP_FL_FLOW) ? 1 : 0) &&
-                            c->rows == c->replace->rows && c->fold_sigma;
-    c->one_launch = 0;
+    // (the node's own conditions here; whether the descriptor has an LP_PH_SIGMA form is plan_step's to say)
+    lp_step_desc d;
+    bool fold_sigma = speculate && c->fold_sigma && c->is_flow == ((c->replace->flags & LP_FL_FLOW) ? 1 : 0) &&
+                      c->rows == c->replace->rows;
     if (fold_sigma) {
-        lp_step_desc d = rep;
+        d = rep;
         d.phases |= LP_PH_SIGMA;
         d.sg_sigma = c->sigma; d.sg_schedule = c->schedule; d.sg_schedule_len = c->schedule_len; d.sg_times_out = c->times_out;
         d.sg_scalars_out = c->scalars_out; d.sg_seq_out = c->seq_out; d.sg_seq = c->seq; d.sg_valid_out = c->valid_word;
         d.sg_n_steps = c->n_steps; d.sg_early_stop = c->early_stop; d.sg_total_steps = c->total_steps; d.sg_guess = c->guess;
         d.sg_min_step_frac = c->min_step_frac;
+        lp::StepPlan plan;
+        fold_sigma = lp::plan_step(d, &plan) == LP_OK;
+    }
+    c->one_launch = 0;
+    if (fold_sigma) {
         // the whole call as ONE graph launch when a copy of the captured call with this very launch as its root exists for the
         // guessed count: refresh the root's arguments, launch, done -- nothing eager in front of the graph
         hipGraphExec_t full = (c->full_exec_by_count && c->full_binding_by_count && c->guess < c->n_counts)

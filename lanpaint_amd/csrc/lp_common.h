@@ -736,4 +736,32 @@ __host__ __device__ inline int xin_dtype(uint32_t flags) {
     return (flags & LP_FL_XIN_BF16) ? DT_BF16 : (flags & LP_FL_XIN_F16) ? DT_F16 : DT_F32;
 }
 
+// ---- one lp_step launch, as plan_step (step_kernel.hip) selects it from a descriptor: no HIP call, no side effect ----
+struct StepPlan {
+    const void* kernel;        // &lp_step_kernel<VEC, MODE, PH, X0W, RNG, ST, ES>; the block is always 256 threads
+    dim3 grid;
+    uint32_t ph_ct;            // the instantiation's compile-time PH and VEC: they decide the argument packing
+    int vec;
+    bool decide;               // an lp_es_decide_kernel launch follows (early stop), on state slot decide_slot
+    int decide_slot;
+    int mode, x0w, rng, es;    // the other template arguments (the LP_TRACE_INSTANTIATIONS build records them)
+    bool st;
+};
+// the kernel arguments of a plan's launch; `ptr` is the argument array hipLaunchKernel / hipKernelNodeParams take (it
+// points into this struct and at the descriptor, which has to outlive it)
+struct StepArgs {
+    void* x_t;
+    void* C;
+    const void *a2, *a3, *a4, *a5;
+    int32_t el_per_row;
+    uint32_t flags;
+    void* ptr[9];
+};
+// LP_OK and the plan, or the status lp_step returns for `d`.  `timed`: for lp_step_timed (an early-stop launch may be two
+// kernels, so it is refused)
+int plan_step(const lp_step_desc& d, StepPlan* out, bool timed = false);
+void pack_step_args(const StepPlan& p, const lp_step_desc& d, StepArgs* a);
+// does a kernel node launching `func` on grid x block run plan `p`, and nothing else?
+bool plan_is_node(const StepPlan& p, const void* func, const dim3& grid, const dim3& block);
+
 }  // namespace lp

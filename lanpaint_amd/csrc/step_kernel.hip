@@ -1517,118 +1517,65 @@ static unsigned st_segments(const lp_step_desc& d) {
     return (gy > 0 && gy <= 65535 && static_cast<int64_t>(d.rng_inc) == 4 * rounds) ? static_cast<unsigned>(gy) : 0u;
 }
 
-// ---- coverage build (-DLP_TRACE_INSTANTIATIONS; build/liblanpaint_hip_trace.so, never the product library) ------------
-// Which lp_step_kernel<...> instantiations does a process really launch?  Every launch notes its template arguments; the
-// set is appended to the file LANPAINT_AMD_TRACE_FILE names when the process exits.  scripts/instantiation_coverage.py
-// compares it with the instantiations the product library contains (tests/test_cabi_exports.py keeps the two in step).
-#ifdef LP_TRACE_INSTANTIATIONS
-}  // namespace lp
-#include <cstdio>
-#include <cstdlib>
-#include <mutex>
-#include <set>
-#include <string>
-namespace lp {
-struct TraceSet {
-    std::mutex mu;
-    std::set<std::string> seen;
-    ~TraceSet() {
-        const char* path = std::getenv("LANPAINT_AMD_TRACE_FILE");
-        if (!path || seen.empty()) return;
-        if (FILE* f = std::fopen(path, "a")) {
-            for (const auto& s : seen) std::fprintf(f, "%s\n", s.c_str());
-            std::fclose(f);
-        }
-    }
-};
-static TraceSet& trace_set() {
-    static TraceSet t;
-    return t;
-}
-static void trace_note(int vec, int mode, unsigned ph, int x0w, int rng, bool st, int es) {
-    char buf[96];
-    std::snprintf(buf, sizeof buf, "%d, %d, %uu, %d, %d, %s, %d", vec, mode, ph, x0w, rng, st ? "true" : "false", es);
-    TraceSet& t = trace_set();
-    std::lock_guard<std::mutex> lock(t.mu);
-    t.seen.insert(buf);
-}
-#define LP_TRACE(es) trace_note(VEC, MODE, PH, X0W, RNG, ST, es)
-#else
-#define LP_TRACE(es)
-#endif
-
-// the preloaded leading arguments of lp_step_kernel<VEC, ...> (see its head) followed by the descriptor
-#define LP_STEP_ARGS(d)                                                                                          \
-    static_cast<void*>((d).x_t), static_cast<void*>((d).C),                                                      \
-        ((PH & LP_PH_REPLACE) ? static_cast<const void*>((d).x) : (d).x0),                                        \
-        ((PH & LP_PH_REPLACE) ? static_cast<const void*>((d).replace_kind == LP_REPLACE_KNOWN ? (d).known : (d).noise) \
-                              : (d).x0_big),                                                                      \
-        ((PH & LP_PH_REPLACE) || VEC != 1 ? static_cast<const void*>((d).y) : static_cast<const void*>((d).coef)), \
-        ((PH & LP_PH_REPLACE) || VEC != 1 ? (d).mask : static_cast<const void*>((d).rng_offset_ptr)),             \
-        static_cast<int32_t>((d).el_per_row), (d).flags, (d)
+// ---- launch plan ------------------------------------------------------------------------------
+// plan_step maps a descriptor to the lp_step_kernel<...> instantiation and grid it runs on (StepPlan, lp_common.h), and to
+// the lp_es_decide_kernel launch that may follow; nothing else decides it.  step_dispatch enqueues the plan; the graph
+// entry points (replace_node_update, lp_graph_bind_replace, lp_graph_clone_sigma_root) compare a captured node with it.
 
 template <int VEC, int MODE, uint32_t PH, int X0W = 0, int RNG = 2, bool ST = false, int ES = 0>
-static hipError_t launch(const lp_step_desc& d, hipStream_t stream, Timer* timer) {
+static void plan_kernel(const lp_step_desc& d, StepPlan* p) {
     const int64_t groups = ST ? static_cast<int64_t>(d.rng_bg) : d.el_per_row / VEC;
-    constexpr int block = kBlock;
-    int64_t bx = (groups + block - 1) / block;
     // One group per lane, no grid-stride loop: capping the grid at 2048 blocks cost 30 % on a 33 M-element
     // batch (220 -> 170 us; profiles/r01_microbench_kernel_variants.log); the BASELINE shapes all fit in
-    // <= 2048 blocks anyway.
+    // <= 2048 blocks anyway.  (el_per_row < 2^31 and rng_bg < 2^32: bx < 2^24.)
+    int64_t bx = (groups + kBlock - 1) / kBlock;
     if (bx < 1) bx = 1;
-    if (bx > 0x7fffffff) return hipErrorInvalidValue;
-    unsigned gy = static_cast<unsigned>(d.rows);
-    if constexpr (ST) gy = st_segments(d);            // (round, row) pairs, see the kernel head
-    const dim3 grid(static_cast<unsigned>(bx), gy);
-    if constexpr (ES != 0) {
-        // gated (replayed) loop: the stop rule of iteration i - 1 rides in launch i -- every wave totals the 64 accumulator
-        // slots itself -- and one closing lp_es_decide_kernel follows the last launch unless the loop closes itself
-        // (LP_FL_ES_CLOSE).  Watched (eager) loop: the host waits for every verdict, so a one-wave kernel forms it right
-        // after the launch.  (The folded kernel is its own instantiation: its extra live state would cost the plain
-        // early-stop launch registers it does not need.)
-        const bool fold = (d.flags & LP_FL_ES_GATED) && !(d.tune & LP_TUNE_ES_NO_FOLD);
-        if constexpr (PH != 0) {
-            // the phase-specialised early-stop kernels exist in their folded form only (the launches a replayed loop
-            // repeats); a fused-phase launch that is not folded (a tuning switch) takes the run-time-phase kernel
-            if (!fold) return launch<VEC, MODE, 0, 0, 2, false, 1>(d, stream, timer);
-            LP_TRACE(2);
-            hipLaunchKernelGGL((lp_step_kernel<VEC, MODE, PH, X0W, RNG, ST, 2>), grid, dim3(block), 0, stream, LP_STEP_ARGS(d));
-        } else {
-            LP_TRACE(fold ? 2 : 1);
-            if (fold) hipLaunchKernelGGL((lp_step_kernel<VEC, MODE, PH, X0W, RNG, ST, 2>), grid, dim3(block), 0, stream, LP_STEP_ARGS(d));
-            else hipLaunchKernelGGL((lp_step_kernel<VEC, MODE, PH, X0W, RNG, ST, 1>), grid, dim3(block), 0, stream, LP_STEP_ARGS(d));
-        }
-        const bool close = fold && (d.flags & LP_FL_ES_CLOSE) && d.es_index + 1 == d.es_n_steps;
-        if ((d.phases & kPost) && !(d.tune & LP_TUNE_ES_NO_DECIDE) && !close && (!fold || d.es_index + 1 == d.es_n_steps)) {
-            if (hipGetLastError() != hipSuccess) return hipErrorLaunchFailure;
-            hipLaunchKernelGGL(lp_es_decide_kernel, dim3(1), dim3(kWave), 0, stream, d, fold ? (d.es_index & 1) : 0);
-        }
-        return hipGetLastError();
+    const unsigned gy = ST ? st_segments(d) : static_cast<unsigned>(d.rows);       // ST: (round, row) pairs, see the kernel head
+    *p = StepPlan{reinterpret_cast<const void*>(&lp_step_kernel<VEC, MODE, PH, X0W, RNG, ST, ES>), dim3(static_cast<unsigned>(bx), gy),
+                  PH, VEC, false, 0, MODE, X0W, RNG, ES, ST};
+}
+
+// Early-stop launches (LP_FL_ES).  Gated (replayed) loop: the stop rule of iteration i - 1 rides in launch i -- every wave
+// totals the 64 accumulator slots itself -- and one closing lp_es_decide_kernel follows the last launch unless the loop
+// closes itself (LP_FL_ES_CLOSE).  Watched (eager) loop: the host waits for every verdict, so a one-wave kernel forms it
+// right after the launch.  (The folded kernel is its own instantiation: its extra live state would cost the plain
+// early-stop launch registers it does not need.)
+template <int VEC, int MODE, uint32_t PH, int X0W = 0, int RNG = 2>
+static void plan_es(const lp_step_desc& d, StepPlan* p) {
+    const bool fold = (d.flags & LP_FL_ES_GATED) && !(d.tune & LP_TUNE_ES_NO_FOLD);
+    if constexpr (PH != 0) {
+        // the phase-specialised early-stop kernels exist in their folded form only (the launches a replayed loop
+        // repeats); a fused-phase launch that is not folded (a tuning switch) takes the run-time-phase kernel
+        if (!fold) return plan_es<VEC, MODE, 0>(d, p);
+        plan_kernel<VEC, MODE, PH, X0W, RNG, false, 2>(d, p);
     } else {
-        // (inside `else`: after an `if constexpr` that returns, the statements below would still be instantiated for the
-        // early-stop launches -- eight lp_step_kernel<..., ES = 1> code objects nothing ever launched, round 3)
-        LP_TRACE(ES);
-        if (timer) {
-            hipExtLaunchKernelGGL((lp_step_kernel<VEC, MODE, PH, X0W, RNG, ST, ES>), grid, dim3(block), 0, stream, timer->start,
-                                  timer->stop, 0, LP_STEP_ARGS(d));
-        } else {
-            hipLaunchKernelGGL((lp_step_kernel<VEC, MODE, PH, X0W, RNG, ST, ES>), grid, dim3(block), 0, stream, LP_STEP_ARGS(d));
-        }
-        return hipGetLastError();
+        if (fold) plan_kernel<VEC, MODE, PH, X0W, RNG, false, 2>(d, p);
+        else plan_kernel<VEC, MODE, PH, X0W, RNG, false, 1>(d, p);
     }
+    const bool close = fold && (d.flags & LP_FL_ES_CLOSE) && d.es_index + 1 == d.es_n_steps;
+    p->decide = (d.phases & kPost) && !(d.tune & LP_TUNE_ES_NO_DECIDE) && !close && (!fold || d.es_index + 1 == d.es_n_steps);
+    p->decide_slot = fold ? (d.es_index & 1) : 0;
+}
+
+// The hot phase combinations: ATen's layout (strided), the width of the heads, the generator.
+template <int VEC, int MODE, uint32_t PH>
+static void plan_hot(const lp_step_desc& d, bool strided, bool x0_half, bool rng_torch, StepPlan* p) {
+    if (strided) return x0_half ? plan_kernel<4, MODE, PH, 2, 1, true>(d, p) : plan_kernel<4, MODE, PH, 4, 1, true>(d, p);
+    if (x0_half) return rng_torch ? plan_kernel<VEC, MODE, PH, 2, 1>(d, p) : plan_kernel<VEC, MODE, PH, 2, 0>(d, p);
+    return rng_torch ? plan_kernel<VEC, MODE, PH, 4, 1>(d, p) : plan_kernel<VEC, MODE, PH, 4, 0>(d, p);
 }
 
 static bool aligned(const void* p, size_t a) { return p == nullptr || (reinterpret_cast<uintptr_t>(p) % a) == 0; }
 
 template <int VEC>
-static hipError_t launch_phase(const lp_step_desc& d, hipStream_t stream, Timer* timer) {
-    if (d.flags & LP_FL_PER_ELEMENT) return launch<VEC, MODE_PER_EL, 0>(d, stream, timer);
+static void plan_phase(const lp_step_desc& d, StepPlan* p) {
+    if (d.flags & LP_FL_PER_ELEMENT) return plan_kernel<VEC, MODE_PER_EL, 0>(d, p);
     constexpr uint32_t R = LP_PH_REPLACE, F = LP_PH_POST_FIRST, S = LP_PH_POST_STEADY, P = LP_PH_PRE_HALF,
                        E = LP_PH_EMIT;
     // a bit-packed mask is hard by construction; the audio correction needs the general branch
     const bool hard = (d.flags & LP_FL_MASK_BITS) && d.corr_el == nullptr;
     if (d.flags & LP_FL_AV)             // two time sets per row (AV packs): the run-time row-table kernels know the flag
-        return (d.flags & LP_FL_ES) ? launch<VEC, MODE_ROW, 0, 0, 2, false, 1>(d, stream, timer) : launch<VEC, MODE_ROW, 0>(d, stream, timer);
+        return (d.flags & LP_FL_ES) ? plan_es<VEC, MODE_ROW, 0>(d, p) : plan_kernel<VEC, MODE_ROW, 0>(d, p);
     // x0s handed in (the public langevin_dynamics) and host-supplied noise (recorded streams, explicit torch.randn_like draws)
     // only exist in the run-time-phase kernels (round 5: their selects left the phase-specialised ones)
     const bool rare = (d.flags & LP_FL_X0S_GIVEN) || d.xi_post || d.xi_pre;
@@ -1644,55 +1591,43 @@ static hipError_t launch_phase(const lp_step_desc& d, hipStream_t stream, Timer*
         if (hard && !x0_half && !rare && (!d.es_ring || (d.flags & LP_FL_ES_RING_BITS))) {
             const bool rt = d.rng_kind == LP_RNG_TORCH;
             if (d.phases == (S | P | E))
-                return rt ? launch<VEC, MODE_HARD, S | P | E, 4, 1, false, 1>(d, stream, timer)
-                          : launch<VEC, MODE_HARD, S | P | E, 4, 0, false, 1>(d, stream, timer);
+                return rt ? plan_es<VEC, MODE_HARD, S | P | E, 4, 1>(d, p) : plan_es<VEC, MODE_HARD, S | P | E, 4, 0>(d, p);
             if (d.phases == (F | P | E))
-                return rt ? launch<VEC, MODE_HARD, F | P | E, 4, 1, false, 1>(d, stream, timer)
-                          : launch<VEC, MODE_HARD, F | P | E, 4, 0, false, 1>(d, stream, timer);
+                return rt ? plan_es<VEC, MODE_HARD, F | P | E, 4, 1>(d, p) : plan_es<VEC, MODE_HARD, F | P | E, 4, 0>(d, p);
         }
-        return hard ? launch<VEC, MODE_HARD, 0, 0, 2, false, 1>(d, stream, timer)
-                    : launch<VEC, MODE_ROW, 0, 0, 2, false, 1>(d, stream, timer);
+        return hard ? plan_es<VEC, MODE_HARD, 0>(d, p) : plan_es<VEC, MODE_ROW, 0>(d, p);
     }
-    if (d.flags & LP_FL_MASK_U8) return launch<VEC, MODE_ROW, 0>(d, stream, timer);   // legacy format: run-time everything
+    if (d.flags & LP_FL_MASK_U8) return plan_kernel<VEC, MODE_ROW, 0>(d, p);   // legacy format: run-time everything
     // (a replace launch WITHOUT the folded table -- a caller that ran lp_coeffs itself -- and a loop of ONE iteration,
     // F | E, run through the run-time-phase kernel: rare launches that do not earn instantiations of their own)
     if (d.phases == (R | E | LP_PH_COEFFS))                                          // replace step + the coefficient table
-        return hard ? launch<VEC, MODE_HARD, R | E | LP_PH_COEFFS>(d, stream, timer)
-                    : launch<VEC, MODE_ROW, R | E | LP_PH_COEFFS>(d, stream, timer);
+        return hard ? plan_kernel<VEC, MODE_HARD, R | E | LP_PH_COEFFS>(d, p) : plan_kernel<VEC, MODE_ROW, R | E | LP_PH_COEFFS>(d, p);
     if (d.phases == (R | E | LP_PH_COEFFS | LP_PH_SIGMA))                            // ... + the sigma algebra of the call (bit mask only)
-        return launch<VEC, MODE_HARD, R | E | LP_PH_COEFFS | LP_PH_SIGMA>(d, stream, timer);
+        return plan_kernel<VEC, MODE_HARD, R | E | LP_PH_COEFFS | LP_PH_SIGMA>(d, p);
     const bool rng_torch = d.rng_kind == LP_RNG_TORCH;
     // ATen's element-to-thread layout pays off when a Philox block really serves several elements of this tensor
     // (batch rows: as long as a row covers at least half a round most lanes still use two or more values of their block)
     const bool strided = VEC == 4 && rng_torch && !d.xi_post && !d.xi_pre && d.n_el > static_cast<int64_t>(d.rng_bg) &&
                          (d.rng_bg % kBlock) == 0 &&           /* a block is 256 whole ATen threads */
                          (d.rows == 1 || d.el_per_row >= 2 * static_cast<int64_t>(d.rng_bg)) && st_segments(d) != 0;
-#define LP_HOT(MODE_, PH_)                                                                                   \
-    (strided ? (x0_half ? launch<4, MODE_, PH_, 2, 1, true>(d, stream, timer) : launch<4, MODE_, PH_, 4, 1, true>(d, stream, timer)) \
-     : x0_half ? (rng_torch ? launch<VEC, MODE_, PH_, 2, 1>(d, stream, timer) : launch<VEC, MODE_, PH_, 2, 0>(d, stream, timer)) \
-               : (rng_torch ? launch<VEC, MODE_, PH_, 4, 1>(d, stream, timer) : launch<VEC, MODE_, PH_, 4, 0>(d, stream, timer)))
-    if (!pair_ok || rare) return hard ? launch<VEC, MODE_HARD, 0>(d, stream, timer) : launch<VEC, MODE_ROW, 0>(d, stream, timer);
+    if (!pair_ok || rare) return hard ? plan_kernel<VEC, MODE_HARD, 0>(d, p) : plan_kernel<VEC, MODE_ROW, 0>(d, p);
     if (hard) {
         switch (d.phases) {
-            case S | P | E: return LP_HOT(MODE_HARD, S | P | E);   // steady state
-            case F | P | E: return LP_HOT(MODE_HARD, F | P | E);   // iteration 0
-            case S | E: return LP_HOT(MODE_HARD, S | E);           // last iteration
-            default: return launch<VEC, MODE_HARD, 0>(d, stream, timer);   // unfused (early stop), n_steps == 1, etc.
+            case S | P | E: return plan_hot<VEC, MODE_HARD, S | P | E>(d, strided, x0_half, rng_torch, p);   // steady state
+            case F | P | E: return plan_hot<VEC, MODE_HARD, F | P | E>(d, strided, x0_half, rng_torch, p);   // iteration 0
+            case S | E: return plan_hot<VEC, MODE_HARD, S | E>(d, strided, x0_half, rng_torch, p);           // last iteration
+            default: return plan_kernel<VEC, MODE_HARD, 0>(d, p);   // unfused (early stop), n_steps == 1, etc.
         }
     }
     switch (d.phases) {
-        case S | P | E: return LP_HOT(MODE_ROW, S | P | E);
-        case F | P | E: return LP_HOT(MODE_ROW, F | P | E);
-        case S | E: return LP_HOT(MODE_ROW, S | E);
-        default: return launch<VEC, MODE_ROW, 0>(d, stream, timer);
+        case S | P | E: return plan_hot<VEC, MODE_ROW, S | P | E>(d, strided, x0_half, rng_torch, p);
+        case F | P | E: return plan_hot<VEC, MODE_ROW, F | P | E>(d, strided, x0_half, rng_torch, p);
+        case S | E: return plan_hot<VEC, MODE_ROW, S | E>(d, strided, x0_half, rng_torch, p);
+        default: return plan_kernel<VEC, MODE_ROW, 0>(d, p);
     }
-#undef LP_HOT
 }
 
-int step_dispatch(const lp_step_desc* dp, hipStream_t stream, void* timer_handle) {
-    Timer* timer = static_cast<Timer*>(timer_handle);
-    if (!dp) return LP_E_INVALID;
-    const lp_step_desc& d = *dp;
+int plan_step(const lp_step_desc& d, StepPlan* out, bool timed) {
     if (d.n_el <= 0 || d.rows <= 0 || d.el_per_row <= 0 || d.n_el != d.el_per_row * d.rows) return LP_E_INVALID;
     if (d.rows > 65535 || d.el_per_row > 0x7fffffff) return LP_E_UNSUPPORTED;
     if (!d.mask || !d.x_t) return LP_E_INVALID;
@@ -1747,7 +1682,7 @@ int step_dispatch(const lp_step_desc* dp, hipStream_t stream, void* timer_handle
     if ((ph & LP_PH_EMIT) && !d.x_in) return LP_E_INVALID;
     if (d.es_reset && !d.es) return LP_E_INVALID;
     if (d.flags & LP_FL_ES) {
-        if (timer) return LP_E_UNSUPPORTED;      // an early-stop launch may be two kernels: no single event pair describes it
+        if (timed) return LP_E_UNSUPPORTED;      // an early-stop launch may be two kernels: no single event pair describes it
         if (per_el || !d.es || !d.es_partials || d.es_index < 0 || d.es_n_steps <= d.es_index) return LP_E_INVALID;
         if (!d.es_x0s[0] || !d.es_x0s[1] || !d.es_x0s[2]) return LP_E_INVALID;
         if ((d.flags & LP_FL_ES_GATED) && !d.es_xte) return LP_E_INVALID;                 // the tentative-state buffer of a gated loop
@@ -1770,54 +1705,118 @@ int step_dispatch(const lp_step_desc* dp, hipStream_t stream, void* timer_handle
     bool vec4 = can_vec4 && d.n_el > 512 * 1024;
     if (d.tune & LP_TUNE_VEC4) vec4 = can_vec4;
     if (d.tune & LP_TUNE_VEC1) vec4 = false;
-    const hipError_t err = vec4 ? launch_phase<4>(d, stream, timer) : launch_phase<1>(d, stream, timer);
-    return err == hipSuccess ? LP_OK : LP_E_LAUNCH;
+    if (vec4) plan_phase<4>(d, out);
+    else plan_phase<1>(d, out);
+    return LP_OK;
 }
 
-// The replace launch as node 0 of a replayed graph: write this call's descriptor into the node's arguments.  The
-// argument list is LP_STEP_ARGS of a replace launch (PH & LP_PH_REPLACE): x_t, C, x, known | noise, y, mask, row length,
-// flags, the descriptor by value.  Which instantiation / grid the node runs was fixed at capture; the caller keeps
-// shape, flags, phases and pointer alignment what they were (the engine's identity pre-check).
-// What step_dispatch looks at when it picks the kernel and the grid of a replace launch.  A captured node keeps its kernel;
-// only its arguments are rewritten per call (replace_node_update), so a rewritten descriptor has to be one the dispatcher
-// would have sent to the SAME instantiation -- otherwise the captured kernel would read fields it was not compiled for
-// (a phase-specialised kernel ignores host noise tensors and treats x0 as backbone heads, for one).
-uint32_t replace_fingerprint(const lp_step_desc& d) {
-    const uint32_t sel = LP_FL_FLOW | LP_FL_MASK_BITS | LP_FL_MASK_U8 | LP_FL_MASK_DENOISE | LP_FL_PER_ELEMENT | LP_FL_AV |
-                         LP_FL_XIN_BF16 | LP_FL_XIN_F16 | LP_FL_X0S_GIVEN | LP_FL_NO_REGION_SKIP;
-    uint64_t h = 0x9E3779B97F4A7C15ull;
-    const uint64_t parts[] = {d.phases, d.flags & sel, static_cast<uint64_t>(static_cast<uint32_t>(d.replace_kind)),
-                              static_cast<uint64_t>(static_cast<uint32_t>(d.rng_kind)), static_cast<uint64_t>(d.n_el),
-                              static_cast<uint64_t>(d.rows), static_cast<uint64_t>(d.tune), d.es ? 1ull : 0ull,
-                              d.corr_el ? 1ull : 0ull};
-    for (uint64_t v : parts) { h ^= v + 0x9E3779B97F4A7C15ull + (h << 6) + (h >> 2); }
-    return static_cast<uint32_t>(h ^ (h >> 32)) | 1u;          // never 0: 0 = "not recorded" (a binding filled in by hand)
+// the preloaded leading arguments of lp_step_kernel (see its head) followed by the descriptor; which pointers lead
+// depends on the instantiation's compile-time PH and VEC, not on d.phases
+void pack_step_args(const StepPlan& p, const lp_step_desc& d, StepArgs* a) {
+    const bool rep = (p.ph_ct & LP_PH_REPLACE) != 0, lead_y = rep || p.vec != 1;
+    a->x_t = d.x_t;
+    a->C = d.C;
+    a->a2 = rep ? static_cast<const void*>(d.x) : d.x0;
+    a->a3 = rep ? static_cast<const void*>(d.replace_kind == LP_REPLACE_KNOWN ? d.known : d.noise) : d.x0_big;
+    a->a4 = lead_y ? static_cast<const void*>(d.y) : static_cast<const void*>(d.coef);
+    a->a5 = lead_y ? d.mask : static_cast<const void*>(d.rng_offset_ptr);
+    a->el_per_row = static_cast<int32_t>(d.el_per_row);
+    a->flags = d.flags;
+    void* const ptr[9] = {&a->x_t, &a->C, &a->a2, &a->a3, &a->a4, &a->a5, &a->el_per_row, &a->flags, const_cast<lp_step_desc*>(&d)};
+    for (int k = 0; k < 9; ++k) a->ptr[k] = ptr[k];
 }
 
+bool plan_is_node(const StepPlan& p, const void* func, const dim3& grid, const dim3& block) {
+    return !p.decide && func == p.kernel && grid.x == p.grid.x && grid.y == p.grid.y && grid.z == p.grid.z &&
+           block.x == static_cast<unsigned>(kBlock) && block.y == 1 && block.z == 1;
+}
+
+// ---- coverage build (-DLP_TRACE_INSTANTIATIONS; build/liblanpaint_hip_trace.so, never the product library) ------------
+// Which lp_step_kernel<...> instantiations does a process really launch?  Every launch notes its template arguments; the
+// set is appended to the file LANPAINT_AMD_TRACE_FILE names when the process exits.  scripts/instantiation_coverage.py
+// compares it with the instantiations the product library contains (tests/test_cabi_exports.py keeps the two in step).
+#ifdef LP_TRACE_INSTANTIATIONS
+}  // namespace lp
+#include <cstdio>
+#include <cstdlib>
+#include <mutex>
+#include <set>
+#include <string>
+namespace lp {
+struct TraceSet {
+    std::mutex mu;
+    std::set<std::string> seen;
+    ~TraceSet() {
+        const char* path = std::getenv("LANPAINT_AMD_TRACE_FILE");
+        if (!path || seen.empty()) return;
+        if (FILE* f = std::fopen(path, "a")) {
+            for (const auto& s : seen) std::fprintf(f, "%s\n", s.c_str());
+            std::fclose(f);
+        }
+    }
+};
+static TraceSet& trace_set() {
+    static TraceSet t;
+    return t;
+}
+static void trace_note(const StepPlan& p) {
+    char buf[96];
+    std::snprintf(buf, sizeof buf, "%d, %d, %uu, %d, %d, %s, %d", p.vec, p.mode, p.ph_ct, p.x0w, p.rng, p.st ? "true" : "false", p.es);
+    TraceSet& t = trace_set();
+    std::lock_guard<std::mutex> lock(t.mu);
+    t.seen.insert(buf);
+}
+#define LP_TRACE(p) trace_note(p)
+#else
+#define LP_TRACE(p)
+#endif
+
+static int enqueue(const StepPlan& p, const lp_step_desc& d, hipStream_t stream, Timer* timer) {
+    LP_TRACE(p);
+    StepArgs a;
+    pack_step_args(p, d, &a);
+    if (timer) (void)hipExtLaunchKernel(p.kernel, p.grid, dim3(kBlock), a.ptr, 0, stream, timer->start, timer->stop, 0);
+    else (void)hipLaunchKernel(p.kernel, p.grid, dim3(kBlock), a.ptr, 0, stream);
+    if (hipGetLastError() != hipSuccess) return LP_E_LAUNCH;
+    if (p.decide) {
+        hipLaunchKernelGGL(lp_es_decide_kernel, dim3(1), dim3(kWave), 0, stream, d, p.decide_slot);
+        if (hipGetLastError() != hipSuccess) return LP_E_LAUNCH;
+    }
+    return LP_OK;
+}
+
+int step_dispatch(const lp_step_desc* dp, hipStream_t stream, void* timer_handle) {
+    if (!dp) return LP_E_INVALID;
+    Timer* timer = static_cast<Timer*>(timer_handle);
+    StepPlan p;
+    const int rc = plan_step(*dp, &p, timer != nullptr);
+    return rc == LP_OK ? enqueue(p, *dp, stream, timer) : rc;
+}
+
+// The replace launch as node 0 of a replayed graph: write this call's descriptor into the node's arguments.  The node keeps
+// the kernel and grid it was captured with, so the rewrite is refused unless plan_step sends this descriptor to exactly
+// that launch -- otherwise the captured kernel would read fields it was not compiled for (a phase-specialised kernel
+// ignores host noise tensors and treats x0 as backbone heads; a VEC = 4 one needs 16-byte aligned streams).
 int replace_node_update(const lp_step_desc* dp, hipGraphExec_t exec, const lp_graph_binding* b) {
     if (!dp || !exec || !b || !b->node || !b->func) return LP_E_INVALID;
-    lp_step_desc d = *dp;
-    if (!(d.phases & LP_PH_REPLACE) || !d.x || !d.x_t) return LP_E_INVALID;
-    // a replace launch carries neither host noise tensors nor given x0s; and it must still be the launch that was captured
-    if (d.xi_post || d.xi_pre || (d.flags & LP_FL_X0S_GIVEN)) return LP_E_INVALID;
-    if (b->fingerprint != 0u && b->fingerprint != replace_fingerprint(d)) return LP_E_INVALID;
-    void* a0 = d.x_t;
-    void* a1 = d.C;
-    const void* a2 = d.x;
-    const void* a3 = d.replace_kind == LP_REPLACE_KNOWN ? static_cast<const void*>(d.known) : static_cast<const void*>(d.noise);
-    const void* a4 = d.y;
-    const void* a5 = d.mask;
-    int32_t epr = static_cast<int32_t>(d.el_per_row);
-    uint32_t fl = d.flags;
-    void* args[9] = {&a0, &a1, &a2, &a3, &a4, &a5, &epr, &fl, &d};
-    hipKernelNodeParams p{};
-    p.func = b->func;
-    p.gridDim = dim3(b->grid[0], b->grid[1], b->grid[2]);
-    p.blockDim = dim3(b->block[0], b->block[1], b->block[2]);
-    p.sharedMemBytes = b->shared_bytes;
-    p.kernelParams = args;
-    p.extra = nullptr;
-    return hipGraphExecKernelNodeSetParams(exec, static_cast<hipGraphNode_t>(b->node), &p) == hipSuccess ? LP_OK : LP_E_LAUNCH;
+    const lp_step_desc& d = *dp;
+    // a replace launch carries neither host noise tensors nor given x0s
+    if (!(d.phases & LP_PH_REPLACE) || d.xi_post || d.xi_pre || (d.flags & LP_FL_X0S_GIVEN)) return LP_E_INVALID;
+    StepPlan p;
+    const int rc = plan_step(d, &p);
+    if (rc != LP_OK) return rc;
+    if (!plan_is_node(p, b->func, dim3(b->grid[0], b->grid[1], b->grid[2]), dim3(b->block[0], b->block[1], b->block[2])))
+        return LP_E_INVALID;
+    StepArgs a;
+    pack_step_args(p, d, &a);
+    hipKernelNodeParams np{};
+    np.func = const_cast<void*>(p.kernel);
+    np.gridDim = p.grid;
+    np.blockDim = dim3(kBlock);
+    np.sharedMemBytes = b->shared_bytes;
+    np.kernelParams = a.ptr;
+    np.extra = nullptr;
+    return hipGraphExecKernelNodeSetParams(exec, static_cast<hipGraphNode_t>(b->node), &np) == hipSuccess ? LP_OK : LP_E_LAUNCH;
 }
 
 int timer_create(void** out) {

@@ -56,6 +56,52 @@ def test_graph_utilities_reject_bad_arguments_without_touching_the_device(hip_li
     assert g.value is None and e.value is None
 
 
+def _replace_desc(rows=2, el_per_row=1024):
+    """A replace launch with the folded coefficient table (the engine's captured node 0) on stand-in device addresses: every
+    check plan_step makes passes, and nothing here dereferences them."""
+    d = _cabi.LpStepDesc()
+    d.n_el, d.rows, d.el_per_row = rows * el_per_row, rows, el_per_row
+    d.phases = _cabi.LP_PH_REPLACE | _cabi.LP_PH_EMIT | _cabi.LP_PH_COEFFS
+    d.flags = _cabi.LP_FL_MASK_BITS
+    d.replace_kind, d.rng_kind = _cabi.LP_REPLACE_VE, _cabi.LP_RNG_PHILOX
+    base = 1 << 32
+    for k, f in enumerate(("mask", "x_t", "x", "noise", "y", "x_in", "coef_out", "t_abt", "t_ve", "t_rsig")):
+        setattr(d, f, base + (k << 20))
+    return d
+
+
+def test_replace_rewrite_refuses_a_binding_of_another_kernel(hip_lib):
+    """lp_replay_call with a binding: the rewrite of node 0 is refused unless the replace descriptor dispatches to exactly the
+    bound kernel, grid and block -- before any HIP call, and whatever the binding's reserved word holds (a hand-filled binding
+    with 0 there used to skip the check)."""
+    import ctypes as C
+    d = _replace_desc()
+    for reserved in (0, 0x1234567):
+        b = _cabi.LpGraphBinding()
+        b.node, b.func, b.reserved0 = 0x1000, 0xBAD0, reserved
+        b.grid[0], b.grid[1], b.grid[2] = 8, 2, 1
+        b.block[0], b.block[1], b.block[2] = 256, 1, 1
+        call = _cabi.LpCallDesc()
+        call.replace, call.graph_exec, call.replace_binding = C.pointer(d), 0x2000, C.pointer(b)
+        assert hip_lib.lp_replay_call(C.byref(call), None) == _cabi.LP_E_INVALID
+
+
+def test_clone_sigma_root_returns_the_dispatch_refusal_before_touching_the_graph(hip_lib):
+    import ctypes as C
+    g, e, b = C.c_void_p(), C.c_void_p(), _cabi.LpGraphBinding()
+    d = _replace_desc(rows=70000, el_per_row=1)          # more rows than a grid holds: lp_step says LP_E_UNSUPPORTED
+    d.phases |= _cabi.LP_PH_SIGMA
+    d.sg_sigma, d.sg_schedule, d.sg_schedule_len, d.sg_scalars_out = 0x3000, 0x4000, 8, 0x5000
+    assert hip_lib.lp_graph_clone_sigma_root(C.c_void_p(1), C.byref(d), C.byref(g), C.byref(e), C.byref(b)) == \
+        _cabi.LP_E_UNSUPPORTED
+    d = _replace_desc()
+    d.phases |= _cabi.LP_PH_SIGMA
+    d.sg_sigma, d.sg_schedule, d.sg_schedule_len, d.sg_scalars_out = 0x3000, 0x4000, 0, 0x5000   # an empty schedule
+    assert hip_lib.lp_graph_clone_sigma_root(C.c_void_p(1), C.byref(d), C.byref(g), C.byref(e), C.byref(b)) == \
+        _cabi.LP_E_INVALID
+    assert g.value is None and e.value is None
+
+
 def test_abi_version_and_strerror(hip_lib):
     assert hip_lib.lp_abi_version() == _cabi.ABI_VERSION
     assert hip_lib.lp_strerror(0) == b"ok"

@@ -426,3 +426,54 @@ print(json.dumps({"graphs": [d[0] for d in done], "finite": all(d[1] for d in do
     assert p.returncode == 0, p.stderr[-3000:]
     rec = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][-1])
     assert rec["graphs"] == [1] * 12 and rec["finite"] and rec["gc_enabled_after"], rec
+
+
+def test_a_bound_rewrite_for_another_kernel_is_refused_and_the_capture_still_replays():
+    """lp_replay_call rewrites node 0 of a captured call only with a descriptor that dispatches to exactly the captured kernel
+    and grid.  A latent above 512 Ki elements takes the 16-byte kernels (VEC = 4); the same descriptor with `x` 4 bytes off
+    that alignment dispatches to the one-element kernel and must be refused (LP_E_INVALID) with nothing run: `out`, `x`, the
+    generator and the misaligned buffer as they were.  (The view stays inside an allocation of n_el + 4 floats, so even a
+    rewrite that went through could not touch memory outside it.)  The capture then replays as before, equal to eager launches."""
+    import torch
+    from lanpaint_amd import LanPaint, _cabi
+    shape, s0 = (1, 4, 384, 384), 1.5
+    n_el = int(np.prod(shape))
+    g = torch.Generator(device="cpu").manual_seed(11)
+    y, noise = torch.randn(shape, generator=g).to(DEV), torch.randn(shape, generator=g).to(DEV)
+    mask = (torch.rand(shape, generator=g) > 0.5).float().to(DEV)
+    s = torch.full((1,), s0, device=DEV)
+    times = (s, 1 / (1 + s ** 2), s / (1 + s))
+    x_src = [(y + noise * s0 + 0.01 * k).contiguous() for k in range(2)]
+
+    def run(graph, probe):
+        torch.manual_seed(7)
+        eng = LanPaint(_Model(False), 3, 15.0, 5.0, 1.0, 0.2, rng="torch", graph=graph)
+        xs = [t.clone() for t in x_src]
+        out0 = eng(xs[0], y, noise, s, mask, times, None, 0)
+        if probe:
+            probe(eng, xs[0], out0)
+        out1 = eng(xs[1], y, noise, s, mask, times, None, 0)
+        torch.cuda.synchronize()
+        return [_np(t) for t in (out0, xs[0], out1, xs[1])]
+
+    def refuse(eng, x, out):
+        cap = next(iter(eng._graphs.values()))
+        assert cap.binding is not None and cap.call is not None
+        assert tuple(cap.binding.grid) == (n_el // (4 * 256), 1, 1)          # the 16-byte kernel: four elements per lane
+        torch.cuda.synchronize()
+        buf = torch.zeros(n_el + 4, device=DEV)
+        d = _cabi.LpStepDesc.from_buffer_copy(cap.k0_desc)
+        d.x = buf.data_ptr() + 4
+        call = _cabi.LpCallDesc.from_buffer_copy(cap.call)
+        call.hyper, call.replace = None, ctypes.pointer(d)
+        before = [_np(t) for t in (out, x)]
+        off = torch.cuda.default_generators[0].get_offset()
+        assert eng._lib.lp_replay_call(ctypes.byref(call), eng._stream(x.device)) == _cabi.LP_E_INVALID
+        torch.cuda.synchronize()
+        for a, b in zip(before, [_np(t) for t in (out, x)]):
+            np.testing.assert_array_equal(a, b)
+        assert torch.cuda.default_generators[0].get_offset() == off and not bool(buf.any())
+
+    eager, replayed = run(False, None), run(True, refuse)
+    for a, b in zip(eager, replayed):
+        np.testing.assert_array_equal(a, b)
