@@ -385,6 +385,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((ES == 2 &&
     // half-width backbone outputs (and a half-width x_in) of a streaming launch travel 16 bytes per lane PAIR (lp_common.h)
     constexpr bool PAIR = X0W == 2 && VEC == 4 && !ST;
     static_assert(!PAIR || ES == 0, "pair accesses: every lane that has not left the kernel is active");
+    // TBL (the phase-specialised LP_PH_COEFFS launches at the latency-bound sizes): block x = 0 of every row is the table
+    // block (below), the element blocks are x = 1 .. gridDim.x - 1 (plan_kernel adds the block).  At 16 bytes per lane the
+    // launch streams for many microseconds and the table wave is one of thousands: those kernels keep the in-block table.
+    constexpr bool TBL = (PH & LP_PH_COEFFS) != 0 && VEC == 1;
+    const unsigned el_bx = blockIdx.x - (TBL ? 1u : 0u);
+    static_assert(!TBL || (!ST && !ES && (PH & LP_PH_REPLACE) != 0), "table block: the fused replace launches only");
     LP_CLK_DECL
     lp_step_desc d = d_arg;
     d.x_t = static_cast<float*>(a0); d.C = static_cast<float*>(a1);
@@ -529,45 +535,77 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((ES == 2 &&
     bool av_mixed = false;          // LP_FL_AV: the wave straddles the video / audio seam of its row
     uint32_t av_nib = 0u;           // LP_FL_AV: this lane's indicator bits (VEC of them)
     const bool fold_coeffs = (ph & LP_PH_COEFFS) != 0;       // compile-time for PH != 0
-    if (fold_coeffs) {
-        // lp_coeffs folded into the replace launch: every block derives the two row scalars its own work needs
-        // (same expressions as the table's), lanes 0..3 of the row's first block build the table for the
-        // launches that follow
-        float abt_f, ve_f, rs_f, tm_sig = 0.0f;
-        constexpr bool fold_sigma = (PH & LP_PH_SIGMA) != 0;
+    constexpr bool fold_sigma = (PH & LP_PH_SIGMA) != 0;
+    static_assert(!fold_sigma || PH != 0, "LP_PH_SIGMA: the phase-specialised kernels only");
+    // the row's times: LP_PH_SIGMA straight from sigma (what lp_sigma_times would have written to t_ve / t_abt / t_model;
+    // the replace sigma IS sigma), otherwise from the time tensors
+    auto row_times = [&](float& abt_f, float& ve_f, float& rs_f, float& tm_f) __attribute__((always_inline)) {
         if constexpr (fold_sigma) {
-            // LP_PH_SIGMA: the times of this row straight from sigma (what lp_sigma_times would have written to t_ve / t_abt /
-            // t_model; the replace sigma IS sigma); the first wave of the first block also does that kernel's part --
-            // the rule's two scalars, the rule against the speculated count, the mailbox
             float ft;
             rs_f = d.sg_sigma[row];
             sigma_to_times(rs_f, flow, ve_f, abt_f, ft);
-            tm_sig = flow ? ft : ve_f;
-            if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x < kWave) {      // (the block's first wave, all 64 lanes alive here)
-                const SigmaRule rule{d.sg_n_steps, d.sg_early_stop, d.sg_total_steps, d.sg_guess, d.sg_min_step_frac, d.sg_valid_out};
-                sigma_rows_and_rule(d.sg_sigma, d.rows, d.sg_schedule, d.sg_schedule_len, flow, d.sg_times_out, d.sg_scalars_out,
-                                    d.sg_seq_out, d.sg_seq, rule);
-            }
+            tm_f = flow ? ft : ve_f;
         } else {
             abt_f = d.t_abt[static_cast<int64_t>(row) * d.t_abt_stride];
             ve_f = d.t_ve ? d.t_ve[static_cast<int64_t>(row) * d.t_ve_stride] : 0.0f;
             rs_f = d.t_rsig ? d.t_rsig[static_cast<int64_t>(row) * d.t_rsig_stride] : 0.0f;
+            tm_f = 0.0f;
         }
-        rc.scale = row_scale(flow, abt_f, ve_f);
-        rc.rscale = 1.0f / rc.scale;        // (what the table's LP_C_RSCALE holds: the emit of this launch divides by it, see EMIT)
-        rc.rsigma = rs_f;
-        if (blockIdx.x == 0 && threadIdx.x < 4) {
-            lp_hyper h;
-            h.lambda = d.lambda; h.beta = d.beta; h.step_size = d.step_size; h.min_step_frac = d.min_step_frac;
-            h.is_flow = flow ? 1 : 0; h.one_plus_lambda = d.one_plus_lambda;
-            const float tm_f = fold_sigma ? tm_sig : (d.t_model ? d.t_model[static_cast<int64_t>(row) * d.t_model_stride] : 0.0f);
-            const float step = d.step_size * fmaxf(1.0f - abt_f, d.min_step_frac);                 // lanpaint.py:81
-            coeffs_lane(h, abt_f, ve_f, rs_f, tm_f, step, (threadIdx.x >> 1) & 1, threadIdx.x & 1,
-                        d.coef_out + static_cast<int64_t>(row) * LP_COEF_STRIDE);
-            if (row == 0 && threadIdx.x == 0 && d.rng_state_out) {     // generator state for the replayed launches
-                d.rng_state_out[0] = d.rng_state_val[0];
-                d.rng_state_out[1] = d.rng_state_val[1];
+    };
+    if (fold_coeffs) {
+        // lp_coeffs folded into the replace launch: every block derives the row scalars its own work needs (same
+        // expressions as the table's); lanes 0..3 of one block per row build the table for the launches that follow.
+        // TBL: that block is an extra block (0, row) that does no element work.  Its first wave builds the table (fp64)
+        // and publishes the generator state, its second wave runs the sigma rule, both while the element blocks stream.
+        // (Until round 9 the first wave of element block 0 did all of it in front of its own loads and was the last wave
+        // of the launch to finish: 2.08 us on the chip at C2 against 0.92 for the other blocks.)
+        auto build_table = [&](float abt_f, float ve_f, float rs_f, float tm_sig) __attribute__((always_inline)) {
+            if (threadIdx.x < 4) {
+                lp_hyper h;
+                h.lambda = d.lambda; h.beta = d.beta; h.step_size = d.step_size; h.min_step_frac = d.min_step_frac;
+                h.is_flow = flow ? 1 : 0; h.one_plus_lambda = d.one_plus_lambda;
+                const float tm_f = fold_sigma ? tm_sig : (d.t_model ? d.t_model[static_cast<int64_t>(row) * d.t_model_stride] : 0.0f);
+                const float step = d.step_size * fmaxf(1.0f - abt_f, d.min_step_frac);                 // lanpaint.py:81
+                coeffs_lane(h, abt_f, ve_f, rs_f, tm_f, step, (threadIdx.x >> 1) & 1, threadIdx.x & 1,
+                            d.coef_out + static_cast<int64_t>(row) * LP_COEF_STRIDE);
+                if (row == 0 && threadIdx.x == 0 && d.rng_state_out) {     // generator state for the replayed launches
+                    d.rng_state_out[0] = d.rng_state_val[0];
+                    d.rng_state_out[1] = d.rng_state_val[1];
+                }
             }
+        };
+        // what lp_sigma_times_mailbox does besides the times: the rule's two scalars, the rule against the speculated count,
+        // the mailbox (one full wave: all 64 lanes alive)
+        auto sigma_rule = [&]() __attribute__((always_inline)) {
+            const SigmaRule rule{d.sg_n_steps, d.sg_early_stop, d.sg_total_steps, d.sg_guess, d.sg_min_step_frac, d.sg_valid_out};
+            sigma_rows_and_rule(d.sg_sigma, d.rows, d.sg_schedule, d.sg_schedule_len, flow, d.sg_times_out,
+                                d.sg_scalars_out, d.sg_seq_out, d.sg_seq, rule);
+        };
+        if constexpr (TBL) {
+            if (blockIdx.x == 0) {                       // the table block
+                if (threadIdx.x < kWave) {
+                    float abt_f, ve_f, rs_f, tm_f;
+                    row_times(abt_f, ve_f, rs_f, tm_f);
+                    build_table(abt_f, ve_f, rs_f, tm_f);
+                    LP_CLK(5)
+                } else if (fold_sigma && blockIdx.y == 0 && threadIdx.x < 2 * kWave) {
+                    sigma_rule();
+                }
+                LP_CLK(6)
+                LP_CLK_FLUSH
+                return;
+            }
+            // (an element block forms its row scalars once its operand loads are in flight, below)
+        } else {
+            float abt_f, ve_f, rs_f, tm_f;
+            row_times(abt_f, ve_f, rs_f, tm_f);
+            if constexpr (fold_sigma) {
+                if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x < kWave) sigma_rule();       // (the block's first wave)
+            }
+            if (blockIdx.x == 0) build_table(abt_f, ve_f, rs_f, tm_f);
+            rc.scale = row_scale(flow, abt_f, ve_f);
+            rc.rscale = 1.0f / rc.scale;        // (what the table's LP_C_RSCALE holds: the emit of this launch divides by it, see EMIT)
+            rc.rsigma = rs_f;
         }
     } else {
         if constexpr (PH == 0) {
@@ -617,7 +655,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((ES == 2 &&
     // one group per lane and no grid-stride loop: the launch covers the row (see launch()), which keeps every
     // address in this straight-line body a kernarg pointer + one offset and lets the scalar loads (coefficient
     // row, replayed-graph RNG counter) fly together with the vector loads instead of ahead of a loop
-    const int64_t g_raw = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
+    const int64_t g_raw = static_cast<int64_t>(el_bx) * kBlock + threadIdx.x;
     // ST (round 5): the block is 256 ATen threads -- [256 b, 256 b + 256) of the generator's launch -- whose values fall on FOUR
     // runs of 256 consecutive elements, bg apart (slot k of thread j: element base + k bg + 256 b + j).  Wave w of the block
     // takes run w, 16 bytes per lane like every other streaming launch; the values reach it through LDS (below).
@@ -936,18 +974,27 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((ES == 2 &&
             }
         }
         // per-call I/O pointers for the launches of this sigma call that live in a captured graph (lp_finalize)
-        if (d.io_table_out && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) {
+        if (d.io_table_out && el_bx == 0 && blockIdx.y == 0 && threadIdx.x == 0) {
             d.io_table_out[0] = d.io_table_val[0];
             d.io_table_out[1] = d.io_table_val[1];
             if (d.io_valid) d.io_table_out[2] = 1ull;      // (not on a speculated call: there the sigma rule owns the word)
         }
         if constexpr (PH == 0 || (PH & LP_PH_REPLACE) != 0) {
-            if (d.es_reset && d.es && blockIdx.x == 0 && blockIdx.y == 0) {
+            if (d.es_reset && d.es && el_bx == 0 && blockIdx.y == 0) {
                 if (d.es_partials) {                      // every accumulator set starts the call at zero
                     for (int k = threadIdx.x; k < kEsSets * kEsSlots * 8; k += kBlock) d.es_partials[k] = 0.0;
                 }
                 if (threadIdx.x == 0) es_reset_state(d, fold_coeffs);
             }
+        }
+        if constexpr (TBL) {
+            // the row scalars of a TBL element block, read and formed while its operand loads are in flight (read at the top,
+            // the times held the noise and y loads behind one more scalar round trip: s_waitcnt lgkmcnt(0) waits for all)
+            float abt_f, ve_f, rs_f, tm_f;
+            row_times(abt_f, ve_f, rs_f, tm_f);
+            rc.scale = row_scale(flow, abt_f, ve_f);
+            rc.rscale = 1.0f / rc.scale;    // (what the table's LP_C_RSCALE holds: the emit of this launch divides by it, see EMIT)
+            rc.rsigma = rs_f;
         }
 
         LP_CLK(1)
@@ -1530,6 +1577,7 @@ static void plan_kernel(const lp_step_desc& d, StepPlan* p) {
     // <= 2048 blocks anyway.  (el_per_row < 2^31 and rng_bg < 2^32: bx < 2^24.)
     int64_t bx = (groups + kBlock - 1) / kBlock;
     if (bx < 1) bx = 1;
+    if constexpr ((PH & LP_PH_COEFFS) != 0 && VEC == 1) bx += 1;     // the table block of every row (lp_step_kernel, TBL)
     const unsigned gy = ST ? st_segments(d) : static_cast<unsigned>(d.rows);       // ST: (round, row) pairs, see the kernel head
     *p = StepPlan{reinterpret_cast<const void*>(&lp_step_kernel<VEC, MODE, PH, X0W, RNG, ST, ES>), dim3(static_cast<unsigned>(bx), gy),
                   PH, VEC, false, 0, MODE, X0W, RNG, ES, ST};
