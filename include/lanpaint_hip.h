@@ -43,7 +43,7 @@
 extern "C" {
 #endif
 
-#define LP_ABI_VERSION 23
+#define LP_ABI_VERSION 24
 
 /* The library is built with -fvisibility=hidden: the entry points declared LP_API below are its ONLY dynamic symbols (the
  * dispatch functions, kernel handles and device stubs of the C++ side stay internal; tests/test_cabi_exports.py checks
@@ -746,6 +746,63 @@ typedef struct lp_audio_desc {
     void*        workspace;
 } lp_audio_desc;
 LP_API int lp_audio_merge(const lp_audio_desc* desc, void* stream);
+
+/* ---- Detailer crop / stitch (beyond the reference: its README lists "Detailer" as its open item) --------------------------
+ * Inpaint at the resolution of the masked region: find the mask's bounding box, cut a window out of the NHWC image and
+ * resample it to a working size, and after sampling resample the result back and blend it into the original through the
+ * MaskBlend-smoothed mask.  The host (lanpaint_amd/detail.py) plans the window from the four bbox integers and builds the tap
+ * tables; the device does every per-pixel pass.  Sides are 1..LP_DETAIL_MAX_SIDE, channels 1..LP_DETAIL_MAX_CHANNELS.    */
+#define LP_DETAIL_MAX_SIDE     32768
+#define LP_DETAIL_MAX_CHANNELS 64
+
+/* Bounding box of mask > 0.5 over every plane.
+ *   mask  [planes, height, width] fp32
+ *   bbox  out, device, 4 x int32 {row_min, row_max, col_min, col_max}, inclusive; {height, -1, width, -1} when no element is
+ *         set.  Initialised by this call.  Integer atomics only: the result does not depend on the order of arrival.
+ * LP_E_INVALID: null pointer, planes <= 0, a side outside 1..LP_DETAIL_MAX_SIDE; LP_E_UNSUPPORTED: planes > 65535.          */
+LP_API int lp_mask_bbox(const float* mask, int32_t planes, int32_t height, int32_t width, int32_t* bbox, void* stream);
+
+/* Window [y0, y0 + win_h) x [x0, x0 + win_w) of src [batch, src_h, src_w, channels] -> dst [batch, out_h, out_w, channels],
+ * separable, from the caller's tables: per axis bounds [out, 2] int32 = (first tap relative to the window, tap count) and
+ * weights [out, ksize] fp32.  With the tables of torch's antialias rule (detail.aa_coeffs) this is
+ * F.interpolate(window, size, mode, align_corners=False, antialias=True); the window's edges are edges, no tap reads outside
+ * it (entries are clamped to the window).  Horizontal pass, then vertical, fp32 sums with the taps in ascending order.  Same
+ * size in and out copies the window bit for bit and reads no table (the table pointers may be NULL).
+ * LP_E_INVALID: null pointer, non-positive size, a side or channel count past the limits, the window outside the image,
+ * ksize <= 0; LP_E_ALIGN: dst not 16-byte aligned; LP_E_UNSUPPORTED: batch > 65535.                                         */
+typedef struct lp_detail_resample_desc {
+    int32_t batch, src_h, src_w, channels;
+    int32_t y0, x0, win_h, win_w;
+    int32_t out_h, out_w, ksize_x, ksize_y;
+    const float*   src;
+    const int32_t* bounds_x;
+    const float*   weights_x;
+    const int32_t* bounds_y;
+    const float*   weights_y;
+    float*         dst;
+} lp_detail_resample_desc;
+LP_API int lp_detail_resample(const lp_detail_resample_desc* desc, void* stream);
+
+/* Stitch a detailed window back:  with m = conv2d(max_pool2d(mask, k, 1, k/2), gaussian_kernel_2d(k), pad k/2) over the WHOLE
+ * image (lp_mask_blend's smoothed mask),
+ *   out = original * (1 - m) + detail * m     inside the window (the arithmetic of lp_mask_blend),
+ *   out = original, bit for bit               outside it.
+ * Two launches: a streaming copy original -> out, then the window's tiles, each with its mask halo in LDS.  No full-frame
+ * temporary; out must not be original.  k odd, 1..51.
+ *   mask [mask_batch, height, width], mask_batch 1 or batch; original, out [batch, height, width, channels];
+ *   detail [batch, win_h, win_w, channels] (already at the window's size: lp_detail_resample brings it there).
+ * LP_E_INVALID: null pointer, out == original, non-positive size, limits, the window outside the image, k even or outside
+ * 1..51, mask_batch; LP_E_UNSUPPORTED: batch > 65535.                                                                      */
+typedef struct lp_detail_stitch_desc {
+    int32_t batch, height, width, channels;
+    int32_t y0, x0, win_h, win_w;
+    int32_t k, mask_batch;
+    const float* mask;
+    const float* original;
+    const float* detail;
+    float*       out;
+} lp_detail_stitch_desc;
+LP_API int lp_detail_stitch(const lp_detail_stitch_desc* desc, void* stream);
 
 #ifdef __cplusplus
 }

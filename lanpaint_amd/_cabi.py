@@ -13,7 +13,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_NAME = "liblanpaint_hip.so"
 LIB_PATH = os.path.join(_HERE, LIB_NAME)
-ABI_VERSION = 23
+ABI_VERSION = 24
 
 # --- constants mirrored from include/lanpaint_hip.h -------------------------------
 LP_OK, LP_E_INVALID, LP_E_UNSUPPORTED, LP_E_LAUNCH, LP_E_ALIGN = 0, -1, -2, -3, -4
@@ -169,6 +169,24 @@ class LpAudioDesc(C.Structure):
                 ("out", C.c_void_p), ("workspace", C.c_void_p)]
 
 
+LP_DETAIL_MAX_SIDE, LP_DETAIL_MAX_CHANNELS = 32768, 64
+
+
+class LpDetailResampleDesc(C.Structure):
+    _fields_ = [("batch", C.c_int32), ("src_h", C.c_int32), ("src_w", C.c_int32), ("channels", C.c_int32),
+                ("y0", C.c_int32), ("x0", C.c_int32), ("win_h", C.c_int32), ("win_w", C.c_int32),
+                ("out_h", C.c_int32), ("out_w", C.c_int32), ("ksize_x", C.c_int32), ("ksize_y", C.c_int32),
+                ("src", C.c_void_p), ("bounds_x", C.c_void_p), ("weights_x", C.c_void_p), ("bounds_y", C.c_void_p),
+                ("weights_y", C.c_void_p), ("dst", C.c_void_p)]
+
+
+class LpDetailStitchDesc(C.Structure):
+    _fields_ = [("batch", C.c_int32), ("height", C.c_int32), ("width", C.c_int32), ("channels", C.c_int32),
+                ("y0", C.c_int32), ("x0", C.c_int32), ("win_h", C.c_int32), ("win_w", C.c_int32),
+                ("k", C.c_int32), ("mask_batch", C.c_int32),
+                ("mask", C.c_void_p), ("original", C.c_void_p), ("detail", C.c_void_p), ("out", C.c_void_p)]
+
+
 def lp_audio_ws_bytes(mask_len):
     """LP_AUDIO_WS_BYTES of include/lanpaint_hip.h."""
     return 12 * (int(mask_len) + 1)
@@ -212,6 +230,9 @@ EXPORTS = {
     "lp_vmask_morph": (C.c_int, [C.POINTER(LpVmaskMorphDesc), C.c_void_p]),
     "lp_vmask_resize": (C.c_int, [C.POINTER(LpVmaskResizeDesc), C.c_void_p]),
     "lp_audio_merge": (C.c_int, [C.POINTER(LpAudioDesc), C.c_void_p]),
+    "lp_mask_bbox": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    "lp_detail_resample": (C.c_int, [C.POINTER(LpDetailResampleDesc), C.c_void_p]),
+    "lp_detail_stitch": (C.c_int, [C.POINTER(LpDetailStitchDesc), C.c_void_p]),
 }
 
 

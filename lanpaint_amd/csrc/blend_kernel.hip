@@ -3,85 +3,30 @@
 // nodes.py:610-638), merge_video_with_mask (nodes.py:1060-1088) and gaussian_kernel_2d (:1049-1057).
 //
 // A block owns a TH x TW tile of one image.  The mask tile plus a 2R halo (R = k/2: R for the
-// dilation, R for the blur) is staged in LDS once; four separable passes run entirely in LDS
-//   A (raw, -inf outside the image)  --row max-->  B  --col max, 0 outside the image-->  C
-//   C  --row blur-->  D  --col blur--> m (registers)  --> out = image1*(1-m) + image2*m
-// The reference's 2-D kernel exp(-(x^2+y^2)/(2 s^2))/sum is exactly the outer product of the
-// normalised 1-D profile, so the separable form differs from conv2d only in summation order.
+// dilation, R for the blur) is staged in LDS once and smoothed there by the separable passes of
+// mask_tile.h (shared with lp_detail_stitch); then
+//   D  --col blur--> m (registers)  --> out = image1*(1-m) + image2*m
 #include "lp_common.h"
+#include "mask_tile.h"
 
 namespace lp {
 
 template <int TH, int TW>
 __global__ __launch_bounds__(256) void lp_mask_blend_kernel(const lp_blend_desc d) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
-    const int k = d.k, R = k / 2;
-    const int AW = TW + 4 * R, AH = TH + 4 * R, BW = TW + 2 * R, CH = TH + 2 * R;
-    float* A = lds;                   // AH x AW raw mask; later C: CH x BW dilated
-    float* B = A + AH * AW;           // AH x BW row-max;  later D: CH x TW row-blurred
-    float* g = B + AH * BW;           // k normalised 1-D Gaussian weights
+    const int k = d.k;
     const int tid = threadIdx.x;
     const int x0 = blockIdx.x * TW, y0 = blockIdx.y * TH, b = blockIdx.z;
     const int H = d.height, W = d.width;
-
-    if (tid < k) {                    // gaussian_kernel_2d: sigma = (k-1)/4; identity for k <= 1
-        float w = 1.0f;
-        if (k > 1) {
-            const float sigma = static_cast<float>(k - 1) / 4.0f, inv = 1.0f / (2.0f * sigma * sigma);
-            float sum = 0.0f;
-            for (int j = 0; j < k; ++j) sum += expf(-static_cast<float>((j - R) * (j - R)) * inv);
-            w = expf(-static_cast<float>((tid - R) * (tid - R)) * inv) / sum;
-        }
-        g[tid] = w;
-    }
-    const bool resample = d.mask_h != H || d.mask_w != W;
     const float* mplane = d.mask + static_cast<int64_t>(d.mask_batch == 1 ? 0 : b) * d.mask_h * d.mask_w;
-    for (int idx = tid; idx < AH * AW; idx += 256) {
-        const int ay = idx / AW, ax = idx - ay * AW;
-        const int y = y0 - 2 * R + ay, x = x0 - 2 * R + ax;
-        float v = -INFINITY;                                   // max_pool2d pads with -inf
-        if (y >= 0 && y < H && x >= 0 && x < W) {
-            const int sy = resample ? nearest_exact_index(y, d.mask_h, H, d.nn_rule) : y;
-            const int sx = resample ? nearest_exact_index(x, d.mask_w, W, d.nn_rule) : x;
-            v = mplane[static_cast<int64_t>(sy) * d.mask_w + sx];
-        }
-        A[idx] = v;
-    }
-    __syncthreads();
-    for (int idx = tid; idx < AH * BW; idx += 256) {           // row max over the k-wide window
-        const int ay = idx / BW, bx = idx - ay * BW;
-        const float* row = A + ay * AW + bx;
-        float v = row[0];
-        for (int j = 1; j < k; ++j) v = fmaxf(v, row[j]);
-        B[idx] = v;
-    }
-    __syncthreads();
-    for (int idx = tid; idx < CH * BW; idx += 256) {           // column max; conv2d pads with ZERO
-        const int cy = idx / BW, bx = idx - cy * BW;
-        const int y = y0 - R + cy, x = x0 - R + bx;
-        float v = 0.0f;
-        if (y >= 0 && y < H && x >= 0 && x < W) {
-            v = B[cy * BW + bx];
-            for (int j = 1; j < k; ++j) v = fmaxf(v, B[(cy + j) * BW + bx]);
-        }
-        A[idx] = v;                                            // C
-    }
-    __syncthreads();
-    for (int idx = tid; idx < CH * TW; idx += 256) {           // row blur
-        const int cy = idx / TW, tx = idx - cy * TW;
-        const float* row = A + cy * BW + tx;
-        float v = 0.0f;
-        for (int j = 0; j < k; ++j) v += g[j] * row[j];
-        B[idx] = v;                                            // D
-    }
-    __syncthreads();
+    float *D, *g;
+    mask_tile_passes<TH, TW>(lds, mplane, d.mask_h, d.mask_w, d.nn_rule, k, x0, y0, H, W, D, g);
     const int C = d.channels;
     for (int idx = tid; idx < TH * TW; idx += 256) {           // column blur + blend
         const int ty = idx / TW, tx = idx - ty * TW;
         const int y = y0 + ty, x = x0 + tx;
         if (y >= H || x >= W) continue;
-        float m = 0.0f;
-        for (int j = 0; j < k; ++j) m += g[j] * B[(ty + j) * TW + tx];
+        const float m = smoothed_mask_at<TW>(D, g, k, ty, tx);
         const int64_t pix = (static_cast<int64_t>(b) * H + y) * W + x;
         if (d.smooth_out) d.smooth_out[pix] = m;
         if (d.out) {
@@ -95,9 +40,7 @@ __global__ __launch_bounds__(256) void lp_mask_blend_kernel(const lp_blend_desc 
 
 template <int TH, int TW>
 static hipError_t launch_blend(const lp_blend_desc& d, hipStream_t stream) {
-    const int R = d.k / 2;
-    const size_t lds = sizeof(float) * (static_cast<size_t>(TH + 4 * R) * (TW + 4 * R) +
-                                        static_cast<size_t>(TH + 4 * R) * (TW + 2 * R) + d.k);
+    const size_t lds = mask_tile_lds_bytes<TH, TW>(d.k);
     // above the default 64 KiB cap the dynamic-LDS limit has to be raised (160 KiB per CU on gfx950).  The attribute is
     // per DEVICE, so it is set on whatever device this launch goes to -- no process-wide "done" flag (the library
     // keeps no state; a second GPU of the same process would otherwise fail to launch)

@@ -34,6 +34,9 @@ int vmask_edt_dispatch(const lp_vmask_edt_desc* d, hipStream_t stream);
 int vmask_morph_dispatch(const lp_vmask_morph_desc* d, hipStream_t stream);
 int vmask_resize_dispatch(const lp_vmask_resize_desc* d, hipStream_t stream);
 int audio_merge_dispatch(const lp_audio_desc* d, hipStream_t stream);
+int mask_bbox_dispatch(const float* mask, int planes, int H, int W, int32_t* bbox, hipStream_t stream);
+int detail_resample_dispatch(const lp_detail_resample_desc* d, hipStream_t stream);
+int detail_stitch_dispatch(const lp_detail_stitch_desc* d, hipStream_t stream);
 int reshape_mask_dispatch(const float* src, int sb, int sc, int sf, int sh, int sw, float* dst, int db, int dc, int df,
                           int dh, int dw, int taps, int flags, hipStream_t stream);
 }  // namespace lp
@@ -94,6 +97,14 @@ int lp_vmask_morph(const lp_vmask_morph_desc* desc, void* stream) { return lp::v
 int lp_vmask_resize(const lp_vmask_resize_desc* desc, void* stream) { return lp::vmask_resize_dispatch(desc, as_stream(stream)); }
 
 int lp_audio_merge(const lp_audio_desc* desc, void* stream) { return lp::audio_merge_dispatch(desc, as_stream(stream)); }
+
+int lp_mask_bbox(const float* mask, int32_t planes, int32_t height, int32_t width, int32_t* bbox, void* stream) {
+    return lp::mask_bbox_dispatch(mask, planes, height, width, bbox, as_stream(stream));
+}
+
+int lp_detail_resample(const lp_detail_resample_desc* desc, void* stream) { return lp::detail_resample_dispatch(desc, as_stream(stream)); }
+
+int lp_detail_stitch(const lp_detail_stitch_desc* desc, void* stream) { return lp::detail_stitch_dispatch(desc, as_stream(stream)); }
 
 
 int lp_finalize(const lp_final_desc* desc, void* stream) { return lp::finalize_dispatch(desc, as_stream(stream)); }

@@ -1,0 +1,326 @@
+// detail_kernel.hip -- Detailer crop / stitch for gfx950: inpaint at the resolution of the masked region.  Pixel space, once
+// per job, around the sampler (lanpaint_amd/detail.py plans the region on the host).  Three jobs on the caller's stream:
+//
+//   lp_mask_bbox        rows / columns of mask > 0.5 over every plane: per wave a __ballot per column slot and an OR of row
+//                       bits, per block one integer atomicMin / atomicMax per bound.  Integer-exact, order-free.
+//   lp_detail_resample  a window of an NHWC image to another size with torch's antialiased bilinear / bicubic rule, from
+//                       host-built fp32 tap tables.  Both passes in one launch: a block stages the horizontal pass of the
+//                       source rows its output tile needs in LDS, then the vertical pass writes 16 B per lane.  Rows are
+//                       indexed as flat fp32 streams of W * C elements, so reads and writes coalesce whatever C is.
+//                       Same size in and out is a plain window copy (bitwise).
+//   lp_detail_stitch    out = original outside the region (one streaming copy), original * (1 - m) + detail * m inside, m the
+//                       MaskBlend-smoothed mask of the WHOLE image evaluated on the region's tiles (mask_tile.h, shared with
+//                       lp_mask_blend).  No full-frame temporary; per-pixel work only over the region plus its halo.
+#include "lp_common.h"
+#include "mask_tile.h"
+
+namespace lp {
+namespace {
+
+constexpr int kBboxRows = 16;       // bbox tile: 16 rows x (256 lanes x V columns)
+constexpr int kRsTX = 256;          // resample tile: 64 lanes x 4 flat elements of the output row ...
+constexpr int kRsTY = 16;           // ... by 16 output rows, 4 waves of 4 rows each
+constexpr int kRsCR = 32;           // source rows staged in LDS per chunk (32 KiB)
+constexpr int kCopyBlocks = 2048;   // streaming copy: grid-stride, 8 blocks per CU
+
+// ---- bounding box -------------------------------------------------------------------------------------------------------
+__global__ void lp_detail_bbox_init_kernel(int32_t* __restrict__ bbox, int H, int W) {
+    const int t = threadIdx.x;
+    if (t < 4) bbox[t] = (t == 0) ? H : (t == 2) ? W : -1;
+}
+
+// Lane l of the block reads columns x .. x + V - 1 of 16 rows of one plane (V = 4: one 16 B load per row).  rowbits: the rows
+// of the tile this lane saw set; hit[j]: whether column slot j was set in any row.
+template <int V>
+__global__ __launch_bounds__(256) void lp_detail_bbox_kernel(const float* __restrict__ mask, int32_t* __restrict__ bbox, int H,
+                                                             int W) {
+    __shared__ int32_t part[4][4];
+    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
+    const int x = (blockIdx.x * 256 + threadIdx.x) * V, y0 = blockIdx.y * kBboxRows;
+    const float* plane = mask + static_cast<int64_t>(blockIdx.z) * H * W;
+    uint32_t rowbits = 0;
+    bool hit[V];
+#pragma unroll
+    for (int j = 0; j < V; ++j) hit[j] = false;
+    if (x < W) {
+#pragma unroll
+        for (int r = 0; r < kBboxRows; ++r) {
+            if (y0 + r >= H) break;
+            const float* p = plane + static_cast<int64_t>(y0 + r) * W + x;
+            float v[V];
+            if constexpr (V == 4) {                            // W % 4 == 0 and a 16 B aligned base: x + 3 < W
+                const float4 q = *reinterpret_cast<const float4*>(p);
+                v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
+            } else {
+                v[0] = p[0];
+            }
+            bool any = false;
+#pragma unroll
+            for (int j = 0; j < V; ++j) {
+                const bool s = v[j] > 0.5f;
+                hit[j] |= s;
+                any |= s;
+            }
+            rowbits |= any ? (1u << r) : 0u;
+        }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) rowbits |= __shfl_xor(rowbits, off);
+    int cmin = W, cmax = -1;
+    const int wx = (blockIdx.x * 256 + wave * kWave) * V;      // first column of this wave
+#pragma unroll
+    for (int j = 0; j < V; ++j) {
+        const unsigned long long bal = __ballot(hit[j]);
+        if (bal) {
+            cmin = min(cmin, wx + __builtin_ctzll(bal) * V + j);
+            cmax = max(cmax, wx + (63 - __builtin_clzll(bal)) * V + j);
+        }
+    }
+    if (lane == 0) {
+        part[wave][0] = rowbits ? y0 + __builtin_ctz(rowbits) : H;
+        part[wave][1] = rowbits ? y0 + 31 - __builtin_clz(rowbits) : -1;
+        part[wave][2] = cmin;
+        part[wave][3] = cmax;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int r0 = H, r1 = -1, c0 = W, c1 = -1;
+#pragma unroll
+        for (int w = 0; w < 4; ++w) {
+            r0 = min(r0, part[w][0]); r1 = max(r1, part[w][1]);
+            c0 = min(c0, part[w][2]); c1 = max(c1, part[w][3]);
+        }
+        if (r1 >= 0) {                                         // one atomic per bound per block; empty tiles send none
+            atomicMin(bbox + 0, r0); atomicMax(bbox + 1, r1);
+            atomicMin(bbox + 2, c0); atomicMax(bbox + 3, c1);
+        }
+    }
+}
+
+// ---- crop + resample ----------------------------------------------------------------------------------------------------
+// A table entry clamped to the window, so a bad table reads nothing outside it.
+__device__ __forceinline__ void tap_window(const int32_t* __restrict__ bounds, int i, int ksize, int in_size, int& first,
+                                           int& count) {
+    first = min(max(bounds[2 * i], 0), in_size - 1);
+    count = min(max(bounds[2 * i + 1], 0), min(ksize, in_size - first));
+}
+
+// One block: output rows [yy0, yy0 + 16) x flat elements [e0, e0 + 256) of the output row (element e = column e / C, channel
+// e % C) of image b.  Lane l of wave w owns elements e0 + 4l .. +3 and output rows yy0 + w + 4r (r < 4).  The window rows
+// those output rows read, [ylo, yhi), go through LDS in chunks of 32: horizontal pass of the chunk (fp32 sums, taps ascending),
+// then each thread adds the chunk's rows that fall in its rows' windows -- chunks ascend, so the vertical taps do too.
+__global__ __launch_bounds__(256) void lp_detail_resample_kernel(const lp_detail_resample_desc d) {
+    __shared__ __attribute__((aligned(16))) float stage[kRsCR][kRsTX];
+    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
+    const int C = d.channels, inH = d.win_h, inW = d.win_w, outH = d.out_h, kx = d.ksize_x, ky = d.ksize_y;
+    const int rowE = d.out_w * C;
+    const int e0 = blockIdx.x * kRsTX + lane * 4, yy0 = blockIdx.y * kRsTY;
+    const int b = blockIdx.z;
+    const int64_t sstride = static_cast<int64_t>(d.src_w) * C;
+    const float* src = d.src + ((static_cast<int64_t>(b) * d.src_h + d.y0) * d.src_w + d.x0) * C;
+
+    int ylo = inH, yhi = 0;                                       // window rows of the whole tile
+    for (int r = 0; r < kRsTY && yy0 + r < outH; ++r) {
+        int b0, b1;
+        tap_window(d.bounds_y, yy0 + r, ky, inH, b0, b1);
+        ylo = min(ylo, b0);
+        yhi = max(yhi, b0 + b1);
+    }
+    int rmin[4], rcnt[4];
+    float acc[4][4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const int yy = yy0 + wave + 4 * r;
+        rmin[r] = 0; rcnt[r] = 0;
+        if (yy < outH) tap_window(d.bounds_y, yy, ky, inH, rmin[r], rcnt[r]);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[r][j] = 0.0f;
+    }
+    int soff[4], ccnt[4], wbase[4];                               // first tap's offset in the window row, taps, table row
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        soff[j] = 0; ccnt[j] = 0; wbase[j] = 0;
+        if (e0 + j < rowE) {
+            const int xx = (e0 + j) / C, c = (e0 + j) - xx * C;
+            int first;
+            tap_window(d.bounds_x, xx, kx, inW, first, ccnt[j]);
+            soff[j] = first * C + c;
+            wbase[j] = xx * kx;
+        }
+    }
+
+    for (int c0 = ylo; c0 < yhi; c0 += kRsCR) {
+        const int rows = min(kRsCR, yhi - c0);
+        for (int rr = wave; rr < rows; rr += 4) {                 // horizontal pass of the chunk
+            const float* srow = src + static_cast<int64_t>(c0 + rr) * sstride;
+            float v[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                float ss = 0.0f;
+                const float* s = srow + soff[j];
+                const float* w = d.weights_x + wbase[j];
+                for (int t = 0; t < ccnt[j]; ++t) ss += s[t * C] * w[t];
+                v[j] = ss;
+            }
+            *reinterpret_cast<float4*>(&stage[rr][lane * 4]) = make_float4(v[0], v[1], v[2], v[3]);
+        }
+        __syncthreads();
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {                            // vertical pass: this chunk's share of each row's sum
+            const int t0 = max(rmin[r], c0), t1 = min(rmin[r] + rcnt[r], c0 + rows);
+            const float* w = d.weights_y + static_cast<int64_t>(yy0 + wave + 4 * r) * ky - rmin[r];
+            for (int t = t0; t < t1; ++t) {
+                const float4 p = *reinterpret_cast<const float4*>(&stage[t - c0][lane * 4]);
+                const float wt = w[t];
+                acc[r][0] += p.x * wt; acc[r][1] += p.y * wt; acc[r][2] += p.z * wt; acc[r][3] += p.w * wt;
+            }
+        }
+        __syncthreads();
+    }
+
+    const bool vec = (rowE & 3) == 0 && e0 + 3 < rowE;           // dst rows then start 16 B aligned (dst is checked)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const int yy = yy0 + wave + 4 * r;
+        if (yy >= outH) continue;
+        float* o = d.dst + (static_cast<int64_t>(b) * outH + yy) * rowE + e0;
+        if (vec) {
+            *reinterpret_cast<float4*>(o) = make_float4(acc[r][0], acc[r][1], acc[r][2], acc[r][3]);
+        } else {
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                if (e0 + j < rowE) o[j] = acc[r][j];
+        }
+    }
+}
+
+// Same size in and out: the window's rows copied as flat streams, one element per lane.
+__global__ __launch_bounds__(256) void lp_detail_crop_kernel(const lp_detail_resample_desc d) {
+    const int C = d.channels, rowE = d.win_w * C;
+    const int e = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y, b = blockIdx.z;
+    if (e >= rowE) return;
+    const float* s = d.src + ((static_cast<int64_t>(b) * d.src_h + d.y0 + y) * d.src_w + d.x0) * C;
+    d.dst[(static_cast<int64_t>(b) * d.win_h + y) * rowE + e] = s[e];
+}
+
+// ---- stitch -------------------------------------------------------------------------------------------------------------
+template <bool VEC>
+__global__ __launch_bounds__(256) void lp_detail_copy_kernel(const float* __restrict__ src, float* __restrict__ dst, int64_t n) {
+    const int64_t stride = static_cast<int64_t>(gridDim.x) * 256;
+    int64_t i = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
+    if constexpr (VEC) {
+        const int64_t n4 = n >> 2;
+        for (int64_t q = i; q < n4; q += stride)
+            reinterpret_cast<float4*>(dst)[q] = reinterpret_cast<const float4*>(src)[q];
+        i += n4 << 2;                                             // the tail, at most 3 elements
+        if (i < n) dst[i] = src[i];
+    } else {
+        for (; i < n; i += stride) dst[i] = src[i];
+    }
+}
+
+// A block owns a TH x TW tile of the REGION of image b; tile origins are image coordinates, so the smoothed mask is the
+// whole image's.  m goes to LDS, then the tile's rows are blended as flat streams of TW * C elements.
+template <int TH, int TW>
+__global__ __launch_bounds__(256) void lp_detail_stitch_kernel(const lp_detail_stitch_desc d) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    const int k = d.k, tid = threadIdx.x;
+    const int x0 = d.x0 + blockIdx.x * TW, y0 = d.y0 + blockIdx.y * TH, b = blockIdx.z;
+    const int H = d.height, W = d.width, C = d.channels;
+    const float* mplane = d.mask + static_cast<int64_t>(d.mask_batch == 1 ? 0 : b) * H * W;
+    float *D, *g;
+    mask_tile_passes<TH, TW>(lds, mplane, H, W, LP_NN_ATEN_SCALAR, k, x0, y0, H, W, D, g);
+    float* M = lds;                                               // the passes' A, free now: TH x TW smoothed mask
+    for (int idx = tid; idx < TH * TW; idx += 256) {
+        const int ty = idx / TW, tx = idx - ty * TW;
+        M[idx] = smoothed_mask_at<TW>(D, g, k, ty, tx);
+    }
+    __syncthreads();
+    const int ty_end = min(TH, d.y0 + d.win_h - y0), tx_end = min(TW, d.x0 + d.win_w - x0);
+    const int rowE = tx_end * C;
+    for (int idx = tid; idx < ty_end * rowE; idx += 256) {
+        const int ty = idx / rowE, e = idx - ty * rowE;
+        const float m = M[ty * TW + e / C];
+        const int64_t io = ((static_cast<int64_t>(b) * H + y0 + ty) * W + x0) * C + e;
+        const int64_t id = ((static_cast<int64_t>(b) * d.win_h + (y0 - d.y0) + ty) * d.win_w + (x0 - d.x0)) * C + e;
+        d.out[io] = d.original[io] * (1.0f - m) + d.detail[id] * m;
+    }
+}
+
+template <int TH, int TW>
+hipError_t launch_stitch(const lp_detail_stitch_desc& d, hipStream_t stream) {
+    const size_t lds = mask_tile_lds_bytes<TH, TW>(d.k);
+    if (lds > 64 * 1024)                                          // per device, like lp_mask_blend
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&lp_detail_stitch_kernel<TH, TW>),
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    const dim3 grid((d.win_w + TW - 1) / TW, (d.win_h + TH - 1) / TH, d.batch);
+    hipLaunchKernelGGL((lp_detail_stitch_kernel<TH, TW>), grid, dim3(256), lds, stream, d);
+    return hipGetLastError();
+}
+
+bool side_ok(int s) { return s > 0 && s <= LP_DETAIL_MAX_SIDE; }
+bool chan_ok(int c) { return c > 0 && c <= LP_DETAIL_MAX_CHANNELS; }
+bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+bool window_ok(int y0, int x0, int h, int w, int H, int W) {
+    return y0 >= 0 && x0 >= 0 && h > 0 && w > 0 && h <= H - y0 && w <= W - x0;
+}
+
+}  // namespace
+
+int mask_bbox_dispatch(const float* mask, int planes, int H, int W, int32_t* bbox, hipStream_t stream) {
+    if (!mask || !bbox || planes <= 0 || !side_ok(H) || !side_ok(W)) return LP_E_INVALID;
+    if (planes > 65535) return LP_E_UNSUPPORTED;
+    hipLaunchKernelGGL(lp_detail_bbox_init_kernel, dim3(1), dim3(kWave), 0, stream, bbox, H, W);
+    if (hipGetLastError() != hipSuccess) return LP_E_LAUNCH;
+    const uint32_t gy = (H + kBboxRows - 1) / kBboxRows;
+    if ((W & 3) == 0 && aligned16(mask))
+        hipLaunchKernelGGL(lp_detail_bbox_kernel<4>, dim3((W + 1023) / 1024, gy, planes), dim3(256), 0, stream, mask, bbox, H, W);
+    else
+        hipLaunchKernelGGL(lp_detail_bbox_kernel<1>, dim3((W + 255) / 256, gy, planes), dim3(256), 0, stream, mask, bbox, H, W);
+    return hipGetLastError() == hipSuccess ? LP_OK : LP_E_LAUNCH;
+}
+
+int detail_resample_dispatch(const lp_detail_resample_desc* dp, hipStream_t stream) {
+    if (!dp) return LP_E_INVALID;
+    const lp_detail_resample_desc& d = *dp;
+    if (d.batch <= 0 || !side_ok(d.src_h) || !side_ok(d.src_w) || !chan_ok(d.channels)) return LP_E_INVALID;
+    if (!window_ok(d.y0, d.x0, d.win_h, d.win_w, d.src_h, d.src_w) || !side_ok(d.out_h) || !side_ok(d.out_w)) return LP_E_INVALID;
+    if (!d.src || !d.dst) return LP_E_INVALID;
+    const bool same = d.out_h == d.win_h && d.out_w == d.win_w;
+    if (!same) {
+        if (d.ksize_x <= 0 || d.ksize_y <= 0) return LP_E_INVALID;
+        if (!d.bounds_x || !d.weights_x || !d.bounds_y || !d.weights_y) return LP_E_INVALID;
+        if (!aligned16(d.dst)) return LP_E_ALIGN;
+    }
+    if (d.batch > 65535) return LP_E_UNSUPPORTED;
+    const int rowE = d.out_w * d.channels;
+    if (same) {
+        hipLaunchKernelGGL(lp_detail_crop_kernel, dim3((rowE + 255) / 256, d.win_h, d.batch), dim3(256), 0, stream, d);
+    } else {
+        const dim3 grid((rowE + kRsTX - 1) / kRsTX, (d.out_h + kRsTY - 1) / kRsTY, d.batch);
+        hipLaunchKernelGGL(lp_detail_resample_kernel, grid, dim3(256), 0, stream, d);
+    }
+    return hipGetLastError() == hipSuccess ? LP_OK : LP_E_LAUNCH;
+}
+
+int detail_stitch_dispatch(const lp_detail_stitch_desc* dp, hipStream_t stream) {
+    if (!dp) return LP_E_INVALID;
+    const lp_detail_stitch_desc& d = *dp;
+    if (d.batch <= 0 || !side_ok(d.height) || !side_ok(d.width) || !chan_ok(d.channels)) return LP_E_INVALID;
+    if (!window_ok(d.y0, d.x0, d.win_h, d.win_w, d.height, d.width)) return LP_E_INVALID;
+    if (d.k < 1 || d.k > 51 || (d.k % 2) == 0) return LP_E_INVALID;
+    if (d.mask_batch != 1 && d.mask_batch != d.batch) return LP_E_INVALID;
+    if (!d.mask || !d.original || !d.detail || !d.out || d.out == d.original) return LP_E_INVALID;
+    if (d.batch > 65535) return LP_E_UNSUPPORTED;
+    const int64_t n = static_cast<int64_t>(d.batch) * d.height * d.width * d.channels;
+    const uint32_t blocks = static_cast<uint32_t>(min(static_cast<int64_t>(kCopyBlocks), (n + 1023) / 1024));
+    if (aligned16(d.original) && aligned16(d.out))
+        hipLaunchKernelGGL(lp_detail_copy_kernel<true>, dim3(blocks), dim3(256), 0, stream, d.original, d.out, n);
+    else                                                          // a frame range of a larger tensor need not start on 16 bytes
+        hipLaunchKernelGGL(lp_detail_copy_kernel<false>, dim3(blocks), dim3(256), 0, stream, d.original, d.out, n);
+    if (hipGetLastError() != hipSuccess) return LP_E_LAUNCH;
+    const hipError_t err = (d.k <= 15) ? launch_stitch<16, 64>(d, stream) : launch_stitch<8, 32>(d, stream);
+    return err == hipSuccess ? LP_OK : LP_E_LAUNCH;
+}
+
+}  // namespace lp

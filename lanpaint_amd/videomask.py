@@ -90,6 +90,13 @@ def audio_mask_frames(intervals, count, fps):
     return out
 
 
+def tap_window(center, support, in_size):
+    """(first tap, tap count) of a filter of half-width `support` centred at `center` (source-pixel units), clipped to
+    [0, in_size): Pillow's precompute_coeffs, which torch's antialiased interpolate took over (detail.aa_coeffs)."""
+    xmin = max(int(center - support + 0.5), 0)
+    return xmin, min(int(center + support + 0.5), in_size) - xmin
+
+
 @functools.lru_cache(maxsize=64)
 def pillow_bilinear_coeffs(in_size, out_size):
     """Pillow's BILINEAR coefficients for one axis (Resample.c precompute_coeffs + normalize_coeffs_8bpc, whole-image box):
@@ -106,8 +113,7 @@ def pillow_bilinear_coeffs(in_size, out_size):
     weights = np.zeros((out_size, ksize), np.int32)
     for xx in range(out_size):
         center = 0.0 + (xx + 0.5) * scale
-        xmin = max(int(center - support + 0.5), 0)
-        xmax = min(int(center + support + 0.5), in_size) - xmin
+        xmin, xmax = tap_window(center, support, in_size)
         taps, ww = [], 0.0
         for x in range(xmax):
             w = abs((x + xmin - center + 0.5) * ss)
