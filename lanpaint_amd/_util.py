@@ -1,7 +1,9 @@
 """Small host-side helpers shared by the engine's modules: stream / tensor-version accessors, dtype normalisation, the capture-time
-garbage-collector hold, ATen's randn launch policy, recognition of a model_sampling's noise_scaling form."""
+garbage-collector hold, the cached upload of host-built coefficient tables, ATen's randn launch policy, recognition of a
+model_sampling's noise_scaling form."""
 from __future__ import annotations
 
+import functools
 import threading
 
 import torch
@@ -65,6 +67,13 @@ def _as_f32c(t: torch.Tensor) -> torch.Tensor:
     if t.dtype != torch.float32 or not t.is_contiguous():
         t = t.to(torch.float32).contiguous()
     return t
+
+
+@functools.lru_cache(maxsize=64)
+def device_tables(builder, device, *key):
+    """The arrays of the host table builder `builder(*key)` (videomask.pillow_bilinear_coeffs, detail's fp32 aa_coeffs) as
+    tensors on `device`.  Cached on (builder, device, key): a geometry's tables are uploaded once, not once per call."""
+    return tuple(torch.tensor(a, device=device) for a in builder(*key))
 
 
 def aten_randn_policy(numel: int, multi_processor_count: int, max_threads_per_multi_processor: int):

@@ -13,6 +13,7 @@ import ctypes
 import torch
 
 from . import _cabi, interp_rule
+from ._util import _as_f32c
 
 
 def gaussian_kernel_2d(kernel_size):
@@ -26,10 +27,6 @@ def gaussian_kernel_2d(kernel_size):
     return k / k.sum()
 
 
-def _f32c(t):
-    return t if (t.dtype == torch.float32 and t.is_contiguous()) else t.to(torch.float32).contiguous()
-
-
 def _launch(mask, image1, image2, k, want_smooth=False, nn_rule=0):
     if not image1.is_cuda:
         raise RuntimeError("lanpaint_amd.blend runs on a HIP device only; no CPU fallback")
@@ -37,8 +34,8 @@ def _launch(mask, image1, image2, k, want_smooth=False, nn_rule=0):
         raise ValueError(f"blend_overlap must be an odd integer in [1, 51], got {k!r}")
     lib = _cabi.load()
     dev = image1.device
-    i1, i2 = _f32c(image1), _f32c(image2.to(dev))
-    m = _f32c(mask.to(dev))
+    i1, i2 = _as_f32c(image1), _as_f32c(image2.to(dev))
+    m = _as_f32c(mask.to(dev))
     b, h, w, c = i1.shape
     out = torch.empty_like(i1)
     smooth = torch.empty((b, h, w), dtype=torch.float32, device=dev) if want_smooth else None

@@ -147,7 +147,6 @@ __global__ __launch_bounds__(kMergeBlock) void lp_audio_merge_kernel(MergeArgs a
     }
 }
 
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 }  // namespace
 

@@ -13,14 +13,12 @@
 //                       lp_mask_blend).  No full-frame temporary; per-pixel work only over the region plus its halo.
 #include "lp_common.h"
 #include "mask_tile.h"
+#include "resample_tile.h"
 
 namespace lp {
 namespace {
 
 constexpr int kBboxRows = 16;       // bbox tile: 16 rows x (256 lanes x V columns)
-constexpr int kRsTX = 256;          // resample tile: 64 lanes x 4 flat elements of the output row ...
-constexpr int kRsTY = 16;           // ... by 16 output rows, 4 waves of 4 rows each
-constexpr int kRsCR = 32;           // source rows staged in LDS per chunk (32 KiB)
 constexpr int kCopyBlocks = 2048;   // streaming copy: grid-stride, 8 blocks per CU
 
 // ---- bounding box -------------------------------------------------------------------------------------------------------
@@ -98,100 +96,32 @@ __global__ __launch_bounds__(256) void lp_detail_bbox_kernel(const float* __rest
 }
 
 // ---- crop + resample ----------------------------------------------------------------------------------------------------
-// A table entry clamped to the window, so a bad table reads nothing outside it.
-__device__ __forceinline__ void tap_window(const int32_t* __restrict__ bounds, int i, int ksize, int in_size, int& first,
-                                           int& count) {
-    first = min(max(bounds[2 * i], 0), in_size - 1);
-    count = min(max(bounds[2 * i + 1], 0), min(ksize, in_size - first));
-}
+// torch's antialiased passes for resample_tile: fp32 NHWC source, fp32 sums from zero with the taps ascending, the horizontal
+// pass parked as one float4.  The library is built with -ffp-contract=on, so a multiply-add fuses only inside one source
+// expression: `ss += s[t * C] * w[t]` here and the tile's `acc += tap * wt` each are one, and have to stay one.
+struct TorchAA {
+    using Src = float;
+    using Weight = float;
+    using Acc = float;
+    using Staged = float4;
+    static __device__ __forceinline__ float acc0() { return 0.0f; }
+    static __device__ __forceinline__ float hsum(const float* s, const float* w, int n, int C) {
+        float ss = 0.0f;
+        for (int t = 0; t < n; ++t) ss += s[t * C] * w[t];
+        return ss;
+    }
+    static __device__ __forceinline__ float4 pack(const float (&v)[4]) { return make_float4(v[0], v[1], v[2], v[3]); }
+    static __device__ __forceinline__ float tap(const float4& p, int j) { return j == 0 ? p.x : j == 1 ? p.y : j == 2 ? p.z : p.w; }
+    static __device__ __forceinline__ float finish(float acc) { return acc; }
+};
 
-// One block: output rows [yy0, yy0 + 16) x flat elements [e0, e0 + 256) of the output row (element e = column e / C, channel
-// e % C) of image b.  Lane l of wave w owns elements e0 + 4l .. +3 and output rows yy0 + w + 4r (r < 4).  The window rows
-// those output rows read, [ylo, yhi), go through LDS in chunks of 32: horizontal pass of the chunk (fp32 sums, taps ascending),
-// then each thread adds the chunk's rows that fall in its rows' windows -- chunks ascend, so the vertical taps do too.
+// One block: a 16 x 256 tile of image b's output (resample_tile.h), read from the window at (y0, x0) of the source image.
 __global__ __launch_bounds__(256) void lp_detail_resample_kernel(const lp_detail_resample_desc d) {
-    __shared__ __attribute__((aligned(16))) float stage[kRsCR][kRsTX];
-    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
-    const int C = d.channels, inH = d.win_h, inW = d.win_w, outH = d.out_h, kx = d.ksize_x, ky = d.ksize_y;
+    const int C = d.channels, b = blockIdx.z;
     const int rowE = d.out_w * C;
-    const int e0 = blockIdx.x * kRsTX + lane * 4, yy0 = blockIdx.y * kRsTY;
-    const int b = blockIdx.z;
-    const int64_t sstride = static_cast<int64_t>(d.src_w) * C;
-    const float* src = d.src + ((static_cast<int64_t>(b) * d.src_h + d.y0) * d.src_w + d.x0) * C;
-
-    int ylo = inH, yhi = 0;                                       // window rows of the whole tile
-    for (int r = 0; r < kRsTY && yy0 + r < outH; ++r) {
-        int b0, b1;
-        tap_window(d.bounds_y, yy0 + r, ky, inH, b0, b1);
-        ylo = min(ylo, b0);
-        yhi = max(yhi, b0 + b1);
-    }
-    int rmin[4], rcnt[4];
-    float acc[4][4];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        const int yy = yy0 + wave + 4 * r;
-        rmin[r] = 0; rcnt[r] = 0;
-        if (yy < outH) tap_window(d.bounds_y, yy, ky, inH, rmin[r], rcnt[r]);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[r][j] = 0.0f;
-    }
-    int soff[4], ccnt[4], wbase[4];                               // first tap's offset in the window row, taps, table row
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        soff[j] = 0; ccnt[j] = 0; wbase[j] = 0;
-        if (e0 + j < rowE) {
-            const int xx = (e0 + j) / C, c = (e0 + j) - xx * C;
-            int first;
-            tap_window(d.bounds_x, xx, kx, inW, first, ccnt[j]);
-            soff[j] = first * C + c;
-            wbase[j] = xx * kx;
-        }
-    }
-
-    for (int c0 = ylo; c0 < yhi; c0 += kRsCR) {
-        const int rows = min(kRsCR, yhi - c0);
-        for (int rr = wave; rr < rows; rr += 4) {                 // horizontal pass of the chunk
-            const float* srow = src + static_cast<int64_t>(c0 + rr) * sstride;
-            float v[4];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                float ss = 0.0f;
-                const float* s = srow + soff[j];
-                const float* w = d.weights_x + wbase[j];
-                for (int t = 0; t < ccnt[j]; ++t) ss += s[t * C] * w[t];
-                v[j] = ss;
-            }
-            *reinterpret_cast<float4*>(&stage[rr][lane * 4]) = make_float4(v[0], v[1], v[2], v[3]);
-        }
-        __syncthreads();
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {                            // vertical pass: this chunk's share of each row's sum
-            const int t0 = max(rmin[r], c0), t1 = min(rmin[r] + rcnt[r], c0 + rows);
-            const float* w = d.weights_y + static_cast<int64_t>(yy0 + wave + 4 * r) * ky - rmin[r];
-            for (int t = t0; t < t1; ++t) {
-                const float4 p = *reinterpret_cast<const float4*>(&stage[t - c0][lane * 4]);
-                const float wt = w[t];
-                acc[r][0] += p.x * wt; acc[r][1] += p.y * wt; acc[r][2] += p.z * wt; acc[r][3] += p.w * wt;
-            }
-        }
-        __syncthreads();
-    }
-
-    const bool vec = (rowE & 3) == 0 && e0 + 3 < rowE;           // dst rows then start 16 B aligned (dst is checked)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        const int yy = yy0 + wave + 4 * r;
-        if (yy >= outH) continue;
-        float* o = d.dst + (static_cast<int64_t>(b) * outH + yy) * rowE + e0;
-        if (vec) {
-            *reinterpret_cast<float4*>(o) = make_float4(acc[r][0], acc[r][1], acc[r][2], acc[r][3]);
-        } else {
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-                if (e0 + j < rowE) o[j] = acc[r][j];
-        }
-    }
+    resample_tile<TorchAA>(d.src + ((static_cast<int64_t>(b) * d.src_h + d.y0) * d.src_w + d.x0) * C,
+                           static_cast<int64_t>(d.src_w) * C, C, d.win_h, d.win_w, d.out_h, rowE, d.bounds_x, d.weights_x,
+                           d.ksize_x, d.bounds_y, d.weights_y, d.ksize_y, d.dst + static_cast<int64_t>(b) * d.out_h * rowE);
 }
 
 // Same size in and out: the window's rows copied as flat streams, one element per lane.
@@ -260,7 +190,6 @@ hipError_t launch_stitch(const lp_detail_stitch_desc& d, hipStream_t stream) {
 
 bool side_ok(int s) { return s > 0 && s <= LP_DETAIL_MAX_SIDE; }
 bool chan_ok(int c) { return c > 0 && c <= LP_DETAIL_MAX_CHANNELS; }
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 bool window_ok(int y0, int x0, int h, int w, int H, int W) {
     return y0 >= 0 && x0 >= 0 && h > 0 && w > 0 && h <= H - y0 && w <= W - x0;
 }
@@ -297,7 +226,7 @@ int detail_resample_dispatch(const lp_detail_resample_desc* dp, hipStream_t stre
     if (same) {
         hipLaunchKernelGGL(lp_detail_crop_kernel, dim3((rowE + 255) / 256, d.win_h, d.batch), dim3(256), 0, stream, d);
     } else {
-        const dim3 grid((rowE + kRsTX - 1) / kRsTX, (d.out_h + kRsTY - 1) / kRsTY, d.batch);
+        const dim3 grid((rowE + kResampleTX - 1) / kResampleTX, (d.out_h + kResampleTY - 1) / kResampleTY, d.batch);
         hipLaunchKernelGGL(lp_detail_resample_kernel, grid, dim3(256), 0, stream, d);
     }
     return hipGetLastError() == hipSuccess ? LP_OK : LP_E_LAUNCH;

@@ -295,6 +295,8 @@ __device__ __forceinline__ uint32_t pack_half2(int dt, float lo, float hi);
 
 // ---- vector loads / stores ------------------------------------------------------
 enum : int { DT_F32 = 0, DT_BF16 = 1, DT_F16 = 2 };
+// may a dispatch take the 16 B per lane path on this pointer?
+inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 __device__ __forceinline__ uint32_t pack_half2(int dt, float lo, float hi) {
     if (dt == DT_BF16) return f32x2_to_bf16x2(lo, hi);
     return static_cast<uint32_t>(f32_to_f16(lo)) | (static_cast<uint32_t>(f32_to_f16(hi)) << 16);

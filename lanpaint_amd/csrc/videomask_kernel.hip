@@ -11,6 +11,7 @@
 //                    stages the horizontal pass of the source rows its output tile needs in LDS, then runs the vertical
 //                    pass and writes fp32 -- the only large tensor, written once, 16 B per lane.
 #include "lp_common.h"
+#include "resample_tile.h"
 
 namespace lp {
 namespace {
@@ -18,9 +19,6 @@ namespace {
 constexpr int kColBlock = 64;       // EDT column pass: one lane per column
 constexpr int kRowBlock = 64;       // EDT row pass: one wave per row (the envelope is built by lane 0)
 constexpr int kColUnroll = 16;      // rows whose loads the column pass issues back to back
-constexpr int kResizeTX = 256;      // resize tile: 64 lanes x 4 columns ...
-constexpr int kResizeTY = 16;       // ... by 16 output rows, 4 waves of 4 rows each
-constexpr int kResizeCR = 32;       // source rows staged in LDS per chunk
 constexpr int kPrec = 22;           // Pillow's PRECISION_BITS for 8-bit images (32 - 8 - 2)
 
 // ---- EDT column pass ---------------------------------------------------------------------------------------------------
@@ -206,96 +204,32 @@ __device__ __forceinline__ uint32_t clip8(int ss) {
     return ss >= (1 << kPrec << 8) ? 255u : (ss <= 0 ? 0u : static_cast<uint32_t>(ss >> kPrec));
 }
 
-// One block: output rows [yy0, yy0 + 16) x columns [xx0, xx0 + 256) of frame f.  Lane l of wave w owns columns
-// xx0 + 4l .. +3 and output rows yy0 + w + 4r (r < 4).  The source rows those rows read, [ylo, yhi), go through LDS in chunks
-// of 32: horizontal pass of the chunk (uint8, clipped, as Pillow's intermediate image), then each thread adds the chunk's
-// rows that fall in its rows' windows.  Table entries are clamped to the image, so a bad table reads nothing out of bounds.
+// Pillow's 8-bit passes for resample_tile: uint8 source, 22-bit fixed-point sums that start at one half, and the horizontal
+// pass parked as four clipped bytes (Pillow's uint8 intermediate image) in one dword.  Integer sums: exact in any order.
+struct Pillow8 {
+    using Src = uint8_t;
+    using Weight = int32_t;
+    using Acc = int;
+    using Staged = uint32_t;
+    static __device__ __forceinline__ int acc0() { return 1 << (kPrec - 1); }
+    static __device__ __forceinline__ int hsum(const uint8_t* s, const int32_t* w, int n, int C) {
+        int ss = acc0();
+        for (int t = 0; t < n; ++t) ss += static_cast<int>(s[t * C]) * w[t];
+        return ss;
+    }
+    static __device__ __forceinline__ uint32_t pack(const int (&v)[4]) {
+        return clip8(v[0]) | clip8(v[1]) << 8 | clip8(v[2]) << 16 | clip8(v[3]) << 24;
+    }
+    static __device__ __forceinline__ int tap(uint32_t p, int j) { return static_cast<int>((p >> (8 * j)) & 255u); }
+    static __device__ __forceinline__ float finish(int acc) { return static_cast<float>(clip8(acc)) / 255.0f; }
+};
+
+// One block: a 16 x 256 tile of frame f (resample_tile.h; a frame is one plane, C = 1).
 __global__ __launch_bounds__(256) void lp_vmask_resize_kernel(const lp_vmask_resize_desc d) {
-    __shared__ uint32_t stage[kResizeCR][kWave];
-    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
-    const int xx0 = blockIdx.x * kResizeTX + lane * 4, yy0 = blockIdx.y * kResizeTY;
     const int f = blockIdx.z;
-    const int inH = d.in_h, inW = d.in_w, outH = d.out_h, outW = d.out_w, kx = d.ksize_x, ky = d.ksize_y;
-    const uint8_t* src = d.src + static_cast<int64_t>(f) * inH * inW;
-
-    int ylo = inH, yhi = 0;                                       // source rows of the whole tile
-    for (int r = 0; r < kResizeTY && yy0 + r < outH; ++r) {
-        const int b0 = min(max(d.bounds_y[2 * (yy0 + r)], 0), inH - 1);
-        const int b1 = min(max(d.bounds_y[2 * (yy0 + r) + 1], 0), min(ky, inH - b0));
-        ylo = min(ylo, b0);
-        yhi = max(yhi, b0 + b1);
-    }
-    int rmin[4], rcnt[4];
-    int acc[4][4];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        const int yy = yy0 + wave + 4 * r;
-        rmin[r] = 0; rcnt[r] = 0;
-        if (yy < outH) {
-            rmin[r] = min(max(d.bounds_y[2 * yy], 0), inH - 1);
-            rcnt[r] = min(max(d.bounds_y[2 * yy + 1], 0), min(ky, inH - rmin[r]));
-        }
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[r][j] = 1 << (kPrec - 1);
-    }
-    int cmin[4], ccnt[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const int xx = xx0 + j;
-        cmin[j] = 0; ccnt[j] = 0;
-        if (xx < outW) {
-            cmin[j] = min(max(d.bounds_x[2 * xx], 0), inW - 1);
-            ccnt[j] = min(max(d.bounds_x[2 * xx + 1], 0), min(kx, inW - cmin[j]));
-        }
-    }
-
-    for (int c0 = ylo; c0 < yhi; c0 += kResizeCR) {
-        const int rows = min(kResizeCR, yhi - c0);
-        for (int rr = wave; rr < rows; rr += 4) {                 // horizontal pass of the chunk
-            const uint8_t* srow = src + static_cast<int64_t>(c0 + rr) * inW;
-            uint32_t packed = 0;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                int ss = 1 << (kPrec - 1);
-                const uint8_t* s = srow + cmin[j];
-                const int32_t* w = d.weights_x + static_cast<int64_t>(xx0 + j) * kx;
-                for (int t = 0; t < ccnt[j]; ++t) ss += static_cast<int>(s[t]) * w[t];
-                packed |= clip8(ss) << (8 * j);
-            }
-            stage[rr][lane] = packed;
-        }
-        __syncthreads();
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {                            // vertical pass: this chunk's share of each row's sum
-            const int t0 = max(rmin[r], c0), t1 = min(rmin[r] + rcnt[r], c0 + rows);
-            const int32_t* w = d.weights_y + static_cast<int64_t>(yy0 + wave + 4 * r) * ky - rmin[r];
-            for (int t = t0; t < t1; ++t) {
-                const uint32_t p = stage[t - c0][lane];
-                const int wt = w[t];
-#pragma unroll
-                for (int j = 0; j < 4; ++j) acc[r][j] += static_cast<int>((p >> (8 * j)) & 255u) * wt;
-            }
-        }
-        __syncthreads();
-    }
-
-    const bool vec = (outW & 3) == 0 && xx0 + 3 < outW;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        const int yy = yy0 + wave + 4 * r;
-        if (yy >= outH) continue;
-        float v[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) v[j] = static_cast<float>(clip8(acc[r][j])) / 255.0f;
-        float* o = d.dst + (static_cast<int64_t>(f) * outH + yy) * outW + xx0;
-        if (vec) {
-            *reinterpret_cast<float4*>(o) = make_float4(v[0], v[1], v[2], v[3]);
-        } else {
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-                if (xx0 + j < outW) o[j] = v[j];
-        }
-    }
+    resample_tile<Pillow8>(d.src + static_cast<int64_t>(f) * d.in_h * d.in_w, d.in_w, 1, d.in_h, d.in_w, d.out_h, d.out_w,
+                           d.bounds_x, d.weights_x, d.ksize_x, d.bounds_y, d.weights_y, d.ksize_y,
+                           d.dst + static_cast<int64_t>(f) * d.out_h * d.out_w);
 }
 
 bool side_ok(int s) { return s > 0 && s <= LP_VMASK_MAX_SIDE; }
@@ -345,7 +279,7 @@ int vmask_resize_dispatch(const lp_vmask_resize_desc* dp, hipStream_t stream) {
     if (d.ksize_x <= 0 || d.ksize_y <= 0) return LP_E_INVALID;
     if (!d.src || !d.dst || !d.bounds_x || !d.weights_x || !d.bounds_y || !d.weights_y) return LP_E_INVALID;
     if (d.n_frames > 65535) return LP_E_UNSUPPORTED;
-    const dim3 grid((d.out_w + kResizeTX - 1) / kResizeTX, (d.out_h + kResizeTY - 1) / kResizeTY, d.n_frames);
+    const dim3 grid((d.out_w + kResampleTX - 1) / kResampleTX, (d.out_h + kResampleTY - 1) / kResampleTY, d.n_frames);
     hipLaunchKernelGGL(lp_vmask_resize_kernel, grid, dim3(256), 0, stream, d);
     return hipGetLastError() == hipSuccess ? LP_OK : LP_E_LAUNCH;
 }

@@ -38,6 +38,7 @@ import numpy as np
 import torch
 
 from . import _cabi
+from ._util import _as_f32c, device_tables, raw_stream
 from .videomask import tap_window
 
 FILTERS = ("bilinear", "bicubic")
@@ -149,14 +150,6 @@ def _hip(t, what):
     return t
 
 
-def _f32c(t):
-    return t if (t.dtype == torch.float32 and t.is_contiguous()) else t.to(torch.float32).contiguous()
-
-
-def _stream(dev):
-    return torch.cuda.current_stream(dev).cuda_stream
-
-
 def _mask3(mask):
     if mask.ndim == 2:
         return mask.unsqueeze(0)
@@ -178,21 +171,19 @@ def _check_region(region, H, W):
 def mask_bbox(mask):
     """(row_min, row_max, col_min, col_max), inclusive, of `mask > 0.5` over every frame of a HIP mask [B, H, W], [1, H, W] or
     [H, W]; (H, -1, W, -1) when nothing is set (plan_region raises on it).  Reads four integers back from the device."""
-    m = _f32c(_mask3(_hip(mask, "mask")))
+    m = _as_f32c(_mask3(_hip(mask, "mask")))
     planes, h, w = m.shape
     dev = m.device
     box = torch.empty(4, dtype=torch.int32, device=dev)
     with torch.cuda.device(dev):
-        _cabi.check(_cabi.load().lp_mask_bbox(m.data_ptr(), planes, h, w, box.data_ptr(), _stream(dev)), "lp_mask_bbox")
+        _cabi.check(_cabi.load().lp_mask_bbox(m.data_ptr(), planes, h, w, box.data_ptr(), raw_stream(dev)), "lp_mask_bbox")
     return tuple(box.cpu().tolist())
 
 
-@functools.lru_cache(maxsize=32)
-def _device_tables(in_size, out_size, filter, dev):
-    """aa_coeffs rounded to fp32 once, on the device: (bounds int32 [out, 2], weights float32 [out, ksize]).  Cached, so a
-    job's second resample of the same geometry uploads nothing."""
+def _aa_tables_f32(in_size, out_size, filter):
+    """aa_coeffs as the kernel reads it: (bounds int32 [out, 2], weights rounded to float32 [out, ksize])."""
     bounds, weights = aa_coeffs(in_size, out_size, filter)
-    return torch.tensor(bounds, device=dev), torch.tensor(weights.astype(np.float32), device=dev)
+    return bounds, weights.astype(np.float32)
 
 
 def _resample(src, y0, x0, h, w, oh, ow, filter):
@@ -203,12 +194,12 @@ def _resample(src, y0, x0, h, w, oh, ow, filter):
     d = _cabi.LpDetailResampleDesc(b, sh, sw, c, y0, x0, h, w, oh, ow, 0, 0)
     d.src, d.dst = src.data_ptr(), out.data_ptr()
     if (oh, ow) != (h, w):
-        bx, wx = _device_tables(w, ow, filter, dev)
-        by, wy = _device_tables(h, oh, filter, dev)
+        bx, wx = device_tables(_aa_tables_f32, dev, w, ow, filter)
+        by, wy = device_tables(_aa_tables_f32, dev, h, oh, filter)
         d.ksize_x, d.ksize_y = wx.shape[1], wy.shape[1]
         d.bounds_x, d.weights_x, d.bounds_y, d.weights_y = bx.data_ptr(), wx.data_ptr(), by.data_ptr(), wy.data_ptr()
     with torch.cuda.device(dev):
-        _cabi.check(_cabi.load().lp_detail_resample(ctypes.byref(d), _stream(dev)), "lp_detail_resample")
+        _cabi.check(_cabi.load().lp_detail_resample(ctypes.byref(d), raw_stream(dev)), "lp_detail_resample")
     return out
 
 
@@ -216,7 +207,7 @@ def crop_resample(image, mask, region, filter="bilinear"):
     """image [B, H, W, C] and mask ([B, H, W], [1, H, W], [H, W] or None) cut to `region` and resampled to its working size:
     (image [B, oh, ow, C], mask [Bm, oh, ow] or None).  The image takes `filter`, the mask bilinear, and it stays soft."""
     _check_filter(filter)
-    img = _f32c(_hip(image, "image"))
+    img = _as_f32c(_hip(image, "image"))
     if img.ndim != 4:
         raise ValueError(f"image must be [B, H, W, C], got {tuple(image.shape)}")
     _check_region(region, img.shape[1], img.shape[2])
@@ -224,7 +215,7 @@ def crop_resample(image, mask, region, filter="bilinear"):
     out = _resample(img, r.y0, r.x0, r.h, r.w, r.oh, r.ow, filter)
     if mask is None:
         return out, None
-    m = _f32c(_mask3(_hip(mask, "mask")))
+    m = _as_f32c(_mask3(_hip(mask, "mask")))
     if tuple(m.shape[1:]) != (r.H, r.W):
         raise ValueError(f"mask shape {tuple(mask.shape)} does not match images {tuple(image.shape)}")
     return out, _resample(m.unsqueeze(-1), r.y0, r.x0, r.h, r.w, r.oh, r.ow, "bilinear").squeeze(-1)
@@ -238,9 +229,9 @@ def stitch(original, detail_img, mask, region, blend_overlap=1, filter="bilinear
     k = blend_overlap
     if not isinstance(k, int) or k < 1 or k > 51 or k % 2 == 0:
         raise ValueError(f"blend_overlap must be an odd integer in [1, 51], got {k!r}")
-    orig = _f32c(_hip(original, "original"))
-    det = _f32c(_hip(detail_img, "detail_img").to(orig.device))
-    m = _f32c(_mask3(_hip(mask, "mask")).to(orig.device))
+    orig = _as_f32c(_hip(original, "original"))
+    det = _as_f32c(_hip(detail_img, "detail_img").to(orig.device))
+    m = _as_f32c(_mask3(_hip(mask, "mask")).to(orig.device))
     if orig.ndim != 4 or det.ndim != 4:
         raise ValueError("original and detail_img must be [B, H, W, C]")
     b, H, W, c = orig.shape
@@ -257,5 +248,5 @@ def stitch(original, detail_img, mask, region, blend_overlap=1, filter="bilinear
     d = _cabi.LpDetailStitchDesc(b, H, W, c, r.y0, r.x0, r.h, r.w, k, m.shape[0],
                                  m.data_ptr(), orig.data_ptr(), det.data_ptr(), out.data_ptr())
     with torch.cuda.device(dev):
-        _cabi.check(_cabi.load().lp_detail_stitch(ctypes.byref(d), _stream(dev)), "lp_detail_stitch")
+        _cabi.check(_cabi.load().lp_detail_stitch(ctypes.byref(d), raw_stream(dev)), "lp_detail_stitch")
     return out

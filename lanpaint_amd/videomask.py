@@ -24,6 +24,7 @@ import numpy as np
 import torch
 
 from . import _cabi
+from ._util import device_tables, raw_stream
 
 # one lp_vmask_frame of include/lanpaint_hip.h
 FRAME_DTYPE = np.dtype([("kind", "<i4"), ("key_lo", "<i4"), ("key_hi", "<i4"), ("sx1", "<i4"), ("sy1", "<i4"),
@@ -164,10 +165,6 @@ def _device(device):
     return dev
 
 
-def _stream(dev):
-    return torch.cuda.current_stream(dev).cuda_stream
-
-
 def _check_side(*sides):
     for s in sides:
         if not 0 < s <= _cabi.LP_VMASK_MAX_SIDE:
@@ -187,7 +184,7 @@ def keyframe_edt(keys):
     csum = torch.empty((k, 3), dtype=torch.int64, device=dev)
     d = _cabi.LpVmaskEdtDesc(k, h, w, 0, keys.data_ptr(), d2.data_ptr(), sdf.data_ptr(), csum.data_ptr())
     with torch.cuda.device(dev):
-        _cabi.check(_cabi.load().lp_vmask_edt(ctypes.byref(d), _stream(dev)), "lp_vmask_edt")
+        _cabi.check(_cabi.load().lp_vmask_edt(ctypes.byref(d), raw_stream(dev)), "lp_vmask_edt")
     return d2, sdf, csum
 
 
@@ -206,7 +203,7 @@ def morph_frames(keys, plan, sdf=None, codes=False):
     d = _cabi.LpVmaskMorphDesc(n, k, h, w, _cabi.LP_VMASK_OUT_U8 if codes else 0, 0, table.data_ptr(), keys.data_ptr(),
                                sdf.data_ptr() if sdf is not None else None, out.data_ptr())
     with torch.cuda.device(dev):
-        _cabi.check(_cabi.load().lp_vmask_morph(ctypes.byref(d), _stream(dev)), "lp_vmask_morph")
+        _cabi.check(_cabi.load().lp_vmask_morph(ctypes.byref(d), raw_stream(dev)), "lp_vmask_morph")
     return out
 
 
@@ -220,14 +217,13 @@ def resize_codes(codes, size):
     out_w, out_h = int(size[0]), int(size[1])
     _check_side(h, w, out_h, out_w)
     dev = codes.device
-    bx, kx = pillow_bilinear_coeffs(w, out_w)
-    by, ky = pillow_bilinear_coeffs(h, out_h)
-    tabs = [torch.tensor(a, device=dev) for a in (bx, kx, by, ky)]
+    bx, kx = device_tables(pillow_bilinear_coeffs, dev, w, out_w)
+    by, ky = device_tables(pillow_bilinear_coeffs, dev, h, out_h)
     out = torch.empty((n, out_h, out_w), dtype=torch.float32, device=dev)
     d = _cabi.LpVmaskResizeDesc(n, h, w, out_h, out_w, kx.shape[1], ky.shape[1], 0, codes.data_ptr(),
-                                *(t.data_ptr() for t in tabs), out.data_ptr())
+                                bx.data_ptr(), kx.data_ptr(), by.data_ptr(), ky.data_ptr(), out.data_ptr())
     with torch.cuda.device(dev):
-        _cabi.check(_cabi.load().lp_vmask_resize(ctypes.byref(d), _stream(dev)), "lp_vmask_resize")
+        _cabi.check(_cabi.load().lp_vmask_resize(ctypes.byref(d), raw_stream(dev)), "lp_vmask_resize")
     return out
 
 
