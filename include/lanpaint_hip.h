@@ -43,7 +43,7 @@
 extern "C" {
 #endif
 
-#define LP_ABI_VERSION 24
+#define LP_ABI_VERSION 25
 
 /* The library is built with -fvisibility=hidden: the entry points declared LP_API below are its ONLY dynamic symbols (the
  * dispatch functions, kernel handles and device stubs of the C++ side stay internal; tests/test_cabi_exports.py checks
@@ -803,6 +803,80 @@ typedef struct lp_detail_stitch_desc {
     float*       out;
 } lp_detail_stitch_desc;
 LP_API int lp_detail_stitch(const lp_detail_stitch_desc* desc, void* stream);
+
+/* ---- Detailer per region (beyond the reference, like the Detailer itself) ------------------------------------------------------
+ * Split the mask into its connected areas, detail each in a window of its own, all windows of one size so the crops stack as
+ * one sampler batch.  The host (lanpaint_amd/detail.py, plan_regions) groups components into regions from the table below. */
+#define LP_DETAIL_MAX_COMPONENTS 4096
+#define LP_DETAIL_MAX_REGIONS    64
+
+/* Connected components of  S = {(y, x): mask[p, y, x] > 0.5 for some plane p},  8-connected.  A
+ * component's label is 1 + the rank of its smallest flat index y * width + x among all components: labels run 1..n in raster
+ * order of first pixel, 0 is background -- scipy.ndimage.label(S, ones((3, 3))).
+ *   mask    [planes, height, width] fp32
+ *   labels  out, device, int32 [height, width]; exact whatever n is
+ *   table   out, device, int32 [1 + 5 * LP_DETAIL_MAX_COMPONENTS]: table[0] = n, the true count even past the cap; for
+ *           id = 1 .. min(n, cap), table[1 + 5 * (id - 1) ..] = {row_min, row_max, col_min, col_max, area}, boxes inclusive;
+ *           rows past n hold {height, -1, width, -1, 0}
+ *   workspace  device, LP_COMPONENTS_WS_BYTES(height, width) bytes, 16-byte aligned: the union-find's parent array and the
+ *           prefix sum's per-chunk counts
+ * Seven plain launches on `stream` (csrc/label_kernel.hip); integer atomics only, the result does not depend on the order of
+ * arrival.  LP_E_INVALID: null pointer, planes <= 0, a side outside 1..LP_DETAIL_MAX_SIDE, a short workspace; LP_E_ALIGN:
+ * workspace not 16-byte aligned; LP_E_UNSUPPORTED: planes > 65535.  All checked before any HIP call.                        */
+#define LP_COMPONENTS_WS_BYTES(height, width) ((((int64_t)(height) * (width) + 1023) / 1024) * 4100)
+LP_API int lp_mask_components(const float* mask, int32_t planes, int32_t height, int32_t width, int32_t* labels,
+                              int32_t* table, void* workspace, int64_t workspace_bytes, void* stream);
+
+/* lp_detail_resample for `regions` windows of one size in one call:  dst [regions * batch, out_h, out_w,
+ * channels], region-major, dst[r * batch + b] = lp_detail_resample of the window at origins[r] of src[b], bit for bit.
+ *   origins  DEVICE int32 [regions, 2] = (y0, x0); an origin is clamped so that its window lies inside the image
+ * With `labels` the source is a mask (channels == 1) and region r sees it with foreign components erased:
+ *   value = 0 where labels[y, x] != 0 and owner[labels[y, x]] != r + 1 (a label >= owner_len is foreign), the mask's own value
+ *   elsewhere -- label 0 (soft values at or below 0.5) is kept.
+ *   labels  device int32 [src_h, src_w] (lp_mask_components), or NULL: no erasing;  owner  device int32 [owner_len]
+ *   scratch device fp32 [regions * batch * win_h * win_w], 16-byte aligned: the erased windows, needed with `labels` when the
+ *           size changes (a window-sized temporary; no frame-sized per-region mask exists anywhere)
+ * Errors as lp_detail_resample, plus LP_E_INVALID: regions outside 1..LP_DETAIL_MAX_REGIONS, null origins, labels with
+ * channels != 1 or without owner / scratch; LP_E_UNSUPPORTED: regions * batch > 65535.                                      */
+typedef struct lp_detail_resample_regions_desc {
+    int32_t batch, src_h, src_w, channels;
+    int32_t regions, win_h, win_w, owner_len;
+    int32_t out_h, out_w, ksize_x, ksize_y;
+    const int32_t* origins;
+    const float*   src;
+    const int32_t* bounds_x;
+    const float*   weights_x;
+    const int32_t* bounds_y;
+    const float*   weights_y;
+    float*         dst;
+    const int32_t* labels;
+    const int32_t* owner;
+    float*         scratch;
+} lp_detail_resample_regions_desc;
+LP_API int lp_detail_resample_regions(const lp_detail_resample_regions_desc* desc, void* stream);
+
+/* lp_detail_stitch composed over regions, in region order:
+ *   out_0 = original;   out_{r+1} = lp_detail_stitch(out_r, detail[r], mask_r, window r);   out = out_regions
+ * bit for bit, mask_r the mask with foreign components erased as above (labels NULL: the mask itself for every region).
+ * Windows may overlap, so the order is part of the result.  One streaming copy original -> out, then one launch per region
+ * over its window's tiles, in place on out: one thread reads and writes a given element.
+ *   origins  HOST int32 [regions, 2] = (y0, x0), read during the call; every window must lie inside the image
+ *   detail   [regions * batch, win_h, win_w, channels], region-major, already at the window's size
+ * Errors as lp_detail_stitch, plus LP_E_INVALID: regions outside 1..LP_DETAIL_MAX_REGIONS, null origins, labels without
+ * owner.                                                                                                                    */
+typedef struct lp_detail_stitch_regions_desc {
+    int32_t batch, height, width, channels;
+    int32_t regions, win_h, win_w, k;
+    int32_t mask_batch, owner_len;
+    const int32_t* origins;
+    const float*   mask;
+    const float*   original;
+    const float*   detail;
+    float*         out;
+    const int32_t* labels;
+    const int32_t* owner;
+} lp_detail_stitch_regions_desc;
+LP_API int lp_detail_stitch_regions(const lp_detail_stitch_regions_desc* desc, void* stream);
 
 #ifdef __cplusplus
 }

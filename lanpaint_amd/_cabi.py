@@ -13,7 +13,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_NAME = "liblanpaint_hip.so"
 LIB_PATH = os.path.join(_HERE, LIB_NAME)
-ABI_VERSION = 24
+ABI_VERSION = 25
 
 # --- constants mirrored from include/lanpaint_hip.h -------------------------------
 LP_OK, LP_E_INVALID, LP_E_UNSUPPORTED, LP_E_LAUNCH, LP_E_ALIGN = 0, -1, -2, -3, -4
@@ -187,6 +187,31 @@ class LpDetailStitchDesc(C.Structure):
                 ("mask", C.c_void_p), ("original", C.c_void_p), ("detail", C.c_void_p), ("out", C.c_void_p)]
 
 
+LP_DETAIL_MAX_COMPONENTS, LP_DETAIL_MAX_REGIONS = 4096, 64
+
+
+class LpDetailResampleRegionsDesc(C.Structure):
+    _fields_ = [("batch", C.c_int32), ("src_h", C.c_int32), ("src_w", C.c_int32), ("channels", C.c_int32),
+                ("regions", C.c_int32), ("win_h", C.c_int32), ("win_w", C.c_int32), ("owner_len", C.c_int32),
+                ("out_h", C.c_int32), ("out_w", C.c_int32), ("ksize_x", C.c_int32), ("ksize_y", C.c_int32),
+                ("origins", C.c_void_p), ("src", C.c_void_p), ("bounds_x", C.c_void_p), ("weights_x", C.c_void_p),
+                ("bounds_y", C.c_void_p), ("weights_y", C.c_void_p), ("dst", C.c_void_p), ("labels", C.c_void_p),
+                ("owner", C.c_void_p), ("scratch", C.c_void_p)]
+
+
+class LpDetailStitchRegionsDesc(C.Structure):
+    _fields_ = [("batch", C.c_int32), ("height", C.c_int32), ("width", C.c_int32), ("channels", C.c_int32),
+                ("regions", C.c_int32), ("win_h", C.c_int32), ("win_w", C.c_int32), ("k", C.c_int32),
+                ("mask_batch", C.c_int32), ("owner_len", C.c_int32),
+                ("origins", C.c_void_p), ("mask", C.c_void_p), ("original", C.c_void_p), ("detail", C.c_void_p),
+                ("out", C.c_void_p), ("labels", C.c_void_p), ("owner", C.c_void_p)]
+
+
+def lp_components_ws_bytes(height, width):
+    """LP_COMPONENTS_WS_BYTES of include/lanpaint_hip.h."""
+    return ((int(height) * int(width) + 1023) // 1024) * 4100
+
+
 def lp_audio_ws_bytes(mask_len):
     """LP_AUDIO_WS_BYTES of include/lanpaint_hip.h."""
     return 12 * (int(mask_len) + 1)
@@ -233,6 +258,10 @@ EXPORTS = {
     "lp_mask_bbox": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "lp_detail_resample": (C.c_int, [C.POINTER(LpDetailResampleDesc), C.c_void_p]),
     "lp_detail_stitch": (C.c_int, [C.POINTER(LpDetailStitchDesc), C.c_void_p]),
+    "lp_mask_components": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+                                     C.c_void_p]),
+    "lp_detail_resample_regions": (C.c_int, [C.POINTER(LpDetailResampleRegionsDesc), C.c_void_p]),
+    "lp_detail_stitch_regions": (C.c_int, [C.POINTER(LpDetailStitchRegionsDesc), C.c_void_p]),
 }
 
 

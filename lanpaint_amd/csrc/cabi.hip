@@ -37,6 +37,10 @@ int audio_merge_dispatch(const lp_audio_desc* d, hipStream_t stream);
 int mask_bbox_dispatch(const float* mask, int planes, int H, int W, int32_t* bbox, hipStream_t stream);
 int detail_resample_dispatch(const lp_detail_resample_desc* d, hipStream_t stream);
 int detail_stitch_dispatch(const lp_detail_stitch_desc* d, hipStream_t stream);
+int mask_components_dispatch(const float* mask, int planes, int H, int W, int32_t* labels, int32_t* table, void* workspace,
+                             int64_t workspace_bytes, hipStream_t stream);
+int detail_resample_regions_dispatch(const lp_detail_resample_regions_desc* d, hipStream_t stream);
+int detail_stitch_regions_dispatch(const lp_detail_stitch_regions_desc* d, hipStream_t stream);
 int reshape_mask_dispatch(const float* src, int sb, int sc, int sf, int sh, int sw, float* dst, int db, int dc, int df,
                           int dh, int dw, int taps, int flags, hipStream_t stream);
 }  // namespace lp
@@ -105,6 +109,19 @@ int lp_mask_bbox(const float* mask, int32_t planes, int32_t height, int32_t widt
 int lp_detail_resample(const lp_detail_resample_desc* desc, void* stream) { return lp::detail_resample_dispatch(desc, as_stream(stream)); }
 
 int lp_detail_stitch(const lp_detail_stitch_desc* desc, void* stream) { return lp::detail_stitch_dispatch(desc, as_stream(stream)); }
+
+int lp_mask_components(const float* mask, int32_t planes, int32_t height, int32_t width, int32_t* labels, int32_t* table,
+                       void* workspace, int64_t workspace_bytes, void* stream) {
+    return lp::mask_components_dispatch(mask, planes, height, width, labels, table, workspace, workspace_bytes, as_stream(stream));
+}
+
+int lp_detail_resample_regions(const lp_detail_resample_regions_desc* desc, void* stream) {
+    return lp::detail_resample_regions_dispatch(desc, as_stream(stream));
+}
+
+int lp_detail_stitch_regions(const lp_detail_stitch_regions_desc* desc, void* stream) {
+    return lp::detail_stitch_regions_dispatch(desc, as_stream(stream));
+}
 
 
 int lp_finalize(const lp_final_desc* desc, void* stream) { return lp::finalize_dispatch(desc, as_stream(stream)); }

@@ -11,6 +11,11 @@
 //   lp_detail_stitch    out = original outside the region (one streaming copy), original * (1 - m) + detail * m inside, m the
 //                       MaskBlend-smoothed mask of the WHOLE image evaluated on the region's tiles (mask_tile.h, shared with
 //                       lp_mask_blend).  No full-frame temporary; per-pixel work only over the region plus its halo.
+//
+// and the same two for several windows of one size (lp_detail_resample_regions, lp_detail_stitch_regions): the crops of all
+// regions in one launch, window origins from a device table; the stitch as one copy, then region after region in place on
+// the result.  Region r sees the mask with the components of other regions erased (EraseForeign reads the label image of
+// label_kernel.hip and an owner table), evaluated where the mask is read: no per-region mask is ever written at frame size.
 #include "lp_common.h"
 #include "mask_tile.h"
 #include "resample_tile.h"
@@ -150,16 +155,18 @@ __global__ __launch_bounds__(256) void lp_detail_copy_kernel(const float* __rest
 }
 
 // A block owns a TH x TW tile of the REGION of image b; tile origins are image coordinates, so the smoothed mask is the
-// whole image's.  m goes to LDS, then the tile's rows are blended as flat streams of TW * C elements.
-template <int TH, int TW>
-__global__ __launch_bounds__(256) void lp_detail_stitch_kernel(const lp_detail_stitch_desc d) {
+// whole image's.  m goes to LDS, then the tile's rows are blended as flat streams of TW * C elements.  `edit` is how a mask
+// element enters the passes (mask_tile.h): as it is, or with another region's components erased.  out may be original: one
+// thread reads and writes a given element, and the halo is read from the mask alone.
+template <int TH, int TW, class Edit>
+__device__ __forceinline__ void stitch_tile(const lp_detail_stitch_desc& d, const Edit edit) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int k = d.k, tid = threadIdx.x;
     const int x0 = d.x0 + blockIdx.x * TW, y0 = d.y0 + blockIdx.y * TH, b = blockIdx.z;
     const int H = d.height, W = d.width, C = d.channels;
     const float* mplane = d.mask + static_cast<int64_t>(d.mask_batch == 1 ? 0 : b) * H * W;
     float *D, *g;
-    mask_tile_passes<TH, TW>(lds, mplane, H, W, LP_NN_ATEN_SCALAR, k, x0, y0, H, W, D, g);
+    mask_tile_passes<TH, TW, Edit>(lds, mplane, H, W, LP_NN_ATEN_SCALAR, k, x0, y0, H, W, D, g, edit);
     float* M = lds;                                               // the passes' A, free now: TH x TW smoothed mask
     for (int idx = tid; idx < TH * TW; idx += 256) {
         const int ty = idx / TW, tx = idx - ty * TW;
@@ -178,14 +185,70 @@ __global__ __launch_bounds__(256) void lp_detail_stitch_kernel(const lp_detail_s
 }
 
 template <int TH, int TW>
-hipError_t launch_stitch(const lp_detail_stitch_desc& d, hipStream_t stream) {
+__global__ __launch_bounds__(256) void lp_detail_stitch_kernel(const lp_detail_stitch_desc d) {
+    stitch_tile<TH, TW>(d, MaskAsIs());
+}
+
+// Region `mine - 1`'s view of the mask: components that belong to another region, or to none, read as 0.  Label 0 -- every
+// value at or below 0.5 -- is nobody's and stays, so feathered edges survive.
+struct EraseForeign {
+    const int32_t* labels;
+    const int32_t* owner;
+    int owner_len, mine;
+    __device__ __forceinline__ float operator()(float v, int64_t at) const {
+        const int label = labels[at];
+        if (label == 0) return v;
+        const int o = (label > 0 && label < owner_len) ? owner[label] : 0;
+        return o == mine ? v : 0.0f;
+    }
+};
+
+template <int TH, int TW>
+__global__ __launch_bounds__(256) void lp_detail_stitch_region_kernel(const lp_detail_stitch_desc d, const EraseForeign erase) {
+    stitch_tile<TH, TW>(d, erase);
+}
+
+template <int TH, int TW, class... Extra>
+hipError_t launch_stitch(void (*kernel)(const lp_detail_stitch_desc, Extra...), const lp_detail_stitch_desc& d,
+                         hipStream_t stream, Extra... extra) {
     const size_t lds = mask_tile_lds_bytes<TH, TW>(d.k);
     if (lds > 64 * 1024)                                          // per device, like lp_mask_blend
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&lp_detail_stitch_kernel<TH, TW>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     const dim3 grid((d.win_w + TW - 1) / TW, (d.win_h + TH - 1) / TH, d.batch);
-    hipLaunchKernelGGL((lp_detail_stitch_kernel<TH, TW>), grid, dim3(256), lds, stream, d);
+    hipLaunchKernelGGL(kernel, grid, dim3(256), lds, stream, d, extra...);
     return hipGetLastError();
+}
+
+// ---- regions: the same jobs for several windows of one size ----------------------------------------------------------------
+__device__ __forceinline__ void region_origin(const int32_t* __restrict__ origins, int r, int H, int W, int h, int w, int& y0,
+                                              int& x0) {                // clamped: a bad table reads nothing outside the image
+    y0 = min(max(origins[2 * r], 0), H - h);
+    x0 = min(max(origins[2 * r + 1], 0), W - w);
+}
+
+// blockIdx.z = region * batch + image; otherwise lp_detail_resample_kernel.
+__global__ __launch_bounds__(256) void lp_detail_resample_regions_kernel(const lp_detail_resample_regions_desc d) {
+    const int C = d.channels, z = blockIdx.z, r = z / d.batch, b = z - r * d.batch;
+    const int rowE = d.out_w * C;
+    int y0, x0;
+    region_origin(d.origins, r, d.src_h, d.src_w, d.win_h, d.win_w, y0, x0);
+    resample_tile<TorchAA>(d.src + ((static_cast<int64_t>(b) * d.src_h + y0) * d.src_w + x0) * C,
+                           static_cast<int64_t>(d.src_w) * C, C, d.win_h, d.win_w, d.out_h, rowE, d.bounds_x, d.weights_x,
+                           d.ksize_x, d.bounds_y, d.weights_y, d.ksize_y, d.dst + static_cast<int64_t>(z) * d.out_h * rowE);
+}
+
+// The windows' rows copied as flat streams into dst [regions * batch, win_h, win_w, C]; ERASE (C == 1): through EraseForeign.
+template <bool ERASE>
+__global__ __launch_bounds__(256) void lp_detail_crop_regions_kernel(const lp_detail_resample_regions_desc d, float* __restrict__ dst) {
+    const int C = d.channels, rowE = d.win_w * C;
+    const int e = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y, z = blockIdx.z, r = z / d.batch, b = z - r * d.batch;
+    if (e >= rowE) return;
+    int y0, x0;
+    region_origin(d.origins, r, d.src_h, d.src_w, d.win_h, d.win_w, y0, x0);
+    const int64_t at = static_cast<int64_t>(y0 + y) * d.src_w + x0;    // of the window row's first pixel in its plane
+    float v = d.src[(static_cast<int64_t>(b) * d.src_h * d.src_w + at) * C + e];
+    if constexpr (ERASE) v = EraseForeign{d.labels, d.owner, d.owner_len, r + 1}(v, at + e);
+    dst[(static_cast<int64_t>(z) * d.win_h + y) * rowE + e] = v;
 }
 
 bool side_ok(int s) { return s > 0 && s <= LP_DETAIL_MAX_SIDE; }
@@ -248,8 +311,80 @@ int detail_stitch_dispatch(const lp_detail_stitch_desc* dp, hipStream_t stream) 
     else                                                          // a frame range of a larger tensor need not start on 16 bytes
         hipLaunchKernelGGL(lp_detail_copy_kernel<false>, dim3(blocks), dim3(256), 0, stream, d.original, d.out, n);
     if (hipGetLastError() != hipSuccess) return LP_E_LAUNCH;
-    const hipError_t err = (d.k <= 15) ? launch_stitch<16, 64>(d, stream) : launch_stitch<8, 32>(d, stream);
+    const hipError_t err = (d.k <= 15) ? launch_stitch<16, 64>(lp_detail_stitch_kernel<16, 64>, d, stream)
+                                       : launch_stitch<8, 32>(lp_detail_stitch_kernel<8, 32>, d, stream);
     return err == hipSuccess ? LP_OK : LP_E_LAUNCH;
+}
+
+int detail_resample_regions_dispatch(const lp_detail_resample_regions_desc* dp, hipStream_t stream) {
+    if (!dp) return LP_E_INVALID;
+    const lp_detail_resample_regions_desc& d = *dp;
+    if (d.batch <= 0 || !side_ok(d.src_h) || !side_ok(d.src_w) || !chan_ok(d.channels)) return LP_E_INVALID;
+    if (d.regions < 1 || d.regions > LP_DETAIL_MAX_REGIONS || !d.origins) return LP_E_INVALID;
+    if (!window_ok(0, 0, d.win_h, d.win_w, d.src_h, d.src_w) || !side_ok(d.out_h) || !side_ok(d.out_w)) return LP_E_INVALID;
+    if (!d.src || !d.dst) return LP_E_INVALID;
+    const bool same = d.out_h == d.win_h && d.out_w == d.win_w;
+    if (d.labels && (d.channels != 1 || !d.owner || d.owner_len < 1 || (!same && !d.scratch))) return LP_E_INVALID;
+    if (!same) {
+        if (d.ksize_x <= 0 || d.ksize_y <= 0) return LP_E_INVALID;
+        if (!d.bounds_x || !d.weights_x || !d.bounds_y || !d.weights_y) return LP_E_INVALID;
+        if (!aligned16(d.dst) || (d.labels && !aligned16(d.scratch))) return LP_E_ALIGN;
+    }
+    if (static_cast<int64_t>(d.regions) * d.batch > 65535) return LP_E_UNSUPPORTED;
+    const int images = d.regions * d.batch;
+    const dim3 crop_grid((d.win_w * d.channels + 255) / 256, d.win_h, images);
+    const dim3 tile_grid((d.out_w * d.channels + kResampleTX - 1) / kResampleTX, (d.out_h + kResampleTY - 1) / kResampleTY, images);
+    if (d.labels) {                                               // erased windows: the result, or the resample's source
+        hipLaunchKernelGGL(lp_detail_crop_regions_kernel<true>, crop_grid, dim3(256), 0, stream, d, same ? d.dst : d.scratch);
+        if (!same) {
+            if (hipGetLastError() != hipSuccess) return LP_E_LAUNCH;
+            lp_detail_resample_desc w = {images, d.win_h, d.win_w, 1, 0, 0, d.win_h, d.win_w, d.out_h, d.out_w, d.ksize_x,
+                                         d.ksize_y, d.scratch, d.bounds_x, d.weights_x, d.bounds_y, d.weights_y, d.dst};
+            hipLaunchKernelGGL(lp_detail_resample_kernel, tile_grid, dim3(256), 0, stream, w);
+        }
+    } else if (same) {
+        hipLaunchKernelGGL(lp_detail_crop_regions_kernel<false>, crop_grid, dim3(256), 0, stream, d, d.dst);
+    } else {
+        hipLaunchKernelGGL(lp_detail_resample_regions_kernel, tile_grid, dim3(256), 0, stream, d);
+    }
+    return hipGetLastError() == hipSuccess ? LP_OK : LP_E_LAUNCH;
+}
+
+int detail_stitch_regions_dispatch(const lp_detail_stitch_regions_desc* dp, hipStream_t stream) {
+    if (!dp) return LP_E_INVALID;
+    const lp_detail_stitch_regions_desc& d = *dp;
+    if (d.batch <= 0 || !side_ok(d.height) || !side_ok(d.width) || !chan_ok(d.channels)) return LP_E_INVALID;
+    if (d.regions < 1 || d.regions > LP_DETAIL_MAX_REGIONS || !d.origins) return LP_E_INVALID;
+    for (int r = 0; r < d.regions; ++r)
+        if (!window_ok(d.origins[2 * r], d.origins[2 * r + 1], d.win_h, d.win_w, d.height, d.width)) return LP_E_INVALID;
+    if (d.k < 1 || d.k > 51 || (d.k % 2) == 0) return LP_E_INVALID;
+    if (d.mask_batch != 1 && d.mask_batch != d.batch) return LP_E_INVALID;
+    if (!d.mask || !d.original || !d.detail || !d.out || d.out == d.original) return LP_E_INVALID;
+    if (d.labels && (!d.owner || d.owner_len < 1)) return LP_E_INVALID;
+    if (d.batch > 65535) return LP_E_UNSUPPORTED;
+    const int64_t n = static_cast<int64_t>(d.batch) * d.height * d.width * d.channels;
+    const uint32_t blocks = static_cast<uint32_t>(min(static_cast<int64_t>(kCopyBlocks), (n + 1023) / 1024));
+    if (aligned16(d.original) && aligned16(d.out))
+        hipLaunchKernelGGL(lp_detail_copy_kernel<true>, dim3(blocks), dim3(256), 0, stream, d.original, d.out, n);
+    else
+        hipLaunchKernelGGL(lp_detail_copy_kernel<false>, dim3(blocks), dim3(256), 0, stream, d.original, d.out, n);
+    if (hipGetLastError() != hipSuccess) return LP_E_LAUNCH;
+    const int64_t per_region = static_cast<int64_t>(d.batch) * d.win_h * d.win_w * d.channels;
+    for (int r = 0; r < d.regions; ++r) {                         // in order, in place: out_{r+1} from out_r
+        const lp_detail_stitch_desc s = {d.batch, d.height, d.width, d.channels, d.origins[2 * r], d.origins[2 * r + 1],
+                                         d.win_h, d.win_w, d.k, d.mask_batch, d.mask, d.out, d.detail + r * per_region, d.out};
+        hipError_t err;
+        if (d.labels) {
+            const EraseForeign erase = {d.labels, d.owner, d.owner_len, r + 1};
+            err = (d.k <= 15) ? launch_stitch<16, 64>(lp_detail_stitch_region_kernel<16, 64>, s, stream, erase)
+                              : launch_stitch<8, 32>(lp_detail_stitch_region_kernel<8, 32>, s, stream, erase);
+        } else {
+            err = (d.k <= 15) ? launch_stitch<16, 64>(lp_detail_stitch_kernel<16, 64>, s, stream)
+                              : launch_stitch<8, 32>(lp_detail_stitch_kernel<8, 32>, s, stream);
+        }
+        if (err != hipSuccess) return LP_E_LAUNCH;
+    }
+    return LP_OK;
 }
 
 }  // namespace lp

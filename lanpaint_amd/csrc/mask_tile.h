@@ -6,7 +6,8 @@
 // and the caller finishes with the column blur, m(ty, tx) = smoothed_mask_at(D, g, k, ty, tx).  The reference's 2-D kernel
 // exp(-(x^2+y^2)/(2 s^2))/sum is exactly the outer product of the normalised 1-D profile, so the separable form differs from
 // conv2d only in summation order.  (y0, x0) is the tile's origin in IMAGE coordinates, so padding applies at the image
-// border wherever the tile lies.  256 threads.
+// border wherever the tile lies.  256 threads.  lp_detail_stitch_regions reads the mask through an `Edit` (another region's
+// components erased, detail_kernel.hip); the default, MaskAsIs, is the mask itself.
 #pragma once
 #include "lp_common.h"
 
@@ -18,11 +19,17 @@ constexpr size_t mask_tile_lds_bytes(int k) {
     return sizeof(float) * (static_cast<size_t>(TH + 4 * R) * (TW + 4 * R) + static_cast<size_t>(TH + 4 * R) * (TW + 2 * R) + k);
 }
 
+// How a mask element enters pass A: Edit(value, flat index in the mask plane).  The default takes it as it is.
+struct MaskAsIs {
+    __device__ __forceinline__ float operator()(float v, int64_t) const { return v; }
+};
+
 // Runs passes A..D on `lds` (mask_tile_lds_bytes<TH, TW>(k) bytes).  On return D (CH x TW, CH = TH + 2R, row-blurred) and g
 // (k weights) are valid for every thread; the first AH x AW floats of `lds` (A) are free for the caller.
-template <int TH, int TW>
+template <int TH, int TW, class Edit = MaskAsIs>
 __device__ __forceinline__ void mask_tile_passes(float* lds, const float* __restrict__ mplane, int mask_h, int mask_w,
-                                                 int nn_rule, int k, int x0, int y0, int H, int W, float*& D, float*& g) {
+                                                 int nn_rule, int k, int x0, int y0, int H, int W, float*& D, float*& g,
+                                                 const Edit edit = Edit()) {
     const int R = k / 2;
     const int AW = TW + 4 * R, AH = TH + 4 * R, BW = TW + 2 * R, CH = TH + 2 * R;
     float* A = lds;                   // AH x AW raw mask; later C: CH x BW dilated
@@ -49,7 +56,8 @@ __device__ __forceinline__ void mask_tile_passes(float* lds, const float* __rest
         if (y >= 0 && y < H && x >= 0 && x < W) {
             const int sy = resample ? nearest_exact_index(y, mask_h, H, nn_rule) : y;
             const int sx = resample ? nearest_exact_index(x, mask_w, W, nn_rule) : x;
-            v = mplane[static_cast<int64_t>(sy) * mask_w + sx];
+            const int64_t at = static_cast<int64_t>(sy) * mask_w + sx;
+            v = edit(mplane[at], at);
         }
         A[idx] = v;
     }

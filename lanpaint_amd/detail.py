@@ -14,6 +14,16 @@
 One region serves every frame of the batch (a video is a batch; the sampler needs one shape).  HIP tensors only, no CPU
 fallback; results stay on the device.
 
+Per region, for a mask of several separate areas (two faces at opposite corners share no useful bounding box):
+
+  1. `mask_components`  the mask's 8-connected components on the device (lp_mask_components): a label image that stays there
+                        and a table of boxes and areas read back, the job's one device -> host read;
+  2. `plan_regions`     host integer arithmetic: components grouped into regions, every region a window of one size;
+  3. `crop_regions`     all regions cut out and resampled in one launch (lp_detail_resample_regions), stacked region-major as
+                        one sampler batch; region i sees the mask with the components of other regions erased;
+  4. `stitch_regions`   the detailed crops back, one frame copy, then region after region in order (lp_detail_stitch_regions):
+                        the composition of `stitch` over the regions, bit for bit.
+
 The region rule, in integers.  `bbox = (r0, r1, c0, c1)` are the inclusive first / last row and column of `mask > 0.5` over
 all frames; `r1 < r0` (what lp_mask_bbox returns for an empty mask: (H, -1, W, -1)) raises ValueError.  `context` counts in
 thousandths, `c = round(context * 1000) >= 1000`.  Per axis, with image size N, box [a0, a1], `side = a1 - a0 + 1` and
@@ -26,6 +36,21 @@ M = multiple_of:
   size   target = 0: the working size is the region's own (h, w): no resample.  target > 0: with L = max(h, w), each side s
          becomes  max(1, floor((2 * s * target + L * M) / (2 * L * M))) * M,  i.e. s * target / L rounded to the nearest
          multiple of M, halves up, at least one multiple; the long side becomes `target` when M divides it.
+
+The regions rule, in integers.  Components are (r0, r1, c0, c1, area) with labels 1..n in raster order of their first pixel.
+  keep     components with area >= min_area.  None left: ValueError ("empty" for an empty mask, naming min_area otherwise).
+           Each kept component starts as a group: raw box = its box, members = (its label,).  Groups are always ordered by
+           their smallest member label.
+  close    a group's window is grow + snap above, on both axes, from its raw box.  While some pair of windows shares a pixel,
+           merge the pair lowest in (i, j) order, i < j: union of the raw boxes, union of the members; then start over.
+  limit    while there are more than max_regions groups: merge the pair whose union raw box has the smallest area (ties: lowest
+           i, then lowest j), then close again.
+  equalise h = the largest window height and w = the largest window width over the groups.  Per axis, a window of size n_i at
+           lo in an image of size N becomes  lo -= (n - n_i) // 2;  lo = min(max(lo, 0), N - n).  Every region is now h x w
+           (equalised windows may overlap; stitch_regions composes them in region order).
+  size     (oh, ow) from (h, w, target) by the size rule above: one scale for all regions.
+More than LP_DETAIL_MAX_COMPONENTS components (a noise-like mask, the table is truncated): one region from the mask's bounding
+box, every label a member.  One group holding every component gives exactly plan_region(mask_bbox(mask), ...).
 """
 from __future__ import annotations
 
@@ -78,6 +103,14 @@ def _plan_axis(a0, a1, n_img, c1000, padding, m):
     return lo, hi - lo
 
 
+def _working_size(h, w, m, target):
+    if target <= 0:
+        return h, w
+    long_side = max(h, w)
+    return (max(1, (2 * h * target + long_side * m) // (2 * long_side * m)) * m,
+            max(1, (2 * w * target + long_side * m) // (2 * long_side * m)) * m)
+
+
 def plan_region(bbox, H, W, context=1.0, padding=0, multiple_of=8, target=0):
     """The module docstring's rule: bbox (r0, r1, c0, c1) inclusive -> Region."""
     r0, r1, c0, c1 = (int(v) for v in bbox)
@@ -95,11 +128,7 @@ def plan_region(bbox, H, W, context=1.0, padding=0, multiple_of=8, target=0):
         raise ValueError(f"padding >= 0, multiple_of >= 1 and target >= 0 are required, got {padding}, {m}, {target}")
     y0, h = _plan_axis(r0, r1, H, c1000, padding, m)
     x0, w = _plan_axis(c0, c1, W, c1000, padding, m)
-    oh, ow = h, w
-    if target > 0:
-        long_side = max(h, w)
-        oh = max(1, (2 * h * target + long_side * m) // (2 * long_side * m)) * m
-        ow = max(1, (2 * w * target + long_side * m) // (2 * long_side * m)) * m
+    oh, ow = _working_size(h, w, m, target)
     return Region(y0, x0, h, w, oh, ow, H, W)
 
 
@@ -249,4 +278,248 @@ def stitch(original, detail_img, mask, region, blend_overlap=1, filter="bilinear
                                  m.data_ptr(), orig.data_ptr(), det.data_ptr(), out.data_ptr())
     with torch.cuda.device(dev):
         _cabi.check(_cabi.load().lp_detail_stitch(ctypes.byref(d), raw_stream(dev)), "lp_detail_stitch")
+    return out
+
+
+# ---- per region --------------------------------------------------------------------------------------------------------------
+@dataclasses.dataclass(frozen=True)
+class Regions:
+    """Windows [y0, y0 + h) x [x0, x0 + w) of one size in an H x W image, one per `origins` entry, all detailed at (oh, ow);
+    `members[i]` are the component labels region i owns, ascending."""
+    H: int
+    W: int
+    h: int
+    w: int
+    oh: int
+    ow: int
+    origins: tuple
+    members: tuple
+
+    def __len__(self):
+        return len(self.origins)
+
+    def region(self, i):
+        y0, x0 = self.origins[i]
+        return Region(y0, x0, self.h, self.w, self.oh, self.ow, self.H, self.W)
+
+    @property
+    def resampled(self):
+        return (self.oh, self.ow) != (self.h, self.w)
+
+
+def mask_components(mask):
+    """8-connected components of `mask > 0.5` over every frame of a HIP mask [B, H, W], [1, H, W] or [H, W]:
+    (labels int32 [H, W] on the device, n, table).  Labels run 1..n in raster order of each component's first pixel, 0 is the
+    background (scipy.ndimage.label with a 3 x 3 structure of ones); table[id - 1] = (r0, r1, c0, c1, area), boxes inclusive,
+    for id = 1..min(n, LP_DETAIL_MAX_COMPONENTS).  Reads the table back from the device, nothing else."""
+    m = _as_f32c(_mask3(_hip(mask, "mask")))
+    planes, h, w = m.shape
+    dev = m.device
+    labels = torch.empty((h, w), dtype=torch.int32, device=dev)
+    table = torch.empty(1 + 5 * _cabi.LP_DETAIL_MAX_COMPONENTS, dtype=torch.int32, device=dev)
+    ws_bytes = _cabi.lp_components_ws_bytes(h, w)
+    ws = torch.empty(ws_bytes // 4, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        _cabi.check(_cabi.load().lp_mask_components(m.data_ptr(), planes, h, w, labels.data_ptr(), table.data_ptr(),
+                                                    ws.data_ptr(), ws_bytes, raw_stream(dev)), "lp_mask_components")
+    host = table.cpu().numpy()
+    n = int(host[0])
+    rows = host[1:1 + 5 * min(n, _cabi.LP_DETAIL_MAX_COMPONENTS)].reshape(-1, 5)
+    return labels, n, tuple(tuple(int(v) for v in row) for row in rows)
+
+
+def _close(boxes, members, plan):
+    """The rule's `close`, in place on the parallel lists `boxes` / `members`.  `cur` walks the groups in order with every pair
+    (a, b), a < cur, known to be apart; a merge into `cur` changes only cur's window, so the lowest pair that may newly share a
+    pixel is (a, cur) with the smallest such a -- the walk goes back to it -- or else (cur, j) again."""
+    win = np.array([plan(b) for b in boxes], np.int64).reshape(-1, 4)
+    cur = 0
+    while cur < len(boxes):
+        y0, h, x0, w = win[cur]
+        hit = (win[:, 0] < y0 + h) & (y0 < win[:, 0] + win[:, 1]) & (win[:, 2] < x0 + w) & (x0 < win[:, 2] + win[:, 3])
+        hit[cur] = False
+        below = np.flatnonzero(hit[:cur])
+        if below.size:
+            i, j = int(below[0]), cur
+        else:
+            above = np.flatnonzero(hit[cur + 1:])
+            if not above.size:
+                cur += 1
+                continue
+            i, j = cur, cur + 1 + int(above[0])
+        a, b = boxes[i], boxes[j]
+        boxes[i] = (min(a[0], b[0]), max(a[1], b[1]), min(a[2], b[2]), max(a[3], b[3]))
+        members[i] = tuple(sorted(members[i] + members[j]))
+        del boxes[j], members[j]
+        win = np.delete(win, j, axis=0)
+        win[i] = plan(boxes[i])
+        cur = i
+
+
+def _merge_smallest_union(boxes, members):
+    """The rule's `limit`, one merge: the pair (i, j), i < j, whose union raw box is smallest; ties to the lowest i, then j."""
+    b = np.array(boxes, np.int64)
+    hh = np.maximum(b[:, None, 1], b[None, :, 1]) - np.minimum(b[:, None, 0], b[None, :, 0]) + 1
+    ww = np.maximum(b[:, None, 3], b[None, :, 3]) - np.minimum(b[:, None, 2], b[None, :, 2]) + 1
+    area = hh * ww
+    area[np.tril_indices(len(boxes))] = np.iinfo(np.int64).max
+    i, j = (int(v) for v in np.unravel_index(int(np.argmin(area)), area.shape))      # argmin: the first in row-major order
+    p, q = boxes[i], boxes[j]
+    boxes[i] = (min(p[0], q[0]), max(p[1], q[1]), min(p[2], q[2]), max(p[3], q[3]))
+    members[i] = tuple(sorted(members[i] + members[j]))
+    del boxes[j], members[j]
+
+
+def plan_regions(components, H, W, context=1.0, padding=0, multiple_of=8, target=0, min_area=1, max_regions=8, bbox=None):
+    """The module docstring's regions rule.  `components` = (n, table) as mask_components returns them after the label image
+    (the 3-tuple itself is taken too) -> Regions.  `bbox`, the mask's bounding box (mask_bbox), is needed only when
+    n > LP_DETAIL_MAX_COMPONENTS, where the table is truncated and one region serves the whole mask."""
+    n, table = components[-2], components[-1]
+    n, H, W, padding, m, target = int(n), int(H), int(W), int(padding), int(multiple_of), int(target)
+    min_area, max_regions = int(min_area), int(max_regions)
+    if H <= 0 or W <= 0:
+        raise ValueError(f"image size must be positive, got {H}x{W}")
+    c1000 = int(round(float(context) * 1000))
+    if c1000 < 1000:
+        raise ValueError(f"context must be >= 1.0, got {context!r}")
+    if padding < 0 or m < 1 or target < 0:
+        raise ValueError(f"padding >= 0, multiple_of >= 1 and target >= 0 are required, got {padding}, {m}, {target}")
+    if min_area < 1 or max_regions < 1:
+        raise ValueError(f"min_area >= 1 and max_regions >= 1 are required, got {min_area}, {max_regions}")
+    if n <= 0:
+        raise ValueError("the mask is empty: there is no region to detail")
+    if n > _cabi.LP_DETAIL_MAX_COMPONENTS:
+        if bbox is None:
+            raise ValueError(f"{n} components exceed the table's {_cabi.LP_DETAIL_MAX_COMPONENTS}: pass bbox=mask_bbox(mask) "
+                             "to plan the single region that serves such a mask")
+        r = plan_region(bbox, H, W, context, padding, m, target)
+        return Regions(H, W, r.h, r.w, r.oh, r.ow, ((r.y0, r.x0),), (tuple(range(1, n + 1)),))
+    if len(table) != n:
+        raise ValueError(f"the table holds {len(table)} components, the count says {n}")
+    boxes, members = [], []
+    for label, (r0, r1, c0, c1, area) in enumerate(table, 1):
+        if r0 < 0 or c0 < 0 or r1 >= H or c1 >= W or r1 < r0 or c1 < c0:
+            raise ValueError(f"component {label}'s box {(r0, r1, c0, c1)} lies outside the {H}x{W} image")
+        if area >= min_area:
+            boxes.append((int(r0), int(r1), int(c0), int(c1)))
+            members.append((label,))
+    if not boxes:
+        raise ValueError(f"min_area = {min_area} leaves none of the mask's {n} components: there is no region to detail")
+
+    def plan(box):
+        return _plan_axis(box[0], box[1], H, c1000, padding, m) + _plan_axis(box[2], box[3], W, c1000, padding, m)
+
+    _close(boxes, members, plan)
+    while len(boxes) > max_regions:
+        _merge_smallest_union(boxes, members)
+        _close(boxes, members, plan)
+    win = [plan(b) for b in boxes]
+    h, w = max(v[1] for v in win), max(v[3] for v in win)
+    origins = tuple((min(max(y0 - (h - hi) // 2, 0), H - h), min(max(x0 - (w - wi) // 2, 0), W - w)) for y0, hi, x0, wi in win)
+    oh, ow = _working_size(h, w, m, target)
+    return Regions(H, W, h, w, oh, ow, origins, tuple(members))
+
+
+def _region_tables(regions, labels, dev):
+    """(origins int32 [R, 2] on the device, owner int32 on the device or None): owner[label] = region + 1, 0 for a label no region
+    owns."""
+    origins = torch.tensor(regions.origins, dtype=torch.int32, device=dev).reshape(-1, 2)
+    if labels is None:
+        return origins, None
+    top = max(max(mem) for mem in regions.members)
+    owner = np.zeros(top + 1, np.int32)
+    for i, mem in enumerate(regions.members):
+        owner[np.asarray(mem, np.int64)] = i + 1
+    return origins, torch.from_numpy(owner).to(dev)
+
+
+def _check_regions(regions, labels, H, W):
+    if (regions.H, regions.W) != (H, W):
+        raise ValueError(f"the regions were planned for a {regions.H}x{regions.W} image, got {H}x{W}")
+    if not 1 <= len(regions) <= _cabi.LP_DETAIL_MAX_REGIONS:
+        raise ValueError(f"1..{_cabi.LP_DETAIL_MAX_REGIONS} regions are supported, got {len(regions)}")
+    if labels is not None:
+        _hip(labels, "labels")
+        if labels.dtype != torch.int32 or tuple(labels.shape) != (H, W) or not labels.is_contiguous():
+            raise ValueError(f"labels must be a contiguous int32 [{H}, {W}] tensor (mask_components), got {labels.dtype} "
+                             f"{tuple(labels.shape)}")
+
+
+def _resample_regions(src, regions, origins, filter, labels=None, owner=None):
+    """lp_detail_resample_regions on a contiguous fp32 HIP tensor [B, H, W, C] -> [R * B, oh, ow, C]."""
+    b, sh, sw, c = src.shape
+    g, dev, n_reg = regions, src.device, len(regions)
+    out = torch.empty((n_reg * b, g.oh, g.ow, c), dtype=torch.float32, device=dev)
+    d = _cabi.LpDetailResampleRegionsDesc(b, sh, sw, c, n_reg, g.h, g.w, 0, g.oh, g.ow, 0, 0)
+    d.origins, d.src, d.dst = origins.data_ptr(), src.data_ptr(), out.data_ptr()
+    scratch = None
+    if labels is not None:
+        d.labels, d.owner, d.owner_len = labels.data_ptr(), owner.data_ptr(), owner.numel()
+    if g.resampled:
+        bx, wx = device_tables(_aa_tables_f32, dev, g.w, g.ow, filter)
+        by, wy = device_tables(_aa_tables_f32, dev, g.h, g.oh, filter)
+        d.ksize_x, d.ksize_y = wx.shape[1], wy.shape[1]
+        d.bounds_x, d.weights_x, d.bounds_y, d.weights_y = bx.data_ptr(), wx.data_ptr(), by.data_ptr(), wy.data_ptr()
+        if labels is not None:
+            scratch = torch.empty((n_reg * b, g.h, g.w), dtype=torch.float32, device=dev)
+            d.scratch = scratch.data_ptr()
+    with torch.cuda.device(dev):
+        _cabi.check(_cabi.load().lp_detail_resample_regions(ctypes.byref(d), raw_stream(dev)), "lp_detail_resample_regions")
+    return out
+
+
+def crop_regions(image, mask, regions, labels=None, filter="bilinear"):
+    """crop_resample for every region at once: (image [R * B, oh, ow, C], mask [R * Bm, oh, ow] or None), region-major, so the
+    stack is one sampler batch.  Region i's mask is `mask` with the components of other regions -- and those min_area dropped
+    -- set to 0 (`labels` from mask_components; None: the mask as it is); values at or below 0.5 are nobody's and stay."""
+    _check_filter(filter)
+    img = _as_f32c(_hip(image, "image"))
+    if img.ndim != 4:
+        raise ValueError(f"image must be [B, H, W, C], got {tuple(image.shape)}")
+    H, W = img.shape[1], img.shape[2]
+    _check_regions(regions, labels, H, W)
+    origins, owner = _region_tables(regions, labels, img.device)
+    out = _resample_regions(img, regions, origins, filter)
+    if mask is None:
+        return out, None
+    m = _as_f32c(_mask3(_hip(mask, "mask")).to(img.device))
+    if tuple(m.shape[1:]) != (H, W):
+        raise ValueError(f"mask shape {tuple(mask.shape)} does not match images {tuple(image.shape)}")
+    return out, _resample_regions(m.unsqueeze(-1), regions, origins, "bilinear", labels, owner).squeeze(-1)
+
+
+def stitch_regions(original, detail_imgs, mask, regions, labels=None, blend_overlap=1, filter="bilinear"):
+    """The detailed crops `detail_imgs` [R * B, oh, ow, C] (region-major, as crop_regions stacks them) back into `original`
+    [B, H, W, C].  The result is the composition of `stitch` in region order,  out_0 = original,  out_{i+1} = stitch(out_i,
+    detail_i, mask_i, region i),  bit for bit -- equalised windows may overlap, so the order counts -- computed as one copy of
+    the frame and then each region's window in place."""
+    _check_filter(filter)
+    k = blend_overlap
+    if not isinstance(k, int) or k < 1 or k > 51 or k % 2 == 0:
+        raise ValueError(f"blend_overlap must be an odd integer in [1, 51], got {k!r}")
+    orig = _as_f32c(_hip(original, "original"))
+    det = _as_f32c(_hip(detail_imgs, "detail_imgs").to(orig.device))
+    m = _as_f32c(_mask3(_hip(mask, "mask")).to(orig.device))
+    if orig.ndim != 4 or det.ndim != 4:
+        raise ValueError("original and detail_imgs must be [B, H, W, C]")
+    b, H, W, c = orig.shape
+    _check_regions(regions, labels, H, W)
+    g, n_reg = regions, len(regions)
+    if tuple(det.shape) != (n_reg * b, g.oh, g.ow, c):
+        raise ValueError(f"detail_imgs must be {(n_reg * b, g.oh, g.ow, c)}, got {tuple(det.shape)}")
+    if m.shape[0] not in (1, b) or tuple(m.shape[1:]) != (H, W):
+        raise ValueError(f"mask shape {tuple(mask.shape)} does not match images {tuple(original.shape)}")
+    if g.resampled:
+        det = _resample(det, 0, 0, g.oh, g.ow, g.h, g.w, filter)             # every crop in one launch
+    dev = orig.device
+    _, owner = _region_tables(regions, labels, dev)
+    host_origins = (ctypes.c_int32 * (2 * n_reg))(*(v for o in g.origins for v in o))
+    out = torch.empty_like(orig)
+    d = _cabi.LpDetailStitchRegionsDesc(b, H, W, c, n_reg, g.h, g.w, k, m.shape[0], 0)
+    d.origins = ctypes.cast(host_origins, ctypes.c_void_p)
+    d.mask, d.original, d.detail, d.out = m.data_ptr(), orig.data_ptr(), det.data_ptr(), out.data_ptr()
+    if labels is not None:
+        d.labels, d.owner, d.owner_len = labels.data_ptr(), owner.data_ptr(), owner.numel()
+    with torch.cuda.device(dev):
+        _cabi.check(_cabi.load().lp_detail_stitch_regions(ctypes.byref(d), raw_stream(dev)), "lp_detail_stitch_regions")
     return out
