@@ -249,9 +249,10 @@ int vmask_edt_dispatch(const lp_vmask_edt_desc* dp, hipStream_t stream) {
                        d.keys, d.d2, csum, H, W);
     if (hipGetLastError() != hipSuccess) return LP_E_LAUNCH;
     const size_t lds = 16 + static_cast<size_t>(W) * (sizeof(int32_t) + 2 * sizeof(uint16_t));   // <= 128 KiB + 16
-    if (lds > 64 * 1024)
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&lp_vmask_row_kernel),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    if (lds > 64 * 1024 &&                                       // a refused opt-in is this job's error, not a later launch's
+        hipFuncSetAttribute(reinterpret_cast<const void*>(&lp_vmask_row_kernel),
+                            hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
+        return LP_E_LAUNCH;
     hipLaunchKernelGGL(lp_vmask_row_kernel, dim3(H, 2, K), dim3(kRowBlock), lds, stream, d.d2, H, W);
     if (hipGetLastError() != hipSuccess) return LP_E_LAUNCH;
     const int64_t plane = static_cast<int64_t>(H) * W;

@@ -1,6 +1,7 @@
 """The video mask editor's host side, no GPU needed: widget parsing, the audio-interval rule, the per-frame plan against the
 reference's recorded fixtures (tests/golden/videomask_*.npz, tests/golden/make_videomask_golden.py), Pillow's BILINEAR
-coefficient tables against live PIL, the new C-ABI entries' argument checks, and the node's protocol."""
+coefficient tables against live PIL, the new C-ABI entries' argument checks, the node's protocol, and the float64 arbiter of
+the device tests (tests/videomask_ref.py) pinned bit for bit to the same fixtures."""
 import ctypes
 import glob
 import json
@@ -15,6 +16,7 @@ import torch
 
 from lanpaint_amd import _cabi, videomask
 from lanpaint_amd.videomask import FRAME_DTYPE, frame_plan, parse_keyframes_widget, pillow_bilinear_coeffs
+from tests import videomask_ref as vref
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FIXTURES = sorted(glob.glob(os.path.join(ROOT, "tests", "golden", "videomask_*.npz")))
@@ -162,6 +164,88 @@ def test_pillow_model_reproduces_the_fixture_resize(path):
     by, ky = pillow_bilinear_coeffs(h, oh)
     for t in range(morph.shape[0]):
         assert np.array_equal(_apply((morph[t] * 255).astype(np.uint8), bx, kx, by, ky), z["final_codes"][t])
+
+
+# ---- the arbiter of the device tests (tests/videomask_ref.py) ------------------------------------------------------------------
+@pytest.mark.parametrize("path", FIXTURES, ids=lambda p: os.path.basename(p)[10:-4])
+def test_arbiter_reproduces_every_fixture_bit_for_bit(path):
+    """morph_ref on this project's frame_plan against what the reference recorded: every fp32 bit of `morph`, every code of
+    `morph_codes`.  The arbiter's own error is therefore zero; whatever a device test shows against it is the device's."""
+    z = np.load(path)
+    keys, indices, count = z["keys"], [int(i) for i in z["indices"]], int(z["count"])
+    plan = frame_plan(indices, count, _centroids(keys))[z["frames"]]
+    got = vref.morph_ref(keys, plan)
+    assert got.dtype == np.float32 and got.shape == _fixture_morph(z).shape
+    if "morph" in z:
+        assert np.array_equal(got.view(np.uint32), z["morph"].view(np.uint32))
+    else:
+        assert np.array_equal(vref.codes_ref(got), z["morph_codes"])
+    if "final_codes" in z and "realistic" not in path:
+        pytest.importorskip("PIL.Image")
+        want = z["final_codes"].astype(np.float32) / np.float32(255)
+        assert np.array_equal(vref.pil_resize_ref(vref.codes_ref(got), [int(v) for v in z["size"]]), want)
+
+
+def test_arbiter_codes_of_the_realistic_fixture():
+    z = np.load(os.path.join(ROOT, "tests", "golden", "videomask_realistic.npz"))
+    keys, indices = z["keys"], [int(i) for i in z["indices"]]
+    plan = frame_plan(indices, int(z["count"]), _centroids(keys))[z["frames"]]
+    assert (plan["kind"] == _cabi.LP_VMASK_INNER).any()
+    codes = vref.codes_ref(vref.morph_ref(keys, plan))
+    assert codes.dtype == np.uint8 and np.array_equal(codes, z["morph_codes"])
+
+
+def test_arbiter_shift():
+    f = np.arange(1.0, 13.0).reshape(3, 4)                 # no zero among the values: a vacated pixel is recognisable
+    assert np.array_equal(vref.shift_ref(f, 0, 0), f)
+    assert np.array_equal(vref.shift_ref(f, 1, 0), [[0, 0, 0, 0], [1, 2, 3, 4], [5, 6, 7, 8]])
+    assert np.array_equal(vref.shift_ref(f, -1, 0), [[5, 6, 7, 8], [9, 10, 11, 12], [0, 0, 0, 0]])
+    assert np.array_equal(vref.shift_ref(f, 0, 1), [[0, 1, 2, 3], [0, 5, 6, 7], [0, 9, 10, 11]])
+    assert np.array_equal(vref.shift_ref(f, 0, -3), [[4, 0, 0, 0], [8, 0, 0, 0], [12, 0, 0, 0]])
+    assert np.array_equal(vref.shift_ref(f, 2, -1), [[0, 0, 0, 0], [0, 0, 0, 0], [2, 3, 4, 0]])
+    assert np.array_equal(vref.shift_ref(f, -2, 3), [[0, 0, 0, 9], [0, 0, 0, 0], [0, 0, 0, 0]])
+    for dy, dx in ((3, 0), (-3, 0), (0, 4), (0, -4), (3, 4), (-3, -4), (100, 1), (1, -100), (-7, 9), (2, 4), (-3, 1)):
+        assert not vref.shift_ref(f, dy, dx).any(), (dy, dx)             # past the frame in either direction: all vacated
+    out = vref.shift_ref(f, 1, 1)
+    assert out.dtype == f.dtype and out is not f and f[0, 0] == 1.0
+    g = np.arange(1.0, 6.0).reshape(1, 5)
+    assert np.array_equal(vref.shift_ref(g, 0, 2), [[0, 0, 1, 2, 3]]) and not vref.shift_ref(g, 1, 0).any()
+    for dy in range(-4, 5):                                # the definition, element by element
+        for dx in range(-5, 6):
+            out = vref.shift_ref(f, dy, dx)
+            for y in range(3):
+                for x in range(4):
+                    inside = 0 <= y - dy < 3 and 0 <= x - dx < 4
+                    assert out[y, x] == (f[y - dy, x - dx] if inside else 0.0)
+
+
+def test_arbiter_sdf_rules():
+    assert np.array_equal(vref.sdf_ref(np.zeros((3, 8), np.float32)), np.full((3, 8), -4.0))
+    assert np.array_equal(vref.sdf_ref(np.ones((9, 2), np.float32)), np.full((9, 2), 4.5))
+    half, below = np.float32(0.5), np.nextafter(np.float32(0.5), np.float32(0))
+    assert np.array_equal(vref.sdf_ref(np.full((2, 2), half)), np.full((2, 2), 1.0))                # 0.5 is foreground
+    assert np.array_equal(vref.sdf_ref(np.full((2, 2), below)), np.full((2, 2), -1.0))
+    k = np.zeros((1, 5), np.float32)
+    k[0, 1:3] = 1.0
+    assert vref.sdf_ref(k).tolist() == [[-1.0, 1.0, 1.0, -1.0, -2.0]]
+    k = np.zeros((4, 4), np.float32)
+    k[0, 0] = 0.75
+    assert vref.sdf_ref(k)[3, 3] == -np.sqrt(18.0) and vref.sdf_ref(k)[0, 0] == 1.0
+
+
+def test_arbiter_own_edt_equals_scipy():
+    ndimage = pytest.importorskip("scipy.ndimage")
+    rng = np.random.default_rng(21)
+    for h, w in ((1, 1), (1, 40), (40, 1), (17, 23), (64, 64), (31, 200)):
+        for p in (0.02, 0.5, 0.98):
+            a = rng.random((h, w)) < p
+            a.flat[rng.integers(a.size)] = False           # a pixel to measure to
+            assert np.array_equal(vref.edt_numpy(a), ndimage.distance_transform_edt(a)), (h, w, p)
+    a = np.ones((50, 70), bool)
+    a[49, 0] = False
+    assert np.array_equal(vref.edt_numpy(a), ndimage.distance_transform_edt(a))
+    assert vref.edt_numpy(a)[0, 69] == np.sqrt(49.0 ** 2 + 69.0 ** 2)
+
 
 
 # ---- the C ABI -------------------------------------------------------------------------------------------------------------
