@@ -878,6 +878,55 @@ typedef struct lp_detail_stitch_regions_desc {
 } lp_detail_stitch_regions_desc;
 LP_API int lp_detail_stitch_regions(const lp_detail_stitch_regions_desc* desc, void* stream);
 
+/* ---- Detailer that follows a moving mask (beyond the reference, like the Detailer itself) --------------------------------------
+ * A video mask moves: the union box of a small subject that crosses the frame is most of the frame.  Here every frame gets a
+ * window of its own, all of one size, so the crops still stack as one sampler batch.  The host (lanpaint_amd/detail.py,
+ * plan_track) plans the windows' path from one box per frame.                                                                */
+
+/* lp_mask_bbox per plane:  row p of `boxes` is what lp_mask_bbox returns for plane p alone.
+ *   mask   [planes, height, width] fp32
+ *   boxes  out, device, int32 [planes, 4] = {row_min, row_max, col_min, col_max}, inclusive; {height, -1, width, -1} for a plane
+ *          with no element set.  Initialised by this call.
+ * One launch over every plane (planes on a grid axis), integer atomics only.  Limits and errors as lp_mask_bbox.            */
+LP_API int lp_mask_bbox_frames(const float* mask, int32_t planes, int32_t height, int32_t width, int32_t* boxes, void* stream);
+
+/* lp_detail_resample with a window per image:  dst [batch, out_h, out_w, channels], dst[b] = lp_detail_resample of the window at
+ * origins[b] of src[b], bit for bit, in one launch.
+ *   origins  DEVICE int32 [batch, 2] = (y0, x0); an origin is clamped so that its window lies inside the image
+ * Same size in and out copies the windows bit for bit and reads no tap table.  Errors as lp_detail_resample, plus
+ * LP_E_INVALID: null origins.                                                                                                */
+typedef struct lp_detail_resample_track_desc {
+    int32_t batch, src_h, src_w, channels;
+    int32_t win_h, win_w, out_h, out_w;
+    int32_t ksize_x, ksize_y;
+    const int32_t* origins;
+    const float*   src;
+    const int32_t* bounds_x;
+    const float*   weights_x;
+    const int32_t* bounds_y;
+    const float*   weights_y;
+    float*         dst;
+} lp_detail_resample_track_desc;
+LP_API int lp_detail_resample_track(const lp_detail_resample_track_desc* desc, void* stream);
+
+/* lp_detail_stitch with a window per image:  out[b] = lp_detail_stitch(original[b], detail[b], mask[b or 0], window at
+ * origins[b]), bit for bit; outside image b's window out[b] is original[b] bit for bit.  Two launches whatever the batch: the
+ * streaming copy original -> out, then the tiles of every image's window (the image on a grid axis).  Images do not overlap
+ * each other, so there is no order to keep.
+ *   origins  DEVICE int32 [batch, 2] = (y0, x0), clamped as above
+ *   detail   [batch, win_h, win_w, channels], already at the window's size
+ * Errors as lp_detail_stitch, plus LP_E_INVALID: null origins.                                                               */
+typedef struct lp_detail_stitch_track_desc {
+    int32_t batch, height, width, channels;
+    int32_t win_h, win_w, k, mask_batch;
+    const int32_t* origins;
+    const float*   mask;
+    const float*   original;
+    const float*   detail;
+    float*         out;
+} lp_detail_stitch_track_desc;
+LP_API int lp_detail_stitch_track(const lp_detail_stitch_track_desc* desc, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

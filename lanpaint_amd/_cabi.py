@@ -207,6 +207,21 @@ class LpDetailStitchRegionsDesc(C.Structure):
                 ("out", C.c_void_p), ("labels", C.c_void_p), ("owner", C.c_void_p)]
 
 
+class LpDetailResampleTrackDesc(C.Structure):
+    _fields_ = [("batch", C.c_int32), ("src_h", C.c_int32), ("src_w", C.c_int32), ("channels", C.c_int32),
+                ("win_h", C.c_int32), ("win_w", C.c_int32), ("out_h", C.c_int32), ("out_w", C.c_int32),
+                ("ksize_x", C.c_int32), ("ksize_y", C.c_int32),
+                ("origins", C.c_void_p), ("src", C.c_void_p), ("bounds_x", C.c_void_p), ("weights_x", C.c_void_p),
+                ("bounds_y", C.c_void_p), ("weights_y", C.c_void_p), ("dst", C.c_void_p)]
+
+
+class LpDetailStitchTrackDesc(C.Structure):
+    _fields_ = [("batch", C.c_int32), ("height", C.c_int32), ("width", C.c_int32), ("channels", C.c_int32),
+                ("win_h", C.c_int32), ("win_w", C.c_int32), ("k", C.c_int32), ("mask_batch", C.c_int32),
+                ("origins", C.c_void_p), ("mask", C.c_void_p), ("original", C.c_void_p), ("detail", C.c_void_p),
+                ("out", C.c_void_p)]
+
+
 def lp_components_ws_bytes(height, width):
     """LP_COMPONENTS_WS_BYTES of include/lanpaint_hip.h."""
     return ((int(height) * int(width) + 1023) // 1024) * 4100
@@ -262,6 +277,9 @@ EXPORTS = {
                                      C.c_void_p]),
     "lp_detail_resample_regions": (C.c_int, [C.POINTER(LpDetailResampleRegionsDesc), C.c_void_p]),
     "lp_detail_stitch_regions": (C.c_int, [C.POINTER(LpDetailStitchRegionsDesc), C.c_void_p]),
+    "lp_mask_bbox_frames": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    "lp_detail_resample_track": (C.c_int, [C.POINTER(LpDetailResampleTrackDesc), C.c_void_p]),
+    "lp_detail_stitch_track": (C.c_int, [C.POINTER(LpDetailStitchTrackDesc), C.c_void_p]),
 }
 
 

@@ -41,6 +41,9 @@ int mask_components_dispatch(const float* mask, int planes, int H, int W, int32_
                              int64_t workspace_bytes, hipStream_t stream);
 int detail_resample_regions_dispatch(const lp_detail_resample_regions_desc* d, hipStream_t stream);
 int detail_stitch_regions_dispatch(const lp_detail_stitch_regions_desc* d, hipStream_t stream);
+int mask_bbox_frames_dispatch(const float* mask, int planes, int H, int W, int32_t* boxes, hipStream_t stream);
+int detail_resample_track_dispatch(const lp_detail_resample_track_desc* d, hipStream_t stream);
+int detail_stitch_track_dispatch(const lp_detail_stitch_track_desc* d, hipStream_t stream);
 int reshape_mask_dispatch(const float* src, int sb, int sc, int sf, int sh, int sw, float* dst, int db, int dc, int df,
                           int dh, int dw, int taps, int flags, hipStream_t stream);
 }  // namespace lp
@@ -121,6 +124,18 @@ int lp_detail_resample_regions(const lp_detail_resample_regions_desc* desc, void
 
 int lp_detail_stitch_regions(const lp_detail_stitch_regions_desc* desc, void* stream) {
     return lp::detail_stitch_regions_dispatch(desc, as_stream(stream));
+}
+
+int lp_mask_bbox_frames(const float* mask, int32_t planes, int32_t height, int32_t width, int32_t* boxes, void* stream) {
+    return lp::mask_bbox_frames_dispatch(mask, planes, height, width, boxes, as_stream(stream));
+}
+
+int lp_detail_resample_track(const lp_detail_resample_track_desc* desc, void* stream) {
+    return lp::detail_resample_track_dispatch(desc, as_stream(stream));
+}
+
+int lp_detail_stitch_track(const lp_detail_stitch_track_desc* desc, void* stream) {
+    return lp::detail_stitch_track_dispatch(desc, as_stream(stream));
 }
 
 

@@ -11,8 +11,8 @@
                       MaskBlend-smoothed mask of the whole image (lp_detail_stitch); outside the region the result is the
                       original bit for bit.
 
-One region serves every frame of the batch (a video is a batch; the sampler needs one shape).  HIP tensors only, no CPU
-fallback; results stay on the device.
+One region serves every frame of the batch (a video is a batch; the sampler needs one shape); the per-frame form below
+moves a window of one size with the mask instead.  HIP tensors only, no CPU fallback; results stay on the device.
 
 Per region, for a mask of several separate areas (two faces at opposite corners share no useful bounding box):
 
@@ -51,6 +51,33 @@ The regions rule, in integers.  Components are (r0, r1, c0, c1, area) with label
   size     (oh, ow) from (h, w, target) by the size rule above: one scale for all regions.
 More than LP_DETAIL_MAX_COMPONENTS components (a noise-like mask, the table is truncated): one region from the mask's bounding
 box, every label a member.  One group holding every component gives exactly plan_region(mask_bbox(mask), ...).
+
+Per frame, for a mask that moves through a video (a small subject crossing the frame has a union box that is most of the
+frame):
+
+  1. `mask_bbox_frames`  one bounding box per frame on the device (lp_mask_bbox_frames, one launch), the [frames, 4] table read
+                         back: the job's one device -> host read;
+  2. `plan_track`        host integer arithmetic: one window size for the clip and a smoothed path of origins, one per frame;
+  3. `crop_track`        every frame's window cut out and resampled in one launch (lp_detail_resample_track);
+  4. `stitch_track`      the detailed crops back, one frame copy, then every frame's window in one launch
+                         (lp_detail_stitch_track): `stitch` frame by frame, bit for bit.
+
+The track rule, in integers, per axis.  Image size N, frame f's box [a0_f, a1_f] (empty for a frame without a set element),
+F frames, c as above, M = multiple_of, k = smooth (odd, >= 1), r = k // 2.  Every division is floor division.
+  centre   s_f = a0_f + a1_f + 1, twice the box centre; a window [lo, lo + n) has twice-centre 2 * lo + n.
+  fill     an empty frame takes s_f by linear interpolation between the nearest non-empty frames before it (p) and after it
+           (q):  s_p + ((s_q - s_p) * (f - p)) // (q - p);  before the first / after the last non-empty frame it holds that
+           frame's value.  Every frame empty: ValueError ("the mask is empty ...").
+  size     side = the largest a1_f - a0_f + 1 over non-empty frames;  g = padding + ceil((c - 1000) * side / 2000);
+           n = min(side + 2 * g, N);  need = ceil(n / M) * M.  If need <= N, n = need; else n stays as grown and is not a
+           multiple (as in the region rule).
+  smooth   S_f = sum over j = -r..r of s_clamp(f + j, 0, F - 1);  lo_f = (S_f - k * n) // (2 * k).
+  contain  non-empty frames only:  lo_f = min(lo_f, a0_f);  lo_f = max(lo_f, a1_f + 1 - n).  n >= side, so both hold: however
+           strong the smoothing, a frame's own mask stays inside its window.
+  clamp    lo_f = min(max(lo_f, 0), N - n).
+  size     (oh, ow) from (h, w, target) by the size rule above: one scale for the whole clip.
+A single box with `frames` = B (a static one-plane mask on a batch of B images) stands for B equal boxes and gives B equal
+origins.
 """
 from __future__ import annotations
 
@@ -522,4 +549,199 @@ def stitch_regions(original, detail_imgs, mask, regions, labels=None, blend_over
         d.labels, d.owner, d.owner_len = labels.data_ptr(), owner.data_ptr(), owner.numel()
     with torch.cuda.device(dev):
         _cabi.check(_cabi.load().lp_detail_stitch_regions(ctypes.byref(d), raw_stream(dev)), "lp_detail_stitch_regions")
+    return out
+
+
+# ---- per frame: a window that follows a moving mask --------------------------------------------------------------------------------
+@dataclasses.dataclass(frozen=True)
+class Track:
+    """Windows [y0, y0 + h) x [x0, x0 + w) of one size in an H x W image, frame f's at `origins[f]`, all detailed at (oh, ow)."""
+    H: int
+    W: int
+    h: int
+    w: int
+    oh: int
+    ow: int
+    origins: tuple
+
+    def __len__(self):
+        return len(self.origins)
+
+    def region(self, f):
+        y0, x0 = self.origins[f]
+        return Region(y0, x0, self.h, self.w, self.oh, self.ow, self.H, self.W)
+
+    @property
+    def resampled(self):
+        return (self.oh, self.ow) != (self.h, self.w)
+
+
+def _track_axis(spans, n_img, c1000, padding, m, k):
+    """One axis of the track rule: spans[f] = (a0, a1) inclusive, or None for an empty frame -> (origins, n)."""
+    frames = len(spans)
+    full = [f for f, span in enumerate(spans) if span is not None]
+    s = [None if span is None else span[0] + span[1] + 1 for span in spans]
+    for f in range(frames):                                               # fill
+        if s[f] is None:
+            before = [p for p in full if p < f]
+            after = [q for q in full if q > f]
+            if before and after:
+                p, q = before[-1], after[0]
+                s[f] = s[p] + ((s[q] - s[p]) * (f - p)) // (q - p)
+            else:
+                s[f] = s[before[-1] if before else after[0]]
+    side = max(spans[f][1] - spans[f][0] + 1 for f in full)               # size
+    g = padding + _ceil_div((c1000 - 1000) * side, 2000)
+    n = min(side + 2 * g, n_img)
+    need = _ceil_div(n, m) * m
+    if need <= n_img:
+        n = need
+    origins = []
+    for f in range(frames):
+        total = sum(s[min(max(f + j, 0), frames - 1)] for j in range(-(k // 2), k // 2 + 1))     # smooth
+        lo = (total - k * n) // (2 * k)
+        if spans[f] is not None:                                          # contain
+            lo = max(min(lo, spans[f][0]), spans[f][1] + 1 - n)
+        origins.append(min(max(lo, 0), n_img - n))                        # clamp
+    return origins, n
+
+
+def plan_track(boxes, H, W, context=1.0, padding=0, multiple_of=8, target=0, smooth=1, frames=None):
+    """The module docstring's track rule: one box (r0, r1, c0, c1) per frame, inclusive, empty frames as lp_mask_bbox marks
+    them (r1 < r0) -> Track.  `frames` is the length of the batch the track serves: len(boxes) when not given, and a single
+    box is repeated to it (a static mask)."""
+    boxes = [tuple(int(v) for v in box) for box in boxes]
+    H, W, padding, m, target = int(H), int(W), int(padding), int(multiple_of), int(target)
+    if H <= 0 or W <= 0:
+        raise ValueError(f"image size must be positive, got {H}x{W}")
+    c1000 = int(round(float(context) * 1000))
+    if c1000 < 1000:
+        raise ValueError(f"context must be >= 1.0, got {context!r}")
+    if padding < 0 or m < 1 or target < 0:
+        raise ValueError(f"padding >= 0, multiple_of >= 1 and target >= 0 are required, got {padding}, {m}, {target}")
+    if isinstance(smooth, bool) or int(smooth) != smooth or smooth < 1 or smooth % 2 == 0:
+        raise ValueError(f"smooth must be an odd integer >= 1, got {smooth!r}")
+    frames = len(boxes) if frames is None else int(frames)
+    if frames < 1 or len(boxes) not in (1, frames) or any(len(box) != 4 for box in boxes):
+        raise ValueError(f"one box of four integers per frame, or a single one, is required: got {len(boxes)} for {frames} frames")
+    if len(boxes) != frames:
+        boxes = boxes * frames
+    rows, cols = [], []
+    for f, (r0, r1, c0, c1) in enumerate(boxes):
+        if r1 < r0 or c1 < c0:
+            rows.append(None)
+            cols.append(None)
+            continue
+        if r0 < 0 or c0 < 0 or r1 >= H or c1 >= W:
+            raise ValueError(f"frame {f}'s box {(r0, r1, c0, c1)} lies outside the {H}x{W} image")
+        rows.append((r0, r1))
+        cols.append((c0, c1))
+    if all(span is None for span in rows):
+        raise ValueError("the mask is empty in every frame: there is no region to detail")
+    ys, h = _track_axis(rows, H, c1000, padding, m, int(smooth))
+    xs, w = _track_axis(cols, W, c1000, padding, m, int(smooth))
+    oh, ow = _working_size(h, w, m, target)
+    return Track(H, W, h, w, oh, ow, tuple(zip(ys, xs)))
+
+
+def mask_bbox_frames(mask):
+    """`mask_bbox` of every frame on its own, in one launch: a tuple of (row_min, row_max, col_min, col_max), one per plane of a
+    HIP mask [B, H, W], [1, H, W] or [H, W]; (H, -1, W, -1) for a frame with nothing set.  Reads the [B, 4] table back."""
+    m = _as_f32c(_mask3(_hip(mask, "mask")))
+    planes, h, w = m.shape
+    dev = m.device
+    boxes = torch.empty((planes, 4), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        _cabi.check(_cabi.load().lp_mask_bbox_frames(m.data_ptr(), planes, h, w, boxes.data_ptr(), raw_stream(dev)),
+                    "lp_mask_bbox_frames")
+    return tuple(tuple(row) for row in boxes.cpu().tolist())
+
+
+def _check_track(track, batch, H, W):
+    if (track.H, track.W) != (H, W):
+        raise ValueError(f"the track was planned for a {track.H}x{track.W} image, got {H}x{W}")
+    if len(track) != batch:
+        raise ValueError(f"the track holds {len(track)} frames, the batch {batch}")
+    if not (0 < track.h <= H and 0 < track.w <= W):
+        raise ValueError(f"a {track.h}x{track.w} window does not fit the {H}x{W} image")
+    for f, (y0, x0) in enumerate(track.origins):
+        if y0 < 0 or x0 < 0 or y0 + track.h > H or x0 + track.w > W:
+            raise ValueError(f"frame {f}'s window at {(y0, x0)} leaves the {H}x{W} image")
+
+
+def _track_origins(track, dev):
+    return torch.tensor(track.origins, dtype=torch.int32, device=dev).reshape(-1, 2)
+
+
+def _resample_track(src, track, origins, filter):
+    """lp_detail_resample_track on a contiguous fp32 HIP tensor [B, H, W, C] -> [B, oh, ow, C]."""
+    b, sh, sw, c = src.shape
+    t, dev = track, src.device
+    out = torch.empty((b, t.oh, t.ow, c), dtype=torch.float32, device=dev)
+    d = _cabi.LpDetailResampleTrackDesc(b, sh, sw, c, t.h, t.w, t.oh, t.ow, 0, 0)
+    d.origins, d.src, d.dst = origins.data_ptr(), src.data_ptr(), out.data_ptr()
+    if t.resampled:
+        bx, wx = device_tables(_aa_tables_f32, dev, t.w, t.ow, filter)
+        by, wy = device_tables(_aa_tables_f32, dev, t.h, t.oh, filter)
+        d.ksize_x, d.ksize_y = wx.shape[1], wy.shape[1]
+        d.bounds_x, d.weights_x, d.bounds_y, d.weights_y = bx.data_ptr(), wx.data_ptr(), by.data_ptr(), wy.data_ptr()
+    with torch.cuda.device(dev):
+        _cabi.check(_cabi.load().lp_detail_resample_track(ctypes.byref(d), raw_stream(dev)), "lp_detail_resample_track")
+    return out
+
+
+def crop_track(image, mask, track, filter="bilinear"):
+    """crop_resample with frame f cut at `track.region(f)`: (image [B, oh, ow, C], mask [Bm, oh, ow] or None), each frame what
+    crop_resample gives for it alone, bit for bit.  A one-plane mask stays one plane while the track stands still (plan_track
+    of a static mask); under a track that moves it is cut once per frame, [B, oh, ow]."""
+    _check_filter(filter)
+    img = _as_f32c(_hip(image, "image"))
+    if img.ndim != 4:
+        raise ValueError(f"image must be [B, H, W, C], got {tuple(image.shape)}")
+    b, H, W = img.shape[0], img.shape[1], img.shape[2]
+    _check_track(track, b, H, W)
+    origins = _track_origins(track, img.device)
+    out = _resample_track(img, track, origins, filter)
+    if mask is None:
+        return out, None
+    m = _mask3(_hip(mask, "mask")).to(img.device)
+    if m.shape[0] not in (1, b) or tuple(m.shape[1:]) != (H, W):
+        raise ValueError(f"mask shape {tuple(mask.shape)} does not match images {tuple(image.shape)}")
+    if m.shape[0] != b:
+        if len(set(track.origins)) == 1:
+            origins = origins[:1]
+        else:
+            m = m.expand(b, H, W)
+    return out, _resample_track(_as_f32c(m).unsqueeze(-1), track, origins, "bilinear").squeeze(-1)
+
+
+def stitch_track(original, detail_img, mask, track, blend_overlap=1, filter="bilinear"):
+    """`stitch` with frame f's crop put back at `track.region(f)`: the detailed crops `detail_img` [B, oh, ow, C] into
+    `original` [B, H, W, C], frame by frame what `stitch` gives, bit for bit, as one copy of the frames and one launch over
+    every frame's window.  `mask` [B, H, W] or one plane for all frames."""
+    _check_filter(filter)
+    k = blend_overlap
+    if not isinstance(k, int) or k < 1 or k > 51 or k % 2 == 0:
+        raise ValueError(f"blend_overlap must be an odd integer in [1, 51], got {k!r}")
+    orig = _as_f32c(_hip(original, "original"))
+    det = _as_f32c(_hip(detail_img, "detail_img").to(orig.device))
+    m = _as_f32c(_mask3(_hip(mask, "mask")).to(orig.device))
+    if orig.ndim != 4 or det.ndim != 4:
+        raise ValueError("original and detail_img must be [B, H, W, C]")
+    b, H, W, c = orig.shape
+    _check_track(track, b, H, W)
+    t = track
+    if tuple(det.shape) != (b, t.oh, t.ow, c):
+        raise ValueError(f"detail_img must be {(b, t.oh, t.ow, c)}, got {tuple(det.shape)}")
+    if m.shape[0] not in (1, b) or tuple(m.shape[1:]) != (H, W):
+        raise ValueError(f"mask shape {tuple(mask.shape)} does not match images {tuple(original.shape)}")
+    if t.resampled:
+        det = _resample(det, 0, 0, t.oh, t.ow, t.h, t.w, filter)
+    dev = orig.device
+    origins = _track_origins(t, dev)
+    out = torch.empty_like(orig)
+    d = _cabi.LpDetailStitchTrackDesc(b, H, W, c, t.h, t.w, k, m.shape[0],
+                                      origins.data_ptr(), m.data_ptr(), orig.data_ptr(), det.data_ptr(), out.data_ptr())
+    with torch.cuda.device(dev):
+        _cabi.check(_cabi.load().lp_detail_stitch_track(ctypes.byref(d), raw_stream(dev)), "lp_detail_stitch_track")
     return out
