@@ -927,6 +927,83 @@ typedef struct lp_detail_stitch_track_desc {
 } lp_detail_stitch_track_desc;
 LP_API int lp_detail_stitch_track(const lp_detail_stitch_track_desc* desc, void* stream);
 
+/* ---- Detailer colour match (beyond the reference, like the Detailer itself) -----------------------------------------------------
+ * A crop that went through resample, VAE, sampler and VAE comes back with a small gain and offset per channel.  Outside the
+ * mask the decoded crop shows what the original crop shows, so statistics taken there are like for like: three calls between
+ * decode and any of the stitches measure the drift (lp_color_stats), turn it into one affine map per image and channel
+ * (lp_color_fit) and undo it (lp_color_apply).  Everything stays on the device; nothing is read back.
+ * Sides are 1..LP_DETAIL_MAX_SIDE, channels 1..LP_DETAIL_MAX_CHANNELS, margin 0..LP_COLOR_MAX_MARGIN.                        */
+#define LP_COLOR_MIN_COUNT  64    /* lp_color_fit: a pooled window with fewer kept pixels than this fits nothing (gain 1, bias 0) */
+#define LP_COLOR_MAX_MARGIN 25
+#define LP_COLOR_TILE_H     32    /* lp_color_stats: one block and one partial row per tile of this many pixels                */
+#define LP_COLOR_TILE_W     128
+#define LP_COLOR_METHOD_MEAN     0
+#define LP_COLOR_METHOD_MEAN_STD 1
+
+/* Masked sums of two images over the pixels far enough from the mask.
+ *   detail, reference  [batch, height, width, channels] fp32
+ *   mask     [mask_batch, height, width] fp32, mask_batch 1 or batch; or NULL: every pixel is kept (mask_batch is not read)
+ *   keep     pixel (y, x) of image i is kept when every mask element of that image with |y' - y| <= margin and |x' - x| <= margin
+ *            inside the image is <= 0.5; neighbours outside the image do not count
+ *   stats    out, device, fp64 [batch, 1 + 4 * channels]: row i = {n, then per channel sum d, sum r, sum d^2, sum r^2} over the
+ *            kept pixels of image i.  n is an exact integer.
+ *   workspace  device, LP_COLOR_WS_BYTES(batch, height, width, channels) bytes, 16-byte aligned: one partial row per tile
+ * Every term is converted to fp64 first, so a square is exact, and is added in fp64 from the first add, each operation rounded
+ * on its own.  Two plain launches on `stream` (csrc/color_kernel.hip): the tiles, each with the mask's halo as bits in LDS,
+ * write their partial rows; the second folds an image's partial rows in a fixed order.  No floating-point atomic anywhere: the
+ * result is the same bits on every run.
+ * LP_E_INVALID: null pointer, batch <= 0, a side, the channel count or margin outside the limits, mask_batch, a short
+ * workspace; LP_E_ALIGN: workspace not 16-byte aligned; LP_E_UNSUPPORTED: batch > 65535.  All checked before any HIP call.  */
+#define LP_COLOR_WS_BYTES(batch, height, width, channels)                                                  \
+    ((int64_t)(batch) * (((height) + LP_COLOR_TILE_H - 1) / LP_COLOR_TILE_H) *                             \
+     (((width) + LP_COLOR_TILE_W - 1) / LP_COLOR_TILE_W) * (1 + 4 * (channels)) * 8)
+typedef struct lp_color_stats_desc {
+    int32_t batch, height, width, channels;
+    int32_t mask_batch, margin;
+    const float* detail;
+    const float* reference;
+    const float* mask;
+    double*      stats;
+    void*        workspace;
+    int64_t      workspace_bytes;
+} lp_color_stats_desc;
+LP_API int lp_color_stats(const lp_color_stats_desc* desc, void* stream);
+
+/* stats [batch, 1 + 4 * channels] -> coef, device, fp32 [batch, channels, 2] = (gain, bias).  One launch, fp64, every operation
+ * rounded on its own.  With L = clip_frames (0: L = batch; L must divide batch), k = smooth (0, or odd 1..129), s = strength:
+ *   pool      image i is frame f = i % L of clip q = i / L.  P = the sum, in ascending frame order, of the stats rows of frames
+ *             max(0, f - k / 2) .. min(L - 1, f + k / 2) of clip q (k = 0: of the whole clip).  The window is cut at the clip's
+ *             ends, not clamped: no frame is counted twice.
+ *   guard     N = P.n < LP_COLOR_MIN_COUNT: gain = 1, bias = 0
+ *   moments   per channel  md = P.d / N, mr = P.r / N, vd = P.dd / N - md * md, vr = P.rr / N - mr * mr
+ *   gain      LP_COLOR_METHOD_MEAN: g = 1.  LP_COLOR_METHOD_MEAN_STD: g = 1 when vd <= 1e-8 or vr is not >= 0, otherwise
+ *             g = sqrt(vr / vd) limited to [0.25, 4]
+ *   bias      b = mr - g * md
+ *   strength  gain = 1 + s * (g - 1), bias = s * b  (lerp(detail, matched, s)), both then rounded to fp32
+ * LP_E_INVALID: null pointer, batch <= 0, channels outside the limits, clip_frames < 0 or not a divisor of batch, smooth even
+ * (other than 0) or outside 0..129, an unknown method, strength outside [0, 1]; LP_E_UNSUPPORTED: batch > 65535.             */
+typedef struct lp_color_fit_desc {
+    int32_t batch, channels;
+    int32_t clip_frames, smooth;
+    int32_t method, reserved0;
+    double  strength;
+    const double* stats;
+    float*        coef;
+} lp_color_fit_desc;
+LP_API int lp_color_fit(const lp_color_fit_desc* desc, void* stream);
+
+/* out[i, y, x, c] = fadd_rn(fmul_rn(detail[i, y, x, c], coef[i, c, 0]), coef[i, c, 1]), unfused.  One launch, 16 bytes per lane
+ * when detail, out and every image's first element are 16-byte aligned.  out may be detail.
+ *   detail, out  [batch, height, width, channels] fp32;  coef  [batch, channels, 2] fp32 (lp_color_fit)
+ * LP_E_INVALID: null pointer, batch <= 0, a side or the channel count outside the limits; LP_E_UNSUPPORTED: batch > 65535.  */
+typedef struct lp_color_apply_desc {
+    int32_t batch, height, width, channels;
+    const float* detail;
+    const float* coef;
+    float*       out;
+} lp_color_apply_desc;
+LP_API int lp_color_apply(const lp_color_apply_desc* desc, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -222,6 +222,34 @@ class LpDetailStitchTrackDesc(C.Structure):
                 ("out", C.c_void_p)]
 
 
+LP_COLOR_MIN_COUNT, LP_COLOR_MAX_MARGIN, LP_COLOR_TILE_H, LP_COLOR_TILE_W = 64, 25, 32, 128
+LP_COLOR_METHOD_MEAN, LP_COLOR_METHOD_MEAN_STD = 0, 1
+
+
+class LpColorStatsDesc(C.Structure):
+    _fields_ = [("batch", C.c_int32), ("height", C.c_int32), ("width", C.c_int32), ("channels", C.c_int32),
+                ("mask_batch", C.c_int32), ("margin", C.c_int32),
+                ("detail", C.c_void_p), ("reference", C.c_void_p), ("mask", C.c_void_p), ("stats", C.c_void_p),
+                ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64)]
+
+
+class LpColorFitDesc(C.Structure):
+    _fields_ = [("batch", C.c_int32), ("channels", C.c_int32), ("clip_frames", C.c_int32), ("smooth", C.c_int32),
+                ("method", C.c_int32), ("reserved0", C.c_int32), ("strength", C.c_double),
+                ("stats", C.c_void_p), ("coef", C.c_void_p)]
+
+
+class LpColorApplyDesc(C.Structure):
+    _fields_ = [("batch", C.c_int32), ("height", C.c_int32), ("width", C.c_int32), ("channels", C.c_int32),
+                ("detail", C.c_void_p), ("coef", C.c_void_p), ("out", C.c_void_p)]
+
+
+def lp_color_ws_bytes(batch, height, width, channels):
+    """LP_COLOR_WS_BYTES of include/lanpaint_hip.h."""
+    tiles = ((int(height) + LP_COLOR_TILE_H - 1) // LP_COLOR_TILE_H) * ((int(width) + LP_COLOR_TILE_W - 1) // LP_COLOR_TILE_W)
+    return int(batch) * tiles * (1 + 4 * int(channels)) * 8
+
+
 def lp_components_ws_bytes(height, width):
     """LP_COMPONENTS_WS_BYTES of include/lanpaint_hip.h."""
     return ((int(height) * int(width) + 1023) // 1024) * 4100
@@ -280,6 +308,9 @@ EXPORTS = {
     "lp_mask_bbox_frames": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "lp_detail_resample_track": (C.c_int, [C.POINTER(LpDetailResampleTrackDesc), C.c_void_p]),
     "lp_detail_stitch_track": (C.c_int, [C.POINTER(LpDetailStitchTrackDesc), C.c_void_p]),
+    "lp_color_stats": (C.c_int, [C.POINTER(LpColorStatsDesc), C.c_void_p]),
+    "lp_color_fit": (C.c_int, [C.POINTER(LpColorFitDesc), C.c_void_p]),
+    "lp_color_apply": (C.c_int, [C.POINTER(LpColorApplyDesc), C.c_void_p]),
 }
 
 

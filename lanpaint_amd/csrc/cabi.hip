@@ -44,6 +44,9 @@ int detail_stitch_regions_dispatch(const lp_detail_stitch_regions_desc* d, hipSt
 int mask_bbox_frames_dispatch(const float* mask, int planes, int H, int W, int32_t* boxes, hipStream_t stream);
 int detail_resample_track_dispatch(const lp_detail_resample_track_desc* d, hipStream_t stream);
 int detail_stitch_track_dispatch(const lp_detail_stitch_track_desc* d, hipStream_t stream);
+int color_stats_dispatch(const lp_color_stats_desc* d, hipStream_t stream);
+int color_fit_dispatch(const lp_color_fit_desc* d, hipStream_t stream);
+int color_apply_dispatch(const lp_color_apply_desc* d, hipStream_t stream);
 int reshape_mask_dispatch(const float* src, int sb, int sc, int sf, int sh, int sw, float* dst, int db, int dc, int df,
                           int dh, int dw, int taps, int flags, hipStream_t stream);
 }  // namespace lp
@@ -138,6 +141,11 @@ int lp_detail_stitch_track(const lp_detail_stitch_track_desc* desc, void* stream
     return lp::detail_stitch_track_dispatch(desc, as_stream(stream));
 }
 
+int lp_color_stats(const lp_color_stats_desc* desc, void* stream) { return lp::color_stats_dispatch(desc, as_stream(stream)); }
+
+int lp_color_fit(const lp_color_fit_desc* desc, void* stream) { return lp::color_fit_dispatch(desc, as_stream(stream)); }
+
+int lp_color_apply(const lp_color_apply_desc* desc, void* stream) { return lp::color_apply_dispatch(desc, as_stream(stream)); }
 
 int lp_finalize(const lp_final_desc* desc, void* stream) { return lp::finalize_dispatch(desc, as_stream(stream)); }
 
