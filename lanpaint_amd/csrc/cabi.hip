@@ -34,14 +34,13 @@ int vmask_edt_dispatch(const lp_vmask_edt_desc* d, hipStream_t stream);
 int vmask_morph_dispatch(const lp_vmask_morph_desc* d, hipStream_t stream);
 int vmask_resize_dispatch(const lp_vmask_resize_desc* d, hipStream_t stream);
 int audio_merge_dispatch(const lp_audio_desc* d, hipStream_t stream);
-int mask_bbox_dispatch(const float* mask, int planes, int H, int W, int32_t* bbox, hipStream_t stream);
+int mask_bbox_dispatch(const float* mask, int planes, int H, int W, int32_t* boxes, bool per_plane, hipStream_t stream);
 int detail_resample_dispatch(const lp_detail_resample_desc* d, hipStream_t stream);
 int detail_stitch_dispatch(const lp_detail_stitch_desc* d, hipStream_t stream);
 int mask_components_dispatch(const float* mask, int planes, int H, int W, int32_t* labels, int32_t* table, void* workspace,
                              int64_t workspace_bytes, hipStream_t stream);
 int detail_resample_regions_dispatch(const lp_detail_resample_regions_desc* d, hipStream_t stream);
 int detail_stitch_regions_dispatch(const lp_detail_stitch_regions_desc* d, hipStream_t stream);
-int mask_bbox_frames_dispatch(const float* mask, int planes, int H, int W, int32_t* boxes, hipStream_t stream);
 int detail_resample_track_dispatch(const lp_detail_resample_track_desc* d, hipStream_t stream);
 int detail_stitch_track_dispatch(const lp_detail_stitch_track_desc* d, hipStream_t stream);
 int color_stats_dispatch(const lp_color_stats_desc* d, hipStream_t stream);
@@ -109,7 +108,7 @@ int lp_vmask_resize(const lp_vmask_resize_desc* desc, void* stream) { return lp:
 int lp_audio_merge(const lp_audio_desc* desc, void* stream) { return lp::audio_merge_dispatch(desc, as_stream(stream)); }
 
 int lp_mask_bbox(const float* mask, int32_t planes, int32_t height, int32_t width, int32_t* bbox, void* stream) {
-    return lp::mask_bbox_dispatch(mask, planes, height, width, bbox, as_stream(stream));
+    return lp::mask_bbox_dispatch(mask, planes, height, width, bbox, false, as_stream(stream));
 }
 
 int lp_detail_resample(const lp_detail_resample_desc* desc, void* stream) { return lp::detail_resample_dispatch(desc, as_stream(stream)); }
@@ -130,7 +129,7 @@ int lp_detail_stitch_regions(const lp_detail_stitch_regions_desc* desc, void* st
 }
 
 int lp_mask_bbox_frames(const float* mask, int32_t planes, int32_t height, int32_t width, int32_t* boxes, void* stream) {
-    return lp::mask_bbox_frames_dispatch(mask, planes, height, width, boxes, as_stream(stream));
+    return lp::mask_bbox_dispatch(mask, planes, height, width, boxes, true, as_stream(stream));
 }
 
 int lp_detail_resample_track(const lp_detail_resample_track_desc* desc, void* stream) {

@@ -37,10 +37,13 @@ __global__ void lp_detail_bbox_init_kernel(int32_t* __restrict__ bbox, int H, in
 }
 
 // Lane l of the block reads columns x .. x + V - 1 of 16 rows of one plane (V = 4: one 16 B load per row).  rowbits: the rows
-// of the tile this lane saw set; hit[j]: whether column slot j was set in any row.  The tile's bounds go into `bbox`.
-template <int V>
-__device__ __forceinline__ void bbox_tile(const float* __restrict__ mask, int32_t* __restrict__ bbox, int H, int W) {
+// of the tile this lane saw set; hit[j]: whether column slot j was set in any row.  The tile's bounds go into one box for
+// every plane, or PER_PLANE into row p of a table for plane p.
+template <int V, bool PER_PLANE>
+__global__ __launch_bounds__(256) void lp_detail_bbox_kernel(const float* __restrict__ mask, int32_t* __restrict__ bbox, int H,
+                                                             int W) {
     __shared__ int32_t part[4][4];
+    if constexpr (PER_PLANE) bbox += 4 * blockIdx.z;
     const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
     const int x = (blockIdx.x * 256 + threadIdx.x) * V, y0 = blockIdx.y * kBboxRows;
     const float* plane = mask + static_cast<int64_t>(blockIdx.z) * H * W;
@@ -103,18 +106,6 @@ __device__ __forceinline__ void bbox_tile(const float* __restrict__ mask, int32_
     }
 }
 
-template <int V>
-__global__ __launch_bounds__(256) void lp_detail_bbox_kernel(const float* __restrict__ mask, int32_t* __restrict__ bbox, int H,
-                                                             int W) {
-    bbox_tile<V>(mask, bbox, H, W);                              // every plane into one box
-}
-
-template <int V>
-__global__ __launch_bounds__(256) void lp_detail_bbox_frames_kernel(const float* __restrict__ mask, int32_t* __restrict__ boxes,
-                                                                    int H, int W) {
-    bbox_tile<V>(mask, boxes + 4 * blockIdx.z, H, W);            // plane p into row p
-}
-
 // ---- crop + resample ----------------------------------------------------------------------------------------------------
 // torch's antialiased passes for resample_tile: fp32 NHWC source, fp32 sums from zero with the taps ascending, the horizontal
 // pass parked as one float4.  The library is built with -ffp-contract=on, so a multiply-add fuses only inside one source
@@ -135,22 +126,81 @@ struct TorchAA {
     static __device__ __forceinline__ float finish(float acc) { return acc; }
 };
 
-// One block: a 16 x 256 tile of image b's output (resample_tile.h), read from the window at (y0, x0) of the source image.
-__global__ __launch_bounds__(256) void lp_detail_resample_kernel(const lp_detail_resample_desc d) {
-    const int C = d.channels, b = blockIdx.z;
-    const int rowE = d.out_w * C;
-    resample_tile<TorchAA>(d.src + ((static_cast<int64_t>(b) * d.src_h + d.y0) * d.src_w + d.x0) * C,
-                           static_cast<int64_t>(d.src_w) * C, C, d.win_h, d.win_w, d.out_h, rowE, d.bounds_x, d.weights_x,
-                           d.ksize_x, d.bounds_y, d.weights_y, d.ksize_y, d.dst + static_cast<int64_t>(b) * d.out_h * rowE);
+// ---- where a window is -----------------------------------------------------------------------------------------------------
+// Block z of a crop or stitch grid works on window z.  A policy, passed to the kernel by value, says which image `b` of the
+// batch that window lies in, which region `r` it is, and where its origin is in an H x W image.
+struct WindowAt {                                                 // the descriptor's (y0, x0), the same in every image
+    int y0, x0;
+    __device__ __forceinline__ void locate(int z, int, int, int, int, int, int& r, int& b, int& y, int& x) const {
+        r = 0; b = z; y = y0; x = x0;
+    }
+};
+template <bool BY_IMAGE>
+struct WindowFrom {                                               // a device table [n, 2] of origins
+    const int32_t* origins;
+    __device__ __forceinline__ void locate(int z, int batch, int H, int W, int h, int w, int& r, int& b, int& y, int& x) const {
+        if constexpr (BY_IMAGE) { r = 0; b = z; } else { r = z / batch; b = z - r * batch; }
+        const int i = BY_IMAGE ? b : r;
+        y = min(max(origins[2 * i], 0), H - h);                   // clamped: a bad table reads nothing outside the image
+        x = min(max(origins[2 * i + 1], 0), W - w);
+    }
+};
+using WindowOfRegion = WindowFrom<false>;                         // z = region * batch + image, origins[region]
+using WindowOfImage = WindowFrom<true>;                           // one window per image, origins[image]
+
+// Region `mine - 1`'s view of the mask: components that belong to another region, or to none, read as 0.  Label 0 -- every
+// value at or below 0.5 -- is nobody's and stays, so feathered edges survive.
+struct EraseForeign {
+    const int32_t* labels;
+    const int32_t* owner;
+    int owner_len, mine;
+    __device__ __forceinline__ float operator()(float v, int64_t at) const {
+        const int label = labels[at];
+        if (label == 0) return v;
+        const int o = (label > 0 && label < owner_len) ? owner[label] : 0;
+        return o == mine ? v : 0.0f;
+    }
+};
+__device__ __forceinline__ MaskAsIs for_region(MaskAsIs edit, int) { return edit; }
+__device__ __forceinline__ EraseForeign for_region(EraseForeign edit, int r) { edit.mine = r + 1; return edit; }
+
+// ---- crop + resample ----------------------------------------------------------------------------------------------------
+// `images` windows of win_h x win_w, one per grid z, out of src [batch, src_h, src_w, channels] into dst [images, out_h, out_w,
+// channels].  `scratch`: the erased windows on their way to the resample, null when there are none.
+struct ResampleJob {
+    int batch, src_h, src_w, channels, win_h, win_w, out_h, out_w, ksize_x, ksize_y;
+    int64_t images;
+    const float* src;
+    const int32_t* bounds_x;
+    const float* weights_x;
+    const int32_t* bounds_y;
+    const float* weights_y;
+    float *dst, *scratch;
+    bool same() const { return out_h == win_h && out_w == win_w; }
+};
+
+// One block: a 16 x 256 tile of window z's output (resample_tile.h).
+template <class Window>
+__global__ __launch_bounds__(256) void lp_detail_resample_kernel(const ResampleJob j, const Window win) {
+    const int C = j.channels, z = blockIdx.z, rowE = j.out_w * C;
+    int r, b, y0, x0;
+    win.locate(z, j.batch, j.src_h, j.src_w, j.win_h, j.win_w, r, b, y0, x0);
+    resample_tile<TorchAA>(j.src + ((static_cast<int64_t>(b) * j.src_h + y0) * j.src_w + x0) * C,
+                           static_cast<int64_t>(j.src_w) * C, C, j.win_h, j.win_w, j.out_h, rowE, j.bounds_x, j.weights_x,
+                           j.ksize_x, j.bounds_y, j.weights_y, j.ksize_y, j.dst + static_cast<int64_t>(z) * j.out_h * rowE);
 }
 
-// Same size in and out: the window's rows copied as flat streams, one element per lane.
-__global__ __launch_bounds__(256) void lp_detail_crop_kernel(const lp_detail_resample_desc d) {
-    const int C = d.channels, rowE = d.win_w * C;
-    const int e = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y, b = blockIdx.z;
+// Same size in and out: the windows' rows copied as flat streams, one element per lane.  EraseForeign (C == 1): region r's view.
+template <class Window, class Edit>
+__global__ __launch_bounds__(256) void lp_detail_crop_kernel(const ResampleJob j, const Window win, const Edit edit) {
+    const int C = j.channels, rowE = j.win_w * C;
+    const int e = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y, z = blockIdx.z;
     if (e >= rowE) return;
-    const float* s = d.src + ((static_cast<int64_t>(b) * d.src_h + d.y0 + y) * d.src_w + d.x0) * C;
-    d.dst[(static_cast<int64_t>(b) * d.win_h + y) * rowE + e] = s[e];
+    int r, b, y0, x0;
+    win.locate(z, j.batch, j.src_h, j.src_w, j.win_h, j.win_w, r, b, y0, x0);
+    const int64_t at = static_cast<int64_t>(y0 + y) * j.src_w + x0;    // of the window row's first pixel in its plane
+    const float v = j.src[(static_cast<int64_t>(b) * j.src_h * j.src_w + at) * C + e];
+    j.dst[(static_cast<int64_t>(z) * j.win_h + y) * rowE + e] = for_region(edit, r)(v, at + e);
 }
 
 // ---- stitch -------------------------------------------------------------------------------------------------------------
@@ -169,18 +219,26 @@ __global__ __launch_bounds__(256) void lp_detail_copy_kernel(const float* __rest
     }
 }
 
-// A block owns a TH x TW tile of the REGION of image b; tile origins are image coordinates, so the smoothed mask is the
-// whole image's.  m goes to LDS, then the tile's rows are blended as flat streams of TW * C elements.  `edit` is how a mask
-// element enters the passes (mask_tile.h): as it is, or with another region's components erased.  out may be original: one
-// thread reads and writes a given element, and the halo is read from the mask alone.  The window is at (wy0, wx0): the
-// descriptor's, or one looked up per image.
-template <int TH, int TW, class Edit>
-__device__ __forceinline__ void stitch_tile(const lp_detail_stitch_desc& d, const int wy0, const int wx0, const Edit edit) {
+// detail [batch, win_h, win_w, channels] into the windows of out [batch, height, width, channels], one window per image.
+struct StitchJob {
+    int batch, height, width, channels, win_h, win_w, k, mask_batch;
+    const float *mask, *original, *detail;
+    float* out;
+};
+
+// A block owns a TH x TW tile of image b's window; tile origins are image coordinates, so the smoothed mask is the whole
+// image's.  m goes to LDS, then the tile's rows are blended as flat streams of TW * C elements.  `edit` is how a mask element
+// enters the passes (mask_tile.h): as it is, or with another region's components erased.  out may be original: one thread
+// reads and writes a given element, and the halo is read from the mask alone.
+template <int TH, int TW, class Window, class Edit>
+__global__ __launch_bounds__(256) void lp_detail_stitch_kernel(const StitchJob j, const Window win, const Edit edit) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
-    const int k = d.k, tid = threadIdx.x;
-    const int x0 = wx0 + blockIdx.x * TW, y0 = wy0 + blockIdx.y * TH, b = blockIdx.z;
-    const int H = d.height, W = d.width, C = d.channels;
-    const float* mplane = d.mask + static_cast<int64_t>(d.mask_batch == 1 ? 0 : b) * H * W;
+    const int k = j.k, tid = threadIdx.x;
+    const int H = j.height, W = j.width, C = j.channels;
+    int r, b, wy0, wx0;
+    win.locate(blockIdx.z, j.batch, H, W, j.win_h, j.win_w, r, b, wy0, wx0);
+    const int x0 = wx0 + blockIdx.x * TW, y0 = wy0 + blockIdx.y * TH;
+    const float* mplane = j.mask + static_cast<int64_t>(j.mask_batch == 1 ? 0 : b) * H * W;
     float *D, *g;
     mask_tile_passes<TH, TW, Edit>(lds, mplane, H, W, LP_NN_ATEN_SCALAR, k, x0, y0, H, W, D, g, edit);
     float* M = lds;                                               // the passes' A, free now: TH x TW smoothed mask
@@ -189,289 +247,204 @@ __device__ __forceinline__ void stitch_tile(const lp_detail_stitch_desc& d, cons
         M[idx] = smoothed_mask_at<TW>(D, g, k, ty, tx);
     }
     __syncthreads();
-    const int ty_end = min(TH, wy0 + d.win_h - y0), tx_end = min(TW, wx0 + d.win_w - x0);
+    const int ty_end = min(TH, wy0 + j.win_h - y0), tx_end = min(TW, wx0 + j.win_w - x0);
     const int rowE = tx_end * C;
     for (int idx = tid; idx < ty_end * rowE; idx += 256) {
         const int ty = idx / rowE, e = idx - ty * rowE;
         const float m = M[ty * TW + e / C];
         const int64_t io = ((static_cast<int64_t>(b) * H + y0 + ty) * W + x0) * C + e;
-        const int64_t id = ((static_cast<int64_t>(b) * d.win_h + (y0 - wy0) + ty) * d.win_w + (x0 - wx0)) * C + e;
-        d.out[io] = d.original[io] * (1.0f - m) + d.detail[id] * m;
+        const int64_t id = ((static_cast<int64_t>(b) * j.win_h + (y0 - wy0) + ty) * j.win_w + (x0 - wx0)) * C + e;
+        j.out[io] = j.original[io] * (1.0f - m) + j.detail[id] * m;
     }
 }
 
-template <int TH, int TW>
-__global__ __launch_bounds__(256) void lp_detail_stitch_kernel(const lp_detail_stitch_desc d) {
-    stitch_tile<TH, TW>(d, d.y0, d.x0, MaskAsIs());
-}
-
-// Region `mine - 1`'s view of the mask: components that belong to another region, or to none, read as 0.  Label 0 -- every
-// value at or below 0.5 -- is nobody's and stays, so feathered edges survive.
-struct EraseForeign {
-    const int32_t* labels;
-    const int32_t* owner;
-    int owner_len, mine;
-    __device__ __forceinline__ float operator()(float v, int64_t at) const {
-        const int label = labels[at];
-        if (label == 0) return v;
-        const int o = (label > 0 && label < owner_len) ? owner[label] : 0;
-        return o == mine ? v : 0.0f;
-    }
-};
-
-template <int TH, int TW>
-__global__ __launch_bounds__(256) void lp_detail_stitch_region_kernel(const lp_detail_stitch_desc d, const EraseForeign erase) {
-    stitch_tile<TH, TW>(d, d.y0, d.x0, erase);
-}
-
-template <int TH, int TW, class... Extra>
-hipError_t launch_stitch(void (*kernel)(const lp_detail_stitch_desc, Extra...), const lp_detail_stitch_desc& d,
-                         hipStream_t stream, Extra... extra) {
-    const size_t lds = mask_tile_lds_bytes<TH, TW>(d.k);
-    if (lds > 64 * 1024)                                          // per device, like lp_mask_blend
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    const dim3 grid((d.win_w + TW - 1) / TW, (d.win_h + TH - 1) / TH, d.batch);
-    hipLaunchKernelGGL(kernel, grid, dim3(256), lds, stream, d, extra...);
-    return hipGetLastError();
-}
-
-// ---- regions: the same jobs for several windows of one size ----------------------------------------------------------------
-__device__ __forceinline__ void region_origin(const int32_t* __restrict__ origins, int r, int H, int W, int h, int w, int& y0,
-                                              int& x0) {                // clamped: a bad table reads nothing outside the image
-    y0 = min(max(origins[2 * r], 0), H - h);
-    x0 = min(max(origins[2 * r + 1], 0), W - w);
-}
-
-// blockIdx.z = region * batch + image; otherwise lp_detail_resample_kernel.  TRACK: one window per image, a table row per
-// image (regions == 1, so blockIdx.z is the image).
-template <bool TRACK>
-__global__ __launch_bounds__(256) void lp_detail_resample_regions_kernel(const lp_detail_resample_regions_desc d) {
-    const int C = d.channels, z = blockIdx.z, r = z / d.batch, b = z - r * d.batch;
-    const int rowE = d.out_w * C;
-    int y0, x0;
-    region_origin(d.origins, TRACK ? b : r, d.src_h, d.src_w, d.win_h, d.win_w, y0, x0);
-    resample_tile<TorchAA>(d.src + ((static_cast<int64_t>(b) * d.src_h + y0) * d.src_w + x0) * C,
-                           static_cast<int64_t>(d.src_w) * C, C, d.win_h, d.win_w, d.out_h, rowE, d.bounds_x, d.weights_x,
-                           d.ksize_x, d.bounds_y, d.weights_y, d.ksize_y, d.dst + static_cast<int64_t>(z) * d.out_h * rowE);
-}
-
-// The windows' rows copied as flat streams into dst [regions * batch, win_h, win_w, C]; ERASE (C == 1): through EraseForeign.
-template <bool ERASE, bool TRACK>
-__global__ __launch_bounds__(256) void lp_detail_crop_regions_kernel(const lp_detail_resample_regions_desc d, float* __restrict__ dst) {
-    const int C = d.channels, rowE = d.win_w * C;
-    const int e = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y, z = blockIdx.z, r = z / d.batch, b = z - r * d.batch;
-    if (e >= rowE) return;
-    int y0, x0;
-    region_origin(d.origins, TRACK ? b : r, d.src_h, d.src_w, d.win_h, d.win_w, y0, x0);
-    const int64_t at = static_cast<int64_t>(y0 + y) * d.src_w + x0;    // of the window row's first pixel in its plane
-    float v = d.src[(static_cast<int64_t>(b) * d.src_h * d.src_w + at) * C + e];
-    if constexpr (ERASE) v = EraseForeign{d.labels, d.owner, d.owner_len, r + 1}(v, at + e);
-    dst[(static_cast<int64_t>(z) * d.win_h + y) * rowE + e] = v;
-}
-
-// Image b's window is at origins[b]; otherwise lp_detail_stitch_kernel.  d.y0 / d.x0 are not read.
-template <int TH, int TW>
-__global__ __launch_bounds__(256) void lp_detail_stitch_track_kernel(const lp_detail_stitch_desc d, const int32_t* __restrict__ origins) {
-    int y0, x0;
-    region_origin(origins, blockIdx.z, d.height, d.width, d.win_h, d.win_w, y0, x0);
-    stitch_tile<TH, TW>(d, y0, x0, MaskAsIs());
-}
-
-// One streaming copy original -> out on `stream`, the first launch of every stitch.
-hipError_t launch_frame_copy(const float* original, float* out, int64_t n, hipStream_t stream) {
-    const uint32_t blocks = static_cast<uint32_t>(min(static_cast<int64_t>(kCopyBlocks), (n + 1023) / 1024));
-    if (aligned16(original) && aligned16(out))
-        hipLaunchKernelGGL(lp_detail_copy_kernel<true>, dim3(blocks), dim3(256), 0, stream, original, out, n);
-    else                                                          // a frame range of a larger tensor need not start on 16 bytes
-        hipLaunchKernelGGL(lp_detail_copy_kernel<false>, dim3(blocks), dim3(256), 0, stream, original, out, n);
-    return hipGetLastError();
-}
-
-// The unerased crops of `images` windows: the resample tile, or the plain copy when the size stays.
-template <bool TRACK>
-void launch_windows(const lp_detail_resample_regions_desc& d, int images, bool same, hipStream_t stream) {
-    if (same) {
-        const dim3 grid((d.win_w * d.channels + 255) / 256, d.win_h, images);
-        hipLaunchKernelGGL((lp_detail_crop_regions_kernel<false, TRACK>), grid, dim3(256), 0, stream, d, d.dst);
-    } else {
-        const dim3 grid((d.out_w * d.channels + kResampleTX - 1) / kResampleTX, (d.out_h + kResampleTY - 1) / kResampleTY, images);
-        hipLaunchKernelGGL(lp_detail_resample_regions_kernel<TRACK>, grid, dim3(256), 0, stream, d);
-    }
-}
-
+// ---- checks and launches, shared by the single, regions and track entries --------------------------------------------------
 bool side_ok(int s) { return s > 0 && s <= LP_DETAIL_MAX_SIDE; }
 bool chan_ok(int c) { return c > 0 && c <= LP_DETAIL_MAX_CHANNELS; }
 bool window_ok(int y0, int x0, int h, int w, int H, int W) {
     return y0 >= 0 && x0 >= 0 && h > 0 && w > 0 && h <= H - y0 && w <= W - x0;
 }
+int launched() { return hipGetLastError() == hipSuccess ? LP_OK : LP_E_LAUNCH; }
+
+// `at`: the descriptor's origin.  A table's windows are clamped on the device, so there only the size has to fit.
+int check_resample(const ResampleJob& j, WindowAt at = {0, 0}) {
+    if (j.batch <= 0 || !side_ok(j.src_h) || !side_ok(j.src_w) || !chan_ok(j.channels)) return LP_E_INVALID;
+    if (!window_ok(at.y0, at.x0, j.win_h, j.win_w, j.src_h, j.src_w) || !side_ok(j.out_h) || !side_ok(j.out_w)) return LP_E_INVALID;
+    if (!j.src || !j.dst) return LP_E_INVALID;
+    if (!j.same()) {
+        if (j.ksize_x <= 0 || j.ksize_y <= 0) return LP_E_INVALID;
+        if (!j.bounds_x || !j.weights_x || !j.bounds_y || !j.weights_y) return LP_E_INVALID;
+        if (!aligned16(j.dst) || !aligned16(j.scratch)) return LP_E_ALIGN;
+    }
+    return j.images > 65535 ? LP_E_UNSUPPORTED : LP_OK;          // the grid's z
+}
+
+int check_stitch(const StitchJob& j, WindowAt at = {0, 0}) {
+    if (j.batch <= 0 || !side_ok(j.height) || !side_ok(j.width) || !chan_ok(j.channels)) return LP_E_INVALID;
+    if (!window_ok(at.y0, at.x0, j.win_h, j.win_w, j.height, j.width)) return LP_E_INVALID;
+    if (j.k < 1 || j.k > 51 || (j.k % 2) == 0) return LP_E_INVALID;
+    if (j.mask_batch != 1 && j.mask_batch != j.batch) return LP_E_INVALID;
+    if (!j.mask || !j.original || !j.detail || !j.out || j.out == j.original) return LP_E_INVALID;
+    return j.batch > 65535 ? LP_E_UNSUPPORTED : LP_OK;
+}
+
+// The same-size copy of the job's windows into j.dst.
+template <class Window, class Edit>
+void launch_crop(const ResampleJob& j, Window win, Edit edit, hipStream_t stream) {
+    const dim3 grid((j.win_w * j.channels + 255) / 256, j.win_h, static_cast<uint32_t>(j.images));
+    hipLaunchKernelGGL((lp_detail_crop_kernel<Window, Edit>), grid, dim3(256), 0, stream, j, win, edit);
+}
+
+// The job's windows as they are in src: the resample tile, or the plain copy when the size stays.
+template <class Window>
+int launch_resample(const ResampleJob& j, Window win, hipStream_t stream) {
+    if (j.same()) {
+        launch_crop(j, win, MaskAsIs(), stream);
+    } else {
+        const dim3 grid((j.out_w * j.channels + kResampleTX - 1) / kResampleTX, (j.out_h + kResampleTY - 1) / kResampleTY,
+                        static_cast<uint32_t>(j.images));
+        hipLaunchKernelGGL(lp_detail_resample_kernel<Window>, grid, dim3(256), 0, stream, j, win);
+    }
+    return launched();
+}
+
+// One streaming copy original -> out on `stream`, the first launch of every stitch.
+hipError_t launch_frame_copy(const StitchJob& j, hipStream_t stream) {
+    const int64_t n = static_cast<int64_t>(j.batch) * j.height * j.width * j.channels;
+    const uint32_t blocks = static_cast<uint32_t>(min(static_cast<int64_t>(kCopyBlocks), (n + 1023) / 1024));
+    if (aligned16(j.original) && aligned16(j.out))
+        hipLaunchKernelGGL(lp_detail_copy_kernel<true>, dim3(blocks), dim3(256), 0, stream, j.original, j.out, n);
+    else                                                          // a frame range of a larger tensor need not start on 16 bytes
+        hipLaunchKernelGGL(lp_detail_copy_kernel<false>, dim3(blocks), dim3(256), 0, stream, j.original, j.out, n);
+    return hipGetLastError();
+}
+
+template <int TH, int TW, class Window, class Edit>
+hipError_t launch_stitch_tiles(const StitchJob& j, Window win, Edit edit, hipStream_t stream) {
+    const auto kernel = lp_detail_stitch_kernel<TH, TW, Window, Edit>;
+    const size_t lds = mask_tile_lds_bytes<TH, TW>(j.k);
+    if (lds > 64 * 1024)                                          // per device, like lp_mask_blend
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    const dim3 grid((j.win_w + TW - 1) / TW, (j.win_h + TH - 1) / TH, j.batch);
+    hipLaunchKernelGGL(kernel, grid, dim3(256), lds, stream, j, win, edit);
+    return hipGetLastError();
+}
+
+// The blend of every image's window, in place on j.out when j.original is j.out.
+template <class Window, class Edit>
+int launch_stitch(const StitchJob& j, Window win, Edit edit, hipStream_t stream) {
+    const hipError_t err = (j.k <= 15) ? launch_stitch_tiles<16, 64>(j, win, edit, stream)
+                                       : launch_stitch_tiles<8, 32>(j, win, edit, stream);
+    return err == hipSuccess ? LP_OK : LP_E_LAUNCH;
+}
 
 }  // namespace
 
-int mask_bbox_dispatch(const float* mask, int planes, int H, int W, int32_t* bbox, hipStream_t stream) {
-    if (!mask || !bbox || planes <= 0 || !side_ok(H) || !side_ok(W)) return LP_E_INVALID;
-    if (planes > 65535) return LP_E_UNSUPPORTED;
-    hipLaunchKernelGGL(lp_detail_bbox_init_kernel, dim3(1), dim3(kWave), 0, stream, bbox, H, W, 1);
-    if (hipGetLastError() != hipSuccess) return LP_E_LAUNCH;
-    const uint32_t gy = (H + kBboxRows - 1) / kBboxRows;
-    if ((W & 3) == 0 && aligned16(mask))
-        hipLaunchKernelGGL(lp_detail_bbox_kernel<4>, dim3((W + 1023) / 1024, gy, planes), dim3(256), 0, stream, mask, bbox, H, W);
-    else
-        hipLaunchKernelGGL(lp_detail_bbox_kernel<1>, dim3((W + 255) / 256, gy, planes), dim3(256), 0, stream, mask, bbox, H, W);
-    return hipGetLastError() == hipSuccess ? LP_OK : LP_E_LAUNCH;
-}
-
-int mask_bbox_frames_dispatch(const float* mask, int planes, int H, int W, int32_t* boxes, hipStream_t stream) {
+int mask_bbox_dispatch(const float* mask, int planes, int H, int W, int32_t* boxes, bool per_plane, hipStream_t stream) {
     if (!mask || !boxes || planes <= 0 || !side_ok(H) || !side_ok(W)) return LP_E_INVALID;
     if (planes > 65535) return LP_E_UNSUPPORTED;
-    hipLaunchKernelGGL(lp_detail_bbox_init_kernel, dim3((4 * planes + 255) / 256), dim3(256), 0, stream, boxes, H, W, planes);
+    const int n = per_plane ? planes : 1;
+    hipLaunchKernelGGL(lp_detail_bbox_init_kernel, dim3((4 * n + 255) / 256), dim3(256), 0, stream, boxes, H, W, n);
     if (hipGetLastError() != hipSuccess) return LP_E_LAUNCH;
-    const uint32_t gy = (H + kBboxRows - 1) / kBboxRows;
-    if ((W & 3) == 0 && aligned16(mask))                          // then every plane starts on 16 bytes too
-        hipLaunchKernelGGL(lp_detail_bbox_frames_kernel<4>, dim3((W + 1023) / 1024, gy, planes), dim3(256), 0, stream, mask, boxes, H, W);
-    else
-        hipLaunchKernelGGL(lp_detail_bbox_frames_kernel<1>, dim3((W + 255) / 256, gy, planes), dim3(256), 0, stream, mask, boxes, H, W);
-    return hipGetLastError() == hipSuccess ? LP_OK : LP_E_LAUNCH;
+    const bool vec = (W & 3) == 0 && aligned16(mask);              // then every plane starts on 16 bytes too
+    const dim3 grid(vec ? (W + 1023) / 1024 : (W + 255) / 256, (H + kBboxRows - 1) / kBboxRows, planes);
+    const auto kernel = vec ? (per_plane ? lp_detail_bbox_kernel<4, true> : lp_detail_bbox_kernel<4, false>)
+                            : (per_plane ? lp_detail_bbox_kernel<1, true> : lp_detail_bbox_kernel<1, false>);
+    hipLaunchKernelGGL(kernel, grid, dim3(256), 0, stream, mask, boxes, H, W);
+    return launched();
 }
 
 int detail_resample_dispatch(const lp_detail_resample_desc* dp, hipStream_t stream) {
     if (!dp) return LP_E_INVALID;
     const lp_detail_resample_desc& d = *dp;
-    if (d.batch <= 0 || !side_ok(d.src_h) || !side_ok(d.src_w) || !chan_ok(d.channels)) return LP_E_INVALID;
-    if (!window_ok(d.y0, d.x0, d.win_h, d.win_w, d.src_h, d.src_w) || !side_ok(d.out_h) || !side_ok(d.out_w)) return LP_E_INVALID;
-    if (!d.src || !d.dst) return LP_E_INVALID;
-    const bool same = d.out_h == d.win_h && d.out_w == d.win_w;
-    if (!same) {
-        if (d.ksize_x <= 0 || d.ksize_y <= 0) return LP_E_INVALID;
-        if (!d.bounds_x || !d.weights_x || !d.bounds_y || !d.weights_y) return LP_E_INVALID;
-        if (!aligned16(d.dst)) return LP_E_ALIGN;
-    }
-    if (d.batch > 65535) return LP_E_UNSUPPORTED;
-    const int rowE = d.out_w * d.channels;
-    if (same) {
-        hipLaunchKernelGGL(lp_detail_crop_kernel, dim3((rowE + 255) / 256, d.win_h, d.batch), dim3(256), 0, stream, d);
-    } else {
-        const dim3 grid((rowE + kResampleTX - 1) / kResampleTX, (d.out_h + kResampleTY - 1) / kResampleTY, d.batch);
-        hipLaunchKernelGGL(lp_detail_resample_kernel, grid, dim3(256), 0, stream, d);
-    }
-    return hipGetLastError() == hipSuccess ? LP_OK : LP_E_LAUNCH;
+    const ResampleJob j = {d.batch, d.src_h, d.src_w, d.channels, d.win_h, d.win_w, d.out_h, d.out_w, d.ksize_x, d.ksize_y,
+                           d.batch, d.src, d.bounds_x, d.weights_x, d.bounds_y, d.weights_y, d.dst, nullptr};
+    const WindowAt at = {d.y0, d.x0};
+    if (const int err = check_resample(j, at)) return err;
+    return launch_resample(j, at, stream);
 }
 
 int detail_stitch_dispatch(const lp_detail_stitch_desc* dp, hipStream_t stream) {
     if (!dp) return LP_E_INVALID;
     const lp_detail_stitch_desc& d = *dp;
-    if (d.batch <= 0 || !side_ok(d.height) || !side_ok(d.width) || !chan_ok(d.channels)) return LP_E_INVALID;
-    if (!window_ok(d.y0, d.x0, d.win_h, d.win_w, d.height, d.width)) return LP_E_INVALID;
-    if (d.k < 1 || d.k > 51 || (d.k % 2) == 0) return LP_E_INVALID;
-    if (d.mask_batch != 1 && d.mask_batch != d.batch) return LP_E_INVALID;
-    if (!d.mask || !d.original || !d.detail || !d.out || d.out == d.original) return LP_E_INVALID;
-    if (d.batch > 65535) return LP_E_UNSUPPORTED;
-    const int64_t n = static_cast<int64_t>(d.batch) * d.height * d.width * d.channels;
-    if (launch_frame_copy(d.original, d.out, n, stream) != hipSuccess) return LP_E_LAUNCH;
-    const hipError_t err = (d.k <= 15) ? launch_stitch<16, 64>(lp_detail_stitch_kernel<16, 64>, d, stream)
-                                       : launch_stitch<8, 32>(lp_detail_stitch_kernel<8, 32>, d, stream);
-    return err == hipSuccess ? LP_OK : LP_E_LAUNCH;
+    const StitchJob j = {d.batch, d.height, d.width, d.channels, d.win_h, d.win_w, d.k, d.mask_batch, d.mask, d.original,
+                         d.detail, d.out};
+    const WindowAt at = {d.y0, d.x0};
+    if (const int err = check_stitch(j, at)) return err;
+    if (launch_frame_copy(j, stream) != hipSuccess) return LP_E_LAUNCH;
+    return launch_stitch(j, at, MaskAsIs(), stream);
 }
 
 int detail_resample_regions_dispatch(const lp_detail_resample_regions_desc* dp, hipStream_t stream) {
     if (!dp) return LP_E_INVALID;
     const lp_detail_resample_regions_desc& d = *dp;
-    if (d.batch <= 0 || !side_ok(d.src_h) || !side_ok(d.src_w) || !chan_ok(d.channels)) return LP_E_INVALID;
     if (d.regions < 1 || d.regions > LP_DETAIL_MAX_REGIONS || !d.origins) return LP_E_INVALID;
-    if (!window_ok(0, 0, d.win_h, d.win_w, d.src_h, d.src_w) || !side_ok(d.out_h) || !side_ok(d.out_w)) return LP_E_INVALID;
-    if (!d.src || !d.dst) return LP_E_INVALID;
-    const bool same = d.out_h == d.win_h && d.out_w == d.win_w;
-    if (d.labels && (d.channels != 1 || !d.owner || d.owner_len < 1 || (!same && !d.scratch))) return LP_E_INVALID;
-    if (!same) {
-        if (d.ksize_x <= 0 || d.ksize_y <= 0) return LP_E_INVALID;
-        if (!d.bounds_x || !d.weights_x || !d.bounds_y || !d.weights_y) return LP_E_INVALID;
-        if (!aligned16(d.dst) || (d.labels && !aligned16(d.scratch))) return LP_E_ALIGN;
+    ResampleJob j = {d.batch, d.src_h, d.src_w, d.channels, d.win_h, d.win_w, d.out_h, d.out_w, d.ksize_x, d.ksize_y,
+                     static_cast<int64_t>(d.regions) * d.batch, d.src, d.bounds_x, d.weights_x, d.bounds_y, d.weights_y, d.dst,
+                     nullptr};
+    const bool erased_resample = d.labels && !j.same();          // erased windows go to scratch, the resample reads them there
+    if (d.labels && (d.channels != 1 || !d.owner || d.owner_len < 1 || (erased_resample && !d.scratch))) return LP_E_INVALID;
+    if (erased_resample) j.scratch = d.scratch;
+    if (const int err = check_resample(j)) return err;
+    const WindowOfRegion win = {d.origins};
+    if (!d.labels) return launch_resample(j, win, stream);
+    const EraseForeign erase = {d.labels, d.owner, d.owner_len, 0};
+    if (!erased_resample) {
+        launch_crop(j, win, erase, stream);
+        return launched();
     }
-    if (static_cast<int64_t>(d.regions) * d.batch > 65535) return LP_E_UNSUPPORTED;
-    const int images = d.regions * d.batch;
-    const dim3 crop_grid((d.win_w * d.channels + 255) / 256, d.win_h, images);
-    const dim3 tile_grid((d.out_w * d.channels + kResampleTX - 1) / kResampleTX, (d.out_h + kResampleTY - 1) / kResampleTY, images);
-    if (d.labels) {                                               // erased windows: the result, or the resample's source
-        hipLaunchKernelGGL((lp_detail_crop_regions_kernel<true, false>), crop_grid, dim3(256), 0, stream, d, same ? d.dst : d.scratch);
-        if (!same) {
-            if (hipGetLastError() != hipSuccess) return LP_E_LAUNCH;
-            lp_detail_resample_desc w = {images, d.win_h, d.win_w, 1, 0, 0, d.win_h, d.win_w, d.out_h, d.out_w, d.ksize_x,
-                                         d.ksize_y, d.scratch, d.bounds_x, d.weights_x, d.bounds_y, d.weights_y, d.dst};
-            hipLaunchKernelGGL(lp_detail_resample_kernel, tile_grid, dim3(256), 0, stream, w);
-        }
-    } else {
-        launch_windows<false>(d, images, same, stream);
-    }
-    return hipGetLastError() == hipSuccess ? LP_OK : LP_E_LAUNCH;
+    ResampleJob crop = j, rest = j;                               // the windows erased, then each resampled whole
+    crop.dst = d.scratch;
+    launch_crop(crop, win, erase, stream);
+    if (hipGetLastError() != hipSuccess) return LP_E_LAUNCH;
+    rest.batch = static_cast<int>(j.images);
+    rest.src_h = d.win_h;
+    rest.src_w = d.win_w;
+    rest.src = d.scratch;
+    return launch_resample(rest, WindowAt{0, 0}, stream);
 }
 
 int detail_stitch_regions_dispatch(const lp_detail_stitch_regions_desc* dp, hipStream_t stream) {
     if (!dp) return LP_E_INVALID;
     const lp_detail_stitch_regions_desc& d = *dp;
-    if (d.batch <= 0 || !side_ok(d.height) || !side_ok(d.width) || !chan_ok(d.channels)) return LP_E_INVALID;
     if (d.regions < 1 || d.regions > LP_DETAIL_MAX_REGIONS || !d.origins) return LP_E_INVALID;
-    for (int r = 0; r < d.regions; ++r)
+    for (int r = 0; r < d.regions; ++r)                           // a host table: checked here, not clamped
         if (!window_ok(d.origins[2 * r], d.origins[2 * r + 1], d.win_h, d.win_w, d.height, d.width)) return LP_E_INVALID;
-    if (d.k < 1 || d.k > 51 || (d.k % 2) == 0) return LP_E_INVALID;
-    if (d.mask_batch != 1 && d.mask_batch != d.batch) return LP_E_INVALID;
-    if (!d.mask || !d.original || !d.detail || !d.out || d.out == d.original) return LP_E_INVALID;
     if (d.labels && (!d.owner || d.owner_len < 1)) return LP_E_INVALID;
-    if (d.batch > 65535) return LP_E_UNSUPPORTED;
-    const int64_t n = static_cast<int64_t>(d.batch) * d.height * d.width * d.channels;
-    if (launch_frame_copy(d.original, d.out, n, stream) != hipSuccess) return LP_E_LAUNCH;
+    StitchJob j = {d.batch, d.height, d.width, d.channels, d.win_h, d.win_w, d.k, d.mask_batch, d.mask, d.original, d.detail,
+                   d.out};
+    if (const int err = check_stitch(j)) return err;
+    if (launch_frame_copy(j, stream) != hipSuccess) return LP_E_LAUNCH;
     const int64_t per_region = static_cast<int64_t>(d.batch) * d.win_h * d.win_w * d.channels;
-    for (int r = 0; r < d.regions; ++r) {                         // in order, in place: out_{r+1} from out_r
-        const lp_detail_stitch_desc s = {d.batch, d.height, d.width, d.channels, d.origins[2 * r], d.origins[2 * r + 1],
-                                         d.win_h, d.win_w, d.k, d.mask_batch, d.mask, d.out, d.detail + r * per_region, d.out};
-        hipError_t err;
-        if (d.labels) {
-            const EraseForeign erase = {d.labels, d.owner, d.owner_len, r + 1};
-            err = (d.k <= 15) ? launch_stitch<16, 64>(lp_detail_stitch_region_kernel<16, 64>, s, stream, erase)
-                              : launch_stitch<8, 32>(lp_detail_stitch_region_kernel<8, 32>, s, stream, erase);
-        } else {
-            err = (d.k <= 15) ? launch_stitch<16, 64>(lp_detail_stitch_kernel<16, 64>, s, stream)
-                              : launch_stitch<8, 32>(lp_detail_stitch_kernel<8, 32>, s, stream);
-        }
-        if (err != hipSuccess) return LP_E_LAUNCH;
+    j.original = d.out;                                           // in order, in place: out_{r+1} from out_r
+    for (int r = 0; r < d.regions; ++r, j.detail += per_region) {
+        const WindowAt at = {d.origins[2 * r], d.origins[2 * r + 1]};
+        const int err = d.labels ? launch_stitch(j, at, EraseForeign{d.labels, d.owner, d.owner_len, r + 1}, stream)
+                                 : launch_stitch(j, at, MaskAsIs(), stream);
+        if (err) return err;
     }
     return LP_OK;
 }
 
 int detail_resample_track_dispatch(const lp_detail_resample_track_desc* dp, hipStream_t stream) {
     if (!dp) return LP_E_INVALID;
-    const lp_detail_resample_track_desc& t = *dp;
-    if (t.batch <= 0 || !side_ok(t.src_h) || !side_ok(t.src_w) || !chan_ok(t.channels) || !t.origins) return LP_E_INVALID;
-    if (!window_ok(0, 0, t.win_h, t.win_w, t.src_h, t.src_w) || !side_ok(t.out_h) || !side_ok(t.out_w)) return LP_E_INVALID;
-    if (!t.src || !t.dst) return LP_E_INVALID;
-    const bool same = t.out_h == t.win_h && t.out_w == t.win_w;
-    if (!same) {
-        if (t.ksize_x <= 0 || t.ksize_y <= 0) return LP_E_INVALID;
-        if (!t.bounds_x || !t.weights_x || !t.bounds_y || !t.weights_y) return LP_E_INVALID;
-        if (!aligned16(t.dst)) return LP_E_ALIGN;
-    }
-    if (t.batch > 65535) return LP_E_UNSUPPORTED;
-    const lp_detail_resample_regions_desc d = {t.batch, t.src_h, t.src_w, t.channels, 1, t.win_h, t.win_w, 0, t.out_h, t.out_w,
-                                               t.ksize_x, t.ksize_y, t.origins, t.src, t.bounds_x, t.weights_x, t.bounds_y,
-                                               t.weights_y, t.dst, nullptr, nullptr, nullptr};
-    launch_windows<true>(d, t.batch, same, stream);
-    return hipGetLastError() == hipSuccess ? LP_OK : LP_E_LAUNCH;
+    const lp_detail_resample_track_desc& d = *dp;
+    if (!d.origins) return LP_E_INVALID;
+    const ResampleJob j = {d.batch, d.src_h, d.src_w, d.channels, d.win_h, d.win_w, d.out_h, d.out_w, d.ksize_x, d.ksize_y,
+                           d.batch, d.src, d.bounds_x, d.weights_x, d.bounds_y, d.weights_y, d.dst, nullptr};
+    if (const int err = check_resample(j)) return err;
+    return launch_resample(j, WindowOfImage{d.origins}, stream);
 }
 
 int detail_stitch_track_dispatch(const lp_detail_stitch_track_desc* dp, hipStream_t stream) {
     if (!dp) return LP_E_INVALID;
-    const lp_detail_stitch_track_desc& t = *dp;
-    if (t.batch <= 0 || !side_ok(t.height) || !side_ok(t.width) || !chan_ok(t.channels) || !t.origins) return LP_E_INVALID;
-    if (!window_ok(0, 0, t.win_h, t.win_w, t.height, t.width)) return LP_E_INVALID;
-    if (t.k < 1 || t.k > 51 || (t.k % 2) == 0) return LP_E_INVALID;
-    if (t.mask_batch != 1 && t.mask_batch != t.batch) return LP_E_INVALID;
-    if (!t.mask || !t.original || !t.detail || !t.out || t.out == t.original) return LP_E_INVALID;
-    if (t.batch > 65535) return LP_E_UNSUPPORTED;
-    const int64_t n = static_cast<int64_t>(t.batch) * t.height * t.width * t.channels;
-    if (launch_frame_copy(t.original, t.out, n, stream) != hipSuccess) return LP_E_LAUNCH;
-    const lp_detail_stitch_desc d = {t.batch, t.height, t.width, t.channels, 0, 0, t.win_h, t.win_w, t.k, t.mask_batch,
-                                     t.mask, t.original, t.detail, t.out};
-    const hipError_t err = (t.k <= 15) ? launch_stitch<16, 64>(lp_detail_stitch_track_kernel<16, 64>, d, stream, t.origins)
-                                       : launch_stitch<8, 32>(lp_detail_stitch_track_kernel<8, 32>, d, stream, t.origins);
-    return err == hipSuccess ? LP_OK : LP_E_LAUNCH;
+    const lp_detail_stitch_track_desc& d = *dp;
+    if (!d.origins) return LP_E_INVALID;
+    const StitchJob j = {d.batch, d.height, d.width, d.channels, d.win_h, d.win_w, d.k, d.mask_batch, d.mask, d.original,
+                         d.detail, d.out};
+    if (const int err = check_stitch(j)) return err;
+    if (launch_frame_copy(j, stream) != hipSuccess) return LP_E_LAUNCH;
+    return launch_stitch(j, WindowOfImage{d.origins}, MaskAsIs(), stream);
 }
 
 }  // namespace lp

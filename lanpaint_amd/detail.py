@@ -114,6 +114,40 @@ class Region:
         return (self.oh, self.ow) != (self.h, self.w)
 
 
+@dataclasses.dataclass(frozen=True)
+class _Windows:
+    """Windows [y0, y0 + h) x [x0, x0 + w) of one size in an H x W image, one per `origins` entry, all detailed at (oh, ow)."""
+    H: int
+    W: int
+    h: int
+    w: int
+    oh: int
+    ow: int
+    origins: tuple
+
+    def __len__(self):
+        return len(self.origins)
+
+    def region(self, i):
+        y0, x0 = self.origins[i]
+        return Region(y0, x0, self.h, self.w, self.oh, self.ow, self.H, self.W)
+
+    @property
+    def resampled(self):
+        return (self.oh, self.ow) != (self.h, self.w)
+
+
+@dataclasses.dataclass(frozen=True)
+class Regions(_Windows):
+    """One window per region of the mask; `members[i]` are the component labels region i owns, ascending."""
+    members: tuple
+
+
+@dataclasses.dataclass(frozen=True)
+class Track(_Windows):
+    """One window per frame of a video: frame f's is at `origins[f]`."""
+
+
 def _ceil_div(a, b):
     return -((-a) // b)
 
@@ -138,21 +172,27 @@ def _working_size(h, w, m, target):
             max(1, (2 * w * target + long_side * m) // (2 * long_side * m)) * m)
 
 
-def plan_region(bbox, H, W, context=1.0, padding=0, multiple_of=8, target=0):
-    """The module docstring's rule: bbox (r0, r1, c0, c1) inclusive -> Region."""
-    r0, r1, c0, c1 = (int(v) for v in bbox)
+def _plan_args(H, W, context, padding, multiple_of, target):
+    """The planners' shared arguments, checked: (H, W, c1000, padding, m, target) as integers, c1000 = context in thousandths."""
     H, W, padding, m, target = int(H), int(W), int(padding), int(multiple_of), int(target)
     if H <= 0 or W <= 0:
         raise ValueError(f"image size must be positive, got {H}x{W}")
-    if r1 < r0 or c1 < c0:
-        raise ValueError("the mask is empty: there is no region to detail")
-    if r0 < 0 or c0 < 0 or r1 >= H or c1 >= W:
-        raise ValueError(f"bbox {(r0, r1, c0, c1)} lies outside the {H}x{W} image")
     c1000 = int(round(float(context) * 1000))
     if c1000 < 1000:
         raise ValueError(f"context must be >= 1.0, got {context!r}")
     if padding < 0 or m < 1 or target < 0:
         raise ValueError(f"padding >= 0, multiple_of >= 1 and target >= 0 are required, got {padding}, {m}, {target}")
+    return H, W, c1000, padding, m, target
+
+
+def plan_region(bbox, H, W, context=1.0, padding=0, multiple_of=8, target=0):
+    """The module docstring's rule: bbox (r0, r1, c0, c1) inclusive -> Region."""
+    r0, r1, c0, c1 = (int(v) for v in bbox)
+    H, W, c1000, padding, m, target = _plan_args(H, W, context, padding, multiple_of, target)
+    if r1 < r0 or c1 < c0:
+        raise ValueError("the mask is empty: there is no region to detail")
+    if r0 < 0 or c0 < 0 or r1 >= H or c1 >= W:
+        raise ValueError(f"bbox {(r0, r1, c0, c1)} lies outside the {H}x{W} image")
     y0, h = _plan_axis(r0, r1, H, c1000, padding, m)
     x0, w = _plan_axis(c0, c1, W, c1000, padding, m)
     oh, ow = _working_size(h, w, m, target)
@@ -242,20 +282,35 @@ def _aa_tables_f32(in_size, out_size, filter):
     return bounds, weights.astype(np.float32)
 
 
-def _resample(src, y0, x0, h, w, oh, ow, filter):
-    """lp_detail_resample on a contiguous fp32 HIP tensor [B, H, W, C]."""
+def _resample(src, win, filter, origins=None, labels=None, owner=None):
+    """Every window of `win` cut out of a contiguous fp32 HIP tensor [B, H, W, C] at win's working size: a Region through
+    lp_detail_resample -> [B, oh, ow, C]; Regions through lp_detail_resample_regions -> [R * B, oh, ow, C], with `labels` and
+    `owner` region r's view of a mask; a Track through lp_detail_resample_track -> [B, oh, ow, C].  `origins`: the device table
+    of the two table forms."""
     b, sh, sw, c = src.shape
-    dev = src.device
-    out = torch.empty((b, oh, ow, c), dtype=torch.float32, device=dev)
-    d = _cabi.LpDetailResampleDesc(b, sh, sw, c, y0, x0, h, w, oh, ow, 0, 0)
+    dev, images, scratch = src.device, b, None
+    if isinstance(win, Region):
+        entry, d = "lp_detail_resample", _cabi.LpDetailResampleDesc(b, sh, sw, c, win.y0, win.x0, win.h, win.w, win.oh, win.ow)
+    elif isinstance(win, Regions):
+        entry, images = "lp_detail_resample_regions", len(win) * b
+        d = _cabi.LpDetailResampleRegionsDesc(b, sh, sw, c, len(win), win.h, win.w, 0, win.oh, win.ow, origins=origins.data_ptr())
+        if labels is not None:
+            d.labels, d.owner, d.owner_len = labels.data_ptr(), owner.data_ptr(), owner.numel()
+            if win.resampled:
+                scratch = torch.empty((images, win.h, win.w), dtype=torch.float32, device=dev)
+                d.scratch = scratch.data_ptr()
+    else:
+        entry = "lp_detail_resample_track"
+        d = _cabi.LpDetailResampleTrackDesc(b, sh, sw, c, win.h, win.w, win.oh, win.ow, origins=origins.data_ptr())
+    out = torch.empty((images, win.oh, win.ow, c), dtype=torch.float32, device=dev)
     d.src, d.dst = src.data_ptr(), out.data_ptr()
-    if (oh, ow) != (h, w):
-        bx, wx = device_tables(_aa_tables_f32, dev, w, ow, filter)
-        by, wy = device_tables(_aa_tables_f32, dev, h, oh, filter)
+    if win.resampled:
+        bx, wx = device_tables(_aa_tables_f32, dev, win.w, win.ow, filter)
+        by, wy = device_tables(_aa_tables_f32, dev, win.h, win.oh, filter)
         d.ksize_x, d.ksize_y = wx.shape[1], wy.shape[1]
         d.bounds_x, d.weights_x, d.bounds_y, d.weights_y = bx.data_ptr(), wx.data_ptr(), by.data_ptr(), wy.data_ptr()
     with torch.cuda.device(dev):
-        _cabi.check(_cabi.load().lp_detail_resample(ctypes.byref(d), raw_stream(dev)), "lp_detail_resample")
+        _cabi.check(getattr(_cabi.load(), entry)(ctypes.byref(d), raw_stream(dev)), entry)
     return out
 
 
@@ -268,40 +323,53 @@ def crop_resample(image, mask, region, filter="bilinear"):
         raise ValueError(f"image must be [B, H, W, C], got {tuple(image.shape)}")
     _check_region(region, img.shape[1], img.shape[2])
     r = region
-    out = _resample(img, r.y0, r.x0, r.h, r.w, r.oh, r.ow, filter)
+    out = _resample(img, r, filter)
     if mask is None:
         return out, None
     m = _as_f32c(_mask3(_hip(mask, "mask")))
     if tuple(m.shape[1:]) != (r.H, r.W):
         raise ValueError(f"mask shape {tuple(mask.shape)} does not match images {tuple(image.shape)}")
-    return out, _resample(m.unsqueeze(-1), r.y0, r.x0, r.h, r.w, r.oh, r.ow, "bilinear").squeeze(-1)
+    return out, _resample(m.unsqueeze(-1), r, "bilinear").squeeze(-1)
+
+
+def _stitch_inputs(original, detail_img, mask, win, blend_overlap, filter, labels=None):
+    """What every stitch starts with: the arguments checked against `win` (a Region, Regions or a Track) and made contiguous
+    fp32 on original's device, the crops resampled back to the windows' size in one launch -> (orig, det, m, b, H, W, c)."""
+    _check_filter(filter)
+    k = blend_overlap
+    if not isinstance(k, int) or k < 1 or k > 51 or k % 2 == 0:
+        raise ValueError(f"blend_overlap must be an odd integer in [1, 51], got {k!r}")
+    name = "detail_imgs" if isinstance(win, Regions) else "detail_img"
+    orig = _as_f32c(_hip(original, "original"))
+    det = _as_f32c(_hip(detail_img, name).to(orig.device))
+    m = _as_f32c(_mask3(_hip(mask, "mask")).to(orig.device))
+    if orig.ndim != 4 or det.ndim != 4:
+        raise ValueError(f"original and {name} must be [B, H, W, C]")
+    b, H, W, c = orig.shape
+    if isinstance(win, Region):
+        _check_region(win, H, W)
+    elif isinstance(win, Regions):
+        _check_regions(win, labels, H, W)
+    else:
+        _check_track(win, b, H, W)
+    want = ((len(win) if isinstance(win, Regions) else 1) * b, win.oh, win.ow, c)
+    if tuple(det.shape) != want:
+        raise ValueError(f"{name} must be {want}, got {tuple(det.shape)}")
+    if m.shape[0] not in (1, b) or tuple(m.shape[1:]) != (H, W):
+        raise ValueError(f"mask shape {tuple(mask.shape)} does not match images {tuple(original.shape)}")
+    if win.resampled:
+        det = _resample(det, Region(0, 0, win.oh, win.ow, win.h, win.w, win.oh, win.ow), filter)
+    return orig, det, m, b, H, W, c
 
 
 def stitch(original, detail_img, mask, region, blend_overlap=1, filter="bilinear"):
     """The detailed crop `detail_img` [B, oh, ow, C] back into `original` [B, H, W, C]: resampled to the region's size, blended
     inside the region through MaskBlend's smoothed mask of the whole image (width `blend_overlap`, odd, 1..51), and the
     original bit for bit outside it.  `mask` as for crop_resample: the full-size mask the region was planned from."""
-    _check_filter(filter)
-    k = blend_overlap
-    if not isinstance(k, int) or k < 1 or k > 51 or k % 2 == 0:
-        raise ValueError(f"blend_overlap must be an odd integer in [1, 51], got {k!r}")
-    orig = _as_f32c(_hip(original, "original"))
-    det = _as_f32c(_hip(detail_img, "detail_img").to(orig.device))
-    m = _as_f32c(_mask3(_hip(mask, "mask")).to(orig.device))
-    if orig.ndim != 4 or det.ndim != 4:
-        raise ValueError("original and detail_img must be [B, H, W, C]")
-    b, H, W, c = orig.shape
-    _check_region(region, H, W)
-    r = region
-    if tuple(det.shape) != (b, r.oh, r.ow, c):
-        raise ValueError(f"detail_img must be {(b, r.oh, r.ow, c)}, got {tuple(det.shape)}")
-    if m.shape[0] not in (1, b) or tuple(m.shape[1:]) != (H, W):
-        raise ValueError(f"mask shape {tuple(mask.shape)} does not match images {tuple(original.shape)}")
-    if r.resampled:
-        det = _resample(det, 0, 0, r.oh, r.ow, r.h, r.w, filter)
-    dev = orig.device
+    orig, det, m, b, H, W, c = _stitch_inputs(original, detail_img, mask, region, blend_overlap, filter)
+    r, dev = region, orig.device
     out = torch.empty_like(orig)
-    d = _cabi.LpDetailStitchDesc(b, H, W, c, r.y0, r.x0, r.h, r.w, k, m.shape[0],
+    d = _cabi.LpDetailStitchDesc(b, H, W, c, r.y0, r.x0, r.h, r.w, blend_overlap, m.shape[0],
                                  m.data_ptr(), orig.data_ptr(), det.data_ptr(), out.data_ptr())
     with torch.cuda.device(dev):
         _cabi.check(_cabi.load().lp_detail_stitch(ctypes.byref(d), raw_stream(dev)), "lp_detail_stitch")
@@ -309,31 +377,6 @@ def stitch(original, detail_img, mask, region, blend_overlap=1, filter="bilinear
 
 
 # ---- per region --------------------------------------------------------------------------------------------------------------
-@dataclasses.dataclass(frozen=True)
-class Regions:
-    """Windows [y0, y0 + h) x [x0, x0 + w) of one size in an H x W image, one per `origins` entry, all detailed at (oh, ow);
-    `members[i]` are the component labels region i owns, ascending."""
-    H: int
-    W: int
-    h: int
-    w: int
-    oh: int
-    ow: int
-    origins: tuple
-    members: tuple
-
-    def __len__(self):
-        return len(self.origins)
-
-    def region(self, i):
-        y0, x0 = self.origins[i]
-        return Region(y0, x0, self.h, self.w, self.oh, self.ow, self.H, self.W)
-
-    @property
-    def resampled(self):
-        return (self.oh, self.ow) != (self.h, self.w)
-
-
 def mask_components(mask):
     """8-connected components of `mask > 0.5` over every frame of a HIP mask [B, H, W], [1, H, W] or [H, W]:
     (labels int32 [H, W] on the device, n, table).  Labels run 1..n in raster order of each component's first pixel, 0 is the
@@ -402,15 +445,8 @@ def plan_regions(components, H, W, context=1.0, padding=0, multiple_of=8, target
     (the 3-tuple itself is taken too) -> Regions.  `bbox`, the mask's bounding box (mask_bbox), is needed only when
     n > LP_DETAIL_MAX_COMPONENTS, where the table is truncated and one region serves the whole mask."""
     n, table = components[-2], components[-1]
-    n, H, W, padding, m, target = int(n), int(H), int(W), int(padding), int(multiple_of), int(target)
-    min_area, max_regions = int(min_area), int(max_regions)
-    if H <= 0 or W <= 0:
-        raise ValueError(f"image size must be positive, got {H}x{W}")
-    c1000 = int(round(float(context) * 1000))
-    if c1000 < 1000:
-        raise ValueError(f"context must be >= 1.0, got {context!r}")
-    if padding < 0 or m < 1 or target < 0:
-        raise ValueError(f"padding >= 0, multiple_of >= 1 and target >= 0 are required, got {padding}, {m}, {target}")
+    H, W, c1000, padding, m, target = _plan_args(H, W, context, padding, multiple_of, target)
+    n, min_area, max_regions = int(n), int(min_area), int(max_regions)
     if min_area < 1 or max_regions < 1:
         raise ValueError(f"min_area >= 1 and max_regions >= 1 are required, got {min_area}, {max_regions}")
     if n <= 0:
@@ -472,29 +508,6 @@ def _check_regions(regions, labels, H, W):
                              f"{tuple(labels.shape)}")
 
 
-def _resample_regions(src, regions, origins, filter, labels=None, owner=None):
-    """lp_detail_resample_regions on a contiguous fp32 HIP tensor [B, H, W, C] -> [R * B, oh, ow, C]."""
-    b, sh, sw, c = src.shape
-    g, dev, n_reg = regions, src.device, len(regions)
-    out = torch.empty((n_reg * b, g.oh, g.ow, c), dtype=torch.float32, device=dev)
-    d = _cabi.LpDetailResampleRegionsDesc(b, sh, sw, c, n_reg, g.h, g.w, 0, g.oh, g.ow, 0, 0)
-    d.origins, d.src, d.dst = origins.data_ptr(), src.data_ptr(), out.data_ptr()
-    scratch = None
-    if labels is not None:
-        d.labels, d.owner, d.owner_len = labels.data_ptr(), owner.data_ptr(), owner.numel()
-    if g.resampled:
-        bx, wx = device_tables(_aa_tables_f32, dev, g.w, g.ow, filter)
-        by, wy = device_tables(_aa_tables_f32, dev, g.h, g.oh, filter)
-        d.ksize_x, d.ksize_y = wx.shape[1], wy.shape[1]
-        d.bounds_x, d.weights_x, d.bounds_y, d.weights_y = bx.data_ptr(), wx.data_ptr(), by.data_ptr(), wy.data_ptr()
-        if labels is not None:
-            scratch = torch.empty((n_reg * b, g.h, g.w), dtype=torch.float32, device=dev)
-            d.scratch = scratch.data_ptr()
-    with torch.cuda.device(dev):
-        _cabi.check(_cabi.load().lp_detail_resample_regions(ctypes.byref(d), raw_stream(dev)), "lp_detail_resample_regions")
-    return out
-
-
 def crop_regions(image, mask, regions, labels=None, filter="bilinear"):
     """crop_resample for every region at once: (image [R * B, oh, ow, C], mask [R * Bm, oh, ow] or None), region-major, so the
     stack is one sampler batch.  Region i's mask is `mask` with the components of other regions -- and those min_area dropped
@@ -506,13 +519,13 @@ def crop_regions(image, mask, regions, labels=None, filter="bilinear"):
     H, W = img.shape[1], img.shape[2]
     _check_regions(regions, labels, H, W)
     origins, owner = _region_tables(regions, labels, img.device)
-    out = _resample_regions(img, regions, origins, filter)
+    out = _resample(img, regions, filter, origins)
     if mask is None:
         return out, None
     m = _as_f32c(_mask3(_hip(mask, "mask")).to(img.device))
     if tuple(m.shape[1:]) != (H, W):
         raise ValueError(f"mask shape {tuple(mask.shape)} does not match images {tuple(image.shape)}")
-    return out, _resample_regions(m.unsqueeze(-1), regions, origins, "bilinear", labels, owner).squeeze(-1)
+    return out, _resample(m.unsqueeze(-1), regions, "bilinear", origins, labels, owner).squeeze(-1)
 
 
 def stitch_regions(original, detail_imgs, mask, regions, labels=None, blend_overlap=1, filter="bilinear"):
@@ -520,25 +533,8 @@ def stitch_regions(original, detail_imgs, mask, regions, labels=None, blend_over
     [B, H, W, C].  The result is the composition of `stitch` in region order,  out_0 = original,  out_{i+1} = stitch(out_i,
     detail_i, mask_i, region i),  bit for bit -- equalised windows may overlap, so the order counts -- computed as one copy of
     the frame and then each region's window in place."""
-    _check_filter(filter)
-    k = blend_overlap
-    if not isinstance(k, int) or k < 1 or k > 51 or k % 2 == 0:
-        raise ValueError(f"blend_overlap must be an odd integer in [1, 51], got {k!r}")
-    orig = _as_f32c(_hip(original, "original"))
-    det = _as_f32c(_hip(detail_imgs, "detail_imgs").to(orig.device))
-    m = _as_f32c(_mask3(_hip(mask, "mask")).to(orig.device))
-    if orig.ndim != 4 or det.ndim != 4:
-        raise ValueError("original and detail_imgs must be [B, H, W, C]")
-    b, H, W, c = orig.shape
-    _check_regions(regions, labels, H, W)
-    g, n_reg = regions, len(regions)
-    if tuple(det.shape) != (n_reg * b, g.oh, g.ow, c):
-        raise ValueError(f"detail_imgs must be {(n_reg * b, g.oh, g.ow, c)}, got {tuple(det.shape)}")
-    if m.shape[0] not in (1, b) or tuple(m.shape[1:]) != (H, W):
-        raise ValueError(f"mask shape {tuple(mask.shape)} does not match images {tuple(original.shape)}")
-    if g.resampled:
-        det = _resample(det, 0, 0, g.oh, g.ow, g.h, g.w, filter)             # every crop in one launch
-    dev = orig.device
+    orig, det, m, b, H, W, c = _stitch_inputs(original, detail_imgs, mask, regions, blend_overlap, filter, labels)
+    g, n_reg, k, dev = regions, len(regions), blend_overlap, orig.device
     _, owner = _region_tables(regions, labels, dev)
     host_origins = (ctypes.c_int32 * (2 * n_reg))(*(v for o in g.origins for v in o))
     out = torch.empty_like(orig)
@@ -553,29 +549,6 @@ def stitch_regions(original, detail_imgs, mask, regions, labels=None, blend_over
 
 
 # ---- per frame: a window that follows a moving mask --------------------------------------------------------------------------------
-@dataclasses.dataclass(frozen=True)
-class Track:
-    """Windows [y0, y0 + h) x [x0, x0 + w) of one size in an H x W image, frame f's at `origins[f]`, all detailed at (oh, ow)."""
-    H: int
-    W: int
-    h: int
-    w: int
-    oh: int
-    ow: int
-    origins: tuple
-
-    def __len__(self):
-        return len(self.origins)
-
-    def region(self, f):
-        y0, x0 = self.origins[f]
-        return Region(y0, x0, self.h, self.w, self.oh, self.ow, self.H, self.W)
-
-    @property
-    def resampled(self):
-        return (self.oh, self.ow) != (self.h, self.w)
-
-
 def _track_axis(spans, n_img, c1000, padding, m, k):
     """One axis of the track rule: spans[f] = (a0, a1) inclusive, or None for an empty frame -> (origins, n)."""
     frames = len(spans)
@@ -611,14 +584,7 @@ def plan_track(boxes, H, W, context=1.0, padding=0, multiple_of=8, target=0, smo
     them (r1 < r0) -> Track.  `frames` is the length of the batch the track serves: len(boxes) when not given, and a single
     box is repeated to it (a static mask)."""
     boxes = [tuple(int(v) for v in box) for box in boxes]
-    H, W, padding, m, target = int(H), int(W), int(padding), int(multiple_of), int(target)
-    if H <= 0 or W <= 0:
-        raise ValueError(f"image size must be positive, got {H}x{W}")
-    c1000 = int(round(float(context) * 1000))
-    if c1000 < 1000:
-        raise ValueError(f"context must be >= 1.0, got {context!r}")
-    if padding < 0 or m < 1 or target < 0:
-        raise ValueError(f"padding >= 0, multiple_of >= 1 and target >= 0 are required, got {padding}, {m}, {target}")
+    H, W, c1000, padding, m, target = _plan_args(H, W, context, padding, multiple_of, target)
     if isinstance(smooth, bool) or int(smooth) != smooth or smooth < 1 or smooth % 2 == 0:
         raise ValueError(f"smooth must be an odd integer >= 1, got {smooth!r}")
     frames = len(boxes) if frames is None else int(frames)
@@ -673,23 +639,6 @@ def _track_origins(track, dev):
     return torch.tensor(track.origins, dtype=torch.int32, device=dev).reshape(-1, 2)
 
 
-def _resample_track(src, track, origins, filter):
-    """lp_detail_resample_track on a contiguous fp32 HIP tensor [B, H, W, C] -> [B, oh, ow, C]."""
-    b, sh, sw, c = src.shape
-    t, dev = track, src.device
-    out = torch.empty((b, t.oh, t.ow, c), dtype=torch.float32, device=dev)
-    d = _cabi.LpDetailResampleTrackDesc(b, sh, sw, c, t.h, t.w, t.oh, t.ow, 0, 0)
-    d.origins, d.src, d.dst = origins.data_ptr(), src.data_ptr(), out.data_ptr()
-    if t.resampled:
-        bx, wx = device_tables(_aa_tables_f32, dev, t.w, t.ow, filter)
-        by, wy = device_tables(_aa_tables_f32, dev, t.h, t.oh, filter)
-        d.ksize_x, d.ksize_y = wx.shape[1], wy.shape[1]
-        d.bounds_x, d.weights_x, d.bounds_y, d.weights_y = bx.data_ptr(), wx.data_ptr(), by.data_ptr(), wy.data_ptr()
-    with torch.cuda.device(dev):
-        _cabi.check(_cabi.load().lp_detail_resample_track(ctypes.byref(d), raw_stream(dev)), "lp_detail_resample_track")
-    return out
-
-
 def crop_track(image, mask, track, filter="bilinear"):
     """crop_resample with frame f cut at `track.region(f)`: (image [B, oh, ow, C], mask [Bm, oh, ow] or None), each frame what
     crop_resample gives for it alone, bit for bit.  A one-plane mask stays one plane while the track stands still (plan_track
@@ -701,7 +650,7 @@ def crop_track(image, mask, track, filter="bilinear"):
     b, H, W = img.shape[0], img.shape[1], img.shape[2]
     _check_track(track, b, H, W)
     origins = _track_origins(track, img.device)
-    out = _resample_track(img, track, origins, filter)
+    out = _resample(img, track, filter, origins)
     if mask is None:
         return out, None
     m = _mask3(_hip(mask, "mask")).to(img.device)
@@ -712,32 +661,15 @@ def crop_track(image, mask, track, filter="bilinear"):
             origins = origins[:1]
         else:
             m = m.expand(b, H, W)
-    return out, _resample_track(_as_f32c(m).unsqueeze(-1), track, origins, "bilinear").squeeze(-1)
+    return out, _resample(_as_f32c(m).unsqueeze(-1), track, "bilinear", origins).squeeze(-1)
 
 
 def stitch_track(original, detail_img, mask, track, blend_overlap=1, filter="bilinear"):
     """`stitch` with frame f's crop put back at `track.region(f)`: the detailed crops `detail_img` [B, oh, ow, C] into
     `original` [B, H, W, C], frame by frame what `stitch` gives, bit for bit, as one copy of the frames and one launch over
     every frame's window.  `mask` [B, H, W] or one plane for all frames."""
-    _check_filter(filter)
-    k = blend_overlap
-    if not isinstance(k, int) or k < 1 or k > 51 or k % 2 == 0:
-        raise ValueError(f"blend_overlap must be an odd integer in [1, 51], got {k!r}")
-    orig = _as_f32c(_hip(original, "original"))
-    det = _as_f32c(_hip(detail_img, "detail_img").to(orig.device))
-    m = _as_f32c(_mask3(_hip(mask, "mask")).to(orig.device))
-    if orig.ndim != 4 or det.ndim != 4:
-        raise ValueError("original and detail_img must be [B, H, W, C]")
-    b, H, W, c = orig.shape
-    _check_track(track, b, H, W)
-    t = track
-    if tuple(det.shape) != (b, t.oh, t.ow, c):
-        raise ValueError(f"detail_img must be {(b, t.oh, t.ow, c)}, got {tuple(det.shape)}")
-    if m.shape[0] not in (1, b) or tuple(m.shape[1:]) != (H, W):
-        raise ValueError(f"mask shape {tuple(mask.shape)} does not match images {tuple(original.shape)}")
-    if t.resampled:
-        det = _resample(det, 0, 0, t.oh, t.ow, t.h, t.w, filter)
-    dev = orig.device
+    orig, det, m, b, H, W, c = _stitch_inputs(original, detail_img, mask, track, blend_overlap, filter)
+    t, k, dev = track, blend_overlap, orig.device
     origins = _track_origins(t, dev)
     out = torch.empty_like(orig)
     d = _cabi.LpDetailStitchTrackDesc(b, H, W, c, t.h, t.w, k, m.shape[0],

@@ -351,3 +351,99 @@ def test_track_at_video_size_frames_0_40_80_equal_the_per_frame_calls():
         assert bool((want != image_d[f:f + 1]).any())
     outside = (~_window_mask(track)).to(DEV)                             # compared on the device: 81 frames are large
     assert bool(outside.any()) and torch.equal(out.view(torch.int32)[outside], image_d.view(torch.int32)[outside])
+
+
+# ---- the device-side origin clamp, through the C entries ------------------------------------------------------------------------------
+# The header promises for both device tables that "an origin is clamped so that its window lies inside the image"; the Python
+# wrappers refuse such tables, so only a raw call reaches the clamp.  Every tensor a window indexes is the middle of one with a
+# guard frame before and after: an origin left unclamped by up to 3 rows still reads and writes allocated memory, and the test
+# fails by value.
+_CLAMP_H, _CLAMP_W, _CLAMP_WIN = 23, 31, (8, 12)
+_CLAMP_ORIGINS = ((-3, -2), (_CLAMP_H - 8 + 3, _CLAMP_W - 12 + 1), (5, 7))
+_GUARD = -7.0
+
+
+def _clamped(origins):
+    h, w = _CLAMP_WIN
+    return tuple((min(max(y, 0), _CLAMP_H - h), min(max(x, 0), _CLAMP_W - w)) for y, x in origins)
+
+
+def _guarded(frames, *rest, seed=None):
+    """(whole, middle): `frames` frames between two guard frames; random in the middle with `seed`, the guard value without."""
+    whole = torch.full((frames + 2, *rest), _GUARD)
+    if seed is not None:
+        whole[1:-1] = torch.rand(frames, *rest, generator=_gen(seed))
+    whole = whole.to(DEV)
+    return whole, whole[1:-1]
+
+
+def _axis_tables(n_in, n_out):
+    bounds, weights = detail.aa_coeffs(n_in, n_out, "bilinear")
+    return torch.from_numpy(bounds.copy()).to(DEV), torch.from_numpy(weights.astype(np.float32)).to(DEV)
+
+
+def _raw(entry, desc):
+    import ctypes
+    from lanpaint_amd import _cabi
+    from lanpaint_amd._util import raw_stream
+    with torch.cuda.device(DEV):
+        _cabi.check(getattr(_cabi.load(), entry)(ctypes.byref(desc), raw_stream(DEV)), entry)
+    torch.cuda.synchronize()
+
+
+@pytest.mark.parametrize("out_hw", [(8, 12), (16, 20)])
+@pytest.mark.parametrize("c", [1, 3])
+def test_device_origin_tables_are_clamped_in_both_resample_entries(c, out_hw):
+    from lanpaint_amd import _cabi
+    assert _clamped(_CLAMP_ORIGINS) == ((0, 0), (15, 19), (5, 7))
+    (h, w), (oh, ow), B = _CLAMP_WIN, out_hw, 3
+    _, src = _guarded(B, _CLAMP_H, _CLAMP_W, c, seed=61)
+    tables = (_axis_tables(w, ow), _axis_tables(h, oh)) if out_hw != _CLAMP_WIN else None
+
+    def run(entry, origins):
+        table = torch.tensor(origins, dtype=torch.int32, device=DEV)
+        regions = len(origins) if entry == "lp_detail_resample_regions" else 1
+        whole, dst = _guarded(regions * B, oh, ow, c)
+        if regions > 1:
+            d = _cabi.LpDetailResampleRegionsDesc(B, _CLAMP_H, _CLAMP_W, c, regions, h, w, 0, oh, ow)
+        else:
+            d = _cabi.LpDetailResampleTrackDesc(B, _CLAMP_H, _CLAMP_W, c, h, w, oh, ow)
+        d.origins, d.src, d.dst = table.data_ptr(), src.data_ptr(), dst.data_ptr()
+        if tables:
+            (bx, wx), (by, wy) = tables
+            d.ksize_x, d.ksize_y = wx.shape[1], wy.shape[1]
+            d.bounds_x, d.weights_x, d.bounds_y, d.weights_y = bx.data_ptr(), wx.data_ptr(), by.data_ptr(), wy.data_ptr()
+        _raw(entry, d)
+        assert bool((whole[0] == _GUARD).all()) and bool((whole[-1] == _GUARD).all()), entry
+        assert bool((dst != _GUARD).all()), entry                        # every element of every window was written
+        return whole
+
+    for entry in ("lp_detail_resample_regions", "lp_detail_resample_track"):
+        assert torch.equal(run(entry, _CLAMP_ORIGINS), run(entry, _clamped(_CLAMP_ORIGINS))), entry
+
+
+@pytest.mark.parametrize("k", [1, 17])
+@pytest.mark.parametrize("c", [1, 3])
+def test_device_origin_table_is_clamped_in_the_track_stitch(c, k):
+    from lanpaint_amd import _cabi
+    (h, w), B = _CLAMP_WIN, 3
+    _, original = _guarded(B, _CLAMP_H, _CLAMP_W, c, seed=62)
+    _, mask = _guarded(B, _CLAMP_H, _CLAMP_W, seed=63)
+    detail_img = (torch.rand(B, h, w, c, generator=_gen(64)) + 2.0).to(DEV)      # [2, 3): a blended element differs from the original
+
+    def run(origins):
+        table = torch.tensor(origins, dtype=torch.int32, device=DEV)
+        whole, out = _guarded(B, _CLAMP_H, _CLAMP_W, c)
+        d = _cabi.LpDetailStitchTrackDesc(B, _CLAMP_H, _CLAMP_W, c, h, w, k, B, table.data_ptr(), mask.data_ptr(),
+                                          original.data_ptr(), detail_img.data_ptr(), out.data_ptr())
+        _raw("lp_detail_stitch_track", d)
+        assert bool((whole[0] == _GUARD).all()) and bool((whole[-1] == _GUARD).all())
+        return whole
+
+    got, want = run(_CLAMP_ORIGINS), run(_clamped(_CLAMP_ORIGINS))
+    assert torch.equal(got, want)
+    inside = torch.zeros(B, _CLAMP_H, _CLAMP_W, dtype=torch.bool)
+    for f, (y0, x0) in enumerate(_clamped(_CLAMP_ORIGINS)):
+        inside[f, y0:y0 + h, x0:x0 + w] = True
+    changed = (got[1:-1] != original).any(dim=-1).cpu()
+    assert bool(changed.any()) and not bool((changed & ~inside).any())   # the blend happened, and only inside the clamped windows
