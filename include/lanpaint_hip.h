@@ -721,8 +721,10 @@ LP_API int lp_vmask_resize(const lp_vmask_resize_desc* desc, void* stream);
  *         = mask[src(i)]                     otherwise; src = ATen's nearest-exact 1-D index, rule nn_rule (LP_NN_ATEN_*)
  *   w'[i] = (1/cf) * sum_{k=0}^{cf-1} w[clamp(i - cf/2 + k, 0, n-1)]      when cf > 1 (integer cf/2; any cf >= 1 vs n);
  *           the reference's replicate pad (cf/2, cf-1-cf/2) + conv1d(ones/cf).  Evaluated as float(S * double(1.0f / cf)):
- *           S the exact window sum in fp64, times the reference's fp32 kernel tap, rounded once -- for a 0/1 mask
- *           w' = fl(count * fl(1/cf)).  cf <= 1: w' = w.
+ *           S the window sum in fp64, times the reference's fp32 kernel tap, rounded once.  For a 0/1 mask S is exact and
+ *           w' = fl(count * fl(1/cf)).  For soft values S is a difference of two fp64 prefixes of the whole signal and
+ *           carries their rounding: |w' - exact| <= ulp32(w') + (mask_len + 4) * 2^-52 * sum_i |w[i]| / cf -- absolute
+ *           error far below the reference's own conv1d, but many fp32 ulps of a w' that is itself tiny.  cf <= 1: w' = w.
  *   out[b][c][i] = o * (1 - w') + p * w'     fp32, every product and the sum rounded on its own (no FMA), like torch's ops
  * o = orig[b * orig_sb + c * orig_sc + i], p = inpainted[b * inp_sb + c * inp_sc + i] (element strides; 0 = broadcast: the
  * reference's mono expand and batch broadcasting; orig[:, :Ci] is orig_sc with channels = Ci).  Samples are contiguous in

@@ -9,7 +9,9 @@
 //                          end terms -- O(1) per sample for any cf -- then o * (1 - w') + p * w' for every output row.
 //
 // The weight is piecewise constant over at most mask_len segments and src() is monotone, so the window sum of samples
-// [lo, hi) is C(hi) - C(lo).  For a 0/1 mask every term is an integer and the sum exact; w' = float(S * double(1.0f / cf)).
+// [lo, hi) is C(hi) - C(lo).  For a 0/1 mask every term is an integer and the sum exact; for soft values the difference
+// carries the rounding of two whole-signal fp64 prefixes, at most (mask_len + 4) * 2^-52 * sum |w| (include/lanpaint_hip.h):
+// small in absolute terms, many fp32 ulps where w' itself is tiny.  w' = float(S * double(1.0f / cf)).
 // Bytes moved: 3 x 4 B per sample and row (two loads, one store); the mask and its tables stay in L2.
 #include "lp_common.h"
 

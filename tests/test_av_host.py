@@ -14,7 +14,7 @@ import torch
 
 from lanpaint_amd import _cabi, audio, av_nodes, interp_rule
 from oracle import lanpaint_oracle as orc
-from tests import av_stubs
+from tests import audio_ref, av_stubs
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden")
@@ -177,7 +177,8 @@ def test_float64_restatement_matches_the_reference(path):
 
 
 @pytest.mark.parametrize("fm,n,cf", [(2, 41, 4), (10, 882, 44), (12, 600, 25), (50, 37, 5), (9, 480, 3), (6, 300, 500),
-                                     (30, 48000, 960), (7, 1001, 1)])
+                                     (30, 48000, 960), (7, 1001, 1), (1025, 2053, 44), (2049, 1500, 45),
+                                     (3000, 3000, 961)])
 @pytest.mark.parametrize("rule", sorted(RULE_NAMES))
 def test_segment_prefix_tables_give_the_window_sums(fm, n, cf, rule):
     """The algorithm of csrc/audio_kernel.hip: start[s] = first sample whose source index is >= s, P[s] = sum over the
@@ -201,6 +202,70 @@ def test_segment_prefix_tables_give_the_window_sums(fm, n, cf, rule):
         S = (lo - lo_raw) * float(am[src[0]]) + (lo_raw + cf - hi) * float(am[src[-1]]) + C[hi] - C[lo]
         direct = np.array([am[src[np.clip(k - cf // 2 + np.arange(cf), 0, n - 1)]].astype(np.float64).sum() for k in i])
         np.testing.assert_allclose(S, direct, rtol=0, atol=1e-9)
+
+
+# ---------------------------------------------------------------- the live reference of the GPU shape tests (tests/audio_ref.py)
+@pytest.mark.parametrize("path", [p for p in MERGE_FIXTURES if "err_" not in p], ids=fixture_id)
+def test_live_reference_matches_the_fixtures(path):
+    """tests/audio_ref.py -- torch's own index, int64 counts or direct float64 window sums, no whole-signal prefix -- against
+    what the reference recorded and against the float64 restatement: the two references of the GPU tests agree here."""
+    rec = load(path)
+    o, p = rec["orig"], rec["inpainted"]
+    n = min(o.shape[-1], p.shape[-1])
+    am = audio.normalize_mask(torch.from_numpy(rec["mask"])).numpy()
+    cf = audio.crossfade_samples(float(rec["crossfade"]), int(rec["orig_sr"]))
+    src = audio_ref.src_index_live(am.shape[0], n, "cpu")
+    w = audio_ref.weights_ref(am, src, cf)
+    assert w.dtype == np.float32 and w.shape == (n,)
+    np.testing.assert_allclose(w, rec["weights"], rtol=0, atol=3e-5)
+    if cf <= 1:
+        np.testing.assert_array_equal(w, rec["weights"])
+    restated = weights_f64(am, n, cf, host_rule(rec))
+    bound = audio_ref.weight_bound(am, src, cf)
+    assert np.all(np.abs(w.astype(np.float64) - restated.astype(np.float64)) <= audio_ref.ulp32(w) + bound)
+    if audio_ref.is_hard(am):
+        assert bound == 0.0
+    out = audio_ref.merge_ref(o[..., :n], p[..., :n], w)
+    assert out.shape == rec["out"].shape
+    np.testing.assert_allclose(out, rec["out"], rtol=0, atol=1e-4)
+
+
+@pytest.mark.parametrize("fm,n", [(1025, 2053), (2049, 1500), (5000, 37), (250, 480000), (2047, 14329), (7, 2 ** 24 + 12)])
+def test_live_source_index_is_the_rule_interp_rule_picks(fm, n):
+    """torch's CPU kernel asked directly (interpolating an arange) gives the index of the rule `interp_rule.rule_for` names
+    for that call, monotone and inside the mask -- also where float(i) is inexact."""
+    src = audio_ref.src_index_live(fm, n, "cpu")
+    am = torch.zeros(fm)
+    rule = interp_rule.rule_for(am, am.reshape(1, 1, -1), (n,))
+    np.testing.assert_array_equal(src, orc.nearest_exact_src_index(n, fm, RULE_NAMES[rule]))
+    assert src.dtype == np.int64 and src.shape == (n,) and src[0] >= 0 and src[-1] <= fm - 1 and np.all(np.diff(src) >= 0)
+    if n >= fm:
+        assert src[0] == 0 and src[-1] == fm - 1 and np.all(np.diff(src) <= 1)            # up-sampled: no segment is empty
+    np.testing.assert_array_equal(audio_ref.src_index_live(9, 9, "cpu"), np.arange(9))
+
+
+@pytest.mark.parametrize("fm,n,cf", [(5, 23, 4), (9, 40, 7), (6, 11, 30), (40, 40, 5), (12, 7, 3)])
+def test_reference_window_sums_against_a_plain_loop(fm, n, cf):
+    """weights_ref's two ways of summing (int64 counts, float64 conv1d) against the header's formula as a loop with an exactly
+    rounded sum; on a 0/1 mask the float64 way, forced, gives the bits of the int64 way."""
+    import math
+    rng = np.random.default_rng(fm * n + cf)
+    src = audio_ref.src_index_live(fm, n, "cpu")
+    tap = np.float64(np.float32(1) / np.float32(cf))
+    for am in ((rng.random(fm) < 0.5).astype(np.float32), rng.random(fm, dtype=np.float32)):
+        w = am[src].astype(np.float64)
+        want = np.array([math.fsum(w[min(max(i - cf // 2 + k, 0), n - 1)] for k in range(cf)) * tap for i in range(n)])
+        got = audio_ref.weights_ref(am, src, cf)
+        if audio_ref.is_hard(am):
+            np.testing.assert_array_equal(got, want.astype(np.float32))
+            nudged = am.copy()
+            nudged[0] = nudged[0] + np.float32(2.0 ** -30) if nudged[0] == 0 else nudged[0]        # soft path, same sums to 1e-9
+            assert not audio_ref.is_hard(nudged) or nudged[0] == 1
+            np.testing.assert_allclose(audio_ref.weights_ref(nudged, src, cf), got, rtol=0, atol=1e-8)
+        else:
+            assert np.all(np.abs(got.astype(np.float64) - want) <= audio_ref.ulp32(got))
+            assert 0 < audio_ref.weight_bound(am, src, cf) < 1e-12
+    assert audio_ref.weights_ref(np.full(3, 0.5, np.float32), np.zeros(10 ** 6, np.int64), 501) is None      # n * cf > 5e8
 
 
 # ---------------------------------------------------------------- lp_audio_merge argument checks (no device call)
