@@ -929,6 +929,96 @@ typedef struct lp_detail_stitch_track_desc {
 } lp_detail_stitch_track_desc;
 LP_API int lp_detail_stitch_track(const lp_detail_stitch_track_desc* desc, void* stream);
 
+/* ---- Detailer per subject of a video (beyond the reference, like the Detailer itself) -------------------------------------------
+ * Several masked subjects that move: the per-region form labels the union over frames, where a walking person is a smear and
+ * two people whose paths cross are one component; the track form has one box per frame, which spans every subject.  Here the
+ * mask is labelled in space and time, a subject is a set of space-time components, and every (subject, frame) gets a window of
+ * its own, all of one size.  The host (lanpaint_amd/detail_subjects.py, plan_subjects) groups components into subjects and plans
+ * each subject's path.  A job reads two tables back: the components table (n and 7 ints per component, about 112 KB at the
+ * cap) and the boxes table (about 83 KB at 64 subjects x 81 frames).                                                          */
+
+/* Connected components of  S = {(f, y, x): mask[f, y, x] > 0.5}  -- no union over planes --, 26-connected in (f, y, x).  A
+ * component's label is 1 + the rank of its smallest flat index (f * height + y) * width + x: labels run 1..n in raster order of
+ * first voxel, 0 is background -- scipy.ndimage.label(S, ones((3, 3, 3))).
+ *   mask    [frames, height, width] fp32
+ *   labels  out, device, int32 [frames, height, width]; exact whatever n is
+ *   table   out, device, int32 [1 + 7 * LP_DETAIL_MAX_COMPONENTS]: table[0] = n, the true count even past the cap; for
+ *           id = 1 .. min(n, cap), table[1 + 7 * (id - 1) ..] = {f_min, f_max, row_min, row_max, col_min, col_max, volume},
+ *           bounds inclusive; rows past n hold {frames, -1, height, -1, width, -1, 0}
+ *   workspace  device, LP_COMPONENTS_FRAMES_WS_BYTES(frames, height, width) bytes, 16-byte aligned
+ * lp_mask_components' seven launches on the volume (tile and border per frame) plus one that unites every frame with the one
+ * before it (csrc/label_kernel.hip); integer atomics only, the result does not depend on the order of arrival.
+ * LP_E_INVALID: null pointer, frames <= 0, a side outside 1..LP_DETAIL_MAX_SIDE, a short workspace; LP_E_ALIGN: workspace not
+ * 16-byte aligned; LP_E_UNSUPPORTED: frames > 65535 or frames * height * width > 2^30 (parents are int32 flat indices).  All
+ * checked before any HIP call.                                                                                               */
+#define LP_COMPONENTS_FRAMES_WS_BYTES(frames, height, width) \
+    ((((int64_t)(frames) * (height) * (width) + 1023) / 1024) * 4100)
+LP_API int lp_mask_components_frames(const float* mask, int32_t frames, int32_t height, int32_t width, int32_t* labels,
+                                     int32_t* table, void* workspace, int64_t workspace_bytes, void* stream);
+
+/* One bounding box per (subject, frame) of a label volume.
+ *   labels  device int32 [frames, height, width] (lp_mask_components_frames)
+ *   owner   device int32 [owner_len]: owner[label] = subject + 1, 0 for a label no subject owns; a label >= owner_len and an
+ *           owner outside 1..subjects are nobody's
+ *   boxes   out, device, int32 [subjects, frames, 4] = {row_min, row_max, col_min, col_max}, inclusive, over the voxels of
+ *           frame f whose label's owner is s + 1; {height, -1, width, -1} where there is none.  Initialised by this call.
+ * One launch over every frame, integer atomics only.  LP_E_INVALID: null pointer, frames <= 0, a side outside
+ * 1..LP_DETAIL_MAX_SIDE, owner_len < 1, subjects outside 1..LP_DETAIL_MAX_REGIONS; LP_E_UNSUPPORTED: frames > 65535.         */
+LP_API int lp_subject_boxes(const int32_t* labels, int32_t frames, int32_t height, int32_t width, const int32_t* owner,
+                            int32_t owner_len, int32_t subjects, int32_t* boxes, void* stream);
+
+/* lp_detail_resample for a window per (subject, image):  dst [subjects * batch, out_h, out_w, channels], subject-major,
+ * dst[s * batch + f] = lp_detail_resample of the window at origins[s * batch + f] of src[f], bit for bit, in one launch.
+ *   origins  DEVICE int32 [subjects * batch, 2] = (y0, x0); an origin is clamped so that its window lies inside the image
+ * With `labels` the source is a mask (channels == 1) and subject s sees image f with foreign components erased, as in
+ * lp_detail_resample_regions but read from image f's label plane:
+ *   labels  device int32 [batch, src_h, src_w] (lp_mask_components_frames), or NULL: no erasing;  owner  device int32 [owner_len]
+ *   scratch device fp32 [subjects * batch * win_h * win_w], 16-byte aligned: the erased windows, needed with `labels` when the
+ *           size changes
+ * Errors as lp_detail_resample, plus LP_E_INVALID: subjects outside 1..LP_DETAIL_MAX_REGIONS, null origins, labels with
+ * channels != 1 or without owner / scratch; LP_E_UNSUPPORTED: subjects * batch > 65535.                                      */
+typedef struct lp_detail_resample_subjects_desc {
+    int32_t batch, src_h, src_w, channels;
+    int32_t subjects, win_h, win_w, owner_len;
+    int32_t out_h, out_w, ksize_x, ksize_y;
+    const int32_t* origins;
+    const float*   src;
+    const int32_t* bounds_x;
+    const float*   weights_x;
+    const int32_t* bounds_y;
+    const float*   weights_y;
+    float*         dst;
+    const int32_t* labels;
+    const int32_t* owner;
+    float*         scratch;
+} lp_detail_resample_subjects_desc;
+LP_API int lp_detail_resample_subjects(const lp_detail_resample_subjects_desc* desc, void* stream);
+
+/* lp_detail_stitch composed over subjects, in subject order, frame by frame:
+ *   out_0 = original;   out_{s+1}[f] = lp_detail_stitch(out_s[f], detail[s * batch + f], mask_s[f], window (s, f));   out = out_subjects
+ * bit for bit, mask_s[f] frame f's mask with foreign components erased as above (labels NULL: the mask itself for every
+ * subject).  Windows of different subjects may overlap, so the order is part of the result.  One streaming copy original ->
+ * out, then one launch per subject over the tiles of all frames' windows (the frame on a grid axis), in place on out: one
+ * thread reads and writes a given element, and the mask halo is read from the mask, never from out.
+ *   origins  DEVICE int32 [subjects * batch, 2] = (y0, x0), clamped as above
+ *   mask     [batch, height, width]: one plane per image
+ *   detail   [subjects * batch, win_h, win_w, channels], subject-major, already at the window's size
+ * Errors as lp_detail_stitch, plus LP_E_INVALID: subjects outside 1..LP_DETAIL_MAX_REGIONS, null origins, labels without
+ * owner.                                                                                                                    */
+typedef struct lp_detail_stitch_subjects_desc {
+    int32_t batch, height, width, channels;
+    int32_t subjects, win_h, win_w, k;
+    int32_t owner_len, reserved0;
+    const int32_t* origins;
+    const float*   mask;
+    const float*   original;
+    const float*   detail;
+    float*         out;
+    const int32_t* labels;
+    const int32_t* owner;
+} lp_detail_stitch_subjects_desc;
+LP_API int lp_detail_stitch_subjects(const lp_detail_stitch_subjects_desc* desc, void* stream);
+
 /* ---- Detailer colour match (beyond the reference, like the Detailer itself) -----------------------------------------------------
  * A crop that went through resample, VAE, sampler and VAE comes back with a small gain and offset per channel.  Outside the
  * mask the decoded crop shows what the original crop shows, so statistics taken there are like for like: three calls between

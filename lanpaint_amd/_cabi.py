@@ -222,6 +222,23 @@ class LpDetailStitchTrackDesc(C.Structure):
                 ("out", C.c_void_p)]
 
 
+class LpDetailResampleSubjectsDesc(C.Structure):
+    _fields_ = [("batch", C.c_int32), ("src_h", C.c_int32), ("src_w", C.c_int32), ("channels", C.c_int32),
+                ("subjects", C.c_int32), ("win_h", C.c_int32), ("win_w", C.c_int32), ("owner_len", C.c_int32),
+                ("out_h", C.c_int32), ("out_w", C.c_int32), ("ksize_x", C.c_int32), ("ksize_y", C.c_int32),
+                ("origins", C.c_void_p), ("src", C.c_void_p), ("bounds_x", C.c_void_p), ("weights_x", C.c_void_p),
+                ("bounds_y", C.c_void_p), ("weights_y", C.c_void_p), ("dst", C.c_void_p), ("labels", C.c_void_p),
+                ("owner", C.c_void_p), ("scratch", C.c_void_p)]
+
+
+class LpDetailStitchSubjectsDesc(C.Structure):
+    _fields_ = [("batch", C.c_int32), ("height", C.c_int32), ("width", C.c_int32), ("channels", C.c_int32),
+                ("subjects", C.c_int32), ("win_h", C.c_int32), ("win_w", C.c_int32), ("k", C.c_int32),
+                ("owner_len", C.c_int32), ("reserved0", C.c_int32),
+                ("origins", C.c_void_p), ("mask", C.c_void_p), ("original", C.c_void_p), ("detail", C.c_void_p),
+                ("out", C.c_void_p), ("labels", C.c_void_p), ("owner", C.c_void_p)]
+
+
 LP_COLOR_MIN_COUNT, LP_COLOR_MAX_MARGIN, LP_COLOR_TILE_H, LP_COLOR_TILE_W = 64, 25, 32, 128
 LP_COLOR_METHOD_MEAN, LP_COLOR_METHOD_MEAN_STD = 0, 1
 
@@ -253,6 +270,11 @@ def lp_color_ws_bytes(batch, height, width, channels):
 def lp_components_ws_bytes(height, width):
     """LP_COMPONENTS_WS_BYTES of include/lanpaint_hip.h."""
     return ((int(height) * int(width) + 1023) // 1024) * 4100
+
+
+def lp_components_frames_ws_bytes(frames, height, width):
+    """LP_COMPONENTS_FRAMES_WS_BYTES of include/lanpaint_hip.h."""
+    return ((int(frames) * int(height) * int(width) + 1023) // 1024) * 4100
 
 
 def lp_audio_ws_bytes(mask_len):
@@ -308,6 +330,12 @@ EXPORTS = {
     "lp_mask_bbox_frames": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "lp_detail_resample_track": (C.c_int, [C.POINTER(LpDetailResampleTrackDesc), C.c_void_p]),
     "lp_detail_stitch_track": (C.c_int, [C.POINTER(LpDetailStitchTrackDesc), C.c_void_p]),
+    "lp_mask_components_frames": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                            C.c_int64, C.c_void_p]),
+    "lp_subject_boxes": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p,
+                                   C.c_void_p]),
+    "lp_detail_resample_subjects": (C.c_int, [C.POINTER(LpDetailResampleSubjectsDesc), C.c_void_p]),
+    "lp_detail_stitch_subjects": (C.c_int, [C.POINTER(LpDetailStitchSubjectsDesc), C.c_void_p]),
     "lp_color_stats": (C.c_int, [C.POINTER(LpColorStatsDesc), C.c_void_p]),
     "lp_color_fit": (C.c_int, [C.POINTER(LpColorFitDesc), C.c_void_p]),
     "lp_color_apply": (C.c_int, [C.POINTER(LpColorApplyDesc), C.c_void_p]),

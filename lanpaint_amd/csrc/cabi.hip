@@ -43,6 +43,12 @@ int detail_resample_regions_dispatch(const lp_detail_resample_regions_desc* d, h
 int detail_stitch_regions_dispatch(const lp_detail_stitch_regions_desc* d, hipStream_t stream);
 int detail_resample_track_dispatch(const lp_detail_resample_track_desc* d, hipStream_t stream);
 int detail_stitch_track_dispatch(const lp_detail_stitch_track_desc* d, hipStream_t stream);
+int mask_components_frames_dispatch(const float* mask, int F, int H, int W, int32_t* labels, int32_t* table, void* workspace,
+                                    int64_t workspace_bytes, hipStream_t stream);
+int subject_boxes_dispatch(const int32_t* labels, int frames, int H, int W, const int32_t* owner, int owner_len, int subjects,
+                           int32_t* boxes, hipStream_t stream);
+int detail_resample_subjects_dispatch(const lp_detail_resample_subjects_desc* d, hipStream_t stream);
+int detail_stitch_subjects_dispatch(const lp_detail_stitch_subjects_desc* d, hipStream_t stream);
 int color_stats_dispatch(const lp_color_stats_desc* d, hipStream_t stream);
 int color_fit_dispatch(const lp_color_fit_desc* d, hipStream_t stream);
 int color_apply_dispatch(const lp_color_apply_desc* d, hipStream_t stream);
@@ -138,6 +144,25 @@ int lp_detail_resample_track(const lp_detail_resample_track_desc* desc, void* st
 
 int lp_detail_stitch_track(const lp_detail_stitch_track_desc* desc, void* stream) {
     return lp::detail_stitch_track_dispatch(desc, as_stream(stream));
+}
+
+int lp_mask_components_frames(const float* mask, int32_t frames, int32_t height, int32_t width, int32_t* labels, int32_t* table,
+                              void* workspace, int64_t workspace_bytes, void* stream) {
+    return lp::mask_components_frames_dispatch(mask, frames, height, width, labels, table, workspace, workspace_bytes,
+                                               as_stream(stream));
+}
+
+int lp_subject_boxes(const int32_t* labels, int32_t frames, int32_t height, int32_t width, const int32_t* owner, int32_t owner_len,
+                     int32_t subjects, int32_t* boxes, void* stream) {
+    return lp::subject_boxes_dispatch(labels, frames, height, width, owner, owner_len, subjects, boxes, as_stream(stream));
+}
+
+int lp_detail_resample_subjects(const lp_detail_resample_subjects_desc* desc, void* stream) {
+    return lp::detail_resample_subjects_dispatch(desc, as_stream(stream));
+}
+
+int lp_detail_stitch_subjects(const lp_detail_stitch_subjects_desc* desc, void* stream) {
+    return lp::detail_stitch_subjects_dispatch(desc, as_stream(stream));
 }
 
 int lp_color_stats(const lp_color_stats_desc* desc, void* stream) { return lp::color_stats_dispatch(desc, as_stream(stream)); }

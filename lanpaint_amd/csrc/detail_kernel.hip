@@ -20,6 +20,12 @@
 // and for a window that follows a moving mask through a video (lp_mask_bbox_frames, lp_detail_resample_track,
 // lp_detail_stitch_track): a box per plane in one launch, then the regions crop and the single-window stitch with the origin
 // looked up by image instead of by region.  Frames never overlap each other, so the whole stitch is one launch after the copy.
+//
+// and per subject of a video (lp_subject_boxes, lp_detail_resample_subjects, lp_detail_stitch_subjects): the labels are a
+// volume (lp_mask_components_frames), a subject is a set of its components, and window (s, f) follows subject s through frame
+// f.  A box per (subject, frame) in one launch; the crops of every (subject, frame) in one launch, subject s seeing frame f's
+// mask with foreign components erased through frame f's label plane; the stitch as one copy, then one launch per subject over
+// all frames' windows, in subject order and in place.
 #include "lp_common.h"
 #include "mask_tile.h"
 #include "resample_tile.h"
@@ -106,6 +112,56 @@ __global__ __launch_bounds__(256) void lp_detail_bbox_kernel(const float* __rest
     }
 }
 
+// ---- a box per (subject, frame) ----------------------------------------------------------------------------------------------
+// lp_detail_bbox_kernel's tile with labels for floats: lane l reads column x of 16 rows of frame blockIdx.z's label plane and
+// looks each label's subject up (owner[label] = subject + 1; 0, or a label outside the table, is nobody's).  A lane keeps the
+// rows of the first subject it meets as bits and sends the rare voxel of a second subject in its column by itself; a wave
+// whose lanes carry one subject reduces to one set of four atomics, otherwise each lane sends its own.  Integer atomics only.
+__global__ __launch_bounds__(256) void lp_detail_subject_boxes_kernel(const int32_t* __restrict__ labels,
+                                                                      const int32_t* __restrict__ owner, int owner_len,
+                                                                      int subjects, int32_t* __restrict__ boxes, int H, int W) {
+    const int lane = threadIdx.x & (kWave - 1);
+    const int x = blockIdx.x * 256 + threadIdx.x, y0 = blockIdx.y * kBboxRows, f = blockIdx.z, frames = gridDim.z;
+    const int32_t* plane = labels + static_cast<int64_t>(f) * H * W;
+    int mine = 0;
+    uint32_t rowbits = 0;
+    if (x < W) {
+#pragma unroll
+        for (int r = 0; r < kBboxRows; ++r) {
+            if (y0 + r >= H) break;
+            const int label = plane[static_cast<int64_t>(y0 + r) * W + x];
+            int o = (label > 0 && label < owner_len) ? owner[label] : 0;
+            if (o < 1 || o > subjects) o = 0;
+            if (o == 0) continue;
+            if (mine == 0) mine = o;
+            if (o == mine) {
+                rowbits |= 1u << r;
+            } else {
+                int32_t* box = boxes + 4 * (static_cast<int64_t>(o - 1) * frames + f);
+                atomicMin(box + 0, y0 + r); atomicMax(box + 1, y0 + r); atomicMin(box + 2, x); atomicMax(box + 3, x);
+            }
+        }
+    }
+    const unsigned long long set = __ballot(mine != 0);
+    if (set == 0) return;                                          // wave-uniform
+    const int first = __shfl(mine, __builtin_ctzll(set), kWave);
+    const bool uniform = __ballot(mine != 0 && mine != first) == 0;
+    if (uniform) {
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) rowbits |= __shfl_xor(rowbits, off);
+        if (lane == 0) {
+            const int wx = x;                                       // lane 0's column: the wave's first
+            int32_t* box = boxes + 4 * (static_cast<int64_t>(first - 1) * frames + f);
+            atomicMin(box + 0, y0 + __builtin_ctz(rowbits)); atomicMax(box + 1, y0 + 31 - __builtin_clz(rowbits));
+            atomicMin(box + 2, wx + __builtin_ctzll(set)); atomicMax(box + 3, wx + 63 - __builtin_clzll(set));
+        }
+    } else if (mine != 0) {
+        int32_t* box = boxes + 4 * (static_cast<int64_t>(mine - 1) * frames + f);
+        atomicMin(box + 0, y0 + __builtin_ctz(rowbits)); atomicMax(box + 1, y0 + 31 - __builtin_clz(rowbits));
+        atomicMin(box + 2, x); atomicMax(box + 3, x);
+    }
+}
+
 // ---- crop + resample ----------------------------------------------------------------------------------------------------
 // torch's antialiased passes for resample_tile: fp32 NHWC source, fp32 sums from zero with the taps ascending, the horizontal
 // pass parked as one float4.  The library is built with -ffp-contract=on, so a multiply-add fuses only inside one source
@@ -147,6 +203,14 @@ struct WindowFrom {                                               // a device ta
 };
 using WindowOfRegion = WindowFrom<false>;                         // z = region * batch + image, origins[region]
 using WindowOfImage = WindowFrom<true>;                           // one window per image, origins[image]
+struct WindowOfSubject {                                          // z = subject * batch + image, origins[z]
+    const int32_t* origins;
+    __device__ __forceinline__ void locate(int z, int batch, int H, int W, int h, int w, int& r, int& b, int& y, int& x) const {
+        r = z / batch; b = z - r * batch;
+        y = min(max(origins[2 * z], 0), H - h);
+        x = min(max(origins[2 * z + 1], 0), W - w);
+    }
+};
 
 // Region `mine - 1`'s view of the mask: components that belong to another region, or to none, read as 0.  Label 0 -- every
 // value at or below 0.5 -- is nobody's and stays, so feathered edges survive.
@@ -163,6 +227,17 @@ struct EraseForeign {
 };
 __device__ __forceinline__ MaskAsIs for_region(MaskAsIs edit, int) { return edit; }
 __device__ __forceinline__ EraseForeign for_region(EraseForeign edit, int r) { edit.mine = r + 1; return edit; }
+
+// The same erasure with a label plane per image (a label volume): in image b it reads plane b.
+struct EraseForeignFrame {
+    EraseForeign erase;
+};
+__device__ __forceinline__ MaskAsIs in_image(MaskAsIs edit, int, int64_t) { return edit; }
+__device__ __forceinline__ EraseForeign in_image(EraseForeign edit, int, int64_t) { return edit; }
+__device__ __forceinline__ EraseForeign in_image(EraseForeignFrame edit, int b, int64_t plane) {
+    edit.erase.labels += b * plane;
+    return edit.erase;
+}
 
 // ---- crop + resample ----------------------------------------------------------------------------------------------------
 // `images` windows of win_h x win_w, one per grid z, out of src [batch, src_h, src_w, channels] into dst [images, out_h, out_w,
@@ -200,7 +275,8 @@ __global__ __launch_bounds__(256) void lp_detail_crop_kernel(const ResampleJob j
     win.locate(z, j.batch, j.src_h, j.src_w, j.win_h, j.win_w, r, b, y0, x0);
     const int64_t at = static_cast<int64_t>(y0 + y) * j.src_w + x0;    // of the window row's first pixel in its plane
     const float v = j.src[(static_cast<int64_t>(b) * j.src_h * j.src_w + at) * C + e];
-    j.dst[(static_cast<int64_t>(z) * j.win_h + y) * rowE + e] = for_region(edit, r)(v, at + e);
+    j.dst[(static_cast<int64_t>(z) * j.win_h + y) * rowE + e] =
+        for_region(in_image(edit, b, static_cast<int64_t>(j.src_h) * j.src_w), r)(v, at + e);
 }
 
 // ---- stitch -------------------------------------------------------------------------------------------------------------
@@ -240,7 +316,8 @@ __global__ __launch_bounds__(256) void lp_detail_stitch_kernel(const StitchJob j
     const int x0 = wx0 + blockIdx.x * TW, y0 = wy0 + blockIdx.y * TH;
     const float* mplane = j.mask + static_cast<int64_t>(j.mask_batch == 1 ? 0 : b) * H * W;
     float *D, *g;
-    mask_tile_passes<TH, TW, Edit>(lds, mplane, H, W, LP_NN_ATEN_SCALAR, k, x0, y0, H, W, D, g, edit);
+    mask_tile_passes<TH, TW>(lds, mplane, H, W, LP_NN_ATEN_SCALAR, k, x0, y0, H, W, D, g,
+                             in_image(edit, b, static_cast<int64_t>(H) * W));
     float* M = lds;                                               // the passes' A, free now: TH x TW smoothed mask
     for (int idx = tid; idx < TH * TW; idx += 256) {
         const int ty = idx / TW, tx = idx - ty * TW;
@@ -306,6 +383,25 @@ int launch_resample(const ResampleJob& j, Window win, hipStream_t stream) {
         hipLaunchKernelGGL(lp_detail_resample_kernel<Window>, grid, dim3(256), 0, stream, j, win);
     }
     return launched();
+}
+
+// A mask's windows as each window's owner sees them: erased on the way out when the size stays, otherwise erased into
+// j.scratch and each resampled whole from there.
+template <class Window, class Edit>
+int launch_resample_erased(const ResampleJob& j, Window win, Edit erase, hipStream_t stream) {
+    if (j.same()) {
+        launch_crop(j, win, erase, stream);
+        return launched();
+    }
+    ResampleJob crop = j, rest = j;
+    crop.dst = j.scratch;
+    launch_crop(crop, win, erase, stream);
+    if (hipGetLastError() != hipSuccess) return LP_E_LAUNCH;
+    rest.batch = static_cast<int>(j.images);
+    rest.src_h = j.win_h;
+    rest.src_w = j.win_w;
+    rest.src = j.scratch;
+    return launch_resample(rest, WindowAt{0, 0}, stream);
 }
 
 // One streaming copy original -> out on `stream`, the first launch of every stitch.
@@ -388,20 +484,7 @@ int detail_resample_regions_dispatch(const lp_detail_resample_regions_desc* dp, 
     if (const int err = check_resample(j)) return err;
     const WindowOfRegion win = {d.origins};
     if (!d.labels) return launch_resample(j, win, stream);
-    const EraseForeign erase = {d.labels, d.owner, d.owner_len, 0};
-    if (!erased_resample) {
-        launch_crop(j, win, erase, stream);
-        return launched();
-    }
-    ResampleJob crop = j, rest = j;                               // the windows erased, then each resampled whole
-    crop.dst = d.scratch;
-    launch_crop(crop, win, erase, stream);
-    if (hipGetLastError() != hipSuccess) return LP_E_LAUNCH;
-    rest.batch = static_cast<int>(j.images);
-    rest.src_h = d.win_h;
-    rest.src_w = d.win_w;
-    rest.src = d.scratch;
-    return launch_resample(rest, WindowAt{0, 0}, stream);
+    return launch_resample_erased(j, win, EraseForeign{d.labels, d.owner, d.owner_len, 0}, stream);
 }
 
 int detail_stitch_regions_dispatch(const lp_detail_stitch_regions_desc* dp, hipStream_t stream) {
@@ -421,6 +504,54 @@ int detail_stitch_regions_dispatch(const lp_detail_stitch_regions_desc* dp, hipS
         const WindowAt at = {d.origins[2 * r], d.origins[2 * r + 1]};
         const int err = d.labels ? launch_stitch(j, at, EraseForeign{d.labels, d.owner, d.owner_len, r + 1}, stream)
                                  : launch_stitch(j, at, MaskAsIs(), stream);
+        if (err) return err;
+    }
+    return LP_OK;
+}
+
+int subject_boxes_dispatch(const int32_t* labels, int frames, int H, int W, const int32_t* owner, int owner_len, int subjects,
+                           int32_t* boxes, hipStream_t stream) {
+    if (!labels || !owner || !boxes || frames <= 0 || !side_ok(H) || !side_ok(W) || owner_len < 1) return LP_E_INVALID;
+    if (subjects < 1 || subjects > LP_DETAIL_MAX_REGIONS) return LP_E_INVALID;
+    if (frames > 65535) return LP_E_UNSUPPORTED;
+    const int n = subjects * frames;
+    hipLaunchKernelGGL(lp_detail_bbox_init_kernel, dim3((4 * n + 255) / 256), dim3(256), 0, stream, boxes, H, W, n);
+    if (hipGetLastError() != hipSuccess) return LP_E_LAUNCH;
+    const dim3 grid((W + 255) / 256, (H + kBboxRows - 1) / kBboxRows, frames);
+    hipLaunchKernelGGL(lp_detail_subject_boxes_kernel, grid, dim3(256), 0, stream, labels, owner, owner_len, subjects, boxes, H, W);
+    return launched();
+}
+
+int detail_resample_subjects_dispatch(const lp_detail_resample_subjects_desc* dp, hipStream_t stream) {
+    if (!dp) return LP_E_INVALID;
+    const lp_detail_resample_subjects_desc& d = *dp;
+    if (d.subjects < 1 || d.subjects > LP_DETAIL_MAX_REGIONS || !d.origins) return LP_E_INVALID;
+    ResampleJob j = {d.batch, d.src_h, d.src_w, d.channels, d.win_h, d.win_w, d.out_h, d.out_w, d.ksize_x, d.ksize_y,
+                     static_cast<int64_t>(d.subjects) * d.batch, d.src, d.bounds_x, d.weights_x, d.bounds_y, d.weights_y, d.dst,
+                     nullptr};
+    const bool erased_resample = d.labels && !j.same();
+    if (d.labels && (d.channels != 1 || !d.owner || d.owner_len < 1 || (erased_resample && !d.scratch))) return LP_E_INVALID;
+    if (erased_resample) j.scratch = d.scratch;
+    if (const int err = check_resample(j)) return err;
+    const WindowOfSubject win = {d.origins};
+    if (!d.labels) return launch_resample(j, win, stream);
+    return launch_resample_erased(j, win, EraseForeignFrame{{d.labels, d.owner, d.owner_len, 0}}, stream);
+}
+
+int detail_stitch_subjects_dispatch(const lp_detail_stitch_subjects_desc* dp, hipStream_t stream) {
+    if (!dp) return LP_E_INVALID;
+    const lp_detail_stitch_subjects_desc& d = *dp;
+    if (d.subjects < 1 || d.subjects > LP_DETAIL_MAX_REGIONS || !d.origins) return LP_E_INVALID;
+    if (d.labels && (!d.owner || d.owner_len < 1)) return LP_E_INVALID;
+    StitchJob j = {d.batch, d.height, d.width, d.channels, d.win_h, d.win_w, d.k, d.batch, d.mask, d.original, d.detail, d.out};
+    if (const int err = check_stitch(j)) return err;
+    if (launch_frame_copy(j, stream) != hipSuccess) return LP_E_LAUNCH;
+    const int64_t per_subject = static_cast<int64_t>(d.batch) * d.win_h * d.win_w * d.channels;
+    j.original = d.out;                                           // in order, in place: out_{s+1} from out_s
+    for (int s = 0; s < d.subjects; ++s, j.detail += per_subject) {
+        const WindowOfImage win = {d.origins + 2 * static_cast<int64_t>(s) * d.batch};      // subject s's row of the table
+        const int err = d.labels ? launch_stitch(j, win, EraseForeignFrame{{d.labels, d.owner, d.owner_len, s + 1}}, stream)
+                                 : launch_stitch(j, win, MaskAsIs(), stream);
         if (err) return err;
     }
     return LP_OK;

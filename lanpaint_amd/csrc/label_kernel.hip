@@ -19,6 +19,26 @@
 //   7 relabel    labels[i] from P (read-only here), boxes and areas by integer atomicMin / atomicMax / atomicAdd
 //
 // The prefix sum is reduce (4) / scan of sums (5) / apply (6) in separate launches: no look-back, no block waits for another.
+//
+// In space and time (lp_mask_components_frames): S = { (f, y, x) : mask[f, y, x] > 0.5 }, no union over planes, 26-connected
+// components, label = 1 + rank of the smallest flat index (f * H + y) * W + x  (scipy.ndimage.label(S, ones((3, 3, 3)))), plus
+// per component (f0, f1, r0, r1, c0, c1, volume).  P is [F * H * W]; the same launches on the volume and one more:
+//
+//   1 union      one voxel per element (planes = 1, n = F * H * W)
+//   2 tile       per frame, the frame on blockIdx.z; a frame's flat indices are a contiguous range, so tile-local order still
+//                ascends with the flat index
+//   3 border     per frame
+//   3t temporal  a set voxel of frame f >= 1 unites with frame f - 1: with (f - 1, y, x) when that is set -- every other set
+//                voxel of the 3 x 3 neighbourhood there is 8-adjacent to it and so already in its component after 2 and 3 --
+//                otherwise with each set voxel among the other eight, which need not be adjacent to each other.  16 B per
+//                lane where W % 4 == 0
+//   4 .. 7       over n = F * H * W; 7 derives (f, y, x) from the flat index and sends seven integer atomics
+//
+// The temporal launch needs no value another block of it must write first, by the argument of launch 3: whether a voxel is set
+// (P >= 0) was settled by launch 1 and no union changes it, so which unions a thread makes does not depend on the others;
+// `unite` reads parents that others are lowering, every value read is a valid ancestor of the same component (parents only
+// decrease, by atomicMin onto a root), and each union ends with both voxels under one root whatever happened meanwhile.  When
+// the launch has finished every 26-adjacent pair has been united once, so a component's root is its smallest flat index.
 #include "lp_common.h"
 
 namespace lp {
@@ -84,14 +104,16 @@ __global__ __launch_bounds__(256) void lp_label_union_kernel(const float* __rest
 
 // ---- 2: unions inside a tile, in LDS -----------------------------------------------------------------------------------------
 // Local index q = ty * 64 + tx ascends with the flat index y * W + x inside a tile, so the tile-local root (smallest q) is the
-// tile-local smallest flat index.  A pixel unites with its W, NW, N and NE neighbours: every 8-adjacent pair once.
+// tile-local smallest flat index.  A pixel unites with its W, NW, N and NE neighbours: every 8-adjacent pair once.  blockIdx.z
+// is the frame of a volume.
 __global__ __launch_bounds__(256) void lp_label_tile_kernel(int32_t* __restrict__ P, int H, int W) {
     __shared__ int L[kTileH * kTileW];
     const int x0 = blockIdx.x * kTileW, y0 = blockIdx.y * kTileH, tid = threadIdx.x;
+    const int base = blockIdx.z * H * W;                          // of the frame; 0 for the single plane
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
         const int q = tid + 256 * j, ty = q >> 6, tx = q & 63, y = y0 + ty, x = x0 + tx;
-        L[q] = (y < H && x < W && P[y * W + x] >= 0) ? q : -1;
+        L[q] = (y < H && x < W && P[base + y * W + x] >= 0) ? q : -1;
     }
     __syncthreads();
 #pragma unroll
@@ -111,7 +133,7 @@ __global__ __launch_bounds__(256) void lp_label_tile_kernel(int32_t* __restrict_
         const int q = tid + 256 * j, ty = q >> 6, tx = q & 63;
         if (L[q] < 0) continue;
         const int r = find(L, q);
-        P[(y0 + ty) * W + x0 + tx] = (y0 + (r >> 6)) * W + x0 + (r & 63);
+        P[base + (y0 + ty) * W + x0 + tx] = base + (y0 + (r >> 6)) * W + x0 + (r & 63);
     }
 }
 
@@ -124,13 +146,51 @@ __global__ __launch_bounds__(256) void lp_label_border_kernel(int32_t* __restric
     const int tx = x & (kTileW - 1), ty = y & (kTileH - 1);
     const bool top = ty == 0 && y > 0, left = tx == 0 && x > 0, right = tx == kTileW - 1 && x + 1 < W && y > 0;
     if (!(top || left || right)) return;
-    const int i = y * W + x;
+    const int i = blockIdx.z * H * W + y * W + x;                 // blockIdx.z: the frame of a volume
     if (P[i] < 0) return;
     if (left && P[i - 1] >= 0) unite(P, i, i - 1);
     if (y > 0) {
         if ((top || left) && x > 0 && P[i - W - 1] >= 0) unite(P, i, i - W - 1);
         if (top && P[i - W] >= 0) unite(P, i, i - W);
         if ((top || right) && x + 1 < W && P[i - W + 1] >= 0) unite(P, i, i - W + 1);
+    }
+}
+
+// ---- 3t: unions between a frame and the one before it --------------------------------------------------------------------
+// Thread t owns voxels V * t .. V * t + V - 1 of frames 1 .. F - 1 (V = 4: W % 4 == 0, so the four share a row and both 16 B
+// loads, the voxels' parents and those straight below, are aligned; the file's header has the rule and why the launch needs
+// no order).  Only whether a loaded parent is >= 0 is used, and no union changes that.
+template <int V>
+__global__ __launch_bounds__(256) void lp_label_temporal_kernel(int32_t* __restrict__ P, int H, int W, int n) {
+    const int plane = H * W, i0 = plane + (blockIdx.x * 256 + threadIdx.x) * V;
+    if (i0 >= n) return;
+    int own[V], under[V];
+    if constexpr (V == 4) {
+        const int4 a = *reinterpret_cast<const int4*>(P + i0), b = *reinterpret_cast<const int4*>(P + i0 - plane);
+        own[0] = a.x; own[1] = a.y; own[2] = a.z; own[3] = a.w;
+        under[0] = b.x; under[1] = b.y; under[2] = b.z; under[3] = b.w;
+    } else {
+        own[0] = P[i0];
+        under[0] = P[i0 - plane];
+    }
+#pragma unroll
+    for (int e = 0; e < V; ++e) {
+        if (own[e] < 0) continue;
+        const int i = i0 + e, below = i - plane;
+        if (under[e] >= 0) {
+            unite(P, i, below);
+            continue;
+        }
+        const int yx = i % plane, y = yx / W, x = yx - y * W;
+#pragma unroll
+        for (int dy = -1; dy <= 1; ++dy) {
+#pragma unroll
+            for (int dx = -1; dx <= 1; ++dx) {
+                if ((dy == 0 && dx == 0) || y + dy < 0 || y + dy >= H || x + dx < 0 || x + dx >= W) continue;
+                const int j = below + dy * W + dx;
+                if (P[j] >= 0) unite(P, i, j);
+            }
+        }
     }
 }
 
@@ -177,8 +237,10 @@ __device__ __forceinline__ int block_exclusive_scan(int v, int* part, int& total
 }
 
 // ---- 5: scan of the chunk counts (one block), table header and reset ---------------------------------------------------------
+// VOLUME: rows of seven, {F, -1, H, -1, W, -1, 0}.
+template <bool VOLUME>
 __global__ __launch_bounds__(256) void lp_label_scan_kernel(int32_t* __restrict__ sums, int chunks, int32_t* __restrict__ table,
-                                                            int H, int W) {
+                                                            int F, int H, int W) {
     __shared__ int part[4];
     int carry = 0;
     for (int c0 = 0; c0 < chunks; c0 += 256) {
@@ -191,7 +253,8 @@ __global__ __launch_bounds__(256) void lp_label_scan_kernel(int32_t* __restrict_
     }
     if (threadIdx.x == 0) table[0] = carry;
     for (int id = threadIdx.x; id < LP_DETAIL_MAX_COMPONENTS; id += 256) {
-        int32_t* row = table + 1 + 5 * id;
+        int32_t* row = table + 1 + (VOLUME ? 7 : 5) * id;
+        if constexpr (VOLUME) { row[0] = F; row[1] = -1; row += 2; }
         row[0] = H; row[1] = -1; row[2] = W; row[3] = -1; row[4] = 0;
     }
 }
@@ -223,9 +286,12 @@ __global__ __launch_bounds__(256) void lp_label_rank_kernel(int32_t* __restrict_
 // ---- 7: relabel, boxes and areas ---------------------------------------------------------------------------------------------
 // A wave holds 64 consecutive flat indices.  When all its set lanes carry one label (the usual case inside a blob) the wave
 // reduces its box and count by shuffles and one lane sends the five atomics; otherwise each lane sends its own.  Integer
-// atomics: the table does not depend on the order of arrival.  Labels past the cap leave the table alone.
+// atomics: the table does not depend on the order of arrival.  Labels past the cap leave the table alone.  VOLUME: (f, y, x)
+// from the flat index and seven atomics, the frame bounds first.
+template <bool VOLUME>
 __global__ __launch_bounds__(256) void lp_label_relabel_kernel(const int32_t* __restrict__ P, int32_t* __restrict__ labels,
-                                                               int32_t* __restrict__ table, int n, int W) {
+                                                               int32_t* __restrict__ table, int n, int H, int W) {
+    constexpr int kRow = VOLUME ? 7 : 5;
     const int lane = threadIdx.x & (kWave - 1);
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
@@ -241,21 +307,26 @@ __global__ __launch_bounds__(256) void lp_label_relabel_kernel(const int32_t* __
         if (set == 0) continue;                                     // wave-uniform
         const int first = __shfl(label, __builtin_ctzll(set), kWave);
         const bool uniform = __ballot(label != 0 && label != first) == 0;
-        const int y = i / W, x = i - y * W;
+        const int row_of = i / W, x = i - row_of * W;               // row_of = f * H + y
+        const int f = VOLUME ? row_of / H : 0, y = row_of - f * H;
         if (uniform) {
+            int f0 = label ? f : INT32_MAX, f1 = label ? f : -1;
             int r0 = label ? y : INT32_MAX, r1 = label ? y : -1, c0 = label ? x : INT32_MAX, c1 = label ? x : -1;
 #pragma unroll
             for (int off = 32; off > 0; off >>= 1) {
+                if constexpr (VOLUME) { f0 = min(f0, __shfl_xor(f0, off, kWave)); f1 = max(f1, __shfl_xor(f1, off, kWave)); }
                 r0 = min(r0, __shfl_xor(r0, off, kWave)); r1 = max(r1, __shfl_xor(r1, off, kWave));
                 c0 = min(c0, __shfl_xor(c0, off, kWave)); c1 = max(c1, __shfl_xor(c1, off, kWave));
             }
             if (lane == 0 && first <= LP_DETAIL_MAX_COMPONENTS) {
-                int32_t* row = table + 1 + 5 * (first - 1);
+                int32_t* row = table + 1 + kRow * (first - 1);
+                if constexpr (VOLUME) { atomicMin(row + 0, f0); atomicMax(row + 1, f1); row += 2; }
                 atomicMin(row + 0, r0); atomicMax(row + 1, r1); atomicMin(row + 2, c0); atomicMax(row + 3, c1);
                 atomicAdd(row + 4, __popcll(set));
             }
         } else if (label != 0 && label <= LP_DETAIL_MAX_COMPONENTS) {
-            int32_t* row = table + 1 + 5 * (label - 1);
+            int32_t* row = table + 1 + kRow * (label - 1);
+            if constexpr (VOLUME) { atomicMin(row + 0, f); atomicMax(row + 1, f); row += 2; }
             atomicMin(row + 0, y); atomicMax(row + 1, y); atomicMin(row + 2, x); atomicMax(row + 3, x);
             atomicAdd(row + 4, 1);
         }
@@ -263,6 +334,36 @@ __global__ __launch_bounds__(256) void lp_label_relabel_kernel(const int32_t* __
 }
 
 bool side_ok(int s) { return s > 0 && s <= LP_DETAIL_MAX_SIDE; }
+
+// The launches after the threshold, shared by the plane and the volume: F frames of H x W in P, n = F * H * W.
+template <bool VOLUME>
+int launch_label(int F, int H, int W, int32_t* P, int32_t* sums, int32_t* labels, int32_t* table, hipStream_t stream) {
+    const int n = F * H * W, chunks = (n + kChunk - 1) / kChunk;
+    hipLaunchKernelGGL(lp_label_tile_kernel, dim3((W + kTileW - 1) / kTileW, (H + kTileH - 1) / kTileH, F), dim3(256), 0, stream,
+                       P, H, W);
+    hipLaunchKernelGGL(lp_label_border_kernel, dim3((W + 255) / 256, H, F), dim3(256), 0, stream, P, H, W);
+    if (VOLUME && F > 1) {
+        const int rest = n - H * W;                                // P is 16 B aligned (the workspace is)
+        if ((W & 3) == 0)
+            hipLaunchKernelGGL(lp_label_temporal_kernel<4>, dim3((rest / 4 + 255) / 256), dim3(256), 0, stream, P, H, W, n);
+        else
+            hipLaunchKernelGGL(lp_label_temporal_kernel<1>, dim3((rest + 255) / 256), dim3(256), 0, stream, P, H, W, n);
+    }
+    hipLaunchKernelGGL(lp_label_flatten_kernel, dim3(chunks), dim3(256), 0, stream, P, sums, n);
+    hipLaunchKernelGGL(lp_label_scan_kernel<VOLUME>, dim3(1), dim3(256), 0, stream, sums, chunks, table, F, H, W);
+    hipLaunchKernelGGL(lp_label_rank_kernel, dim3(chunks), dim3(256), 0, stream, P, sums, n);
+    hipLaunchKernelGGL(lp_label_relabel_kernel<VOLUME>, dim3(chunks), dim3(256), 0, stream, P, labels, table, n, H, W);
+    return hipGetLastError() == hipSuccess ? LP_OK : LP_E_LAUNCH;
+}
+
+// Launch 1 over `planes` planes of n elements each.
+bool launch_union(const float* mask, int32_t* P, int planes, int n, hipStream_t stream) {
+    if ((n & 3) == 0 && aligned16(mask))
+        hipLaunchKernelGGL(lp_label_union_kernel<4>, dim3((n / 4 + 255) / 256), dim3(256), 0, stream, mask, P, planes, n);
+    else
+        hipLaunchKernelGGL(lp_label_union_kernel<1>, dim3((n + 255) / 256), dim3(256), 0, stream, mask, P, planes, n);
+    return hipGetLastError() == hipSuccess;
+}
 
 }  // namespace
 
@@ -276,19 +377,22 @@ int mask_components_dispatch(const float* mask, int planes, int H, int W, int32_
     const int chunks = (n + kChunk - 1) / kChunk;
     int32_t* P = static_cast<int32_t*>(workspace);                  // chunks * 1024 elements, then the chunk counts
     int32_t* sums = P + static_cast<int64_t>(chunks) * kChunk;
-    if ((n & 3) == 0 && aligned16(mask))
-        hipLaunchKernelGGL(lp_label_union_kernel<4>, dim3((n / 4 + 255) / 256), dim3(256), 0, stream, mask, P, planes, n);
-    else
-        hipLaunchKernelGGL(lp_label_union_kernel<1>, dim3((n + 255) / 256), dim3(256), 0, stream, mask, P, planes, n);
-    if (hipGetLastError() != hipSuccess) return LP_E_LAUNCH;
-    hipLaunchKernelGGL(lp_label_tile_kernel, dim3((W + kTileW - 1) / kTileW, (H + kTileH - 1) / kTileH), dim3(256), 0, stream,
-                       P, H, W);
-    hipLaunchKernelGGL(lp_label_border_kernel, dim3((W + 255) / 256, H), dim3(256), 0, stream, P, H, W);
-    hipLaunchKernelGGL(lp_label_flatten_kernel, dim3(chunks), dim3(256), 0, stream, P, sums, n);
-    hipLaunchKernelGGL(lp_label_scan_kernel, dim3(1), dim3(256), 0, stream, sums, chunks, table, H, W);
-    hipLaunchKernelGGL(lp_label_rank_kernel, dim3(chunks), dim3(256), 0, stream, P, sums, n);
-    hipLaunchKernelGGL(lp_label_relabel_kernel, dim3(chunks), dim3(256), 0, stream, P, labels, table, n, W);
-    return hipGetLastError() == hipSuccess ? LP_OK : LP_E_LAUNCH;
+    if (!launch_union(mask, P, planes, n, stream)) return LP_E_LAUNCH;
+    return launch_label<false>(1, H, W, P, sums, labels, table, stream);
+}
+
+int mask_components_frames_dispatch(const float* mask, int F, int H, int W, int32_t* labels, int32_t* table, void* workspace,
+                                    int64_t workspace_bytes, hipStream_t stream) {
+    if (!mask || !labels || !table || !workspace || F <= 0 || !side_ok(H) || !side_ok(W)) return LP_E_INVALID;
+    if (workspace_bytes < LP_COMPONENTS_FRAMES_WS_BYTES(F, H, W)) return LP_E_INVALID;
+    if (!aligned16(workspace)) return LP_E_ALIGN;
+    if (F > 65535 || static_cast<int64_t>(F) * H * W > (1ll << 30)) return LP_E_UNSUPPORTED;   // the grid's z; int32 parents
+    const int n = F * H * W;
+    const int chunks = (n + kChunk - 1) / kChunk;
+    int32_t* P = static_cast<int32_t*>(workspace);
+    int32_t* sums = P + static_cast<int64_t>(chunks) * kChunk;
+    if (!launch_union(mask, P, 1, n, stream)) return LP_E_LAUNCH;   // one voxel per element: no union over planes
+    return launch_label<true>(F, H, W, P, sums, labels, table, stream);
 }
 
 }  // namespace lp

@@ -549,8 +549,17 @@ def stitch_regions(original, detail_imgs, mask, regions, labels=None, blend_over
 
 
 # ---- per frame: a window that follows a moving mask --------------------------------------------------------------------------------
-def _track_axis(spans, n_img, c1000, padding, m, k):
-    """One axis of the track rule: spans[f] = (a0, a1) inclusive, or None for an empty frame -> (origins, n)."""
+def _track_size(side, n_img, c1000, padding, m):
+    """The track rule's first `size` step on one axis: the window size for boxes whose largest side is `side`."""
+    g = padding + _ceil_div((c1000 - 1000) * side, 2000)
+    n = min(side + 2 * g, n_img)
+    need = _ceil_div(n, m) * m
+    return need if need <= n_img else n
+
+
+def _track_axis(spans, n_img, c1000, padding, m, k, n=None):
+    """One axis of the track rule: spans[f] = (a0, a1) inclusive, or None for an empty frame -> (origins, n).  `n`: the window
+    size when the caller has fixed it (at least the largest side), otherwise the rule's own from these spans."""
     frames = len(spans)
     full = [f for f, span in enumerate(spans) if span is not None]
     s = [None if span is None else span[0] + span[1] + 1 for span in spans]
@@ -563,12 +572,8 @@ def _track_axis(spans, n_img, c1000, padding, m, k):
                 s[f] = s[p] + ((s[q] - s[p]) * (f - p)) // (q - p)
             else:
                 s[f] = s[before[-1] if before else after[0]]
-    side = max(spans[f][1] - spans[f][0] + 1 for f in full)               # size
-    g = padding + _ceil_div((c1000 - 1000) * side, 2000)
-    n = min(side + 2 * g, n_img)
-    need = _ceil_div(n, m) * m
-    if need <= n_img:
-        n = need
+    if n is None:                                                         # size
+        n = _track_size(max(spans[f][1] - spans[f][0] + 1 for f in full), n_img, c1000, padding, m)
     origins = []
     for f in range(frames):
         total = sum(s[min(max(f + j, 0), frames - 1)] for j in range(-(k // 2), k // 2 + 1))     # smooth
