@@ -75,11 +75,10 @@ def test_plan_rejects_an_empty_mask_and_bad_arguments():
 
 # ---- tap tables ----------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("filter", detail.FILTERS)
-@pytest.mark.parametrize("in_hw,out_hw", SHAPES)
+@pytest.mark.parametrize("in_hw,out_hw", SHAPES + detail_ref.ALL_PAIRS)
 def test_aa_coeffs_are_torchs_antialias_rule(in_hw, out_hw, filter):
     x = torch.rand(1, in_hw[0], in_hw[1], 1, dtype=torch.float64, generator=torch.Generator().manual_seed(in_hw[0] + out_hw[1]))
-    want = torch.nn.functional.interpolate(x.movedim(-1, 1), size=out_hw, mode=filter, align_corners=False,
-                                           antialias=True)[0, 0].numpy()
+    want = detail_ref.torch_aa(x.movedim(-1, 1), out_hw, filter)[0, 0].numpy()       # F.interpolate; see there for a width of 1
     got = detail_ref.apply_tables64(x[0, :, :, 0].numpy(), out_hw, filter)
     err = float(np.abs(got - want).max())
     print(f"{in_hw}->{out_hw} {filter}: max |tables - F.interpolate| = {err:.3g}")
@@ -95,7 +94,7 @@ def test_aa_coeffs_are_torchs_antialias_rule(in_hw, out_hw, filter):
 
 
 @pytest.mark.parametrize("filter", detail.FILTERS)
-@pytest.mark.parametrize("in_hw,out_hw", SHAPES[:4])
+@pytest.mark.parametrize("in_hw,out_hw", SHAPES[:4] + detail_ref.ALL_PAIRS)
 def test_fp32_restatement_of_the_kernel_is_inside_the_derived_bound(in_hw, out_hw, filter):
     """The GPU test holds lp_detail_resample to detail_ref.bound; here numpy fp32 sums stand in for the kernel."""
     x = torch.rand(in_hw, dtype=torch.float32, generator=torch.Generator().manual_seed(7))
@@ -104,6 +103,24 @@ def test_fp32_restatement_of_the_kernel_is_inside_the_derived_bound(in_hw, out_h
     b = detail_ref.bound(in_hw, out_hw, filter, float(x.abs().max()))
     print(f"{in_hw}->{out_hw} {filter}: e = {err:.3g}, b = {b:.3g}")
     assert err <= b
+
+
+@pytest.mark.parametrize("filter", detail.FILTERS)
+@pytest.mark.parametrize("in_hw,out_hw", detail_ref.ALL_PAIRS)
+def test_fp32_restatement_equals_the_impulse_reference_exactly(in_hw, out_hw, filter):
+    """tests/test_gpu_detail_shapes.py holds lp_detail_resample to detail_ref.impulse_ref as values, exactly; here the numpy
+    restatement of the kernel, which sums every tap in order, is held to it at the same sites."""
+    sites = detail_ref.impulse_sites(in_hw, out_hw, filter)
+    assert len(sites) >= 1 and all(0 <= sy < in_hw[0] and 0 <= sx < in_hw[1] for sy, sx in sites)
+    if (in_hw, out_hw) == ((2000, 40), (50, 40)):
+        assert len(sites) == 9                  # the first and the last of its four tiles span more than one chunk
+    for sy, sx in sites:
+        x = np.zeros(in_hw, np.float32)
+        x[sy, sx] = detail_ref.IMPULSE
+        want = detail_ref.impulse_ref(in_hw, out_hw, filter, (sy, sx))
+        got = detail_ref.apply_tables32(x, out_hw, filter)
+        assert got.dtype == np.float32 and want.shape == tuple(out_hw) and np.array_equal(got, want), (sy, sx)
+        assert np.count_nonzero(want) > 0       # every source element reaches some output
 
 
 def test_aa_coeffs_rejects_bad_arguments():
