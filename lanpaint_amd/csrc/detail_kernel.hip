@@ -26,6 +26,11 @@
 // f.  A box per (subject, frame) in one launch; the crops of every (subject, frame) in one launch, subject s seeing frame f's
 // mask with foreign components erased through frame f's label plane; the stitch as one copy, then one launch per subject over
 // all frames' windows, in subject order and in place.
+//
+// All four forms run the same three kernels (resample, same-size crop, stitch), templates over where block z's window is --
+// WindowAt, or WindowFrom<OriginOf>: a device table indexed by region, by image or by z itself, clamped in one place -- and
+// over how a mask element is read: MaskAsIs, or EraseForeign<PER_IMAGE> through one label plane or one per image, either
+// asked for window (r, b)'s view.  The regions and subjects entries share their crop dispatcher and their stitch loop.
 #include "lp_common.h"
 #include "mask_tile.h"
 #include "resample_tile.h"
@@ -191,29 +196,26 @@ struct WindowAt {                                                 // the descrip
         r = 0; b = z; y = y0; x = x0;
     }
 };
-template <bool BY_IMAGE>
-struct WindowFrom {                                               // a device table [n, 2] of origins
+enum class OriginOf { Region, Image, Window };                    // which row of a device table [n, 2] of origins is block z's
+template <OriginOf BY>
+struct WindowFrom {
     const int32_t* origins;
     __device__ __forceinline__ void locate(int z, int batch, int H, int W, int h, int w, int& r, int& b, int& y, int& x) const {
-        if constexpr (BY_IMAGE) { r = 0; b = z; } else { r = z / batch; b = z - r * batch; }
-        const int i = BY_IMAGE ? b : r;
+        if constexpr (BY == OriginOf::Image) { r = 0; b = z; } else { r = z / batch; b = z - r * batch; }
+        const int i = BY == OriginOf::Region ? r : BY == OriginOf::Image ? b : z;
         y = min(max(origins[2 * i], 0), H - h);                   // clamped: a bad table reads nothing outside the image
         x = min(max(origins[2 * i + 1], 0), W - w);
     }
 };
-using WindowOfRegion = WindowFrom<false>;                         // z = region * batch + image, origins[region]
-using WindowOfImage = WindowFrom<true>;                           // one window per image, origins[image]
-struct WindowOfSubject {                                          // z = subject * batch + image, origins[z]
-    const int32_t* origins;
-    __device__ __forceinline__ void locate(int z, int batch, int H, int W, int h, int w, int& r, int& b, int& y, int& x) const {
-        r = z / batch; b = z - r * batch;
-        y = min(max(origins[2 * z], 0), H - h);
-        x = min(max(origins[2 * z + 1], 0), W - w);
-    }
-};
+using WindowOfRegion = WindowFrom<OriginOf::Region>;              // z = region * batch + image, origins[region]
+using WindowOfImage = WindowFrom<OriginOf::Image>;                // one window per image, origins[image]
+using WindowOfSubject = WindowFrom<OriginOf::Window>;             // z = subject * batch + image, origins[z]
 
-// Region `mine - 1`'s view of the mask: components that belong to another region, or to none, read as 0.  Label 0 -- every
-// value at or below 0.5 -- is nobody's and stays, so feathered edges survive.
+// A region's view of the mask: components that belong to another region, or to none, read as 0.  Label 0 -- every value at or
+// below 0.5 -- is nobody's and stays, so feathered edges survive.  `mine` is the owner id (region + 1) of the launch's region 0;
+// view(r, b, plane) is window (r, b)'s edit: region r of the launch, and with PER_IMAGE -- the labels a volume, one plane of
+// `plane` elements per image -- through image b's plane.  MaskAsIs::view (mask_tile.h) is the mask itself for every window.
+template <bool PER_IMAGE>
 struct EraseForeign {
     const int32_t* labels;
     const int32_t* owner;
@@ -224,20 +226,13 @@ struct EraseForeign {
         const int o = (label > 0 && label < owner_len) ? owner[label] : 0;
         return o == mine ? v : 0.0f;
     }
+    __device__ __forceinline__ EraseForeign view(int r, int b, int64_t plane) const {
+        EraseForeign e = *this;
+        e.mine += r;
+        if constexpr (PER_IMAGE) e.labels += b * plane;
+        return e;
+    }
 };
-__device__ __forceinline__ MaskAsIs for_region(MaskAsIs edit, int) { return edit; }
-__device__ __forceinline__ EraseForeign for_region(EraseForeign edit, int r) { edit.mine = r + 1; return edit; }
-
-// The same erasure with a label plane per image (a label volume): in image b it reads plane b.
-struct EraseForeignFrame {
-    EraseForeign erase;
-};
-__device__ __forceinline__ MaskAsIs in_image(MaskAsIs edit, int, int64_t) { return edit; }
-__device__ __forceinline__ EraseForeign in_image(EraseForeign edit, int, int64_t) { return edit; }
-__device__ __forceinline__ EraseForeign in_image(EraseForeignFrame edit, int b, int64_t plane) {
-    edit.erase.labels += b * plane;
-    return edit.erase;
-}
 
 // ---- crop + resample ----------------------------------------------------------------------------------------------------
 // `images` windows of win_h x win_w, one per grid z, out of src [batch, src_h, src_w, channels] into dst [images, out_h, out_w,
@@ -265,7 +260,7 @@ __global__ __launch_bounds__(256) void lp_detail_resample_kernel(const ResampleJ
                            j.ksize_x, j.bounds_y, j.weights_y, j.ksize_y, j.dst + static_cast<int64_t>(z) * j.out_h * rowE);
 }
 
-// Same size in and out: the windows' rows copied as flat streams, one element per lane.  EraseForeign (C == 1): region r's view.
+// Same size in and out: the windows' rows copied as flat streams, one element per lane.  EraseForeign (C == 1): window z's view.
 template <class Window, class Edit>
 __global__ __launch_bounds__(256) void lp_detail_crop_kernel(const ResampleJob j, const Window win, const Edit edit) {
     const int C = j.channels, rowE = j.win_w * C;
@@ -275,8 +270,7 @@ __global__ __launch_bounds__(256) void lp_detail_crop_kernel(const ResampleJob j
     win.locate(z, j.batch, j.src_h, j.src_w, j.win_h, j.win_w, r, b, y0, x0);
     const int64_t at = static_cast<int64_t>(y0 + y) * j.src_w + x0;    // of the window row's first pixel in its plane
     const float v = j.src[(static_cast<int64_t>(b) * j.src_h * j.src_w + at) * C + e];
-    j.dst[(static_cast<int64_t>(z) * j.win_h + y) * rowE + e] =
-        for_region(in_image(edit, b, static_cast<int64_t>(j.src_h) * j.src_w), r)(v, at + e);
+    j.dst[(static_cast<int64_t>(z) * j.win_h + y) * rowE + e] = edit.view(r, b, static_cast<int64_t>(j.src_h) * j.src_w)(v, at + e);
 }
 
 // ---- stitch -------------------------------------------------------------------------------------------------------------
@@ -317,7 +311,7 @@ __global__ __launch_bounds__(256) void lp_detail_stitch_kernel(const StitchJob j
     const float* mplane = j.mask + static_cast<int64_t>(j.mask_batch == 1 ? 0 : b) * H * W;
     float *D, *g;
     mask_tile_passes<TH, TW>(lds, mplane, H, W, LP_NN_ATEN_SCALAR, k, x0, y0, H, W, D, g,
-                             in_image(edit, b, static_cast<int64_t>(H) * W));
+                             edit.view(r, b, static_cast<int64_t>(H) * W));
     float* M = lds;                                               // the passes' A, free now: TH x TW smoothed mask
     for (int idx = tid; idx < TH * TW; idx += 256) {
         const int ty = idx / TW, tx = idx - ty * TW;
@@ -335,7 +329,7 @@ __global__ __launch_bounds__(256) void lp_detail_stitch_kernel(const StitchJob j
     }
 }
 
-// ---- checks and launches, shared by the single, regions and track entries --------------------------------------------------
+// ---- checks and launches, shared by the single, regions, track and subjects entries ----------------------------------------
 bool side_ok(int s) { return s > 0 && s <= LP_DETAIL_MAX_SIDE; }
 bool chan_ok(int c) { return c > 0 && c <= LP_DETAIL_MAX_CHANNELS; }
 bool window_ok(int y0, int x0, int h, int w, int H, int W) {
@@ -434,6 +428,42 @@ int launch_stitch(const StitchJob& j, Window win, Edit edit, hipStream_t stream)
     return err == hipSuccess ? LP_OK : LP_E_LAUNCH;
 }
 
+// The regions and the subjects crop: `groups` windows per image (the descriptor's `count`), origins from a device table read
+// by `Window`, a mask's windows through `Erase` when the descriptor has labels.  The two descriptors differ in that field's name.
+template <class Window, class Erase, class Desc>
+int resample_groups_dispatch(const Desc* dp, int Desc::*count, hipStream_t stream) {
+    if (!dp) return LP_E_INVALID;
+    const Desc& d = *dp;
+    const int groups = d.*count;
+    if (groups < 1 || groups > LP_DETAIL_MAX_REGIONS || !d.origins) return LP_E_INVALID;
+    ResampleJob j = {d.batch, d.src_h, d.src_w, d.channels, d.win_h, d.win_w, d.out_h, d.out_w, d.ksize_x, d.ksize_y,
+                     static_cast<int64_t>(groups) * d.batch, d.src, d.bounds_x, d.weights_x, d.bounds_y, d.weights_y, d.dst,
+                     nullptr};
+    const bool erased_resample = d.labels && !j.same();          // erased windows go to scratch, the resample reads them there
+    if (d.labels && (d.channels != 1 || !d.owner || d.owner_len < 1 || (erased_resample && !d.scratch))) return LP_E_INVALID;
+    if (erased_resample) j.scratch = d.scratch;
+    if (const int err = check_resample(j)) return err;
+    const Window win = {d.origins};
+    if (!d.labels) return launch_resample(j, win, stream);
+    return launch_resample_erased(j, win, Erase{d.labels, d.owner, d.owner_len, 1}, stream);
+}
+
+// The regions and the subjects stitch, after each entry's own checks: one copy of the frames, then group after group in order
+// and in place, out_{g+1} from out_g; group g's windows are where `window_of(g)` says and see the mask through `Erase`.
+template <class Erase, class Desc, class WindowOf>
+int stitch_groups(StitchJob j, const Desc& d, int groups, WindowOf window_of, hipStream_t stream) {
+    if (launch_frame_copy(j, stream) != hipSuccess) return LP_E_LAUNCH;
+    const int64_t per_group = static_cast<int64_t>(d.batch) * d.win_h * d.win_w * d.channels;
+    j.original = d.out;
+    for (int g = 0; g < groups; ++g, j.detail += per_group) {
+        const auto win = window_of(g);
+        const int err = d.labels ? launch_stitch(j, win, Erase{d.labels, d.owner, d.owner_len, g + 1}, stream)
+                                 : launch_stitch(j, win, MaskAsIs(), stream);
+        if (err) return err;
+    }
+    return LP_OK;
+}
+
 }  // namespace
 
 int mask_bbox_dispatch(const float* mask, int planes, int H, int W, int32_t* boxes, bool per_plane, hipStream_t stream) {
@@ -472,19 +502,7 @@ int detail_stitch_dispatch(const lp_detail_stitch_desc* dp, hipStream_t stream) 
 }
 
 int detail_resample_regions_dispatch(const lp_detail_resample_regions_desc* dp, hipStream_t stream) {
-    if (!dp) return LP_E_INVALID;
-    const lp_detail_resample_regions_desc& d = *dp;
-    if (d.regions < 1 || d.regions > LP_DETAIL_MAX_REGIONS || !d.origins) return LP_E_INVALID;
-    ResampleJob j = {d.batch, d.src_h, d.src_w, d.channels, d.win_h, d.win_w, d.out_h, d.out_w, d.ksize_x, d.ksize_y,
-                     static_cast<int64_t>(d.regions) * d.batch, d.src, d.bounds_x, d.weights_x, d.bounds_y, d.weights_y, d.dst,
-                     nullptr};
-    const bool erased_resample = d.labels && !j.same();          // erased windows go to scratch, the resample reads them there
-    if (d.labels && (d.channels != 1 || !d.owner || d.owner_len < 1 || (erased_resample && !d.scratch))) return LP_E_INVALID;
-    if (erased_resample) j.scratch = d.scratch;
-    if (const int err = check_resample(j)) return err;
-    const WindowOfRegion win = {d.origins};
-    if (!d.labels) return launch_resample(j, win, stream);
-    return launch_resample_erased(j, win, EraseForeign{d.labels, d.owner, d.owner_len, 0}, stream);
+    return resample_groups_dispatch<WindowOfRegion, EraseForeign<false>>(dp, &lp_detail_resample_regions_desc::regions, stream);
 }
 
 int detail_stitch_regions_dispatch(const lp_detail_stitch_regions_desc* dp, hipStream_t stream) {
@@ -494,19 +512,11 @@ int detail_stitch_regions_dispatch(const lp_detail_stitch_regions_desc* dp, hipS
     for (int r = 0; r < d.regions; ++r)                           // a host table: checked here, not clamped
         if (!window_ok(d.origins[2 * r], d.origins[2 * r + 1], d.win_h, d.win_w, d.height, d.width)) return LP_E_INVALID;
     if (d.labels && (!d.owner || d.owner_len < 1)) return LP_E_INVALID;
-    StitchJob j = {d.batch, d.height, d.width, d.channels, d.win_h, d.win_w, d.k, d.mask_batch, d.mask, d.original, d.detail,
-                   d.out};
+    const StitchJob j = {d.batch, d.height, d.width, d.channels, d.win_h, d.win_w, d.k, d.mask_batch, d.mask, d.original,
+                         d.detail, d.out};
     if (const int err = check_stitch(j)) return err;
-    if (launch_frame_copy(j, stream) != hipSuccess) return LP_E_LAUNCH;
-    const int64_t per_region = static_cast<int64_t>(d.batch) * d.win_h * d.win_w * d.channels;
-    j.original = d.out;                                           // in order, in place: out_{r+1} from out_r
-    for (int r = 0; r < d.regions; ++r, j.detail += per_region) {
-        const WindowAt at = {d.origins[2 * r], d.origins[2 * r + 1]};
-        const int err = d.labels ? launch_stitch(j, at, EraseForeign{d.labels, d.owner, d.owner_len, r + 1}, stream)
-                                 : launch_stitch(j, at, MaskAsIs(), stream);
-        if (err) return err;
-    }
-    return LP_OK;
+    const auto window_of = [&d](int r) { return WindowAt{d.origins[2 * r], d.origins[2 * r + 1]}; };      // checked above
+    return stitch_groups<EraseForeign<false>>(j, d, d.regions, window_of, stream);
 }
 
 int subject_boxes_dispatch(const int32_t* labels, int frames, int H, int W, const int32_t* owner, int owner_len, int subjects,
@@ -523,19 +533,7 @@ int subject_boxes_dispatch(const int32_t* labels, int frames, int H, int W, cons
 }
 
 int detail_resample_subjects_dispatch(const lp_detail_resample_subjects_desc* dp, hipStream_t stream) {
-    if (!dp) return LP_E_INVALID;
-    const lp_detail_resample_subjects_desc& d = *dp;
-    if (d.subjects < 1 || d.subjects > LP_DETAIL_MAX_REGIONS || !d.origins) return LP_E_INVALID;
-    ResampleJob j = {d.batch, d.src_h, d.src_w, d.channels, d.win_h, d.win_w, d.out_h, d.out_w, d.ksize_x, d.ksize_y,
-                     static_cast<int64_t>(d.subjects) * d.batch, d.src, d.bounds_x, d.weights_x, d.bounds_y, d.weights_y, d.dst,
-                     nullptr};
-    const bool erased_resample = d.labels && !j.same();
-    if (d.labels && (d.channels != 1 || !d.owner || d.owner_len < 1 || (erased_resample && !d.scratch))) return LP_E_INVALID;
-    if (erased_resample) j.scratch = d.scratch;
-    if (const int err = check_resample(j)) return err;
-    const WindowOfSubject win = {d.origins};
-    if (!d.labels) return launch_resample(j, win, stream);
-    return launch_resample_erased(j, win, EraseForeignFrame{{d.labels, d.owner, d.owner_len, 0}}, stream);
+    return resample_groups_dispatch<WindowOfSubject, EraseForeign<true>>(dp, &lp_detail_resample_subjects_desc::subjects, stream);
 }
 
 int detail_stitch_subjects_dispatch(const lp_detail_stitch_subjects_desc* dp, hipStream_t stream) {
@@ -543,18 +541,10 @@ int detail_stitch_subjects_dispatch(const lp_detail_stitch_subjects_desc* dp, hi
     const lp_detail_stitch_subjects_desc& d = *dp;
     if (d.subjects < 1 || d.subjects > LP_DETAIL_MAX_REGIONS || !d.origins) return LP_E_INVALID;
     if (d.labels && (!d.owner || d.owner_len < 1)) return LP_E_INVALID;
-    StitchJob j = {d.batch, d.height, d.width, d.channels, d.win_h, d.win_w, d.k, d.batch, d.mask, d.original, d.detail, d.out};
+    const StitchJob j = {d.batch, d.height, d.width, d.channels, d.win_h, d.win_w, d.k, d.batch, d.mask, d.original, d.detail, d.out};
     if (const int err = check_stitch(j)) return err;
-    if (launch_frame_copy(j, stream) != hipSuccess) return LP_E_LAUNCH;
-    const int64_t per_subject = static_cast<int64_t>(d.batch) * d.win_h * d.win_w * d.channels;
-    j.original = d.out;                                           // in order, in place: out_{s+1} from out_s
-    for (int s = 0; s < d.subjects; ++s, j.detail += per_subject) {
-        const WindowOfImage win = {d.origins + 2 * static_cast<int64_t>(s) * d.batch};      // subject s's row of the table
-        const int err = d.labels ? launch_stitch(j, win, EraseForeignFrame{{d.labels, d.owner, d.owner_len, s + 1}}, stream)
-                                 : launch_stitch(j, win, MaskAsIs(), stream);
-        if (err) return err;
-    }
-    return LP_OK;
+    const auto window_of = [&d](int s) { return WindowOfImage{d.origins + 2 * static_cast<int64_t>(s) * d.batch}; };   // s's row
+    return stitch_groups<EraseForeign<true>>(j, d, d.subjects, window_of, stream);
 }
 
 int detail_resample_track_dispatch(const lp_detail_resample_track_desc* dp, hipStream_t stream) {

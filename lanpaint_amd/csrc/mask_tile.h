@@ -19,9 +19,11 @@ constexpr size_t mask_tile_lds_bytes(int k) {
     return sizeof(float) * (static_cast<size_t>(TH + 4 * R) * (TW + 4 * R) + static_cast<size_t>(TH + 4 * R) * (TW + 2 * R) + k);
 }
 
-// How a mask element enters pass A: Edit(value, flat index in the mask plane).  The default takes it as it is.
+// How a mask element enters pass A: Edit(value, flat index in the mask plane).  The default takes it as it is, and is the
+// same for every window (region, image) of a launch (detail_kernel.hip).
 struct MaskAsIs {
     __device__ __forceinline__ float operator()(float v, int64_t) const { return v; }
+    __device__ __forceinline__ MaskAsIs view(int, int, int64_t) const { return *this; }
 };
 
 // Runs passes A..D on `lds` (mask_tile_lds_bytes<TH, TW>(k) bytes).  On return D (CH x TW, CH = TH + 2R, row-blurred) and g

@@ -85,6 +85,7 @@ import ctypes
 import dataclasses
 import functools
 import math
+import typing
 
 import numpy as np
 import torch
@@ -108,6 +109,7 @@ class Region:
     ow: int
     H: int
     W: int
+    groups = 1                                            # windows per image
 
     @property
     def resampled(self):
@@ -124,6 +126,7 @@ class _Windows:
     oh: int
     ow: int
     origins: tuple
+    groups = 1                                            # windows per image
 
     def __len__(self):
         return len(self.origins)
@@ -141,11 +144,29 @@ class _Windows:
 class Regions(_Windows):
     """One window per region of the mask; `members[i]` are the component labels region i owns, ascending."""
     members: tuple
+    groups = property(_Windows.__len__)
 
 
 @dataclasses.dataclass(frozen=True)
 class Track(_Windows):
     """One window per frame of a video: frame f's is at `origins[f]`."""
+
+
+@dataclasses.dataclass(frozen=True)
+class Subjects(_Windows):
+    """One window per (subject, frame) (lanpaint_amd/detail_subjects.py): window (s, f) is at `origins[s * frames + f]`;
+    `members[s]` are the space-time component labels subject s owns, ascending."""
+    frames: int
+    members: tuple
+
+    @property
+    def subjects(self):
+        return len(self.members)
+
+    groups = subjects
+
+    def window(self, s, f):
+        return self.region(s * self.frames + f)
 
 
 def _ceil_div(a, b):
@@ -283,25 +304,20 @@ def _aa_tables_f32(in_size, out_size, filter):
 
 
 def _resample(src, win, filter, origins=None, labels=None, owner=None):
-    """Every window of `win` cut out of a contiguous fp32 HIP tensor [B, H, W, C] at win's working size: a Region through
-    lp_detail_resample -> [B, oh, ow, C]; Regions through lp_detail_resample_regions -> [R * B, oh, ow, C], with `labels` and
-    `owner` region r's view of a mask; a Track through lp_detail_resample_track -> [B, oh, ow, C].  `origins`: the device table
-    of the two table forms."""
+    """Every window of `win` cut out of a contiguous fp32 HIP tensor [B, H, W, C] at win's working size through its form's
+    crop entry (_FORMS) -> [win.groups * B, oh, ow, C], group-major.  `origins`: the device table of the three table forms;
+    `labels` and `owner` (Regions, Subjects): each window is its group's view of a mask."""
     b, sh, sw, c = src.shape
-    dev, images, scratch = src.device, b, None
-    if isinstance(win, Region):
-        entry, d = "lp_detail_resample", _cabi.LpDetailResampleDesc(b, sh, sw, c, win.y0, win.x0, win.h, win.w, win.oh, win.ow)
-    elif isinstance(win, Regions):
-        entry, images = "lp_detail_resample_regions", len(win) * b
-        d = _cabi.LpDetailResampleRegionsDesc(b, sh, sw, c, len(win), win.h, win.w, 0, win.oh, win.ow, origins=origins.data_ptr())
-        if labels is not None:
-            d.labels, d.owner, d.owner_len = labels.data_ptr(), owner.data_ptr(), owner.numel()
-            if win.resampled:
-                scratch = torch.empty((images, win.h, win.w), dtype=torch.float32, device=dev)
-                d.scratch = scratch.data_ptr()
-    else:
-        entry = "lp_detail_resample_track"
-        d = _cabi.LpDetailResampleTrackDesc(b, sh, sw, c, win.h, win.w, win.oh, win.ow, origins=origins.data_ptr())
+    dev, images, scratch = src.device, win.groups * b, None
+    entry = _FORMS[type(win)].crop
+    d = _FORMS[type(win)].desc(win, b, sh, sw, c)
+    if origins is not None:
+        d.origins = origins.data_ptr()
+    if labels is not None:
+        d.labels, d.owner, d.owner_len = labels.data_ptr(), owner.data_ptr(), owner.numel()
+        if win.resampled:
+            scratch = torch.empty((images, win.h, win.w), dtype=torch.float32, device=dev)
+            d.scratch = scratch.data_ptr()
     out = torch.empty((images, win.oh, win.ow, c), dtype=torch.float32, device=dev)
     d.src, d.dst = src.data_ptr(), out.data_ptr()
     if win.resampled:
@@ -332,30 +348,28 @@ def crop_resample(image, mask, region, filter="bilinear"):
     return out, _resample(m.unsqueeze(-1), r, "bilinear").squeeze(-1)
 
 
-def _stitch_inputs(original, detail_img, mask, win, blend_overlap, filter, labels=None):
-    """What every stitch starts with: the arguments checked against `win` (a Region, Regions or a Track) and made contiguous
-    fp32 on original's device, the crops resampled back to the windows' size in one launch -> (orig, det, m, b, H, W, c)."""
+def _stitch_inputs(original, detail_img, mask, win, blend_overlap, filter, labels=None, frame_mask=None):
+    """What every stitch starts with: the arguments checked against `win` (any of the four forms) and made contiguous fp32 on
+    original's device, the crops resampled back to the windows' size in one launch -> (orig, det, m, b, H, W, c).  The mask is
+    [B, H, W] or one plane for all images, unless the form has a rule of its own: `frame_mask(mask, B, H, W)`."""
     _check_filter(filter)
     k = blend_overlap
     if not isinstance(k, int) or k < 1 or k > 51 or k % 2 == 0:
         raise ValueError(f"blend_overlap must be an odd integer in [1, 51], got {k!r}")
-    name = "detail_imgs" if isinstance(win, Regions) else "detail_img"
+    name = _FORMS[type(win)].crops
     orig = _as_f32c(_hip(original, "original"))
     det = _as_f32c(_hip(detail_img, name).to(orig.device))
-    m = _as_f32c(_mask3(_hip(mask, "mask")).to(orig.device))
+    m = None if frame_mask else _as_f32c(_mask3(_hip(mask, "mask")).to(orig.device))
     if orig.ndim != 4 or det.ndim != 4:
         raise ValueError(f"original and {name} must be [B, H, W, C]")
     b, H, W, c = orig.shape
-    if isinstance(win, Region):
-        _check_region(win, H, W)
-    elif isinstance(win, Regions):
-        _check_regions(win, labels, H, W)
-    else:
-        _check_track(win, b, H, W)
-    want = ((len(win) if isinstance(win, Regions) else 1) * b, win.oh, win.ow, c)
+    _FORMS[type(win)].check(win, labels, b, H, W)
+    want = (win.groups * b, win.oh, win.ow, c)
     if tuple(det.shape) != want:
         raise ValueError(f"{name} must be {want}, got {tuple(det.shape)}")
-    if m.shape[0] not in (1, b) or tuple(m.shape[1:]) != (H, W):
+    if frame_mask:
+        m = _as_f32c(frame_mask(mask, b, H, W).to(orig.device))
+    elif m.shape[0] not in (1, b) or tuple(m.shape[1:]) != (H, W):
         raise ValueError(f"mask shape {tuple(mask.shape)} does not match images {tuple(original.shape)}")
     if win.resampled:
         det = _resample(det, Region(0, 0, win.oh, win.ow, win.h, win.w, win.oh, win.ow), filter)
@@ -382,19 +396,25 @@ def mask_components(mask):
     (labels int32 [H, W] on the device, n, table).  Labels run 1..n in raster order of each component's first pixel, 0 is the
     background (scipy.ndimage.label with a 3 x 3 structure of ones); table[id - 1] = (r0, r1, c0, c1, area), boxes inclusive,
     for id = 1..min(n, LP_DETAIL_MAX_COMPONENTS).  Reads the table back from the device, nothing else."""
+    return _components(mask, "lp_mask_components", 5)
+
+
+def _components(mask, entry, cols, volume=False):
+    """A labelling entry called and its table read back: (labels, n, rows of `cols` integers).  The labels are one image for
+    every plane of the mask, or with `volume` one plane each."""
     m = _as_f32c(_mask3(_hip(mask, "mask")))
     planes, h, w = m.shape
     dev = m.device
-    labels = torch.empty((h, w), dtype=torch.int32, device=dev)
-    table = torch.empty(1 + 5 * _cabi.LP_DETAIL_MAX_COMPONENTS, dtype=torch.int32, device=dev)
-    ws_bytes = _cabi.lp_components_ws_bytes(h, w)
+    labels = torch.empty((planes, h, w) if volume else (h, w), dtype=torch.int32, device=dev)
+    table = torch.empty(1 + cols * _cabi.LP_DETAIL_MAX_COMPONENTS, dtype=torch.int32, device=dev)
+    ws_bytes = _cabi.lp_components_frames_ws_bytes(planes, h, w) if volume else _cabi.lp_components_ws_bytes(h, w)
     ws = torch.empty(ws_bytes // 4, dtype=torch.int32, device=dev)
     with torch.cuda.device(dev):
-        _cabi.check(_cabi.load().lp_mask_components(m.data_ptr(), planes, h, w, labels.data_ptr(), table.data_ptr(),
-                                                    ws.data_ptr(), ws_bytes, raw_stream(dev)), "lp_mask_components")
+        _cabi.check(getattr(_cabi.load(), entry)(m.data_ptr(), planes, h, w, labels.data_ptr(), table.data_ptr(), ws.data_ptr(),
+                                                 ws_bytes, raw_stream(dev)), entry)
     host = table.cpu().numpy()
     n = int(host[0])
-    rows = host[1:1 + 5 * min(n, _cabi.LP_DETAIL_MAX_COMPONENTS)].reshape(-1, 5)
+    rows = host[1:1 + cols * min(n, _cabi.LP_DETAIL_MAX_COMPONENTS)].reshape(-1, cols)
     return labels, n, tuple(tuple(int(v) for v in row) for row in rows)
 
 
@@ -427,15 +447,16 @@ def _close(boxes, members, plan):
 
 
 def _merge_smallest_union(boxes, members):
-    """The rule's `limit`, one merge: the pair (i, j), i < j, whose union raw box is smallest; ties to the lowest i, then j."""
+    """A rule's `limit`, one merge: the pair (i, j), i < j, whose union box -- (lo, hi) inclusive per axis, any number of axes --
+    has the smallest product of extents; ties to the lowest i, then j."""
     b = np.array(boxes, np.int64)
-    hh = np.maximum(b[:, None, 1], b[None, :, 1]) - np.minimum(b[:, None, 0], b[None, :, 0]) + 1
-    ww = np.maximum(b[:, None, 3], b[None, :, 3]) - np.minimum(b[:, None, 2], b[None, :, 2]) + 1
-    area = hh * ww
-    area[np.tril_indices(len(boxes))] = np.iinfo(np.int64).max
-    i, j = (int(v) for v in np.unravel_index(int(np.argmin(area)), area.shape))      # argmin: the first in row-major order
+    size = np.ones((len(boxes), len(boxes)), np.int64)
+    for a in range(0, b.shape[1], 2):
+        size *= np.maximum(b[:, None, a + 1], b[None, :, a + 1]) - np.minimum(b[:, None, a], b[None, :, a]) + 1
+    size[np.tril_indices(len(boxes))] = np.iinfo(np.int64).max
+    i, j = (int(v) for v in np.unravel_index(int(np.argmin(size)), size.shape))      # argmin: the first in row-major order
     p, q = boxes[i], boxes[j]
-    boxes[i] = (min(p[0], q[0]), max(p[1], q[1]), min(p[2], q[2]), max(p[3], q[3]))
+    boxes[i] = tuple(min(p[a], q[a]) if a % 2 == 0 else max(p[a], q[a]) for a in range(len(p)))
     members[i] = tuple(sorted(members[i] + members[j]))
     del boxes[j], members[j]
 
@@ -483,17 +504,26 @@ def plan_regions(components, H, W, context=1.0, padding=0, multiple_of=8, target
     return Regions(H, W, h, w, oh, ow, origins, tuple(members))
 
 
-def _region_tables(regions, labels, dev):
-    """(origins int32 [R, 2] on the device, owner int32 on the device or None): owner[label] = region + 1, 0 for a label no region
-    owns."""
-    origins = torch.tensor(regions.origins, dtype=torch.int32, device=dev).reshape(-1, 2)
-    if labels is None:
-        return origins, None
-    top = max(max(mem) for mem in regions.members)
-    owner = np.zeros(top + 1, np.int32)
-    for i, mem in enumerate(regions.members):
+def _origins_table(win, dev):
+    """win's origins as the table forms' entries read them: int32 [n, 2] on the device."""
+    return torch.tensor(win.origins, dtype=torch.int32, device=dev).reshape(-1, 2)
+
+
+def _owner_table(members, dev):
+    """owner int32 on the device: owner[label] = group + 1, 0 for a label no region or subject owns."""
+    owner = np.zeros(max(max(mem) for mem in members) + 1, np.int32)
+    for i, mem in enumerate(members):
         owner[np.asarray(mem, np.int64)] = i + 1
-    return origins, torch.from_numpy(owner).to(dev)
+    return torch.from_numpy(owner).to(dev)
+
+
+def _check_labels(labels, planes, H, W):
+    """`planes`: None for one label image (mask_components), else the planes of a label volume (mask_components_frames)."""
+    _hip(labels, "labels")
+    shape, source = ((H, W), "mask_components") if planes is None else ((planes, H, W), "mask_components_frames")
+    if labels.dtype != torch.int32 or tuple(labels.shape) != shape or not labels.is_contiguous():
+        raise ValueError(f"labels must be a contiguous int32 {list(shape)} tensor ({source}), got {labels.dtype} "
+                         f"{tuple(labels.shape)}")
 
 
 def _check_regions(regions, labels, H, W):
@@ -502,10 +532,7 @@ def _check_regions(regions, labels, H, W):
     if not 1 <= len(regions) <= _cabi.LP_DETAIL_MAX_REGIONS:
         raise ValueError(f"1..{_cabi.LP_DETAIL_MAX_REGIONS} regions are supported, got {len(regions)}")
     if labels is not None:
-        _hip(labels, "labels")
-        if labels.dtype != torch.int32 or tuple(labels.shape) != (H, W) or not labels.is_contiguous():
-            raise ValueError(f"labels must be a contiguous int32 [{H}, {W}] tensor (mask_components), got {labels.dtype} "
-                             f"{tuple(labels.shape)}")
+        _check_labels(labels, None, H, W)
 
 
 def crop_regions(image, mask, regions, labels=None, filter="bilinear"):
@@ -518,7 +545,8 @@ def crop_regions(image, mask, regions, labels=None, filter="bilinear"):
         raise ValueError(f"image must be [B, H, W, C], got {tuple(image.shape)}")
     H, W = img.shape[1], img.shape[2]
     _check_regions(regions, labels, H, W)
-    origins, owner = _region_tables(regions, labels, img.device)
+    origins = _origins_table(regions, img.device)
+    owner = None if labels is None else _owner_table(regions.members, img.device)
     out = _resample(img, regions, filter, origins)
     if mask is None:
         return out, None
@@ -535,13 +563,13 @@ def stitch_regions(original, detail_imgs, mask, regions, labels=None, blend_over
     the frame and then each region's window in place."""
     orig, det, m, b, H, W, c = _stitch_inputs(original, detail_imgs, mask, regions, blend_overlap, filter, labels)
     g, n_reg, k, dev = regions, len(regions), blend_overlap, orig.device
-    _, owner = _region_tables(regions, labels, dev)
     host_origins = (ctypes.c_int32 * (2 * n_reg))(*(v for o in g.origins for v in o))
     out = torch.empty_like(orig)
     d = _cabi.LpDetailStitchRegionsDesc(b, H, W, c, n_reg, g.h, g.w, k, m.shape[0], 0)
     d.origins = ctypes.cast(host_origins, ctypes.c_void_p)
     d.mask, d.original, d.detail, d.out = m.data_ptr(), orig.data_ptr(), det.data_ptr(), out.data_ptr()
     if labels is not None:
+        owner = _owner_table(g.members, dev)
         d.labels, d.owner, d.owner_len = labels.data_ptr(), owner.data_ptr(), owner.numel()
     with torch.cuda.device(dev):
         _cabi.check(_cabi.load().lp_detail_stitch_regions(ctypes.byref(d), raw_stream(dev)), "lp_detail_stitch_regions")
@@ -584,19 +612,15 @@ def _track_axis(spans, n_img, c1000, padding, m, k, n=None):
     return origins, n
 
 
-def plan_track(boxes, H, W, context=1.0, padding=0, multiple_of=8, target=0, smooth=1, frames=None):
-    """The module docstring's track rule: one box (r0, r1, c0, c1) per frame, inclusive, empty frames as lp_mask_bbox marks
-    them (r1 < r0) -> Track.  `frames` is the length of the batch the track serves: len(boxes) when not given, and a single
-    box is repeated to it (a static mask)."""
-    boxes = [tuple(int(v) for v in box) for box in boxes]
-    H, W, c1000, padding, m, target = _plan_args(H, W, context, padding, multiple_of, target)
+def _check_smooth(smooth):
     if isinstance(smooth, bool) or int(smooth) != smooth or smooth < 1 or smooth % 2 == 0:
         raise ValueError(f"smooth must be an odd integer >= 1, got {smooth!r}")
-    frames = len(boxes) if frames is None else int(frames)
-    if frames < 1 or len(boxes) not in (1, frames) or any(len(box) != 4 for box in boxes):
-        raise ValueError(f"one box of four integers per frame, or a single one, is required: got {len(boxes)} for {frames} frames")
-    if len(boxes) != frames:
-        boxes = boxes * frames
+    return int(smooth)
+
+
+def _box_spans(boxes, H, W, what):
+    """One path's boxes (r0, r1, c0, c1), inclusive, as the row spans and the column spans _track_axis takes: None for an empty
+    frame (r1 < r0).  `what(f)` names frame f's box in the error for one outside the image."""
     rows, cols = [], []
     for f, (r0, r1, c0, c1) in enumerate(boxes):
         if r1 < r0 or c1 < c0:
@@ -604,13 +628,29 @@ def plan_track(boxes, H, W, context=1.0, padding=0, multiple_of=8, target=0, smo
             cols.append(None)
             continue
         if r0 < 0 or c0 < 0 or r1 >= H or c1 >= W:
-            raise ValueError(f"frame {f}'s box {(r0, r1, c0, c1)} lies outside the {H}x{W} image")
+            raise ValueError(f"{what(f)} {(r0, r1, c0, c1)} lies outside the {H}x{W} image")
         rows.append((r0, r1))
         cols.append((c0, c1))
+    return rows, cols
+
+
+def plan_track(boxes, H, W, context=1.0, padding=0, multiple_of=8, target=0, smooth=1, frames=None):
+    """The module docstring's track rule: one box (r0, r1, c0, c1) per frame, inclusive, empty frames as lp_mask_bbox marks
+    them (r1 < r0) -> Track.  `frames` is the length of the batch the track serves: len(boxes) when not given, and a single
+    box is repeated to it (a static mask)."""
+    boxes = [tuple(int(v) for v in box) for box in boxes]
+    H, W, c1000, padding, m, target = _plan_args(H, W, context, padding, multiple_of, target)
+    smooth = _check_smooth(smooth)
+    frames = len(boxes) if frames is None else int(frames)
+    if frames < 1 or len(boxes) not in (1, frames) or any(len(box) != 4 for box in boxes):
+        raise ValueError(f"one box of four integers per frame, or a single one, is required: got {len(boxes)} for {frames} frames")
+    if len(boxes) != frames:
+        boxes = boxes * frames
+    rows, cols = _box_spans(boxes, H, W, lambda f: f"frame {f}'s box")
     if all(span is None for span in rows):
         raise ValueError("the mask is empty in every frame: there is no region to detail")
-    ys, h = _track_axis(rows, H, c1000, padding, m, int(smooth))
-    xs, w = _track_axis(cols, W, c1000, padding, m, int(smooth))
+    ys, h = _track_axis(rows, H, c1000, padding, m, smooth)
+    xs, w = _track_axis(cols, W, c1000, padding, m, smooth)
     oh, ow = _working_size(h, w, m, target)
     return Track(H, W, h, w, oh, ow, tuple(zip(ys, xs)))
 
@@ -633,15 +673,60 @@ def _check_track(track, batch, H, W):
         raise ValueError(f"the track was planned for a {track.H}x{track.W} image, got {H}x{W}")
     if len(track) != batch:
         raise ValueError(f"the track holds {len(track)} frames, the batch {batch}")
-    if not (0 < track.h <= H and 0 < track.w <= W):
-        raise ValueError(f"a {track.h}x{track.w} window does not fit the {H}x{W} image")
-    for f, (y0, x0) in enumerate(track.origins):
-        if y0 < 0 or x0 < 0 or y0 + track.h > H or x0 + track.w > W:
-            raise ValueError(f"frame {f}'s window at {(y0, x0)} leaves the {H}x{W} image")
+    _check_fit(track, H, W, lambda f: f"frame {f}'s window")
 
 
-def _track_origins(track, dev):
-    return torch.tensor(track.origins, dtype=torch.int32, device=dev).reshape(-1, 2)
+def _check_fit(win, H, W, what):
+    """Every window of a table form lies inside the H x W image; `what(i)` names window i in the error."""
+    if not (0 < win.h <= H and 0 < win.w <= W):
+        raise ValueError(f"a {win.h}x{win.w} window does not fit the {H}x{W} image")
+    for i, (y0, x0) in enumerate(win.origins):
+        if y0 < 0 or x0 < 0 or y0 + win.h > H or x0 + win.w > W:
+            raise ValueError(f"{what(i)} at {(y0, x0)} leaves the {H}x{W} image")
+
+
+def _check_members(members):
+    members = tuple(tuple(int(v) for v in mem) for mem in members)
+    if not 1 <= len(members) <= _cabi.LP_DETAIL_MAX_REGIONS:
+        raise ValueError(f"1..{_cabi.LP_DETAIL_MAX_REGIONS} subjects are supported, got {len(members)}")
+    if any(not mem or min(mem) < 1 for mem in members):
+        raise ValueError("every subject needs at least one member label, and labels start at 1")
+    return members
+
+
+def _check_subjects(subjects, labels, frames, H, W):
+    if (subjects.H, subjects.W) != (H, W):
+        raise ValueError(f"the subjects were planned for a {subjects.H}x{subjects.W} image, got {H}x{W}")
+    if subjects.frames != frames or len(subjects.origins) != subjects.subjects * frames:
+        raise ValueError(f"the subjects were planned for {subjects.frames} frames, the batch holds {frames}")
+    _check_members(subjects.members)
+    _check_fit(subjects, H, W, lambda i: f"subject {i // frames}, frame {i % frames}: the window")
+    if labels is not None:
+        _check_labels(labels, frames, H, W)
+
+
+class _Form(typing.NamedTuple):
+    """What differs between the four forms behind _resample and _stitch_inputs, by window class."""
+    crop: str                                             # the crop entry
+    desc: typing.Callable                                 # (win, b, sh, sw, c) -> its descriptor, up to the pointers
+    check: typing.Callable                                # (win, labels, b, H, W): the windows against a batch, or ValueError
+    crops: str                                            # what the stitch calls its crops
+
+
+_FORMS = {
+    Region: _Form("lp_detail_resample",
+                  lambda r, *src: _cabi.LpDetailResampleDesc(*src, r.y0, r.x0, r.h, r.w, r.oh, r.ow),
+                  lambda r, labels, b, H, W: _check_region(r, H, W), "detail_img"),
+    Regions: _Form("lp_detail_resample_regions",
+                   lambda g, *src: _cabi.LpDetailResampleRegionsDesc(*src, g.groups, g.h, g.w, 0, g.oh, g.ow),
+                   lambda g, labels, b, H, W: _check_regions(g, labels, H, W), "detail_imgs"),
+    Track: _Form("lp_detail_resample_track",
+                 lambda t, *src: _cabi.LpDetailResampleTrackDesc(*src, t.h, t.w, t.oh, t.ow),
+                 lambda t, labels, b, H, W: _check_track(t, b, H, W), "detail_img"),
+    Subjects: _Form("lp_detail_resample_subjects",
+                    lambda g, *src: _cabi.LpDetailResampleSubjectsDesc(*src, g.groups, g.h, g.w, 0, g.oh, g.ow),
+                    _check_subjects, "detail_imgs"),
+}
 
 
 def crop_track(image, mask, track, filter="bilinear"):
@@ -654,7 +739,7 @@ def crop_track(image, mask, track, filter="bilinear"):
         raise ValueError(f"image must be [B, H, W, C], got {tuple(image.shape)}")
     b, H, W = img.shape[0], img.shape[1], img.shape[2]
     _check_track(track, b, H, W)
-    origins = _track_origins(track, img.device)
+    origins = _origins_table(track, img.device)
     out = _resample(img, track, filter, origins)
     if mask is None:
         return out, None
@@ -675,7 +760,7 @@ def stitch_track(original, detail_img, mask, track, blend_overlap=1, filter="bil
     every frame's window.  `mask` [B, H, W] or one plane for all frames."""
     orig, det, m, b, H, W, c = _stitch_inputs(original, detail_img, mask, track, blend_overlap, filter)
     t, k, dev = track, blend_overlap, orig.device
-    origins = _track_origins(t, dev)
+    origins = _origins_table(t, dev)
     out = torch.empty_like(orig)
     d = _cabi.LpDetailStitchTrackDesc(b, H, W, c, t.h, t.w, k, m.shape[0],
                                       origins.data_ptr(), m.data_ptr(), orig.data_ptr(), det.data_ptr(), out.data_ptr())

@@ -27,6 +27,12 @@ def _hip_device(t):
     return torch.device("cuda", torch.cuda.current_device())
 
 
+def _on_device(image, mask):
+    """What every crop node starts with: (image, mask as [B, H, W]) on the HIP device the crop runs on."""
+    dev = _hip_device(image)
+    return image.to(dev), (mask.unsqueeze(0) if mask.ndim == 2 else mask).to(dev)
+
+
 class LanPaint_DetailerCrop:
     """Crop image and mask to the masked region (one region for every frame of the batch) at a working size."""
 
@@ -54,10 +60,7 @@ class LanPaint_DetailerCrop:
                    "Feed the outputs to LanPaint_ImageEncode and the stitch output to LanPaint_DetailerStitch.")
 
     def crop(self, image, mask, context=1.5, padding=32, target=1024, multiple_of=8, filter="bicubic"):
-        dev = _hip_device(image)
-        img, m = image.to(dev), mask.to(dev)
-        if m.ndim == 2:
-            m = m.unsqueeze(0)
+        img, m = _on_device(image, mask)
         region = detail.plan_region(detail.mask_bbox(m), img.shape[1], img.shape[2], context, padding, multiple_of, target)
         cimg, cmask = detail.crop_resample(img, m, region, filter)
         stitch = {"original": image, "mask": mask, "region": region, "filter": filter}
@@ -65,31 +68,28 @@ class LanPaint_DetailerCrop:
 
 
 class LanPaint_DetailerStitch:
-    """Resample the inpainted region back and blend it into the original; outside the region the original is untouched."""
+    """Resample the inpainted region back and blend it into the original; outside the region the original is untouched.  The other
+    three stitch nodes subclass it and name their socket, crop node, texts, the stitch dict's key for the windows and the call."""
+    STITCH_TYPE, CROP_NODE, WINDOWS, CALL = "LANPAINT_STITCH", "LanPaint_DetailerCrop", "region", staticmethod(detail.stitch)
+    IMAGE_TIP = "The inpainted region, at the working resolution."
+    DESCRIPTION = "Stitch the inpainted region from LanPaint_DetailerCrop back into the original image."
+    RETURN_TYPES, RETURN_NAMES, FUNCTION, CATEGORY = ("IMAGE",), ("image",), "stitch", "image"
 
     @classmethod
     def INPUT_TYPES(s):
-        return {"required": {
-            "stitch": ("LANPAINT_STITCH", {"tooltip": "From LanPaint_DetailerCrop."}),
-            "image": ("IMAGE", {"tooltip": "The inpainted region, at the working resolution."}),
-            "blend_overlap": ("INT", {"default": 9, "min": 1, "max": 51, "step": 2,
-                                      "tooltip": "Boundary blend width in pixels between the inpainted and original image (MaskBlend-style)."}),
-        }}
-
-    RETURN_TYPES = ("IMAGE",)
-    RETURN_NAMES = ("image",)
-    FUNCTION = "stitch"
-    CATEGORY = "image"
-    DESCRIPTION = "Stitch the inpainted region from LanPaint_DetailerCrop back into the original image."
+        blend = {"default": 9, "min": 1, "max": 51, "step": 2,
+                 "tooltip": "Boundary blend width in pixels between the inpainted and original image (MaskBlend-style)."}
+        return {"required": {"stitch": (s.STITCH_TYPE, {"tooltip": f"From {s.CROP_NODE}."}),
+                             "image": ("IMAGE", {"tooltip": s.IMAGE_TIP}), "blend_overlap": ("INT", blend)}}
 
     def stitch(self, stitch, image, blend_overlap=9):
         original = stitch["original"]
         dev = _hip_device(original)
-        out = detail.stitch(original.to(dev), image.to(dev), stitch["mask"].to(dev), stitch["region"], blend_overlap,
-                            stitch["filter"])
+        labels = (stitch["labels"].to(dev),) if "labels" in stitch else ()        # after the windows, where the crop node left some
+        out = self.CALL(original.to(dev), image.to(dev), stitch["mask"].to(dev), stitch[self.WINDOWS], *labels, blend_overlap,
+                        stitch["filter"])
         return (out.to(original.device),)
 
 
 NODE_CLASS_MAPPINGS = {"LanPaint_DetailerCrop": LanPaint_DetailerCrop, "LanPaint_DetailerStitch": LanPaint_DetailerStitch}
-NODE_DISPLAY_NAME_MAPPINGS = {"LanPaint_DetailerCrop": "LanPaint Detailer Crop",
-                              "LanPaint_DetailerStitch": "LanPaint Detailer Stitch"}
+NODE_DISPLAY_NAME_MAPPINGS = {"LanPaint_DetailerCrop": "LanPaint Detailer Crop", "LanPaint_DetailerStitch": "LanPaint Detailer Stitch"}

@@ -16,7 +16,7 @@ This module has its own NODE_CLASS_MAPPINGS: merge them with the others' (INTEGR
 from __future__ import annotations
 
 from . import _cabi, detail
-from .detail_nodes import LanPaint_DetailerCrop, LanPaint_DetailerStitch, _hip_device
+from .detail_nodes import LanPaint_DetailerCrop, LanPaint_DetailerStitch, _on_device
 
 
 class LanPaint_DetailerCropRegions:
@@ -42,10 +42,7 @@ class LanPaint_DetailerCropRegions:
 
     def crop(self, image, mask, context=1.5, padding=32, target=1024, multiple_of=8, filter="bicubic", min_area=64,
              max_regions=8):
-        dev = _hip_device(image)
-        img, m = image.to(dev), mask.to(dev)
-        if m.ndim == 2:
-            m = m.unsqueeze(0)
+        img, m = _on_device(image, mask)
         labels, n, table = detail.mask_components(m)
         bbox = detail.mask_bbox(m) if n > _cabi.LP_DETAIL_MAX_COMPONENTS else None
         regions = detail.plan_regions((n, table), img.shape[1], img.shape[2], context, padding, multiple_of, target, min_area,
@@ -55,28 +52,12 @@ class LanPaint_DetailerCropRegions:
         return (cimg.to(image.device), cmask.to(mask.device), stitch, len(regions))
 
 
-class LanPaint_DetailerStitchRegions:
+class LanPaint_DetailerStitchRegions(LanPaint_DetailerStitch):
     """Resample the inpainted regions back and blend them into the original, region after region."""
-
-    @classmethod
-    def INPUT_TYPES(s):
-        required = dict(LanPaint_DetailerStitch.INPUT_TYPES()["required"])
-        required["stitch"] = ("LANPAINT_STITCH_REGIONS", {"tooltip": "From LanPaint_DetailerCropRegions."})
-        required["image"] = ("IMAGE", {"tooltip": "The inpainted regions, at the working resolution, stacked as they were cropped."})
-        return {"required": required}
-
-    RETURN_TYPES = ("IMAGE",)
-    RETURN_NAMES = ("image",)
-    FUNCTION = "stitch"
-    CATEGORY = "image"
+    STITCH_TYPE, CROP_NODE = "LANPAINT_STITCH_REGIONS", "LanPaint_DetailerCropRegions"
+    WINDOWS, CALL = "regions", staticmethod(detail.stitch_regions)
+    IMAGE_TIP = "The inpainted regions, at the working resolution, stacked as they were cropped."
     DESCRIPTION = "Stitch the inpainted regions from LanPaint_DetailerCropRegions back into the original image."
-
-    def stitch(self, stitch, image, blend_overlap=9):
-        original = stitch["original"]
-        dev = _hip_device(original)
-        out = detail.stitch_regions(original.to(dev), image.to(dev), stitch["mask"].to(dev), stitch["regions"],
-                                    stitch["labels"].to(dev), blend_overlap, stitch["filter"])
-        return (out.to(original.device),)
 
 
 NODE_CLASS_MAPPINGS = {"LanPaint_DetailerCropRegions": LanPaint_DetailerCropRegions,

@@ -20,7 +20,7 @@ This module has its own NODE_CLASS_MAPPINGS: merge them with the others' (INTEGR
 from __future__ import annotations
 
 from . import _cabi, detail, detail_subjects
-from .detail_nodes import LanPaint_DetailerStitch, _hip_device
+from .detail_nodes import LanPaint_DetailerStitch, _on_device
 from .detail_track_nodes import LanPaint_DetailerCropTrack
 
 
@@ -52,10 +52,7 @@ class LanPaint_DetailerCropSubjects:
 
     def crop(self, image, mask, context=1.5, padding=32, target=1024, multiple_of=8, filter="bicubic", smooth=9, min_area=64,
              max_subjects=4):
-        dev = _hip_device(image)
-        img, m = image.to(dev), mask.to(dev)
-        if m.ndim == 2:
-            m = m.unsqueeze(0)
+        img, m = _on_device(image, mask)
         labels, n, table = detail_subjects.mask_components_frames(detail_subjects._frame_mask(m, img.shape[0], img.shape[1],
                                                                                              img.shape[2]))
         members = detail_subjects.group_subjects((n, table), min_area, min(int(max_subjects), _cabi.LP_DETAIL_MAX_REGIONS))
@@ -70,28 +67,12 @@ class LanPaint_DetailerCropSubjects:
         return (cimg.to(image.device), cmask.to(mask.device), stitch, subjects.subjects)
 
 
-class LanPaint_DetailerStitchSubjects:
+class LanPaint_DetailerStitchSubjects(LanPaint_DetailerStitch):
     """Resample the inpainted windows back and blend them into the original frames, subject after subject."""
-
-    @classmethod
-    def INPUT_TYPES(s):
-        required = dict(LanPaint_DetailerStitch.INPUT_TYPES()["required"])
-        required["stitch"] = ("LANPAINT_STITCH_SUBJECTS", {"tooltip": "From LanPaint_DetailerCropSubjects."})
-        required["image"] = ("IMAGE", {"tooltip": "The inpainted windows, at the working resolution, stacked as they were cropped."})
-        return {"required": required}
-
-    RETURN_TYPES = ("IMAGE",)
-    RETURN_NAMES = ("image",)
-    FUNCTION = "stitch"
-    CATEGORY = "image"
+    STITCH_TYPE, CROP_NODE = "LANPAINT_STITCH_SUBJECTS", "LanPaint_DetailerCropSubjects"
+    WINDOWS, CALL = "subjects", staticmethod(detail_subjects.stitch_subjects)
+    IMAGE_TIP = "The inpainted windows, at the working resolution, stacked as they were cropped."
     DESCRIPTION = "Stitch the inpainted windows from LanPaint_DetailerCropSubjects back into the original frames."
-
-    def stitch(self, stitch, image, blend_overlap=9):
-        original = stitch["original"]
-        dev = _hip_device(original)
-        out = detail_subjects.stitch_subjects(original.to(dev), image.to(dev), stitch["mask"].to(dev), stitch["subjects"],
-                                              stitch["labels"].to(dev), blend_overlap, stitch["filter"])
-        return (out.to(original.device),)
 
 
 NODE_CLASS_MAPPINGS = {"LanPaint_DetailerCropSubjects": LanPaint_DetailerCropSubjects,

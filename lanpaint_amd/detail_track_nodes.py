@@ -18,7 +18,7 @@ This module has its own NODE_CLASS_MAPPINGS: merge them with the others' (INTEGR
 from __future__ import annotations
 
 from . import detail
-from .detail_nodes import LanPaint_DetailerCrop, LanPaint_DetailerStitch, _hip_device
+from .detail_nodes import LanPaint_DetailerCrop, LanPaint_DetailerStitch, _on_device
 
 
 class LanPaint_DetailerCropTrack:
@@ -42,10 +42,7 @@ class LanPaint_DetailerCropTrack:
                    "resolution. Feed the outputs to LanPaint_ImageEncode and the stitch output to LanPaint_DetailerStitchTrack.")
 
     def crop(self, image, mask, context=1.5, padding=32, target=1024, multiple_of=8, filter="bicubic", smooth=9):
-        dev = _hip_device(image)
-        img, m = image.to(dev), mask.to(dev)
-        if m.ndim == 2:
-            m = m.unsqueeze(0)
+        img, m = _on_device(image, mask)
         track = detail.plan_track(detail.mask_bbox_frames(m), img.shape[1], img.shape[2], context, padding, multiple_of, target,
                                   smooth, frames=img.shape[0])
         cimg, cmask = detail.crop_track(img, m, track, filter)
@@ -53,28 +50,12 @@ class LanPaint_DetailerCropTrack:
         return (cimg.to(image.device), cmask.to(mask.device), stitch)
 
 
-class LanPaint_DetailerStitchTrack:
+class LanPaint_DetailerStitchTrack(LanPaint_DetailerStitch):
     """Resample every frame's inpainted window back and blend it into the original where it was cut."""
-
-    @classmethod
-    def INPUT_TYPES(s):
-        required = dict(LanPaint_DetailerStitch.INPUT_TYPES()["required"])
-        required["stitch"] = ("LANPAINT_STITCH_TRACK", {"tooltip": "From LanPaint_DetailerCropTrack."})
-        required["image"] = ("IMAGE", {"tooltip": "The inpainted windows, at the working resolution, one per frame."})
-        return {"required": required}
-
-    RETURN_TYPES = ("IMAGE",)
-    RETURN_NAMES = ("image",)
-    FUNCTION = "stitch"
-    CATEGORY = "image"
+    STITCH_TYPE, CROP_NODE = "LANPAINT_STITCH_TRACK", "LanPaint_DetailerCropTrack"
+    WINDOWS, CALL = "track", staticmethod(detail.stitch_track)
+    IMAGE_TIP = "The inpainted windows, at the working resolution, one per frame."
     DESCRIPTION = "Stitch the inpainted windows from LanPaint_DetailerCropTrack back into the original frames."
-
-    def stitch(self, stitch, image, blend_overlap=9):
-        original = stitch["original"]
-        dev = _hip_device(original)
-        out = detail.stitch_track(original.to(dev), image.to(dev), stitch["mask"].to(dev), stitch["track"], blend_overlap,
-                                  stitch["filter"])
-        return (out.to(original.device),)
 
 
 NODE_CLASS_MAPPINGS = {"LanPaint_DetailerCropTrack": LanPaint_DetailerCropTrack,

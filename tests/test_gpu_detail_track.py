@@ -354,12 +354,14 @@ def test_track_at_video_size_frames_0_40_80_equal_the_per_frame_calls():
 
 
 # ---- the device-side origin clamp, through the C entries ------------------------------------------------------------------------------
-# The header promises for both device tables that "an origin is clamped so that its window lies inside the image"; the Python
+# The header promises for every device table that "an origin is clamped so that its window lies inside the image"; the Python
 # wrappers refuse such tables, so only a raw call reaches the clamp.  Every tensor a window indexes is the middle of one with a
 # guard frame before and after: an origin left unclamped by up to 3 rows still reads and writes allocated memory, and the test
 # fails by value.
 _CLAMP_H, _CLAMP_W, _CLAMP_WIN = 23, 31, (8, 12)
 _CLAMP_ORIGINS = ((-3, -2), (_CLAMP_H - 8 + 3, _CLAMP_W - 12 + 1), (5, 7))
+# two subjects on the same three frames, subject-major: subject 0's row is the table above; each side of each axis is left once
+_CLAMP_SUBJECT_ORIGINS = _CLAMP_ORIGINS + ((2, -1), (-1, _CLAMP_W - 12 + 3), (_CLAMP_H - 8 + 1, 9))
 _GUARD = -7.0
 
 
@@ -394,18 +396,22 @@ def _raw(entry, desc):
 @pytest.mark.parametrize("out_hw", [(8, 12), (16, 20)])
 @pytest.mark.parametrize("c", [1, 3])
 def test_device_origin_tables_are_clamped_in_both_resample_entries(c, out_hw):
+    """The regions and track entries, and lp_detail_resample_subjects, whose table is indexed by the block itself."""
     from lanpaint_amd import _cabi
     assert _clamped(_CLAMP_ORIGINS) == ((0, 0), (15, 19), (5, 7))
+    assert _clamped(_CLAMP_SUBJECT_ORIGINS)[3:] == ((2, 0), (0, 19), (15, 9))
     (h, w), (oh, ow), B = _CLAMP_WIN, out_hw, 3
     _, src = _guarded(B, _CLAMP_H, _CLAMP_W, c, seed=61)
     tables = (_axis_tables(w, ow), _axis_tables(h, oh)) if out_hw != _CLAMP_WIN else None
 
     def run(entry, origins):
         table = torch.tensor(origins, dtype=torch.int32, device=DEV)
-        regions = len(origins) if entry == "lp_detail_resample_regions" else 1
-        whole, dst = _guarded(regions * B, oh, ow, c)
-        if regions > 1:
-            d = _cabi.LpDetailResampleRegionsDesc(B, _CLAMP_H, _CLAMP_W, c, regions, h, w, 0, oh, ow)
+        groups = {"lp_detail_resample_regions": len(origins), "lp_detail_resample_subjects": len(origins) // B}.get(entry, 1)
+        whole, dst = _guarded(groups * B, oh, ow, c)
+        if entry == "lp_detail_resample_regions":
+            d = _cabi.LpDetailResampleRegionsDesc(B, _CLAMP_H, _CLAMP_W, c, groups, h, w, 0, oh, ow)
+        elif entry == "lp_detail_resample_subjects":
+            d = _cabi.LpDetailResampleSubjectsDesc(B, _CLAMP_H, _CLAMP_W, c, groups, h, w, 0, oh, ow)
         else:
             d = _cabi.LpDetailResampleTrackDesc(B, _CLAMP_H, _CLAMP_W, c, h, w, oh, ow)
         d.origins, d.src, d.dst = table.data_ptr(), src.data_ptr(), dst.data_ptr()
@@ -418,8 +424,9 @@ def test_device_origin_tables_are_clamped_in_both_resample_entries(c, out_hw):
         assert bool((dst != _GUARD).all()), entry                        # every element of every window was written
         return whole
 
-    for entry in ("lp_detail_resample_regions", "lp_detail_resample_track"):
-        assert torch.equal(run(entry, _CLAMP_ORIGINS), run(entry, _clamped(_CLAMP_ORIGINS))), entry
+    for entry, origins in (("lp_detail_resample_regions", _CLAMP_ORIGINS), ("lp_detail_resample_track", _CLAMP_ORIGINS),
+                           ("lp_detail_resample_subjects", _CLAMP_SUBJECT_ORIGINS)):
+        assert torch.equal(run(entry, origins), run(entry, _clamped(origins))), entry
 
 
 @pytest.mark.parametrize("k", [1, 17])
@@ -445,5 +452,32 @@ def test_device_origin_table_is_clamped_in_the_track_stitch(c, k):
     inside = torch.zeros(B, _CLAMP_H, _CLAMP_W, dtype=torch.bool)
     for f, (y0, x0) in enumerate(_clamped(_CLAMP_ORIGINS)):
         inside[f, y0:y0 + h, x0:x0 + w] = True
+    changed = (got[1:-1] != original).any(dim=-1).cpu()
+    assert bool(changed.any()) and not bool((changed & ~inside).any())   # the blend happened, and only inside the clamped windows
+
+
+@pytest.mark.parametrize("k", [1, 17])
+@pytest.mark.parametrize("c", [1, 3])
+def test_device_origin_table_is_clamped_in_the_subjects_stitch(c, k):
+    from lanpaint_amd import _cabi
+    (h, w), B, S = _CLAMP_WIN, 3, len(_CLAMP_SUBJECT_ORIGINS) // 3
+    _, original = _guarded(B, _CLAMP_H, _CLAMP_W, c, seed=65)
+    _, mask = _guarded(B, _CLAMP_H, _CLAMP_W, seed=66)
+    detail_imgs = (torch.rand(S * B, h, w, c, generator=_gen(67)) + 2.0).to(DEV)  # [2, 3): a blended element differs from the original
+
+    def run(origins):
+        table = torch.tensor(origins, dtype=torch.int32, device=DEV)
+        whole, out = _guarded(B, _CLAMP_H, _CLAMP_W, c)
+        d = _cabi.LpDetailStitchSubjectsDesc(B, _CLAMP_H, _CLAMP_W, c, S, h, w, k, 0, 0, table.data_ptr(), mask.data_ptr(),
+                                             original.data_ptr(), detail_imgs.data_ptr(), out.data_ptr())       # no labels
+        _raw("lp_detail_stitch_subjects", d)
+        assert bool((whole[0] == _GUARD).all()) and bool((whole[-1] == _GUARD).all())
+        return whole
+
+    got, want = run(_CLAMP_SUBJECT_ORIGINS), run(_clamped(_CLAMP_SUBJECT_ORIGINS))
+    assert torch.equal(got, want)
+    inside = torch.zeros(B, _CLAMP_H, _CLAMP_W, dtype=torch.bool)
+    for i, (y0, x0) in enumerate(_clamped(_CLAMP_SUBJECT_ORIGINS)):                # subject 0's windows and subject 1's
+        inside[i % B, y0:y0 + h, x0:x0 + w] = True
     changed = (got[1:-1] != original).any(dim=-1).cpu()
     assert bool(changed.any()) and not bool((changed & ~inside).any())   # the blend happened, and only inside the clamped windows
