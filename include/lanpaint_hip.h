@@ -1096,6 +1096,71 @@ typedef struct lp_color_apply_desc {
 } lp_color_apply_desc;
 LP_API int lp_color_apply(const lp_color_apply_desc* desc, void* stream);
 
+/* ---- Masked-area fill and outpaint canvas (beyond the reference) ------------------------------------------------------------------
+ * The sampler ignores the latent under the mask, the VAE encoder does not ignore the pixels there: its receptive field reaches
+ * across the mask's edge.  lp_mask_fill replaces the masked pixels by a smooth continuation of the known ones before the
+ * encode; lp_outpaint_pad builds the extended canvas and its mask.  Everything stays on the device; nothing is read back.
+ * Sides are 1..LP_DETAIL_MAX_SIDE, channels 1..LP_DETAIL_MAX_CHANNELS.                                                       */
+#define LP_FILL_TILE 32    /* lp_mask_fill: the side of the tile of a level one block stages                                   */
+#define LP_FILL_SPAN 5     /*               the levels above that tile one launch covers                                       */
+
+/* Push-pull pyramid fill, every image on its own, fp32, every operation rounded on its own.
+ *   image, out  [batch, height, width, channels] fp32, out != image
+ *   mask        [mask_batch, height, width] fp32, mask_batch 1 or batch.  A pixel is masked when mask > 0.5 (a NaN is not), else
+ *               known, as for lp_mask_bbox
+ *   ws          device, lp_fill_ws_bytes(batch, height, width, channels) bytes, 16-byte aligned; contents need not be set
+ * levels  (h_0, w_0) = (height, width), (h_{l+1}, w_{l+1}) = (ceil(h_l / 2), ceil(w_l / 2)) down to (1, 1): levels 0 .. L - 1
+ * pull    k_0 = known, v_0 = image where known (never read elsewhere).  For l = 0 .. L - 2 and coarse pixel (i, j): the children
+ *         (2 i + dy, 2 j + dx) in the order (0,0), (0,1), (1,0), (1,1) that lie inside level l and have k_l = 1 are present,
+ *         n = their number, k_{l+1} = (n > 0), and per channel s = 0, s = s + v_l(child) for each present child in that order,
+ *         v_{l+1} = s / (float)n (IEEE)
+ * empty   k_{L-1} = 0: the image has no known pixel; out = image, bit for bit
+ * push    f_{L-1} = v_{L-1}; for l = L - 2 .. 0: f_l = v_l where k_l = 1, elsewhere the 2x bilinear upsample of f_{l+1} with
+ *         pixel centres aligned and taps clamped.  Per axis, fine index i over a coarse axis of n' entries: i even: i0 = i / 2 - 1,
+ *         weights (0.25, 0.75); i odd: i0 = (i - 1) / 2, weights (0.75, 0.25); taps t0 = clamp(i0, 0, n' - 1),
+ *         t1 = clamp(i0 + 1, 0, n' - 1).  Rows first, r(x') = a0 * f(ty0, x') + a1 * f(ty1, x') for both column taps, then
+ *         up = b0 * r(tx0) + b1 * r(tx1); every product and every sum rounded.
+ * out     a known pixel takes the image's value bit for bit, a masked one f_0.  No output depends on the image under the mask.
+ * The whole job is enqueued on `stream` by this call (csrc/fill_kernel.hip): one launch covers LP_FILL_SPAN levels, so a
+ * 720 x 1280 image (12 levels) takes three launches each way.  The same bits on every run.
+ * LP_E_INVALID: null pointer, batch <= 0, a side or the channel count outside the limits, mask_batch, out == image, a short
+ * workspace; LP_E_ALIGN: ws not 16-byte aligned; LP_E_UNSUPPORTED: batch > 65535.  All checked before any HIP call.           */
+typedef struct lp_fill_desc {
+    int32_t batch, height, width, channels;
+    int32_t mask_batch, reserved0;
+    const float* image;
+    const float* mask;
+    float*       out;
+    void*        ws;
+    int64_t      ws_bytes;
+} lp_fill_desc;
+LP_API int lp_mask_fill(const lp_fill_desc* desc, void* stream);
+
+/* Bytes of lp_mask_fill's workspace: per image and pixel of levels 1 .. L - 1, `channels` fp32 values and one flag byte, the
+ * total rounded up to 16 (and at least 16).  Host arithmetic, no HIP call.  A negative LP_E_* for arguments lp_mask_fill
+ * refuses.                                                                                                                   */
+LP_API int64_t lp_fill_ws_bytes(int32_t batch, int32_t height, int32_t width, int32_t channels);
+
+/* The outpaint canvas and its mask, one launch.  H' = top + height + bottom, W' = left + width + right.
+ *   image      [batch, height, width, channels] fp32
+ *   mask       [mask_batch, height, width] fp32, mask_batch 1 or batch; mask_batch 0: no mask (the pointer is not read)
+ *   image_out  [batch, H', W', channels]: the original inside its rectangle, bit for bit, 0.0 elsewhere
+ *   mask_out   [max(mask_batch, 1), H', W']: max(band, m).  band = 1.0 outside the original's rectangle and inside it within
+ *              `overlap` pixels of a side whose pad is positive, 0.0 elsewhere (hard, not feathered); m = the incoming mask's
+ *              value, soft values kept, 0 outside the rectangle or without a mask; a NaN m gives band
+ * LP_E_INVALID: null pointer, batch <= 0, a side or the channel count outside the limits, mask_batch not 0, 1 or batch, a
+ * negative pad or overlap, all four pads 0, a canvas side above LP_DETAIL_MAX_SIDE; LP_E_UNSUPPORTED: batch > 65535.         */
+typedef struct lp_outpaint_desc {
+    int32_t batch, height, width, channels;
+    int32_t mask_batch, left, top, right;
+    int32_t bottom, overlap, reserved0;
+    const float* image;
+    const float* mask;
+    float*       image_out;
+    float*       mask_out;
+} lp_outpaint_desc;
+LP_API int lp_outpaint_pad(const lp_outpaint_desc* desc, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -267,6 +267,37 @@ def lp_color_ws_bytes(batch, height, width, channels):
     return int(batch) * tiles * (1 + 4 * int(channels)) * 8
 
 
+LP_FILL_TILE, LP_FILL_SPAN = 32, 5
+
+
+class LpFillDesc(C.Structure):
+    _fields_ = [("batch", C.c_int32), ("height", C.c_int32), ("width", C.c_int32), ("channels", C.c_int32),
+                ("mask_batch", C.c_int32), ("reserved0", C.c_int32),
+                ("image", C.c_void_p), ("mask", C.c_void_p), ("out", C.c_void_p), ("ws", C.c_void_p), ("ws_bytes", C.c_int64)]
+
+
+class LpOutpaintDesc(C.Structure):
+    _fields_ = [("batch", C.c_int32), ("height", C.c_int32), ("width", C.c_int32), ("channels", C.c_int32),
+                ("mask_batch", C.c_int32), ("left", C.c_int32), ("top", C.c_int32), ("right", C.c_int32),
+                ("bottom", C.c_int32), ("overlap", C.c_int32), ("reserved0", C.c_int32),
+                ("image", C.c_void_p), ("mask", C.c_void_p), ("image_out", C.c_void_p), ("mask_out", C.c_void_p)]
+
+
+def fill_levels(height, width):
+    """The sides of lp_mask_fill's pyramid levels 0 .. L - 1: halved, rounded up, down to (1, 1)."""
+    levels = [(int(height), int(width))]
+    while levels[-1] != (1, 1):
+        h, w = levels[-1]
+        levels.append(((h + 1) // 2, (w + 1) // 2))
+    return levels
+
+
+def fill_ws_bytes(batch, height, width, channels):
+    """What the C entry lp_fill_ws_bytes returns for arguments inside the limits."""
+    pix = sum(h * w for h, w in fill_levels(height, width)[1:])
+    return max(16, (int(batch) * pix * (4 * int(channels) + 1) + 15) // 16 * 16)
+
+
 def lp_components_ws_bytes(height, width):
     """LP_COMPONENTS_WS_BYTES of include/lanpaint_hip.h."""
     return ((int(height) * int(width) + 1023) // 1024) * 4100
@@ -339,6 +370,9 @@ EXPORTS = {
     "lp_color_stats": (C.c_int, [C.POINTER(LpColorStatsDesc), C.c_void_p]),
     "lp_color_fit": (C.c_int, [C.POINTER(LpColorFitDesc), C.c_void_p]),
     "lp_color_apply": (C.c_int, [C.POINTER(LpColorApplyDesc), C.c_void_p]),
+    "lp_mask_fill": (C.c_int, [C.POINTER(LpFillDesc), C.c_void_p]),
+    "lp_fill_ws_bytes": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "lp_outpaint_pad": (C.c_int, [C.POINTER(LpOutpaintDesc), C.c_void_p]),
 }
 
 

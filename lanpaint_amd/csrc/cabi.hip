@@ -52,6 +52,9 @@ int detail_stitch_subjects_dispatch(const lp_detail_stitch_subjects_desc* d, hip
 int color_stats_dispatch(const lp_color_stats_desc* d, hipStream_t stream);
 int color_fit_dispatch(const lp_color_fit_desc* d, hipStream_t stream);
 int color_apply_dispatch(const lp_color_apply_desc* d, hipStream_t stream);
+int mask_fill_dispatch(const lp_fill_desc* d, hipStream_t stream);
+int64_t fill_ws_bytes(int batch, int height, int width, int channels);
+int outpaint_pad_dispatch(const lp_outpaint_desc* d, hipStream_t stream);
 int reshape_mask_dispatch(const float* src, int sb, int sc, int sf, int sh, int sw, float* dst, int db, int dc, int df,
                           int dh, int dw, int taps, int flags, hipStream_t stream);
 }  // namespace lp
@@ -170,6 +173,14 @@ int lp_color_stats(const lp_color_stats_desc* desc, void* stream) { return lp::c
 int lp_color_fit(const lp_color_fit_desc* desc, void* stream) { return lp::color_fit_dispatch(desc, as_stream(stream)); }
 
 int lp_color_apply(const lp_color_apply_desc* desc, void* stream) { return lp::color_apply_dispatch(desc, as_stream(stream)); }
+
+int lp_mask_fill(const lp_fill_desc* desc, void* stream) { return lp::mask_fill_dispatch(desc, as_stream(stream)); }
+
+int64_t lp_fill_ws_bytes(int32_t batch, int32_t height, int32_t width, int32_t channels) {
+    return lp::fill_ws_bytes(batch, height, width, channels);
+}
+
+int lp_outpaint_pad(const lp_outpaint_desc* desc, void* stream) { return lp::outpaint_pad_dispatch(desc, as_stream(stream)); }
 
 int lp_finalize(const lp_final_desc* desc, void* stream) { return lp::finalize_dispatch(desc, as_stream(stream)); }
 

@@ -1,0 +1,157 @@
+"""Masked-area fill and outpaint canvas: decide what lies under the mask before the image goes into the VAE.
+
+The sampler ignores the latent inside the mask; the VAE encoder does not ignore the pixels there, because its receptive field
+reaches across the mask's edge.  A grey border on an extended canvas, or an unwanted object under an inpaint mask, leaks into the
+known latent beside the edge and comes back as a halo or a seam; with denoise < 1 it is also where the sampler starts.  Both
+functions run on the device (csrc/fill_kernel.hip) and read nothing back.
+
+fill_masked(image, mask) -> image
+        Every masked pixel (mask > 0.5; a NaN is not) is replaced by a smooth continuation of the known ones, every image of the
+        batch on its own, by a push-pull pyramid in fp32 with every operation rounded on its own:
+          levels  (h_0, w_0) = (H, W), then halved and rounded up until (1, 1)
+          pull    a coarse pixel is the mean of its known children -- s = 0, s = s + child in the order (0,0), (0,1), (1,0),
+                  (1,1), then s / n -- and known when it has one
+          push    from the top down, a pixel that is not known takes the 2x bilinear upsample of the level above (pixel centres
+                  aligned, taps clamped, weights 0.25 / 0.75, rows first)
+        Known pixels come back bit for bit; an image with no known pixel comes back unchanged; no output depends on the image
+        under the mask.  include/lanpaint_hip.h (lp_mask_fill) states the rule in full.
+
+plan_outpaint(H, W, left, top, right, bottom, overlap, multiple_of) -> OutpaintPlan
+        The final pads and the canvas size.  Per axis with pads (p0, p1) and M = multiple_of: when the axis is padded and M > 1,
+        the canvas is brought up to the next multiple of M by e = (-(p0 + N + p1)) mod M more pixels -- split e // 2 low and the
+        rest high when both pads are positive, otherwise added to the one positive pad.  An unpadded axis is left alone.
+
+outpaint_pad(image, mask=None, left=0, top=0, right=0, bottom=0, overlap=0, multiple_of=8, fill=True) -> (image, mask)
+        The canvas [B, H', W', C] with the original inside and 0.0 elsewhere, and its mask [Bm, H', W'] = max(band, incoming mask):
+        band is 1.0 outside the original and, inside it, within `overlap` pixels of every padded side (hard, not feathered: the
+        sampler binarises at 0.5, the soft seam is blend_overlap's after the decode).  With `fill`, the canvas's masked area is
+        then filled from the original by fill_masked.
+
+HIP tensors only, no CPU fallback.
+"""
+from __future__ import annotations
+
+import ctypes
+import dataclasses
+
+import torch
+
+from . import _cabi
+from ._util import _as_f32c, raw_stream
+from .detail import _mask3
+
+MAX_SIDE = _cabi.LP_DETAIL_MAX_SIDE
+
+
+@dataclasses.dataclass(frozen=True)
+class OutpaintPlan:
+    left: int
+    top: int
+    right: int
+    bottom: int
+    overlap: int
+    height: int      # of the canvas
+    width: int
+
+
+def _hip(t, what):
+    if not torch.is_tensor(t) or not t.is_cuda:
+        raise RuntimeError(f"lanpaint_amd.fill runs on a HIP device only; no CPU fallback ({what} is not on one)")
+    return t
+
+
+def _image4(t, what):
+    if t.ndim != 4:
+        raise ValueError(f"{what} must be [B, H, W, C], got {tuple(t.shape)}")
+    b, h, w, c = t.shape
+    if min(b, h, w, c) < 1 or max(h, w) > MAX_SIDE or c > _cabi.LP_DETAIL_MAX_CHANNELS or b > 65535:
+        raise ValueError(f"{what} {tuple(t.shape)}: sides 1..{MAX_SIDE}, channels 1..{_cabi.LP_DETAIL_MAX_CHANNELS}, batch 1..65535")
+    return t
+
+
+def _mask_for(mask, image, dev):
+    m = _as_f32c(_mask3(_hip(mask, "mask")).to(dev))
+    if m.shape[0] not in (1, image.shape[0]) or tuple(m.shape[1:]) != tuple(image.shape[1:3]):
+        raise ValueError(f"mask shape {tuple(mask.shape)} does not match image {tuple(image.shape)}")
+    return m
+
+
+def _int(v, what):
+    if not isinstance(v, int) or isinstance(v, bool):
+        raise ValueError(f"{what} must be an integer, got {v!r}")
+    return v
+
+
+def _snap(n, p0, p1, m):
+    if p0 + p1 > 0 and m > 1:
+        e = (-(p0 + n + p1)) % m
+        if p0 > 0 and p1 > 0:
+            p0, p1 = p0 + e // 2, p1 + e - e // 2
+        elif p0 > 0:
+            p0 += e
+        else:
+            p1 += e
+    return p0, p1
+
+
+def plan_outpaint(H, W, left=0, top=0, right=0, bottom=0, overlap=0, multiple_of=8):
+    """The final pads and the canvas size (module docstring).  ValueError: a negative value, multiple_of < 1, all four pads zero,
+    an overlap that leaves no known pixel on an axis, a canvas side above the limit."""
+    for v, what in ((H, "H"), (W, "W"), (left, "left"), (top, "top"), (right, "right"), (bottom, "bottom"), (overlap, "overlap"),
+                    (multiple_of, "multiple_of")):
+        _int(v, what)
+    if H < 1 or W < 1:
+        raise ValueError(f"image sides must be positive, got {H} x {W}")
+    if min(left, top, right, bottom, overlap) < 0:
+        raise ValueError(f"pads and overlap must not be negative, got {(left, top, right, bottom)}, overlap {overlap}")
+    if multiple_of < 1:
+        raise ValueError(f"multiple_of must be at least 1, got {multiple_of}")
+    if left == top == right == bottom == 0:
+        raise ValueError("all four pads are zero: nothing to outpaint")
+    left, right = _snap(W, left, right, multiple_of)
+    top, bottom = _snap(H, top, bottom, multiple_of)
+    for n, p0, p1, axis in ((W, left, right, "width"), (H, top, bottom, "height")):
+        if overlap * ((p0 > 0) + (p1 > 0)) >= n:
+            raise ValueError(f"overlap {overlap} along every padded side leaves no known pixel of the {axis} {n}")
+    height, width = top + H + bottom, left + W + right
+    if max(height, width) > MAX_SIDE:
+        raise ValueError(f"canvas {height} x {width} exceeds the largest side {MAX_SIDE}")
+    return OutpaintPlan(left, top, right, bottom, overlap, height, width)
+
+
+def fill_masked(image, mask):
+    """`image` [B, H, W, C] with its masked pixels filled from the known ones (module docstring).  `mask` is [B, H, W], [1, H, W]
+    or [H, W].  At most six launches on the current stream and no device -> host read."""
+    img = _as_f32c(_image4(_hip(image, "image"), "image"))
+    dev = img.device
+    m = _mask_for(mask, img, dev)
+    b, h, w, c = img.shape
+    lib = _cabi.load()
+    ws_bytes = lib.lp_fill_ws_bytes(b, h, w, c)
+    _cabi.check(min(ws_bytes, 0), "lp_fill_ws_bytes")
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    out = torch.empty_like(img)
+    d = _cabi.LpFillDesc(b, h, w, c, m.shape[0], 0, img.data_ptr(), m.data_ptr(), out.data_ptr(), ws.data_ptr(), ws_bytes)
+    with torch.cuda.device(dev):
+        _cabi.check(lib.lp_mask_fill(ctypes.byref(d), raw_stream(dev)), "lp_mask_fill")
+    return out
+
+
+def outpaint_pad(image, mask=None, left=0, top=0, right=0, bottom=0, overlap=0, multiple_of=8, fill=True):
+    """(canvas [B, H', W', C], mask [Bm, H', W']) on the device (module docstring); the pads are plan_outpaint's."""
+    img = _image4(_hip(image, "image"), "image")
+    b, h, w, c = img.shape
+    plan = plan_outpaint(h, w, left, top, right, bottom, overlap, multiple_of)
+    img = _as_f32c(img)
+    dev = img.device
+    m = _mask_for(mask, img, dev) if mask is not None else None
+    canvas = torch.empty((b, plan.height, plan.width, c), dtype=torch.float32, device=dev)
+    mask_out = torch.empty((m.shape[0] if m is not None else 1, plan.height, plan.width), dtype=torch.float32, device=dev)
+    d = _cabi.LpOutpaintDesc(b, h, w, c, m.shape[0] if m is not None else 0, plan.left, plan.top, plan.right, plan.bottom,
+                             plan.overlap, 0, img.data_ptr(), m.data_ptr() if m is not None else None, canvas.data_ptr(),
+                             mask_out.data_ptr())
+    with torch.cuda.device(dev):
+        _cabi.check(_cabi.load().lp_outpaint_pad(ctypes.byref(d), raw_stream(dev)), "lp_outpaint_pad")
+    if fill:
+        canvas = fill_masked(canvas, mask_out)
+    return canvas, mask_out
