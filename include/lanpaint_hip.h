@@ -351,8 +351,9 @@ typedef struct lp_step_desc {
 #define LP_TUNE_ES_NO_FOLD    (1u << 3)   /* LP_FL_ES_GATED: decision kernel after every launch instead of the folded verdict */
 #define LP_TUNE_ES_NO_ATOMICS (1u << 4)   /* LP_FL_ES: the blocks do not add their sums to the accumulator set (WRONG verdicts: a
                                              measurement switch that prices the atomics)                                    */
-#define LP_CLK_STAMPS 8  /* 0 entry, 1 operand loads issued, 2 noise generated, 3 operands arrived, 4 stop verdict
-                            formed, 5 arithmetic done, 6 stores issued, 7 per-block sums written                */
+#define LP_CLK_STAMPS 9  /* 0 entry, 1 operand loads issued, 2 noise generated, 3 operands arrived, 4 stop verdict
+                            formed, 5 arithmetic done, 6 stores issued, 7 per-block sums written, 8 generator started:
+                            counter and seed in registers (one-element-per-lane launches)                      */
 
 typedef struct lp_final_desc {
     int64_t   n_el;

@@ -27,10 +27,10 @@ def _hipcc():
     raise RuntimeError("hipcc not found (set HIPCC or install ROCm)")
 
 
-def needs_build():
-    if not os.path.exists(OUT):
+def needs_build(out=OUT):
+    if not os.path.exists(out):
         return True
-    t = os.path.getmtime(OUT)
+    t = os.path.getmtime(out)
     deps = [os.path.join(CSRC, s) for s in SOURCES] + HEADERS
     return any(os.path.getmtime(p) > t for p in deps)
 
@@ -42,11 +42,11 @@ def build(force=False, verbose=True, shader_clock=False, trace=False):
     if trace:
         out = os.path.join(ROOT, "build", "liblanpaint_hip_trace.so")
         os.makedirs(os.path.dirname(out), exist_ok=True)
-        return _compile(out, ["-DLP_TRACE_INSTANTIATIONS"], verbose)
+        return _compile(out, ["-DLP_TRACE_INSTANTIATIONS"], verbose) if force or needs_build(out) else out
     if shader_clock:
         out = os.path.join(ROOT, "build", "liblanpaint_hip_clk.so")
         os.makedirs(os.path.dirname(out), exist_ok=True)
-        return _compile(out, ["-DLP_SHADER_CLOCK"], verbose)
+        return _compile(out, ["-DLP_SHADER_CLOCK"], verbose) if force or needs_build(out) else out
     if not force and not needs_build():
         return OUT
     return _compile(OUT, [], verbose)

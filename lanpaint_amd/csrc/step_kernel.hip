@@ -319,6 +319,13 @@ __device__ __forceinline__ uint64_t clk_real() {
     const bool clk_on = d_arg.clk_out && threadIdx.x == 0 && blockIdx.y == 0 && (blockIdx.x == 0 || blockIdx.x == gridDim.x - 1); \
     if (clk_on) { clk_t[0] = clk_now(); clk_r0 = clk_real(); }
 #define LP_CLK(k) if (clk_on) clk_t[k] = clk_now();
+// a stamp that is taken once the scalars a and b have arrived (what the Philox rounds wait for: counter and seed)
+__device__ __forceinline__ uint64_t clk_when(uint32_t a, uint32_t b) {
+    uint64_t t;
+    asm volatile("s_memtime %0\n s_waitcnt lgkmcnt(0)" : "=s"(t) : "s"(a), "s"(b) : "memory");
+    return t;
+}
+#define LP_CLK_WHEN(k, a, b) if (clk_on) clk_t[k] = clk_when(a, b);
 #define LP_CLK_LOADS(k) if (clk_on) clk_t[k] = clk_after_loads();
 #define LP_CLK_FLUSH                                                                                                 \
     if (clk_on) {                                                                                                    \
@@ -330,6 +337,7 @@ __device__ __forceinline__ uint64_t clk_real() {
 #else
 #define LP_CLK_DECL
 #define LP_CLK(k)
+#define LP_CLK_WHEN(k, a, b)
 #define LP_CLK_LOADS(k)
 #define LP_CLK_FLUSH
 #endif
@@ -524,7 +532,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((ES == 2 &&
     // (Philox kernels without early stop only: the early-stop kernels sit at their register limits -- the changed schedule sent one of
     // them to scratch memory -- and the torch-stream kernels, whose two Philox4x32 blocks per lane the scheduler then interleaves
     // further, went from 52-64 to 65-74 VGPRs, i.e. below 8 waves per SIMD)
-    constexpr bool HOT = PH != 0 && ES == 0 && RNG == 0;
+    // (round 21: the torch-stream kernels at ONE element per lane are hot as well -- 42 VGPRs at one wave per SIMD, registers
+    // decide nothing there, and every run-time test in front of the generator is a scalar round trip of its own, see TS below)
+    constexpr bool HOT = PH != 0 && ES == 0 && (RNG == 0 || (RNG == 1 && VEC == 1));
+    // TS: the image-size torch-stream think kernels (one element per lane, phase-specialised, no early stop).  A launch of
+    // theirs is ~1.4 us of dependent latency and nothing else, so they are written for ONE wait on the argument segment:
+    // the generator state of a replayed graph comes through a scalar load next to the descriptor's fields, nothing is read
+    // behind a run-time test of its own, and the draws assume one ATen thread per element (n_el <= rng_bg; plan_phase sends
+    // every other descriptor to the run-time-phase kernel, likewise one that carries an I/O table).
+    constexpr bool TS = HOT && RNG == 1 && VEC == 1;
+    static_assert(!TS || (!ST && (PH & LP_PH_REPLACE) == 0), "TS: think launches only");
     const bool given = HOT ? false : (fl & LP_FL_X0S_GIVEN) != 0;
     const int x0dt = X0W == 4 ? static_cast<int>(DT_F32) : x0_dtype(fl), xindt = xin_dtype(fl);
     const int64_t groups = ST ? static_cast<int64_t>(d.rng_bg) : d.el_per_row / VEC;
@@ -644,7 +661,19 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((ES == 2 &&
     // device-side generator state of a replayed graph: with the pointer preloaded its load starts here
     uint64_t rng_w0 = 0, rng_w1 = 0;
     bool rng_have = false;
-    if constexpr (SMALL) {
+    if constexpr (TS) {
+        // The words were written by an earlier launch of the graph and never by this one: a SCALAR load through the constant
+        // address space, in flight next to the descriptor's own fields and waited for with them -- once, behind the last operand
+        // load.  (As a vector load the seed had to become wave-uniform on the spot: s_waitcnt vmcnt(0) + v_readfirstlane in
+        // front of the loads of x_t, C and the heads -- a whole memory round trip per replayed launch.)  No branch on the
+        // pointer: without one (eager launches, the state by value) the load reads the coefficient row and is discarded.
+        typedef const __attribute__((address_space(4))) uint64_t* state_words;
+        rng_have = d.rng_offset_ptr != nullptr;
+        const state_words sw = (state_words)(rng_have ? d.rng_offset_ptr : reinterpret_cast<const uint64_t*>(d.coef));
+        const uint64_t w0 = sw[0], w1 = sw[1];
+        rng_w0 = rng_have ? w0 : 0ull;
+        rng_w1 = rng_have ? w1 : 0ull;
+    } else if constexpr (SMALL) {
         if (d.rng_offset_ptr) {
             rng_w0 = d.rng_offset_ptr[0];
             rng_w1 = d.rng_offset_ptr[1];
@@ -904,8 +933,20 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((ES == 2 &&
             }
         }
         // ---- from here on the descriptor proper is needed (the first wait for the argument segment) ----
+        if constexpr (TS) {
+            // ONE wait: everything this kernel reads from the argument segment beyond the preloaded dwords, and the generator
+            // state, is in registers HERE -- so all of it is requested in front of this point and arrives in one round trip,
+            // under the operand loads issued above.  (Left to the uses, the reads sat behind three waits in a row: mask and
+            // y pointers; then the generator's seed, offset and increment; then the rest.)
+            asm volatile("" ::"s"(rng_w0), "s"(rng_w1), "s"(d.rng_offset), "s"(d.rng_seed), "s"(d.rng_inc),
+                         "s"(reinterpret_cast<uintptr_t>(d.mask)), "s"(reinterpret_cast<uintptr_t>(d.y)),
+                         "s"(reinterpret_cast<uintptr_t>(d.x_in)), "s"(reinterpret_cast<uintptr_t>(d.x0s)),
+                         "s"(HARD ? uintptr_t(0) : reinterpret_cast<uintptr_t>(d.corr_el)), "s"(d.lambda),
+                         "s"(d.one_plus_lambda), "s"(d.cfg_scale), "s"(d.cfg_scale_big));
+        }
         if constexpr (SMALL) load_mask_raw<VEC>(d.mask, mfl, i, m_raw);
-        const bool has_corr = d.corr_el != nullptr && !given;
+        // (TS: a bit-packed mask never comes with the audio correction -- plan_phase -- so its pointer is not even read)
+        const bool has_corr = (TS && HARD) ? false : (d.corr_el != nullptr && !given);
         const bool host_post = HOT ? false : d.xi_post != nullptr, host_pre = HOT ? false : d.xi_pre != nullptr;
         const bool need_rng = (post && !host_post) || ((ph & LP_PH_PRE_HALF) && !host_pre);
         if (post) {
@@ -974,10 +1015,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((ES == 2 &&
             }
         }
         // per-call I/O pointers for the launches of this sigma call that live in a captured graph (lp_finalize)
+        // (TS: the table belongs to the replace launch; a think launch that carries one takes the run-time-phase kernel)
+        if constexpr (!TS) {
         if (d.io_table_out && el_bx == 0 && blockIdx.y == 0 && threadIdx.x == 0) {
             d.io_table_out[0] = d.io_table_val[0];
             d.io_table_out[1] = d.io_table_val[1];
             if (d.io_valid) d.io_table_out[2] = 1ull;      // (not on a speculated call: there the sigma rule owns the word)
+        }
         }
         if constexpr (PH == 0 || (PH & LP_PH_REPLACE) != 0) {
             if (d.es_reset && d.es && el_bx == 0 && blockIdx.y == 0) {
@@ -1005,6 +1049,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((ES == 2 &&
             if (rng_have) {
                 seq += rng_w0;
                 if (torch_kind) seed = rng_w1;
+            }
+            if constexpr (SMALL) {
+                LP_CLK_WHEN(8, static_cast<uint32_t>(seq), static_cast<uint32_t>(seed))
             }
             if (torch_kind) {
                 // torch.randn_like(x_t) twice, in the reference's order: the POST draw, then the PRE draw
@@ -1044,7 +1091,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((ES == 2 &&
                         xi_b[0] = q.x; xi_b[1] = q.y; xi_b[2] = q.z; xi_b[3] = q.w;
                     }
                 } else {
-                    const bool small = d.n_el <= static_cast<int64_t>(d.rng_bg);     // one ATen thread per element
+                    // one ATen thread per element; TS: at compile time (plan_phase) -- neither n_el nor bg is read, both draws
+                    // are one straight-line block whose multiply chains interleave, and the last Philox round and Box-Muller
+                    // form only what element 0 of the thread takes (c.x, c.y; the sine branch)
+                    const bool small = TS ? true : d.n_el <= static_cast<int64_t>(d.rng_bg);
 #pragma unroll
                     for (int k = 0; k < VEC; ++k) {
                         const uint64_t li = static_cast<uint64_t>(elem_index(i, k));
@@ -1088,6 +1138,20 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((ES == 2 &&
             }
         }
 
+        if constexpr (TS) {
+            // The heads are looked at BEHIND the draws: one head serving both (x0_big == x0) and fused CFG combine them with
+            // nothing but the loaded words, and the scheduler otherwise puts that -- with its wait for the loads -- in front
+            // of the Philox rounds, which then start after the memory latency instead of under it.  (The scheduling barrier keeps
+            // the widening of a 16-bit head word, which feeds the asm, from being hoisted over the rounds all the same.)
+            __builtin_amdgcn_sched_barrier(0);
+            if constexpr (X0W == 2) {        // (as the 16 bits that were loaded: a 32-bit operand is widened first, in front of the rounds)
+                uint16_t h = static_cast<uint16_t>(x0_raw.w[0]);
+                asm volatile("" : "+v"(h) : "v"(xi_a[0]));
+                x0_raw.w[0] = h;
+            } else {
+                asm volatile("" : "+v"(x0_raw.w[0]) : "v"(xi_a[0]));
+            }
+        }
         if constexpr (ES == 2 && VEC == 4) {
             // exactly the buffers the metric compares against -- the previous x0s, the drift anchor while one is held, the ring
             // bits of a 4-D latent -- now that the verdict (formed behind the operand loads, above) says which they are
@@ -1658,7 +1722,11 @@ static void plan_phase(const lp_step_desc& d, StepPlan* p) {
     const bool strided = VEC == 4 && rng_torch && !d.xi_post && !d.xi_pre && d.n_el > static_cast<int64_t>(d.rng_bg) &&
                          (d.rng_bg % kBlock) == 0 &&           /* a block is 256 whole ATen threads */
                          (d.rows == 1 || d.el_per_row >= 2 * static_cast<int64_t>(d.rng_bg)) && st_segments(d) != 0;
-    if (!pair_ok || rare) return hard ? plan_kernel<VEC, MODE_HARD, 0>(d, p) : plan_kernel<VEC, MODE_ROW, 0>(d, p);
+    // the image-size torch-stream think kernels (lp_step_kernel, TS) draw for one ATen thread per element and write no I/O
+    // table: a descriptor past ATen's grid (n_el > bg at one element per lane: a hand-made bg, LP_TUNE_VEC1) or a think launch
+    // that carries the table (the engine clears it, the replace launch owns it) keeps the run-time-phase kernel
+    const bool ts_rare = VEC == 1 && rng_torch && (d.n_el > static_cast<int64_t>(d.rng_bg) || d.io_table_out != nullptr);
+    if (!pair_ok || rare || ts_rare) return hard ? plan_kernel<VEC, MODE_HARD, 0>(d, p) : plan_kernel<VEC, MODE_ROW, 0>(d, p);
     if (hard) {
         switch (d.phases) {
             case S | P | E: return plan_hot<VEC, MODE_HARD, S | P | E>(d, strided, x0_half, rng_torch, p);   // steady state

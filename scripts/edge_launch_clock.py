@@ -3,7 +3,9 @@
 launch (replace + coefficient table), the first think iteration, a steady one and the last one, at one workload's shape
 with the engine's default noise stream.  Same instrumented library and stamp layout as scripts/shader_clock.py (thread 0 of
 the first and of the last block; for the fused replace launch the first block is its table block).  Prints, per launch,
-the wall time per launch of the replayed graph and the time from block entry to each stamp.
+the wall time per launch of the replayed graph and the time from block entry to each stamp.  The think launches read the
+generator state from the device words the replace launch publishes, as every launch of a replayed sigma call does (a launch
+without a state pointer -- scripts/shader_clock.py -- does not show what that read costs).
 
     python scripts/edge_launch_clock.py [workload=c2_sdxl]
 """
@@ -23,14 +25,15 @@ import bench                                         # noqa: E402
 from lanpaint_amd import _cabi                       # noqa: E402
 
 STAMPS = ["kernel entry", "operand loads issued", "noise generated", "operands arrived", "stop verdict formed",
-          "arithmetic done", "stores issued", "block sums written"]      # (scripts/shader_clock.py; table block: 5 = table built)
+          "arithmetic done", "stores issued", "block sums written",      # (scripts/shader_clock.py; table block: 5 = table built)
+          "generator started"]                                           # counter and seed in registers (one element per lane)
 
 
 def descriptors(wl, dev):
     """replace (fused table), first, steady, last -- one descriptor each on shared buffers of the workload's shape"""
     R, F, S, P, E, K = (_cabi.LP_PH_REPLACE, _cabi.LP_PH_POST_FIRST, _cabi.LP_PH_POST_STEADY, _cabi.LP_PH_PRE_HALF,
                         _cabi.LP_PH_EMIT, _cabi.LP_PH_COEFFS)
-    out, keep = [], []
+    out, keep, state = [], [], None
     for name, ph in (("replace", R | E | K), ("first", F | P | E), ("steady", S | P | E), ("last", S | E)):
         d, k, n_el = bench.standalone_step(_cabi, wl, dev, ph, rng="torch")
         if ph & K:
@@ -41,6 +44,8 @@ def descriptors(wl, dev):
             state = torch.zeros(2, dtype=torch.int64, device=dev)
             d.rng_state_out, d.rng_state_val[0], d.rng_state_val[1] = state.data_ptr(), 0, 1234
             k = k + (state,)
+        elif state is not None:
+            d.rng_offset_ptr = state.data_ptr()
         out.append((name, d))
         keep.append(k)
     return out, keep, n_el

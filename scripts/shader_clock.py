@@ -24,7 +24,7 @@ from lanpaint_amd import _cabi                       # noqa: E402
 from lanpaint_amd.lanpaint import _DeviceStop        # noqa: E402
 
 STAMPS = ["kernel entry", "operand loads issued", "noise generated", "operands arrived", "stop verdict formed",
-          "arithmetic done", "stores issued", "block sums written"]
+          "arithmetic done", "stores issued", "block sums written", "generator started"]
 
 
 def run(wl, early_stop, half=False, rng="philox"):
