@@ -1162,6 +1162,59 @@ typedef struct lp_outpaint_desc {
 } lp_outpaint_desc;
 LP_API int lp_outpaint_pad(const lp_outpaint_desc* desc, void* stream);
 
+/* ---- Multiband blend (beyond the reference) -------------------------------------------------------------------------------------
+ * Every path that puts a generated image back into the original ends in lp_mask_blend's rule: one feather of at most 51 pixels.
+ * What low-frequency difference a VAE round trip, an outpaint continuation or a detailed crop leaves is squeezed into that one
+ * band.  lp_multiband_blend is the Burt-Adelson blend: every frequency band is blended over a width in proportion to its
+ * wavelength.  It goes after any stitch or decode (stitch hard, blend_overlap = 1, then blend original and stitched through
+ * the mask).  Everything stays on the device; nothing is read back.
+ *   image1 (a), image2 (b), out  [batch, height, width, channels] fp32, finite; out != image1, out != image2
+ *   mask                         [mask_batch, height, width] fp32, mask_batch 1 or batch
+ *   levels                       >= 0
+ *   ws                           device, lp_multiband_ws_bytes(batch, height, width, channels, levels) bytes, 16-byte aligned;
+ *                                contents need not be set
+ * Every image of the batch is independent of the others.  Every product, sum and difference below is one fp32 operation
+ * rounded on its own; nothing is fused.
+ * levels    (h_0, w_0) = (height, width), (h_{l+1}, w_{l+1}) = (ceil(h_l / 2), ceil(w_l / 2)).  The level count n is the smaller
+ *           of `levels` and the number of halvings until (1, 1); a 1 x 1 image has n = 0.
+ * weight    W_0 = (m > 0) ? min(m, 1) : 0; a NaN mask value gives 0.  The soft mask is used as given: no binarisation, no
+ *           dilation.
+ * diff      D_0 = b - a.
+ * REDUCE    level l -> l + 1, separable, axis 0 (rows) first over the full width, then axis 1.  Along an axis of length N,
+ *           output i reads inputs 2 i - 2 .. 2 i + 2, each index clamped to [0, N - 1]:
+ *           s = 0.0625 * v[-2]; s = s + 0.25 * v[-1]; s = s + 0.375 * v[0]; s = s + 0.25 * v[+1]; s = s + 0.0625 * v[+2],
+ *           in that order.  D_{l+1} = REDUCE(D_l) and W_{l+1} = REDUCE(W_l) for l < n.
+ * EXPAND    level l + 1 -> the size of level l, axis 0 first (giving [h_l, w_{l+1}]), then axis 1.  Along an axis, output i has
+ *           p = i / 2 (rounded down), coarse indices clamped to the coarse length.  i even: e = 0.125 * c[p - 1];
+ *           e = e + 0.75 * c[p]; e = e + 0.125 * c[p + 1].  i odd: 0.5 * c[p] + 0.5 * c[p + 1].
+ * collapse  R_n = W_n * D_n.  For l = n - 1 .. 0: Lap_l = D_l - EXPAND(D_{l+1}), R_l = EXPAND(R_{l+1}) + W_l * Lap_l (the
+ *           product first, then the sum with the expansion on the left).  out = a + R_0.  levels = 0 is a + W_0 * (b - a).
+ * What follows from the rule: image1 == image2 gives image1 bit for bit whatever the mask; an all-zero mask gives image1 bit
+ * for bit (inputs that are not -0); a pixel whose Chebyshev distance to every pixel with W_0 > 0 exceeds 2^(n+2) - 4 is image1
+ * bit for bit (REDUCE carries weight out by 2 * 2^l per level, EXPAND by 2^l): levels = 5 touches nothing further than 124
+ * pixels from the mask.
+ * The whole job is enqueued on `stream` by this call (csrc/multiband_kernel.hip): n reduce launches and max(n, 1) collapse
+ * launches.  Level 0 is never stored, R_n is formed where it is read.  The same bits on every run.
+ * LP_E_INVALID: null pointer, batch <= 0, a side or the channel count outside the limits (1..LP_DETAIL_MAX_SIDE,
+ * 1..LP_DETAIL_MAX_CHANNELS), mask_batch, levels < 0, out == image1 or image2, a short workspace; LP_E_ALIGN: ws not 16-byte
+ * aligned; LP_E_UNSUPPORTED: batch > 65535.  All checked before any HIP call.                                                 */
+typedef struct lp_multiband_desc {
+    int32_t batch, height, width, channels;
+    int32_t mask_batch, levels;
+    const float* image1;
+    const float* image2;
+    const float* mask;
+    float*       out;
+    void*        ws;
+    int64_t      ws_bytes;
+} lp_multiband_desc;
+LP_API int lp_multiband_blend(const lp_multiband_desc* desc, void* stream);
+
+/* Bytes of lp_multiband_blend's workspace: batch * sum over l = 1 .. n of h_l * w_l * (2 * channels + 1) * 4 -- per image and
+ * pixel of levels 1 .. n, D with `channels` floats, W with one and R with `channels` -- rounded up to 16 (and at least 16).
+ * Host arithmetic, no HIP call.  A negative LP_E_* for arguments lp_multiband_blend refuses.                                */
+LP_API int64_t lp_multiband_ws_bytes(int32_t batch, int32_t height, int32_t width, int32_t channels, int32_t levels);
+
 #ifdef __cplusplus
 }
 #endif

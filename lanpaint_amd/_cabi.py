@@ -298,6 +298,28 @@ def fill_ws_bytes(batch, height, width, channels):
     return max(16, (int(batch) * pix * (4 * int(channels) + 1) + 15) // 16 * 16)
 
 
+class LpMultibandDesc(C.Structure):
+    _fields_ = [("batch", C.c_int32), ("height", C.c_int32), ("width", C.c_int32), ("channels", C.c_int32),
+                ("mask_batch", C.c_int32), ("levels", C.c_int32),
+                ("image1", C.c_void_p), ("image2", C.c_void_p), ("mask", C.c_void_p), ("out", C.c_void_p), ("ws", C.c_void_p),
+                ("ws_bytes", C.c_int64)]
+
+
+def multiband_levels(height, width, levels):
+    """The sides of lp_multiband_blend's pyramid levels 0 .. n: halved, rounded up, `levels` times or until (1, 1)."""
+    sizes = [(int(height), int(width))]
+    while len(sizes) <= int(levels) and sizes[-1] != (1, 1):
+        h, w = sizes[-1]
+        sizes.append(((h + 1) // 2, (w + 1) // 2))
+    return sizes
+
+
+def multiband_ws_bytes(batch, height, width, channels, levels):
+    """What the C entry lp_multiband_ws_bytes returns for arguments inside the limits."""
+    pix = sum(h * w for h, w in multiband_levels(height, width, levels)[1:])
+    return max(16, (int(batch) * pix * (2 * int(channels) + 1) * 4 + 15) // 16 * 16)
+
+
 def lp_components_ws_bytes(height, width):
     """LP_COMPONENTS_WS_BYTES of include/lanpaint_hip.h."""
     return ((int(height) * int(width) + 1023) // 1024) * 4100
@@ -373,6 +395,8 @@ EXPORTS = {
     "lp_mask_fill": (C.c_int, [C.POINTER(LpFillDesc), C.c_void_p]),
     "lp_fill_ws_bytes": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     "lp_outpaint_pad": (C.c_int, [C.POINTER(LpOutpaintDesc), C.c_void_p]),
+    "lp_multiband_blend": (C.c_int, [C.POINTER(LpMultibandDesc), C.c_void_p]),
+    "lp_multiband_ws_bytes": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
 }
 
 
