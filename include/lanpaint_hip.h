@@ -1215,6 +1215,71 @@ LP_API int lp_multiband_blend(const lp_multiband_desc* desc, void* stream);
  * Host arithmetic, no HIP call.  A negative LP_E_* for arguments lp_multiband_blend refuses.                                */
 LP_API int64_t lp_multiband_ws_bytes(int32_t batch, int32_t height, int32_t width, int32_t channels, int32_t levels);
 
+/* ---- Mask refine (beyond the reference) ---------------------------------------------------------------------------------------
+ * Every node after the sampler takes the mask as given, and the mask is what nobody helps the user with: a painted blob, or the
+ * SDF morph of two blobs, follows the subject's centroid and not its outline.  lp_mask_refine is the colour guided filter (He,
+ * Sun, Tang 2013) with the image as the guide: it pulls the mask's edge onto the nearest edge of the image underneath.  It goes
+ * in front of the encode, a Detailer crop, the mask fill and the multiband blend, and behind the video mask editor (every frame
+ * with that frame as its guide).  Everything stays on the device; nothing is read back.
+ *   guide   [batch, height, width, channels] fp32; channels 1 is a grey guide (one guide plane, a 1 x 1 system), channels >= 3
+ *           uses the first three, channels 2 is refused
+ *   mask    [mask_batch, height, width] fp32, mask_batch 1 or batch
+ *   out     [batch, height, width] fp32; out != guide, out != mask
+ *   radius  r in 1..LP_REFINE_MAX_RADIUS;  eps in [1e-6, 1], in units of the [0, 1] image scale, squared
+ *   ws      device, lp_refine_ws_bytes(batch, height, width, channels, radius) bytes, 16-byte aligned; contents need not be set
+ * Every image of the batch is independent of the others.
+ * codes     For a guide or mask value v: t = (v > 0) ? min(v, 1) : 0 (a NaN gives 0); code = (int)(t * 255.0f + 0.5f), the fp32
+ *           product and the fp32 sum each rounded on its own (no FMA), then truncated.  G_c are the guide's codes (c = 0, 1, 2;
+ *           a grey guide has G_0 only), P the mask's.
+ * stage 1   The window of pixel (y, x) is the (2r + 1)-square around it cut at the image border (not clamped, not reflected),
+ *           n its pixel count.  S_c = sum G_c, S_p = sum P, S_cp = sum G_c * P, S_cd = sum G_c * G_d for c <= d, over the
+ *           window: exact integers, at most 129^2 * 255^2 = 1 082 081 025 < 2^31, so the order of summation is free.
+ * stage 2   Per pixel, in fp64, every operation rounded on its own, a product always before the sum or difference it goes
+ *           into, sums from left to right:
+ *             C_c  = n * S_cp - S_c * S_p,  V_cd = n * S_cd - S_c * S_d      (exact integers below 2^53)
+ *             R    = (n * n) * (eps * 65025.0)
+ *             m00 = V_00 + R, m11 = V_11 + R, m22 = V_22 + R, m01 = V_01, m02 = V_02, m12 = V_12
+ *             c00 = m11 * m22 - m12 * m12   c01 = m02 * m12 - m01 * m22   c02 = m01 * m12 - m02 * m11
+ *             c11 = m00 * m22 - m02 * m02   c12 = m01 * m02 - m00 * m12   c22 = m00 * m11 - m01 * m01
+ *             det = (m00 * c00 + m01 * c01) + m02 * c02
+ *             a_0 = ((c00 * C_0 + c01 * C_1) + c02 * C_2) / det
+ *             a_1 = ((c01 * C_0 + c11 * C_1) + c12 * C_2) / det
+ *             a_2 = ((c02 * C_0 + c12 * C_1) + c22 * C_2) / det
+ *             if det is not > 0: a_0 = a_1 = a_2 = 0
+ *             b   = (S_p - ((a_0 * S_0 + a_1 * S_1) + a_2 * S_2)) / n
+ *           A grey guide: det = m00, a_0 = C_0 / det (0 if det is not > 0), b = (S_p - a_0 * S_0) / n.
+ *           a_c and b are then rounded to fp32: the workspace holds (a_0, a_1, a_2, b) per pixel, 16 bytes (a grey guide leaves
+ *           a_1 = a_2 = 0).
+ * stage 3   A_c and B are the sums of a_c and b over the same window, in fp64: first the sum over the window's columns in
+ *           ascending x for every row of the window, starting from +0.0, then the sum of those row sums in ascending y, starting
+ *           from +0.0.  Terms outside the image are skipped (adding +0.0 for them gives the same bits).  Then
+ *             t = A_0 * G_0; t = t + A_1 * G_1; t = t + A_2 * G_2; t = t + B; t = t / n; t = t / 255.0
+ *           (a grey guide: t = A_0 * G_0; t = t + B; ...), and out = (float)min(max(t, 0), 1).
+ * What follows from the rule: an all-zero mask gives exactly 0 and an all-one mask exactly 1.0 whatever the guide; a pixel whose
+ * Chebyshev distance to every pixel with P > 0 exceeds 2r is exactly 0, and exactly 1.0 when it is that far from every pixel
+ * with P < 255; a constant guide gives the mask box-blurred twice.  The same bits on every run.
+ * The whole job is enqueued on `stream` by this call (csrc/refine_kernel.hip): two launches, one for stages 1 and 2 and one for
+ * stage 3.  No floating-point atomics.
+ * LP_E_INVALID: null pointer, batch <= 0, a side outside 1..LP_DETAIL_MAX_SIDE, channels 2, < 1 or > LP_DETAIL_MAX_CHANNELS,
+ * radius outside 1..LP_REFINE_MAX_RADIUS, eps outside [1e-6, 1] or NaN, mask_batch, out == guide or mask, a short workspace;
+ * LP_E_ALIGN: ws not 16-byte aligned; LP_E_UNSUPPORTED: batch > 65535.  All checked before any HIP call.                      */
+#define LP_REFINE_MAX_RADIUS 64
+typedef struct lp_refine_desc {
+    int32_t batch, height, width, channels;
+    int32_t mask_batch, radius;
+    double       eps;
+    const float* guide;
+    const float* mask;
+    float*       out;
+    void*        ws;
+    int64_t      ws_bytes;
+} lp_refine_desc;
+LP_API int lp_mask_refine(const lp_refine_desc* desc, void* stream);
+
+/* Bytes of lp_mask_refine's workspace: batch * height * width * 16 -- (a_0, a_1, a_2, b) as fp32 per pixel.  Host arithmetic,
+ * no HIP call.  A negative LP_E_* for arguments lp_mask_refine refuses.                                                       */
+LP_API int64_t lp_refine_ws_bytes(int32_t batch, int32_t height, int32_t width, int32_t channels, int32_t radius);
+
 #ifdef __cplusplus
 }
 #endif

@@ -320,6 +320,20 @@ def multiband_ws_bytes(batch, height, width, channels, levels):
     return max(16, (int(batch) * pix * (2 * int(channels) + 1) * 4 + 15) // 16 * 16)
 
 
+LP_REFINE_MAX_RADIUS = 64
+
+
+class LpRefineDesc(C.Structure):
+    _fields_ = [("batch", C.c_int32), ("height", C.c_int32), ("width", C.c_int32), ("channels", C.c_int32),
+                ("mask_batch", C.c_int32), ("radius", C.c_int32), ("eps", C.c_double),
+                ("guide", C.c_void_p), ("mask", C.c_void_p), ("out", C.c_void_p), ("ws", C.c_void_p), ("ws_bytes", C.c_int64)]
+
+
+def refine_ws_bytes(batch, height, width, channels, radius):
+    """What the C entry lp_refine_ws_bytes returns for arguments inside the limits: (a_0, a_1, a_2, b) as fp32 per pixel."""
+    return int(batch) * int(height) * int(width) * 16
+
+
 def lp_components_ws_bytes(height, width):
     """LP_COMPONENTS_WS_BYTES of include/lanpaint_hip.h."""
     return ((int(height) * int(width) + 1023) // 1024) * 4100
@@ -397,6 +411,8 @@ EXPORTS = {
     "lp_outpaint_pad": (C.c_int, [C.POINTER(LpOutpaintDesc), C.c_void_p]),
     "lp_multiband_blend": (C.c_int, [C.POINTER(LpMultibandDesc), C.c_void_p]),
     "lp_multiband_ws_bytes": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "lp_mask_refine": (C.c_int, [C.POINTER(LpRefineDesc), C.c_void_p]),
+    "lp_refine_ws_bytes": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
 }
 
 

@@ -57,6 +57,8 @@ int64_t fill_ws_bytes(int batch, int height, int width, int channels);
 int outpaint_pad_dispatch(const lp_outpaint_desc* d, hipStream_t stream);
 int multiband_blend_dispatch(const lp_multiband_desc* d, hipStream_t stream);
 int64_t multiband_ws_bytes(int batch, int height, int width, int channels, int levels);
+int mask_refine_dispatch(const lp_refine_desc* d, hipStream_t stream);
+int64_t refine_ws_bytes(int batch, int height, int width, int channels, int radius);
 int reshape_mask_dispatch(const float* src, int sb, int sc, int sf, int sh, int sw, float* dst, int db, int dc, int df,
                           int dh, int dw, int taps, int flags, hipStream_t stream);
 }  // namespace lp
@@ -188,6 +190,12 @@ int lp_multiband_blend(const lp_multiband_desc* desc, void* stream) { return lp:
 
 int64_t lp_multiband_ws_bytes(int32_t batch, int32_t height, int32_t width, int32_t channels, int32_t levels) {
     return lp::multiband_ws_bytes(batch, height, width, channels, levels);
+}
+
+int lp_mask_refine(const lp_refine_desc* desc, void* stream) { return lp::mask_refine_dispatch(desc, as_stream(stream)); }
+
+int64_t lp_refine_ws_bytes(int32_t batch, int32_t height, int32_t width, int32_t channels, int32_t radius) {
+    return lp::refine_ws_bytes(batch, height, width, channels, radius);
 }
 
 int lp_finalize(const lp_final_desc* desc, void* stream) { return lp::finalize_dispatch(desc, as_stream(stream)); }
