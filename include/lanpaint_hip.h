@@ -1280,6 +1280,59 @@ LP_API int lp_mask_refine(const lp_refine_desc* desc, void* stream);
  * no HIP call.  A negative LP_E_* for arguments lp_mask_refine refuses.                                                       */
 LP_API int64_t lp_refine_ws_bytes(int32_t batch, int32_t height, int32_t width, int32_t channels, int32_t radius);
 
+/* ---- Video mask stabilize (beyond the reference) --------------------------------------------------------------------------------
+ * A per-frame mask that comes from a segmenter, or was painted frame by frame, flickers: its edge jitters by a pixel or two from
+ * frame to frame, and single frames come back empty or carry a stray blob.  Everything downstream inherits that.  lp_mask_stabilize
+ * filters the mask's signed distance field along time: a temporal median removes what lasts at most median_radius frames, a
+ * binomial smoothing calms the edge.  It goes behind a per-frame segmenter or the video mask editor and in front of the mask
+ * refine, the encode and the Detailer crops.  Everything stays on the device; nothing is read back.
+ *   mask    [frames, height, width] fp32, binarised as lp_vmask_edt does: foreground = (v >= 0.5), a NaN is background
+ *   sides   1..LP_VMASK_MAX_SIDE; frames >= 1
+ * stage 1   (lp_mask_signed_d2)  q[t, y, x], int32, from the two planes lp_vmask_edt wrote for frame t: on a foreground pixel
+ *           (d2_fg == 0) q = +d2_bg >= 1, on a background pixel q = -d2_fg <= -1.  Where the wanted plane holds LP_VMASK_D2_NONE
+ *           q = +LP_STAB_Q_FAR (a full frame) or -LP_STAB_Q_FAR (an empty frame); 2^30 lies above every real squared distance
+ *           (at most 2 * 16383^2).
+ * stage 2   Temporal median, radius Tm = median_radius in 0..LP_STAB_MAX_MEDIAN: qm[t] is the median of the 2 Tm + 1 values
+ *           q[clamp(t + k, 0, frames - 1)], k = -Tm..Tm.  The end frames are replicated, so the count is odd; integers, exact.
+ * stage 3   s[t] = sign(qm) * sqrt((double)|qm|), the correctly rounded fp64 square root lp_vmask_edt's sdf uses, then
+ *           s = min(max(s, -LP_STAB_SD_CAP), LP_STAB_SD_CAP): far from every edge, and on empty and full frames, a distance must
+ *           not outweigh the frames that do have an edge nearby.
+ * stage 4   Temporal smoothing, radius Ts = smooth_radius in 0..LP_STAB_MAX_SMOOTH, binomial weights: acc = +0.0; for k = -Ts..Ts
+ *           in ascending order  acc = acc + (double)C(2 Ts, Ts + k) * s[clamp(t + k, 0, frames - 1)],  the product and the sum
+ *           each rounded on its own (no FMA); then sd = acc / 4^Ts (a power of two: exact).
+ * stage 5   u = sd + grow.  feather == 0: out = (u > 0) ? 1.0f : 0.0f;  feather > 0: out = (float)min(max(0.5 + u / (2.0 *
+ *           feather), 0), 1), the quotient and the sum each rounded on its own.  |grow| <= LP_STAB_MAX_GROW, feather in
+ *           0..LP_STAB_MAX_FEATHER, both in pixels.
+ * What follows from the rule, at grow = 0: an all-zero video stays exactly 0 and an all-one video exactly 1.0; Tm = Ts = 0 and
+ * feather = 0 give the binarised input; a video whose frames are all equal gives that binarised frame for every Tm and Ts at
+ * feather = 0; a dropout or a stray blob that lasts at most Tm frames disappears (the smoothing alone does not repair one).  The
+ * same bits on every run.
+ * lp_mask_signed_d2 is one launch.  lp_mask_stabilize is one launch for stages 2 to 5 (csrc/stabilize_kernel.hip): every lane
+ * owns one pixel and marches over t with both windows in registers, so q is read once and out written once.  Where the plane has
+ * too few pixels to fill the device the time axis is cut into segments of at least LP_STAB_SEG_FRAMES frames; a segment warms
+ * its windows up over the frames in front of it, which cannot change a bit.  No workspace, no floating-point atomics.
+ * LP_E_INVALID: null pointer, frames <= 0, a side outside 1..LP_VMASK_MAX_SIDE, a radius outside its range, grow or feather
+ * outside its range or NaN, out == q (q == d2 for lp_mask_signed_d2); LP_E_UNSUPPORTED: lp_mask_stabilize with frames > 2^30.
+ * All checked before any HIP call.                                                                                             */
+#define LP_STAB_Q_FAR       (1 << 30)
+#define LP_STAB_MAX_MEDIAN  3
+#define LP_STAB_MAX_SMOOTH  8
+#define LP_STAB_MAX_GROW    256
+#define LP_STAB_MAX_FEATHER 64
+#define LP_STAB_SEG_FRAMES  16
+#define LP_STAB_SD_CAP      64.0
+/*   d2  [frames, 2, height, width] int32 as lp_vmask_edt writes it;  q  out [frames, height, width] int32                      */
+LP_API int lp_mask_signed_d2(const int32_t* d2, int32_t frames, int32_t height, int32_t width, int32_t* q, void* stream);
+
+typedef struct lp_stabilize_desc {
+    int32_t frames, height, width;
+    int32_t median_radius, smooth_radius, reserved0;
+    double  grow, feather;
+    const int32_t* q;
+    float*         out;
+} lp_stabilize_desc;
+LP_API int lp_mask_stabilize(const lp_stabilize_desc* desc, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -334,6 +334,16 @@ def refine_ws_bytes(batch, height, width, channels, radius):
     return int(batch) * int(height) * int(width) * 16
 
 
+LP_STAB_Q_FAR, LP_STAB_MAX_MEDIAN, LP_STAB_MAX_SMOOTH, LP_STAB_MAX_GROW, LP_STAB_MAX_FEATHER = 1 << 30, 3, 8, 256, 64
+LP_STAB_SEG_FRAMES, LP_STAB_SD_CAP = 16, 64.0
+
+
+class LpStabilizeDesc(C.Structure):
+    _fields_ = [("frames", C.c_int32), ("height", C.c_int32), ("width", C.c_int32),
+                ("median_radius", C.c_int32), ("smooth_radius", C.c_int32), ("reserved0", C.c_int32),
+                ("grow", C.c_double), ("feather", C.c_double), ("q", C.c_void_p), ("out", C.c_void_p)]
+
+
 def lp_components_ws_bytes(height, width):
     """LP_COMPONENTS_WS_BYTES of include/lanpaint_hip.h."""
     return ((int(height) * int(width) + 1023) // 1024) * 4100
@@ -413,6 +423,8 @@ EXPORTS = {
     "lp_multiband_ws_bytes": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     "lp_mask_refine": (C.c_int, [C.POINTER(LpRefineDesc), C.c_void_p]),
     "lp_refine_ws_bytes": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "lp_mask_signed_d2": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    "lp_mask_stabilize": (C.c_int, [C.POINTER(LpStabilizeDesc), C.c_void_p]),
 }
 
 

@@ -59,6 +59,8 @@ int multiband_blend_dispatch(const lp_multiband_desc* d, hipStream_t stream);
 int64_t multiband_ws_bytes(int batch, int height, int width, int channels, int levels);
 int mask_refine_dispatch(const lp_refine_desc* d, hipStream_t stream);
 int64_t refine_ws_bytes(int batch, int height, int width, int channels, int radius);
+int mask_signed_d2_dispatch(const int32_t* d2, int frames, int height, int width, int32_t* q, hipStream_t stream);
+int mask_stabilize_dispatch(const lp_stabilize_desc* d, hipStream_t stream);
 int reshape_mask_dispatch(const float* src, int sb, int sc, int sf, int sh, int sw, float* dst, int db, int dc, int df,
                           int dh, int dw, int taps, int flags, hipStream_t stream);
 }  // namespace lp
@@ -197,6 +199,12 @@ int lp_mask_refine(const lp_refine_desc* desc, void* stream) { return lp::mask_r
 int64_t lp_refine_ws_bytes(int32_t batch, int32_t height, int32_t width, int32_t channels, int32_t radius) {
     return lp::refine_ws_bytes(batch, height, width, channels, radius);
 }
+
+int lp_mask_signed_d2(const int32_t* d2, int32_t frames, int32_t height, int32_t width, int32_t* q, void* stream) {
+    return lp::mask_signed_d2_dispatch(d2, frames, height, width, q, as_stream(stream));
+}
+
+int lp_mask_stabilize(const lp_stabilize_desc* desc, void* stream) { return lp::mask_stabilize_dispatch(desc, as_stream(stream)); }
 
 int lp_finalize(const lp_final_desc* desc, void* stream) { return lp::finalize_dispatch(desc, as_stream(stream)); }
 
