@@ -20,7 +20,7 @@ from dataclasses import dataclass
 import torch
 
 from . import _cabi, interp_rule
-from .resample import _hip_device
+from ._hostcall import launch, node_device
 
 try:
     import torchaudio
@@ -91,7 +91,6 @@ def plan_merge(orig, inpainted, am, cf, nn_rule):
 
 
 def _launch(plan, m, o, p):
-    lib = _cabi.load()
     dev = o.device
     out = torch.empty((plan.batch, plan.channels, plan.n), dtype=torch.float32, device=dev)
     ws = torch.empty(_cabi.lp_audio_ws_bytes(plan.mask_len), dtype=torch.uint8, device=dev) if plan.cf > 1 else None
@@ -102,8 +101,7 @@ def _launch(plan, m, o, p):
     d.inp_sb, d.inp_sc = plan.inp_strides
     d.mask, d.orig, d.inpainted, d.out = m.data_ptr(), o.data_ptr(), p.data_ptr(), out.data_ptr()
     d.workspace = ws.data_ptr() if ws is not None else None
-    with torch.cuda.device(dev):
-        _cabi.check(lib.lp_audio_merge(ctypes.byref(d), torch.cuda.current_stream(dev).cuda_stream), "lp_audio_merge")
+    launch("lp_audio_merge", dev, ctypes.byref(d))
     return out
 
 
@@ -121,7 +119,7 @@ def merge_audio_with_mask(orig, inpainted, mask, crossfade, orig_sr, result_sr):
     # the reference up-samples the mask with a 1-D F.interpolate on the MASK's device: the kernel follows that kernel's rule
     rule = interp_rule.rule_for(am, am.reshape(1, 1, -1), (n,)) if am.shape[0] != n else _cabi.LP_NN_ATEN_SCALAR
     plan_merge(orig, inpainted, am, cf, rule)            # shape errors surface before anything touches the device
-    dev = _hip_device(orig)
+    dev = node_device(orig)
 
     def on_device(t):
         t = t.to(device=dev, dtype=torch.float32)

@@ -14,8 +14,8 @@ from __future__ import annotations
 import torch
 
 from . import audio as _audio
+from ._hostcall import node_device
 from .blend import merge_video_with_mask
-from .resample import _hip_device
 
 
 def _nested_tensor():
@@ -171,7 +171,7 @@ class LanPaint_AVDecode:
         if tuple(frames.shape[1:3]) != size:          # VAE decodes can round the size
             frames = torch.nn.functional.interpolate(frames.movedim(-1, 1), size=size, mode="bilinear",
                                                      align_corners=False).movedim(1, -1)
-        dev = _hip_device(src_frames)
+        dev = node_device(src_frames)
         # the mask is handed over where it lives: its device decides the index rule of a lower-resolution mask's resample
         merged_frames = merge_video_with_mask(src_frames.to(dev), frames.to(dev), mask, blend_overlap).to(src_frames.device)
 

@@ -13,6 +13,7 @@ import ctypes
 import torch
 
 from . import _cabi, interp_rule
+from ._hostcall import int_in, launch, mask_for, node_device
 from ._util import _as_f32c
 
 
@@ -30,9 +31,8 @@ def gaussian_kernel_2d(kernel_size):
 def _launch(mask, image1, image2, k, want_smooth=False, nn_rule=0):
     if not image1.is_cuda:
         raise RuntimeError("lanpaint_amd.blend runs on a HIP device only; no CPU fallback")
-    if not isinstance(k, int) or k < 1 or k > 51 or k % 2 == 0:
-        raise ValueError(f"blend_overlap must be an odd integer in [1, 51], got {k!r}")
-    lib = _cabi.load()
+    if int_in(k, 1, 51, "blend_overlap") % 2 == 0:
+        raise ValueError(f"blend_overlap must be an odd integer in 1..51, got {k!r}")
     dev = image1.device
     i1, i2 = _as_f32c(image1), _as_f32c(image2.to(dev))
     m = _as_f32c(mask.to(dev))
@@ -45,8 +45,7 @@ def _launch(mask, image1, image2, k, want_smooth=False, nn_rule=0):
     d.nn_rule = int(nn_rule)
     d.mask, d.image1, d.image2, d.out = m.data_ptr(), i1.data_ptr(), i2.data_ptr(), out.data_ptr()
     d.smooth_out = smooth.data_ptr() if smooth is not None else None
-    with torch.cuda.device(dev):
-        _cabi.check(lib.lp_mask_blend(ctypes.byref(d), torch.cuda.current_stream(dev).cuda_stream), "lp_mask_blend")
+    launch("lp_mask_blend", dev, ctypes.byref(d))
     return (out, smooth) if want_smooth else out
 
 
@@ -58,10 +57,7 @@ def mask_blend(image1, image2, mask, blend_overlap):
             "Additionally, ensure both images have width and height that are multiples of 8 (VAE decode always "
             "produces such sizes).\nCurrent sizes - Image1: {}x{}, Image2: {}x{}".format(
                 image1.shape[2], image1.shape[1], image2.shape[2], image2.shape[1]))
-    m = mask.float()
-    if m.shape[0] not in (1, image1.shape[0]) or tuple(m.shape[1:]) != tuple(image1.shape[1:3]):
-        raise ValueError(f"mask shape {tuple(mask.shape)} does not match images {tuple(image1.shape)}")
-    return _launch(m, image1, image2, blend_overlap)
+    return _launch(mask_for(mask, *image1.shape[:3], mask.device), image1, image2, blend_overlap)
 
 
 def merge_video_with_mask(orig, inpainted, mask, blend_overlap):
@@ -104,7 +100,7 @@ class MaskBlend:
     CATEGORY = "image/postprocessing"
 
     def blend_images(self, image1, image2, mask, blend_overlap):
-        dev = image1.device if image1.is_cuda else torch.device("cuda", torch.cuda.current_device())
+        dev = node_device(image1)
         out = mask_blend(image1.to(dev), image2.to(dev), mask.to(dev), blend_overlap)
         return (out.to(image1.device),)
 

@@ -91,7 +91,8 @@ import numpy as np
 import torch
 
 from . import _cabi
-from ._util import _as_f32c, device_tables, raw_stream
+from ._hostcall import int_in, launch, mask3, mask_for, require_hip
+from ._util import _as_f32c, device_tables
 from .videomask import tap_window
 
 FILTERS = ("bilinear", "bicubic")
@@ -261,20 +262,6 @@ def aa_coeffs(in_size, out_size, filter="bilinear"):
     return bounds, weights
 
 
-def _hip(t, what):
-    if not torch.is_tensor(t) or not t.is_cuda:
-        raise RuntimeError(f"lanpaint_amd.detail runs on a HIP device only; no CPU fallback ({what} is not on one)")
-    return t
-
-
-def _mask3(mask):
-    if mask.ndim == 2:
-        return mask.unsqueeze(0)
-    if mask.ndim != 3:
-        raise ValueError(f"mask must be [B, H, W], [1, H, W] or [H, W], got {tuple(mask.shape)}")
-    return mask
-
-
 def _check_filter(filter):
     if filter not in FILTERS:
         raise ValueError(f"filter must be one of {FILTERS}, got {filter!r}")
@@ -288,12 +275,11 @@ def _check_region(region, H, W):
 def mask_bbox(mask):
     """(row_min, row_max, col_min, col_max), inclusive, of `mask > 0.5` over every frame of a HIP mask [B, H, W], [1, H, W] or
     [H, W]; (H, -1, W, -1) when nothing is set (plan_region raises on it).  Reads four integers back from the device."""
-    m = _as_f32c(_mask3(_hip(mask, "mask")))
+    m = _as_f32c(mask3(require_hip(mask, "mask", __name__)))
     planes, h, w = m.shape
     dev = m.device
     box = torch.empty(4, dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        _cabi.check(_cabi.load().lp_mask_bbox(m.data_ptr(), planes, h, w, box.data_ptr(), raw_stream(dev)), "lp_mask_bbox")
+    launch("lp_mask_bbox", dev, m.data_ptr(), planes, h, w, box.data_ptr())
     return tuple(box.cpu().tolist())
 
 
@@ -325,8 +311,7 @@ def _resample(src, win, filter, origins=None, labels=None, owner=None):
         by, wy = device_tables(_aa_tables_f32, dev, win.h, win.oh, filter)
         d.ksize_x, d.ksize_y = wx.shape[1], wy.shape[1]
         d.bounds_x, d.weights_x, d.bounds_y, d.weights_y = bx.data_ptr(), wx.data_ptr(), by.data_ptr(), wy.data_ptr()
-    with torch.cuda.device(dev):
-        _cabi.check(getattr(_cabi.load(), entry)(ctypes.byref(d), raw_stream(dev)), entry)
+    launch(entry, dev, ctypes.byref(d))
     return out
 
 
@@ -334,7 +319,7 @@ def crop_resample(image, mask, region, filter="bilinear"):
     """image [B, H, W, C] and mask ([B, H, W], [1, H, W], [H, W] or None) cut to `region` and resampled to its working size:
     (image [B, oh, ow, C], mask [Bm, oh, ow] or None).  The image takes `filter`, the mask bilinear, and it stays soft."""
     _check_filter(filter)
-    img = _as_f32c(_hip(image, "image"))
+    img = _as_f32c(require_hip(image, "image", __name__))
     if img.ndim != 4:
         raise ValueError(f"image must be [B, H, W, C], got {tuple(image.shape)}")
     _check_region(region, img.shape[1], img.shape[2])
@@ -342,7 +327,7 @@ def crop_resample(image, mask, region, filter="bilinear"):
     out = _resample(img, r, filter)
     if mask is None:
         return out, None
-    m = _as_f32c(_mask3(_hip(mask, "mask")))
+    m = _as_f32c(mask3(require_hip(mask, "mask", __name__)))
     if tuple(m.shape[1:]) != (r.H, r.W):
         raise ValueError(f"mask shape {tuple(mask.shape)} does not match images {tuple(image.shape)}")
     return out, _resample(m.unsqueeze(-1), r, "bilinear").squeeze(-1)
@@ -353,13 +338,13 @@ def _stitch_inputs(original, detail_img, mask, win, blend_overlap, filter, label
     original's device, the crops resampled back to the windows' size in one launch -> (orig, det, m, b, H, W, c).  The mask is
     [B, H, W] or one plane for all images, unless the form has a rule of its own: `frame_mask(mask, B, H, W)`."""
     _check_filter(filter)
-    k = blend_overlap
-    if not isinstance(k, int) or k < 1 or k > 51 or k % 2 == 0:
-        raise ValueError(f"blend_overlap must be an odd integer in [1, 51], got {k!r}")
+    if int_in(blend_overlap, 1, 51, "blend_overlap") % 2 == 0:
+        raise ValueError(f"blend_overlap must be an odd integer in 1..51, got {blend_overlap!r}")
     name = _FORMS[type(win)].crops
-    orig = _as_f32c(_hip(original, "original"))
-    det = _as_f32c(_hip(detail_img, name).to(orig.device))
-    m = None if frame_mask else _as_f32c(_mask3(_hip(mask, "mask")).to(orig.device))
+    orig = _as_f32c(require_hip(original, "original", __name__))
+    det = _as_f32c(require_hip(detail_img, name, __name__).to(orig.device))
+    if not frame_mask:
+        require_hip(mask, "mask", __name__)
     if orig.ndim != 4 or det.ndim != 4:
         raise ValueError(f"original and {name} must be [B, H, W, C]")
     b, H, W, c = orig.shape
@@ -367,10 +352,7 @@ def _stitch_inputs(original, detail_img, mask, win, blend_overlap, filter, label
     want = (win.groups * b, win.oh, win.ow, c)
     if tuple(det.shape) != want:
         raise ValueError(f"{name} must be {want}, got {tuple(det.shape)}")
-    if frame_mask:
-        m = _as_f32c(frame_mask(mask, b, H, W).to(orig.device))
-    elif m.shape[0] not in (1, b) or tuple(m.shape[1:]) != (H, W):
-        raise ValueError(f"mask shape {tuple(mask.shape)} does not match images {tuple(original.shape)}")
+    m = _as_f32c(frame_mask(mask, b, H, W).to(orig.device)) if frame_mask else mask_for(mask, b, H, W, orig.device)
     if win.resampled:
         det = _resample(det, Region(0, 0, win.oh, win.ow, win.h, win.w, win.oh, win.ow), filter)
     return orig, det, m, b, H, W, c
@@ -385,8 +367,7 @@ def stitch(original, detail_img, mask, region, blend_overlap=1, filter="bilinear
     out = torch.empty_like(orig)
     d = _cabi.LpDetailStitchDesc(b, H, W, c, r.y0, r.x0, r.h, r.w, blend_overlap, m.shape[0],
                                  m.data_ptr(), orig.data_ptr(), det.data_ptr(), out.data_ptr())
-    with torch.cuda.device(dev):
-        _cabi.check(_cabi.load().lp_detail_stitch(ctypes.byref(d), raw_stream(dev)), "lp_detail_stitch")
+    launch("lp_detail_stitch", dev, ctypes.byref(d))
     return out
 
 
@@ -402,16 +383,14 @@ def mask_components(mask):
 def _components(mask, entry, cols, volume=False):
     """A labelling entry called and its table read back: (labels, n, rows of `cols` integers).  The labels are one image for
     every plane of the mask, or with `volume` one plane each."""
-    m = _as_f32c(_mask3(_hip(mask, "mask")))
+    m = _as_f32c(mask3(require_hip(mask, "mask", __name__)))
     planes, h, w = m.shape
     dev = m.device
     labels = torch.empty((planes, h, w) if volume else (h, w), dtype=torch.int32, device=dev)
     table = torch.empty(1 + cols * _cabi.LP_DETAIL_MAX_COMPONENTS, dtype=torch.int32, device=dev)
     ws_bytes = _cabi.lp_components_frames_ws_bytes(planes, h, w) if volume else _cabi.lp_components_ws_bytes(h, w)
     ws = torch.empty(ws_bytes // 4, dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        _cabi.check(getattr(_cabi.load(), entry)(m.data_ptr(), planes, h, w, labels.data_ptr(), table.data_ptr(), ws.data_ptr(),
-                                                 ws_bytes, raw_stream(dev)), entry)
+    launch(entry, dev, m.data_ptr(), planes, h, w, labels.data_ptr(), table.data_ptr(), ws.data_ptr(), ws_bytes)
     host = table.cpu().numpy()
     n = int(host[0])
     rows = host[1:1 + cols * min(n, _cabi.LP_DETAIL_MAX_COMPONENTS)].reshape(-1, cols)
@@ -519,7 +498,7 @@ def _owner_table(members, dev):
 
 def _check_labels(labels, planes, H, W):
     """`planes`: None for one label image (mask_components), else the planes of a label volume (mask_components_frames)."""
-    _hip(labels, "labels")
+    require_hip(labels, "labels", __name__)
     shape, source = ((H, W), "mask_components") if planes is None else ((planes, H, W), "mask_components_frames")
     if labels.dtype != torch.int32 or tuple(labels.shape) != shape or not labels.is_contiguous():
         raise ValueError(f"labels must be a contiguous int32 {list(shape)} tensor ({source}), got {labels.dtype} "
@@ -540,7 +519,7 @@ def crop_regions(image, mask, regions, labels=None, filter="bilinear"):
     stack is one sampler batch.  Region i's mask is `mask` with the components of other regions -- and those min_area dropped
     -- set to 0 (`labels` from mask_components; None: the mask as it is); values at or below 0.5 are nobody's and stay."""
     _check_filter(filter)
-    img = _as_f32c(_hip(image, "image"))
+    img = _as_f32c(require_hip(image, "image", __name__))
     if img.ndim != 4:
         raise ValueError(f"image must be [B, H, W, C], got {tuple(image.shape)}")
     H, W = img.shape[1], img.shape[2]
@@ -550,7 +529,7 @@ def crop_regions(image, mask, regions, labels=None, filter="bilinear"):
     out = _resample(img, regions, filter, origins)
     if mask is None:
         return out, None
-    m = _as_f32c(_mask3(_hip(mask, "mask")).to(img.device))
+    m = _as_f32c(mask3(require_hip(mask, "mask", __name__)).to(img.device))
     if tuple(m.shape[1:]) != (H, W):
         raise ValueError(f"mask shape {tuple(mask.shape)} does not match images {tuple(image.shape)}")
     return out, _resample(m.unsqueeze(-1), regions, "bilinear", origins, labels, owner).squeeze(-1)
@@ -571,8 +550,7 @@ def stitch_regions(original, detail_imgs, mask, regions, labels=None, blend_over
     if labels is not None:
         owner = _owner_table(g.members, dev)
         d.labels, d.owner, d.owner_len = labels.data_ptr(), owner.data_ptr(), owner.numel()
-    with torch.cuda.device(dev):
-        _cabi.check(_cabi.load().lp_detail_stitch_regions(ctypes.byref(d), raw_stream(dev)), "lp_detail_stitch_regions")
+    launch("lp_detail_stitch_regions", dev, ctypes.byref(d))
     return out
 
 
@@ -658,13 +636,11 @@ def plan_track(boxes, H, W, context=1.0, padding=0, multiple_of=8, target=0, smo
 def mask_bbox_frames(mask):
     """`mask_bbox` of every frame on its own, in one launch: a tuple of (row_min, row_max, col_min, col_max), one per plane of a
     HIP mask [B, H, W], [1, H, W] or [H, W]; (H, -1, W, -1) for a frame with nothing set.  Reads the [B, 4] table back."""
-    m = _as_f32c(_mask3(_hip(mask, "mask")))
+    m = _as_f32c(mask3(require_hip(mask, "mask", __name__)))
     planes, h, w = m.shape
     dev = m.device
     boxes = torch.empty((planes, 4), dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        _cabi.check(_cabi.load().lp_mask_bbox_frames(m.data_ptr(), planes, h, w, boxes.data_ptr(), raw_stream(dev)),
-                    "lp_mask_bbox_frames")
+    launch("lp_mask_bbox_frames", dev, m.data_ptr(), planes, h, w, boxes.data_ptr())
     return tuple(tuple(row) for row in boxes.cpu().tolist())
 
 
@@ -734,7 +710,7 @@ def crop_track(image, mask, track, filter="bilinear"):
     crop_resample gives for it alone, bit for bit.  A one-plane mask stays one plane while the track stands still (plan_track
     of a static mask); under a track that moves it is cut once per frame, [B, oh, ow]."""
     _check_filter(filter)
-    img = _as_f32c(_hip(image, "image"))
+    img = _as_f32c(require_hip(image, "image", __name__))
     if img.ndim != 4:
         raise ValueError(f"image must be [B, H, W, C], got {tuple(image.shape)}")
     b, H, W = img.shape[0], img.shape[1], img.shape[2]
@@ -743,9 +719,7 @@ def crop_track(image, mask, track, filter="bilinear"):
     out = _resample(img, track, filter, origins)
     if mask is None:
         return out, None
-    m = _mask3(_hip(mask, "mask")).to(img.device)
-    if m.shape[0] not in (1, b) or tuple(m.shape[1:]) != (H, W):
-        raise ValueError(f"mask shape {tuple(mask.shape)} does not match images {tuple(image.shape)}")
+    m = mask_for(require_hip(mask, "mask", __name__), b, H, W, img.device)
     if m.shape[0] != b:
         if len(set(track.origins)) == 1:
             origins = origins[:1]
@@ -764,6 +738,5 @@ def stitch_track(original, detail_img, mask, track, blend_overlap=1, filter="bil
     out = torch.empty_like(orig)
     d = _cabi.LpDetailStitchTrackDesc(b, H, W, c, t.h, t.w, k, m.shape[0],
                                       origins.data_ptr(), m.data_ptr(), orig.data_ptr(), det.data_ptr(), out.data_ptr())
-    with torch.cuda.device(dev):
-        _cabi.check(_cabi.load().lp_detail_stitch_track(ctypes.byref(d), raw_stream(dev)), "lp_detail_stitch_track")
+    launch("lp_detail_stitch_track", dev, ctypes.byref(d))
     return out

@@ -37,97 +37,72 @@ import ctypes
 import torch
 
 from . import _cabi
-from ._util import _as_f32c, raw_stream
-from .detail import _mask3
+from ._hostcall import MAX_BATCH, float_in, image4, int_in, launch, mask_for, require_hip
+from ._util import _as_f32c
 
 METHODS = ("mean_std", "mean")
 MAX_MARGIN = _cabi.LP_COLOR_MAX_MARGIN
 
 
-def _hip(t, what):
-    if not torch.is_tensor(t) or not t.is_cuda:
-        raise RuntimeError(f"lanpaint_amd.detail_color runs on a HIP device only; no CPU fallback ({what} is not on one)")
-    return t
-
-
-def _image4(t, what):
-    if t.ndim != 4:
-        raise ValueError(f"{what} must be [B, H, W, C], got {tuple(t.shape)}")
-    b, h, w, c = t.shape
-    if min(b, h, w, c) < 1 or max(h, w) > _cabi.LP_DETAIL_MAX_SIDE or c > _cabi.LP_DETAIL_MAX_CHANNELS or b > 65535:
-        raise ValueError(f"{what} {tuple(t.shape)}: sides 1..{_cabi.LP_DETAIL_MAX_SIDE}, channels "
-                         f"1..{_cabi.LP_DETAIL_MAX_CHANNELS}, batch 1..65535")
-    return t
-
-
 def _check_fit(batch, method, strength, smooth, clip_frames):
     if method not in METHODS:
         raise ValueError(f"method must be one of {METHODS}, got {method!r}")
-    if not isinstance(strength, (int, float)) or isinstance(strength, bool) or not 0.0 <= strength <= 1.0:
-        raise ValueError(f"strength must be in [0, 1], got {strength!r}")
-    if not isinstance(smooth, int) or isinstance(smooth, bool) or smooth < 0 or smooth > 129 or (smooth and smooth % 2 == 0):
-        raise ValueError(f"smooth must be 0 or an odd integer in [1, 129], got {smooth!r}")
-    if not isinstance(clip_frames, int) or isinstance(clip_frames, bool) or clip_frames < 0 or \
-            (clip_frames and batch % clip_frames):
+    float_in(strength, 0.0, 1.0, "strength")
+    if int_in(smooth, 0, 129, "smooth") and smooth % 2 == 0:
+        raise ValueError(f"smooth must be 0 or an odd integer in 1..129, got {smooth!r}")
+    if int_in(clip_frames, 0, batch, "clip_frames") and batch % clip_frames:
         raise ValueError(f"clip_frames must be 0 or a divisor of the batch {batch}, got {clip_frames!r}")
 
 
 def _check_margin(margin):
-    if not isinstance(margin, int) or isinstance(margin, bool) or margin < 0 or margin > MAX_MARGIN:
-        raise ValueError(f"margin must be an integer in [0, {MAX_MARGIN}], got {margin!r}")
+    int_in(margin, 0, MAX_MARGIN, "margin")
 
 
 def color_stats(detail, reference, mask=None, margin=8):
     """The masked sums of `detail` and `reference` [B, H, W, C] as fp64 [B, 1 + 4 C] on the device (module docstring).  `mask`
     is [B, H, W], [1, H, W], [H, W] or None (every pixel kept)."""
     _check_margin(margin)
-    det = _as_f32c(_image4(_hip(detail, "detail"), "detail"))
-    ref = _as_f32c(_hip(reference, "reference").to(det.device))
+    det = _as_f32c(image4(require_hip(detail, "detail", __name__), "detail", MAX_BATCH))
+    ref = _as_f32c(require_hip(reference, "reference", __name__).to(det.device))
     if tuple(ref.shape) != tuple(det.shape):
         raise ValueError(f"reference must be {tuple(det.shape)} like detail, got {tuple(reference.shape)}")
     b, h, w, c = det.shape
     dev = det.device
-    m = None
-    if mask is not None:
-        m = _as_f32c(_mask3(_hip(mask, "mask")).to(dev))
-        if m.shape[0] not in (1, b) or tuple(m.shape[1:]) != (h, w):
-            raise ValueError(f"mask shape {tuple(mask.shape)} does not match images {tuple(detail.shape)}")
+    m = None if mask is None else mask_for(require_hip(mask, "mask", __name__), b, h, w, dev)
     ws_bytes = _cabi.lp_color_ws_bytes(b, h, w, c)
     ws = torch.empty(ws_bytes // 8, dtype=torch.float64, device=dev)
     stats = torch.empty((b, 1 + 4 * c), dtype=torch.float64, device=dev)
     d = _cabi.LpColorStatsDesc(b, h, w, c, m.shape[0] if m is not None else 1, margin, det.data_ptr(), ref.data_ptr(),
                                m.data_ptr() if m is not None else None, stats.data_ptr(), ws.data_ptr(), ws_bytes)
-    with torch.cuda.device(dev):
-        _cabi.check(_cabi.load().lp_color_stats(ctypes.byref(d), raw_stream(dev)), "lp_color_stats")
+    launch("lp_color_stats", dev, ctypes.byref(d))
     return stats
 
 
 def color_fit(stats, method="mean_std", strength=1.0, smooth=1, clip_frames=0):
     """color_stats' table fp64 [B, 1 + 4 C] -> (gain, bias) fp32 [B, C, 2] on the device, by the rule of the module docstring."""
-    s = _hip(stats, "stats")
+    s = require_hip(stats, "stats", __name__)
     if s.ndim != 2 or s.dtype != torch.float64 or s.shape[0] < 1 or s.shape[1] < 5 or (s.shape[1] - 1) % 4:
         raise ValueError(f"stats must be float64 [B, 1 + 4 C], got {s.dtype} {tuple(s.shape)}")
     b, c = s.shape[0], (s.shape[1] - 1) // 4
-    if c > _cabi.LP_DETAIL_MAX_CHANNELS or b > 65535:
-        raise ValueError(f"stats {tuple(s.shape)}: channels 1..{_cabi.LP_DETAIL_MAX_CHANNELS}, batch 1..65535")
+    if c > _cabi.LP_DETAIL_MAX_CHANNELS or b > MAX_BATCH:
+        raise ValueError(f"stats {tuple(s.shape)}: channels 1..{_cabi.LP_DETAIL_MAX_CHANNELS}, batch 1..{MAX_BATCH}")
     _check_fit(b, method, strength, smooth, clip_frames)
     s = s.contiguous()
     dev = s.device
     coef = torch.empty((b, c, 2), dtype=torch.float32, device=dev)
     kind = _cabi.LP_COLOR_METHOD_MEAN_STD if method == "mean_std" else _cabi.LP_COLOR_METHOD_MEAN
     d = _cabi.LpColorFitDesc(b, c, clip_frames, smooth, kind, 0, float(strength), s.data_ptr(), coef.data_ptr())
-    with torch.cuda.device(dev):
-        _cabi.check(_cabi.load().lp_color_fit(ctypes.byref(d), raw_stream(dev)), "lp_color_fit")
+    launch("lp_color_fit", dev, ctypes.byref(d))
     return coef
 
 
 def color_apply(detail, coef, out=None):
     """fl(fl(detail * gain) + bias) per image and channel: detail [B, H, W, C], coef fp32 [B, C, 2].  `out` may be a contiguous
     fp32 tensor of detail's shape on the same device, detail itself included."""
-    det = _as_f32c(_image4(_hip(detail, "detail"), "detail"))
+    det = _as_f32c(image4(require_hip(detail, "detail", __name__), "detail", MAX_BATCH))
     b, h, w, c = det.shape
     dev = det.device
-    k = _hip(coef, "coef")
+    k = require_hip(coef, "coef", __name__)
     if tuple(k.shape) != (b, c, 2) or k.dtype != torch.float32:
         raise ValueError(f"coef must be float32 {(b, c, 2)}, got {k.dtype} {tuple(k.shape)}")
     k = k.to(dev).contiguous()
@@ -137,15 +112,14 @@ def color_apply(detail, coef, out=None):
             or not out.is_contiguous():
         raise ValueError(f"out must be a contiguous float32 tensor {tuple(det.shape)} on {dev}")
     d = _cabi.LpColorApplyDesc(b, h, w, c, det.data_ptr(), k.data_ptr(), out.data_ptr())
-    with torch.cuda.device(dev):
-        _cabi.check(_cabi.load().lp_color_apply(ctypes.byref(d), raw_stream(dev)), "lp_color_apply")
+    launch("lp_color_apply", dev, ctypes.byref(d))
     return out
 
 
 def match(detail, reference, mask, method="mean_std", strength=1.0, margin=8, smooth=1, clip_frames=0):
     """`detail` [B, H, W, C] with its tone brought to `reference`'s, both measured outside `mask` (module docstring).  Four
     launches on the current stream and no device -> host read."""
-    det = _image4(_hip(detail, "detail"), "detail")
+    det = image4(require_hip(detail, "detail", __name__), "detail", MAX_BATCH)
     _check_margin(margin)
     _check_fit(det.shape[0], method, strength, smooth, clip_frames)
     det = _as_f32c(det)

@@ -19,7 +19,7 @@ This module has its own NODE_CLASS_MAPPINGS: merge them with the others' (INTEGR
 from __future__ import annotations
 
 from . import detail_color
-from .detail_nodes import _hip_device
+from ._hostcall import node_device
 
 
 class LanPaint_DetailerColorMatch:
@@ -52,7 +52,7 @@ class LanPaint_DetailerColorMatch:
                    "between LanPaint_ImageDecode and any LanPaint_DetailerStitch node.")
 
     def match(self, image, reference, mask, method="mean_std", strength=1.0, margin=8, smooth=1, clip_frames=0):
-        dev = _hip_device(image)
+        dev = node_device(image)
         out = detail_color.match(image.to(dev), reference.to(dev), mask.to(dev), method, strength, margin, smooth, clip_frames)
         return (out.to(image.device),)
 

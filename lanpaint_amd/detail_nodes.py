@@ -14,23 +14,14 @@ This module has its own NODE_CLASS_MAPPINGS: merge them with lanpaint_amd.nodes'
 """
 from __future__ import annotations
 
-import torch
-
 from . import detail
-
-
-def _hip_device(t):
-    if t.is_cuda:
-        return t.device
-    if not torch.cuda.is_available():
-        raise RuntimeError("the Detailer nodes run on a HIP device only; no CPU fallback")
-    return torch.device("cuda", torch.cuda.current_device())
+from ._hostcall import node_device, node_mask
 
 
 def _on_device(image, mask):
     """What every crop node starts with: (image, mask as [B, H, W]) on the HIP device the crop runs on."""
-    dev = _hip_device(image)
-    return image.to(dev), (mask.unsqueeze(0) if mask.ndim == 2 else mask).to(dev)
+    dev = node_device(image)
+    return image.to(dev), node_mask(mask, dev)
 
 
 class LanPaint_DetailerCrop:
@@ -84,7 +75,7 @@ class LanPaint_DetailerStitch:
 
     def stitch(self, stitch, image, blend_overlap=9):
         original = stitch["original"]
-        dev = _hip_device(original)
+        dev = node_device(original)
         labels = (stitch["labels"].to(dev),) if "labels" in stitch else ()        # after the windows, where the crop node left some
         out = self.CALL(original.to(dev), image.to(dev), stitch["mask"].to(dev), stitch[self.WINDOWS], *labels, blend_overlap,
                         stitch["filter"])

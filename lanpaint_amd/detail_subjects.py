@@ -52,19 +52,20 @@ import ctypes
 import torch
 
 from . import _cabi, detail
-from ._util import _as_f32c, raw_stream
-from .detail import Subjects, _check_subjects, _hip   # Subjects is defined beside its siblings and is this module's to export
+from ._hostcall import launch, mask3, require_hip
+from ._util import _as_f32c
+from .detail import Subjects, _check_subjects         # Subjects is defined beside its siblings and is this module's to export
 
 
 def _frame_mask(mask, frames, H, W):
     """The mask as [frames, H, W]: one plane per image."""
-    m = detail._mask3(mask if torch.is_tensor(mask) else _hip(mask, "mask"))
+    m = mask3(mask if torch.is_tensor(mask) else require_hip(mask, "mask", __name__))
     if m.shape[0] == 1 and frames > 1:
         raise ValueError(f"the subjects form needs one mask plane per image, got one plane for {frames} images: a mask that "
                          "stands still is served by the region nodes (LanPaint_DetailerCropRegions)")
     if m.shape[0] != frames or tuple(m.shape[1:]) != (H, W):
         raise ValueError(f"mask shape {tuple(mask.shape)} does not match {frames} images of {H}x{W}")
-    return _hip(m, "mask")
+    return require_hip(m, "mask", __name__)
 
 
 def mask_components_frames(mask):
@@ -108,7 +109,7 @@ def subject_boxes(labels, members):
     """One bounding box per (subject, frame): boxes[s][f] = (row_min, row_max, col_min, col_max), inclusive, over the voxels of
     frame f whose label is one of members[s]; (H, -1, W, -1) for a frame the subject is absent from.  One launch
     (lp_subject_boxes); reads the [subjects, frames, 4] table back: the second of a job's two reads."""
-    _hip(labels, "labels")
+    require_hip(labels, "labels", __name__)
     if labels.ndim != 3:
         raise ValueError(f"labels must be [F, H, W], got {tuple(labels.shape)}")
     frames, h, w = labels.shape
@@ -117,9 +118,8 @@ def subject_boxes(labels, members):
     dev = labels.device
     owner = detail._owner_table(members, dev)
     boxes = torch.empty((len(members), frames, 4), dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        _cabi.check(_cabi.load().lp_subject_boxes(labels.data_ptr(), frames, h, w, owner.data_ptr(), owner.numel(), len(members),
-                                                  boxes.data_ptr(), raw_stream(dev)), "lp_subject_boxes")
+    launch("lp_subject_boxes", dev, labels.data_ptr(), frames, h, w, owner.data_ptr(), owner.numel(), len(members),
+           boxes.data_ptr())
     return tuple(tuple(tuple(row) for row in sub) for sub in boxes.cpu().tolist())
 
 
@@ -157,7 +157,7 @@ def crop_subjects(image, mask, subjects, labels=None, filter="bilinear"):
     mask is frame f's with the components of other subjects -- and those min_area dropped -- set to 0 (`labels` from
     mask_components_frames; None: the mask as it is); values at or below 0.5 are nobody's and stay."""
     detail._check_filter(filter)
-    img = _as_f32c(_hip(image, "image"))
+    img = _as_f32c(require_hip(image, "image", __name__))
     if img.ndim != 4:
         raise ValueError(f"image must be [B, H, W, C], got {tuple(image.shape)}")
     frames, H, W = img.shape[0], img.shape[1], img.shape[2]
@@ -187,6 +187,5 @@ def stitch_subjects(original, detail_imgs, mask, subjects, labels=None, blend_ov
     if labels is not None:
         owner = detail._owner_table(g.members, dev)
         d.labels, d.owner, d.owner_len = labels.data_ptr(), owner.data_ptr(), owner.numel()
-    with torch.cuda.device(dev):
-        _cabi.check(_cabi.load().lp_detail_stitch_subjects(ctypes.byref(d), raw_stream(dev)), "lp_detail_stitch_subjects")
+    launch("lp_detail_stitch_subjects", dev, ctypes.byref(d))
     return out

@@ -37,8 +37,8 @@ import dataclasses
 import torch
 
 from . import _cabi
-from ._util import _as_f32c, raw_stream
-from .detail import _mask3
+from ._hostcall import MAX_BATCH, image4, int_in, launch, mask_for, require_hip, workspace
+from ._util import _as_f32c
 
 MAX_SIDE = _cabi.LP_DETAIL_MAX_SIDE
 
@@ -54,32 +54,8 @@ class OutpaintPlan:
     width: int
 
 
-def _hip(t, what):
-    if not torch.is_tensor(t) or not t.is_cuda:
-        raise RuntimeError(f"lanpaint_amd.fill runs on a HIP device only; no CPU fallback ({what} is not on one)")
-    return t
-
-
-def _image4(t, what):
-    if t.ndim != 4:
-        raise ValueError(f"{what} must be [B, H, W, C], got {tuple(t.shape)}")
-    b, h, w, c = t.shape
-    if min(b, h, w, c) < 1 or max(h, w) > MAX_SIDE or c > _cabi.LP_DETAIL_MAX_CHANNELS or b > 65535:
-        raise ValueError(f"{what} {tuple(t.shape)}: sides 1..{MAX_SIDE}, channels 1..{_cabi.LP_DETAIL_MAX_CHANNELS}, batch 1..65535")
-    return t
-
-
 def _mask_for(mask, image, dev):
-    m = _as_f32c(_mask3(_hip(mask, "mask")).to(dev))
-    if m.shape[0] not in (1, image.shape[0]) or tuple(m.shape[1:]) != tuple(image.shape[1:3]):
-        raise ValueError(f"mask shape {tuple(mask.shape)} does not match image {tuple(image.shape)}")
-    return m
-
-
-def _int(v, what):
-    if not isinstance(v, int) or isinstance(v, bool):
-        raise ValueError(f"{what} must be an integer, got {v!r}")
-    return v
+    return mask_for(require_hip(mask, "mask", __name__), image.shape[0], image.shape[1], image.shape[2], dev)
 
 
 def _snap(n, p0, p1, m):
@@ -97,15 +73,10 @@ def _snap(n, p0, p1, m):
 def plan_outpaint(H, W, left=0, top=0, right=0, bottom=0, overlap=0, multiple_of=8):
     """The final pads and the canvas size (module docstring).  ValueError: a negative value, multiple_of < 1, all four pads zero,
     an overlap that leaves no known pixel on an axis, a canvas side above the limit."""
-    for v, what in ((H, "H"), (W, "W"), (left, "left"), (top, "top"), (right, "right"), (bottom, "bottom"), (overlap, "overlap"),
-                    (multiple_of, "multiple_of")):
-        _int(v, what)
-    if H < 1 or W < 1:
-        raise ValueError(f"image sides must be positive, got {H} x {W}")
-    if min(left, top, right, bottom, overlap) < 0:
-        raise ValueError(f"pads and overlap must not be negative, got {(left, top, right, bottom)}, overlap {overlap}")
-    if multiple_of < 1:
-        raise ValueError(f"multiple_of must be at least 1, got {multiple_of}")
+    for v, what in ((H, "H"), (W, "W"), (multiple_of, "multiple_of")):
+        int_in(v, 1, MAX_SIDE, what)             # (a multiple_of above the largest side has no canvas)
+    for v, what in ((left, "left"), (top, "top"), (right, "right"), (bottom, "bottom"), (overlap, "overlap")):
+        int_in(v, 0, MAX_SIDE, what)
     if left == top == right == bottom == 0:
         raise ValueError("all four pads are zero: nothing to outpaint")
     left, right = _snap(W, left, right, multiple_of)
@@ -122,24 +93,20 @@ def plan_outpaint(H, W, left=0, top=0, right=0, bottom=0, overlap=0, multiple_of
 def fill_masked(image, mask):
     """`image` [B, H, W, C] with its masked pixels filled from the known ones (module docstring).  `mask` is [B, H, W], [1, H, W]
     or [H, W].  At most six launches on the current stream and no device -> host read."""
-    img = _as_f32c(_image4(_hip(image, "image"), "image"))
+    img = _as_f32c(image4(require_hip(image, "image", __name__), "image", MAX_BATCH))
     dev = img.device
     m = _mask_for(mask, img, dev)
     b, h, w, c = img.shape
-    lib = _cabi.load()
-    ws_bytes = lib.lp_fill_ws_bytes(b, h, w, c)
-    _cabi.check(min(ws_bytes, 0), "lp_fill_ws_bytes")
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    ws = workspace(_cabi.load().lp_fill_ws_bytes(b, h, w, c), dev, "lp_fill_ws_bytes")
     out = torch.empty_like(img)
-    d = _cabi.LpFillDesc(b, h, w, c, m.shape[0], 0, img.data_ptr(), m.data_ptr(), out.data_ptr(), ws.data_ptr(), ws_bytes)
-    with torch.cuda.device(dev):
-        _cabi.check(lib.lp_mask_fill(ctypes.byref(d), raw_stream(dev)), "lp_mask_fill")
+    d = _cabi.LpFillDesc(b, h, w, c, m.shape[0], 0, img.data_ptr(), m.data_ptr(), out.data_ptr(), ws.data_ptr(), ws.numel())
+    launch("lp_mask_fill", dev, ctypes.byref(d))
     return out
 
 
 def outpaint_pad(image, mask=None, left=0, top=0, right=0, bottom=0, overlap=0, multiple_of=8, fill=True):
     """(canvas [B, H', W', C], mask [Bm, H', W']) on the device (module docstring); the pads are plan_outpaint's."""
-    img = _image4(_hip(image, "image"), "image")
+    img = image4(require_hip(image, "image", __name__), "image", MAX_BATCH)
     b, h, w, c = img.shape
     plan = plan_outpaint(h, w, left, top, right, bottom, overlap, multiple_of)
     img = _as_f32c(img)
@@ -150,8 +117,7 @@ def outpaint_pad(image, mask=None, left=0, top=0, right=0, bottom=0, overlap=0, 
     d = _cabi.LpOutpaintDesc(b, h, w, c, m.shape[0] if m is not None else 0, plan.left, plan.top, plan.right, plan.bottom,
                              plan.overlap, 0, img.data_ptr(), m.data_ptr() if m is not None else None, canvas.data_ptr(),
                              mask_out.data_ptr())
-    with torch.cuda.device(dev):
-        _cabi.check(_cabi.load().lp_outpaint_pad(ctypes.byref(d), raw_stream(dev)), "lp_outpaint_pad")
+    launch("lp_outpaint_pad", dev, ctypes.byref(d))
     if fill:
         canvas = fill_masked(canvas, mask_out)
     return canvas, mask_out

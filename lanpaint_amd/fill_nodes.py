@@ -18,7 +18,7 @@ This module has its own NODE_CLASS_MAPPINGS: merge them with the others' (INTEGR
 from __future__ import annotations
 
 from . import fill as _fill
-from .detail_nodes import _hip_device
+from ._hostcall import node_device, node_mask
 
 
 class LanPaint_OutpaintPad:
@@ -51,10 +51,8 @@ class LanPaint_OutpaintPad:
                    "to LanPaint_ImageDecode.")
 
     def pad(self, image, left=0, top=0, right=0, bottom=0, overlap=16, multiple_of=8, fill=True, mask=None):
-        dev = _hip_device(image)
-        m = None
-        if mask is not None:
-            m = (mask.unsqueeze(0) if mask.ndim == 2 else mask).to(dev)
+        dev = node_device(image)
+        m = None if mask is None else node_mask(mask, dev)
         canvas, mask_out = _fill.outpaint_pad(image.to(dev), m, left, top, right, bottom, overlap, multiple_of,
                                               bool(fill))
         return canvas.to(image.device), mask_out.to(image.device)
@@ -78,9 +76,8 @@ class LanPaint_MaskFill:
                    "against the original image.")
 
     def fill(self, image, mask):
-        dev = _hip_device(image)
-        m = (mask.unsqueeze(0) if mask.ndim == 2 else mask).to(dev)
-        return (_fill.fill_masked(image.to(dev), m).to(image.device),)
+        dev = node_device(image)
+        return (_fill.fill_masked(image.to(dev), node_mask(mask, dev)).to(image.device),)
 
 
 NODE_CLASS_MAPPINGS = {"LanPaint_OutpaintPad": LanPaint_OutpaintPad, "LanPaint_MaskFill": LanPaint_MaskFill}

@@ -6,7 +6,8 @@ import torch
 
 from . import interp_rule
 from .blend import merge_video_with_mask
-from .resample import _hip_device, _resample
+from ._hostcall import node_device
+from .resample import _resample
 
 
 def _snap_mask_nearest_exact(mask_hw, out_h, out_w):
@@ -14,7 +15,7 @@ def _snap_mask_nearest_exact(mask_hw, out_h, out_w):
     goes back to the mask's own device (node tensors normally live on the host)."""
     if tuple(mask_hw.shape) == (out_h, out_w):
         return mask_hw
-    dev = _hip_device(mask_hw)
+    dev = node_device(mask_hw)
     src = mask_hw.to(device=dev, dtype=torch.float32).contiguous()
     rule = interp_rule.rule_for(mask_hw, src.reshape(1, 1, *src.shape), (out_h, out_w))      # nodes.py:1278-1287: 2-D call on the mask's device
     return _resample(src.reshape(1, 1, 1, *src.shape), 1, 1, 1, out_h, out_w, 1, rule)[0, 0, 0].to(mask_hw.device)
@@ -101,7 +102,7 @@ class LanPaint_ImageDecode:
                                                   align_corners=False).movedim(1, -1)
         if mask is None:
             return (img,)
-        dev = _hip_device(image)
+        dev = node_device(image)
         # (the mask is handed over where it lives: its device decides which of torch's index rules the reference's resample followed)
         merged = merge_video_with_mask(image.to(dev), img.to(dev), mask, blend_overlap)
         return (merged.to(image.device),)

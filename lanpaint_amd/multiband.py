@@ -28,62 +28,35 @@ import ctypes
 import torch
 
 from . import _cabi
-from ._util import _as_f32c, raw_stream
-from .detail import _mask3
+from ._hostcall import chunks, image4, int_in, launch, mask_for, require_hip, workspace
+from ._util import _as_f32c
 
 MAX_SIDE = _cabi.LP_DETAIL_MAX_SIDE
 MAX_LEVELS = 16
 WS_CAP_BYTES = 1 << 30
 
 
-def _hip(t, what):
-    if not torch.is_tensor(t) or not t.is_cuda:
-        raise RuntimeError(f"lanpaint_amd.multiband runs on a HIP device only; no CPU fallback ({what} is not on one)")
-    return t
-
-
-def _image4(t, what):
-    if t.ndim != 4:
-        raise ValueError(f"{what} must be [B, H, W, C], got {tuple(t.shape)}")
-    b, h, w, c = t.shape
-    if min(b, h, w, c) < 1 or max(h, w) > MAX_SIDE or c > _cabi.LP_DETAIL_MAX_CHANNELS:
-        raise ValueError(f"{what} {tuple(t.shape)}: sides 1..{MAX_SIDE}, channels 1..{_cabi.LP_DETAIL_MAX_CHANNELS}, batch >= 1")
-    return t
-
-
 def blend_multiband(image1, image2, mask, levels=5):
     """`image1` where the mask is 0, `image2` where it is 1, every frequency band blended over its own width (module
     docstring).  Images [B, H, W, C], `mask` [B, H, W], [1, H, W] or [H, W].  At most 2 * levels launches per chunk on the
     current stream and no device -> host read."""
-    a = _image4(_hip(image1, "image1"), "image1")
-    b = _hip(image2, "image2")
-    _hip(mask, "mask")
-    if not isinstance(levels, int) or isinstance(levels, bool):
-        raise ValueError(f"levels must be an integer, got {levels!r}")
-    if not 0 <= levels <= MAX_LEVELS:
-        raise ValueError(f"levels must lie in 0..{MAX_LEVELS}, got {levels}")
+    a = image4(require_hip(image1, "image1", __name__), "image1")
+    b = require_hip(image2, "image2", __name__)
+    require_hip(mask, "mask", __name__)
+    int_in(levels, 0, MAX_LEVELS, "levels")
     if tuple(b.shape) != tuple(a.shape):
         raise ValueError(f"image2 shape {tuple(b.shape)} does not match image1 {tuple(a.shape)}")
     a = _as_f32c(a)
     dev = a.device
     b = _as_f32c(b.to(dev))
-    m = _as_f32c(_mask3(mask).to(dev))
     B, H, W, C = a.shape
-    if m.shape[0] not in (1, B) or tuple(m.shape[1:]) != (H, W):
-        raise ValueError(f"mask shape {tuple(mask.shape)} does not match image {tuple(a.shape)}")
-    lib = _cabi.load()
-    per_image = _cabi.multiband_ws_bytes(1, H, W, C, levels)
-    chunk = min(B, 65535, max(1, WS_CAP_BYTES // per_image))
-    ws_bytes = lib.lp_multiband_ws_bytes(chunk, H, W, C, levels)
-    _cabi.check(min(ws_bytes, 0), "lp_multiband_ws_bytes")
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    m = mask_for(mask, B, H, W, dev)
+    parts = list(chunks(B, _cabi.multiband_ws_bytes(1, H, W, C, levels), WS_CAP_BYTES))
+    ws = workspace(_cabi.load().lp_multiband_ws_bytes(parts[0][1], H, W, C, levels), dev, "lp_multiband_ws_bytes")
     out = torch.empty_like(a)
-    stream = raw_stream(dev)
-    with torch.cuda.device(dev):
-        for s in range(0, B, chunk):
-            n = min(chunk, B - s)
-            mc = m if m.shape[0] == 1 else m[s:s + n]
-            d = _cabi.LpMultibandDesc(n, H, W, C, mc.shape[0], levels, a[s:s + n].data_ptr(), b[s:s + n].data_ptr(),
-                                      mc.data_ptr(), out[s:s + n].data_ptr(), ws.data_ptr(), ws_bytes)
-            _cabi.check(lib.lp_multiband_blend(ctypes.byref(d), stream), "lp_multiband_blend")
+    for s, n in parts:
+        mc = m if m.shape[0] == 1 else m[s:s + n]
+        d = _cabi.LpMultibandDesc(n, H, W, C, mc.shape[0], levels, a[s:s + n].data_ptr(), b[s:s + n].data_ptr(),
+                                  mc.data_ptr(), out[s:s + n].data_ptr(), ws.data_ptr(), ws.numel())
+        launch("lp_multiband_blend", dev, ctypes.byref(d))
     return out

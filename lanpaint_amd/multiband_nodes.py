@@ -19,7 +19,7 @@ This module has its own NODE_CLASS_MAPPINGS: merge them with the others' (INTEGR
 from __future__ import annotations
 
 from . import multiband as _multiband
-from .detail_nodes import _hip_device
+from ._hostcall import node_device, node_mask
 
 
 class LanPaint_MultibandBlend:
@@ -44,9 +44,9 @@ class LanPaint_MultibandBlend:
                    "original (image1) and the result (image2) here.")
 
     def blend(self, image1, image2, mask, levels=5):
-        dev = _hip_device(image1)
-        m = (mask.unsqueeze(0) if mask.ndim == 2 else mask).to(dev)
-        return (_multiband.blend_multiband(image1.to(dev), image2.to(dev), m, int(levels)).to(image1.device),)
+        dev = node_device(image1)
+        out = _multiband.blend_multiband(image1.to(dev), image2.to(dev), node_mask(mask, dev), int(levels))
+        return (out.to(image1.device),)
 
 
 NODE_CLASS_MAPPINGS = {"LanPaint_MultibandBlend": LanPaint_MultibandBlend}

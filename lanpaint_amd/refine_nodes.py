@@ -16,7 +16,7 @@ This module has its own NODE_CLASS_MAPPINGS: merge them with the others' (INTEGR
 from __future__ import annotations
 
 from . import refine as _refine
-from .detail_nodes import _hip_device
+from ._hostcall import node_device, node_mask
 
 
 class LanPaint_MaskRefine:
@@ -49,9 +49,8 @@ class LanPaint_MaskRefine:
                    "the multiband blend.")
 
     def refine(self, image, mask, grow=0, radius=8, eps=1e-3):
-        dev = _hip_device(image)
-        m = (mask.unsqueeze(0) if mask.ndim == 2 else mask).to(dev)
-        return (_refine.refine_mask(image.to(dev), m, int(radius), float(eps), int(grow)).to(image.device),)
+        dev = node_device(image)
+        return (_refine.refine_mask(image.to(dev), node_mask(mask, dev), int(radius), float(eps), int(grow)).to(image.device),)
 
 
 NODE_CLASS_MAPPINGS = {"LanPaint_MaskRefine": LanPaint_MaskRefine}

@@ -22,12 +22,12 @@ folded into one int32 [F, H, W]; frames are independent there, so chunking canno
 from __future__ import annotations
 
 import ctypes
-import math
 
 import torch
 
 from . import _cabi, videomask
-from ._util import _as_f32c, raw_stream
+from ._hostcall import float_in, int_in, launch, require_hip
+from ._util import _as_f32c
 
 MAX_SIDE = _cabi.LP_VMASK_MAX_SIDE
 MAX_MEDIAN = _cabi.LP_STAB_MAX_MEDIAN
@@ -35,69 +35,43 @@ MAX_SMOOTH = _cabi.LP_STAB_MAX_SMOOTH
 MAX_GROW = _cabi.LP_STAB_MAX_GROW
 MAX_FEATHER = _cabi.LP_STAB_MAX_FEATHER
 WS_CAP_BYTES = 1 << 30
-_EDT_BYTES_PER_PIXEL = 16           # keyframe_edt's buffers: two int32 planes and one fp64 per pixel
-
-
-def _hip(t, what):
-    if not torch.is_tensor(t) or not t.is_cuda:
-        raise RuntimeError(f"lanpaint_amd.stabilize runs on a HIP device only; no CPU fallback ({what} is not on one)")
-    return t
-
-
-def _int_in(v, lo, hi, what):
-    if not isinstance(v, int) or isinstance(v, bool) or not lo <= v <= hi:
-        raise ValueError(f"{what} must be an integer in {lo}..{hi}, got {v!r}")
-    return v
-
-
-def _float_in(v, lo, hi, what):
-    if isinstance(v, bool) or not isinstance(v, (int, float)) or math.isnan(v) or not lo <= v <= hi:
-        raise ValueError(f"{what} must be a number in {lo}..{hi}, got {v!r}")
-    return float(v)
 
 
 def signed_d2(mask):
     """Stage 1 for `mask` fp32 [F, H, W] on a HIP device: int32 [F, H, W], +d2 to the nearest background pixel on the foreground
     (v >= 0.5), -d2 to the nearest foreground pixel on the background, +-LP_STAB_Q_FAR on a full or an empty frame.  The frames
-    go through videomask.keyframe_edt in chunks under WS_CAP_BYTES; one lp_mask_signed_d2 launch per chunk."""
+    go through videomask.edt_chunks under WS_CAP_BYTES; one lp_mask_signed_d2 launch per chunk."""
     F, H, W = mask.shape
-    dev = mask.device
-    lib = _cabi.load()
-    q = torch.empty((F, H, W), dtype=torch.int32, device=dev)
-    chunk = min(F, 65535, max(1, WS_CAP_BYTES // (_EDT_BYTES_PER_PIXEL * H * W)))
-    with torch.cuda.device(dev):
-        for s in range(0, F, chunk):
-            n = min(chunk, F - s)
-            d2, _, _ = videomask.keyframe_edt(mask[s:s + n])
-            _cabi.check(lib.lp_mask_signed_d2(d2.data_ptr(), n, H, W, q[s:s + n].data_ptr(), raw_stream(dev)), "lp_mask_signed_d2")
+    q = torch.empty((F, H, W), dtype=torch.int32, device=mask.device)
+    for s, n, d2 in videomask.edt_chunks(mask, WS_CAP_BYTES):
+        launch("lp_mask_signed_d2", mask.device, d2.data_ptr(), n, H, W, q[s:s + n].data_ptr())
     return q
 
 
 def stabilize_q(q, median=1, smooth=2, grow=0.0, feather=0.0):
     """Stages 2 to 5 on the signed squared distances `q` int32 [F, H, W] (from `signed_d2`): fp32 [F, H, W].  One launch."""
-    _int_in(median, 0, MAX_MEDIAN, "median")
-    _int_in(smooth, 0, MAX_SMOOTH, "smooth")
-    grow = _float_in(grow, -MAX_GROW, MAX_GROW, "grow")
-    feather = _float_in(feather, 0, MAX_FEATHER, "feather")
-    _hip(q, "q")
+    int_in(median, 0, MAX_MEDIAN, "median")
+    int_in(smooth, 0, MAX_SMOOTH, "smooth")
+    grow = float_in(grow, -MAX_GROW, MAX_GROW, "grow")
+    feather = float_in(feather, 0, MAX_FEATHER, "feather")
+    require_hip(q, "q", __name__)
     if q.dtype != torch.int32 or q.ndim != 3 or not q.is_contiguous():
         raise ValueError("q must be a contiguous int32 [F, H, W]")
     F, H, W = q.shape
     out = torch.empty((F, H, W), dtype=torch.float32, device=q.device)
     d = _cabi.LpStabilizeDesc(F, H, W, median, smooth, 0, grow, feather, q.data_ptr(), out.data_ptr())
-    with torch.cuda.device(q.device):
-        _cabi.check(_cabi.load().lp_mask_stabilize(ctypes.byref(d), raw_stream(q.device)), "lp_mask_stabilize")
+    launch("lp_mask_stabilize", q.device, ctypes.byref(d))
     return out
 
 
 def stabilize_masks(mask, median=1, smooth=2, grow=0.0, feather=0.0):
     """`mask` [F, H, W] (or one frame [H, W]) stabilized along time (module docstring); fp32 [F, H, W] back, on the mask's
     device.  The EDT's launches per chunk of frames, one fold per chunk, one temporal launch; no device -> host read."""
-    _int_in(median, 0, MAX_MEDIAN, "median")
-    _int_in(smooth, 0, MAX_SMOOTH, "smooth")
-    _float_in(grow, -MAX_GROW, MAX_GROW, "grow")
-    _float_in(feather, 0, MAX_FEATHER, "feather")
-    _hip(mask, "mask")
+    int_in(median, 0, MAX_MEDIAN, "median")
+    int_in(smooth, 0, MAX_SMOOTH, "smooth")
+    float_in(grow, -MAX_GROW, MAX_GROW, "grow")
+    float_in(feather, 0, MAX_FEATHER, "feather")
+    require_hip(mask, "mask", __name__)
     if mask.ndim == 2:
         mask = mask.unsqueeze(0)
     if mask.ndim != 3:

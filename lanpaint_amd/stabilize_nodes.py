@@ -15,7 +15,7 @@ This module has its own NODE_CLASS_MAPPINGS: merge them with the others' (INTEGR
 from __future__ import annotations
 
 from . import stabilize as _stabilize
-from .detail_nodes import _hip_device
+from ._hostcall import node_device
 
 
 class LanPaint_VideoMaskStabilize:
@@ -49,7 +49,7 @@ class LanPaint_VideoMaskStabilize:
                    "the encode and the Detailer crops. Smoothing alone does not repair dropped frames; the median does.")
 
     def stabilize(self, mask, median_radius=1, smooth_radius=2, grow=0.0, feather=0.0):
-        dev = _hip_device(mask)
+        dev = node_device(mask)
         out = _stabilize.stabilize_masks(mask.to(dev), int(median_radius), int(smooth_radius), float(grow), float(feather))
         return (out.to(mask.device),)
 

@@ -24,7 +24,8 @@ import numpy as np
 import torch
 
 from . import _cabi
-from ._util import device_tables, raw_stream
+from ._hostcall import chunks, launch
+from ._util import device_tables
 
 # one lp_vmask_frame of include/lanpaint_hip.h
 FRAME_DTYPE = np.dtype([("kind", "<i4"), ("key_lo", "<i4"), ("key_hi", "<i4"), ("sx1", "<i4"), ("sy1", "<i4"),
@@ -183,9 +184,20 @@ def keyframe_edt(keys):
     sdf = torch.empty((k, h, w), dtype=torch.float64, device=dev)
     csum = torch.empty((k, 3), dtype=torch.int64, device=dev)
     d = _cabi.LpVmaskEdtDesc(k, h, w, 0, keys.data_ptr(), d2.data_ptr(), sdf.data_ptr(), csum.data_ptr())
-    with torch.cuda.device(dev):
-        _cabi.check(_cabi.load().lp_vmask_edt(ctypes.byref(d), raw_stream(dev)), "lp_vmask_edt")
+    launch("lp_vmask_edt", dev, ctypes.byref(d))
     return d2, sdf, csum
+
+
+EDT_BYTES_PER_PIXEL = 16              # what keyframe_edt allocates: two int32 planes and one fp64 per pixel
+
+
+def edt_chunks(mask, cap_bytes):
+    """keyframe_edt over the frames of a float32 HIP tensor [F, h, w], as many at a time as keep its buffers under `cap_bytes`
+    (at least one): yields (start, count, d2 of those frames).  Frames are independent, so chunking cannot change a bit."""
+    k, h, w = mask.shape
+    _check_side(h, w)
+    for s, n in chunks(k, EDT_BYTES_PER_PIXEL * h * w, cap_bytes):
+        yield s, n, keyframe_edt(mask[s:s + n])[0]
 
 
 def morph_frames(keys, plan, sdf=None, codes=False):
@@ -202,8 +214,7 @@ def morph_frames(keys, plan, sdf=None, codes=False):
         assert sdf.dtype == torch.float64 and tuple(sdf.shape) == (k, h, w)
     d = _cabi.LpVmaskMorphDesc(n, k, h, w, _cabi.LP_VMASK_OUT_U8 if codes else 0, 0, table.data_ptr(), keys.data_ptr(),
                                sdf.data_ptr() if sdf is not None else None, out.data_ptr())
-    with torch.cuda.device(dev):
-        _cabi.check(_cabi.load().lp_vmask_morph(ctypes.byref(d), raw_stream(dev)), "lp_vmask_morph")
+    launch("lp_vmask_morph", dev, ctypes.byref(d))
     return out
 
 
@@ -222,8 +233,7 @@ def resize_codes(codes, size):
     out = torch.empty((n, out_h, out_w), dtype=torch.float32, device=dev)
     d = _cabi.LpVmaskResizeDesc(n, h, w, out_h, out_w, kx.shape[1], ky.shape[1], 0, codes.data_ptr(),
                                 bx.data_ptr(), kx.data_ptr(), by.data_ptr(), ky.data_ptr(), out.data_ptr())
-    with torch.cuda.device(dev):
-        _cabi.check(_cabi.load().lp_vmask_resize(ctypes.byref(d), raw_stream(dev)), "lp_vmask_resize")
+    launch("lp_vmask_resize", dev, ctypes.byref(d))
     return out
 
 

@@ -8,7 +8,7 @@ import numpy as np
 import pytest
 import torch
 
-from lanpaint_amd import _cabi, refine, refine_nodes
+from lanpaint_amd import _cabi, refine, refine_nodes, videomask
 from lanpaint_amd._util import raw_stream
 from tests import refine_ref as ref
 
@@ -189,6 +189,44 @@ def test_chunks_give_the_bits_of_one_call(monkeypatch):
         assert (_bits(_refine(guide, mask[:1], 6, 1e-3)) == _bits(_check(guide, mask[:1], 6, 1e-3, "one mask"))).all(), images
     monkeypatch.setattr(refine, "WS_CAP_BYTES", 1)                  # always at least one image per chunk
     assert (_bits(_refine(guide, mask, 6, 1e-3)) == _bits(whole)).all()
+
+
+def _drifting_blobs(F, H, W, seed):
+    """tests/test_gpu_stabilize.py's blobs: a disc that drifts and jitters, an empty frame and a stray blob in it."""
+    rng = _rng(F, H, W, seed)
+    yy, xx = np.mgrid[:H, :W]
+    m = np.zeros((F, H, W), dtype=np.float32)
+    for t in range(F):
+        cy, cx = H / 2 + rng.normal(0, 1), W / 3 + 0.7 * t + rng.normal(0, 1)
+        m[t] = (yy - cy) ** 2 + (xx - cx) ** 2 <= (min(H, W) / 3 + rng.normal(0, 1)) ** 2
+    m[F // 3] = 0.0
+    m[F // 2, :2, -3:] = 1.0
+    return m
+
+
+def test_grow_chunks_give_the_bits_of_one_call(monkeypatch):
+    """grow_mask hands the EDT no more frames at a time than stay under WS_CAP_BYTES, and chunking changes no bit."""
+    F, H, W = 7, 21, 40
+    mask = _drifting_blobs(F, H, W, 15)
+    t = torch.from_numpy(mask).to(DEV)
+    seen, edt = [], videomask.keyframe_edt
+
+    def recorder(keys):
+        seen.append(int(keys.shape[0]))
+        return edt(keys)
+    monkeypatch.setattr(videomask, "keyframe_edt", recorder)
+    per_frame = videomask.EDT_BYTES_PER_PIXEL * H * W
+    for grow in (3, -2):
+        whole = refine.grow_mask(t, grow).cpu().numpy()
+        assert (_bits(whole) == _bits(np.stack([ref.grow_ref(m, grow) for m in mask]))).all(), grow
+        for frames, cap in ((1, per_frame + 8), (2, 2 * per_frame + 8), (3, 3 * per_frame + 8), (0, 1)):
+            monkeypatch.setattr(refine, "WS_CAP_BYTES", cap)
+            del seen[:]
+            got = refine.grow_mask(t, grow).cpu().numpy()
+            print(f"GROW_CHUNKS grow={grow} cap={cap} calls={seen}")
+            assert (_bits(got) == _bits(whole)).all(), (grow, frames)
+            assert max(seen) <= max(1, frames) and sum(seen) == F, (grow, frames, seen)
+        monkeypatch.setattr(refine, "WS_CAP_BYTES", 1 << 30)
 
 
 def test_wrapper_takes_views_half_precision_and_a_plain_mask():

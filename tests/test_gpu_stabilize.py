@@ -236,7 +236,7 @@ def test_chunks_give_the_bits_of_one_call(monkeypatch):
     t = torch.from_numpy(mask).to(DEV)
     whole = stabilize.stabilize_masks(t, 1, 2, 0.5, 3.0).cpu().numpy()
     _same(whole, ref.stabilize_ref(mask, 1, 2, 0.5, 3.0), "one chunk")
-    per_frame = 16 * 21 * 40
+    per_frame = videomask.EDT_BYTES_PER_PIXEL * 21 * 40
     for frames in (1, 2, 3):
         monkeypatch.setattr(stabilize, "WS_CAP_BYTES", frames * per_frame + 8)
         _same(stabilize.stabilize_masks(t, 1, 2, 0.5, 3.0).cpu().numpy(), whole, frames)
