@@ -1333,6 +1333,125 @@ typedef struct lp_stabilize_desc {
 } lp_stabilize_desc;
 LP_API int lp_mask_stabilize(const lp_stabilize_desc* desc, void* stream);
 
+/* ---- Grain match (beyond the reference) -----------------------------------------------------------------------------------------
+ * What the VAE decoder returns under the mask is clean; the photograph or video frame around it carries sensor noise, film grain
+ * or compression noise, and on video the clean area reads as a patch that sits still while the grain around it moves.  These four
+ * entries measure the grain (lp_grain_stats), turn the two measurements into one amplitude per image, channel and tone band and
+ * one grain size per image (lp_grain_fit), and add a synthesized grain under the mask (lp_grain_apply; its noise alone:
+ * lp_grain_field).  Last in the chain: ... -> stitch -> multiband blend -> grain match.  Everything stays on the device; nothing is
+ * read back.  Exact integers first, then fp64 and fp32 with every operation rounded on its own: the same bits on every run, for
+ * every tile, block and chunk.  Sides 1..LP_DETAIL_MAX_SIDE, channels 1..LP_DETAIL_MAX_CHANNELS, batch 1..65535.
+ *
+ * Kernels  per grain size s = 0, 1, 2 the kernel k_s is the delta, [1 2 1] x [1 2 1] and [1 4 6 4 1] x [1 4 6 4 1], unnormalised.
+ *          B3 = k_1.  N3 = [[1,-2,1],[-2,4,-2],[1,-2,1]] (Immerkaer's noise operator, blind to planes); N5 = N3 with its taps two
+ *          pixels apart.  With S1_s = sum (N3 * k_s)^2 and S2_s = sum (N5 * k_s)^2:
+ *                        s = 0    s = 1    s = 2
+ *            sum k^2         1       36     4900
+ *            S1             36       36      784
+ *            S2             36      784    39204
+ *
+ * stage 1  lp_grain_stats, integers.  q = the 8-bit codes of image i, channel c, as lp_mask_refine takes them: t = (v > 0) ?
+ *          min(v, 1) : 0 (a NaN gives 0), q = (int)(t * 255.0f + 0.5f), product and sum rounded on their own.  Pixel (y, x) takes
+ *          part when its 5 x 5 window lies inside the image, max - min of q over that window is <= flat (0..255; 255 keeps
+ *          everything: the texture reject), and its region test holds:
+ *            LP_GRAIN_REGION_ALL      no mask
+ *            LP_GRAIN_REGION_OUTSIDE  every mask element with |y' - y| <= margin and |x' - x| <= margin inside the image is
+ *                                     <= 0.5 (lp_color_stats' rule; margin 0..LP_GRAIN_MAX_MARGIN)
+ *            LP_GRAIN_REGION_INSIDE   every mask element of the 5 x 5 window is > 0.5
+ *          (a NaN in the mask fails either test).  Per pixel mu16 = sum B3 q over the 3 x 3 window (0..4080), band = (mu16 *
+ *          LP_GRAIN_BANDS) / 4081 (integer division), e1 = sum N3 q, e2 = sum N5 q.  stats is int64 [batch, channels,
+ *          LP_GRAIN_BANDS, 3] = {n, sum e1^2, sum e2^2}.  A side under 5 gives all zeros.  One block per 16 x 64 tile and group
+ *          of four channels (codes packed four to a word in LDS); a block adds into 32-bit LDS counters and then into stats with
+ *          64-bit integer atomics, after a memset of stats on the same stream: integer sums, the same bits in any order.
+ *
+ * stage 2  lp_grain_fit, fp64, every operation rounded on its own; one launch, a block per clip.  gen [batch, channels, K, 3]
+ *          (the image, LP_GRAIN_REGION_INSIDE) and ref [ref_batch, channels, K, 3] are stage 1 tables.  L = clip_frames (0: L =
+ *          batch; L must divide batch); image i belongs to clip i / L.
+ *            pool    P = 0.0 + (double)row, the rows of the clip's frames in ascending order, per entry.  ref is pooled over the
+ *                    same frames when ref_batch == batch and over all its rows otherwise (a separate grain plate).
+ *            energy  per (c, k): valid when P.n >= LP_GRAIN_MIN_COUNT; E_j = P.e_j / P.n.  An invalid band takes E_1, E_2 of the
+ *                    nearest valid band of its channel, the lower index on a tie.  A channel without a valid ref band has need
+ *                    0; a channel without a valid gen band has Egen = 0.
+ *            need    need_j = max(0, Eref_j - Egen_j).
+ *            size    size in 0..2 is taken as given.  size == -1: A = sum need_1, Bq = sum need_2 over (c, k) ascending from 0.0;
+ *                    A <= 0: size 0 and every amplitude 0;  3 Bq < 14 A: size 0;  else Bq < 33 A: size 1;  else size 2 (the
+ *                    geometric means of S2 / S1 of neighbouring sizes).
+ *            amp     a = strength * sqrt((need_1 + need_2) / (double)(V * (S1_s + S2_s))), V = LP_GRAIN_WHITE_VAR;
+ *                    a = min(a, LP_GRAIN_MAX_STD / sqrt((double)(V * sum k_s^2)));  amp = (float)(a / 255.0).
+ *          amp is fp32 [batch, channels, K], size int32 [batch]; every frame of a clip gets its clip's values.
+ *
+ * field    w(frame, y, x, c), -2 <= y < height + 2, -2 <= x < width + 2: the Philox4x32-10 block (Random123) with counter
+ *          ((y + 2) * (width + 4) + (x + 2) [64 bit], frame * 16 + c / 4 [64 bit]) and key seed; of its word c % 4, the sum of
+ *          the four bytes minus 510 (variance LP_GRAIN_WHITE_VAR = 4 * (256^2 - 1) / 12).  monochrome: c = 0 for every channel.
+ *          frame = frame0 + i.  g = sum k_s(dy, dx) w(y + dy, x + dx), an exact integer that depends on (seed, frame, y, x, c,
+ *          width, s) only.  lp_grain_field writes g as int32 [batch, height, width, channels].
+ *
+ * stage 3  lp_grain_apply, fp32, every operation rounded on its own.  mu16 as in stage 1 but with coordinates clamped to the
+ *          image, on `image`; K = LP_GRAIN_BANDS:
+ *            u = min(max((float)(mu16 * K) / 4080.0f - 0.5f, 0), K - 1);  k0 = min((int)u, K - 2);  f = u - (float)k0
+ *            a = amp[k0] + f * (amp[k0 + 1] - amp[k0]);  m = (mask > 0) ? min(mask, 1) : 0 (a NaN gives 0);  t = m * a
+ *            out = image + t * (float)g, and where t == 0 out is image's bits (no clamp of the result)
+ *          s = size[i], read on the device.  One launch: a block per 16 x 64 tile and group of four channels computes each white
+ *          value of its lattice once (one Philox block serves four channels), filters along x and then along y through LDS.
+ *
+ * LP_E_INVALID: null pointer, batch <= 0, a side or the channel count outside the limits, mask_batch not 1 or batch, margin,
+ * flat, region, size, strength (NaN included), clip_frames < 0 or not a divisor of batch, ref_batch <= 0, frame0 outside
+ * 0..LP_GRAIN_MAX_FRAME0, out == image; LP_E_UNSUPPORTED: batch (or ref_batch) > 65535.  All checked before any HIP call.          */
+#define LP_GRAIN_BANDS      8
+#define LP_GRAIN_MIN_COUNT  64
+#define LP_GRAIN_WHITE_VAR  21845
+#define LP_GRAIN_MAX_STD    64
+#define LP_GRAIN_MAX_MARGIN 25
+#define LP_GRAIN_TILE_H     16
+#define LP_GRAIN_TILE_W     64
+#define LP_GRAIN_REGION_ALL     0
+#define LP_GRAIN_REGION_OUTSIDE 1
+#define LP_GRAIN_REGION_INSIDE  2
+#define LP_GRAIN_SIZE_AUTO  -1
+#define LP_GRAIN_MAX_FRAME0 (1 << 30)
+
+typedef struct lp_grain_stats_desc {
+    int32_t batch, height, width, channels;
+    int32_t mask_batch, margin, flat, region;
+    const float* image;     /* [batch, height, width, channels] fp32                                             */
+    const float* mask;      /* [mask_batch, height, width] fp32; may be null with LP_GRAIN_REGION_ALL               */
+    int64_t*     stats;     /* out, [batch, channels, LP_GRAIN_BANDS, 3]                                          */
+} lp_grain_stats_desc;
+LP_API int lp_grain_stats(const lp_grain_stats_desc* desc, void* stream);
+
+typedef struct lp_grain_fit_desc {
+    int32_t batch, ref_batch, channels, clip_frames;
+    int32_t size, reserved0;      /* LP_GRAIN_SIZE_AUTO or 0..2                                                  */
+    double  strength;             /* 0..2                                                                        */
+    const int64_t* gen;
+    const int64_t* ref;
+    float*   amp;                 /* out, [batch, channels, LP_GRAIN_BANDS]                                       */
+    int32_t* size_out;            /* out, [batch]                                                                */
+} lp_grain_fit_desc;
+LP_API int lp_grain_fit(const lp_grain_fit_desc* desc, void* stream);
+
+typedef struct lp_grain_field_desc {
+    int32_t  batch, height, width, channels;
+    int32_t  size, monochrome;    /* size 0..2                                                                   */
+    int64_t  frame0;
+    uint64_t seed;
+    int32_t* out;                 /* [batch, height, width, channels]                                            */
+} lp_grain_field_desc;
+LP_API int lp_grain_field(const lp_grain_field_desc* desc, void* stream);
+
+typedef struct lp_grain_apply_desc {
+    int32_t  batch, height, width, channels;
+    int32_t  mask_batch, monochrome;
+    int64_t  frame0;
+    uint64_t seed;
+    const float*   image;         /* [batch, height, width, channels] fp32                                       */
+    const float*   mask;          /* [mask_batch, height, width] fp32                                            */
+    const float*   amp;           /* [batch, channels, LP_GRAIN_BANDS] (lp_grain_fit)                            */
+    const int32_t* size;          /* [batch], each 0..2 (lp_grain_fit)                                           */
+    float*         out;           /* [batch, height, width, channels]                                            */
+} lp_grain_apply_desc;
+LP_API int lp_grain_apply(const lp_grain_apply_desc* desc, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -344,6 +344,36 @@ class LpStabilizeDesc(C.Structure):
                 ("grow", C.c_double), ("feather", C.c_double), ("q", C.c_void_p), ("out", C.c_void_p)]
 
 
+LP_GRAIN_BANDS, LP_GRAIN_MIN_COUNT, LP_GRAIN_WHITE_VAR, LP_GRAIN_MAX_STD, LP_GRAIN_MAX_MARGIN = 8, 64, 21845, 64, 25
+LP_GRAIN_TILE_H, LP_GRAIN_TILE_W = 16, 64
+LP_GRAIN_REGION_ALL, LP_GRAIN_REGION_OUTSIDE, LP_GRAIN_REGION_INSIDE = 0, 1, 2
+LP_GRAIN_SIZE_AUTO, LP_GRAIN_MAX_FRAME0 = -1, 1 << 30
+
+
+class LpGrainStatsDesc(C.Structure):
+    _fields_ = [("batch", C.c_int32), ("height", C.c_int32), ("width", C.c_int32), ("channels", C.c_int32),
+                ("mask_batch", C.c_int32), ("margin", C.c_int32), ("flat", C.c_int32), ("region", C.c_int32),
+                ("image", C.c_void_p), ("mask", C.c_void_p), ("stats", C.c_void_p)]
+
+
+class LpGrainFitDesc(C.Structure):
+    _fields_ = [("batch", C.c_int32), ("ref_batch", C.c_int32), ("channels", C.c_int32), ("clip_frames", C.c_int32),
+                ("size", C.c_int32), ("reserved0", C.c_int32), ("strength", C.c_double),
+                ("gen", C.c_void_p), ("ref", C.c_void_p), ("amp", C.c_void_p), ("size_out", C.c_void_p)]
+
+
+class LpGrainFieldDesc(C.Structure):
+    _fields_ = [("batch", C.c_int32), ("height", C.c_int32), ("width", C.c_int32), ("channels", C.c_int32),
+                ("size", C.c_int32), ("monochrome", C.c_int32), ("frame0", C.c_int64), ("seed", C.c_uint64),
+                ("out", C.c_void_p)]
+
+
+class LpGrainApplyDesc(C.Structure):
+    _fields_ = [("batch", C.c_int32), ("height", C.c_int32), ("width", C.c_int32), ("channels", C.c_int32),
+                ("mask_batch", C.c_int32), ("monochrome", C.c_int32), ("frame0", C.c_int64), ("seed", C.c_uint64),
+                ("image", C.c_void_p), ("mask", C.c_void_p), ("amp", C.c_void_p), ("size", C.c_void_p), ("out", C.c_void_p)]
+
+
 def lp_components_ws_bytes(height, width):
     """LP_COMPONENTS_WS_BYTES of include/lanpaint_hip.h."""
     return ((int(height) * int(width) + 1023) // 1024) * 4100
@@ -425,6 +455,10 @@ EXPORTS = {
     "lp_refine_ws_bytes": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     "lp_mask_signed_d2": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "lp_mask_stabilize": (C.c_int, [C.POINTER(LpStabilizeDesc), C.c_void_p]),
+    "lp_grain_stats": (C.c_int, [C.POINTER(LpGrainStatsDesc), C.c_void_p]),
+    "lp_grain_fit": (C.c_int, [C.POINTER(LpGrainFitDesc), C.c_void_p]),
+    "lp_grain_field": (C.c_int, [C.POINTER(LpGrainFieldDesc), C.c_void_p]),
+    "lp_grain_apply": (C.c_int, [C.POINTER(LpGrainApplyDesc), C.c_void_p]),
 }
 
 

@@ -61,6 +61,10 @@ int mask_refine_dispatch(const lp_refine_desc* d, hipStream_t stream);
 int64_t refine_ws_bytes(int batch, int height, int width, int channels, int radius);
 int mask_signed_d2_dispatch(const int32_t* d2, int frames, int height, int width, int32_t* q, hipStream_t stream);
 int mask_stabilize_dispatch(const lp_stabilize_desc* d, hipStream_t stream);
+int grain_stats_dispatch(const lp_grain_stats_desc* d, hipStream_t stream);
+int grain_fit_dispatch(const lp_grain_fit_desc* d, hipStream_t stream);
+int grain_field_dispatch(const lp_grain_field_desc* d, hipStream_t stream);
+int grain_apply_dispatch(const lp_grain_apply_desc* d, hipStream_t stream);
 int reshape_mask_dispatch(const float* src, int sb, int sc, int sf, int sh, int sw, float* dst, int db, int dc, int df,
                           int dh, int dw, int taps, int flags, hipStream_t stream);
 }  // namespace lp
@@ -205,6 +209,14 @@ int lp_mask_signed_d2(const int32_t* d2, int32_t frames, int32_t height, int32_t
 }
 
 int lp_mask_stabilize(const lp_stabilize_desc* desc, void* stream) { return lp::mask_stabilize_dispatch(desc, as_stream(stream)); }
+
+int lp_grain_stats(const lp_grain_stats_desc* desc, void* stream) { return lp::grain_stats_dispatch(desc, as_stream(stream)); }
+
+int lp_grain_fit(const lp_grain_fit_desc* desc, void* stream) { return lp::grain_fit_dispatch(desc, as_stream(stream)); }
+
+int lp_grain_field(const lp_grain_field_desc* desc, void* stream) { return lp::grain_field_dispatch(desc, as_stream(stream)); }
+
+int lp_grain_apply(const lp_grain_apply_desc* desc, void* stream) { return lp::grain_apply_dispatch(desc, as_stream(stream)); }
 
 int lp_finalize(const lp_final_desc* desc, void* stream) { return lp::finalize_dispatch(desc, as_stream(stream)); }
 
