@@ -1452,6 +1452,113 @@ typedef struct lp_grain_apply_desc {
 } lp_grain_apply_desc;
 LP_API int lp_grain_apply(const lp_grain_apply_desc* desc, void* stream);
 
+/* ---- Video mask propagate (beyond the reference) ----------------------------------------------------------------------------------
+ * One mask painted on one frame of a clip follows the picture's motion through the other frames.  The video mask editor morphs
+ * between painted keyframes and follows a subject's centroid, not its outline; the stabilize is not motion-compensated.  These
+ * entries are the first link of the chain:  one painted mask + the video -> propagate -> stabilize -> refine -> encode / Detailer
+ * crops.  A block matching, weighted by the mask, measures the motion from a frame s to the next frame t (one frame further from
+ * the key); a map of key-frame positions is carried along that motion and the key mask is sampled through it.  Everything stays on
+ * the device; nothing is read back.  All of it is integer arithmetic: the same bits on every run, for every tile and every chunk
+ * of frames.  Not handled: several keyframes, occlusion, re-anchoring against drift.
+ *   sides 1..LP_VMASK_MAX_SIDE; levels L in 1..LP_PROP_MAX_LEVELS; search R in 1..LP_PROP_MAX_SEARCH; smooth 0..LP_PROP_MAX_SMOOTH
+ *   B = LP_PROP_BLOCK = 8; a block's window is the block grown by LP_PROP_HALO = 4 on every side and cut at the image border (at
+ *   most 16 x 16); vectors and positions are in units of 1 / LP_PROP_SUBPEL = 1/16 pixel, (y, x) pairs of int32.  `>>` is the
+ *   arithmetic shift (a floor); clamp(i) holds a coordinate inside its plane.
+ *
+ * 1 luma      The 8-bit codes of image values are taken as lp_mask_refine takes them: t = (v > 0) ? min(v, 1) : 0 (a NaN gives 0),
+ *             code = (int)(t * 255.0f + 0.5f), product and sum rounded on their own.  channels >= 3: Y = (77 R + 150 G + 29 B +
+ *             128) >> 8 on the first three channels; channels 1 or 2: Y = the code of channel 0.  uint8 [frames, height, width].
+ * 2 pyramids  Level l + 1 of a plane of h x w is ceil(h / 2) x ceil(w / 2); pixel (y, x) is (a + b + c + d + 2) >> 2 of the luma
+ *             at (clamp(2y + i), clamp(2x + j)), i, j in {0, 1}, of the level below.  The mask pyramid of a frame is the OR of
+ *             the mask bits over the same footprints.  Level l of a height x width plane is ceil(height / 2^l) x ceil(width / 2^l).
+ *             A frame's pyramid is one byte string: level l, row-major, starts LP_PROP_ALIGN-aligned behind level l - 1;
+ *             lp_prop_pyramid_ws_bytes(1, ...) is a frame's stride.
+ * 3 one step  s -> t with the mask bits m of s known, levels l = L - 1 down to 0, on the grid of ceil(h_l / 8) x ceil(w_l / 8) blocks:
+ *   predictor p (integer pixels): 0 at level L - 1, else per component p = 2 * ((v + 8) >> 4) of the final vector v of the parent
+ *             block (by >> 1, bx >> 1), clamped to the parent's grid.
+ *   valid     the block's window holds at least LP_PROP_MIN_PIXELS = 16 mask pixels of this level.
+ *   match     (lp_prop_match; valid blocks) for oy, ox in -R..R in raster order, idx = (oy + R) (2R + 1) + ox + R:
+ *             S(oy, ox) = sum over the window's mask pixels (y, x) of |Ys(y, x) - Yt(clamp(y + py + oy), clamp(x + px + ox))|,
+ *             cost = S + smooth * (|oy| + |ox|); the winner has the least key = cost << 12 | (|oy| + |ox|) << 8 | idx, and
+ *             v = 16 (p + o).  S <= 256 * 255 and cost < 2^17, so the key stays inside 32 bits.
+ *             Level 0 only, per axis, when the winner is not at -R or R on that axis and S0 = S(winner) != 0: with cm, cp the S
+ *             one step below and above on that axis and d = cm + cp - 2 S0:  d <= 0 adds nothing, else v += sign(cm - cp) *
+ *             min(|8 (cm - cp)| / d, 8), the division truncating.  (S0 == 0 adds nothing: a noise-free whole-pixel shift and a
+ *             still video are tracked exactly.)  An invalid block holds v = 16 p.
+ *   fill      (lp_prop_fill) LP_PROP_FILL_ITERS = 3 Jacobi passes: an invalid block with n >= 1 valid blocks among its 3 x 3
+ *             neighbours inside the grid takes per component floor((2 sum + n) / (2 n)) of their vectors and becomes valid for
+ *             the next pass.  Blocks still invalid keep 16 p: an empty mask gives the zero field without any read-back.
+ *   median    then per component the median of the 3 x 3 neighbourhood, the border replicated: the level's final field.
+ *   per pixel (lp_prop_advance, level 0) per axis u = 2x - 7, b0 = u >> 4, f = u - 16 b0, blocks b0 and b0 + 1 clamped to the grid;
+ *             V = ((16 - fy) * ((16 - fx) v00 + fx v01) + fy * ((16 - fx) v10 + fx v11) + 128) >> 8.
+ *   advance   P_key(y, x) = (16 y, 16 x).  P_t(y, x) = (bil(P_s, 16 y - Vy, 16 x - Vx) + 128) >> 8 per component, where bil(A, qy,
+ *             qx) clamps q to 0..16 (n - 1) per axis, i = q >> 4, f = q & 15, i1 = min(i + 1, n - 1) and returns (16 - fy) * ((16 -
+ *             fx) A[iy, ix] + fx A[iy, ix1]) + fy * ((16 - fx) A[iy1, ix] + fx A[iy1, ix1]).  The mask code of t is c = bil(b, P_t)
+ *             in 0..256 with b the key mask binarised at >= 0.5 (a NaN gives 0); out = c / 256 as fp32; the bits that weight the
+ *             next step are c >= 128.  Positions are below 2^18 and their weighted sums below 2^26: inside an int32.
+ * The frames behind the key and the frames in front of it are two independent chains that start from the key.  The key frame's own
+ * output is its binarised mask (lp_prop_key_mask).  What follows from the rule: one frame returns the binarised mask; an empty
+ * mask gives exactly 0 and a full mask exactly 1.0 on every frame; a video of equal frames returns the binarised key mask on every
+ * frame.
+ * Launches (csrc/propagate_kernel.hip): lp_prop_luma 1 + (levels - 1) for all its frames; lp_prop_key_mask, lp_prop_match,
+ * lp_prop_fill and lp_prop_advance one each, so a step is 2 L + 1 launches.  lp_prop_match: one wave per block; the source window,
+ * its per-byte mask and the (16 + 2R)^2 target patch in LDS, the candidates over the lanes, v_sad_u8 on four pixels at a time.
+ * LP_E_INVALID: null pointer, a side, levels, level, search, smooth, channels or grid outside its range, frames <= 0, parent null
+ * below the top level or not null at it, pos_dst == pos_src; LP_E_UNSUPPORTED: frames > 65535.  All checked before any HIP call. */
+#define LP_PROP_BLOCK       8
+#define LP_PROP_HALO        4
+#define LP_PROP_MIN_PIXELS  16
+#define LP_PROP_FILL_ITERS  3
+#define LP_PROP_SUBPEL      16
+#define LP_PROP_MAX_LEVELS  6
+#define LP_PROP_MAX_SEARCH  7
+#define LP_PROP_MAX_SMOOTH  64
+#define LP_PROP_ALIGN       16
+#define LP_PROP_MAX_GRID    2048   /* ceil(LP_VMASK_MAX_SIDE / LP_PROP_BLOCK) */
+
+/* Bytes of `frames` pyramids of `levels` levels of a height x width uint8 plane (stage 2's layout); frames = 1 gives one frame's
+ * stride.  Host arithmetic, no HIP call.  LP_E_INVALID for frames <= 0, a side or levels outside its range.                      */
+LP_API int64_t lp_prop_pyramid_ws_bytes(int32_t frames, int32_t height, int32_t width, int32_t levels);
+
+typedef struct lp_prop_luma_desc {
+    int32_t frames, height, width, channels;      /* channels 1..LP_DETAIL_MAX_CHANNELS                                     */
+    int32_t levels, reserved0;
+    const float* image;                           /* [frames, height, width, channels] fp32                                 */
+    uint8_t*     pyramid;                         /* out, lp_prop_pyramid_ws_bytes(frames, height, width, levels) bytes      */
+} lp_prop_luma_desc;
+LP_API int lp_prop_luma(const lp_prop_luma_desc* desc, void* stream);
+
+/* mask [height, width] fp32 -> its bits' pyramid (one frame, values 0 / 1) and, unless null, out [height, width] = the bits as fp32 */
+LP_API int lp_prop_key_mask(const float* mask, int32_t height, int32_t width, int32_t levels, uint8_t* mask_pyramid, float* out,
+                            void* stream);
+
+typedef struct lp_prop_match_desc {
+    int32_t height, width, levels, level;         /* height, width: level 0's                                               */
+    int32_t search, smooth;
+    const uint8_t* src;                           /* the luma pyramid of frame s (its level 0's address)                    */
+    const uint8_t* tgt;                           /* the luma pyramid of frame t                                            */
+    const uint8_t* mask;                          /* the mask pyramid of frame s                                            */
+    const int32_t* parent;                        /* level + 1's final field [gh', gw', 2]; null exactly at level levels - 1 */
+    int32_t*       vec;                           /* out, [gh, gw, 2]                                                       */
+    int32_t*       valid;                         /* out, [gh, gw], 0 / 1                                                   */
+} lp_prop_match_desc;
+LP_API int lp_prop_match(const lp_prop_match_desc* desc, void* stream);
+
+/* fill and median of one level: vec [grid_h, grid_w, 2], valid [grid_h, grid_w] as lp_prop_match wrote them -> out, the final field;
+ * out != vec.  grid sides 1..LP_PROP_MAX_GRID.                                                                                     */
+LP_API int lp_prop_fill(const int32_t* vec, const int32_t* valid, int32_t grid_h, int32_t grid_w, int32_t* out, void* stream);
+
+typedef struct lp_prop_advance_desc {
+    int32_t height, width, levels, reserved0;
+    const int32_t* vec;                           /* level 0's final field                                                  */
+    const int32_t* pos_src;                       /* P_s [height, width, 2]; null: P_key                                    */
+    const uint8_t* key;                           /* the key mask's bits [height, width] (level 0 of its pyramid)           */
+    int32_t*       pos_dst;                       /* out, P_t; != pos_src                                                   */
+    float*         out;                           /* out, [height, width] fp32                                              */
+    uint8_t*       mask_pyramid;                  /* out, the pyramid of frame t's bits                                     */
+} lp_prop_advance_desc;
+LP_API int lp_prop_advance(const lp_prop_advance_desc* desc, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -374,6 +374,52 @@ class LpGrainApplyDesc(C.Structure):
                 ("image", C.c_void_p), ("mask", C.c_void_p), ("amp", C.c_void_p), ("size", C.c_void_p), ("out", C.c_void_p)]
 
 
+LP_PROP_BLOCK, LP_PROP_HALO, LP_PROP_MIN_PIXELS, LP_PROP_FILL_ITERS, LP_PROP_SUBPEL = 8, 4, 16, 3, 16
+LP_PROP_MAX_LEVELS, LP_PROP_MAX_SEARCH, LP_PROP_MAX_SMOOTH, LP_PROP_ALIGN, LP_PROP_MAX_GRID = 6, 7, 64, 16, 2048
+
+
+class LpPropLumaDesc(C.Structure):
+    _fields_ = [("frames", C.c_int32), ("height", C.c_int32), ("width", C.c_int32), ("channels", C.c_int32),
+                ("levels", C.c_int32), ("reserved0", C.c_int32), ("image", C.c_void_p), ("pyramid", C.c_void_p)]
+
+
+class LpPropMatchDesc(C.Structure):
+    _fields_ = [("height", C.c_int32), ("width", C.c_int32), ("levels", C.c_int32), ("level", C.c_int32),
+                ("search", C.c_int32), ("smooth", C.c_int32), ("src", C.c_void_p), ("tgt", C.c_void_p), ("mask", C.c_void_p),
+                ("parent", C.c_void_p), ("vec", C.c_void_p), ("valid", C.c_void_p)]
+
+
+class LpPropAdvanceDesc(C.Structure):
+    _fields_ = [("height", C.c_int32), ("width", C.c_int32), ("levels", C.c_int32), ("reserved0", C.c_int32),
+                ("vec", C.c_void_p), ("pos_src", C.c_void_p), ("key", C.c_void_p), ("pos_dst", C.c_void_p), ("out", C.c_void_p),
+                ("mask_pyramid", C.c_void_p)]
+
+
+def prop_level_shape(height, width, level):
+    """Level `level` of a height x width plane: ceil(height / 2^level) x ceil(width / 2^level)."""
+    return (int(height) + (1 << level) - 1) >> level, (int(width) + (1 << level) - 1) >> level
+
+
+def prop_level_offset(height, width, level):
+    """Where level `level` starts in a frame's pyramid: every level LP_PROP_ALIGN-aligned behind the one below."""
+    off = 0
+    for k in range(level):
+        h, w = prop_level_shape(height, width, k)
+        off += (h * w + LP_PROP_ALIGN - 1) // LP_PROP_ALIGN * LP_PROP_ALIGN
+    return off
+
+
+def prop_pyramid_ws_bytes(frames, height, width, levels):
+    """What the C entry lp_prop_pyramid_ws_bytes returns for arguments inside the limits."""
+    return int(frames) * prop_level_offset(height, width, levels)
+
+
+def prop_grid(height, width, level=0):
+    """The block grid of a level: ceil(h_l / 8) x ceil(w_l / 8)."""
+    h, w = prop_level_shape(height, width, level)
+    return (h + LP_PROP_BLOCK - 1) // LP_PROP_BLOCK, (w + LP_PROP_BLOCK - 1) // LP_PROP_BLOCK
+
+
 def lp_components_ws_bytes(height, width):
     """LP_COMPONENTS_WS_BYTES of include/lanpaint_hip.h."""
     return ((int(height) * int(width) + 1023) // 1024) * 4100
@@ -459,6 +505,12 @@ EXPORTS = {
     "lp_grain_fit": (C.c_int, [C.POINTER(LpGrainFitDesc), C.c_void_p]),
     "lp_grain_field": (C.c_int, [C.POINTER(LpGrainFieldDesc), C.c_void_p]),
     "lp_grain_apply": (C.c_int, [C.POINTER(LpGrainApplyDesc), C.c_void_p]),
+    "lp_prop_pyramid_ws_bytes": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "lp_prop_luma": (C.c_int, [C.POINTER(LpPropLumaDesc), C.c_void_p]),
+    "lp_prop_key_mask": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "lp_prop_match": (C.c_int, [C.POINTER(LpPropMatchDesc), C.c_void_p]),
+    "lp_prop_fill": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    "lp_prop_advance": (C.c_int, [C.POINTER(LpPropAdvanceDesc), C.c_void_p]),
 }
 
 

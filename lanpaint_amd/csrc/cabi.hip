@@ -65,6 +65,12 @@ int grain_stats_dispatch(const lp_grain_stats_desc* d, hipStream_t stream);
 int grain_fit_dispatch(const lp_grain_fit_desc* d, hipStream_t stream);
 int grain_field_dispatch(const lp_grain_field_desc* d, hipStream_t stream);
 int grain_apply_dispatch(const lp_grain_apply_desc* d, hipStream_t stream);
+int64_t prop_pyramid_ws_bytes(int frames, int height, int width, int levels);
+int prop_luma_dispatch(const lp_prop_luma_desc* d, hipStream_t stream);
+int prop_key_mask_dispatch(const float* mask, int height, int width, int levels, uint8_t* mpyr, float* out, hipStream_t stream);
+int prop_match_dispatch(const lp_prop_match_desc* d, hipStream_t stream);
+int prop_fill_dispatch(const int32_t* vec, const int32_t* valid, int gh, int gw, int32_t* out, hipStream_t stream);
+int prop_advance_dispatch(const lp_prop_advance_desc* d, hipStream_t stream);
 int reshape_mask_dispatch(const float* src, int sb, int sc, int sf, int sh, int sw, float* dst, int db, int dc, int df,
                           int dh, int dw, int taps, int flags, hipStream_t stream);
 }  // namespace lp
@@ -217,6 +223,25 @@ int lp_grain_fit(const lp_grain_fit_desc* desc, void* stream) { return lp::grain
 int lp_grain_field(const lp_grain_field_desc* desc, void* stream) { return lp::grain_field_dispatch(desc, as_stream(stream)); }
 
 int lp_grain_apply(const lp_grain_apply_desc* desc, void* stream) { return lp::grain_apply_dispatch(desc, as_stream(stream)); }
+
+int64_t lp_prop_pyramid_ws_bytes(int32_t frames, int32_t height, int32_t width, int32_t levels) {
+    return lp::prop_pyramid_ws_bytes(frames, height, width, levels);
+}
+
+int lp_prop_luma(const lp_prop_luma_desc* desc, void* stream) { return lp::prop_luma_dispatch(desc, as_stream(stream)); }
+
+int lp_prop_key_mask(const float* mask, int32_t height, int32_t width, int32_t levels, uint8_t* mask_pyramid, float* out,
+                     void* stream) {
+    return lp::prop_key_mask_dispatch(mask, height, width, levels, mask_pyramid, out, as_stream(stream));
+}
+
+int lp_prop_match(const lp_prop_match_desc* desc, void* stream) { return lp::prop_match_dispatch(desc, as_stream(stream)); }
+
+int lp_prop_fill(const int32_t* vec, const int32_t* valid, int32_t grid_h, int32_t grid_w, int32_t* out, void* stream) {
+    return lp::prop_fill_dispatch(vec, valid, grid_h, grid_w, out, as_stream(stream));
+}
+
+int lp_prop_advance(const lp_prop_advance_desc* desc, void* stream) { return lp::prop_advance_dispatch(desc, as_stream(stream)); }
 
 int lp_finalize(const lp_final_desc* desc, void* stream) { return lp::finalize_dispatch(desc, as_stream(stream)); }
 

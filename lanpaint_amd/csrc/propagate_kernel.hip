@@ -1,0 +1,468 @@
+// propagate_kernel.hip -- video mask propagate for gfx950 (lanpaint_amd/propagate.py): a mask painted on one frame follows the
+// picture's motion.  include/lanpaint_hip.h (lp_prop_*) states the rule, all of it integer arithmetic.
+//
+//   luma, down   one lane per pixel: the 8-bit luma of every frame into level 0 of its pyramid, then one launch per further level.
+//   key_mask     a block per 32 x 32 tile: binarises the key mask and writes every level of its bits' pyramid (OR over the 2^l
+//                footprint) from LDS.  advance ends in the same tile code, so a step needs no launch of its own for the pyramid.
+//   match        the hot path.  One wave per 8 x 8 block of the level's grid.  The 16 x 16 source window goes to LDS as 64 dwords
+//                of four pixels, already ANDed with its per-byte mask (0xFF on a mask pixel inside the image, else 0); the mask
+//                dwords go next to it; the (16 + 2R)^2 target patch, read with clamped coordinates around the predictor, goes to
+//                rows of 32 bytes.  Lane c takes candidates c, c + 64, ...: per window row and dword, v_alignbyte_b32 cuts the
+//                four target pixels out of two patch dwords, the AND with the mask drops what is not mask, v_sad_u8 adds the four
+//                absolute differences.  The candidate's S stays in LDS for the sub-pixel step, the 32-bit key is reduced across
+//                the wave with a butterfly of minima.  A block whose window holds fewer than 16 mask pixels leaves after staging.
+//   fill         a block per 16 x 16 tile of the grid with a halo of 4 in LDS: three Jacobi passes between two buffers (a pass
+//                is wrong on the outermost ring it still reads, so three passes leave the tile and one ring around it exact),
+//                then the 3 x 3 median (the 19-exchange network) per component.
+//   advance      a block per 32 x 32 tile, four pixels per lane: the per-pixel vector from the block field, the new position
+//                map, the mask code through it, the output, and the bits' pyramid for the next step.
+// No scratch, no atomics, no floating point beyond the luma codes and the final c / 256.
+#include "lp_common.h"
+
+#include <algorithm>
+
+namespace lp {
+namespace {
+
+constexpr int kB = LP_PROP_BLOCK, kHalo = LP_PROP_HALO, kWin = kB + 2 * kHalo;        // 8, 4, 16
+constexpr int kPatchPitch = 8;                                                         // dwords per patch row: 32 bytes >= 30
+constexpr int kPatchRows = kWin + 2 * LP_PROP_MAX_SEARCH;                              // 30
+constexpr int kMaxCand = (2 * LP_PROP_MAX_SEARCH + 1) * (2 * LP_PROP_MAX_SEARCH + 1);  // 225
+constexpr int kTile = 32;                                                              // key_mask / advance: pixels per tile side
+constexpr int kFillTile = 16, kFillHalo = LP_PROP_FILL_ITERS + 1, kFillSide = kFillTile + 2 * kFillHalo;   // 16, 4, 24
+
+static_assert(kWin == 16 && kPatchRows <= 32 && kWin + 2 * LP_PROP_MAX_SEARCH <= 4 * kPatchPitch, "the match kernel's LDS layout");
+static_assert(kTile == 1 << (LP_PROP_MAX_LEVELS - 1), "a tile holds one pixel of the coarsest level");
+
+__host__ __device__ inline int level_side(int n, int l) { return (n + (1 << l) - 1) >> l; }
+__host__ __device__ inline int64_t level_offset(int h, int w, int l) {
+    int64_t off = 0;
+    for (int k = 0; k < l; ++k) {
+        const int64_t n = static_cast<int64_t>(level_side(h, k)) * level_side(w, k);
+        off += (n + LP_PROP_ALIGN - 1) / LP_PROP_ALIGN * LP_PROP_ALIGN;
+    }
+    return off;
+}
+
+__device__ __forceinline__ int clampi(int v, int lo, int hi) { return min(max(v, lo), hi); }
+
+__device__ __forceinline__ uint32_t code_of(float v) {                                   // a NaN gives 0
+    const float t = v > 0.0f ? (v < 1.0f ? v : 1.0f) : 0.0f;
+    return static_cast<uint32_t>(static_cast<int>(__fadd_rn(__fmul_rn(t, 255.0f), 0.5f)));
+}
+
+// ---- luma and pyramids ---------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void lp_prop_luma_kernel(const float* __restrict__ image, uint8_t* __restrict__ pyr, int64_t plane,
+                                                           int channels, int64_t stride) {
+    const int64_t p = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
+    if (p >= plane) return;
+    const int64_t f = blockIdx.y;
+    const float* px = image + (f * plane + p) * channels;
+    uint32_t y = code_of(px[0]);
+    if (channels >= 3) y = (77u * y + 150u * code_of(px[1]) + 29u * code_of(px[2]) + 128u) >> 8;
+    pyr[f * stride + p] = static_cast<uint8_t>(y);
+}
+
+__global__ __launch_bounds__(256) void lp_prop_down_kernel(uint8_t* __restrict__ pyr, int64_t stride, int64_t src_off, int64_t dst_off,
+                                                           int sh, int sw, int dh, int dw) {
+    const int64_t p = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
+    if (p >= static_cast<int64_t>(dh) * dw) return;
+    const int y = static_cast<int>(p / dw), x = static_cast<int>(p - static_cast<int64_t>(y) * dw);
+    const uint8_t* src = pyr + static_cast<int64_t>(blockIdx.y) * stride + src_off;
+    const int y0 = 2 * y, y1 = min(2 * y + 1, sh - 1), x0 = 2 * x, x1 = min(2 * x + 1, sw - 1);        // 2y <= sh - 1 always
+    const uint32_t s = src[static_cast<int64_t>(y0) * sw + x0] + src[static_cast<int64_t>(y0) * sw + x1] +
+                       src[static_cast<int64_t>(y1) * sw + x0] + src[static_cast<int64_t>(y1) * sw + x1];
+    pyr[static_cast<int64_t>(blockIdx.y) * stride + dst_off + p] = static_cast<uint8_t>((s + 2u) >> 2);
+}
+
+// Every level of the bits' pyramid of one 32 x 32 tile.  s0 holds the tile's level-0 bits (0 outside the image) and is complete
+// (the caller has synchronised); tile (ty, tx) of a height x width plane.  256 lanes.
+__device__ __forceinline__ void tile_mask_pyramid(uint8_t* s0, uint8_t* s1, int ty, int tx, int height, int width, int levels,
+                                                  uint8_t* __restrict__ out) {
+    const int tid = threadIdx.x;
+    uint8_t* cur = s0;
+    uint8_t* nxt = s1;
+    int64_t off = 0;
+    for (int l = 0; l < levels; ++l) {
+        const int side = kTile >> l, h = level_side(height, l), w = level_side(width, l);
+        const int oy = (ty * kTile) >> l, ox = (tx * kTile) >> l;
+        for (int i = tid; i < side * side; i += 256) {
+            const int y = i / side, x = i - y * side;
+            if (oy + y < h && ox + x < w) out[off + static_cast<int64_t>(oy + y) * w + ox + x] = cur[i];
+        }
+        if (l + 1 == levels) break;
+        const int half = side >> 1;
+        for (int i = tid; i < half * half; i += 256) {
+            const int y = i / half, x = i - y * half;
+            const uint8_t* r = cur + (2 * y) * side + 2 * x;
+            nxt[i] = r[0] | r[1] | r[side] | r[side + 1];
+        }
+        __syncthreads();
+        uint8_t* t = cur; cur = nxt; nxt = t;
+        off += (static_cast<int64_t>(h) * w + LP_PROP_ALIGN - 1) / LP_PROP_ALIGN * LP_PROP_ALIGN;
+    }
+}
+
+__global__ __launch_bounds__(256) void lp_prop_key_mask_kernel(const float* __restrict__ mask, int height, int width, int levels,
+                                                               uint8_t* __restrict__ mpyr, float* __restrict__ out) {
+    __shared__ uint8_t s0[kTile * kTile], s1[kTile * kTile / 4];
+    for (int i = threadIdx.x; i < kTile * kTile; i += 256) {
+        const int y = blockIdx.y * kTile + (i >> 5), x = blockIdx.x * kTile + (i & 31);
+        uint8_t bit = 0;
+        if (y < height && x < width) {
+            const int64_t p = static_cast<int64_t>(y) * width + x;
+            bit = mask[p] >= 0.5f ? 1 : 0;                                               // a NaN gives 0
+            if (out) out[p] = bit ? 1.0f : 0.0f;
+        }
+        s0[i] = bit;
+    }
+    __syncthreads();
+    tile_mask_pyramid(s0, s1, blockIdx.y, blockIdx.x, height, width, levels, mpyr);
+}
+
+// ---- the masked block matching ---------------------------------------------------------------------------------------------------------
+struct match_args {
+    const uint8_t* src;          // this level's planes
+    const uint8_t* tgt;
+    const uint8_t* msk;
+    const int32_t* parent;       // [pgh, pgw, 2] or null
+    int32_t*       vec;
+    int32_t*       valid;
+    int32_t h, w, gw, pgh, pgw, search, smooth, subpel;
+};
+
+__global__ __launch_bounds__(kWave) void lp_prop_match_kernel(const match_args a) {
+    __shared__ uint32_t s_src[kWin * 4], s_bm[kWin * 4], s_pat[kPatchRows * kPatchPitch];
+    __shared__ int32_t s_S[kMaxCand];
+    const int lane = threadIdx.x, bx = blockIdx.x, by = blockIdx.y;
+    const int R = a.search, n = 2 * R + 1, ncand = n * n;
+    int py = 0, px = 0;
+    if (a.parent) {
+        const int32_t* pv = a.parent + (static_cast<int64_t>(min(by >> 1, a.pgh - 1)) * a.pgw + min(bx >> 1, a.pgw - 1)) * 2;
+        py = 2 * ((pv[0] + 8) >> 4);
+        px = 2 * ((pv[1] + 8) >> 4);
+    }
+    const int64_t cell = static_cast<int64_t>(by) * a.gw + bx;
+    // the window: lane = row * 4 + dword
+    const int wy = by * kB - kHalo, wx = bx * kB - kHalo;
+    int count = 0;
+    {
+        const int y = wy + (lane >> 2);
+        uint32_t sv = 0, bm = 0;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int x = wx + (lane & 3) * 4 + k;
+            if (y >= 0 && y < a.h && x >= 0 && x < a.w) {
+                const int64_t p = static_cast<int64_t>(y) * a.w + x;
+                if (a.msk[p]) {
+                    bm |= 0xFFu << (8 * k);
+                    sv |= static_cast<uint32_t>(a.src[p]) << (8 * k);
+                    ++count;
+                }
+            }
+        }
+        s_src[lane] = sv;
+        s_bm[lane] = bm;
+    }
+#pragma unroll
+    for (int d = 1; d < kWave; d <<= 1) count += __shfl_xor(count, d, kWave);
+    if (count < LP_PROP_MIN_PIXELS) {                                    // the whole wave leaves together
+        if (lane == 0) {
+            a.vec[cell * 2] = 16 * py;
+            a.vec[cell * 2 + 1] = 16 * px;
+            a.valid[cell] = 0;
+        }
+        return;
+    }
+    // the target patch: row j, byte i is Yt(clamp(wy + py - R + j), clamp(wx + px - R + i))
+    const int rows = kWin + 2 * R;
+    for (int i = lane; i < rows * kPatchPitch; i += kWave) {
+        const int j = i >> 3, c0 = (i & 7) * 4;
+        const uint8_t* row = a.tgt + static_cast<int64_t>(clampi(wy + py - R + j, 0, a.h - 1)) * a.w;
+        uint32_t v = 0;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) v |= static_cast<uint32_t>(row[clampi(wx + px - R + c0 + k, 0, a.w - 1)]) << (8 * k);
+        s_pat[i] = v;
+    }
+    __syncthreads();
+    uint32_t best = 0xFFFFFFFFu;
+    for (int c = lane; c < ncand; c += kWave) {
+        const int cy = c / n, cx = c - cy * n;                          // oy + R, ox + R
+        const int word = cx >> 2, shift = cx & 3;                       // word + 3 + 1 <= 7: inside the patch row
+        uint32_t S = 0;
+        for (int r = 0; r < kWin; ++r) {
+            const uint32_t* pr = s_pat + (r + cy) * kPatchPitch + word;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const uint32_t t = __builtin_amdgcn_alignbyte(pr[k + 1], pr[k], shift) & s_bm[r * 4 + k];
+                S = __builtin_amdgcn_sad_u8(s_src[r * 4 + k], t, S);
+            }
+        }
+        s_S[c] = static_cast<int32_t>(S);
+        const uint32_t dist = static_cast<uint32_t>(abs(cy - R) + abs(cx - R));
+        best = min(best, ((S + static_cast<uint32_t>(a.smooth) * dist) << 12) | (dist << 8) | static_cast<uint32_t>(c));
+    }
+#pragma unroll
+    for (int d = 1; d < kWave; d <<= 1) best = min(best, static_cast<uint32_t>(__shfl_xor(static_cast<int>(best), d, kWave)));
+    __syncthreads();                                                     // s_S is complete
+    if (lane == 0) {
+        const int c = static_cast<int>(best & 255u), cy = c / n, cx = c - cy * n;
+        int vy = 16 * (py + cy - R), vx = 16 * (px + cx - R);
+        const int s0 = s_S[c];
+        if (a.subpel && s0 != 0) {
+            if (cy > 0 && cy < 2 * R) {
+                const int cm = s_S[c - n], cp = s_S[c + n], d = cm + cp - 2 * s0, g = cm - cp;
+                if (d > 0) vy += (g > 0 ? 1 : (g < 0 ? -1 : 0)) * min(abs(8 * g) / d, 8);
+            }
+            if (cx > 0 && cx < 2 * R) {
+                const int cm = s_S[c - 1], cp = s_S[c + 1], d = cm + cp - 2 * s0, g = cm - cp;
+                if (d > 0) vx += (g > 0 ? 1 : (g < 0 ? -1 : 0)) * min(abs(8 * g) / d, 8);
+            }
+        }
+        a.vec[cell * 2] = vy;
+        a.vec[cell * 2 + 1] = vx;
+        a.valid[cell] = 1;
+    }
+}
+
+// ---- fill and median ---------------------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ void cmpswap(int& a, int& b) {
+    const int lo = min(a, b), hi = max(a, b);
+    a = lo; b = hi;
+}
+
+__device__ __forceinline__ int median9(int p0, int p1, int p2, int p3, int p4, int p5, int p6, int p7, int p8) {
+    cmpswap(p1, p2); cmpswap(p4, p5); cmpswap(p7, p8); cmpswap(p0, p1); cmpswap(p3, p4); cmpswap(p6, p7);
+    cmpswap(p1, p2); cmpswap(p4, p5); cmpswap(p7, p8); cmpswap(p0, p3); cmpswap(p5, p8); cmpswap(p4, p7);
+    cmpswap(p3, p6); cmpswap(p1, p4); cmpswap(p2, p5); cmpswap(p4, p7); cmpswap(p4, p2); cmpswap(p6, p4);
+    cmpswap(p4, p2);
+    return p4;
+}
+
+__device__ __forceinline__ int floor_div(int a, int b) {                 // b > 0
+    const int q = a / b;
+    return (a % b != 0 && a < 0) ? q - 1 : q;
+}
+
+__global__ __launch_bounds__(256) void lp_prop_fill_kernel(const int32_t* __restrict__ vec, const int32_t* __restrict__ valid, int gh,
+                                                           int gw, int32_t* __restrict__ out) {
+    constexpr int N = kFillSide * kFillSide;                             // 576
+    __shared__ int32_t s_y[2][N], s_x[2][N], s_ok[2][N];                 // ok: 1 valid, 0 invalid, -1 outside the grid
+    const int y00 = blockIdx.y * kFillTile - kFillHalo, x00 = blockIdx.x * kFillTile - kFillHalo;
+    for (int i = threadIdx.x; i < N; i += 256) {
+        const int y = y00 + i / kFillSide, x = x00 + i % kFillSide;
+        int vy = 0, vx = 0, ok = -1;
+        if (y >= 0 && y < gh && x >= 0 && x < gw) {
+            const int64_t c = static_cast<int64_t>(y) * gw + x;
+            vy = vec[c * 2];
+            vx = vec[c * 2 + 1];
+            ok = valid[c] != 0;
+        }
+        s_y[0][i] = vy; s_x[0][i] = vx; s_ok[0][i] = ok;
+    }
+    __syncthreads();
+    int cur = 0;
+#pragma unroll 1
+    for (int pass = 0; pass < LP_PROP_FILL_ITERS; ++pass) {
+        for (int i = threadIdx.x; i < N; i += 256) {
+            const int r = i / kFillSide, c = i % kFillSide;
+            int vy = s_y[cur][i], vx = s_x[cur][i], ok = s_ok[cur][i];
+            if (ok == 0) {
+                int cnt = 0, sy = 0, sx = 0;
+                for (int dy = -1; dy <= 1; ++dy)
+                    for (int dx = -1; dx <= 1; ++dx) {
+                        const int rr = r + dy, cc = c + dx;
+                        if (rr < 0 || rr >= kFillSide || cc < 0 || cc >= kFillSide) continue;
+                        const int j = rr * kFillSide + cc;
+                        if (s_ok[cur][j] == 1) { ++cnt; sy += s_y[cur][j]; sx += s_x[cur][j]; }
+                    }
+                if (cnt > 0) {
+                    vy = floor_div(2 * sy + cnt, 2 * cnt);
+                    vx = floor_div(2 * sx + cnt, 2 * cnt);
+                    ok = 1;
+                }
+            }
+            s_y[cur ^ 1][i] = vy; s_x[cur ^ 1][i] = vx; s_ok[cur ^ 1][i] = ok;
+        }
+        __syncthreads();
+        cur ^= 1;
+    }
+    const int ty = threadIdx.x >> 4, tx = threadIdx.x & 15;
+    const int y = blockIdx.y * kFillTile + ty, x = blockIdx.x * kFillTile + tx;
+    if (y >= gh || x >= gw) return;
+    int py[9], px[9];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) {
+        const int yy = clampi(y + k / 3 - 1, 0, gh - 1) - y00, xx = clampi(x + k % 3 - 1, 0, gw - 1) - x00;
+        py[k] = s_y[cur][yy * kFillSide + xx];
+        px[k] = s_x[cur][yy * kFillSide + xx];
+    }
+    const int64_t c = static_cast<int64_t>(y) * gw + x;
+    out[c * 2] = median9(py[0], py[1], py[2], py[3], py[4], py[5], py[6], py[7], py[8]);
+    out[c * 2 + 1] = median9(px[0], px[1], px[2], px[3], px[4], px[5], px[6], px[7], px[8]);
+}
+
+// ---- advance -------------------------------------------------------------------------------------------------------------------------------
+struct advance_args {
+    const int32_t* vec;
+    const int32_t* pos_src;
+    const uint8_t* key;
+    int32_t*       pos_dst;
+    float*         out;
+    uint8_t*       mpyr;
+    int32_t height, width, levels, gh, gw;
+};
+
+struct bil_tap { int i0, i1, f; };
+
+__device__ __forceinline__ bil_tap tap_of(int q, int n) {
+    q = clampi(q, 0, 16 * (n - 1));
+    bil_tap t;
+    t.i0 = q >> 4;
+    t.f = q & 15;
+    t.i1 = min(t.i0 + 1, n - 1);
+    return t;
+}
+
+__device__ __forceinline__ int bil_sum(int a00, int a01, int a10, int a11, int fy, int fx) {
+    return (16 - fy) * ((16 - fx) * a00 + fx * a01) + fy * ((16 - fx) * a10 + fx * a11);
+}
+
+__global__ __launch_bounds__(256) void lp_prop_advance_kernel(const advance_args a) {
+    __shared__ uint8_t s0[kTile * kTile], s1[kTile * kTile / 4];
+    const int H = a.height, W = a.width;
+    for (int i = threadIdx.x; i < kTile * kTile; i += 256) {
+        const int y = blockIdx.y * kTile + (i >> 5), x = blockIdx.x * kTile + (i & 31);
+        uint8_t bit = 0;
+        if (y < H && x < W) {
+            // the per-pixel vector
+            const int uy = 2 * y - 7, ux = 2 * x - 7, by0 = uy >> 4, bx0 = ux >> 4, fy = uy - 16 * by0, fx = ux - 16 * bx0;
+            const int64_t r0 = static_cast<int64_t>(clampi(by0, 0, a.gh - 1)) * a.gw, r1 = static_cast<int64_t>(clampi(by0 + 1, 0, a.gh - 1)) * a.gw;
+            const int c0 = clampi(bx0, 0, a.gw - 1), c1 = clampi(bx0 + 1, 0, a.gw - 1);
+            const int32_t *v00 = a.vec + (r0 + c0) * 2, *v01 = a.vec + (r0 + c1) * 2, *v10 = a.vec + (r1 + c0) * 2, *v11 = a.vec + (r1 + c1) * 2;
+            const int Vy = (bil_sum(v00[0], v01[0], v10[0], v11[0], fy, fx) + 128) >> 8;
+            const int Vx = (bil_sum(v00[1], v01[1], v10[1], v11[1], fy, fx) + 128) >> 8;
+            // the new position
+            const bil_tap ty = tap_of(16 * y - Vy, H), tx = tap_of(16 * x - Vx, W);
+            int Py, Px;
+            if (a.pos_src) {
+                const int32_t *p00 = a.pos_src + (static_cast<int64_t>(ty.i0) * W + tx.i0) * 2, *p01 = a.pos_src + (static_cast<int64_t>(ty.i0) * W + tx.i1) * 2;
+                const int32_t *p10 = a.pos_src + (static_cast<int64_t>(ty.i1) * W + tx.i0) * 2, *p11 = a.pos_src + (static_cast<int64_t>(ty.i1) * W + tx.i1) * 2;
+                Py = (bil_sum(p00[0], p01[0], p10[0], p11[0], ty.f, tx.f) + 128) >> 8;
+                Px = (bil_sum(p00[1], p01[1], p10[1], p11[1], ty.f, tx.f) + 128) >> 8;
+            } else {                                                     // P_key(y, x) = (16 y, 16 x)
+                Py = (bil_sum(16 * ty.i0, 16 * ty.i0, 16 * ty.i1, 16 * ty.i1, ty.f, tx.f) + 128) >> 8;
+                Px = (bil_sum(16 * tx.i0, 16 * tx.i1, 16 * tx.i0, 16 * tx.i1, ty.f, tx.f) + 128) >> 8;
+            }
+            const int64_t p = static_cast<int64_t>(y) * W + x;
+            a.pos_dst[p * 2] = Py;
+            a.pos_dst[p * 2 + 1] = Px;
+            // the mask code through it
+            const bil_tap ky = tap_of(Py, H), kx = tap_of(Px, W);
+            const uint8_t *k0 = a.key + static_cast<int64_t>(ky.i0) * W, *k1 = a.key + static_cast<int64_t>(ky.i1) * W;
+            const int c = bil_sum(k0[kx.i0], k0[kx.i1], k1[kx.i0], k1[kx.i1], ky.f, kx.f);
+            a.out[p] = static_cast<float>(c) * (1.0f / 256.0f);           // c <= 256 and a power of two: exact
+            bit = c >= 128 ? 1 : 0;
+        }
+        s0[i] = bit;
+    }
+    __syncthreads();
+    tile_mask_pyramid(s0, s1, blockIdx.y, blockIdx.x, H, W, a.levels, a.mpyr);
+}
+
+bool side_ok(int s) { return s > 0 && s <= LP_VMASK_MAX_SIDE; }
+bool levels_ok(int l) { return l >= 1 && l <= LP_PROP_MAX_LEVELS; }
+int launched() { return hipGetLastError() == hipSuccess ? LP_OK : LP_E_LAUNCH; }
+uint32_t blocks_of(int64_t n, int per) { return static_cast<uint32_t>((n + per - 1) / per); }
+
+}  // namespace
+
+int64_t prop_pyramid_ws_bytes(int frames, int height, int width, int levels) {
+    if (frames <= 0 || !side_ok(height) || !side_ok(width) || !levels_ok(levels)) return LP_E_INVALID;
+    return static_cast<int64_t>(frames) * level_offset(height, width, levels);
+}
+
+int prop_luma_dispatch(const lp_prop_luma_desc* dp, hipStream_t stream) {
+    if (!dp) return LP_E_INVALID;
+    const lp_prop_luma_desc& d = *dp;
+    if (d.frames <= 0 || !side_ok(d.height) || !side_ok(d.width) || !levels_ok(d.levels)) return LP_E_INVALID;
+    if (d.channels < 1 || d.channels > LP_DETAIL_MAX_CHANNELS || !d.image || !d.pyramid) return LP_E_INVALID;
+    if (d.frames > 65535) return LP_E_UNSUPPORTED;
+    const int64_t plane = static_cast<int64_t>(d.height) * d.width, stride = level_offset(d.height, d.width, d.levels);
+    hipLaunchKernelGGL(lp_prop_luma_kernel, dim3(blocks_of(plane, 256), d.frames), dim3(256), 0, stream, d.image, d.pyramid, plane,
+                       d.channels, stride);
+    if (hipGetLastError() != hipSuccess) return LP_E_LAUNCH;
+    for (int l = 1; l < d.levels; ++l) {
+        const int sh = level_side(d.height, l - 1), sw = level_side(d.width, l - 1), dh = level_side(d.height, l), dw = level_side(d.width, l);
+        hipLaunchKernelGGL(lp_prop_down_kernel, dim3(blocks_of(static_cast<int64_t>(dh) * dw, 256), d.frames), dim3(256), 0, stream,
+                           d.pyramid, stride, level_offset(d.height, d.width, l - 1), level_offset(d.height, d.width, l), sh, sw, dh, dw);
+        if (hipGetLastError() != hipSuccess) return LP_E_LAUNCH;
+    }
+    return LP_OK;
+}
+
+int prop_key_mask_dispatch(const float* mask, int height, int width, int levels, uint8_t* mpyr, float* out, hipStream_t stream) {
+    if (!mask || !mpyr || !side_ok(height) || !side_ok(width) || !levels_ok(levels)) return LP_E_INVALID;
+    if (out == mask) return LP_E_INVALID;
+    hipLaunchKernelGGL(lp_prop_key_mask_kernel, dim3(blocks_of(width, kTile), blocks_of(height, kTile)), dim3(256), 0, stream, mask,
+                       height, width, levels, mpyr, out);
+    return launched();
+}
+
+int prop_match_dispatch(const lp_prop_match_desc* dp, hipStream_t stream) {
+    if (!dp) return LP_E_INVALID;
+    const lp_prop_match_desc& d = *dp;
+    if (!side_ok(d.height) || !side_ok(d.width) || !levels_ok(d.levels) || d.level < 0 || d.level >= d.levels) return LP_E_INVALID;
+    if (d.search < 1 || d.search > LP_PROP_MAX_SEARCH || d.smooth < 0 || d.smooth > LP_PROP_MAX_SMOOTH) return LP_E_INVALID;
+    if (!d.src || !d.tgt || !d.mask || !d.vec || !d.valid) return LP_E_INVALID;
+    if ((d.parent == nullptr) != (d.level == d.levels - 1) || d.parent == d.vec) return LP_E_INVALID;
+    match_args a = {};
+    const int64_t off = level_offset(d.height, d.width, d.level);
+    a.src = d.src + off;
+    a.tgt = d.tgt + off;
+    a.msk = d.mask + off;
+    a.parent = d.parent;
+    a.vec = d.vec;
+    a.valid = d.valid;
+    a.h = level_side(d.height, d.level);
+    a.w = level_side(d.width, d.level);
+    a.gw = (a.w + kB - 1) / kB;
+    const int gh = (a.h + kB - 1) / kB;
+    a.pgh = (level_side(d.height, d.level + 1) + kB - 1) / kB;
+    a.pgw = (level_side(d.width, d.level + 1) + kB - 1) / kB;
+    a.search = d.search;
+    a.smooth = d.smooth;
+    a.subpel = d.level == 0;
+    hipLaunchKernelGGL(lp_prop_match_kernel, dim3(a.gw, gh), dim3(kWave), 0, stream, a);
+    return launched();
+}
+
+int prop_fill_dispatch(const int32_t* vec, const int32_t* valid, int gh, int gw, int32_t* out, hipStream_t stream) {
+    if (!vec || !valid || !out || out == vec || gh < 1 || gw < 1 || gh > LP_PROP_MAX_GRID || gw > LP_PROP_MAX_GRID) return LP_E_INVALID;
+    hipLaunchKernelGGL(lp_prop_fill_kernel, dim3(blocks_of(gw, kFillTile), blocks_of(gh, kFillTile)), dim3(256), 0, stream, vec, valid,
+                       gh, gw, out);
+    return launched();
+}
+
+int prop_advance_dispatch(const lp_prop_advance_desc* dp, hipStream_t stream) {
+    if (!dp) return LP_E_INVALID;
+    const lp_prop_advance_desc& d = *dp;
+    if (!side_ok(d.height) || !side_ok(d.width) || !levels_ok(d.levels)) return LP_E_INVALID;
+    if (!d.vec || !d.key || !d.pos_dst || !d.out || !d.mask_pyramid || d.pos_dst == d.pos_src || d.mask_pyramid == d.key) return LP_E_INVALID;
+    advance_args a = {};
+    a.vec = d.vec;
+    a.pos_src = d.pos_src;
+    a.key = d.key;
+    a.pos_dst = d.pos_dst;
+    a.out = d.out;
+    a.mpyr = d.mask_pyramid;
+    a.height = d.height;
+    a.width = d.width;
+    a.levels = d.levels;
+    a.gh = (d.height + kB - 1) / kB;
+    a.gw = (d.width + kB - 1) / kB;
+    hipLaunchKernelGGL(lp_prop_advance_kernel, dim3(blocks_of(d.width, kTile), blocks_of(d.height, kTile)), dim3(256), 0, stream, a);
+    return launched();
+}
+
+}  // namespace lp
