@@ -1459,7 +1459,7 @@ LP_API int lp_grain_apply(const lp_grain_apply_desc* desc, void* stream);
  * crops.  A block matching, weighted by the mask, measures the motion from a frame s to the next frame t (one frame further from
  * the key); a map of key-frame positions is carried along that motion and the key mask is sampled through it.  Everything stays on
  * the device; nothing is read back.  All of it is integer arithmetic: the same bits on every run, for every tile and every chunk
- * of frames.  Not handled: several keyframes, occlusion, re-anchoring against drift.
+ * of frames.  Several keyframes: the lp_prop_*_batch section below.  Not handled: occlusion.
  *   sides 1..LP_VMASK_MAX_SIDE; levels L in 1..LP_PROP_MAX_LEVELS; search R in 1..LP_PROP_MAX_SEARCH; smooth 0..LP_PROP_MAX_SMOOTH
  *   B = LP_PROP_BLOCK = 8; a block's window is the block grown by LP_PROP_HALO = 4 on every side and cut at the image border (at
  *   most 16 x 16); vectors and positions are in units of 1 / LP_PROP_SUBPEL = 1/16 pixel, (y, x) pairs of int32.  `>>` is the
@@ -1558,6 +1558,90 @@ typedef struct lp_prop_advance_desc {
     uint8_t*       mask_pyramid;                  /* out, the pyramid of frame t's bits                                     */
 } lp_prop_advance_desc;
 LP_API int lp_prop_advance(const lp_prop_advance_desc* desc, void* stream);
+
+/* ---- Video mask propagate from several keyframes (beyond the reference) -----------------------------------------------------------
+ * One chain loses accuracy with its distance from the key, and a user who repaints a later frame wants both paintings honoured.
+ * With several painted keys every key is carried along the picture's motion in both directions; between two keys the two carried
+ * masks are merged through their signed distance fields with weights that move from one key to the other, so the result equals
+ * the painted mask on every key frame and drift is pulled back to zero there.
+ *   inputs    key frames k_0 < k_1 < ... < k_{K-1} in 0..F-1, a painted mask per key, the lp_prop_* parameters unchanged.
+ *   chains    each chain is exactly stages 1 to 3 of the section above started from one key, in this order: backward from k_0 to
+ *             frame 0 if k_0 > 0; per gap i = 0..K-2 forward from k_i to k_{i+1} - 1, then backward from k_{i+1} to k_i + 1;
+ *             forward from k_{K-1} to F - 1 if it is not the last frame.  A chain of length 0 does not exist.  Chain c with key k
+ *             and direction d = +-1 goes at step s >= 1 from frame k + d (s - 1) to frame k + d s.
+ *   output    a key frame gets its binarised painted mask, as lp_prop_key_mask writes it; a frame outside [k_0, k_{K-1}] gets its
+ *             one chain's output c / 256; a frame t strictly inside a gap (a, b) gets the merge of A, the forward chain's output
+ *             at t, and B, the backward chain's, with n = b - a and j = t - a.
+ *   merge     (lp_prop_merge) qA, qB: the signed squared distances of A and B binarised at >= 0.5, exactly as lp_mask_signed_d2
+ *             defines them, +-LP_STAB_Q_FAR on an empty or a full frame.  sX = sign(qX) * sqrt((double)|qX|), the correctly rounded
+ *             fp64 root, capped at +-LP_STAB_SD_CAP exactly as stage 3 of lp_mask_stabilize.  acc = (double)(n - j) * sA +
+ *             (double)j * sB, the two products and the sum each rounded on its own (no FMA); sd = acc / (double)n;
+ *             out = (float)min(max(0.5 + sd, 0.0), 1.0).
+ * What follows from the rule: where A and B have the same bits the output is exactly those bits, since |s| >= 1 puts 0.5 + sd
+ * beyond the ramp; K = 1 is the single-key propagate, bit for bit; a still video with the same mask on every key returns that
+ * binarised mask on every frame; empty masks everywhere stay exactly 0 and full masks everywhere exactly 1.0.  An empty key next to
+ * a non-empty one says "nothing here": its distance is the cap, 64, which outweighs a small object's depth, so the other key's mask
+ * appears only in the last frames before that key.  This is deliberate.  The same bits on every run.
+ * The up to 2 K chains do not depend on one another: lp_prop_match_batch, lp_prop_fill_batch and lp_prop_advance_batch run up to
+ * LP_PROP_MAX_JOBS independent chain steps in one launch, the job on blockIdx.z, every job with the meaning and the bits of the
+ * single entry (the single entries are one-job batches of the same kernels).  The job table is read from host memory and travels
+ * by value in the kernel's arguments (32 x 48 bytes); no device table is uploaded.  A call has as many dependent steps as its longest
+ * chain, each 2 L + 1 launches per 32 active chains.  Two jobs that write the same buffer are the caller's error; nothing checks it.
+ * LP_E_INVALID: jobs outside 1..LP_PROP_MAX_JOBS; a null pointer, except parent at the top level and pos_src; parent given at the
+ * top level or missing below it, in any job; out == vec, pos_dst == pos_src or mask_pyramid == key within a job; every range the
+ * single entries check.  lp_prop_merge: a null pointer, a side outside 1..LP_VMASK_MAX_SIDE, span < 2, first < 1, frames < 1,
+ * first + frames - 1 > span - 1, out aliasing qa or qb; LP_E_UNSUPPORTED: span > 65535.  All checked before any HIP call.            */
+#define LP_PROP_MAX_JOBS    32
+
+typedef struct lp_prop_match_job {
+    const uint8_t* src;                           /* as in lp_prop_match_desc                                               */
+    const uint8_t* tgt;
+    const uint8_t* mask;
+    const int32_t* parent;
+    int32_t*       vec;
+    int32_t*       valid;
+} lp_prop_match_job;
+
+typedef struct lp_prop_match_batch_desc {
+    int32_t height, width, levels, level;
+    int32_t search, smooth;
+    int32_t jobs, reserved0;                      /* jobs 1..LP_PROP_MAX_JOBS                                               */
+    const lp_prop_match_job* job;                 /* host memory, `jobs` entries                                            */
+} lp_prop_match_batch_desc;
+LP_API int lp_prop_match_batch(const lp_prop_match_batch_desc* desc, void* stream);
+
+typedef struct lp_prop_fill_job {
+    const int32_t* vec;                           /* as lp_prop_fill's arguments; out != vec                                */
+    const int32_t* valid;
+    int32_t*       out;
+} lp_prop_fill_job;
+/* job: host memory, `jobs` entries, every job's grid grid_h x grid_w                                                      */
+LP_API int lp_prop_fill_batch(const lp_prop_fill_job* job, int32_t jobs, int32_t grid_h, int32_t grid_w, void* stream);
+
+typedef struct lp_prop_advance_job {
+    const int32_t* vec;                           /* as in lp_prop_advance_desc; a null pos_src means P_key                 */
+    const int32_t* pos_src;
+    const uint8_t* key;
+    int32_t*       pos_dst;
+    float*         out;
+    uint8_t*       mask_pyramid;
+} lp_prop_advance_job;
+
+typedef struct lp_prop_advance_batch_desc {
+    int32_t height, width, levels, jobs;
+    const lp_prop_advance_job* job;               /* host memory, `jobs` entries                                            */
+} lp_prop_advance_batch_desc;
+LP_API int lp_prop_advance_batch(const lp_prop_advance_batch_desc* desc, void* stream);
+
+/* The in-between frames of one gap: frame f of the stacks is frame j = first + f of the gap, 1 <= j <= span - 1.  One launch. */
+typedef struct lp_prop_merge_desc {
+    int32_t frames, height, width, span;          /* span = n, the distance between the two keys                            */
+    int32_t first, reserved0;
+    const int32_t* qa;                            /* [frames, height, width] signed squared distances of the forward chain  */
+    const int32_t* qb;                            /* the same of the backward chain                                         */
+    float*         out;                           /* [frames, height, width] fp32                                           */
+} lp_prop_merge_desc;
+LP_API int lp_prop_merge(const lp_prop_merge_desc* desc, void* stream);
 
 #ifdef __cplusplus
 }

@@ -395,6 +395,37 @@ class LpPropAdvanceDesc(C.Structure):
                 ("mask_pyramid", C.c_void_p)]
 
 
+LP_PROP_MAX_JOBS = 32
+
+
+class LpPropMatchJob(C.Structure):
+    _fields_ = [("src", C.c_void_p), ("tgt", C.c_void_p), ("mask", C.c_void_p), ("parent", C.c_void_p), ("vec", C.c_void_p),
+                ("valid", C.c_void_p)]
+
+
+class LpPropMatchBatchDesc(C.Structure):
+    _fields_ = [("height", C.c_int32), ("width", C.c_int32), ("levels", C.c_int32), ("level", C.c_int32),
+                ("search", C.c_int32), ("smooth", C.c_int32), ("jobs", C.c_int32), ("reserved0", C.c_int32), ("job", C.c_void_p)]
+
+
+class LpPropFillJob(C.Structure):
+    _fields_ = [("vec", C.c_void_p), ("valid", C.c_void_p), ("out", C.c_void_p)]
+
+
+class LpPropAdvanceJob(C.Structure):
+    _fields_ = [("vec", C.c_void_p), ("pos_src", C.c_void_p), ("key", C.c_void_p), ("pos_dst", C.c_void_p), ("out", C.c_void_p),
+                ("mask_pyramid", C.c_void_p)]
+
+
+class LpPropAdvanceBatchDesc(C.Structure):
+    _fields_ = [("height", C.c_int32), ("width", C.c_int32), ("levels", C.c_int32), ("jobs", C.c_int32), ("job", C.c_void_p)]
+
+
+class LpPropMergeDesc(C.Structure):
+    _fields_ = [("frames", C.c_int32), ("height", C.c_int32), ("width", C.c_int32), ("span", C.c_int32),
+                ("first", C.c_int32), ("reserved0", C.c_int32), ("qa", C.c_void_p), ("qb", C.c_void_p), ("out", C.c_void_p)]
+
+
 def prop_level_shape(height, width, level):
     """Level `level` of a height x width plane: ceil(height / 2^level) x ceil(width / 2^level)."""
     return (int(height) + (1 << level) - 1) >> level, (int(width) + (1 << level) - 1) >> level
@@ -511,6 +542,10 @@ EXPORTS = {
     "lp_prop_match": (C.c_int, [C.POINTER(LpPropMatchDesc), C.c_void_p]),
     "lp_prop_fill": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "lp_prop_advance": (C.c_int, [C.POINTER(LpPropAdvanceDesc), C.c_void_p]),
+    "lp_prop_match_batch": (C.c_int, [C.POINTER(LpPropMatchBatchDesc), C.c_void_p]),
+    "lp_prop_fill_batch": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
+    "lp_prop_advance_batch": (C.c_int, [C.POINTER(LpPropAdvanceBatchDesc), C.c_void_p]),
+    "lp_prop_merge": (C.c_int, [C.POINTER(LpPropMergeDesc), C.c_void_p]),
 }
 
 

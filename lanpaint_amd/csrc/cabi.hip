@@ -71,6 +71,10 @@ int prop_key_mask_dispatch(const float* mask, int height, int width, int levels,
 int prop_match_dispatch(const lp_prop_match_desc* d, hipStream_t stream);
 int prop_fill_dispatch(const int32_t* vec, const int32_t* valid, int gh, int gw, int32_t* out, hipStream_t stream);
 int prop_advance_dispatch(const lp_prop_advance_desc* d, hipStream_t stream);
+int prop_match_batch_dispatch(const lp_prop_match_batch_desc* d, hipStream_t stream);
+int prop_fill_batch_dispatch(const lp_prop_fill_job* job, int jobs, int gh, int gw, hipStream_t stream);
+int prop_advance_batch_dispatch(const lp_prop_advance_batch_desc* d, hipStream_t stream);
+int prop_merge_dispatch(const lp_prop_merge_desc* d, hipStream_t stream);
 int reshape_mask_dispatch(const float* src, int sb, int sc, int sf, int sh, int sw, float* dst, int db, int dc, int df,
                           int dh, int dw, int taps, int flags, hipStream_t stream);
 }  // namespace lp
@@ -242,6 +246,20 @@ int lp_prop_fill(const int32_t* vec, const int32_t* valid, int32_t grid_h, int32
 }
 
 int lp_prop_advance(const lp_prop_advance_desc* desc, void* stream) { return lp::prop_advance_dispatch(desc, as_stream(stream)); }
+
+int lp_prop_match_batch(const lp_prop_match_batch_desc* desc, void* stream) {
+    return lp::prop_match_batch_dispatch(desc, as_stream(stream));
+}
+
+int lp_prop_fill_batch(const lp_prop_fill_job* job, int32_t jobs, int32_t grid_h, int32_t grid_w, void* stream) {
+    return lp::prop_fill_batch_dispatch(job, jobs, grid_h, grid_w, as_stream(stream));
+}
+
+int lp_prop_advance_batch(const lp_prop_advance_batch_desc* desc, void* stream) {
+    return lp::prop_advance_batch_dispatch(desc, as_stream(stream));
+}
+
+int lp_prop_merge(const lp_prop_merge_desc* desc, void* stream) { return lp::prop_merge_dispatch(desc, as_stream(stream)); }
 
 int lp_finalize(const lp_final_desc* desc, void* stream) { return lp::finalize_dispatch(desc, as_stream(stream)); }
 

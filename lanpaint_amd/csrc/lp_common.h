@@ -766,4 +766,12 @@ void pack_step_args(const StepPlan& p, const lp_step_desc& d, StepArgs* a);
 // does a kernel node launching `func` on grid x block run plan `p`, and nothing else?
 bool plan_is_node(const StepPlan& p, const void* func, const dim3& grid, const dim3& block);
 
+// stage 3 of lp_mask_stabilize, and lp_prop_merge: sign(q) * sqrt(|q|) capped at LP_STAB_SD_CAP = sign(q) * sqrt(min(|q|, 4096)), the
+// square root being monotonic and 64^2 exact
+__device__ __forceinline__ double capped_distance(int32_t q) {
+    const uint32_t mag = q < 0 ? 0u - static_cast<uint32_t>(q) : static_cast<uint32_t>(q);
+    const double r = sqrt(static_cast<double>(mag < 4096u ? mag : 4096u));
+    return q < 0 ? -r : r;
+}
+
 }  // namespace lp

@@ -16,8 +16,15 @@
 //                then the 3 x 3 median (the 19-exchange network) per component.
 //   advance      a block per 32 x 32 tile, four pixels per lane: the per-pixel vector from the block field, the new position
 //                map, the mask code through it, the output, and the bits' pyramid for the next step.
-// No scratch, no atomics, no floating point beyond the luma codes and the final c / 256.
+//   batches      match, fill and advance take up to LP_PROP_MAX_JOBS independent chain steps in one launch, the job on blockIdx.z.
+//                The job table (the jobs' pointers) travels by value in the kernel's arguments and is read with scalar loads;
+//                nothing is uploaded.  The single entries are one-job batches: every stage has one device body and one dispatch.
+//   merge        one lane per pixel and frame of a gap between two keys: the two chains' signed squared distances, their capped
+//                fp64 roots, the weighted mean in a fixed order, the ramp of half-width 1/2 around the zero crossing.
+// No scratch, no atomics, no floating point beyond the luma codes, the final c / 256 and the merge.
 #include "lp_common.h"
+
+#include <math.h>
 
 #include <algorithm>
 
@@ -121,24 +128,29 @@ __global__ __launch_bounds__(256) void lp_prop_key_mask_kernel(const float* __re
 }
 
 // ---- the masked block matching ---------------------------------------------------------------------------------------------------------
-struct match_args {
+struct match_job {
     const uint8_t* src;          // this level's planes
     const uint8_t* tgt;
     const uint8_t* msk;
     const int32_t* parent;       // [pgh, pgw, 2] or null
     int32_t*       vec;
     int32_t*       valid;
+};
+
+struct match_args {
     int32_t h, w, gw, pgh, pgw, search, smooth, subpel;
+    match_job job[LP_PROP_MAX_JOBS];                                 // blockIdx.z picks one: a uniform index, scalar loads
 };
 
 __global__ __launch_bounds__(kWave) void lp_prop_match_kernel(const match_args a) {
     __shared__ uint32_t s_src[kWin * 4], s_bm[kWin * 4], s_pat[kPatchRows * kPatchPitch];
     __shared__ int32_t s_S[kMaxCand];
+    const match_job jb = a.job[blockIdx.z];
     const int lane = threadIdx.x, bx = blockIdx.x, by = blockIdx.y;
     const int R = a.search, n = 2 * R + 1, ncand = n * n;
     int py = 0, px = 0;
-    if (a.parent) {
-        const int32_t* pv = a.parent + (static_cast<int64_t>(min(by >> 1, a.pgh - 1)) * a.pgw + min(bx >> 1, a.pgw - 1)) * 2;
+    if (jb.parent) {
+        const int32_t* pv = jb.parent + (static_cast<int64_t>(min(by >> 1, a.pgh - 1)) * a.pgw + min(bx >> 1, a.pgw - 1)) * 2;
         py = 2 * ((pv[0] + 8) >> 4);
         px = 2 * ((pv[1] + 8) >> 4);
     }
@@ -154,9 +166,9 @@ __global__ __launch_bounds__(kWave) void lp_prop_match_kernel(const match_args a
             const int x = wx + (lane & 3) * 4 + k;
             if (y >= 0 && y < a.h && x >= 0 && x < a.w) {
                 const int64_t p = static_cast<int64_t>(y) * a.w + x;
-                if (a.msk[p]) {
+                if (jb.msk[p]) {
                     bm |= 0xFFu << (8 * k);
-                    sv |= static_cast<uint32_t>(a.src[p]) << (8 * k);
+                    sv |= static_cast<uint32_t>(jb.src[p]) << (8 * k);
                     ++count;
                 }
             }
@@ -168,9 +180,9 @@ __global__ __launch_bounds__(kWave) void lp_prop_match_kernel(const match_args a
     for (int d = 1; d < kWave; d <<= 1) count += __shfl_xor(count, d, kWave);
     if (count < LP_PROP_MIN_PIXELS) {                                    // the whole wave leaves together
         if (lane == 0) {
-            a.vec[cell * 2] = 16 * py;
-            a.vec[cell * 2 + 1] = 16 * px;
-            a.valid[cell] = 0;
+            jb.vec[cell * 2] = 16 * py;
+            jb.vec[cell * 2 + 1] = 16 * px;
+            jb.valid[cell] = 0;
         }
         return;
     }
@@ -178,7 +190,7 @@ __global__ __launch_bounds__(kWave) void lp_prop_match_kernel(const match_args a
     const int rows = kWin + 2 * R;
     for (int i = lane; i < rows * kPatchPitch; i += kWave) {
         const int j = i >> 3, c0 = (i & 7) * 4;
-        const uint8_t* row = a.tgt + static_cast<int64_t>(clampi(wy + py - R + j, 0, a.h - 1)) * a.w;
+        const uint8_t* row = jb.tgt + static_cast<int64_t>(clampi(wy + py - R + j, 0, a.h - 1)) * a.w;
         uint32_t v = 0;
 #pragma unroll
         for (int k = 0; k < 4; ++k) v |= static_cast<uint32_t>(row[clampi(wx + px - R + c0 + k, 0, a.w - 1)]) << (8 * k);
@@ -219,9 +231,9 @@ __global__ __launch_bounds__(kWave) void lp_prop_match_kernel(const match_args a
                 if (d > 0) vx += (g > 0 ? 1 : (g < 0 ? -1 : 0)) * min(abs(8 * g) / d, 8);
             }
         }
-        a.vec[cell * 2] = vy;
-        a.vec[cell * 2 + 1] = vx;
-        a.valid[cell] = 1;
+        jb.vec[cell * 2] = vy;
+        jb.vec[cell * 2 + 1] = vx;
+        jb.valid[cell] = 1;
     }
 }
 
@@ -244,9 +256,23 @@ __device__ __forceinline__ int floor_div(int a, int b) {                 // b > 
     return (a % b != 0 && a < 0) ? q - 1 : q;
 }
 
-__global__ __launch_bounds__(256) void lp_prop_fill_kernel(const int32_t* __restrict__ vec, const int32_t* __restrict__ valid, int gh,
-                                                           int gw, int32_t* __restrict__ out) {
+struct fill_job {
+    const int32_t* vec;
+    const int32_t* valid;
+    int32_t*       out;
+};
+
+struct fill_args {
+    int32_t gh, gw;
+    fill_job job[LP_PROP_MAX_JOBS];
+};
+
+__global__ __launch_bounds__(256) void lp_prop_fill_kernel(const fill_args a) {
     constexpr int N = kFillSide * kFillSide;                             // 576
+    const int gh = a.gh, gw = a.gw;
+    const int32_t* __restrict__ vec = a.job[blockIdx.z].vec;
+    const int32_t* __restrict__ valid = a.job[blockIdx.z].valid;
+    int32_t* __restrict__ out = a.job[blockIdx.z].out;
     __shared__ int32_t s_y[2][N], s_x[2][N], s_ok[2][N];                 // ok: 1 valid, 0 invalid, -1 outside the grid
     const int y00 = blockIdx.y * kFillTile - kFillHalo, x00 = blockIdx.x * kFillTile - kFillHalo;
     for (int i = threadIdx.x; i < N; i += 256) {
@@ -303,14 +329,18 @@ __global__ __launch_bounds__(256) void lp_prop_fill_kernel(const int32_t* __rest
 }
 
 // ---- advance -------------------------------------------------------------------------------------------------------------------------------
-struct advance_args {
+struct advance_job {
     const int32_t* vec;
     const int32_t* pos_src;
     const uint8_t* key;
     int32_t*       pos_dst;
     float*         out;
     uint8_t*       mpyr;
+};
+
+struct advance_args {
     int32_t height, width, levels, gh, gw;
+    advance_job job[LP_PROP_MAX_JOBS];
 };
 
 struct bil_tap { int i0, i1, f; };
@@ -330,6 +360,7 @@ __device__ __forceinline__ int bil_sum(int a00, int a01, int a10, int a11, int f
 
 __global__ __launch_bounds__(256) void lp_prop_advance_kernel(const advance_args a) {
     __shared__ uint8_t s0[kTile * kTile], s1[kTile * kTile / 4];
+    const advance_job jb = a.job[blockIdx.z];
     const int H = a.height, W = a.width;
     for (int i = threadIdx.x; i < kTile * kTile; i += 256) {
         const int y = blockIdx.y * kTile + (i >> 5), x = blockIdx.x * kTile + (i & 31);
@@ -339,15 +370,15 @@ __global__ __launch_bounds__(256) void lp_prop_advance_kernel(const advance_args
             const int uy = 2 * y - 7, ux = 2 * x - 7, by0 = uy >> 4, bx0 = ux >> 4, fy = uy - 16 * by0, fx = ux - 16 * bx0;
             const int64_t r0 = static_cast<int64_t>(clampi(by0, 0, a.gh - 1)) * a.gw, r1 = static_cast<int64_t>(clampi(by0 + 1, 0, a.gh - 1)) * a.gw;
             const int c0 = clampi(bx0, 0, a.gw - 1), c1 = clampi(bx0 + 1, 0, a.gw - 1);
-            const int32_t *v00 = a.vec + (r0 + c0) * 2, *v01 = a.vec + (r0 + c1) * 2, *v10 = a.vec + (r1 + c0) * 2, *v11 = a.vec + (r1 + c1) * 2;
+            const int32_t *v00 = jb.vec + (r0 + c0) * 2, *v01 = jb.vec + (r0 + c1) * 2, *v10 = jb.vec + (r1 + c0) * 2, *v11 = jb.vec + (r1 + c1) * 2;
             const int Vy = (bil_sum(v00[0], v01[0], v10[0], v11[0], fy, fx) + 128) >> 8;
             const int Vx = (bil_sum(v00[1], v01[1], v10[1], v11[1], fy, fx) + 128) >> 8;
             // the new position
             const bil_tap ty = tap_of(16 * y - Vy, H), tx = tap_of(16 * x - Vx, W);
             int Py, Px;
-            if (a.pos_src) {
-                const int32_t *p00 = a.pos_src + (static_cast<int64_t>(ty.i0) * W + tx.i0) * 2, *p01 = a.pos_src + (static_cast<int64_t>(ty.i0) * W + tx.i1) * 2;
-                const int32_t *p10 = a.pos_src + (static_cast<int64_t>(ty.i1) * W + tx.i0) * 2, *p11 = a.pos_src + (static_cast<int64_t>(ty.i1) * W + tx.i1) * 2;
+            if (jb.pos_src) {
+                const int32_t *p00 = jb.pos_src + (static_cast<int64_t>(ty.i0) * W + tx.i0) * 2, *p01 = jb.pos_src + (static_cast<int64_t>(ty.i0) * W + tx.i1) * 2;
+                const int32_t *p10 = jb.pos_src + (static_cast<int64_t>(ty.i1) * W + tx.i0) * 2, *p11 = jb.pos_src + (static_cast<int64_t>(ty.i1) * W + tx.i1) * 2;
                 Py = (bil_sum(p00[0], p01[0], p10[0], p11[0], ty.f, tx.f) + 128) >> 8;
                 Px = (bil_sum(p00[1], p01[1], p10[1], p11[1], ty.f, tx.f) + 128) >> 8;
             } else {                                                     // P_key(y, x) = (16 y, 16 x)
@@ -355,22 +386,37 @@ __global__ __launch_bounds__(256) void lp_prop_advance_kernel(const advance_args
                 Px = (bil_sum(16 * tx.i0, 16 * tx.i1, 16 * tx.i0, 16 * tx.i1, ty.f, tx.f) + 128) >> 8;
             }
             const int64_t p = static_cast<int64_t>(y) * W + x;
-            a.pos_dst[p * 2] = Py;
-            a.pos_dst[p * 2 + 1] = Px;
+            jb.pos_dst[p * 2] = Py;
+            jb.pos_dst[p * 2 + 1] = Px;
             // the mask code through it
             const bil_tap ky = tap_of(Py, H), kx = tap_of(Px, W);
-            const uint8_t *k0 = a.key + static_cast<int64_t>(ky.i0) * W, *k1 = a.key + static_cast<int64_t>(ky.i1) * W;
+            const uint8_t *k0 = jb.key + static_cast<int64_t>(ky.i0) * W, *k1 = jb.key + static_cast<int64_t>(ky.i1) * W;
             const int c = bil_sum(k0[kx.i0], k0[kx.i1], k1[kx.i0], k1[kx.i1], ky.f, kx.f);
-            a.out[p] = static_cast<float>(c) * (1.0f / 256.0f);           // c <= 256 and a power of two: exact
+            jb.out[p] = static_cast<float>(c) * (1.0f / 256.0f);           // c <= 256 and a power of two: exact
             bit = c >= 128 ? 1 : 0;
         }
         s0[i] = bit;
     }
     __syncthreads();
-    tile_mask_pyramid(s0, s1, blockIdx.y, blockIdx.x, H, W, a.levels, a.mpyr);
+    tile_mask_pyramid(s0, s1, blockIdx.y, blockIdx.x, H, W, a.levels, jb.mpyr);
+}
+
+// ---- merge ---------------------------------------------------------------------------------------------------------------------------------
+// Frame f of the stack is frame j = first + f of a gap of n = span frames: out = 0.5 + ((n - j) sA + j sB) / n, clamped to 0..1.
+__global__ __launch_bounds__(256) void lp_prop_merge_kernel(const int32_t* __restrict__ qa, const int32_t* __restrict__ qb,
+                                                            float* __restrict__ out, int64_t plane, int span, int first) {
+    const int64_t p = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
+    if (p >= plane) return;
+    const int64_t i = static_cast<int64_t>(blockIdx.y) * plane + p;
+    const int j = first + static_cast<int>(blockIdx.y);
+    const double sa = capped_distance(qa[i]), sb = capped_distance(qb[i]);
+    const double acc = __dadd_rn(__dmul_rn(static_cast<double>(span - j), sa), __dmul_rn(static_cast<double>(j), sb));
+    const double sd = __ddiv_rn(acc, static_cast<double>(span));
+    out[i] = static_cast<float>(fmin(fmax(__dadd_rn(0.5, sd), 0.0), 1.0));
 }
 
 bool side_ok(int s) { return s > 0 && s <= LP_VMASK_MAX_SIDE; }
+bool jobs_ok(int n) { return n >= 1 && n <= LP_PROP_MAX_JOBS; }
 bool levels_ok(int l) { return l >= 1 && l <= LP_PROP_MAX_LEVELS; }
 int launched() { return hipGetLastError() == hipSuccess ? LP_OK : LP_E_LAUNCH; }
 uint32_t blocks_of(int64_t n, int per) { return static_cast<uint32_t>((n + per - 1) / per); }
@@ -409,21 +455,20 @@ int prop_key_mask_dispatch(const float* mask, int height, int width, int levels,
     return launched();
 }
 
-int prop_match_dispatch(const lp_prop_match_desc* dp, hipStream_t stream) {
+int prop_match_batch_dispatch(const lp_prop_match_batch_desc* dp, hipStream_t stream) {
     if (!dp) return LP_E_INVALID;
-    const lp_prop_match_desc& d = *dp;
+    const lp_prop_match_batch_desc& d = *dp;
     if (!side_ok(d.height) || !side_ok(d.width) || !levels_ok(d.levels) || d.level < 0 || d.level >= d.levels) return LP_E_INVALID;
     if (d.search < 1 || d.search > LP_PROP_MAX_SEARCH || d.smooth < 0 || d.smooth > LP_PROP_MAX_SMOOTH) return LP_E_INVALID;
-    if (!d.src || !d.tgt || !d.mask || !d.vec || !d.valid) return LP_E_INVALID;
-    if ((d.parent == nullptr) != (d.level == d.levels - 1) || d.parent == d.vec) return LP_E_INVALID;
+    if (!jobs_ok(d.jobs) || !d.job) return LP_E_INVALID;
     match_args a = {};
     const int64_t off = level_offset(d.height, d.width, d.level);
-    a.src = d.src + off;
-    a.tgt = d.tgt + off;
-    a.msk = d.mask + off;
-    a.parent = d.parent;
-    a.vec = d.vec;
-    a.valid = d.valid;
+    for (int i = 0; i < d.jobs; ++i) {
+        const lp_prop_match_job& j = d.job[i];
+        if (!j.src || !j.tgt || !j.mask || !j.vec || !j.valid) return LP_E_INVALID;
+        if ((j.parent == nullptr) != (d.level == d.levels - 1) || j.parent == j.vec) return LP_E_INVALID;
+        a.job[i] = {j.src + off, j.tgt + off, j.mask + off, j.parent, j.vec, j.valid};
+    }
     a.h = level_side(d.height, d.level);
     a.w = level_side(d.width, d.level);
     a.gw = (a.w + kB - 1) / kB;
@@ -433,35 +478,73 @@ int prop_match_dispatch(const lp_prop_match_desc* dp, hipStream_t stream) {
     a.search = d.search;
     a.smooth = d.smooth;
     a.subpel = d.level == 0;
-    hipLaunchKernelGGL(lp_prop_match_kernel, dim3(a.gw, gh), dim3(kWave), 0, stream, a);
+    hipLaunchKernelGGL(lp_prop_match_kernel, dim3(a.gw, gh, d.jobs), dim3(kWave), 0, stream, a);
+    return launched();
+}
+
+int prop_match_dispatch(const lp_prop_match_desc* dp, hipStream_t stream) {
+    if (!dp) return LP_E_INVALID;
+    const lp_prop_match_job job = {dp->src, dp->tgt, dp->mask, dp->parent, dp->vec, dp->valid};
+    const lp_prop_match_batch_desc d = {dp->height, dp->width, dp->levels, dp->level, dp->search, dp->smooth, 1, 0, &job};
+    return prop_match_batch_dispatch(&d, stream);
+}
+
+int prop_fill_batch_dispatch(const lp_prop_fill_job* job, int jobs, int gh, int gw, hipStream_t stream) {
+    if (!job || !jobs_ok(jobs) || gh < 1 || gw < 1 || gh > LP_PROP_MAX_GRID || gw > LP_PROP_MAX_GRID) return LP_E_INVALID;
+    fill_args a = {};
+    a.gh = gh;
+    a.gw = gw;
+    for (int i = 0; i < jobs; ++i) {
+        if (!job[i].vec || !job[i].valid || !job[i].out || job[i].out == job[i].vec) return LP_E_INVALID;
+        a.job[i] = {job[i].vec, job[i].valid, job[i].out};
+    }
+    hipLaunchKernelGGL(lp_prop_fill_kernel, dim3(blocks_of(gw, kFillTile), blocks_of(gh, kFillTile), jobs), dim3(256), 0, stream, a);
     return launched();
 }
 
 int prop_fill_dispatch(const int32_t* vec, const int32_t* valid, int gh, int gw, int32_t* out, hipStream_t stream) {
-    if (!vec || !valid || !out || out == vec || gh < 1 || gw < 1 || gh > LP_PROP_MAX_GRID || gw > LP_PROP_MAX_GRID) return LP_E_INVALID;
-    hipLaunchKernelGGL(lp_prop_fill_kernel, dim3(blocks_of(gw, kFillTile), blocks_of(gh, kFillTile)), dim3(256), 0, stream, vec, valid,
-                       gh, gw, out);
-    return launched();
+    const lp_prop_fill_job job = {vec, valid, out};
+    return prop_fill_batch_dispatch(&job, 1, gh, gw, stream);
 }
 
-int prop_advance_dispatch(const lp_prop_advance_desc* dp, hipStream_t stream) {
+int prop_advance_batch_dispatch(const lp_prop_advance_batch_desc* dp, hipStream_t stream) {
     if (!dp) return LP_E_INVALID;
-    const lp_prop_advance_desc& d = *dp;
-    if (!side_ok(d.height) || !side_ok(d.width) || !levels_ok(d.levels)) return LP_E_INVALID;
-    if (!d.vec || !d.key || !d.pos_dst || !d.out || !d.mask_pyramid || d.pos_dst == d.pos_src || d.mask_pyramid == d.key) return LP_E_INVALID;
+    const lp_prop_advance_batch_desc& d = *dp;
+    if (!side_ok(d.height) || !side_ok(d.width) || !levels_ok(d.levels) || !jobs_ok(d.jobs) || !d.job) return LP_E_INVALID;
     advance_args a = {};
-    a.vec = d.vec;
-    a.pos_src = d.pos_src;
-    a.key = d.key;
-    a.pos_dst = d.pos_dst;
-    a.out = d.out;
-    a.mpyr = d.mask_pyramid;
+    for (int i = 0; i < d.jobs; ++i) {
+        const lp_prop_advance_job& j = d.job[i];
+        if (!j.vec || !j.key || !j.pos_dst || !j.out || !j.mask_pyramid || j.pos_dst == j.pos_src || j.mask_pyramid == j.key)
+            return LP_E_INVALID;
+        a.job[i] = {j.vec, j.pos_src, j.key, j.pos_dst, j.out, j.mask_pyramid};
+    }
     a.height = d.height;
     a.width = d.width;
     a.levels = d.levels;
     a.gh = (d.height + kB - 1) / kB;
     a.gw = (d.width + kB - 1) / kB;
-    hipLaunchKernelGGL(lp_prop_advance_kernel, dim3(blocks_of(d.width, kTile), blocks_of(d.height, kTile)), dim3(256), 0, stream, a);
+    hipLaunchKernelGGL(lp_prop_advance_kernel, dim3(blocks_of(d.width, kTile), blocks_of(d.height, kTile), d.jobs), dim3(256), 0, stream, a);
+    return launched();
+}
+
+int prop_advance_dispatch(const lp_prop_advance_desc* dp, hipStream_t stream) {
+    if (!dp) return LP_E_INVALID;
+    const lp_prop_advance_job job = {dp->vec, dp->pos_src, dp->key, dp->pos_dst, dp->out, dp->mask_pyramid};
+    const lp_prop_advance_batch_desc d = {dp->height, dp->width, dp->levels, 1, &job};
+    return prop_advance_batch_dispatch(&d, stream);
+}
+
+int prop_merge_dispatch(const lp_prop_merge_desc* dp, hipStream_t stream) {
+    if (!dp) return LP_E_INVALID;
+    const lp_prop_merge_desc& d = *dp;
+    if (!d.qa || !d.qb || !d.out || !side_ok(d.height) || !side_ok(d.width)) return LP_E_INVALID;
+    if (d.span < 2 || d.first < 1 || d.frames < 1 || static_cast<int64_t>(d.first) + d.frames - 1 > static_cast<int64_t>(d.span) - 1)
+        return LP_E_INVALID;
+    if (static_cast<const void*>(d.out) == d.qa || static_cast<const void*>(d.out) == d.qb) return LP_E_INVALID;
+    if (d.span > 65535) return LP_E_UNSUPPORTED;                     // frames <= span - 1: inside a grid's y limit
+    const int64_t plane = static_cast<int64_t>(d.height) * d.width;
+    hipLaunchKernelGGL(lp_prop_merge_kernel, dim3(blocks_of(plane, 256), d.frames), dim3(256), 0, stream, d.qa, d.qb, d.out, plane, d.span,
+                       d.first);
     return launched();
 }
 

@@ -65,13 +65,6 @@ __device__ __forceinline__ int32_t window_median(const int32_t (&m)[2 * TM + 1],
     }
 }
 
-// stage 3: sign(qm) * sqrt(|qm|) capped at 64 = sign(qm) * sqrt(min(|qm|, 4096)), the square root being monotonic and 64^2 exact
-__device__ __forceinline__ double capped_distance(int32_t qm) {
-    const uint32_t mag = qm < 0 ? 0u - static_cast<uint32_t>(qm) : static_cast<uint32_t>(qm);
-    const double r = sqrt(static_cast<double>(min(mag, 4096u)));
-    return qm < 0 ? -r : r;
-}
-
 template <int TM, int TS>
 __global__ __launch_bounds__(kBlock) void lp_stabilize_kernel(const stab_args a) {
     const int64_t p = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;

@@ -1,0 +1,308 @@
+"""Video mask propagate from several keyframes: every painted key follows the picture's motion in both directions, and between
+two keys the two carried masks are merged through their signed distance fields.
+
+`propagate.propagate_masks` carries one key through the clip and loses accuracy with the distance from it; the video mask editor
+morphs between painted keys but does not follow the picture.  This joins the two:
+
+propagate_keys(images, masks, key_frames, levels=4, search=2, smooth=8) -> mask [F, H, W]
+        `images` [F, H, W, C]; `key_frames` strictly increasing frame indices; `masks` [K, H, W] (the k-th mask belongs to the
+        k-th key), [F, H, W] (the frames at the keys are read) or [H, W] for one key.  Every chain is the chain of
+        `propagate_masks` started from one key (`chain_plan` lists them).  A key frame returns its binarised painted mask, a
+        frame in front of the first or behind the last key its one chain's output, a frame between two keys a and b the merge:
+        the signed distances of the two chains' masks, capped at 64 pixels, weighted (b - t) : (t - a), a ramp of half a pixel
+        around their zero crossing.  So drift is pulled back to zero at every key.  One key gives `propagate_masks` bit for bit;
+        a still video with the same mask on every key returns that binarised mask; empty stays exactly 0, full exactly 1.  An
+        empty key next to a non-empty one says "nothing here": the other key's mask appears only in the last frames before it.
+        include/lanpaint_hip.h (lp_prop_*_batch, lp_prop_merge) states the rule in full.  Not handled: occlusion.
+
+HIP tensors only, no CPU fallback, no device -> host read.  The up to 2 K chains do not depend on one another, so step s of all
+of them is one batch: 2 levels + 1 launches per 32 active chains, and the call has as many dependent steps as its longest chain.
+The luma pyramids of the whole clip are held at once (uint8, about 4/3 byte per pixel; they must fit WS_CAP_BYTES); the fp32
+conversion of other input goes in chunks under WS_CAP_BYTES.  The step loop allocates nothing: the job tables are host arrays
+whose addresses move with the step.
+"""
+from __future__ import annotations
+
+import ctypes
+
+import numpy as np
+import torch
+
+from . import _cabi, stabilize
+from ._hostcall import chunks, int_in, launch, require_hip
+from ._util import _as_f32c
+from .propagate import _images, _params, _plane, key_mask
+
+MAX_JOBS = _cabi.LP_PROP_MAX_JOBS
+WS_CAP_BYTES = 1 << 30
+
+
+def chain_plan(frames, key_frames):
+    """The chains of a clip of `frames` frames with keys `key_frames`, as (key index, key frame, direction, length): backward
+    from the first key, per gap forward from its left key and backward from its right key, forward from the last key.  Step s
+    of a call runs the chains with length >= s, in this order, in launches of at most LP_PROP_MAX_JOBS.  No device."""
+    int_in(frames, 1, 1 << 30, "frames")
+    try:
+        keys = list(key_frames)
+    except TypeError:
+        raise ValueError(f"key_frames must be a sequence of frame indices, got {key_frames!r}") from None
+    if not keys:
+        raise ValueError("key_frames is empty: at least one key frame")
+    for k in keys:
+        int_in(k, 0, frames - 1, "a key frame")
+    if any(b <= a for a, b in zip(keys, keys[1:])):
+        raise ValueError(f"key_frames must be strictly increasing, got {keys}")
+    plan = [(0, keys[0], -1, keys[0])]
+    for i, (a, b) in enumerate(zip(keys, keys[1:])):
+        plan += [(i, a, 1, b - a - 1), (i + 1, b, -1, b - a - 1)]
+    plan.append((len(keys) - 1, keys[-1], 1, frames - 1 - keys[-1]))
+    return [c for c in plan if c[3] > 0]
+
+
+def _table(rows, what):
+    """`rows`: per job a tuple of tensors (or None); the tensors' addresses as a host uint64 [jobs, fields]."""
+    if not 1 <= len(rows) <= MAX_JOBS:
+        raise ValueError(f"{what}: 1..{MAX_JOBS} jobs, got {len(rows)}")
+    return np.array([[0 if t is None else t.data_ptr() for t in row] for row in rows], dtype=np.uint64)
+
+
+def _int32c(t, shape, what):
+    require_hip(t, what, __name__)
+    if t.dtype != torch.int32 or not t.is_contiguous() or tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{what} must be a contiguous int32 {list(shape)}, got {t.dtype} {list(t.shape)}")
+    return t
+
+
+def match_level_batch(jobs, H, W, levels, level, search=2, smooth=8):
+    """`propagate.match_level` for several independent steps in one launch.  `jobs`: per job (src, tgt, mpyr, parent) as there,
+    `parent` None exactly at the top level.  A list of (vec int32 [gh, gw, 2], valid int32 [gh, gw])."""
+    _params(levels, search, smooth)
+    int_in(level, 0, levels - 1, "level")
+    _plane(H, W)
+    stride = _cabi.prop_pyramid_ws_bytes(1, H, W, levels)
+    gh, gw = _cabi.prop_grid(H, W, level)
+    rows, outs = [], []
+    for src, tgt, mpyr, parent in jobs:
+        for t, what in ((src, "src"), (tgt, "tgt"), (mpyr, "mpyr")):
+            require_hip(t, what, __name__)
+            if t.dtype != torch.uint8 or not t.is_contiguous() or t.numel() != stride:
+                raise ValueError(f"{what} must be one frame's pyramid: {stride} contiguous uint8")
+        if (parent is None) != (level == levels - 1):
+            raise ValueError("parent is given exactly below the top level")
+        if parent is not None:
+            _int32c(parent, (*_cabi.prop_grid(H, W, level + 1), 2), "parent")
+        vec = torch.empty((gh, gw, 2), dtype=torch.int32, device=src.device)
+        valid = torch.empty((gh, gw), dtype=torch.int32, device=src.device)
+        rows.append((src, tgt, mpyr, parent, vec, valid))
+        outs.append((vec, valid))
+    table = _table(rows, "match_level_batch")
+    d = _cabi.LpPropMatchBatchDesc(H, W, levels, level, search, smooth, len(rows), 0, table.ctypes.data)
+    launch("lp_prop_match_batch", rows[0][0].device, ctypes.byref(d))
+    return outs
+
+
+def fill_median_batch(jobs):
+    """`propagate.fill_median` for several fields of one grid in one launch.  `jobs`: per job (vec, valid).  A list of fields."""
+    rows = []
+    for vec, valid in jobs:
+        require_hip(vec, "vec", __name__)
+        grid = tuple(rows[0][0].shape[:2] if rows else vec.shape[:2])    # the first job's grid is every job's
+        _int32c(vec, (*grid, 2), "vec")
+        _int32c(valid, grid, "valid")
+        rows.append((vec, valid, torch.empty_like(vec)))
+    table = _table(rows, "fill_median_batch")
+    gh, gw = rows[0][0].shape[:2]
+    launch("lp_prop_fill_batch", rows[0][0].device, table.ctypes.data, len(rows), gh, gw)
+    return [r[2] for r in rows]
+
+
+def advance_batch(jobs, levels):
+    """`propagate.advance` for several independent steps of one plane in one launch.  `jobs`: per job (vec, pos, key_bits), `pos`
+    None for the key frame's positions.  A list of (positions, mask fp32 [H, W], the pyramid of its bits uint8 [1, stride])."""
+    int_in(levels, 1, _cabi.LP_PROP_MAX_LEVELS, "levels")
+    rows, outs = [], []
+    for vec, pos, key_bits in jobs:
+        require_hip(vec, "vec", __name__)
+        require_hip(key_bits, "key_bits", __name__)
+        if key_bits.dtype != torch.uint8 or key_bits.ndim != 2 or not key_bits.is_contiguous() \
+                or (rows and key_bits.shape != rows[0][2].shape):
+            raise ValueError("key_bits must be a contiguous uint8 [H, W], the same plane in every job")
+        H, W = key_bits.shape
+        _plane(H, W)
+        _int32c(vec, (*_cabi.prop_grid(H, W), 2), "vec")
+        if pos is not None:
+            _int32c(pos, (H, W, 2), "pos")
+        dev = vec.device
+        new = (torch.empty((H, W, 2), dtype=torch.int32, device=dev), torch.empty((H, W), dtype=torch.float32, device=dev),
+               torch.empty((1, _cabi.prop_pyramid_ws_bytes(1, H, W, levels)), dtype=torch.uint8, device=dev))
+        rows.append((vec, pos, key_bits, *new))
+        outs.append(new)
+    table = _table(rows, "advance_batch")
+    H, W = rows[0][2].shape
+    d = _cabi.LpPropAdvanceBatchDesc(H, W, levels, len(rows), table.ctypes.data)
+    launch("lp_prop_advance_batch", rows[0][0].device, ctypes.byref(d))
+    return outs
+
+
+def merge_gap(qa, qb, span, first=1, out=None):
+    """The merge of one gap's in-between frames: `qa`, `qb` int32 [n, H, W], the signed squared distances (stabilize.signed_d2)
+    of the forward and the backward chain's masks at the gap's frames first..first + n - 1; `span` the distance between the two
+    keys.  fp32 [n, H, W].  One launch."""
+    int_in(span, 2, 65535, "span")
+    int_in(first, 1, span - 1, "first")
+    require_hip(qa, "qa", __name__)
+    require_hip(qb, "qb", __name__)
+    if qa.ndim != 3 or not 1 <= qa.shape[0] <= span - first:
+        raise ValueError(f"qa must be [n, H, W] with first + n - 1 <= span - 1, got {tuple(qa.shape)}")
+    _int32c(qa, qa.shape, "qa")
+    _int32c(qb, qa.shape, "qb")
+    n, H, W = qa.shape
+    _plane(H, W)
+    out = torch.empty((n, H, W), dtype=torch.float32, device=qa.device) if out is None else out
+    d = _cabi.LpPropMergeDesc(n, H, W, span, first, 0, qa.data_ptr(), qb.data_ptr(), out.data_ptr())
+    launch("lp_prop_merge", qa.device, ctypes.byref(d))
+    return out
+
+
+def _clip_pyramids(images, levels):
+    """The luma pyramids of all frames, uint8 [F, stride]; input that needs a conversion to contiguous fp32 goes through it in
+    chunks of frames under WS_CAP_BYTES (a frame's pyramid depends on that frame only)."""
+    F, H, W, C = images.shape
+    stride = _cabi.prop_pyramid_ws_bytes(1, H, W, levels)
+    if F * stride > WS_CAP_BYTES:
+        raise ValueError(f"the luma pyramids of {F} frames of {H}x{W} take {F * stride} bytes, above WS_CAP_BYTES = {WS_CAP_BYTES}")
+    pyr = torch.empty((F, stride), dtype=torch.uint8, device=images.device)
+    direct = images.dtype == torch.float32 and images.is_contiguous()
+    for s, n in chunks(F, 1 if direct else H * W * C * 4, WS_CAP_BYTES):
+        part = _as_f32c(images[s:s + n])
+        d = _cabi.LpPropLumaDesc(n, H, W, C, levels, 0, part.data_ptr(), pyr[s:s + n].data_ptr())
+        launch("lp_prop_luma", images.device, ctypes.byref(d))
+    return pyr
+
+
+class _Chains:
+    """The buffers of all chains of a call and the job tables of their steps.  A table is a host uint64 array of device
+    addresses, one row per chain; step s of chain c reads and writes at addresses that are linear in s or alternate with its
+    parity, so a step fills columns with a few numpy operations and allocates nothing on the device."""
+
+    def __init__(self, plan, pyr, key_pyrs, outs, H, W, levels, search, smooth):
+        dev = pyr.device
+        self.H, self.W, self.levels, self.search, self.smooth, self.dev = H, W, levels, search, smooth, dev
+        n = len(plan)
+        self.length = np.array([c[3] for c in plan], dtype=np.int64)
+        self.grids = [_cabi.prop_grid(H, W, lv) for lv in range(levels)]
+        stride = pyr.shape[1]
+        self._keep = []                                              # the device buffers behind the addresses
+
+        def buffers(shape, dtype):
+            t = torch.empty((n, *shape), dtype=dtype, device=dev)
+            self._keep.append(t)
+            step = t[0].numel() * t.element_size()
+            return np.uint64(t.data_ptr()) + np.arange(n, dtype=np.uint64) * np.uint64(step)
+        self.raw = [buffers((gh, gw, 2), torch.int32) for gh, gw in self.grids]
+        self.valid = [buffers((gh, gw), torch.int32) for gh, gw in self.grids]
+        self.field = [buffers((gh, gw, 2), torch.int32) for gh, gw in self.grids]
+        self.pos = [buffers((H, W, 2), torch.int32) for _ in range(2)]
+        self.mpyr = [buffers((stride,), torch.uint8) for _ in range(2)]
+        self.key = np.array([key_pyrs[c[0]].data_ptr() for c in plan], dtype=np.uint64)
+        # frame k + d s of the clip's pyramids, and where step s writes its mask: both base + s * step, the step signed
+        self.luma0 = np.array([pyr.data_ptr() + c[1] * stride for c in plan], dtype=np.int64)
+        self.luma_step = np.array([c[2] * stride for c in plan], dtype=np.int64)
+        self.out0 = np.array([o[0] for o in outs], dtype=np.int64)
+        self.out_step = np.array([o[1] for o in outs], dtype=np.int64)
+        self.match_desc = [_cabi.LpPropMatchBatchDesc(H, W, levels, lv, search, smooth, 0, 0, None) for lv in range(levels)]
+        self.advance_desc = _cabi.LpPropAdvanceBatchDesc(H, W, levels, 0, None)
+        self.active = None
+
+    def _select(self, idx):
+        """The tables of the chains `idx`; the columns that do not move with the step are filled here."""
+        self.active, m = idx, len(idx)
+        self.t_match = [np.zeros((m, 6), dtype=np.uint64) for _ in range(self.levels)]
+        self.t_fill = [np.stack([self.raw[lv][idx], self.valid[lv][idx], self.field[lv][idx]], axis=1) for lv in range(self.levels)]
+        self.t_advance = np.zeros((m, 6), dtype=np.uint64)
+        for lv, t in enumerate(self.t_match):
+            if lv + 1 < self.levels:
+                t[:, 3] = self.field[lv + 1][idx]
+            t[:, 4], t[:, 5] = self.raw[lv][idx], self.valid[lv][idx]
+        self.t_advance[:, 0], self.t_advance[:, 2] = self.field[0][idx], self.key[idx]
+
+    def step(self, s):
+        """Step s of every chain that has one: 2 levels + 1 launches per MAX_JOBS chains."""
+        idx = np.flatnonzero(self.length >= s)
+        if self.active is None or len(idx) != len(self.active):
+            self._select(idx)
+        src = (self.luma0[idx] + (s - 1) * self.luma_step[idx]).astype(np.uint64)
+        tgt = (self.luma0[idx] + s * self.luma_step[idx]).astype(np.uint64)
+        mask = self.key[idx] if s == 1 else self.mpyr[(s - 1) & 1][idx]
+        for t in self.t_match:
+            t[:, 0], t[:, 1], t[:, 2] = src, tgt, mask
+        a = self.t_advance
+        a[:, 1] = 0 if s == 1 else self.pos[(s - 1) & 1][idx]
+        a[:, 3], a[:, 5] = self.pos[s & 1][idx], self.mpyr[s & 1][idx]
+        a[:, 4] = (self.out0[idx] + s * self.out_step[idx]).astype(np.uint64)
+        for lo in range(0, len(idx), MAX_JOBS):
+            n = min(MAX_JOBS, len(idx) - lo)
+            for lv in range(self.levels - 1, -1, -1):
+                d = self.match_desc[lv]
+                d.jobs, d.job = n, self.t_match[lv][lo:].ctypes.data
+                launch("lp_prop_match_batch", self.dev, ctypes.byref(d))
+                gh, gw = self.grids[lv]
+                launch("lp_prop_fill_batch", self.dev, self.t_fill[lv][lo:].ctypes.data, n, gh, gw)
+            d = self.advance_desc
+            d.jobs, d.job = n, a[lo:].ctypes.data
+            launch("lp_prop_advance_batch", self.dev, ctypes.byref(d))
+
+
+def _key_masks(masks, keys, F, H, W):
+    """The K key masks as a list of [H, W] tensors."""
+    if masks.ndim == 2 and len(keys) == 1:
+        masks = masks.unsqueeze(0)
+    if masks.ndim != 3 or masks.shape[0] not in (len(keys), F) or tuple(masks.shape[1:]) != (H, W):
+        raise ValueError(f"masks {tuple(masks.shape)} do not match {len(keys)} keys in {F} frames of {H}x{W}: [K, H, W], "
+                         "[F, H, W], or [H, W] for one key")
+    return [masks[i] for i in (range(len(keys)) if masks.shape[0] == len(keys) else keys)]
+
+
+def propagate_keys(images, masks, key_frames, levels=4, search=2, smooth=8):
+    """The masks painted on the frames `key_frames` of `images` [F, H, W, C], followed through every frame and merged between
+    the keys (module docstring): fp32 [F, H, W] on the images' device.  No device -> host read."""
+    _params(levels, search, smooth)
+    if not torch.is_tensor(images) or images.ndim != 4:
+        _images(images)                                              # raises: the frame count is needed for the keys' check
+    plan = chain_plan(images.shape[0], key_frames)                   # the numbers before the tensors
+    keys = list(key_frames)
+    _images(images)
+    require_hip(masks, "masks", __name__)
+    F, H, W, _ = images.shape
+    dev = images.device
+    painted = _key_masks(masks, keys, F, H, W)
+    out = torch.empty((F, H, W), dtype=torch.float32, device=dev)
+    key_pyrs = []
+    for k, m in zip(keys, painted):
+        mpyr, bits = key_mask(m.to(dev), levels)
+        key_pyrs.append(mpyr)
+        out[k] = bits
+    if not plan:
+        return out
+    # a gap's forward chain writes into `out`, its backward chain into `back`; the merge then overwrites the gap's frames of `out`
+    gaps = [(a, b) for a, b in zip(keys, keys[1:]) if b - a > 1]
+    back = torch.empty((sum(b - a - 1 for a, b in gaps), H, W), dtype=torch.float32, device=dev)
+    back_at, n = {}, 0
+    for a, b in gaps:
+        back_at[b] = back[n:n + b - a - 1]
+        n += b - a - 1
+    plane = H * W * 4
+    outs = []
+    for i, k, d, length in plan:
+        if d < 0 and i > 0:                                          # frame k - s is row (k - s) - (k - length) of the gap's stack
+            outs.append((back_at[k].data_ptr() + length * plane, -plane))
+        else:
+            outs.append((out.data_ptr() + k * plane, d * plane))
+    pyr = _clip_pyramids(images, levels)
+    chains = _Chains(plan, pyr, key_pyrs, outs, H, W, levels, search, smooth)
+    for s in range(1, int(chains.length.max()) + 1):
+        chains.step(s)
+    for a, b in gaps:
+        mid = out[a + 1:b]
+        merge_gap(stabilize.signed_d2(mid), stabilize.signed_d2(back_at[b]), b - a, 1, mid)
+    return out
