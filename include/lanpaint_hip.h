@@ -1643,6 +1643,68 @@ typedef struct lp_prop_merge_desc {
 } lp_prop_merge_desc;
 LP_API int lp_prop_merge(const lp_prop_merge_desc* desc, void* stream);
 
+/* ---- Video mask propagate, occlusion-aware (beyond the reference) ------------------------------------------------------------------
+ * When the masked subject passes behind something, the carried mask of the single-key section lies on what is in front, and the
+ * sampler repaints it.  The position map P_t names, for every pixel of frame t, where it was in the key frame; sampling the key
+ * frame's luma through it shows what the subject should look like there.  Where the picture of t looks different, something is in
+ * front: that part of the mask is taken out and returned separately as `hidden`.  A step of this form is the single-key step with
+ * two launches behind it (the existing entries keep their meaning and their bits):
+ *   lp_prop_match / lp_prop_fill per level -> lp_prop_advance (its out and mask_pyramid go to scratch) -> lp_prop_visible ->
+ *   lp_prop_occlude.
+ * All of it is integer arithmetic.  For frame t after lp_prop_advance: c(y, x) in 0..256 the advance's mask code, m = c >= 128
+ * (level 0 of the pyramid the advance wrote), P_t the positions, Yt and Yk level 0 of the luma pyramids of t and of the key frame;
+ * bil, the block grid, the window, LP_PROP_BLOCK, LP_PROP_HALO and LP_PROP_MIN_PIXELS as in the single-key section.
+ * 1 warped key luma  K(y, x) = (bil(Yk, P_t(y, x)) + 128) >> 8, in 0..255;  d = Yt(y, x) - K(y, x).
+ * 2 per block  (lp_prop_visible) M: the pixels of the block's window with m = 1, n = |M|.  n < LP_PROP_MIN_PIXELS: the flag is 0
+ *              (no evidence: the block counts as visible).  Else D = sum over M of d; mu = floor((2 D + n) / (2 n)), the
+ *              mathematical floor, clamped to +-LP_PROP_VIS_MAX_BIAS = 32 (an exposure change is forgiven, a dark object in front
+ *              of a bright one is not); R = sum over M of |d - mu|; the flag is 1 (occluded) iff R > occlusion * n, with occlusion
+ *              in 1..255 the mean residual in grey levels.  |D| and R stay below 2^17.  flags: int32 [gh, gw].
+ * 3 per pixel  (lp_prop_occlude) v = 1 - flag; w in 0..256 is v interpolated over the blocks exactly as lp_prop_advance
+ *              interpolates the field: per axis u = 2x - 7, b0 = u >> 4, f = u - 16 b0, blocks b0 and b0 + 1 clamped to the grid,
+ *              w = (16 - fy) * ((16 - fx) v00 + fx v01) + fy * ((16 - fx) v10 + fx v11).  c' = (c * w + 128) >> 8;
+ *              mask = c' / 256 and hidden = (c - c') / 256, both fp32 and exact; the bits that weight the next step's match are
+ *              c' >= 128, and their pyramid is written as lp_prop_advance writes its own.  c is read back from the advance's out:
+ *              c = (int)(out * 256), exact, held inside 0..256.
+ * 4 no memory between frames: the test is against the key in every frame, so a part that was hidden is visible again as soon as
+ *   its residual drops.  Blocks whose bits are gone are invalid in the next match and are filled from their valid neighbours (the
+ *   existing rule): the hidden part's positions follow the visible rest.  A subject that is hidden entirely leaves the zero field;
+ *   if it reappears elsewhere it is lost.
+ * 5 the key frame's own output is its binarised mask (lp_prop_key_mask), its hidden is 0.
+ * What follows from the rule, bit for bit: a video of equal frames returns the binarised key mask and an all-zero hidden for every
+ * occlusion >= 1 (d = 0 everywhere, w = 256); so does a noise-free whole-pixel shift away from the border; an empty mask gives 0
+ * and 0; mask + hidden = c / 256 on every frame where the chain's bits so far equal the plain chain's.  occlusion = 0 is the
+ * caller's "off": it makes neither launch and returns the plain chain and zeros.
+ * Launches (csrc/propagate_kernel.hip): lp_prop_visible, a block of 256 lanes per 32 x 32 pixels: d of the tile and its halo of 4
+ * goes to LDS once as int16 (a pixel outside the image or the mask holds a marker), four pixels per lane with P_t read as two
+ * 16-byte vectors when width % 4 == 0; then 16 lanes per window, a row each, D and n and then R summed across them in registers.
+ * lp_prop_occlude: a block per 32 x 32 tile, one lane per four pixels, ending in the pyramid's tile code.  One job each.
+ * LP_E_INVALID: a null pointer, a side or levels outside its range, occlusion outside 1..255, flags aliasing an input of
+ * lp_prop_visible; out, hidden or mask_pyramid aliasing code or flags or one another in lp_prop_occlude (the advance's pyramid is
+ * no input there: c carries its bits, so mask_pyramid may not be the buffer lp_prop_visible still reads, which the caller orders).
+ * All checked before any HIP call.                                                                                                  */
+#define LP_PROP_VIS_MAX_BIAS 32
+
+typedef struct lp_prop_visible_desc {
+    int32_t height, width, occlusion, reserved0;  /* occlusion 1..255                                                       */
+    const int32_t* pos;                           /* P_t [height, width, 2], as lp_prop_advance wrote it                    */
+    const uint8_t* tgt;                           /* Yt: level 0 of frame t's luma pyramid [height, width]                  */
+    const uint8_t* key;                           /* Yk: level 0 of the key frame's luma pyramid                            */
+    const uint8_t* mask;                          /* m: level 0 of the pyramid lp_prop_advance wrote                        */
+    int32_t*       flags;                         /* out, [gh, gw], 0 visible / 1 occluded                                  */
+} lp_prop_visible_desc;
+LP_API int lp_prop_visible(const lp_prop_visible_desc* desc, void* stream);
+
+typedef struct lp_prop_occlude_desc {
+    int32_t height, width, levels, reserved0;
+    const float*   code;                          /* c / 256 [height, width]: lp_prop_advance's out                         */
+    const int32_t* flags;                         /* [gh, gw] as lp_prop_visible wrote them                                 */
+    float*         out;                           /* out, mask = c' / 256 [height, width]                                   */
+    float*         hidden;                        /* out, (c - c') / 256 [height, width]                                    */
+    uint8_t*       mask_pyramid;                  /* out, the pyramid of the bits c' >= 128                                 */
+} lp_prop_occlude_desc;
+LP_API int lp_prop_occlude(const lp_prop_occlude_desc* desc, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -426,6 +426,20 @@ class LpPropMergeDesc(C.Structure):
                 ("first", C.c_int32), ("reserved0", C.c_int32), ("qa", C.c_void_p), ("qb", C.c_void_p), ("out", C.c_void_p)]
 
 
+LP_PROP_VIS_MAX_BIAS = 32
+
+
+class LpPropVisibleDesc(C.Structure):
+    _fields_ = [("height", C.c_int32), ("width", C.c_int32), ("occlusion", C.c_int32), ("reserved0", C.c_int32),
+                ("pos", C.c_void_p), ("tgt", C.c_void_p), ("key", C.c_void_p), ("mask", C.c_void_p), ("flags", C.c_void_p)]
+
+
+class LpPropOccludeDesc(C.Structure):
+    _fields_ = [("height", C.c_int32), ("width", C.c_int32), ("levels", C.c_int32), ("reserved0", C.c_int32),
+                ("code", C.c_void_p), ("flags", C.c_void_p), ("out", C.c_void_p), ("hidden", C.c_void_p),
+                ("mask_pyramid", C.c_void_p)]
+
+
 def prop_level_shape(height, width, level):
     """Level `level` of a height x width plane: ceil(height / 2^level) x ceil(width / 2^level)."""
     return (int(height) + (1 << level) - 1) >> level, (int(width) + (1 << level) - 1) >> level
@@ -546,6 +560,8 @@ EXPORTS = {
     "lp_prop_fill_batch": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
     "lp_prop_advance_batch": (C.c_int, [C.POINTER(LpPropAdvanceBatchDesc), C.c_void_p]),
     "lp_prop_merge": (C.c_int, [C.POINTER(LpPropMergeDesc), C.c_void_p]),
+    "lp_prop_visible": (C.c_int, [C.POINTER(LpPropVisibleDesc), C.c_void_p]),
+    "lp_prop_occlude": (C.c_int, [C.POINTER(LpPropOccludeDesc), C.c_void_p]),
 }
 
 

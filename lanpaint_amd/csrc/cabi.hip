@@ -75,6 +75,8 @@ int prop_match_batch_dispatch(const lp_prop_match_batch_desc* d, hipStream_t str
 int prop_fill_batch_dispatch(const lp_prop_fill_job* job, int jobs, int gh, int gw, hipStream_t stream);
 int prop_advance_batch_dispatch(const lp_prop_advance_batch_desc* d, hipStream_t stream);
 int prop_merge_dispatch(const lp_prop_merge_desc* d, hipStream_t stream);
+int prop_visible_dispatch(const lp_prop_visible_desc* d, hipStream_t stream);
+int prop_occlude_dispatch(const lp_prop_occlude_desc* d, hipStream_t stream);
 int reshape_mask_dispatch(const float* src, int sb, int sc, int sf, int sh, int sw, float* dst, int db, int dc, int df,
                           int dh, int dw, int taps, int flags, hipStream_t stream);
 }  // namespace lp
@@ -260,6 +262,10 @@ int lp_prop_advance_batch(const lp_prop_advance_batch_desc* desc, void* stream) 
 }
 
 int lp_prop_merge(const lp_prop_merge_desc* desc, void* stream) { return lp::prop_merge_dispatch(desc, as_stream(stream)); }
+
+int lp_prop_visible(const lp_prop_visible_desc* desc, void* stream) { return lp::prop_visible_dispatch(desc, as_stream(stream)); }
+
+int lp_prop_occlude(const lp_prop_occlude_desc* desc, void* stream) { return lp::prop_occlude_dispatch(desc, as_stream(stream)); }
 
 int lp_finalize(const lp_final_desc* desc, void* stream) { return lp::finalize_dispatch(desc, as_stream(stream)); }
 

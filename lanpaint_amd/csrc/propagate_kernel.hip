@@ -19,9 +19,15 @@
 //   batches      match, fill and advance take up to LP_PROP_MAX_JOBS independent chain steps in one launch, the job on blockIdx.z.
 //                The job table (the jobs' pointers) travels by value in the kernel's arguments and is read with scalar loads;
 //                nothing is uploaded.  The single entries are one-job batches: every stage has one device body and one dispatch.
+//   visible      the occlusion-aware form's hot path.  A block per 32 x 32 tile: d = Yt - K (K the key frame's luma sampled through
+//                P_t) of the tile and its halo of 4 goes to LDS once as int16, a marker where the pixel is outside the image or the
+//                mask, four pixels per lane, P_t read as two 16-byte vectors; then 16 lanes per window of the tile's 4 x 4 blocks,
+//                a row each (two ds_read_b128 on an 80-byte pitch), D and n and then R summed across them with shuffles.
+//   occlude      a block per 32 x 32 tile, four pixels per lane: the flags interpolated as advance interpolates the field, the
+//                visible and the hidden part of the advance's code, and the visible bits' pyramid from the same tile code.
 //   merge        one lane per pixel and frame of a gap between two keys: the two chains' signed squared distances, their capped
 //                fp64 roots, the weighted mean in a fixed order, the ramp of half-width 1/2 around the zero crossing.
-// No scratch, no atomics, no floating point beyond the luma codes, the final c / 256 and the merge.
+// No scratch, no atomics, no floating point beyond the luma codes, the final c / 256 (read back by occlude) and the merge.
 #include "lp_common.h"
 
 #include <math.h>
@@ -401,6 +407,142 @@ __global__ __launch_bounds__(256) void lp_prop_advance_kernel(const advance_args
     tile_mask_pyramid(s0, s1, blockIdx.y, blockIdx.x, H, W, a.levels, jb.mpyr);
 }
 
+// ---- visible and occlude: the occlusion-aware form ------------------------------------------------------------------------------------
+constexpr int kVisSide = kTile + 2 * kHalo;                             // 40: a tile and its halo
+constexpr int kVisQuads = kVisSide / 4;                                 // 10 quads of four pixels per row
+constexpr int16_t kVisNone = INT16_MIN;                                 // a pixel outside the image or the mask; |d| <= 255
+
+static_assert(kVisSide % 8 == 0 && kTile / kB == 4 && kWin == 16, "the visible kernel's window rows: 16 int16, 16-byte aligned");
+
+// d = Yt - K for one mask pixel inside the image: K = (bil(Yk, P_t) + 128) >> 8
+__device__ __forceinline__ int16_t residual_of(const uint8_t* __restrict__ key, int H, int W, int Py, int Px, int yt) {
+    const bil_tap ky = tap_of(Py, H), kx = tap_of(Px, W);
+    const uint8_t *k0 = key + static_cast<int64_t>(ky.i0) * W, *k1 = key + static_cast<int64_t>(ky.i1) * W;
+    const int K = (bil_sum(k0[kx.i0], k0[kx.i1], k1[kx.i0], k1[kx.i1], ky.f, kx.f) + 128) >> 8;
+    return static_cast<int16_t>(yt - K);
+}
+
+__global__ __launch_bounds__(256) void lp_prop_visible_kernel(const int32_t* __restrict__ pos, const uint8_t* __restrict__ tgt,
+                                                              const uint8_t* __restrict__ key, const uint8_t* __restrict__ msk,
+                                                              int32_t* __restrict__ flags, int H, int W, int gh, int gw, int occlusion,
+                                                              int wide) {
+    __shared__ __attribute__((aligned(16))) int16_t s_d[kVisSide * kVisSide];      // 3200 bytes; a row is 80 bytes = 5 x 16
+    const int y00 = blockIdx.y * kTile - kHalo, x00 = blockIdx.x * kTile - kHalo;     // x00 is a multiple of 4
+    // wide: width % 4 == 0 and the planes 16-byte aligned, so a quad is inside its row or outside it, and one vector
+    for (int i = threadIdx.x; i < kVisSide * kVisQuads; i += 256) {
+        const int r = i / kVisQuads, q = i - r * kVisQuads;
+        const int y = y00 + r, x = x00 + 4 * q;
+        int16_t d[4] = {kVisNone, kVisNone, kVisNone, kVisNone};
+        if (y >= 0 && y < H && x + 3 >= 0 && x < W) {
+            const int64_t p = static_cast<int64_t>(y) * W + x;
+            if (wide) {                                                  // x >= 0 and x + 3 < W; p is a multiple of 4
+                const uchar4 m4 = *reinterpret_cast<const uchar4*>(msk + p);
+                if (m4.x | m4.y | m4.z | m4.w) {
+                    const uchar4 t4 = *reinterpret_cast<const uchar4*>(tgt + p);
+                    const int4 pa = *reinterpret_cast<const int4*>(pos + p * 2), pb = *reinterpret_cast<const int4*>(pos + p * 2 + 4);
+                    if (m4.x) d[0] = residual_of(key, H, W, pa.x, pa.y, t4.x);
+                    if (m4.y) d[1] = residual_of(key, H, W, pa.z, pa.w, t4.y);
+                    if (m4.z) d[2] = residual_of(key, H, W, pb.x, pb.y, t4.z);
+                    if (m4.w) d[3] = residual_of(key, H, W, pb.z, pb.w, t4.w);
+                }
+            } else {
+#pragma unroll
+                for (int k = 0; k < 4; ++k)
+                    if (x + k >= 0 && x + k < W && msk[p + k]) d[k] = residual_of(key, H, W, pos[(p + k) * 2], pos[(p + k) * 2 + 1], tgt[p + k]);
+            }
+        }
+        *reinterpret_cast<short4*>(s_d + r * kVisSide + 4 * q) = make_short4(d[0], d[1], d[2], d[3]);
+    }
+    __syncthreads();
+    // 16 lanes per window, a row each: block (wy, wx) of the tile's 4 x 4, window row `row`
+    const int win = threadIdx.x >> 4, row = threadIdx.x & 15, wy = win >> 2, wx = win & 3;
+    const int16_t* src = s_d + (wy * kB + row) * kVisSide + wx * kB;     // 16 int16, 16-byte aligned
+    const int4 lo = *reinterpret_cast<const int4*>(src), hi = *reinterpret_cast<const int4*>(src + 8);
+    const int packed[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+    int v[16];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        v[2 * k] = static_cast<int16_t>(packed[k] & 0xFFFF);
+        v[2 * k + 1] = packed[k] >> 16;                                  // arithmetic: the sign comes along
+    }
+    int D = 0, n = 0;
+#pragma unroll
+    for (int k = 0; k < 16; ++k) {
+        const bool in = v[k] != kVisNone;
+        D += in ? v[k] : 0;
+        n += in ? 1 : 0;
+    }
+#pragma unroll
+    for (int s = 1; s < 16; s <<= 1) {                                   // the 16 lanes of a window are one aligned group of a wave
+        D += __shfl_xor(D, s, kWave);
+        n += __shfl_xor(n, s, kWave);
+    }
+    const int mu = n > 0 ? clampi(floor_div(2 * D + n, 2 * n), -LP_PROP_VIS_MAX_BIAS, LP_PROP_VIS_MAX_BIAS) : 0;
+    int R = 0;
+#pragma unroll
+    for (int k = 0; k < 16; ++k) R += v[k] != kVisNone ? abs(v[k] - mu) : 0;
+#pragma unroll
+    for (int s = 1; s < 16; s <<= 1) R += __shfl_xor(R, s, kWave);
+    const int by = blockIdx.y * (kTile / kB) + wy, bx = blockIdx.x * (kTile / kB) + wx;
+    if (row == 0 && by < gh && bx < gw)
+        flags[static_cast<int64_t>(by) * gw + bx] = (n >= LP_PROP_MIN_PIXELS && R > occlusion * n) ? 1 : 0;
+}
+
+// w of one pixel: v = 1 - flag between the block centres, the advance's weights, unrounded (0..256)
+__device__ __forceinline__ int weight_of(const int32_t* __restrict__ flags, int gh, int gw, int y, int x) {
+    const int uy = 2 * y - 7, ux = 2 * x - 7, by0 = uy >> 4, bx0 = ux >> 4, fy = uy - 16 * by0, fx = ux - 16 * bx0;
+    const int64_t r0 = static_cast<int64_t>(clampi(by0, 0, gh - 1)) * gw, r1 = static_cast<int64_t>(clampi(by0 + 1, 0, gh - 1)) * gw;
+    const int c0 = clampi(bx0, 0, gw - 1), c1 = clampi(bx0 + 1, 0, gw - 1);
+    return bil_sum(flags[r0 + c0] == 0, flags[r0 + c1] == 0, flags[r1 + c0] == 0, flags[r1 + c1] == 0, fy, fx);
+}
+
+__global__ __launch_bounds__(256) void lp_prop_occlude_kernel(const float* __restrict__ code, const int32_t* __restrict__ flags,
+                                                              float* __restrict__ out, float* __restrict__ hidden,
+                                                              uint8_t* __restrict__ mpyr, int H, int W, int levels, int gh, int gw,
+                                                              int wide) {
+    __shared__ uint8_t s0[kTile * kTile], s1[kTile * kTile / 4];
+    const int r = threadIdx.x >> 3, q = threadIdx.x & 7;                  // four pixels per lane: row r, columns 4 q .. 4 q + 3
+    const int y = blockIdx.y * kTile + r, x = blockIdx.x * kTile + 4 * q;
+    float c4[4] = {0.0f, 0.0f, 0.0f, 0.0f}, m4[4], h4[4];
+    const bool row_in = y < H && x < W;                                  // wide (as in the visible kernel): x + 3 < W too
+    const int64_t p = static_cast<int64_t>(y) * W + x;
+    if (row_in) {
+        if (wide) {
+            *reinterpret_cast<float4*>(c4) = *reinterpret_cast<const float4*>(code + p);
+        } else {
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                if (x + k < W) c4[k] = code[p + k];
+        }
+    }
+    uint8_t bits[4] = {0, 0, 0, 0};
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        m4[k] = h4[k] = 0.0f;
+        if (row_in && x + k < W) {
+            const int c = clampi(static_cast<int>(c4[k] * 256.0f), 0, 256);
+            const int cv = (c * weight_of(flags, gh, gw, y, x + k) + 128) >> 8;
+            m4[k] = static_cast<float>(cv) * (1.0f / 256.0f);               // exact, as the advance's
+            h4[k] = static_cast<float>(c - cv) * (1.0f / 256.0f);
+            bits[k] = cv >= 128 ? 1 : 0;
+        }
+    }
+    if (row_in) {
+        if (wide) {
+            *reinterpret_cast<float4*>(out + p) = *reinterpret_cast<const float4*>(m4);
+            *reinterpret_cast<float4*>(hidden + p) = *reinterpret_cast<const float4*>(h4);
+        } else {
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                if (x + k < W) { out[p + k] = m4[k]; hidden[p + k] = h4[k]; }
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) s0[r * kTile + 4 * q + k] = bits[k];
+    __syncthreads();
+    tile_mask_pyramid(s0, s1, blockIdx.y, blockIdx.x, H, W, levels, mpyr);
+}
+
 // ---- merge ---------------------------------------------------------------------------------------------------------------------------------
 // Frame f of the stack is frame j = first + f of a gap of n = span frames: out = 0.5 + ((n - j) sA + j sB) / n, clamped to 0..1.
 __global__ __launch_bounds__(256) void lp_prop_merge_kernel(const int32_t* __restrict__ qa, const int32_t* __restrict__ qb,
@@ -532,6 +674,37 @@ int prop_advance_dispatch(const lp_prop_advance_desc* dp, hipStream_t stream) {
     const lp_prop_advance_job job = {dp->vec, dp->pos_src, dp->key, dp->pos_dst, dp->out, dp->mask_pyramid};
     const lp_prop_advance_batch_desc d = {dp->height, dp->width, dp->levels, 1, &job};
     return prop_advance_batch_dispatch(&d, stream);
+}
+
+int prop_visible_dispatch(const lp_prop_visible_desc* dp, hipStream_t stream) {
+    if (!dp) return LP_E_INVALID;
+    const lp_prop_visible_desc& d = *dp;
+    if (!side_ok(d.height) || !side_ok(d.width) || d.occlusion < 1 || d.occlusion > 255) return LP_E_INVALID;
+    if (!d.pos || !d.tgt || !d.key || !d.mask || !d.flags) return LP_E_INVALID;
+    const void* out = d.flags;
+    if (out == d.pos || out == d.tgt || out == d.key || out == d.mask) return LP_E_INVALID;
+    const int gh = (d.height + kB - 1) / kB, gw = (d.width + kB - 1) / kB;
+    // wide: the kernel reads a row's four pixels as one vector
+    const int wide = d.width % 4 == 0 && aligned16(d.pos) && aligned16(d.tgt) && aligned16(d.mask);
+    hipLaunchKernelGGL(lp_prop_visible_kernel, dim3(blocks_of(d.width, kTile), blocks_of(d.height, kTile)), dim3(256), 0, stream, d.pos,
+                       d.tgt, d.key, d.mask, d.flags, d.height, d.width, gh, gw, d.occlusion, wide);
+    return launched();
+}
+
+int prop_occlude_dispatch(const lp_prop_occlude_desc* dp, hipStream_t stream) {
+    if (!dp) return LP_E_INVALID;
+    const lp_prop_occlude_desc& d = *dp;
+    if (!side_ok(d.height) || !side_ok(d.width) || !levels_ok(d.levels)) return LP_E_INVALID;
+    if (!d.code || !d.flags || !d.out || !d.hidden || !d.mask_pyramid) return LP_E_INVALID;
+    const void *in[2] = {d.code, d.flags}, *outs[3] = {d.out, d.hidden, d.mask_pyramid};
+    for (int i = 0; i < 3; ++i) {
+        if (outs[i] == in[0] || outs[i] == in[1] || outs[i] == outs[(i + 1) % 3]) return LP_E_INVALID;
+    }
+    const int gh = (d.height + kB - 1) / kB, gw = (d.width + kB - 1) / kB;
+    const int wide = d.width % 4 == 0 && aligned16(d.code) && aligned16(d.out) && aligned16(d.hidden);
+    hipLaunchKernelGGL(lp_prop_occlude_kernel, dim3(blocks_of(d.width, kTile), blocks_of(d.height, kTile)), dim3(256), 0, stream, d.code,
+                       d.flags, d.out, d.hidden, d.mask_pyramid, d.height, d.width, d.levels, gh, gw, wide);
+    return launched();
 }
 
 int prop_merge_dispatch(const lp_prop_merge_desc* dp, hipStream_t stream) {

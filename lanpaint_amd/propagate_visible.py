@@ -1,0 +1,146 @@
+"""Video mask propagate, occlusion-aware: the carried mask stays off whatever passes in front of the subject.
+
+`propagate.propagate_masks` carries one painted mask along the picture's motion; when the subject passes behind a lamp post, that
+mask lies on the post and the sampler repaints the post.  Nothing downstream repairs it: the stabilize is not motion-compensated,
+the refine only snaps edges, the Detailer crops take the mask as given.  The position map every step carries names, for each pixel
+of frame t, where it was in the key frame; the key frame's luma sampled through it shows what the subject should look like there.
+Where the picture of t looks different, something is in front.
+
+propagate_masks_visible(images, mask, key_frame=0, levels=4, search=2, smooth=8, occlusion=16) -> (mask [F, H, W], hidden [F, H, W])
+        The single-key chain with two launches behind every advance.  lp_prop_visible: per 8 x 8 block, over the mask pixels of the
+        block's 16 x 16 window, the mean absolute difference between the frame's luma and the warped key luma, after a brightness
+        bias of at most 32 grey levels is forgiven; above `occlusion` grey levels the block counts as occluded.  lp_prop_occlude:
+        the flags, interpolated between block centres, split the carried mask code c into the visible part c' (`mask`, which also
+        gives the bits that weight the next step's match) and the rest (`hidden`, the part of the subject behind something; add it
+        back to inpaint through the occluder).  Nothing is remembered between frames: the test is against the key frame every
+        time, so what was hidden is visible again as soon as it looks like the key again, and the hidden part's positions follow
+        the visible rest (blocks without bits are filled from their neighbours).  The key frame returns its binarised mask and a
+        zero `hidden`.  occlusion = 0 switches the test off: propagate_masks and zeros, no further launch.
+        Integer arithmetic throughout: a still video and a noise-free whole-pixel shift return the binarised key mask and a zero
+        `hidden`; an empty mask gives 0 and 0.  include/lanpaint_hip.h (lp_prop_visible, lp_prop_occlude) states the rule in full.
+        Not handled: a subject that is hidden entirely leaves the zero field and is lost if it reappears elsewhere; what leaves
+        the picture; several keyframes with occlusion (propagate_keys.py has none); occlusion edges finer than a block --
+        `LanPaint_MaskRefine` follows in the chain.  A lower `occlusion` hides more and starts to take sub-pixel motion and noise
+        for an occluder; profiles/r29_propagate_visible.md has the numbers behind the default.
+
+HIP tensors only, no CPU fallback, no device -> host read.  The frames' luma pyramids come in propagate's chunks, under
+propagate.WS_CAP_BYTES; the key frame's luma plane is copied once per chain, so it outlives its chunk.  A step is 2 levels + 3
+launches and allocates nothing.
+"""
+from __future__ import annotations
+
+import ctypes
+
+import torch
+
+from . import _cabi, propagate
+from ._hostcall import int_in, launch, require_hip
+from .propagate import _Step, _chain_frames, _images, _params, _plane, advance, key_mask, level_view
+
+MAX_OCCLUSION = 255
+DEFAULT_OCCLUSION = 16
+
+
+def _plane_u8(t, what, H=None, W=None):
+    require_hip(t, what, __name__)
+    if t.dtype != torch.uint8 or t.ndim != 2 or not t.is_contiguous() or (H is not None and tuple(t.shape) != (H, W)):
+        raise ValueError(f"{what} must be a contiguous uint8 [H, W]" + ("" if H is None else f" of {H}x{W}"))
+    return t
+
+
+def visible_flags(pos, tgt, key, mask_bits, occlusion=DEFAULT_OCCLUSION, out=None):
+    """One occlusion flag per level-0 block of frame t: `pos` its positions int32 [H, W, 2], `tgt` and `key` level 0 of its and of
+    the key frame's luma pyramid, `mask_bits` level 0 of the pyramid the advance wrote, all uint8 [H, W].  int32 [gh, gw], 1 where
+    the block is occluded.  One launch."""
+    int_in(occlusion, 1, MAX_OCCLUSION, "occlusion")
+    H, W = _plane_u8(tgt, "tgt").shape
+    _plane(H, W)
+    _plane_u8(key, "key", H, W)
+    _plane_u8(mask_bits, "mask_bits", H, W)
+    require_hip(pos, "pos", __name__)
+    if pos.dtype != torch.int32 or not pos.is_contiguous() or tuple(pos.shape) != (H, W, 2):
+        raise ValueError("pos must be a contiguous int32 [H, W, 2]")
+    out = torch.empty(_cabi.prop_grid(H, W), dtype=torch.int32, device=tgt.device) if out is None else out
+    d = _cabi.LpPropVisibleDesc(H, W, occlusion, 0, pos.data_ptr(), tgt.data_ptr(), key.data_ptr(), mask_bits.data_ptr(), out.data_ptr())
+    launch("lp_prop_visible", tgt.device, ctypes.byref(d))
+    return out
+
+
+def occlude(code, flags, levels, out=None, hidden=None, mpyr_out=None):
+    """The advance's mask `code` fp32 [H, W] (c / 256) split by the blocks' `flags` int32 [gh, gw]: (the visible part, the hidden
+    part, both fp32 [H, W], and the pyramid of the visible part's bits uint8 [1, stride]).  One launch."""
+    int_in(levels, 1, propagate.MAX_LEVELS, "levels")
+    require_hip(code, "code", __name__)
+    require_hip(flags, "flags", __name__)
+    if code.dtype != torch.float32 or code.ndim != 2 or not code.is_contiguous():
+        raise ValueError("code must be a contiguous fp32 [H, W]")
+    H, W = code.shape
+    _plane(H, W)
+    if flags.dtype != torch.int32 or not flags.is_contiguous() or tuple(flags.shape) != _cabi.prop_grid(H, W):
+        raise ValueError("flags must be level 0's contiguous int32 [gh, gw]")
+    dev = code.device
+    out = torch.empty((H, W), dtype=torch.float32, device=dev) if out is None else out
+    hidden = torch.empty((H, W), dtype=torch.float32, device=dev) if hidden is None else hidden
+    if mpyr_out is None:
+        mpyr_out = torch.empty((1, _cabi.prop_pyramid_ws_bytes(1, H, W, levels)), dtype=torch.uint8, device=dev)
+    d = _cabi.LpPropOccludeDesc(H, W, levels, 0, code.data_ptr(), flags.data_ptr(), out.data_ptr(), hidden.data_ptr(),
+                                mpyr_out.data_ptr())
+    launch("lp_prop_occlude", dev, ctypes.byref(d))
+    return out, hidden, mpyr_out
+
+
+class _VisibleStep(_Step):
+    """propagate's step buffers and the three this form adds: the advance's code and pyramid, now scratch, and the flags."""
+
+    def __init__(self, H, W, levels, search, smooth, occlusion, dev):
+        super().__init__(H, W, levels, search, smooth, dev)
+        self.occlusion = occlusion
+        self.code = torch.empty((H, W), dtype=torch.float32, device=dev)
+        self.raw_mpyr = torch.empty_like(self.mpyr[0])
+        self.flags = torch.empty(_cabi.prop_grid(H, W), dtype=torch.int32, device=dev)
+
+    def chain(self, frames, key_pyr, out, hidden):
+        """`frames`: (index into out, that frame's luma pyramid) from the key outwards, the key first; writes out[t] and hidden[t]
+        behind it."""
+        H, W = self.H, self.W
+        pos, mpyr, src, k, key_luma = None, key_pyr, None, 0, None
+        key_bits = level_view(key_pyr, H, W, 0)[0]
+        for t, pyr in frames:
+            luma = level_view(pyr[None], H, W, 0)[0]
+            if src is None:
+                key_luma = luma.clone()                               # its own copy: the key's chunk may go
+            else:
+                vec = self.field_of(src, pyr, mpyr)
+                pos, _, _ = advance(vec, pos, key_bits, self.levels, self.pos[k], self.code, self.raw_mpyr)
+                visible_flags(pos, luma, key_luma, level_view(self.raw_mpyr, H, W, 0)[0], self.occlusion, self.flags)
+                _, _, mpyr = occlude(self.code, self.flags, self.levels, out[t], hidden[t], self.mpyr[k])
+                k ^= 1
+            src = pyr
+
+
+def propagate_masks_visible(images, mask, key_frame=0, levels=4, search=2, smooth=8, occlusion=DEFAULT_OCCLUSION):
+    """`mask`, painted on frame `key_frame` of `images` [F, H, W, C], followed through every frame and kept off what passes in
+    front of it (module docstring): (mask, hidden), fp32 [F, H, W] each, on the images' device.  No device -> host read."""
+    _params(levels, search, smooth)
+    int_in(occlusion, 0, MAX_OCCLUSION, "occlusion")
+    _images(images)
+    require_hip(mask, "mask", __name__)
+    F, H, W, _ = images.shape
+    int_in(key_frame, 0, F - 1, "key_frame")
+    if occlusion == 0:
+        return propagate.propagate_masks(images, mask, key_frame, levels, search, smooth), images.new_zeros((F, H, W), dtype=torch.float32)
+    if mask.ndim == 2:
+        mask = mask.unsqueeze(0)
+    if mask.ndim != 3 or mask.shape[0] not in (1, F) or tuple(mask.shape[1:]) != (H, W):
+        raise ValueError(f"mask {tuple(mask.shape)} does not match {F} frames of {H}x{W}: [H, W], [1, H, W] or [F, H, W]")
+    dev = images.device
+    key_pyr, key_out = key_mask(mask[key_frame if mask.shape[0] == F else 0].to(dev), levels)
+    out = torch.empty((F, H, W), dtype=torch.float32, device=dev)
+    hidden = torch.empty((F, H, W), dtype=torch.float32, device=dev)
+    out[key_frame] = key_out
+    hidden[key_frame].zero_()
+    step = _VisibleStep(H, W, levels, search, smooth, occlusion, dev)
+    for order in (list(range(key_frame, F)), list(range(key_frame, -1, -1))):
+        if len(order) > 1:
+            step.chain(_chain_frames(images, order, levels), key_pyr, out, hidden)
+    return out, hidden
