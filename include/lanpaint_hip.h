@@ -1678,7 +1678,8 @@ LP_API int lp_prop_merge(const lp_prop_merge_desc* desc, void* stream);
  * Launches (csrc/propagate_kernel.hip): lp_prop_visible, a block of 256 lanes per 32 x 32 pixels: d of the tile and its halo of 4
  * goes to LDS once as int16 (a pixel outside the image or the mask holds a marker), four pixels per lane with P_t read as two
  * 16-byte vectors when width % 4 == 0; then 16 lanes per window, a row each, D and n and then R summed across them in registers.
- * lp_prop_occlude: a block per 32 x 32 tile, one lane per four pixels, ending in the pyramid's tile code.  One job each.
+ * lp_prop_occlude: a block per 32 x 32 tile, one lane per four pixels, ending in the pyramid's tile code.  One job each
+ * (one-job batches of the next section's kernels).
  * LP_E_INVALID: a null pointer, a side or levels outside its range, occlusion outside 1..255, flags aliasing an input of
  * lp_prop_visible; out, hidden or mask_pyramid aliasing code or flags or one another in lp_prop_occlude (the advance's pyramid is
  * no input there: c carries its bits, so mask_pyramid may not be the buffer lp_prop_visible still reads, which the caller orders).
@@ -1704,6 +1705,95 @@ typedef struct lp_prop_occlude_desc {
     uint8_t*       mask_pyramid;                  /* out, the pyramid of the bits c' >= 128                                 */
 } lp_prop_occlude_desc;
 LP_API int lp_prop_occlude(const lp_prop_occlude_desc* desc, void* stream);
+
+/* ---- Video mask propagate from several keyframes, occlusion-aware (beyond the reference) ---------------------------------------------
+ * The several-keys section has no occlusion handling and the occlusion-aware section has one key: a subject that is hidden entirely
+ * is lost there.  The remedy is a second key painted behind the occluder.  This section joins the two, and adds the rule the join
+ * needs: between two keys, the chain that went through a full occlusion is stale, and a merge weighted by time alone would drag the
+ * good chain towards it.  A chain that is lost gives way to the other.
+ * 1 chains   the plan of the several-keys section, unchanged.  Every chain is the occlusion-aware chain of the section above started
+ *            from its own key: match / fill per level -> advance -> visible (Yk is that chain's key frame's luma) -> occlude.  For
+ *            chain X at frame t this gives the advance's code c_X, the visible code c'_X and the flags f_X [gh, gw] on frame t's block
+ *            grid.  The subject code is c_X; hidden_X = (c_X - c'_X) / 256.
+ * 2 lost     N_X(u) is the number of pixels with c'_X >= 128 at frame u; at the key itself, the number of key bits.  Chain X is lost
+ *            at t if N_X(key) >= LP_PROP_MIN_PIXELS and N_X(u) < LP_PROP_MIN_PIXELS for some frame u from its first step up to t
+ *            inclusive: below 16 visible bits no level-0 block of the next match can be valid.  A chain from a key with fewer than
+ *            16 bits is never lost: an empty key keeps its "nothing here" meaning.  Lost is sticky along the chain; the chain still
+ *            runs on.
+ * 3 output   a key frame gets its binarised painted mask and hidden = 0.  A frame outside [k_0, k_{K-1}] gets its one chain's
+ *            (c' / 256, (c - c') / 256), lost or not.  A frame t strictly inside a gap (a, b), n = b - a, j = t - a, with A the forward
+ *            and B the backward chain (lp_prop_merge_visible):
+ *              exactly one of A, B lost at t: the other chain's mask and hidden, bit for bit.
+ *              otherwise (none or both lost): S = the lp_prop_merge value of qA and qB, the signed squared distances of c_A >= 128
+ *              and of c_B >= 128 (the subject codes, not the visible parts), the arithmetic exactly lp_prop_merge's;
+ *              c_S = (int)(S * 256.0f + 0.5f), product and sum rounded on their own, in 0..256; f = f_A if 2 j <= n, else f_B (the
+ *              nearer key's verdict); w = f interpolated exactly as lp_prop_occlude does; c'_S = (c_S * w + 128) >> 8;
+ *              mask = c'_S / 256 and hidden = (c_S - c'_S) / 256.
+ * What follows from the rule, bit for bit: K = 1 is the occlusion-aware single-key form; occlusion = 0 is the caller's "off" (the
+ * several-keys form and a zero hidden, none of this section's launches); a still video with the same mask on every key returns
+ * the binarised mask and a zero hidden on every frame; empty keys everywhere give 0 and 0; mask + hidden is a multiple of 1 / 256
+ * everywhere; on every key the output is the painting.
+ * lp_prop_visible_batch and lp_prop_occlude_batch run up to LP_PROP_MAX_JOBS independent chain steps in one launch, the job on
+ * blockIdx.z, the job table read from host memory and passed by value, every job with the meaning and the bits of the single entry
+ * (the single entries are one-job batches of the same kernels; a job takes the 16-byte paths when its own planes allow).  A step of
+ * this form is 2 L + 3 launches per 32 active chains.  An occlude job with a count adds the number of its pixels with c' >= 128
+ * to *count (int32, zeroed by the caller): one integer atomic add per wave, so any order gives the same bits.  count null: none.
+ * lp_prop_merge_visible: one launch per gap, or per chunk of its frames through `first`; a streaming kernel, four pixels per lane
+ * in 16-byte accesses when width % 4 == 0 and the planes are 16-byte aligned, one pixel per lane otherwise, the same bits.  The
+ * two lost bits of a frame are derived on the device from the chains' counts, which are indexed by the chain's step (index 0 the
+ * key's count, count_a[j] frame a + j, count_b[s] frame b - s), span entries each, whatever `first` is: nothing is read back.
+ * out may be mask_a and hidden may be code_a (in place on the forward chain's planes; a lane reads its pixels before it writes).
+ * LP_E_INVALID: jobs outside 1..LP_PROP_MAX_JOBS; per job every check of the single entries; a count that aliases another pointer
+ * of its job.  lp_prop_merge_visible: a null pointer, a side outside 1..LP_VMASK_MAX_SIDE, span < 2, first < 1, frames < 1,
+ * first + frames - 1 > span - 1, out == hidden, out or hidden aliasing an input other than the in-place pair; LP_E_UNSUPPORTED:
+ * span > 65535.  All checked before any HIP call.                                                                                 */
+typedef struct lp_prop_visible_job {
+    const int32_t* pos;                           /* as in lp_prop_visible_desc                                             */
+    const uint8_t* tgt;
+    const uint8_t* key;
+    const uint8_t* mask;
+    int32_t*       flags;
+} lp_prop_visible_job;
+
+typedef struct lp_prop_visible_batch_desc {
+    int32_t height, width, occlusion, jobs;       /* occlusion 1..255, jobs 1..LP_PROP_MAX_JOBS                             */
+    const lp_prop_visible_job* job;               /* host memory, `jobs` entries                                            */
+} lp_prop_visible_batch_desc;
+LP_API int lp_prop_visible_batch(const lp_prop_visible_batch_desc* desc, void* stream);
+
+typedef struct lp_prop_occlude_job {
+    const float*   code;                          /* as in lp_prop_occlude_desc                                             */
+    const int32_t* flags;
+    float*         out;
+    float*         hidden;
+    uint8_t*       mask_pyramid;
+    int32_t*       count;                         /* += the number of pixels with c' >= 128; null: not counted              */
+} lp_prop_occlude_job;
+
+typedef struct lp_prop_occlude_batch_desc {
+    int32_t height, width, levels, jobs;
+    const lp_prop_occlude_job* job;               /* host memory, `jobs` entries                                            */
+} lp_prop_occlude_batch_desc;
+LP_API int lp_prop_occlude_batch(const lp_prop_occlude_batch_desc* desc, void* stream);
+
+/* The in-between frames of one gap: frame f of the stacks is frame j = first + f of the gap, 1 <= j <= span - 1.  One launch. */
+typedef struct lp_prop_merge_visible_desc {
+    int32_t frames, height, width, span;          /* span = n, the distance between the two keys                            */
+    int32_t first, reserved0;
+    const int32_t* qa;                            /* [frames, height, width] signed squared distances of c_A >= 128         */
+    const int32_t* qb;                            /* the same of c_B >= 128                                                 */
+    const float*   code_a;                        /* [frames, height, width] c_A / 256: the forward chain's advance         */
+    const float*   mask_a;                        /* c'_A / 256: its occlude's out                                          */
+    const float*   code_b;                        /* the same two of the backward chain                                     */
+    const float*   mask_b;
+    const int32_t* flags_a;                       /* [frames, gh, gw] f_A                                                   */
+    const int32_t* flags_b;                       /* f_B                                                                    */
+    const int32_t* count_a;                       /* [span] N_A by step: [0] the key's bits, [j] frame a + j                */
+    const int32_t* count_b;                       /* [span] N_B by step: [0] the key's bits, [s] frame b - s                */
+    float*         out;                           /* [frames, height, width] mask                                           */
+    float*         hidden;                        /* [frames, height, width]                                                */
+} lp_prop_merge_visible_desc;
+LP_API int lp_prop_merge_visible(const lp_prop_merge_visible_desc* desc, void* stream);
 
 #ifdef __cplusplus
 }

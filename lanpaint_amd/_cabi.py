@@ -440,6 +440,31 @@ class LpPropOccludeDesc(C.Structure):
                 ("mask_pyramid", C.c_void_p)]
 
 
+class LpPropVisibleJob(C.Structure):
+    _fields_ = [("pos", C.c_void_p), ("tgt", C.c_void_p), ("key", C.c_void_p), ("mask", C.c_void_p), ("flags", C.c_void_p)]
+
+
+class LpPropVisibleBatchDesc(C.Structure):
+    _fields_ = [("height", C.c_int32), ("width", C.c_int32), ("occlusion", C.c_int32), ("jobs", C.c_int32), ("job", C.c_void_p)]
+
+
+class LpPropOccludeJob(C.Structure):
+    _fields_ = [("code", C.c_void_p), ("flags", C.c_void_p), ("out", C.c_void_p), ("hidden", C.c_void_p),
+                ("mask_pyramid", C.c_void_p), ("count", C.c_void_p)]
+
+
+class LpPropOccludeBatchDesc(C.Structure):
+    _fields_ = [("height", C.c_int32), ("width", C.c_int32), ("levels", C.c_int32), ("jobs", C.c_int32), ("job", C.c_void_p)]
+
+
+class LpPropMergeVisibleDesc(C.Structure):
+    _fields_ = [("frames", C.c_int32), ("height", C.c_int32), ("width", C.c_int32), ("span", C.c_int32),
+                ("first", C.c_int32), ("reserved0", C.c_int32), ("qa", C.c_void_p), ("qb", C.c_void_p),
+                ("code_a", C.c_void_p), ("mask_a", C.c_void_p), ("code_b", C.c_void_p), ("mask_b", C.c_void_p),
+                ("flags_a", C.c_void_p), ("flags_b", C.c_void_p), ("count_a", C.c_void_p), ("count_b", C.c_void_p),
+                ("out", C.c_void_p), ("hidden", C.c_void_p)]
+
+
 def prop_level_shape(height, width, level):
     """Level `level` of a height x width plane: ceil(height / 2^level) x ceil(width / 2^level)."""
     return (int(height) + (1 << level) - 1) >> level, (int(width) + (1 << level) - 1) >> level
@@ -562,6 +587,9 @@ EXPORTS = {
     "lp_prop_merge": (C.c_int, [C.POINTER(LpPropMergeDesc), C.c_void_p]),
     "lp_prop_visible": (C.c_int, [C.POINTER(LpPropVisibleDesc), C.c_void_p]),
     "lp_prop_occlude": (C.c_int, [C.POINTER(LpPropOccludeDesc), C.c_void_p]),
+    "lp_prop_visible_batch": (C.c_int, [C.POINTER(LpPropVisibleBatchDesc), C.c_void_p]),
+    "lp_prop_occlude_batch": (C.c_int, [C.POINTER(LpPropOccludeBatchDesc), C.c_void_p]),
+    "lp_prop_merge_visible": (C.c_int, [C.POINTER(LpPropMergeVisibleDesc), C.c_void_p]),
 }
 
 

@@ -77,6 +77,9 @@ int prop_advance_batch_dispatch(const lp_prop_advance_batch_desc* d, hipStream_t
 int prop_merge_dispatch(const lp_prop_merge_desc* d, hipStream_t stream);
 int prop_visible_dispatch(const lp_prop_visible_desc* d, hipStream_t stream);
 int prop_occlude_dispatch(const lp_prop_occlude_desc* d, hipStream_t stream);
+int prop_visible_batch_dispatch(const lp_prop_visible_batch_desc* d, hipStream_t stream);
+int prop_occlude_batch_dispatch(const lp_prop_occlude_batch_desc* d, hipStream_t stream);
+int prop_merge_visible_dispatch(const lp_prop_merge_visible_desc* d, hipStream_t stream);
 int reshape_mask_dispatch(const float* src, int sb, int sc, int sf, int sh, int sw, float* dst, int db, int dc, int df,
                           int dh, int dw, int taps, int flags, hipStream_t stream);
 }  // namespace lp
@@ -266,6 +269,18 @@ int lp_prop_merge(const lp_prop_merge_desc* desc, void* stream) { return lp::pro
 int lp_prop_visible(const lp_prop_visible_desc* desc, void* stream) { return lp::prop_visible_dispatch(desc, as_stream(stream)); }
 
 int lp_prop_occlude(const lp_prop_occlude_desc* desc, void* stream) { return lp::prop_occlude_dispatch(desc, as_stream(stream)); }
+
+int lp_prop_visible_batch(const lp_prop_visible_batch_desc* desc, void* stream) {
+    return lp::prop_visible_batch_dispatch(desc, as_stream(stream));
+}
+
+int lp_prop_occlude_batch(const lp_prop_occlude_batch_desc* desc, void* stream) {
+    return lp::prop_occlude_batch_dispatch(desc, as_stream(stream));
+}
+
+int lp_prop_merge_visible(const lp_prop_merge_visible_desc* desc, void* stream) {
+    return lp::prop_merge_visible_dispatch(desc, as_stream(stream));
+}
 
 int lp_finalize(const lp_final_desc* desc, void* stream) { return lp::finalize_dispatch(desc, as_stream(stream)); }
 

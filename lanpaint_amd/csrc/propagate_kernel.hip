@@ -24,10 +24,17 @@
 //                mask, four pixels per lane, P_t read as two 16-byte vectors; then 16 lanes per window of the tile's 4 x 4 blocks,
 //                a row each (two ds_read_b128 on an 80-byte pitch), D and n and then R summed across them with shuffles.
 //   occlude      a block per 32 x 32 tile, four pixels per lane: the flags interpolated as advance interpolates the field, the
-//                visible and the hidden part of the advance's code, and the visible bits' pyramid from the same tile code.
+//                visible and the hidden part of the advance's code, and the visible bits' pyramid from the same tile code.  With a
+//                count pointer, the number of visible bits goes into it: a sum per wave, one integer atomic add per wave.
+//                visible and occlude are batches like match, fill and advance; a job's vector path is a bit of a mask.
 //   merge        one lane per pixel and frame of a gap between two keys: the two chains' signed squared distances, their capped
 //                fp64 roots, the weighted mean in a fixed order, the ramp of half-width 1/2 around the zero crossing.
-// No scratch, no atomics, no floating point beyond the luma codes, the final c / 256 (read back by occlude) and the merge.
+//   merge_visible the merge of a gap whose chains are occlusion-aware: a streaming kernel over [frames, H, W], four pixels per lane
+//                as 16-byte vectors when the width allows.  Per frame the two chains' lost bits come from their visible-bit
+//                counts (a uniform loop over scalar loads).  Exactly one lost: the other chain's planes pass through.  Else the
+//                merge of the subject codes' distances, rounded to a code and split by the nearer key's flags as occlude does.
+// No scratch, no floating point beyond the luma codes, the final c / 256 (read back by occlude) and the merges.  The only atomics
+// are occlude's integer adds into a count: any order gives the same bits.
 #include "lp_common.h"
 
 #include <math.h>
@@ -422,10 +429,28 @@ __device__ __forceinline__ int16_t residual_of(const uint8_t* __restrict__ key, 
     return static_cast<int16_t>(yt - K);
 }
 
-__global__ __launch_bounds__(256) void lp_prop_visible_kernel(const int32_t* __restrict__ pos, const uint8_t* __restrict__ tgt,
-                                                              const uint8_t* __restrict__ key, const uint8_t* __restrict__ msk,
-                                                              int32_t* __restrict__ flags, int H, int W, int gh, int gw, int occlusion,
-                                                              int wide) {
+struct visible_job {
+    const int32_t* pos;
+    const uint8_t* tgt;
+    const uint8_t* key;
+    const uint8_t* msk;
+    int32_t*       flags;
+};
+
+struct visible_args {
+    int32_t  H, W, gh, gw, occlusion;
+    uint32_t wide;                                                   // bit i: job i takes the vector path
+    visible_job job[LP_PROP_MAX_JOBS];
+};
+
+__global__ __launch_bounds__(256) void lp_prop_visible_kernel(const visible_args a) {
+    const int32_t* __restrict__ pos = a.job[blockIdx.z].pos;
+    const uint8_t* __restrict__ tgt = a.job[blockIdx.z].tgt;
+    const uint8_t* __restrict__ key = a.job[blockIdx.z].key;
+    const uint8_t* __restrict__ msk = a.job[blockIdx.z].msk;
+    int32_t* __restrict__ flags = a.job[blockIdx.z].flags;
+    const int H = a.H, W = a.W, gh = a.gh, gw = a.gw, occlusion = a.occlusion;
+    const int wide = static_cast<int>((a.wide >> blockIdx.z) & 1u);
     __shared__ __attribute__((aligned(16))) int16_t s_d[kVisSide * kVisSide];      // 3200 bytes; a row is 80 bytes = 5 x 16
     const int y00 = blockIdx.y * kTile - kHalo, x00 = blockIdx.x * kTile - kHalo;     // x00 is a multiple of 4
     // wide: width % 4 == 0 and the planes 16-byte aligned, so a quad is inside its row or outside it, and one vector
@@ -496,10 +521,30 @@ __device__ __forceinline__ int weight_of(const int32_t* __restrict__ flags, int 
     return bil_sum(flags[r0 + c0] == 0, flags[r0 + c1] == 0, flags[r1 + c0] == 0, flags[r1 + c1] == 0, fy, fx);
 }
 
-__global__ __launch_bounds__(256) void lp_prop_occlude_kernel(const float* __restrict__ code, const int32_t* __restrict__ flags,
-                                                              float* __restrict__ out, float* __restrict__ hidden,
-                                                              uint8_t* __restrict__ mpyr, int H, int W, int levels, int gh, int gw,
-                                                              int wide) {
+struct occlude_job {
+    const float*   code;
+    const int32_t* flags;
+    float*         out;
+    float*         hidden;
+    uint8_t*       mpyr;
+    int32_t*       count;        // or null
+};
+
+struct occlude_args {
+    int32_t  H, W, levels, gh, gw;
+    uint32_t wide;
+    occlude_job job[LP_PROP_MAX_JOBS];
+};
+
+__global__ __launch_bounds__(256) void lp_prop_occlude_kernel(const occlude_args a) {
+    const float* __restrict__ code = a.job[blockIdx.z].code;
+    const int32_t* __restrict__ flags = a.job[blockIdx.z].flags;
+    float* __restrict__ out = a.job[blockIdx.z].out;
+    float* __restrict__ hidden = a.job[blockIdx.z].hidden;
+    uint8_t* __restrict__ mpyr = a.job[blockIdx.z].mpyr;
+    int32_t* count = a.job[blockIdx.z].count;
+    const int H = a.H, W = a.W, levels = a.levels, gh = a.gh, gw = a.gw;
+    const int wide = static_cast<int>((a.wide >> blockIdx.z) & 1u);
     __shared__ uint8_t s0[kTile * kTile], s1[kTile * kTile / 4];
     const int r = threadIdx.x >> 3, q = threadIdx.x & 7;                  // four pixels per lane: row r, columns 4 q .. 4 q + 3
     const int y = blockIdx.y * kTile + r, x = blockIdx.x * kTile + 4 * q;
@@ -539,22 +584,114 @@ __global__ __launch_bounds__(256) void lp_prop_occlude_kernel(const float* __res
     }
 #pragma unroll
     for (int k = 0; k < 4; ++k) s0[r * kTile + 4 * q + k] = bits[k];
+    if (count) {                                                         // the job's: the whole block takes the branch
+        int n = bits[0] + bits[1] + bits[2] + bits[3];
+#pragma unroll
+        for (int d = 1; d < kWave; d <<= 1) n += __shfl_xor(n, d, kWave);
+        if ((threadIdx.x & (kWave - 1)) == 0 && n != 0) atomicAdd(count, n);
+    }
     __syncthreads();
     tile_mask_pyramid(s0, s1, blockIdx.y, blockIdx.x, H, W, levels, mpyr);
 }
 
 // ---- merge ---------------------------------------------------------------------------------------------------------------------------------
 // Frame f of the stack is frame j = first + f of a gap of n = span frames: out = 0.5 + ((n - j) sA + j sB) / n, clamped to 0..1.
+__device__ __forceinline__ float merge_value(int32_t qa, int32_t qb, int span, int j) {
+    const double sa = capped_distance(qa), sb = capped_distance(qb);
+    const double acc = __dadd_rn(__dmul_rn(static_cast<double>(span - j), sa), __dmul_rn(static_cast<double>(j), sb));
+    const double sd = __ddiv_rn(acc, static_cast<double>(span));
+    return static_cast<float>(fmin(fmax(__dadd_rn(0.5, sd), 0.0), 1.0));
+}
+
 __global__ __launch_bounds__(256) void lp_prop_merge_kernel(const int32_t* __restrict__ qa, const int32_t* __restrict__ qb,
                                                             float* __restrict__ out, int64_t plane, int span, int first) {
     const int64_t p = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
     if (p >= plane) return;
     const int64_t i = static_cast<int64_t>(blockIdx.y) * plane + p;
-    const int j = first + static_cast<int>(blockIdx.y);
-    const double sa = capped_distance(qa[i]), sb = capped_distance(qb[i]);
-    const double acc = __dadd_rn(__dmul_rn(static_cast<double>(span - j), sa), __dmul_rn(static_cast<double>(j), sb));
-    const double sd = __ddiv_rn(acc, static_cast<double>(span));
-    out[i] = static_cast<float>(fmin(fmax(__dadd_rn(0.5, sd), 0.0), 1.0));
+    out[i] = merge_value(qa[i], qb[i], span, first + static_cast<int>(blockIdx.y));
+}
+
+// ---- merge of occlusion-aware chains ---------------------------------------------------------------------------------------------------------
+// out may be mask_a and hidden may be code_a (the caller's in-place form): a lane reads its pixels before it writes them, and no
+// other lane touches them, so these four carry no __restrict__.
+struct merge_visible_args {
+    const int32_t* qa;
+    const int32_t* qb;
+    const float*   code_a;
+    const float*   mask_a;
+    const float*   code_b;
+    const float*   mask_b;
+    const int32_t* flags_a;
+    const int32_t* flags_b;
+    const int32_t* count_a;
+    const int32_t* count_b;
+    float*         out;
+    float*         hidden;
+    int64_t plane;
+    int32_t W, gh, gw, span, first;
+};
+
+// a chain is lost at its step s: its key has at least LP_PROP_MIN_PIXELS bits and some step 1..s has fewer visible bits
+__device__ __forceinline__ bool lost_at(const int32_t* __restrict__ count, int s) {
+    if (count[0] < LP_PROP_MIN_PIXELS) return false;
+    bool lost = false;
+#pragma unroll 1
+    for (int u = 1; u <= s; ++u) lost |= count[u] < LP_PROP_MIN_PIXELS;
+    return lost;
+}
+
+template <int V>                                                         // pixels per lane: 4 (16-byte accesses) or 1
+__global__ __launch_bounds__(256) void lp_prop_merge_visible_kernel(const merge_visible_args a) {
+    const int64_t p = (static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x) * V;
+    if (p >= a.plane) return;                                            // V == 4: the plane is a multiple of 4
+    const int f = static_cast<int>(blockIdx.y), j = a.first + f;
+    const bool lost_a = lost_at(a.count_a, j), lost_b = lost_at(a.count_b, a.span - j);       // the same in every lane
+    const int64_t i = static_cast<int64_t>(f) * a.plane + p;
+    float m[V], h[V];
+    if (lost_a != lost_b) {                                              // the chain that is not lost, bit for bit
+        const float* code = lost_a ? a.code_b : a.code_a;
+        const float* mask = lost_a ? a.mask_b : a.mask_a;
+        float c[V];
+        if constexpr (V == 4) {
+            *reinterpret_cast<float4*>(c) = *reinterpret_cast<const float4*>(code + i);
+            *reinterpret_cast<float4*>(m) = *reinterpret_cast<const float4*>(mask + i);
+        } else {
+            c[0] = code[i];
+            m[0] = mask[i];
+        }
+#pragma unroll
+        for (int k = 0; k < V; ++k) {
+            const int cc = clampi(static_cast<int>(c[k] * 256.0f), 0, 256), cv = clampi(static_cast<int>(m[k] * 256.0f), 0, 256);
+            m[k] = static_cast<float>(cv) * (1.0f / 256.0f);
+            h[k] = static_cast<float>(cc - cv) * (1.0f / 256.0f);
+        }
+    } else {
+        int32_t qa[V], qb[V];
+        if constexpr (V == 4) {
+            *reinterpret_cast<int4*>(qa) = *reinterpret_cast<const int4*>(a.qa + i);
+            *reinterpret_cast<int4*>(qb) = *reinterpret_cast<const int4*>(a.qb + i);
+        } else {
+            qa[0] = a.qa[i];
+            qb[0] = a.qb[i];
+        }
+        const int32_t* __restrict__ flags = (2 * j <= a.span ? a.flags_a : a.flags_b) + static_cast<int64_t>(f) * a.gh * a.gw;
+        const int y = static_cast<int>(p / a.W), x = static_cast<int>(p - static_cast<int64_t>(y) * a.W);   // V == 4: one row
+#pragma unroll
+        for (int k = 0; k < V; ++k) {
+            const float s = merge_value(qa[k], qb[k], a.span, j);
+            const int cs = static_cast<int>(__fadd_rn(__fmul_rn(s, 256.0f), 0.5f));
+            const int cv = (cs * weight_of(flags, a.gh, a.gw, y, x + k) + 128) >> 8;
+            m[k] = static_cast<float>(cv) * (1.0f / 256.0f);
+            h[k] = static_cast<float>(cs - cv) * (1.0f / 256.0f);
+        }
+    }
+    if constexpr (V == 4) {
+        *reinterpret_cast<float4*>(a.out + i) = *reinterpret_cast<const float4*>(m);
+        *reinterpret_cast<float4*>(a.hidden + i) = *reinterpret_cast<const float4*>(h);
+    } else {
+        a.out[i] = m[0];
+        a.hidden[i] = h[0];
+    }
 }
 
 bool side_ok(int s) { return s > 0 && s <= LP_VMASK_MAX_SIDE; }
@@ -676,35 +813,69 @@ int prop_advance_dispatch(const lp_prop_advance_desc* dp, hipStream_t stream) {
     return prop_advance_batch_dispatch(&d, stream);
 }
 
+int prop_visible_batch_dispatch(const lp_prop_visible_batch_desc* dp, hipStream_t stream) {
+    if (!dp) return LP_E_INVALID;
+    const lp_prop_visible_batch_desc& d = *dp;
+    if (!side_ok(d.height) || !side_ok(d.width) || d.occlusion < 1 || d.occlusion > 255) return LP_E_INVALID;
+    if (!jobs_ok(d.jobs) || !d.job) return LP_E_INVALID;
+    visible_args a = {};
+    for (int i = 0; i < d.jobs; ++i) {
+        const lp_prop_visible_job& j = d.job[i];
+        if (!j.pos || !j.tgt || !j.key || !j.mask || !j.flags) return LP_E_INVALID;
+        const void* out = j.flags;
+        if (out == j.pos || out == j.tgt || out == j.key || out == j.mask) return LP_E_INVALID;
+        a.job[i] = {j.pos, j.tgt, j.key, j.mask, j.flags};
+        // wide: the kernel reads a row's four pixels as one vector
+        if (d.width % 4 == 0 && aligned16(j.pos) && aligned16(j.tgt) && aligned16(j.mask)) a.wide |= 1u << i;
+    }
+    a.H = d.height;
+    a.W = d.width;
+    a.gh = (d.height + kB - 1) / kB;
+    a.gw = (d.width + kB - 1) / kB;
+    a.occlusion = d.occlusion;
+    hipLaunchKernelGGL(lp_prop_visible_kernel, dim3(blocks_of(d.width, kTile), blocks_of(d.height, kTile), d.jobs), dim3(256), 0, stream, a);
+    return launched();
+}
+
 int prop_visible_dispatch(const lp_prop_visible_desc* dp, hipStream_t stream) {
     if (!dp) return LP_E_INVALID;
-    const lp_prop_visible_desc& d = *dp;
-    if (!side_ok(d.height) || !side_ok(d.width) || d.occlusion < 1 || d.occlusion > 255) return LP_E_INVALID;
-    if (!d.pos || !d.tgt || !d.key || !d.mask || !d.flags) return LP_E_INVALID;
-    const void* out = d.flags;
-    if (out == d.pos || out == d.tgt || out == d.key || out == d.mask) return LP_E_INVALID;
-    const int gh = (d.height + kB - 1) / kB, gw = (d.width + kB - 1) / kB;
-    // wide: the kernel reads a row's four pixels as one vector
-    const int wide = d.width % 4 == 0 && aligned16(d.pos) && aligned16(d.tgt) && aligned16(d.mask);
-    hipLaunchKernelGGL(lp_prop_visible_kernel, dim3(blocks_of(d.width, kTile), blocks_of(d.height, kTile)), dim3(256), 0, stream, d.pos,
-                       d.tgt, d.key, d.mask, d.flags, d.height, d.width, gh, gw, d.occlusion, wide);
+    const lp_prop_visible_job job = {dp->pos, dp->tgt, dp->key, dp->mask, dp->flags};
+    const lp_prop_visible_batch_desc d = {dp->height, dp->width, dp->occlusion, 1, &job};
+    return prop_visible_batch_dispatch(&d, stream);
+}
+
+int prop_occlude_batch_dispatch(const lp_prop_occlude_batch_desc* dp, hipStream_t stream) {
+    if (!dp) return LP_E_INVALID;
+    const lp_prop_occlude_batch_desc& d = *dp;
+    if (!side_ok(d.height) || !side_ok(d.width) || !levels_ok(d.levels) || !jobs_ok(d.jobs) || !d.job) return LP_E_INVALID;
+    occlude_args a = {};
+    for (int i = 0; i < d.jobs; ++i) {
+        const lp_prop_occlude_job& j = d.job[i];
+        if (!j.code || !j.flags || !j.out || !j.hidden || !j.mask_pyramid) return LP_E_INVALID;
+        const void *in[2] = {j.code, j.flags}, *outs[4] = {j.out, j.hidden, j.mask_pyramid, j.count};
+        for (int k = 0; k < 4; ++k) {                                    // count may be null; given, it aliases nothing
+            if (!outs[k]) continue;
+            if (outs[k] == in[0] || outs[k] == in[1]) return LP_E_INVALID;
+            for (int m = k + 1; m < 4; ++m)
+                if (outs[k] == outs[m]) return LP_E_INVALID;
+        }
+        a.job[i] = {j.code, j.flags, j.out, j.hidden, j.mask_pyramid, j.count};
+        if (d.width % 4 == 0 && aligned16(j.code) && aligned16(j.out) && aligned16(j.hidden)) a.wide |= 1u << i;
+    }
+    a.H = d.height;
+    a.W = d.width;
+    a.levels = d.levels;
+    a.gh = (d.height + kB - 1) / kB;
+    a.gw = (d.width + kB - 1) / kB;
+    hipLaunchKernelGGL(lp_prop_occlude_kernel, dim3(blocks_of(d.width, kTile), blocks_of(d.height, kTile), d.jobs), dim3(256), 0, stream, a);
     return launched();
 }
 
 int prop_occlude_dispatch(const lp_prop_occlude_desc* dp, hipStream_t stream) {
     if (!dp) return LP_E_INVALID;
-    const lp_prop_occlude_desc& d = *dp;
-    if (!side_ok(d.height) || !side_ok(d.width) || !levels_ok(d.levels)) return LP_E_INVALID;
-    if (!d.code || !d.flags || !d.out || !d.hidden || !d.mask_pyramid) return LP_E_INVALID;
-    const void *in[2] = {d.code, d.flags}, *outs[3] = {d.out, d.hidden, d.mask_pyramid};
-    for (int i = 0; i < 3; ++i) {
-        if (outs[i] == in[0] || outs[i] == in[1] || outs[i] == outs[(i + 1) % 3]) return LP_E_INVALID;
-    }
-    const int gh = (d.height + kB - 1) / kB, gw = (d.width + kB - 1) / kB;
-    const int wide = d.width % 4 == 0 && aligned16(d.code) && aligned16(d.out) && aligned16(d.hidden);
-    hipLaunchKernelGGL(lp_prop_occlude_kernel, dim3(blocks_of(d.width, kTile), blocks_of(d.height, kTile)), dim3(256), 0, stream, d.code,
-                       d.flags, d.out, d.hidden, d.mask_pyramid, d.height, d.width, d.levels, gh, gw, wide);
-    return launched();
+    const lp_prop_occlude_job job = {dp->code, dp->flags, dp->out, dp->hidden, dp->mask_pyramid, nullptr};
+    const lp_prop_occlude_batch_desc d = {dp->height, dp->width, dp->levels, 1, &job};
+    return prop_occlude_batch_dispatch(&d, stream);
 }
 
 int prop_merge_dispatch(const lp_prop_merge_desc* dp, hipStream_t stream) {
@@ -718,6 +889,37 @@ int prop_merge_dispatch(const lp_prop_merge_desc* dp, hipStream_t stream) {
     const int64_t plane = static_cast<int64_t>(d.height) * d.width;
     hipLaunchKernelGGL(lp_prop_merge_kernel, dim3(blocks_of(plane, 256), d.frames), dim3(256), 0, stream, d.qa, d.qb, d.out, plane, d.span,
                        d.first);
+    return launched();
+}
+
+int prop_merge_visible_dispatch(const lp_prop_merge_visible_desc* dp, hipStream_t stream) {
+    if (!dp) return LP_E_INVALID;
+    const lp_prop_merge_visible_desc& d = *dp;
+    const void* in[10] = {d.qa, d.qb, d.code_a, d.mask_a, d.code_b, d.mask_b, d.flags_a, d.flags_b, d.count_a, d.count_b};
+    for (const void* p : in)
+        if (!p) return LP_E_INVALID;
+    if (!d.out || !d.hidden || d.out == d.hidden || !side_ok(d.height) || !side_ok(d.width)) return LP_E_INVALID;
+    if (d.span < 2 || d.first < 1 || d.frames < 1 || static_cast<int64_t>(d.first) + d.frames - 1 > static_cast<int64_t>(d.span) - 1)
+        return LP_E_INVALID;
+    for (const void* p : in) {                                       // in place on the forward chain's planes only
+        if (p == d.out && p != d.mask_a) return LP_E_INVALID;
+        if (p == d.hidden && p != d.code_a) return LP_E_INVALID;
+    }
+    if (d.span > 65535) return LP_E_UNSUPPORTED;                     // frames <= span - 1: inside a grid's y limit
+    merge_visible_args a = {d.qa, d.qb, d.code_a, d.mask_a, d.code_b, d.mask_b, d.flags_a, d.flags_b, d.count_a, d.count_b, d.out, d.hidden};
+    a.plane = static_cast<int64_t>(d.height) * d.width;
+    a.W = d.width;
+    a.gh = (d.height + kB - 1) / kB;
+    a.gw = (d.width + kB - 1) / kB;
+    a.span = d.span;
+    a.first = d.first;
+    bool wide = d.width % 4 == 0;
+    for (const void* p : {in[0], in[1], in[2], in[3], in[4], in[5], static_cast<const void*>(d.out), static_cast<const void*>(d.hidden)})
+        wide = wide && aligned16(p);
+    if (wide)
+        hipLaunchKernelGGL(lp_prop_merge_visible_kernel<4>, dim3(blocks_of(a.plane / 4, 256), d.frames), dim3(256), 0, stream, a);
+    else
+        hipLaunchKernelGGL(lp_prop_merge_visible_kernel<1>, dim3(blocks_of(a.plane, 256), d.frames), dim3(256), 0, stream, a);
     return launched();
 }
 

@@ -13,7 +13,8 @@ propagate_keys(images, masks, key_frames, levels=4, search=2, smooth=8) -> mask 
         around their zero crossing.  So drift is pulled back to zero at every key.  One key gives `propagate_masks` bit for bit;
         a still video with the same mask on every key returns that binarised mask; empty stays exactly 0, full exactly 1.  An
         empty key next to a non-empty one says "nothing here": the other key's mask appears only in the last frames before it.
-        include/lanpaint_hip.h (lp_prop_*_batch, lp_prop_merge) states the rule in full.  Not handled: occlusion.
+        include/lanpaint_hip.h (lp_prop_*_batch, lp_prop_merge) states the rule in full.  Not handled: occlusion; several
+        keyframes with occlusion are propagate_keys_visible.py's, which builds on this module's chains.
 
 HIP tensors only, no CPU fallback, no device -> host read.  The up to 2 K chains do not depend on one another, so step s of all
 of them is one batch: 2 levels + 1 launches per 32 active chains, and the call has as many dependent steps as its longest chain.
@@ -188,17 +189,11 @@ class _Chains:
     def __init__(self, plan, pyr, key_pyrs, outs, H, W, levels, search, smooth):
         dev = pyr.device
         self.H, self.W, self.levels, self.search, self.smooth, self.dev = H, W, levels, search, smooth, dev
-        n = len(plan)
         self.length = np.array([c[3] for c in plan], dtype=np.int64)
         self.grids = [_cabi.prop_grid(H, W, lv) for lv in range(levels)]
         stride = pyr.shape[1]
         self._keep = []                                              # the device buffers behind the addresses
-
-        def buffers(shape, dtype):
-            t = torch.empty((n, *shape), dtype=dtype, device=dev)
-            self._keep.append(t)
-            step = t[0].numel() * t.element_size()
-            return np.uint64(t.data_ptr()) + np.arange(n, dtype=np.uint64) * np.uint64(step)
+        buffers = self._buffers
         self.raw = [buffers((gh, gw, 2), torch.int32) for gh, gw in self.grids]
         self.valid = [buffers((gh, gw), torch.int32) for gh, gw in self.grids]
         self.field = [buffers((gh, gw, 2), torch.int32) for gh, gw in self.grids]
@@ -213,6 +208,14 @@ class _Chains:
         self.match_desc = [_cabi.LpPropMatchBatchDesc(H, W, levels, lv, search, smooth, 0, 0, None) for lv in range(levels)]
         self.advance_desc = _cabi.LpPropAdvanceBatchDesc(H, W, levels, 0, None)
         self.active = None
+
+    def _buffers(self, shape, dtype):
+        """One buffer of `shape` per chain: their addresses."""
+        n = len(self.length)
+        t = torch.empty((n, *shape), dtype=dtype, device=self.dev)
+        self._keep.append(t)
+        step = t[0].numel() * t.element_size()
+        return np.uint64(t.data_ptr()) + np.arange(n, dtype=np.uint64) * np.uint64(step)
 
     def _select(self, idx):
         """The tables of the chains `idx`; the columns that do not move with the step are filled here."""
@@ -231,6 +234,12 @@ class _Chains:
         idx = np.flatnonzero(self.length >= s)
         if self.active is None or len(idx) != len(self.active):
             self._select(idx)
+        self._bind(s, idx)
+        for lo in range(0, len(idx), MAX_JOBS):
+            self._launch(lo, min(MAX_JOBS, len(idx) - lo))
+
+    def _bind(self, s, idx):
+        """The columns that move with the step."""
         src = (self.luma0[idx] + (s - 1) * self.luma_step[idx]).astype(np.uint64)
         tgt = (self.luma0[idx] + s * self.luma_step[idx]).astype(np.uint64)
         mask = self.key[idx] if s == 1 else self.mpyr[(s - 1) & 1][idx]
@@ -240,17 +249,18 @@ class _Chains:
         a[:, 1] = 0 if s == 1 else self.pos[(s - 1) & 1][idx]
         a[:, 3], a[:, 5] = self.pos[s & 1][idx], self.mpyr[s & 1][idx]
         a[:, 4] = (self.out0[idx] + s * self.out_step[idx]).astype(np.uint64)
-        for lo in range(0, len(idx), MAX_JOBS):
-            n = min(MAX_JOBS, len(idx) - lo)
-            for lv in range(self.levels - 1, -1, -1):
-                d = self.match_desc[lv]
-                d.jobs, d.job = n, self.t_match[lv][lo:].ctypes.data
-                launch("lp_prop_match_batch", self.dev, ctypes.byref(d))
-                gh, gw = self.grids[lv]
-                launch("lp_prop_fill_batch", self.dev, self.t_fill[lv][lo:].ctypes.data, n, gh, gw)
-            d = self.advance_desc
-            d.jobs, d.job = n, a[lo:].ctypes.data
-            launch("lp_prop_advance_batch", self.dev, ctypes.byref(d))
+
+    def _launch(self, lo, n):
+        """The launches of the `n` active chains from row `lo` of the tables."""
+        for lv in range(self.levels - 1, -1, -1):
+            d = self.match_desc[lv]
+            d.jobs, d.job = n, self.t_match[lv][lo:].ctypes.data
+            launch("lp_prop_match_batch", self.dev, ctypes.byref(d))
+            gh, gw = self.grids[lv]
+            launch("lp_prop_fill_batch", self.dev, self.t_fill[lv][lo:].ctypes.data, n, gh, gw)
+        d = self.advance_desc
+        d.jobs, d.job = n, self.t_advance[lo:].ctypes.data
+        launch("lp_prop_advance_batch", self.dev, ctypes.byref(d))
 
 
 def _key_masks(masks, keys, F, H, W):

@@ -19,8 +19,8 @@ propagate_masks_visible(images, mask, key_frame=0, levels=4, search=2, smooth=8,
         Integer arithmetic throughout: a still video and a noise-free whole-pixel shift return the binarised key mask and a zero
         `hidden`; an empty mask gives 0 and 0.  include/lanpaint_hip.h (lp_prop_visible, lp_prop_occlude) states the rule in full.
         Not handled: a subject that is hidden entirely leaves the zero field and is lost if it reappears elsewhere; what leaves
-        the picture; several keyframes with occlusion (propagate_keys.py has none); occlusion edges finer than a block --
-        `LanPaint_MaskRefine` follows in the chain.  A lower `occlusion` hides more and starts to take sub-pixel motion and noise
+        the picture; occlusion edges finer than a block -- `LanPaint_MaskRefine` follows in the chain.  Several keyframes with
+        occlusion, where a second key behind the occluder recovers a lost subject: propagate_keys_visible.py.  A lower `occlusion` hides more and starts to take sub-pixel motion and noise
         for an occluder; profiles/r29_propagate_visible.md has the numbers behind the default.
 
 HIP tensors only, no CPU fallback, no device -> host read.  The frames' luma pyramids come in propagate's chunks, under
