@@ -1795,6 +1795,85 @@ typedef struct lp_prop_merge_visible_desc {
 } lp_prop_merge_visible_desc;
 LP_API int lp_prop_merge_visible(const lp_prop_merge_visible_desc* desc, void* stream);
 
+/* ---- Video temporal fill (beyond the reference) -------------------------------------------------------------------------------------
+ * What lies under the mask of a video frame is, in most clips, plain background a few frames earlier or later: a subject moves
+ * across it, or the camera pans past.  These entries borrow it from there, in front of the spatial fill (lp_mask_fill) and the
+ * encode:  mask chain -> temporal fill -> (remaining mask) lp_mask_fill -> encode / Detailer crops.  The motion of the background
+ * is the block field of the propagate section, weighted by the known pixels (the mask's complement) and continued across the hole
+ * by its fill; an origin (frame, position) is carried along it frame by frame in both directions, and the picture is sampled once,
+ * at the origin.  Integer arithmetic decides everything except that sample.  Everything stays on the device.
+ *   limits    sides 1..LP_VMASK_MAX_SIDE; channels 1..LP_DETAIL_MAX_CHANNELS; frames F <= 65535; levels, search and smooth as in the
+ *             propagate section; reach 0..LP_TFILL_MAX_REACH, 0 meaning the whole clip.  Positions are (y, x) pairs of int32 in
+ *             1/16 pixel; `>>` is the arithmetic shift.
+ * 1 known     m = mask >= 0.5 (a NaN gives 0, as lp_prop_key_mask binarises), known = 1 - m.  Every frame gets the pyramid of its
+ *             known bits: the footprints, the OR rule and the byte layout of the propagate section's stage 2
+ *             (lp_prop_pyramid_ws_bytes(1, ...) is a frame's stride).  lp_tfill_known builds them for all frames, a mask of one
+ *             frame serving every frame, and unless the pointers are null the planes the carry starts from:
+ *             source[t] = t on a known pixel and -1 under the mask, remaining[t] = 0.0 and 1.0.  A call for a part of the clip
+ *             names its first frame in frame0, 0..65535 - frames.
+ * 2 fields    For a direction d in {+1, -1} and a frame t whose donor t - d is a frame of the clip, the field of the step is the
+ *             level-0 final field of the propagate section's stage 3 (match, fill and median, levels L - 1 down to 0) with
+ *             src = the luma pyramid of frame t, tgt = the luma pyramid of frame t - d, mask = the known pyramid of frame t;
+ *             V(y, x) is that section's "per pixel" interpolation, and pixel (y, x) of t lies at q = (16 y + Vy, 16 x + Vx) in the
+ *             donor.  A field depends on the two frames and the mask of t only, never on what was carried, so the 2 (F - 1) fields
+ *             of a clip are independent jobs of lp_prop_match_batch / lp_prop_fill_batch, LP_PROP_MAX_JOBS to a launch.
+ * 3 carry     (lp_tfill_carry, one step of one direction) The state of a frame is per pixel an origin (f, P), a frame and a position
+ *             in it, or none.  A known pixel (y, x) of t has the origin (t, (16 y, 16 x)).  A masked pixel: if q is outside
+ *             0..16 (n - 1) on either axis it has none from this direction; otherwise i = (q + 8) >> 4 per axis, r = q - 16 i, and
+ *             if the donor's pixel i has an origin (f, P) with |t - f| <= reach the pixel's origin is (f, P + r), else none.  The
+ *             first frame of a direction has only its known pixels.  The donor's state under its known pixels is implicit (its
+ *             known bits are read, not a stored plane), so the state planes org [height, width] (f, or -1 for none) and pos
+ *             [height, width, 2] are written and read under the mask only; null state planes of the donor say it has none there.
+ * 4 choice    The forward pass (d = +1, t ascending, nearer = 0) runs first and writes every masked pixel for which it has an
+ *             origin.  The backward pass (d = -1, t descending, nearer = 1) writes a pixel only where source[t] is -1 or |t - f| is
+ *             strictly smaller than |t - source[t]|: a tie stays with the past.  A written pixel gets source[t] = f,
+ *             remaining[t] = 0.0 and the sample.  So source[t] ends as f, as t itself on a known pixel, or as -1 where neither pass
+ *             found an origin, and remaining = 1.0 exactly where m = 1 and source = -1.
+ *   sample    of images[f] at P clamped to 0..16 (n - 1) per axis: i = P >> 4, fr = P & 15, i1 = min(i + 1, n - 1); per channel
+ *             row(a, b) = fx == 0 ? 16 a : (16 - fx) a + fx b, value = (fy == 0 ? 16 top : (16 - fy) top + fy bot) * (1 / 256), in
+ *             fp32, every product and sum rounded on its own (no FMA).  A tap with weight 0 is not read, so a non-finite
+ *             neighbour cannot leak.  Image values pass through as fp32, neither clamped nor coded.  `filled` starts as a copy of
+ *             `images` (the caller's), so a pixel with source in {t, -1} keeps images[t] bit for bit.
+ * What follows from the rule: one frame, an empty mask or a full mask returns the images unchanged; a subject that does not move
+ * against the background is left entirely in `remaining`; under noise-free whole-pixel motion the borrowed pixels equal the true
+ * background bit for bit; nothing outside the mask ever changes; the same bits on every run and for every chunking of the fields.
+ * Launches (csrc/temporal_fill_kernel.hip): lp_tfill_known 1 + (levels - 1) for all its frames; lp_tfill_carry one, a block per
+ * 32 x 32 tile that leaves after reading its known bytes when all are 1.  A call is the two pyramids, 2 L launches per
+ * LP_PROP_MAX_JOBS fields and 2 (F - 1) carries; only the carries depend on one another.
+ * LP_E_INVALID: a null pointer (except source and remaining of lp_tfill_known, and the donor's state planes, both or neither); a
+ * side, levels, channels or reach outside its range; frames <= 0 (lp_tfill_carry: frames < 2); mask_frames neither 1 nor frames;
+ * frame0 < 0; frame or donor outside the clip or not neighbours; nearer not 0 / 1; an output plane that is an input or another
+ * output.  LP_E_UNSUPPORTED: frames or frame0 + frames > 65535.  All checked before any HIP call.                                  */
+#define LP_TFILL_MAX_REACH  65535
+
+typedef struct lp_tfill_known_desc {
+    int32_t frames, height, width, levels;
+    int32_t mask_frames, frame0;                  /* 1: one mask plane for every frame, else == frames; frame0: see source  */
+    const float* mask;                            /* [mask_frames, height, width] fp32                                      */
+    uint8_t*     pyramid;                         /* out, lp_prop_pyramid_ws_bytes(frames, height, width, levels) bytes      */
+    int32_t*     source;                          /* out or null, [frames, height, width]; plane f is frame t = frame0 + f  */
+    float*       remaining;                       /* out or null, [frames, height, width]                                   */
+} lp_tfill_known_desc;
+LP_API int lp_tfill_known(const lp_tfill_known_desc* desc, void* stream);
+
+typedef struct lp_tfill_carry_desc {
+    int32_t frames, height, width, channels;
+    int32_t frame, donor;                         /* t and t - d, neighbours inside the clip                                */
+    int32_t reach, nearer;                        /* nearer 0: write wherever an origin is found; 1: only where it is nearer */
+    const int32_t* vec;                           /* the step's level-0 final field [gh, gw, 2]                             */
+    const uint8_t* known;                         /* frame t's known bits [height, width] (level 0 of its pyramid)          */
+    const uint8_t* donor_known;                   /* the donor's                                                            */
+    const int32_t* org_src;                       /* the donor's state [height, width]; null with pos_src: none             */
+    const int32_t* pos_src;                       /* [height, width, 2]                                                     */
+    int32_t*       org_dst;                       /* out, frame t's state, written under its mask only                      */
+    int32_t*       pos_dst;
+    const float*   images;                        /* [frames, height, width, channels] fp32                                 */
+    float*         filled;                        /* in / out, [frames, height, width, channels]: frame t is written        */
+    int32_t*       source;                        /* in / out, [frames, height, width]: frame t is read (nearer) and written */
+    float*         remaining;                     /* in / out, [frames, height, width]: frame t is written                  */
+} lp_tfill_carry_desc;
+LP_API int lp_tfill_carry(const lp_tfill_carry_desc* desc, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

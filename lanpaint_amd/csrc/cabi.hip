@@ -80,6 +80,8 @@ int prop_occlude_dispatch(const lp_prop_occlude_desc* d, hipStream_t stream);
 int prop_visible_batch_dispatch(const lp_prop_visible_batch_desc* d, hipStream_t stream);
 int prop_occlude_batch_dispatch(const lp_prop_occlude_batch_desc* d, hipStream_t stream);
 int prop_merge_visible_dispatch(const lp_prop_merge_visible_desc* d, hipStream_t stream);
+int tfill_known_dispatch(const lp_tfill_known_desc* d, hipStream_t stream);
+int tfill_carry_dispatch(const lp_tfill_carry_desc* d, hipStream_t stream);
 int reshape_mask_dispatch(const float* src, int sb, int sc, int sf, int sh, int sw, float* dst, int db, int dc, int df,
                           int dh, int dw, int taps, int flags, hipStream_t stream);
 }  // namespace lp
@@ -281,6 +283,10 @@ int lp_prop_occlude_batch(const lp_prop_occlude_batch_desc* desc, void* stream) 
 int lp_prop_merge_visible(const lp_prop_merge_visible_desc* desc, void* stream) {
     return lp::prop_merge_visible_dispatch(desc, as_stream(stream));
 }
+
+int lp_tfill_known(const lp_tfill_known_desc* desc, void* stream) { return lp::tfill_known_dispatch(desc, as_stream(stream)); }
+
+int lp_tfill_carry(const lp_tfill_carry_desc* desc, void* stream) { return lp::tfill_carry_dispatch(desc, as_stream(stream)); }
 
 int lp_finalize(const lp_final_desc* desc, void* stream) { return lp::finalize_dispatch(desc, as_stream(stream)); }
 

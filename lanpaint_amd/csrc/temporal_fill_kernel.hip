@@ -1,0 +1,244 @@
+// temporal_fill_kernel.hip -- video temporal fill for gfx950 (lanpaint_amd/temporal_fill.py): what lies under the mask of a frame is
+// borrowed from the nearest frame in which the same piece of background is visible.  include/lanpaint_hip.h (lp_tfill_*) states
+// the rule.  The motion of the known pixels is the propagate section's block field, computed by lp_prop_match_batch and
+// lp_prop_fill_batch unchanged with the known bits as weights; this file holds what is new.
+//
+//   known, down  one lane per pixel and frame: known = !(mask >= 0.5) into level 0 of every frame's pyramid, with the initial
+//                source (the frame itself, or -1 under the mask) and remaining planes; then one launch per further level, the OR
+//                over the propagate section's footprints.  1 + (levels - 1) launches for all frames.
+//   carry        one step of one direction.  A block per 32 x 32 tile, a lane per pixel.  The block reads its known bytes
+//                first and leaves when all are 1 -- most of a frame.  Else the 6 x 6 block vectors the tile's pixels interpolate
+//                between go to LDS; a masked pixel follows its vector into the donor, takes over the donor's origin (implicit under
+//                the donor's known pixels, a stored plane under its mask) and, where the pass writes, samples the origin's frame:
+//                a gather bound by memory.  The arguments travel by value.
+// Integer arithmetic decides everything but the sample, which is fp32 in a fixed order, every operation rounded on its own
+// (__fmul_rn / __fadd_rn: nothing contracts).  No scratch, no atomics.
+#include "lp_common.h"
+
+namespace lp {
+
+int64_t prop_pyramid_ws_bytes(int frames, int height, int width, int levels);         // propagate_kernel.hip: the pyramid's layout
+
+namespace {
+
+constexpr int kB = LP_PROP_BLOCK;                                                     // 8
+constexpr int kTile = 32;                                                             // carry: pixels per tile side
+constexpr int kTileBlocks = kTile / kB + 2;                                           // 6: the block centres a tile interpolates between
+
+static_assert(kTile % (2 * kB) == 0, "a tile starts on an even block, so its first pixel's lower block is 4 ty - 1");
+
+__device__ __forceinline__ int clampi(int v, int lo, int hi) { return min(max(v, lo), hi); }
+
+inline int level_side(int n, int l) { return (n + (1 << l) - 1) >> l; }
+inline int64_t level_offset(int h, int w, int l) { return l == 0 ? 0 : prop_pyramid_ws_bytes(1, h, w, l); }
+
+// ---- known bits and their pyramids --------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void lp_tfill_known_kernel(const float* __restrict__ mask, int64_t mask_step, uint8_t* __restrict__ pyr,
+                                                             int64_t stride, int64_t plane, int frame0, int32_t* __restrict__ source,
+                                                             float* __restrict__ remaining) {
+    const int64_t p = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
+    if (p >= plane) return;
+    const int64_t f = blockIdx.y;
+    const bool m = mask[f * mask_step + p] >= 0.5f;                                      // a NaN gives 0: known
+    pyr[f * stride + p] = m ? 0 : 1;
+    if (source) source[f * plane + p] = m ? -1 : frame0 + static_cast<int32_t>(f);
+    if (remaining) remaining[f * plane + p] = m ? 1.0f : 0.0f;
+}
+
+__global__ __launch_bounds__(256) void lp_tfill_down_kernel(uint8_t* __restrict__ pyr, int64_t stride, int64_t src_off, int64_t dst_off,
+                                                            int sh, int sw, int dh, int dw) {
+    const int64_t p = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
+    if (p >= static_cast<int64_t>(dh) * dw) return;
+    const int y = static_cast<int>(p / dw), x = static_cast<int>(p - static_cast<int64_t>(y) * dw);
+    const uint8_t* src = pyr + static_cast<int64_t>(blockIdx.y) * stride + src_off;
+    const int y0 = 2 * y, y1 = min(2 * y + 1, sh - 1), x0 = 2 * x, x1 = min(2 * x + 1, sw - 1);        // 2y <= sh - 1 always
+    const uint8_t v = src[static_cast<int64_t>(y0) * sw + x0] | src[static_cast<int64_t>(y0) * sw + x1] |
+                      src[static_cast<int64_t>(y1) * sw + x0] | src[static_cast<int64_t>(y1) * sw + x1];
+    pyr[static_cast<int64_t>(blockIdx.y) * stride + dst_off + p] = v;
+}
+
+// ---- carry --------------------------------------------------------------------------------------------------------------------------
+struct carry_args {
+    const int32_t* vec;          // [gh, gw, 2]
+    const uint8_t* known;        // frame t's bits [H, W]
+    const uint8_t* donor_known;
+    const int32_t* org_src;      // the donor's state, read under its mask; null: the donor has none there
+    const int32_t* pos_src;
+    int32_t*       org_dst;      // frame t's state, written under its mask
+    int32_t*       pos_dst;
+    const float*   images;       // [frames, H, W, C]
+    float*         filled;       // frame t's planes
+    int32_t*       source;
+    float*         remaining;
+    int32_t H, W, C, gh, gw, frames, t, donor, reach, nearer;
+};
+
+// (16 - f) a + f b, or 16 a without reading b's weight into it: the products and the sum rounded on their own
+__device__ __forceinline__ float lerp16(float a, float b, int f) {
+    if (f == 0) return __fmul_rn(16.0f, a);
+    return __fadd_rn(__fmul_rn(static_cast<float>(16 - f), a), __fmul_rn(static_cast<float>(f), b));
+}
+
+// One lane per pixel: a masked pixel's work is a chain of dependent reads (known byte, block vectors, the donor's byte and state, the
+// taps), so the 1024 pixels of a tile go side by side on 16 waves rather than four after another on 4.
+__global__ __launch_bounds__(kTile * kTile) void lp_tfill_carry_kernel(const carry_args a) {
+    __shared__ int32_t s_v[kTileBlocks * kTileBlocks * 2];
+    const int H = a.H, W = a.W, C = a.C;
+    const int ly = threadIdx.x >> 5, lx = threadIdx.x & 31, y = blockIdx.y * kTile + ly, x = blockIdx.x * kTile + lx;
+    const int64_t p = static_cast<int64_t>(y) * W + x;
+    const bool masked = y < H && x < W && a.known[p] == 0;
+    if (__syncthreads_and(!masked)) return;                              // the whole block: nothing under a mask here
+    // the block vectors around the tile: row j is block clamp(4 ty - 1 + j)
+    if (threadIdx.x < kTileBlocks * kTileBlocks) {
+        const int j = threadIdx.x / kTileBlocks, i = threadIdx.x - j * kTileBlocks;
+        const int by = clampi(static_cast<int>(blockIdx.y) * (kTile / kB) - 1 + j, 0, a.gh - 1);
+        const int bx = clampi(static_cast<int>(blockIdx.x) * (kTile / kB) - 1 + i, 0, a.gw - 1);
+        const int32_t* v = a.vec + (static_cast<int64_t>(by) * a.gw + bx) * 2;
+        s_v[threadIdx.x * 2] = v[0];
+        s_v[threadIdx.x * 2 + 1] = v[1];
+    }
+    __syncthreads();
+    if (!masked) return;                                                 // known, or outside the plane
+    // the per-pixel vector: the propagate section's interpolation; block b0 of the plane is row b0 - (4 ty - 1) of s_v
+    const int uy = 2 * ly + 9, ux = 2 * lx + 9;                          // u = 2 y - 7, counted from block 4 ty - 1: u - 16 (4 ty - 1)
+    const int jy = uy >> 4, jx = ux >> 4, fy = uy & 15, fx = ux & 15;
+    const int32_t *v00 = s_v + (jy * kTileBlocks + jx) * 2, *v01 = v00 + 2, *v10 = v00 + kTileBlocks * 2, *v11 = v10 + 2;
+    const int Vy = ((16 - fy) * ((16 - fx) * v00[0] + fx * v01[0]) + fy * ((16 - fx) * v10[0] + fx * v11[0]) + 128) >> 8;
+    const int Vx = ((16 - fy) * ((16 - fx) * v00[1] + fx * v01[1]) + fy * ((16 - fx) * v10[1] + fx * v11[1]) + 128) >> 8;
+    const int qy = 16 * y + Vy, qx = 16 * x + Vx;
+    const int cur = a.nearer ? a.source[p] : -1;                         // what an earlier pass found; read ahead of its use
+    int f = -1, Py = 0, Px = 0;
+    if (qy >= 0 && qy <= 16 * (H - 1) && qx >= 0 && qx <= 16 * (W - 1)) {
+        const int iy = (qy + 8) >> 4, ix = (qx + 8) >> 4;                // <= n - 1: inside the plane
+        const int64_t dp = static_cast<int64_t>(iy) * W + ix;
+        // the donor's byte and its state are asked for together; the state's values count under the donor's mask only
+        const uint8_t dk = a.donor_known[dp];
+        const int sf = a.org_src ? a.org_src[dp] : -1;
+        const int spy = a.org_src ? a.pos_src[dp * 2] : 0, spx = a.org_src ? a.pos_src[dp * 2 + 1] : 0;
+        f = dk ? a.donor : sf;
+        Py = dk ? 16 * iy : spy;
+        Px = dk ? 16 * ix : spx;
+        if (f >= 0 && f < a.frames && abs(a.t - f) <= a.reach) {         // f < frames: a state plane this entry wrote holds no other
+            Py += qy - 16 * iy;
+            Px += qx - 16 * ix;
+        } else {
+            f = -1;
+        }
+    }
+    a.org_dst[p] = f;
+    a.pos_dst[p * 2] = f >= 0 ? Py : 0;
+    a.pos_dst[p * 2 + 1] = f >= 0 ? Px : 0;
+    if (f < 0) return;
+    if (cur >= 0 && abs(a.t - f) >= abs(a.t - cur)) return;              // nearer: a tie stays with what is there
+    // the sample of frame f at P clamped to the plane; a tap with weight 0 is not read
+    const int cy = clampi(Py, 0, 16 * (H - 1)), cx = clampi(Px, 0, 16 * (W - 1));
+    const int sy = cy >> 4, sx = cx >> 4, gy = cy & 15, gx = cx & 15;
+    const float* __restrict__ r0 = a.images + ((static_cast<int64_t>(f) * H + sy) * W + sx) * C;
+    const float* __restrict__ r1 = r0 + (gy ? static_cast<int64_t>(W) * C : 0);   // gy != 0 puts sy + 1 inside the plane, as gx does sx + 1
+    const int nx = gx ? C : 0;
+    float* __restrict__ out = a.filled + p * C;
+#pragma unroll 1
+    for (int c0 = 0; c0 < C; c0 += 4) {                                  // four channels' taps are asked for before the first is used
+        float t00[4], t01[4], t10[4], t11[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const bool in = c0 + k < C;
+            t00[k] = in ? r0[c0 + k] : 0.0f;
+            t01[k] = in && gx ? r0[nx + c0 + k] : 0.0f;
+            t10[k] = in && gy ? r1[c0 + k] : 0.0f;
+            t11[k] = in && gy && gx ? r1[nx + c0 + k] : 0.0f;
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            if (c0 + k >= C) break;
+            const float top = lerp16(t00[k], t01[k], gx);
+            const float v = gy == 0 ? __fmul_rn(16.0f, top)
+                                    : __fadd_rn(__fmul_rn(static_cast<float>(16 - gy), top), __fmul_rn(static_cast<float>(gy), lerp16(t10[k], t11[k], gx)));
+            out[c0 + k] = __fmul_rn(v, 1.0f / 256.0f);
+        }
+    }
+    a.source[p] = f;
+    a.remaining[p] = 0.0f;
+}
+
+bool side_ok(int s) { return s > 0 && s <= LP_VMASK_MAX_SIDE; }
+bool levels_ok(int l) { return l >= 1 && l <= LP_PROP_MAX_LEVELS; }
+int launched() { return hipGetLastError() == hipSuccess ? LP_OK : LP_E_LAUNCH; }
+uint32_t blocks_of(int64_t n, int per) { return static_cast<uint32_t>((n + per - 1) / per); }
+
+}  // namespace
+
+int tfill_known_dispatch(const lp_tfill_known_desc* dp, hipStream_t stream) {
+    if (!dp) return LP_E_INVALID;
+    const lp_tfill_known_desc& d = *dp;
+    if (d.frames <= 0 || !side_ok(d.height) || !side_ok(d.width) || !levels_ok(d.levels)) return LP_E_INVALID;
+    if ((d.mask_frames != 1 && d.mask_frames != d.frames) || d.frame0 < 0) return LP_E_INVALID;
+    if (!d.mask || !d.pyramid) return LP_E_INVALID;
+    const void *in = d.mask, *outs[3] = {d.pyramid, d.source, d.remaining};
+    for (int k = 0; k < 3; ++k) {                                        // source and remaining may be null; given, nothing aliases
+        if (!outs[k]) continue;
+        if (outs[k] == in) return LP_E_INVALID;
+        for (int m = k + 1; m < 3; ++m)
+            if (outs[k] == outs[m]) return LP_E_INVALID;
+    }
+    if (d.frames > 65535 || d.frame0 > 65535 - d.frames) return LP_E_UNSUPPORTED;
+    const int64_t plane = static_cast<int64_t>(d.height) * d.width, stride = level_offset(d.height, d.width, d.levels);
+    hipLaunchKernelGGL(lp_tfill_known_kernel, dim3(blocks_of(plane, 256), d.frames), dim3(256), 0, stream, d.mask,
+                       d.mask_frames == 1 ? int64_t{0} : plane, d.pyramid, stride, plane, d.frame0, d.source, d.remaining);
+    if (hipGetLastError() != hipSuccess) return LP_E_LAUNCH;
+    for (int l = 1; l < d.levels; ++l) {
+        const int sh = level_side(d.height, l - 1), sw = level_side(d.width, l - 1), dh = level_side(d.height, l), dw = level_side(d.width, l);
+        hipLaunchKernelGGL(lp_tfill_down_kernel, dim3(blocks_of(static_cast<int64_t>(dh) * dw, 256), d.frames), dim3(256), 0, stream,
+                           d.pyramid, stride, level_offset(d.height, d.width, l - 1), level_offset(d.height, d.width, l), sh, sw, dh, dw);
+        if (hipGetLastError() != hipSuccess) return LP_E_LAUNCH;
+    }
+    return LP_OK;
+}
+
+int tfill_carry_dispatch(const lp_tfill_carry_desc* dp, hipStream_t stream) {
+    if (!dp) return LP_E_INVALID;
+    const lp_tfill_carry_desc& d = *dp;
+    if (d.frames < 2 || !side_ok(d.height) || !side_ok(d.width) || d.channels < 1 || d.channels > LP_DETAIL_MAX_CHANNELS) return LP_E_INVALID;
+    if (d.reach < 0 || d.reach > LP_TFILL_MAX_REACH || (d.nearer != 0 && d.nearer != 1)) return LP_E_INVALID;
+    if (d.frames > 65535) return LP_E_UNSUPPORTED;
+    if (d.frame < 0 || d.frame >= d.frames || d.donor < 0 || d.donor >= d.frames || (d.donor != d.frame - 1 && d.donor != d.frame + 1))
+        return LP_E_INVALID;
+    if (!d.vec || !d.known || !d.donor_known || !d.org_dst || !d.pos_dst || !d.images || !d.filled || !d.source || !d.remaining)
+        return LP_E_INVALID;
+    if ((d.org_src == nullptr) != (d.pos_src == nullptr)) return LP_E_INVALID;
+    const void *outs[5] = {d.org_dst, d.pos_dst, d.filled, d.source, d.remaining};
+    const void *in[6] = {d.vec, d.known, d.donor_known, d.org_src, d.pos_src, d.images};
+    for (int k = 0; k < 5; ++k) {
+        for (const void* p : in)
+            if (outs[k] == p) return LP_E_INVALID;
+        for (int m = k + 1; m < 5; ++m)
+            if (outs[k] == outs[m]) return LP_E_INVALID;
+    }
+    const int64_t plane = static_cast<int64_t>(d.height) * d.width;
+    carry_args a = {};
+    a.vec = d.vec;
+    a.known = d.known;
+    a.donor_known = d.donor_known;
+    a.org_src = d.org_src;
+    a.pos_src = d.pos_src;
+    a.org_dst = d.org_dst;
+    a.pos_dst = d.pos_dst;
+    a.images = d.images;
+    a.filled = d.filled + d.frame * plane * d.channels;
+    a.source = d.source + d.frame * plane;
+    a.remaining = d.remaining + d.frame * plane;
+    a.H = d.height;
+    a.W = d.width;
+    a.C = d.channels;
+    a.gh = (d.height + kB - 1) / kB;
+    a.gw = (d.width + kB - 1) / kB;
+    a.frames = d.frames;
+    a.t = d.frame;
+    a.donor = d.donor;
+    a.reach = d.reach ? d.reach : LP_TFILL_MAX_REACH;                    // 0: the whole clip; frames <= 65535, so no age exceeds it
+    a.nearer = d.nearer;
+    hipLaunchKernelGGL(lp_tfill_carry_kernel, dim3(blocks_of(d.width, kTile), blocks_of(d.height, kTile)), dim3(kTile * kTile), 0, stream, a);
+    return launched();
+}
+
+}  // namespace lp

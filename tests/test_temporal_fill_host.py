@@ -1,0 +1,271 @@
+"""The video temporal fill, the parts that need no device: the properties the rule promises on the restatement
+(tests/temporal_fill_ref.py) as bits and counts, the C entries' argument checks (made before any HIP call), the descriptors'
+layout against the header as gcc reads it, the names' presence everywhere, the wrappers' argument checks, the node's protocol and
+the no-fallback errors."""
+import ctypes
+import functools
+import os
+import re
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+from lanpaint_amd import _cabi
+from tests import propagate_ref as ref
+from tests import temporal_fill_ref as tref
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+NEW_ENTRIES = ("lp_tfill_known", "lp_tfill_carry")
+
+
+def _bits(a):
+    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
+
+
+# ---- the scenes of the three properties; tests/test_gpu_temporal_fill.py runs the device on the same ones ---------------------------------
+@functools.lru_cache(maxsize=None)
+def pan_clip():
+    """(boxless clip, clip, mask): 8 frames of 48 x 64 x 3 cut from one random canvas, panning (1, -2) px per frame; a 12 x 12
+    constant box moves 5 px per frame across it; the mask is the box grown by 1."""
+    rng = np.random.default_rng(5)
+    F, H, W = 8, 48, 64
+    canvas = rng.random((H + F, W + 2 * F, 3), dtype=np.float32)
+    clean = np.stack([canvas[t:t + H, 2 * (F - 1 - t):2 * (F - 1 - t) + W] for t in range(F)])
+    clip, mask = clean.copy(), np.zeros((F, H, W), np.float32)
+    for t in range(F):
+        y, x = 18, 4 + 5 * t
+        clip[t, y:y + 12, x:x + 12] = 0.5
+        mask[t, y - 1:y + 13, x - 1:x + 13] = 1
+    return clean, clip, mask
+
+
+@functools.lru_cache(maxsize=None)
+def still_clip(step):
+    """(still canvas, clip, mask): 8 equal frames of 32 x 48 x 3 with an 8 x 8 constant box that moves `step` px per frame."""
+    F, H, W = 8, 32, 48
+    still = np.repeat(np.random.default_rng(6).random((1, H, W, 3), dtype=np.float32), F, axis=0)
+    clip, mask = still.copy(), np.zeros((F, H, W), np.float32)
+    for t in range(F):
+        clip[t, 12:20, 10 + step * t:18 + step * t] = 0.25
+        mask[t, 12:20, 10 + step * t:18 + step * t] = 1
+    return still, clip, mask
+
+
+STILL_REMAINING = {1: 288, 2: 96, 8: 0}                               # reach -> pixels no frame within it shows
+
+
+def check_pan(filled, remaining, source):
+    clean, clip, mask = pan_clip()
+    assert int(mask.sum()) == 1568 and not remaining.any()
+    assert (_bits(filled) == _bits(clean)).all()                       # all 1568 masked pixels are the true background, bit for bit
+    assert ((source >= 0) & (source < 8)).all() and ((source == np.arange(8)[:, None, None]) == (mask == 0)).all()
+
+
+def check_still(reach, filled, remaining, source):
+    still, clip, mask = still_clip(2)
+    assert int(remaining.sum()) == STILL_REMAINING[reach]
+    assert ((remaining == 1) == ((mask == 1) & (source == -1))).all()
+    age = np.abs(source - np.arange(8)[:, None, None])
+    assert (age[source >= 0] <= reach).all()
+    assert (_bits(filled) == np.where((remaining == 1)[..., None], _bits(clip), _bits(still))).all()
+
+
+def check_fixed(filled, remaining, source):
+    _, clip, mask = still_clip(0)
+    assert (_bits(remaining) == _bits(mask)).all() and (_bits(filled) == _bits(clip)).all()
+    assert (source == np.where(mask == 1, -1, np.arange(8)[:, None, None])).all()
+
+
+# ---- the properties, on the restatement ---------------------------------------------------------------------------------------------------
+def test_pan_clip_is_filled_with_the_true_background_bit_for_bit():
+    _, clip, mask = pan_clip()
+    check_pan(*tref.temporal_fill_ref(clip, mask))
+
+
+@pytest.mark.parametrize("reach", list(STILL_REMAINING))
+def test_reach_bounds_the_age_on_a_still_canvas(reach):
+    _, clip, mask = still_clip(2)
+    check_still(reach, *tref.temporal_fill_ref(clip, mask, reach=reach))
+
+
+def test_a_fixed_subject_stays_in_remaining():
+    _, clip, mask = still_clip(0)
+    check_fixed(*tref.temporal_fill_ref(clip, mask))
+
+
+def test_one_frame_empty_and_full_masks_return_the_images_and_a_tie_stays_with_the_past():
+    rng = np.random.default_rng(7)
+    video = rng.random((4, 16, 17, 3), dtype=np.float32)
+    soft = rng.random((4, 16, 17), dtype=np.float32)
+    filled, remaining, source = tref.temporal_fill_ref(video[:1], soft[:1], 3)
+    assert (_bits(filled) == _bits(video[:1])).all() and (remaining[0] == ref.binarise(soft[0])).all()
+    for value in (0.0, 1.0):
+        filled, remaining, source = tref.temporal_fill_ref(video, np.full((16, 17), value, np.float32), 3)
+        assert (_bits(filled) == _bits(video)).all() and (remaining == value).all()
+        assert (source == (np.arange(4)[:, None, None] if value == 0 else -1)).all()
+    # frame 1 of three equal frames, masked there only: both neighbours show it at age 1, the earlier one is taken
+    still = np.repeat(video[:1], 3, axis=0)
+    mask = np.zeros((3, 16, 17), np.float32)
+    mask[1, 4:9, 5:12] = 1
+    filled, remaining, source = tref.temporal_fill_ref(still, mask, 3)
+    assert not remaining.any() and (source[1][mask[1] == 1] == 0).all() and (_bits(filled) == _bits(still)).all()
+    # a NaN in the mask is known; a non-finite neighbour of a whole-pixel origin does not leak
+    wild = still.copy()
+    wild[:, 3, :] = np.nan
+    wild[:, :, 4] = np.inf
+    filled, _, _ = tref.temporal_fill_ref(wild, mask, 3)
+    assert (_bits(filled) == _bits(wild)).all()
+
+
+def test_the_sample_one_value_at_a_time():
+    img = np.zeros((1, 2, 2, 1), np.float32)
+    img[0, :, :, 0] = [[1, 3], [5, 9]]
+    one = lambda y, x: tref.sample(img, np.array([0]), np.array([y]), np.array([x]))[0, 0]    # noqa: E731
+    assert one(0, 0) == 1 and one(0, 16) == 3 and one(16, 0) == 5 and one(16, 16) == 9
+    assert one(0, 8) == 2 and one(8, 0) == 3 and one(8, 8) == np.float32(4.5) and one(4, 12) == np.float32(((4 * 1 + 12 * 3) * 12 + (4 * 5 + 12 * 9) * 4) / 256)
+    assert one(-5, 40) == 3 and one(99, -1) == 5                       # clamped to the plane
+    img[0, 1, 1, 0] = np.nan
+    assert one(0, 0) == 1 and one(0, 16) == 3 and one(16, 0) == 5 and np.isnan(one(1, 1))
+
+
+# ---- the C ABI ------------------------------------------------------------------------------------------------------------------------
+def test_entries_reject_bad_arguments_without_a_device(hip_lib):
+    C, E, U = ctypes, _cabi.LP_E_INVALID, _cabi.LP_E_UNSUPPORTED
+    side = _cabi.LP_VMASK_MAX_SIDE
+    a = [C.c_void_p(4096 * (i + 1)) for i in range(12)]               # never dereferenced: validation comes before any HIP call
+
+    good = dict(frames=5, height=40, width=70, levels=3, mask_frames=5, mask=a[0], pyramid=a[1], source=a[2], remaining=a[3])
+    assert hip_lib.lp_tfill_known(None, None) == E
+    for change in ({"frames": 0}, {"frames": -1}, {"height": 0}, {"height": side + 1}, {"width": 0}, {"width": side + 1},
+                   {"levels": 0}, {"levels": _cabi.LP_PROP_MAX_LEVELS + 1}, {"mask_frames": 0}, {"mask_frames": 2}, {"mask_frames": 6},
+                   {"frame0": -1},
+                   {"mask": None}, {"pyramid": None}, {"pyramid": a[0]}, {"source": a[0]}, {"remaining": a[0]}, {"source": a[1]},
+                   {"remaining": a[1]}, {"remaining": a[2]}):
+        assert hip_lib.lp_tfill_known(C.byref(_cabi.LpTfillKnownDesc(**{**good, **change})), None) == E, change
+    assert hip_lib.lp_tfill_known(C.byref(_cabi.LpTfillKnownDesc(**{**good, "frames": 65536, "mask_frames": 1})), None) == U
+    assert hip_lib.lp_tfill_known(C.byref(_cabi.LpTfillKnownDesc(**{**good, "frames": 65536, "mask_frames": 65536})), None) == U
+    assert hip_lib.lp_tfill_known(C.byref(_cabi.LpTfillKnownDesc(**{**good, "frame0": 65531})), None) == U      # frame 65535 would be its last
+
+    names = [f for f, t in _cabi.LpTfillCarryDesc._fields_ if t is C.c_void_p]
+    good = dict(frames=5, height=40, width=70, channels=3, frame=2, donor=1, reach=0, nearer=0, **dict(zip(names, a)))
+    assert len(names) == 11 and hip_lib.lp_tfill_carry(None, None) == E
+    for change in ({"frames": 1}, {"frames": 0}, {"height": 0}, {"height": side + 1}, {"width": 0}, {"width": side + 1},
+                   {"channels": 0}, {"channels": _cabi.LP_DETAIL_MAX_CHANNELS + 1}, {"reach": -1}, {"reach": _cabi.LP_TFILL_MAX_REACH + 1},
+                   {"nearer": 2}, {"nearer": -1}, {"frame": -1}, {"frame": 5}, {"donor": 2}, {"donor": 4}, {"donor": 0},
+                   {"frame": 0, "donor": -1}, {"frame": 4, "donor": 5}, {"org_src": None}, {"pos_src": None}):
+        assert hip_lib.lp_tfill_carry(C.byref(_cabi.LpTfillCarryDesc(**{**good, **change})), None) == E, change
+    for name in names:
+        if name not in ("org_src", "pos_src"):                         # the donor's state: both null is "none"
+            assert hip_lib.lp_tfill_carry(C.byref(_cabi.LpTfillCarryDesc(**{**good, name: None})), None) == E, name
+    outs = ("org_dst", "pos_dst", "filled", "source", "remaining")
+    for out in outs:                                                   # an output plane that is an input or another output
+        for other in names:
+            if other != out:
+                assert hip_lib.lp_tfill_carry(C.byref(_cabi.LpTfillCarryDesc(**{**good, out: good[other]})), None) == E, (out, other)
+    assert hip_lib.lp_tfill_carry(C.byref(_cabi.LpTfillCarryDesc(**{**good, "frames": 65536})), None) == U
+
+
+def test_descriptor_layouts_and_constants_match_c(tmp_path):
+    structs = (("lp_tfill_known_desc", _cabi.LpTfillKnownDesc), ("lp_tfill_carry_desc", _cabi.LpTfillCarryDesc))
+    prog = ['#include <stdio.h>', '#include <stddef.h>', '#include "lanpaint_hip.h"', "int main(void){"]
+    for cname, py in structs:
+        for f, _ in py._fields_:
+            prog.append(f'printf("%zu ", offsetof({cname}, {f}));')
+        prog.append(f'printf("%zu\\n", sizeof({cname}));')
+    prog.append('printf("%d %d\\n", LP_TFILL_MAX_REACH, LP_ABI_VERSION); return 0;}')
+    src = tmp_path / "layout.c"
+    src.write_text("\n".join(prog))
+    exe = tmp_path / "layout"
+    subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
+    lines = subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.strip().split("\n")
+    for line, (_, py) in zip(lines, structs):
+        assert [int(v) for v in line.split()] == [getattr(py, f).offset for f, _ in py._fields_] + [ctypes.sizeof(py)]
+    assert [int(v) for v in lines[-1].split()] == [_cabi.LP_TFILL_MAX_REACH, _cabi.ABI_VERSION]
+
+
+def test_the_names_are_everywhere_and_the_abi_version_stays(hip_lib):
+    header = open(os.path.join(ROOT, "include", "lanpaint_hip.h")).read()
+    dynamic = subprocess.run(["nm", "-D", "--defined-only", _cabi.LIB_PATH], capture_output=True, text=True, check=True).stdout
+    exports = open(os.path.join(ROOT, "lanpaint_amd", "csrc", "exports.map")).read()
+    assert re.search(r"global:\s*lp_\*;", exports)                     # every lp_* entry, these two among them
+    for name in NEW_ENTRIES:
+        assert re.search(r"LP_API\s+int\s+%s\s*\(" % name, header), name
+        assert name in _cabi.EXPORTS and hasattr(hip_lib, name)
+        assert re.search(r"\bT %s$" % name, dynamic, flags=re.M), name
+    assert _cabi.ABI_VERSION == 25 and hip_lib.lp_abi_version() == 25
+    for word in ("LP_TFILL_MAX_REACH", "a tie stays with the past", "A tap with weight 0 is not read", "no FMA", "known = 1 - m",
+                 "r = q - 16 i", "for every chunking"):
+        assert word in header, word
+
+
+# ---- the wrappers and the node ----------------------------------------------------------------------------------------------------------
+def test_temporal_fill_refuses_cpu_tensors_and_bad_arguments():
+    from lanpaint_amd import temporal_fill as tf
+    images, mask = torch.zeros(4, 16, 16, 3), torch.zeros(4, 16, 16)
+    with pytest.raises(RuntimeError, match="no CPU fallback"):
+        tf.temporal_fill(images, mask)
+    with pytest.raises(RuntimeError, match="no CPU fallback"):
+        tf.temporal_fill(images.numpy(), mask)
+    with pytest.raises(RuntimeError, match="no CPU fallback"):
+        tf.known_pyramids(mask, 4, 3)
+    row = torch.zeros(2, _cabi.prop_pyramid_ws_bytes(1, 16, 16, 3), dtype=torch.uint8)
+    with pytest.raises(RuntimeError, match="no CPU fallback"):
+        tf.step_fields(row, row, [(1, 0)], 16, 16, 3)
+    planes = (torch.zeros(2, 2, 2, dtype=torch.int32), torch.zeros(16, 16, dtype=torch.uint8), torch.zeros(16, 16, dtype=torch.uint8), None,
+              images, images.clone(), torch.zeros(4, 16, 16, dtype=torch.int32), mask.clone())
+    with pytest.raises(RuntimeError, match="no CPU fallback"):
+        tf.carry(*planes, 1, 0)
+    # the numbers are checked before the tensors are looked at
+    for bad in (dict(levels=0), dict(levels=7), dict(levels=2.0), dict(search=0), dict(search=8), dict(smooth=-1), dict(smooth=65),
+                dict(smooth=None), dict(reach=-1), dict(reach=65536), dict(reach=1.0), dict(reach=True)):
+        with pytest.raises(ValueError):
+            tf.temporal_fill(images, mask, **bad)
+    for bad in (dict(levels=0), dict(levels=7), dict(frames=0), dict(frames=65536), dict(frame0=-1), dict(frame0=65532)):
+        with pytest.raises(ValueError):
+            tf.known_pyramids(mask, **{"frames": 4, "levels": 3, **bad})
+    for bad in (dict(levels=0), dict(search=8), dict(smooth=65), dict(H=0), dict(W=_cabi.LP_VMASK_MAX_SIDE + 1)):
+        with pytest.raises(ValueError):
+            tf.step_fields(row, row, [(1, 0)], **{"H": 16, "W": 16, "levels": 3, **bad})
+    for bad in (dict(reach=-1), dict(reach=65536)):
+        with pytest.raises(ValueError):
+            tf.carry(*planes, 1, 0, **bad)
+    assert tf.WS_CAP_BYTES == 1 << 30 and tf.MAX_JOBS == 32 and tf.MAX_REACH == 65535 and tf.MAX_FRAMES == 65535
+
+
+def test_node_protocol_and_own_mappings():
+    from lanpaint_amd import (detail_nodes, fill_nodes, grain_nodes, multiband_nodes, nodes, propagate_keys_nodes,
+                              propagate_keys_visible_nodes, propagate_nodes, propagate_visible_nodes, refine_nodes, stabilize_nodes,
+                              temporal_fill_nodes, video_nodes)
+    node = temporal_fill_nodes.LanPaint_VideoTemporalFill
+    assert temporal_fill_nodes.NODE_CLASS_MAPPINGS == {"LanPaint_VideoTemporalFill": node}
+    assert list(temporal_fill_nodes.NODE_DISPLAY_NAME_MAPPINGS) == ["LanPaint_VideoTemporalFill"]
+    for other in (nodes, detail_nodes, fill_nodes, multiband_nodes, refine_nodes, stabilize_nodes, grain_nodes, video_nodes,
+                  propagate_nodes, propagate_keys_nodes, propagate_visible_nodes, propagate_keys_visible_nodes):
+        assert not set(temporal_fill_nodes.NODE_CLASS_MAPPINGS) & set(other.NODE_CLASS_MAPPINGS)
+        assert not set(temporal_fill_nodes.NODE_DISPLAY_NAME_MAPPINGS.values()) & set(other.NODE_DISPLAY_NAME_MAPPINGS.values())
+    types = node.INPUT_TYPES()
+    req = types["required"]
+    assert list(types) == ["required"] and list(req) == ["image", "mask", "levels", "search", "smooth", "reach"]
+    assert req["image"][0] == "IMAGE" and req["mask"][0] == "MASK"
+    assert req["levels"][0] == "INT" and req["levels"][1] == {**req["levels"][1], "default": 4, "min": 1, "max": 6}
+    assert req["search"][0] == "INT" and req["search"][1] == {**req["search"][1], "default": 2, "min": 1, "max": 7}
+    assert req["smooth"][0] == "INT" and req["smooth"][1] == {**req["smooth"][1], "default": 8, "min": 0, "max": 64}
+    assert req["reach"][0] == "INT" and req["reach"][1] == {**req["reach"][1], "default": 0, "min": 0, "max": 65535}
+    for name in req:
+        assert len(req[name][1]["tooltip"]) > 20, name
+    for word in ("other frames", "motion", "nearest frame", "mask fill", "encode", "Detailer", "remaining", "colour-matched"):
+        assert word in node.DESCRIPTION, word
+    assert node.RETURN_TYPES == ("IMAGE", "MASK", "MASK") and node.RETURN_NAMES == ("image", "remaining", "filled")
+    assert node.FUNCTION == "fill" and callable(getattr(node, node.FUNCTION))
+    if not torch.cuda.is_available():
+        with pytest.raises(RuntimeError, match="no CPU fallback"):
+            node().fill(torch.zeros(3, 16, 16, 3), torch.zeros(3, 16, 16))
+
+
+def test_modules_have_no_unbound_names():
+    files = [os.path.join(ROOT, "lanpaint_amd", f) for f in ("temporal_fill.py", "temporal_fill_nodes.py")]
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "scripts", "check_names.py"), *files], capture_output=True, text=True)
+    assert p.returncode == 0, p.stdout
