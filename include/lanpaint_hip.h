@@ -1874,6 +1874,62 @@ typedef struct lp_tfill_carry_desc {
 } lp_tfill_carry_desc;
 LP_API int lp_tfill_carry(const lp_tfill_carry_desc* desc, void* stream);
 
+/* Checked temporal fill.  The fill above believes the one-layer background field everywhere: when something other than the masked
+ * subject moves through the hole it borrows the wrong picture, and a wrong known pixel is worse than one left in `remaining`.
+ * Here the two directions are witnesses of one another: where both have an origin for a pixel and their samples disagree over a
+ * block, the block is left to the sampler.  Stages 1 to 4 stay word for word; the forward pass is lp_tfill_carry with nearer = 0,
+ * unchanged.  After it a masked pixel p of frame t with source[t](p) = f_A >= 0 has witness A, and S_A = filled[t](p) is its
+ * sample.  The backward pass is one launch of lp_tfill_carry_pair per step t <- t + 1 (donor = frame + 1), t = F - 2 .. 0:
+ * 1 witness B   Stage 3 gives B, the backward origin (f_B, P_B), reach applied as there; S_B is its stage-"sample" value.  The
+ *               state written for the next step (org_dst, pos_dst) is exactly what lp_tfill_carry writes: a dispute never alters
+ *               what is carried.
+ * 2 luma        both = masked and has A and has B.  Y_A, Y_B are the propagate section's 8-bit luma codes of S_A and S_B (stage
+ *               "1 luma" there: a NaN gives 0, +inf 255; channels 1 or 2 take channel 0);  d = Y_B - Y_A.
+ * 3 block flag  per block of LP_PROP_BLOCK x LP_PROP_BLOCK pixels, aligned to the plane's origin and cut at its edges (no halo):
+ *               M = the block's `both` pixels, n = |M|.  n < LP_PROP_MIN_PIXELS: the flag is 0, for lack of evidence.  Else
+ *               D = sum over M of d; mu = floor((2 D + n) / (2 n)), the mathematical floor, clamped to +-LP_PROP_VIS_MAX_BIAS (a
+ *               brightness bias between the two frames is forgiven); R = sum over M of |d - mu|; the flag is 1 (disputed) iff
+ *               R > agree * n, with agree in 1..255 the mean residual in grey levels.  The arithmetic of lp_prop_visible, on
+ *               integers: the order of the sums cannot matter.
+ * 4 per masked pixel
+ *               disputed (both and flag 1): filled = images[t], source = -2 (LP_TFILL_DISPUTED), remaining = 1.0, witnesses = 0;
+ *               both and flag 0: stage 4's choice, B is written iff |t - f_B| < |t - f_A| (a tie stays with the past);
+ *                                witnesses = 2 when n >= LP_PROP_MIN_PIXELS, else 1;
+ *               only A: left as it is, witnesses = 1;     only B: B is written as in stage 4, witnesses = 1;
+ *               neither: remaining = 1.0, witnesses = 0.  A known pixel has witnesses = 0.
+ *               witnesses int32 [frames, height, width]: the launch writes every pixel of plane t, known ones included.
+ * Frame F - 1 has no backward step, so A alone counts there: witnesses = 1 where it is masked and source >= 0, else 0 (the
+ * caller's, from `source`, on the device).
+ * What follows from the rule: wherever source != -2 the outputs filled, remaining and source carry the bits of the plain fill on
+ * the same arguments; wherever source == -2 the plain fill had source >= 0 and the checked one returns images; remaining = 1.0
+ * exactly where m = 1 and source < 0; the same bits on every run and for every chunking of the fields.
+ * Launch (csrc/temporal_fill_kernel.hip): the carry's geometry, a block of 1024 lanes per 32 x 32 tile -- exactly 16 aligned
+ * blocks of 8 x 8, so no sum crosses a tile -- that leaves after reading its known bytes (and writing witnesses = 0) when all are
+ * 1.  Else two integer reductions per block in LDS, n and D packed in one word, then R, a barrier between them; every lane of the
+ * tile reaches both.  The B sample is gathered wherever B exists, not only where it is nearer.  No scratch, no global atomics.
+ * LP_E_INVALID: as lp_tfill_carry, and donor != frame + 1, agree outside 1..255, a null witnesses, witnesses aliasing any other
+ * plane.  LP_E_UNSUPPORTED: frames > 65535.  All checked before any HIP call.                                                    */
+#define LP_TFILL_DISPUTED   (-2)
+
+typedef struct lp_tfill_carry_pair_desc {
+    int32_t frames, height, width, channels;
+    int32_t frame, donor;                         /* t and t + 1                                                            */
+    int32_t reach, agree;                         /* agree 1..255                                                           */
+    const int32_t* vec;                           /* as in lp_tfill_carry_desc                                              */
+    const uint8_t* known;
+    const uint8_t* donor_known;
+    const int32_t* org_src;
+    const int32_t* pos_src;
+    int32_t*       org_dst;
+    int32_t*       pos_dst;
+    const float*   images;
+    float*         filled;                        /* in / out: frame t holds S_A where A exists; only the own pixel is touched */
+    int32_t*       source;                        /* in / out: frame t holds f_A, -1 or t                                   */
+    float*         remaining;                     /* in / out: frame t is written                                           */
+    int32_t*       witnesses;                     /* out, [frames, height, width]: frame t is written, every pixel          */
+} lp_tfill_carry_pair_desc;
+LP_API int lp_tfill_carry_pair(const lp_tfill_carry_pair_desc* desc, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

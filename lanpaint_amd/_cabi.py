@@ -482,6 +482,17 @@ class LpTfillCarryDesc(C.Structure):
                 ("filled", C.c_void_p), ("source", C.c_void_p), ("remaining", C.c_void_p)]
 
 
+LP_TFILL_DISPUTED = -2
+
+
+class LpTfillCarryPairDesc(C.Structure):
+    _fields_ = [("frames", C.c_int32), ("height", C.c_int32), ("width", C.c_int32), ("channels", C.c_int32),
+                ("frame", C.c_int32), ("donor", C.c_int32), ("reach", C.c_int32), ("agree", C.c_int32),
+                ("vec", C.c_void_p), ("known", C.c_void_p), ("donor_known", C.c_void_p), ("org_src", C.c_void_p),
+                ("pos_src", C.c_void_p), ("org_dst", C.c_void_p), ("pos_dst", C.c_void_p), ("images", C.c_void_p),
+                ("filled", C.c_void_p), ("source", C.c_void_p), ("remaining", C.c_void_p), ("witnesses", C.c_void_p)]
+
+
 def prop_level_shape(height, width, level):
     """Level `level` of a height x width plane: ceil(height / 2^level) x ceil(width / 2^level)."""
     return (int(height) + (1 << level) - 1) >> level, (int(width) + (1 << level) - 1) >> level
@@ -609,6 +620,7 @@ EXPORTS = {
     "lp_prop_merge_visible": (C.c_int, [C.POINTER(LpPropMergeVisibleDesc), C.c_void_p]),
     "lp_tfill_known": (C.c_int, [C.POINTER(LpTfillKnownDesc), C.c_void_p]),
     "lp_tfill_carry": (C.c_int, [C.POINTER(LpTfillCarryDesc), C.c_void_p]),
+    "lp_tfill_carry_pair": (C.c_int, [C.POINTER(LpTfillCarryPairDesc), C.c_void_p]),
 }
 
 

@@ -11,6 +11,9 @@
 //                between go to LDS; a masked pixel follows its vector into the donor, takes over the donor's origin (implicit under
 //                the donor's known pixels, a stored plane under its mask) and, where the pass writes, samples the origin's frame:
 //                a gather bound by memory.  The arguments travel by value.
+//   carry pair   the checked form's backward step (lp_tfill_carry_pair): the carry, with the forward pass's sample as a second
+//                witness.  Where both exist their lumas are compared per 8 x 8 block, two integer sums through LDS, and a block
+//                that disagrees is handed back to `remaining`.  The backward sample is gathered wherever it exists.
 // Integer arithmetic decides everything but the sample, which is fp32 in a fixed order, every operation rounded on its own
 // (__fmul_rn / __fadd_rn: nothing contracts).  No scratch, no atomics.
 #include "lp_common.h"
@@ -161,6 +164,189 @@ __global__ __launch_bounds__(kTile * kTile) void lp_tfill_carry_kernel(const car
     a.remaining[p] = 0.0f;
 }
 
+// ---- carry, checked: the backward step with the forward pass as second witness -------------------------------------------------------
+struct pair_args {
+    carry_args c;                // nearer is not read: the step is the backward one
+    int32_t*   witnesses;        // frame t's plane
+    int32_t    agree;
+};
+
+__device__ __forceinline__ int code_of(float v) {                       // the propagate section's 8-bit code; a NaN gives 0
+    const float t = v > 0.0f ? (v < 1.0f ? v : 1.0f) : 0.0f;
+    return static_cast<int>(__fadd_rn(__fmul_rn(t, 255.0f), 0.5f));
+}
+
+__device__ __forceinline__ int luma_of(float c0, float c1, float c2, int C) {
+    const int y = code_of(c0);
+    return C >= 3 ? (77 * y + 150 * code_of(c1) + 29 * code_of(c2) + 128) >> 8 : y;
+}
+
+// over the 8 lanes of one row of an 8 x 8 block: lane = 32 (ly & 1) + lx, so the xor stays inside the aligned group of 8
+__device__ __forceinline__ int sum8(int v) {
+    v += __shfl_xor(v, 1);
+    v += __shfl_xor(v, 2);
+    v += __shfl_xor(v, 4);
+    return v;
+}
+
+// Where a frame's origin is sampled: the two rows of taps of stage "sample"
+struct tap_rows {
+    const float* r0;
+    const float* r1;
+    int nx, gy, gx;
+};
+
+__device__ __forceinline__ tap_rows taps_of(const carry_args& a, int f, int Py, int Px) {
+    const int cy = clampi(Py, 0, 16 * (a.H - 1)), cx = clampi(Px, 0, 16 * (a.W - 1));
+    const int sy = cy >> 4, sx = cx >> 4;
+    tap_rows t;
+    t.gy = cy & 15;
+    t.gx = cx & 15;
+    t.r0 = a.images + ((static_cast<int64_t>(f) * a.H + sy) * a.W + sx) * a.C;
+    t.r1 = t.r0 + (t.gy ? static_cast<int64_t>(a.W) * a.C : 0);
+    t.nx = t.gx ? a.C : 0;
+    return t;
+}
+
+// channels c0 .. c0 + 3 of the sample (0 beyond C): the four channels' taps are asked for before the first is used
+__device__ __forceinline__ void sample4(const tap_rows& t, int C, int c0, float (&v)[4]) {
+    float t00[4], t01[4], t10[4], t11[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const bool in = c0 + k < C;
+        t00[k] = in ? t.r0[c0 + k] : 0.0f;
+        t01[k] = in && t.gx ? t.r0[t.nx + c0 + k] : 0.0f;
+        t10[k] = in && t.gy ? t.r1[c0 + k] : 0.0f;
+        t11[k] = in && t.gy && t.gx ? t.r1[t.nx + c0 + k] : 0.0f;
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const float top = lerp16(t00[k], t01[k], t.gx);
+        const float s = t.gy == 0 ? __fmul_rn(16.0f, top)
+                                  : __fadd_rn(__fmul_rn(static_cast<float>(16 - t.gy), top), __fmul_rn(static_cast<float>(t.gy), lerp16(t10[k], t11[k], t.gx)));
+        v[k] = __fmul_rn(s, 1.0f / 256.0f);
+    }
+}
+
+// The carry's geometry.  A tile is 4 x 4 aligned blocks of 8 x 8, block b = 4 (ly >> 3) + (lx >> 3); its two sums go through s_nd
+// (n in the low byte, D above it: n <= 64, so the arithmetic shift gives D back) and s_r.  No lane leaves between the barriers.
+__global__ __launch_bounds__(kTile * kTile) void lp_tfill_carry_pair_kernel(const pair_args g) {
+    __shared__ int32_t s_v[kTileBlocks * kTileBlocks * 2];
+    __shared__ int32_t s_nd[(kTile / kB) * (kTile / kB)], s_r[(kTile / kB) * (kTile / kB)];
+    const carry_args& a = g.c;
+    const int H = a.H, W = a.W, C = a.C;
+    const int ly = threadIdx.x >> 5, lx = threadIdx.x & 31, y = blockIdx.y * kTile + ly, x = blockIdx.x * kTile + lx;
+    const int64_t p = static_cast<int64_t>(y) * W + x;
+    const bool inside = y < H && x < W;
+    const bool masked = inside && a.known[p] == 0;
+    if (threadIdx.x < (kTile / kB) * (kTile / kB)) s_nd[threadIdx.x] = s_r[threadIdx.x] = 0;
+    if (__syncthreads_and(!masked)) {                                    // the whole block: nothing under a mask here
+        if (inside) g.witnesses[p] = 0;
+        return;
+    }
+    if (threadIdx.x < kTileBlocks * kTileBlocks) {
+        const int j = threadIdx.x / kTileBlocks, i = threadIdx.x - j * kTileBlocks;
+        const int by = clampi(static_cast<int>(blockIdx.y) * (kTile / kB) - 1 + j, 0, a.gh - 1);
+        const int bx = clampi(static_cast<int>(blockIdx.x) * (kTile / kB) - 1 + i, 0, a.gw - 1);
+        const int32_t* v = a.vec + (static_cast<int64_t>(by) * a.gw + bx) * 2;
+        s_v[threadIdx.x * 2] = v[0];
+        s_v[threadIdx.x * 2 + 1] = v[1];
+    }
+    __syncthreads();
+    // witness B: stage 3 as lp_tfill_carry_kernel has it.  A's frame and the first channels of its sample are asked for up front.
+    int f = -1, Py = 0, Px = 0, cur = -1;
+    float fa[3] = {0.0f, 0.0f, 0.0f};
+    if (masked) {
+        cur = a.source[p];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) fa[k] = k < C ? a.filled[p * C + k] : 0.0f;
+        const int uy = 2 * ly + 9, ux = 2 * lx + 9;
+        const int jy = uy >> 4, jx = ux >> 4, fy = uy & 15, fx = ux & 15;
+        const int32_t *v00 = s_v + (jy * kTileBlocks + jx) * 2, *v01 = v00 + 2, *v10 = v00 + kTileBlocks * 2, *v11 = v10 + 2;
+        const int Vy = ((16 - fy) * ((16 - fx) * v00[0] + fx * v01[0]) + fy * ((16 - fx) * v10[0] + fx * v11[0]) + 128) >> 8;
+        const int Vx = ((16 - fy) * ((16 - fx) * v00[1] + fx * v01[1]) + fy * ((16 - fx) * v10[1] + fx * v11[1]) + 128) >> 8;
+        const int qy = 16 * y + Vy, qx = 16 * x + Vx;
+        if (qy >= 0 && qy <= 16 * (H - 1) && qx >= 0 && qx <= 16 * (W - 1)) {
+            const int iy = (qy + 8) >> 4, ix = (qx + 8) >> 4;
+            const int64_t dp = static_cast<int64_t>(iy) * W + ix;
+            const uint8_t dk = a.donor_known[dp];
+            const int sf = a.org_src ? a.org_src[dp] : -1;
+            const int spy = a.org_src ? a.pos_src[dp * 2] : 0, spx = a.org_src ? a.pos_src[dp * 2 + 1] : 0;
+            f = dk ? a.donor : sf;
+            Py = dk ? 16 * iy : spy;
+            Px = dk ? 16 * ix : spx;
+            if (f >= 0 && f < a.frames && abs(a.t - f) <= a.reach) {
+                Py += qy - 16 * iy;
+                Px += qx - 16 * ix;
+            } else {
+                f = -1;
+            }
+        }
+        a.org_dst[p] = f;
+        a.pos_dst[p * 2] = f >= 0 ? Py : 0;
+        a.pos_dst[p * 2 + 1] = f >= 0 ? Px : 0;
+    }
+    const bool has_b = f >= 0, both = has_b && cur >= 0;
+    tap_rows taps = {};
+    float sb[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    if (has_b) {
+        taps = taps_of(a, f, Py, Px);
+        sample4(taps, C, 0, sb);
+    }
+    const int d = both ? luma_of(sb[0], sb[1], sb[2], C) - luma_of(fa[0], fa[1], fa[2], C) : 0;
+    const int b = (ly >> 3) * (kTile / kB) + (lx >> 3);
+    const int nd_row = sum8(both ? d * 256 + 1 : 0);
+    if ((lx & 7) == 0 && nd_row != 0) atomicAdd(&s_nd[b], nd_row);
+    __syncthreads();
+    const int nd = s_nd[b], n = nd & 255, D = nd >> 8;
+    const bool enough = n >= LP_PROP_MIN_PIXELS;
+    int mu = 0;
+    if (enough) {
+        const int num = 2 * D + n, den = 2 * n;
+        mu = num / den;
+        if (num - mu * den < 0) --mu;                                    // the mathematical floor
+        mu = clampi(mu, -LP_PROP_VIS_MAX_BIAS, LP_PROP_VIS_MAX_BIAS);
+    }
+    const int r_row = sum8(both && enough ? abs(d - mu) : 0);
+    if ((lx & 7) == 0 && r_row != 0) atomicAdd(&s_r[b], r_row);
+    __syncthreads();
+    if (!masked) {                                                       // known, or outside the plane
+        if (inside) g.witnesses[p] = 0;
+        return;
+    }
+    const bool disputed = both && enough && s_r[b] > g.agree * n;
+    int wit = 0;
+    if (disputed) {
+        const float* __restrict__ own = a.images + (static_cast<int64_t>(a.t) * H * W + p) * C;
+        float* __restrict__ out = a.filled + p * C;
+#pragma unroll 1
+        for (int c = 0; c < C; ++c) out[c] = own[c];
+        a.source[p] = LP_TFILL_DISPUTED;
+        a.remaining[p] = 1.0f;
+    } else if (has_b && (cur < 0 || abs(a.t - f) < abs(a.t - cur))) {    // nearer: a tie stays with what is there
+        float* __restrict__ out = a.filled + p * C;
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            if (k < C) out[k] = sb[k];
+#pragma unroll 1
+        for (int c0 = 4; c0 < C; c0 += 4) {
+            float v[4];
+            sample4(taps, C, c0, v);
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                if (c0 + k < C) out[c0 + k] = v[k];
+        }
+        a.source[p] = f;
+        a.remaining[p] = 0.0f;
+        wit = both && enough ? 2 : 1;
+    } else if (cur >= 0) {
+        wit = both && enough ? 2 : 1;
+    } else {
+        a.remaining[p] = 1.0f;
+    }
+    g.witnesses[p] = wit;
+}
+
 bool side_ok(int s) { return s > 0 && s <= LP_VMASK_MAX_SIDE; }
 bool levels_ok(int l) { return l >= 1 && l <= LP_PROP_MAX_LEVELS; }
 int launched() { return hipGetLastError() == hipSuccess ? LP_OK : LP_E_LAUNCH; }
@@ -238,6 +424,55 @@ int tfill_carry_dispatch(const lp_tfill_carry_desc* dp, hipStream_t stream) {
     a.reach = d.reach ? d.reach : LP_TFILL_MAX_REACH;                    // 0: the whole clip; frames <= 65535, so no age exceeds it
     a.nearer = d.nearer;
     hipLaunchKernelGGL(lp_tfill_carry_kernel, dim3(blocks_of(d.width, kTile), blocks_of(d.height, kTile)), dim3(kTile * kTile), 0, stream, a);
+    return launched();
+}
+
+int tfill_carry_pair_dispatch(const lp_tfill_carry_pair_desc* dp, hipStream_t stream) {
+    if (!dp) return LP_E_INVALID;
+    const lp_tfill_carry_pair_desc& d = *dp;
+    if (d.frames < 2 || !side_ok(d.height) || !side_ok(d.width) || d.channels < 1 || d.channels > LP_DETAIL_MAX_CHANNELS) return LP_E_INVALID;
+    if (d.reach < 0 || d.reach > LP_TFILL_MAX_REACH || d.agree < 1 || d.agree > 255) return LP_E_INVALID;
+    if (d.frames > 65535) return LP_E_UNSUPPORTED;
+    if (d.frame < 0 || d.donor >= d.frames || d.donor != d.frame + 1) return LP_E_INVALID;
+    if (!d.vec || !d.known || !d.donor_known || !d.org_dst || !d.pos_dst || !d.images || !d.filled || !d.source || !d.remaining ||
+        !d.witnesses)
+        return LP_E_INVALID;
+    if ((d.org_src == nullptr) != (d.pos_src == nullptr)) return LP_E_INVALID;
+    const void *outs[6] = {d.org_dst, d.pos_dst, d.filled, d.source, d.remaining, d.witnesses};
+    const void *in[6] = {d.vec, d.known, d.donor_known, d.org_src, d.pos_src, d.images};
+    for (int k = 0; k < 6; ++k) {
+        for (const void* p : in)
+            if (outs[k] == p) return LP_E_INVALID;
+        for (int m = k + 1; m < 6; ++m)
+            if (outs[k] == outs[m]) return LP_E_INVALID;
+    }
+    const int64_t plane = static_cast<int64_t>(d.height) * d.width;
+    pair_args g = {};
+    carry_args& a = g.c;
+    a.vec = d.vec;
+    a.known = d.known;
+    a.donor_known = d.donor_known;
+    a.org_src = d.org_src;
+    a.pos_src = d.pos_src;
+    a.org_dst = d.org_dst;
+    a.pos_dst = d.pos_dst;
+    a.images = d.images;
+    a.filled = d.filled + d.frame * plane * d.channels;
+    a.source = d.source + d.frame * plane;
+    a.remaining = d.remaining + d.frame * plane;
+    a.H = d.height;
+    a.W = d.width;
+    a.C = d.channels;
+    a.gh = (d.height + kB - 1) / kB;
+    a.gw = (d.width + kB - 1) / kB;
+    a.frames = d.frames;
+    a.t = d.frame;
+    a.donor = d.donor;
+    a.reach = d.reach ? d.reach : LP_TFILL_MAX_REACH;
+    a.nearer = 1;
+    g.witnesses = d.witnesses + d.frame * plane;
+    g.agree = d.agree;
+    hipLaunchKernelGGL(lp_tfill_carry_pair_kernel, dim3(blocks_of(d.width, kTile), blocks_of(d.height, kTile)), dim3(kTile * kTile), 0, stream, g);
     return launched();
 }
 

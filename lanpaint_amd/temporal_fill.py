@@ -18,7 +18,7 @@ temporal_fill(images, mask, levels=4, search=2, smooth=8, reach=0) -> (filled, r
         a full mask returns the images; a subject that does not move against its background stays in `remaining`; under
         noise-free whole-pixel motion the borrowed pixels are the true background bit for bit; nothing outside the mask changes.
         include/lanpaint_hip.h (lp_tfill_*) states the rule in full.  Not done: colour or exposure matching of what is borrowed
-        (DetailerColorMatch exists), a consistency check on it, motion boundaries finer than a block.
+        (DetailerColorMatch exists), motion boundaries finer than a block; the consistency check on it is temporal_fill_checked's.
 
 HIP tensors only, no CPU fallback, no device -> host read.  A step's field depends on its two frames and one mask only, so the
 2 (F - 1) fields of a clip are independent jobs of lp_prop_match_batch / lp_prop_fill_batch, 32 to a launch; only the carry, one

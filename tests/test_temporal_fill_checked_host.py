@@ -1,0 +1,356 @@
+"""The checked video temporal fill, the parts that need no device: what the rule promises, on the two restatements
+(tests/temporal_fill_ref.py, tests/temporal_fill_checked_ref.py), as bits and counts; that the case of the device's stage test
+reaches every branch of the rule; the C entry's argument checks (made before any HIP call), the descriptor's layout against the
+header as gcc reads it, the names' presence everywhere, the wrappers' argument checks, the node's protocol and the no-fallback
+errors."""
+import ctypes
+import functools
+import os
+import re
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+from lanpaint_amd import _cabi
+from tests import propagate_ref as ref
+from tests import temporal_fill_checked_ref as cref
+from tests import temporal_fill_ref as tref
+from tests.test_gpu_propagate import _rng, _video, _wild_video
+from tests.test_temporal_fill_host import pan_clip, still_clip
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+ENTRY = "lp_tfill_carry_pair"
+F = 5                                                                  # the stage case: frame 2 of 5, its donor frame 3
+
+
+def _bits(a):
+    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
+
+
+# ---- the scenes; tests/test_gpu_temporal_fill_checked.py runs the device on the same ones --------------------------------------------
+@functools.lru_cache(maxsize=None)
+def second_object_clip():
+    """(boxless clip, clip, mask): 10 frames of 64 x 96 x 3 on one still random canvas; a second object, a 40 x 40 texture, moves
+    2 px per frame down through the path of a 12 x 12 constant box that moves 5 px per frame to the right on top of it; the mask
+    is the box grown by 1.  The one-layer background field cannot hold both motions."""
+    frames, H, W = 10, 64, 96
+    rng = np.random.default_rng(11)
+    clean = np.repeat(rng.random((1, H, W, 3), dtype=np.float32), frames, axis=0)
+    tex = rng.random((40, 40, 3), dtype=np.float32)
+    for t in range(frames):
+        clean[t, 2 * t:2 * t + 40, 36:76] = tex
+    clip, mask = clean.copy(), np.zeros((frames, H, W), np.float32)
+    for t in range(frames):
+        y, x = 26, 6 + 5 * t
+        clip[t, y:y + 12, x:x + 12] = 0.5
+        mask[t, y - 1:y + 13, x - 1:x + 13] = 1
+    return clean, clip, mask
+
+
+# what the restatements give on it at the defaults and agree = 8; the conditions these satisfy are in the test below
+SECOND_OBJECT = dict(masked=1960, plain_wrong=556, filled=1169, wrong=67, disputed=791, verified=343, verified_wrong=14)
+
+
+def second_object_counts(plain, checked):
+    """The counts of SECOND_OBJECT from the outputs of the plain and the checked call on the clip.  Wrong: a borrowed pixel whose
+    bits differ from the clip drawn without the box."""
+    clean, _, mask = second_object_clip()
+    m = mask == 1
+    (pf, _, ps), (cf, cr, cs, cw) = plain, checked
+    plain_wrong = (_bits(pf) != _bits(clean)).any(-1) & m & (ps >= 0)
+    wrong = (_bits(cf) != _bits(clean)).any(-1) & m & (cs >= 0)
+    assert ((cr == 1) == (m & (cs < 0))).all()
+    return dict(masked=int(m.sum()), plain_wrong=int(plain_wrong.sum()), filled=int((m & (cs >= 0)).sum()), wrong=int(wrong.sum()),
+                disputed=int((cs == cref.DISPUTED).sum()), verified=int((cw == 2).sum()), verified_wrong=int((wrong & (cw == 2)).sum()))
+
+
+@functools.lru_cache(maxsize=None)
+def clean_clip(name, noisy):
+    """(clip, mask) of `pan_clip()` or `still_clip(2)`, with Gaussian noise of sigma 4 grey levels on every frame when `noisy`."""
+    _, clip, mask = pan_clip() if name == "pan" else still_clip(2)
+    if noisy:
+        clip = (clip + np.random.default_rng(3).normal(0, 4 / 255, clip.shape)).astype(np.float32)
+    return clip, mask
+
+
+CLEAN_CLIPS = [("pan", False), ("still", False), ("pan", True), ("still", True)]
+
+
+@functools.lru_cache(maxsize=None)
+def random_clip():
+    """A random moving video of 5 x 40 x 70 x 3 under random masks: every pixel class, disputes included."""
+    images = _video(F, 40, 70)
+    mask = (_rng(F, 40, 70, 0, 5).random((F, 40, 70)) < 0.3).astype(np.float32)
+    return images, mask
+
+
+def check_invariant(images, plain, checked, what):
+    """What follows from the rule, between a plain and a checked result on the same arguments."""
+    (pf, pr, ps), (cf, cr, cs, cw) = plain, checked
+    agreed, nan = cs != cref.DISPUTED, np.isnan(pf)
+    assert (cs[agreed] == ps[agreed]).all() and (_bits(cr)[agreed] == _bits(pr)[agreed]).all(), what
+    assert (((_bits(cf) == _bits(pf)) | (nan & np.isnan(cf)))[agreed]).all(), what
+    assert (ps[~agreed] >= 0).all(), what
+    assert ((_bits(cf) == _bits(images)) | np.isnan(images))[~agreed].all(), what
+    masked = pr.astype(bool) | (ps != np.arange(len(ps))[:, None, None])          # the plain call's mask bits
+    assert ((cr == 1) == (masked & (cs < 0))).all() and ((cr == 0) | (cr == 1)).all(), what
+    assert (cw[~masked] == 0).all() and (cw[cs < 0] == 0).all() and ((cw >= 1) == (masked & (cs >= 0))).all() and cw.max() <= 2, what
+
+
+# ---- the case of the device's stage test ----------------------------------------------------------------------------------------------
+@functools.lru_cache(maxsize=None)
+def pair_case(H, W, wild=False, C=3):
+    """Frame 2 of 5 with its donor 3: random known bits of both, of the frame a quarter to three quarters by block, a random field of up to 2.5 pixels, a random state of the donor
+    with origins in every frame, a random forward `source` under the mask and a forward `filled` that is, block by block, the
+    backward sample itself, that sample darker or brighter by 0.3 or by 0.05, or noise.
+    (images, vec, known [2, H, W], org, pos, source_t, filled_t)."""
+    rng = _rng(H, W, int(wild), C, 8)
+    images = (_wild_video if wild else _video)(F, H, W, C)
+    gh, gw = ref.grid_of(H, W)
+    vec = rng.integers(-40, 41, (gh, gw, 2)).astype(np.int32)
+    share = cref.per_pixel(rng.choice([0.25, 0.5, 0.75], (gh, gw)), H, W)   # so that a block holds few or many pixels to compare
+    known = (rng.random((2, H, W)) < np.stack([share, np.full((H, W), 0.5)])).astype(np.uint8)
+    org = rng.integers(-1, F, (H, W)).astype(np.int32)
+    pos = np.stack([rng.integers(-40, 16 * H + 40, (H, W)), rng.integers(-40, 16 * W + 40, (H, W))], axis=-1).astype(np.int32)
+    source = np.where(known[0] != 0, 2, rng.choice([-1, 0, 1, 3, 4], (H, W))).astype(np.int32)
+    b_org, b_pos = tref.carry(2, known[0], 3, known[1], vec, (org, pos), 0)
+    has_b = (known[0] == 0) & (b_org >= 0)
+    filled = images[2].copy()
+    filled[has_b] = tref.sample(images, b_org[has_b], b_pos[has_b][:, 0], b_pos[has_b][:, 1])
+    mode = cref.per_pixel(rng.integers(0, 5, (gh, gw)), H, W)
+    with np.errstate(invalid="ignore"):
+        filled = filled + np.choose(mode, [0, -0.3, 0.3, 0, 0.05]).astype(np.float32)[..., None] + rng.normal(0, 0.004, filled.shape)
+    filled = np.where((mode == 3)[..., None], rng.random(filled.shape), filled).astype(np.float32)
+    filled = np.where((known[0] != 0)[..., None], images[2], filled)
+    return images, vec, known, org, pos, source, filled
+
+
+def pair_want(case, state, reach, agree, stats=None):
+    """What the step must leave for `case`: the state (org, pos) and frame 2's (filled, source, remaining, witnesses)."""
+    images, vec, known, org, pos, source, filled = case
+    b_org, b_pos = tref.carry(2, known[0], 3, known[1], vec, (org, pos) if state else None, reach)
+    remaining = ((known[0] == 0) & (source == -1)).astype(np.float32)
+    return (b_org, b_pos), cref.pair(2, known[0], images, b_org, b_pos, filled, source, remaining, agree, stats)
+
+
+@pytest.mark.parametrize("plane", [(40, 70), (23, 33)], ids=lambda s: "x".join(map(str, s)))
+def test_the_stage_case_reaches_every_branch_of_the_rule(plane):
+    H, W = plane
+    stats = {}
+    _, (filled, source, remaining, witnesses) = pair_want(pair_case(H, W), True, 0, 8, stats)
+    n, mu, flag = stats["n"], stats["mu"], stats["flag"]
+    for name in ("both", "only_a", "only_b", "neither", "disputed"):
+        assert stats[name].any(), name
+    assert (flag == 0).any() and (flag == 1).any() and ((flag == 0) & (n >= cref.MIN_PIXELS)).any()
+    assert ((n > 0) & (n < cref.MIN_PIXELS)).any() and (flag[n < cref.MIN_PIXELS] == 0).all()
+    assert set(np.unique(witnesses)) == {0, 1, 2} and (source == cref.DISPUTED).any()
+    # the unclamped bias of a tested block, from d itself
+    raw = np.zeros_like(mu)
+    for by, bx in np.argwhere(n >= cref.MIN_PIXELS):
+        win = (slice(8 * by, 8 * by + 8), slice(8 * bx, 8 * bx + 8))
+        raw[by, bx] = (2 * int(stats["d"][win][stats["both"][win]].sum()) + n[by, bx]) // (2 * n[by, bx])
+    assert (mu == np.clip(raw, -32, 32)).all()
+    if plane == (40, 70):
+        assert (n == cref.MIN_PIXELS).any()                            # at the threshold, and below it above
+        assert ((raw > 32) & (mu == 32)).any() and ((raw < -32) & (mu == -32)).any()
+        assert W % 8 and flag[:, -1].any()                             # a disputed block cut by the plane's right edge
+    else:
+        assert H % 8 and W % 8 and (n[-1] >= cref.MIN_PIXELS).any()   # a tested block cut by the plane's lower edge
+    # under agree = 255 nothing is disputed, under agree = 1 more is
+    for agree, cmp in ((255, lambda a, b: a == 0), (1, lambda a, b: a >= b)):
+        other = {}
+        pair_want(pair_case(H, W), True, 0, agree, other)
+        assert cmp(int(other["flag"].sum()), int(flag.sum())), agree
+
+
+def test_block_statistics_one_block_at_a_time():
+    both = np.zeros((9, 20), bool)
+    d = np.zeros((9, 20), np.int64)
+    both[:2, :8], d[:2, :8] = True, 40                                 # 16 pixels, all 40 above: mu clamps at 32, R = 16 * 8
+    both[:2, 8:16], d[:2, 8:16] = True, -3                             # a small bias is forgiven entirely
+    both[:2, 16:], d[:2, 16:] = True, 100                              # 8 pixels of a block cut by the edge: not enough
+    both[8, :8], d[8, :8] = True, 100                                  # a row of the bottom blocks, 8 pixels
+    n, mu, R, flag = cref.block_stats(both, d, 8)
+    assert n.tolist() == [[16, 16, 8], [8, 0, 0]] and mu.tolist() == [[32, -3, 0], [0, 0, 0]]
+    assert R.tolist() == [[128, 0, 0], [0, 0, 0]] and flag.tolist() == [[0, 0, 0], [0, 0, 0]]        # R > agree n is strict
+    assert cref.block_stats(both, d, 7)[3].tolist() == [[1, 0, 0], [0, 0, 0]]
+    d[0, :8] = -41                                                     # D = 8 * 40 - 8 * 41 = -8: floor((-16 + 16) / 32) = 0
+    assert cref.block_stats(both, d, 8)[1][0, 0] == 0
+    d[0, 0] = -42                                                      # D = -9: floor(-2 / 32) = -1, the mathematical floor
+    assert cref.block_stats(both, d, 8)[1][0, 0] == -1
+    assert cref.sample_luma(np.array([[np.nan, np.inf, -np.inf], [1, 1, 1], [0.5, 7, 7]], np.float32)).tolist() == [149, 255, 217]
+    assert cref.sample_luma(np.array([[0.5, 7], [np.nan, 1]], np.float32)).tolist() == [128, 0]
+
+
+# ---- the properties, on the restatements ----------------------------------------------------------------------------------------------
+@functools.lru_cache(maxsize=None)
+def second_object_results():
+    _, clip, mask = second_object_clip()
+    return tref.temporal_fill_ref(clip, mask), cref.temporal_fill_checked_ref(clip, mask)
+
+
+def test_the_second_object_is_disputed_rather_than_pasted():
+    counts = second_object_counts(*second_object_results())
+    assert counts["plain_wrong"] >= 400                                # the clip tests something
+    assert 4 * counts["wrong"] <= counts["plain_wrong"]                # at most a quarter as many wrong pixels
+    assert 100 * counts["verified_wrong"] <= 15 * counts["verified"]   # at most 15 % of the verified ones
+    assert counts["filled"] >= 1000                                    # and the fill still fills
+    assert counts == SECOND_OBJECT
+
+
+@pytest.mark.parametrize("scene", ["second object", "pan", "still", "random"])
+def test_outside_a_dispute_the_checked_fill_is_the_plain_fill(scene):
+    if scene == "second object":
+        images, mask = second_object_clip()[1:]
+        plain, checked = second_object_results()
+    else:
+        images, mask = random_clip() if scene == "random" else clean_clip(scene, False)
+        levels = 3 if scene == "random" else 4
+        plain, checked = tref.temporal_fill_ref(images, mask, levels), cref.temporal_fill_checked_ref(images, mask, levels)
+    check_invariant(images, plain, checked, scene)
+    if scene in ("second object", "random"):
+        assert (checked[2] == cref.DISPUTED).any() and (checked[3] == 2).any() and (checked[3] == 1).any()
+
+
+@pytest.mark.parametrize("name,noisy", CLEAN_CLIPS)
+def test_clean_geometry_is_never_disputed_with_and_without_noise(name, noisy):
+    clip, mask = clean_clip(name, noisy)
+    plain, checked = tref.temporal_fill_ref(clip, mask), cref.temporal_fill_checked_ref(clip, mask)
+    check_clean(plain, checked)
+
+
+def check_clean(plain, checked):
+    assert not (checked[2] == cref.DISPUTED).any() and (checked[3] == 2).any()
+    for p, c in zip(plain, checked):
+        assert (_bits(p) == _bits(c)).all() if p.dtype == np.float32 else (p == c).all()
+
+
+def test_one_and_two_frames_and_the_last_frame():
+    rng = np.random.default_rng(7)
+    video = rng.random((3, 16, 17, 3), dtype=np.float32)
+    mask = (rng.random((3, 16, 17)) < 0.4).astype(np.float32)
+    filled, remaining, source, witnesses = cref.temporal_fill_checked_ref(video[:1], mask[:1], 3)
+    assert (_bits(filled) == _bits(video[:1])).all() and (remaining == mask[:1]).all() and not witnesses.any()
+    for frames in (2, 3):
+        plain = tref.temporal_fill_ref(video[:frames], mask[:frames], 3)
+        checked = cref.temporal_fill_checked_ref(video[:frames], mask[:frames], 3)
+        check_invariant(video[:frames], plain, checked, frames)
+        last = frames - 1                                              # no backward step: one witness at the most, no dispute
+        assert (checked[3][last] == ((mask[last] == 1) & (checked[2][last] >= 0))).all() and (checked[2][last] >= -1).all()
+
+
+# ---- the C ABI ------------------------------------------------------------------------------------------------------------------------
+def test_entry_rejects_bad_arguments_without_a_device(hip_lib):
+    C, E, U = ctypes, _cabi.LP_E_INVALID, _cabi.LP_E_UNSUPPORTED
+    side = _cabi.LP_VMASK_MAX_SIDE
+    a = [C.c_void_p(4096 * (i + 1)) for i in range(12)]               # never dereferenced: validation comes before any HIP call
+    names = [f for f, t in _cabi.LpTfillCarryPairDesc._fields_ if t is C.c_void_p]
+    good = dict(frames=5, height=40, width=70, channels=3, frame=2, donor=3, reach=0, agree=8, **dict(zip(names, a)))
+    call = lambda **change: hip_lib.lp_tfill_carry_pair(C.byref(_cabi.LpTfillCarryPairDesc(**{**good, **change})), None)   # noqa: E731
+    assert len(names) == 12 and names[-1] == "witnesses" and hip_lib.lp_tfill_carry_pair(None, None) == E
+    for change in ({"frames": 1}, {"frames": 0}, {"height": 0}, {"height": side + 1}, {"width": 0}, {"width": side + 1},
+                   {"channels": 0}, {"channels": _cabi.LP_DETAIL_MAX_CHANNELS + 1}, {"reach": -1}, {"reach": _cabi.LP_TFILL_MAX_REACH + 1},
+                   {"agree": 0}, {"agree": -1}, {"agree": 256}, {"frame": -1, "donor": 0}, {"frame": 4, "donor": 5}, {"donor": 1},
+                   {"donor": 2}, {"donor": 4}, {"frame": 5, "donor": 6}, {"org_src": None}, {"pos_src": None}):
+        assert call(**change) == E, change
+    for name in names:
+        if name not in ("org_src", "pos_src"):                         # the donor's state: both null is "none"
+            assert call(**{name: None}) == E, name
+    for out in ("org_dst", "pos_dst", "filled", "source", "remaining", "witnesses"):    # an output that is an input or another output
+        for other in names:
+            if other != out:
+                assert call(**{out: good[other]}) == E, (out, other)
+    assert call(frames=65536) == U
+
+
+def test_descriptor_layout_and_constants_match_c(tmp_path):
+    py = _cabi.LpTfillCarryPairDesc
+    prog = ['#include <stdio.h>', '#include <stddef.h>', '#include "lanpaint_hip.h"', "int main(void){"]
+    prog += [f'printf("%zu ", offsetof(lp_tfill_carry_pair_desc, {f}));' for f, _ in py._fields_]
+    prog.append('printf("%zu\\n", sizeof(lp_tfill_carry_pair_desc));')
+    prog.append('printf("%d %d %d %d %d\\n", LP_TFILL_DISPUTED, LP_PROP_VIS_MAX_BIAS, LP_PROP_MIN_PIXELS, LP_PROP_BLOCK, LP_ABI_VERSION);'
+                ' return 0;}')
+    src, exe = tmp_path / "layout.c", tmp_path / "layout"
+    src.write_text("\n".join(prog))
+    subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
+    lines = subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.strip().split("\n")
+    assert [int(v) for v in lines[0].split()] == [getattr(py, f).offset for f, _ in py._fields_] + [ctypes.sizeof(py)]
+    assert [int(v) for v in lines[1].split()] == [_cabi.LP_TFILL_DISPUTED, _cabi.LP_PROP_VIS_MAX_BIAS, _cabi.LP_PROP_MIN_PIXELS,
+                                                  _cabi.LP_PROP_BLOCK, _cabi.ABI_VERSION]
+    assert [cref.DISPUTED, cref.MAX_BIAS, cref.MIN_PIXELS, cref.BLOCK] == [int(v) for v in lines[1].split()][:4]
+
+
+def test_the_name_is_everywhere_and_the_abi_version_stays(hip_lib):
+    header = open(os.path.join(ROOT, "include", "lanpaint_hip.h")).read()
+    dynamic = subprocess.run(["nm", "-D", "--defined-only", _cabi.LIB_PATH], capture_output=True, text=True, check=True).stdout
+    assert re.search(r"LP_API\s+int\s+%s\s*\(" % ENTRY, header)
+    assert ENTRY in _cabi.EXPORTS and hasattr(hip_lib, ENTRY) and re.search(r"\bT %s$" % ENTRY, dynamic, flags=re.M)
+    assert _cabi.ABI_VERSION == 25 and hip_lib.lp_abi_version() == 25
+    for word in ("Checked temporal fill", "a dispute never alters", "mu = floor((2 D + n) / (2 n))", "R > agree * n", "source = -2",
+                 "witnesses = 2 when n >= LP_PROP_MIN_PIXELS", "wherever source != -2", "Frame F - 1 has no backward step"):
+        assert word in header, word
+
+
+# ---- the wrappers and the node --------------------------------------------------------------------------------------------------------
+def test_the_wrappers_refuse_cpu_tensors_and_bad_arguments():
+    from lanpaint_amd import temporal_fill as tf, temporal_fill_checked as tc
+    images, mask = torch.zeros(4, 16, 16, 3), torch.zeros(4, 16, 16)
+    with pytest.raises(RuntimeError, match="no CPU fallback"):
+        tc.temporal_fill_checked(images, mask)
+    with pytest.raises(RuntimeError, match="no CPU fallback"):
+        tc.temporal_fill_checked(images.numpy(), mask)
+    planes = (torch.zeros(2, 2, 2, dtype=torch.int32), torch.zeros(16, 16, dtype=torch.uint8), torch.zeros(16, 16, dtype=torch.uint8), None,
+              images, images.clone(), torch.zeros(4, 16, 16, dtype=torch.int32), mask.clone(), torch.zeros(4, 16, 16, dtype=torch.int32))
+    with pytest.raises(RuntimeError, match="no CPU fallback"):
+        tc.carry_pair(*planes, 1)
+    # the numbers are checked before the tensors are looked at
+    for bad in (dict(levels=0), dict(levels=7), dict(search=0), dict(search=8), dict(smooth=-1), dict(smooth=65), dict(reach=-1),
+                dict(reach=65536), dict(reach=1.0), dict(agree=0), dict(agree=256), dict(agree=8.0), dict(agree=True), dict(agree=None)):
+        with pytest.raises(ValueError):
+            tc.temporal_fill_checked(images, mask, **bad)
+    for bad in (dict(reach=-1), dict(reach=65536), dict(agree=0), dict(agree=256)):
+        with pytest.raises(ValueError):
+            tc.carry_pair(*planes, 1, **bad)
+    assert tc.DISPUTED == -2 and tc.MAX_AGREE == 255 and tf.WS_CAP_BYTES == 1 << 30
+    assert "temporal_fill_checked" in tf.__doc__ and "a consistency check on it" not in tf.__doc__
+
+
+def test_node_protocol_and_own_mappings():
+    import importlib
+    import pkgutil
+
+    import lanpaint_amd
+    from lanpaint_amd import temporal_fill_checked_nodes as mod, temporal_fill_nodes
+    node = mod.LanPaint_VideoTemporalFillChecked
+    assert mod.NODE_CLASS_MAPPINGS == {"LanPaint_VideoTemporalFillChecked": node}
+    assert list(mod.NODE_DISPLAY_NAME_MAPPINGS) == ["LanPaint_VideoTemporalFillChecked"]
+    others = [m.name for m in pkgutil.iter_modules(lanpaint_amd.__path__) if m.name.endswith("nodes") and m.name != "temporal_fill_checked_nodes"]
+    assert len(others) >= 13 and "temporal_fill_nodes" in others
+    for name in others:                                                # every other node module of the package
+        other = importlib.import_module("lanpaint_amd." + name)
+        if not hasattr(other, "NODE_CLASS_MAPPINGS"):                  # a module of parts that others assemble
+            continue
+        assert not set(mod.NODE_CLASS_MAPPINGS) & set(other.NODE_CLASS_MAPPINGS), name
+        assert not set(mod.NODE_DISPLAY_NAME_MAPPINGS.values()) & set(other.NODE_DISPLAY_NAME_MAPPINGS.values()), name
+    types = node.INPUT_TYPES()
+    req, plain = types["required"], temporal_fill_nodes.LanPaint_VideoTemporalFill.INPUT_TYPES()["required"]
+    assert list(types) == ["required"] and list(req) == list(plain) + ["agree"] and all(req[k] == plain[k] for k in plain)
+    assert req["agree"][0] == "INT" and req["agree"][1] == {**req["agree"][1], "default": 8, "min": 1, "max": 255}
+    for name in req:
+        assert len(req[name][1]["tooltip"]) > 20, name
+    for word in ("dispute", "disagree", "remaining", "mask fill", "encode", "Detailer", "verified", "colour-matched"):
+        assert word in node.DESCRIPTION, word
+    assert node.RETURN_TYPES == ("IMAGE", "MASK", "MASK", "MASK") and node.RETURN_NAMES == ("image", "remaining", "filled", "verified")
+    assert node.FUNCTION == "fill" and callable(getattr(node, node.FUNCTION))
+    if not torch.cuda.is_available():
+        with pytest.raises(RuntimeError, match="no CPU fallback"):
+            node().fill(torch.zeros(3, 16, 16, 3), torch.zeros(3, 16, 16))
+
+
+def test_modules_have_no_unbound_names():
+    files = [os.path.join(ROOT, "lanpaint_amd", f) for f in ("temporal_fill_checked.py", "temporal_fill_checked_nodes.py")]
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "scripts", "check_names.py"), *files], capture_output=True, text=True)
+    assert p.returncode == 0, p.stdout
