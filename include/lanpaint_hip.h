@@ -1930,6 +1930,73 @@ typedef struct lp_tfill_carry_pair_desc {
 } lp_tfill_carry_pair_desc;
 LP_API int lp_tfill_carry_pair(const lp_tfill_carry_pair_desc* desc, void* stream);
 
+/* ---- Video temporal smooth (beyond the reference) -----------------------------------------------------------------------------------
+ * The sampler invents what lies under the mask frame by frame, so texture that should be one piece of background boils from frame
+ * to frame.  This entry follows the picture's motion from every masked pixel a few frames into the past and the future, looks at
+ * what the sampler put at the same scene point there, and pulls the pixel towards the weighted mean of what agrees with it:
+ *   decode / stitch -> temporal smooth -> multiband blend -> grain match.  Grain is synthesized afterwards, which is why smoothing
+ * it away here is wanted.  Integer arithmetic decides where every sample is taken and whether it counts; the sums are fp32 in a
+ * fixed order.  Everything stays on the device.
+ *   limits    sides, channels, frames, levels, search and smooth as in the temporal fill section; radius R in
+ *             1..LP_TSMOOTH_MAX_RADIUS; tolerance 0..255 grey levels.  Positions are (y, x) pairs of int32 in 1/16 pixel; `>>` is
+ *             the arithmetic shift.
+ *   mask      m = mask >= 0.5 (a NaN gives 0: known), exactly as lp_tfill_known binarises; known = 1 - m.
+ *   fields    The field of frame u towards its neighbour v = u +- 1 is stage 2 of the temporal fill section, word for word: the
+ *             level-0 final field of the propagate section with src = the luma pyramid of u, tgt = that of v.  With motion
+ *             "background" the weights are the known pyramid of u: exactly the fields the temporal fill computes.  With motion
+ *             "picture" the weights are the pyramid of an all-known plane, every pixel weighs in: for an inpainted subject that
+ *             moves on its own.  V_{u->v}(i) is that section's "per pixel" interpolation at the integer pixel i.  The motion is the
+ *             caller's choice of fields; the entry takes the fields.
+ *   walk      per masked pixel (y, x) of frame t and per direction d in {-1, +1}.  p_0 = (16 y, 16 x).  For k = 1..R:
+ *             u = t + (k - 1) d, v = t + k d.  The chain ends if v is outside the clip.  Otherwise i = (p_{k-1} + 8) >> 4 per axis
+ *             and q = p_{k-1} + V_{u->v}(i); the chain ends if q is outside 0..16 (n - 1) on either axis.  Otherwise s_k is the
+ *             temporal fill section's `sample` of images[v] at q: the same taps, the same fp32 order, a tap with weight 0 is not
+ *             read.  The sample is accepted iff max over channels of |code(s_k[c]) - code(x[c])| <= tolerance, with
+ *             x = images[t, y, x] and code the project's 8-bit code: clamp to 0..1 with NaN -> 0, then (int)(v * 255.0f + 0.5f),
+ *             product and sum rounded on their own.  The chain ends at the first sample that is not accepted; otherwise p_k = q.
+ *             A chain that has ended contributes nothing further in its direction.
+ *   result    under the mask.  Integer weights w_k = C(2R, R + k).  acc = 0; then, in the order of the walk (k = -1, -2, .., -R,
+ *             then +1, .., +R: past before future, nearer before farther), for every accepted sample, per channel
+ *             acc = acc + w_k * (s_k - x), the difference, the product and the sum each rounded to fp32 on its own (no FMA).
+ *             W = w_0 + the sum of the accepted w_k; W <= 65536, exact in fp32.  out = x + acc / W, an IEEE division and a sum,
+ *             rounded on their own.  A pixel with no accepted sample keeps x bit for bit.  support (int32) = the number of
+ *             accepted samples, 0..2R.
+ *   outside   the mask out = images bit for bit and support = -1.
+ * What follows from the rule: one frame returns the images; an empty mask returns the images; a clip whose masked area does not
+ * change along the field is returned bit for bit (the difference form gives exactly 0); nothing outside the mask ever changes; an
+ * object more than `tolerance` away from the pixel is never averaged in; the same bits on every run and for every chunking.
+ * Non-finite values behave as fp32 arithmetic gives: a NaN or a negative value has code 0 and +inf code 255, so a non-finite sample
+ * can be accepted, and an accepted NaN sample makes that pixel NaN.
+ * Not done: a reference value other than the frame's own pixel -- a single outlier frame therefore keeps its value, because every
+ * neighbour is rejected; motion boundaries finer than a block; a soft mask edge (the multiband blend follows).
+ * Launch (csrc/temporal_smooth_kernel.hip): one for the frames first .. first + count - 1 of the clip, a block per 32 x 32 tile and
+ * frame, a lane per pixel; a wave (two rows of a tile) with nothing masked copies its pixels and leaves, elsewhere a known pixel is copied by its lane.  `fwd` row j is the field of frame fwd_first + j towards the next
+ * frame, `bwd` row j that of frame bwd_first + j towards the one before, [gh, gw, 2] each; the walks read `fwd` of the frames
+ * first .. min(first + count + R - 2, frames - 2) and `bwd` of max(first - R + 1, 1) .. first + count - 1, and the rows given must
+ * cover those.  Where a range is empty (one frame) its pointer is not read and may be null.  `known` is level 0 of frame
+ * `first`'s known pyramid, the next frame's known_stride bytes on (a frame's pyramid stride, or height * width).  No scratch, no
+ * atomics, no LDS.
+ * LP_E_INVALID: a null pointer (except an unread field array); frames < 1; a side, channels, radius or tolerance outside its range;
+ * first < 0, count < 1 or first + count > frames; field rows that do not cover what is read; known_stride < height * width with
+ * count > 1; out or support aliasing an input or one another.  LP_E_UNSUPPORTED: frames > 65535.  All checked before any HIP call. */
+#define LP_TSMOOTH_MAX_RADIUS 8
+
+typedef struct lp_tsmooth_desc {
+    int32_t frames, height, width, channels;      /* the clip                                                                */
+    int32_t first, count;                         /* the frames this launch writes                                           */
+    int32_t radius, tolerance;
+    int32_t fwd_first, fwd_count;                 /* the frames whose rows `fwd` holds                                       */
+    int32_t bwd_first, bwd_count;
+    const int32_t* fwd;                           /* [fwd_count, gh, gw, 2] level-0 final fields towards the next frame      */
+    const int32_t* bwd;                           /* [bwd_count, gh, gw, 2] towards the frame before                         */
+    const uint8_t* known;                         /* frame `first`'s known bits [height, width]                              */
+    int64_t        known_stride;                  /* bytes from a frame's known bits to the next frame's                     */
+    const float*   images;                        /* [frames, height, width, channels] fp32                                  */
+    float*         out;                           /* [frames, height, width, channels]: frames first .. are written, whole   */
+    int32_t*       support;                       /* [frames, height, width]: likewise                                       */
+} lp_tsmooth_desc;
+LP_API int lp_tsmooth(const lp_tsmooth_desc* desc, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -493,6 +493,17 @@ class LpTfillCarryPairDesc(C.Structure):
                 ("filled", C.c_void_p), ("source", C.c_void_p), ("remaining", C.c_void_p), ("witnesses", C.c_void_p)]
 
 
+LP_TSMOOTH_MAX_RADIUS = 8
+
+
+class LpTsmoothDesc(C.Structure):
+    _fields_ = [("frames", C.c_int32), ("height", C.c_int32), ("width", C.c_int32), ("channels", C.c_int32),
+                ("first", C.c_int32), ("count", C.c_int32), ("radius", C.c_int32), ("tolerance", C.c_int32),
+                ("fwd_first", C.c_int32), ("fwd_count", C.c_int32), ("bwd_first", C.c_int32), ("bwd_count", C.c_int32),
+                ("fwd", C.c_void_p), ("bwd", C.c_void_p), ("known", C.c_void_p), ("known_stride", C.c_int64),
+                ("images", C.c_void_p), ("out", C.c_void_p), ("support", C.c_void_p)]
+
+
 def prop_level_shape(height, width, level):
     """Level `level` of a height x width plane: ceil(height / 2^level) x ceil(width / 2^level)."""
     return (int(height) + (1 << level) - 1) >> level, (int(width) + (1 << level) - 1) >> level
@@ -621,6 +632,7 @@ EXPORTS = {
     "lp_tfill_known": (C.c_int, [C.POINTER(LpTfillKnownDesc), C.c_void_p]),
     "lp_tfill_carry": (C.c_int, [C.POINTER(LpTfillCarryDesc), C.c_void_p]),
     "lp_tfill_carry_pair": (C.c_int, [C.POINTER(LpTfillCarryPairDesc), C.c_void_p]),
+    "lp_tsmooth": (C.c_int, [C.POINTER(LpTsmoothDesc), C.c_void_p]),
 }
 
 

@@ -1,0 +1,287 @@
+// temporal_smooth_kernel.hip -- video temporal smooth for gfx950 (lanpaint_amd/temporal_smooth.py): what the sampler put under the
+// mask of a frame is pulled towards the weighted mean of what it put at the same scene point in the frames around it, as far as
+// that agrees with the pixel.  include/lanpaint_hip.h (lp_tsmooth) states the rule.  The fields are the temporal fill's, computed
+// by lp_prop_match_batch and lp_prop_fill_batch unchanged; this file holds the gather.
+//
+//   smooth   one launch for all frames of a chunk: a block per 32 x 32 tile and frame, a lane per pixel.  A lane reads its known
+//            byte first.  A wave -- two rows of the tile -- in which none is masked, most of a frame, copies its two runs of
+//            pixels, 16 bytes a lane where they are aligned, writes support = -1 and leaves; no wave waits for another, so a
+//            block's slots on its CU free up wave by wave (with a barrier and a copy by the whole block the launch was slower:
+//            profiles/r33_temporal_smooth.md).  Else a known pixel is copied by its lane, and a masked pixel walks up to R steps
+//            into the past, then into the future: per step the four block vectors around its position (the field stays cached:
+//            gh gw 8 bytes), the sample's taps, the codes' comparison.  The walk of a pixel depends on nothing another pixel
+//            computes: no barrier, no LDS -- every step, the first included, reads its vectors from the field, so the tile's
+//            6 x 6 vectors of the carry are not staged.
+// Registers: a chain accepts a prefix of its steps, so two counts describe it.  Channels go four at a time: the first four are
+// accumulated while the walk decides (every further group is sampled there only to be compared), and each further group walks the
+// accepted steps again -- the positions are integers and come out the same -- to accumulate its own four.  Nothing is indexed by a
+// register, so nothing lives in scratch.  The sums keep the rule's order: past before future, nearer before farther.
+// fp32 in a fixed order, every operation rounded on its own (__fmul_rn / __fadd_rn / __fsub_rn / __fdiv_rn: nothing contracts).
+// No atomics.
+#include "lp_common.h"
+
+namespace lp {
+namespace {
+
+constexpr int kB = LP_PROP_BLOCK;                                                     // 8
+constexpr int kTile = 32;
+constexpr int kWave = 64;                                                            // two rows of a tile
+
+__device__ __forceinline__ int clampi(int v, int lo, int hi) { return min(max(v, lo), hi); }
+
+struct smooth_args {
+    const int32_t* fwd;          // row j: the field of frame fwd0 + j towards the next frame, [gh, gw, 2]
+    const int32_t* bwd;          // row j: of frame bwd0 + j towards the one before
+    const uint8_t* known;        // frame `first`'s bits [H, W]; the next frame's lie known_stride bytes on
+    int64_t        known_stride;
+    const float*   images;       // [frames, H, W, C]
+    float*         out;
+    int32_t*       support;      // [frames, H, W]
+    int32_t H, W, C, gh, gw, frames, first, fwd0, bwd0, radius, tolerance, w0;
+};
+
+// (16 - f) a + f b, or 16 a without reading b's weight into it: the products and the sum rounded on their own
+__device__ __forceinline__ float lerp16(float a, float b, int f) {
+    if (f == 0) return __fmul_rn(16.0f, a);
+    return __fadd_rn(__fmul_rn(static_cast<float>(16 - f), a), __fmul_rn(static_cast<float>(f), b));
+}
+
+__device__ __forceinline__ int code_of(float v) {                       // the propagate section's 8-bit code; a NaN gives 0
+    const float t = v > 0.0f ? (v < 1.0f ? v : 1.0f) : 0.0f;
+    return static_cast<int>(__fadd_rn(__fmul_rn(t, 255.0f), 0.5f));
+}
+
+// Where a frame is sampled: the two rows of taps of the temporal fill's "sample"
+struct tap_rows {
+    const float* r0;
+    const float* r1;
+    int nx, gy, gx;
+};
+
+// q lies inside the plane: gy != 0 puts row qy / 16 + 1 inside it, as gx does the next column
+__device__ __forceinline__ tap_rows taps_of(const smooth_args& a, int f, int qy, int qx) {
+    tap_rows t;
+    t.gy = qy & 15;
+    t.gx = qx & 15;
+    t.r0 = a.images + ((static_cast<int64_t>(f) * a.H + (qy >> 4)) * a.W + (qx >> 4)) * a.C;
+    t.r1 = t.r0 + (t.gy ? static_cast<int64_t>(a.W) * a.C : 0);
+    t.nx = t.gx ? a.C : 0;
+    return t;
+}
+
+// channels c0 .. c0 + 3 of the sample (0 beyond C): the four channels' taps are asked for before the first is used
+__device__ __forceinline__ void sample4(const tap_rows& t, int C, int c0, float (&v)[4]) {
+    float t00[4], t01[4], t10[4], t11[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const bool in = c0 + k < C;
+        t00[k] = in ? t.r0[c0 + k] : 0.0f;
+        t01[k] = in && t.gx ? t.r0[t.nx + c0 + k] : 0.0f;
+        t10[k] = in && t.gy ? t.r1[c0 + k] : 0.0f;
+        t11[k] = in && t.gy && t.gx ? t.r1[t.nx + c0 + k] : 0.0f;
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const float top = lerp16(t00[k], t01[k], t.gx);
+        const float s = t.gy == 0 ? __fmul_rn(16.0f, top)
+                                  : __fadd_rn(__fmul_rn(static_cast<float>(16 - t.gy), top), __fmul_rn(static_cast<float>(t.gy), lerp16(t10[k], t11[k], t.gx)));
+        v[k] = __fmul_rn(s, 1.0f / 256.0f);
+    }
+}
+
+__device__ __forceinline__ void own4(const float* __restrict__ x, int C, int c0, float (&v)[4]) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) v[k] = c0 + k < C ? x[c0 + k] : 0.0f;
+}
+
+// the largest |code(s) - code(x)| over the group; channels beyond C are 0 on both sides
+__device__ __forceinline__ int apart4(const float (&s)[4], const float (&x)[4]) {
+    int m = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) m = max(m, abs(code_of(s[k]) - code_of(x[k])));
+    return m;
+}
+
+// One step from p (inside the plane) along `vec`: the propagate section's per-pixel interpolation at the integer pixel nearest p.
+// False: q leaves the plane.
+__device__ __forceinline__ bool step(const smooth_args& a, const int32_t* __restrict__ vec, int py, int px, int& qy, int& qx) {
+    const int uy = 2 * ((py + 8) >> 4) - 7, ux = 2 * ((px + 8) >> 4) - 7;
+    const int by = uy >> 4, bx = ux >> 4, fy = uy & 15, fx = ux & 15;   // >> floors: u = -7 .. -1 gives block -1, clamped to 0
+    const int y0 = clampi(by, 0, a.gh - 1), y1 = clampi(by + 1, 0, a.gh - 1), x0 = clampi(bx, 0, a.gw - 1), x1 = clampi(bx + 1, 0, a.gw - 1);
+    const int2 v00 = *reinterpret_cast<const int2*>(vec + (static_cast<int64_t>(y0) * a.gw + x0) * 2);
+    const int2 v01 = *reinterpret_cast<const int2*>(vec + (static_cast<int64_t>(y0) * a.gw + x1) * 2);
+    const int2 v10 = *reinterpret_cast<const int2*>(vec + (static_cast<int64_t>(y1) * a.gw + x0) * 2);
+    const int2 v11 = *reinterpret_cast<const int2*>(vec + (static_cast<int64_t>(y1) * a.gw + x1) * 2);
+    const int Vy = ((16 - fy) * ((16 - fx) * v00.x + fx * v01.x) + fy * ((16 - fx) * v10.x + fx * v11.x) + 128) >> 8;
+    const int Vx = ((16 - fy) * ((16 - fx) * v00.y + fx * v01.y) + fy * ((16 - fx) * v10.y + fx * v11.y) + 128) >> 8;
+    qy = py + Vy;
+    qx = px + Vx;
+    return qy >= 0 && qy <= 16 * (a.H - 1) && qx >= 0 && qx <= 16 * (a.W - 1);
+}
+
+// The chain of direction d from pixel (y, x) of frame t, for the channels c0 .. c0 + 3 with their own values x4.
+// Decide: at most `limit` = R steps; the chain ends at the clip's end, where q leaves the plane or at the first sample some channel
+// of which is more than `tolerance` codes away from the pixel; W gathers the accepted weights.  Else: exactly `limit` steps, those
+// an earlier deciding walk accepted.  Returns the steps accepted.
+template <bool Decide>
+__device__ __forceinline__ int chain(const smooth_args& a, int t, int d, int limit, int y, int x, const float* __restrict__ own, int c0,
+                                     const float (&x4)[4], float (&acc)[4], int& W) {
+    const int64_t field = static_cast<int64_t>(a.gh) * a.gw * 2;
+    int py = 16 * y, px = 16 * x, w = a.w0, n = 0;
+#pragma unroll 1
+    for (int k = 1; k <= limit; ++k) {
+        const int u = t + (k - 1) * d, v = u + d;
+        if (Decide && (v < 0 || v >= a.frames)) break;
+        const int32_t* vec = d > 0 ? a.fwd + (u - a.fwd0) * field : a.bwd + (u - a.bwd0) * field;
+        int qy, qx;
+        const bool inside = step(a, vec, py, px, qy, qx);
+        if (Decide && !inside) break;
+        const tap_rows taps = taps_of(a, v, qy, qx);
+        float s[4];
+        sample4(taps, a.C, c0, s);
+        if (Decide) {
+            int apart = apart4(s, x4);
+#pragma unroll 1
+            for (int c = 4; c < a.C && apart <= a.tolerance; c += 4) {  // the further groups: compared here, accumulated later
+                float sc[4], xc[4];
+                sample4(taps, a.C, c, sc);
+                own4(own, a.C, c, xc);
+                apart = max(apart, apart4(sc, xc));
+            }
+            if (apart > a.tolerance) break;
+        }
+        w = w * (a.radius - k + 1) / (a.radius + k);                     // C(2R, R + k) from C(2R, R + k - 1): the division is exact
+        const float wf = static_cast<float>(w);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[j] = __fadd_rn(acc[j], __fmul_rn(wf, __fsub_rn(s[j], x4[j])));
+        if (Decide) W += w;
+        py = qy;
+        px = qx;
+        ++n;
+    }
+    return n;
+}
+
+// `rows` runs of `run` elements, `pitch` elements apart, by one wave: consecutive lanes take consecutive elements of a run, and two
+// loads are asked for before the first store.
+template <typename T>
+__device__ __forceinline__ void copy_rows(const T* __restrict__ src, T* __restrict__ dst, int rows, int run, int64_t pitch, int lane) {
+    const int total = rows * run;
+#pragma unroll 1
+    for (int i0 = lane; i0 < total; i0 += 2 * kWave) {
+        const int i1 = min(i0 + kWave, total - 1);                       // past the end: the last element again, not stored
+        const int r0 = i0 / run, r1 = i1 / run;
+        const T v0 = src[r0 * pitch + (i0 - r0 * run)], v1 = src[r1 * pitch + (i1 - r1 * run)];
+        dst[r0 * pitch + (i0 - r0 * run)] = v0;
+        if (i0 + kWave < total) dst[r1 * pitch + (i1 - r1 * run)] = v1;
+    }
+}
+
+// One lane per pixel, as the temporal fill's carry has it: a masked pixel's work is a chain of dependent reads.
+__global__ __launch_bounds__(kTile * kTile) void lp_tsmooth_kernel(const smooth_args a) {
+    const int H = a.H, W = a.W, C = a.C;
+    const int ly = threadIdx.x >> 5, lx = threadIdx.x & 31, y = blockIdx.y * kTile + ly, x = blockIdx.x * kTile + lx;
+    const int t = a.first + static_cast<int>(blockIdx.z);
+    const int64_t p = static_cast<int64_t>(y) * W + x;
+    const bool inside = y < H && x < W;
+    const bool masked = inside && a.known[static_cast<int64_t>(blockIdx.z) * a.known_stride + p] == 0;
+    const int64_t at = static_cast<int64_t>(t) * H * W + p;
+    const float* __restrict__ own = a.images + at * C;
+    float* __restrict__ out = a.out + at * C;
+    if (__all(!masked)) {                                                // the whole wave, two rows of the tile: nothing under a mask here
+        if (inside) a.support[at] = -1;
+        const int y0 = static_cast<int>(blockIdx.y) * kTile + (ly & ~1);
+        if (y0 >= H) return;
+        const int tw = min(kTile, W - static_cast<int>(blockIdx.x) * kTile), rows = min(2, H - y0), lane = threadIdx.x & (kWave - 1);
+        const int64_t pitch = static_cast<int64_t>(W) * C;               // floats from a row to the next
+        const int64_t corner = ((static_cast<int64_t>(t) * H + y0) * W + static_cast<int64_t>(blockIdx.x) * kTile) * C;
+        // 16 bytes a lane where both rows start and end on them: the tile's first column is a multiple of 32 pixels
+        if (((pitch | (tw * C)) & 3) == 0 && ((reinterpret_cast<uintptr_t>(a.images) | reinterpret_cast<uintptr_t>(a.out)) & 15) == 0)
+            copy_rows(reinterpret_cast<const float4*>(a.images + corner), reinterpret_cast<float4*>(a.out + corner), rows, tw * C / 4, pitch / 4, lane);
+        else
+            copy_rows(a.images + corner, a.out + corner, rows, tw * C, pitch, lane);
+        return;
+    }
+    if (!inside) return;
+    if (!masked) {
+#pragma unroll 1
+        for (int c = 0; c < C; ++c) out[c] = own[c];
+        a.support[at] = -1;
+        return;
+    }
+    float x4[4], acc[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    own4(own, C, 0, x4);
+    int Wsum = a.w0;
+    const int n_past = chain<true>(a, t, -1, a.radius, y, x, own, 0, x4, acc, Wsum);
+    const int n_next = chain<true>(a, t, +1, a.radius, y, x, own, 0, x4, acc, Wsum);
+    const int n = n_past + n_next;
+    a.support[at] = n;
+    const float Wf = static_cast<float>(Wsum);
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+        if (j < C) out[j] = n ? __fadd_rn(x4[j], __fdiv_rn(acc[j], Wf)) : x4[j];
+#pragma unroll 1
+    for (int c0 = 4; c0 < C; c0 += 4) {
+        float xc[4], ac[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+        own4(own, C, c0, xc);
+        int unused = 0;
+        chain<false>(a, t, -1, n_past, y, x, own, c0, xc, ac, unused);
+        chain<false>(a, t, +1, n_next, y, x, own, c0, xc, ac, unused);
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            if (c0 + j < C) out[c0 + j] = n ? __fadd_rn(xc[j], __fdiv_rn(ac[j], Wf)) : xc[j];
+    }
+}
+
+bool side_ok(int s) { return s > 0 && s <= LP_VMASK_MAX_SIDE; }
+
+}  // namespace
+
+int tsmooth_dispatch(const lp_tsmooth_desc* dp, hipStream_t stream) {
+    if (!dp) return LP_E_INVALID;
+    const lp_tsmooth_desc& d = *dp;
+    if (d.frames < 1 || !side_ok(d.height) || !side_ok(d.width) || d.channels < 1 || d.channels > LP_DETAIL_MAX_CHANNELS) return LP_E_INVALID;
+    if (d.radius < 1 || d.radius > LP_TSMOOTH_MAX_RADIUS || d.tolerance < 0 || d.tolerance > 255) return LP_E_INVALID;
+    if (d.frames > 65535) return LP_E_UNSUPPORTED;
+    if (d.first < 0 || d.count < 1 || d.count > d.frames - d.first) return LP_E_INVALID;
+    if (!d.known || !d.images || !d.out || !d.support) return LP_E_INVALID;
+    const int64_t plane = static_cast<int64_t>(d.height) * d.width;
+    if (d.known_stride < plane && d.count > 1) return LP_E_INVALID;
+    // the frames whose fields the walks of first .. first + count - 1 can read
+    const int last = d.first + d.count - 1;
+    const int f_lo = d.first, f_hi = min(last + d.radius - 1, d.frames - 2);             // towards the next frame
+    const int b_lo = max(d.first - d.radius + 1, 1), b_hi = last;                        // towards the one before
+    if (f_lo <= f_hi && (!d.fwd || d.fwd_first < 0 || d.fwd_count < 1 || d.fwd_first > f_lo || f_hi - d.fwd_first >= d.fwd_count)) return LP_E_INVALID;
+    if (b_lo <= b_hi && (!d.bwd || d.bwd_first < 0 || d.bwd_count < 1 || d.bwd_first > b_lo || b_hi - d.bwd_first >= d.bwd_count)) return LP_E_INVALID;
+    const void* in[4] = {d.fwd, d.bwd, d.known, d.images};
+    for (const void* q : in)
+        if (q && (q == d.out || q == d.support)) return LP_E_INVALID;
+    if (static_cast<const void*>(d.out) == static_cast<const void*>(d.support)) return LP_E_INVALID;
+    smooth_args a = {};
+    a.fwd = d.fwd;
+    a.bwd = d.bwd;
+    a.known = d.known;
+    a.known_stride = d.known_stride;
+    a.images = d.images;
+    a.out = d.out;
+    a.support = d.support;
+    a.H = d.height;
+    a.W = d.width;
+    a.C = d.channels;
+    a.gh = (d.height + kB - 1) / kB;
+    a.gw = (d.width + kB - 1) / kB;
+    a.frames = d.frames;
+    a.first = d.first;
+    a.fwd0 = d.fwd_first;
+    a.bwd0 = d.bwd_first;
+    a.radius = d.radius;
+    a.tolerance = d.tolerance;
+    a.w0 = 1;
+    for (int k = 1; k <= d.radius; ++k) a.w0 = a.w0 * (d.radius + k) / k;                // C(2R, R): C(R + k, k) at every step
+    const dim3 grid(static_cast<uint32_t>((d.width + kTile - 1) / kTile), static_cast<uint32_t>((d.height + kTile - 1) / kTile),
+                    static_cast<uint32_t>(d.count));
+    hipLaunchKernelGGL(lp_tsmooth_kernel, grid, dim3(kTile * kTile), 0, stream, a);
+    return hipGetLastError() == hipSuccess ? LP_OK : LP_E_LAUNCH;
+}
+
+}  // namespace lp

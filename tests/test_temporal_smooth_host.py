@@ -1,0 +1,325 @@
+"""The video temporal smooth, the parts that need no device: the properties the rule promises on the restatement
+(tests/temporal_smooth_ref.py) as bits and counts, the C entry's argument checks (made before any HIP call), the descriptor's
+layout against the header as gcc reads it, the names' presence everywhere, the wrappers' argument checks, the node's protocol and
+the no-fallback errors."""
+import ctypes
+import functools
+import os
+import re
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+from lanpaint_amd import _cabi
+from tests import temporal_smooth_ref as sref
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+RADII = (1, 2, 3)
+PAN_PIXELS = {1: 1344, 2: 896, 3: 448}                               # masked pixels of the frames R .. F - 1 - R: 224 a frame
+NOISE_RATIO = {1: 6 / 16, 2: 70 / 256, 3: 924 / 4096}                # sum w^2 / (sum w)^2: 0.375, 0.273, 0.226
+
+
+def _bits(a):
+    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
+
+
+# ---- the scenes of the three properties; tests/test_gpu_temporal_smooth.py runs the device on the same ones -----------------------------
+@functools.lru_cache(maxsize=None)
+def pan_clip():
+    """(clean clip, flickering clip, mask): 8 frames of 48 x 64 x 3 cut from one canvas of 8-bit values, panning (1, -2) px per
+    frame; the mask is fixed to the canvas, and under it even frames are 8 / 256 too bright and odd frames as much too dark."""
+    rng = np.random.default_rng(6)
+    F, H, W = 8, 48, 64
+    canvas = (rng.integers(64, 192, (H + F, W + 2 * F, 3)) / 256).astype(np.float32)
+    cm = np.zeros((H + F, W + 2 * F), np.float32)
+    cm[26:40, 30:46] = 1
+
+    def cut(a, t):
+        return a[t:t + H, 2 * (F - 1 - t):2 * (F - 1 - t) + W]
+    clean = np.stack([cut(canvas, t) for t in range(F)])
+    mask = np.stack([cut(cm, t) for t in range(F)])
+    clip = clean.copy()
+    for t in range(F):
+        clip[t][mask[t] == 1] += np.float32(8 / 256 if t % 2 == 0 else -8 / 256)
+    return clean, clip, mask
+
+
+@functools.lru_cache(maxsize=None)
+def still_clip():
+    """(still clip, mask): 9 equal frames of 32 x 48 x 3 in 0.25 .. 0.75 and a static mask."""
+    F, H, W = 9, 32, 48
+    frame = (0.25 + 0.5 * np.random.default_rng(7).random((1, H, W, 3))).astype(np.float32)
+    mask = np.zeros((H, W), np.float32)
+    mask[10:22, 14:34] = 1
+    return np.repeat(frame, F, axis=0), mask
+
+
+@functools.lru_cache(maxsize=None)
+def noise_clip():
+    """(still clip, noisy clip, mask): iid normal noise of sigma 0.02 under the mask of the still clip."""
+    still, mask = still_clip()
+    clip = still.copy()
+    clip[:, mask == 1] += np.random.default_rng(8).normal(0, 0.02, (still.shape[0], int(mask.sum()), 3)).astype(np.float32)
+    return still, clip, mask
+
+
+GHOST_FRAME, GHOST = 4, (slice(13, 19), slice(20, 28))               # a 6 x 8 patch inside the hole
+
+
+@functools.lru_cache(maxsize=None)
+def ghost_clip():
+    """(clip, mask): the still clip with a patch of 1.0 in one frame, inside the hole: at least 64 grey levels from the canvas."""
+    still, mask = still_clip()
+    clip = still.copy()
+    clip[GHOST_FRAME][GHOST] = 1.0
+    return clip, mask
+
+
+def check_outside(images, mask, out, support):
+    """Everything outside the mask is bits of the input with support -1; under it support counts 0 .. 2R."""
+    under = np.broadcast_to(mask == 1, support.shape)
+    assert (_bits(out)[~under] == _bits(images)[~under]).all() and (support[~under] == -1).all() and (support[under] >= 0).all()
+
+
+def check_pan(radius, motion, out, support):
+    clean, clip, mask = pan_clip()
+    F = clip.shape[0]
+    under = mask == 1
+    assert (np.abs(clip - clean)[under] == np.float32(8 / 256)).all()   # the error of the input, everywhere under the mask
+    check_outside(clip, mask, out, support)
+    inner = np.zeros_like(under)
+    inner[radius:F - radius] = under[radius:F - radius]
+    assert int(inner.sum()) == PAN_PIXELS[radius]
+    if motion == "background":
+        assert (_bits(out)[inner] == _bits(clean)[inner]).all()        # every one of them is the clean canvas, bit for bit
+        assert (support[inner] == 2 * radius).all()
+    else:
+        assert np.abs(out - clean)[under].mean() < np.abs(clip - clean)[under].mean()
+
+
+def check_noise(radius, out, support):
+    still, clip, mask = noise_clip()
+    F = clip.shape[0]
+    check_outside(clip, mask, out, support)
+    inner = slice(radius, F - radius)
+    before, after = (clip - still)[inner][:, mask == 1], (out - still)[inner][:, mask == 1]
+    ratio = float(after.astype(np.float64).var() / before.astype(np.float64).var())
+    print(f"radius {radius}: variance ratio {ratio:.4f}, the weights give {NOISE_RATIO[radius]:.4f}")
+    assert abs(ratio / NOISE_RATIO[radius] - 1) <= 0.15, (radius, ratio)
+
+
+def check_ghost(out, support):
+    clip, mask = ghost_clip()
+    check_outside(clip, mask, out, support)
+    for t in range(GHOST_FRAME - 2, GHOST_FRAME + 3):                  # the patch's frame and its four neighbours
+        assert (_bits(out[t][GHOST]) == _bits(clip[t][GHOST])).all(), t
+    assert (support[GHOST_FRAME][GHOST] == 0).all()
+    assert (support[GHOST_FRAME - 1][GHOST] == 2).all() and (support[GHOST_FRAME + 2][GHOST] == 3).all()   # the chain ends at the patch
+    assert (_bits(out) == _bits(clip)).all()                           # and the rest of the clip is still
+
+
+# ---- the properties, on the restatement ---------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("motion", sref.MOTIONS)
+@pytest.mark.parametrize("radius", RADII)
+def test_pan_with_alternating_flicker_is_recovered_bit_for_bit(radius, motion):
+    _, clip, mask = pan_clip()
+    check_pan(radius, motion, *sref.temporal_smooth_ref(clip, mask, radius, 24, motion))
+
+
+@pytest.mark.parametrize("radius", RADII)
+def test_noise_variance_falls_as_the_weights_say(radius):
+    _, clip, mask = noise_clip()
+    check_noise(radius, *sref.temporal_smooth_ref(clip, mask, radius, 24))
+
+
+def test_an_object_beyond_the_tolerance_leaves_no_ghost():
+    clip, mask = ghost_clip()
+    check_ghost(*sref.temporal_smooth_ref(clip, mask, 2, 24))
+
+
+def test_one_frame_an_empty_mask_and_a_still_clip_return_the_images():
+    _, clip, mask = noise_clip()
+    out, support = sref.temporal_smooth_ref(clip[:1], mask, 2, 24)
+    assert (_bits(out) == _bits(clip[:1])).all() and (support[0] == np.where(mask == 1, 0, -1)).all()
+    out, support = sref.temporal_smooth_ref(clip, np.zeros_like(mask), 2, 24)
+    assert (_bits(out) == _bits(clip)).all() and (support == -1).all()
+    still, mask = still_clip()
+    for motion in sref.MOTIONS:
+        out, support = sref.temporal_smooth_ref(still, mask, 3, 24, motion)
+        assert (_bits(out) == _bits(still)).all()
+        assert (support[4][mask == 1] == 6).all() and (support[0][mask == 1] == 3).all() and (support[7][mask == 1] == 4).all()
+    negative = -still                                                  # -x + 0 / W keeps the sign bit of every value too
+    out, _ = sref.temporal_smooth_ref(negative, mask, 2, 0)
+    assert (_bits(out) == _bits(negative)).all()
+
+
+def test_tolerance_zero_leaves_a_noisy_clip_and_the_outside_never_changes():
+    # tolerance 0 accepts a sample only when every channel has the pixel's own code; under noise of 15 codes none of the 8640 has
+    still, mask = still_clip()
+    loud = still.copy()
+    loud[:, mask == 1] += np.random.default_rng(9).normal(0, 0.06, (still.shape[0], int(mask.sum()), 3)).astype(np.float32)
+    out, support = sref.temporal_smooth_ref(loud, mask, 2, 0)
+    check_outside(loud, mask, out, support)
+    assert (_bits(out) == _bits(loud)).all() and (support[:, mask == 1] == 0).all()
+    _, clip, mask = noise_clip()
+    out, support = sref.temporal_smooth_ref(clip, mask, 2, 255)
+    check_outside(clip, mask, out, support)
+    assert (support[2:7][:, mask == 1] == 4).all() and (_bits(out) != _bits(clip))[:, mask == 1].any()
+
+
+def test_a_nan_sample_that_is_accepted_makes_the_pixel_nan_and_a_nan_mask_is_known():
+    still, mask = still_clip()
+    clip = still.copy()
+    clip[3, 12, 16] = np.nan                                           # code 0: 64 or more away from the canvas, rejected
+    out, support = sref.temporal_smooth_ref(clip, mask, 1, 24)
+    assert (_bits(out) == _bits(clip)).all() and support[3, 12, 16] == 0 and support[2, 12, 16] == 1
+    out, support = sref.temporal_smooth_ref(clip, mask, 1, 255)
+    assert np.isnan(out[2:5, 12, 16]).all() and not np.isnan(out[[1, 5], 12, 16]).any() and support[2, 12, 16] == 2
+    holes = mask.copy()
+    holes[11, 15] = np.nan
+    assert sref.temporal_smooth_ref(clip, holes, 1, 24)[1][0, 11, 15] == -1
+
+
+def test_weights_are_the_binomial_row():
+    assert sref.weights(1) == [2, 1] and sref.weights(2) == [6, 4, 1] and sref.weights(8)[0] == 12870
+    for radius in range(1, _cabi.LP_TSMOOTH_MAX_RADIUS + 1):
+        w = sref.weights(radius)
+        assert w[0] + 2 * sum(w[1:]) == 4 ** radius <= 65536
+    for radius in RADII:
+        w = sref.weights(radius)
+        assert NOISE_RATIO[radius] == (w[0] ** 2 + 2 * sum(v * v for v in w[1:])) / 16 ** radius
+
+
+# ---- the C ABI ------------------------------------------------------------------------------------------------------------------------
+def test_entry_rejects_bad_arguments_without_a_device(hip_lib):
+    C, E, U = ctypes, _cabi.LP_E_INVALID, _cabi.LP_E_UNSUPPORTED
+    side = _cabi.LP_VMASK_MAX_SIDE
+    a = [C.c_void_p(4096 * (i + 1)) for i in range(8)]                # never dereferenced: validation comes before any HIP call
+    names = [f for f, t in _cabi.LpTsmoothDesc._fields_ if t is C.c_void_p]
+    assert names == ["fwd", "bwd", "known", "images", "out", "support"]
+    # frames 3 .. 5 of 10 with radius 2: fwd of 3 .. 6, bwd of 2 .. 5
+    good = dict(frames=10, height=40, width=70, channels=3, first=3, count=3, radius=2, tolerance=24, fwd_first=3, fwd_count=4,
+                bwd_first=2, bwd_count=4, known_stride=40 * 70, **dict(zip(names, a)))
+
+    def call(**change):
+        return hip_lib.lp_tsmooth(C.byref(_cabi.LpTsmoothDesc(**{**good, **change})), None)
+    assert hip_lib.lp_tsmooth(None, None) == E
+    for change in ({"frames": 0}, {"frames": -1}, {"height": 0}, {"height": side + 1}, {"width": 0}, {"width": side + 1},
+                   {"channels": 0}, {"channels": _cabi.LP_DETAIL_MAX_CHANNELS + 1}, {"radius": 0}, {"radius": _cabi.LP_TSMOOTH_MAX_RADIUS + 1},
+                   {"tolerance": -1}, {"tolerance": 256}, {"first": -1}, {"first": 10}, {"count": 0}, {"count": 8}, {"count": -1},
+                   {"fwd_first": 4}, {"fwd_first": -1}, {"fwd_count": 3}, {"fwd_count": 0}, {"bwd_first": 3}, {"bwd_first": -1},
+                   {"bwd_count": 3}, {"bwd_count": 0}, {"known_stride": 40 * 70 - 1}, {"known_stride": -1}, {"radius": 3}):
+        assert call(**change) == E, change
+    for name in names:
+        assert call(**{name: None}) == E, name
+    for out in ("out", "support"):                                     # an output that is an input or the other output
+        for other in names:
+            if other != out:
+                assert call(**{out: good[other]}) == E, (out, other)
+    assert call(frames=65536) == U
+
+
+def test_descriptor_layout_and_constants_match_c(tmp_path):
+    py = _cabi.LpTsmoothDesc
+    prog = ['#include <stdio.h>', '#include <stddef.h>', '#include "lanpaint_hip.h"', "int main(void){"]
+    for f, _ in py._fields_:
+        prog.append(f'printf("%zu ", offsetof(lp_tsmooth_desc, {f}));')
+    prog.append('printf("%zu\\n", sizeof(lp_tsmooth_desc));')
+    prog.append('printf("%d %d\\n", LP_TSMOOTH_MAX_RADIUS, LP_ABI_VERSION); return 0;}')
+    src = tmp_path / "layout.c"
+    src.write_text("\n".join(prog))
+    exe = tmp_path / "layout"
+    subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
+    lines = subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.strip().split("\n")
+    assert [int(v) for v in lines[0].split()] == [getattr(py, f).offset for f, _ in py._fields_] + [ctypes.sizeof(py)]
+    assert [int(v) for v in lines[1].split()] == [_cabi.LP_TSMOOTH_MAX_RADIUS, _cabi.ABI_VERSION]
+
+
+def test_the_names_are_everywhere_and_the_abi_version_stays(hip_lib):
+    read = lambda *path: open(os.path.join(ROOT, *path)).read()       # noqa: E731
+    header = read("include", "lanpaint_hip.h")
+    dynamic = subprocess.run(["nm", "-D", "--defined-only", _cabi.LIB_PATH], capture_output=True, text=True, check=True).stdout
+    assert re.search(r"global:\s*lp_\*;", read("lanpaint_amd", "csrc", "exports.map"))     # every lp_* entry, this one among them
+    assert re.search(r"LP_API\s+int\s+lp_tsmooth\s*\(", header)
+    assert "lp_tsmooth" in _cabi.EXPORTS and hasattr(hip_lib, "lp_tsmooth")
+    assert re.search(r"\bT lp_tsmooth$", dynamic, flags=re.M)
+    assert _cabi.ABI_VERSION == 25 and hip_lib.lp_abi_version() == 25
+    assert "temporal_smooth_kernel.hip" in read("lanpaint_amd", "build.py")
+    for word in ("LP_TSMOOTH_MAX_RADIUS", "w_k = C(2R, R + k)", "keeps x bit for bit", "a tap with weight 0 is not", "no FMA",
+                 "an accepted NaN sample makes that pixel NaN", "for every chunking", "a single outlier frame", "support = -1"):
+        assert word in header, word
+    for doc in ("README.md", "DESIGN.md", "CHANGES.md", "INTEGRATION.md"):
+        text = read(doc)
+        assert "LanPaint_VideoTemporalSmooth" in text and "temporal_smooth" in text, doc
+    assert re.search(r"VideoTemporalSmooth\s*->\s*(LanPaint_)?MultibandBlend", read("INTEGRATION.md"))
+
+
+# ---- the wrappers and the node ----------------------------------------------------------------------------------------------------------
+def test_temporal_smooth_refuses_cpu_tensors_and_bad_arguments():
+    from lanpaint_amd import temporal_smooth as ts
+    images, mask = torch.zeros(4, 16, 16, 3), torch.zeros(4, 16, 16)
+    with pytest.raises(RuntimeError, match="no CPU fallback"):
+        ts.temporal_smooth(images, mask)
+    with pytest.raises(RuntimeError, match="no CPU fallback"):
+        ts.temporal_smooth(images.numpy(), mask)
+    fields = torch.zeros(3, 2, 2, 2, dtype=torch.int32)
+    with pytest.raises(RuntimeError, match="no CPU fallback"):
+        ts.smooth_frames(fields, fields, torch.zeros(4, 16, 16, dtype=torch.uint8), images)
+    # the numbers are checked before the tensors are looked at
+    for bad in (dict(radius=0), dict(radius=9), dict(radius=2.0), dict(radius=True), dict(tolerance=-1), dict(tolerance=256),
+                dict(tolerance=24.0), dict(motion="subject"), dict(motion=None), dict(levels=0), dict(levels=7), dict(search=0),
+                dict(search=8), dict(smooth=-1), dict(smooth=65)):
+        with pytest.raises(ValueError):
+            ts.temporal_smooth(images, mask, **bad)
+    for bad in (dict(radius=0), dict(radius=9), dict(tolerance=-1), dict(tolerance=256)):
+        with pytest.raises(ValueError):
+            ts.smooth_frames(fields, fields, torch.zeros(4, 16, 16, dtype=torch.uint8), images, **bad)
+    assert ts.WS_CAP_BYTES == 1 << 30 and ts.MAX_RADIUS == 8 and ts.MOTIONS == sref.MOTIONS
+    # frames 3 .. 5 of 10 with radius 2 read fwd of 3 .. 6 and bwd of 2 .. 5; the clip's ends cut both
+    assert [list(r) for r in ts.field_steps(3, 6, 10, 2)] == [[3, 4, 5, 6], [2, 3, 4, 5]]
+    assert [list(r) for r in ts.field_steps(0, 10, 10, 8)] == [list(range(9)), list(range(1, 10))]
+    assert [list(r) for r in ts.field_steps(0, 1, 1, 3)] == [[], []]
+    assert [list(r) for r in ts.field_steps(9, 10, 10, 1)] == [[], [9]]
+
+
+def test_node_protocol_and_own_mappings():
+    from lanpaint_amd import (detail_nodes, fill_nodes, grain_nodes, multiband_nodes, nodes, propagate_keys_nodes,
+                              propagate_keys_visible_nodes, propagate_nodes, propagate_visible_nodes, refine_nodes, stabilize_nodes,
+                              temporal_fill_checked_nodes, temporal_fill_nodes, temporal_smooth_nodes, video_nodes)
+    node = temporal_smooth_nodes.LanPaint_VideoTemporalSmooth
+    assert temporal_smooth_nodes.NODE_CLASS_MAPPINGS == {"LanPaint_VideoTemporalSmooth": node}
+    assert list(temporal_smooth_nodes.NODE_DISPLAY_NAME_MAPPINGS) == ["LanPaint_VideoTemporalSmooth"]
+    for other in (nodes, detail_nodes, fill_nodes, multiband_nodes, refine_nodes, stabilize_nodes, grain_nodes, video_nodes,
+                  propagate_nodes, propagate_keys_nodes, propagate_visible_nodes, propagate_keys_visible_nodes, temporal_fill_nodes,
+                  temporal_fill_checked_nodes):
+        assert not set(temporal_smooth_nodes.NODE_CLASS_MAPPINGS) & set(other.NODE_CLASS_MAPPINGS)
+        assert not set(temporal_smooth_nodes.NODE_DISPLAY_NAME_MAPPINGS.values()) & set(other.NODE_DISPLAY_NAME_MAPPINGS.values())
+    types = node.INPUT_TYPES()
+    req = types["required"]
+    assert list(types) == ["required"]
+    assert list(req) == ["image", "mask", "radius", "tolerance", "motion", "levels", "search", "smooth"]
+    assert req["image"][0] == "IMAGE" and req["mask"][0] == "MASK"
+    assert req["radius"][0] == "INT" and req["radius"][1] == {**req["radius"][1], "default": 2, "min": 1, "max": 8}
+    assert req["tolerance"][0] == "INT" and req["tolerance"][1] == {**req["tolerance"][1], "default": 24, "min": 0, "max": 255}
+    assert req["motion"][0] == ["background", "picture"] and req["motion"][1]["default"] == "background"
+    assert req["levels"][0] == "INT" and req["levels"][1] == {**req["levels"][1], "default": 4, "min": 1, "max": 6}
+    assert req["search"][0] == "INT" and req["search"][1] == {**req["search"][1], "default": 2, "min": 1, "max": 7}
+    assert req["smooth"][0] == "INT" and req["smooth"][1] == {**req["smooth"][1], "default": 8, "min": 0, "max": 64}
+    for name in req:
+        assert len(req[name][1]["tooltip"]) > 20, name
+    for word in ("boiling", "motion", "neighbouring frames", "tolerance", "multiband blend", "grain", "support", "outlier"):
+        assert word in node.DESCRIPTION, word
+    assert node.RETURN_TYPES == ("IMAGE", "MASK") and node.RETURN_NAMES == ("image", "support")
+    assert node.FUNCTION == "smooth" and callable(getattr(node, node.FUNCTION))
+    if not torch.cuda.is_available():
+        with pytest.raises(RuntimeError, match="no CPU fallback"):
+            node().smooth(torch.zeros(3, 16, 16, 3), torch.zeros(3, 16, 16))
+
+
+def test_modules_have_no_unbound_names():
+    files = [os.path.join(ROOT, "lanpaint_amd", f) for f in ("temporal_smooth.py", "temporal_smooth_nodes.py")]
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "scripts", "check_names.py"), *files], capture_output=True, text=True)
+    assert p.returncode == 0, p.stdout
