@@ -93,11 +93,11 @@ def test_batched_fields_equal_the_single_entries_and_the_restatement():
 
 # ---- stages 3 and 4: one carry, fed with the restatement's inputs ---------------------------------------------------------------------------
 @functools.lru_cache(maxsize=None)
-def _carry_case(H, W, wild):
+def _carry_case(H, W, wild, channels=3):
     """A frame 2 of 5 with random known bits, a random field of up to 2.5 pixels, a random state of both neighbours with origins
     in every frame, and a random `source` under the mask from an earlier pass."""
     rng = _rng(H, W, int(wild), 6)
-    images = (_wild_video if wild else _video)(F, H, W, 3)
+    images = (_wild_video if wild else _video)(F, H, W, channels)
     gh, gw = ref.grid_of(H, W)
     vec = rng.integers(-40, 41, (gh, gw, 2)).astype(np.int32)
     known = (rng.random((3, H, W)) < 0.5).astype(np.uint8)            # of the frames 1, 2, 3
@@ -107,9 +107,9 @@ def _carry_case(H, W, wild):
     return images, vec, known, org, pos, source
 
 
-def _check_carry(H, W, wild, donor, state, reach, nearer):
+def _check_carry(H, W, wild, donor, state, reach, nearer, channels=3):
     t = 2
-    images, vec, known, org, pos, source_t = _carry_case(H, W, wild)
+    images, vec, known, org, pos, source_t = _carry_case(H, W, wild, channels)
     known_t, known_s = known[1], known[donor - 1]
     want_org, want_pos = tref.carry(t, known_t, donor, known_s, vec, (org, pos) if state else None, reach)
     write = tref.choose(t, known_t, want_org, source_t, nearer)
@@ -125,7 +125,7 @@ def _check_carry(H, W, wild, donor, state, reach, nearer):
     d_filled, d_source, d_remaining = _dev(filled), _dev(source), _dev(remaining)
     got_org, got_pos = tf.carry(_dev(vec), _dev(known_t), _dev(known_s), (_dev(org), _dev(pos)) if state else None, _dev(images),
                                 d_filled, d_source, d_remaining, t, donor, reach, nearer)
-    what = ((H, W), wild, donor, state, reach, nearer)
+    what = ((H, W), wild, donor, state, reach, nearer, channels)
     under = known_t == 0                                               # the state planes matter under the mask only
     _same(got_org.cpu().numpy()[under], want_org[under], (what, "org"))
     _same(got_pos.cpu().numpy()[under], want_pos[under], (what, "pos"))
