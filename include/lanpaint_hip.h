@@ -1997,6 +1997,70 @@ typedef struct lp_tsmooth_desc {
 } lp_tsmooth_desc;
 LP_API int lp_tsmooth(const lp_tsmooth_desc* desc, void* stream);
 
+/* ---- Video shot detect (beyond the reference) ---------------------------------------------------------------------------------------
+ * Every temporal link of the video chain (the propagates, the stabilize, the two temporal fills, the temporal smooth) takes a clip
+ * as one continuous shot.  Across a hard cut the block matcher still returns a field, and that field means nothing.  These entries
+ * give the boundary signal: two integer scores per pair of neighbouring frames and a decision that turns them into a shot index per
+ * frame, so that the host can run every link shot by shot.  Integers throughout: the same bits on every run, and the chunking of
+ * the frames cannot change a bit, because a score depends on its two frames only.  Everything stays on the device.
+ *   limits    level 0..LP_PROP_MAX_LEVELS - 1; search R in 1..LP_SHOT_MAX_SEARCH = 3 ((2R + 1)^2 <= 49 displacements: the lanes of
+ *             one wave); frames F in 1..65535; sides of the plane 1..LP_VMASK_MAX_SIDE.
+ *   plane     Y_t, the plane of frame t, is level `level` of the 8-bit luma pyramid of the propagate section (stages 1 and 2, built
+ *             by lp_prop_luma with levels = level + 1): h x w with N = h w pixels.  clamp(i) holds a coordinate inside the plane.
+ *   A[t]      the motion-compensated residual of the pair (t, t + 1), t = 0..F - 2.  Blocks of LP_PROP_BLOCK = 8 are aligned to the
+ *             plane's origin and cut at its edges.  For block b with pixel set P and every displacement d = (dy, dx) in [-R, R]^2:
+ *             SAD_b(d) = sum over p in P of |Y_t(p) - Y_{t+1}(clamp(p + d))|.  A[t] = sum over b of min over d of SAD_b(d).
+ *             A[t] <= 255 * 2^28: an int64.
+ *   B[t]      the histogram change of the pair.  h_t[k] = the number of pixels of Y_t with Y >> 2 == k, k = 0..63;
+ *             B[t] = sum over k of |h_t[k] - h_{t+1}[k]|.  A pixel that changes its bin counts twice: B[t] <= 2 N.
+ *   score     int64 [F - 1, 2]: score[t] = (A[t], B[t]).
+ *   decision  threshold 1..255, hist 0..100, ratio 100..10000, window 1..LP_SHOT_MAX_WINDOW = 16.  cut[t] = 1 iff all of
+ *               A[t] >= threshold * N                     (the mean residual, in grey levels)
+ *               100 * B[t] >= hist * 2 N                  (the share of the pixels that change their bin, in percent)
+ *               100 * A[t] >= ratio * A[u]                for every other pair u != t with |u - t| <= window and 0 <= u <= F - 2.
+ *             Every product stays below 2^50.  The last condition keeps a flash (two high pairs in a row, neither beats the other),
+ *             a run of fast motion and a large object that moves further than the search (its residual is high, its histogram
+ *             stays) from being called cuts.  It also makes `window` the shortest shot that can be told apart: two cuts closer
+ *             than `window` pairs suppress one another unless one residual is `ratio` percent of the other, and with ratio > 100
+ *             two equal residuals inside a window are never cuts; with ratio = 100 both are.
+ *   shot      int32 [F]: shot[0] = 0, shot[f] = sum over t < f of cut[t].  F = 1 gives shot = [0]; there is no score.
+ * Not done: dissolves, fades and wipes are not detected (no pair of such a transition stands out of its neighbours); the
+ * several-key propagates and the colour match's pooling over neighbouring frames have no shot-aware form.
+ * Launches (csrc/shot_kernel.hip).  lp_shot_measure, for the `frames` planes of a chunk: the histograms and the A words are
+ * cleared, then one launch for all frames, a 256-lane block per 32 x 32 tile and frame.  The block adds its pixels into per-wave
+ * 64-bin histograms in LDS, folded once per block into hist[t] with at most one integer atomic per bin.  If frame t + 1 is in the
+ * chunk the tile of t and the (32 + 2R)^2 clamped window of t + 1 are staged in LDS once and the tile's sixteen 8 x 8 blocks are
+ * matched, one per wave and round, the displacements over the lanes (v_alignbyte_b32 cuts four pixels out of two dwords, v_sad_u8
+ * adds four absolute differences), a wave-wide minimum per block; the tile leaves one 64-bit integer atomic into A[t].  A second,
+ * small launch folds hist[t], hist[t + 1] into B[t].  Integer sums: no order changes a bit.  score receives frames - 1 rows, hist
+ * (int32 [frames, 64], a workspace that holds the histograms afterwards) frames rows.  Neighbouring chunks share one frame.
+ * lp_shot_decide is one block: lanes stride over the pairs, every pair looks at up to 2 window neighbours, the cut bits of 64
+ * pairs are one ballot word in LDS, and a scan over the words' counts gives `shot`.  No scratch, no floating point.
+ * LP_E_INVALID: a null pointer (score may be null exactly when frames == 1); frames < 1; a side, search, stride (< height * width
+ * with frames > 1), n_pixels (1..2^28), threshold, hist, ratio or window outside its range; hist, score and plane, or shot and
+ * score, aliasing.  LP_E_UNSUPPORTED: frames > 65535.  All checked before any HIP call. */
+#define LP_SHOT_MAX_SEARCH 3
+#define LP_SHOT_MAX_WINDOW 16
+#define LP_SHOT_BINS       64
+
+typedef struct lp_shot_measure_desc {
+    int32_t frames, height, width, search;        /* the chunk's frames; height x width: the plane's own sides               */
+    const uint8_t* plane;                         /* frame 0's plane [height, width] (its level's address in the pyramid)    */
+    int64_t        stride;                        /* bytes from a frame's plane to the next frame's                          */
+    int32_t*       hist;                          /* out, [frames, LP_SHOT_BINS]                                             */
+    int64_t*       score;                         /* out, [frames - 1, 2]: (A, B) per pair                                   */
+} lp_shot_measure_desc;
+LP_API int lp_shot_measure(const lp_shot_measure_desc* desc, void* stream);
+
+typedef struct lp_shot_decide_desc {
+    int32_t frames, threshold, hist, ratio;
+    int32_t window, reserved0;
+    int64_t        n_pixels;                      /* N = the plane's height * width                                          */
+    const int64_t* score;                         /* [frames - 1, 2]                                                         */
+    int32_t*       shot;                          /* out, [frames]                                                           */
+} lp_shot_decide_desc;
+LP_API int lp_shot_decide(const lp_shot_decide_desc* desc, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -504,6 +504,22 @@ class LpTsmoothDesc(C.Structure):
                 ("images", C.c_void_p), ("out", C.c_void_p), ("support", C.c_void_p)]
 
 
+LP_SHOT_MAX_SEARCH = 3
+LP_SHOT_MAX_WINDOW = 16
+LP_SHOT_BINS = 64
+
+
+class LpShotMeasureDesc(C.Structure):
+    _fields_ = [("frames", C.c_int32), ("height", C.c_int32), ("width", C.c_int32), ("search", C.c_int32),
+                ("plane", C.c_void_p), ("stride", C.c_int64), ("hist", C.c_void_p), ("score", C.c_void_p)]
+
+
+class LpShotDecideDesc(C.Structure):
+    _fields_ = [("frames", C.c_int32), ("threshold", C.c_int32), ("hist", C.c_int32), ("ratio", C.c_int32),
+                ("window", C.c_int32), ("reserved0", C.c_int32), ("n_pixels", C.c_int64), ("score", C.c_void_p),
+                ("shot", C.c_void_p)]
+
+
 def prop_level_shape(height, width, level):
     """Level `level` of a height x width plane: ceil(height / 2^level) x ceil(width / 2^level)."""
     return (int(height) + (1 << level) - 1) >> level, (int(width) + (1 << level) - 1) >> level
@@ -633,6 +649,8 @@ EXPORTS = {
     "lp_tfill_carry": (C.c_int, [C.POINTER(LpTfillCarryDesc), C.c_void_p]),
     "lp_tfill_carry_pair": (C.c_int, [C.POINTER(LpTfillCarryPairDesc), C.c_void_p]),
     "lp_tsmooth": (C.c_int, [C.POINTER(LpTsmoothDesc), C.c_void_p]),
+    "lp_shot_measure": (C.c_int, [C.POINTER(LpShotMeasureDesc), C.c_void_p]),
+    "lp_shot_decide": (C.c_int, [C.POINTER(LpShotDecideDesc), C.c_void_p]),
 }
 
 
