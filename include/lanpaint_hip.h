@@ -1996,6 +1996,81 @@ typedef struct lp_tsmooth_desc {
     int32_t*       support;                       /* [frames, height, width]: likewise                                       */
 } lp_tsmooth_desc;
 LP_API int lp_tsmooth(const lp_tsmooth_desc* desc, void* stream);
+/* The robust form below (lp_tsmooth_robust) takes a temporal median as the reference value, so that an outlier frame is repaired. */
+
+/* ---- Robust video temporal smooth (beyond the reference) ----------------------------------------------------------------------------
+ * lp_tsmooth compares every neighbouring sample with the frame's own pixel, so the one frame in which the sampler invented
+ * something else under the mask -- a "pop", the defect a viewer sees first -- keeps its value, and a neighbour of that frame loses
+ * its whole chain on that side.  This entry is a second, stricter form beside it: the reference value is the temporal median of
+ * the samples along the motion, every sample is compared with that, and a pixel that disagrees with it is overruled when two
+ * witnesses stand against it.  It takes the plain smooth's place: decode / stitch -> robust temporal smooth -> multiband blend ->
+ * grain match.  Integer arithmetic decides where every sample is taken, which is the reference and what counts; the sums are fp32
+ * in a fixed order.  Everything stays on the device.
+ *   limits, mask, fields, `sample`, code, the 1/16-pixel positions and the integer weights w_k = C(2R, R + k) are those of the
+ *             lp_tsmooth section, word for word.
+ *   walk      per masked pixel (y, x) of frame t and per direction d in {-1, +1}.  p_0 = (16 y, 16 x).  For k = 1..R:
+ *             u = t + (k - 1) d, v = t + k d.  The chain ends if v is outside the clip.  Otherwise i = (p_{k-1} + 8) >> 4 per axis
+ *             and q = p_{k-1} + V_{u->v}(i); the chain ends if q is outside 0..16 (n - 1) on either axis.  Otherwise p_k = q and
+ *             the step exists: it gives the sample `sample`(images[v], q).  A chain does NOT end at a sample that is rejected
+ *             later: the trajectory depends on the fields only, so a pop frame in between does not cut off the frames behind it.
+ *             The order index o is 0 for the own pixel, s_0 = x = images[t, y, x]; k for step k into the past (d = -1); R + k for
+ *             step k into the future.  X is the set of the o that exist, n = |X| <= 2R + 1.
+ *   luma      Y_o = the propagate section's 8-bit luma of the sample's codes: (77 c0 + 150 c1 + 29 c2 + 128) >> 8 with
+ *             c_i = code(s_o[i]) where channels >= 3, else c0 -- the quantity the checked temporal fill compares.
+ *   reference if n < 3, j* = 0.  Otherwise X is sorted by the pair (Y_o, o) ascending and j* is the element at 0-based position
+ *             (n - 1) >> 1: the lower median, ties broken by the walk's order.  r = s_{j*}, a whole sample with every channel; it
+ *             is x itself when j* = 0.
+ *   accepted  o in X is accepted iff max over channels of |code(s_o[c]) - code(r[c])| <= tolerance.  a = the number of accepted
+ *             o != 0.  LP_TSMOOTH_ROBUST_QUORUM = 2 is a constant of the rule, not a parameter.
+ *   result    under the mask, three cases; fp32, the difference, the product, the sum and the division each rounded on its own (no
+ *             FMA), the terms in the order of the walk (o = 1, .., R, then R + 1, .., 2R: past before future, nearer before
+ *             farther), w of o being w_k of its step k.
+ *             1. the own pixel is accepted: acc = sum of w (s_o - x) over the accepted o != 0, W = w_0 + their weights,
+ *                out = x + acc / W, and with a = 0 the output keeps x bit for bit.  support = a, replaced = 0.
+ *             2. the own pixel is not accepted and a >= LP_TSMOOTH_ROBUST_QUORUM -- two witnesses overrule the pixel, the reference
+ *                and at least one more sample: acc = sum of w (s_o - r) over the accepted o not in {0, j*}, W = the weights of the
+ *                accepted o != 0 (that of j* among them, w_0 not), out = r + acc / W.  support = a, replaced = 1.
+ *             3. the own pixel is not accepted and a < LP_TSMOOTH_ROBUST_QUORUM: out = x bit for bit, support = 0, replaced = 0.
+ *             W <= 65536, exact in fp32.
+ *   outside   the mask out = images bit for bit, support = -1 and replaced = -1.
+ * Non-finite values behave as in the plain rule: a NaN or a negative value has code 0 and +inf code 255, and the fp32 arithmetic
+ * is taken as it comes.
+ * What follows from the rule (checked on the clips of tests/test_temporal_smooth_host.py): where nothing is rejected under either
+ * reference -- a pan with alternating flicker below the tolerance -- out and support are the plain rule's bit for bit and replaced
+ * is 0 under the mask.  A pop of one frame (+64/256 under the mask of one frame of a clean pan) is removed: the result is the clean
+ * clip bit for bit in every frame for R = 1, 2, 3, replaced == 1 on every masked pixel of that frame and nowhere else, where the
+ * plain rule returns the input.  The same pop on two frames in a row is removed for R = 2, 3 and returned bit for bit for R = 1:
+ * whatever lasts R frames or fewer under the mask is an outlier and is removed on purpose, whatever lasts longer stays.  A clip of
+ * one frame returns the images; a clip of two frames gives the plain rule's bits (n < 3: the reference is the own pixel and a chain
+ * has one step); an empty mask returns the images; a still clip is returned bit for bit; nothing outside the mask ever changes; the
+ * same bits on every run and for every chunking.
+ * Not done: a weighted median; a quorum the caller sets; motion boundaries finer than a block; a soft mask edge.
+ * Launch (csrc/temporal_smooth_kernel.hip): as lp_tsmooth's, one for the frames first .. first + count - 1, a block per 32 x 32
+ * tile and frame, a lane per pixel, the wave-wide copy where nothing is masked.  A masked pixel walks up to three times -- the
+ * positions are integers and come out the same --: for the lumas, packed four to a dword and ranked by counting; to j* for r; and
+ * for the acceptance and the sums, four channels at a time.  The fields, `known` and the rows that must be covered are those of
+ * lp_tsmooth.  The frames first .. first + count - 1 of out, support and replaced are written whole.  No scratch, no atomics, no
+ * LDS.
+ * LP_E_INVALID and LP_E_UNSUPPORTED: as lp_tsmooth, with `replaced` not null and out, support and replaced aliasing neither an
+ * input nor one another.  All checked before any HIP call. */
+#define LP_TSMOOTH_ROBUST_QUORUM 2
+
+typedef struct lp_tsmooth_robust_desc {
+    int32_t frames, height, width, channels;      /* lp_tsmooth_desc's fields, in its order                                  */
+    int32_t first, count;
+    int32_t radius, tolerance;
+    int32_t fwd_first, fwd_count;
+    int32_t bwd_first, bwd_count;
+    const int32_t* fwd;
+    const int32_t* bwd;
+    const uint8_t* known;
+    int64_t        known_stride;
+    const float*   images;
+    float*         out;
+    int32_t*       support;
+    int32_t*       replaced;                      /* [frames, height, width]: frames first .. are written, whole             */
+} lp_tsmooth_robust_desc;
+LP_API int lp_tsmooth_robust(const lp_tsmooth_robust_desc* desc, void* stream);
 
 /* ---- Video shot detect (beyond the reference) ---------------------------------------------------------------------------------------
  * Every temporal link of the video chain (the propagates, the stabilize, the two temporal fills, the temporal smooth) takes a clip

@@ -504,6 +504,13 @@ class LpTsmoothDesc(C.Structure):
                 ("images", C.c_void_p), ("out", C.c_void_p), ("support", C.c_void_p)]
 
 
+LP_TSMOOTH_ROBUST_QUORUM = 2
+
+
+class LpTsmoothRobustDesc(C.Structure):
+    _fields_ = LpTsmoothDesc._fields_ + [("replaced", C.c_void_p)]
+
+
 LP_SHOT_MAX_SEARCH = 3
 LP_SHOT_MAX_WINDOW = 16
 LP_SHOT_BINS = 64
@@ -649,6 +656,7 @@ EXPORTS = {
     "lp_tfill_carry": (C.c_int, [C.POINTER(LpTfillCarryDesc), C.c_void_p]),
     "lp_tfill_carry_pair": (C.c_int, [C.POINTER(LpTfillCarryPairDesc), C.c_void_p]),
     "lp_tsmooth": (C.c_int, [C.POINTER(LpTsmoothDesc), C.c_void_p]),
+    "lp_tsmooth_robust": (C.c_int, [C.POINTER(LpTsmoothRobustDesc), C.c_void_p]),
     "lp_shot_measure": (C.c_int, [C.POINTER(LpShotMeasureDesc), C.c_void_p]),
     "lp_shot_decide": (C.c_int, [C.POINTER(LpShotDecideDesc), C.c_void_p]),
 }

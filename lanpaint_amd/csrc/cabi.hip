@@ -84,6 +84,7 @@ int tfill_known_dispatch(const lp_tfill_known_desc* d, hipStream_t stream);
 int tfill_carry_dispatch(const lp_tfill_carry_desc* d, hipStream_t stream);
 int tfill_carry_pair_dispatch(const lp_tfill_carry_pair_desc* d, hipStream_t stream);
 int tsmooth_dispatch(const lp_tsmooth_desc* d, hipStream_t stream);
+int tsmooth_robust_dispatch(const lp_tsmooth_robust_desc* d, hipStream_t stream);
 int shot_measure_dispatch(const lp_shot_measure_desc* d, hipStream_t stream);
 int shot_decide_dispatch(const lp_shot_decide_desc* d, hipStream_t stream);
 int reshape_mask_dispatch(const float* src, int sb, int sc, int sf, int sh, int sw, float* dst, int db, int dc, int df,
@@ -297,6 +298,7 @@ int lp_tfill_carry_pair(const lp_tfill_carry_pair_desc* desc, void* stream) {
 }
 
 int lp_tsmooth(const lp_tsmooth_desc* desc, void* stream) { return lp::tsmooth_dispatch(desc, as_stream(stream)); }
+int lp_tsmooth_robust(const lp_tsmooth_robust_desc* desc, void* stream) { return lp::tsmooth_robust_dispatch(desc, as_stream(stream)); }
 
 int lp_shot_measure(const lp_shot_measure_desc* desc, void* stream) { return lp::shot_measure_dispatch(desc, as_stream(stream)); }
 

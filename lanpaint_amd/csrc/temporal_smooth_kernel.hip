@@ -18,6 +18,14 @@
 // register, so nothing lives in scratch.  The sums keep the rule's order: past before future, nearer before farther.
 // fp32 in a fixed order, every operation rounded on its own (__fmul_rn / __fadd_rn / __fsub_rn / __fdiv_rn: nothing contracts).
 // No atomics.
+//
+//   robust   (lp_tsmooth_robust, the header's robust section) the same geometry and the same copy of what is not masked.  A masked
+//            pixel walks up to three times, the positions being integers that come out the same: for the 8-bit lumas of the up to
+//            17 samples, a byte each in three named registers (two 64-bit words and one more), ranked by counting -- a candidate
+//            in a register against the others named by constants --, which gives j*; along the chain of j* for the position of r;
+//            and for the acceptance against r and the sums, the first four channels while the walk decides, every further four
+//            in a walk of their own.  What exists is two counts, what is accepted a bit mask in one register.  No array is
+//            indexed by a register: nothing in scratch, no LDS.
 #include "lp_common.h"
 
 namespace lp {
@@ -233,13 +241,254 @@ __global__ __launch_bounds__(kTile * kTile) void lp_tsmooth_kernel(const smooth_
     }
 }
 
+// ---- the robust form (lp_tsmooth_robust): the reference is the temporal median of the samples along the motion ----------------------
+constexpr int kSlots = 2 * LP_TSMOOTH_MAX_RADIUS + 1;                                // order indices o = 0 .. 16
+
+// One step of direction d on from p, step k of the walk from frame t: false where the chain ends (the clip's end, or q leaves the
+// plane); else p moves on to q.  The fields alone decide.
+__device__ __forceinline__ bool advance(const smooth_args& a, int t, int d, int k, int& py, int& px) {
+    const int u = t + (k - 1) * d, v = u + d;
+    if (v < 0 || v >= a.frames) return false;
+    const int64_t field = static_cast<int64_t>(a.gh) * a.gw * 2;
+    int qy, qx;
+    if (!step(a, d > 0 ? a.fwd + (u - a.fwd0) * field : a.bwd + (u - a.bwd0) * field, py, px, qy, qx)) return false;
+    py = qy;
+    px = qx;
+    return true;
+}
+
+__device__ __forceinline__ int luma_of(const float (&s)[4], int C) {                 // the propagate section's 8-bit luma of the codes
+    const int c0 = code_of(s[0]);
+    return C >= 3 ? (77 * c0 + 150 * code_of(s[1]) + 29 * code_of(s[2]) + 128) >> 8 : c0;
+}
+
+// The lumas of the order indices, a byte each: 0..7 in `lo`, 8..15 in `hi`, 16 in `top`.  Three named registers and no array, so
+// that an index in a register selects and shifts and nothing goes to scratch.
+struct lumas17 {
+    uint64_t lo, hi;
+    uint32_t top;
+};
+
+__device__ __forceinline__ void put_luma(lumas17& pk, int o, int Y) {
+    const uint64_t b = static_cast<uint64_t>(Y) << ((o & 7) * 8);
+    pk.lo |= o < 8 ? b : 0;
+    pk.hi |= o >= 8 && o < 16 ? b : 0;
+    pk.top = o == 16 ? static_cast<uint32_t>(Y) : pk.top;
+}
+
+__device__ __forceinline__ int get_luma(const lumas17& pk, int o) {
+    const uint64_t word = o < 8 ? pk.lo : pk.hi;
+    return o == 16 ? static_cast<int>(pk.top) : static_cast<int>((word >> ((o & 7) * 8)) & 255u);
+}
+
+// The first walk: the lumas of the steps that exist in direction d go to the bytes o0 + 1 ..; returns how many exist.
+__device__ __forceinline__ int lumas(const smooth_args& a, int t, int d, int o0, int y, int x, lumas17& pk) {
+    int py = 16 * y, px = 16 * x, n = 0;
+#pragma unroll 1
+    for (int k = 1; k <= a.radius; ++k) {
+        if (!advance(a, t, d, k, py, px)) break;
+        float s[4];
+        sample4(taps_of(a, t + k * d, py, px), a.C, 0, s);
+        put_luma(pk, o0 + k, luma_of(s, a.C));
+        ++n;
+    }
+    return n;
+}
+
+// how many of the existing keys Y_j * 32 + j, j = J .. J + 7, of a word lie in front of `key`
+template <int J>
+__device__ __forceinline__ int in_front(uint64_t word, uint32_t exist, int key) {
+    int before = 0;
+#pragma unroll
+    for (int b = 0; b < 8; ++b) {
+        const int other = (static_cast<int>((word >> (8 * b)) & 255u) << 5) | (J + b);
+        before += (other < key ? 1 : 0) & static_cast<int>((exist >> (J + b)) & 1u);
+    }
+    return before;
+}
+
+// The lower median of the existing o by (Y_o, o): the one with exactly (n - 1) >> 1 others in front of it.  The keys Y_o * 32 + o
+// are all different.  The candidates run over a register, the others over constants; with R < 4 `hi` and `top` hold nothing.
+__device__ __forceinline__ int median_of(const lumas17& pk, uint32_t exist, int n, int radius) {
+    const int want = (n - 1) >> 1;
+    int found = 0;
+#pragma unroll 1
+    for (int i = 0; i <= 2 * radius; ++i) {
+        const int key = (get_luma(pk, i) << 5) | i;
+        int before = in_front<0>(pk.lo, exist, key);
+        if (radius >= 4) {
+            before += in_front<8>(pk.hi, exist, key);
+            before += (((static_cast<int>(pk.top) << 5) | (kSlots - 1)) < key ? 1 : 0) & static_cast<int>((exist >> (kSlots - 1)) & 1u);
+        }
+        found = ((exist >> i) & 1u) && before == want ? i : found;
+    }
+    return found;
+}
+
+// Where r is: the own pixel (v < 0) or a position in frame v
+struct ref_at {
+    int v, qy, qx;
+};
+
+__device__ __forceinline__ void ref4(const smooth_args& a, const ref_at& r, const float* __restrict__ own, int c0, float (&v)[4]) {
+    if (r.v < 0)
+        own4(own, a.C, c0, v);
+    else
+        sample4(taps_of(a, r.v, r.qy, r.qx), a.C, c0, v);
+}
+
+// The chain of direction d again, all `steps` of it that exist, for the channels c0 .. c0 + 3: the sums of the accepted samples
+// about `base` (x or r of these channels), the sample `skip` left out of the sum (j* where r overrules the pixel; -1 else).
+// Decide (c0 = 0): a sample is accepted where no channel's code is more than `tolerance` from r's (r4: its first four channels);
+// its bit goes into `accepted` and its weight into W.  Else the bits decide.
+template <bool Decide>
+__device__ __forceinline__ void robust_chain(const smooth_args& a, int t, int d, int steps, int o0, int y, int x, const float* __restrict__ own,
+                                             int c0, const float (&base)[4], const float (&r4)[4], const ref_at& r, int skip,
+                                             float (&acc)[4], int& W, uint32_t& accepted) {
+    int py = 16 * y, px = 16 * x, w = a.w0;
+#pragma unroll 1
+    for (int k = 1; k <= steps; ++k) {
+        advance(a, t, d, k, py, px);                                     // exists: the first walk came this far
+        const tap_rows taps = taps_of(a, t + k * d, py, px);
+        float s[4];
+        sample4(taps, a.C, c0, s);
+        w = w * (a.radius - k + 1) / (a.radius + k);
+        const int o = o0 + k;
+        bool ok;
+        if (Decide) {
+            int apart = apart4(s, r4);
+#pragma unroll 1
+            for (int c = 4; c < a.C && apart <= a.tolerance; c += 4) {
+                float sc[4], rc[4];
+                sample4(taps, a.C, c, sc);
+                ref4(a, r, own, c, rc);
+                apart = max(apart, apart4(sc, rc));
+            }
+            ok = apart <= a.tolerance;
+            if (ok) {
+                accepted |= 1u << o;
+                W += w;
+            }
+        } else {
+            ok = (accepted >> o) & 1u;
+        }
+        if (ok && o != skip) {
+            const float wf = static_cast<float>(w);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) acc[j] = __fadd_rn(acc[j], __fmul_rn(wf, __fsub_rn(s[j], base[j])));
+        }
+    }
+}
+
+struct robust_args {
+    smooth_args s;
+    int32_t*    replaced;        // [frames, H, W]
+};
+
+// The plain kernel's geometry and its copy of what is not masked; a masked pixel ranks its lumas and walks again.
+__global__ __launch_bounds__(kTile * kTile) void lp_tsmooth_robust_kernel(const robust_args ra) {
+    const smooth_args& a = ra.s;
+    const int H = a.H, W = a.W, C = a.C, R = a.radius;
+    const int ly = threadIdx.x >> 5, lx = threadIdx.x & 31, y = blockIdx.y * kTile + ly, x = blockIdx.x * kTile + lx;
+    const int t = a.first + static_cast<int>(blockIdx.z);
+    const int64_t p = static_cast<int64_t>(y) * W + x;
+    const bool inside = y < H && x < W;
+    const bool masked = inside && a.known[static_cast<int64_t>(blockIdx.z) * a.known_stride + p] == 0;
+    const int64_t at = static_cast<int64_t>(t) * H * W + p;
+    const float* __restrict__ own = a.images + at * C;
+    float* __restrict__ out = a.out + at * C;
+    if (__all(!masked)) {
+        if (inside) {
+            a.support[at] = -1;
+            ra.replaced[at] = -1;
+        }
+        const int y0 = static_cast<int>(blockIdx.y) * kTile + (ly & ~1);
+        if (y0 >= H) return;
+        const int tw = min(kTile, W - static_cast<int>(blockIdx.x) * kTile), rows = min(2, H - y0), lane = threadIdx.x & (kWave - 1);
+        const int64_t pitch = static_cast<int64_t>(W) * C;
+        const int64_t corner = ((static_cast<int64_t>(t) * H + y0) * W + static_cast<int64_t>(blockIdx.x) * kTile) * C;
+        if (((pitch | (tw * C)) & 3) == 0 && ((reinterpret_cast<uintptr_t>(a.images) | reinterpret_cast<uintptr_t>(a.out)) & 15) == 0)
+            copy_rows(reinterpret_cast<const float4*>(a.images + corner), reinterpret_cast<float4*>(a.out + corner), rows, tw * C / 4, pitch / 4, lane);
+        else
+            copy_rows(a.images + corner, a.out + corner, rows, tw * C, pitch, lane);
+        return;
+    }
+    if (!inside) return;
+    if (!masked) {
+#pragma unroll 1
+        for (int c = 0; c < C; ++c) out[c] = own[c];
+        a.support[at] = -1;
+        ra.replaced[at] = -1;
+        return;
+    }
+    // the first walk: the lumas
+    float x4[4];
+    own4(own, C, 0, x4);
+    lumas17 pk = {static_cast<uint64_t>(luma_of(x4, C)), 0, 0};
+    const int n_past = lumas(a, t, -1, 0, y, x, pk), n_next = lumas(a, t, +1, R, y, x, pk);
+    const int n = 1 + n_past + n_next;
+    const uint32_t exist = 1u | (((1u << n_past) - 1u) << 1) | (((1u << n_next) - 1u) << (R + 1));
+    const int js = n < 3 ? 0 : median_of(pk, exist, n, R);
+    // the second walk: to j*
+    ref_at r = {-1, 0, 0};
+    if (js) {
+        const int d = js <= R ? -1 : +1, steps = js <= R ? js : js - R;
+        r.qy = 16 * y;
+        r.qx = 16 * x;
+#pragma unroll 1
+        for (int k = 1; k <= steps; ++k) advance(a, t, d, k, r.qy, r.qx);
+        r.v = t + steps * d;
+    }
+    float r4[4];
+    ref4(a, r, own, 0, r4);
+    int apart = apart4(x4, r4);
+#pragma unroll 1
+    for (int c = 4; c < C && apart <= a.tolerance; c += 4) {
+        float xc[4], rc[4];
+        own4(own, C, c, xc);
+        ref4(a, r, own, c, rc);
+        apart = max(apart, apart4(xc, rc));
+    }
+    const bool own_ok = apart <= a.tolerance;                            // with j* = 0 always
+    // the third walk: what is accepted, and the first four channels' sums about x, or about r where r may overrule the pixel
+    const int skip = own_ok ? -1 : js;
+    uint32_t accepted = 0;
+    int Wsum = own_ok ? a.w0 : 0;
+    float base[4], acc[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+    for (int j = 0; j < 4; ++j) base[j] = own_ok ? x4[j] : r4[j];
+    robust_chain<true>(a, t, -1, n_past, 0, y, x, own, 0, base, r4, r, skip, acc, Wsum, accepted);
+    robust_chain<true>(a, t, +1, n_next, R, y, x, own, 0, base, r4, r, skip, acc, Wsum, accepted);
+    const int count = __popc(accepted);
+    const bool moved = own_ok ? count > 0 : count >= LP_TSMOOTH_ROBUST_QUORUM;
+    a.support[at] = moved ? count : 0;
+    ra.replaced[at] = !own_ok && moved ? 1 : 0;
+    const float Wf = static_cast<float>(Wsum);
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+        if (j < C) out[j] = moved ? __fadd_rn(base[j], __fdiv_rn(acc[j], Wf)) : x4[j];
+#pragma unroll 1
+    for (int c0 = 4; c0 < C; c0 += 4) {
+        float xc[4], bc[4], ac[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+        own4(own, C, c0, xc);
+        ref4(a, r, own, c0, bc);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) bc[j] = own_ok ? xc[j] : bc[j];
+        if (moved) {
+            int unused = 0;
+            robust_chain<false>(a, t, -1, n_past, 0, y, x, own, c0, bc, bc, r, skip, ac, unused, accepted);
+            robust_chain<false>(a, t, +1, n_next, R, y, x, own, c0, bc, bc, r, skip, ac, unused, accepted);
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            if (c0 + j < C) out[c0 + j] = moved ? __fadd_rn(bc[j], __fdiv_rn(ac[j], Wf)) : xc[j];
+    }
+}
+
 bool side_ok(int s) { return s > 0 && s <= LP_VMASK_MAX_SIDE; }
 
-}  // namespace
-
-int tsmooth_dispatch(const lp_tsmooth_desc* dp, hipStream_t stream) {
-    if (!dp) return LP_E_INVALID;
-    const lp_tsmooth_desc& d = *dp;
+// The checks both entries share, and the kernel's arguments; `extra` is the robust form's third output (null: the plain form)
+int smooth_args_of(const lp_tsmooth_desc& d, const void* extra, smooth_args& a) {
     if (d.frames < 1 || !side_ok(d.height) || !side_ok(d.width) || d.channels < 1 || d.channels > LP_DETAIL_MAX_CHANNELS) return LP_E_INVALID;
     if (d.radius < 1 || d.radius > LP_TSMOOTH_MAX_RADIUS || d.tolerance < 0 || d.tolerance > 255) return LP_E_INVALID;
     if (d.frames > 65535) return LP_E_UNSUPPORTED;
@@ -257,7 +506,9 @@ int tsmooth_dispatch(const lp_tsmooth_desc* dp, hipStream_t stream) {
     for (const void* q : in)
         if (q && (q == d.out || q == d.support)) return LP_E_INVALID;
     if (static_cast<const void*>(d.out) == static_cast<const void*>(d.support)) return LP_E_INVALID;
-    smooth_args a = {};
+    for (const void* q : in)
+        if (q && q == extra) return LP_E_INVALID;
+    if (extra && (extra == static_cast<const void*>(d.out) || extra == static_cast<const void*>(d.support))) return LP_E_INVALID;
     a.fwd = d.fwd;
     a.bwd = d.bwd;
     a.known = d.known;
@@ -278,9 +529,35 @@ int tsmooth_dispatch(const lp_tsmooth_desc* dp, hipStream_t stream) {
     a.tolerance = d.tolerance;
     a.w0 = 1;
     for (int k = 1; k <= d.radius; ++k) a.w0 = a.w0 * (d.radius + k) / k;                // C(2R, R): C(R + k, k) at every step
+    return LP_OK;
+}
+
+}  // namespace
+
+int tsmooth_dispatch(const lp_tsmooth_desc* dp, hipStream_t stream) {
+    if (!dp) return LP_E_INVALID;
+    smooth_args a = {};
+    const int status = smooth_args_of(*dp, nullptr, a);
+    if (status != LP_OK) return status;
+    const dim3 grid(static_cast<uint32_t>((dp->width + kTile - 1) / kTile), static_cast<uint32_t>((dp->height + kTile - 1) / kTile),
+                    static_cast<uint32_t>(dp->count));
+    hipLaunchKernelGGL(lp_tsmooth_kernel, grid, dim3(kTile * kTile), 0, stream, a);
+    return hipGetLastError() == hipSuccess ? LP_OK : LP_E_LAUNCH;
+}
+
+int tsmooth_robust_dispatch(const lp_tsmooth_robust_desc* dp, hipStream_t stream) {
+    if (!dp) return LP_E_INVALID;
+    if (!dp->replaced) return LP_E_INVALID;
+    const lp_tsmooth_desc d = {dp->frames, dp->height, dp->width, dp->channels, dp->first, dp->count, dp->radius, dp->tolerance,
+                               dp->fwd_first, dp->fwd_count, dp->bwd_first, dp->bwd_count, dp->fwd, dp->bwd, dp->known, dp->known_stride,
+                               dp->images, dp->out, dp->support};
+    robust_args ra = {};
+    const int status = smooth_args_of(d, dp->replaced, ra.s);
+    if (status != LP_OK) return status;
+    ra.replaced = dp->replaced;
     const dim3 grid(static_cast<uint32_t>((d.width + kTile - 1) / kTile), static_cast<uint32_t>((d.height + kTile - 1) / kTile),
                     static_cast<uint32_t>(d.count));
-    hipLaunchKernelGGL(lp_tsmooth_kernel, grid, dim3(kTile * kTile), 0, stream, a);
+    hipLaunchKernelGGL(lp_tsmooth_robust_kernel, grid, dim3(kTile * kTile), 0, stream, ra);
     return hipGetLastError() == hipSuccess ? LP_OK : LP_E_LAUNCH;
 }
 

@@ -27,6 +27,8 @@ per_shot(fn, ranges, clips, *args, frame_outputs=(), **kw)
         the outputs joined along the frames; see the function.
 temporal_fill_shots, temporal_fill_checked_shots, temporal_smooth_shots, stabilize_masks_shots, propagate_masks_shots
         The five links run per shot; each takes the ranges, or the `shot` tensor, behind the clip.
+temporal_smooth_robust_shots
+        `temporal_smooth_robust`, the robust form of the smooth, per shot in the same way.
 
 include/lanpaint_hip.h (lp_shot_*) states the rule in full: integers throughout, the same bits on every run.  Not done:
 dissolves, fades and wipes are not detected; the several-key propagates and the colour match's pooling over neighbouring
@@ -176,6 +178,14 @@ def temporal_smooth_shots(images, mask, shots, radius=2, tolerance=24, motion="b
     """`temporal_smooth` inside every shot: no chain walks across a cut.  (out, support)."""
     from .temporal_smooth import temporal_smooth
     return per_shot(temporal_smooth, clip_ranges(shots, images.shape[0]), (images, mask), radius, tolerance, motion, levels, search, smooth)
+
+
+def temporal_smooth_robust_shots(images, mask, shots, radius=2, tolerance=24, motion="background", levels=4, search=2, smooth=8):
+    """`temporal_smooth_robust` inside every shot: no chain walks across a cut and no median is taken over two scenes.
+    (out, support, replaced)."""
+    from .temporal_smooth_robust import temporal_smooth_robust
+    return per_shot(temporal_smooth_robust, clip_ranges(shots, images.shape[0]), (images, mask), radius, tolerance, motion, levels, search,
+                    smooth)
 
 
 def stabilize_masks_shots(mask, shots, median=1, smooth=2, grow=0.0, feather=0.0):

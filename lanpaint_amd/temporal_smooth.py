@@ -22,7 +22,7 @@ temporal_smooth(images, mask, radius=2, tolerance=24, motion="background", level
         changes; what is more than `tolerance` away is never averaged in.  include/lanpaint_hip.h (lp_tsmooth) states the rule
         in full.  Not done: a reference value other than the frame's own pixel, so a single outlier frame keeps its value,
         because every neighbour is rejected; motion boundaries finer than a block; a soft mask edge (the multiband blend
-        follows).
+        follows).  `temporal_smooth_robust` is the robust form: a temporal median as the reference repairs an outlier frame.
 
 HIP tensors only, no CPU fallback, no device -> host read.  The fields are independent jobs of lp_prop_match_batch /
 lp_prop_fill_batch as in `temporal_fill`; the gather is one launch for all frames of a chunk (`smooth_frames`).  Pyramids and
@@ -60,14 +60,9 @@ def field_steps(lo, hi, frames, radius):
     return range(lo, min(hi + radius - 1, frames - 1)), range(max(lo - radius + 1, 1), hi)
 
 
-def smooth_frames(fwd, bwd, known, images, radius=2, tolerance=24, first=0, count=None, fwd_first=0, bwd_first=1, out=None,
-                  support=None):
-    """The one launch: the frames first .. first + count - 1 (to the clip's end by default) of `images` fp32 [F, H, W, C] are
-    smoothed into `out` and `support` (new when not given: the other frames are then left unwritten).  `fwd` int32
-    [n, gh, gw, 2]: row j is the level-0 final field of frame fwd_first + j towards the next frame; `bwd` likewise of frame
-    bwd_first + j towards the one before; they must cover `field_steps(first, first + count, F, radius)` and may be None where
-    that is empty.  `known` uint8 [count, H, W], or frame pyramids [count, stride]: the bits of the frames written.
-    Returns (out, support)."""
+def _launch_frames(entry, desc, planes, fwd, bwd, known, images, radius, tolerance, first, count, fwd_first, bwd_first):
+    """What `smooth_frames` and `temporal_smooth_robust.robust_frames` share: the checks, and the call of `entry` with the
+    descriptor `desc`.  `planes`: the outputs behind `out`, int32 [F, H, W] each, as (given or None, name).  Returns the outputs."""
     int_in(radius, 1, MAX_RADIUS, "radius")
     int_in(tolerance, 0, 255, "tolerance")
     images = _images(images)
@@ -76,8 +71,9 @@ def smooth_frames(fwd, bwd, known, images, radius=2, tolerance=24, first=0, coun
     int_in(first, 0, F - 1, "first")
     count = int_in(F - first if count is None else count, 1, F - first, "count")
     dev = images.device
+    (out, _), planes = planes[0], planes[1:]
     out = torch.empty((F, H, W, C), dtype=torch.float32, device=dev) if out is None else out
-    support = torch.empty((F, H, W), dtype=torch.int32, device=dev) if support is None else support
+    planes = [(torch.empty((F, H, W), dtype=torch.int32, device=dev) if t is None else t, what) for t, what in planes]
     grid = _cabi.prop_grid(H, W)
     need = field_steps(first, first + count, F, radius)
     rows = []
@@ -99,20 +95,31 @@ def smooth_frames(fwd, bwd, known, images, radius=2, tolerance=24, first=0, coun
         raise ValueError(f"known must be a contiguous uint8 [{count}, {H}, {W}] or frame pyramids [{count}, stride], got "
                          f"{known.dtype} {list(known.shape)}")
     for t, dtype, shape, what in ((images, torch.float32, (F, H, W, C), "images"), (out, torch.float32, (F, H, W, C), "out"),
-                                  (support, torch.int32, (F, H, W), "support")):
+                                  *((t, torch.int32, (F, H, W), what) for t, what in planes)):
         if require_hip(t, what, __name__).dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous():
             raise ValueError(f"{what} must be a contiguous {dtype} {list(shape)}, got {t.dtype} {list(t.shape)}")
     (f_ptr, f_first, f_n), (b_ptr, b_first, b_n) = rows
-    d = _cabi.LpTsmoothDesc(F, H, W, C, first, count, radius, tolerance, f_first, f_n, b_first, b_n, f_ptr, b_ptr,
-                            known.data_ptr(), known[0].numel(), images.data_ptr(), out.data_ptr(), support.data_ptr())
-    launch("lp_tsmooth", dev, ctypes.byref(d))
-    return out, support
+    d = desc(F, H, W, C, first, count, radius, tolerance, f_first, f_n, b_first, b_n, f_ptr, b_ptr, known.data_ptr(), known[0].numel(),
+             images.data_ptr(), out.data_ptr(), *(t.data_ptr() for t, _ in planes))
+    launch(entry, dev, ctypes.byref(d))
+    return (out, *(t for t, _ in planes))
 
 
-def temporal_smooth(images, mask, radius=2, tolerance=24, motion="background", levels=4, search=2, smooth=8):
-    """What lies under `mask` in the frames `images` [F, H, W, C], pulled towards what the neighbouring frames hold at the same
-    scene point (module docstring): (out fp32 [F, H, W, C], support int32 [F, H, W]) on the images' device.  No device -> host
-    read."""
+def smooth_frames(fwd, bwd, known, images, radius=2, tolerance=24, first=0, count=None, fwd_first=0, bwd_first=1, out=None,
+                  support=None):
+    """The one launch: the frames first .. first + count - 1 (to the clip's end by default) of `images` fp32 [F, H, W, C] are
+    smoothed into `out` and `support` (new when not given: the other frames are then left unwritten).  `fwd` int32
+    [n, gh, gw, 2]: row j is the level-0 final field of frame fwd_first + j towards the next frame; `bwd` likewise of frame
+    bwd_first + j towards the one before; they must cover `field_steps(first, first + count, F, radius)` and may be None where
+    that is empty.  `known` uint8 [count, H, W], or frame pyramids [count, stride]: the bits of the frames written.
+    Returns (out, support)."""
+    return _launch_frames("lp_tsmooth", _cabi.LpTsmoothDesc, ((out, "out"), (support, "support")), fwd, bwd, known, images, radius,
+                          tolerance, first, count, fwd_first, bwd_first)
+
+
+def _over_chunks(frames_fn, planes, images, mask, radius, tolerance, motion, levels, search, smooth):
+    """The whole call of `temporal_smooth` and of `temporal_smooth_robust.temporal_smooth_robust`: the fields chunk by chunk, and
+    `frames_fn` (`smooth_frames` or `robust_frames`) on every chunk, into `out` and `planes` int32 [F, H, W] held whole."""
     _numbers(radius, tolerance, motion)
     _params(levels, search, smooth)
     _images(images)
@@ -122,7 +129,7 @@ def temporal_smooth(images, mask, radius=2, tolerance=24, motion="background", l
     mask = _as_f32c(_mask3(mask, F, H, W).to(dev))
     images = _as_f32c(images)                                            # what is sampled; `out` is written next to it
     out = torch.empty((F, H, W, C), dtype=torch.float32, device=dev)
-    support = torch.empty((F, H, W), dtype=torch.int32, device=dev)
+    outputs = (out, *(torch.empty((F, H, W), dtype=torch.int32, device=dev) for _ in range(planes)))
     stride = _cabi.prop_pyramid_ws_bytes(1, H, W, levels)
     gh, gw = _cabi.prop_grid(H, W)
     per_frame = (3 if motion == "picture" else 2) * stride + 2 * gh * gw * 8     # a frame's pyramids and its two fields
@@ -139,6 +146,13 @@ def temporal_smooth(images, mask, radius=2, tolerance=24, motion="background", l
                                                                           p_hi - p_lo, levels)
             fields = step_fields(luma, weights, steps, H, W, levels, search, smooth)
             del luma, weights
-        smooth_frames(fields[:len(fwd)] if len(fwd) else None, fields[len(fwd):] if len(bwd) else None, known[lo - p_lo:hi - p_lo],
-                      images, radius, tolerance, lo, n, fwd[0] if len(fwd) else 0, bwd[0] if len(bwd) else 0, out, support)
-    return out, support
+        frames_fn(fields[:len(fwd)] if len(fwd) else None, fields[len(fwd):] if len(bwd) else None, known[lo - p_lo:hi - p_lo],
+                  images, radius, tolerance, lo, n, fwd[0] if len(fwd) else 0, bwd[0] if len(bwd) else 0, *outputs)
+    return outputs
+
+
+def temporal_smooth(images, mask, radius=2, tolerance=24, motion="background", levels=4, search=2, smooth=8):
+    """What lies under `mask` in the frames `images` [F, H, W, C], pulled towards what the neighbouring frames hold at the same
+    scene point (module docstring): (out fp32 [F, H, W, C], support int32 [F, H, W]) on the images' device.  No device -> host
+    read."""
+    return _over_chunks(smooth_frames, 1, images, mask, radius, tolerance, motion, levels, search, smooth)

@@ -11,7 +11,8 @@ behind the decode or the stitch and in front of the blend and the grain:
 
 Grain is synthesized afterwards, which is why smoothing it away here is wanted.  A single outlier frame keeps its value, because
 every neighbour is rejected; the mask edge is hard (the multiband blend follows).  Host tensors in and out like the other nodes.
-The reference has no such node.
+The reference has no such node.  LanPaint_VideoTemporalSmoothRobust (lanpaint_amd.temporal_smooth_robust_nodes) is the robust form:
+it repairs the outlier frame.
 
 This module has its own NODE_CLASS_MAPPINGS: merge them with the others' (INTEGRATION.md section 2(b)).
 """
@@ -59,7 +60,7 @@ class LanPaint_VideoTemporalSmooth:
                    "frames hold at the same scene point, as far as that agrees with it within `tolerance`. Put it behind the decode "
                    "or the Detailer stitch and in front of the multiband blend and the grain match: grain is synthesized "
                    "afterwards. `support` is the share of the neighbouring frames that counted, 0 outside the mask. A single "
-                   "outlier frame keeps its value.")
+                   "outlier frame keeps its value; LanPaint_VideoTemporalSmoothRobust repairs it.")
 
     def smooth(self, image, mask, radius=2, tolerance=24, motion="background", levels=4, search=2, smooth=8):
         dev = node_device(image)
