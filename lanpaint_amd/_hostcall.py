@@ -1,6 +1,8 @@
 """What the image-space modules (video mask, audio merge, blend, Detailer, colour match, fill, multiband, refine, stabilize) and
 their nodes share between a node and a C entry point: the device rule, argument checks, the launch, workspaces and chunking.
-Plain functions; nothing of the engine's path is here (that is _util.py's).  HIP tensors only, no CPU fallback."""
+Plain functions; nothing of the engine's path is here (that is _util.py's).  HIP tensors only, no CPU fallback.  The motion
+modules (the propagates, the temporal fills and smooths, shot detection) use these too; what only they share -- the block
+matcher's checks, the luma pyramids, the batched field walk -- is the layer next to this one, _motion.py."""
 from __future__ import annotations
 
 import math
@@ -17,6 +19,19 @@ def require_hip(t, what, module):
     """`t` when it is a tensor on a HIP device; `module` is the caller's __name__, `what` its argument."""
     if not torch.is_tensor(t) or not t.is_cuda:
         raise RuntimeError(f"{module} runs on a HIP device only; no CPU fallback ({what} is not on one)")
+    return t
+
+
+def tensor_is(t, dtype, shape, what, module):
+    """`t` when it is a contiguous tensor of `dtype` and exactly `shape` on a HIP device; a None in `shape` leaves that
+    dimension free.  `what` names the argument, `module` is the caller's __name__."""
+    require_hip(t, what, module)
+    fits = t.shape == shape                                          # the usual case in one comparison: this runs before every launch
+    if not fits and t.ndim == len(shape):
+        fits = all(n is None or n == s for n, s in zip(shape, t.shape))
+    if not fits or t.dtype != dtype or not t.is_contiguous():
+        want = ", ".join("n" if n is None else str(n) for n in shape)
+        raise ValueError(f"{what} must be a contiguous {dtype} [{want}], got {t.dtype} {list(t.shape)}")
     return t
 
 

@@ -29,52 +29,12 @@ import ctypes
 import torch
 
 from . import _cabi
-from ._hostcall import chunks, int_in, launch, require_hip, workspace
+from ._hostcall import chunks, int_in, launch, require_hip, tensor_is, workspace
+from ._motion import (MAX_LEVELS, MAX_SEARCH, MAX_SIDE, MAX_SMOOTH, check_images, check_params, check_plane,     # noqa: F401
+                      clip_mask, level_view, luma_pyramids)                    # (the limits are this module's to export, as before)
 from ._util import _as_f32c
 
-MAX_SIDE = _cabi.LP_VMASK_MAX_SIDE
-MAX_LEVELS = _cabi.LP_PROP_MAX_LEVELS
-MAX_SEARCH = _cabi.LP_PROP_MAX_SEARCH
-MAX_SMOOTH = _cabi.LP_PROP_MAX_SMOOTH
 WS_CAP_BYTES = 1 << 30
-
-
-def _params(levels, search, smooth):
-    int_in(levels, 1, MAX_LEVELS, "levels")
-    int_in(search, 1, MAX_SEARCH, "search")
-    int_in(smooth, 0, MAX_SMOOTH, "smooth")
-
-
-def _plane(H, W):
-    if min(H, W) < 1 or max(H, W) > MAX_SIDE:
-        raise ValueError(f"a {H}x{W} plane: sides 1..{MAX_SIDE}")
-
-
-def _images(images):
-    require_hip(images, "images", __name__)
-    if images.ndim != 4 or min(images.shape) < 1 or images.shape[3] > _cabi.LP_DETAIL_MAX_CHANNELS:
-        raise ValueError(f"images must be [F, H, W, C] with 1..{_cabi.LP_DETAIL_MAX_CHANNELS} channels, got {tuple(images.shape)}")
-    _plane(images.shape[1], images.shape[2])
-    return images
-
-
-def level_view(pyr, H, W, level):
-    """Level `level` of the frame pyramids `pyr` uint8 [n, stride]: a view [n, h_l, w_l]."""
-    h, w = _cabi.prop_level_shape(H, W, level)
-    off = _cabi.prop_level_offset(H, W, level)
-    return pyr[:, off:off + h * w].view(pyr.shape[0], h, w)
-
-
-def luma_pyramids(images, levels):
-    """Stages 1 and 2 for `images` [n, H, W, C] on a HIP device: uint8 [n, stride], every frame's luma pyramid as one row
-    (`level_view` cuts a level out).  1 + (levels - 1) launches for all n frames; n <= 65535."""
-    int_in(levels, 1, MAX_LEVELS, "levels")
-    images = _as_f32c(_images(images))
-    n, H, W, C = images.shape
-    ws = workspace(_cabi.load().lp_prop_pyramid_ws_bytes(n, H, W, levels), images.device, "lp_prop_pyramid_ws_bytes")
-    d = _cabi.LpPropLumaDesc(n, H, W, C, levels, 0, images.data_ptr(), ws.data_ptr())
-    launch("lp_prop_luma", images.device, ctypes.byref(d))
-    return ws.view(n, -1)
 
 
 def key_mask(mask, levels):
@@ -85,36 +45,28 @@ def key_mask(mask, levels):
         raise ValueError(f"the key mask must be [H, W], got {tuple(mask.shape)}")
     mask = _as_f32c(mask)
     H, W = mask.shape
-    _plane(H, W)
+    check_plane(H, W)
     mpyr = workspace(_cabi.load().lp_prop_pyramid_ws_bytes(1, H, W, levels), mask.device, "lp_prop_pyramid_ws_bytes")
     out = torch.empty((H, W), dtype=torch.float32, device=mask.device)
     launch("lp_prop_key_mask", mask.device, mask.data_ptr(), H, W, levels, mpyr.data_ptr(), out.data_ptr())
     return mpyr.view(1, -1), out
 
 
-def _row(t, what):
-    if t.dtype != torch.uint8 or not t.is_contiguous():
-        raise ValueError(f"{what} must be one frame's pyramid, contiguous uint8")
-    return t
-
-
 def match_level(src, tgt, mpyr, H, W, levels, level, search=2, smooth=8, parent=None, vec=None, valid=None):
     """The match of one level of one step: `src`, `tgt` one frame's luma pyramid each, `mpyr` the source frame's mask pyramid,
     `parent` the level above's final field (None exactly at the top level).  (vec int32 [gh, gw, 2], valid int32 [gh, gw])."""
-    _params(levels, search, smooth)
+    check_params(levels, search, smooth)
     int_in(level, 0, levels - 1, "level")
-    _plane(H, W)
-    for t, what in ((src, "src"), (tgt, "tgt"), (mpyr, "mpyr")):
-        _row(require_hip(t, what, __name__), what)
-        if t.numel() != _cabi.prop_pyramid_ws_bytes(1, H, W, levels):
-            raise ValueError(f"{what} holds {t.numel()} bytes, a {H}x{W} pyramid of {levels} levels "
-                             f"{_cabi.prop_pyramid_ws_bytes(1, H, W, levels)}")
+    check_plane(H, W)
+    stride = _cabi.prop_pyramid_ws_bytes(1, H, W, levels)
+    for t, what in ((src, "src"), (tgt, "tgt"), (mpyr, "mpyr")):               # one frame's pyramid, [stride] or [1, stride]
+        if tensor_is(t, torch.uint8, t.shape, what, __name__).numel() != stride:
+            raise ValueError(f"{what} holds {t.numel()} bytes, a {H}x{W} pyramid of {levels} levels {stride}")
     if (parent is None) != (level == levels - 1):
         raise ValueError("parent is given exactly below the top level")
     gh, gw = _cabi.prop_grid(H, W, level)
-    if parent is not None and (parent.dtype != torch.int32 or not parent.is_contiguous()
-                               or tuple(parent.shape) != (*_cabi.prop_grid(H, W, level + 1), 2)):
-        raise ValueError("parent must be the level above's contiguous int32 [gh, gw, 2]")
+    if parent is not None:
+        tensor_is(parent, torch.int32, (*_cabi.prop_grid(H, W, level + 1), 2), "parent", __name__)
     dev = src.device
     vec = torch.empty((gh, gw, 2), dtype=torch.int32, device=dev) if vec is None else vec
     valid = torch.empty((gh, gw), dtype=torch.int32, device=dev) if valid is None else valid
@@ -126,11 +78,8 @@ def match_level(src, tgt, mpyr, H, W, levels, level, search=2, smooth=8, parent=
 
 def fill_median(vec, valid, out=None):
     """Fill and median of one level's field: int32 [gh, gw, 2].  One launch."""
-    require_hip(vec, "vec", __name__)
-    require_hip(valid, "valid", __name__)
-    if vec.dtype != torch.int32 or valid.dtype != torch.int32 or vec.ndim != 3 or vec.shape[2] != 2 \
-            or tuple(valid.shape) != tuple(vec.shape[:2]) or not vec.is_contiguous() or not valid.is_contiguous():
-        raise ValueError("vec must be a contiguous int32 [gh, gw, 2] and valid a contiguous int32 [gh, gw]")
+    tensor_is(vec, torch.int32, (None, None, 2), "vec", __name__)
+    tensor_is(valid, torch.int32, vec.shape[:2], "valid", __name__)
     out = torch.empty_like(vec) if out is None else out
     launch("lp_prop_fill", vec.device, vec.data_ptr(), valid.data_ptr(), vec.shape[0], vec.shape[1], out.data_ptr())
     return out
@@ -141,15 +90,11 @@ def advance(vec, pos, key_bits, levels, pos_out=None, out=None, mpyr_out=None):
     frame's), `key_bits` uint8 [H, W].  (positions of t, mask of t fp32 [H, W], the pyramid of its bits uint8 [1, stride])."""
     int_in(levels, 1, MAX_LEVELS, "levels")
     require_hip(vec, "vec", __name__)
-    require_hip(key_bits, "key_bits", __name__)
-    if key_bits.dtype != torch.uint8 or key_bits.ndim != 2 or not key_bits.is_contiguous():
-        raise ValueError("key_bits must be a contiguous uint8 [H, W]")
-    H, W = key_bits.shape
-    _plane(H, W)
-    if vec.dtype != torch.int32 or not vec.is_contiguous() or tuple(vec.shape) != (*_cabi.prop_grid(H, W), 2):
-        raise ValueError("vec must be level 0's contiguous int32 [gh, gw, 2]")
-    if pos is not None and (pos.dtype != torch.int32 or not pos.is_contiguous() or tuple(pos.shape) != (H, W, 2)):
-        raise ValueError("pos must be a contiguous int32 [H, W, 2]")
+    H, W = tensor_is(key_bits, torch.uint8, (None, None), "key_bits", __name__).shape
+    check_plane(H, W)
+    tensor_is(vec, torch.int32, (*_cabi.prop_grid(H, W), 2), "vec", __name__)
+    if pos is not None:
+        tensor_is(pos, torch.int32, (H, W, 2), "pos", __name__)
     dev = vec.device
     pos_out = torch.empty((H, W, 2), dtype=torch.int32, device=dev) if pos_out is None else pos_out
     out = torch.empty((H, W), dtype=torch.float32, device=dev) if out is None else out
@@ -161,7 +106,7 @@ def advance(vec, pos, key_bits, levels, pos_out=None, out=None, mpyr_out=None):
     return pos_out, out, mpyr_out
 
 
-class _Step:
+class Step:
     """The buffers one chain's steps share, and one step s -> t on them: 2 levels + 1 launches, nothing allocated."""
 
     def __init__(self, H, W, levels, search, smooth, dev):
@@ -194,7 +139,7 @@ class _Step:
             src = pyr
 
 
-def _chain_frames(images, order, levels):
+def chain_frames(images, order, levels):
     """(frame index, its luma pyramid) along `order`, the pyramids built a chunk of frames at a time under WS_CAP_BYTES."""
     F, H, W, C = images.shape
     per_frame = _cabi.prop_pyramid_ws_bytes(1, H, W, levels) + (0 if images.dtype == torch.float32 else H * W * C * 4)
@@ -206,24 +151,26 @@ def _chain_frames(images, order, levels):
             yield f, (pyr[f - lo].clone() if f == idx[-1] else pyr[f - lo])     # its own copy lets the chunk go
 
 
+def key_and_orders(images, mask, key_frame, levels):
+    """What the two single-key forms start from: (the pyramid of the key mask's bits, an output fp32 [F, H, W] with the key frame
+    written, the frames of the chains that have a step: forwards from the key, backwards from it).  One launch."""
+    F, H, W, _ = images.shape
+    mask = clip_mask(mask, F, H, W, __name__)
+    key_pyr, key_out = key_mask(mask[key_frame if mask.shape[0] == F else 0].to(images.device), levels)
+    out = torch.empty((F, H, W), dtype=torch.float32, device=images.device)
+    out[key_frame] = key_out
+    return key_pyr, out, [o for o in (list(range(key_frame, F)), list(range(key_frame, -1, -1))) if len(o) > 1]
+
+
 def propagate_masks(images, mask, key_frame=0, levels=4, search=2, smooth=8):
     """`mask`, painted on frame `key_frame` of `images` [F, H, W, C], followed through every frame (module docstring): fp32
     [F, H, W] on the images' device.  No device -> host read."""
-    _params(levels, search, smooth)
-    _images(images)
+    check_params(levels, search, smooth)
+    check_images(images)
     require_hip(mask, "mask", __name__)
-    F, H, W, _ = images.shape
-    int_in(key_frame, 0, F - 1, "key_frame")
-    if mask.ndim == 2:
-        mask = mask.unsqueeze(0)
-    if mask.ndim != 3 or mask.shape[0] not in (1, F) or tuple(mask.shape[1:]) != (H, W):
-        raise ValueError(f"mask {tuple(mask.shape)} does not match {F} frames of {H}x{W}: [H, W], [1, H, W] or [F, H, W]")
-    dev = images.device
-    key_pyr, key_out = key_mask(mask[key_frame if mask.shape[0] == F else 0].to(dev), levels)
-    out = torch.empty((F, H, W), dtype=torch.float32, device=dev)
-    out[key_frame] = key_out
-    step = _Step(H, W, levels, search, smooth, dev)
-    for order in (list(range(key_frame, F)), list(range(key_frame, -1, -1))):
-        if len(order) > 1:
-            step.chain(_chain_frames(images, order, levels), key_pyr, out)
+    int_in(key_frame, 0, images.shape[0] - 1, "key_frame")
+    key_pyr, out, orders = key_and_orders(images, mask, key_frame, levels)
+    step = Step(*images.shape[1:3], levels, search, smooth, images.device)
+    for order in orders:
+        step.chain(chain_frames(images, order, levels), key_pyr, out)
     return out

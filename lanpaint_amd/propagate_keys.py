@@ -30,11 +30,10 @@ import numpy as np
 import torch
 
 from . import _cabi, stabilize
-from ._hostcall import chunks, int_in, launch, require_hip
-from ._util import _as_f32c
-from .propagate import _images, _params, _plane, key_mask
+from ._hostcall import int_in, launch, require_hip, tensor_is
+from ._motion import MAX_JOBS, FieldWalk, check_images, check_params, check_plane, luma_pyramids, row_addresses
+from .propagate import key_mask
 
-MAX_JOBS = _cabi.LP_PROP_MAX_JOBS
 WS_CAP_BYTES = 1 << 30
 
 
@@ -60,43 +59,35 @@ def chain_plan(frames, key_frames):
     return [c for c in plan if c[3] > 0]
 
 
-def _table(rows, what):
+def job_table(rows, what):
     """`rows`: per job a tuple of tensors (or None); the tensors' addresses as a host uint64 [jobs, fields]."""
     if not 1 <= len(rows) <= MAX_JOBS:
         raise ValueError(f"{what}: 1..{MAX_JOBS} jobs, got {len(rows)}")
     return np.array([[0 if t is None else t.data_ptr() for t in row] for row in rows], dtype=np.uint64)
 
 
-def _int32c(t, shape, what):
-    require_hip(t, what, __name__)
-    if t.dtype != torch.int32 or not t.is_contiguous() or tuple(t.shape) != tuple(shape):
-        raise ValueError(f"{what} must be a contiguous int32 {list(shape)}, got {t.dtype} {list(t.shape)}")
-    return t
-
-
 def match_level_batch(jobs, H, W, levels, level, search=2, smooth=8):
     """`propagate.match_level` for several independent steps in one launch.  `jobs`: per job (src, tgt, mpyr, parent) as there,
     `parent` None exactly at the top level.  A list of (vec int32 [gh, gw, 2], valid int32 [gh, gw])."""
-    _params(levels, search, smooth)
+    check_params(levels, search, smooth)
     int_in(level, 0, levels - 1, "level")
-    _plane(H, W)
+    check_plane(H, W)
     stride = _cabi.prop_pyramid_ws_bytes(1, H, W, levels)
     gh, gw = _cabi.prop_grid(H, W, level)
     rows, outs = [], []
     for src, tgt, mpyr, parent in jobs:
         for t, what in ((src, "src"), (tgt, "tgt"), (mpyr, "mpyr")):
-            require_hip(t, what, __name__)
-            if t.dtype != torch.uint8 or not t.is_contiguous() or t.numel() != stride:
+            if tensor_is(t, torch.uint8, t.shape, what, __name__).numel() != stride:
                 raise ValueError(f"{what} must be one frame's pyramid: {stride} contiguous uint8")
         if (parent is None) != (level == levels - 1):
             raise ValueError("parent is given exactly below the top level")
         if parent is not None:
-            _int32c(parent, (*_cabi.prop_grid(H, W, level + 1), 2), "parent")
+            tensor_is(parent, torch.int32, (*_cabi.prop_grid(H, W, level + 1), 2), "parent", __name__)
         vec = torch.empty((gh, gw, 2), dtype=torch.int32, device=src.device)
         valid = torch.empty((gh, gw), dtype=torch.int32, device=src.device)
         rows.append((src, tgt, mpyr, parent, vec, valid))
         outs.append((vec, valid))
-    table = _table(rows, "match_level_batch")
+    table = job_table(rows, "match_level_batch")
     d = _cabi.LpPropMatchBatchDesc(H, W, levels, level, search, smooth, len(rows), 0, table.ctypes.data)
     launch("lp_prop_match_batch", rows[0][0].device, ctypes.byref(d))
     return outs
@@ -108,10 +99,10 @@ def fill_median_batch(jobs):
     for vec, valid in jobs:
         require_hip(vec, "vec", __name__)
         grid = tuple(rows[0][0].shape[:2] if rows else vec.shape[:2])    # the first job's grid is every job's
-        _int32c(vec, (*grid, 2), "vec")
-        _int32c(valid, grid, "valid")
+        tensor_is(vec, torch.int32, (*grid, 2), "vec", __name__)
+        tensor_is(valid, torch.int32, grid, "valid", __name__)
         rows.append((vec, valid, torch.empty_like(vec)))
-    table = _table(rows, "fill_median_batch")
+    table = job_table(rows, "fill_median_batch")
     gh, gw = rows[0][0].shape[:2]
     launch("lp_prop_fill_batch", rows[0][0].device, table.ctypes.data, len(rows), gh, gw)
     return [r[2] for r in rows]
@@ -124,21 +115,17 @@ def advance_batch(jobs, levels):
     rows, outs = [], []
     for vec, pos, key_bits in jobs:
         require_hip(vec, "vec", __name__)
-        require_hip(key_bits, "key_bits", __name__)
-        if key_bits.dtype != torch.uint8 or key_bits.ndim != 2 or not key_bits.is_contiguous() \
-                or (rows and key_bits.shape != rows[0][2].shape):
-            raise ValueError("key_bits must be a contiguous uint8 [H, W], the same plane in every job")
-        H, W = key_bits.shape
-        _plane(H, W)
-        _int32c(vec, (*_cabi.prop_grid(H, W), 2), "vec")
+        H, W = tensor_is(key_bits, torch.uint8, rows[0][2].shape if rows else (None, None), "key_bits", __name__).shape   # one plane
+        check_plane(H, W)
+        tensor_is(vec, torch.int32, (*_cabi.prop_grid(H, W), 2), "vec", __name__)
         if pos is not None:
-            _int32c(pos, (H, W, 2), "pos")
+            tensor_is(pos, torch.int32, (H, W, 2), "pos", __name__)
         dev = vec.device
         new = (torch.empty((H, W, 2), dtype=torch.int32, device=dev), torch.empty((H, W), dtype=torch.float32, device=dev),
                torch.empty((1, _cabi.prop_pyramid_ws_bytes(1, H, W, levels)), dtype=torch.uint8, device=dev))
         rows.append((vec, pos, key_bits, *new))
         outs.append(new)
-    table = _table(rows, "advance_batch")
+    table = job_table(rows, "advance_batch")
     H, W = rows[0][2].shape
     d = _cabi.LpPropAdvanceBatchDesc(H, W, levels, len(rows), table.ctypes.data)
     launch("lp_prop_advance_batch", rows[0][0].device, ctypes.byref(d))
@@ -155,112 +142,80 @@ def merge_gap(qa, qb, span, first=1, out=None):
     require_hip(qb, "qb", __name__)
     if qa.ndim != 3 or not 1 <= qa.shape[0] <= span - first:
         raise ValueError(f"qa must be [n, H, W] with first + n - 1 <= span - 1, got {tuple(qa.shape)}")
-    _int32c(qa, qa.shape, "qa")
-    _int32c(qb, qa.shape, "qb")
+    tensor_is(qa, torch.int32, qa.shape, "qa", __name__)
+    tensor_is(qb, torch.int32, qa.shape, "qb", __name__)
     n, H, W = qa.shape
-    _plane(H, W)
+    check_plane(H, W)
     out = torch.empty((n, H, W), dtype=torch.float32, device=qa.device) if out is None else out
     d = _cabi.LpPropMergeDesc(n, H, W, span, first, 0, qa.data_ptr(), qb.data_ptr(), out.data_ptr())
     launch("lp_prop_merge", qa.device, ctypes.byref(d))
     return out
 
 
-def _clip_pyramids(images, levels):
-    """The luma pyramids of all frames, uint8 [F, stride]; input that needs a conversion to contiguous fp32 goes through it in
-    chunks of frames under WS_CAP_BYTES (a frame's pyramid depends on that frame only)."""
-    F, H, W, C = images.shape
+def clip_pyramids(images, levels):
+    """The luma pyramids of all frames, uint8 [F, stride], held whole under WS_CAP_BYTES; input that needs a conversion to
+    contiguous fp32 goes through it in chunks of frames under WS_CAP_BYTES."""
+    F, H, W, _ = images.shape
     stride = _cabi.prop_pyramid_ws_bytes(1, H, W, levels)
     if F * stride > WS_CAP_BYTES:
         raise ValueError(f"the luma pyramids of {F} frames of {H}x{W} take {F * stride} bytes, above WS_CAP_BYTES = {WS_CAP_BYTES}")
-    pyr = torch.empty((F, stride), dtype=torch.uint8, device=images.device)
-    direct = images.dtype == torch.float32 and images.is_contiguous()
-    for s, n in chunks(F, 1 if direct else H * W * C * 4, WS_CAP_BYTES):
-        part = _as_f32c(images[s:s + n])
-        d = _cabi.LpPropLumaDesc(n, H, W, C, levels, 0, part.data_ptr(), pyr[s:s + n].data_ptr())
-        launch("lp_prop_luma", images.device, ctypes.byref(d))
-    return pyr
+    return luma_pyramids(images, levels, torch.empty((F, stride), dtype=torch.uint8, device=images.device), WS_CAP_BYTES)
 
 
-class _Chains:
-    """The buffers of all chains of a call and the job tables of their steps.  A table is a host uint64 array of device
-    addresses, one row per chain; step s of chain c reads and writes at addresses that are linear in s or alternate with its
-    parity, so a step fills columns with a few numpy operations and allocates nothing on the device."""
+class Chains:
+    """What outlives a step of the chains of a call -- per chain two position maps and two mask pyramids, and the addresses of
+    its key, its frames' luma and its outputs -- and the advance's job table.  The fields are scratch within a step: they are
+    the rows of a `FieldWalk`, which belong to the j-th chain of the group being launched.  A table is a host uint64 array of
+    device addresses; step s of chain c reads and writes at addresses that are linear in s or alternate with its parity, so a
+    step fills columns with a few numpy operations and allocates nothing on the device."""
 
     def __init__(self, plan, pyr, key_pyrs, outs, H, W, levels, search, smooth):
         dev = pyr.device
-        self.H, self.W, self.levels, self.search, self.smooth, self.dev = H, W, levels, search, smooth, dev
+        self.dev = dev
         self.length = np.array([c[3] for c in plan], dtype=np.int64)
-        self.grids = [_cabi.prop_grid(H, W, lv) for lv in range(levels)]
         stride = pyr.shape[1]
+        self.walk = FieldWalk(min(len(plan), MAX_JOBS), H, W, levels, search, smooth, dev)
         self._keep = []                                              # the device buffers behind the addresses
-        buffers = self._buffers
-        self.raw = [buffers((gh, gw, 2), torch.int32) for gh, gw in self.grids]
-        self.valid = [buffers((gh, gw), torch.int32) for gh, gw in self.grids]
-        self.field = [buffers((gh, gw, 2), torch.int32) for gh, gw in self.grids]
-        self.pos = [buffers((H, W, 2), torch.int32) for _ in range(2)]
-        self.mpyr = [buffers((stride,), torch.uint8) for _ in range(2)]
+        self.pos = [self._buffers((H, W, 2), torch.int32) for _ in range(2)]
+        self.mpyr = [self._buffers((stride,), torch.uint8) for _ in range(2)]
         self.key = np.array([key_pyrs[c[0]].data_ptr() for c in plan], dtype=np.uint64)
         # frame k + d s of the clip's pyramids, and where step s writes its mask: both base + s * step, the step signed
         self.luma0 = np.array([pyr.data_ptr() + c[1] * stride for c in plan], dtype=np.int64)
         self.luma_step = np.array([c[2] * stride for c in plan], dtype=np.int64)
         self.out0 = np.array([o[0] for o in outs], dtype=np.int64)
         self.out_step = np.array([o[1] for o in outs], dtype=np.int64)
-        self.match_desc = [_cabi.LpPropMatchBatchDesc(H, W, levels, lv, search, smooth, 0, 0, None) for lv in range(levels)]
-        self.advance_desc = _cabi.LpPropAdvanceBatchDesc(H, W, levels, 0, None)
-        self.active = None
+        self.t_advance = np.zeros((len(self.walk.field0), 6), dtype=np.uint64)
+        self.t_advance[:, 0] = self.walk.field0
+        self.advance_desc = _cabi.LpPropAdvanceBatchDesc(H, W, levels, 0, self.t_advance.ctypes.data)
 
     def _buffers(self, shape, dtype):
         """One buffer of `shape` per chain: their addresses."""
-        n = len(self.length)
-        t = torch.empty((n, *shape), dtype=dtype, device=self.dev)
-        self._keep.append(t)
-        step = t[0].numel() * t.element_size()
-        return np.uint64(t.data_ptr()) + np.arange(n, dtype=np.uint64) * np.uint64(step)
-
-    def _select(self, idx):
-        """The tables of the chains `idx`; the columns that do not move with the step are filled here."""
-        self.active, m = idx, len(idx)
-        self.t_match = [np.zeros((m, 6), dtype=np.uint64) for _ in range(self.levels)]
-        self.t_fill = [np.stack([self.raw[lv][idx], self.valid[lv][idx], self.field[lv][idx]], axis=1) for lv in range(self.levels)]
-        self.t_advance = np.zeros((m, 6), dtype=np.uint64)
-        for lv, t in enumerate(self.t_match):
-            if lv + 1 < self.levels:
-                t[:, 3] = self.field[lv + 1][idx]
-            t[:, 4], t[:, 5] = self.raw[lv][idx], self.valid[lv][idx]
-        self.t_advance[:, 0], self.t_advance[:, 2] = self.field[0][idx], self.key[idx]
+        self._keep.append(torch.empty((len(self.length), *shape), dtype=dtype, device=self.dev))
+        return row_addresses(self._keep[-1], len(self.length))
 
     def step(self, s):
         """Step s of every chain that has one: 2 levels + 1 launches per MAX_JOBS chains."""
         idx = np.flatnonzero(self.length >= s)
-        if self.active is None or len(idx) != len(self.active):
-            self._select(idx)
-        self._bind(s, idx)
         for lo in range(0, len(idx), MAX_JOBS):
-            self._launch(lo, min(MAX_JOBS, len(idx) - lo))
+            self._bind(s, idx[lo:lo + MAX_JOBS])
+            self._launch(min(MAX_JOBS, len(idx) - lo))
 
     def _bind(self, s, idx):
-        """The columns that move with the step."""
-        src = (self.luma0[idx] + (s - 1) * self.luma_step[idx]).astype(np.uint64)
-        tgt = (self.luma0[idx] + s * self.luma_step[idx]).astype(np.uint64)
-        mask = self.key[idx] if s == 1 else self.mpyr[(s - 1) & 1][idx]
-        for t in self.t_match:
-            t[:, 0], t[:, 1], t[:, 2] = src, tgt, mask
+        """The tables' rows 0 .. len(idx) - 1 for step s of the chains `idx`, one group."""
+        n = len(idx)
+        self.luma = (self.luma0[idx] + s * self.luma_step[idx]).astype(np.uint64)        # the frame the step arrives at
+        self.jobs = ((self.luma0[idx] + (s - 1) * self.luma_step[idx]).astype(np.uint64), self.luma,
+                     self.key[idx] if s == 1 else self.mpyr[(s - 1) & 1][idx])
         a = self.t_advance
-        a[:, 1] = 0 if s == 1 else self.pos[(s - 1) & 1][idx]
-        a[:, 3], a[:, 5] = self.pos[s & 1][idx], self.mpyr[s & 1][idx]
-        a[:, 4] = (self.out0[idx] + s * self.out_step[idx]).astype(np.uint64)
+        a[:n, 1] = 0 if s == 1 else self.pos[(s - 1) & 1][idx]
+        a[:n, 2], a[:n, 3], a[:n, 5] = self.key[idx], self.pos[s & 1][idx], self.mpyr[s & 1][idx]
+        a[:n, 4] = (self.out0[idx] + s * self.out_step[idx]).astype(np.uint64)
 
-    def _launch(self, lo, n):
-        """The launches of the `n` active chains from row `lo` of the tables."""
-        for lv in range(self.levels - 1, -1, -1):
-            d = self.match_desc[lv]
-            d.jobs, d.job = n, self.t_match[lv][lo:].ctypes.data
-            launch("lp_prop_match_batch", self.dev, ctypes.byref(d))
-            gh, gw = self.grids[lv]
-            launch("lp_prop_fill_batch", self.dev, self.t_fill[lv][lo:].ctypes.data, n, gh, gw)
-        d = self.advance_desc
-        d.jobs, d.job = n, self.t_advance[lo:].ctypes.data
-        launch("lp_prop_advance_batch", self.dev, ctypes.byref(d))
+    def _launch(self, n):
+        """The launches of the group of `n` chains that was bound."""
+        self.walk.run(*self.jobs)
+        self.advance_desc.jobs = n
+        launch("lp_prop_advance_batch", self.dev, ctypes.byref(self.advance_desc))
 
 
 def _key_masks(masks, keys, F, H, W):
@@ -273,25 +228,34 @@ def _key_masks(masks, keys, F, H, W):
     return [masks[i] for i in (range(len(keys)) if masks.shape[0] == len(keys) else keys)]
 
 
+def painted_keys(images, masks, key_frames, levels, module, planes=1):
+    """What the two several-keys forms start from: (the plan, the keys, the pyramid of every key's bits, `planes` outputs fp32
+    [F, H, W]: on the key frames the first holds the binarised paintings and the others zero).  `module` is the caller's
+    __name__.  One launch per key."""
+    if not torch.is_tensor(images) or images.ndim != 4:
+        check_images(images)                                         # raises: the frame count is needed for the keys' check
+    plan = chain_plan(images.shape[0], key_frames)                   # the numbers before the tensors
+    keys = list(key_frames)
+    check_images(images)
+    require_hip(masks, "masks", module)
+    (F, H, W, _), dev = images.shape, images.device
+    outs = [torch.empty((F, H, W), dtype=torch.float32, device=dev) for _ in range(planes)]
+    key_pyrs = []
+    for k, m in zip(keys, _key_masks(masks, keys, F, H, W)):
+        mpyr, bits = key_mask(m.to(dev), levels)
+        key_pyrs.append(mpyr)
+        outs[0][k] = bits
+        for o in outs[1:]:
+            o[k].zero_()
+    return plan, keys, key_pyrs, outs
+
+
 def propagate_keys(images, masks, key_frames, levels=4, search=2, smooth=8):
     """The masks painted on the frames `key_frames` of `images` [F, H, W, C], followed through every frame and merged between
     the keys (module docstring): fp32 [F, H, W] on the images' device.  No device -> host read."""
-    _params(levels, search, smooth)
-    if not torch.is_tensor(images) or images.ndim != 4:
-        _images(images)                                              # raises: the frame count is needed for the keys' check
-    plan = chain_plan(images.shape[0], key_frames)                   # the numbers before the tensors
-    keys = list(key_frames)
-    _images(images)
-    require_hip(masks, "masks", __name__)
-    F, H, W, _ = images.shape
-    dev = images.device
-    painted = _key_masks(masks, keys, F, H, W)
-    out = torch.empty((F, H, W), dtype=torch.float32, device=dev)
-    key_pyrs = []
-    for k, m in zip(keys, painted):
-        mpyr, bits = key_mask(m.to(dev), levels)
-        key_pyrs.append(mpyr)
-        out[k] = bits
+    check_params(levels, search, smooth)
+    plan, keys, key_pyrs, (out,) = painted_keys(images, masks, key_frames, levels, __name__)
+    (F, H, W, _), dev = images.shape, images.device
     if not plan:
         return out
     # a gap's forward chain writes into `out`, its backward chain into `back`; the merge then overwrites the gap's frames of `out`
@@ -308,8 +272,8 @@ def propagate_keys(images, masks, key_frames, levels=4, search=2, smooth=8):
             outs.append((back_at[k].data_ptr() + length * plane, -plane))
         else:
             outs.append((out.data_ptr() + k * plane, d * plane))
-    pyr = _clip_pyramids(images, levels)
-    chains = _Chains(plan, pyr, key_pyrs, outs, H, W, levels, search, smooth)
+    pyr = clip_pyramids(images, levels)
+    chains = Chains(plan, pyr, key_pyrs, outs, H, W, levels, search, smooth)
     for s in range(1, int(chains.length.max()) + 1):
         chains.step(s)
     for a, b in gaps:

@@ -34,19 +34,12 @@ import numpy as np
 import torch
 
 from . import _cabi, propagate_keys, stabilize
-from ._hostcall import chunks, int_in, launch, require_hip
-from .propagate import _images, _params, _plane, key_mask
-from .propagate_keys import MAX_JOBS, _Chains, _clip_pyramids, _int32c, _key_masks, _table, chain_plan
-from .propagate_visible import DEFAULT_OCCLUSION, MAX_OCCLUSION, _plane_u8
+from ._hostcall import chunks, int_in, launch, require_hip, tensor_is
+from ._motion import MAX_JOBS, check_params, check_plane
+from .propagate_keys import Chains, chain_plan, clip_pyramids, job_table, painted_keys     # noqa: F401  (chain_plan: the node's)
+from .propagate_visible import DEFAULT_OCCLUSION, MAX_OCCLUSION
 
 WS_CAP_BYTES = 1 << 30
-
-
-def _f32_plane(t, what, H=None, W=None):
-    require_hip(t, what, __name__)
-    if t.dtype != torch.float32 or t.ndim != 2 or not t.is_contiguous() or (H is not None and tuple(t.shape) != (H, W)):
-        raise ValueError(f"{what} must be a contiguous fp32 [H, W]" + ("" if H is None else f" of {H}x{W}"))
-    return t
 
 
 def visible_flags_batch(jobs, occlusion=DEFAULT_OCCLUSION):
@@ -55,14 +48,13 @@ def visible_flags_batch(jobs, occlusion=DEFAULT_OCCLUSION):
     int_in(occlusion, 1, MAX_OCCLUSION, "occlusion")
     rows = []
     for pos, tgt, key, mask_bits in jobs:
-        H, W = _plane_u8(tgt, "tgt", *(rows[0][1].shape if rows else (None, None))).shape
-        _plane(H, W)
-        _plane_u8(key, "key", H, W)
-        _plane_u8(mask_bits, "mask_bits", H, W)
-        require_hip(pos, "pos", __name__)
-        _int32c(pos, (H, W, 2), "pos")
+        H, W = tensor_is(tgt, torch.uint8, rows[0][1].shape if rows else (None, None), "tgt", __name__).shape
+        check_plane(H, W)
+        tensor_is(key, torch.uint8, (H, W), "key", __name__)
+        tensor_is(mask_bits, torch.uint8, (H, W), "mask_bits", __name__)
+        tensor_is(pos, torch.int32, (H, W, 2), "pos", __name__)
         rows.append((pos, tgt, key, mask_bits, torch.empty(_cabi.prop_grid(H, W), dtype=torch.int32, device=tgt.device)))
-    table = _table(rows, "visible_flags_batch")
+    table = job_table(rows, "visible_flags_batch")
     H, W = rows[0][1].shape
     d = _cabi.LpPropVisibleBatchDesc(H, W, occlusion, len(rows), table.ctypes.data)
     launch("lp_prop_visible_batch", rows[0][1].device, ctypes.byref(d))
@@ -76,18 +68,17 @@ def occlude_batch(jobs, levels, counts=None):
     int_in(levels, 1, _cabi.LP_PROP_MAX_LEVELS, "levels")
     rows, outs = [], []
     if counts is not None:
-        _int32c(counts, (len(jobs),), "counts")
+        tensor_is(counts, torch.int32, (len(jobs),), "counts", __name__)
     for i, (code, flags) in enumerate(jobs):
-        H, W = _f32_plane(code, "code", *(rows[0][0].shape if rows else (None, None))).shape
-        _plane(H, W)
-        require_hip(flags, "flags", __name__)
-        _int32c(flags, _cabi.prop_grid(H, W), "flags")
+        H, W = tensor_is(code, torch.float32, rows[0][0].shape if rows else (None, None), "code", __name__).shape
+        check_plane(H, W)
+        tensor_is(flags, torch.int32, _cabi.prop_grid(H, W), "flags", __name__)
         dev = code.device
         new = (torch.empty((H, W), dtype=torch.float32, device=dev), torch.empty((H, W), dtype=torch.float32, device=dev),
                torch.empty((1, _cabi.prop_pyramid_ws_bytes(1, H, W, levels)), dtype=torch.uint8, device=dev))
         rows.append((code, flags, *new, None if counts is None else counts[i:]))
         outs.append(new)
-    table = _table(rows, "occlude_batch")
+    table = job_table(rows, "occlude_batch")
     H, W = rows[0][0].shape
     d = _cabi.LpPropOccludeBatchDesc(H, W, levels, len(rows), table.ctypes.data)
     launch("lp_prop_occlude_batch", rows[0][0].device, ctypes.byref(d))
@@ -104,17 +95,14 @@ def merge_gap_visible(qa, qb, code_a, mask_a, code_b, mask_b, flags_a, flags_b, 
     if qa.ndim != 3 or not 1 <= qa.shape[0] <= span - first:
         raise ValueError(f"qa must be [n, H, W] with first + n - 1 <= span - 1, got {tuple(qa.shape)}")
     n, H, W = qa.shape
-    _plane(H, W)
-    for t, what in ((qa, "qa"), (qb, "qb")):
-        _int32c(t, (n, H, W), what)
-    for t, what in ((code_a, "code_a"), (mask_a, "mask_a"), (code_b, "code_b"), (mask_b, "mask_b")):
-        require_hip(t, what, __name__)
-        if t.dtype != torch.float32 or not t.is_contiguous() or tuple(t.shape) != (n, H, W):
-            raise ValueError(f"{what} must be a contiguous fp32 {[n, H, W]}, got {t.dtype} {list(t.shape)}")
-    for t, what in ((flags_a, "flags_a"), (flags_b, "flags_b")):
-        _int32c(t, (n, *_cabi.prop_grid(H, W)), what)
-    for t, what in ((count_a, "count_a"), (count_b, "count_b")):
-        _int32c(t, (span,), what)
+    check_plane(H, W)
+    i32, f32, grid = torch.int32, torch.float32, _cabi.prop_grid(H, W)
+    for t, dtype, shape, what in ((qa, i32, (n, H, W), "qa"), (qb, i32, (n, H, W), "qb"), (code_a, f32, (n, H, W), "code_a"),
+                                  (mask_a, f32, (n, H, W), "mask_a"), (code_b, f32, (n, H, W), "code_b"),
+                                  (mask_b, f32, (n, H, W), "mask_b"), (flags_a, i32, (n, *grid), "flags_a"),
+                                  (flags_b, i32, (n, *grid), "flags_b"), (count_a, i32, (span,), "count_a"),
+                                  (count_b, i32, (span,), "count_b")):
+        tensor_is(t, dtype, shape, what, __name__)
     out = torch.empty((n, H, W), dtype=torch.float32, device=qa.device) if out is None else out
     hidden = torch.empty((n, H, W), dtype=torch.float32, device=qa.device) if hidden is None else hidden
     d = _cabi.LpPropMergeVisibleDesc(n, H, W, span, first, 0, qa.data_ptr(), qb.data_ptr(), code_a.data_ptr(), mask_a.data_ptr(),
@@ -124,8 +112,8 @@ def merge_gap_visible(qa, qb, code_a, mask_a, code_b, mask_b, flags_a, flags_b, 
     return out, hidden
 
 
-class _VisibleChains(_Chains):
-    """`propagate_keys._Chains` with the two launches of the occlusion-aware form behind every advance.  The advance's code goes
+class VisibleChains(Chains):
+    """`propagate_keys.Chains` with the two launches of the occlusion-aware form behind every advance.  The advance's code goes
     where `code` says (the base class's `outs`) and its pyramid to a buffer per chain; `mask`, `hidden`, `flags` and `count` say,
     as (address, step in bytes) per chain, where step s writes the visible part, the hidden part, the flags and the number of
     visible bits (address 0: not counted).  The key frame's luma is level 0 of its pyramid in `pyr`."""
@@ -135,31 +123,25 @@ class _VisibleChains(_Chains):
         self.raw_mpyr = self._buffers((pyr.shape[1],), torch.uint8)
         self.lin = [(np.array([o[0] for o in col], dtype=np.int64), np.array([o[1] for o in col], dtype=np.int64))
                     for col in (mask, hidden, flags, count)]
-        self.visible_desc = _cabi.LpPropVisibleBatchDesc(H, W, occlusion, 0, None)
-        self.occlude_desc = _cabi.LpPropOccludeBatchDesc(H, W, levels, 0, None)
-
-    def _select(self, idx):
-        super()._select(idx)
-        self.t_visible = np.zeros((len(idx), 5), dtype=np.uint64)
-        self.t_occlude = np.zeros((len(idx), 6), dtype=np.uint64)
-        self.t_visible[:, 2], self.t_visible[:, 3] = self.luma0[idx].astype(np.uint64), self.raw_mpyr[idx]
+        self.t_visible = np.zeros((len(self.t_advance), 5), dtype=np.uint64)
+        self.t_occlude = np.zeros((len(self.t_advance), 6), dtype=np.uint64)
+        self.visible_desc = _cabi.LpPropVisibleBatchDesc(H, W, occlusion, 0, self.t_visible.ctypes.data)
+        self.occlude_desc = _cabi.LpPropOccludeBatchDesc(H, W, levels, 0, self.t_occlude.ctypes.data)
 
     def _bind(self, s, idx):
         super()._bind(s, idx)
+        n = len(idx)
         a, v, o = self.t_advance, self.t_visible, self.t_occlude
-        a[:, 5] = self.raw_mpyr[idx]
+        a[:n, 5] = self.raw_mpyr[idx]
         at = [(base[idx] + s * step[idx]).astype(np.uint64) for base, step in self.lin]
-        v[:, 0], v[:, 1], v[:, 4] = a[:, 3], (self.luma0[idx] + s * self.luma_step[idx]).astype(np.uint64), at[2]
-        o[:, 0], o[:, 1], o[:, 2], o[:, 3], o[:, 4], o[:, 5] = a[:, 4], at[2], at[0], at[1], self.mpyr[s & 1][idx], at[3]
+        v[:n, 0], v[:n, 1], v[:n, 2], v[:n, 3], v[:n, 4] = a[:n, 3], self.luma, self.luma0[idx].astype(np.uint64), a[:n, 5], at[2]
+        o[:n, 0], o[:n, 1], o[:n, 2], o[:n, 3], o[:n, 4], o[:n, 5] = a[:n, 4], at[2], at[0], at[1], self.mpyr[s & 1][idx], at[3]
 
-    def _launch(self, lo, n):
-        super()._launch(lo, n)
-        d = self.visible_desc
-        d.jobs, d.job = n, self.t_visible[lo:].ctypes.data
-        launch("lp_prop_visible_batch", self.dev, ctypes.byref(d))
-        d = self.occlude_desc
-        d.jobs, d.job = n, self.t_occlude[lo:].ctypes.data
-        launch("lp_prop_occlude_batch", self.dev, ctypes.byref(d))
+    def _launch(self, n):
+        super()._launch(n)
+        self.visible_desc.jobs = self.occlude_desc.jobs = n
+        launch("lp_prop_visible_batch", self.dev, ctypes.byref(self.visible_desc))
+        launch("lp_prop_occlude_batch", self.dev, ctypes.byref(self.occlude_desc))
 
     def count_keys(self, painted, zero_flags):
         """Entry 0 of every counted chain's counts: the key's bits, counted by the occlude launch on the key's binarised mask with
@@ -168,38 +150,23 @@ class _VisibleChains(_Chains):
         rows = [(painted[c].data_ptr(), zero_flags.data_ptr(), int(self.pos[0][c]), int(self.lin[1][0][c]), int(self.mpyr[0][c]),
                  int(self.lin[3][0][c])) for c in range(len(self.length)) if self.lin[3][0][c]]
         table = np.array(rows, dtype=np.uint64).reshape(len(rows), 6)
-        d = self.occlude_desc
-        for lo in range(0, len(rows), MAX_JOBS):
-            d.jobs, d.job = min(MAX_JOBS, len(rows) - lo), table[lo:].ctypes.data
-            launch("lp_prop_occlude_batch", self.dev, ctypes.byref(d))
+        for lo in range(0, len(rows), MAX_JOBS):                         # through the occlude table, a group at a time
+            n = self.occlude_desc.jobs = min(MAX_JOBS, len(rows) - lo)
+            self.t_occlude[:n] = table[lo:lo + n]
+            launch("lp_prop_occlude_batch", self.dev, ctypes.byref(self.occlude_desc))
 
 
 def propagate_keys_visible(images, masks, key_frames, levels=4, search=2, smooth=8, occlusion=DEFAULT_OCCLUSION):
     """The masks painted on the frames `key_frames` of `images` [F, H, W, C], followed through every frame, kept off what passes
     in front and merged between the keys (module docstring): (mask, hidden), fp32 [F, H, W] each, on the images' device.  No
     device -> host read."""
-    _params(levels, search, smooth)
+    check_params(levels, search, smooth)
     int_in(occlusion, 0, MAX_OCCLUSION, "occlusion")
-    if not torch.is_tensor(images) or images.ndim != 4:
-        _images(images)                                              # raises: the frame count is needed for the keys' check
-    plan = chain_plan(images.shape[0], key_frames)                   # the numbers before the tensors
-    keys = list(key_frames)
-    _images(images)
-    require_hip(masks, "masks", __name__)
-    F, H, W, _ = images.shape
-    dev = images.device
-    if occlusion == 0:
-        return (propagate_keys.propagate_keys(images, masks, keys, levels, search, smooth),
-                torch.zeros((F, H, W), dtype=torch.float32, device=dev))
-    painted = _key_masks(masks, keys, F, H, W)
-    out = torch.empty((F, H, W), dtype=torch.float32, device=dev)
-    hidden = torch.empty((F, H, W), dtype=torch.float32, device=dev)
-    key_pyrs = []
-    for k, m in zip(keys, painted):
-        mpyr, bits = key_mask(m.to(dev), levels)
-        key_pyrs.append(mpyr)
-        out[k] = bits
-        hidden[k].zero_()
+    if occlusion == 0:                                               # the plain form makes every further check itself
+        out = propagate_keys.propagate_keys(images, masks, key_frames, levels, search, smooth)
+        return out, torch.zeros_like(out)
+    plan, keys, key_pyrs, (out, hidden) = painted_keys(images, masks, key_frames, levels, __name__, 2)
+    (F, H, W, _), dev = images.shape, images.device
     if not plan:
         return out, hidden
     gaps = [(a, b) for a, b in zip(keys, keys[1:]) if b - a > 1]
@@ -242,8 +209,8 @@ def propagate_keys_visible(images, masks, key_frames, levels=4, search=2, smooth
             hid.append((hidden.data_ptr() + k * plane, d * plane))
             flag.append(tmp_flags)
             count.append((0, 0))
-    pyr = _clip_pyramids(images, levels)
-    chains = _VisibleChains(plan, pyr, key_pyrs, code, mask, hid, flag, count, H, W, levels, search, smooth, occlusion)
+    pyr = clip_pyramids(images, levels)
+    chains = VisibleChains(plan, pyr, key_pyrs, code, mask, hid, flag, count, H, W, levels, search, smooth, occlusion)
     if gaps:
         scratch_flags[-1].zero_()
         chains.count_keys([out[k] for _, k, _, _ in plan], scratch_flags[-1])

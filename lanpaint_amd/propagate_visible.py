@@ -34,18 +34,12 @@ import ctypes
 import torch
 
 from . import _cabi, propagate
-from ._hostcall import int_in, launch, require_hip
-from .propagate import _Step, _chain_frames, _images, _params, _plane, advance, key_mask, level_view
+from ._hostcall import int_in, launch, require_hip, tensor_is
+from ._motion import check_images, check_params, check_plane, level_view
+from .propagate import Step, advance, chain_frames, key_and_orders
 
 MAX_OCCLUSION = 255
 DEFAULT_OCCLUSION = 16
-
-
-def _plane_u8(t, what, H=None, W=None):
-    require_hip(t, what, __name__)
-    if t.dtype != torch.uint8 or t.ndim != 2 or not t.is_contiguous() or (H is not None and tuple(t.shape) != (H, W)):
-        raise ValueError(f"{what} must be a contiguous uint8 [H, W]" + ("" if H is None else f" of {H}x{W}"))
-    return t
 
 
 def visible_flags(pos, tgt, key, mask_bits, occlusion=DEFAULT_OCCLUSION, out=None):
@@ -53,13 +47,11 @@ def visible_flags(pos, tgt, key, mask_bits, occlusion=DEFAULT_OCCLUSION, out=Non
     the key frame's luma pyramid, `mask_bits` level 0 of the pyramid the advance wrote, all uint8 [H, W].  int32 [gh, gw], 1 where
     the block is occluded.  One launch."""
     int_in(occlusion, 1, MAX_OCCLUSION, "occlusion")
-    H, W = _plane_u8(tgt, "tgt").shape
-    _plane(H, W)
-    _plane_u8(key, "key", H, W)
-    _plane_u8(mask_bits, "mask_bits", H, W)
-    require_hip(pos, "pos", __name__)
-    if pos.dtype != torch.int32 or not pos.is_contiguous() or tuple(pos.shape) != (H, W, 2):
-        raise ValueError("pos must be a contiguous int32 [H, W, 2]")
+    H, W = tensor_is(tgt, torch.uint8, (None, None), "tgt", __name__).shape
+    check_plane(H, W)
+    tensor_is(key, torch.uint8, (H, W), "key", __name__)
+    tensor_is(mask_bits, torch.uint8, (H, W), "mask_bits", __name__)
+    tensor_is(pos, torch.int32, (H, W, 2), "pos", __name__)
     out = torch.empty(_cabi.prop_grid(H, W), dtype=torch.int32, device=tgt.device) if out is None else out
     d = _cabi.LpPropVisibleDesc(H, W, occlusion, 0, pos.data_ptr(), tgt.data_ptr(), key.data_ptr(), mask_bits.data_ptr(), out.data_ptr())
     launch("lp_prop_visible", tgt.device, ctypes.byref(d))
@@ -70,14 +62,9 @@ def occlude(code, flags, levels, out=None, hidden=None, mpyr_out=None):
     """The advance's mask `code` fp32 [H, W] (c / 256) split by the blocks' `flags` int32 [gh, gw]: (the visible part, the hidden
     part, both fp32 [H, W], and the pyramid of the visible part's bits uint8 [1, stride]).  One launch."""
     int_in(levels, 1, propagate.MAX_LEVELS, "levels")
-    require_hip(code, "code", __name__)
-    require_hip(flags, "flags", __name__)
-    if code.dtype != torch.float32 or code.ndim != 2 or not code.is_contiguous():
-        raise ValueError("code must be a contiguous fp32 [H, W]")
-    H, W = code.shape
-    _plane(H, W)
-    if flags.dtype != torch.int32 or not flags.is_contiguous() or tuple(flags.shape) != _cabi.prop_grid(H, W):
-        raise ValueError("flags must be level 0's contiguous int32 [gh, gw]")
+    H, W = tensor_is(code, torch.float32, (None, None), "code", __name__).shape
+    check_plane(H, W)
+    tensor_is(flags, torch.int32, _cabi.prop_grid(H, W), "flags", __name__)
     dev = code.device
     out = torch.empty((H, W), dtype=torch.float32, device=dev) if out is None else out
     hidden = torch.empty((H, W), dtype=torch.float32, device=dev) if hidden is None else hidden
@@ -89,7 +76,7 @@ def occlude(code, flags, levels, out=None, hidden=None, mpyr_out=None):
     return out, hidden, mpyr_out
 
 
-class _VisibleStep(_Step):
+class VisibleStep(Step):
     """propagate's step buffers and the three this form adds: the advance's code and pyramid, now scratch, and the flags."""
 
     def __init__(self, H, W, levels, search, smooth, occlusion, dev):
@@ -121,26 +108,18 @@ class _VisibleStep(_Step):
 def propagate_masks_visible(images, mask, key_frame=0, levels=4, search=2, smooth=8, occlusion=DEFAULT_OCCLUSION):
     """`mask`, painted on frame `key_frame` of `images` [F, H, W, C], followed through every frame and kept off what passes in
     front of it (module docstring): (mask, hidden), fp32 [F, H, W] each, on the images' device.  No device -> host read."""
-    _params(levels, search, smooth)
+    check_params(levels, search, smooth)
     int_in(occlusion, 0, MAX_OCCLUSION, "occlusion")
-    _images(images)
+    check_images(images)
     require_hip(mask, "mask", __name__)
     F, H, W, _ = images.shape
     int_in(key_frame, 0, F - 1, "key_frame")
     if occlusion == 0:
         return propagate.propagate_masks(images, mask, key_frame, levels, search, smooth), images.new_zeros((F, H, W), dtype=torch.float32)
-    if mask.ndim == 2:
-        mask = mask.unsqueeze(0)
-    if mask.ndim != 3 or mask.shape[0] not in (1, F) or tuple(mask.shape[1:]) != (H, W):
-        raise ValueError(f"mask {tuple(mask.shape)} does not match {F} frames of {H}x{W}: [H, W], [1, H, W] or [F, H, W]")
-    dev = images.device
-    key_pyr, key_out = key_mask(mask[key_frame if mask.shape[0] == F else 0].to(dev), levels)
-    out = torch.empty((F, H, W), dtype=torch.float32, device=dev)
-    hidden = torch.empty((F, H, W), dtype=torch.float32, device=dev)
-    out[key_frame] = key_out
+    key_pyr, out, orders = key_and_orders(images, mask, key_frame, levels)
+    hidden = torch.empty_like(out)
     hidden[key_frame].zero_()
-    step = _VisibleStep(H, W, levels, search, smooth, occlusion, dev)
-    for order in (list(range(key_frame, F)), list(range(key_frame, -1, -1))):
-        if len(order) > 1:
-            step.chain(_chain_frames(images, order, levels), key_pyr, out, hidden)
+    step = VisibleStep(H, W, levels, search, smooth, occlusion, images.device)
+    for order in orders:
+        step.chain(chain_frames(images, order, levels), key_pyr, out, hidden)
     return out, hidden

@@ -45,8 +45,8 @@ import ctypes
 import torch
 
 from . import _cabi
-from ._hostcall import chunks, int_in, launch, require_hip
-from .propagate import _images, luma_pyramids
+from ._hostcall import chunks, int_in, launch, tensor_is
+from ._motion import check_images, luma_pyramids
 
 MAX_LEVEL = _cabi.LP_PROP_MAX_LEVELS - 1
 MAX_SEARCH = _cabi.LP_SHOT_MAX_SEARCH
@@ -77,7 +77,7 @@ def shot_scores(images, level=2, search=2):
     read."""
     int_in(level, 0, MAX_LEVEL, "level")
     int_in(search, 1, MAX_SEARCH, "search")
-    _images(images)
+    check_images(images)
     F, H, W, C = images.shape
     int_in(F, 1, MAX_FRAMES, "the frame count")
     h, w = _cabi.prop_level_shape(H, W, level)
@@ -95,9 +95,7 @@ def shot_decide(score, n_pixels, threshold=THRESHOLD, hist=HIST, ratio=200, wind
     """`score` int64 [F - 1, 2] -> shot int32 [F] on its device (module docstring).  No device -> host read."""
     _decision(threshold, hist, ratio, window)
     int_in(n_pixels, 1, 1 << 28, "n_pixels")
-    require_hip(score, "score", __name__)
-    if score.dtype != torch.int64 or score.ndim != 2 or score.shape[1] != 2 or not score.is_contiguous():
-        raise ValueError(f"score must be a contiguous int64 [F - 1, 2], got {score.dtype} {list(score.shape)}")
+    tensor_is(score, torch.int64, (None, 2), "score", __name__)
     F = int_in(score.shape[0] + 1, 1, MAX_FRAMES, "the frame count")
     shot = torch.empty((F,), dtype=torch.int32, device=score.device)
     d = _cabi.LpShotDecideDesc(F, threshold, hist, ratio, window, 0, n_pixels, score.data_ptr() if F > 1 else None, shot.data_ptr())
@@ -200,7 +198,7 @@ def propagate_masks_shots(images, mask, shots, key_frame=0, levels=4, search=2, 
     """`propagate_masks` inside the key frame's shot; exactly 0 in every other shot: the subject of one scene is not in the next.
     fp32 [F, H, W]."""
     from .propagate import propagate_masks
-    _images(images)
+    check_images(images)
     F = images.shape[0]
     ranges = clip_ranges(shots, F)
     int_in(key_frame, 0, F - 1, "key_frame")

@@ -34,31 +34,13 @@ import numpy as np
 import torch
 
 from . import _cabi
-from ._hostcall import chunks, int_in, launch, require_hip, workspace
+from ._hostcall import chunks, int_in, launch, require_hip, tensor_is, workspace
+from ._motion import MAX_JOBS, FieldWalk, check_images, check_params, check_plane, clip_mask, luma_pyramids, row_addresses
 from ._util import _as_f32c
-from .propagate import _images, _params, _plane, luma_pyramids
 
 MAX_REACH = _cabi.LP_TFILL_MAX_REACH
 MAX_FRAMES = 65535
-MAX_JOBS = _cabi.LP_PROP_MAX_JOBS
 WS_CAP_BYTES = 1 << 30
-
-
-def _mask3(mask, F, H, W):
-    require_hip(mask, "mask", __name__)
-    if mask.ndim == 2:
-        mask = mask.unsqueeze(0)
-    if mask.ndim != 3 or mask.shape[0] not in (1, F) or tuple(mask.shape[1:]) != (H, W):
-        raise ValueError(f"mask {tuple(mask.shape)} does not match {F} frames of {H}x{W}: [H, W], [1, H, W] or [F, H, W]")
-    return mask
-
-
-def _pyramid_rows(t, H, W, levels, what):
-    require_hip(t, what, __name__)
-    stride = _cabi.prop_pyramid_ws_bytes(1, H, W, levels)
-    if t.dtype != torch.uint8 or t.ndim != 2 or t.shape[1] != stride or not t.is_contiguous():
-        raise ValueError(f"{what} must be frame pyramids, contiguous uint8 [n, {stride}]")
-    return t
 
 
 def known_pyramids(mask, frames, levels, source=None, remaining=None, frame0=0):
@@ -74,10 +56,10 @@ def known_pyramids(mask, frames, levels, source=None, remaining=None, frame0=0):
         raise ValueError(f"mask must be [{frames}, H, W] or [1, H, W], got {tuple(mask.shape)}")
     mask = _as_f32c(mask)
     _, H, W = mask.shape
-    _plane(H, W)
+    check_plane(H, W)
     for t, dtype, what in ((source, torch.int32, "source"), (remaining, torch.float32, "remaining")):
-        if t is not None and (require_hip(t, what, __name__).dtype != dtype or tuple(t.shape) != (frames, H, W) or not t.is_contiguous()):
-            raise ValueError(f"{what} must be a contiguous {dtype} [{frames}, {H}, {W}]")
+        if t is not None:
+            tensor_is(t, dtype, (frames, H, W), what, __name__)
     pyr = workspace(_cabi.load().lp_prop_pyramid_ws_bytes(frames, H, W, levels), mask.device, "lp_prop_pyramid_ws_bytes")
     d = _cabi.LpTfillKnownDesc(frames, H, W, levels, mask.shape[0], frame0, mask.data_ptr(), pyr.data_ptr(),
                                None if source is None else source.data_ptr(), None if remaining is None else remaining.data_ptr())
@@ -89,49 +71,47 @@ def step_fields(luma, known, steps, H, W, levels, search=2, smooth=8):
     """Stage 2: the level-0 final fields of `steps`, a list of (frame, donor) rows of `luma` and `known` (frame pyramids uint8
     [n, stride]): int32 [len(steps), gh, gw, 2].  Per MAX_JOBS steps 2 levels launches of lp_prop_match_batch / lp_prop_fill_batch;
     what the levels above 0 leave is scratch shared by every group of jobs."""
-    _params(levels, search, smooth)
-    _plane(H, W)
-    _pyramid_rows(luma, H, W, levels, "luma")
-    _pyramid_rows(known, H, W, levels, "known")
+    check_params(levels, search, smooth)
+    check_plane(H, W)
+    stride = _cabi.prop_pyramid_ws_bytes(1, H, W, levels)
+    tensor_is(luma, torch.uint8, (None, stride), "luma", __name__)
+    tensor_is(known, torch.uint8, (None, stride), "known", __name__)
     if known.shape[0] != luma.shape[0]:
         raise ValueError(f"luma holds {luma.shape[0]} frames and known {known.shape[0]}")
     steps = [(int_in(t, 0, luma.shape[0] - 1, "a step's frame"), int_in(s, 0, luma.shape[0] - 1, "a step's donor")) for t, s in steps]
-    dev = luma.device
-    grids = [_cabi.prop_grid(H, W, lv) for lv in range(levels)]
-    out = torch.empty((len(steps), *grids[0], 2), dtype=torch.int32, device=dev)
+    out = torch.empty((len(steps), *_cabi.prop_grid(H, W), 2), dtype=torch.int32, device=luma.device)
     if not steps:
         return out
-    m = min(MAX_JOBS, len(steps))
-    raw = [torch.empty((m, gh, gw, 2), dtype=torch.int32, device=dev) for gh, gw in grids]
-    valid = [torch.empty((m, gh, gw), dtype=torch.int32, device=dev) for gh, gw in grids]
-    field = [None] + [torch.empty((m, gh, gw, 2), dtype=torch.int32, device=dev) for gh, gw in grids[1:]]
-
-    def rows(t, n, first=0):                                             # the addresses of rows first .. first + n - 1 of t
-        return np.uint64(t.data_ptr()) + (np.arange(n, dtype=np.uint64) + np.uint64(first)) * np.uint64(t[0].numel() * t.element_size())
-    stride = luma.shape[1]
-    frame = np.array([t for t, _ in steps], dtype=np.uint64)
-    donor = np.array([s for _, s in steps], dtype=np.uint64)
-    t_match, t_fill = np.zeros((m, 6), dtype=np.uint64), np.zeros((m, 3), dtype=np.uint64)
-    desc = _cabi.LpPropMatchBatchDesc(H, W, levels, 0, search, smooth, 0, 0, t_match.ctypes.data)
+    walk = FieldWalk(min(MAX_JOBS, len(steps)), H, W, levels, search, smooth, luma.device, level0=False)
+    frame = np.array([t for t, _ in steps], dtype=np.uint64) * np.uint64(stride)
+    donor = np.array([s for _, s in steps], dtype=np.uint64) * np.uint64(stride)
+    src, tgt, weight = np.uint64(luma.data_ptr()) + frame, np.uint64(luma.data_ptr()) + donor, np.uint64(known.data_ptr()) + frame
+    dst = row_addresses(out, len(steps))
     for lo in range(0, len(steps), MAX_JOBS):
-        n = min(MAX_JOBS, len(steps) - lo)
-        t_match[:n, 0] = np.uint64(luma.data_ptr()) + frame[lo:lo + n] * np.uint64(stride)
-        t_match[:n, 1] = np.uint64(luma.data_ptr()) + donor[lo:lo + n] * np.uint64(stride)
-        t_match[:n, 2] = np.uint64(known.data_ptr()) + frame[lo:lo + n] * np.uint64(stride)
-        for lv in range(levels - 1, -1, -1):
-            t_match[:n, 3] = 0 if lv == levels - 1 else rows(field[lv + 1], n)
-            t_match[:n, 4] = t_fill[:n, 0] = rows(raw[lv], n)
-            t_match[:n, 5] = t_fill[:n, 1] = rows(valid[lv], n)
-            t_fill[:n, 2] = rows(field[lv], n) if lv else rows(out, n, lo)
-            desc.level, desc.jobs = lv, n
-            launch("lp_prop_match_batch", dev, ctypes.byref(desc))
-            launch("lp_prop_fill_batch", dev, t_fill.ctypes.data, n, *grids[lv])
+        walk.run(src[lo:lo + MAX_JOBS], tgt[lo:lo + MAX_JOBS], weight[lo:lo + MAX_JOBS], dst[lo:lo + MAX_JOBS])
     return out
 
 
 def new_state(H, W, dev):
     """The state planes of one frame: (org int32 [H, W], pos int32 [H, W, 2]).  Their content matters under the mask only."""
     return torch.empty((H, W), dtype=torch.int32, device=dev), torch.empty((H, W, 2), dtype=torch.int32, device=dev)
+
+
+def carry_planes(vec, known, donor_known, state, images, filled, source, remaining, out, **more):
+    """The planes of a carry, checked: `images` (already checked) gives the shapes, `more` names further int32 [F, H, W] planes.
+    Returns the frame's (org, pos): `out`, new when it is None."""
+    F, H, W, C = images.shape
+    out = new_state(H, W, images.device) if out is None else out
+    i32, f32, u8 = torch.int32, torch.float32, torch.uint8
+    planes = [(vec, i32, (*_cabi.prop_grid(H, W), 2), "vec"), (known, u8, (H, W), "known"), (donor_known, u8, (H, W), "donor_known"),
+              (images, f32, (F, H, W, C), "images"), (filled, f32, (F, H, W, C), "filled"), (source, i32, (F, H, W), "source"),
+              (remaining, f32, (F, H, W), "remaining"), *((t, i32, (F, H, W), what) for what, t in more.items()),
+              (out[0], i32, (H, W), "the state's org"), (out[1], i32, (H, W, 2), "the state's pos")]
+    if state is not None:
+        planes += [(state[0], i32, (H, W), "the donor state's org"), (state[1], i32, (H, W, 2), "the donor state's pos")]
+    for t, dtype, shape, what in planes:
+        tensor_is(t, dtype, shape, what, __name__)
+    return out
 
 
 def carry(vec, known, donor_known, state, images, filled, source, remaining, frame, donor, reach=0, nearer=False, out=None):
@@ -141,24 +121,13 @@ def carry(vec, known, donor_known, state, images, filled, source, remaining, fra
     [H, W]; `state` the donor's (org, pos) or None when the donor is the first frame of the direction.  The frame's (org, pos),
     `out` when given.  One launch."""
     int_in(reach, 0, MAX_REACH, "reach")
-    images = _images(images)
-    F, H, W, C = images.shape
+    F, H, W, C = check_images(images).shape
     int_in(F, 2, MAX_FRAMES, "the frame count")
     int_in(frame, 0, F - 1, "frame")
     int_in(donor, 0, F - 1, "donor")
     if abs(frame - donor) != 1:
         raise ValueError(f"donor {donor} is not a neighbour of frame {frame}")
-    out = new_state(H, W, images.device) if out is None else out
-    planes = [(vec, torch.int32, (*_cabi.prop_grid(H, W), 2), "vec"), (known, torch.uint8, (H, W), "known"),
-              (donor_known, torch.uint8, (H, W), "donor_known"), (images, torch.float32, (F, H, W, C), "images"),
-              (filled, torch.float32, (F, H, W, C), "filled"), (source, torch.int32, (F, H, W), "source"),
-              (remaining, torch.float32, (F, H, W), "remaining"), (out[0], torch.int32, (H, W), "the state's org"),
-              (out[1], torch.int32, (H, W, 2), "the state's pos")]
-    if state is not None:
-        planes += [(state[0], torch.int32, (H, W), "the donor state's org"), (state[1], torch.int32, (H, W, 2), "the donor state's pos")]
-    for t, dtype, shape, what in planes:
-        if require_hip(t, what, __name__).dtype != dtype or tuple(t.shape) != tuple(shape) or not t.is_contiguous():
-            raise ValueError(f"{what} must be a contiguous {dtype} {list(shape)}, got {t.dtype} {list(t.shape)}")
+    out = carry_planes(vec, known, donor_known, state, images, filled, source, remaining, out)
     d = _cabi.LpTfillCarryDesc(F, H, W, C, frame, donor, reach, int(bool(nearer)), vec.data_ptr(), known.data_ptr(),
                                donor_known.data_ptr(), None if state is None else state[0].data_ptr(),
                                None if state is None else state[1].data_ptr(), out[0].data_ptr(), out[1].data_ptr(),
@@ -167,7 +136,7 @@ def carry(vec, known, donor_known, state, images, filled, source, remaining, fra
     return out
 
 
-class _Pyramids:
+class Pyramids:
     """The luma and known pyramids of a range of frames, built when another range is asked for.  The first time a frame's known
     bits are built its `source` and `remaining` planes are started with them."""
 
@@ -191,47 +160,62 @@ class _Pyramids:
         return self.luma, self.known
 
 
+def clip_outputs(images, mask, levels):
+    """What the two fills start from: (the contiguous fp32 clip that is sampled, `filled`, a copy of it, written next to it,
+    remaining fp32 [F, H, W], source int32 [F, H, W], their `Pyramids`).  One frame: its source and remaining are written."""
+    check_images(images)
+    F, H, W, _ = images.shape
+    int_in(F, 1, MAX_FRAMES, "the frame count")
+    dev = images.device
+    mask = _as_f32c(clip_mask(mask, F, H, W, __name__).to(dev))
+    images = _as_f32c(images)
+    filled = images.clone()
+    source = torch.empty((F, H, W), dtype=torch.int32, device=dev)
+    remaining = torch.empty((F, H, W), dtype=torch.float32, device=dev)
+    pyramids = Pyramids(images, mask, levels, source, remaining)
+    if F == 1:
+        pyramids.get(0, 1)
+    return images, filled, remaining, source, pyramids
+
+
+def carry_direction(entry, desc, order, pyramids, states, fields_args, cap):
+    """The carries of one direction of a clip, one launch of `entry` per step along the frames `order`: `desc` holds what does
+    not move with the step; `states` are the two (org, pos) the steps alternate between; `fields_args` = (H, W, levels, search,
+    smooth).  Pyramids and fields are built for as many steps at a time as stay under `cap` bytes."""
+    H, W, levels = fields_args[:3]
+    stride = _cabi.prop_pyramid_ws_bytes(1, H, W, levels)
+    gh, gw = _cabi.prop_grid(H, W)
+    per_step = 2 * stride + gh * gw * 8                                  # a frame's two pyramids and a field
+    dev = pyramids.images.device
+    done = 0                                                             # carries of this direction so far
+    for first, n in chunks(len(order) - 1, per_step, max(cap - 2 * stride, 1)):
+        lo, hi = min(order[first], order[first + n]), max(order[first], order[first + n]) + 1
+        luma, known = pyramids.get(lo, hi)
+        fields = step_fields(luma, known, [(order[k] - lo, order[k - 1] - lo) for k in range(first + 1, first + n + 1)], *fields_args)
+        for j, k in enumerate(range(first + 1, first + n + 1)):
+            t, s = order[k], order[k - 1]
+            src, dst = states[(done + 1) & 1], states[done & 1]
+            desc.frame, desc.donor, desc.vec = t, s, fields[j].data_ptr()
+            desc.known, desc.donor_known = known[t - lo].data_ptr(), known[s - lo].data_ptr()
+            desc.org_src, desc.pos_src = (None, None) if done == 0 else (src[0].data_ptr(), src[1].data_ptr())
+            desc.org_dst, desc.pos_dst = dst[0].data_ptr(), dst[1].data_ptr()
+            launch(entry, dev, ctypes.byref(desc))
+            done += 1
+
+
 def temporal_fill(images, mask, levels=4, search=2, smooth=8, reach=0):
     """What lies under `mask` in the frames `images` [F, H, W, C], borrowed from the nearest frame that shows it (module
     docstring): (filled fp32 [F, H, W, C], remaining fp32 [F, H, W], source int32 [F, H, W]) on the images' device.  No
     device -> host read."""
-    _params(levels, search, smooth)
+    check_params(levels, search, smooth)
     int_in(reach, 0, MAX_REACH, "reach")
-    _images(images)
+    images, filled, remaining, source, pyramids = clip_outputs(images, mask, levels)
     F, H, W, C = images.shape
-    int_in(F, 1, MAX_FRAMES, "the frame count")
-    dev = images.device
-    mask = _as_f32c(_mask3(mask, F, H, W).to(dev))
-    images = _as_f32c(images)                                            # what is sampled; `filled` is written next to it
-    filled = images.clone()
-    source = torch.empty((F, H, W), dtype=torch.int32, device=dev)
-    remaining = torch.empty((F, H, W), dtype=torch.float32, device=dev)
-    pyramids = _Pyramids(images, mask, levels, source, remaining)
-    if F == 1:
-        pyramids.get(0, 1)                                               # source and remaining of the one frame
-        return filled, remaining, source
-    stride = _cabi.prop_pyramid_ws_bytes(1, H, W, levels)
-    gh, gw = _cabi.prop_grid(H, W)
-    per_step = 2 * stride + gh * gw * 8                                  # a frame's two pyramids and a field
-    states = [new_state(H, W, dev) for _ in range(2)]
-    desc = _cabi.LpTfillCarryDesc(F, H, W, C, 0, 0, reach, 0, None, None, None, None, None, None, None, images.data_ptr(),
-                                  filled.data_ptr(), source.data_ptr(), remaining.data_ptr())
-    for d in (1, -1):
-        order = list(range(F)) if d == 1 else list(range(F - 1, -1, -1))
-        desc.nearer = int(d == -1)
-        done = 0                                                         # carries of this direction so far
-        for first, n in chunks(F - 1, per_step, max(WS_CAP_BYTES - 2 * stride, 1)):
-            lo, hi = min(order[first], order[first + n]), max(order[first], order[first + n]) + 1
-            luma, known = pyramids.get(lo, hi)
-            fields = step_fields(luma, known, [(order[k] - lo, order[k - 1] - lo) for k in range(first + 1, first + n + 1)],
-                                 H, W, levels, search, smooth)
-            for j, k in enumerate(range(first + 1, first + n + 1)):
-                t, s = order[k], order[k - 1]
-                src, dst = states[(done + 1) & 1], states[done & 1]
-                desc.frame, desc.donor, desc.vec = t, s, fields[j].data_ptr()
-                desc.known, desc.donor_known = known[t - lo].data_ptr(), known[s - lo].data_ptr()
-                desc.org_src, desc.pos_src = (None, None) if done == 0 else (src[0].data_ptr(), src[1].data_ptr())
-                desc.org_dst, desc.pos_dst = dst[0].data_ptr(), dst[1].data_ptr()
-                launch("lp_tfill_carry", dev, ctypes.byref(desc))
-                done += 1
+    if F > 1:
+        states = [new_state(H, W, images.device) for _ in range(2)]
+        desc = _cabi.LpTfillCarryDesc(F, H, W, C, 0, 0, reach, 0, None, None, None, None, None, None, None, images.data_ptr(),
+                                      filled.data_ptr(), source.data_ptr(), remaining.data_ptr())
+        for order in (list(range(F)), list(range(F - 1, -1, -1))):       # forwards, then backwards: only what is nearer in time
+            carry_direction("lp_tfill_carry", desc, order, pyramids, states, (H, W, levels, search, smooth), WS_CAP_BYTES)
+            desc.nearer = 1
     return filled, remaining, source

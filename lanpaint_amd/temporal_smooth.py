@@ -37,10 +37,10 @@ import ctypes
 import torch
 
 from . import _cabi
-from ._hostcall import chunks, int_in, launch, require_hip
+from ._hostcall import chunks, int_in, launch, require_hip, tensor_is
+from ._motion import check_images, check_params, clip_mask, luma_pyramids
 from ._util import _as_f32c
-from .propagate import _images, _params, luma_pyramids
-from .temporal_fill import MAX_FRAMES, _mask3, known_pyramids, step_fields
+from .temporal_fill import MAX_FRAMES, known_pyramids, step_fields
 
 MAX_RADIUS = _cabi.LP_TSMOOTH_MAX_RADIUS
 MOTIONS = ("background", "picture")
@@ -60,13 +60,12 @@ def field_steps(lo, hi, frames, radius):
     return range(lo, min(hi + radius - 1, frames - 1)), range(max(lo - radius + 1, 1), hi)
 
 
-def _launch_frames(entry, desc, planes, fwd, bwd, known, images, radius, tolerance, first, count, fwd_first, bwd_first):
+def launch_frames(entry, desc, planes, fwd, bwd, known, images, radius, tolerance, first, count, fwd_first, bwd_first):
     """What `smooth_frames` and `temporal_smooth_robust.robust_frames` share: the checks, and the call of `entry` with the
     descriptor `desc`.  `planes`: the outputs behind `out`, int32 [F, H, W] each, as (given or None, name).  Returns the outputs."""
     int_in(radius, 1, MAX_RADIUS, "radius")
     int_in(tolerance, 0, 255, "tolerance")
-    images = _images(images)
-    F, H, W, C = images.shape
+    F, H, W, C = check_images(images).shape
     int_in(F, 1, MAX_FRAMES, "the frame count")
     int_in(first, 0, F - 1, "first")
     count = int_in(F - first if count is None else count, 1, F - first, "count")
@@ -83,8 +82,7 @@ def _launch_frames(entry, desc, planes, fwd, bwd, known, images, radius, toleran
                 raise ValueError(f"{what} is needed for the frames {steps[0]}..{steps[-1]}")
             rows.append((None, 0, 0))
             continue
-        if require_hip(t, what, __name__).dtype != torch.int32 or t.ndim != 4 or tuple(t.shape[1:]) != (*grid, 2) or not t.is_contiguous():
-            raise ValueError(f"{what} must be a contiguous int32 [n, {grid[0]}, {grid[1]}, 2], got {t.dtype} {list(t.shape)}")
+        tensor_is(t, torch.int32, (None, *grid, 2), what, __name__)
         int_in(start, 0, F - 1, f"{what}_first")
         if len(steps) and (start > steps[0] or start + t.shape[0] <= steps[-1]):
             raise ValueError(f"{what} holds the frames {start}..{start + t.shape[0] - 1}, the walks read {steps[0]}..{steps[-1]}")
@@ -96,8 +94,7 @@ def _launch_frames(entry, desc, planes, fwd, bwd, known, images, radius, toleran
                          f"{known.dtype} {list(known.shape)}")
     for t, dtype, shape, what in ((images, torch.float32, (F, H, W, C), "images"), (out, torch.float32, (F, H, W, C), "out"),
                                   *((t, torch.int32, (F, H, W), what) for t, what in planes)):
-        if require_hip(t, what, __name__).dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous():
-            raise ValueError(f"{what} must be a contiguous {dtype} {list(shape)}, got {t.dtype} {list(t.shape)}")
+        tensor_is(t, dtype, shape, what, __name__)
     (f_ptr, f_first, f_n), (b_ptr, b_first, b_n) = rows
     d = desc(F, H, W, C, first, count, radius, tolerance, f_first, f_n, b_first, b_n, f_ptr, b_ptr, known.data_ptr(), known[0].numel(),
              images.data_ptr(), out.data_ptr(), *(t.data_ptr() for t, _ in planes))
@@ -113,20 +110,20 @@ def smooth_frames(fwd, bwd, known, images, radius=2, tolerance=24, first=0, coun
     bwd_first + j towards the one before; they must cover `field_steps(first, first + count, F, radius)` and may be None where
     that is empty.  `known` uint8 [count, H, W], or frame pyramids [count, stride]: the bits of the frames written.
     Returns (out, support)."""
-    return _launch_frames("lp_tsmooth", _cabi.LpTsmoothDesc, ((out, "out"), (support, "support")), fwd, bwd, known, images, radius,
+    return launch_frames("lp_tsmooth", _cabi.LpTsmoothDesc, ((out, "out"), (support, "support")), fwd, bwd, known, images, radius,
                           tolerance, first, count, fwd_first, bwd_first)
 
 
-def _over_chunks(frames_fn, planes, images, mask, radius, tolerance, motion, levels, search, smooth):
+def over_chunks(frames_fn, planes, images, mask, radius, tolerance, motion, levels, search, smooth):
     """The whole call of `temporal_smooth` and of `temporal_smooth_robust.temporal_smooth_robust`: the fields chunk by chunk, and
     `frames_fn` (`smooth_frames` or `robust_frames`) on every chunk, into `out` and `planes` int32 [F, H, W] held whole."""
     _numbers(radius, tolerance, motion)
-    _params(levels, search, smooth)
-    _images(images)
+    check_params(levels, search, smooth)
+    check_images(images)
     F, H, W, C = images.shape
     int_in(F, 1, MAX_FRAMES, "the frame count")
     dev = images.device
-    mask = _as_f32c(_mask3(mask, F, H, W).to(dev))
+    mask = _as_f32c(clip_mask(mask, F, H, W, __name__).to(dev))
     images = _as_f32c(images)                                            # what is sampled; `out` is written next to it
     out = torch.empty((F, H, W, C), dtype=torch.float32, device=dev)
     outputs = (out, *(torch.empty((F, H, W), dtype=torch.int32, device=dev) for _ in range(planes)))
@@ -155,4 +152,4 @@ def temporal_smooth(images, mask, radius=2, tolerance=24, motion="background", l
     """What lies under `mask` in the frames `images` [F, H, W, C], pulled towards what the neighbouring frames hold at the same
     scene point (module docstring): (out fp32 [F, H, W, C], support int32 [F, H, W]) on the images' device.  No device -> host
     read."""
-    return _over_chunks(smooth_frames, 1, images, mask, radius, tolerance, motion, levels, search, smooth)
+    return over_chunks(smooth_frames, 1, images, mask, radius, tolerance, motion, levels, search, smooth)

@@ -32,7 +32,7 @@ chunk (`robust_frames`).  Nothing is carried from chunk to chunk, so chunking ca
 from __future__ import annotations
 
 from . import _cabi
-from .temporal_smooth import _launch_frames, _over_chunks
+from .temporal_smooth import launch_frames, over_chunks
 
 QUORUM = _cabi.LP_TSMOOTH_ROBUST_QUORUM
 
@@ -42,7 +42,7 @@ def robust_frames(fwd, bwd, known, images, radius=2, tolerance=24, first=0, coun
     """The one launch, with the arguments and the checks of `temporal_smooth.smooth_frames` and a third output: the frames
     first .. first + count - 1 of `out`, `support` and `replaced` int32 [F, H, W] are written (new when not given: the other
     frames are then left unwritten).  Returns (out, support, replaced)."""
-    return _launch_frames("lp_tsmooth_robust", _cabi.LpTsmoothRobustDesc, ((out, "out"), (support, "support"), (replaced, "replaced")),
+    return launch_frames("lp_tsmooth_robust", _cabi.LpTsmoothRobustDesc, ((out, "out"), (support, "support"), (replaced, "replaced")),
                           fwd, bwd, known, images, radius, tolerance, first, count, fwd_first, bwd_first)
 
 
@@ -50,4 +50,4 @@ def temporal_smooth_robust(images, mask, radius=2, tolerance=24, motion="backgro
     """What lies under `mask` in the frames `images` [F, H, W, C], pulled towards what agrees with the temporal median along the
     motion, and replaced by it where it is an outlier (module docstring): (out fp32 [F, H, W, C], support int32 [F, H, W],
     replaced int32 [F, H, W]) on the images' device.  No device -> host read."""
-    return _over_chunks(robust_frames, 2, images, mask, radius, tolerance, motion, levels, search, smooth)
+    return over_chunks(robust_frames, 2, images, mask, radius, tolerance, motion, levels, search, smooth)

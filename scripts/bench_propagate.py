@@ -236,18 +236,19 @@ def wall(fn):
     return (time.perf_counter() - t0) * 1e3
 
 
-def count_launches(fn):
-    from lanpaint_amd import propagate
-    names, real = [], propagate.launch
-
-    def counting(entry, *a):
-        names.append(entry)
-        return real(entry, *a)
-    propagate.launch = counting
+def count_launches(fn, *modules):
+    """The entry names `fn` launches from `modules` (lanpaint_amd.propagate when none is named) and from the motion layer they
+    share, in call order: every module binds `launch` by name, so each one's own name is wrapped."""
+    from lanpaint_amd import _motion, propagate
+    real = {m: m.launch for m in (*(modules or (propagate,)), _motion)}
+    names = []
+    for m, f in real.items():
+        m.launch = lambda entry, *a, f=f: (names.append(entry), f(entry, *a))[1]
     try:
         fn()
     finally:
-        propagate.launch = real
+        for m, f in real.items():
+            m.launch = f
     return names
 
 
@@ -262,7 +263,7 @@ def stage_times(job, reps):
     pyr = propagate.luma_pyramids(job["images"][:2], LEVELS)
     out["key_mask"] = events(lambda: propagate.key_mask(job["mask"], LEVELS), reps)
     mpyr, _ = propagate.key_mask(job["mask"], LEVELS)
-    step = propagate._Step(H, W, LEVELS, SEARCH, SMOOTH, job["images"].device)
+    step = propagate.Step(H, W, LEVELS, SEARCH, SMOOTH, job["images"].device)
     step.field_of(pyr[0], pyr[1], mpyr)
     torch.cuda.synchronize()
     for lv in range(LEVELS - 1, -1, -1):

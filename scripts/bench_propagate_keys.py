@@ -89,17 +89,7 @@ def composed(images, masks, keys):
 
 def count_launches(fn):
     from lanpaint_amd import propagate_keys
-    names, real = [], propagate_keys.launch
-
-    def counting(entry, *a):
-        names.append(entry)
-        return real(entry, *a)
-    propagate_keys.launch = counting
-    try:
-        fn()
-    finally:
-        propagate_keys.launch = real
-    return names
+    return single.count_launches(fn, propagate_keys)
 
 
 def measure(job, name, keys, iters, warmup):

@@ -39,17 +39,7 @@ KEY_SETS = {"ends": lambda F: [0, F - 1], "ends and middle": lambda F: [0, F // 
 
 def count_launches(fn):
     from lanpaint_amd import propagate_keys, propagate_keys_visible
-    names, real = [], (propagate_keys.launch, propagate_keys_visible.launch)
-
-    def counting(entry, *a):
-        names.append(entry)
-        return real[0](entry, *a)
-    propagate_keys.launch = propagate_keys_visible.launch = counting
-    try:
-        fn()
-    finally:
-        propagate_keys.launch, propagate_keys_visible.launch = real
-    return names
+    return single.count_launches(fn, propagate_keys, propagate_keys_visible)
 
 
 def stage_times(job, masks, keys, reps):
@@ -62,7 +52,7 @@ def stage_times(job, masks, keys, reps):
     dev = job["images"].device
     plan = propagate_keys.chain_plan(F, keys)
     jobs = min(len(plan), kv.MAX_JOBS)
-    pyr = propagate_keys._clip_pyramids(job["images"][:2], LEVELS)
+    pyr = propagate_keys.clip_pyramids(job["images"][:2], LEVELS)
     mpyr, bits = propagate.key_mask(masks[0], LEVELS)
     luma = [propagate.level_view(pyr[i:i + 1], H, W, 0)[0] for i in (0, 1)]
     yy, xx = torch.meshgrid(torch.arange(H, device=dev), torch.arange(W, device=dev), indexing="ij")

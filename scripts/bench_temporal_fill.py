@@ -122,17 +122,7 @@ def torch_temporal_fill(images, mask, levels=LEVELS, search=SEARCH, smooth=SMOOT
 # ---- measurements ---------------------------------------------------------------------------------------------------------------------------
 def count_launches(fn):
     from lanpaint_amd import propagate, temporal_fill
-    names, real = [], (propagate.launch, temporal_fill.launch)
-
-    def counting(entry, *a):
-        names.append(entry)
-        return real[0](entry, *a)
-    propagate.launch = temporal_fill.launch = counting
-    try:
-        fn()
-    finally:
-        propagate.launch, temporal_fill.launch = real
-    return names
+    return single.count_launches(fn, propagate, temporal_fill)
 
 
 def expected_launches(F, levels):

@@ -103,17 +103,7 @@ def torch_temporal_smooth(images, mask, radius, tolerance=TOLERANCE, motion=MOTI
 # ---- measurements ---------------------------------------------------------------------------------------------------------------------------
 def count_launches(fn):
     from lanpaint_amd import propagate, temporal_fill, temporal_smooth
-    names, real = [], (propagate.launch, temporal_fill.launch, temporal_smooth.launch)
-
-    def counting(entry, *a):
-        names.append(entry)
-        return real[0](entry, *a)
-    propagate.launch = temporal_fill.launch = temporal_smooth.launch = counting
-    try:
-        fn()
-    finally:
-        propagate.launch, temporal_fill.launch, temporal_smooth.launch = real
-    return names
+    return single.count_launches(fn, propagate, temporal_fill, temporal_smooth)
 
 
 def measure(job, iters, warmup, torch_frames, reps):

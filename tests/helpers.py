@@ -75,6 +75,17 @@ def run_product_case(name, device="cuda", rng="recorded", model_cls=None, sampli
                 golden=g, case=case, model_options=mo)
 
 
+def record_launches(monkeypatch, *modules):
+    """The C entry names launched from `modules` and from the motion layer they share, in call order: the list fills as calls
+    are made.  Every module binds `launch` by name (`from ._hostcall import launch`), so each one's own name is patched."""
+    from lanpaint_amd import _motion
+    names = []
+    for module in dict.fromkeys((*modules, _motion)):
+        if hasattr(module, "launch"):                                  # a module that only composes others has none of its own
+            monkeypatch.setattr(module, "launch", lambda entry, *a, real=module.launch: (names.append(entry), real(entry, *a))[1])
+    return names
+
+
 def assert_digest(a, g, prefix, sample_seed, what, rel=2e-5):
     """Tensor `a` against the digest stored under `prefix` in fixture `g` (golden_cases.digest): the sampled elements and
     the per-slice sums / sums of squares."""

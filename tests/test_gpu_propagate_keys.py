@@ -13,6 +13,7 @@ from lanpaint_amd import _cabi, propagate, propagate_keys, propagate_keys_nodes,
 from tests import propagate_keys_ref as kref
 from tests import propagate_ref as ref
 from tests import stabilize_ref as stab
+from tests.helpers import record_launches
 from tests.test_gpu_propagate import MASKS, _bits, _dev, _disc, _rng, _same_bits, _soft, _video
 
 pytestmark = pytest.mark.gpu
@@ -198,16 +199,6 @@ def test_half_precision_images_and_a_still_video():
     _same_bits(got.cpu().numpy(), np.repeat(ref.binarise(soft).astype(np.float32)[None], F7, axis=0), "a still video")
 
 
-def _counting(monkeypatch):
-    names, real = [], propagate_keys.launch
-
-    def counting(entry, *a):
-        names.append(entry)
-        return real(entry, *a)
-    monkeypatch.setattr(propagate_keys, "launch", counting)
-    return names
-
-
 def test_more_chains_than_one_launch_holds(monkeypatch):
     """A key on every even frame of 36: 35 chains of one step, so every stage of the step takes two launches (32 + 3)."""
     F, H, W = 36, 24, 40
@@ -215,18 +206,35 @@ def test_more_chains_than_one_launch_holds(monkeypatch):
     assert len(propagate_keys.chain_plan(F, keys)) == 35
     images = _video(F, H, W, 3, seed=2)
     masks = np.stack([MASKS[("disc", "soft", "full")[k % 3]](H, W, k) for k in keys])
-    names = _counting(monkeypatch)
+    names = record_launches(monkeypatch, propagate_keys)
     got = propagate_keys.propagate_keys(_dev(images), _dev(masks), keys, LEVELS, SEARCH, SMOOTH)
     batched = [n for n in names if n.endswith("_batch")]
     assert len(batched) == 2 * (2 * LEVELS + 1) and names.count("lp_prop_merge") == 17
     _same_bits(got.cpu().numpy(), kref.propagate_keys_ref(images, masks, keys, LEVELS, SEARCH, SMOOTH), "35 chains")
 
 
+def test_the_active_chains_are_no_prefix_of_the_plan_and_more_than_one_launch_holds(monkeypatch):
+    """Keys on 0, 2, ..., 64 and on 69 of 70 frames: 64 chains of one step, then the two chains of the gap 64 to 69 with four.  Step
+    1 takes three launches per stage (32 + 32 + 2 jobs); steps 2 to 4 run plan rows 64 and 65 alone, in the field walk's scratch
+    rows 0 and 1."""
+    F, H, W = 70, 9, 15
+    keys = list(range(0, 65, 2)) + [69]
+    plan = propagate_keys.chain_plan(F, keys)
+    assert len(plan) == 66 and [c[3] for c in plan] == [1] * 64 + [4, 4]
+    images = _video(F, H, W, 3, seed=5)
+    masks = np.stack([MASKS[("disc", "soft", "full")[k % 3]](H, W, k) for k in keys])
+    names = record_launches(monkeypatch, propagate_keys)
+    got = propagate_keys.propagate_keys(_dev(images), _dev(masks), keys, LEVELS, SEARCH, SMOOTH)
+    batched = [n for n in names if n.endswith("_batch")]
+    assert len(batched) == (3 + 3) * (2 * LEVELS + 1) and names.count("lp_prop_merge") == 33
+    _same_bits(got.cpu().numpy(), kref.propagate_keys_ref(images, masks, keys, LEVELS, SEARCH, SMOOTH), "66 chains")
+
+
 def test_the_chains_of_a_step_share_their_launches(monkeypatch):
     """F = 7 with keys on both ends at 3 levels: two chains of 5 steps run side by side, 5 x 7 batched launches and not 10 x 7."""
     H, W = 40, 70
     images, masks = _dev(_clip((H, W), False)[0]), _dev(np.stack([_disc(H, W), _disc(H, W)]))
-    names = _counting(monkeypatch)
+    names = record_launches(monkeypatch, propagate_keys)
     propagate_keys.propagate_keys(images, masks, [0, 6], LEVELS, SEARCH, SMOOTH)
     batched = [n for n in names if n.endswith("_batch")]
     assert len(batched) == 5 * (2 * LEVELS + 1) == 35
@@ -248,7 +256,7 @@ def test_two_calls_small_chunks_and_the_pyramid_cap(monkeypatch):
     assert pyramids < H * W * 3 * 4 * 2                               # the cap below holds the pyramids and one frame's conversion
     monkeypatch.setattr(propagate_keys, "WS_CAP_BYTES", pyramids + 8)
     monkeypatch.setattr(stabilize, "WS_CAP_BYTES", 1)                 # the distances one frame at a time
-    names = _counting(monkeypatch)
+    names = record_launches(monkeypatch, propagate_keys)
     _equal(propagate_keys.propagate_keys(images.half(), masks, keys, LEVELS, SEARCH, SMOOTH), half, "one frame per chunk")
     assert names.count("lp_prop_luma") == F7
     _equal(propagate_keys.propagate_keys(images, masks, keys, LEVELS, SEARCH, SMOOTH), whole, "fp32 needs no conversion")

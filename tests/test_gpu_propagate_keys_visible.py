@@ -15,6 +15,7 @@ from tests import propagate_keys_ref as kref
 from tests import propagate_keys_visible_ref as kvref
 from tests import propagate_ref as ref
 from tests import propagate_visible_ref as vref
+from tests.helpers import record_launches
 from tests.test_gpu_propagate_visible import MASKS, _dev, _flags, _lumas, _occluded_video, _positions, _rng, _same, _same_bits
 from tests.test_propagate_visible_host import occluded_disc_clip
 
@@ -271,14 +272,6 @@ def test_the_clip_on_which_chains_get_lost():
     assert torch.equal(again, got) and torch.equal(again_hidden, hidden)                                     # two runs, the same bits
 
 
-def _counting(monkeypatch):
-    names = []
-    for module in (propagate_keys, propagate_keys_visible):
-        real = module.launch
-        monkeypatch.setattr(module, "launch", lambda entry, *a, real=real: (names.append(entry), real(entry, *a))[1])
-    return names
-
-
 STEP = ["lp_prop_match_batch", "lp_prop_fill_batch"] * LEVELS + ["lp_prop_advance_batch", "lp_prop_visible_batch", "lp_prop_occlude_batch"]
 
 
@@ -290,7 +283,7 @@ def test_more_chains_than_one_launch_holds(monkeypatch):
     assert len(propagate_keys.chain_plan(F, keys)) == 39
     images = _rng(F, H, W, 41).random((F, H, W, 3), dtype=np.float32)
     masks = np.stack([MASKS[("disc", "full", "sparse")[k % 3]](H, W).astype(np.float32) for k in keys])
-    names = _counting(monkeypatch)
+    names = record_launches(monkeypatch, propagate_keys, propagate_keys_visible)
     got, hidden = kv.propagate_keys_visible(_dev(images), _dev(masks), keys, LEVELS, SEARCH, SMOOTH, 16)
     batched = [n for n in names if n.endswith("_batch")]
     assert batched == ["lp_prop_occlude_batch"] * 2 + STEP * 2 and names.count("lp_prop_merge_visible") == 19
@@ -299,13 +292,32 @@ def test_more_chains_than_one_launch_holds(monkeypatch):
     _same_bits(hidden.cpu().numpy(), want_hidden, "39 chains")
 
 
+def test_the_active_chains_are_no_prefix_of_the_plan_and_more_than_one_launch_holds(monkeypatch):
+    """Keys on 0, 2, ..., 64 and on 69 of 70 frames: 64 chains of one step, then the two chains of the gap 64 to 69 with four.  Step
+    1 takes three launches per stage (32 + 32 + 2 jobs), as does the count of the 66 chains' key bits; steps 2 to 4 run plan rows 64
+    and 65 alone, in the field walk's scratch rows 0 and 1."""
+    F, H, W = 70, 9, 15
+    keys = list(range(0, 65, 2)) + [69]
+    plan = propagate_keys.chain_plan(F, keys)
+    assert len(plan) == 66 and [c[3] for c in plan] == [1] * 64 + [4, 4]
+    images = _rng(F, H, W, 43).random((F, H, W, 3), dtype=np.float32)
+    masks = np.stack([MASKS[("disc", "full", "sparse")[k % 3]](H, W).astype(np.float32) for k in keys])
+    names = record_launches(monkeypatch, propagate_keys, propagate_keys_visible)
+    got, hidden = kv.propagate_keys_visible(_dev(images), _dev(masks), keys, LEVELS, SEARCH, SMOOTH, 16)
+    batched = [n for n in names if n.endswith("_batch")]
+    assert batched == ["lp_prop_occlude_batch"] * 3 + STEP * (3 + 3) and names.count("lp_prop_merge_visible") == 33
+    want, want_hidden = kvref.propagate_keys_visible_ref(images, masks, keys, LEVELS, SEARCH, SMOOTH, 16)
+    _same_bits(got.cpu().numpy(), want, "66 chains")
+    _same_bits(hidden.cpu().numpy(), want_hidden, "66 chains")
+
+
 def test_the_launches_of_a_call_and_the_merge_in_chunks(monkeypatch):
     """F = 7 with keys on both ends: two chains of 5 steps side by side, 2 L + 3 launches per step; one launch counts both keys'
     bits; one merge for the gap, or one per frame when the distances go a frame at a time."""
     H, W = 70, 130
     images, mask = _occluded_video(7, H, W)
     t, m = _dev(images), _dev(_painted(mask, (0, 6)))
-    names = _counting(monkeypatch)
+    names = record_launches(monkeypatch, propagate_keys, propagate_keys_visible)
     got, hidden = kv.propagate_keys_visible(t, m, [0, 6], LEVELS, SEARCH, SMOOTH, 16)
     batched = [n for n in names if n.endswith("_batch")]
     assert batched == ["lp_prop_occlude_batch"] + STEP * 5
@@ -346,7 +358,7 @@ def test_occlusion_zero_is_propagate_keys_and_makes_no_new_launch(monkeypatch):
     images, mask = _occluded_video(7, H, W)
     t, m = _dev(images), _dev(_painted(mask, (1, 5)))
     want = propagate_keys.propagate_keys(t, m, [1, 5], LEVELS, SEARCH, SMOOTH)
-    names = _counting(monkeypatch)
+    names = record_launches(monkeypatch, propagate_keys, propagate_keys_visible)
     got, hidden = kv.propagate_keys_visible(t, m, [1, 5], LEVELS, SEARCH, SMOOTH, 0)
     assert torch.equal(got, want)
     assert hidden.is_cuda and hidden.dtype == torch.float32 and tuple(hidden.shape) == (7, H, W) and not hidden.any()

@@ -11,6 +11,7 @@ import torch
 from lanpaint_amd import _cabi, propagate, propagate_visible, propagate_visible_nodes
 from tests import propagate_ref as ref
 from tests import propagate_visible_ref as vref
+from tests.helpers import record_launches
 
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda", 0)
@@ -216,17 +217,22 @@ def test_occlusion_zero_is_propagate_masks_and_makes_no_new_launch(monkeypatch):
     H, W = 40, 70
     images, mask = _occluded_video(4, H, W)
     t, m = _dev(images), _dev(mask)
-    names, real = [], propagate_visible.launch
-    monkeypatch.setattr(propagate_visible, "launch", lambda entry, *a: (names.append(entry), real(entry, *a))[1])
+    names = record_launches(monkeypatch, propagate_visible)           # this module's launches and the shared layer's: the pyramids
+    want = propagate.propagate_masks(t, m, 2, 3, 2, 8)
+    plain = list(names)
+    assert set(plain) == {"lp_prop_luma"}
+    del names[:]
     got, hidden = propagate_visible.propagate_masks_visible(t, m, 2, 3, 2, 8, 0)
-    assert names == [] and torch.equal(got, propagate.propagate_masks(t, m, 2, 3, 2, 8))
+    assert names == plain and torch.equal(got, want)                  # nothing but what propagate_masks launches itself
     assert hidden.is_cuda and hidden.dtype == torch.float32 and tuple(hidden.shape) == (4, H, W) and not hidden.any()
+    del names[:]
     propagate_visible.propagate_masks_visible(t, m, 2, 3, 2, 8, 16)
-    assert names == ["lp_prop_visible", "lp_prop_occlude"] * 3          # two launches behind each of the three advances
+    assert [n for n in names if n != "lp_prop_luma"] == ["lp_prop_visible", "lp_prop_occlude"] * 3    # two behind each of the three advances
+    assert [n for n in names if n == "lp_prop_luma"] == plain
 
 
 def test_one_frame_per_chunk_gives_the_bits_of_one_chunk(monkeypatch):
-    """The chunks are propagate's (the new module reuses its _chain_frames), so its cap is the one that is lowered; the key frame's
+    """The chunks are propagate's (the new module reuses its chain_frames), so its cap is the one that is lowered; the key frame's
     luma has to outlive the chunk it came in."""
     H, W = 40, 70
     images, mask = _occluded_video(5, H, W)
