@@ -18,7 +18,7 @@ SOURCES = ["step_kernel.hip", "aux_kernels.hip", "blend_kernel.hip", "videomask_
            "propagate_kernel.hip", "temporal_fill_kernel.hip", "temporal_smooth_kernel.hip",
            "shot_kernel.hip", "cabi.hip"]
 HEADERS = [os.path.join(CSRC, "lp_common.h"), os.path.join(CSRC, "mask_tile.h"), os.path.join(CSRC, "resample_tile.h"),
-           os.path.join(CSRC, "exports.map"), os.path.join(ROOT, "include", "lanpaint_hip.h")]
+           os.path.join(CSRC, "motion_tile.h"), os.path.join(CSRC, "exports.map"), os.path.join(ROOT, "include", "lanpaint_hip.h")]
 OUT = os.path.join(HERE, "liblanpaint_hip.so")
 
 

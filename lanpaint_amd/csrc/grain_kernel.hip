@@ -28,18 +28,13 @@ constexpr int kEntries = 4 * kK * 3;                // four channels x bands x {
 static_assert(kTW == 64 && kTH == 16, "a lane owns column tid % 64; of four rows: 4 wave + j (stats), wave + 4 j (grain)");
 static_assert(255 * 8 * 255 * 8 * (kTH * kTW / kCopies) < (1ll << 32), "a copy's sum of squares stays inside 32 bits");
 
-__device__ __forceinline__ uint32_t code_of(float v) {                                   // a NaN gives 0
-    const float t = v > 0.0f ? (v < 1.0f ? v : 1.0f) : 0.0f;
-    return static_cast<uint32_t>(static_cast<int>(__fadd_rn(__fmul_rn(t, 255.0f), 0.5f)));
-}
-
 // codes of channels c0 .. c0 + 3 (those below C) of pixel (y, x) of image b, channel c0 in bits 0..7
 __device__ __forceinline__ uint32_t codes4(const float* __restrict__ image, int b, int y, int x, int H, int W, int C, int c0) {
     const float* p = image + ((static_cast<int64_t>(b) * H + y) * W + x) * C + c0;
-    uint32_t w = code_of(p[0]);
-    if (c0 + 1 < C) w |= code_of(p[1]) << 8;
-    if (c0 + 2 < C) w |= code_of(p[2]) << 16;
-    if (c0 + 3 < C) w |= code_of(p[3]) << 24;
+    uint32_t w = static_cast<uint32_t>(code_of(p[0]));
+    if (c0 + 1 < C) w |= static_cast<uint32_t>(code_of(p[1])) << 8;
+    if (c0 + 2 < C) w |= static_cast<uint32_t>(code_of(p[2])) << 16;
+    if (c0 + 3 < C) w |= static_cast<uint32_t>(code_of(p[3])) << 24;
     return w;
 }
 

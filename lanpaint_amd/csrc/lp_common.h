@@ -766,6 +766,13 @@ void pack_step_args(const StepPlan& p, const lp_step_desc& d, StepArgs* a);
 // does a kernel node launching `func` on grid x block run plan `p`, and nothing else?
 bool plan_is_node(const StepPlan& p, const void* func, const dim3& grid, const dim3& block);
 
+// The 8-bit code of a value in 0..1 (the propagate section's "1 luma"; the grain and refine sections' codes): clamped, times 255,
+// rounded half up; a NaN gives 0.  A site that packs codes into a word casts to its unsigned type.
+__device__ __forceinline__ int code_of(float v) {
+    const float t = v > 0.0f ? (v < 1.0f ? v : 1.0f) : 0.0f;
+    return static_cast<int>(__fadd_rn(__fmul_rn(t, 255.0f), 0.5f));
+}
+
 // stage 3 of lp_mask_stabilize, and lp_prop_merge: sign(q) * sqrt(|q|) capped at LP_STAB_SD_CAP = sign(q) * sqrt(min(|q|, 4096)), the
 // square root being monotonic and 64^2 exact
 __device__ __forceinline__ double capped_distance(int32_t q) {

@@ -35,7 +35,7 @@
 //                merge of the subject codes' distances, rounded to a code and split by the nearer key's flags as occlude does.
 // No scratch, no floating point beyond the luma codes, the final c / 256 (read back by occlude) and the merges.  The only atomics
 // are occlude's integer adds into a count: any order gives the same bits.
-#include "lp_common.h"
+#include "motion_tile.h"
 
 #include <math.h>
 
@@ -54,33 +54,13 @@ constexpr int kFillTile = 16, kFillHalo = LP_PROP_FILL_ITERS + 1, kFillSide = kF
 static_assert(kWin == 16 && kPatchRows <= 32 && kWin + 2 * LP_PROP_MAX_SEARCH <= 4 * kPatchPitch, "the match kernel's LDS layout");
 static_assert(kTile == 1 << (LP_PROP_MAX_LEVELS - 1), "a tile holds one pixel of the coarsest level");
 
-__host__ __device__ inline int level_side(int n, int l) { return (n + (1 << l) - 1) >> l; }
-__host__ __device__ inline int64_t level_offset(int h, int w, int l) {
-    int64_t off = 0;
-    for (int k = 0; k < l; ++k) {
-        const int64_t n = static_cast<int64_t>(level_side(h, k)) * level_side(w, k);
-        off += (n + LP_PROP_ALIGN - 1) / LP_PROP_ALIGN * LP_PROP_ALIGN;
-    }
-    return off;
-}
-
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return min(max(v, lo), hi); }
-
-__device__ __forceinline__ uint32_t code_of(float v) {                                   // a NaN gives 0
-    const float t = v > 0.0f ? (v < 1.0f ? v : 1.0f) : 0.0f;
-    return static_cast<uint32_t>(static_cast<int>(__fadd_rn(__fmul_rn(t, 255.0f), 0.5f)));
-}
-
 // ---- luma and pyramids ---------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void lp_prop_luma_kernel(const float* __restrict__ image, uint8_t* __restrict__ pyr, int64_t plane,
                                                            int channels, int64_t stride) {
     const int64_t p = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
     if (p >= plane) return;
     const int64_t f = blockIdx.y;
-    const float* px = image + (f * plane + p) * channels;
-    uint32_t y = code_of(px[0]);
-    if (channels >= 3) y = (77u * y + 150u * code_of(px[1]) + 29u * code_of(px[2]) + 128u) >> 8;
-    pyr[f * stride + p] = static_cast<uint8_t>(y);
+    pyr[f * stride + p] = static_cast<uint8_t>(luma_of(image + (f * plane + p) * channels, channels));
 }
 
 __global__ __launch_bounds__(256) void lp_prop_down_kernel(uint8_t* __restrict__ pyr, int64_t stride, int64_t src_off, int64_t dst_off,
@@ -251,11 +231,6 @@ __global__ __launch_bounds__(kWave) void lp_prop_match_kernel(const match_args a
 }
 
 // ---- fill and median ---------------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void cmpswap(int& a, int& b) {
-    const int lo = min(a, b), hi = max(a, b);
-    a = lo; b = hi;
-}
-
 __device__ __forceinline__ int median9(int p0, int p1, int p2, int p3, int p4, int p5, int p6, int p7, int p8) {
     cmpswap(p1, p2); cmpswap(p4, p5); cmpswap(p7, p8); cmpswap(p0, p1); cmpswap(p3, p4); cmpswap(p6, p7);
     cmpswap(p1, p2); cmpswap(p4, p5); cmpswap(p7, p8); cmpswap(p0, p3); cmpswap(p5, p8); cmpswap(p4, p7);
@@ -367,10 +342,6 @@ __device__ __forceinline__ bil_tap tap_of(int q, int n) {
     return t;
 }
 
-__device__ __forceinline__ int bil_sum(int a00, int a01, int a10, int a11, int fy, int fx) {
-    return (16 - fy) * ((16 - fx) * a00 + fx * a01) + fy * ((16 - fx) * a10 + fx * a11);
-}
-
 __global__ __launch_bounds__(256) void lp_prop_advance_kernel(const advance_args a) {
     __shared__ uint8_t s0[kTile * kTile], s1[kTile * kTile / 4];
     const advance_job jb = a.job[blockIdx.z];
@@ -380,12 +351,11 @@ __global__ __launch_bounds__(256) void lp_prop_advance_kernel(const advance_args
         uint8_t bit = 0;
         if (y < H && x < W) {
             // the per-pixel vector
-            const int uy = 2 * y - 7, ux = 2 * x - 7, by0 = uy >> 4, bx0 = ux >> 4, fy = uy - 16 * by0, fx = ux - 16 * bx0;
-            const int64_t r0 = static_cast<int64_t>(clampi(by0, 0, a.gh - 1)) * a.gw, r1 = static_cast<int64_t>(clampi(by0 + 1, 0, a.gh - 1)) * a.gw;
-            const int c0 = clampi(bx0, 0, a.gw - 1), c1 = clampi(bx0 + 1, 0, a.gw - 1);
-            const int32_t *v00 = jb.vec + (r0 + c0) * 2, *v01 = jb.vec + (r0 + c1) * 2, *v10 = jb.vec + (r1 + c0) * 2, *v11 = jb.vec + (r1 + c1) * 2;
-            const int Vy = (bil_sum(v00[0], v01[0], v10[0], v11[0], fy, fx) + 128) >> 8;
-            const int Vx = (bil_sum(v00[1], v01[1], v10[1], v11[1], fy, fx) + 128) >> 8;
+            const field_tap by = field_tap_of(y, a.gh), bx = field_tap_of(x, a.gw);
+            const int64_t r0 = static_cast<int64_t>(by.b0) * a.gw, r1 = static_cast<int64_t>(by.b1) * a.gw;
+            const int32_t *v00 = jb.vec + (r0 + bx.b0) * 2, *v01 = jb.vec + (r0 + bx.b1) * 2, *v10 = jb.vec + (r1 + bx.b0) * 2, *v11 = jb.vec + (r1 + bx.b1) * 2;
+            const int Vy = field_vector(v00[0], v01[0], v10[0], v11[0], by.f, bx.f);
+            const int Vx = field_vector(v00[1], v01[1], v10[1], v11[1], by.f, bx.f);
             // the new position
             const bil_tap ty = tap_of(16 * y - Vy, H), tx = tap_of(16 * x - Vx, W);
             int Py, Px;
@@ -515,10 +485,9 @@ __global__ __launch_bounds__(256) void lp_prop_visible_kernel(const visible_args
 
 // w of one pixel: v = 1 - flag between the block centres, the advance's weights, unrounded (0..256)
 __device__ __forceinline__ int weight_of(const int32_t* __restrict__ flags, int gh, int gw, int y, int x) {
-    const int uy = 2 * y - 7, ux = 2 * x - 7, by0 = uy >> 4, bx0 = ux >> 4, fy = uy - 16 * by0, fx = ux - 16 * bx0;
-    const int64_t r0 = static_cast<int64_t>(clampi(by0, 0, gh - 1)) * gw, r1 = static_cast<int64_t>(clampi(by0 + 1, 0, gh - 1)) * gw;
-    const int c0 = clampi(bx0, 0, gw - 1), c1 = clampi(bx0 + 1, 0, gw - 1);
-    return bil_sum(flags[r0 + c0] == 0, flags[r0 + c1] == 0, flags[r1 + c0] == 0, flags[r1 + c1] == 0, fy, fx);
+    const field_tap by = field_tap_of(y, gh), bx = field_tap_of(x, gw);
+    const int64_t r0 = static_cast<int64_t>(by.b0) * gw, r1 = static_cast<int64_t>(by.b1) * gw;
+    return bil_sum(flags[r0 + bx.b0] == 0, flags[r0 + bx.b1] == 0, flags[r1 + bx.b0] == 0, flags[r1 + bx.b1] == 0, by.f, bx.f);
 }
 
 struct occlude_job {
@@ -694,11 +663,7 @@ __global__ __launch_bounds__(256) void lp_prop_merge_visible_kernel(const merge_
     }
 }
 
-bool side_ok(int s) { return s > 0 && s <= LP_VMASK_MAX_SIDE; }
 bool jobs_ok(int n) { return n >= 1 && n <= LP_PROP_MAX_JOBS; }
-bool levels_ok(int l) { return l >= 1 && l <= LP_PROP_MAX_LEVELS; }
-int launched() { return hipGetLastError() == hipSuccess ? LP_OK : LP_E_LAUNCH; }
-uint32_t blocks_of(int64_t n, int per) { return static_cast<uint32_t>((n + per - 1) / per); }
 
 }  // namespace
 

@@ -27,18 +27,13 @@ constexpr int kApplyTH = 64;             // apply: tile height, 8 pixels per thr
 constexpr int kChunk = 16;               // region rows per pass
 constexpr int kCoeffPix = kCoeffTH / 8, kApplyPix = kApplyTH / 8;
 
-__device__ __forceinline__ uint32_t code_of(float v) {                                   // a NaN gives 0
-    const float t = v > 0.0f ? (v < 1.0f ? v : 1.0f) : 0.0f;
-    return static_cast<uint32_t>(static_cast<int>(__fadd_rn(__fmul_rn(t, 255.0f), 0.5f)));
-}
-
 // (G_0, G_1, G_2, P) of pixel (y, x) of image `img` as one dword, G_0 in bits 0..7; a grey guide leaves G_1 = G_2 = 0
 __device__ __forceinline__ uint32_t codes_at(const lp_refine_desc& d, int img, int y, int x) {
     const int64_t pix = static_cast<int64_t>(y) * d.width + x, plane = static_cast<int64_t>(d.height) * d.width;
     const float* g = d.guide + (static_cast<int64_t>(img) * plane + pix) * d.channels;
-    uint32_t w = code_of(g[0]);
-    if (d.channels >= 3) w |= (code_of(g[1]) << 8) | (code_of(g[2]) << 16);
-    return w | (code_of(d.mask[(d.mask_batch == 1 ? 0 : static_cast<int64_t>(img) * plane) + pix]) << 24);
+    uint32_t w = static_cast<uint32_t>(code_of(g[0]));
+    if (d.channels >= 3) w |= (static_cast<uint32_t>(code_of(g[1])) << 8) | (static_cast<uint32_t>(code_of(g[2])) << 16);
+    return w | (static_cast<uint32_t>(code_of(d.mask[(d.mask_batch == 1 ? 0 : static_cast<int64_t>(img) * plane) + pix])) << 24);
 }
 
 // the pixel count of the (2r + 1) window around index i, cut at [0, n)

@@ -16,7 +16,7 @@
 //            neighbours.  The cut bits of 64 consecutive pairs are one ballot word in LDS; the words' counts are scanned (four
 //            words a lane, then the lanes' sums), and shot[f] is a word's prefix plus the count of the bits up to pair f - 1.
 // Integers only: the atomics are integer adds, any order gives the same bits.  No scratch, no floating point.
-#include "lp_common.h"
+#include "motion_tile.h"
 
 namespace lp {
 namespace {
@@ -31,8 +31,6 @@ constexpr int kMaxWords = 1024;                                                 
 static_assert(kBins == kWave && kTile % kB == 0, "a lane per bin, whole blocks per tile");
 static_assert((kTile - kB + 2 * LP_SHOT_MAX_SEARCH) / 4 + 2 < kPatPitch, "a block row's two dwords and the one behind them lie inside a window row");
 static_assert((2 * LP_SHOT_MAX_SEARCH + 1) * (2 * LP_SHOT_MAX_SEARCH + 1) <= kWave, "the displacements fit the lanes of a wave");
-
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return min(max(v, lo), hi); }
 
 struct measure_args {
     const uint8_t* plane;        // frame 0's plane [h, w]; the next frame's lies `stride` bytes on
@@ -180,8 +178,6 @@ __global__ __launch_bounds__(256) void lp_shot_decide_kernel(const decide_args a
     }
 }
 
-bool side_ok(int s) { return s > 0 && s <= LP_VMASK_MAX_SIDE; }
-
 }  // namespace
 
 int shot_measure_dispatch(const lp_shot_measure_desc* dp, hipStream_t stream) {
@@ -205,12 +201,11 @@ int shot_measure_dispatch(const lp_shot_measure_desc* dp, hipStream_t stream) {
     a.w = d.width;
     a.frames = d.frames;
     a.search = d.search;
-    const dim3 grid(static_cast<uint32_t>((d.width + kTile - 1) / kTile), static_cast<uint32_t>((d.height + kTile - 1) / kTile),
-                    static_cast<uint32_t>(d.frames));
+    const dim3 grid(blocks_of(d.width, kTile), blocks_of(d.height, kTile), static_cast<uint32_t>(d.frames));
     hipLaunchKernelGGL(lp_shot_measure_kernel, grid, dim3(256), 0, stream, a);
     if (hipGetLastError() != hipSuccess) return LP_E_LAUNCH;
     if (d.frames > 1) hipLaunchKernelGGL(lp_shot_fold_kernel, dim3(static_cast<uint32_t>(d.frames - 1)), dim3(kWave), 0, stream, d.hist, d.score);
-    return hipGetLastError() == hipSuccess ? LP_OK : LP_E_LAUNCH;
+    return launched();
 }
 
 int shot_decide_dispatch(const lp_shot_decide_desc* dp, hipStream_t stream) {
@@ -233,7 +228,7 @@ int shot_decide_dispatch(const lp_shot_decide_desc* dp, hipStream_t stream) {
     a.ratio = d.ratio;
     a.window = d.window;
     hipLaunchKernelGGL(lp_shot_decide_kernel, dim3(1), dim3(256), 0, stream, a);
-    return hipGetLastError() == hipSuccess ? LP_OK : LP_E_LAUNCH;
+    return launched();
 }
 
 }  // namespace lp

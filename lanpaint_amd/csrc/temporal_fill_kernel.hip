@@ -16,24 +16,13 @@
 //                that disagrees is handed back to `remaining`.  The backward sample is gathered wherever it exists.
 // Integer arithmetic decides everything but the sample, which is fp32 in a fixed order, every operation rounded on its own
 // (__fmul_rn / __fadd_rn: nothing contracts).  No scratch, no atomics.
-#include "lp_common.h"
+#include "motion_tile.h"
 
 namespace lp {
-
-int64_t prop_pyramid_ws_bytes(int frames, int height, int width, int levels);         // propagate_kernel.hip: the pyramid's layout
-
 namespace {
 
 constexpr int kB = LP_PROP_BLOCK;                                                     // 8
-constexpr int kTile = 32;                                                             // carry: pixels per tile side
-constexpr int kTileBlocks = kTile / kB + 2;                                           // 6: the block centres a tile interpolates between
-
-static_assert(kTile % (2 * kB) == 0, "a tile starts on an even block, so its first pixel's lower block is 4 ty - 1");
-
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return min(max(v, lo), hi); }
-
-inline int level_side(int n, int l) { return (n + (1 << l) - 1) >> l; }
-inline int64_t level_offset(int h, int w, int l) { return l == 0 ? 0 : prop_pyramid_ws_bytes(1, h, w, l); }
+constexpr int kTile = kFieldTile;                                                     // carry: pixels per tile side, 32
 
 // ---- known bits and their pyramids --------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void lp_tfill_known_kernel(const float* __restrict__ mask, int64_t mask_step, uint8_t* __restrict__ pyr,
@@ -76,44 +65,18 @@ struct carry_args {
     int32_t H, W, C, gh, gw, frames, t, donor, reach, nearer;
 };
 
-// (16 - f) a + f b, or 16 a without reading b's weight into it: the products and the sum rounded on their own
-__device__ __forceinline__ float lerp16(float a, float b, int f) {
-    if (f == 0) return __fmul_rn(16.0f, a);
-    return __fadd_rn(__fmul_rn(static_cast<float>(16 - f), a), __fmul_rn(static_cast<float>(f), b));
-}
-
-// One lane per pixel: a masked pixel's work is a chain of dependent reads (known byte, block vectors, the donor's byte and state, the
-// taps), so the 1024 pixels of a tile go side by side on 16 waves rather than four after another on 4.
-__global__ __launch_bounds__(kTile * kTile) void lp_tfill_carry_kernel(const carry_args a) {
-    __shared__ int32_t s_v[kTileBlocks * kTileBlocks * 2];
-    const int H = a.H, W = a.W, C = a.C;
-    const int ly = threadIdx.x >> 5, lx = threadIdx.x & 31, y = blockIdx.y * kTile + ly, x = blockIdx.x * kTile + lx;
-    const int64_t p = static_cast<int64_t>(y) * W + x;
-    const bool masked = y < H && x < W && a.known[p] == 0;
-    if (__syncthreads_and(!masked)) return;                              // the whole block: nothing under a mask here
-    // the block vectors around the tile: row j is block clamp(4 ty - 1 + j)
-    if (threadIdx.x < kTileBlocks * kTileBlocks) {
-        const int j = threadIdx.x / kTileBlocks, i = threadIdx.x - j * kTileBlocks;
-        const int by = clampi(static_cast<int>(blockIdx.y) * (kTile / kB) - 1 + j, 0, a.gh - 1);
-        const int bx = clampi(static_cast<int>(blockIdx.x) * (kTile / kB) - 1 + i, 0, a.gw - 1);
-        const int32_t* v = a.vec + (static_cast<int64_t>(by) * a.gw + bx) * 2;
-        s_v[threadIdx.x * 2] = v[0];
-        s_v[threadIdx.x * 2 + 1] = v[1];
-    }
-    __syncthreads();
-    if (!masked) return;                                                 // known, or outside the plane
-    // the per-pixel vector: the propagate section's interpolation; block b0 of the plane is row b0 - (4 ty - 1) of s_v
-    const int uy = 2 * ly + 9, ux = 2 * lx + 9;                          // u = 2 y - 7, counted from block 4 ty - 1: u - 16 (4 ty - 1)
-    const int jy = uy >> 4, jx = ux >> 4, fy = uy & 15, fx = ux & 15;
-    const int32_t *v00 = s_v + (jy * kTileBlocks + jx) * 2, *v01 = v00 + 2, *v10 = v00 + kTileBlocks * 2, *v11 = v10 + 2;
-    const int Vy = ((16 - fy) * ((16 - fx) * v00[0] + fx * v01[0]) + fy * ((16 - fx) * v10[0] + fx * v11[0]) + 128) >> 8;
-    const int Vx = ((16 - fy) * ((16 - fx) * v00[1] + fx * v01[1]) + fy * ((16 - fx) * v10[1] + fx * v11[1]) + 128) >> 8;
+// Stage 3 for the masked pixel p = (y, x), (ly, lx) of its tile: it follows its vector (the propagate section's interpolation, from
+// the tile's vectors in s_v) into the donor and takes over the donor's origin, implicit under the donor's known pixels, the stored
+// state under its mask.  Writes frame t's state; returns the origin's frame, P its position there, or -1.
+__device__ __forceinline__ int carry_origin(const carry_args& a, const int32_t* s_v, int ly, int lx, int y, int x, int64_t p, int& Py, int& Px) {
+    int Vy, Vx;
+    field_tile_vector(s_v, ly, lx, Vy, Vx);
     const int qy = 16 * y + Vy, qx = 16 * x + Vx;
-    const int cur = a.nearer ? a.source[p] : -1;                         // what an earlier pass found; read ahead of its use
-    int f = -1, Py = 0, Px = 0;
-    if (qy >= 0 && qy <= 16 * (H - 1) && qx >= 0 && qx <= 16 * (W - 1)) {
+    int f = -1;
+    Py = Px = 0;
+    if (qy >= 0 && qy <= 16 * (a.H - 1) && qx >= 0 && qx <= 16 * (a.W - 1)) {
         const int iy = (qy + 8) >> 4, ix = (qx + 8) >> 4;                // <= n - 1: inside the plane
-        const int64_t dp = static_cast<int64_t>(iy) * W + ix;
+        const int64_t dp = static_cast<int64_t>(iy) * a.W + ix;
         // the donor's byte and its state are asked for together; the state's values count under the donor's mask only
         const uint8_t dk = a.donor_known[dp];
         const int sf = a.org_src ? a.org_src[dp] : -1;
@@ -131,34 +94,40 @@ __global__ __launch_bounds__(kTile * kTile) void lp_tfill_carry_kernel(const car
     a.org_dst[p] = f;
     a.pos_dst[p * 2] = f >= 0 ? Py : 0;
     a.pos_dst[p * 2 + 1] = f >= 0 ? Px : 0;
+    return f;
+}
+
+// Where frame f is sampled for an origin at P: P clamped to the plane
+__device__ __forceinline__ tap_rows origin_taps(const carry_args& a, int f, int Py, int Px) {
+    return taps_of(a.images, a.H, a.W, a.C, f, clampi(Py, 0, 16 * (a.H - 1)), clampi(Px, 0, 16 * (a.W - 1)));
+}
+
+// One lane per pixel: a masked pixel's work is a chain of dependent reads (known byte, block vectors, the donor's byte and state, the
+// taps), so the 1024 pixels of a tile go side by side on 16 waves rather than four after another on 4.
+__global__ __launch_bounds__(kTile * kTile) void lp_tfill_carry_kernel(const carry_args a) {
+    __shared__ int32_t s_v[kFieldTileBlocks * kFieldTileBlocks * 2];
+    const int H = a.H, W = a.W, C = a.C;
+    const int ly = threadIdx.x >> 5, lx = threadIdx.x & 31, y = blockIdx.y * kTile + ly, x = blockIdx.x * kTile + lx;
+    const int64_t p = static_cast<int64_t>(y) * W + x;
+    const bool masked = y < H && x < W && a.known[p] == 0;
+    if (__syncthreads_and(!masked)) return;                              // the whole block: nothing under a mask here
+    stage_field_tile(s_v, a.vec, a.gh, a.gw);
+    __syncthreads();
+    if (!masked) return;                                                 // known, or outside the plane
+    const int cur = a.nearer ? a.source[p] : -1;                         // what an earlier pass found; read ahead of its use
+    int Py, Px;
+    const int f = carry_origin(a, s_v, ly, lx, y, x, p, Py, Px);
     if (f < 0) return;
     if (cur >= 0 && abs(a.t - f) >= abs(a.t - cur)) return;              // nearer: a tie stays with what is there
-    // the sample of frame f at P clamped to the plane; a tap with weight 0 is not read
-    const int cy = clampi(Py, 0, 16 * (H - 1)), cx = clampi(Px, 0, 16 * (W - 1));
-    const int sy = cy >> 4, sx = cx >> 4, gy = cy & 15, gx = cx & 15;
-    const float* __restrict__ r0 = a.images + ((static_cast<int64_t>(f) * H + sy) * W + sx) * C;
-    const float* __restrict__ r1 = r0 + (gy ? static_cast<int64_t>(W) * C : 0);   // gy != 0 puts sy + 1 inside the plane, as gx does sx + 1
-    const int nx = gx ? C : 0;
+    const tap_rows taps = origin_taps(a, f, Py, Px);
     float* __restrict__ out = a.filled + p * C;
 #pragma unroll 1
-    for (int c0 = 0; c0 < C; c0 += 4) {                                  // four channels' taps are asked for before the first is used
-        float t00[4], t01[4], t10[4], t11[4];
+    for (int c0 = 0; c0 < C; c0 += 4) {
+        float v[4];
+        sample4(taps, C, c0, v);
 #pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const bool in = c0 + k < C;
-            t00[k] = in ? r0[c0 + k] : 0.0f;
-            t01[k] = in && gx ? r0[nx + c0 + k] : 0.0f;
-            t10[k] = in && gy ? r1[c0 + k] : 0.0f;
-            t11[k] = in && gy && gx ? r1[nx + c0 + k] : 0.0f;
-        }
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            if (c0 + k >= C) break;
-            const float top = lerp16(t00[k], t01[k], gx);
-            const float v = gy == 0 ? __fmul_rn(16.0f, top)
-                                    : __fadd_rn(__fmul_rn(static_cast<float>(16 - gy), top), __fmul_rn(static_cast<float>(gy), lerp16(t10[k], t11[k], gx)));
-            out[c0 + k] = __fmul_rn(v, 1.0f / 256.0f);
-        }
+        for (int k = 0; k < 4; ++k)
+            if (c0 + k < C) out[c0 + k] = v[k];
     }
     a.source[p] = f;
     a.remaining[p] = 0.0f;
@@ -171,16 +140,6 @@ struct pair_args {
     int32_t    agree;
 };
 
-__device__ __forceinline__ int code_of(float v) {                       // the propagate section's 8-bit code; a NaN gives 0
-    const float t = v > 0.0f ? (v < 1.0f ? v : 1.0f) : 0.0f;
-    return static_cast<int>(__fadd_rn(__fmul_rn(t, 255.0f), 0.5f));
-}
-
-__device__ __forceinline__ int luma_of(float c0, float c1, float c2, int C) {
-    const int y = code_of(c0);
-    return C >= 3 ? (77 * y + 150 * code_of(c1) + 29 * code_of(c2) + 128) >> 8 : y;
-}
-
 // over the 8 lanes of one row of an 8 x 8 block: lane = 32 (ly & 1) + lx, so the xor stays inside the aligned group of 8
 __device__ __forceinline__ int sum8(int v) {
     v += __shfl_xor(v, 1);
@@ -189,49 +148,10 @@ __device__ __forceinline__ int sum8(int v) {
     return v;
 }
 
-// Where a frame's origin is sampled: the two rows of taps of stage "sample"
-struct tap_rows {
-    const float* r0;
-    const float* r1;
-    int nx, gy, gx;
-};
-
-__device__ __forceinline__ tap_rows taps_of(const carry_args& a, int f, int Py, int Px) {
-    const int cy = clampi(Py, 0, 16 * (a.H - 1)), cx = clampi(Px, 0, 16 * (a.W - 1));
-    const int sy = cy >> 4, sx = cx >> 4;
-    tap_rows t;
-    t.gy = cy & 15;
-    t.gx = cx & 15;
-    t.r0 = a.images + ((static_cast<int64_t>(f) * a.H + sy) * a.W + sx) * a.C;
-    t.r1 = t.r0 + (t.gy ? static_cast<int64_t>(a.W) * a.C : 0);
-    t.nx = t.gx ? a.C : 0;
-    return t;
-}
-
-// channels c0 .. c0 + 3 of the sample (0 beyond C): the four channels' taps are asked for before the first is used
-__device__ __forceinline__ void sample4(const tap_rows& t, int C, int c0, float (&v)[4]) {
-    float t00[4], t01[4], t10[4], t11[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const bool in = c0 + k < C;
-        t00[k] = in ? t.r0[c0 + k] : 0.0f;
-        t01[k] = in && t.gx ? t.r0[t.nx + c0 + k] : 0.0f;
-        t10[k] = in && t.gy ? t.r1[c0 + k] : 0.0f;
-        t11[k] = in && t.gy && t.gx ? t.r1[t.nx + c0 + k] : 0.0f;
-    }
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const float top = lerp16(t00[k], t01[k], t.gx);
-        const float s = t.gy == 0 ? __fmul_rn(16.0f, top)
-                                  : __fadd_rn(__fmul_rn(static_cast<float>(16 - t.gy), top), __fmul_rn(static_cast<float>(t.gy), lerp16(t10[k], t11[k], t.gx)));
-        v[k] = __fmul_rn(s, 1.0f / 256.0f);
-    }
-}
-
 // The carry's geometry.  A tile is 4 x 4 aligned blocks of 8 x 8, block b = 4 (ly >> 3) + (lx >> 3); its two sums go through s_nd
 // (n in the low byte, D above it: n <= 64, so the arithmetic shift gives D back) and s_r.  No lane leaves between the barriers.
 __global__ __launch_bounds__(kTile * kTile) void lp_tfill_carry_pair_kernel(const pair_args g) {
-    __shared__ int32_t s_v[kTileBlocks * kTileBlocks * 2];
+    __shared__ int32_t s_v[kFieldTileBlocks * kFieldTileBlocks * 2];
     __shared__ int32_t s_nd[(kTile / kB) * (kTile / kB)], s_r[(kTile / kB) * (kTile / kB)];
     const carry_args& a = g.c;
     const int H = a.H, W = a.W, C = a.C;
@@ -244,14 +164,7 @@ __global__ __launch_bounds__(kTile * kTile) void lp_tfill_carry_pair_kernel(cons
         if (inside) g.witnesses[p] = 0;
         return;
     }
-    if (threadIdx.x < kTileBlocks * kTileBlocks) {
-        const int j = threadIdx.x / kTileBlocks, i = threadIdx.x - j * kTileBlocks;
-        const int by = clampi(static_cast<int>(blockIdx.y) * (kTile / kB) - 1 + j, 0, a.gh - 1);
-        const int bx = clampi(static_cast<int>(blockIdx.x) * (kTile / kB) - 1 + i, 0, a.gw - 1);
-        const int32_t* v = a.vec + (static_cast<int64_t>(by) * a.gw + bx) * 2;
-        s_v[threadIdx.x * 2] = v[0];
-        s_v[threadIdx.x * 2 + 1] = v[1];
-    }
+    stage_field_tile(s_v, a.vec, a.gh, a.gw);
     __syncthreads();
     // witness B: stage 3 as lp_tfill_carry_kernel has it.  A's frame and the first channels of its sample are asked for up front.
     int f = -1, Py = 0, Px = 0, cur = -1;
@@ -260,40 +173,16 @@ __global__ __launch_bounds__(kTile * kTile) void lp_tfill_carry_pair_kernel(cons
         cur = a.source[p];
 #pragma unroll
         for (int k = 0; k < 3; ++k) fa[k] = k < C ? a.filled[p * C + k] : 0.0f;
-        const int uy = 2 * ly + 9, ux = 2 * lx + 9;
-        const int jy = uy >> 4, jx = ux >> 4, fy = uy & 15, fx = ux & 15;
-        const int32_t *v00 = s_v + (jy * kTileBlocks + jx) * 2, *v01 = v00 + 2, *v10 = v00 + kTileBlocks * 2, *v11 = v10 + 2;
-        const int Vy = ((16 - fy) * ((16 - fx) * v00[0] + fx * v01[0]) + fy * ((16 - fx) * v10[0] + fx * v11[0]) + 128) >> 8;
-        const int Vx = ((16 - fy) * ((16 - fx) * v00[1] + fx * v01[1]) + fy * ((16 - fx) * v10[1] + fx * v11[1]) + 128) >> 8;
-        const int qy = 16 * y + Vy, qx = 16 * x + Vx;
-        if (qy >= 0 && qy <= 16 * (H - 1) && qx >= 0 && qx <= 16 * (W - 1)) {
-            const int iy = (qy + 8) >> 4, ix = (qx + 8) >> 4;
-            const int64_t dp = static_cast<int64_t>(iy) * W + ix;
-            const uint8_t dk = a.donor_known[dp];
-            const int sf = a.org_src ? a.org_src[dp] : -1;
-            const int spy = a.org_src ? a.pos_src[dp * 2] : 0, spx = a.org_src ? a.pos_src[dp * 2 + 1] : 0;
-            f = dk ? a.donor : sf;
-            Py = dk ? 16 * iy : spy;
-            Px = dk ? 16 * ix : spx;
-            if (f >= 0 && f < a.frames && abs(a.t - f) <= a.reach) {
-                Py += qy - 16 * iy;
-                Px += qx - 16 * ix;
-            } else {
-                f = -1;
-            }
-        }
-        a.org_dst[p] = f;
-        a.pos_dst[p * 2] = f >= 0 ? Py : 0;
-        a.pos_dst[p * 2 + 1] = f >= 0 ? Px : 0;
+        f = carry_origin(a, s_v, ly, lx, y, x, p, Py, Px);
     }
     const bool has_b = f >= 0, both = has_b && cur >= 0;
     tap_rows taps = {};
     float sb[4] = {0.0f, 0.0f, 0.0f, 0.0f};
     if (has_b) {
-        taps = taps_of(a, f, Py, Px);
+        taps = origin_taps(a, f, Py, Px);
         sample4(taps, C, 0, sb);
     }
-    const int d = both ? luma_of(sb[0], sb[1], sb[2], C) - luma_of(fa[0], fa[1], fa[2], C) : 0;
+    const int d = both ? luma_of(sb, C) - luma_of(fa, C) : 0;
     const int b = (ly >> 3) * (kTile / kB) + (lx >> 3);
     const int nd_row = sum8(both ? d * 256 + 1 : 0);
     if ((lx & 7) == 0 && nd_row != 0) atomicAdd(&s_nd[b], nd_row);
@@ -347,10 +236,49 @@ __global__ __launch_bounds__(kTile * kTile) void lp_tfill_carry_pair_kernel(cons
     g.witnesses[p] = wit;
 }
 
-bool side_ok(int s) { return s > 0 && s <= LP_VMASK_MAX_SIDE; }
-bool levels_ok(int l) { return l >= 1 && l <= LP_PROP_MAX_LEVELS; }
-int launched() { return hipGetLastError() == hipSuccess ? LP_OK : LP_E_LAUNCH; }
-uint32_t blocks_of(int64_t n, int per) { return static_cast<uint32_t>((n + per - 1) / per); }
+// The checks both carry entries share, and the kernel's arguments; `extra` is the checked form's sixth output (null: the plain form)
+int carry_args_of(const lp_tfill_carry_desc& d, const void* extra, carry_args& a) {
+    if (d.frames < 2 || !side_ok(d.height) || !side_ok(d.width) || d.channels < 1 || d.channels > LP_DETAIL_MAX_CHANNELS) return LP_E_INVALID;
+    if (d.reach < 0 || d.reach > LP_TFILL_MAX_REACH || (d.nearer != 0 && d.nearer != 1)) return LP_E_INVALID;
+    if (d.frames > 65535) return LP_E_UNSUPPORTED;
+    if (d.frame < 0 || d.frame >= d.frames || d.donor < 0 || d.donor >= d.frames || (d.donor != d.frame - 1 && d.donor != d.frame + 1))
+        return LP_E_INVALID;
+    if (!d.vec || !d.known || !d.donor_known || !d.org_dst || !d.pos_dst || !d.images || !d.filled || !d.source || !d.remaining)
+        return LP_E_INVALID;
+    if ((d.org_src == nullptr) != (d.pos_src == nullptr)) return LP_E_INVALID;
+    const void *outs[6] = {d.org_dst, d.pos_dst, d.filled, d.source, d.remaining, extra};
+    const void *in[6] = {d.vec, d.known, d.donor_known, d.org_src, d.pos_src, d.images};
+    for (int k = 0; k < 6; ++k) {
+        if (!outs[k]) continue;                                          // `extra` of the plain form
+        for (const void* p : in)
+            if (outs[k] == p) return LP_E_INVALID;
+        for (int m = k + 1; m < 6; ++m)
+            if (outs[k] == outs[m]) return LP_E_INVALID;
+    }
+    const int64_t plane = static_cast<int64_t>(d.height) * d.width;
+    a.vec = d.vec;
+    a.known = d.known;
+    a.donor_known = d.donor_known;
+    a.org_src = d.org_src;
+    a.pos_src = d.pos_src;
+    a.org_dst = d.org_dst;
+    a.pos_dst = d.pos_dst;
+    a.images = d.images;
+    a.filled = d.filled + d.frame * plane * d.channels;
+    a.source = d.source + d.frame * plane;
+    a.remaining = d.remaining + d.frame * plane;
+    a.H = d.height;
+    a.W = d.width;
+    a.C = d.channels;
+    a.gh = (d.height + kB - 1) / kB;
+    a.gw = (d.width + kB - 1) / kB;
+    a.frames = d.frames;
+    a.t = d.frame;
+    a.donor = d.donor;
+    a.reach = d.reach ? d.reach : LP_TFILL_MAX_REACH;                    // 0: the whole clip; frames <= 65535, so no age exceeds it
+    a.nearer = d.nearer;
+    return LP_OK;
+}
 
 }  // namespace
 
@@ -383,95 +311,25 @@ int tfill_known_dispatch(const lp_tfill_known_desc* dp, hipStream_t stream) {
 
 int tfill_carry_dispatch(const lp_tfill_carry_desc* dp, hipStream_t stream) {
     if (!dp) return LP_E_INVALID;
-    const lp_tfill_carry_desc& d = *dp;
-    if (d.frames < 2 || !side_ok(d.height) || !side_ok(d.width) || d.channels < 1 || d.channels > LP_DETAIL_MAX_CHANNELS) return LP_E_INVALID;
-    if (d.reach < 0 || d.reach > LP_TFILL_MAX_REACH || (d.nearer != 0 && d.nearer != 1)) return LP_E_INVALID;
-    if (d.frames > 65535) return LP_E_UNSUPPORTED;
-    if (d.frame < 0 || d.frame >= d.frames || d.donor < 0 || d.donor >= d.frames || (d.donor != d.frame - 1 && d.donor != d.frame + 1))
-        return LP_E_INVALID;
-    if (!d.vec || !d.known || !d.donor_known || !d.org_dst || !d.pos_dst || !d.images || !d.filled || !d.source || !d.remaining)
-        return LP_E_INVALID;
-    if ((d.org_src == nullptr) != (d.pos_src == nullptr)) return LP_E_INVALID;
-    const void *outs[5] = {d.org_dst, d.pos_dst, d.filled, d.source, d.remaining};
-    const void *in[6] = {d.vec, d.known, d.donor_known, d.org_src, d.pos_src, d.images};
-    for (int k = 0; k < 5; ++k) {
-        for (const void* p : in)
-            if (outs[k] == p) return LP_E_INVALID;
-        for (int m = k + 1; m < 5; ++m)
-            if (outs[k] == outs[m]) return LP_E_INVALID;
-    }
-    const int64_t plane = static_cast<int64_t>(d.height) * d.width;
     carry_args a = {};
-    a.vec = d.vec;
-    a.known = d.known;
-    a.donor_known = d.donor_known;
-    a.org_src = d.org_src;
-    a.pos_src = d.pos_src;
-    a.org_dst = d.org_dst;
-    a.pos_dst = d.pos_dst;
-    a.images = d.images;
-    a.filled = d.filled + d.frame * plane * d.channels;
-    a.source = d.source + d.frame * plane;
-    a.remaining = d.remaining + d.frame * plane;
-    a.H = d.height;
-    a.W = d.width;
-    a.C = d.channels;
-    a.gh = (d.height + kB - 1) / kB;
-    a.gw = (d.width + kB - 1) / kB;
-    a.frames = d.frames;
-    a.t = d.frame;
-    a.donor = d.donor;
-    a.reach = d.reach ? d.reach : LP_TFILL_MAX_REACH;                    // 0: the whole clip; frames <= 65535, so no age exceeds it
-    a.nearer = d.nearer;
-    hipLaunchKernelGGL(lp_tfill_carry_kernel, dim3(blocks_of(d.width, kTile), blocks_of(d.height, kTile)), dim3(kTile * kTile), 0, stream, a);
+    const int status = carry_args_of(*dp, nullptr, a);
+    if (status != LP_OK) return status;
+    hipLaunchKernelGGL(lp_tfill_carry_kernel, dim3(blocks_of(dp->width, kTile), blocks_of(dp->height, kTile)), dim3(kTile * kTile), 0, stream, a);
     return launched();
 }
 
 int tfill_carry_pair_dispatch(const lp_tfill_carry_pair_desc* dp, hipStream_t stream) {
     if (!dp) return LP_E_INVALID;
-    const lp_tfill_carry_pair_desc& d = *dp;
-    if (d.frames < 2 || !side_ok(d.height) || !side_ok(d.width) || d.channels < 1 || d.channels > LP_DETAIL_MAX_CHANNELS) return LP_E_INVALID;
-    if (d.reach < 0 || d.reach > LP_TFILL_MAX_REACH || d.agree < 1 || d.agree > 255) return LP_E_INVALID;
-    if (d.frames > 65535) return LP_E_UNSUPPORTED;
-    if (d.frame < 0 || d.donor >= d.frames || d.donor != d.frame + 1) return LP_E_INVALID;
-    if (!d.vec || !d.known || !d.donor_known || !d.org_dst || !d.pos_dst || !d.images || !d.filled || !d.source || !d.remaining ||
-        !d.witnesses)
-        return LP_E_INVALID;
-    if ((d.org_src == nullptr) != (d.pos_src == nullptr)) return LP_E_INVALID;
-    const void *outs[6] = {d.org_dst, d.pos_dst, d.filled, d.source, d.remaining, d.witnesses};
-    const void *in[6] = {d.vec, d.known, d.donor_known, d.org_src, d.pos_src, d.images};
-    for (int k = 0; k < 6; ++k) {
-        for (const void* p : in)
-            if (outs[k] == p) return LP_E_INVALID;
-        for (int m = k + 1; m < 6; ++m)
-            if (outs[k] == outs[m]) return LP_E_INVALID;
-    }
-    const int64_t plane = static_cast<int64_t>(d.height) * d.width;
+    if (dp->agree < 1 || dp->agree > 255) return LP_E_INVALID;
+    const lp_tfill_carry_desc d = {dp->frames, dp->height, dp->width, dp->channels, dp->frame, dp->donor, dp->reach, 1,
+                                   dp->vec, dp->known, dp->donor_known, dp->org_src, dp->pos_src, dp->org_dst, dp->pos_dst,
+                                   dp->images, dp->filled, dp->source, dp->remaining};
     pair_args g = {};
-    carry_args& a = g.c;
-    a.vec = d.vec;
-    a.known = d.known;
-    a.donor_known = d.donor_known;
-    a.org_src = d.org_src;
-    a.pos_src = d.pos_src;
-    a.org_dst = d.org_dst;
-    a.pos_dst = d.pos_dst;
-    a.images = d.images;
-    a.filled = d.filled + d.frame * plane * d.channels;
-    a.source = d.source + d.frame * plane;
-    a.remaining = d.remaining + d.frame * plane;
-    a.H = d.height;
-    a.W = d.width;
-    a.C = d.channels;
-    a.gh = (d.height + kB - 1) / kB;
-    a.gw = (d.width + kB - 1) / kB;
-    a.frames = d.frames;
-    a.t = d.frame;
-    a.donor = d.donor;
-    a.reach = d.reach ? d.reach : LP_TFILL_MAX_REACH;
-    a.nearer = 1;
-    g.witnesses = d.witnesses + d.frame * plane;
-    g.agree = d.agree;
+    const int status = carry_args_of(d, dp->witnesses, g.c);
+    if (status != LP_OK) return status;
+    if (!dp->witnesses || d.donor != d.frame + 1) return LP_E_INVALID;   // the step is the backward one
+    g.witnesses = dp->witnesses + d.frame * (static_cast<int64_t>(d.height) * d.width);
+    g.agree = dp->agree;
     hipLaunchKernelGGL(lp_tfill_carry_pair_kernel, dim3(blocks_of(d.width, kTile), blocks_of(d.height, kTile)), dim3(kTile * kTile), 0, stream, g);
     return launched();
 }

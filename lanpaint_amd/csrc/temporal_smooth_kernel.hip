@@ -26,16 +26,14 @@
 //            and for the acceptance against r and the sums, the first four channels while the walk decides, every further four
 //            in a walk of their own.  What exists is two counts, what is accepted a bit mask in one register.  No array is
 //            indexed by a register: nothing in scratch, no LDS.
-#include "lp_common.h"
+#include "motion_tile.h"
 
 namespace lp {
 namespace {
 
 constexpr int kB = LP_PROP_BLOCK;                                                     // 8
-constexpr int kTile = 32;
+constexpr int kTile = kFieldTile;                                                    // 32
 constexpr int kWave = 64;                                                            // two rows of a tile
-
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return min(max(v, lo), hi); }
 
 struct smooth_args {
     const int32_t* fwd;          // row j: the field of frame fwd0 + j towards the next frame, [gh, gw, 2]
@@ -47,55 +45,6 @@ struct smooth_args {
     int32_t*       support;      // [frames, H, W]
     int32_t H, W, C, gh, gw, frames, first, fwd0, bwd0, radius, tolerance, w0;
 };
-
-// (16 - f) a + f b, or 16 a without reading b's weight into it: the products and the sum rounded on their own
-__device__ __forceinline__ float lerp16(float a, float b, int f) {
-    if (f == 0) return __fmul_rn(16.0f, a);
-    return __fadd_rn(__fmul_rn(static_cast<float>(16 - f), a), __fmul_rn(static_cast<float>(f), b));
-}
-
-__device__ __forceinline__ int code_of(float v) {                       // the propagate section's 8-bit code; a NaN gives 0
-    const float t = v > 0.0f ? (v < 1.0f ? v : 1.0f) : 0.0f;
-    return static_cast<int>(__fadd_rn(__fmul_rn(t, 255.0f), 0.5f));
-}
-
-// Where a frame is sampled: the two rows of taps of the temporal fill's "sample"
-struct tap_rows {
-    const float* r0;
-    const float* r1;
-    int nx, gy, gx;
-};
-
-// q lies inside the plane: gy != 0 puts row qy / 16 + 1 inside it, as gx does the next column
-__device__ __forceinline__ tap_rows taps_of(const smooth_args& a, int f, int qy, int qx) {
-    tap_rows t;
-    t.gy = qy & 15;
-    t.gx = qx & 15;
-    t.r0 = a.images + ((static_cast<int64_t>(f) * a.H + (qy >> 4)) * a.W + (qx >> 4)) * a.C;
-    t.r1 = t.r0 + (t.gy ? static_cast<int64_t>(a.W) * a.C : 0);
-    t.nx = t.gx ? a.C : 0;
-    return t;
-}
-
-// channels c0 .. c0 + 3 of the sample (0 beyond C): the four channels' taps are asked for before the first is used
-__device__ __forceinline__ void sample4(const tap_rows& t, int C, int c0, float (&v)[4]) {
-    float t00[4], t01[4], t10[4], t11[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const bool in = c0 + k < C;
-        t00[k] = in ? t.r0[c0 + k] : 0.0f;
-        t01[k] = in && t.gx ? t.r0[t.nx + c0 + k] : 0.0f;
-        t10[k] = in && t.gy ? t.r1[c0 + k] : 0.0f;
-        t11[k] = in && t.gy && t.gx ? t.r1[t.nx + c0 + k] : 0.0f;
-    }
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const float top = lerp16(t00[k], t01[k], t.gx);
-        const float s = t.gy == 0 ? __fmul_rn(16.0f, top)
-                                  : __fadd_rn(__fmul_rn(static_cast<float>(16 - t.gy), top), __fmul_rn(static_cast<float>(t.gy), lerp16(t10[k], t11[k], t.gx)));
-        v[k] = __fmul_rn(s, 1.0f / 256.0f);
-    }
-}
 
 __device__ __forceinline__ void own4(const float* __restrict__ x, int C, int c0, float (&v)[4]) {
 #pragma unroll
@@ -113,17 +62,13 @@ __device__ __forceinline__ int apart4(const float (&s)[4], const float (&x)[4]) 
 // One step from p (inside the plane) along `vec`: the propagate section's per-pixel interpolation at the integer pixel nearest p.
 // False: q leaves the plane.
 __device__ __forceinline__ bool step(const smooth_args& a, const int32_t* __restrict__ vec, int py, int px, int& qy, int& qx) {
-    const int uy = 2 * ((py + 8) >> 4) - 7, ux = 2 * ((px + 8) >> 4) - 7;
-    const int by = uy >> 4, bx = ux >> 4, fy = uy & 15, fx = ux & 15;   // >> floors: u = -7 .. -1 gives block -1, clamped to 0
-    const int y0 = clampi(by, 0, a.gh - 1), y1 = clampi(by + 1, 0, a.gh - 1), x0 = clampi(bx, 0, a.gw - 1), x1 = clampi(bx + 1, 0, a.gw - 1);
-    const int2 v00 = *reinterpret_cast<const int2*>(vec + (static_cast<int64_t>(y0) * a.gw + x0) * 2);
-    const int2 v01 = *reinterpret_cast<const int2*>(vec + (static_cast<int64_t>(y0) * a.gw + x1) * 2);
-    const int2 v10 = *reinterpret_cast<const int2*>(vec + (static_cast<int64_t>(y1) * a.gw + x0) * 2);
-    const int2 v11 = *reinterpret_cast<const int2*>(vec + (static_cast<int64_t>(y1) * a.gw + x1) * 2);
-    const int Vy = ((16 - fy) * ((16 - fx) * v00.x + fx * v01.x) + fy * ((16 - fx) * v10.x + fx * v11.x) + 128) >> 8;
-    const int Vx = ((16 - fy) * ((16 - fx) * v00.y + fx * v01.y) + fy * ((16 - fx) * v10.y + fx * v11.y) + 128) >> 8;
-    qy = py + Vy;
-    qx = px + Vx;
+    const field_tap by = field_tap_of((py + 8) >> 4, a.gh), bx = field_tap_of((px + 8) >> 4, a.gw);
+    const int2 v00 = *reinterpret_cast<const int2*>(vec + (static_cast<int64_t>(by.b0) * a.gw + bx.b0) * 2);
+    const int2 v01 = *reinterpret_cast<const int2*>(vec + (static_cast<int64_t>(by.b0) * a.gw + bx.b1) * 2);
+    const int2 v10 = *reinterpret_cast<const int2*>(vec + (static_cast<int64_t>(by.b1) * a.gw + bx.b0) * 2);
+    const int2 v11 = *reinterpret_cast<const int2*>(vec + (static_cast<int64_t>(by.b1) * a.gw + bx.b1) * 2);
+    qy = py + field_vector(v00.x, v01.x, v10.x, v11.x, by.f, bx.f);
+    qx = px + field_vector(v00.y, v01.y, v10.y, v11.y, by.f, bx.f);
     return qy >= 0 && qy <= 16 * (a.H - 1) && qx >= 0 && qx <= 16 * (a.W - 1);
 }
 
@@ -144,7 +89,7 @@ __device__ __forceinline__ int chain(const smooth_args& a, int t, int d, int lim
         int qy, qx;
         const bool inside = step(a, vec, py, px, qy, qx);
         if (Decide && !inside) break;
-        const tap_rows taps = taps_of(a, v, qy, qx);
+        const tap_rows taps = taps_of(a.images, a.H, a.W, a.C, v, qy, qx);
         float s[4];
         sample4(taps, a.C, c0, s);
         if (Decide) {
@@ -185,21 +130,27 @@ __device__ __forceinline__ void copy_rows(const T* __restrict__ src, T* __restri
     }
 }
 
-// One lane per pixel, as the temporal fill's carry has it: a masked pixel's work is a chain of dependent reads.
-__global__ __launch_bounds__(kTile * kTile) void lp_tsmooth_kernel(const smooth_args a) {
+// The geometry of both kernels and their copy of what is not masked: the lane's pixel (y, x) of frame t, element `at` of a plane
+// stack.  A wave -- two rows of the tile -- in which none is masked copies its two runs and leaves; else a known pixel is copied by
+// its lane.  Both write support = -1, and `replaced` = -1 where the robust form passes its plane (the plain form: null).
+// True: the pixel is masked and the lane goes on; false: the lane is done.
+__device__ __forceinline__ bool masked_pixel(const smooth_args& a, int32_t* __restrict__ replaced, int& y, int& x, int& t, int64_t& at) {
     const int H = a.H, W = a.W, C = a.C;
-    const int ly = threadIdx.x >> 5, lx = threadIdx.x & 31, y = blockIdx.y * kTile + ly, x = blockIdx.x * kTile + lx;
-    const int t = a.first + static_cast<int>(blockIdx.z);
+    const int ly = threadIdx.x >> 5, lx = threadIdx.x & 31;
+    y = blockIdx.y * kTile + ly;
+    x = blockIdx.x * kTile + lx;
+    t = a.first + static_cast<int>(blockIdx.z);
     const int64_t p = static_cast<int64_t>(y) * W + x;
     const bool inside = y < H && x < W;
     const bool masked = inside && a.known[static_cast<int64_t>(blockIdx.z) * a.known_stride + p] == 0;
-    const int64_t at = static_cast<int64_t>(t) * H * W + p;
-    const float* __restrict__ own = a.images + at * C;
-    float* __restrict__ out = a.out + at * C;
+    at = static_cast<int64_t>(t) * H * W + p;
     if (__all(!masked)) {                                                // the whole wave, two rows of the tile: nothing under a mask here
-        if (inside) a.support[at] = -1;
+        if (inside) {
+            a.support[at] = -1;
+            if (replaced) replaced[at] = -1;
+        }
         const int y0 = static_cast<int>(blockIdx.y) * kTile + (ly & ~1);
-        if (y0 >= H) return;
+        if (y0 >= H) return false;
         const int tw = min(kTile, W - static_cast<int>(blockIdx.x) * kTile), rows = min(2, H - y0), lane = threadIdx.x & (kWave - 1);
         const int64_t pitch = static_cast<int64_t>(W) * C;               // floats from a row to the next
         const int64_t corner = ((static_cast<int64_t>(t) * H + y0) * W + static_cast<int64_t>(blockIdx.x) * kTile) * C;
@@ -208,15 +159,29 @@ __global__ __launch_bounds__(kTile * kTile) void lp_tsmooth_kernel(const smooth_
             copy_rows(reinterpret_cast<const float4*>(a.images + corner), reinterpret_cast<float4*>(a.out + corner), rows, tw * C / 4, pitch / 4, lane);
         else
             copy_rows(a.images + corner, a.out + corner, rows, tw * C, pitch, lane);
-        return;
+        return false;
     }
-    if (!inside) return;
+    if (!inside) return false;
     if (!masked) {
+        const float* __restrict__ own = a.images + at * C;
+        float* __restrict__ out = a.out + at * C;
 #pragma unroll 1
         for (int c = 0; c < C; ++c) out[c] = own[c];
         a.support[at] = -1;
-        return;
+        if (replaced) replaced[at] = -1;
+        return false;
     }
+    return true;
+}
+
+// One lane per pixel, as the temporal fill's carry has it: a masked pixel's work is a chain of dependent reads.
+__global__ __launch_bounds__(kTile * kTile) void lp_tsmooth_kernel(const smooth_args a) {
+    const int C = a.C;
+    int y, x, t;
+    int64_t at;
+    if (!masked_pixel(a, nullptr, y, x, t, at)) return;
+    const float* __restrict__ own = a.images + at * C;
+    float* __restrict__ out = a.out + at * C;
     float x4[4], acc[4] = {0.0f, 0.0f, 0.0f, 0.0f};
     own4(own, C, 0, x4);
     int Wsum = a.w0;
@@ -257,11 +222,6 @@ __device__ __forceinline__ bool advance(const smooth_args& a, int t, int d, int 
     return true;
 }
 
-__device__ __forceinline__ int luma_of(const float (&s)[4], int C) {                 // the propagate section's 8-bit luma of the codes
-    const int c0 = code_of(s[0]);
-    return C >= 3 ? (77 * c0 + 150 * code_of(s[1]) + 29 * code_of(s[2]) + 128) >> 8 : c0;
-}
-
 // The lumas of the order indices, a byte each: 0..7 in `lo`, 8..15 in `hi`, 16 in `top`.  Three named registers and no array, so
 // that an index in a register selects and shifts and nothing goes to scratch.
 struct lumas17 {
@@ -288,7 +248,7 @@ __device__ __forceinline__ int lumas(const smooth_args& a, int t, int d, int o0,
     for (int k = 1; k <= a.radius; ++k) {
         if (!advance(a, t, d, k, py, px)) break;
         float s[4];
-        sample4(taps_of(a, t + k * d, py, px), a.C, 0, s);
+        sample4(taps_of(a.images, a.H, a.W, a.C, t + k * d, py, px), a.C, 0, s);
         put_luma(pk, o0 + k, luma_of(s, a.C));
         ++n;
     }
@@ -334,7 +294,7 @@ __device__ __forceinline__ void ref4(const smooth_args& a, const ref_at& r, cons
     if (r.v < 0)
         own4(own, a.C, c0, v);
     else
-        sample4(taps_of(a, r.v, r.qy, r.qx), a.C, c0, v);
+        sample4(taps_of(a.images, a.H, a.W, a.C, r.v, r.qy, r.qx), a.C, c0, v);
 }
 
 // The chain of direction d again, all `steps` of it that exist, for the channels c0 .. c0 + 3: the sums of the accepted samples
@@ -349,7 +309,7 @@ __device__ __forceinline__ void robust_chain(const smooth_args& a, int t, int d,
 #pragma unroll 1
     for (int k = 1; k <= steps; ++k) {
         advance(a, t, d, k, py, px);                                     // exists: the first walk came this far
-        const tap_rows taps = taps_of(a, t + k * d, py, px);
+        const tap_rows taps = taps_of(a.images, a.H, a.W, a.C, t + k * d, py, px);
         float s[4];
         sample4(taps, a.C, c0, s);
         w = w * (a.radius - k + 1) / (a.radius + k);
@@ -388,39 +348,12 @@ struct robust_args {
 // The plain kernel's geometry and its copy of what is not masked; a masked pixel ranks its lumas and walks again.
 __global__ __launch_bounds__(kTile * kTile) void lp_tsmooth_robust_kernel(const robust_args ra) {
     const smooth_args& a = ra.s;
-    const int H = a.H, W = a.W, C = a.C, R = a.radius;
-    const int ly = threadIdx.x >> 5, lx = threadIdx.x & 31, y = blockIdx.y * kTile + ly, x = blockIdx.x * kTile + lx;
-    const int t = a.first + static_cast<int>(blockIdx.z);
-    const int64_t p = static_cast<int64_t>(y) * W + x;
-    const bool inside = y < H && x < W;
-    const bool masked = inside && a.known[static_cast<int64_t>(blockIdx.z) * a.known_stride + p] == 0;
-    const int64_t at = static_cast<int64_t>(t) * H * W + p;
+    const int C = a.C, R = a.radius;
+    int y, x, t;
+    int64_t at;
+    if (!masked_pixel(a, ra.replaced, y, x, t, at)) return;
     const float* __restrict__ own = a.images + at * C;
     float* __restrict__ out = a.out + at * C;
-    if (__all(!masked)) {
-        if (inside) {
-            a.support[at] = -1;
-            ra.replaced[at] = -1;
-        }
-        const int y0 = static_cast<int>(blockIdx.y) * kTile + (ly & ~1);
-        if (y0 >= H) return;
-        const int tw = min(kTile, W - static_cast<int>(blockIdx.x) * kTile), rows = min(2, H - y0), lane = threadIdx.x & (kWave - 1);
-        const int64_t pitch = static_cast<int64_t>(W) * C;
-        const int64_t corner = ((static_cast<int64_t>(t) * H + y0) * W + static_cast<int64_t>(blockIdx.x) * kTile) * C;
-        if (((pitch | (tw * C)) & 3) == 0 && ((reinterpret_cast<uintptr_t>(a.images) | reinterpret_cast<uintptr_t>(a.out)) & 15) == 0)
-            copy_rows(reinterpret_cast<const float4*>(a.images + corner), reinterpret_cast<float4*>(a.out + corner), rows, tw * C / 4, pitch / 4, lane);
-        else
-            copy_rows(a.images + corner, a.out + corner, rows, tw * C, pitch, lane);
-        return;
-    }
-    if (!inside) return;
-    if (!masked) {
-#pragma unroll 1
-        for (int c = 0; c < C; ++c) out[c] = own[c];
-        a.support[at] = -1;
-        ra.replaced[at] = -1;
-        return;
-    }
     // the first walk: the lumas
     float x4[4];
     own4(own, C, 0, x4);
@@ -485,8 +418,6 @@ __global__ __launch_bounds__(kTile * kTile) void lp_tsmooth_robust_kernel(const 
     }
 }
 
-bool side_ok(int s) { return s > 0 && s <= LP_VMASK_MAX_SIDE; }
-
 // The checks both entries share, and the kernel's arguments; `extra` is the robust form's third output (null: the plain form)
 int smooth_args_of(const lp_tsmooth_desc& d, const void* extra, smooth_args& a) {
     if (d.frames < 1 || !side_ok(d.height) || !side_ok(d.width) || d.channels < 1 || d.channels > LP_DETAIL_MAX_CHANNELS) return LP_E_INVALID;
@@ -539,10 +470,9 @@ int tsmooth_dispatch(const lp_tsmooth_desc* dp, hipStream_t stream) {
     smooth_args a = {};
     const int status = smooth_args_of(*dp, nullptr, a);
     if (status != LP_OK) return status;
-    const dim3 grid(static_cast<uint32_t>((dp->width + kTile - 1) / kTile), static_cast<uint32_t>((dp->height + kTile - 1) / kTile),
-                    static_cast<uint32_t>(dp->count));
+    const dim3 grid(blocks_of(dp->width, kTile), blocks_of(dp->height, kTile), static_cast<uint32_t>(dp->count));
     hipLaunchKernelGGL(lp_tsmooth_kernel, grid, dim3(kTile * kTile), 0, stream, a);
-    return hipGetLastError() == hipSuccess ? LP_OK : LP_E_LAUNCH;
+    return launched();
 }
 
 int tsmooth_robust_dispatch(const lp_tsmooth_robust_desc* dp, hipStream_t stream) {
@@ -555,10 +485,9 @@ int tsmooth_robust_dispatch(const lp_tsmooth_robust_desc* dp, hipStream_t stream
     const int status = smooth_args_of(d, dp->replaced, ra.s);
     if (status != LP_OK) return status;
     ra.replaced = dp->replaced;
-    const dim3 grid(static_cast<uint32_t>((d.width + kTile - 1) / kTile), static_cast<uint32_t>((d.height + kTile - 1) / kTile),
-                    static_cast<uint32_t>(d.count));
+    const dim3 grid(blocks_of(d.width, kTile), blocks_of(d.height, kTile), static_cast<uint32_t>(d.count));
     hipLaunchKernelGGL(lp_tsmooth_robust_kernel, grid, dim3(kTile * kTile), 0, stream, ra);
-    return hipGetLastError() == hipSuccess ? LP_OK : LP_E_LAUNCH;
+    return launched();
 }
 
 }  // namespace lp

@@ -282,3 +282,20 @@ def test_no_kernel_uses_scratch_memory_and_streaming_kernels_fit_eight_waves(hip
         if a and a[0] == 4 and a[2] != 0 and a not in allowed and (k[".vgpr_count"] > 64 or k[".sgpr_count"] > 100):
             short.append((a, k[".vgpr_count"], k[".sgpr_count"]))
     assert not short, short
+
+
+def test_every_included_file_is_a_build_dependency():
+    """Every file a csrc/*.hip or csrc/*.h names in a quoted #include is a source or a header `build.needs_build` looks at: an
+    edit to a shared header that is not in `build.HEADERS` would leave a stale library in place."""
+    from lanpaint_amd import build
+    known = {os.path.basename(p) for p in build.HEADERS} | set(build.SOURCES)
+    files = sorted(f for f in os.listdir(build.CSRC) if f.endswith((".hip", ".h")))
+    assert "motion_tile.h" in files and set(build.SOURCES) <= set(files)
+    included = {}
+    for f in files:
+        for name in re.findall(r'^\s*#\s*include\s+"([^"]+)"', open(os.path.join(build.CSRC, f)).read(), flags=re.M):
+            included.setdefault(os.path.basename(name), f)
+    assert {"lp_common.h", "motion_tile.h", "mask_tile.h", "resample_tile.h", "lanpaint_hip.h"} <= set(included)
+    missing = {name: f for name, f in included.items() if name not in known}
+    assert not missing, missing
+    assert all(os.path.exists(p) for p in build.HEADERS)

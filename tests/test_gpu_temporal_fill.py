@@ -146,6 +146,20 @@ def test_carry_equals_the_restatement(plane):
     _check_carry(H, W, True, 3, True, 2, True)
 
 
+# One block high with several across, and the other way round: the grid is one block wide, so both blocks a pixel interpolates
+# between are the same clamped one.  The plane list's own thin planes (1 x 1, 1 x 7, 7 x 1) are thinner than the case's vectors are
+# long: there every masked pixel's vector leaves the plane and its value is never seen (counted on the restatement alone).
+THIN_PLANES = [(7, 33), (33, 5)]
+
+
+@pytest.mark.parametrize("plane", THIN_PLANES, ids=plane_ids)
+def test_carry_on_a_grid_one_block_wide(plane):
+    for donor in (1, 3):
+        for state in (True, False):
+            want_org, write = _check_carry(*plane, False, donor, state, 0, False)
+            assert write.sum() >= 16                                   # vectors that stay inside the plane: origins found and sampled
+
+
 def test_carry_case_covers_the_borders_the_reach_and_both_forms():
     H, W = 40, 70
     images, vec, known, org, pos, source_t = _carry_case(H, W, False)

@@ -12,7 +12,7 @@ import torch
 from lanpaint_amd import _cabi, temporal_fill as tf, temporal_fill_checked as tc, temporal_fill_checked_nodes
 from tests import temporal_fill_checked_ref as cref
 from tests.test_gpu_propagate import _dev, _same, _video, _wild_mask, _wild_video
-from tests.test_gpu_temporal_fill import ALL_PLANES, LEVELS, F, _random_masks, _same_values, plane_ids
+from tests.test_gpu_temporal_fill import ALL_PLANES, LEVELS, THIN_PLANES, F, _random_masks, _same_values, plane_ids
 from tests.test_temporal_fill_checked_host import (CLEAN_CLIPS, SECOND_OBJECT, check_clean, check_invariant, clean_clip, pair_case,
                                                    pair_want, random_clip, second_object_clip, second_object_counts)
 
@@ -54,6 +54,15 @@ def test_carry_pair_equals_the_restatement(plane):
         _check_pair(H, W, False, C, True, 0, 8)
     _check_pair(H, W, True, 3, True, 0, 8)                             # NaN and infinities in the video
     _check_pair(H, W, True, 3, True, 1, 1)
+
+
+@pytest.mark.parametrize("plane", THIN_PLANES, ids=plane_ids)
+def test_carry_pair_on_a_grid_one_block_wide(plane):
+    case = pair_case(*plane, False, 3)
+    (want_org, _), _ = pair_want(case, True, 0, 8)
+    assert ((case[2][0] == 0) & (want_org >= 0)).sum() >= 16           # masked pixels whose vector stays inside the plane
+    for state in (True, False):
+        _check_pair(*plane, False, 3, state, 0, 8)
 
 
 def test_carry_pair_with_more_channels_than_one_gather_holds():

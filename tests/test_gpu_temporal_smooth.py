@@ -14,7 +14,7 @@ from tests import propagate_ref as ref
 from tests import temporal_fill_ref as tref
 from tests import temporal_smooth_ref as sref
 from tests.test_gpu_propagate import _dev, _rng, _same, _video, _wild_video
-from tests.test_gpu_temporal_fill import ALL_PLANES, _random_masks, _same_values, plane_ids
+from tests.test_gpu_temporal_fill import ALL_PLANES, THIN_PLANES, _random_masks, _same_values, plane_ids
 from tests.test_temporal_smooth_host import (RADII, check_ghost, check_noise, check_pan, ghost_clip, noise_clip, pan_clip)
 
 pytestmark = pytest.mark.gpu
@@ -56,6 +56,16 @@ def test_the_launch_equals_the_restatement_on_every_plane(plane, channels):
     if plane == (40, 70):
         support = sref.smooth_frames(images, known, fwd, bwd, 2, 24)[1]
         assert {0, 1, 2, 3, 4} <= set(np.unique(support).tolist())     # chains of every length, and rejected ones
+
+
+@pytest.mark.parametrize("plane", THIN_PLANES, ids=plane_ids)
+def test_the_launch_on_a_grid_one_block_wide(plane):
+    images, mask, known, fwd, bwd = _scene(*plane)
+    assert np.count_nonzero(fwd) >= 16 and np.count_nonzero(bwd) >= 16          # fields that move
+    for radius, tolerance in ((1, 255), (2, 24), (8, 255)):
+        want = sref.smooth_frames(images, known, fwd, bwd, radius, tolerance)
+        assert tolerance < 255 or (want[1] > 0).sum() >= 16            # masked pixels whose walks stay inside the plane
+        _check(_launch(images, known, fwd, bwd, radius, tolerance), want, (plane, radius, tolerance))
 
 
 @pytest.mark.parametrize("channels", [6, 9])

@@ -17,7 +17,7 @@ from tests import temporal_fill_ref as tref
 from tests import temporal_smooth_ref as sref
 from tests import temporal_smooth_robust_ref as rref
 from tests.test_gpu_propagate import _dev, _rng, _same, _video, _wild_video
-from tests.test_gpu_temporal_fill import ALL_PLANES, _random_masks, _same_values, plane_ids
+from tests.test_gpu_temporal_fill import ALL_PLANES, THIN_PLANES, _random_masks, _same_values, plane_ids
 from tests.test_temporal_smooth_host import RADII, ghost_clip, noise_clip, pan_clip
 from tests.test_temporal_smooth_robust_host import (check_ghost_removed, check_noise, check_pan_equals_plain, check_pop, check_two_frame_pop,
                                                     pop_clip)
@@ -94,6 +94,17 @@ def test_the_launch_equals_the_restatement_on_every_plane(plane, channels):
             wants.add((plane, channels, radius, tolerance), images, known, fwd, bwd, radius, tolerance)
     if plane[0] * plane[1] >= 23 * 33:
         wants.every_branch()
+    wants.compare()
+
+
+@pytest.mark.parametrize("plane", THIN_PLANES, ids=plane_ids)
+def test_the_launch_on_a_grid_one_block_wide(plane):
+    images, mask, known, fwd, bwd = _scene(*plane)
+    assert np.count_nonzero(fwd) >= 16 and np.count_nonzero(bwd) >= 16          # fields that move
+    wants = _Wants()
+    for radius, tolerance in ((1, 255), (2, 24), (8, 255)):
+        want = wants.add((plane, radius, tolerance), images, known, fwd, bwd, radius, tolerance)
+        assert tolerance < 255 or (want[1] > 0).sum() >= 16            # masked pixels whose walks stay inside the plane
     wants.compare()
 
 
