@@ -1795,6 +1795,55 @@ typedef struct lp_prop_merge_visible_desc {
 } lp_prop_merge_visible_desc;
 LP_API int lp_prop_merge_visible(const lp_prop_merge_visible_desc* desc, void* stream);
 
+/* ---- Video mask propagate, anchored (beyond the reference) ---------------------------------------------------------------------------
+ * The single-key chain composes one-frame fields.  Every step's sub-pixel estimate is pulled towards zero by `smooth` and by the
+ * parabola fit, and nothing ever looks at the key frame again, so on a long clip with sub-pixel motion the mask falls behind its
+ * subject.  The position map P_t names, for every pixel of frame t, where it was in the key frame; the key frame's luma sampled
+ * through it is the picture the chain believes frame t to be.  Matched against the real frame t with the block-match rule, the block
+ * field is the error the chain has built up, and one more advance along it takes the error out.  The match is against the key every
+ * time, so the error no longer accumulates.  A step of this form is the single-key step with three launches behind it (the existing
+ * entries keep their meaning and their bits):
+ *   lp_prop_match / lp_prop_fill per level -> lp_prop_advance (its out and mask_pyramid go to scratch) -> lp_prop_anchor_match ->
+ *   lp_prop_fill -> lp_prop_advance.
+ * All of it is integer arithmetic.  For frame t after the first lp_prop_advance: c(y, x) in 0..256 the advance's mask code,
+ * m = c >= 128 (level 0 of the pyramid the advance wrote), P_t the positions, Yt and Yk level 0 of the luma pyramids of t and of the
+ * key frame; everything else as in the single-key section.
+ * 1 warped key luma  K(y, x) = (bil(Yk, P_t(y, x)) + 128) >> 8, in 0..255: exactly lp_prop_visible's K.
+ * 2 correction field (lp_prop_anchor_match) e [gh, gw, 2] is step 3's `match` at level 0 of the single-key section with Ys := K,
+ *              Yt := Yt, the mask := m, the predictor p = 0, search := anchor in 1..LP_PROP_MAX_SEARCH, the chain's smooth, and the
+ *              level-0 sub-pixel refinement: the same window (the block grown by LP_PROP_HALO, cut at the border), validity
+ *              (LP_PROP_MIN_PIXELS), key order and clamping of target coordinates.  An invalid block holds 0.
+ * 3 fill       the existing lp_prop_fill (fill + median) on e.
+ * 4 advance    the existing lp_prop_advance with vec = e, pos_src = P_t and the key bits: its pos_dst, out and mask_pyramid are the
+ *              step's results, the positions, the mask and the bits that weight the next step's match.
+ * 5 no memory between frames except P_t itself; the key frame's own output is its binarised mask (lp_prop_key_mask).
+ * What follows from the rule, bit for bit: a video of equal frames gives e = 0 on every frame and the plain chain's bits, and so
+ * does a noise-free whole-pixel shift that the plain chain tracks exactly (K = Yt under the mask, S = 0 at the zero vector, which
+ * every other candidate can only tie at a larger distance); an empty mask gives 0 and a full mask 1.0; one frame returns the
+ * binarised mask.  anchor = 0 is the caller's "off": it makes none of the three launches and returns the plain chain.
+ * Not handled: anchoring inside the occlusion-aware and the several-keys forms (an occluded block would be matched against the
+ * occluder); a subject whose look changes away from the key (turning, relighting beyond what `smooth` refuses) gets e ~ 0 there and
+ * drifts as before; re-anchoring every n-th frame only.
+ * Launch (csrc/propagate_kernel.hip): lp_prop_anchor_match fuses the warp and the match, K never goes to memory.  A block of 256
+ * lanes per 32 x 32 pixels, that is 4 x 4 level-0 blocks: K of the tile and its halo of 4 (40 x 40 bytes, ANDed with the per-byte
+ * mask beside it) goes to LDS once, gathered through P_t, which is read as 16-byte vectors when width % 4 == 0 and the planes are
+ * 16-byte aligned; the clamped target patch, (40 + 2 anchor)^2 <= 54^2 bytes, next to it.  Each wave takes four windows; the
+ * (2 anchor + 1)^2 <= 225 candidates are spread over its lanes in up to four passes, v_alignbyte_b32 cuts the four target pixels
+ * out of two patch dwords, v_sad_u8 adds the four absolute differences, the minimum of the key is taken wave-wide and the
+ * sub-pixel term from the winner's neighbours as lp_prop_match does it.  A tile without a mask pixel leaves after staging.  One job.
+ * LP_E_INVALID: a null pointer, a side outside its range, anchor outside 1..LP_PROP_MAX_SEARCH, smooth outside
+ * 0..LP_PROP_MAX_SMOOTH, vec or valid aliasing an input or one another.  All checked before any HIP call.                          */
+typedef struct lp_prop_anchor_desc {
+    int32_t height, width, anchor, smooth;        /* anchor 1..LP_PROP_MAX_SEARCH, smooth 0..LP_PROP_MAX_SMOOTH             */
+    const int32_t* pos;                           /* P_t [height, width, 2], as lp_prop_advance wrote it                    */
+    const uint8_t* tgt;                           /* Yt: level 0 of frame t's luma pyramid [height, width]                  */
+    const uint8_t* key;                           /* Yk: level 0 of the key frame's luma pyramid                            */
+    const uint8_t* mask;                          /* m: level 0 of the pyramid lp_prop_advance wrote                        */
+    int32_t*       vec;                           /* out, [gh, gw, 2], the raw correction field                             */
+    int32_t*       valid;                         /* out, [gh, gw], 0 / 1: the inputs of lp_prop_fill                       */
+} lp_prop_anchor_desc;
+LP_API int lp_prop_anchor_match(const lp_prop_anchor_desc* desc, void* stream);
+
 /* ---- Video temporal fill (beyond the reference) -------------------------------------------------------------------------------------
  * What lies under the mask of a video frame is, in most clips, plain background a few frames earlier or later: a subject moves
  * across it, or the camera pans past.  These entries borrow it from there, in front of the spatial fill (lp_mask_fill) and the

@@ -440,6 +440,12 @@ class LpPropOccludeDesc(C.Structure):
                 ("mask_pyramid", C.c_void_p)]
 
 
+class LpPropAnchorDesc(C.Structure):
+    _fields_ = [("height", C.c_int32), ("width", C.c_int32), ("anchor", C.c_int32), ("smooth", C.c_int32),
+                ("pos", C.c_void_p), ("tgt", C.c_void_p), ("key", C.c_void_p), ("mask", C.c_void_p), ("vec", C.c_void_p),
+                ("valid", C.c_void_p)]
+
+
 class LpPropVisibleJob(C.Structure):
     _fields_ = [("pos", C.c_void_p), ("tgt", C.c_void_p), ("key", C.c_void_p), ("mask", C.c_void_p), ("flags", C.c_void_p)]
 
@@ -652,6 +658,7 @@ EXPORTS = {
     "lp_prop_visible_batch": (C.c_int, [C.POINTER(LpPropVisibleBatchDesc), C.c_void_p]),
     "lp_prop_occlude_batch": (C.c_int, [C.POINTER(LpPropOccludeBatchDesc), C.c_void_p]),
     "lp_prop_merge_visible": (C.c_int, [C.POINTER(LpPropMergeVisibleDesc), C.c_void_p]),
+    "lp_prop_anchor_match": (C.c_int, [C.POINTER(LpPropAnchorDesc), C.c_void_p]),
     "lp_tfill_known": (C.c_int, [C.POINTER(LpTfillKnownDesc), C.c_void_p]),
     "lp_tfill_carry": (C.c_int, [C.POINTER(LpTfillCarryDesc), C.c_void_p]),
     "lp_tfill_carry_pair": (C.c_int, [C.POINTER(LpTfillCarryPairDesc), C.c_void_p]),

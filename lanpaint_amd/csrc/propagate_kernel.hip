@@ -27,6 +27,11 @@
 //                visible and the hidden part of the advance's code, and the visible bits' pyramid from the same tile code.  With a
 //                count pointer, the number of visible bits goes into it: a sum per wave, one integer atomic add per wave.
 //                visible and occlude are batches like match, fill and advance; a job's vector path is a bit of a mask.
+//   anchor match the anchored form's hot path: the warp of the key luma and its match against the frame in one launch.  A block per
+//                32 x 32 tile: K of the tile and its halo of 4 goes to LDS once, four pixels a dword, ANDed with its per-byte mask
+//                as match has it, P_t read as two 16-byte vectors; the (40 + 2R)^2 clamped target patch goes to rows of 56 bytes.  A
+//                wave takes four of the tile's 4 x 4 windows in turn, the candidates over its lanes in up to four passes, match's
+//                v_alignbyte_b32 / v_sad_u8 inner loop, key and sub-pixel step.  A tile with no mask pixel leaves after staging K.
 //   merge        one lane per pixel and frame of a gap between two keys: the two chains' signed squared distances, their capped
 //                fp64 roots, the weighted mean in a fixed order, the ramp of half-width 1/2 around the zero crossing.
 //   merge_visible the merge of a gap whose chains are occlusion-aware: a streaming kernel over [frames, H, W], four pixels per lane
@@ -391,12 +396,16 @@ constexpr int16_t kVisNone = INT16_MIN;                                 // a pix
 
 static_assert(kVisSide % 8 == 0 && kTile / kB == 4 && kWin == 16, "the visible kernel's window rows: 16 int16, 16-byte aligned");
 
-// d = Yt - K for one mask pixel inside the image: K = (bil(Yk, P_t) + 128) >> 8
-__device__ __forceinline__ int16_t residual_of(const uint8_t* __restrict__ key, int H, int W, int Py, int Px, int yt) {
+// The warped key luma of one pixel: K = (bil(Yk, P_t) + 128) >> 8, in 0..255
+__device__ __forceinline__ int warped_key_of(const uint8_t* __restrict__ key, int H, int W, int Py, int Px) {
     const bil_tap ky = tap_of(Py, H), kx = tap_of(Px, W);
     const uint8_t *k0 = key + static_cast<int64_t>(ky.i0) * W, *k1 = key + static_cast<int64_t>(ky.i1) * W;
-    const int K = (bil_sum(k0[kx.i0], k0[kx.i1], k1[kx.i0], k1[kx.i1], ky.f, kx.f) + 128) >> 8;
-    return static_cast<int16_t>(yt - K);
+    return (bil_sum(k0[kx.i0], k0[kx.i1], k1[kx.i0], k1[kx.i1], ky.f, kx.f) + 128) >> 8;
+}
+
+// d = Yt - K for one mask pixel inside the image
+__device__ __forceinline__ int16_t residual_of(const uint8_t* __restrict__ key, int H, int W, int Py, int Px, int yt) {
+    return static_cast<int16_t>(yt - warped_key_of(key, H, W, Py, Px));
 }
 
 struct visible_job {
@@ -561,6 +570,147 @@ __global__ __launch_bounds__(256) void lp_prop_occlude_kernel(const occlude_args
     }
     __syncthreads();
     tile_mask_pyramid(s0, s1, blockIdx.y, blockIdx.x, H, W, levels, mpyr);
+}
+
+// ---- anchor match: the anchored form ---------------------------------------------------------------------------------------------------
+constexpr int kAncPitch = kVisQuads;                                    // dwords per row of K and of its mask: 40 bytes
+constexpr int kAncPatRows = kVisSide + 2 * LP_PROP_MAX_SEARCH;          // 54
+constexpr int kAncPatPitch = 14;                                        // dwords per patch row: 56 bytes >= 54
+
+static_assert(4 * kAncPatPitch >= kAncPatRows, "a patch row holds the tile, its halo and the search range");
+static_assert((kTile - kB + 2 * LP_PROP_MAX_SEARCH) / 4 + 4 < kAncPatPitch, "a window row's four dwords and the one behind them lie inside a patch row");
+static_assert(kWin * 4 == kWave, "a lane per dword of a window's mask");
+
+struct anchor_args {
+    const int32_t* pos;
+    const uint8_t* tgt;
+    const uint8_t* key;
+    const uint8_t* msk;
+    int32_t*       vec;
+    int32_t*       valid;
+    int32_t H, W, gh, gw, search, smooth, wide;
+};
+
+__global__ __launch_bounds__(256) void lp_prop_anchor_match_kernel(const anchor_args a) {
+    __shared__ uint32_t s_src[kVisSide * kAncPitch], s_bm[kVisSide * kAncPitch], s_pat[kAncPatRows * kAncPatPitch];
+    __shared__ int32_t s_S[4][kMaxCand];
+    const int32_t* __restrict__ pos = a.pos;
+    const uint8_t* __restrict__ tgt = a.tgt;
+    const uint8_t* __restrict__ key = a.key;
+    const uint8_t* __restrict__ msk = a.msk;
+    const int tid = threadIdx.x, lane = tid & (kWave - 1), wv = tid >> 6;
+    const int H = a.H, W = a.W, R = a.search, n = 2 * R + 1, ncand = n * n;
+    const int y00 = blockIdx.y * kTile - kHalo, x00 = blockIdx.x * kTile - kHalo;     // x00 is a multiple of 4
+    // K of the tile and its halo, four pixels a dword, 0 where the pixel is outside the image or the mask, and the per-byte mask.
+    // wide: width % 4 == 0 and the planes 16-byte aligned, so a quad is inside its row or outside it, and one vector
+    uint32_t any = 0;
+    for (int i = tid; i < kVisSide * kAncPitch; i += 256) {
+        const int r = i / kAncPitch, q = i - r * kAncPitch;
+        const int y = y00 + r, x = x00 + 4 * q;
+        uint32_t sv = 0, bm = 0;
+        if (y >= 0 && y < H && x + 3 >= 0 && x < W) {
+            const int64_t p = static_cast<int64_t>(y) * W + x;
+            if (a.wide) {                                                // x >= 0 and x + 3 < W; p is a multiple of 4
+                const uchar4 m4 = *reinterpret_cast<const uchar4*>(msk + p);
+                if (m4.x | m4.y | m4.z | m4.w) {
+                    const int4 pa = *reinterpret_cast<const int4*>(pos + p * 2), pb = *reinterpret_cast<const int4*>(pos + p * 2 + 4);
+                    if (m4.x) { bm |= 0xFFu;       sv |= static_cast<uint32_t>(warped_key_of(key, H, W, pa.x, pa.y)); }
+                    if (m4.y) { bm |= 0xFFu << 8;  sv |= static_cast<uint32_t>(warped_key_of(key, H, W, pa.z, pa.w)) << 8; }
+                    if (m4.z) { bm |= 0xFFu << 16; sv |= static_cast<uint32_t>(warped_key_of(key, H, W, pb.x, pb.y)) << 16; }
+                    if (m4.w) { bm |= 0xFFu << 24; sv |= static_cast<uint32_t>(warped_key_of(key, H, W, pb.z, pb.w)) << 24; }
+                }
+            } else {
+#pragma unroll
+                for (int k = 0; k < 4; ++k)
+                    if (x + k >= 0 && x + k < W && msk[p + k]) {
+                        bm |= 0xFFu << (8 * k);
+                        sv |= static_cast<uint32_t>(warped_key_of(key, H, W, pos[(p + k) * 2], pos[(p + k) * 2 + 1])) << (8 * k);
+                    }
+            }
+        }
+        s_src[i] = sv;
+        s_bm[i] = bm;
+        any |= bm;
+    }
+    const int by0 = blockIdx.y * (kTile / kB), bx0 = blockIdx.x * (kTile / kB);
+    if (!__syncthreads_or(any != 0)) {                                   // no mask pixel in reach of the tile: the whole block leaves
+        const int by = by0 + (tid >> 2), bx = bx0 + (tid & 3);
+        if (tid < 16 && by < a.gh && bx < a.gw) {
+            const int64_t cell = static_cast<int64_t>(by) * a.gw + bx;
+            a.vec[cell * 2] = 0;
+            a.vec[cell * 2 + 1] = 0;
+            a.valid[cell] = 0;
+        }
+        return;
+    }
+    // the target patch: row j, byte i is Yt(clamp(y00 - R + j), clamp(x00 - R + i))
+    const int rows = kVisSide + 2 * R;
+    for (int i = tid; i < rows * kAncPatPitch; i += 256) {
+        const int j = i / kAncPatPitch, c0 = (i - j * kAncPatPitch) * 4;
+        const uint8_t* row = tgt + static_cast<int64_t>(clampi(y00 - R + j, 0, H - 1)) * W;
+        uint32_t v = 0;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) v |= static_cast<uint32_t>(row[clampi(x00 - R + c0 + k, 0, W - 1)]) << (8 * k);
+        s_pat[i] = v;
+    }
+    __syncthreads();
+    // a wave takes four of the tile's 4 x 4 windows, one a round; every wave reaches every barrier
+#pragma unroll 1
+    for (int round = 0; round < 4; ++round) {
+        const int win = round * 4 + wv, wy = win >> 2, wx = win & 3;
+        const int by = by0 + wy, bx = bx0 + wx;
+        const int q0 = wy * kB * kAncPitch + wx * (kB / 4);              // the window's first dword of s_src / s_bm
+        int count = __popc(s_bm[q0 + (lane >> 2) * kAncPitch + (lane & 3)]) >> 3;
+#pragma unroll
+        for (int d = 1; d < kWave; d <<= 1) count += __shfl_xor(count, d, kWave);
+        const bool live = by < a.gh && bx < a.gw && count >= LP_PROP_MIN_PIXELS;      // the same in every lane of the wave
+        uint32_t best = 0xFFFFFFFFu;
+        if (live) {
+            for (int c = lane; c < ncand; c += kWave) {
+                const int cy = c / n, cx = c - cy * n;                  // oy + R, ox + R
+                const int o = wx * kB + cx, word = o >> 2, shift = o & 3;       // word + 4 <= 13: inside the patch row
+                uint32_t S = 0;
+                for (int r = 0; r < kWin; ++r) {
+                    const uint32_t* pr = s_pat + (wy * kB + r + cy) * kAncPatPitch + word;
+                    const int q = q0 + r * kAncPitch;
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) {
+                        const uint32_t t = __builtin_amdgcn_alignbyte(pr[k + 1], pr[k], shift) & s_bm[q + k];
+                        S = __builtin_amdgcn_sad_u8(s_src[q + k], t, S);
+                    }
+                }
+                s_S[wv][c] = static_cast<int32_t>(S);
+                const uint32_t dist = static_cast<uint32_t>(abs(cy - R) + abs(cx - R));
+                best = min(best, ((S + static_cast<uint32_t>(a.smooth) * dist) << 12) | (dist << 8) | static_cast<uint32_t>(c));
+            }
+#pragma unroll
+            for (int d = 1; d < kWave; d <<= 1) best = min(best, static_cast<uint32_t>(__shfl_xor(static_cast<int>(best), d, kWave)));
+        }
+        __syncthreads();                                                 // the wave's s_S is complete
+        if (lane == 0 && by < a.gh && bx < a.gw) {
+            int vy = 0, vx = 0;
+            if (live) {
+                const int c = static_cast<int>(best & 255u), cy = c / n, cx = c - cy * n;
+                vy = 16 * (cy - R);
+                vx = 16 * (cx - R);
+                const int s0 = s_S[wv][c];
+                if (s0 != 0) {
+                    if (cy > 0 && cy < 2 * R) {
+                        const int cm = s_S[wv][c - n], cp = s_S[wv][c + n], d = cm + cp - 2 * s0, g = cm - cp;
+                        if (d > 0) vy += (g > 0 ? 1 : (g < 0 ? -1 : 0)) * min(abs(8 * g) / d, 8);
+                    }
+                    if (cx > 0 && cx < 2 * R) {
+                        const int cm = s_S[wv][c - 1], cp = s_S[wv][c + 1], d = cm + cp - 2 * s0, g = cm - cp;
+                        if (d > 0) vx += (g > 0 ? 1 : (g < 0 ? -1 : 0)) * min(abs(8 * g) / d, 8);
+                    }
+                }
+            }
+            const int64_t cell = static_cast<int64_t>(by) * a.gw + bx;
+            a.vec[cell * 2] = vy;
+            a.vec[cell * 2 + 1] = vx;
+            a.valid[cell] = live ? 1 : 0;
+        }
+    }
 }
 
 // ---- merge ---------------------------------------------------------------------------------------------------------------------------------
@@ -841,6 +991,29 @@ int prop_occlude_dispatch(const lp_prop_occlude_desc* dp, hipStream_t stream) {
     const lp_prop_occlude_job job = {dp->code, dp->flags, dp->out, dp->hidden, dp->mask_pyramid, nullptr};
     const lp_prop_occlude_batch_desc d = {dp->height, dp->width, dp->levels, 1, &job};
     return prop_occlude_batch_dispatch(&d, stream);
+}
+
+int prop_anchor_match_dispatch(const lp_prop_anchor_desc* dp, hipStream_t stream) {
+    if (!dp) return LP_E_INVALID;
+    const lp_prop_anchor_desc& d = *dp;
+    if (!side_ok(d.height) || !side_ok(d.width)) return LP_E_INVALID;
+    if (d.anchor < 1 || d.anchor > LP_PROP_MAX_SEARCH || d.smooth < 0 || d.smooth > LP_PROP_MAX_SMOOTH) return LP_E_INVALID;
+    if (!d.pos || !d.tgt || !d.key || !d.mask || !d.vec || !d.valid) return LP_E_INVALID;
+    const void *vec = d.vec, *valid = d.valid;
+    for (const void* in : {static_cast<const void*>(d.pos), static_cast<const void*>(d.tgt), static_cast<const void*>(d.key),
+                           static_cast<const void*>(d.mask)})
+        if (vec == in || valid == in) return LP_E_INVALID;
+    if (vec == valid) return LP_E_INVALID;
+    anchor_args a = {d.pos, d.tgt, d.key, d.mask, d.vec, d.valid};
+    a.H = d.height;
+    a.W = d.width;
+    a.gh = (d.height + kB - 1) / kB;
+    a.gw = (d.width + kB - 1) / kB;
+    a.search = d.anchor;
+    a.smooth = d.smooth;
+    a.wide = d.width % 4 == 0 && aligned16(d.pos) && aligned16(d.mask);    // the kernel reads a row's four pixels as one vector
+    hipLaunchKernelGGL(lp_prop_anchor_match_kernel, dim3(blocks_of(d.width, kTile), blocks_of(d.height, kTile)), dim3(256), 0, stream, a);
+    return launched();
 }
 
 int prop_merge_dispatch(const lp_prop_merge_desc* dp, hipStream_t stream) {

@@ -16,7 +16,8 @@ propagate_masks(images, mask, key_frame=0, levels=4, search=2, smooth=8) -> mask
         integer arithmetic: the same bits on every run; one frame returns the binarised mask, an empty mask stays exactly 0, a full
         mask exactly 1, a still video returns the binarised key mask on every frame, a noise-free whole-pixel shift is tracked
         exactly.  include/lanpaint_hip.h (lp_prop_*) states the rule in full.  Not handled: occlusion -- what leaves the
-        picture or is covered does not come back.  Several keyframes, which pull drift back: propagate_keys.py.
+        picture or is covered does not come back.  Several keyframes, which pull drift back: propagate_keys.py.  One key matched
+        against every frame again, which keeps sub-pixel drift from adding up: propagate_anchored.py.
 
 HIP tensors only, no CPU fallback, no device -> host read.  The luma pyramids are built in chunks of frames that stay under
 WS_CAP_BYTES; a frame's pyramid depends on that frame only, so chunking cannot change a bit.  A step is 2 levels + 1 launches

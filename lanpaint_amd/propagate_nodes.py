@@ -7,8 +7,8 @@ the key mask is sampled through the accumulated motion.  It is the first link of
 
     one painted mask + the video -> VideoMaskPropagate -> VideoMaskStabilize -> MaskRefine -> ImageEncode / DetailerCrop*
 
-One keyframe only; nothing handles occlusion or re-anchors against drift.  Host tensors in and out like the other nodes.  The
-reference has no such node.
+One keyframe only; nothing handles occlusion or re-anchors against drift (propagate_anchored_nodes.py does the latter).  Host
+tensors in and out like the other nodes.  The reference has no such node.
 
 This module has its own NODE_CLASS_MAPPINGS: merge them with the others' (INTEGRATION.md section 2(b)).
 """

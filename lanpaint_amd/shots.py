@@ -29,6 +29,8 @@ temporal_fill_shots, temporal_fill_checked_shots, temporal_smooth_shots, stabili
         The five links run per shot; each takes the ranges, or the `shot` tensor, behind the clip.
 temporal_smooth_robust_shots
         `temporal_smooth_robust`, the robust form of the smooth, per shot in the same way.
+propagate_masks_anchored_shots
+        `propagate_masks_anchored`, the anchored form of the propagate, inside the key frame's shot as `propagate_masks_shots`.
 
 include/lanpaint_hip.h (lp_shot_*) states the rule in full: integers throughout, the same bits on every run.  Not done:
 dissolves, fades and wipes are not detected; the several-key propagates and the colour match's pooling over neighbouring
@@ -194,18 +196,29 @@ def stabilize_masks_shots(mask, shots, median=1, smooth=2, grow=0.0, feather=0.0
     return per_shot(stabilize_masks, clip_ranges(shots, mask.shape[0]), (mask,), median, smooth, grow, feather)
 
 
-def propagate_masks_shots(images, mask, shots, key_frame=0, levels=4, search=2, smooth=8):
-    """`propagate_masks` inside the key frame's shot; exactly 0 in every other shot: the subject of one scene is not in the next.
-    fp32 [F, H, W]."""
-    from .propagate import propagate_masks
+def _in_key_shot(fn, images, mask, shots, key_frame, *args):
+    """A single-key propagate `fn(images, mask, key_frame, *args)` inside the key frame's shot; exactly 0 in every other shot."""
     check_images(images)
     F = images.shape[0]
     ranges = clip_ranges(shots, F)
     int_in(key_frame, 0, F - 1, "key_frame")
     lo, hi = next(r for r in ranges if r[0] <= key_frame < r[1])
     if len(ranges) == 1:
-        return propagate_masks(images, mask, key_frame, levels, search, smooth)
+        return fn(images, mask, key_frame, *args)
     per_frame = torch.is_tensor(mask) and mask.ndim == 3 and mask.shape[0] == F
     out = torch.zeros(tuple(images.shape[:3]), dtype=torch.float32, device=images.device)
-    out[lo:hi] = propagate_masks(images[lo:hi], mask[lo:hi] if per_frame else mask, key_frame - lo, levels, search, smooth)
+    out[lo:hi] = fn(images[lo:hi], mask[lo:hi] if per_frame else mask, key_frame - lo, *args)
     return out
+
+
+def propagate_masks_shots(images, mask, shots, key_frame=0, levels=4, search=2, smooth=8):
+    """`propagate_masks` inside the key frame's shot; exactly 0 in every other shot: the subject of one scene is not in the next.
+    fp32 [F, H, W]."""
+    from .propagate import propagate_masks
+    return _in_key_shot(propagate_masks, images, mask, shots, key_frame, levels, search, smooth)
+
+
+def propagate_masks_anchored_shots(images, mask, shots, key_frame=0, levels=4, search=2, smooth=8, anchor=2):
+    """`propagate_masks_anchored` inside the key frame's shot; exactly 0 in every other shot.  fp32 [F, H, W]."""
+    from .propagate_anchored import propagate_masks_anchored
+    return _in_key_shot(propagate_masks_anchored, images, mask, shots, key_frame, levels, search, smooth, anchor)
