@@ -1823,7 +1823,8 @@ LP_API int lp_prop_merge_visible(const lp_prop_merge_visible_desc* desc, void* s
  * binarised mask.  anchor = 0 is the caller's "off": it makes none of the three launches and returns the plain chain.
  * Not handled: anchoring inside the occlusion-aware and the several-keys forms (an occluded block would be matched against the
  * occluder); a subject whose look changes away from the key (turning, relighting beyond what `smooth` refuses) gets e ~ 0 there and
- * drifts as before; re-anchoring every n-th frame only.
+ * drifts as before; re-anchoring every n-th frame only.  (Anchoring inside the single-key occlusion-aware form is the section
+ * behind this one, lp_prop_anchor_match_gated.)
  * Launch (csrc/propagate_kernel.hip): lp_prop_anchor_match fuses the warp and the match, K never goes to memory.  A block of 256
  * lanes per 32 x 32 pixels, that is 4 x 4 level-0 blocks: K of the tile and its halo of 4 (40 x 40 bytes, ANDed with the per-byte
  * mask beside it) goes to LDS once, gathered through P_t, which is read as 16-byte vectors when width % 4 == 0 and the planes are
@@ -1843,6 +1844,57 @@ typedef struct lp_prop_anchor_desc {
     int32_t*       valid;                         /* out, [gh, gw], 0 / 1: the inputs of lp_prop_fill                       */
 } lp_prop_anchor_desc;
 LP_API int lp_prop_anchor_match(const lp_prop_anchor_desc* desc, void* stream);
+
+/* ---- Video mask propagate, anchored and occlusion-aware (beyond the reference) -------------------------------------------------------
+ * The two single-key refinements above each fail where the other works.  The occlusion-aware form tests against the key frame through
+ * positions that have drifted, so on sub-pixel motion drift reads as occlusion and the chain collapses; the anchored form pulls the
+ * blocks under an occluder onto the occluder.  This form has both: the anchored re-match with an occlusion gate in the same pass, and
+ * the occlusion-aware form's test and split on the corrected positions.  A step is the single-key step with six launches behind it
+ * (the existing entries keep their meaning and their bits), 2 levels + 6 in all:
+ *   lp_prop_match / lp_prop_fill per level -> lp_prop_advance (out, mask_pyramid to scratch: P_t, c, m = c >= 128)
+ *     -> lp_prop_anchor_match_gated -> lp_prop_fill -> lp_prop_advance (vec = e, pos_src = P_t, key bits: P'_t, c', m' = c' >= 128)
+ *     -> lp_prop_visible (on P'_t, Yt, Yk, m') -> lp_prop_occlude (on c' and those flags: mask, hidden, next step's bit pyramid).
+ * All of it is integer arithmetic.
+ * lp_prop_anchor_match_gated does, per level-0 block, exactly what lp_prop_anchor_match does: the same K(y, x) = (bil(Yk, P_t) + 128)
+ * >> 8, window and validity (LP_PROP_MIN_PIXELS), candidates, key order, clamping of target coordinates and sub-pixel step.  Then,
+ * for a live block with whole-pixel winner (oy, ox), the one the key order chose before the sub-pixel step:
+ *   M the mask pixels (m = 1) of the block's window, n = |M|;  d(y, x) = Yt(clamp(y + oy), clamp(x + ox)) - K(y, x);  D = sum_M d;
+ *   mu = floor((2 D + n) / (2 n)), the mathematical floor, clamped to +-LP_PROP_VIS_MAX_BIAS;  R = sum_M |d - mu|;
+ *   the block is gated iff R > occlusion * n.
+ * This is lp_prop_visible's statistic, taken at the alignment the match found, so drift of up to `anchor` pixels is not taken for an
+ * occluder.  gated [gh, gw] is 0 / 1, 0 for a block that is not live; valid = live and not gated; vec is lp_prop_anchor_match's
+ * vector where valid and 0 elsewhere.  lp_prop_fill gives a gated block the correction of its visible neighbours.  Hence, bit for
+ * bit: where gated = 0, vec and valid are lp_prop_anchor_match's; where gated = 1, valid = 0 and vec = 0.
+ * The final visibility test is the existing one on the corrected positions; mask, hidden and the bits that weight the next step's
+ * match come from lp_prop_occlude, as in the occlusion-aware form.  The key frame returns its binarised mask and a zero hidden;
+ * nothing is remembered between frames but the positions.
+ * What follows from the rule, bit for bit: a clip of equal frames, and a noise-free whole-pixel shift that the plain chain tracks
+ * exactly, return the plain chain's bits and a zero hidden; an empty mask gives 0 and 0; one frame gives the binarised mask; where
+ * no block is gated and no final flag fires, mask is the anchored form's and hidden is 0.  anchor = 0 is the caller's "off" for the
+ * re-match (the occlusion-aware form, its launches only), occlusion = 0 for the tests (the anchored form and zeros, its launches
+ * only), both 0 the plain chain and zeros.
+ * Not handled: a subject hidden entirely; what leaves the picture; occlusion edges finer than a block; several keys; a subject
+ * whose look changes away from the key.
+ * Launch (csrc/propagate_kernel.hip): lp_prop_anchor_match's kernel with a compile-time tail on its window loop.  Behind the
+ * wave-wide minimum every lane knows the winner; the window is 16 rows x 4 dwords, the 64 lanes of the wave: each lane cuts its
+ * target dword for the winner out of the patch in LDS (v_alignbyte_b32), unpacks four bytes against K under the per-byte mask, D is
+ * reduced across the wave, then mu, then R.  LDS as lp_prop_anchor_match has it.  One lane per block writes.  A tile without a mask
+ * pixel leaves after staging and writes 0 / 0 / 0.  One job.
+ * LP_E_INVALID: a null descriptor or pointer, a side outside 1..LP_VMASK_MAX_SIDE, anchor outside 1..LP_PROP_MAX_SEARCH, smooth
+ * outside 0..LP_PROP_MAX_SMOOTH, occlusion outside 1..255, reserved0 != 0, any output aliasing an input or another output.  All
+ * checked before any HIP call.                                                                                                     */
+typedef struct lp_prop_anchor_gated_desc {
+    int32_t height, width, anchor, smooth;        /* anchor 1..LP_PROP_MAX_SEARCH, smooth 0..LP_PROP_MAX_SMOOTH             */
+    int32_t occlusion, reserved0;                 /* occlusion 1..255 grey levels; reserved0 must be 0                      */
+    const int32_t* pos;                           /* P_t [height, width, 2], as lp_prop_advance wrote it                    */
+    const uint8_t* tgt;                           /* Yt: level 0 of frame t's luma pyramid [height, width]                  */
+    const uint8_t* key;                           /* Yk: level 0 of the key frame's luma pyramid                            */
+    const uint8_t* mask;                          /* m: level 0 of the pyramid lp_prop_advance wrote                        */
+    int32_t*       vec;                           /* out, [gh, gw, 2], the raw correction field, 0 where gated              */
+    int32_t*       valid;                         /* out, [gh, gw], 0 / 1: the inputs of lp_prop_fill                       */
+    int32_t*       gated;                         /* out, [gh, gw], 0 / 1: a live block that does not look like the key     */
+} lp_prop_anchor_gated_desc;
+LP_API int lp_prop_anchor_match_gated(const lp_prop_anchor_gated_desc* desc, void* stream);
 
 /* ---- Video temporal fill (beyond the reference) -------------------------------------------------------------------------------------
  * What lies under the mask of a video frame is, in most clips, plain background a few frames earlier or later: a subject moves

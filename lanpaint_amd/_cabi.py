@@ -446,6 +446,13 @@ class LpPropAnchorDesc(C.Structure):
                 ("valid", C.c_void_p)]
 
 
+class LpPropAnchorGatedDesc(C.Structure):
+    _fields_ = [("height", C.c_int32), ("width", C.c_int32), ("anchor", C.c_int32), ("smooth", C.c_int32),
+                ("occlusion", C.c_int32), ("reserved0", C.c_int32),
+                ("pos", C.c_void_p), ("tgt", C.c_void_p), ("key", C.c_void_p), ("mask", C.c_void_p), ("vec", C.c_void_p),
+                ("valid", C.c_void_p), ("gated", C.c_void_p)]
+
+
 class LpPropVisibleJob(C.Structure):
     _fields_ = [("pos", C.c_void_p), ("tgt", C.c_void_p), ("key", C.c_void_p), ("mask", C.c_void_p), ("flags", C.c_void_p)]
 
@@ -659,6 +666,7 @@ EXPORTS = {
     "lp_prop_occlude_batch": (C.c_int, [C.POINTER(LpPropOccludeBatchDesc), C.c_void_p]),
     "lp_prop_merge_visible": (C.c_int, [C.POINTER(LpPropMergeVisibleDesc), C.c_void_p]),
     "lp_prop_anchor_match": (C.c_int, [C.POINTER(LpPropAnchorDesc), C.c_void_p]),
+    "lp_prop_anchor_match_gated": (C.c_int, [C.POINTER(LpPropAnchorGatedDesc), C.c_void_p]),
     "lp_tfill_known": (C.c_int, [C.POINTER(LpTfillKnownDesc), C.c_void_p]),
     "lp_tfill_carry": (C.c_int, [C.POINTER(LpTfillCarryDesc), C.c_void_p]),
     "lp_tfill_carry_pair": (C.c_int, [C.POINTER(LpTfillCarryPairDesc), C.c_void_p]),

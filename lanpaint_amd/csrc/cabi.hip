@@ -81,6 +81,7 @@ int prop_visible_batch_dispatch(const lp_prop_visible_batch_desc* d, hipStream_t
 int prop_occlude_batch_dispatch(const lp_prop_occlude_batch_desc* d, hipStream_t stream);
 int prop_merge_visible_dispatch(const lp_prop_merge_visible_desc* d, hipStream_t stream);
 int prop_anchor_match_dispatch(const lp_prop_anchor_desc* d, hipStream_t stream);
+int prop_anchor_match_gated_dispatch(const lp_prop_anchor_gated_desc* d, hipStream_t stream);
 int tfill_known_dispatch(const lp_tfill_known_desc* d, hipStream_t stream);
 int tfill_carry_dispatch(const lp_tfill_carry_desc* d, hipStream_t stream);
 int tfill_carry_pair_dispatch(const lp_tfill_carry_pair_desc* d, hipStream_t stream);
@@ -292,6 +293,10 @@ int lp_prop_merge_visible(const lp_prop_merge_visible_desc* desc, void* stream) 
 
 int lp_prop_anchor_match(const lp_prop_anchor_desc* desc, void* stream) {
     return lp::prop_anchor_match_dispatch(desc, as_stream(stream));
+}
+
+int lp_prop_anchor_match_gated(const lp_prop_anchor_gated_desc* desc, void* stream) {
+    return lp::prop_anchor_match_gated_dispatch(desc, as_stream(stream));
 }
 
 int lp_tfill_known(const lp_tfill_known_desc* desc, void* stream) { return lp::tfill_known_dispatch(desc, as_stream(stream)); }

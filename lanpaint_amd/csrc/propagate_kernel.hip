@@ -32,6 +32,8 @@
 //                as match has it, P_t read as two 16-byte vectors; the (40 + 2R)^2 clamped target patch goes to rows of 56 bytes.  A
 //                wave takes four of the tile's 4 x 4 windows in turn, the candidates over its lanes in up to four passes, match's
 //                v_alignbyte_b32 / v_sad_u8 inner loop, key and sub-pixel step.  A tile with no mask pixel leaves after staging K.
+//                The anchored occlusion-aware form's launch is the same kernel with a compile-time tail on the window loop: behind
+//                the minimum a lane per dword of the window takes visible's D, mu and R at the winner's alignment from the same LDS.
 //   merge        one lane per pixel and frame of a gap between two keys: the two chains' signed squared distances, their capped
 //                fp64 roots, the weighted mean in a fixed order, the ramp of half-width 1/2 around the zero crossing.
 //   merge_visible the merge of a gap whose chains are occlusion-aware: a streaming kernel over [frames, H, W], four pixels per lane
@@ -588,9 +590,14 @@ struct anchor_args {
     const uint8_t* msk;
     int32_t*       vec;
     int32_t*       valid;
-    int32_t H, W, gh, gw, search, smooth, wide;
+    int32_t*       gated;                                            // the gated form's third output, else null
+    int32_t H, W, gh, gw, search, smooth, wide, occlusion;
 };
 
+// Gated: the anchored occlusion-aware form.  Behind the wave-wide minimum every lane knows the winner; lane = row * 4 + dword of the
+// window cuts its four target pixels for the winner out of s_pat and takes lp_prop_visible's statistic there: D, mu and R over the
+// window's mask pixels.  A gated block gives no correction: vec 0, valid 0.
+template <bool Gated>
 __global__ __launch_bounds__(256) void lp_prop_anchor_match_kernel(const anchor_args a) {
     __shared__ uint32_t s_src[kVisSide * kAncPitch], s_bm[kVisSide * kAncPitch], s_pat[kAncPatRows * kAncPatPitch];
     __shared__ int32_t s_S[4][kMaxCand];
@@ -640,6 +647,7 @@ __global__ __launch_bounds__(256) void lp_prop_anchor_match_kernel(const anchor_
             a.vec[cell * 2] = 0;
             a.vec[cell * 2 + 1] = 0;
             a.valid[cell] = 0;
+            if (Gated) a.gated[cell] = 0;
         }
         return;
     }
@@ -665,6 +673,7 @@ __global__ __launch_bounds__(256) void lp_prop_anchor_match_kernel(const anchor_
         for (int d = 1; d < kWave; d <<= 1) count += __shfl_xor(count, d, kWave);
         const bool live = by < a.gh && bx < a.gw && count >= LP_PROP_MIN_PIXELS;      // the same in every lane of the wave
         uint32_t best = 0xFFFFFFFFu;
+        bool gate = false;                                               // the same in every lane of the wave
         if (live) {
             for (int c = lane; c < ncand; c += kWave) {
                 const int cy = c / n, cx = c - cy * n;                  // oy + R, ox + R
@@ -685,11 +694,33 @@ __global__ __launch_bounds__(256) void lp_prop_anchor_match_kernel(const anchor_
             }
 #pragma unroll
             for (int d = 1; d < kWave; d <<= 1) best = min(best, static_cast<uint32_t>(__shfl_xor(static_cast<int>(best), d, kWave)));
+            if (Gated) {
+                const int c = static_cast<int>(best & 255u), cy = c / n, cx = c - cy * n;
+                const int o = wx * kB + cx, shift = o & 3, r = lane >> 2, k = lane & 3;
+                const uint32_t* pr = s_pat + (wy * kB + r + cy) * kAncPatPitch + (o >> 2) + k;
+                const uint32_t t = __builtin_amdgcn_alignbyte(pr[1], pr[0], shift);
+                const uint32_t bm = s_bm[q0 + r * kAncPitch + k], sv = s_src[q0 + r * kAncPitch + k];
+                int dd[4], D = 0;
+#pragma unroll
+                for (int b = 0; b < 4; ++b) {                            // d = Yt - K on a mask pixel
+                    dd[b] = static_cast<int>((t >> (8 * b)) & 255u) - static_cast<int>((sv >> (8 * b)) & 255u);
+                    D += (bm >> (8 * b)) & 1u ? dd[b] : 0;
+                }
+#pragma unroll
+                for (int d = 1; d < kWave; d <<= 1) D += __shfl_xor(D, d, kWave);
+                const int mu = clampi(floor_div(2 * D + count, 2 * count), -LP_PROP_VIS_MAX_BIAS, LP_PROP_VIS_MAX_BIAS);
+                int Rs = 0;
+#pragma unroll
+                for (int b = 0; b < 4; ++b) Rs += (bm >> (8 * b)) & 1u ? abs(dd[b] - mu) : 0;
+#pragma unroll
+                for (int d = 1; d < kWave; d <<= 1) Rs += __shfl_xor(Rs, d, kWave);
+                gate = Rs > a.occlusion * count;
+            }
         }
         __syncthreads();                                                 // the wave's s_S is complete
         if (lane == 0 && by < a.gh && bx < a.gw) {
             int vy = 0, vx = 0;
-            if (live) {
+            if (live && !gate) {
                 const int c = static_cast<int>(best & 255u), cy = c / n, cx = c - cy * n;
                 vy = 16 * (cy - R);
                 vx = 16 * (cx - R);
@@ -708,7 +739,8 @@ __global__ __launch_bounds__(256) void lp_prop_anchor_match_kernel(const anchor_
             const int64_t cell = static_cast<int64_t>(by) * a.gw + bx;
             a.vec[cell * 2] = vy;
             a.vec[cell * 2 + 1] = vx;
-            a.valid[cell] = live ? 1 : 0;
+            a.valid[cell] = live && !gate ? 1 : 0;
+            if (Gated) a.gated[cell] = gate ? 1 : 0;
         }
     }
 }
@@ -993,27 +1025,49 @@ int prop_occlude_dispatch(const lp_prop_occlude_desc* dp, hipStream_t stream) {
     return prop_occlude_batch_dispatch(&d, stream);
 }
 
+// The two anchor entries' one dispatch: `gated` null is the anchored form, else the anchored occlusion-aware one.
+static int anchor_launch(int height, int width, int anchor, int smooth, int occlusion, const int32_t* pos, const uint8_t* tgt,
+                         const uint8_t* key, const uint8_t* mask, int32_t* vec, int32_t* valid, int32_t* gated, hipStream_t stream) {
+    if (!side_ok(height) || !side_ok(width)) return LP_E_INVALID;
+    if (anchor < 1 || anchor > LP_PROP_MAX_SEARCH || smooth < 0 || smooth > LP_PROP_MAX_SMOOTH) return LP_E_INVALID;
+    if (!pos || !tgt || !key || !mask || !vec || !valid) return LP_E_INVALID;
+    const void* outs[3] = {vec, valid, gated};
+    for (int k = 0; k < 3; ++k) {                                        // gated may be null; an output aliases nothing
+        if (!outs[k]) continue;
+        for (const void* in : {static_cast<const void*>(pos), static_cast<const void*>(tgt), static_cast<const void*>(key),
+                               static_cast<const void*>(mask)})
+            if (outs[k] == in) return LP_E_INVALID;
+        for (int m = k + 1; m < 3; ++m)
+            if (outs[k] == outs[m]) return LP_E_INVALID;
+    }
+    anchor_args a = {pos, tgt, key, mask, vec, valid, gated};
+    a.H = height;
+    a.W = width;
+    a.gh = (height + kB - 1) / kB;
+    a.gw = (width + kB - 1) / kB;
+    a.search = anchor;
+    a.smooth = smooth;
+    a.wide = width % 4 == 0 && aligned16(pos) && aligned16(mask);        // the kernel reads a row's four pixels as one vector
+    a.occlusion = occlusion;
+    const dim3 grid(blocks_of(width, kTile), blocks_of(height, kTile));
+    if (gated)
+        hipLaunchKernelGGL(lp_prop_anchor_match_kernel<true>, grid, dim3(256), 0, stream, a);
+    else
+        hipLaunchKernelGGL(lp_prop_anchor_match_kernel<false>, grid, dim3(256), 0, stream, a);
+    return launched();
+}
+
 int prop_anchor_match_dispatch(const lp_prop_anchor_desc* dp, hipStream_t stream) {
     if (!dp) return LP_E_INVALID;
-    const lp_prop_anchor_desc& d = *dp;
-    if (!side_ok(d.height) || !side_ok(d.width)) return LP_E_INVALID;
-    if (d.anchor < 1 || d.anchor > LP_PROP_MAX_SEARCH || d.smooth < 0 || d.smooth > LP_PROP_MAX_SMOOTH) return LP_E_INVALID;
-    if (!d.pos || !d.tgt || !d.key || !d.mask || !d.vec || !d.valid) return LP_E_INVALID;
-    const void *vec = d.vec, *valid = d.valid;
-    for (const void* in : {static_cast<const void*>(d.pos), static_cast<const void*>(d.tgt), static_cast<const void*>(d.key),
-                           static_cast<const void*>(d.mask)})
-        if (vec == in || valid == in) return LP_E_INVALID;
-    if (vec == valid) return LP_E_INVALID;
-    anchor_args a = {d.pos, d.tgt, d.key, d.mask, d.vec, d.valid};
-    a.H = d.height;
-    a.W = d.width;
-    a.gh = (d.height + kB - 1) / kB;
-    a.gw = (d.width + kB - 1) / kB;
-    a.search = d.anchor;
-    a.smooth = d.smooth;
-    a.wide = d.width % 4 == 0 && aligned16(d.pos) && aligned16(d.mask);    // the kernel reads a row's four pixels as one vector
-    hipLaunchKernelGGL(lp_prop_anchor_match_kernel, dim3(blocks_of(d.width, kTile), blocks_of(d.height, kTile)), dim3(256), 0, stream, a);
-    return launched();
+    return anchor_launch(dp->height, dp->width, dp->anchor, dp->smooth, 0, dp->pos, dp->tgt, dp->key, dp->mask, dp->vec, dp->valid,
+                         nullptr, stream);
+}
+
+int prop_anchor_match_gated_dispatch(const lp_prop_anchor_gated_desc* dp, hipStream_t stream) {
+    if (!dp) return LP_E_INVALID;
+    if (!dp->gated || dp->occlusion < 1 || dp->occlusion > 255 || dp->reserved0 != 0) return LP_E_INVALID;
+    return anchor_launch(dp->height, dp->width, dp->anchor, dp->smooth, dp->occlusion, dp->pos, dp->tgt, dp->key, dp->mask, dp->vec,
+                         dp->valid, dp->gated, stream);
 }
 
 int prop_merge_dispatch(const lp_prop_merge_desc* dp, hipStream_t stream) {

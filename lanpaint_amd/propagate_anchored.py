@@ -18,7 +18,8 @@ propagate_masks_anchored(images, mask, key_frame=0, levels=4, search=2, smooth=8
         binarised mask.  include/lanpaint_hip.h (lp_prop_anchor_match) states the rule in full.
         Not handled: anchoring inside the occlusion-aware and the several-key forms -- an occluded block would be matched against
         the occluder; a subject whose look changes away from the key frame (it turns, or the light changes beyond what `smooth`
-        refuses) gets no correction there and drifts as before; re-anchoring every n-th frame only.
+        refuses) gets no correction there and drifts as before; re-anchoring every n-th frame only.  Anchoring inside the
+        single-key occlusion-aware form, with a gate that keeps an occluded block out of the match: propagate_anchored_visible.py.
         profiles/r36_propagate_anchored.md has the numbers.
 
 HIP tensors only, no CPU fallback, no device -> host read.  The frames' luma pyramids come in propagate's chunks, under

@@ -21,7 +21,9 @@ propagate_masks_visible(images, mask, key_frame=0, levels=4, search=2, smooth=8,
         Not handled: a subject that is hidden entirely leaves the zero field and is lost if it reappears elsewhere; what leaves
         the picture; occlusion edges finer than a block -- `LanPaint_MaskRefine` follows in the chain.  Several keyframes with
         occlusion, where a second key behind the occluder recovers a lost subject: propagate_keys_visible.py.  A lower `occlusion` hides more and starts to take sub-pixel motion and noise
-        for an occluder; profiles/r29_propagate_visible.md has the numbers behind the default.
+        for an occluder; profiles/r29_propagate_visible.md has the numbers behind the default.  On a long clip with sub-pixel
+        motion the carried positions drift, drift reads as occlusion and the subject is lost; the form that re-matches the key
+        frame first: propagate_anchored_visible.py.
 
 HIP tensors only, no CPU fallback, no device -> host read.  The frames' luma pyramids come in propagate's chunks, under
 propagate.WS_CAP_BYTES; the key frame's luma plane is copied once per chain, so it outlives its chunk.  A step is 2 levels + 3

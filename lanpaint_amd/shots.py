@@ -31,6 +31,8 @@ temporal_smooth_robust_shots
         `temporal_smooth_robust`, the robust form of the smooth, per shot in the same way.
 propagate_masks_anchored_shots
         `propagate_masks_anchored`, the anchored form of the propagate, inside the key frame's shot as `propagate_masks_shots`.
+propagate_masks_anchored_visible_shots
+        `propagate_masks_anchored_visible`, the anchored occlusion-aware form, in the same way: both outputs 0 outside that shot.
 
 include/lanpaint_hip.h (lp_shot_*) states the rule in full: integers throughout, the same bits on every run.  Not done:
 dissolves, fades and wipes are not detected; the several-key propagates and the colour match's pooling over neighbouring
@@ -197,7 +199,8 @@ def stabilize_masks_shots(mask, shots, median=1, smooth=2, grow=0.0, feather=0.0
 
 
 def _in_key_shot(fn, images, mask, shots, key_frame, *args):
-    """A single-key propagate `fn(images, mask, key_frame, *args)` inside the key frame's shot; exactly 0 in every other shot."""
+    """A single-key propagate `fn(images, mask, key_frame, *args)` inside the key frame's shot; exactly 0 in every other shot.
+    `fn` returns one fp32 [F, H, W] or a tuple of them; so does this."""
     check_images(images)
     F = images.shape[0]
     ranges = clip_ranges(shots, F)
@@ -206,9 +209,13 @@ def _in_key_shot(fn, images, mask, shots, key_frame, *args):
     if len(ranges) == 1:
         return fn(images, mask, key_frame, *args)
     per_frame = torch.is_tensor(mask) and mask.ndim == 3 and mask.shape[0] == F
-    out = torch.zeros(tuple(images.shape[:3]), dtype=torch.float32, device=images.device)
-    out[lo:hi] = fn(images[lo:hi], mask[lo:hi] if per_frame else mask, key_frame - lo, *args)
-    return out
+    part = fn(images[lo:hi], mask[lo:hi] if per_frame else mask, key_frame - lo, *args)
+    outs = []
+    for p in part if isinstance(part, tuple) else (part,):
+        out = torch.zeros(tuple(images.shape[:3]), dtype=torch.float32, device=images.device)
+        out[lo:hi] = p
+        outs.append(out)
+    return tuple(outs) if isinstance(part, tuple) else outs[0]
 
 
 def propagate_masks_shots(images, mask, shots, key_frame=0, levels=4, search=2, smooth=8):
@@ -222,3 +229,10 @@ def propagate_masks_anchored_shots(images, mask, shots, key_frame=0, levels=4, s
     """`propagate_masks_anchored` inside the key frame's shot; exactly 0 in every other shot.  fp32 [F, H, W]."""
     from .propagate_anchored import propagate_masks_anchored
     return _in_key_shot(propagate_masks_anchored, images, mask, shots, key_frame, levels, search, smooth, anchor)
+
+
+def propagate_masks_anchored_visible_shots(images, mask, shots, key_frame=0, levels=4, search=2, smooth=8, anchor=2, occlusion=16):
+    """`propagate_masks_anchored_visible` inside the key frame's shot; `mask` and `hidden` exactly 0 in every other shot.
+    (fp32 [F, H, W], fp32 [F, H, W])."""
+    from .propagate_anchored_visible import propagate_masks_anchored_visible
+    return _in_key_shot(propagate_masks_anchored_visible, images, mask, shots, key_frame, levels, search, smooth, anchor, occlusion)

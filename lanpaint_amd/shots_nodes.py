@@ -129,17 +129,18 @@ class _PerShot:
         return _shots.per_shot(lambda *cut: fn(**dict(zip(clips, cut)), **kw), self._ranges(shots, frames), tuple(clips.values()))
 
     def _in_key_shot(self, shots, image, mask, key_frame, *args):
-        """The single-key propagate nodes: the parent's function on the key frame's shot, an empty mask in every other shot."""
+        """The single-key propagate nodes: the parent's function on the key frame's shot, every output empty in every other shot."""
         frames, key = image.shape[0], int(key_frame)
         if not 0 <= key < frames:
             raise ValueError(f"key_frame must be in 0..{frames - 1}, got {key_frame}")
         lo, hi = next(r for r in self._ranges(shots, frames) if r[0] <= key < r[1])
-        (part,) = getattr(super(), self.FUNCTION)(image[lo:hi], mask[lo:hi] if _per_frame(mask, frames) else mask, key - lo, *args)
+        parts = getattr(super(), self.FUNCTION)(image[lo:hi], mask[lo:hi] if _per_frame(mask, frames) else mask, key - lo, *args)
         if (lo, hi) == (0, frames):
-            return (part,)
-        out = torch.zeros((frames, *part.shape[1:]), dtype=part.dtype, device=part.device)
-        out[lo:hi] = part
-        return (out,)
+            return parts
+        outs = tuple(torch.zeros((frames, *part.shape[1:]), dtype=part.dtype, device=part.device) for part in parts)
+        for out, part in zip(outs, parts):
+            out[lo:hi] = part
+        return outs
 
 
 _NOTE = " With `shots` it works inside every shot on its own, so nothing crosses a hard cut."
