@@ -76,6 +76,18 @@ def device_tables(builder, device, *key):
     return tuple(torch.tensor(a, device=device) for a in builder(*key))
 
 
+def tables_for_launch(builder, device, *key):
+    """`device_tables(builder, device, *key)` for a launch on torch's current stream of `device`: each table records that
+    stream.  The cache hands one upload to every stream of the process, and when it evicts an entry the block goes back to the
+    pool of the stream that uploaded it; without the record the allocator may give it out again while a launch queued on another
+    stream still reads it.  On the uploading stream itself the record is a no-op."""
+    tables = device_tables(builder, device, *key)
+    stream = torch.cuda.current_stream(device)
+    for t in tables:
+        t.record_stream(stream)
+    return tables
+
+
 def aten_randn_policy(numel: int, multi_processor_count: int, max_threads_per_multi_processor: int):
     """calc_execution_policy of ATen's random kernels for one fp32 randn of `numel` elements: 256-thread blocks, the
     grid capped at SMs * (maxThreadsPerSM / 256), four values per thread and loop trip.  Returns (block * grid,

@@ -92,7 +92,7 @@ import torch
 
 from . import _cabi
 from ._hostcall import int_in, launch, mask3, mask_for, require_hip
-from ._util import _as_f32c, device_tables
+from ._util import _as_f32c, tables_for_launch
 from .videomask import tap_window
 
 FILTERS = ("bilinear", "bicubic")
@@ -307,8 +307,8 @@ def _resample(src, win, filter, origins=None, labels=None, owner=None):
     out = torch.empty((images, win.oh, win.ow, c), dtype=torch.float32, device=dev)
     d.src, d.dst = src.data_ptr(), out.data_ptr()
     if win.resampled:
-        bx, wx = device_tables(_aa_tables_f32, dev, win.w, win.ow, filter)
-        by, wy = device_tables(_aa_tables_f32, dev, win.h, win.oh, filter)
+        bx, wx = tables_for_launch(_aa_tables_f32, dev, win.w, win.ow, filter)
+        by, wy = tables_for_launch(_aa_tables_f32, dev, win.h, win.oh, filter)
         d.ksize_x, d.ksize_y = wx.shape[1], wy.shape[1]
         d.bounds_x, d.weights_x, d.bounds_y, d.weights_y = bx.data_ptr(), wx.data_ptr(), by.data_ptr(), wy.data_ptr()
     launch(entry, dev, ctypes.byref(d))

@@ -170,8 +170,8 @@ def match(image, mask, reference=None, strength=1.0, size="auto", monochrome=Fal
           frame0=0):
     """`image` [B, H, W, C] with the grain it lacks under `mask` put back.  The reference side is `reference` measured everywhere
     when given (any batch and size, the same channel count: a grain plate or the untouched original), otherwise `image`
-    outside the mask; the generated side is `image` inside the mask.  Two measurements, one fit and one apply per chunk of
-    frames on the current stream, and no device -> host read."""
+    outside the mask; the generated side is `image` inside the mask.  On the current stream: two measurements (lp_grain_stats)
+    and one apply per chunk of frames, and between them one fit for the whole batch; no device -> host read."""
     _check_stats("all", flat, margin)
     _check_fit(0, strength, size, 0)
     int_in(clip_frames, 0, MAX_BATCH, "clip_frames")

@@ -25,7 +25,7 @@ import torch
 
 from . import _cabi
 from ._hostcall import chunks, launch
-from ._util import device_tables
+from ._util import tables_for_launch
 
 # one lp_vmask_frame of include/lanpaint_hip.h
 FRAME_DTYPE = np.dtype([("kind", "<i4"), ("key_lo", "<i4"), ("key_hi", "<i4"), ("sx1", "<i4"), ("sy1", "<i4"),
@@ -228,8 +228,8 @@ def resize_codes(codes, size):
     out_w, out_h = int(size[0]), int(size[1])
     _check_side(h, w, out_h, out_w)
     dev = codes.device
-    bx, kx = device_tables(pillow_bilinear_coeffs, dev, w, out_w)
-    by, ky = device_tables(pillow_bilinear_coeffs, dev, h, out_h)
+    bx, kx = tables_for_launch(pillow_bilinear_coeffs, dev, w, out_w)
+    by, ky = tables_for_launch(pillow_bilinear_coeffs, dev, h, out_h)
     out = torch.empty((n, out_h, out_w), dtype=torch.float32, device=dev)
     d = _cabi.LpVmaskResizeDesc(n, h, w, out_h, out_w, kx.shape[1], ky.shape[1], 0, codes.data_ptr(),
                                 bx.data_ptr(), kx.data_ptr(), by.data_ptr(), ky.data_ptr(), out.data_ptr())
@@ -241,7 +241,9 @@ def interpolate_masks(keyframes, count, size=None, device=None):
     """{frame: [h, w] mask in [0, 1]} (numpy arrays or tensors) -> float32 [count, H, W] on the HIP device: keyframes
     keep their painted values, frames between two keyframes get the SDF morph, frames outside the keyframe window are 0;
     then, when `size` = (W, H) differs from (w, h), Pillow's 8-bit BILINEAR up to it.  Unlike the reference, which raises
-    IndexError when a frame between two keyframes lies at or beyond `count`, the frames 0..count-1 are returned."""
+    IndexError when a frame between two keyframes lies at or beyond `count`, the frames 0..count-1 are returned.  With more
+    than one keyframe the centroid sums [K, 3] are read back for the plan: the call's one device -> host read; with one
+    keyframe there is none."""
     count = int(count)
     if count <= 0:
         raise ValueError("count must be positive")

@@ -38,6 +38,23 @@ def test_00_reads_as_zero_and_other_bytes_as_themselves(monkeypatch):
     assert (torch.empty(2, dtype=torch.int32) == 0x5A5A5A5A).all()
 
 
+def test_the_eight_byte_types_read_as_minus_one_nan_and_zero(monkeypatch):
+    """int64 and float64, which the image-space family allocates through it (the grain tables and the EDT's centroid sums, the
+    colour match's workspace and table, the EDT's SDF): every one of the eight bytes holds the poison."""
+    filled = poisoned_empty(monkeypatch, 0xFF)
+    i, f = torch.empty((2, 3, 8, 3), dtype=torch.int64), torch.empty((3, 13), dtype=torch.float64)
+    assert i.dtype == torch.int64 and tuple(i.shape) == (2, 3, 8, 3) and (i == -1).all()
+    assert f.dtype == torch.float64 and tuple(f.shape) == (3, 13) and torch.isnan(f).all() and (f.view(torch.int64) == -1).all()
+    assert (torch.empty_like(i) == -1).all() and torch.isnan(torch.empty_like(f)).all()
+    assert filled == [1152, 312, 1152, 312]
+    monkeypatch.undo()
+    filled = poisoned_empty(monkeypatch, 0x00)
+    i, f = torch.empty((2, 3, 8, 3), dtype=torch.int64), torch.empty((3, 13), dtype=torch.float64)
+    assert (i == 0).all() and (f == 0).all() and (f.view(torch.int64) == 0).all()                # +0.0, not -0.0
+    assert (torch.empty_like(i) == 0).all() and (torch.empty_like(f).view(torch.int64) == 0).all()
+    assert filled == [1152, 312, 1152, 312]
+
+
 def test_a_tensor_without_elements_survives_and_zeros_is_not_touched(monkeypatch):
     filled = poisoned_empty(monkeypatch, 0xFF)
     for shape in ((0,), (0, 2), (3, 0, 5)):
