@@ -1,6 +1,7 @@
-"""What the motion modules (propagate, propagate_visible, propagate_keys, propagate_keys_visible, temporal_fill,
-temporal_fill_checked, temporal_smooth, temporal_smooth_robust, shots) share on top of _hostcall.py: the checks of the block
-matcher's numbers and planes, the clip-mask shapes, the luma pyramids, and the batched coarse-to-fine field walk.  Plain
+"""What the motion modules (propagate, propagate_visible, propagate_anchored, propagate_anchored_visible, propagate_keys,
+propagate_keys_visible, temporal_fill, temporal_fill_checked, temporal_smooth, temporal_smooth_robust, shots) share on top of
+_hostcall.py: the checks of the block matcher's numbers and planes, of a frame's planes next to the warped key frame
+(`check_frame_planes`), the clip-mask shapes, the luma pyramids, and the batched coarse-to-fine field walk.  Plain
 functions and one small class; no nodes, nothing of the engine's path.  HIP tensors only, no CPU fallback.
 
 Who owns which buffer.  A `FieldWalk` owns the scratch of one group of at most LP_PROP_MAX_JOBS jobs: per level the raw field,
@@ -17,7 +18,7 @@ import numpy as np
 import torch
 
 from . import _cabi
-from ._hostcall import chunks, int_in, launch, require_hip, workspace
+from ._hostcall import chunks, int_in, launch, require_hip, tensor_is, workspace
 from ._util import _as_f32c
 
 MAX_SIDE = _cabi.LP_VMASK_MAX_SIDE
@@ -44,6 +45,17 @@ def check_images(images):
         raise ValueError(f"images must be [F, H, W, C] with 1..{_cabi.LP_DETAIL_MAX_CHANNELS} channels, got {tuple(images.shape)}")
     check_plane(images.shape[1], images.shape[2])
     return images
+
+
+def check_frame_planes(pos, tgt, key, mask_bits, module):
+    """What the stages that hold a frame against the warped key frame take: `tgt`, `key` and `mask_bits` uint8 [H, W] of one
+    plane within the limits, `pos` int32 [H, W, 2].  (H, W); `module` is the caller's __name__."""
+    H, W = tensor_is(tgt, torch.uint8, (None, None), "tgt", module).shape
+    check_plane(H, W)
+    tensor_is(key, torch.uint8, (H, W), "key", module)
+    tensor_is(mask_bits, torch.uint8, (H, W), "mask_bits", module)
+    tensor_is(pos, torch.int32, (H, W, 2), "pos", module)
+    return H, W
 
 
 def clip_mask(mask, F, H, W, module):

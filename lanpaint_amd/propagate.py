@@ -108,10 +108,18 @@ def advance(vec, pos, key_bits, levels, pos_out=None, out=None, mpyr_out=None):
 
 
 class Step:
-    """The buffers one chain's steps share, and one step s -> t on them: 2 levels + 1 launches, nothing allocated."""
+    """The buffers one chain's steps share, and one step s -> t on them: 2 levels + 1 launches, nothing allocated.  The two
+    refinements of the single-key family are options, each off by default, handed in by the module that owns their stages:
+        rematch  (match, *numbers): propagate_anchored's (anchor_field, anchor, smooth), or propagate_anchored_visible's
+                 (gated_anchor_field, anchor, smooth, occlusion) -- the gated one when `split` is on too.  A first advance, the
+                 match of the warped key against the frame, fill_median, and the advance proper along that correction: + 3.
+        split    (visible_flags, occlude, occlusion), propagate_visible's: the flags, then occlude, behind the last advance: + 2.
+    Scratch comes with the option that needs it.  Either: `code` and `raw_mpyr`, an advance's mask and the pyramid of its bits.
+    rematch: `raw_pos`, the first advance's positions.  split: `flags`.  Both: `gated`.  The plain step has none of them."""
 
-    def __init__(self, H, W, levels, search, smooth, dev):
+    def __init__(self, H, W, levels, search, smooth, dev, rematch=None, split=None):
         self.H, self.W, self.levels, self.search, self.smooth = H, W, levels, search, smooth
+        self.rematch, self.split = rematch, split
         grids = [_cabi.prop_grid(H, W, lv) for lv in range(levels)]
         self.raw = [torch.empty((gh, gw, 2), dtype=torch.int32, device=dev) for gh, gw in grids]
         self.valid = [torch.empty((gh, gw), dtype=torch.int32, device=dev) for gh, gw in grids]
@@ -119,6 +127,15 @@ class Step:
         self.pos = [torch.empty((H, W, 2), dtype=torch.int32, device=dev) for _ in range(2)]
         stride = _cabi.prop_pyramid_ws_bytes(1, H, W, levels)
         self.mpyr = [torch.empty((1, stride), dtype=torch.uint8, device=dev) for _ in range(2)]
+        if rematch or split:
+            self.code = torch.empty((H, W), dtype=torch.float32, device=dev)
+            self.raw_mpyr = torch.empty_like(self.mpyr[0])
+        if rematch:
+            self.raw_pos = torch.empty_like(self.pos[0])
+        if split:
+            self.flags = torch.empty(grids[0], dtype=torch.int32, device=dev)
+        if rematch and split:
+            self.gated = torch.empty_like(self.flags)
 
     def field_of(self, src, tgt, mpyr):
         """Level 0's final field of the step from the frame with pyramid `src` to the one with `tgt`, weighted by `mpyr`."""
@@ -128,14 +145,39 @@ class Step:
             parent = fill_median(self.raw[lv], self.valid[lv], self.field[lv])
         return parent
 
-    def chain(self, frames, key_pyr, out):
-        """`frames`: (index into out, that frame's luma pyramid) from the key outwards, the key first; writes out[t] behind it."""
-        pos, mpyr, src, k = None, key_pyr, None, 0
-        key_bits = level_view(key_pyr, self.H, self.W, 0)[0]
+    def chain(self, frames, key_pyr, out, hidden=None):
+        """`frames`: (index into out, that frame's luma pyramid) from the key outwards, the key first; writes out[t] behind it,
+        and hidden[t] when the split is on.  Which buffer serves what:
+          - level 0's raw, valid and field serve the correction too: the step's own field is spent by the first advance;
+          - the first advance's code and raw_mpyr are scratch once the re-match has read them: the second advance rewrites both;
+          - with the split on, the last advance's mask is the code to split and its bits are raw_mpyr; occlude writes the
+            pyramid of the next step's weights to self.mpyr[k], never to raw_mpyr, whose bits the flags have just been read from;
+          - the key frame's luma is this chain's own copy, since the key's chunk may go; the plain step never looks at luma."""
+        H, W, levels = self.H, self.W, self.levels
+        match, *numbers = self.rematch or (None,)
+        flags_of, occlude, occlusion = self.split or (None, None, None)
+        refined = bool(match or occlude)
+        gate = (self.gated,) if match and occlude else ()
+        pos, mpyr, src, k, luma, key_luma = None, key_pyr, None, 0, None, None
+        key_bits = level_view(key_pyr, H, W, 0)[0]
+        bits = level_view(self.raw_mpyr, H, W, 0)[0] if refined else None
         for t, pyr in frames:
-            if src is not None:
+            if refined:
+                luma = level_view(pyr[None], H, W, 0)[0]
+            if src is None:
+                key_luma = luma.clone() if refined else None
+            else:
                 vec = self.field_of(src, pyr, mpyr)
-                pos, _, mpyr = advance(vec, pos, key_bits, self.levels, self.pos[k], out[t], self.mpyr[k])
+                if match:
+                    advance(vec, pos, key_bits, levels, self.raw_pos, self.code, self.raw_mpyr)
+                    match(self.raw_pos, luma, key_luma, bits, *numbers, self.raw[0], self.valid[0], *gate)
+                    vec, pos = fill_median(self.raw[0], self.valid[0], self.field[0]), self.raw_pos
+                if occlude:
+                    pos, _, _ = advance(vec, pos, key_bits, levels, self.pos[k], self.code, self.raw_mpyr)
+                    flags_of(pos, luma, key_luma, bits, occlusion, self.flags)
+                    _, _, mpyr = occlude(self.code, self.flags, levels, out[t], hidden[t], self.mpyr[k])
+                else:
+                    pos, _, mpyr = advance(vec, pos, key_bits, levels, self.pos[k], out[t], self.mpyr[k])
                 k ^= 1
             src = pyr
 
@@ -163,6 +205,20 @@ def key_and_orders(images, mask, key_frame, levels):
     return key_pyr, out, [o for o in (list(range(key_frame, F)), list(range(key_frame, -1, -1))) if len(o) > 1]
 
 
+def run(images, mask, key_frame, levels, search, smooth, rematch=None, split=None):
+    """What the four single-key forms do behind their checks, `rematch` and `split` as Step takes them: the mask fp32 [F, H, W],
+    and with the split (mask, hidden), the key frame's `hidden` zero."""
+    key_pyr, out, orders = key_and_orders(images, mask, key_frame, levels)
+    hidden = None
+    if split:
+        hidden = torch.empty_like(out)
+        hidden[key_frame].zero_()
+    step = Step(*images.shape[1:3], levels, search, smooth, images.device, rematch, split)
+    for order in orders:
+        step.chain(chain_frames(images, order, levels), key_pyr, out, hidden)
+    return (out, hidden) if split else out
+
+
 def propagate_masks(images, mask, key_frame=0, levels=4, search=2, smooth=8):
     """`mask`, painted on frame `key_frame` of `images` [F, H, W, C], followed through every frame (module docstring): fp32
     [F, H, W] on the images' device.  No device -> host read."""
@@ -170,8 +226,4 @@ def propagate_masks(images, mask, key_frame=0, levels=4, search=2, smooth=8):
     check_images(images)
     require_hip(mask, "mask", __name__)
     int_in(key_frame, 0, images.shape[0] - 1, "key_frame")
-    key_pyr, out, orders = key_and_orders(images, mask, key_frame, levels)
-    step = Step(*images.shape[1:3], levels, search, smooth, images.device)
-    for order in orders:
-        step.chain(chain_frames(images, order, levels), key_pyr, out)
-    return out
+    return run(images, mask, key_frame, levels, search, smooth)

@@ -33,9 +33,9 @@ import ctypes
 import torch
 
 from . import _cabi, propagate
-from ._hostcall import int_in, launch, require_hip, tensor_is
-from ._motion import check_images, check_params, check_plane, level_view
-from .propagate import Step, advance, chain_frames, fill_median, key_and_orders
+from ._hostcall import int_in, launch, require_hip
+from ._motion import check_frame_planes, check_images, check_params
+from .propagate import Step                                          # noqa: F401  (the family's one step, options and all)
 
 MAX_ANCHOR = propagate.MAX_SEARCH
 DEFAULT_ANCHOR = 2
@@ -47,11 +47,7 @@ def anchor_field(pos, tgt, key, mask_bits, anchor=DEFAULT_ANCHOR, smooth=8, vec=
     valid int32 [gh, gw]), what fill_median takes.  One launch."""
     int_in(anchor, 1, MAX_ANCHOR, "anchor")
     int_in(smooth, 0, propagate.MAX_SMOOTH, "smooth")
-    H, W = tensor_is(tgt, torch.uint8, (None, None), "tgt", __name__).shape
-    check_plane(H, W)
-    tensor_is(key, torch.uint8, (H, W), "key", __name__)
-    tensor_is(mask_bits, torch.uint8, (H, W), "mask_bits", __name__)
-    tensor_is(pos, torch.int32, (H, W, 2), "pos", __name__)
+    H, W = check_frame_planes(pos, tgt, key, mask_bits, __name__)
     gh, gw = _cabi.prop_grid(H, W)
     vec = torch.empty((gh, gw, 2), dtype=torch.int32, device=tgt.device) if vec is None else vec
     valid = torch.empty((gh, gw), dtype=torch.int32, device=tgt.device) if valid is None else valid
@@ -59,37 +55,6 @@ def anchor_field(pos, tgt, key, mask_bits, anchor=DEFAULT_ANCHOR, smooth=8, vec=
                                vec.data_ptr(), valid.data_ptr())
     launch("lp_prop_anchor_match", tgt.device, ctypes.byref(d))
     return vec, valid
-
-
-class AnchoredStep(Step):
-    """propagate's step buffers and the three this form adds: the first advance's code and pyramid, now scratch, and its
-    positions.  Level 0's raw, valid and field buffers serve the correction too: the step's own field is spent by then."""
-
-    def __init__(self, H, W, levels, search, smooth, anchor, dev):
-        super().__init__(H, W, levels, search, smooth, dev)
-        self.anchor = anchor
-        self.code = torch.empty((H, W), dtype=torch.float32, device=dev)
-        self.raw_mpyr = torch.empty_like(self.mpyr[0])
-        self.raw_pos = torch.empty_like(self.pos[0])
-
-    def chain(self, frames, key_pyr, out):
-        """`frames`: (index into out, that frame's luma pyramid) from the key outwards, the key first; writes out[t] behind it."""
-        H, W = self.H, self.W
-        pos, mpyr, src, k, key_luma = None, key_pyr, None, 0, None
-        key_bits = level_view(key_pyr, H, W, 0)[0]
-        for t, pyr in frames:
-            luma = level_view(pyr[None], H, W, 0)[0]
-            if src is None:
-                key_luma = luma.clone()                               # its own copy: the key's chunk may go
-            else:
-                vec = self.field_of(src, pyr, mpyr)
-                advance(vec, pos, key_bits, self.levels, self.raw_pos, self.code, self.raw_mpyr)
-                anchor_field(self.raw_pos, luma, key_luma, level_view(self.raw_mpyr, H, W, 0)[0], self.anchor, self.smooth,
-                             self.raw[0], self.valid[0])
-                e = fill_median(self.raw[0], self.valid[0], self.field[0])
-                pos, _, mpyr = advance(e, self.raw_pos, key_bits, self.levels, self.pos[k], out[t], self.mpyr[k])
-                k ^= 1
-            src = pyr
 
 
 def propagate_masks_anchored(images, mask, key_frame=0, levels=4, search=2, smooth=8, anchor=DEFAULT_ANCHOR):
@@ -102,8 +67,4 @@ def propagate_masks_anchored(images, mask, key_frame=0, levels=4, search=2, smoo
     int_in(key_frame, 0, images.shape[0] - 1, "key_frame")
     if anchor == 0:
         return propagate.propagate_masks(images, mask, key_frame, levels, search, smooth)
-    key_pyr, out, orders = key_and_orders(images, mask, key_frame, levels)
-    step = AnchoredStep(*images.shape[1:3], levels, search, smooth, anchor, images.device)
-    for order in orders:
-        step.chain(chain_frames(images, order, levels), key_pyr, out)
-    return out
+    return propagate.run(images, mask, key_frame, levels, search, smooth, rematch=(anchor_field, anchor, smooth))

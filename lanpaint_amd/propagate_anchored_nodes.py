@@ -19,6 +19,7 @@ from __future__ import annotations
 
 from . import propagate_anchored as _anchored
 from ._hostcall import int_in, node_device
+from .propagate_nodes import MATCHER_WIDGETS
 from .shots_nodes import _PerShot
 
 
@@ -34,15 +35,7 @@ class LanPaint_VideoMaskPropagateAnchored:
             "key_frame": ("INT", {"default": 0, "min": 0, "max": 65534, "step": 1,
                                   "tooltip": "The frame the mask was painted on. The mask is carried forwards and backwards "
                                              "from it, and every frame is matched against this frame's picture."}),
-            "levels": ("INT", {"default": 4, "min": 1, "max": 6, "step": 1,
-                               "tooltip": "Pyramid levels of the motion search. Every level doubles the motion per frame that can "
-                                          "be followed: about search * 2^levels pixels."}),
-            "search": ("INT", {"default": 2, "min": 1, "max": 7, "step": 1,
-                               "tooltip": "Pixels searched around the coarser level's motion at every level. More follows "
-                                          "faster or less regular motion and costs time with its square."}),
-            "smooth": ("INT", {"default": 8, "min": 0, "max": 64, "step": 1,
-                               "tooltip": "The price of a pixel of displacement in the match, in grey levels summed over a block: "
-                                          "keeps flat, textureless areas from drifting. 0 switches it off."}),
+            **MATCHER_WIDGETS,
             "anchor": ("INT", {"default": _anchored.DEFAULT_ANCHOR, "min": 0, "max": _anchored.MAX_ANCHOR, "step": 1,
                                "tooltip": "Pixels searched around the carried position when a frame is matched against the key "
                                           "frame: the largest error one frame can take out. It costs time with its square; 0 "

@@ -38,9 +38,9 @@ import ctypes
 import torch
 
 from . import _cabi, propagate
-from ._hostcall import int_in, launch, require_hip, tensor_is
-from ._motion import check_images, check_params, check_plane, level_view
-from .propagate import Step, advance, chain_frames, fill_median, key_and_orders
+from ._hostcall import int_in, launch, require_hip
+from ._motion import check_frame_planes, check_images, check_params
+from .propagate import Step                                          # noqa: F401  (the family's one step, options and all)
 from .propagate_anchored import DEFAULT_ANCHOR, MAX_ANCHOR, propagate_masks_anchored
 from .propagate_visible import DEFAULT_OCCLUSION, MAX_OCCLUSION, occlude, propagate_masks_visible, visible_flags
 
@@ -53,11 +53,7 @@ def gated_anchor_field(pos, tgt, key, mask_bits, anchor=DEFAULT_ANCHOR, smooth=8
     int_in(anchor, 1, MAX_ANCHOR, "anchor")
     int_in(smooth, 0, propagate.MAX_SMOOTH, "smooth")
     int_in(occlusion, 1, MAX_OCCLUSION, "occlusion")
-    H, W = tensor_is(tgt, torch.uint8, (None, None), "tgt", __name__).shape
-    check_plane(H, W)
-    tensor_is(key, torch.uint8, (H, W), "key", __name__)
-    tensor_is(mask_bits, torch.uint8, (H, W), "mask_bits", __name__)
-    tensor_is(pos, torch.int32, (H, W, 2), "pos", __name__)
+    H, W = check_frame_planes(pos, tgt, key, mask_bits, __name__)
     gh, gw = _cabi.prop_grid(H, W)
     vec = torch.empty((gh, gw, 2), dtype=torch.int32, device=tgt.device) if vec is None else vec
     valid = torch.empty((gh, gw), dtype=torch.int32, device=tgt.device) if valid is None else valid
@@ -66,44 +62,6 @@ def gated_anchor_field(pos, tgt, key, mask_bits, anchor=DEFAULT_ANCHOR, smooth=8
                                     mask_bits.data_ptr(), vec.data_ptr(), valid.data_ptr(), gated.data_ptr())
     launch("lp_prop_anchor_match_gated", tgt.device, ctypes.byref(d))
     return vec, valid, gated
-
-
-class AnchoredVisibleStep(Step):
-    """propagate's step buffers and the five this form adds: an advance's code and pyramid -- the first advance's are scratch
-    once the re-match has read them, so the second advance writes the same two --, the first advance's positions, the gate and
-    the flags.  Level 0's raw, valid and field buffers serve the correction too: the step's own field is spent by then."""
-
-    def __init__(self, H, W, levels, search, smooth, anchor, occlusion, dev):
-        super().__init__(H, W, levels, search, smooth, dev)
-        self.anchor, self.occlusion = anchor, occlusion
-        self.code = torch.empty((H, W), dtype=torch.float32, device=dev)
-        self.raw_mpyr = torch.empty_like(self.mpyr[0])
-        self.raw_pos = torch.empty_like(self.pos[0])
-        self.gated = torch.empty(_cabi.prop_grid(H, W), dtype=torch.int32, device=dev)
-        self.flags = torch.empty_like(self.gated)
-
-    def chain(self, frames, key_pyr, out, hidden):
-        """`frames`: (index into out, that frame's luma pyramid) from the key outwards, the key first; writes out[t] and hidden[t]
-        behind it."""
-        H, W = self.H, self.W
-        pos, mpyr, src, k, key_luma = None, key_pyr, None, 0, None
-        key_bits = level_view(key_pyr, H, W, 0)[0]
-        bits = level_view(self.raw_mpyr, H, W, 0)[0]
-        for t, pyr in frames:
-            luma = level_view(pyr[None], H, W, 0)[0]
-            if src is None:
-                key_luma = luma.clone()                               # its own copy: the key's chunk may go
-            else:
-                vec = self.field_of(src, pyr, mpyr)
-                advance(vec, pos, key_bits, self.levels, self.raw_pos, self.code, self.raw_mpyr)
-                gated_anchor_field(self.raw_pos, luma, key_luma, bits, self.anchor, self.smooth, self.occlusion, self.raw[0],
-                                   self.valid[0], self.gated)
-                e = fill_median(self.raw[0], self.valid[0], self.field[0])
-                pos, _, _ = advance(e, self.raw_pos, key_bits, self.levels, self.pos[k], self.code, self.raw_mpyr)
-                visible_flags(pos, luma, key_luma, bits, self.occlusion, self.flags)
-                _, _, mpyr = occlude(self.code, self.flags, self.levels, out[t], hidden[t], self.mpyr[k])     # not raw_mpyr:
-                k ^= 1                                                                      # lp_prop_visible has just read it
-            src = pyr
 
 
 def propagate_masks_anchored_visible(images, mask, key_frame=0, levels=4, search=2, smooth=8, anchor=DEFAULT_ANCHOR,
@@ -123,10 +81,5 @@ def propagate_masks_anchored_visible(images, mask, key_frame=0, levels=4, search
     if occlusion == 0:
         return (propagate_masks_anchored(images, mask, key_frame, levels, search, smooth, anchor),
                 images.new_zeros((F, H, W), dtype=torch.float32))
-    key_pyr, out, orders = key_and_orders(images, mask, key_frame, levels)
-    hidden = torch.empty_like(out)
-    hidden[key_frame].zero_()
-    step = AnchoredVisibleStep(H, W, levels, search, smooth, anchor, occlusion, images.device)
-    for order in orders:
-        step.chain(chain_frames(images, order, levels), key_pyr, out, hidden)
-    return out, hidden
+    return propagate.run(images, mask, key_frame, levels, search, smooth, rematch=(gated_anchor_field, anchor, smooth, occlusion),
+                         split=(visible_flags, occlude, occlusion))

@@ -19,6 +19,7 @@ import re
 
 from . import propagate_keys as _keys
 from ._hostcall import node_device
+from .propagate_nodes import MATCHER_WIDGETS
 
 
 def parse_key_frames(text):
@@ -44,15 +45,7 @@ class LanPaint_VideoMaskPropagateKeys:
             "key_frames": ("STRING", {"default": "0",
                                       "tooltip": "The frames the masks were painted on: increasing integers separated by commas "
                                                  "or blanks, each a frame of the video."}),
-            "levels": ("INT", {"default": 4, "min": 1, "max": 6, "step": 1,
-                               "tooltip": "Pyramid levels of the motion search. Every level doubles the motion per frame that can "
-                                          "be followed: about search * 2^levels pixels."}),
-            "search": ("INT", {"default": 2, "min": 1, "max": 7, "step": 1,
-                               "tooltip": "Pixels searched around the coarser level's motion at every level. More follows "
-                                          "faster or less regular motion and costs time with its square."}),
-            "smooth": ("INT", {"default": 8, "min": 0, "max": 64, "step": 1,
-                               "tooltip": "The price of a pixel of displacement in the match, in grey levels summed over a block: "
-                                          "keeps flat, textureless areas from drifting. 0 switches it off."}),
+            **MATCHER_WIDGETS,
         }}
 
     RETURN_TYPES = ("MASK",)

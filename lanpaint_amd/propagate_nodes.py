@@ -17,6 +17,18 @@ from __future__ import annotations
 from . import propagate as _propagate
 from ._hostcall import node_device
 
+# The block matcher's three widgets, as every propagate node shows them: spliced into INPUT_TYPES where they stood.
+MATCHER_WIDGETS = {
+    "levels": ("INT", {"default": 4, "min": 1, "max": 6, "step": 1,
+                       "tooltip": "Pyramid levels of the motion search. Every level doubles the motion per frame that can "
+                                  "be followed: about search * 2^levels pixels."}),
+    "search": ("INT", {"default": 2, "min": 1, "max": 7, "step": 1,
+                       "tooltip": "Pixels searched around the coarser level's motion at every level. More follows "
+                                  "faster or less regular motion and costs time with its square."}),
+    "smooth": ("INT", {"default": 8, "min": 0, "max": 64, "step": 1,
+                       "tooltip": "The price of a pixel of displacement in the match, in grey levels summed over a block: "
+                                  "keeps flat, textureless areas from drifting. 0 switches it off."}),
+}
 
 class LanPaint_VideoMaskPropagate:
     """Carry a mask painted on one frame through the video along the picture's motion."""
@@ -30,15 +42,7 @@ class LanPaint_VideoMaskPropagate:
             "key_frame": ("INT", {"default": 0, "min": 0, "max": 65534, "step": 1,
                                   "tooltip": "The frame the mask was painted on. The mask is carried forwards and backwards "
                                              "from it; it must be a frame of the video."}),
-            "levels": ("INT", {"default": 4, "min": 1, "max": 6, "step": 1,
-                               "tooltip": "Pyramid levels of the motion search. Every level doubles the motion per frame that can "
-                                          "be followed: about search * 2^levels pixels."}),
-            "search": ("INT", {"default": 2, "min": 1, "max": 7, "step": 1,
-                               "tooltip": "Pixels searched around the coarser level's motion at every level. More follows "
-                                          "faster or less regular motion and costs time with its square."}),
-            "smooth": ("INT", {"default": 8, "min": 0, "max": 64, "step": 1,
-                               "tooltip": "The price of a pixel of displacement in the match, in grey levels summed over a block: "
-                                          "keeps flat, textureless areas from drifting. 0 switches it off."}),
+            **MATCHER_WIDGETS,
         }}
 
     RETURN_TYPES = ("MASK",)

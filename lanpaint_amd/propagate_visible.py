@@ -37,8 +37,8 @@ import torch
 
 from . import _cabi, propagate
 from ._hostcall import int_in, launch, require_hip, tensor_is
-from ._motion import check_images, check_params, check_plane, level_view
-from .propagate import Step, advance, chain_frames, key_and_orders
+from ._motion import check_frame_planes, check_images, check_params, check_plane
+from .propagate import Step                                          # noqa: F401  (the family's one step, options and all)
 
 MAX_OCCLUSION = 255
 DEFAULT_OCCLUSION = 16
@@ -49,11 +49,7 @@ def visible_flags(pos, tgt, key, mask_bits, occlusion=DEFAULT_OCCLUSION, out=Non
     the key frame's luma pyramid, `mask_bits` level 0 of the pyramid the advance wrote, all uint8 [H, W].  int32 [gh, gw], 1 where
     the block is occluded.  One launch."""
     int_in(occlusion, 1, MAX_OCCLUSION, "occlusion")
-    H, W = tensor_is(tgt, torch.uint8, (None, None), "tgt", __name__).shape
-    check_plane(H, W)
-    tensor_is(key, torch.uint8, (H, W), "key", __name__)
-    tensor_is(mask_bits, torch.uint8, (H, W), "mask_bits", __name__)
-    tensor_is(pos, torch.int32, (H, W, 2), "pos", __name__)
+    H, W = check_frame_planes(pos, tgt, key, mask_bits, __name__)
     out = torch.empty(_cabi.prop_grid(H, W), dtype=torch.int32, device=tgt.device) if out is None else out
     d = _cabi.LpPropVisibleDesc(H, W, occlusion, 0, pos.data_ptr(), tgt.data_ptr(), key.data_ptr(), mask_bits.data_ptr(), out.data_ptr())
     launch("lp_prop_visible", tgt.device, ctypes.byref(d))
@@ -78,35 +74,6 @@ def occlude(code, flags, levels, out=None, hidden=None, mpyr_out=None):
     return out, hidden, mpyr_out
 
 
-class VisibleStep(Step):
-    """propagate's step buffers and the three this form adds: the advance's code and pyramid, now scratch, and the flags."""
-
-    def __init__(self, H, W, levels, search, smooth, occlusion, dev):
-        super().__init__(H, W, levels, search, smooth, dev)
-        self.occlusion = occlusion
-        self.code = torch.empty((H, W), dtype=torch.float32, device=dev)
-        self.raw_mpyr = torch.empty_like(self.mpyr[0])
-        self.flags = torch.empty(_cabi.prop_grid(H, W), dtype=torch.int32, device=dev)
-
-    def chain(self, frames, key_pyr, out, hidden):
-        """`frames`: (index into out, that frame's luma pyramid) from the key outwards, the key first; writes out[t] and hidden[t]
-        behind it."""
-        H, W = self.H, self.W
-        pos, mpyr, src, k, key_luma = None, key_pyr, None, 0, None
-        key_bits = level_view(key_pyr, H, W, 0)[0]
-        for t, pyr in frames:
-            luma = level_view(pyr[None], H, W, 0)[0]
-            if src is None:
-                key_luma = luma.clone()                               # its own copy: the key's chunk may go
-            else:
-                vec = self.field_of(src, pyr, mpyr)
-                pos, _, _ = advance(vec, pos, key_bits, self.levels, self.pos[k], self.code, self.raw_mpyr)
-                visible_flags(pos, luma, key_luma, level_view(self.raw_mpyr, H, W, 0)[0], self.occlusion, self.flags)
-                _, _, mpyr = occlude(self.code, self.flags, self.levels, out[t], hidden[t], self.mpyr[k])
-                k ^= 1
-            src = pyr
-
-
 def propagate_masks_visible(images, mask, key_frame=0, levels=4, search=2, smooth=8, occlusion=DEFAULT_OCCLUSION):
     """`mask`, painted on frame `key_frame` of `images` [F, H, W, C], followed through every frame and kept off what passes in
     front of it (module docstring): (mask, hidden), fp32 [F, H, W] each, on the images' device.  No device -> host read."""
@@ -118,10 +85,4 @@ def propagate_masks_visible(images, mask, key_frame=0, levels=4, search=2, smoot
     int_in(key_frame, 0, F - 1, "key_frame")
     if occlusion == 0:
         return propagate.propagate_masks(images, mask, key_frame, levels, search, smooth), images.new_zeros((F, H, W), dtype=torch.float32)
-    key_pyr, out, orders = key_and_orders(images, mask, key_frame, levels)
-    hidden = torch.empty_like(out)
-    hidden[key_frame].zero_()
-    step = VisibleStep(H, W, levels, search, smooth, occlusion, images.device)
-    for order in orders:
-        step.chain(chain_frames(images, order, levels), key_pyr, out, hidden)
-    return out, hidden
+    return propagate.run(images, mask, key_frame, levels, search, smooth, split=(visible_flags, occlude, occlusion))

@@ -16,6 +16,7 @@ from __future__ import annotations
 
 from . import propagate_visible as _visible
 from ._hostcall import node_device
+from .propagate_nodes import MATCHER_WIDGETS
 
 
 class LanPaint_VideoMaskPropagateVisible:
@@ -30,15 +31,7 @@ class LanPaint_VideoMaskPropagateVisible:
             "key_frame": ("INT", {"default": 0, "min": 0, "max": 65534, "step": 1,
                                   "tooltip": "The frame the mask was painted on. The mask is carried forwards and backwards "
                                              "from it, and every frame is compared with this frame's picture."}),
-            "levels": ("INT", {"default": 4, "min": 1, "max": 6, "step": 1,
-                               "tooltip": "Pyramid levels of the motion search. Every level doubles the motion per frame that can "
-                                          "be followed: about search * 2^levels pixels."}),
-            "search": ("INT", {"default": 2, "min": 1, "max": 7, "step": 1,
-                               "tooltip": "Pixels searched around the coarser level's motion at every level. More follows "
-                                          "faster or less regular motion and costs time with its square."}),
-            "smooth": ("INT", {"default": 8, "min": 0, "max": 64, "step": 1,
-                               "tooltip": "The price of a pixel of displacement in the match, in grey levels summed over a block: "
-                                          "keeps flat, textureless areas from drifting. 0 switches it off."}),
+            **MATCHER_WIDGETS,
             "occlusion": ("INT", {"default": _visible.DEFAULT_OCCLUSION, "min": 0, "max": _visible.MAX_OCCLUSION, "step": 1,
                                   "tooltip": "How far, in grey levels averaged over a block, the picture under the mask may differ "
                                              "from the key frame's before the block counts as covered. Lower hides more and starts "

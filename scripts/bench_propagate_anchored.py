@@ -91,7 +91,7 @@ def stage_times(job, reps):
     out = {}
     pyr = propagate.luma_pyramids(job["images"][:2], LEVELS)
     mpyr, _ = propagate.key_mask(job["mask"], LEVELS)
-    step = pa.AnchoredStep(H, W, LEVELS, SEARCH, SMOOTH, ANCHOR, job["images"].device)
+    step = propagate.Step(H, W, LEVELS, SEARCH, SMOOTH, job["images"].device, rematch=(pa.anchor_field, ANCHOR, SMOOTH))
     step.field_of(pyr[0], pyr[1], mpyr)
     for lv in range(LEVELS - 1, -1, -1):
         parent = None if lv == LEVELS - 1 else step.field[lv + 1]

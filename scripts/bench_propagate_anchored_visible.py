@@ -111,7 +111,8 @@ def gate_times(job, reps, rounds, anchor=ANCHOR):
     F, H, W = job["shape"]
     pyr = propagate.luma_pyramids(job["images"][:2], LEVELS)
     mpyr, _ = propagate.key_mask(job["mask"], LEVELS)
-    step = pav.AnchoredVisibleStep(H, W, LEVELS, SEARCH, SMOOTH, anchor, OCCLUSION, job["images"].device)
+    step = propagate.Step(H, W, LEVELS, SEARCH, SMOOTH, job["images"].device, rematch=(pav.gated_anchor_field, anchor, SMOOTH, OCCLUSION),
+                          split=(pav.visible_flags, pav.occlude, OCCLUSION))
     vec = step.field_of(pyr[0], pyr[1], mpyr)
     key_bits = propagate.level_view(mpyr, H, W, 0)[0]
     propagate.advance(vec, None, key_bits, LEVELS, step.raw_pos, step.code, step.raw_mpyr)

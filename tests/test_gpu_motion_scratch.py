@@ -12,14 +12,16 @@ against its numpy restatement -- bit for bit, NaN matching NaN in the fills and 
 vector, a position map, a carried origin's frame, a field), and both values stay next to the buffer should one ever be used raw.
 """
 import functools
+import json
+import os
 import time
 
 import numpy as np
 import pytest
 import torch
 
-from lanpaint_amd import (_cabi, propagate, propagate_anchored, propagate_keys, propagate_keys_visible, propagate_visible, shots,
-                          temporal_fill, temporal_fill_checked, temporal_smooth, temporal_smooth_robust)
+from lanpaint_amd import (_cabi, propagate, propagate_anchored, propagate_anchored_visible, propagate_keys, propagate_keys_visible,
+                          propagate_visible, shots, temporal_fill, temporal_fill_checked, temporal_smooth, temporal_smooth_robust)
 from tests import propagate_anchored_ref as aref
 from tests import propagate_keys_ref as kref
 from tests import propagate_keys_visible_ref as kvref
@@ -40,7 +42,7 @@ from tests import test_gpu_temporal_fill as t_fill
 from tests import test_gpu_temporal_fill_checked as t_checked
 from tests import test_gpu_temporal_smooth as t_smooth
 from tests import test_gpu_temporal_smooth_robust as t_robust
-from tests.helpers import record_launches
+from tests.helpers import GOLDEN_DIR, record_launches
 from tests.poison import poisoned_empty
 from tests.test_gpu_propagate import _dev, _disc, _levels_of, _rng, _same, _same_bits, _video
 from tests.test_gpu_temporal_fill import _random_masks
@@ -204,6 +206,48 @@ def test_the_call_under_poison_equals_the_restatement(call, plane, levels, mode,
     lumas = names.count("lp_prop_luma")
     assert lumas <= 2 if mode == "whole" else lumas >= 5, (mode, lumas)
     _compare(call, got, want, (call, plane, levels, mode, poison_id(poison)))
+
+
+# ---- B: what each single-key form allocates ------------------------------------------------------------------------------------------------
+# The four forms run on one step class with the refinements as options; each has to get the buffers it had as a class of its own and
+# no more: the plain form no code, raw_mpyr, raw_pos, flags or gate, the visible form no raw_pos.  The lists are the record of the
+# last commit that had the four classes, taken on the MI355X (CHANGES.md has the command).
+SINGLE_KEY_CALLS = {
+    "propagate_masks": lambda images, mask: propagate.propagate_masks(images, mask, KEY, 3, SEARCH, SMOOTH),
+    "propagate_masks_visible": lambda images, mask: propagate_visible.propagate_masks_visible(images, mask, KEY, 3, SEARCH, SMOOTH),
+    "propagate_masks_anchored": lambda images, mask: propagate_anchored.propagate_masks_anchored(images, mask, KEY, 3, SEARCH, SMOOTH),
+    "propagate_masks_anchored_visible":
+        lambda images, mask: propagate_anchored_visible.propagate_masks_anchored_visible(images, mask, KEY, 3, SEARCH, SMOOTH),
+}
+SCRATCH_FIXTURE = os.path.join(GOLDEN_DIR, "propagate_scratch_bytes.json")
+
+
+def scratch_bytes(call, monkeypatch):
+    """The sorted byte counts of every buffer the single-key form `call` takes through `torch.empty` / `torch.empty_like` on the
+    7-frame fp32 clip of (23, 33), key frame 3, 3 levels, the caps as they are."""
+    images, disc, _, _ = _device_inputs(SMALL, "whole")
+    filled = poisoned_empty(monkeypatch, 0xFF)
+    SINGLE_KEY_CALLS[call](images, disc)
+    torch.cuda.synchronize()
+    return sorted(filled)
+
+
+def record_scratch_bytes():
+    """What SCRATCH_FIXTURE holds, from whichever lanpaint_amd is first on the path."""
+    record = {}
+    for call in SINGLE_KEY_CALLS:
+        with pytest.MonkeyPatch.context() as patch:
+            record[call] = scratch_bytes(call, patch)
+    return record
+
+
+@pytest.mark.parametrize("call", list(SINGLE_KEY_CALLS))
+def test_each_single_key_form_allocates_what_it_did_as_a_class_of_its_own(call, monkeypatch):
+    with open(SCRATCH_FIXTURE) as f:
+        want = json.load(f)[call]
+    got = scratch_bytes(call, monkeypatch)
+    print(f"{call}: {len(got)} buffers, {sum(got)} bytes; recorded {len(want)} buffers, {sum(want)} bytes")
+    assert got == want, (call, got, want)
 
 
 # ---- B: the stage functions that allocate their own results, fed as their suites feed them, at (23, 33) -----------------------------------

@@ -236,7 +236,11 @@ def test_propagate_anchored_visible_refuses_cpu_tensors_and_bad_arguments():
         with pytest.raises(ValueError):
             pav.gated_anchor_field(pos, u8, u8, u8, **bad)
     assert pav.DEFAULT_ANCHOR == 2 and pav.MAX_ANCHOR == 7 and pav.DEFAULT_OCCLUSION == 16 and pav.MAX_OCCLUSION == 255
-    assert issubclass(pav.AnchoredVisibleStep, pav.Step)
+    from lanpaint_amd import propagate, propagate_anchored, propagate_visible
+    for module in (pav, propagate_anchored, propagate_visible):        # one step and one chain loop, propagate's, behind every form
+        assert module.Step is propagate.Step
+        assert not [n for n, v in vars(module).items() if isinstance(v, type) and v.__module__ == module.__name__], module
+        assert not hasattr(module, "chain") and "def chain" not in open(module.__file__).read(), module
     for word in ("a subject hidden entirely", "what leaves the picture", "occlusion edges finer than a block", "several keys",
                  "a subject whose look changes away from the key"):
         assert word in pav.__doc__, word
