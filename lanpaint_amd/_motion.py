@@ -47,10 +47,11 @@ def check_images(images):
     return images
 
 
-def check_frame_planes(pos, tgt, key, mask_bits, module):
+def check_frame_planes(pos, tgt, key, mask_bits, module, plane=(None, None)):
     """What the stages that hold a frame against the warped key frame take: `tgt`, `key` and `mask_bits` uint8 [H, W] of one
-    plane within the limits, `pos` int32 [H, W, 2].  (H, W); `module` is the caller's __name__."""
-    H, W = tensor_is(tgt, torch.uint8, (None, None), "tgt", module).shape
+    plane within the limits (of `plane`, where a batch's first job has set it), `pos` int32 [H, W, 2].  (H, W); `module` is the
+    caller's __name__."""
+    H, W = tensor_is(tgt, torch.uint8, plane, "tgt", module).shape
     check_plane(H, W)
     tensor_is(key, torch.uint8, (H, W), "key", module)
     tensor_is(mask_bits, torch.uint8, (H, W), "mask_bits", module)

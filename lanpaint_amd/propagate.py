@@ -53,21 +53,28 @@ def key_mask(mask, levels):
     return mpyr.view(1, -1), out
 
 
-def match_level(src, tgt, mpyr, H, W, levels, level, search=2, smooth=8, parent=None, vec=None, valid=None):
-    """The match of one level of one step: `src`, `tgt` one frame's luma pyramid each, `mpyr` the source frame's mask pyramid,
-    `parent` the level above's final field (None exactly at the top level).  (vec int32 [gh, gw, 2], valid int32 [gh, gw])."""
+def check_match(src, tgt, mpyr, parent, H, W, levels, level, search, smooth, module):
+    """The argument block of a match of one level, single or one job of a batch: the numbers first, then one frame's pyramid
+    each, [stride] or [1, stride], and `parent` exactly below the top level.  The level's grid; `module` is the caller's
+    __name__."""
     check_params(levels, search, smooth)
     int_in(level, 0, levels - 1, "level")
     check_plane(H, W)
     stride = _cabi.prop_pyramid_ws_bytes(1, H, W, levels)
-    for t, what in ((src, "src"), (tgt, "tgt"), (mpyr, "mpyr")):               # one frame's pyramid, [stride] or [1, stride]
-        if tensor_is(t, torch.uint8, t.shape, what, __name__).numel() != stride:
+    for t, what in ((src, "src"), (tgt, "tgt"), (mpyr, "mpyr")):
+        if tensor_is(t, torch.uint8, t.shape, what, module).numel() != stride:
             raise ValueError(f"{what} holds {t.numel()} bytes, a {H}x{W} pyramid of {levels} levels {stride}")
     if (parent is None) != (level == levels - 1):
         raise ValueError("parent is given exactly below the top level")
-    gh, gw = _cabi.prop_grid(H, W, level)
     if parent is not None:
-        tensor_is(parent, torch.int32, (*_cabi.prop_grid(H, W, level + 1), 2), "parent", __name__)
+        tensor_is(parent, torch.int32, (*_cabi.prop_grid(H, W, level + 1), 2), "parent", module)
+    return _cabi.prop_grid(H, W, level)
+
+
+def match_level(src, tgt, mpyr, H, W, levels, level, search=2, smooth=8, parent=None, vec=None, valid=None):
+    """The match of one level of one step: `src`, `tgt` one frame's luma pyramid each, `mpyr` the source frame's mask pyramid,
+    `parent` the level above's final field (None exactly at the top level).  (vec int32 [gh, gw, 2], valid int32 [gh, gw])."""
+    gh, gw = check_match(src, tgt, mpyr, parent, H, W, levels, level, search, smooth, __name__)
     dev = src.device
     vec = torch.empty((gh, gw, 2), dtype=torch.int32, device=dev) if vec is None else vec
     valid = torch.empty((gh, gw), dtype=torch.int32, device=dev) if valid is None else valid
@@ -77,25 +84,39 @@ def match_level(src, tgt, mpyr, H, W, levels, level, search=2, smooth=8, parent=
     return vec, valid
 
 
+def check_field(vec, valid, module, grid=(None, None)):
+    """The argument block of a fill, single or one job of a batch: `vec` int32 [gh, gw, 2] and `valid` int32 [gh, gw], of `grid`
+    where a batch's first job has set it.  (gh, gw)."""
+    grid = tensor_is(vec, torch.int32, (*grid, 2), "vec", module).shape[:2]
+    tensor_is(valid, torch.int32, grid, "valid", module)
+    return grid
+
+
 def fill_median(vec, valid, out=None):
     """Fill and median of one level's field: int32 [gh, gw, 2].  One launch."""
-    tensor_is(vec, torch.int32, (None, None, 2), "vec", __name__)
-    tensor_is(valid, torch.int32, vec.shape[:2], "valid", __name__)
+    gh, gw = check_field(vec, valid, __name__)
     out = torch.empty_like(vec) if out is None else out
-    launch("lp_prop_fill", vec.device, vec.data_ptr(), valid.data_ptr(), vec.shape[0], vec.shape[1], out.data_ptr())
+    launch("lp_prop_fill", vec.device, vec.data_ptr(), valid.data_ptr(), gh, gw, out.data_ptr())
     return out
+
+
+def check_advance(vec, pos, key_bits, levels, module, plane=(None, None)):
+    """The argument block of an advance, single or one job of a batch: `levels` first, then `key_bits` uint8 [H, W] (of `plane`
+    where a batch's first job has set it), `vec` level 0's field of that plane, `pos` int32 [H, W, 2] or None.  (H, W)."""
+    int_in(levels, 1, MAX_LEVELS, "levels")
+    require_hip(vec, "vec", module)
+    H, W = tensor_is(key_bits, torch.uint8, plane, "key_bits", module).shape
+    check_plane(H, W)
+    tensor_is(vec, torch.int32, (*_cabi.prop_grid(H, W), 2), "vec", module)
+    if pos is not None:
+        tensor_is(pos, torch.int32, (H, W, 2), "pos", module)
+    return H, W
 
 
 def advance(vec, pos, key_bits, levels, pos_out=None, out=None, mpyr_out=None):
     """The advance of one step: `vec` level 0's final field, `pos` the source frame's positions int32 [H, W, 2] (None: the key
     frame's), `key_bits` uint8 [H, W].  (positions of t, mask of t fp32 [H, W], the pyramid of its bits uint8 [1, stride])."""
-    int_in(levels, 1, MAX_LEVELS, "levels")
-    require_hip(vec, "vec", __name__)
-    H, W = tensor_is(key_bits, torch.uint8, (None, None), "key_bits", __name__).shape
-    check_plane(H, W)
-    tensor_is(vec, torch.int32, (*_cabi.prop_grid(H, W), 2), "vec", __name__)
-    if pos is not None:
-        tensor_is(pos, torch.int32, (H, W, 2), "pos", __name__)
+    H, W = check_advance(vec, pos, key_bits, levels, __name__)
     dev = vec.device
     pos_out = torch.empty((H, W, 2), dtype=torch.int32, device=dev) if pos_out is None else pos_out
     out = torch.empty((H, W), dtype=torch.float32, device=dev) if out is None else out

@@ -32,7 +32,7 @@ import torch
 from . import _cabi, stabilize
 from ._hostcall import int_in, launch, require_hip, tensor_is
 from ._motion import MAX_JOBS, FieldWalk, check_images, check_params, check_plane, luma_pyramids, row_addresses
-from .propagate import key_mask
+from .propagate import check_advance, check_field, check_match, key_mask
 
 WS_CAP_BYTES = 1 << 30
 
@@ -69,41 +69,23 @@ def job_table(rows, what):
 def match_level_batch(jobs, H, W, levels, level, search=2, smooth=8):
     """`propagate.match_level` for several independent steps in one launch.  `jobs`: per job (src, tgt, mpyr, parent) as there,
     `parent` None exactly at the top level.  A list of (vec int32 [gh, gw, 2], valid int32 [gh, gw])."""
-    check_params(levels, search, smooth)
-    int_in(level, 0, levels - 1, "level")
-    check_plane(H, W)
-    stride = _cabi.prop_pyramid_ws_bytes(1, H, W, levels)
-    gh, gw = _cabi.prop_grid(H, W, level)
-    rows, outs = [], []
-    for src, tgt, mpyr, parent in jobs:
-        for t, what in ((src, "src"), (tgt, "tgt"), (mpyr, "mpyr")):
-            if tensor_is(t, torch.uint8, t.shape, what, __name__).numel() != stride:
-                raise ValueError(f"{what} must be one frame's pyramid: {stride} contiguous uint8")
-        if (parent is None) != (level == levels - 1):
-            raise ValueError("parent is given exactly below the top level")
-        if parent is not None:
-            tensor_is(parent, torch.int32, (*_cabi.prop_grid(H, W, level + 1), 2), "parent", __name__)
-        vec = torch.empty((gh, gw, 2), dtype=torch.int32, device=src.device)
-        valid = torch.empty((gh, gw), dtype=torch.int32, device=src.device)
-        rows.append((src, tgt, mpyr, parent, vec, valid))
-        outs.append((vec, valid))
+    for job in jobs:
+        gh, gw = check_match(*job, H, W, levels, level, search, smooth, __name__)
+    rows = [(*job, torch.empty((gh, gw, 2), dtype=torch.int32, device=job[0].device),
+             torch.empty((gh, gw), dtype=torch.int32, device=job[0].device)) for job in jobs]
     table = job_table(rows, "match_level_batch")
     d = _cabi.LpPropMatchBatchDesc(H, W, levels, level, search, smooth, len(rows), 0, table.ctypes.data)
     launch("lp_prop_match_batch", rows[0][0].device, ctypes.byref(d))
-    return outs
+    return [r[4:] for r in rows]
 
 
 def fill_median_batch(jobs):
     """`propagate.fill_median` for several fields of one grid in one launch.  `jobs`: per job (vec, valid).  A list of fields."""
-    rows = []
+    grid = (None, None)
     for vec, valid in jobs:
-        require_hip(vec, "vec", __name__)
-        grid = tuple(rows[0][0].shape[:2] if rows else vec.shape[:2])    # the first job's grid is every job's
-        tensor_is(vec, torch.int32, (*grid, 2), "vec", __name__)
-        tensor_is(valid, torch.int32, grid, "valid", __name__)
-        rows.append((vec, valid, torch.empty_like(vec)))
+        gh, gw = grid = check_field(vec, valid, __name__, grid)     # the first job's grid is every job's
+    rows = [(vec, valid, torch.empty_like(vec)) for vec, valid in jobs]
     table = job_table(rows, "fill_median_batch")
-    gh, gw = rows[0][0].shape[:2]
     launch("lp_prop_fill_batch", rows[0][0].device, table.ctypes.data, len(rows), gh, gw)
     return [r[2] for r in rows]
 
@@ -111,25 +93,18 @@ def fill_median_batch(jobs):
 def advance_batch(jobs, levels):
     """`propagate.advance` for several independent steps of one plane in one launch.  `jobs`: per job (vec, pos, key_bits), `pos`
     None for the key frame's positions.  A list of (positions, mask fp32 [H, W], the pyramid of its bits uint8 [1, stride])."""
-    int_in(levels, 1, _cabi.LP_PROP_MAX_LEVELS, "levels")
-    rows, outs = [], []
-    for vec, pos, key_bits in jobs:
-        require_hip(vec, "vec", __name__)
-        H, W = tensor_is(key_bits, torch.uint8, rows[0][2].shape if rows else (None, None), "key_bits", __name__).shape   # one plane
-        check_plane(H, W)
-        tensor_is(vec, torch.int32, (*_cabi.prop_grid(H, W), 2), "vec", __name__)
-        if pos is not None:
-            tensor_is(pos, torch.int32, (H, W, 2), "pos", __name__)
-        dev = vec.device
-        new = (torch.empty((H, W, 2), dtype=torch.int32, device=dev), torch.empty((H, W), dtype=torch.float32, device=dev),
-               torch.empty((1, _cabi.prop_pyramid_ws_bytes(1, H, W, levels)), dtype=torch.uint8, device=dev))
-        rows.append((vec, pos, key_bits, *new))
-        outs.append(new)
+    plane = (None, None)
+    for job in jobs:
+        H, W = plane = check_advance(*job, levels, __name__, plane)  # the first job's plane is every job's
+
+    def new(dev):
+        return (torch.empty((H, W, 2), dtype=torch.int32, device=dev), torch.empty((H, W), dtype=torch.float32, device=dev),
+                torch.empty((1, _cabi.prop_pyramid_ws_bytes(1, H, W, levels)), dtype=torch.uint8, device=dev))
+    rows = [(*job, *new(job[0].device)) for job in jobs]
     table = job_table(rows, "advance_batch")
-    H, W = rows[0][2].shape
     d = _cabi.LpPropAdvanceBatchDesc(H, W, levels, len(rows), table.ctypes.data)
     launch("lp_prop_advance_batch", rows[0][0].device, ctypes.byref(d))
-    return outs
+    return [r[3:] for r in rows]
 
 
 def merge_gap(qa, qb, span, first=1, out=None):
@@ -162,14 +137,76 @@ def clip_pyramids(images, levels):
     return luma_pyramids(images, levels, torch.empty((F, stride), dtype=torch.uint8, device=images.device), WS_CAP_BYTES)
 
 
-class Chains:
-    """What outlives a step of the chains of a call -- per chain two position maps and two mask pyramids, and the addresses of
-    its key, its frames' luma and its outputs -- and the advance's job table.  The fields are scratch within a step: they are
-    the rows of a `FieldWalk`, which belong to the j-th chain of the group being launched.  A table is a host uint64 array of
-    device addresses; step s of chain c reads and writes at addresses that are linear in s or alternate with its parity, so a
-    step fills columns with a few numpy operations and allocates nothing on the device."""
+class Gaps:
+    """Where the chains of a call write.  `pairs`: the key pairs (a, b) that have frames between them; `first[a, b]`: the gap's
+    first row in a stack of all in-between frames, gap after gap; `between`: their number.  The other methods say where step s of
+    a chain of `chain_plan` goes in a contiguous tensor, as (address, byte step): address + s * step, the step signed."""
 
-    def __init__(self, plan, pyr, key_pyrs, outs, H, W, levels, search, smooth):
+    def __init__(self, keys):
+        self.keys = keys
+        self.pairs = [(a, b) for a, b in zip(keys, keys[1:]) if b - a > 1]
+        self.first, self.between = {}, 0
+        for a, b in self.pairs:
+            self.first[a, b] = self.between
+            self.between += b - a - 1
+
+    def of(self, chain):
+        """The gap a chain runs in; None for an edge chain, in front of the first or behind the last key."""
+        i, k, d, _ = chain
+        if d > 0 and i < len(self.keys) - 1:
+            return k, self.keys[i + 1]
+        return (self.keys[i - 1], k) if d < 0 and i > 0 else None
+
+    def stacked(self, t, chain):
+        """A gap's chain in `t` [between, ...]: the forward chain's frame a + s is row first + s - 1, the backward chain's frame
+        b - s is row first + length - s."""
+        _, _, d, length = chain
+        row = t.stride(0) * t.element_size()
+        return t.data_ptr() + (self.first[self.of(chain)] + (-1 if d > 0 else length)) * row, d * row
+
+    @staticmethod
+    def in_place(t, chain):
+        """Frame k + d s is row k + d s of `t` [F, ...]: a gap's forward chain or an edge chain in one of the call's outputs."""
+        _, k, d, _ = chain
+        row = t.stride(0) * t.element_size()
+        return t.data_ptr() + k * row, d * row
+
+    @staticmethod
+    def fixed(t, r):
+        """Every step at row `r` of `t`: what only the next launch reads."""
+        return t[r].data_ptr(), 0
+
+
+def _linear(column):
+    """A column of per-chain (address, byte step) as two int64 arrays."""
+    return np.array([c[0] for c in column], dtype=np.int64), np.array([c[1] for c in column], dtype=np.int64)
+
+
+class Chains:
+    """What outlives a step of the chains of a call, and the job tables of a step's launches.  A table is a host uint64 array of
+    device addresses; step s of chain c reads and writes at addresses that are linear in s or alternate with its parity, so a
+    step fills columns with a few numpy operations and allocates nothing on the device.  `outs`: per chain the (address, byte
+    step) of where step s writes its mask.  The occlusion-aware form is an option, off by default, handed in by the module that
+    owns it: `split` = (occlusion, mask, hidden, flags, counts), the last four per-chain (address, byte step) columns of where
+    step s writes the visible part, the hidden part, the block flags and the number of visible bits (address 0: not counted);
+    `outs` then says where the advance's code goes.  With it a group's launches are the walk, the advance, lp_prop_visible_batch
+    and lp_prop_occlude_batch; without it, the walk and the advance.  Which buffer serves what:
+      - `pos` and `mpyr`, two position maps and two mask pyramids per chain, alternate with the step's parity: step s reads
+        [(s - 1) & 1] and writes [s & 1]; step 1 reads a null position map (the key frame's) and the key's own pyramid;
+      - the advance writes the pyramid of its mask's bits to mpyr[s & 1], the next step's weights.  With the option it writes
+        it to `raw_mpyr`, a buffer per chain that comes with the option, where the flags read the bits; occlude then writes the
+        next step's weights, the visible part's bits, to mpyr[s & 1], never to raw_mpyr;
+      - the fields are scratch within a step: they are the rows of a `FieldWalk`, which belong to the j-th chain of the group
+        being launched, not to a chain of the plan;
+      - the key frame's luma is level 0 of its pyramid in `pyr`, which the clip holds whole;
+      - `count_keys` runs the occlude launch before step 1 and needs three outputs per chain that nobody reads: it scribbles on
+        pos[0], on mpyr[0] and on the chain's `hidden` base address.  Step 1 reads none of them (its positions are null, its
+        weights the key's) and writes pos[1] and mpyr[1]; step 2 overwrites pos[0] and mpyr[0] before step 3 reads them; and
+        the hidden base, address + 0 * step, is a fixed scratch row that every step's occlude rewrites (a gap's chain; only
+        gaps' chains are counted).
+    The plain form allocates no raw_mpyr, no visible or occlude table and no descriptor for them."""
+
+    def __init__(self, plan, pyr, key_pyrs, outs, H, W, levels, search, smooth, split=None):
         dev = pyr.device
         self.dev = dev
         self.length = np.array([c[3] for c in plan], dtype=np.int64)
@@ -179,14 +216,22 @@ class Chains:
         self.pos = [self._buffers((H, W, 2), torch.int32) for _ in range(2)]
         self.mpyr = [self._buffers((stride,), torch.uint8) for _ in range(2)]
         self.key = np.array([key_pyrs[c[0]].data_ptr() for c in plan], dtype=np.uint64)
-        # frame k + d s of the clip's pyramids, and where step s writes its mask: both base + s * step, the step signed
-        self.luma0 = np.array([pyr.data_ptr() + c[1] * stride for c in plan], dtype=np.int64)
-        self.luma_step = np.array([c[2] * stride for c in plan], dtype=np.int64)
-        self.out0 = np.array([o[0] for o in outs], dtype=np.int64)
-        self.out_step = np.array([o[1] for o in outs], dtype=np.int64)
-        self.t_advance = np.zeros((len(self.walk.field0), 6), dtype=np.uint64)
+        # frame k + d s of the clip's pyramids, and where step s writes: both base + s * step, the step signed
+        self.luma = _linear([(pyr.data_ptr() + c[1] * stride, c[2] * stride) for c in plan])
+        self.out = _linear(outs)
+        m = len(self.walk.field0)
+        self.t_advance = np.zeros((m, 6), dtype=np.uint64)
         self.t_advance[:, 0] = self.walk.field0
-        self.advance_desc = _cabi.LpPropAdvanceBatchDesc(H, W, levels, 0, self.t_advance.ctypes.data)
+        self.launches = [("lp_prop_advance_batch", _cabi.LpPropAdvanceBatchDesc(H, W, levels, 0, self.t_advance.ctypes.data))]
+        self.lin = None
+        if split:
+            occlusion, *columns = split
+            self.raw_mpyr = self._buffers((stride,), torch.uint8)
+            self.lin = [_linear(column) for column in columns]
+            self.t_visible, self.t_occlude = np.zeros((m, 5), dtype=np.uint64), np.zeros((m, 6), dtype=np.uint64)
+            self.occlude_desc = _cabi.LpPropOccludeBatchDesc(H, W, levels, 0, self.t_occlude.ctypes.data)
+            self.launches += [("lp_prop_visible_batch", _cabi.LpPropVisibleBatchDesc(H, W, occlusion, 0, self.t_visible.ctypes.data)),
+                              ("lp_prop_occlude_batch", self.occlude_desc)]
 
     def _buffers(self, shape, dtype):
         """One buffer of `shape` per chain: their addresses."""
@@ -194,7 +239,7 @@ class Chains:
         return row_addresses(self._keep[-1], len(self.length))
 
     def step(self, s):
-        """Step s of every chain that has one: 2 levels + 1 launches per MAX_JOBS chains."""
+        """Step s of every chain that has one: 2 levels + 1 launches per MAX_JOBS chains, + 2 with the option."""
         idx = np.flatnonzero(self.length >= s)
         for lo in range(0, len(idx), MAX_JOBS):
             self._bind(s, idx[lo:lo + MAX_JOBS])
@@ -203,19 +248,40 @@ class Chains:
     def _bind(self, s, idx):
         """The tables' rows 0 .. len(idx) - 1 for step s of the chains `idx`, one group."""
         n = len(idx)
-        self.luma = (self.luma0[idx] + s * self.luma_step[idx]).astype(np.uint64)        # the frame the step arrives at
-        self.jobs = ((self.luma0[idx] + (s - 1) * self.luma_step[idx]).astype(np.uint64), self.luma,
-                     self.key[idx] if s == 1 else self.mpyr[(s - 1) & 1][idx])
+
+        def at(lin, s=s):
+            return (lin[0][idx] + s * lin[1][idx]).astype(np.uint64)
+        luma = at(self.luma)                                         # the frame the step arrives at
+        self.jobs = (at(self.luma, s - 1), luma, self.key[idx] if s == 1 else self.mpyr[(s - 1) & 1][idx])
         a = self.t_advance
         a[:n, 1] = 0 if s == 1 else self.pos[(s - 1) & 1][idx]
-        a[:n, 2], a[:n, 3], a[:n, 5] = self.key[idx], self.pos[s & 1][idx], self.mpyr[s & 1][idx]
-        a[:n, 4] = (self.out0[idx] + s * self.out_step[idx]).astype(np.uint64)
+        a[:n, 2], a[:n, 3], a[:n, 4] = self.key[idx], self.pos[s & 1][idx], at(self.out)
+        a[:n, 5] = self.raw_mpyr[idx] if self.lin else self.mpyr[s & 1][idx]
+        if self.lin:
+            mask, hidden, flags, count = map(at, self.lin)
+            v, o = self.t_visible, self.t_occlude
+            v[:n, 0], v[:n, 1], v[:n, 2], v[:n, 3], v[:n, 4] = a[:n, 3], luma, at(self.luma, 0), a[:n, 5], flags
+            o[:n, 0], o[:n, 1], o[:n, 2], o[:n, 3], o[:n, 4], o[:n, 5] = a[:n, 4], flags, mask, hidden, self.mpyr[s & 1][idx], count
 
     def _launch(self, n):
         """The launches of the group of `n` chains that was bound."""
         self.walk.run(*self.jobs)
-        self.advance_desc.jobs = n
-        launch("lp_prop_advance_batch", self.dev, ctypes.byref(self.advance_desc))
+        for entry, desc in self.launches:
+            desc.jobs = n
+            launch(entry, self.dev, ctypes.byref(desc))
+
+    def count_keys(self, painted, zero_flags):
+        """With the option, before step 1: entry 0 of every counted chain's counts, the key's bits, counted by the occlude launch
+        on the key's binarised mask with no block flagged, through the occlude table in groups of MAX_JOBS.  `painted`: per
+        chain the key's fp32 bits.  What it writes besides is scribbled where the class's docstring says."""
+        (_, (hidden, _), _, (count, _)), pos, mpyr = self.lin, self.pos[0], self.mpyr[0]
+        rows = [(painted[c].data_ptr(), zero_flags.data_ptr(), int(pos[c]), int(hidden[c]), int(mpyr[c]), int(count[c]))
+                for c in np.flatnonzero(count)]
+        table = np.array(rows, dtype=np.uint64).reshape(len(rows), 6)
+        for lo in range(0, len(rows), MAX_JOBS):
+            n = self.occlude_desc.jobs = min(MAX_JOBS, len(rows) - lo)
+            self.t_occlude[:n] = table[lo:lo + n]
+            launch("lp_prop_occlude_batch", self.dev, ctypes.byref(self.occlude_desc))
 
 
 def _key_masks(masks, keys, F, H, W):
@@ -259,24 +325,14 @@ def propagate_keys(images, masks, key_frames, levels=4, search=2, smooth=8):
     if not plan:
         return out
     # a gap's forward chain writes into `out`, its backward chain into `back`; the merge then overwrites the gap's frames of `out`
-    gaps = [(a, b) for a, b in zip(keys, keys[1:]) if b - a > 1]
-    back = torch.empty((sum(b - a - 1 for a, b in gaps), H, W), dtype=torch.float32, device=dev)
-    back_at, n = {}, 0
-    for a, b in gaps:
-        back_at[b] = back[n:n + b - a - 1]
-        n += b - a - 1
-    plane = H * W * 4
-    outs = []
-    for i, k, d, length in plan:
-        if d < 0 and i > 0:                                          # frame k - s is row (k - s) - (k - length) of the gap's stack
-            outs.append((back_at[k].data_ptr() + length * plane, -plane))
-        else:
-            outs.append((out.data_ptr() + k * plane, d * plane))
+    gaps = Gaps(keys)
+    back = torch.empty((gaps.between, H, W), dtype=torch.float32, device=dev)
+    outs = [gaps.stacked(back, c) if c[2] < 0 and gaps.of(c) else gaps.in_place(out, c) for c in plan]
     pyr = clip_pyramids(images, levels)
     chains = Chains(plan, pyr, key_pyrs, outs, H, W, levels, search, smooth)
     for s in range(1, int(chains.length.max()) + 1):
         chains.step(s)
-    for a, b in gaps:
-        mid = out[a + 1:b]
-        merge_gap(stabilize.signed_d2(mid), stabilize.signed_d2(back_at[b]), b - a, 1, mid)
+    for a, b in gaps.pairs:
+        mid, r = out[a + 1:b], gaps.first[a, b]
+        merge_gap(stabilize.signed_d2(mid), stabilize.signed_d2(back[r:r + b - a - 1]), b - a, 1, mid)
     return out

@@ -30,14 +30,13 @@ from __future__ import annotations
 
 import ctypes
 
-import numpy as np
 import torch
 
 from . import _cabi, propagate_keys, stabilize
 from ._hostcall import chunks, int_in, launch, require_hip, tensor_is
-from ._motion import MAX_JOBS, check_params, check_plane
-from .propagate_keys import Chains, chain_plan, clip_pyramids, job_table, painted_keys     # noqa: F401  (chain_plan: the node's)
-from .propagate_visible import DEFAULT_OCCLUSION, MAX_OCCLUSION
+from ._motion import MAX_JOBS, check_frame_planes, check_params, check_plane              # noqa: F401  (MAX_JOBS: this module's to export)
+from .propagate_keys import Chains, Gaps, chain_plan, clip_pyramids, job_table, painted_keys     # noqa: F401  (chain_plan: the node's)
+from .propagate_visible import DEFAULT_OCCLUSION, MAX_OCCLUSION, check_occlude
 
 WS_CAP_BYTES = 1 << 30
 
@@ -46,16 +45,11 @@ def visible_flags_batch(jobs, occlusion=DEFAULT_OCCLUSION):
     """`propagate_visible.visible_flags` for several independent steps of one plane in one launch.  `jobs`: per job (pos, tgt, key,
     mask_bits) as there.  A list of flags int32 [gh, gw]."""
     int_in(occlusion, 1, MAX_OCCLUSION, "occlusion")
-    rows = []
-    for pos, tgt, key, mask_bits in jobs:
-        H, W = tensor_is(tgt, torch.uint8, rows[0][1].shape if rows else (None, None), "tgt", __name__).shape
-        check_plane(H, W)
-        tensor_is(key, torch.uint8, (H, W), "key", __name__)
-        tensor_is(mask_bits, torch.uint8, (H, W), "mask_bits", __name__)
-        tensor_is(pos, torch.int32, (H, W, 2), "pos", __name__)
-        rows.append((pos, tgt, key, mask_bits, torch.empty(_cabi.prop_grid(H, W), dtype=torch.int32, device=tgt.device)))
+    plane = (None, None)
+    for job in jobs:
+        H, W = plane = check_frame_planes(*job, __name__, plane)    # the first job's plane is every job's
+    rows = [(*job, torch.empty(_cabi.prop_grid(H, W), dtype=torch.int32, device=job[1].device)) for job in jobs]
     table = job_table(rows, "visible_flags_batch")
-    H, W = rows[0][1].shape
     d = _cabi.LpPropVisibleBatchDesc(H, W, occlusion, len(rows), table.ctypes.data)
     launch("lp_prop_visible_batch", rows[0][1].device, ctypes.byref(d))
     return [r[4] for r in rows]
@@ -65,24 +59,21 @@ def occlude_batch(jobs, levels, counts=None):
     """`propagate_visible.occlude` for several independent steps of one plane in one launch.  `jobs`: per job (code, flags).
     `counts`, an int32 [jobs] tensor, receives += the number of visible bits per job.  A list of (mask, hidden, the pyramid of
     the visible bits)."""
-    int_in(levels, 1, _cabi.LP_PROP_MAX_LEVELS, "levels")
-    rows, outs = [], []
+    int_in(levels, 1, _cabi.LP_PROP_MAX_LEVELS, "levels")            # the number before `counts`, a tensor, is looked at
     if counts is not None:
         tensor_is(counts, torch.int32, (len(jobs),), "counts", __name__)
-    for i, (code, flags) in enumerate(jobs):
-        H, W = tensor_is(code, torch.float32, rows[0][0].shape if rows else (None, None), "code", __name__).shape
-        check_plane(H, W)
-        tensor_is(flags, torch.int32, _cabi.prop_grid(H, W), "flags", __name__)
-        dev = code.device
-        new = (torch.empty((H, W), dtype=torch.float32, device=dev), torch.empty((H, W), dtype=torch.float32, device=dev),
-               torch.empty((1, _cabi.prop_pyramid_ws_bytes(1, H, W, levels)), dtype=torch.uint8, device=dev))
-        rows.append((code, flags, *new, None if counts is None else counts[i:]))
-        outs.append(new)
+    plane = (None, None)
+    for job in jobs:
+        H, W = plane = check_occlude(*job, levels, __name__, plane)
+
+    def new(dev):
+        return (torch.empty((H, W), dtype=torch.float32, device=dev), torch.empty((H, W), dtype=torch.float32, device=dev),
+                torch.empty((1, _cabi.prop_pyramid_ws_bytes(1, H, W, levels)), dtype=torch.uint8, device=dev))
+    rows = [(*job, *new(job[0].device), None if counts is None else counts[i:]) for i, job in enumerate(jobs)]
     table = job_table(rows, "occlude_batch")
-    H, W = rows[0][0].shape
     d = _cabi.LpPropOccludeBatchDesc(H, W, levels, len(rows), table.ctypes.data)
     launch("lp_prop_occlude_batch", rows[0][0].device, ctypes.byref(d))
-    return outs
+    return [r[2:5] for r in rows]
 
 
 def merge_gap_visible(qa, qb, code_a, mask_a, code_b, mask_b, flags_a, flags_b, count_a, count_b, span, first=1, out=None, hidden=None):
@@ -112,50 +103,6 @@ def merge_gap_visible(qa, qb, code_a, mask_a, code_b, mask_b, flags_a, flags_b, 
     return out, hidden
 
 
-class VisibleChains(Chains):
-    """`propagate_keys.Chains` with the two launches of the occlusion-aware form behind every advance.  The advance's code goes
-    where `code` says (the base class's `outs`) and its pyramid to a buffer per chain; `mask`, `hidden`, `flags` and `count` say,
-    as (address, step in bytes) per chain, where step s writes the visible part, the hidden part, the flags and the number of
-    visible bits (address 0: not counted).  The key frame's luma is level 0 of its pyramid in `pyr`."""
-
-    def __init__(self, plan, pyr, key_pyrs, code, mask, hidden, flags, count, H, W, levels, search, smooth, occlusion):
-        super().__init__(plan, pyr, key_pyrs, code, H, W, levels, search, smooth)
-        self.raw_mpyr = self._buffers((pyr.shape[1],), torch.uint8)
-        self.lin = [(np.array([o[0] for o in col], dtype=np.int64), np.array([o[1] for o in col], dtype=np.int64))
-                    for col in (mask, hidden, flags, count)]
-        self.t_visible = np.zeros((len(self.t_advance), 5), dtype=np.uint64)
-        self.t_occlude = np.zeros((len(self.t_advance), 6), dtype=np.uint64)
-        self.visible_desc = _cabi.LpPropVisibleBatchDesc(H, W, occlusion, 0, self.t_visible.ctypes.data)
-        self.occlude_desc = _cabi.LpPropOccludeBatchDesc(H, W, levels, 0, self.t_occlude.ctypes.data)
-
-    def _bind(self, s, idx):
-        super()._bind(s, idx)
-        n = len(idx)
-        a, v, o = self.t_advance, self.t_visible, self.t_occlude
-        a[:n, 5] = self.raw_mpyr[idx]
-        at = [(base[idx] + s * step[idx]).astype(np.uint64) for base, step in self.lin]
-        v[:n, 0], v[:n, 1], v[:n, 2], v[:n, 3], v[:n, 4] = a[:n, 3], self.luma, self.luma0[idx].astype(np.uint64), a[:n, 5], at[2]
-        o[:n, 0], o[:n, 1], o[:n, 2], o[:n, 3], o[:n, 4], o[:n, 5] = a[:n, 4], at[2], at[0], at[1], self.mpyr[s & 1][idx], at[3]
-
-    def _launch(self, n):
-        super()._launch(n)
-        self.visible_desc.jobs = self.occlude_desc.jobs = n
-        launch("lp_prop_visible_batch", self.dev, ctypes.byref(self.visible_desc))
-        launch("lp_prop_occlude_batch", self.dev, ctypes.byref(self.occlude_desc))
-
-    def count_keys(self, painted, zero_flags):
-        """Entry 0 of every counted chain's counts: the key's bits, counted by the occlude launch on the key's binarised mask with
-        no block flagged.  `painted`: per chain the key's fp32 bits.  What it writes besides goes to buffers that step 1 or 2
-        overwrites before they are read: the chain's hidden scratch, a position map and a pyramid."""
-        rows = [(painted[c].data_ptr(), zero_flags.data_ptr(), int(self.pos[0][c]), int(self.lin[1][0][c]), int(self.mpyr[0][c]),
-                 int(self.lin[3][0][c])) for c in range(len(self.length)) if self.lin[3][0][c]]
-        table = np.array(rows, dtype=np.uint64).reshape(len(rows), 6)
-        for lo in range(0, len(rows), MAX_JOBS):                         # through the occlude table, a group at a time
-            n = self.occlude_desc.jobs = min(MAX_JOBS, len(rows) - lo)
-            self.t_occlude[:n] = table[lo:lo + n]
-            launch("lp_prop_occlude_batch", self.dev, ctypes.byref(self.occlude_desc))
-
-
 def propagate_keys_visible(images, masks, key_frames, levels=4, search=2, smooth=8, occlusion=DEFAULT_OCCLUSION):
     """The masks painted on the frames `key_frames` of `images` [F, H, W, C], followed through every frame, kept off what passes
     in front and merged between the keys (module docstring): (mask, hidden), fp32 [F, H, W] each, on the images' device.  No
@@ -169,8 +116,8 @@ def propagate_keys_visible(images, masks, key_frames, levels=4, search=2, smooth
     (F, H, W, _), dev = images.shape, images.device
     if not plan:
         return out, hidden
-    gaps = [(a, b) for a, b in zip(keys, keys[1:]) if b - a > 1]
-    between = sum(b - a - 1 for a, b in gaps)
+    gaps = Gaps(keys)
+    between = gaps.between
     gh, gw = _cabi.prop_grid(H, W)
     plane, cells = H * W * 4, gh * gw * 4
     kept = between * 2 * (plane + cells) + (len(plan) + 1) * (plane + cells)
@@ -181,43 +128,34 @@ def propagate_keys_visible(images, masks, key_frames, levels=4, search=2, smooth
     flags = torch.empty((2, between, gh, gw), dtype=torch.int32, device=dev)            # the forward and the backward chains'
     scratch = torch.empty((len(plan), H, W), dtype=torch.float32, device=dev)           # an edge chain's code, a gap chain's hidden
     scratch_flags = torch.empty((len(plan) + 1, gh, gw), dtype=torch.int32, device=dev)   # an edge chain's flags; the last: no flag
-    counts = torch.zeros(2 * sum(b - a for a, b in gaps), dtype=torch.int32, device=dev)     # per gap [span] forward, [span] backward
-    row_of, count_of, n, m = {}, {}, 0, 0
-    for a, b in gaps:
-        row_of[a, b], count_of[a, b] = n, m
-        n, m = n + b - a - 1, m + 2 * (b - a)
+    counts = torch.zeros(2 * sum(b - a for a, b in gaps.pairs), dtype=torch.int32, device=dev)   # per gap [span] forward, [span] backward
+    # a gap's counts lie behind those of the g gaps before it, which take 2 (b - a) = 2 (b - a - 1) + 2 each
+    count_of = {gap: 2 * (gaps.first[gap] + g) for g, gap in enumerate(gaps.pairs)}
     code, mask, hid, flag, count = [], [], [], [], []
-    for c, (i, k, d, length) in enumerate(plan):
-        tmp, tmp_flags = (scratch[c].data_ptr(), 0), (scratch_flags[c].data_ptr(), 0)
-        if d > 0 and i < len(keys) - 1:                              # a gap's forward chain: frame k + s, in place in the outputs
-            gap = (k, keys[i + 1])
-            code.append((hidden.data_ptr() + k * plane, plane))
-            mask.append((out.data_ptr() + k * plane, plane))
-            hid.append(tmp)
-            flag.append((flags[0, row_of[gap]].data_ptr() - cells, cells))
-            count.append((counts[count_of[gap]:].data_ptr(), 4))
-        elif d < 0 and i > 0:                                        # a gap's backward chain: frame k - s is row length - s of its stack
-            gap = (keys[i - 1], k)
-            code.append((back[0, row_of[gap]].data_ptr() + length * plane, -plane))
-            mask.append((back[1, row_of[gap]].data_ptr() + length * plane, -plane))
-            hid.append(tmp)
-            flag.append((flags[1, row_of[gap]].data_ptr() + length * cells, -cells))
-            count.append((counts[count_of[gap] + (k - gap[0]):].data_ptr(), 4))
-        else:                                                        # outside the keys: the chain's own output
+    for c, chain in enumerate(plan):
+        gap, forward = gaps.of(chain), chain[2] > 0
+        tmp = gaps.fixed(scratch, c)
+        if gap is None:                                              # outside the keys: the chain's own outputs, no count
             code.append(tmp)
-            mask.append((out.data_ptr() + k * plane, d * plane))
-            hid.append((hidden.data_ptr() + k * plane, d * plane))
-            flag.append(tmp_flags)
+            mask.append(gaps.in_place(out, chain))
+            hid.append(gaps.in_place(hidden, chain))
+            flag.append(gaps.fixed(scratch_flags, c))
             count.append((0, 0))
+        else:                                # a gap's forward chain in place in the outputs, its backward chain in the stacks
+            code.append(gaps.in_place(hidden, chain) if forward else gaps.stacked(back[0], chain))
+            mask.append(gaps.in_place(out, chain) if forward else gaps.stacked(back[1], chain))
+            hid.append(tmp)
+            flag.append(gaps.stacked(flags[0 if forward else 1], chain))
+            count.append((counts[count_of[gap] + (0 if forward else gap[1] - gap[0]):].data_ptr(), 4))
     pyr = clip_pyramids(images, levels)
-    chains = VisibleChains(plan, pyr, key_pyrs, code, mask, hid, flag, count, H, W, levels, search, smooth, occlusion)
-    if gaps:
+    chains = Chains(plan, pyr, key_pyrs, code, H, W, levels, search, smooth, split=(occlusion, mask, hid, flag, count))
+    if gaps.pairs:
         scratch_flags[-1].zero_()
         chains.count_keys([out[k] for _, k, _, _ in plan], scratch_flags[-1])
     for s in range(1, int(chains.length.max()) + 1):
         chains.step(s)
-    for a, b in gaps:
-        r, span = row_of[a, b], b - a
+    for a, b in gaps.pairs:
+        r, span = gaps.first[a, b], b - a
         count_a, count_b = counts[count_of[a, b]:][:span], counts[count_of[a, b] + span:][:span]
         for s, n in chunks(span - 1, 2 * plane, WS_CAP_BYTES):       # the two chains' distances of a chunk's frames
             code_a, mask_a = hidden[a + 1 + s:a + 1 + s + n], out[a + 1 + s:a + 1 + s + n]

@@ -56,13 +56,20 @@ def visible_flags(pos, tgt, key, mask_bits, occlusion=DEFAULT_OCCLUSION, out=Non
     return out
 
 
+def check_occlude(code, flags, levels, module, plane=(None, None)):
+    """The argument block of an occlude, single or one job of a batch: `levels` first, then `code` fp32 [H, W] (of `plane` where
+    a batch's first job has set it) and `flags` int32 on its level-0 grid.  (H, W); `module` is the caller's __name__."""
+    int_in(levels, 1, propagate.MAX_LEVELS, "levels")
+    H, W = tensor_is(code, torch.float32, plane, "code", module).shape
+    check_plane(H, W)
+    tensor_is(flags, torch.int32, _cabi.prop_grid(H, W), "flags", module)
+    return H, W
+
+
 def occlude(code, flags, levels, out=None, hidden=None, mpyr_out=None):
     """The advance's mask `code` fp32 [H, W] (c / 256) split by the blocks' `flags` int32 [gh, gw]: (the visible part, the hidden
     part, both fp32 [H, W], and the pyramid of the visible part's bits uint8 [1, stride]).  One launch."""
-    int_in(levels, 1, propagate.MAX_LEVELS, "levels")
-    H, W = tensor_is(code, torch.float32, (None, None), "code", __name__).shape
-    check_plane(H, W)
-    tensor_is(flags, torch.int32, _cabi.prop_grid(H, W), "flags", __name__)
+    H, W = check_occlude(code, flags, levels, __name__)
     dev = code.device
     out = torch.empty((H, W), dtype=torch.float32, device=dev) if out is None else out
     hidden = torch.empty((H, W), dtype=torch.float32, device=dev) if hidden is None else hidden

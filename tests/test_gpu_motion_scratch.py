@@ -208,10 +208,12 @@ def test_the_call_under_poison_equals_the_restatement(call, plane, levels, mode,
     _compare(call, got, want, (call, plane, levels, mode, poison_id(poison)))
 
 
-# ---- B: what each single-key form allocates ------------------------------------------------------------------------------------------------
-# The four forms run on one step class with the refinements as options; each has to get the buffers it had as a class of its own and
-# no more: the plain form no code, raw_mpyr, raw_pos, flags or gate, the visible form no raw_pos.  The lists are the record of the
-# last commit that had the four classes, taken on the MI355X (CHANGES.md has the command).
+# ---- B: what each propagate form allocates -------------------------------------------------------------------------------------------------
+# The four single-key forms run on one step class with the refinements as options; each has to get the buffers it had as a class of
+# its own and no more: the plain form no code, raw_mpyr, raw_pos, flags or gate, the visible form no raw_pos.  Their lists are the
+# record of the last commit that had the four classes, taken on the MI355X (CHANGES.md has the command).  The two several-keys
+# forms run on one chain class with the occlusion-aware form as an option, and the plain one has to get no raw_mpyr and no stack
+# but `back`: their lists are the record of the last commit that had `VisibleChains`, taken the same way.
 SINGLE_KEY_CALLS = {
     "propagate_masks": lambda images, mask: propagate.propagate_masks(images, mask, KEY, 3, SEARCH, SMOOTH),
     "propagate_masks_visible": lambda images, mask: propagate_visible.propagate_masks_visible(images, mask, KEY, 3, SEARCH, SMOOTH),
@@ -219,15 +221,22 @@ SINGLE_KEY_CALLS = {
     "propagate_masks_anchored_visible":
         lambda images, mask: propagate_anchored_visible.propagate_masks_anchored_visible(images, mask, KEY, 3, SEARCH, SMOOTH),
 }
+KEYS_CALLS = {
+    "propagate_keys": lambda images, keys: propagate_keys.propagate_keys(images, keys, list(KEYS), 3, SEARCH, SMOOTH),
+    "propagate_keys_visible": lambda images, keys: propagate_keys_visible.propagate_keys_visible(images, keys, list(KEYS), 3, SEARCH, SMOOTH),
+}
 SCRATCH_FIXTURE = os.path.join(GOLDEN_DIR, "propagate_scratch_bytes.json")
 
 
 def scratch_bytes(call, monkeypatch):
-    """The sorted byte counts of every buffer the single-key form `call` takes through `torch.empty` / `torch.empty_like` on the
-    7-frame fp32 clip of (23, 33), key frame 3, 3 levels, the caps as they are."""
-    images, disc, _, _ = _device_inputs(SMALL, "whole")
+    """The sorted byte counts of every buffer the form `call` takes through `torch.empty` / `torch.empty_like` on the 7-frame fp32
+    clip of (23, 33), key frame 3 or keys (1, 4), 3 levels, the caps as they are."""
+    images, disc, keys, _ = _device_inputs(SMALL, "whole")
     filled = poisoned_empty(monkeypatch, 0xFF)
-    SINGLE_KEY_CALLS[call](images, disc)
+    if call in KEYS_CALLS:
+        KEYS_CALLS[call](images, keys)
+    else:
+        SINGLE_KEY_CALLS[call](images, disc)
     torch.cuda.synchronize()
     return sorted(filled)
 
@@ -235,19 +244,28 @@ def scratch_bytes(call, monkeypatch):
 def record_scratch_bytes():
     """What SCRATCH_FIXTURE holds, from whichever lanpaint_amd is first on the path."""
     record = {}
-    for call in SINGLE_KEY_CALLS:
+    for call in (*SINGLE_KEY_CALLS, *KEYS_CALLS):
         with pytest.MonkeyPatch.context() as patch:
             record[call] = scratch_bytes(call, patch)
     return record
 
 
-@pytest.mark.parametrize("call", list(SINGLE_KEY_CALLS))
-def test_each_single_key_form_allocates_what_it_did_as_a_class_of_its_own(call, monkeypatch):
+def _allocates_what_was_recorded(call, monkeypatch):
     with open(SCRATCH_FIXTURE) as f:
         want = json.load(f)[call]
     got = scratch_bytes(call, monkeypatch)
     print(f"{call}: {len(got)} buffers, {sum(got)} bytes; recorded {len(want)} buffers, {sum(want)} bytes")
     assert got == want, (call, got, want)
+
+
+@pytest.mark.parametrize("call", list(SINGLE_KEY_CALLS))
+def test_each_single_key_form_allocates_what_it_did_as_a_class_of_its_own(call, monkeypatch):
+    _allocates_what_was_recorded(call, monkeypatch)
+
+
+@pytest.mark.parametrize("call", list(KEYS_CALLS))
+def test_each_several_keys_form_allocates_what_it_did_with_a_chain_class_of_its_own(call, monkeypatch):
+    _allocates_what_was_recorded(call, monkeypatch)
 
 
 # ---- B: the stage functions that allocate their own results, fed as their suites feed them, at (23, 33) -----------------------------------
