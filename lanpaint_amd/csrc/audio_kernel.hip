@@ -13,6 +13,7 @@
 // carries the rounding of two whole-signal fp64 prefixes, at most (mask_len + 4) * 2^-52 * sum |w| (include/lanpaint_hip.h):
 // small in absolute terms, many fp32 ulps where w' itself is tiny.  w' = float(S * double(1.0f / cf)).
 // Bytes moved: 3 x 4 B per sample and row (two loads, one store); the mask and its tables stay in L2.
+// Entry point defined here: lp_audio_merge.
 #include "lp_common.h"
 
 namespace lp {
@@ -152,7 +153,8 @@ __global__ __launch_bounds__(kMergeBlock) void lp_audio_merge_kernel(MergeArgs a
 
 }  // namespace
 
-int audio_merge_dispatch(const lp_audio_desc* dp, hipStream_t stream) {
+extern "C" int lp_audio_merge(const lp_audio_desc* dp, void* stream_) {
+    const hipStream_t stream = as_stream(stream_);
     if (!dp) return LP_E_INVALID;
     const lp_audio_desc& d = *dp;
     if (d.n < 1 || d.mask_len < 1 || d.mask_len == INT32_MAX || d.batch < 1 || d.channels < 1 || d.cf < 0) return LP_E_INVALID;

@@ -6,6 +6,9 @@
 //                        via wave ballots + an LDS tile of row bitmasks, and a
 //                        deterministic weighted-MSE reduction
 //   K5 lp_reshape_mask  exact-integer nearest-exact resample + temporal union
+// Entry points defined here: lp_philox_normal, lp_torch_normal, lp_boundary_ring, lp_wmse_pair, lp_pack_mask,
+// lp_pack_mask_latent, lp_reshape_mask.  (lp_coeffs, lp_finalize and the two lp_sigma_times forms are in cabi.hip, whose host
+// logic makes the same launches through coeffs_dispatch, finalize_dispatch and the sigma_times dispatches below.)
 #include "lp_common.h"
 
 namespace lp {
@@ -192,7 +195,8 @@ __global__ __launch_bounds__(256) void lp_philox_kernel(float* __restrict__ out,
     }
 }
 
-int philox_dispatch(float* out, int64_t n_el, uint64_t seed, uint64_t offset, uint32_t slot, hipStream_t stream) {
+extern "C" int lp_philox_normal(float* out, int64_t n_el, uint64_t seed, uint64_t offset, uint32_t slot, void* stream_) {
+    const hipStream_t stream = as_stream(stream_);
     if (!out || n_el <= 0) return LP_E_INVALID;
     if (slot > 1) return LP_E_INVALID;
     int64_t bx = (n_el + 255) / 256;
@@ -242,7 +246,8 @@ __global__ __launch_bounds__(256) void lp_ring_kernel(const float* __restrict__ 
     }
 }
 
-int ring_dispatch(const float* mask, float* ring, int64_t planes, int height, int width, hipStream_t stream) {
+extern "C" int lp_boundary_ring(const float* mask, float* ring, int64_t planes, int32_t height, int32_t width, void* stream_) {
+    const hipStream_t stream = as_stream(stream_);
     if (!mask || !ring || planes <= 0 || height <= 0 || width <= 0) return LP_E_INVALID;
     if (planes > 65535) return LP_E_UNSUPPORTED;
     dim3 grid((width + kRingCols - 1) / kRingCols, (height + kRingRows - 1) / kRingRows, static_cast<unsigned>(planes));
@@ -314,8 +319,9 @@ __global__ __launch_bounds__(64) void lp_wmse_final_kernel(const double* __restr
     }
 }
 
-int wmse_dispatch(const float* a, const float* b, const float* mask, const float* ring, int64_t n_el, double* acc,
-                  double* scratch, int scratch_blocks, hipStream_t stream) {
+extern "C" int lp_wmse_pair(const float* a, const float* b, const float* mask, const float* ring, int64_t n_el, double* acc,
+                            double* scratch, int32_t scratch_blocks, void* stream_) {
+    const hipStream_t stream = as_stream(stream_);
     if (!a || !b || !mask || !acc || !scratch || n_el <= 0 || scratch_blocks <= 0) return LP_E_INVALID;
     const auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; };
     const bool vec4 = n_el % 4 == 0 && al16(a) && al16(b) && al16(mask) && (!ring || al16(ring));
@@ -369,8 +375,9 @@ __global__ __launch_bounds__(256) void lp_reshape_mask_kernel(const float* __res
     }
 }
 
-int reshape_mask_dispatch(const float* src, int sb, int sc, int sf, int sh, int sw, float* dst, int db, int dc, int df,
-                          int dh, int dw, int taps, int flags, hipStream_t stream) {
+extern "C" int lp_reshape_mask(const float* src, int32_t sb, int32_t sc, int32_t sf, int32_t sh, int32_t sw, float* dst, int32_t db,
+                               int32_t dc, int32_t df, int32_t dh, int32_t dw, int32_t taps, int32_t flags, void* stream_) {
+    const hipStream_t stream = as_stream(stream_);
     if (!src || !dst || sb <= 0 || sc <= 0 || sf <= 0 || sh <= 0 || sw <= 0 || db <= 0 || dc <= 0 || df <= 0 ||
         dh <= 0 || dw <= 0)
         return LP_E_INVALID;
@@ -412,8 +419,9 @@ __global__ __launch_bounds__(256) void lp_pack_mask_kernel(const float* mask, in
     if (nonbinary && !(flags & LP_FL_MASK_DENOISE) && __ballot(soft) != 0ull && lane == 0) *nonbinary = 1;
 }
 
-int pack_mask_dispatch(const float* mask, int64_t n_el, uint32_t flags, void* bits, int32_t* nonbinary, float* latent_out,
-                       hipStream_t stream) {
+// lp_pack_mask and lp_pack_mask_latent: one launch, with either output
+static int pack_mask(const float* mask, int64_t n_el, uint32_t flags, void* bits, int32_t* nonbinary, float* latent_out,
+                     hipStream_t stream) {
     if (!mask || !bits || n_el <= 0 || (flags & ~LP_FL_MASK_DENOISE) || !aligned(bits, 8)) return LP_E_INVALID;
     const int64_t words = (n_el + 63) / 64;
     int64_t bx = (words + 3) / 4;                       // 4 waves per block
@@ -421,6 +429,15 @@ int pack_mask_dispatch(const float* mask, int64_t n_el, uint32_t flags, void* bi
     hipLaunchKernelGGL(lp_pack_mask_kernel, dim3(static_cast<unsigned>(bx)), dim3(256), 0, stream, mask, n_el, flags,
                        static_cast<unsigned long long*>(bits), nonbinary, latent_out);
     return hipGetLastError() == hipSuccess ? LP_OK : LP_E_LAUNCH;
+}
+
+extern "C" int lp_pack_mask(const float* mask, int64_t n_el, uint32_t flags, void* bits, int32_t* nonbinary, void* stream) {
+    return pack_mask(mask, n_el, flags, bits, nonbinary, nullptr, as_stream(stream));
+}
+
+extern "C" int lp_pack_mask_latent(const float* mask, int64_t n_el, uint32_t flags, void* bits, float* latent_out, void* stream) {
+    if (!latent_out) return LP_E_INVALID;
+    return pack_mask(mask, n_el, flags, bits, nullptr, latent_out, as_stream(stream));
 }
 
 // ---------------------------------------------------------------------------------
@@ -432,7 +449,8 @@ __global__ __launch_bounds__(256) void lp_torch_normal_kernel(float* __restrict_
     if (li < n) out[li] = torch_normal(static_cast<uint64_t>(li), seed, offset, bg, n <= static_cast<int64_t>(bg));
 }
 
-int torch_normal_dispatch(float* out, int64_t n, uint64_t seed, uint64_t offset, uint32_t bg, hipStream_t stream) {
+extern "C" int lp_torch_normal(float* out, int64_t n, uint64_t seed, uint64_t offset, uint32_t bg, void* stream_) {
+    const hipStream_t stream = as_stream(stream_);
     if (!out || n <= 0 || bg == 0 || (offset & 3ull)) return LP_E_INVALID;
     const int64_t bx = (n + 255) / 256;
     if (bx > 0x7fffffff) return LP_E_INVALID;

@@ -6,6 +6,7 @@
 // dilation, R for the blur) is staged in LDS once and smoothed there by the separable passes of
 // mask_tile.h (shared with lp_detail_stitch); then
 //   D  --col blur--> m (registers)  --> out = image1*(1-m) + image2*m
+// Entry point defined here: lp_mask_blend.
 #include "lp_common.h"
 #include "mask_tile.h"
 
@@ -52,7 +53,8 @@ static hipError_t launch_blend(const lp_blend_desc& d, hipStream_t stream) {
     return hipGetLastError();
 }
 
-int blend_dispatch(const lp_blend_desc* dp, hipStream_t stream) {
+extern "C" int lp_mask_blend(const lp_blend_desc* dp, void* stream_) {
+    const hipStream_t stream = as_stream(stream_);
     if (!dp) return LP_E_INVALID;
     const lp_blend_desc& d = *dp;
     if (d.batch <= 0 || d.height <= 0 || d.width <= 0 || d.channels <= 0 || !d.mask) return LP_E_INVALID;

@@ -1,99 +1,19 @@
-// cabi.hip -- extern "C" surface of liblanpaint_hip.so (declared in include/lanpaint_hip.h).
+// cabi.hip -- the part of liblanpaint_hip.so's extern "C" surface (include/lanpaint_hip.h) that is host logic of its own.
 // Plain pointers and sizes in, int status out; no device allocation, no global state, nothing read from the environment.
-// Every entry point enqueues on the caller's stream and returns; the ones that block the calling thread or drive graph
-// handles from the host (lp_node_call, lp_replay_call, lp_timer_elapsed_ns, lp_graph_*) are listed in the header's
-// conventions block and are not capture-safe.
+// An entry point that only checks its arguments and launches is defined, extern "C", in the file that holds its kernels
+// (each file's banner lists them; a new one goes there, next to its kernels, not here).  Defined here:
+//   lp_abi_version, lp_strerror;
+//   the sigma-call family, whose launches the host logic below also makes (the functions lp_common.h declares): lp_step,
+//   lp_step_timed, lp_step_timed_burst, lp_timer_create / _destroy / _elapsed_ns, lp_coeffs, lp_finalize, lp_sigma_times,
+//   lp_sigma_times_mailbox;
+//   the entries that block the calling thread or drive graph handles from the host, listed in the header's conventions block
+//   and not capture-safe: lp_replay_call, lp_replay_burst, lp_graph_bind_replace / _clone_tail / _clone_sigma_root / _release,
+//   lp_node_call; and its rule alone, lp_effective_inner_steps.
 #include <cmath>
 
 #include "lp_common.h"
 
-namespace lp {
-int step_dispatch(const lp_step_desc* d, hipStream_t stream, void* timer);
-int replace_node_update(const lp_step_desc* d, hipGraphExec_t exec, const lp_graph_binding* b);
-int timer_create(void** out);
-int timer_destroy(void* h);
-int timer_elapsed_ns(void* h, double* ns);
-int coeffs_dispatch(const lp_hyper* h, const float* ve, int ve_stride, const float* abt, int abt_stride,
-                    const float* rs, int rs_stride, const float* step_ov, int step_stride, const float* t_model,
-                    int t_stride, int rows, float* table, hipStream_t stream);
-int finalize_dispatch(const lp_final_desc* d, hipStream_t stream);
-int sigma_times_dispatch(const float* sigma, int rows, const float* schedule, int schedule_len, int is_flow, float* times,
-                         float* scalars, int32_t* seq_out, int32_t seq, hipStream_t stream);
-int sigma_times_rule_dispatch(const float* sigma, int rows, const float* schedule, int schedule_len, int is_flow,
-                              float* times, float* scalars, int32_t* seq_out, int32_t seq, int32_t n_steps, int32_t early_stop,
-                              int32_t total_steps, double min_step_frac, int32_t guess, uint64_t* valid_out, hipStream_t stream);
-int blend_dispatch(const lp_blend_desc* d, hipStream_t stream);
-int philox_dispatch(float* out, int64_t n_el, uint64_t seed, uint64_t offset, uint32_t slot, hipStream_t stream);
-int ring_dispatch(const float* mask, float* ring, int64_t planes, int height, int width, hipStream_t stream);
-int wmse_dispatch(const float* a, const float* b, const float* mask, const float* ring, int64_t n_el, double* acc,
-                  double* scratch, int scratch_blocks, hipStream_t stream);
-int torch_normal_dispatch(float* out, int64_t n, uint64_t seed, uint64_t offset, uint32_t bg, hipStream_t stream);
-int pack_mask_dispatch(const float* mask, int64_t n_el, uint32_t flags, void* bits, int32_t* nonbinary, float* latent_out,
-                       hipStream_t stream);
-int vmask_edt_dispatch(const lp_vmask_edt_desc* d, hipStream_t stream);
-int vmask_morph_dispatch(const lp_vmask_morph_desc* d, hipStream_t stream);
-int vmask_resize_dispatch(const lp_vmask_resize_desc* d, hipStream_t stream);
-int audio_merge_dispatch(const lp_audio_desc* d, hipStream_t stream);
-int mask_bbox_dispatch(const float* mask, int planes, int H, int W, int32_t* boxes, bool per_plane, hipStream_t stream);
-int detail_resample_dispatch(const lp_detail_resample_desc* d, hipStream_t stream);
-int detail_stitch_dispatch(const lp_detail_stitch_desc* d, hipStream_t stream);
-int mask_components_dispatch(const float* mask, int planes, int H, int W, int32_t* labels, int32_t* table, void* workspace,
-                             int64_t workspace_bytes, hipStream_t stream);
-int detail_resample_regions_dispatch(const lp_detail_resample_regions_desc* d, hipStream_t stream);
-int detail_stitch_regions_dispatch(const lp_detail_stitch_regions_desc* d, hipStream_t stream);
-int detail_resample_track_dispatch(const lp_detail_resample_track_desc* d, hipStream_t stream);
-int detail_stitch_track_dispatch(const lp_detail_stitch_track_desc* d, hipStream_t stream);
-int mask_components_frames_dispatch(const float* mask, int F, int H, int W, int32_t* labels, int32_t* table, void* workspace,
-                                    int64_t workspace_bytes, hipStream_t stream);
-int subject_boxes_dispatch(const int32_t* labels, int frames, int H, int W, const int32_t* owner, int owner_len, int subjects,
-                           int32_t* boxes, hipStream_t stream);
-int detail_resample_subjects_dispatch(const lp_detail_resample_subjects_desc* d, hipStream_t stream);
-int detail_stitch_subjects_dispatch(const lp_detail_stitch_subjects_desc* d, hipStream_t stream);
-int color_stats_dispatch(const lp_color_stats_desc* d, hipStream_t stream);
-int color_fit_dispatch(const lp_color_fit_desc* d, hipStream_t stream);
-int color_apply_dispatch(const lp_color_apply_desc* d, hipStream_t stream);
-int mask_fill_dispatch(const lp_fill_desc* d, hipStream_t stream);
-int64_t fill_ws_bytes(int batch, int height, int width, int channels);
-int outpaint_pad_dispatch(const lp_outpaint_desc* d, hipStream_t stream);
-int multiband_blend_dispatch(const lp_multiband_desc* d, hipStream_t stream);
-int64_t multiband_ws_bytes(int batch, int height, int width, int channels, int levels);
-int mask_refine_dispatch(const lp_refine_desc* d, hipStream_t stream);
-int64_t refine_ws_bytes(int batch, int height, int width, int channels, int radius);
-int mask_signed_d2_dispatch(const int32_t* d2, int frames, int height, int width, int32_t* q, hipStream_t stream);
-int mask_stabilize_dispatch(const lp_stabilize_desc* d, hipStream_t stream);
-int grain_stats_dispatch(const lp_grain_stats_desc* d, hipStream_t stream);
-int grain_fit_dispatch(const lp_grain_fit_desc* d, hipStream_t stream);
-int grain_field_dispatch(const lp_grain_field_desc* d, hipStream_t stream);
-int grain_apply_dispatch(const lp_grain_apply_desc* d, hipStream_t stream);
-int64_t prop_pyramid_ws_bytes(int frames, int height, int width, int levels);
-int prop_luma_dispatch(const lp_prop_luma_desc* d, hipStream_t stream);
-int prop_key_mask_dispatch(const float* mask, int height, int width, int levels, uint8_t* mpyr, float* out, hipStream_t stream);
-int prop_match_dispatch(const lp_prop_match_desc* d, hipStream_t stream);
-int prop_fill_dispatch(const int32_t* vec, const int32_t* valid, int gh, int gw, int32_t* out, hipStream_t stream);
-int prop_advance_dispatch(const lp_prop_advance_desc* d, hipStream_t stream);
-int prop_match_batch_dispatch(const lp_prop_match_batch_desc* d, hipStream_t stream);
-int prop_fill_batch_dispatch(const lp_prop_fill_job* job, int jobs, int gh, int gw, hipStream_t stream);
-int prop_advance_batch_dispatch(const lp_prop_advance_batch_desc* d, hipStream_t stream);
-int prop_merge_dispatch(const lp_prop_merge_desc* d, hipStream_t stream);
-int prop_visible_dispatch(const lp_prop_visible_desc* d, hipStream_t stream);
-int prop_occlude_dispatch(const lp_prop_occlude_desc* d, hipStream_t stream);
-int prop_visible_batch_dispatch(const lp_prop_visible_batch_desc* d, hipStream_t stream);
-int prop_occlude_batch_dispatch(const lp_prop_occlude_batch_desc* d, hipStream_t stream);
-int prop_merge_visible_dispatch(const lp_prop_merge_visible_desc* d, hipStream_t stream);
-int prop_anchor_match_dispatch(const lp_prop_anchor_desc* d, hipStream_t stream);
-int prop_anchor_match_gated_dispatch(const lp_prop_anchor_gated_desc* d, hipStream_t stream);
-int tfill_known_dispatch(const lp_tfill_known_desc* d, hipStream_t stream);
-int tfill_carry_dispatch(const lp_tfill_carry_desc* d, hipStream_t stream);
-int tfill_carry_pair_dispatch(const lp_tfill_carry_pair_desc* d, hipStream_t stream);
-int tsmooth_dispatch(const lp_tsmooth_desc* d, hipStream_t stream);
-int tsmooth_robust_dispatch(const lp_tsmooth_robust_desc* d, hipStream_t stream);
-int shot_measure_dispatch(const lp_shot_measure_desc* d, hipStream_t stream);
-int shot_decide_dispatch(const lp_shot_decide_desc* d, hipStream_t stream);
-int reshape_mask_dispatch(const float* src, int sb, int sc, int sf, int sh, int sw, float* dst, int db, int dc, int df,
-                          int dh, int dw, int taps, int flags, hipStream_t stream);
-}  // namespace lp
-
-static inline hipStream_t as_stream(void* s) { return static_cast<hipStream_t>(s); }
+using lp::as_stream;
 
 extern "C" {
 
@@ -140,194 +60,7 @@ int lp_step_timed(const lp_step_desc* desc, void* stream, void* timer) {
 }
 int lp_timer_elapsed_ns(void* timer, double* ns) { return lp::timer_elapsed_ns(timer, ns); }
 
-int lp_mask_blend(const lp_blend_desc* desc, void* stream) { return lp::blend_dispatch(desc, as_stream(stream)); }
-
-int lp_vmask_edt(const lp_vmask_edt_desc* desc, void* stream) { return lp::vmask_edt_dispatch(desc, as_stream(stream)); }
-
-int lp_vmask_morph(const lp_vmask_morph_desc* desc, void* stream) { return lp::vmask_morph_dispatch(desc, as_stream(stream)); }
-
-int lp_vmask_resize(const lp_vmask_resize_desc* desc, void* stream) { return lp::vmask_resize_dispatch(desc, as_stream(stream)); }
-
-int lp_audio_merge(const lp_audio_desc* desc, void* stream) { return lp::audio_merge_dispatch(desc, as_stream(stream)); }
-
-int lp_mask_bbox(const float* mask, int32_t planes, int32_t height, int32_t width, int32_t* bbox, void* stream) {
-    return lp::mask_bbox_dispatch(mask, planes, height, width, bbox, false, as_stream(stream));
-}
-
-int lp_detail_resample(const lp_detail_resample_desc* desc, void* stream) { return lp::detail_resample_dispatch(desc, as_stream(stream)); }
-
-int lp_detail_stitch(const lp_detail_stitch_desc* desc, void* stream) { return lp::detail_stitch_dispatch(desc, as_stream(stream)); }
-
-int lp_mask_components(const float* mask, int32_t planes, int32_t height, int32_t width, int32_t* labels, int32_t* table,
-                       void* workspace, int64_t workspace_bytes, void* stream) {
-    return lp::mask_components_dispatch(mask, planes, height, width, labels, table, workspace, workspace_bytes, as_stream(stream));
-}
-
-int lp_detail_resample_regions(const lp_detail_resample_regions_desc* desc, void* stream) {
-    return lp::detail_resample_regions_dispatch(desc, as_stream(stream));
-}
-
-int lp_detail_stitch_regions(const lp_detail_stitch_regions_desc* desc, void* stream) {
-    return lp::detail_stitch_regions_dispatch(desc, as_stream(stream));
-}
-
-int lp_mask_bbox_frames(const float* mask, int32_t planes, int32_t height, int32_t width, int32_t* boxes, void* stream) {
-    return lp::mask_bbox_dispatch(mask, planes, height, width, boxes, true, as_stream(stream));
-}
-
-int lp_detail_resample_track(const lp_detail_resample_track_desc* desc, void* stream) {
-    return lp::detail_resample_track_dispatch(desc, as_stream(stream));
-}
-
-int lp_detail_stitch_track(const lp_detail_stitch_track_desc* desc, void* stream) {
-    return lp::detail_stitch_track_dispatch(desc, as_stream(stream));
-}
-
-int lp_mask_components_frames(const float* mask, int32_t frames, int32_t height, int32_t width, int32_t* labels, int32_t* table,
-                              void* workspace, int64_t workspace_bytes, void* stream) {
-    return lp::mask_components_frames_dispatch(mask, frames, height, width, labels, table, workspace, workspace_bytes,
-                                               as_stream(stream));
-}
-
-int lp_subject_boxes(const int32_t* labels, int32_t frames, int32_t height, int32_t width, const int32_t* owner, int32_t owner_len,
-                     int32_t subjects, int32_t* boxes, void* stream) {
-    return lp::subject_boxes_dispatch(labels, frames, height, width, owner, owner_len, subjects, boxes, as_stream(stream));
-}
-
-int lp_detail_resample_subjects(const lp_detail_resample_subjects_desc* desc, void* stream) {
-    return lp::detail_resample_subjects_dispatch(desc, as_stream(stream));
-}
-
-int lp_detail_stitch_subjects(const lp_detail_stitch_subjects_desc* desc, void* stream) {
-    return lp::detail_stitch_subjects_dispatch(desc, as_stream(stream));
-}
-
-int lp_color_stats(const lp_color_stats_desc* desc, void* stream) { return lp::color_stats_dispatch(desc, as_stream(stream)); }
-
-int lp_color_fit(const lp_color_fit_desc* desc, void* stream) { return lp::color_fit_dispatch(desc, as_stream(stream)); }
-
-int lp_color_apply(const lp_color_apply_desc* desc, void* stream) { return lp::color_apply_dispatch(desc, as_stream(stream)); }
-
-int lp_mask_fill(const lp_fill_desc* desc, void* stream) { return lp::mask_fill_dispatch(desc, as_stream(stream)); }
-
-int64_t lp_fill_ws_bytes(int32_t batch, int32_t height, int32_t width, int32_t channels) {
-    return lp::fill_ws_bytes(batch, height, width, channels);
-}
-
-int lp_outpaint_pad(const lp_outpaint_desc* desc, void* stream) { return lp::outpaint_pad_dispatch(desc, as_stream(stream)); }
-
-int lp_multiband_blend(const lp_multiband_desc* desc, void* stream) { return lp::multiband_blend_dispatch(desc, as_stream(stream)); }
-
-int64_t lp_multiband_ws_bytes(int32_t batch, int32_t height, int32_t width, int32_t channels, int32_t levels) {
-    return lp::multiband_ws_bytes(batch, height, width, channels, levels);
-}
-
-int lp_mask_refine(const lp_refine_desc* desc, void* stream) { return lp::mask_refine_dispatch(desc, as_stream(stream)); }
-
-int64_t lp_refine_ws_bytes(int32_t batch, int32_t height, int32_t width, int32_t channels, int32_t radius) {
-    return lp::refine_ws_bytes(batch, height, width, channels, radius);
-}
-
-int lp_mask_signed_d2(const int32_t* d2, int32_t frames, int32_t height, int32_t width, int32_t* q, void* stream) {
-    return lp::mask_signed_d2_dispatch(d2, frames, height, width, q, as_stream(stream));
-}
-
-int lp_mask_stabilize(const lp_stabilize_desc* desc, void* stream) { return lp::mask_stabilize_dispatch(desc, as_stream(stream)); }
-
-int lp_grain_stats(const lp_grain_stats_desc* desc, void* stream) { return lp::grain_stats_dispatch(desc, as_stream(stream)); }
-
-int lp_grain_fit(const lp_grain_fit_desc* desc, void* stream) { return lp::grain_fit_dispatch(desc, as_stream(stream)); }
-
-int lp_grain_field(const lp_grain_field_desc* desc, void* stream) { return lp::grain_field_dispatch(desc, as_stream(stream)); }
-
-int lp_grain_apply(const lp_grain_apply_desc* desc, void* stream) { return lp::grain_apply_dispatch(desc, as_stream(stream)); }
-
-int64_t lp_prop_pyramid_ws_bytes(int32_t frames, int32_t height, int32_t width, int32_t levels) {
-    return lp::prop_pyramid_ws_bytes(frames, height, width, levels);
-}
-
-int lp_prop_luma(const lp_prop_luma_desc* desc, void* stream) { return lp::prop_luma_dispatch(desc, as_stream(stream)); }
-
-int lp_prop_key_mask(const float* mask, int32_t height, int32_t width, int32_t levels, uint8_t* mask_pyramid, float* out,
-                     void* stream) {
-    return lp::prop_key_mask_dispatch(mask, height, width, levels, mask_pyramid, out, as_stream(stream));
-}
-
-int lp_prop_match(const lp_prop_match_desc* desc, void* stream) { return lp::prop_match_dispatch(desc, as_stream(stream)); }
-
-int lp_prop_fill(const int32_t* vec, const int32_t* valid, int32_t grid_h, int32_t grid_w, int32_t* out, void* stream) {
-    return lp::prop_fill_dispatch(vec, valid, grid_h, grid_w, out, as_stream(stream));
-}
-
-int lp_prop_advance(const lp_prop_advance_desc* desc, void* stream) { return lp::prop_advance_dispatch(desc, as_stream(stream)); }
-
-int lp_prop_match_batch(const lp_prop_match_batch_desc* desc, void* stream) {
-    return lp::prop_match_batch_dispatch(desc, as_stream(stream));
-}
-
-int lp_prop_fill_batch(const lp_prop_fill_job* job, int32_t jobs, int32_t grid_h, int32_t grid_w, void* stream) {
-    return lp::prop_fill_batch_dispatch(job, jobs, grid_h, grid_w, as_stream(stream));
-}
-
-int lp_prop_advance_batch(const lp_prop_advance_batch_desc* desc, void* stream) {
-    return lp::prop_advance_batch_dispatch(desc, as_stream(stream));
-}
-
-int lp_prop_merge(const lp_prop_merge_desc* desc, void* stream) { return lp::prop_merge_dispatch(desc, as_stream(stream)); }
-
-int lp_prop_visible(const lp_prop_visible_desc* desc, void* stream) { return lp::prop_visible_dispatch(desc, as_stream(stream)); }
-
-int lp_prop_occlude(const lp_prop_occlude_desc* desc, void* stream) { return lp::prop_occlude_dispatch(desc, as_stream(stream)); }
-
-int lp_prop_visible_batch(const lp_prop_visible_batch_desc* desc, void* stream) {
-    return lp::prop_visible_batch_dispatch(desc, as_stream(stream));
-}
-
-int lp_prop_occlude_batch(const lp_prop_occlude_batch_desc* desc, void* stream) {
-    return lp::prop_occlude_batch_dispatch(desc, as_stream(stream));
-}
-
-int lp_prop_merge_visible(const lp_prop_merge_visible_desc* desc, void* stream) {
-    return lp::prop_merge_visible_dispatch(desc, as_stream(stream));
-}
-
-int lp_prop_anchor_match(const lp_prop_anchor_desc* desc, void* stream) {
-    return lp::prop_anchor_match_dispatch(desc, as_stream(stream));
-}
-
-int lp_prop_anchor_match_gated(const lp_prop_anchor_gated_desc* desc, void* stream) {
-    return lp::prop_anchor_match_gated_dispatch(desc, as_stream(stream));
-}
-
-int lp_tfill_known(const lp_tfill_known_desc* desc, void* stream) { return lp::tfill_known_dispatch(desc, as_stream(stream)); }
-
-int lp_tfill_carry(const lp_tfill_carry_desc* desc, void* stream) { return lp::tfill_carry_dispatch(desc, as_stream(stream)); }
-
-int lp_tfill_carry_pair(const lp_tfill_carry_pair_desc* desc, void* stream) {
-    return lp::tfill_carry_pair_dispatch(desc, as_stream(stream));
-}
-
-int lp_tsmooth(const lp_tsmooth_desc* desc, void* stream) { return lp::tsmooth_dispatch(desc, as_stream(stream)); }
-int lp_tsmooth_robust(const lp_tsmooth_robust_desc* desc, void* stream) { return lp::tsmooth_robust_dispatch(desc, as_stream(stream)); }
-
-int lp_shot_measure(const lp_shot_measure_desc* desc, void* stream) { return lp::shot_measure_dispatch(desc, as_stream(stream)); }
-
-int lp_shot_decide(const lp_shot_decide_desc* desc, void* stream) { return lp::shot_decide_dispatch(desc, as_stream(stream)); }
-
 int lp_finalize(const lp_final_desc* desc, void* stream) { return lp::finalize_dispatch(desc, as_stream(stream)); }
-
-int lp_philox_normal(float* out, int64_t n_el, uint64_t seed, uint64_t offset, uint32_t slot, void* stream) {
-    return lp::philox_dispatch(out, n_el, seed, offset, slot, as_stream(stream));
-}
-
-int lp_boundary_ring(const float* mask, float* ring, int64_t planes, int32_t height, int32_t width, void* stream) {
-    return lp::ring_dispatch(mask, ring, planes, height, width, as_stream(stream));
-}
-
-int lp_wmse_pair(const float* a, const float* b, const float* mask, const float* ring, int64_t n_el, double* acc,
-                 double* block_scratch, int32_t scratch_blocks, void* stream) {
-    return lp::wmse_dispatch(a, b, mask, ring, n_el, acc, block_scratch, scratch_blocks, as_stream(stream));
-}
 
 int lp_replay_call(const lp_call_desc* c, void* stream) {
     if (!c || (!c->replace && !c->graph_exec && !c->final)) return LP_E_INVALID;    // nothing to enqueue
@@ -606,26 +339,6 @@ int lp_replay_burst(void* const* graph_execs, int32_t n, const lp_step_desc* bef
         }
     }
     return LP_OK;
-}
-
-int lp_torch_normal(float* out, int64_t n_el, uint64_t seed, uint64_t offset, uint32_t bg, void* stream) {
-    return lp::torch_normal_dispatch(out, n_el, seed, offset, bg, as_stream(stream));
-}
-
-int lp_pack_mask(const float* mask, int64_t n_el, uint32_t flags, void* bits, int32_t* nonbinary, void* stream) {
-    return lp::pack_mask_dispatch(mask, n_el, flags, bits, nonbinary, nullptr, as_stream(stream));
-}
-
-int lp_pack_mask_latent(const float* mask, int64_t n_el, uint32_t flags, void* bits, float* latent_out, void* stream) {
-    if (!latent_out) return LP_E_INVALID;
-    return lp::pack_mask_dispatch(mask, n_el, flags, bits, nullptr, latent_out, as_stream(stream));
-}
-
-int lp_reshape_mask(const float* src, int32_t src_b, int32_t src_c, int32_t src_f, int32_t src_h, int32_t src_w,
-                    float* dst, int32_t batch, int32_t channels, int32_t dst_f, int32_t dst_h, int32_t dst_w,
-                    int32_t temporal_taps, int32_t flags, void* stream) {
-    return lp::reshape_mask_dispatch(src, src_b, src_c, src_f, src_h, src_w, dst, batch, channels, dst_f, dst_h, dst_w,
-                                     temporal_taps, flags, as_stream(stream));
 }
 
 }  // extern "C"

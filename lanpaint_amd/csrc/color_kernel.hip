@@ -13,6 +13,7 @@
 //
 // The library is built with -ffp-contract=on: every fp64 step whose fusing would change a bit goes through __dmul_rn / __dadd_rn
 // and friends, one operation per call.
+// Entry points defined here: lp_color_stats, lp_color_fit, lp_color_apply.
 #include "lp_common.h"
 
 namespace lp {
@@ -279,7 +280,8 @@ void launch_stats(const lp_color_stats_desc& d, bool vec, bool mvec, hipStream_t
 
 }  // namespace
 
-int color_stats_dispatch(const lp_color_stats_desc* dp, hipStream_t stream) {
+extern "C" int lp_color_stats(const lp_color_stats_desc* dp, void* stream_) {
+    const hipStream_t stream = as_stream(stream_);
     if (!dp) return LP_E_INVALID;
     const lp_color_stats_desc& d = *dp;
     if (d.batch <= 0 || !side_ok(d.height) || !side_ok(d.width) || !chan_ok(d.channels)) return LP_E_INVALID;
@@ -307,7 +309,8 @@ int color_stats_dispatch(const lp_color_stats_desc* dp, hipStream_t stream) {
     return hipGetLastError() == hipSuccess ? LP_OK : LP_E_LAUNCH;
 }
 
-int color_fit_dispatch(const lp_color_fit_desc* dp, hipStream_t stream) {
+extern "C" int lp_color_fit(const lp_color_fit_desc* dp, void* stream_) {
+    const hipStream_t stream = as_stream(stream_);
     if (!dp) return LP_E_INVALID;
     const lp_color_fit_desc& d = *dp;
     if (d.batch <= 0 || !chan_ok(d.channels) || !d.stats || !d.coef) return LP_E_INVALID;
@@ -320,7 +323,8 @@ int color_fit_dispatch(const lp_color_fit_desc* dp, hipStream_t stream) {
     return hipGetLastError() == hipSuccess ? LP_OK : LP_E_LAUNCH;
 }
 
-int color_apply_dispatch(const lp_color_apply_desc* dp, hipStream_t stream) {
+extern "C" int lp_color_apply(const lp_color_apply_desc* dp, void* stream_) {
+    const hipStream_t stream = as_stream(stream_);
     if (!dp) return LP_E_INVALID;
     const lp_color_apply_desc& d = *dp;
     if (d.batch <= 0 || !side_ok(d.height) || !side_ok(d.width) || !chan_ok(d.channels)) return LP_E_INVALID;

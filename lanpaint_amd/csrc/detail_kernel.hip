@@ -31,6 +31,8 @@
 // WindowAt, or WindowFrom<OriginOf>: a device table indexed by region, by image or by z itself, clamped in one place -- and
 // over how a mask element is read: MaskAsIs, or EraseForeign<PER_IMAGE> through one label plane or one per image, either
 // asked for window (r, b)'s view.  The regions and subjects entries share their crop dispatcher and their stitch loop.
+// Entry points defined here: lp_mask_bbox, lp_mask_bbox_frames, lp_subject_boxes, lp_detail_resample, lp_detail_stitch and
+// their _regions, _track and _subjects forms.
 #include "lp_common.h"
 #include "mask_tile.h"
 #include "resample_tile.h"
@@ -464,9 +466,8 @@ int stitch_groups(StitchJob j, const Desc& d, int groups, WindowOf window_of, hi
     return LP_OK;
 }
 
-}  // namespace
-
-int mask_bbox_dispatch(const float* mask, int planes, int H, int W, int32_t* boxes, bool per_plane, hipStream_t stream) {
+// lp_mask_bbox (one box over every plane) and lp_mask_bbox_frames (a box per plane)
+int mask_bbox(const float* mask, int planes, int H, int W, int32_t* boxes, bool per_plane, hipStream_t stream) {
     if (!mask || !boxes || planes <= 0 || !side_ok(H) || !side_ok(W)) return LP_E_INVALID;
     if (planes > 65535) return LP_E_UNSUPPORTED;
     const int n = per_plane ? planes : 1;
@@ -480,7 +481,18 @@ int mask_bbox_dispatch(const float* mask, int planes, int H, int W, int32_t* box
     return launched();
 }
 
-int detail_resample_dispatch(const lp_detail_resample_desc* dp, hipStream_t stream) {
+}  // namespace
+
+extern "C" int lp_mask_bbox(const float* mask, int32_t planes, int32_t height, int32_t width, int32_t* bbox, void* stream) {
+    return mask_bbox(mask, planes, height, width, bbox, false, as_stream(stream));
+}
+
+extern "C" int lp_mask_bbox_frames(const float* mask, int32_t planes, int32_t height, int32_t width, int32_t* boxes, void* stream) {
+    return mask_bbox(mask, planes, height, width, boxes, true, as_stream(stream));
+}
+
+extern "C" int lp_detail_resample(const lp_detail_resample_desc* dp, void* stream_) {
+    const hipStream_t stream = as_stream(stream_);
     if (!dp) return LP_E_INVALID;
     const lp_detail_resample_desc& d = *dp;
     const ResampleJob j = {d.batch, d.src_h, d.src_w, d.channels, d.win_h, d.win_w, d.out_h, d.out_w, d.ksize_x, d.ksize_y,
@@ -490,7 +502,8 @@ int detail_resample_dispatch(const lp_detail_resample_desc* dp, hipStream_t stre
     return launch_resample(j, at, stream);
 }
 
-int detail_stitch_dispatch(const lp_detail_stitch_desc* dp, hipStream_t stream) {
+extern "C" int lp_detail_stitch(const lp_detail_stitch_desc* dp, void* stream_) {
+    const hipStream_t stream = as_stream(stream_);
     if (!dp) return LP_E_INVALID;
     const lp_detail_stitch_desc& d = *dp;
     const StitchJob j = {d.batch, d.height, d.width, d.channels, d.win_h, d.win_w, d.k, d.mask_batch, d.mask, d.original,
@@ -501,11 +514,13 @@ int detail_stitch_dispatch(const lp_detail_stitch_desc* dp, hipStream_t stream) 
     return launch_stitch(j, at, MaskAsIs(), stream);
 }
 
-int detail_resample_regions_dispatch(const lp_detail_resample_regions_desc* dp, hipStream_t stream) {
+extern "C" int lp_detail_resample_regions(const lp_detail_resample_regions_desc* dp, void* stream_) {
+    const hipStream_t stream = as_stream(stream_);
     return resample_groups_dispatch<WindowOfRegion, EraseForeign<false>>(dp, &lp_detail_resample_regions_desc::regions, stream);
 }
 
-int detail_stitch_regions_dispatch(const lp_detail_stitch_regions_desc* dp, hipStream_t stream) {
+extern "C" int lp_detail_stitch_regions(const lp_detail_stitch_regions_desc* dp, void* stream_) {
+    const hipStream_t stream = as_stream(stream_);
     if (!dp) return LP_E_INVALID;
     const lp_detail_stitch_regions_desc& d = *dp;
     if (d.regions < 1 || d.regions > LP_DETAIL_MAX_REGIONS || !d.origins) return LP_E_INVALID;
@@ -519,8 +534,9 @@ int detail_stitch_regions_dispatch(const lp_detail_stitch_regions_desc* dp, hipS
     return stitch_groups<EraseForeign<false>>(j, d, d.regions, window_of, stream);
 }
 
-int subject_boxes_dispatch(const int32_t* labels, int frames, int H, int W, const int32_t* owner, int owner_len, int subjects,
-                           int32_t* boxes, hipStream_t stream) {
+extern "C" int lp_subject_boxes(const int32_t* labels, int32_t frames, int32_t H, int32_t W, const int32_t* owner, int32_t owner_len,
+                                int32_t subjects, int32_t* boxes, void* stream_) {
+    const hipStream_t stream = as_stream(stream_);
     if (!labels || !owner || !boxes || frames <= 0 || !side_ok(H) || !side_ok(W) || owner_len < 1) return LP_E_INVALID;
     if (subjects < 1 || subjects > LP_DETAIL_MAX_REGIONS) return LP_E_INVALID;
     if (frames > 65535) return LP_E_UNSUPPORTED;
@@ -532,11 +548,13 @@ int subject_boxes_dispatch(const int32_t* labels, int frames, int H, int W, cons
     return launched();
 }
 
-int detail_resample_subjects_dispatch(const lp_detail_resample_subjects_desc* dp, hipStream_t stream) {
+extern "C" int lp_detail_resample_subjects(const lp_detail_resample_subjects_desc* dp, void* stream_) {
+    const hipStream_t stream = as_stream(stream_);
     return resample_groups_dispatch<WindowOfSubject, EraseForeign<true>>(dp, &lp_detail_resample_subjects_desc::subjects, stream);
 }
 
-int detail_stitch_subjects_dispatch(const lp_detail_stitch_subjects_desc* dp, hipStream_t stream) {
+extern "C" int lp_detail_stitch_subjects(const lp_detail_stitch_subjects_desc* dp, void* stream_) {
+    const hipStream_t stream = as_stream(stream_);
     if (!dp) return LP_E_INVALID;
     const lp_detail_stitch_subjects_desc& d = *dp;
     if (d.subjects < 1 || d.subjects > LP_DETAIL_MAX_REGIONS || !d.origins) return LP_E_INVALID;
@@ -547,7 +565,8 @@ int detail_stitch_subjects_dispatch(const lp_detail_stitch_subjects_desc* dp, hi
     return stitch_groups<EraseForeign<true>>(j, d, d.subjects, window_of, stream);
 }
 
-int detail_resample_track_dispatch(const lp_detail_resample_track_desc* dp, hipStream_t stream) {
+extern "C" int lp_detail_resample_track(const lp_detail_resample_track_desc* dp, void* stream_) {
+    const hipStream_t stream = as_stream(stream_);
     if (!dp) return LP_E_INVALID;
     const lp_detail_resample_track_desc& d = *dp;
     if (!d.origins) return LP_E_INVALID;
@@ -557,7 +576,8 @@ int detail_resample_track_dispatch(const lp_detail_resample_track_desc* dp, hipS
     return launch_resample(j, WindowOfImage{d.origins}, stream);
 }
 
-int detail_stitch_track_dispatch(const lp_detail_stitch_track_desc* dp, hipStream_t stream) {
+extern "C" int lp_detail_stitch_track(const lp_detail_stitch_track_desc* dp, void* stream_) {
+    const hipStream_t stream = as_stream(stream_);
     if (!dp) return LP_E_INVALID;
     const lp_detail_stitch_track_desc& d = *dp;
     if (!d.origins) return LP_E_INVALID;

@@ -17,6 +17,7 @@
 //
 // The rule fixes every value and the order of every operation, so what a launch covers cannot change a bit; every product,
 // sum and quotient below is one __f*_rn call (the library is built with -ffp-contract=on).
+// Entry points defined here: lp_mask_fill, lp_fill_ws_bytes, lp_outpaint_pad.
 #include "lp_common.h"
 
 namespace lp {
@@ -318,7 +319,7 @@ FillSpan make_span(int L, const int32_t* h, const int32_t* w, const int64_t* off
 
 }  // namespace
 
-int64_t fill_ws_bytes(int batch, int height, int width, int channels) {
+extern "C" int64_t lp_fill_ws_bytes(int32_t batch, int32_t height, int32_t width, int32_t channels) {
     if (batch <= 0 || !side_ok(height) || !side_ok(width) || !chan_ok(channels)) return LP_E_INVALID;
     if (batch > 65535) return LP_E_UNSUPPORTED;
     int32_t h[17], w[17];
@@ -328,7 +329,8 @@ int64_t fill_ws_bytes(int batch, int height, int width, int channels) {
     return bytes < 16 ? 16 : (bytes + 15) / 16 * 16;
 }
 
-int mask_fill_dispatch(const lp_fill_desc* dp, hipStream_t stream) {
+extern "C" int lp_mask_fill(const lp_fill_desc* dp, void* stream_) {
+    const hipStream_t stream = as_stream(stream_);
     if (!dp) return LP_E_INVALID;
     const lp_fill_desc& d = *dp;
     if (d.batch <= 0 || !side_ok(d.height) || !side_ok(d.width) || !chan_ok(d.channels)) return LP_E_INVALID;
@@ -336,7 +338,7 @@ int mask_fill_dispatch(const lp_fill_desc* dp, hipStream_t stream) {
     if (d.mask_batch != 1 && d.mask_batch != d.batch) return LP_E_INVALID;
     if (d.batch > 65535) return LP_E_UNSUPPORTED;
     if (!aligned16(d.ws)) return LP_E_ALIGN;
-    if (d.ws_bytes < fill_ws_bytes(d.batch, d.height, d.width, d.channels)) return LP_E_INVALID;
+    if (d.ws_bytes < lp_fill_ws_bytes(d.batch, d.height, d.width, d.channels)) return LP_E_INVALID;
     int32_t h[17], w[17];
     int64_t off[17], pix;
     const int L = fill_levels(d.height, d.width, h, w, off, &pix);
@@ -364,7 +366,8 @@ int mask_fill_dispatch(const lp_fill_desc* dp, hipStream_t stream) {
     return LP_OK;
 }
 
-int outpaint_pad_dispatch(const lp_outpaint_desc* dp, hipStream_t stream) {
+extern "C" int lp_outpaint_pad(const lp_outpaint_desc* dp, void* stream_) {
+    const hipStream_t stream = as_stream(stream_);
     if (!dp) return LP_E_INVALID;
     const lp_outpaint_desc& d = *dp;
     if (d.batch <= 0 || !side_ok(d.height) || !side_ok(d.width) || !chan_ok(d.channels)) return LP_E_INVALID;

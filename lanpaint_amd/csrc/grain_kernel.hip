@@ -16,6 +16,7 @@
 //                   as 4 x int16 per point in LDS, filtered along x into a second LDS image and along y into registers.
 //
 // The library is built with -ffp-contract=on: every floating-point step goes through __fmul_rn / __dadd_rn and friends.
+// Entry points defined here: lp_grain_stats, lp_grain_fit, lp_grain_field, lp_grain_apply.
 #include "lp_common.h"
 
 namespace lp {
@@ -370,7 +371,8 @@ dim3 tile_grid(int batch, int H, int W, int C, int* tiles_x) {
 
 }  // namespace
 
-int grain_stats_dispatch(const lp_grain_stats_desc* dp, hipStream_t stream) {
+extern "C" int lp_grain_stats(const lp_grain_stats_desc* dp, void* stream_) {
+    const hipStream_t stream = as_stream(stream_);
     if (!dp) return LP_E_INVALID;
     const lp_grain_stats_desc& d = *dp;
     if (d.batch <= 0 || !side_ok(d.height) || !side_ok(d.width) || !chan_ok(d.channels)) return LP_E_INVALID;
@@ -389,7 +391,8 @@ int grain_stats_dispatch(const lp_grain_stats_desc* dp, hipStream_t stream) {
     return hipGetLastError() == hipSuccess ? LP_OK : LP_E_LAUNCH;
 }
 
-int grain_fit_dispatch(const lp_grain_fit_desc* dp, hipStream_t stream) {
+extern "C" int lp_grain_fit(const lp_grain_fit_desc* dp, void* stream_) {
+    const hipStream_t stream = as_stream(stream_);
     if (!dp) return LP_E_INVALID;
     const lp_grain_fit_desc& d = *dp;
     if (d.batch <= 0 || d.ref_batch <= 0 || !chan_ok(d.channels)) return LP_E_INVALID;
@@ -403,7 +406,8 @@ int grain_fit_dispatch(const lp_grain_fit_desc* dp, hipStream_t stream) {
     return hipGetLastError() == hipSuccess ? LP_OK : LP_E_LAUNCH;
 }
 
-int grain_field_dispatch(const lp_grain_field_desc* dp, hipStream_t stream) {
+extern "C" int lp_grain_field(const lp_grain_field_desc* dp, void* stream_) {
+    const hipStream_t stream = as_stream(stream_);
     if (!dp) return LP_E_INVALID;
     const lp_grain_field_desc& d = *dp;
     if (d.batch <= 0 || !side_ok(d.height) || !side_ok(d.width) || !chan_ok(d.channels)) return LP_E_INVALID;
@@ -418,7 +422,8 @@ int grain_field_dispatch(const lp_grain_field_desc* dp, hipStream_t stream) {
     return hipGetLastError() == hipSuccess ? LP_OK : LP_E_LAUNCH;
 }
 
-int grain_apply_dispatch(const lp_grain_apply_desc* dp, hipStream_t stream) {
+extern "C" int lp_grain_apply(const lp_grain_apply_desc* dp, void* stream_) {
+    const hipStream_t stream = as_stream(stream_);
     if (!dp) return LP_E_INVALID;
     const lp_grain_apply_desc& d = *dp;
     if (d.batch <= 0 || !side_ok(d.height) || !side_ok(d.width) || !chan_ok(d.channels)) return LP_E_INVALID;

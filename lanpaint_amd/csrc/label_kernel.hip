@@ -39,6 +39,7 @@
 // `unite` reads parents that others are lowering, every value read is a valid ancestor of the same component (parents only
 // decrease, by atomicMin onto a root), and each union ends with both voxels under one root whatever happened meanwhile.  When
 // the launch has finished every 26-adjacent pair has been united once, so a component's root is its smallest flat index.
+// Entry points defined here: lp_mask_components, lp_mask_components_frames.
 #include "lp_common.h"
 
 namespace lp {
@@ -367,8 +368,9 @@ bool launch_union(const float* mask, int32_t* P, int planes, int n, hipStream_t 
 
 }  // namespace
 
-int mask_components_dispatch(const float* mask, int planes, int H, int W, int32_t* labels, int32_t* table, void* workspace,
-                             int64_t workspace_bytes, hipStream_t stream) {
+extern "C" int lp_mask_components(const float* mask, int32_t planes, int32_t H, int32_t W, int32_t* labels, int32_t* table,
+                                  void* workspace, int64_t workspace_bytes, void* stream_) {
+    const hipStream_t stream = as_stream(stream_);
     if (!mask || !labels || !table || !workspace || planes <= 0 || !side_ok(H) || !side_ok(W)) return LP_E_INVALID;
     if (workspace_bytes < LP_COMPONENTS_WS_BYTES(H, W)) return LP_E_INVALID;
     if (!aligned16(workspace)) return LP_E_ALIGN;
@@ -381,8 +383,9 @@ int mask_components_dispatch(const float* mask, int planes, int H, int W, int32_
     return launch_label<false>(1, H, W, P, sums, labels, table, stream);
 }
 
-int mask_components_frames_dispatch(const float* mask, int F, int H, int W, int32_t* labels, int32_t* table, void* workspace,
-                                    int64_t workspace_bytes, hipStream_t stream) {
+extern "C" int lp_mask_components_frames(const float* mask, int32_t F, int32_t H, int32_t W, int32_t* labels, int32_t* table,
+                                         void* workspace, int64_t workspace_bytes, void* stream_) {
+    const hipStream_t stream = as_stream(stream_);
     if (!mask || !labels || !table || !workspace || F <= 0 || !side_ok(H) || !side_ok(W)) return LP_E_INVALID;
     if (workspace_bytes < LP_COMPONENTS_FRAMES_WS_BYTES(F, H, W)) return LP_E_INVALID;
     if (!aligned16(workspace)) return LP_E_ALIGN;

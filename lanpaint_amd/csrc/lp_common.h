@@ -766,6 +766,25 @@ void pack_step_args(const StepPlan& p, const lp_step_desc& d, StepArgs* a);
 // does a kernel node launching `func` on grid x block run plan `p`, and nothing else?
 bool plan_is_node(const StepPlan& p, const void* func, const dim3& grid, const dim3& block);
 
+// ---- what cabi.hip's host logic (the sigma call, graph replay) calls in step_kernel.hip and aux_kernels.hip ----
+// Every other entry point of lanpaint_hip.h is defined, extern "C", in the file that holds its kernels; the `void* stream` of
+// the C ABI is a hipStream_t.
+inline hipStream_t as_stream(void* s) { return static_cast<hipStream_t>(s); }
+int step_dispatch(const lp_step_desc* d, hipStream_t stream, void* timer);
+int replace_node_update(const lp_step_desc* d, hipGraphExec_t exec, const lp_graph_binding* b);
+int timer_create(void** out);
+int timer_destroy(void* h);
+int timer_elapsed_ns(void* h, double* ns);
+int coeffs_dispatch(const lp_hyper* h, const float* ve, int ve_stride, const float* abt, int abt_stride,
+                    const float* rs, int rs_stride, const float* step_ov, int step_stride, const float* t_model,
+                    int t_stride, int rows, float* table, hipStream_t stream);
+int finalize_dispatch(const lp_final_desc* d, hipStream_t stream);
+int sigma_times_dispatch(const float* sigma, int rows, const float* schedule, int schedule_len, int is_flow, float* times,
+                         float* scalars, int32_t* seq_out, int32_t seq, hipStream_t stream);
+int sigma_times_rule_dispatch(const float* sigma, int rows, const float* schedule, int schedule_len, int is_flow,
+                              float* times, float* scalars, int32_t* seq_out, int32_t seq, int32_t n_steps, int32_t early_stop,
+                              int32_t total_steps, double min_step_frac, int32_t guess, uint64_t* valid_out, hipStream_t stream);
+
 // The 8-bit code of a value in 0..1 (the propagate section's "1 luma"; the grain and refine sections' codes): clamped, times 255,
 // rounded half up; a NaN gives 0.  A site that packs codes into a word casts to its unsigned type.
 __device__ __forceinline__ int code_of(float v) {

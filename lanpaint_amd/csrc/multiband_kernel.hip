@@ -16,6 +16,7 @@
 // level below or above as the previous launch left it; nothing waits inside a launch.  The rule fixes every value and the
 // order of every operation, so tiling, halos and vector width cannot change a bit; every product, sum and difference below is
 // one __f*_rn call (the library is built with -ffp-contract=on).
+// Entry points defined here: lp_multiband_blend, lp_multiband_ws_bytes.
 #include "lp_common.h"
 
 namespace lp {
@@ -245,7 +246,7 @@ int multiband_levels(int H, int W, int levels, int32_t* h, int32_t* w, int64_t* 
 
 }  // namespace
 
-int64_t multiband_ws_bytes(int batch, int height, int width, int channels, int levels) {
+extern "C" int64_t lp_multiband_ws_bytes(int32_t batch, int32_t height, int32_t width, int32_t channels, int32_t levels) {
     if (batch <= 0 || !side_ok(height) || !side_ok(width) || !chan_ok(channels) || levels < 0) return LP_E_INVALID;
     if (batch > 65535) return LP_E_UNSUPPORTED;
     int32_t h[kMaxLevels + 1], w[kMaxLevels + 1];
@@ -255,7 +256,8 @@ int64_t multiband_ws_bytes(int batch, int height, int width, int channels, int l
     return bytes < 16 ? 16 : (bytes + 15) / 16 * 16;
 }
 
-int multiband_blend_dispatch(const lp_multiband_desc* dp, hipStream_t stream) {
+extern "C" int lp_multiband_blend(const lp_multiband_desc* dp, void* stream_) {
+    const hipStream_t stream = as_stream(stream_);
     if (!dp) return LP_E_INVALID;
     const lp_multiband_desc& d = *dp;
     if (d.batch <= 0 || !side_ok(d.height) || !side_ok(d.width) || !chan_ok(d.channels) || d.levels < 0) return LP_E_INVALID;
@@ -263,7 +265,7 @@ int multiband_blend_dispatch(const lp_multiband_desc* dp, hipStream_t stream) {
     if (d.mask_batch != 1 && d.mask_batch != d.batch) return LP_E_INVALID;
     if (d.batch > 65535) return LP_E_UNSUPPORTED;
     if (!aligned16(d.ws)) return LP_E_ALIGN;
-    if (d.ws_bytes < multiband_ws_bytes(d.batch, d.height, d.width, d.channels, d.levels)) return LP_E_INVALID;
+    if (d.ws_bytes < lp_multiband_ws_bytes(d.batch, d.height, d.width, d.channels, d.levels)) return LP_E_INVALID;
     int32_t h[kMaxLevels + 1], w[kMaxLevels + 1];
     int64_t off[kMaxLevels + 1], pix;
     const int n = multiband_levels(d.height, d.width, d.levels, h, w, off, &pix);

@@ -42,6 +42,9 @@
 //                merge of the subject codes' distances, rounded to a code and split by the nearer key's flags as occlude does.
 // No scratch, no floating point beyond the luma codes, the final c / 256 (read back by occlude) and the merges.  The only atomics
 // are occlude's integer adds into a count: any order gives the same bits.
+// Entry points defined here: the seventeen lp_prop_* (lp_prop_pyramid_ws_bytes, _luma, _key_mask; _match, _fill, _advance, _visible and
+// _occlude, each beside its _batch form, which it calls with a batch of one job; _anchor_match, _anchor_match_gated; _merge,
+// _merge_visible).
 #include "motion_tile.h"
 
 #include <math.h>
@@ -849,12 +852,13 @@ bool jobs_ok(int n) { return n >= 1 && n <= LP_PROP_MAX_JOBS; }
 
 }  // namespace
 
-int64_t prop_pyramid_ws_bytes(int frames, int height, int width, int levels) {
+extern "C" int64_t lp_prop_pyramid_ws_bytes(int32_t frames, int32_t height, int32_t width, int32_t levels) {
     if (frames <= 0 || !side_ok(height) || !side_ok(width) || !levels_ok(levels)) return LP_E_INVALID;
     return static_cast<int64_t>(frames) * level_offset(height, width, levels);
 }
 
-int prop_luma_dispatch(const lp_prop_luma_desc* dp, hipStream_t stream) {
+extern "C" int lp_prop_luma(const lp_prop_luma_desc* dp, void* stream_) {
+    const hipStream_t stream = as_stream(stream_);
     if (!dp) return LP_E_INVALID;
     const lp_prop_luma_desc& d = *dp;
     if (d.frames <= 0 || !side_ok(d.height) || !side_ok(d.width) || !levels_ok(d.levels)) return LP_E_INVALID;
@@ -873,7 +877,8 @@ int prop_luma_dispatch(const lp_prop_luma_desc* dp, hipStream_t stream) {
     return LP_OK;
 }
 
-int prop_key_mask_dispatch(const float* mask, int height, int width, int levels, uint8_t* mpyr, float* out, hipStream_t stream) {
+extern "C" int lp_prop_key_mask(const float* mask, int32_t height, int32_t width, int32_t levels, uint8_t* mpyr, float* out, void* stream_) {
+    const hipStream_t stream = as_stream(stream_);
     if (!mask || !mpyr || !side_ok(height) || !side_ok(width) || !levels_ok(levels)) return LP_E_INVALID;
     if (out == mask) return LP_E_INVALID;
     hipLaunchKernelGGL(lp_prop_key_mask_kernel, dim3(blocks_of(width, kTile), blocks_of(height, kTile)), dim3(256), 0, stream, mask,
@@ -881,7 +886,8 @@ int prop_key_mask_dispatch(const float* mask, int height, int width, int levels,
     return launched();
 }
 
-int prop_match_batch_dispatch(const lp_prop_match_batch_desc* dp, hipStream_t stream) {
+extern "C" int lp_prop_match_batch(const lp_prop_match_batch_desc* dp, void* stream_) {
+    const hipStream_t stream = as_stream(stream_);
     if (!dp) return LP_E_INVALID;
     const lp_prop_match_batch_desc& d = *dp;
     if (!side_ok(d.height) || !side_ok(d.width) || !levels_ok(d.levels) || d.level < 0 || d.level >= d.levels) return LP_E_INVALID;
@@ -908,14 +914,15 @@ int prop_match_batch_dispatch(const lp_prop_match_batch_desc* dp, hipStream_t st
     return launched();
 }
 
-int prop_match_dispatch(const lp_prop_match_desc* dp, hipStream_t stream) {
+extern "C" int lp_prop_match(const lp_prop_match_desc* dp, void* stream) {
     if (!dp) return LP_E_INVALID;
     const lp_prop_match_job job = {dp->src, dp->tgt, dp->mask, dp->parent, dp->vec, dp->valid};
     const lp_prop_match_batch_desc d = {dp->height, dp->width, dp->levels, dp->level, dp->search, dp->smooth, 1, 0, &job};
-    return prop_match_batch_dispatch(&d, stream);
+    return lp_prop_match_batch(&d, stream);
 }
 
-int prop_fill_batch_dispatch(const lp_prop_fill_job* job, int jobs, int gh, int gw, hipStream_t stream) {
+extern "C" int lp_prop_fill_batch(const lp_prop_fill_job* job, int32_t jobs, int32_t gh, int32_t gw, void* stream_) {
+    const hipStream_t stream = as_stream(stream_);
     if (!job || !jobs_ok(jobs) || gh < 1 || gw < 1 || gh > LP_PROP_MAX_GRID || gw > LP_PROP_MAX_GRID) return LP_E_INVALID;
     fill_args a = {};
     a.gh = gh;
@@ -928,12 +935,13 @@ int prop_fill_batch_dispatch(const lp_prop_fill_job* job, int jobs, int gh, int 
     return launched();
 }
 
-int prop_fill_dispatch(const int32_t* vec, const int32_t* valid, int gh, int gw, int32_t* out, hipStream_t stream) {
+extern "C" int lp_prop_fill(const int32_t* vec, const int32_t* valid, int32_t gh, int32_t gw, int32_t* out, void* stream) {
     const lp_prop_fill_job job = {vec, valid, out};
-    return prop_fill_batch_dispatch(&job, 1, gh, gw, stream);
+    return lp_prop_fill_batch(&job, 1, gh, gw, stream);
 }
 
-int prop_advance_batch_dispatch(const lp_prop_advance_batch_desc* dp, hipStream_t stream) {
+extern "C" int lp_prop_advance_batch(const lp_prop_advance_batch_desc* dp, void* stream_) {
+    const hipStream_t stream = as_stream(stream_);
     if (!dp) return LP_E_INVALID;
     const lp_prop_advance_batch_desc& d = *dp;
     if (!side_ok(d.height) || !side_ok(d.width) || !levels_ok(d.levels) || !jobs_ok(d.jobs) || !d.job) return LP_E_INVALID;
@@ -953,14 +961,15 @@ int prop_advance_batch_dispatch(const lp_prop_advance_batch_desc* dp, hipStream_
     return launched();
 }
 
-int prop_advance_dispatch(const lp_prop_advance_desc* dp, hipStream_t stream) {
+extern "C" int lp_prop_advance(const lp_prop_advance_desc* dp, void* stream) {
     if (!dp) return LP_E_INVALID;
     const lp_prop_advance_job job = {dp->vec, dp->pos_src, dp->key, dp->pos_dst, dp->out, dp->mask_pyramid};
     const lp_prop_advance_batch_desc d = {dp->height, dp->width, dp->levels, 1, &job};
-    return prop_advance_batch_dispatch(&d, stream);
+    return lp_prop_advance_batch(&d, stream);
 }
 
-int prop_visible_batch_dispatch(const lp_prop_visible_batch_desc* dp, hipStream_t stream) {
+extern "C" int lp_prop_visible_batch(const lp_prop_visible_batch_desc* dp, void* stream_) {
+    const hipStream_t stream = as_stream(stream_);
     if (!dp) return LP_E_INVALID;
     const lp_prop_visible_batch_desc& d = *dp;
     if (!side_ok(d.height) || !side_ok(d.width) || d.occlusion < 1 || d.occlusion > 255) return LP_E_INVALID;
@@ -984,14 +993,15 @@ int prop_visible_batch_dispatch(const lp_prop_visible_batch_desc* dp, hipStream_
     return launched();
 }
 
-int prop_visible_dispatch(const lp_prop_visible_desc* dp, hipStream_t stream) {
+extern "C" int lp_prop_visible(const lp_prop_visible_desc* dp, void* stream) {
     if (!dp) return LP_E_INVALID;
     const lp_prop_visible_job job = {dp->pos, dp->tgt, dp->key, dp->mask, dp->flags};
     const lp_prop_visible_batch_desc d = {dp->height, dp->width, dp->occlusion, 1, &job};
-    return prop_visible_batch_dispatch(&d, stream);
+    return lp_prop_visible_batch(&d, stream);
 }
 
-int prop_occlude_batch_dispatch(const lp_prop_occlude_batch_desc* dp, hipStream_t stream) {
+extern "C" int lp_prop_occlude_batch(const lp_prop_occlude_batch_desc* dp, void* stream_) {
+    const hipStream_t stream = as_stream(stream_);
     if (!dp) return LP_E_INVALID;
     const lp_prop_occlude_batch_desc& d = *dp;
     if (!side_ok(d.height) || !side_ok(d.width) || !levels_ok(d.levels) || !jobs_ok(d.jobs) || !d.job) return LP_E_INVALID;
@@ -1018,11 +1028,11 @@ int prop_occlude_batch_dispatch(const lp_prop_occlude_batch_desc* dp, hipStream_
     return launched();
 }
 
-int prop_occlude_dispatch(const lp_prop_occlude_desc* dp, hipStream_t stream) {
+extern "C" int lp_prop_occlude(const lp_prop_occlude_desc* dp, void* stream) {
     if (!dp) return LP_E_INVALID;
     const lp_prop_occlude_job job = {dp->code, dp->flags, dp->out, dp->hidden, dp->mask_pyramid, nullptr};
     const lp_prop_occlude_batch_desc d = {dp->height, dp->width, dp->levels, 1, &job};
-    return prop_occlude_batch_dispatch(&d, stream);
+    return lp_prop_occlude_batch(&d, stream);
 }
 
 // The two anchor entries' one dispatch: `gated` null is the anchored form, else the anchored occlusion-aware one.
@@ -1057,20 +1067,23 @@ static int anchor_launch(int height, int width, int anchor, int smooth, int occl
     return launched();
 }
 
-int prop_anchor_match_dispatch(const lp_prop_anchor_desc* dp, hipStream_t stream) {
+extern "C" int lp_prop_anchor_match(const lp_prop_anchor_desc* dp, void* stream_) {
+    const hipStream_t stream = as_stream(stream_);
     if (!dp) return LP_E_INVALID;
     return anchor_launch(dp->height, dp->width, dp->anchor, dp->smooth, 0, dp->pos, dp->tgt, dp->key, dp->mask, dp->vec, dp->valid,
                          nullptr, stream);
 }
 
-int prop_anchor_match_gated_dispatch(const lp_prop_anchor_gated_desc* dp, hipStream_t stream) {
+extern "C" int lp_prop_anchor_match_gated(const lp_prop_anchor_gated_desc* dp, void* stream_) {
+    const hipStream_t stream = as_stream(stream_);
     if (!dp) return LP_E_INVALID;
     if (!dp->gated || dp->occlusion < 1 || dp->occlusion > 255 || dp->reserved0 != 0) return LP_E_INVALID;
     return anchor_launch(dp->height, dp->width, dp->anchor, dp->smooth, dp->occlusion, dp->pos, dp->tgt, dp->key, dp->mask, dp->vec,
                          dp->valid, dp->gated, stream);
 }
 
-int prop_merge_dispatch(const lp_prop_merge_desc* dp, hipStream_t stream) {
+extern "C" int lp_prop_merge(const lp_prop_merge_desc* dp, void* stream_) {
+    const hipStream_t stream = as_stream(stream_);
     if (!dp) return LP_E_INVALID;
     const lp_prop_merge_desc& d = *dp;
     if (!d.qa || !d.qb || !d.out || !side_ok(d.height) || !side_ok(d.width)) return LP_E_INVALID;
@@ -1084,7 +1097,8 @@ int prop_merge_dispatch(const lp_prop_merge_desc* dp, hipStream_t stream) {
     return launched();
 }
 
-int prop_merge_visible_dispatch(const lp_prop_merge_visible_desc* dp, hipStream_t stream) {
+extern "C" int lp_prop_merge_visible(const lp_prop_merge_visible_desc* dp, void* stream_) {
+    const hipStream_t stream = as_stream(stream_);
     if (!dp) return LP_E_INVALID;
     const lp_prop_merge_visible_desc& d = *dp;
     const void* in[10] = {d.qa, d.qb, d.code_a, d.mask_a, d.code_b, d.mask_b, d.flags_a, d.flags_b, d.count_a, d.count_b};

@@ -16,6 +16,7 @@
 // Two launches on the caller's stream.  The sums of stage 3 cost O(r) additions per pixel: the rule fixes their order, which
 // keeps exact zeros away from the mask and makes the result the same bits whatever the tiling.  Every fp64 step goes through
 // __dmul_rn / __dadd_rn / __dsub_rn / __ddiv_rn (the library is built with -ffp-contract=on).  No floating-point atomics.
+// Entry points defined here: lp_mask_refine, lp_refine_ws_bytes.
 #include "lp_common.h"
 
 namespace lp {
@@ -244,13 +245,14 @@ size_t apply_lds(int r) { return static_cast<size_t>(kChunk) * ((kTW + 2 * r) * 
 
 }  // namespace
 
-int64_t refine_ws_bytes(int batch, int height, int width, int channels, int radius) {
+extern "C" int64_t lp_refine_ws_bytes(int32_t batch, int32_t height, int32_t width, int32_t channels, int32_t radius) {
     if (batch <= 0 || !side_ok(height) || !side_ok(width) || !chan_ok(channels) || !radius_ok(radius)) return LP_E_INVALID;
     if (batch > 65535) return LP_E_UNSUPPORTED;
     return static_cast<int64_t>(batch) * height * width * 16;
 }
 
-int mask_refine_dispatch(const lp_refine_desc* dp, hipStream_t stream) {
+extern "C" int lp_mask_refine(const lp_refine_desc* dp, void* stream_) {
+    const hipStream_t stream = as_stream(stream_);
     if (!dp) return LP_E_INVALID;
     const lp_refine_desc& d = *dp;
     if (d.batch <= 0 || !side_ok(d.height) || !side_ok(d.width) || !chan_ok(d.channels) || !radius_ok(d.radius)) return LP_E_INVALID;
@@ -259,7 +261,7 @@ int mask_refine_dispatch(const lp_refine_desc* dp, hipStream_t stream) {
     if (d.mask_batch != 1 && d.mask_batch != d.batch) return LP_E_INVALID;
     if (d.batch > 65535) return LP_E_UNSUPPORTED;
     if (!aligned16(d.ws)) return LP_E_ALIGN;
-    if (d.ws_bytes < refine_ws_bytes(d.batch, d.height, d.width, d.channels, d.radius)) return LP_E_INVALID;
+    if (d.ws_bytes < lp_refine_ws_bytes(d.batch, d.height, d.width, d.channels, d.radius)) return LP_E_INVALID;
     const size_t lds_c = coeff_lds(d.radius), lds_a = apply_lds(d.radius);       // at r = 64: 135 808 and 57 344 bytes
     if (lds_c > 64 * 1024 &&
         hipFuncSetAttribute(reinterpret_cast<const void*>(&lp_refine_coeff_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,

@@ -16,6 +16,7 @@
 //            neighbours.  The cut bits of 64 consecutive pairs are one ballot word in LDS; the words' counts are scanned (four
 //            words a lane, then the lanes' sums), and shot[f] is a word's prefix plus the count of the bits up to pair f - 1.
 // Integers only: the atomics are integer adds, any order gives the same bits.  No scratch, no floating point.
+// Entry points defined here: lp_shot_measure, lp_shot_decide.
 #include "motion_tile.h"
 
 namespace lp {
@@ -180,7 +181,8 @@ __global__ __launch_bounds__(256) void lp_shot_decide_kernel(const decide_args a
 
 }  // namespace
 
-int shot_measure_dispatch(const lp_shot_measure_desc* dp, hipStream_t stream) {
+extern "C" int lp_shot_measure(const lp_shot_measure_desc* dp, void* stream_) {
+    const hipStream_t stream = as_stream(stream_);
     if (!dp) return LP_E_INVALID;
     const lp_shot_measure_desc& d = *dp;
     if (d.frames < 1 || !side_ok(d.height) || !side_ok(d.width) || d.search < 1 || d.search > LP_SHOT_MAX_SEARCH) return LP_E_INVALID;
@@ -208,7 +210,8 @@ int shot_measure_dispatch(const lp_shot_measure_desc* dp, hipStream_t stream) {
     return launched();
 }
 
-int shot_decide_dispatch(const lp_shot_decide_desc* dp, hipStream_t stream) {
+extern "C" int lp_shot_decide(const lp_shot_decide_desc* dp, void* stream_) {
+    const hipStream_t stream = as_stream(stream_);
     if (!dp) return LP_E_INVALID;
     const lp_shot_decide_desc& d = *dp;
     if (d.frames < 1) return LP_E_INVALID;

@@ -18,6 +18,7 @@
 // fewer taps gives the outer taps the weight 0.0, whose products are +-0.0 and leave the sum's bits alone (the sum starts from +0.0
 // and the capped distances are finite).  Every fp64 step goes through __dmul_rn / __dadd_rn / __ddiv_rn (the library is built with
 // -ffp-contract=on).  No scratch, no LDS, no atomics.
+// Entry points defined here: lp_mask_signed_d2, lp_mask_stabilize.
 #include "lp_common.h"
 
 #include <math.h>
@@ -133,7 +134,8 @@ int launch(const stab_args& a, dim3 grid, hipStream_t stream) {
 
 }  // namespace
 
-int mask_signed_d2_dispatch(const int32_t* d2, int frames, int height, int width, int32_t* q, hipStream_t stream) {
+extern "C" int lp_mask_signed_d2(const int32_t* d2, int32_t frames, int32_t height, int32_t width, int32_t* q, void* stream_) {
+    const hipStream_t stream = as_stream(stream_);
     if (!d2 || !q || d2 == q || frames <= 0 || !side_ok(height) || !side_ok(width)) return LP_E_INVALID;
     const int64_t plane = static_cast<int64_t>(height) * width;
     const dim3 grid(static_cast<uint32_t>((plane + kBlock - 1) / kBlock), static_cast<uint32_t>(std::min(frames, 65535)));
@@ -141,7 +143,8 @@ int mask_signed_d2_dispatch(const int32_t* d2, int frames, int height, int width
     return hipGetLastError() == hipSuccess ? LP_OK : LP_E_LAUNCH;
 }
 
-int mask_stabilize_dispatch(const lp_stabilize_desc* dp, hipStream_t stream) {
+extern "C" int lp_mask_stabilize(const lp_stabilize_desc* dp, void* stream_) {
+    const hipStream_t stream = as_stream(stream_);
     if (!dp) return LP_E_INVALID;
     const lp_stabilize_desc& d = *dp;
     if (d.frames <= 0 || !side_ok(d.height) || !side_ok(d.width)) return LP_E_INVALID;

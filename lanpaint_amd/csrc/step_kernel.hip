@@ -18,6 +18,8 @@
 //   exact OU step + noise       lanpaint.py:232-254
 //   overdamped scheme           lanpaint.py:274-286 (second half-step uses the OLD C)
 //   back to model space         lanpaint.py:144-147, 163, 168
+// No entry point is defined here: lp_step, its timed forms and the graph entries are in cabi.hip, which calls plan_step,
+// step_dispatch, replace_node_update and the timer functions below (declared in lp_common.h).
 #include <cstddef>
 
 #include "lp_common.h"

@@ -16,6 +16,7 @@
 //                that disagrees is handed back to `remaining`.  The backward sample is gathered wherever it exists.
 // Integer arithmetic decides everything but the sample, which is fp32 in a fixed order, every operation rounded on its own
 // (__fmul_rn / __fadd_rn: nothing contracts).  No scratch, no atomics.
+// Entry points defined here: lp_tfill_known, lp_tfill_carry, lp_tfill_carry_pair.
 #include "motion_tile.h"
 
 namespace lp {
@@ -282,7 +283,8 @@ int carry_args_of(const lp_tfill_carry_desc& d, const void* extra, carry_args& a
 
 }  // namespace
 
-int tfill_known_dispatch(const lp_tfill_known_desc* dp, hipStream_t stream) {
+extern "C" int lp_tfill_known(const lp_tfill_known_desc* dp, void* stream_) {
+    const hipStream_t stream = as_stream(stream_);
     if (!dp) return LP_E_INVALID;
     const lp_tfill_known_desc& d = *dp;
     if (d.frames <= 0 || !side_ok(d.height) || !side_ok(d.width) || !levels_ok(d.levels)) return LP_E_INVALID;
@@ -309,7 +311,8 @@ int tfill_known_dispatch(const lp_tfill_known_desc* dp, hipStream_t stream) {
     return LP_OK;
 }
 
-int tfill_carry_dispatch(const lp_tfill_carry_desc* dp, hipStream_t stream) {
+extern "C" int lp_tfill_carry(const lp_tfill_carry_desc* dp, void* stream_) {
+    const hipStream_t stream = as_stream(stream_);
     if (!dp) return LP_E_INVALID;
     carry_args a = {};
     const int status = carry_args_of(*dp, nullptr, a);
@@ -318,7 +321,8 @@ int tfill_carry_dispatch(const lp_tfill_carry_desc* dp, hipStream_t stream) {
     return launched();
 }
 
-int tfill_carry_pair_dispatch(const lp_tfill_carry_pair_desc* dp, hipStream_t stream) {
+extern "C" int lp_tfill_carry_pair(const lp_tfill_carry_pair_desc* dp, void* stream_) {
+    const hipStream_t stream = as_stream(stream_);
     if (!dp) return LP_E_INVALID;
     if (dp->agree < 1 || dp->agree > 255) return LP_E_INVALID;
     const lp_tfill_carry_desc d = {dp->frames, dp->height, dp->width, dp->channels, dp->frame, dp->donor, dp->reach, 1,

@@ -26,6 +26,7 @@
 //            and for the acceptance against r and the sums, the first four channels while the walk decides, every further four
 //            in a walk of their own.  What exists is two counts, what is accepted a bit mask in one register.  No array is
 //            indexed by a register: nothing in scratch, no LDS.
+// Entry points defined here: lp_tsmooth, lp_tsmooth_robust.
 #include "motion_tile.h"
 
 namespace lp {
@@ -465,7 +466,8 @@ int smooth_args_of(const lp_tsmooth_desc& d, const void* extra, smooth_args& a) 
 
 }  // namespace
 
-int tsmooth_dispatch(const lp_tsmooth_desc* dp, hipStream_t stream) {
+extern "C" int lp_tsmooth(const lp_tsmooth_desc* dp, void* stream_) {
+    const hipStream_t stream = as_stream(stream_);
     if (!dp) return LP_E_INVALID;
     smooth_args a = {};
     const int status = smooth_args_of(*dp, nullptr, a);
@@ -475,7 +477,8 @@ int tsmooth_dispatch(const lp_tsmooth_desc* dp, hipStream_t stream) {
     return launched();
 }
 
-int tsmooth_robust_dispatch(const lp_tsmooth_robust_desc* dp, hipStream_t stream) {
+extern "C" int lp_tsmooth_robust(const lp_tsmooth_robust_desc* dp, void* stream_) {
+    const hipStream_t stream = as_stream(stream_);
     if (!dp) return LP_E_INVALID;
     if (!dp->replaced) return LP_E_INVALID;
     const lp_tsmooth_desc d = {dp->frames, dp->height, dp->width, dp->channels, dp->first, dp->count, dp->radius, dp->tolerance,

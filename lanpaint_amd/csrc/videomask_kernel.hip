@@ -10,6 +10,7 @@
 //   lp_vmask_resize  Pillow's 8-bit two-pass BILINEAR from host-built coefficient tables, both passes in one launch: a block
 //                    stages the horizontal pass of the source rows its output tile needs in LDS, then runs the vertical
 //                    pass and writes fp32 -- the only large tensor, written once, 16 B per lane.
+// Entry points defined here: lp_vmask_edt, lp_vmask_morph, lp_vmask_resize.
 #include "lp_common.h"
 #include "resample_tile.h"
 
@@ -236,7 +237,8 @@ bool side_ok(int s) { return s > 0 && s <= LP_VMASK_MAX_SIDE; }
 
 }  // namespace
 
-int vmask_edt_dispatch(const lp_vmask_edt_desc* dp, hipStream_t stream) {
+extern "C" int lp_vmask_edt(const lp_vmask_edt_desc* dp, void* stream_) {
+    const hipStream_t stream = as_stream(stream_);
     if (!dp) return LP_E_INVALID;
     const lp_vmask_edt_desc& d = *dp;
     if (d.n_keys <= 0 || !side_ok(d.height) || !side_ok(d.width)) return LP_E_INVALID;
@@ -261,7 +263,8 @@ int vmask_edt_dispatch(const lp_vmask_edt_desc* dp, hipStream_t stream) {
     return hipGetLastError() == hipSuccess ? LP_OK : LP_E_LAUNCH;
 }
 
-int vmask_morph_dispatch(const lp_vmask_morph_desc* dp, hipStream_t stream) {
+extern "C" int lp_vmask_morph(const lp_vmask_morph_desc* dp, void* stream_) {
+    const hipStream_t stream = as_stream(stream_);
     if (!dp) return LP_E_INVALID;
     const lp_vmask_morph_desc& d = *dp;
     if (d.n_frames <= 0 || d.n_keys <= 0 || !side_ok(d.height) || !side_ok(d.width)) return LP_E_INVALID;
@@ -273,7 +276,8 @@ int vmask_morph_dispatch(const lp_vmask_morph_desc* dp, hipStream_t stream) {
     return hipGetLastError() == hipSuccess ? LP_OK : LP_E_LAUNCH;
 }
 
-int vmask_resize_dispatch(const lp_vmask_resize_desc* dp, hipStream_t stream) {
+extern "C" int lp_vmask_resize(const lp_vmask_resize_desc* dp, void* stream_) {
+    const hipStream_t stream = as_stream(stream_);
     if (!dp) return LP_E_INVALID;
     const lp_vmask_resize_desc& d = *dp;
     if (d.n_frames <= 0 || !side_ok(d.in_h) || !side_ok(d.in_w) || !side_ok(d.out_h) || !side_ok(d.out_w)) return LP_E_INVALID;

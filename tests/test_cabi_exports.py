@@ -39,6 +39,79 @@ def test_the_c_abi_is_the_only_dynamic_surface(hip_lib):
         assert re.search(r"LP_API\s+[a-z_0-9 \*]+\b%s\s*\(" % n, hdr), n
 
 
+# What cabi.hip keeps: the version and error text, the sigma-call family whose launches its own host logic also makes, and the
+# entries that block the host or drive graph handles.  Every other entry is defined next to its kernels and begins with its
+# argument checks.
+_HOST_LOGIC_ENTRIES = {
+    "lp_abi_version", "lp_strerror",
+    "lp_step", "lp_step_timed", "lp_step_timed_burst", "lp_timer_create", "lp_timer_destroy", "lp_timer_elapsed_ns",
+    "lp_coeffs", "lp_finalize", "lp_sigma_times", "lp_sigma_times_mailbox",
+    "lp_replay_call", "lp_replay_burst", "lp_graph_bind_replace", "lp_graph_clone_tail", "lp_graph_clone_sigma_root",
+    "lp_graph_release", "lp_node_call", "lp_effective_inner_steps"}
+
+
+def test_every_launching_entry_refuses_null_arguments_before_touching_the_device(hip_lib):
+    """Each entry that lives beside its kernels, called with NULL for every pointer and 0 for every number, returns
+    LP_E_INVALID -- here, without a GPU, so no HIP call was made on the way.  The excluded names are spelled out and must
+    make up EXPORTS together with the called ones: a new entry cannot be left out of both."""
+    assert len(_HOST_LOGIC_ENTRIES) == 20 and _HOST_LOGIC_ENTRIES <= set(_cabi.EXPORTS)
+    called = {}
+    for name, (_res, argtypes) in _cabi.EXPORTS.items():
+        if name in _HOST_LOGIC_ENTRIES:
+            continue
+        args = [None if issubclass(t, (ctypes._Pointer, ctypes.c_void_p, ctypes.c_char_p)) else 0 for t in argtypes]
+        called[name] = getattr(hip_lib, name)(*args)
+    assert _HOST_LOGIC_ENTRIES | set(called) == set(_cabi.EXPORTS) and len(called) == 65
+    wrong = {n: rc for n, rc in called.items() if rc != _cabi.LP_E_INVALID}
+    assert not wrong, wrong
+
+
+def _without_comments(src):
+    src = re.sub(r"/\*.*?\*/", lambda m: re.sub(r"[^\n]", " ", m.group(0)), src, flags=re.S)
+    return re.sub(r"//[^\n]*", "", src)
+
+
+def _column0_functions(src):
+    """(name, is_definition) of every function declared or defined from column 0: a return type, a name, a parenthesised
+    parameter list, then `{` (a definition) or `;` (a prototype).  Macros, static_asserts and variable initialisers have no
+    `type name(` shape; calls and nested declarations are indented."""
+    out = []
+    for m in re.finditer(r'^(?:extern "C" )?(?:template\s*<[^\n]*>\s*)?[A-Za-z_][\w:<>,\*& ]*?[\s\*&]([A-Za-z_]\w*)\s*\(', src, flags=re.M):
+        if m.group(1) in ("__attribute__", "__launch_bounds__", "alignas"):
+            continue
+        depth, i = 1, m.end()
+        while depth and i < len(src):
+            depth += {"(": 1, ")": -1}.get(src[i], 0)
+            i += 1
+        rest = src[i:].lstrip()
+        while rest.startswith(("const", "noexcept")):
+            rest = rest.split(None, 1)[1] if " " in rest else ""
+        if rest[:1] in "{;":
+            out.append((m.group(1), rest[0] == "{"))
+    return out
+
+
+def test_each_entry_is_defined_once_and_no_source_declares_anothers_function():
+    """Every function of include/lanpaint_hip.h has exactly one definition among build.SOURCES, in the one file that holds its
+    kernels or in cabi.hip; and no .hip file holds a prototype -- a function another .hip defines is declared in lp_common.h
+    or in the public header, where the compiler holds the definition against it."""
+    from lanpaint_amd import build
+    defined, prototypes = {}, []
+    for f in build.SOURCES:
+        funcs = _column0_functions(_without_comments(open(os.path.join(build.CSRC, f)).read()))
+        assert funcs, f
+        for name, is_def in funcs:
+            if not is_def:
+                prototypes.append((f, name))
+            elif name.startswith("lp_") and not name.endswith("_kernel"):
+                defined.setdefault(name, []).append(f)
+    assert not prototypes, prototypes
+    declared = _declared_functions()
+    assert len(declared) == len(_cabi.EXPORTS)
+    assert {n: defined.get(n, []) for n in declared if len(defined.get(n, [])) != 1} == {}
+    assert sorted(defined) == declared, sorted(set(defined) ^ set(declared))
+
+
 def test_graph_utilities_reject_bad_arguments_without_touching_the_device(hip_lib):
     """lp_replay_burst / lp_graph_clone_sigma_root / lp_graph_bind_replace validate before any HIP call: usable error codes on a
     box without a GPU."""

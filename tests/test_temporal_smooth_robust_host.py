@@ -262,7 +262,7 @@ def test_the_names_are_everywhere_and_the_abi_version_stays(hip_lib):
     assert "lp_tsmooth_robust" in _cabi.EXPORTS and hasattr(hip_lib, "lp_tsmooth_robust")
     assert re.search(r"\bT lp_tsmooth_robust$", dynamic, flags=re.M) and re.search(r"\bT lp_tsmooth$", dynamic, flags=re.M)
     assert _cabi.ABI_VERSION == 25 and hip_lib.lp_abi_version() == 25
-    assert "tsmooth_robust_dispatch" in read("lanpaint_amd", "csrc", "cabi.hip")
+    assert 'extern "C" int lp_tsmooth_robust(' in read("lanpaint_amd", "csrc", "temporal_smooth_kernel.hip")   # beside its kernels
     assert header.index("Robust video temporal smooth") > header.index("LP_API int lp_tsmooth(")      # the section stands behind the plain one
     for word in ("LP_TSMOOTH_ROBUST_QUORUM", "lower median", "(n - 1) >> 1", "ties broken by the walk's order", "does NOT end at a sample",
                  "two witnesses overrule", "replaced = 1", "replaced = -1", "keeps x bit for bit", "R frames or fewer", "n < 3",
