@@ -1592,6 +1592,7 @@ LP_API int lp_prop_advance(const lp_prop_advance_desc* desc, void* stream);
  * single entries check.  lp_prop_merge: a null pointer, a side outside 1..LP_VMASK_MAX_SIDE, span < 2, first < 1, frames < 1,
  * first + frames - 1 > span - 1, out aliasing qa or qb; LP_E_UNSUPPORTED: span > 65535.  All checked before any HIP call.            */
 #define LP_PROP_MAX_JOBS    32
+#define LP_PROP_MATCH_WARPED_KEY 1                /* lp_prop_match_batch_desc.reserved0: the several-keys anchored section  */
 
 typedef struct lp_prop_match_job {
     const uint8_t* src;                           /* as in lp_prop_match_desc                                               */
@@ -1605,7 +1606,9 @@ typedef struct lp_prop_match_job {
 typedef struct lp_prop_match_batch_desc {
     int32_t height, width, levels, level;
     int32_t search, smooth;
-    int32_t jobs, reserved0;                      /* jobs 1..LP_PROP_MAX_JOBS                                               */
+    int32_t jobs, reserved0;                      /* jobs 1..LP_PROP_MAX_JOBS; reserved0 is the source form: 0 the source
+                                                     frame's luma, LP_PROP_MATCH_WARPED_KEY the key frame's luma warped
+                                                     through the job's positions (the several-keys anchored section)       */
     const lp_prop_match_job* job;                 /* host memory, `jobs` entries                                            */
 } lp_prop_match_batch_desc;
 LP_API int lp_prop_match_batch(const lp_prop_match_batch_desc* desc, void* stream);
@@ -1824,7 +1827,7 @@ LP_API int lp_prop_merge_visible(const lp_prop_merge_visible_desc* desc, void* s
  * Not handled: anchoring inside the occlusion-aware and the several-keys forms (an occluded block would be matched against the
  * occluder); a subject whose look changes away from the key (turning, relighting beyond what `smooth` refuses) gets e ~ 0 there and
  * drifts as before; re-anchoring every n-th frame only.  (Anchoring inside the single-key occlusion-aware form is the section
- * behind this one, lp_prop_anchor_match_gated.)
+ * behind this one, lp_prop_anchor_match_gated; anchoring inside the several-keys form the one behind that.)
  * Launch (csrc/propagate_kernel.hip): lp_prop_anchor_match fuses the warp and the match, K never goes to memory.  A block of 256
  * lanes per 32 x 32 pixels, that is 4 x 4 level-0 blocks: K of the tile and its halo of 4 (40 x 40 bytes, ANDed with the per-byte
  * mask beside it) goes to LDS once, gathered through P_t, which is read as 16-byte vectors when width % 4 == 0 and the planes are
@@ -1895,6 +1898,28 @@ typedef struct lp_prop_anchor_gated_desc {
     int32_t*       gated;                         /* out, [gh, gw], 0 / 1: a live block that does not look like the key     */
 } lp_prop_anchor_gated_desc;
 LP_API int lp_prop_anchor_match_gated(const lp_prop_anchor_gated_desc* desc, void* stream);
+
+/* ---- Video mask propagate from several keys, anchored (beyond the reference) ----------------------------------------------------------
+ * Between two keys the merge pins the mask to each painting, but half way through a long gap both chains have fallen behind the
+ * subject by the drift the anchored section describes.  The rule of this form is the several-keys rule with one change: each chain
+ * is the anchored chain of its key (the anchored section's steps 1 to 5, the key frame of the chain as Yk); the plan of the chains,
+ * what a key frame and a frame outside the keys return, and the merge are unchanged.  K = 1 is the anchored single-key form bit for
+ * bit; anchor = 0 is the caller's "off": the several-keys form, its launches only.  A still video with the same mask on every key
+ * returns that binarised mask; empty stays exactly 0 and full exactly 1.0.
+ * No new entry: the batched re-match is lp_prop_match_batch with reserved0 = LP_PROP_MATCH_WARPED_KEY, since a match job and an anchor
+ * job are the same six pointers.  reserved0 = 0 keeps the meaning and the bits it had; any other value is LP_E_INVALID.  With
+ * LP_PROP_MATCH_WARPED_KEY, per job: src is the key frame's luma pyramid and tgt the frame's (level 0 of each is read), mask the
+ * pyramid whose level 0 is m, parent the positions P_t int32 [height, width, 2], required whatever `levels` is; level must be 0;
+ * search is the anchor, 1..LP_PROP_MAX_SEARCH; vec and valid alias no input and not each other.  The result is exactly
+ * lp_prop_anchor_match's for that job: lp_prop_anchor_match and lp_prop_anchor_match_gated are one-job launches of the same kernel,
+ * which takes its job from a table on blockIdx.z (32 x 56 bytes by value in its arguments, a `wide` bit per job).
+ * A step of a group of up to LP_PROP_MAX_JOBS chains is 2 L + 4 launches:
+ *   lp_prop_match_batch / lp_prop_fill_batch per level -> lp_prop_advance_batch (P_t, m to per-chain scratch)
+ *     -> lp_prop_match_batch (warped key) -> lp_prop_fill_batch -> lp_prop_advance_batch (vec = e, pos_src = P_t).
+ * Not handled here: anchoring inside the several-keys occlusion-aware form -- a gated batch needs a third output and `occlusion`,
+ * which this job does not hold; what the anchored section lists.
+ * LP_E_INVALID in the warped form: level != 0, search outside 1..LP_PROP_MAX_SEARCH, a null pointer in any job (parent included),
+ * vec or valid aliasing an input or one another, next to every range lp_prop_match_batch checks.  All checked before any HIP call. */
 
 /* ---- Video temporal fill (beyond the reference) -------------------------------------------------------------------------------------
  * What lies under the mask of a video frame is, in most clips, plain background a few frames earlier or later: a subject moves

@@ -396,6 +396,7 @@ class LpPropAdvanceDesc(C.Structure):
 
 
 LP_PROP_MAX_JOBS = 32
+LP_PROP_MATCH_WARPED_KEY = 1                                         # LpPropMatchBatchDesc.reserved0: the source form
 
 
 class LpPropMatchJob(C.Structure):

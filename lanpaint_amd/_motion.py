@@ -1,5 +1,5 @@
 """What the motion modules (propagate, propagate_visible, propagate_anchored, propagate_anchored_visible, propagate_keys,
-propagate_keys_visible, temporal_fill, temporal_fill_checked, temporal_smooth, temporal_smooth_robust, shots) share on top of
+propagate_keys_visible, propagate_keys_anchored, temporal_fill, temporal_fill_checked, temporal_smooth, temporal_smooth_robust, shots) share on top of
 _hostcall.py: the checks of the block matcher's numbers and planes, of a frame's planes next to the warped key frame
 (`check_frame_planes`), the clip-mask shapes, the luma pyramids, and the batched coarse-to-fine field walk.  Plain
 functions and one small class; no nodes, nothing of the engine's path.  HIP tensors only, no CPU fallback.

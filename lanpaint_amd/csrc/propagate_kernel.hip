@@ -586,7 +586,7 @@ static_assert(4 * kAncPatPitch >= kAncPatRows, "a patch row holds the tile, its 
 static_assert((kTile - kB + 2 * LP_PROP_MAX_SEARCH) / 4 + 4 < kAncPatPitch, "a window row's four dwords and the one behind them lie inside a patch row");
 static_assert(kWin * 4 == kWave, "a lane per dword of a window's mask");
 
-struct anchor_args {
+struct anchor_job {
     const int32_t* pos;
     const uint8_t* tgt;
     const uint8_t* key;
@@ -594,8 +594,15 @@ struct anchor_args {
     int32_t*       vec;
     int32_t*       valid;
     int32_t*       gated;                                            // the gated form's third output, else null
-    int32_t H, W, gh, gw, search, smooth, wide, occlusion;
 };
+
+struct anchor_args {
+    int32_t  H, W, gh, gw, search, smooth, occlusion;
+    uint32_t wide;                                                   // bit i: job i takes the vector path
+    anchor_job job[LP_PROP_MAX_JOBS];
+};
+
+static_assert(sizeof(anchor_args) <= 4096, "the job table travels by value in the kernel's arguments");
 
 // Gated: the anchored occlusion-aware form.  Behind the wave-wide minimum every lane knows the winner; lane = row * 4 + dword of the
 // window cuts its four target pixels for the winner out of s_pat and takes lp_prop_visible's statistic there: D, mu and R over the
@@ -604,10 +611,14 @@ template <bool Gated>
 __global__ __launch_bounds__(256) void lp_prop_anchor_match_kernel(const anchor_args a) {
     __shared__ uint32_t s_src[kVisSide * kAncPitch], s_bm[kVisSide * kAncPitch], s_pat[kAncPatRows * kAncPatPitch];
     __shared__ int32_t s_S[4][kMaxCand];
-    const int32_t* __restrict__ pos = a.pos;
-    const uint8_t* __restrict__ tgt = a.tgt;
-    const uint8_t* __restrict__ key = a.key;
-    const uint8_t* __restrict__ msk = a.msk;
+    const int32_t* __restrict__ pos = a.job[blockIdx.z].pos;
+    const uint8_t* __restrict__ tgt = a.job[blockIdx.z].tgt;
+    const uint8_t* __restrict__ key = a.job[blockIdx.z].key;
+    const uint8_t* __restrict__ msk = a.job[blockIdx.z].msk;
+    int32_t* __restrict__ vec = a.job[blockIdx.z].vec;
+    int32_t* __restrict__ valid = a.job[blockIdx.z].valid;
+    int32_t* __restrict__ gated = Gated ? a.job[blockIdx.z].gated : nullptr;
+    const int wide = static_cast<int>((a.wide >> blockIdx.z) & 1u);
     const int tid = threadIdx.x, lane = tid & (kWave - 1), wv = tid >> 6;
     const int H = a.H, W = a.W, R = a.search, n = 2 * R + 1, ncand = n * n;
     const int y00 = blockIdx.y * kTile - kHalo, x00 = blockIdx.x * kTile - kHalo;     // x00 is a multiple of 4
@@ -620,7 +631,7 @@ __global__ __launch_bounds__(256) void lp_prop_anchor_match_kernel(const anchor_
         uint32_t sv = 0, bm = 0;
         if (y >= 0 && y < H && x + 3 >= 0 && x < W) {
             const int64_t p = static_cast<int64_t>(y) * W + x;
-            if (a.wide) {                                                // x >= 0 and x + 3 < W; p is a multiple of 4
+            if (wide) {                                                  // x >= 0 and x + 3 < W; p is a multiple of 4
                 const uchar4 m4 = *reinterpret_cast<const uchar4*>(msk + p);
                 if (m4.x | m4.y | m4.z | m4.w) {
                     const int4 pa = *reinterpret_cast<const int4*>(pos + p * 2), pb = *reinterpret_cast<const int4*>(pos + p * 2 + 4);
@@ -647,10 +658,10 @@ __global__ __launch_bounds__(256) void lp_prop_anchor_match_kernel(const anchor_
         const int by = by0 + (tid >> 2), bx = bx0 + (tid & 3);
         if (tid < 16 && by < a.gh && bx < a.gw) {
             const int64_t cell = static_cast<int64_t>(by) * a.gw + bx;
-            a.vec[cell * 2] = 0;
-            a.vec[cell * 2 + 1] = 0;
-            a.valid[cell] = 0;
-            if (Gated) a.gated[cell] = 0;
+            vec[cell * 2] = 0;
+            vec[cell * 2 + 1] = 0;
+            valid[cell] = 0;
+            if (Gated) gated[cell] = 0;
         }
         return;
     }
@@ -740,10 +751,10 @@ __global__ __launch_bounds__(256) void lp_prop_anchor_match_kernel(const anchor_
                 }
             }
             const int64_t cell = static_cast<int64_t>(by) * a.gw + bx;
-            a.vec[cell * 2] = vy;
-            a.vec[cell * 2 + 1] = vx;
-            a.valid[cell] = live && !gate ? 1 : 0;
-            if (Gated) a.gated[cell] = gate ? 1 : 0;
+            vec[cell * 2] = vy;
+            vec[cell * 2 + 1] = vx;
+            valid[cell] = live && !gate ? 1 : 0;
+            if (Gated) gated[cell] = gate ? 1 : 0;
         }
     }
 }
@@ -886,13 +897,62 @@ extern "C" int lp_prop_key_mask(const float* mask, int32_t height, int32_t width
     return launched();
 }
 
+// The anchor match's one dispatch, `jobs` of them on blockIdx.z: the two single entries with one job, `gated` the anchored
+// occlusion-aware form's, and lp_prop_match_batch's warped-key form.
+static int anchor_launch(int height, int width, int anchor, int smooth, int occlusion, const anchor_job* job, int jobs, bool gated,
+                         hipStream_t stream) {
+    if (!side_ok(height) || !side_ok(width)) return LP_E_INVALID;
+    if (anchor < 1 || anchor > LP_PROP_MAX_SEARCH || smooth < 0 || smooth > LP_PROP_MAX_SMOOTH) return LP_E_INVALID;
+    if (!jobs_ok(jobs) || !job) return LP_E_INVALID;
+    anchor_args a = {};
+    for (int i = 0; i < jobs; ++i) {
+        const anchor_job& j = job[i];
+        if (!j.pos || !j.tgt || !j.key || !j.msk || !j.vec || !j.valid || (j.gated != nullptr) != gated) return LP_E_INVALID;
+        const void* outs[3] = {j.vec, j.valid, j.gated};
+        for (int k = 0; k < 3; ++k) {                                    // gated may be null; an output aliases nothing
+            if (!outs[k]) continue;
+            for (const void* in : {static_cast<const void*>(j.pos), static_cast<const void*>(j.tgt), static_cast<const void*>(j.key),
+                                   static_cast<const void*>(j.msk)})
+                if (outs[k] == in) return LP_E_INVALID;
+            for (int m = k + 1; m < 3; ++m)
+                if (outs[k] == outs[m]) return LP_E_INVALID;
+        }
+        a.job[i] = j;
+        // wide: the kernel reads a row's four pixels as one vector
+        if (width % 4 == 0 && aligned16(j.pos) && aligned16(j.msk)) a.wide |= 1u << i;
+    }
+    a.H = height;
+    a.W = width;
+    a.gh = (height + kB - 1) / kB;
+    a.gw = (width + kB - 1) / kB;
+    a.search = anchor;
+    a.smooth = smooth;
+    a.occlusion = occlusion;
+    const dim3 grid(blocks_of(width, kTile), blocks_of(height, kTile), jobs);
+    if (gated)
+        hipLaunchKernelGGL(lp_prop_anchor_match_kernel<true>, grid, dim3(256), 0, stream, a);
+    else
+        hipLaunchKernelGGL(lp_prop_anchor_match_kernel<false>, grid, dim3(256), 0, stream, a);
+    return launched();
+}
+
 extern "C" int lp_prop_match_batch(const lp_prop_match_batch_desc* dp, void* stream_) {
     const hipStream_t stream = as_stream(stream_);
     if (!dp) return LP_E_INVALID;
     const lp_prop_match_batch_desc& d = *dp;
+    if (d.reserved0 != 0 && d.reserved0 != LP_PROP_MATCH_WARPED_KEY) return LP_E_INVALID;
     if (!side_ok(d.height) || !side_ok(d.width) || !levels_ok(d.levels) || d.level < 0 || d.level >= d.levels) return LP_E_INVALID;
     if (d.search < 1 || d.search > LP_PROP_MAX_SEARCH || d.smooth < 0 || d.smooth > LP_PROP_MAX_SMOOTH) return LP_E_INVALID;
     if (!jobs_ok(d.jobs) || !d.job) return LP_E_INVALID;
+    if (d.reserved0 == LP_PROP_MATCH_WARPED_KEY) {                       // the anchor match: level 0 of the three pyramids is their start
+        if (d.level != 0) return LP_E_INVALID;
+        anchor_job job[LP_PROP_MAX_JOBS];
+        for (int i = 0; i < d.jobs; ++i) {
+            const lp_prop_match_job& j = d.job[i];
+            job[i] = {j.parent, j.tgt, j.src, j.mask, j.vec, j.valid, nullptr};
+        }
+        return anchor_launch(d.height, d.width, d.search, d.smooth, 0, job, d.jobs, false, stream);
+    }
     match_args a = {};
     const int64_t off = level_offset(d.height, d.width, d.level);
     for (int i = 0; i < d.jobs; ++i) {
@@ -1035,51 +1095,19 @@ extern "C" int lp_prop_occlude(const lp_prop_occlude_desc* dp, void* stream) {
     return lp_prop_occlude_batch(&d, stream);
 }
 
-// The two anchor entries' one dispatch: `gated` null is the anchored form, else the anchored occlusion-aware one.
-static int anchor_launch(int height, int width, int anchor, int smooth, int occlusion, const int32_t* pos, const uint8_t* tgt,
-                         const uint8_t* key, const uint8_t* mask, int32_t* vec, int32_t* valid, int32_t* gated, hipStream_t stream) {
-    if (!side_ok(height) || !side_ok(width)) return LP_E_INVALID;
-    if (anchor < 1 || anchor > LP_PROP_MAX_SEARCH || smooth < 0 || smooth > LP_PROP_MAX_SMOOTH) return LP_E_INVALID;
-    if (!pos || !tgt || !key || !mask || !vec || !valid) return LP_E_INVALID;
-    const void* outs[3] = {vec, valid, gated};
-    for (int k = 0; k < 3; ++k) {                                        // gated may be null; an output aliases nothing
-        if (!outs[k]) continue;
-        for (const void* in : {static_cast<const void*>(pos), static_cast<const void*>(tgt), static_cast<const void*>(key),
-                               static_cast<const void*>(mask)})
-            if (outs[k] == in) return LP_E_INVALID;
-        for (int m = k + 1; m < 3; ++m)
-            if (outs[k] == outs[m]) return LP_E_INVALID;
-    }
-    anchor_args a = {pos, tgt, key, mask, vec, valid, gated};
-    a.H = height;
-    a.W = width;
-    a.gh = (height + kB - 1) / kB;
-    a.gw = (width + kB - 1) / kB;
-    a.search = anchor;
-    a.smooth = smooth;
-    a.wide = width % 4 == 0 && aligned16(pos) && aligned16(mask);        // the kernel reads a row's four pixels as one vector
-    a.occlusion = occlusion;
-    const dim3 grid(blocks_of(width, kTile), blocks_of(height, kTile));
-    if (gated)
-        hipLaunchKernelGGL(lp_prop_anchor_match_kernel<true>, grid, dim3(256), 0, stream, a);
-    else
-        hipLaunchKernelGGL(lp_prop_anchor_match_kernel<false>, grid, dim3(256), 0, stream, a);
-    return launched();
-}
-
 extern "C" int lp_prop_anchor_match(const lp_prop_anchor_desc* dp, void* stream_) {
     const hipStream_t stream = as_stream(stream_);
     if (!dp) return LP_E_INVALID;
-    return anchor_launch(dp->height, dp->width, dp->anchor, dp->smooth, 0, dp->pos, dp->tgt, dp->key, dp->mask, dp->vec, dp->valid,
-                         nullptr, stream);
+    const anchor_job job = {dp->pos, dp->tgt, dp->key, dp->mask, dp->vec, dp->valid, nullptr};
+    return anchor_launch(dp->height, dp->width, dp->anchor, dp->smooth, 0, &job, 1, false, stream);
 }
 
 extern "C" int lp_prop_anchor_match_gated(const lp_prop_anchor_gated_desc* dp, void* stream_) {
     const hipStream_t stream = as_stream(stream_);
     if (!dp) return LP_E_INVALID;
     if (!dp->gated || dp->occlusion < 1 || dp->occlusion > 255 || dp->reserved0 != 0) return LP_E_INVALID;
-    return anchor_launch(dp->height, dp->width, dp->anchor, dp->smooth, dp->occlusion, dp->pos, dp->tgt, dp->key, dp->mask, dp->vec,
-                         dp->valid, dp->gated, stream);
+    const anchor_job job = {dp->pos, dp->tgt, dp->key, dp->mask, dp->vec, dp->valid, dp->gated};
+    return anchor_launch(dp->height, dp->width, dp->anchor, dp->smooth, dp->occlusion, &job, 1, true, stream);
 }
 
 extern "C" int lp_prop_merge(const lp_prop_merge_desc* dp, void* stream_) {

@@ -16,8 +16,9 @@ propagate_masks_anchored(images, mask, key_frame=0, levels=4, search=2, smooth=8
         no further launch.  Integer arithmetic throughout: a still video and a noise-free whole-pixel shift that the plain chain
         tracks exactly give a zero correction and the plain chain's bits; an empty mask gives 0, a full mask 1.0, one frame the
         binarised mask.  include/lanpaint_hip.h (lp_prop_anchor_match) states the rule in full.
-        Not handled: anchoring inside the occlusion-aware and the several-key forms -- an occluded block would be matched against
-        the occluder; a subject whose look changes away from the key frame (it turns, or the light changes beyond what `smooth`
+        Not handled: anchoring inside the several-key occlusion-aware form (propagate_keys_visible.py) -- an occluded block would
+        be matched against the occluder, and the batched re-match of propagate_keys_anchored.py, which anchors the several-key
+        form, has no gate; a subject whose look changes away from the key frame (it turns, or the light changes beyond what `smooth`
         refuses) gets no correction there and drifts as before; re-anchoring every n-th frame only.  Anchoring inside the
         single-key occlusion-aware form, with a gate that keeps an occluded block out of the match: propagate_anchored_visible.py.
         profiles/r36_propagate_anchored.md has the numbers.

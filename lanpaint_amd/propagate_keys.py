@@ -31,7 +31,7 @@ import torch
 
 from . import _cabi, stabilize
 from ._hostcall import int_in, launch, require_hip, tensor_is
-from ._motion import MAX_JOBS, FieldWalk, check_images, check_params, check_plane, luma_pyramids, row_addresses
+from ._motion import MAX_JOBS, MAX_SEARCH, FieldWalk, check_images, check_params, check_plane, luma_pyramids, row_addresses
 from .propagate import check_advance, check_field, check_match, key_mask
 
 WS_CAP_BYTES = 1 << 30
@@ -75,6 +75,24 @@ def match_level_batch(jobs, H, W, levels, level, search=2, smooth=8):
              torch.empty((gh, gw), dtype=torch.int32, device=job[0].device)) for job in jobs]
     table = job_table(rows, "match_level_batch")
     d = _cabi.LpPropMatchBatchDesc(H, W, levels, level, search, smooth, len(rows), 0, table.ctypes.data)
+    launch("lp_prop_match_batch", rows[0][0].device, ctypes.byref(d))
+    return [r[4:] for r in rows]
+
+
+def anchor_field_batch(jobs, H, W, levels, anchor=2, smooth=8):
+    """`propagate_anchored.anchor_field` for several independent frames in one launch: lp_prop_match_batch in its warped-key form.
+    `jobs`: per job (key, tgt, mpyr, pos): the key frame's and the frame's luma pyramid, the pyramid of the bits the advance wrote
+    and the frame's positions int32 [H, W, 2].  A list of (vec int32 [gh, gw, 2], valid int32 [gh, gw]), what fill_median takes."""
+    int_in(anchor, 1, MAX_SEARCH, "anchor")
+    check_params(levels, anchor, smooth)
+    for key, tgt, mpyr, pos in jobs:
+        check_match(key, tgt, mpyr, None, H, W, levels, levels - 1, anchor, smooth, __name__)    # the numbers and three pyramids
+        tensor_is(pos, torch.int32, (H, W, 2), "pos", __name__)
+    gh, gw = _cabi.prop_grid(H, W)
+    rows = [(*job, torch.empty((gh, gw, 2), dtype=torch.int32, device=job[0].device),
+             torch.empty((gh, gw), dtype=torch.int32, device=job[0].device)) for job in jobs]
+    table = job_table(rows, "anchor_field_batch")
+    d = _cabi.LpPropMatchBatchDesc(H, W, levels, 0, anchor, smooth, len(rows), _cabi.LP_PROP_MATCH_WARPED_KEY, table.ctypes.data)
     launch("lp_prop_match_batch", rows[0][0].device, ctypes.byref(d))
     return [r[4:] for r in rows]
 
@@ -204,9 +222,21 @@ class Chains:
         weights the key's) and writes pos[1] and mpyr[1]; step 2 overwrites pos[0] and mpyr[0] before step 3 reads them; and
         the hidden base, address + 0 * step, is a fixed scratch row that every step's occlude rewrites (a gap's chain; only
         gaps' chains are counted).
-    The plain form allocates no raw_mpyr, no visible or occlude table and no descriptor for them."""
+    The plain form allocates no raw_mpyr, no visible or occlude table and no descriptor for them.
+    The anchored form is the second option, off by default: `rematch` = (anchor,), propagate_keys_anchored's.  With it a group's
+    launches are the walk, a first advance, lp_prop_match_batch in its warped-key form, lp_prop_fill_batch and the advance proper
+    along that correction, 2 levels + 4.  It comes with `raw_pos` and `raw_mpyr`, a buffer per chain each, where the first advance
+    writes the positions and the bits the re-match reads, and with a second advance table and the re-match's descriptor:
+      - the first advance's mask goes to the step's output address, which the second advance rewrites;
+      - the re-match writes the walk's level-0 raw and valid rows, the fill its level-0 table as the walk left it: the step's own
+        field is spent by the first advance;
+      - the second advance reads raw_pos and writes pos[s & 1], the output and mpyr[s & 1], as the plain step's one advance does.
+    `rematch` with `split` raises: an occluded block needs the gate."""
 
-    def __init__(self, plan, pyr, key_pyrs, outs, H, W, levels, search, smooth, split=None):
+    def __init__(self, plan, pyr, key_pyrs, outs, H, W, levels, search, smooth, split=None, rematch=None):
+        if split and rematch:
+            raise ValueError("rematch with split: an occluded block would be matched against the occluder, and the batched re-match "
+                             "has no gate")
         dev = pyr.device
         self.dev = dev
         self.length = np.array([c[3] for c in plan], dtype=np.int64)
@@ -232,6 +262,19 @@ class Chains:
             self.occlude_desc = _cabi.LpPropOccludeBatchDesc(H, W, levels, 0, self.t_occlude.ctypes.data)
             self.launches += [("lp_prop_visible_batch", _cabi.LpPropVisibleBatchDesc(H, W, occlusion, 0, self.t_visible.ctypes.data)),
                               ("lp_prop_occlude_batch", self.occlude_desc)]
+        self.rematch = bool(rematch)
+        if rematch:
+            (anchor,) = rematch
+            int_in(anchor, 1, MAX_SEARCH, "anchor")
+            self.raw_pos, self.raw_mpyr = self._buffers((H, W, 2), torch.int32), self._buffers((stride,), torch.uint8)
+            self.t_rematch, self.t_second = np.zeros((m, 6), dtype=np.uint64), np.zeros((m, 6), dtype=np.uint64)
+            self.t_rematch[:, 4], self.t_rematch[:, 5] = self.walk.t_match[0][:, 4], self.walk.t_match[0][:, 5]
+            self.t_second[:, 0] = self.walk.field0
+            warped = _cabi.LpPropMatchBatchDesc(H, W, levels, 0, anchor, smooth, 0, _cabi.LP_PROP_MATCH_WARPED_KEY,
+                                                self.t_rematch.ctypes.data)
+            # a fill has no descriptor: None stands for the one on the walk's own level-0 table
+            self.launches += [("lp_prop_match_batch", warped), ("lp_prop_fill_batch", None),
+                              ("lp_prop_advance_batch", _cabi.LpPropAdvanceBatchDesc(H, W, levels, 0, self.t_second.ctypes.data))]
 
     def _buffers(self, shape, dtype):
         """One buffer of `shape` per chain: their addresses."""
@@ -239,7 +282,7 @@ class Chains:
         return row_addresses(self._keep[-1], len(self.length))
 
     def step(self, s):
-        """Step s of every chain that has one: 2 levels + 1 launches per MAX_JOBS chains, + 2 with the option."""
+        """Step s of every chain that has one: 2 levels + 1 launches per MAX_JOBS chains, + 2 with `split`, + 3 with `rematch`."""
         idx = np.flatnonzero(self.length >= s)
         for lo in range(0, len(idx), MAX_JOBS):
             self._bind(s, idx[lo:lo + MAX_JOBS])
@@ -262,11 +305,19 @@ class Chains:
             v, o = self.t_visible, self.t_occlude
             v[:n, 0], v[:n, 1], v[:n, 2], v[:n, 3], v[:n, 4] = a[:n, 3], luma, at(self.luma, 0), a[:n, 5], flags
             o[:n, 0], o[:n, 1], o[:n, 2], o[:n, 3], o[:n, 4], o[:n, 5] = a[:n, 4], flags, mask, hidden, self.mpyr[s & 1][idx], count
+        if self.rematch:
+            r, b = self.t_rematch, self.t_second
+            b[:n, 1], b[:n, 2], b[:n, 3], b[:n, 4], b[:n, 5] = self.raw_pos[idx], a[:n, 2], a[:n, 3], a[:n, 4], a[:n, 5]
+            a[:n, 3], a[:n, 5] = self.raw_pos[idx], self.raw_mpyr[idx]
+            r[:n, 0], r[:n, 1], r[:n, 2], r[:n, 3] = at(self.luma, 0), luma, a[:n, 5], a[:n, 3]
 
     def _launch(self, n):
         """The launches of the group of `n` chains that was bound."""
         self.walk.run(*self.jobs)
         for entry, desc in self.launches:
+            if desc is None:
+                launch(entry, self.dev, self.walk.t_fill[0].ctypes.data, n, *self.walk.grids[0])
+                continue
             desc.jobs = n
             launch(entry, self.dev, ctypes.byref(desc))
 
