@@ -1593,6 +1593,8 @@ LP_API int lp_prop_advance(const lp_prop_advance_desc* desc, void* stream);
  * first + frames - 1 > span - 1, out aliasing qa or qb; LP_E_UNSUPPORTED: span > 65535.  All checked before any HIP call.            */
 #define LP_PROP_MAX_JOBS    32
 #define LP_PROP_MATCH_WARPED_KEY 1                /* lp_prop_match_batch_desc.reserved0: the several-keys anchored section  */
+/* reserved0 of the gated warped-key form, occlusion 1..255 in bits 8..15: the several-keys anchored occlusion-aware section */
+#define LP_PROP_MATCH_GATED(occlusion) (LP_PROP_MATCH_WARPED_KEY | ((occlusion) << 8))
 
 typedef struct lp_prop_match_job {
     const uint8_t* src;                           /* as in lp_prop_match_desc                                               */
@@ -1608,7 +1610,8 @@ typedef struct lp_prop_match_batch_desc {
     int32_t search, smooth;
     int32_t jobs, reserved0;                      /* jobs 1..LP_PROP_MAX_JOBS; reserved0 is the source form: 0 the source
                                                      frame's luma, LP_PROP_MATCH_WARPED_KEY the key frame's luma warped
-                                                     through the job's positions (the several-keys anchored section)       */
+                                                     through the job's positions (the several-keys anchored section),
+                                                     LP_PROP_MATCH_GATED(occlusion) that with the occlusion gate           */
     const lp_prop_match_job* job;                 /* host memory, `jobs` entries                                            */
 } lp_prop_match_batch_desc;
 LP_API int lp_prop_match_batch(const lp_prop_match_batch_desc* desc, void* stream);
@@ -1907,19 +1910,54 @@ LP_API int lp_prop_anchor_match_gated(const lp_prop_anchor_gated_desc* desc, voi
  * bit; anchor = 0 is the caller's "off": the several-keys form, its launches only.  A still video with the same mask on every key
  * returns that binarised mask; empty stays exactly 0 and full exactly 1.0.
  * No new entry: the batched re-match is lp_prop_match_batch with reserved0 = LP_PROP_MATCH_WARPED_KEY, since a match job and an anchor
- * job are the same six pointers.  reserved0 = 0 keeps the meaning and the bits it had; any other value is LP_E_INVALID.  With
- * LP_PROP_MATCH_WARPED_KEY, per job: src is the key frame's luma pyramid and tgt the frame's (level 0 of each is read), mask the
- * pyramid whose level 0 is m, parent the positions P_t int32 [height, width, 2], required whatever `levels` is; level must be 0;
- * search is the anchor, 1..LP_PROP_MAX_SEARCH; vec and valid alias no input and not each other.  The result is exactly
- * lp_prop_anchor_match's for that job: lp_prop_anchor_match and lp_prop_anchor_match_gated are one-job launches of the same kernel,
- * which takes its job from a table on blockIdx.z (32 x 56 bytes by value in its arguments, a `wide` bit per job).
+ * job are the same six pointers.  reserved0 = 0 keeps the meaning and the bits it had; any other value but the gated form's below
+ * is LP_E_INVALID.  With LP_PROP_MATCH_WARPED_KEY, per job: src is the key frame's luma pyramid and tgt the frame's (level 0 of each
+ * is read), mask the pyramid whose level 0 is m, parent the positions P_t int32 [height, width, 2], required whatever `levels` is;
+ * level must be 0; search is the anchor, 1..LP_PROP_MAX_SEARCH; vec and valid alias no input and not each other.  The result is
+ * exactly lp_prop_anchor_match's for that job: lp_prop_anchor_match and lp_prop_anchor_match_gated are one-job launches of the same
+ * kernel, which takes its job from a table on blockIdx.z (32 x 56 bytes by value in its arguments, a `wide` bit per job).
  * A step of a group of up to LP_PROP_MAX_JOBS chains is 2 L + 4 launches:
  *   lp_prop_match_batch / lp_prop_fill_batch per level -> lp_prop_advance_batch (P_t, m to per-chain scratch)
  *     -> lp_prop_match_batch (warped key) -> lp_prop_fill_batch -> lp_prop_advance_batch (vec = e, pos_src = P_t).
  * Not handled here: anchoring inside the several-keys occlusion-aware form -- a gated batch needs a third output and `occlusion`,
- * which this job does not hold; what the anchored section lists.
+ * which this job does not hold; what the anchored section lists.  (The section behind this one is that form: its batch goes
+ * without the third output and carries `occlusion` in reserved0, LP_PROP_MATCH_GATED.)
  * LP_E_INVALID in the warped form: level != 0, search outside 1..LP_PROP_MAX_SEARCH, a null pointer in any job (parent included),
- * vec or valid aliasing an input or one another, next to every range lp_prop_match_batch checks.  All checked before any HIP call. */
+ * vec or valid aliasing an input or one another, next to every range lp_prop_match_batch checks.  All checked before any HIP call.
+ * The gated form, reserved0 = LP_PROP_MATCH_GATED(occlusion) = LP_PROP_MATCH_WARPED_KEY | (occlusion << 8): occlusion 1..255 in bits
+ * 8..15, bits 1..7 and 16..31 zero.  reserved0 = LP_PROP_MATCH_WARPED_KEY, occlusion bits 0, stays the ungated form with the bits it
+ * had.  A launch is all gated or all ungated, with one occlusion.  The job is the same six pointers and every check of the warped
+ * form holds.  There is no `gated` plane: the kernel writes that plane only where its pointer is non-null, and a batch job has none.
+ * Per job, vec and valid are exactly what lp_prop_anchor_match_gated writes for that job: valid = live and not gated, vec = 0 where
+ * gated.  The two single entries and the ungated batch return the bits they returned.                                                */
+
+/* ---- Video mask propagate from several keys, anchored and occlusion-aware (beyond the reference) --------------------------------------
+ * The last of the eight combinations of the three refinements: several painted keys, every chain anchored, every chain
+ * occlusion-aware.  It is for a long clip whose subject moves a fraction of a pixel per frame while something passes in front, with a
+ * second key painted behind the occluder: the several-keys occlusion-aware form takes the drift for occlusion there, and the
+ * several-keys anchored form pulls the blocks under the occluder onto it and reports no hidden part.
+ * The rule is the several-keys occlusion-aware section with one change: every chain is the anchored occlusion-aware chain of its own
+ * key, the steps of the "anchored and occlusion-aware" section with Yk the chain's key frame's luma.  For chain X arriving at frame t:
+ *   match / fill per level -> advance (P_t, c and m = c >= 128, to per-chain scratch)
+ *     -> the gated anchor match on (P_t, Yt, Yk, m) -> fill
+ *     -> advance with vec = e, pos_src = P_t and the key bits: P'_t and the code c_X
+ *     -> visible on (P'_t, Yt, Yk, c_X >= 128): the flags f_X
+ *     -> occlude: c'_X, hidden_X = (c_X - c'_X) / 256, the bits that weight the next step's match, and N_X(t).
+ * Everything else is the several-keys occlusion-aware section unchanged, with these c_X, c'_X, f_X and N_X: the plan of the chains,
+ * what a key frame and a frame outside the keys return, the lost rule (LP_PROP_MIN_PIXELS, sticky, never for a key with fewer than 16
+ * bits) and lp_prop_merge_visible.
+ * What follows from the rule, bit for bit: K = 1 is the anchored occlusion-aware single-key form, both outputs; anchor = 0 is the
+ * several-keys occlusion-aware form with its launches only; occlusion = 0 is the several-keys anchored form and a zero hidden, with
+ * its launches only; both 0 the several-keys form and zeros; a still video with the same mask on every key returns that binarised
+ * mask and a zero hidden; empty keys everywhere give 0 and 0; mask + hidden is a multiple of 1 / 256 everywhere; every key frame
+ * returns its painting and a zero hidden; a frame outside the keys is the single-key anchored occlusion-aware chain of the nearest
+ * key.
+ * No new entry.  A step of a group of up to LP_PROP_MAX_JOBS chains is 2 L + 6 launches:
+ *   lp_prop_match_batch / lp_prop_fill_batch per level -> lp_prop_advance_batch (P_t, m to per-chain scratch)
+ *     -> lp_prop_match_batch (LP_PROP_MATCH_GATED(occlusion)) -> lp_prop_fill_batch -> lp_prop_advance_batch (vec = e, pos_src = P_t)
+ *     -> lp_prop_visible_batch -> lp_prop_occlude_batch (mask, hidden, the next step's bit pyramid, the count).
+ * Not handled: following a subject through a full occlusion without a second key; what leaves the picture; occlusion edges finer
+ * than a block; a subject whose look changes away from its key.  Lost chains are not stopped early.                                  */
 
 /* ---- Video temporal fill (beyond the reference) -------------------------------------------------------------------------------------
  * What lies under the mask of a video frame is, in most clips, plain background a few frames earlier or later: a subject moves
@@ -2226,7 +2264,8 @@ LP_API int lp_tsmooth_robust(const lp_tsmooth_robust_desc* desc, void* stream);
  *             two equal residuals inside a window are never cuts; with ratio = 100 both are.
  *   shot      int32 [F]: shot[0] = 0, shot[f] = sum over t < f of cut[t].  F = 1 gives shot = [0]; there is no score.
  * Not done: dissolves, fades and wipes are not detected (no pair of such a transition stands out of its neighbours); the
- * several-key propagates and the colour match's pooling over neighbouring frames have no shot-aware form.
+ * several-key propagates (but the anchored occlusion-aware one, which with its options off is each of them) and the colour match's
+ * pooling over neighbouring frames have no shot-aware form.
  * Launches (csrc/shot_kernel.hip).  lp_shot_measure, for the `frames` planes of a chunk: the histograms and the A words are
  * cleared, then one launch for all frames, a 256-lane block per 32 x 32 tile and frame.  The block adds its pixels into per-wave
  * 64-bin histograms in LDS, folded once per block into hist[t] with at most one integer atomic per bin.  If frame t + 1 is in the

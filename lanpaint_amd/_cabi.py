@@ -399,6 +399,11 @@ LP_PROP_MAX_JOBS = 32
 LP_PROP_MATCH_WARPED_KEY = 1                                         # LpPropMatchBatchDesc.reserved0: the source form
 
 
+def LP_PROP_MATCH_GATED(occlusion):
+    """The header's macro: the warped-key form with the occlusion gate, `occlusion` 1..255 in bits 8..15 of reserved0."""
+    return LP_PROP_MATCH_WARPED_KEY | (occlusion << 8)
+
+
 class LpPropMatchJob(C.Structure):
     _fields_ = [("src", C.c_void_p), ("tgt", C.c_void_p), ("mask", C.c_void_p), ("parent", C.c_void_p), ("vec", C.c_void_p),
                 ("valid", C.c_void_p)]

@@ -34,6 +34,7 @@
 //                v_alignbyte_b32 / v_sad_u8 inner loop, key and sub-pixel step.  A tile with no mask pixel leaves after staging K.
 //                The anchored occlusion-aware form's launch is the same kernel with a compile-time tail on the window loop: behind
 //                the minimum a lane per dword of the window takes visible's D, mu and R at the winner's alignment from the same LDS.
+//                Four ways in, one body: the two single entries, and lp_prop_match_batch's warped-key and gated forms.
 //   merge        one lane per pixel and frame of a gap between two keys: the two chains' signed squared distances, their capped
 //                fp64 roots, the weighted mean in a fixed order, the ramp of half-width 1/2 around the zero crossing.
 //   merge_visible the merge of a gap whose chains are occlusion-aware: a streaming kernel over [frames, H, W], four pixels per lane
@@ -606,7 +607,8 @@ static_assert(sizeof(anchor_args) <= 4096, "the job table travels by value in th
 
 // Gated: the anchored occlusion-aware form.  Behind the wave-wide minimum every lane knows the winner; lane = row * 4 + dword of the
 // window cuts its four target pixels for the winner out of s_pat and takes lp_prop_visible's statistic there: D, mu and R over the
-// window's mask pixels.  A gated block gives no correction: vec 0, valid 0.
+// window's mask pixels.  A gated block gives no correction: vec 0, valid 0.  The `gated` plane is written where the job has one: the
+// batched gated form (lp_prop_match_batch with LP_PROP_MATCH_GATED) has none, its jobs hold six pointers.
 template <bool Gated>
 __global__ __launch_bounds__(256) void lp_prop_anchor_match_kernel(const anchor_args a) {
     __shared__ uint32_t s_src[kVisSide * kAncPitch], s_bm[kVisSide * kAncPitch], s_pat[kAncPatRows * kAncPatPitch];
@@ -661,7 +663,7 @@ __global__ __launch_bounds__(256) void lp_prop_anchor_match_kernel(const anchor_
             vec[cell * 2] = 0;
             vec[cell * 2 + 1] = 0;
             valid[cell] = 0;
-            if (Gated) gated[cell] = 0;
+            if (Gated && gated) gated[cell] = 0;
         }
         return;
     }
@@ -754,7 +756,7 @@ __global__ __launch_bounds__(256) void lp_prop_anchor_match_kernel(const anchor_
             vec[cell * 2] = vy;
             vec[cell * 2 + 1] = vx;
             valid[cell] = live && !gate ? 1 : 0;
-            if (Gated) gated[cell] = gate ? 1 : 0;
+            if (Gated && gated) gated[cell] = gate ? 1 : 0;
         }
     }
 }
@@ -898,7 +900,8 @@ extern "C" int lp_prop_key_mask(const float* mask, int32_t height, int32_t width
 }
 
 // The anchor match's one dispatch, `jobs` of them on blockIdx.z: the two single entries with one job, `gated` the anchored
-// occlusion-aware form's, and lp_prop_match_batch's warped-key form.
+// occlusion-aware form's, and lp_prop_match_batch's warped-key and gated forms.  A launch is all gated or all ungated, with one
+// `occlusion`; a gated job may go without its `gated` plane (the batch's jobs do), an ungated job has none.
 static int anchor_launch(int height, int width, int anchor, int smooth, int occlusion, const anchor_job* job, int jobs, bool gated,
                          hipStream_t stream) {
     if (!side_ok(height) || !side_ok(width)) return LP_E_INVALID;
@@ -907,7 +910,7 @@ static int anchor_launch(int height, int width, int anchor, int smooth, int occl
     anchor_args a = {};
     for (int i = 0; i < jobs; ++i) {
         const anchor_job& j = job[i];
-        if (!j.pos || !j.tgt || !j.key || !j.msk || !j.vec || !j.valid || (j.gated != nullptr) != gated) return LP_E_INVALID;
+        if (!j.pos || !j.tgt || !j.key || !j.msk || !j.vec || !j.valid || (j.gated && !gated)) return LP_E_INVALID;
         const void* outs[3] = {j.vec, j.valid, j.gated};
         for (int k = 0; k < 3; ++k) {                                    // gated may be null; an output aliases nothing
             if (!outs[k]) continue;
@@ -940,18 +943,21 @@ extern "C" int lp_prop_match_batch(const lp_prop_match_batch_desc* dp, void* str
     const hipStream_t stream = as_stream(stream_);
     if (!dp) return LP_E_INVALID;
     const lp_prop_match_batch_desc& d = *dp;
-    if (d.reserved0 != 0 && d.reserved0 != LP_PROP_MATCH_WARPED_KEY) return LP_E_INVALID;
+    // the source form: 0, LP_PROP_MATCH_WARPED_KEY, or LP_PROP_MATCH_GATED(occlusion) with occlusion 1..255 in bits 8..15
+    const bool warped = (d.reserved0 & 0xFF) == LP_PROP_MATCH_WARPED_KEY && (d.reserved0 & ~0xFFFF) == 0;
+    if (d.reserved0 != 0 && !warped) return LP_E_INVALID;
+    const int occlusion = d.reserved0 >> 8;                              // 0: the ungated form
     if (!side_ok(d.height) || !side_ok(d.width) || !levels_ok(d.levels) || d.level < 0 || d.level >= d.levels) return LP_E_INVALID;
     if (d.search < 1 || d.search > LP_PROP_MAX_SEARCH || d.smooth < 0 || d.smooth > LP_PROP_MAX_SMOOTH) return LP_E_INVALID;
     if (!jobs_ok(d.jobs) || !d.job) return LP_E_INVALID;
-    if (d.reserved0 == LP_PROP_MATCH_WARPED_KEY) {                       // the anchor match: level 0 of the three pyramids is their start
+    if (warped) {                                                        // the anchor match: level 0 of the three pyramids is their start
         if (d.level != 0) return LP_E_INVALID;
         anchor_job job[LP_PROP_MAX_JOBS];
         for (int i = 0; i < d.jobs; ++i) {
             const lp_prop_match_job& j = d.job[i];
             job[i] = {j.parent, j.tgt, j.src, j.mask, j.vec, j.valid, nullptr};
         }
-        return anchor_launch(d.height, d.width, d.search, d.smooth, 0, job, d.jobs, false, stream);
+        return anchor_launch(d.height, d.width, d.search, d.smooth, occlusion, job, d.jobs, occlusion != 0, stream);
     }
     match_args a = {};
     const int64_t off = level_offset(d.height, d.width, d.level);

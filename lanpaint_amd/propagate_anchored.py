@@ -21,6 +21,7 @@ propagate_masks_anchored(images, mask, key_frame=0, levels=4, search=2, smooth=8
         form, has no gate; a subject whose look changes away from the key frame (it turns, or the light changes beyond what `smooth`
         refuses) gets no correction there and drifts as before; re-anchoring every n-th frame only.  Anchoring inside the
         single-key occlusion-aware form, with a gate that keeps an occluded block out of the match: propagate_anchored_visible.py.
+        The several-key occlusion-aware form is anchored by propagate_keys_anchored_visible.py, whose batched re-match has the gate.
         profiles/r36_propagate_anchored.md has the numbers.
 
 HIP tensors only, no CPU fallback, no device -> host read.  The frames' luma pyramids come in propagate's chunks, under

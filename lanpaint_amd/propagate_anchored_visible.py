@@ -25,6 +25,7 @@ propagate_masks_anchored_visible(images, mask, key_frame=0, levels=4, search=2, 
         form's, bit for bit.  include/lanpaint_hip.h (lp_prop_anchor_match_gated) states the rule in full.
         Not handled: a subject hidden entirely; what leaves the picture; occlusion edges finer than a block --
         `LanPaint_MaskRefine` follows in the chain; several keys; a subject whose look changes away from the key.
+        (Several keys, every chain this one: propagate_keys_anchored_visible.py.)
         profiles/r37_propagate_anchored_visible.md has the numbers.
 
 HIP tensors only, no CPU fallback, no device -> host read.  The frames' luma pyramids come in propagate's chunks, under

@@ -79,11 +79,14 @@ def match_level_batch(jobs, H, W, levels, level, search=2, smooth=8):
     return [r[4:] for r in rows]
 
 
-def anchor_field_batch(jobs, H, W, levels, anchor=2, smooth=8):
+def anchor_field_batch(jobs, H, W, levels, anchor=2, smooth=8, occlusion=0):
     """`propagate_anchored.anchor_field` for several independent frames in one launch: lp_prop_match_batch in its warped-key form.
     `jobs`: per job (key, tgt, mpyr, pos): the key frame's and the frame's luma pyramid, the pyramid of the bits the advance wrote
-    and the frame's positions int32 [H, W, 2].  A list of (vec int32 [gh, gw, 2], valid int32 [gh, gw]), what fill_median takes."""
+    and the frame's positions int32 [H, W, 2].  A list of (vec int32 [gh, gw, 2], valid int32 [gh, gw]), what fill_median takes.
+    `occlusion` above 0, up to 255, selects the gated form: `propagate_anchored_visible.gated_anchor_field`'s vec and valid per
+    job, with no `gated` plane."""
     int_in(anchor, 1, MAX_SEARCH, "anchor")
+    int_in(occlusion, 0, 255, "occlusion")
     check_params(levels, anchor, smooth)
     for key, tgt, mpyr, pos in jobs:
         check_match(key, tgt, mpyr, None, H, W, levels, levels - 1, anchor, smooth, __name__)    # the numbers and three pyramids
@@ -92,7 +95,8 @@ def anchor_field_batch(jobs, H, W, levels, anchor=2, smooth=8):
     rows = [(*job, torch.empty((gh, gw, 2), dtype=torch.int32, device=job[0].device),
              torch.empty((gh, gw), dtype=torch.int32, device=job[0].device)) for job in jobs]
     table = job_table(rows, "anchor_field_batch")
-    d = _cabi.LpPropMatchBatchDesc(H, W, levels, 0, anchor, smooth, len(rows), _cabi.LP_PROP_MATCH_WARPED_KEY, table.ctypes.data)
+    form = _cabi.LP_PROP_MATCH_GATED(occlusion) if occlusion else _cabi.LP_PROP_MATCH_WARPED_KEY
+    d = _cabi.LpPropMatchBatchDesc(H, W, levels, 0, anchor, smooth, len(rows), form, table.ctypes.data)
     launch("lp_prop_match_batch", rows[0][0].device, ctypes.byref(d))
     return [r[4:] for r in rows]
 
@@ -231,12 +235,30 @@ class Chains:
       - the re-match writes the walk's level-0 raw and valid rows, the fill its level-0 table as the walk left it: the step's own
         field is spent by the first advance;
       - the second advance reads raw_pos and writes pos[s & 1], the output and mpyr[s & 1], as the plain step's one advance does.
-    `rematch` with `split` raises: an occluded block needs the gate."""
+    `rematch` with `split` raises: an occluded block needs the gate.
+    Both options at once are spelled `rematch` = (anchor, occlusion) next to `split`, propagate_keys_anchored_visible's; the same
+    pair without `split` raises, and so does an occlusion that is not split's.  The re-match is then lp_prop_match_batch in its
+    gated form and a group's launches are the walk, the first advance, the gated re-match, the fill, the second advance,
+    lp_prop_visible_batch and lp_prop_occlude_batch, 2 levels + 6.  No buffer is added to the two options':
+      - the first advance writes raw_pos and raw_mpyr, which the gated re-match reads, and its code to the step's code address;
+      - the second advance reads raw_pos and writes pos[s & 1], the code to the same address and its bits to raw_mpyr again (the
+        re-match has read the first bits by then: the launches are in stream order), where the flags read them;
+      - visible and occlude are the split's: occlude writes mask, hidden, the next step's weights to mpyr[s & 1] and the count;
+      - `count_keys` scribbles where it did: step 1 reads neither pos[0] nor mpyr[0] and writes raw_pos, raw_mpyr, pos[1], mpyr[1]."""
 
     def __init__(self, plan, pyr, key_pyrs, outs, H, W, levels, search, smooth, split=None, rematch=None):
-        if split and rematch:
+        gate = 0                                                     # the re-match's occlusion: above 0 with both options only
+        if rematch and len(rematch) > 2:
+            raise ValueError(f"rematch must be (anchor,) or (anchor, occlusion), got {rematch!r}")
+        if rematch and len(rematch) == 2:
+            if not split:
+                raise ValueError("rematch=(anchor, occlusion) without split: the gated re-match belongs to the occlusion-aware chains")
+            gate = int_in(rematch[1], 1, 255, "rematch's occlusion")
+            if gate != split[0]:
+                raise ValueError(f"rematch's occlusion {gate} is not split's {split[0]}: a chain has one")
+        elif split and rematch:
             raise ValueError("rematch with split: an occluded block would be matched against the occluder, and the batched re-match "
-                             "has no gate")
+                             "has no gate; rematch=(anchor, occlusion) is the gated one")
         dev = pyr.device
         self.dev = dev
         self.length = np.array([c[3] for c in plan], dtype=np.int64)
@@ -254,27 +276,30 @@ class Chains:
         self.t_advance[:, 0] = self.walk.field0
         self.launches = [("lp_prop_advance_batch", _cabi.LpPropAdvanceBatchDesc(H, W, levels, 0, self.t_advance.ctypes.data))]
         self.lin = None
+        tail = []                                                    # the split's two launches: behind the re-match's, if any
         if split:
             occlusion, *columns = split
             self.raw_mpyr = self._buffers((stride,), torch.uint8)
             self.lin = [_linear(column) for column in columns]
             self.t_visible, self.t_occlude = np.zeros((m, 5), dtype=np.uint64), np.zeros((m, 6), dtype=np.uint64)
             self.occlude_desc = _cabi.LpPropOccludeBatchDesc(H, W, levels, 0, self.t_occlude.ctypes.data)
-            self.launches += [("lp_prop_visible_batch", _cabi.LpPropVisibleBatchDesc(H, W, occlusion, 0, self.t_visible.ctypes.data)),
-                              ("lp_prop_occlude_batch", self.occlude_desc)]
+            tail = [("lp_prop_visible_batch", _cabi.LpPropVisibleBatchDesc(H, W, occlusion, 0, self.t_visible.ctypes.data)),
+                    ("lp_prop_occlude_batch", self.occlude_desc)]
         self.rematch = bool(rematch)
         if rematch:
-            (anchor,) = rematch
-            int_in(anchor, 1, MAX_SEARCH, "anchor")
-            self.raw_pos, self.raw_mpyr = self._buffers((H, W, 2), torch.int32), self._buffers((stride,), torch.uint8)
+            anchor = int_in(rematch[0], 1, MAX_SEARCH, "anchor")
+            self.raw_pos = self._buffers((H, W, 2), torch.int32)
+            if not split:                                            # with both options the split's raw_mpyr serves both advances
+                self.raw_mpyr = self._buffers((stride,), torch.uint8)
             self.t_rematch, self.t_second = np.zeros((m, 6), dtype=np.uint64), np.zeros((m, 6), dtype=np.uint64)
             self.t_rematch[:, 4], self.t_rematch[:, 5] = self.walk.t_match[0][:, 4], self.walk.t_match[0][:, 5]
             self.t_second[:, 0] = self.walk.field0
-            warped = _cabi.LpPropMatchBatchDesc(H, W, levels, 0, anchor, smooth, 0, _cabi.LP_PROP_MATCH_WARPED_KEY,
-                                                self.t_rematch.ctypes.data)
+            form = _cabi.LP_PROP_MATCH_GATED(gate) if gate else _cabi.LP_PROP_MATCH_WARPED_KEY
+            warped = _cabi.LpPropMatchBatchDesc(H, W, levels, 0, anchor, smooth, 0, form, self.t_rematch.ctypes.data)
             # a fill has no descriptor: None stands for the one on the walk's own level-0 table
             self.launches += [("lp_prop_match_batch", warped), ("lp_prop_fill_batch", None),
                               ("lp_prop_advance_batch", _cabi.LpPropAdvanceBatchDesc(H, W, levels, 0, self.t_second.ctypes.data))]
+        self.launches += tail
 
     def _buffers(self, shape, dtype):
         """One buffer of `shape` per chain: their addresses."""
@@ -282,7 +307,8 @@ class Chains:
         return row_addresses(self._keep[-1], len(self.length))
 
     def step(self, s):
-        """Step s of every chain that has one: 2 levels + 1 launches per MAX_JOBS chains, + 2 with `split`, + 3 with `rematch`."""
+        """Step s of every chain that has one: 2 levels + 1 launches per MAX_JOBS chains, + 2 with `split`, + 3 with `rematch`,
+        + 5 with both."""
         idx = np.flatnonzero(self.length >= s)
         for lo in range(0, len(idx), MAX_JOBS):
             self._bind(s, idx[lo:lo + MAX_JOBS])
@@ -335,8 +361,9 @@ class Chains:
             launch("lp_prop_occlude_batch", self.dev, ctypes.byref(self.occlude_desc))
 
 
-def _key_masks(masks, keys, F, H, W):
-    """The K key masks as a list of [H, W] tensors."""
+def painted_masks(masks, keys, F, H, W):
+    """The K key masks of `masks` ([K, H, W], [F, H, W] or, for one key, [H, W]) as a list of [H, W] tensors; the per-shot form
+    (shots.py) picks a shot's keys out of it."""
     if masks.ndim == 2 and len(keys) == 1:
         masks = masks.unsqueeze(0)
     if masks.ndim != 3 or masks.shape[0] not in (len(keys), F) or tuple(masks.shape[1:]) != (H, W):
@@ -358,7 +385,7 @@ def painted_keys(images, masks, key_frames, levels, module, planes=1):
     (F, H, W, _), dev = images.shape, images.device
     outs = [torch.empty((F, H, W), dtype=torch.float32, device=dev) for _ in range(planes)]
     key_pyrs = []
-    for k, m in zip(keys, _key_masks(masks, keys, F, H, W)):
+    for k, m in zip(keys, painted_masks(masks, keys, F, H, W)):
         mpyr, bits = key_mask(m.to(dev), levels)
         key_pyrs.append(mpyr)
         outs[0][k] = bits

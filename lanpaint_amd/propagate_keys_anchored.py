@@ -15,8 +15,8 @@ propagate_keys_anchored(images, masks, key_frames, levels=4, search=2, smooth=8,
         correction off: propagate_keys, no further launch.  A still video with the same mask on every key returns that
         binarised mask; empty stays exactly 0, full exactly 1.  include/lanpaint_hip.h (the several-keys anchored section)
         states the rule.  Not handled: occlusion -- anchoring inside propagate_keys_visible needs a gated batch; a subject whose
-        look changes away from its key; re-anchoring every n-th frame only.  profiles/r38_propagate_keys_anchored.md has the
-        numbers.
+        look changes away from its key; re-anchoring every n-th frame only.  (That gated batch is propagate_keys_anchored_visible.py's:
+        several keys, anchored and occlusion-aware.)  profiles/r38_propagate_keys_anchored.md has the numbers.
 
 HIP tensors only, no CPU fallback, no device -> host read.  The re-match of up to 32 chains is one launch, lp_prop_match_batch in
 its warped-key form (`propagate_keys.anchor_field_batch` is that launch on its own); a step of a group is 2 levels + 4 launches

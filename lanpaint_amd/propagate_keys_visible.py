@@ -18,7 +18,9 @@ propagate_keys_visible(images, masks, key_frames, levels=4, search=2, smooth=8, 
         mask and a zero `hidden`; empty keys everywhere give 0 and 0; mask + hidden is a multiple of 1/256.  include/lanpaint_hip.h
         (lp_prop_visible_batch, lp_prop_occlude_batch, lp_prop_merge_visible) states the rule in full.  Not handled: occlusion
         edges finer than a block; following a subject through a full occlusion (positions stall while nothing is visible: the
-        second key is what recovers it); what leaves the picture.  Lost chains are not stopped early.
+        second key is what recovers it); what leaves the picture.  Lost chains are not stopped early.  On a long clip whose
+        subject moves a fraction of a pixel per frame drift reads as occlusion here: propagate_keys_anchored_visible.py anchors
+        every chain of this form, and shares this module's chains and merge (`visible_chains`).
 
 HIP tensors only, no CPU fallback, no device -> host read: the visible bits are counted by the occlude launch (an integer atomic
 add per chain and step) and the lost decision is taken inside the merge launch.  A step is 2 levels + 3 launches per 32 active
@@ -112,7 +114,15 @@ def propagate_keys_visible(images, masks, key_frames, levels=4, search=2, smooth
     if occlusion == 0:                                               # the plain form makes every further check itself
         out = propagate_keys.propagate_keys(images, masks, key_frames, levels, search, smooth)
         return out, torch.zeros_like(out)
-    plan, keys, key_pyrs, (out, hidden) = painted_keys(images, masks, key_frames, levels, __name__, 2)
+    return visible_chains(images, masks, key_frames, levels, search, smooth, occlusion, __name__, WS_CAP_BYTES)
+
+
+def visible_chains(images, masks, key_frames, levels, search, smooth, occlusion, module, cap, anchor=0):
+    """The occlusion-aware chains of a call and their merge, the numbers checked: what propagate_keys_visible is behind its "off"
+    route.  `module` and `cap` are the caller's __name__ and WS_CAP_BYTES.  `anchor` above 0 makes every chain the anchored
+    occlusion-aware chain of its key (propagate_keys_anchored_visible.py): the chain table's second option next to the first,
+    and a position map per chain more to keep."""
+    plan, keys, key_pyrs, (out, hidden) = painted_keys(images, masks, key_frames, levels, module, 2)
     (F, H, W, _), dev = images.shape, images.device
     if not plan:
         return out, hidden
@@ -120,10 +130,11 @@ def propagate_keys_visible(images, masks, key_frames, levels=4, search=2, smooth
     between = gaps.between
     gh, gw = _cabi.prop_grid(H, W)
     plane, cells = H * W * 4, gh * gw * 4
-    kept = between * 2 * (plane + cells) + (len(plan) + 1) * (plane + cells)
-    if kept > WS_CAP_BYTES:
-        raise ValueError(f"the backward chains' codes and masks and the flags of {between} in-between frames of {H}x{W} take {kept} "
-                         f"bytes, above WS_CAP_BYTES = {WS_CAP_BYTES}: paint fewer frames apart or split the clip")
+    kept = between * 2 * (plane + cells) + (len(plan) + 1) * (plane + cells) + (len(plan) * 2 * plane if anchor else 0)
+    if kept > cap:
+        more = f" and the position maps of {len(plan)} anchored chains" if anchor else ""
+        raise ValueError(f"the backward chains' codes and masks and the flags of {between} in-between frames of {H}x{W}{more} take "
+                         f"{kept} bytes, above WS_CAP_BYTES = {cap}: paint fewer frames apart or split the clip")
     back = torch.empty((2, between, H, W), dtype=torch.float32, device=dev)              # the backward chains' code and mask
     flags = torch.empty((2, between, gh, gw), dtype=torch.int32, device=dev)            # the forward and the backward chains'
     scratch = torch.empty((len(plan), H, W), dtype=torch.float32, device=dev)           # an edge chain's code, a gap chain's hidden
@@ -148,7 +159,8 @@ def propagate_keys_visible(images, masks, key_frames, levels=4, search=2, smooth
             flag.append(gaps.stacked(flags[0 if forward else 1], chain))
             count.append((counts[count_of[gap] + (0 if forward else gap[1] - gap[0]):].data_ptr(), 4))
     pyr = clip_pyramids(images, levels)
-    chains = Chains(plan, pyr, key_pyrs, code, H, W, levels, search, smooth, split=(occlusion, mask, hid, flag, count))
+    chains = Chains(plan, pyr, key_pyrs, code, H, W, levels, search, smooth, split=(occlusion, mask, hid, flag, count),
+                    rematch=(anchor, occlusion) if anchor else None)
     if gaps.pairs:
         scratch_flags[-1].zero_()
         chains.count_keys([out[k] for _, k, _, _ in plan], scratch_flags[-1])
@@ -157,7 +169,7 @@ def propagate_keys_visible(images, masks, key_frames, levels=4, search=2, smooth
     for a, b in gaps.pairs:
         r, span = gaps.first[a, b], b - a
         count_a, count_b = counts[count_of[a, b]:][:span], counts[count_of[a, b] + span:][:span]
-        for s, n in chunks(span - 1, 2 * plane, WS_CAP_BYTES):       # the two chains' distances of a chunk's frames
+        for s, n in chunks(span - 1, 2 * plane, cap):                # the two chains' distances of a chunk's frames
             code_a, mask_a = hidden[a + 1 + s:a + 1 + s + n], out[a + 1 + s:a + 1 + s + n]
             code_b, mask_b = back[0, r + s:r + s + n], back[1, r + s:r + s + n]
             merge_gap_visible(stabilize.signed_d2(code_a), stabilize.signed_d2(code_b), code_a, mask_a, code_b, mask_b,

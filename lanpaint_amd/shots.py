@@ -33,10 +33,13 @@ propagate_masks_anchored_shots
         `propagate_masks_anchored`, the anchored form of the propagate, inside the key frame's shot as `propagate_masks_shots`.
 propagate_masks_anchored_visible_shots
         `propagate_masks_anchored_visible`, the anchored occlusion-aware form, in the same way: both outputs 0 outside that shot.
+propagate_keys_anchored_visible_shots
+        `propagate_keys_anchored_visible` per shot on the keys inside it, 0 in a shot without a key.  With anchor = 0 and / or
+        occlusion = 0 it is the per-shot form of the three other several-keys propagates, which have none of their own.
 
 include/lanpaint_hip.h (lp_shot_*) states the rule in full: integers throughout, the same bits on every run.  Not done:
-dissolves, fades and wipes are not detected; the several-key propagates and the colour match's pooling over neighbouring
-frames have no shot-aware form.
+dissolves, fades and wipes are not detected; the several-key propagates (but through propagate_keys_anchored_visible_shots) and
+the colour match's pooling over neighbouring frames have no shot-aware form.
 
 HIP tensors only, no CPU fallback.  The pyramids are built for as many frames at a time as stay under WS_CAP_BYTES; neighbouring
 chunks share one frame, so every pair is measured inside one chunk, and a pair's scores depend on its two frames only: chunking
@@ -236,3 +239,33 @@ def propagate_masks_anchored_visible_shots(images, mask, shots, key_frame=0, lev
     (fp32 [F, H, W], fp32 [F, H, W])."""
     from .propagate_anchored_visible import propagate_masks_anchored_visible
     return _in_key_shot(propagate_masks_anchored_visible, images, mask, shots, key_frame, levels, search, smooth, anchor, occlusion)
+
+
+def propagate_keys_anchored_visible_shots(images, masks, shots, key_frames, levels=4, search=2, smooth=8, anchor=2, occlusion=16):
+    """`propagate_keys_anchored_visible` inside every shot, on the keys that lie inside it: no chain runs across a cut and no
+    merge joins the keys of two scenes.  A shot without a key is exactly 0 in both outputs; a single range returns the plain
+    call's result.  `masks` as the call takes them, [K, H, W], [F, H, W] or [H, W] for one key.  With anchor = 0 and / or
+    occlusion = 0 this is the per-shot form of `propagate_keys_visible`, `propagate_keys_anchored` (and zeros) and
+    `propagate_keys` (and zeros) as well.  (fp32 [F, H, W], fp32 [F, H, W])."""
+    from .propagate_keys import chain_plan, painted_masks
+    from .propagate_keys_anchored_visible import propagate_keys_anchored_visible
+    if not torch.is_tensor(images) or images.ndim != 4:
+        check_images(images)                                         # raises; every other check of the clip is the call's own
+    F, H, W = images.shape[:3]
+    ranges = clip_ranges(shots, F)
+    chain_plan(F, key_frames)                                        # the keys' own checks, before anything is cut
+    keys = list(key_frames)
+    if len(ranges) == 1:
+        return propagate_keys_anchored_visible(images, masks, keys, levels, search, smooth, anchor, occlusion)
+    if not torch.is_tensor(masks):
+        raise ValueError("masks must be a tensor [K, H, W], [F, H, W] or [H, W]")
+    painted = painted_masks(masks, keys, F, H, W)
+    out = torch.zeros((F, H, W), dtype=torch.float32, device=images.device)
+    hidden = torch.zeros_like(out)
+    for lo, hi in ranges:
+        inside = [i for i, k in enumerate(keys) if lo <= k < hi]
+        if inside:
+            out[lo:hi], hidden[lo:hi] = propagate_keys_anchored_visible(
+                images[lo:hi], torch.stack([painted[i] for i in inside]), [keys[i] - lo for i in inside], levels, search, smooth,
+                anchor, occlusion)
+    return out, hidden

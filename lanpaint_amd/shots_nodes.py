@@ -9,7 +9,8 @@ for any node; and a subclass of each of the five temporal nodes takes the `shots
                                    ... -> VideoTemporalSmoothShots
 
 Hard cuts only: dissolves, fades and wipes are not detected.  Two cuts closer than `window` frames suppress one another.  The
-several-key propagate nodes and the colour match's pooling over neighbouring frames have no shot-aware form.  Host tensors in
+several-key propagate nodes (but LanPaint_VideoMaskPropagateKeysAnchoredVisibleShots, in its own module, which with its options
+off is each of them) and the colour match's pooling over neighbouring frames have no shot-aware form.  Host tensors in
 and out like the other nodes.  The reference has no such nodes.
 
 This module has its own NODE_CLASS_MAPPINGS: merge them with the others' (INTEGRATION.md section 2(b)).
