@@ -182,77 +182,6 @@ def test_abi_version_and_strerror(hip_lib):
         assert len(hip_lib.lp_strerror(code)) > 0
 
 
-def _header_constants():
-    src = open(HEADER).read()
-    out = {}
-    for name, val in re.findall(r"#define\s+(LP_[A-Z0-9_]+)\s+(\(?[-0-9a-fx u<]+\)?)", src):
-        v = val.strip("() ").replace("u", "")
-        try:
-            out[name] = eval(v)       # "1 << 3" style literals only
-        except Exception:
-            pass
-    return out
-
-
-def test_python_constants_mirror_header():
-    consts = _header_constants()
-    checked = 0
-    for name, val in consts.items():
-        if hasattr(_cabi, name):
-            assert getattr(_cabi, name) == val, name
-            checked += 1
-    assert checked >= 40
-
-
-def test_struct_layout_matches_c(tmp_path):
-    """sizeof / offsetof of the two descriptors as gcc sees them == ctypes."""
-    import subprocess
-    fields_step = [f for f, _ in _cabi.LpStepDesc._fields_]
-    fields_final = [f for f, _ in _cabi.LpFinalDesc._fields_]
-    fields_call = [f for f, _ in _cabi.LpCallDesc._fields_]
-    cname = lambda f: "lambda" if f == "lambda_" else f      # noqa: E731
-    prog = ['#include <stdio.h>', '#include <stddef.h>', '#include "lanpaint_hip.h"', 'int main(void){',
-            'printf("%zu %zu %zu\\n", sizeof(lp_step_desc), sizeof(lp_final_desc), sizeof(lp_hyper));']
-    for f in fields_step:
-        prog.append(f'printf("%zu ", offsetof(lp_step_desc, {cname(f)}));')
-    prog.append('printf("\\n");')
-    for f in fields_final:
-        prog.append(f'printf("%zu ", offsetof(lp_final_desc, {cname(f)}));')
-    prog.append('printf("\\n");')
-    for f in fields_call:
-        prog.append(f'printf("%zu ", offsetof(lp_call_desc, {f}));')
-    prog.append('printf("%zu\\n", sizeof(lp_call_desc));')
-    fields_es = [f for f, _ in _cabi.LpEsState._fields_]
-    for f in fields_es:
-        prog.append(f'printf("%zu ", offsetof(lp_es_state, {f}));')
-    prog.append('printf("%zu %d %d\\n", sizeof(lp_es_state), LP_ES_SEQ_DONE, LP_ES_TRACE0);')
-    fields_node = [f for f, _ in _cabi.LpNodeCallDesc._fields_]
-    fields_bind = [f for f, _ in _cabi.LpGraphBinding._fields_]
-    for f in fields_node:
-        prog.append(f'printf("%zu ", offsetof(lp_node_call_desc, {f}));')
-    prog.append('printf("%zu\\n", sizeof(lp_node_call_desc));')
-    for f in fields_bind:
-        prog.append(f'printf("%zu ", offsetof(lp_graph_binding, {f}));')
-    prog.append('printf("%zu %d\\n", sizeof(lp_graph_binding), LP_ES_ACC_DOUBLES); return 0;}')
-    src = tmp_path / "layout.c"
-    src.write_text("\n".join(prog))
-    exe = tmp_path / "layout"
-    subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
-    lines = subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.strip().split("\n")
-    sizes = [int(v) for v in lines[0].split()]
-    assert sizes == [ctypes.sizeof(_cabi.LpStepDesc), ctypes.sizeof(_cabi.LpFinalDesc), ctypes.sizeof(_cabi.LpHyper)]
-    assert [int(v) for v in lines[1].split()] == [getattr(_cabi.LpStepDesc, f).offset for f in fields_step]
-    assert [int(v) for v in lines[2].split()] == [getattr(_cabi.LpFinalDesc, f).offset for f in fields_final]
-    assert [int(v) for v in lines[3].split()] == [getattr(_cabi.LpCallDesc, f).offset for f in fields_call] + \
-        [ctypes.sizeof(_cabi.LpCallDesc)]
-    assert [int(v) for v in lines[4].split()] == [getattr(_cabi.LpEsState, f).offset for f in fields_es] + \
-        [ctypes.sizeof(_cabi.LpEsState), _cabi.LP_ES_SEQ_DONE, _cabi.LP_ES_TRACE0]
-    assert [int(v) for v in lines[5].split()] == [getattr(_cabi.LpNodeCallDesc, f).offset for f in fields_node] + \
-        [ctypes.sizeof(_cabi.LpNodeCallDesc)]
-    assert [int(v) for v in lines[6].split()] == [getattr(_cabi.LpGraphBinding, f).offset for f in fields_bind] + \
-        [ctypes.sizeof(_cabi.LpGraphBinding), _cabi.LP_ES_ACC_DOUBLES]
-
-
 def test_engine_refuses_cpu_tensors(hip_lib):
     import pytest
     import torch

@@ -1,11 +1,8 @@
-"""The Detailer colour match, the parts that need no device: the three C entries' argument checks (made before any HIP call),
-the descriptors' layout and LP_COLOR_WS_BYTES against the header as gcc reads it, the names' presence everywhere, the node's
-protocol, the no-fallback errors, and the plain restatement (tests/color_ref.py) checked on its own."""
+"""The Detailer colour match, the parts that need no device: the three C entries' argument checks (made before any HIP call), the
+node's protocol, the no-fallback errors, and the plain restatement (tests/color_ref.py) checked on its own.  Layouts, constants
+and names against the header are tests/test_cabi_mirror.py's, for the whole C ABI."""
 import ctypes
 import os
-import re
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -13,10 +10,6 @@ import torch
 
 from lanpaint_amd import _cabi, detail_color
 from tests import color_ref
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NEW_ENTRIES = ("lp_color_stats", "lp_color_fit", "lp_color_apply")
-WS_CASES = [(1, 1, 1, 1), (2, 17, 33, 3), (7, 32, 128, 4), (3, 33, 129, 5), (81, 576, 1024, 3), (65535, 32768, 32768, 64)]
 
 
 # ---- the C ABI ------------------------------------------------------------------------------------------------------------------------
@@ -71,44 +64,7 @@ def test_color_apply_rejects_bad_arguments_without_a_device(hip_lib):
     assert hip_lib.lp_color_apply(C.byref(A(**{**good, "batch": 65536})), None) == U
 
 
-def test_color_descriptor_layout_and_workspace_macro_match_c(tmp_path):
-    structs = [("lp_color_stats_desc", _cabi.LpColorStatsDesc), ("lp_color_fit_desc", _cabi.LpColorFitDesc),
-               ("lp_color_apply_desc", _cabi.LpColorApplyDesc)]
-    prog = ['#include <stdio.h>', '#include <stddef.h>', '#include "lanpaint_hip.h"', "int main(void){"]
-    for cname, py in structs:
-        for f, _ in py._fields_:
-            prog.append(f'printf("%zu ", offsetof({cname}, {f}));')
-        prog.append(f'printf("%zu\\n", sizeof({cname}));')
-    for case in WS_CASES:
-        prog.append('printf("%lld ", (long long)LP_COLOR_WS_BYTES({}, {}, {}, {}));'.format(*case))
-    prog.append('printf("\\n%d %d %d %d %d %d %d\\n", LP_ABI_VERSION, LP_COLOR_MIN_COUNT, LP_COLOR_MAX_MARGIN, LP_COLOR_TILE_H, '
-                'LP_COLOR_TILE_W, LP_COLOR_METHOD_MEAN, LP_COLOR_METHOD_MEAN_STD); return 0;}')
-    src = tmp_path / "layout.c"
-    src.write_text("\n".join(prog))
-    exe = tmp_path / "layout"
-    subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
-    lines = subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.strip().split("\n")
-    for line, (_, py) in zip(lines, structs):
-        assert [int(v) for v in line.split()] == [getattr(py, f).offset for f, _ in py._fields_] + [ctypes.sizeof(py)]
-    assert [int(v) for v in lines[3].split()] == [_cabi.lp_color_ws_bytes(*case) for case in WS_CASES]
-    assert _cabi.lp_color_ws_bytes(81, 576, 1024, 3) == 81 * 18 * 8 * 13 * 8       # one partial row per 32 x 128 tile
-    assert [int(v) for v in lines[4].split()] == [25, _cabi.LP_COLOR_MIN_COUNT, _cabi.LP_COLOR_MAX_MARGIN, _cabi.LP_COLOR_TILE_H,
-                                                  _cabi.LP_COLOR_TILE_W, _cabi.LP_COLOR_METHOD_MEAN, _cabi.LP_COLOR_METHOD_MEAN_STD]
-    assert _cabi.LP_COLOR_MIN_COUNT == 64 == color_ref.MIN_COUNT and _cabi.LP_COLOR_MAX_MARGIN == 25
-
-
-def test_abi_version_is_unchanged_and_the_color_names_are_everywhere(hip_lib):
-    assert _cabi.ABI_VERSION == 25 and hip_lib.lp_abi_version() == 25
-    header = open(os.path.join(ROOT, "include", "lanpaint_hip.h")).read()
-    assert re.search(r"#define\s+LP_ABI_VERSION\s+25\b", header)
-    exports = open(os.path.join(ROOT, "lanpaint_amd", "csrc", "exports.map")).read()
-    patterns = re.findall(r"global:\s*([^;]+);", exports)                        # the map lists the C ABI as a glob
-    assert patterns and [p.strip() for p in patterns[0].split()] == ["lp_*"]
-    dynamic = subprocess.run(["nm", "-D", "--defined-only", _cabi.LIB_PATH], capture_output=True, text=True, check=True).stdout
-    for name in NEW_ENTRIES:
-        assert re.search(r"LP_API\s+int\s+%s\s*\(" % name, header), name
-        assert name in _cabi.EXPORTS and hasattr(hip_lib, name)
-        assert re.search(r"\bT %s$" % name, dynamic, flags=re.M), name
+def test_the_color_kernels_are_a_source_of_the_build():
     from lanpaint_amd import build
     assert "color_kernel.hip" in build.SOURCES and os.path.exists(os.path.join(build.CSRC, "color_kernel.hip"))
 
@@ -141,12 +97,10 @@ def test_color_parameter_checks_raise_value_error():
 
 
 def test_color_node_protocol_and_own_mappings():
-    from lanpaint_amd import detail_color_nodes, detail_nodes, detail_region_nodes, detail_track_nodes, nodes
+    from lanpaint_amd import detail_color_nodes
     node = detail_color_nodes.LanPaint_DetailerColorMatch
     assert detail_color_nodes.NODE_CLASS_MAPPINGS == {"LanPaint_DetailerColorMatch": node}
     assert set(detail_color_nodes.NODE_DISPLAY_NAME_MAPPINGS) == set(detail_color_nodes.NODE_CLASS_MAPPINGS)
-    for other in (nodes, detail_nodes, detail_region_nodes, detail_track_nodes):
-        assert not set(detail_color_nodes.NODE_CLASS_MAPPINGS) & set(other.NODE_CLASS_MAPPINGS)
     req = node.INPUT_TYPES()["required"]
     assert list(req) == ["image", "reference", "mask", "method", "strength", "margin", "smooth", "clip_frames"]
     assert req["image"][0] == "IMAGE" and req["reference"][0] == "IMAGE" and req["mask"][0] == "MASK"
@@ -162,12 +116,6 @@ def test_color_node_protocol_and_own_mappings():
     if not torch.cuda.is_available():
         with pytest.raises(RuntimeError, match="no CPU fallback"):
             node().match(torch.zeros(2, 16, 16, 3), torch.zeros(2, 16, 16, 3), torch.zeros(2, 16, 16))
-
-
-def test_color_modules_have_no_unbound_names():
-    files = [os.path.join(ROOT, "lanpaint_amd", f) for f in ("detail_color.py", "detail_color_nodes.py")]
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "scripts", "check_names.py"), *files], capture_output=True, text=True)
-    assert p.returncode == 0, p.stdout
 
 
 # ---- the restatement on its own -------------------------------------------------------------------------------------------------------

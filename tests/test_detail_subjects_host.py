@@ -1,12 +1,9 @@
 """The per-subject Detailer, the parts that need no device: the subjects rule's worked answers, its plain restatement
 (tests/subjects_ref.py) and its properties over generated box lists, the identity with plan_track, the argument checks of the
-four C entries (made before any HIP call), the descriptors' layout, and the nodes' protocol."""
+four C entries (made before any HIP call), and the nodes' protocol.  Layouts, constants and names against the header are
+tests/test_cabi_mirror.py's, for the whole C ABI."""
 import ctypes
 import dataclasses
-import os
-import re
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -16,8 +13,6 @@ from hypothesis import given, settings, strategies as st
 from lanpaint_amd import _cabi, detail, detail_subjects
 from tests import subjects_ref
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NEW_ENTRIES = ("lp_mask_components_frames", "lp_subject_boxes", "lp_detail_resample_subjects", "lp_detail_stitch_subjects")
 CAP = _cabi.LP_DETAIL_MAX_COMPONENTS
 
 
@@ -289,50 +284,13 @@ def test_subject_entries_reject_bad_arguments_without_a_device(hip_lib):
     assert hip_lib.lp_detail_stitch_subjects(C.byref(S(**{**good, "batch": 65536})), None) == U
 
 
-def test_subject_descriptor_layout_and_the_workspace_macro_match_c(tmp_path):
-    structs = [("lp_detail_resample_subjects_desc", _cabi.LpDetailResampleSubjectsDesc),
-               ("lp_detail_stitch_subjects_desc", _cabi.LpDetailStitchSubjectsDesc)]
-    prog = ['#include <stdio.h>', '#include <stddef.h>', '#include "lanpaint_hip.h"', "int main(void){"]
-    for cname, py in structs:
-        for f, _ in py._fields_:
-            prog.append(f'printf("%zu ", offsetof({cname}, {f}));')
-        prog.append(f'printf("%zu\\n", sizeof({cname}));')
-    prog.append('printf("%lld %lld %lld %lld %d %d %d\\n", (long long)LP_COMPONENTS_FRAMES_WS_BYTES(1, 1, 1), '
-                '(long long)LP_COMPONENTS_FRAMES_WS_BYTES(81, 720, 1280), (long long)LP_COMPONENTS_FRAMES_WS_BYTES(65535, 128, 128), '
-                '(long long)LP_COMPONENTS_FRAMES_WS_BYTES(1, 720, 1280) - (long long)LP_COMPONENTS_WS_BYTES(720, 1280), '
-                'LP_DETAIL_MAX_COMPONENTS, LP_DETAIL_MAX_REGIONS, LP_ABI_VERSION); return 0;}')
-    src = tmp_path / "layout.c"
-    src.write_text("\n".join(prog))
-    exe = tmp_path / "layout"
-    subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
-    lines = subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.strip().split("\n")
-    for line, (_, py) in zip(lines, structs):
-        assert [int(v) for v in line.split()] == [getattr(py, f).offset for f, _ in py._fields_] + [ctypes.sizeof(py)]
-    ws = _cabi.lp_components_frames_ws_bytes
-    assert [int(v) for v in lines[2].split()] == [ws(1, 1, 1), ws(81, 720, 1280), ws(65535, 128, 128), 0, CAP,
-                                                  _cabi.LP_DETAIL_MAX_REGIONS, _cabi.ABI_VERSION]
-    assert ws(1, 1, 1) == 4100 and ws(3, 17, 65) == _cabi.lp_components_ws_bytes(51, 65)
-
-
-def test_the_new_names_are_everywhere(hip_lib):
-    header = open(os.path.join(ROOT, "include", "lanpaint_hip.h")).read()
-    dynamic = subprocess.run(["nm", "-D", "--defined-only", _cabi.LIB_PATH], capture_output=True, text=True, check=True).stdout
-    for name in NEW_ENTRIES:
-        assert re.search(r"LP_API\s+int\s+%s\s*\(" % name, header), name
-        assert name in _cabi.EXPORTS and hasattr(hip_lib, name)
-        assert re.search(r"\bT %s$" % name, dynamic, flags=re.M), name
-    assert hip_lib.lp_abi_version() == _cabi.ABI_VERSION
-
-
 # ---- nodes ----------------------------------------------------------------------------------------------------------------------------
 def test_subject_nodes_protocol_and_own_mappings():
-    from lanpaint_amd import detail_nodes, detail_region_nodes, detail_subject_nodes, detail_track_nodes, nodes
+    from lanpaint_amd import detail_nodes, detail_region_nodes, detail_subject_nodes, detail_track_nodes
     crop, stitch = detail_subject_nodes.LanPaint_DetailerCropSubjects, detail_subject_nodes.LanPaint_DetailerStitchSubjects
     assert detail_subject_nodes.NODE_CLASS_MAPPINGS == {"LanPaint_DetailerCropSubjects": crop,
                                                         "LanPaint_DetailerStitchSubjects": stitch}
     assert set(detail_subject_nodes.NODE_DISPLAY_NAME_MAPPINGS) == set(detail_subject_nodes.NODE_CLASS_MAPPINGS)
-    for other in (nodes, detail_nodes, detail_region_nodes, detail_track_nodes):
-        assert not set(detail_subject_nodes.NODE_CLASS_MAPPINGS) & set(other.NODE_CLASS_MAPPINGS)
     assert len(detail_track_nodes.NODE_CLASS_MAPPINGS) == 2 and len(detail_region_nodes.NODE_CLASS_MAPPINGS) == 2
     req = crop.INPUT_TYPES()["required"]
     old = detail_track_nodes.LanPaint_DetailerCropTrack.INPUT_TYPES()["required"]
@@ -360,9 +318,3 @@ def test_subject_nodes_protocol_and_own_mappings():
             crop().crop(torch.zeros(2, 16, 16, 3), torch.zeros(2, 16, 16))
         with pytest.raises(RuntimeError, match="no CPU fallback"):
             stitch().stitch({"original": torch.zeros(2, 16, 16, 3)}, torch.zeros(2, 8, 8, 3), 9)
-
-
-def test_subject_modules_have_no_unbound_names():
-    files = [os.path.join(ROOT, "lanpaint_amd", f) for f in ("detail_subjects.py", "detail_subject_nodes.py", "detail.py")]
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "scripts", "check_names.py"), *files], capture_output=True, text=True)
-    assert p.returncode == 0, p.stdout

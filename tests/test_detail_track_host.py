@@ -1,12 +1,9 @@
 """The Detailer that follows a moving mask, the parts that need no device: the track rule's worked answers, its plain
 restatement (tests/track_ref.py) and its properties over generated box lists, the argument checks of plan_track and of the three
-C entries (made before any HIP call), the descriptors' layout, and the nodes' protocol."""
+C entries (made before any HIP call), and the nodes' protocol.  Layouts, constants and names against the header are
+tests/test_cabi_mirror.py's, for the whole C ABI."""
 import ctypes
 import dataclasses
-import os
-import re
-import subprocess
-import sys
 
 import pytest
 import torch
@@ -14,9 +11,6 @@ from hypothesis import given, settings, strategies as st
 
 from lanpaint_amd import _cabi, detail
 from tests import track_ref
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NEW_ENTRIES = ("lp_mask_bbox_frames", "lp_detail_resample_track", "lp_detail_stitch_track")
 
 
 def _empty(H, W):
@@ -244,46 +238,12 @@ def test_track_entries_reject_bad_arguments_without_a_device(hip_lib):
     assert hip_lib.lp_detail_stitch_track(C.byref(S(**{**good, "batch": 65536, "mask_batch": 65536})), None) == U
 
 
-def test_track_descriptor_layout_matches_c(tmp_path):
-    structs = [("lp_detail_resample_track_desc", _cabi.LpDetailResampleTrackDesc),
-               ("lp_detail_stitch_track_desc", _cabi.LpDetailStitchTrackDesc)]
-    prog = ['#include <stdio.h>', '#include <stddef.h>', '#include "lanpaint_hip.h"', "int main(void){"]
-    for cname, py in structs:
-        for f, _ in py._fields_:
-            prog.append(f'printf("%zu ", offsetof({cname}, {f}));')
-        prog.append(f'printf("%zu\\n", sizeof({cname}));')
-    prog.append('printf("%d\\n", LP_ABI_VERSION); return 0;}')
-    src = tmp_path / "layout.c"
-    src.write_text("\n".join(prog))
-    exe = tmp_path / "layout"
-    subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
-    lines = subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.strip().split("\n")
-    for line, (_, py) in zip(lines, structs):
-        assert [int(v) for v in line.split()] == [getattr(py, f).offset for f, _ in py._fields_] + [ctypes.sizeof(py)]
-    assert int(lines[2]) == _cabi.ABI_VERSION == 25
-
-
-def test_abi_version_is_unchanged_and_the_new_names_are_everywhere(hip_lib):
-    assert _cabi.ABI_VERSION == 25 and hip_lib.lp_abi_version() == 25
-    header = open(os.path.join(ROOT, "include", "lanpaint_hip.h")).read()
-    exports = open(os.path.join(ROOT, "lanpaint_amd", "csrc", "exports.map")).read()
-    patterns = re.findall(r"global:\s*([^;]+);", exports)                        # the map lists the C ABI as a glob
-    assert patterns and [p.strip() for p in patterns[0].split()] == ["lp_*"]
-    dynamic = subprocess.run(["nm", "-D", "--defined-only", _cabi.LIB_PATH], capture_output=True, text=True, check=True).stdout
-    for name in NEW_ENTRIES:
-        assert re.search(r"LP_API\s+int\s+%s\s*\(" % name, header), name
-        assert name in _cabi.EXPORTS and hasattr(hip_lib, name)
-        assert re.search(r"\bT %s$" % name, dynamic, flags=re.M), name
-
-
 # ---- nodes ----------------------------------------------------------------------------------------------------------------------------
 def test_track_nodes_protocol_and_own_mappings():
-    from lanpaint_amd import detail_nodes, detail_region_nodes, detail_track_nodes, nodes
+    from lanpaint_amd import detail_nodes, detail_region_nodes, detail_track_nodes
     crop, stitch = detail_track_nodes.LanPaint_DetailerCropTrack, detail_track_nodes.LanPaint_DetailerStitchTrack
     assert detail_track_nodes.NODE_CLASS_MAPPINGS == {"LanPaint_DetailerCropTrack": crop, "LanPaint_DetailerStitchTrack": stitch}
     assert set(detail_track_nodes.NODE_DISPLAY_NAME_MAPPINGS) == set(detail_track_nodes.NODE_CLASS_MAPPINGS)
-    for other in (nodes, detail_nodes, detail_region_nodes):
-        assert not set(detail_track_nodes.NODE_CLASS_MAPPINGS) & set(other.NODE_CLASS_MAPPINGS)
     assert len(detail_nodes.NODE_CLASS_MAPPINGS) == 2 and len(detail_region_nodes.NODE_CLASS_MAPPINGS) == 2
     req = crop.INPUT_TYPES()["required"]
     old = detail_nodes.LanPaint_DetailerCrop.INPUT_TYPES()["required"]
@@ -308,9 +268,3 @@ def test_track_nodes_protocol_and_own_mappings():
             crop().crop(torch.zeros(2, 16, 16, 3), torch.zeros(2, 16, 16))
         with pytest.raises(RuntimeError, match="no CPU fallback"):
             stitch().stitch({"original": torch.zeros(2, 16, 16, 3)}, torch.zeros(2, 8, 8, 3), 9)
-
-
-def test_track_modules_have_no_unbound_names():
-    files = [os.path.join(ROOT, "lanpaint_amd", f) for f in ("detail.py", "detail_track_nodes.py")]
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "scripts", "check_names.py"), *files], capture_output=True, text=True)
-    assert p.returncode == 0, p.stdout

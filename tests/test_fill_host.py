@@ -1,13 +1,10 @@
 """The masked-area fill and the outpaint canvas, the parts that need no device: the restatement (tests/fill_ref.py) checked on its
-own, plan_outpaint's arithmetic, the pad's mask rule on an example written out by hand, the three C entries' argument checks
-(made before any HIP call), the descriptors' layout against the header as gcc reads it, lp_fill_ws_bytes against its Python
-mirror, the names' presence everywhere, the nodes' protocol and the no-fallback errors."""
+own, plan_outpaint's arithmetic, the pad's mask rule on an example written out by hand, the three C entries' argument checks (made
+before any HIP call), lp_fill_ws_bytes against its Python mirror, the nodes' protocol and the no-fallback errors.  Layouts,
+constants and names against the header are tests/test_cabi_mirror.py's, for the whole C ABI."""
 import ctypes
 import dataclasses
 import os
-import re
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -16,8 +13,6 @@ import torch
 from lanpaint_amd import _cabi, fill
 from tests import fill_ref
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NEW_ENTRIES = ("lp_mask_fill", "lp_fill_ws_bytes", "lp_outpaint_pad")
 WS_CASES = [(1, 1, 1, 1), (1, 1, 2, 1), (2, 17, 33, 3), (3, 32, 32, 4), (1, 2049, 1, 5), (81, 720, 1280, 3), (65535, 32768, 32768, 64)]
 REF_SHAPES = [(1, 1), (1, 7), (7, 1), (63, 65), (64, 64), (129, 65), (130, 200)]
 
@@ -166,38 +161,7 @@ def test_outpaint_pad_rejects_bad_arguments_without_a_device(hip_lib):
     assert hip_lib.lp_outpaint_pad(C.byref(O(**{**good, "batch": 65536, "mask_batch": 0, "mask": None})), None) == U
 
 
-def test_fill_descriptor_layouts_match_c(tmp_path):
-    structs = [("lp_fill_desc", _cabi.LpFillDesc), ("lp_outpaint_desc", _cabi.LpOutpaintDesc)]
-    prog = ['#include <stdio.h>', '#include <stddef.h>', '#include "lanpaint_hip.h"', "int main(void){"]
-    for cname, py in structs:
-        for f, _ in py._fields_:
-            prog.append(f'printf("%zu ", offsetof({cname}, {f}));')
-        prog.append(f'printf("%zu\\n", sizeof({cname}));')
-    prog.append('printf("%d %d %d\\n", LP_ABI_VERSION, LP_FILL_TILE, LP_FILL_SPAN); return 0;}')
-    src = tmp_path / "layout.c"
-    src.write_text("\n".join(prog))
-    exe = tmp_path / "layout"
-    subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
-    lines = subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.strip().split("\n")
-    for line, (_, py) in zip(lines, structs):
-        assert [int(v) for v in line.split()] == [getattr(py, f).offset for f, _ in py._fields_] + [ctypes.sizeof(py)]
-    assert [f for f, _ in _cabi.LpFillDesc._fields_] == ["batch", "height", "width", "channels", "mask_batch", "reserved0", "image",
-                                                         "mask", "out", "ws", "ws_bytes"]
-    assert [f for f, _ in _cabi.LpOutpaintDesc._fields_] == ["batch", "height", "width", "channels", "mask_batch", "left", "top",
-                                                             "right", "bottom", "overlap", "reserved0", "image", "mask",
-                                                             "image_out", "mask_out"]
-    assert [int(v) for v in lines[2].split()] == [25, _cabi.LP_FILL_TILE, _cabi.LP_FILL_SPAN]
-
-
-def test_abi_version_is_unchanged_and_the_fill_names_are_everywhere(hip_lib):
-    assert _cabi.ABI_VERSION == 25 and hip_lib.lp_abi_version() == 25
-    header = open(os.path.join(ROOT, "include", "lanpaint_hip.h")).read()
-    assert re.search(r"#define\s+LP_ABI_VERSION\s+25\b", header)
-    dynamic = subprocess.run(["nm", "-D", "--defined-only", _cabi.LIB_PATH], capture_output=True, text=True, check=True).stdout
-    for name in NEW_ENTRIES:
-        assert re.search(r"LP_API\s+(int|int64_t)\s+%s\s*\(" % name, header), name
-        assert name in _cabi.EXPORTS and hasattr(hip_lib, name)
-        assert re.search(r"\bT %s$" % name, dynamic, flags=re.M), name
+def test_the_fill_kernels_are_a_source_of_the_build():
     from lanpaint_amd import build
     assert "fill_kernel.hip" in build.SOURCES and os.path.exists(os.path.join(build.CSRC, "fill_kernel.hip"))
 
@@ -214,13 +178,11 @@ def test_fill_functions_refuse_cpu_tensors():
 
 
 def test_fill_nodes_protocol_and_own_mappings():
-    from lanpaint_amd import detail_color_nodes, detail_nodes, detail_region_nodes, detail_track_nodes, fill_nodes, nodes
+    from lanpaint_amd import fill_nodes
     pad, mf = fill_nodes.LanPaint_OutpaintPad, fill_nodes.LanPaint_MaskFill
     assert fill_nodes.NODE_CLASS_MAPPINGS == {"LanPaint_OutpaintPad": pad, "LanPaint_MaskFill": mf}
     assert fill_nodes.NODE_DISPLAY_NAME_MAPPINGS == {"LanPaint_OutpaintPad": "LanPaint Outpaint Pad",
                                                      "LanPaint_MaskFill": "LanPaint Mask Fill"}
-    for other in (nodes, detail_nodes, detail_region_nodes, detail_track_nodes, detail_color_nodes):
-        assert not set(fill_nodes.NODE_CLASS_MAPPINGS) & set(other.NODE_CLASS_MAPPINGS)
     types = pad.INPUT_TYPES()
     req = types["required"]
     assert list(req) == ["image", "left", "top", "right", "bottom", "overlap", "multiple_of", "fill"]
@@ -240,9 +202,3 @@ def test_fill_nodes_protocol_and_own_mappings():
             mf().fill(torch.zeros(2, 16, 16, 3), torch.zeros(2, 16, 16))
         with pytest.raises(RuntimeError, match="no CPU fallback"):
             pad().pad(torch.zeros(2, 16, 16, 3), left=8)
-
-
-def test_fill_modules_have_no_unbound_names():
-    files = [os.path.join(ROOT, "lanpaint_amd", f) for f in ("fill.py", "fill_nodes.py")]
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "scripts", "check_names.py"), *files], capture_output=True, text=True)
-    assert p.returncode == 0, p.stdout

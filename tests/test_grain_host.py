@@ -1,13 +1,10 @@
 """The grain match, the parts that need no device: the restatement (tests/grain_ref.py) checked on its own -- Philox against
 Random123's vector, the kernel table by convolution, the white value's variance, and the case the rule was tried on --, the four C
-entries' argument checks (made before any HIP call), the descriptors' layout against the header as gcc reads it, the names'
-presence everywhere, the node's protocol and the no-fallback errors."""
+entries' argument checks (made before any HIP call), the node's protocol and the no-fallback errors.  Layouts, constants and names
+against the header are tests/test_cabi_mirror.py's, for the whole C ABI."""
 import ctypes
 import functools
 import os
-import re
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -16,10 +13,7 @@ import torch
 from lanpaint_amd import _cabi, grain, grain_nodes
 from tests import grain_ref as ref
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW_ENTRIES = ("lp_grain_stats", "lp_grain_fit", "lp_grain_field", "lp_grain_apply")
-DESCS = {"lp_grain_stats_desc": _cabi.LpGrainStatsDesc, "lp_grain_fit_desc": _cabi.LpGrainFitDesc,
-         "lp_grain_field_desc": _cabi.LpGrainFieldDesc, "lp_grain_apply_desc": _cabi.LpGrainApplyDesc}
 
 
 def _bits(a):
@@ -209,41 +203,9 @@ def test_grain_entries_reject_bad_arguments_without_a_device(hip_lib):
     assert hip_lib.lp_grain_apply(C.byref(_cabi.LpGrainApplyDesc(**{**good, "batch": 65536, "mask_batch": 1})), None) == U
 
 
-def test_grain_descriptor_layouts_and_constants_match_c(tmp_path):
-    prog = ['#include <stdio.h>', '#include <stddef.h>', '#include "lanpaint_hip.h"', "int main(void){"]
-    for cname, py in DESCS.items():
-        for f, _ in py._fields_:
-            prog.append(f'printf("%zu ", offsetof({cname}, {f}));')
-        prog.append(f'printf("%zu\\n", sizeof({cname}));')
-    names = ["LP_ABI_VERSION", "LP_GRAIN_BANDS", "LP_GRAIN_MIN_COUNT", "LP_GRAIN_WHITE_VAR", "LP_GRAIN_MAX_STD",
-             "LP_GRAIN_MAX_MARGIN", "LP_GRAIN_TILE_H", "LP_GRAIN_TILE_W", "LP_GRAIN_REGION_ALL", "LP_GRAIN_REGION_OUTSIDE",
-             "LP_GRAIN_REGION_INSIDE", "LP_GRAIN_SIZE_AUTO", "LP_GRAIN_MAX_FRAME0"]
-    prog.append('printf("' + "%d " * len(names) + '\\n", ' + ", ".join(names) + "); return 0;}")
-    src = tmp_path / "layout.c"
-    src.write_text("\n".join(prog))
-    exe = tmp_path / "layout"
-    subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
-    lines = subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.strip().split("\n")
-    for line, py in zip(lines, DESCS.values()):
-        assert [int(v) for v in line.split()] == [getattr(py, f).offset for f, _ in py._fields_] + [ctypes.sizeof(py)], py
-    values = [int(v) for v in lines[len(DESCS)].split()]
-    assert values == [_cabi.ABI_VERSION] + [getattr(_cabi, n) for n in names[1:]]
-    assert _cabi.ABI_VERSION == 25
-    assert values[1:8] == [8, 64, 21845, 64, 25, 16, 64] and values[8:12] == [0, 1, 2, -1]
-    assert (ref.K, ref.MIN_COUNT, ref.WHITE_VAR, ref.MAX_STD, ref.MAX_MARGIN) == tuple(values[1:6])
-    assert (ref.ALL, ref.OUTSIDE, ref.INSIDE, ref.AUTO) == tuple(values[8:12])
-
-
-def test_the_grain_names_are_everywhere(hip_lib):
-    header = open(os.path.join(ROOT, "include", "lanpaint_hip.h")).read()
-    dynamic = subprocess.run(["nm", "-D", "--defined-only", _cabi.LIB_PATH], capture_output=True, text=True, check=True).stdout
-    for name in NEW_ENTRIES:
-        assert re.search(r"LP_API\s+int\s+%s\s*\(" % name, header), name
-        assert name in _cabi.EXPORTS and hasattr(hip_lib, name)
-        assert re.search(r"\bT %s$" % name, dynamic, flags=re.M), name
+def test_the_grain_kernels_are_a_source_of_the_build():
     from lanpaint_amd import build
     assert "grain_kernel.hip" in build.SOURCES and os.path.exists(os.path.join(build.CSRC, "grain_kernel.hip"))
-    assert hip_lib.lp_abi_version() == 25
 
 
 # ---- the wrapper and the node ---------------------------------------------------------------------------------------------------------
@@ -278,15 +240,9 @@ def test_grain_refuses_cpu_tensors_and_bad_arguments():
 
 
 def test_grain_node_protocol_and_own_mappings():
-    from lanpaint_amd import (detail_color_nodes, detail_nodes, detail_region_nodes, detail_subject_nodes, detail_track_nodes,
-                              fill_nodes, multiband_nodes, nodes, refine_nodes, stabilize_nodes)
     node = grain_nodes.LanPaint_GrainMatch
     assert grain_nodes.NODE_CLASS_MAPPINGS == {"LanPaint_GrainMatch": node}
     assert grain_nodes.NODE_DISPLAY_NAME_MAPPINGS == {"LanPaint_GrainMatch": "LanPaint Grain Match"}
-    for other in (nodes, detail_nodes, detail_region_nodes, detail_track_nodes, detail_subject_nodes, detail_color_nodes, fill_nodes,
-                  multiband_nodes, refine_nodes, stabilize_nodes):
-        assert not set(grain_nodes.NODE_CLASS_MAPPINGS) & set(other.NODE_CLASS_MAPPINGS)
-        assert not set(grain_nodes.NODE_DISPLAY_NAME_MAPPINGS) & set(other.NODE_DISPLAY_NAME_MAPPINGS)
     types = node.INPUT_TYPES()
     req, opt = types["required"], types["optional"]
     assert list(types) == ["required", "optional"] and list(opt) == ["reference"] and opt["reference"][0] == "IMAGE"
@@ -308,9 +264,3 @@ def test_grain_node_protocol_and_own_mappings():
     if not torch.cuda.is_available():
         with pytest.raises(RuntimeError, match="no CPU fallback"):
             node().match(torch.zeros(1, 16, 16, 3), torch.zeros(1, 16, 16))
-
-
-def test_grain_modules_have_no_unbound_names():
-    files = [os.path.join(ROOT, "lanpaint_amd", f) for f in ("grain.py", "grain_nodes.py")]
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "scripts", "check_names.py"), *files], capture_output=True, text=True)
-    assert p.returncode == 0, p.stdout

@@ -1,13 +1,9 @@
-"""The multiband blend, the parts that need no device: the restatement (tests/multiband_ref.py) checked on its own -- the
-properties the rule promises, as bits, and REDUCE / EXPAND against an independent statement of Burt-Adelson --, the two C
-entries' argument checks (made before any HIP call), the descriptor's layout against the header as gcc reads it,
-lp_multiband_ws_bytes against its Python mirror and the closed form, the names' presence everywhere, the node's protocol and
-the no-fallback errors."""
+"""The multiband blend, the parts that need no device: the restatement (tests/multiband_ref.py) checked on its own -- the properties
+the rule promises, as bits, and REDUCE / EXPAND against an independent statement of Burt-Adelson --, the two C entries' argument
+checks (made before any HIP call), lp_multiband_ws_bytes against its Python mirror and the closed form, the node's protocol and
+the no-fallback errors.  Layouts, constants and names against the header are tests/test_cabi_mirror.py's, for the whole C ABI."""
 import ctypes
 import os
-import re
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -17,8 +13,6 @@ import torch.nn.functional as F
 from lanpaint_amd import _cabi, multiband
 from tests import multiband_ref as ref
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NEW_ENTRIES = ("lp_multiband_blend", "lp_multiband_ws_bytes")
 LEVELS = (0, 1, 2, 3, 5, 12)
 SHAPES = [(1, 1), (1, 7), (7, 1), (2, 2), (3, 5), (63, 65), (64, 64), (130, 200), (300, 300)]
 WS_CASES = [(1, 1, 1, 1, 5), (1, 1, 2, 1, 1), (1, 1, 2, 1, 0), (2, 17, 33, 3, 2), (3, 32, 32, 4, 16), (1, 2049, 1, 5, 12),
@@ -183,33 +177,7 @@ def test_multiband_ws_bytes_equals_its_mirror_and_the_closed_form(hip_lib):
     assert hip_lib.lp_multiband_ws_bytes(65536, 8, 8, 3, 5) == U
 
 
-def test_multiband_descriptor_layout_matches_c(tmp_path):
-    py = _cabi.LpMultibandDesc
-    prog = ['#include <stdio.h>', '#include <stddef.h>', '#include "lanpaint_hip.h"', "int main(void){"]
-    for f, _ in py._fields_:
-        prog.append(f'printf("%zu ", offsetof(lp_multiband_desc, {f}));')
-    prog.append('printf("%zu\\n", sizeof(lp_multiband_desc));')
-    prog.append('printf("%d\\n", LP_ABI_VERSION); return 0;}')
-    src = tmp_path / "layout.c"
-    src.write_text("\n".join(prog))
-    exe = tmp_path / "layout"
-    subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
-    lines = subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.strip().split("\n")
-    assert [int(v) for v in lines[0].split()] == [getattr(py, f).offset for f, _ in py._fields_] + [ctypes.sizeof(py)]
-    assert [f for f, _ in py._fields_] == ["batch", "height", "width", "channels", "mask_batch", "levels", "image1", "image2", "mask",
-                                           "out", "ws", "ws_bytes"]
-    assert int(lines[1]) == 25
-
-
-def test_abi_version_is_unchanged_and_the_multiband_names_are_everywhere(hip_lib):
-    assert _cabi.ABI_VERSION == 25 and hip_lib.lp_abi_version() == 25
-    header = open(os.path.join(ROOT, "include", "lanpaint_hip.h")).read()
-    assert re.search(r"#define\s+LP_ABI_VERSION\s+25\b", header)
-    dynamic = subprocess.run(["nm", "-D", "--defined-only", _cabi.LIB_PATH], capture_output=True, text=True, check=True).stdout
-    for name in NEW_ENTRIES:
-        assert re.search(r"LP_API\s+(int|int64_t)\s+%s\s*\(" % name, header), name
-        assert name in _cabi.EXPORTS and hasattr(hip_lib, name)
-        assert re.search(r"\bT %s$" % name, dynamic, flags=re.M), name
+def test_the_multiband_kernels_are_a_source_of_the_build():
     from lanpaint_amd import build
     assert "multiband_kernel.hip" in build.SOURCES and os.path.exists(os.path.join(build.CSRC, "multiband_kernel.hip"))
 
@@ -224,14 +192,10 @@ def test_blend_multiband_refuses_cpu_tensors():
 
 
 def test_multiband_node_protocol_and_own_mappings():
-    from lanpaint_amd import (detail_color_nodes, detail_nodes, detail_region_nodes, detail_subject_nodes, detail_track_nodes,
-                              fill_nodes, multiband_nodes, nodes)
+    from lanpaint_amd import multiband_nodes
     node = multiband_nodes.LanPaint_MultibandBlend
     assert multiband_nodes.NODE_CLASS_MAPPINGS == {"LanPaint_MultibandBlend": node}
     assert multiband_nodes.NODE_DISPLAY_NAME_MAPPINGS == {"LanPaint_MultibandBlend": "LanPaint Multiband Blend"}
-    for other in (nodes, detail_nodes, detail_region_nodes, detail_track_nodes, detail_subject_nodes, detail_color_nodes, fill_nodes):
-        assert not set(multiband_nodes.NODE_CLASS_MAPPINGS) & set(other.NODE_CLASS_MAPPINGS)
-        assert not set(multiband_nodes.NODE_DISPLAY_NAME_MAPPINGS) & set(other.NODE_DISPLAY_NAME_MAPPINGS)
     types = node.INPUT_TYPES()
     req = types["required"]
     assert list(types) == ["required"] and list(req) == ["image1", "image2", "mask", "levels"]
@@ -242,9 +206,3 @@ def test_multiband_node_protocol_and_own_mappings():
     if not torch.cuda.is_available():
         with pytest.raises(RuntimeError, match="no CPU fallback"):
             node().blend(torch.zeros(2, 16, 16, 3), torch.zeros(2, 16, 16, 3), torch.zeros(2, 16, 16), 5)
-
-
-def test_multiband_modules_have_no_unbound_names():
-    files = [os.path.join(ROOT, "lanpaint_amd", f) for f in ("multiband.py", "multiband_nodes.py")]
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "scripts", "check_names.py"), *files], capture_output=True, text=True)
-    assert p.returncode == 0, p.stdout

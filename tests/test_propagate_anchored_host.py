@@ -1,13 +1,10 @@
-"""The anchored video mask propagate, the parts that need no device: the restatement (tests/propagate_anchored_ref.py) checked on
-its own -- that the rule does what it is for, on a clip with sub-pixel motion, and the properties it promises, as bits --, the C
-entry's argument checks (made before any HIP call), the descriptor's layout against the header as gcc reads it, the names'
-presence, the nodes' protocol, and that the existing propagate nodes are as they were."""
+"""The anchored video mask propagate, the parts that need no device: the restatement (tests/propagate_anchored_ref.py) checked on its
+own -- that the rule does what it is for, on a clip with sub-pixel motion, and the properties it promises, as bits --, the C
+entry's argument checks (made before any HIP call), the nodes' protocol, and that the existing propagate nodes are as they were.
+Layouts, constants and names against the header are tests/test_cabi_mirror.py's, for the whole C ABI."""
 import ctypes
 import functools
 import os
-import re
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -111,33 +108,8 @@ def test_anchor_match_rejects_bad_arguments_without_a_device(hip_lib):
         assert hip_lib.lp_prop_anchor_match(C.byref(_cabi.LpPropAnchorDesc(**{**good, **change})), None) == E, change
 
 
-def test_anchor_descriptor_layout_and_constants_match_c(tmp_path):
-    prog = ['#include <stdio.h>', '#include <stddef.h>', '#include "lanpaint_hip.h"', "int main(void){"]
-    for f, _ in _cabi.LpPropAnchorDesc._fields_:
-        prog.append(f'printf("%zu ", offsetof(lp_prop_anchor_desc, {f}));')
-    prog.append('printf("%zu\\n", sizeof(lp_prop_anchor_desc));')
-    prog.append('printf("%d %d %d\\n", LP_PROP_MAX_SEARCH, LP_PROP_MAX_SMOOTH, LP_ABI_VERSION); return 0;}')
-    src = tmp_path / "layout.c"
-    src.write_text("\n".join(prog))
-    exe = tmp_path / "layout"
-    subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
-    lines = subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.strip().split("\n")
-    py = _cabi.LpPropAnchorDesc
-    assert [int(v) for v in lines[0].split()] == [getattr(py, f).offset for f, _ in py._fields_] + [ctypes.sizeof(py)]
-    assert ctypes.sizeof(py) == 64
-    assert [int(v) for v in lines[1].split()] == [_cabi.LP_PROP_MAX_SEARCH, _cabi.LP_PROP_MAX_SMOOTH, _cabi.ABI_VERSION] == [7, 64, 25]
-
-
-def test_the_anchor_names_are_everywhere(hip_lib):
+def test_the_header_and_the_documents_say_the_anchor_words():
     header = open(os.path.join(ROOT, "include", "lanpaint_hip.h")).read()
-    exports = open(os.path.join(ROOT, "lanpaint_amd", "csrc", "exports.map")).read()
-    dynamic = subprocess.run(["nm", "-D", "--defined-only", _cabi.LIB_PATH], capture_output=True, text=True, check=True).stdout
-    assert re.search(r"global:\s*lp_\*;", exports)                      # the version script exports every lp_* entry
-    name = "lp_prop_anchor_match"
-    assert re.search(r"LP_API\s+int\s+%s\s*\(" % name, header)
-    assert name in _cabi.EXPORTS and hasattr(hip_lib, name)
-    assert re.search(r"\bT %s$" % name, dynamic, flags=re.M)
-    assert _cabi.ABI_VERSION == 25 and hip_lib.lp_abi_version() == 25
     for word in ("Video mask propagate, anchored", "An invalid block holds 0", "predictor p = 0", "anchor = 0 is the caller's",
                  "re-anchoring every n-th frame only"):
         assert word in header, word
@@ -165,8 +137,7 @@ def test_propagate_anchored_refuses_cpu_tensors_and_bad_arguments():
 
 
 def test_anchored_node_protocol_and_the_existing_propagate_nodes_are_untouched():
-    from lanpaint_amd import (propagate_anchored_nodes, propagate_keys_nodes, propagate_keys_visible_nodes, propagate_nodes,
-                              propagate_visible_nodes, shots_nodes, stabilize_nodes, video_nodes)
+    from lanpaint_amd import propagate_anchored_nodes, propagate_nodes, shots_nodes
     node = propagate_anchored_nodes.LanPaint_VideoMaskPropagateAnchored
     per_shot = propagate_anchored_nodes.LanPaint_VideoMaskPropagateAnchoredShots
     assert propagate_anchored_nodes.NODE_CLASS_MAPPINGS == {"LanPaint_VideoMaskPropagateAnchored": node,
@@ -174,10 +145,6 @@ def test_anchored_node_protocol_and_the_existing_propagate_nodes_are_untouched()
     assert propagate_anchored_nodes.NODE_DISPLAY_NAME_MAPPINGS == {
         "LanPaint_VideoMaskPropagateAnchored": "LanPaint Video Mask Propagate (Anchored)",
         "LanPaint_VideoMaskPropagateAnchoredShots": "LanPaint Video Mask Propagate (Anchored, Shots)"}
-    for other in (propagate_nodes, propagate_keys_nodes, propagate_visible_nodes, propagate_keys_visible_nodes, shots_nodes,
-                  stabilize_nodes, video_nodes):
-        assert not set(propagate_anchored_nodes.NODE_CLASS_MAPPINGS) & set(other.NODE_CLASS_MAPPINGS)
-        assert not set(propagate_anchored_nodes.NODE_DISPLAY_NAME_MAPPINGS.values()) & set(other.NODE_DISPLAY_NAME_MAPPINGS.values())
     assert propagate_nodes.NODE_CLASS_MAPPINGS == {"LanPaint_VideoMaskPropagate": propagate_nodes.LanPaint_VideoMaskPropagate}
     assert len(shots_nodes.NODE_CLASS_MAPPINGS) == 7
     types = node.INPUT_TYPES()
@@ -205,10 +172,3 @@ def test_anchored_node_protocol_and_the_existing_propagate_nodes_are_untouched()
     for bad in (-1, 8):                                                  # anchor outside 0..7 raises, with or without a device
         with pytest.raises(ValueError):
             node().propagate(torch.zeros(4, 16, 16, 3), torch.zeros(16, 16), 0, 4, 2, 8, bad)
-
-
-def test_propagate_anchored_modules_have_no_unbound_names():
-    files = [os.path.join(ROOT, "lanpaint_amd", f) for f in ("propagate_anchored.py", "propagate_anchored_nodes.py", "shots.py",
-                                                              "shots_nodes.py")]
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "scripts", "check_names.py"), *files], capture_output=True, text=True)
-    assert p.returncode == 0, p.stdout

@@ -1,13 +1,10 @@
 """The video mask propagate, the parts that need no device: the restatement (tests/propagate_ref.py) checked on its own -- the
 properties the rule promises, as bits, and the one quality condition it has to meet on moving-disc scenes --, the C entries'
-argument checks (made before any HIP call), the descriptors' layout against the header as gcc reads it, the names' presence
-everywhere, the node's protocol and the no-fallback errors."""
+argument checks (made before any HIP call), the node's protocol and the no-fallback errors.  Layouts, constants and names against
+the header are tests/test_cabi_mirror.py's, for the whole C ABI."""
 import ctypes
 import functools
 import os
-import re
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -17,7 +14,6 @@ from lanpaint_amd import _cabi
 from tests import propagate_ref as ref
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NEW_ENTRIES = ("lp_prop_pyramid_ws_bytes", "lp_prop_luma", "lp_prop_key_mask", "lp_prop_match", "lp_prop_fill", "lp_prop_advance")
 ONE = np.float32(1.0).view(np.uint32)
 
 
@@ -233,36 +229,8 @@ def test_propagate_entries_reject_bad_arguments_without_a_device(hip_lib):
         assert hip_lib.lp_prop_advance(C.byref(_cabi.LpPropAdvanceDesc(**{**good, **change})), None) == E, change
 
 
-def test_propagate_descriptor_layouts_and_constants_match_c(tmp_path):
-    structs = (("lp_prop_luma_desc", _cabi.LpPropLumaDesc), ("lp_prop_match_desc", _cabi.LpPropMatchDesc),
-               ("lp_prop_advance_desc", _cabi.LpPropAdvanceDesc))
-    names = ("LP_PROP_BLOCK", "LP_PROP_HALO", "LP_PROP_MIN_PIXELS", "LP_PROP_FILL_ITERS", "LP_PROP_SUBPEL", "LP_PROP_MAX_LEVELS",
-             "LP_PROP_MAX_SEARCH", "LP_PROP_MAX_SMOOTH", "LP_PROP_ALIGN", "LP_PROP_MAX_GRID")
-    prog = ['#include <stdio.h>', '#include <stddef.h>', '#include "lanpaint_hip.h"', "int main(void){"]
-    for cname, py in structs:
-        for f, _ in py._fields_:
-            prog.append(f'printf("%zu ", offsetof({cname}, {f}));')
-        prog.append(f'printf("%zu\\n", sizeof({cname}));')
-    prog.append('printf("' + "%d " * len(names) + '\\n", ' + ", ".join(names) + "); return 0;}")
-    src = tmp_path / "layout.c"
-    src.write_text("\n".join(prog))
-    exe = tmp_path / "layout"
-    subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
-    lines = subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.strip().split("\n")
-    for line, (_, py) in zip(lines, structs):
-        assert [int(v) for v in line.split()] == [getattr(py, f).offset for f, _ in py._fields_] + [ctypes.sizeof(py)]
-    assert [int(v) for v in lines[3].split()] == [getattr(_cabi, n) for n in names] == [8, 4, 16, 3, 16, 6, 7, 64, 16, 2048]
-    assert (ref.BLOCK, ref.HALO, ref.MIN_PIXELS, ref.FILL_ITERS) == (8, 4, 16, 3)
-    assert _cabi.LP_PROP_MAX_GRID == -(-_cabi.LP_VMASK_MAX_SIDE // _cabi.LP_PROP_BLOCK)
-
-
-def test_the_propagate_names_are_everywhere(hip_lib):
+def test_the_propagate_kernels_are_built_and_the_header_says_the_words():
     header = open(os.path.join(ROOT, "include", "lanpaint_hip.h")).read()
-    dynamic = subprocess.run(["nm", "-D", "--defined-only", _cabi.LIB_PATH], capture_output=True, text=True, check=True).stdout
-    for name in NEW_ENTRIES:
-        assert re.search(r"LP_API\s+int(64_t)?\s+%s\s*\(" % name, header), name
-        assert name in _cabi.EXPORTS and hasattr(hip_lib, name)
-        assert re.search(r"\bT %s$" % name, dynamic, flags=re.M), name
     from lanpaint_amd import build
     assert "propagate_kernel.hip" in build.SOURCES and os.path.exists(os.path.join(build.CSRC, "propagate_kernel.hip"))
     for word in ("LP_PROP_MIN_PIXELS", "cost << 12", "inside an int32", "inside 32 bits"):
@@ -302,14 +270,10 @@ def test_propagate_refuses_cpu_tensors_and_bad_arguments():
 
 
 def test_propagate_node_protocol_and_own_mappings():
-    from lanpaint_amd import (detail_nodes, fill_nodes, grain_nodes, multiband_nodes, nodes, propagate_nodes, refine_nodes,
-                              stabilize_nodes, video_nodes)
+    from lanpaint_amd import propagate_nodes
     node = propagate_nodes.LanPaint_VideoMaskPropagate
     assert propagate_nodes.NODE_CLASS_MAPPINGS == {"LanPaint_VideoMaskPropagate": node}
     assert propagate_nodes.NODE_DISPLAY_NAME_MAPPINGS == {"LanPaint_VideoMaskPropagate": "LanPaint Video Mask Propagate"}
-    for other in (nodes, detail_nodes, fill_nodes, multiband_nodes, refine_nodes, stabilize_nodes, grain_nodes, video_nodes):
-        assert not set(propagate_nodes.NODE_CLASS_MAPPINGS) & set(other.NODE_CLASS_MAPPINGS)
-        assert not set(propagate_nodes.NODE_DISPLAY_NAME_MAPPINGS) & set(other.NODE_DISPLAY_NAME_MAPPINGS)
     types = node.INPUT_TYPES()
     req = types["required"]
     assert list(types) == ["required"] and list(req) == ["image", "mask", "key_frame", "levels", "search", "smooth"]
@@ -327,9 +291,3 @@ def test_propagate_node_protocol_and_own_mappings():
     if not torch.cuda.is_available():
         with pytest.raises(RuntimeError, match="no CPU fallback"):
             node().propagate(torch.zeros(4, 16, 16, 3), torch.zeros(16, 16), 0, 4, 2, 8)
-
-
-def test_propagate_modules_have_no_unbound_names():
-    files = [os.path.join(ROOT, "lanpaint_amd", f) for f in ("propagate.py", "propagate_nodes.py")]
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "scripts", "check_names.py"), *files], capture_output=True, text=True)
-    assert p.returncode == 0, p.stdout

@@ -1,14 +1,11 @@
 """The occlusion-aware video mask propagate from several keyframes, the parts that need no device: the restatement
-(tests/propagate_keys_visible_ref.py) checked on its own -- what the rule promises, as bits, an empty key, and the quality conditions
-on a disc that passes behind a bar with a key on either side --, the three C entries' argument checks (made before any HIP call),
-the descriptors' layout against the header as gcc reads it, the names' presence everywhere, the wrapper's refusals, the node's
-protocol, and that the existing propagate nodes are as they were."""
+(tests/propagate_keys_visible_ref.py) checked on its own -- what the rule promises, as bits, an empty key, and the quality
+conditions on a disc that passes behind a bar with a key on either side --, the three C entries' argument checks (made before any
+HIP call), the wrapper's refusals, the node's protocol, and that the existing propagate nodes are as they were.  Layouts,
+constants and names against the header are tests/test_cabi_mirror.py's, for the whole C ABI."""
 import ctypes
 import functools
 import os
-import re
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -22,7 +19,6 @@ from tests import propagate_visible_ref as vref
 from tests.test_propagate_visible_host import _iou, _texture, occluded_disc_clip
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NEW_ENTRIES = ("lp_prop_visible_batch", "lp_prop_occlude_batch", "lp_prop_merge_visible")
 LEVELS, SEARCH, SMOOTH = 3, 2, 8
 
 
@@ -217,36 +213,8 @@ def test_the_batch_entries_and_the_merge_reject_bad_arguments_without_a_device(h
     assert hip_lib.lp_prop_merge_visible(C.byref(_cabi.LpPropMergeVisibleDesc(**too_long)), None) == _cabi.LP_E_UNSUPPORTED
 
 
-def test_keys_visible_descriptor_layouts_and_constants_match_c(tmp_path):
-    structs = (("lp_prop_visible_job", _cabi.LpPropVisibleJob), ("lp_prop_visible_batch_desc", _cabi.LpPropVisibleBatchDesc),
-               ("lp_prop_occlude_job", _cabi.LpPropOccludeJob), ("lp_prop_occlude_batch_desc", _cabi.LpPropOccludeBatchDesc),
-               ("lp_prop_merge_visible_desc", _cabi.LpPropMergeVisibleDesc))
-    prog = ['#include <stdio.h>', '#include <stddef.h>', '#include "lanpaint_hip.h"', "int main(void){"]
-    for cname, py in structs:
-        for f, _ in py._fields_:
-            prog.append(f'printf("%zu ", offsetof({cname}, {f}));')
-        prog.append(f'printf("%zu\\n", sizeof({cname}));')
-    prog.append('printf("%d %d %d\\n", LP_PROP_MAX_JOBS, LP_PROP_MIN_PIXELS, LP_ABI_VERSION); return 0;}')
-    src = tmp_path / "layout.c"
-    src.write_text("\n".join(prog))
-    exe = tmp_path / "layout"
-    subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
-    lines = subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.strip().split("\n")
-    for line, (_, py) in zip(lines, structs):
-        assert [int(v) for v in line.split()] == [getattr(py, f).offset for f, _ in py._fields_] + [ctypes.sizeof(py)]
-    assert [ctypes.sizeof(py) for _, py in structs] == [40, 24, 48, 24, 120]
-    assert [int(v) for v in lines[5].split()] == [_cabi.LP_PROP_MAX_JOBS, _cabi.LP_PROP_MIN_PIXELS, _cabi.ABI_VERSION] == [32, 16, 25]
-
-
-def test_the_keys_visible_names_are_everywhere(hip_lib):
+def test_the_header_says_the_keys_visible_words():
     header = open(os.path.join(ROOT, "include", "lanpaint_hip.h")).read()
-    exports = open(os.path.join(ROOT, "lanpaint_amd", "csrc", "exports.map")).read()
-    dynamic = subprocess.run(["nm", "-D", "--defined-only", _cabi.LIB_PATH], capture_output=True, text=True, check=True).stdout
-    assert re.search(r"global:\s*lp_\*;", exports)                      # the version script exports every lp_* entry
-    for name in NEW_ENTRIES:
-        assert re.search(r"LP_API\s+int\s+%s\s*\(" % name, header), name
-        assert name in _cabi.EXPORTS and hasattr(hip_lib, name)
-        assert re.search(r"\bT %s$" % name, dynamic, flags=re.M), name
     for word in ("exactly one of A, B lost at t", "c_S = (int)(S * 256.0f + 0.5f)", "f = f_A if 2 j <= n, else f_B", "never lost",
                  "c'_S = (c_S * w + 128) >> 8", "Lost is sticky", "one integer atomic add per wave"):
         assert word in header, word
@@ -278,16 +246,11 @@ def test_propagate_keys_visible_refuses_cpu_tensors_and_bad_arguments():
 
 
 def test_keys_visible_node_protocol_and_the_existing_propagate_nodes_are_untouched():
-    from lanpaint_amd import (detail_nodes, fill_nodes, grain_nodes, multiband_nodes, nodes, propagate_keys_nodes, propagate_keys_visible_nodes,
-                              propagate_nodes, propagate_visible_nodes, refine_nodes, stabilize_nodes, video_nodes)
+    from lanpaint_amd import propagate_keys_nodes, propagate_keys_visible_nodes, propagate_nodes, propagate_visible_nodes
     mod, name = propagate_keys_visible_nodes, "LanPaint_VideoMaskPropagateKeysVisible"
     node = mod.LanPaint_VideoMaskPropagateKeysVisible
     assert mod.NODE_CLASS_MAPPINGS == {name: node}
     assert mod.NODE_DISPLAY_NAME_MAPPINGS == {name: "LanPaint Video Mask Propagate (Keys, Visible)"}
-    for other in (nodes, detail_nodes, fill_nodes, multiband_nodes, refine_nodes, stabilize_nodes, grain_nodes, video_nodes,
-                  propagate_nodes, propagate_keys_nodes, propagate_visible_nodes):
-        assert not set(mod.NODE_CLASS_MAPPINGS) & set(other.NODE_CLASS_MAPPINGS)
-        assert not set(mod.NODE_DISPLAY_NAME_MAPPINGS) & set(other.NODE_DISPLAY_NAME_MAPPINGS)
     assert propagate_nodes.NODE_CLASS_MAPPINGS == {"LanPaint_VideoMaskPropagate": propagate_nodes.LanPaint_VideoMaskPropagate}
     assert list(propagate_keys_nodes.NODE_CLASS_MAPPINGS) == ["LanPaint_VideoMaskPropagateKeys"]
     assert list(propagate_visible_nodes.NODE_CLASS_MAPPINGS) == ["LanPaint_VideoMaskPropagateVisible"]
@@ -314,9 +277,3 @@ def test_keys_visible_node_protocol_and_the_existing_propagate_nodes_are_untouch
     if not torch.cuda.is_available():
         with pytest.raises(RuntimeError, match="no CPU fallback"):
             node().propagate(torch.zeros(4, 16, 16, 3), torch.zeros(2, 16, 16), "0 3", 4, 2, 8, 16)
-
-
-def test_propagate_keys_visible_modules_have_no_unbound_names():
-    files = [os.path.join(ROOT, "lanpaint_amd", f) for f in ("propagate_keys_visible.py", "propagate_keys_visible_nodes.py", "propagate_keys.py")]
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "scripts", "check_names.py"), *files], capture_output=True, text=True)
-    assert p.returncode == 0, p.stdout

@@ -1,13 +1,10 @@
-"""The occlusion-aware video mask propagate, the parts that need no device: the restatement (tests/propagate_visible_ref.py)
-checked on its own -- the properties the rule promises, as bits, and the quality conditions on a disc that passes behind a bar --,
-the two C entries' argument checks (made before any HIP call), the descriptors' layout against the header as gcc reads it, the
-names' presence everywhere, the node's protocol, and that the existing propagate modules are as they were."""
+"""The occlusion-aware video mask propagate, the parts that need no device: the restatement (tests/propagate_visible_ref.py) checked
+on its own -- the properties the rule promises, as bits, and the quality conditions on a disc that passes behind a bar --, the two
+C entries' argument checks (made before any HIP call), the node's protocol, and that the existing propagate modules are as they
+were.  Layouts, constants and names against the header are tests/test_cabi_mirror.py's, for the whole C ABI."""
 import ctypes
 import functools
 import os
-import re
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -18,7 +15,6 @@ from tests import propagate_ref as ref
 from tests import propagate_visible_ref as vref
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NEW_ENTRIES = ("lp_prop_visible", "lp_prop_occlude")
 DEFAULT_OCCLUSION = 16
 
 
@@ -224,34 +220,8 @@ def test_visible_and_occlude_reject_bad_arguments_without_a_device(hip_lib):
         assert hip_lib.lp_prop_occlude(C.byref(_cabi.LpPropOccludeDesc(**{**good, **change})), None) == E, change
 
 
-def test_visible_descriptor_layouts_and_constants_match_c(tmp_path):
-    structs = (("lp_prop_visible_desc", _cabi.LpPropVisibleDesc), ("lp_prop_occlude_desc", _cabi.LpPropOccludeDesc))
-    prog = ['#include <stdio.h>', '#include <stddef.h>', '#include "lanpaint_hip.h"', "int main(void){"]
-    for cname, py in structs:
-        for f, _ in py._fields_:
-            prog.append(f'printf("%zu ", offsetof({cname}, {f}));')
-        prog.append(f'printf("%zu\\n", sizeof({cname}));')
-    prog.append('printf("%d %d\\n", LP_PROP_VIS_MAX_BIAS, LP_ABI_VERSION); return 0;}')
-    src = tmp_path / "layout.c"
-    src.write_text("\n".join(prog))
-    exe = tmp_path / "layout"
-    subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
-    lines = subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.strip().split("\n")
-    for line, (_, py) in zip(lines, structs):
-        assert [int(v) for v in line.split()] == [getattr(py, f).offset for f, _ in py._fields_] + [ctypes.sizeof(py)]
-    assert ctypes.sizeof(_cabi.LpPropVisibleDesc) == 56 and ctypes.sizeof(_cabi.LpPropOccludeDesc) == 56
-    assert [int(v) for v in lines[2].split()] == [_cabi.LP_PROP_VIS_MAX_BIAS, _cabi.ABI_VERSION] == [32, 25]
-
-
-def test_the_visible_names_are_everywhere(hip_lib):
+def test_the_header_says_the_visible_words():
     header = open(os.path.join(ROOT, "include", "lanpaint_hip.h")).read()
-    exports = open(os.path.join(ROOT, "lanpaint_amd", "csrc", "exports.map")).read()
-    dynamic = subprocess.run(["nm", "-D", "--defined-only", _cabi.LIB_PATH], capture_output=True, text=True, check=True).stdout
-    assert re.search(r"global:\s*lp_\*;", exports)                      # the version script exports every lp_* entry
-    for name in NEW_ENTRIES:
-        assert re.search(r"LP_API\s+int\s+%s\s*\(" % name, header), name
-        assert name in _cabi.EXPORTS and hasattr(hip_lib, name)
-        assert re.search(r"\bT %s$" % name, dynamic, flags=re.M), name
     for word in ("LP_PROP_VIS_MAX_BIAS", "floor((2 D + n) / (2 n))", "R > occlusion * n", "c' = (c * w + 128) >> 8",
                  "hidden entirely", "Not handled: occlusion."):
         assert word in header, word
@@ -277,15 +247,10 @@ def test_propagate_visible_refuses_cpu_tensors_and_bad_arguments():
 
 
 def test_visible_node_protocol_and_the_existing_propagate_nodes_are_untouched():
-    from lanpaint_amd import (detail_nodes, fill_nodes, grain_nodes, multiband_nodes, nodes, propagate_keys_nodes, propagate_nodes,
-                              propagate_visible_nodes, refine_nodes, stabilize_nodes, video_nodes)
+    from lanpaint_amd import propagate_keys_nodes, propagate_nodes, propagate_visible_nodes
     node = propagate_visible_nodes.LanPaint_VideoMaskPropagateVisible
     assert propagate_visible_nodes.NODE_CLASS_MAPPINGS == {"LanPaint_VideoMaskPropagateVisible": node}
     assert propagate_visible_nodes.NODE_DISPLAY_NAME_MAPPINGS == {"LanPaint_VideoMaskPropagateVisible": "LanPaint Video Mask Propagate (Visible)"}
-    for other in (nodes, detail_nodes, fill_nodes, multiband_nodes, refine_nodes, stabilize_nodes, grain_nodes, video_nodes,
-                  propagate_nodes, propagate_keys_nodes):
-        assert not set(propagate_visible_nodes.NODE_CLASS_MAPPINGS) & set(other.NODE_CLASS_MAPPINGS)
-        assert not set(propagate_visible_nodes.NODE_DISPLAY_NAME_MAPPINGS) & set(other.NODE_DISPLAY_NAME_MAPPINGS)
     assert propagate_nodes.NODE_CLASS_MAPPINGS == {"LanPaint_VideoMaskPropagate": propagate_nodes.LanPaint_VideoMaskPropagate}
     assert list(propagate_keys_nodes.NODE_CLASS_MAPPINGS) == ["LanPaint_VideoMaskPropagateKeys"]
     assert "occlusion is not handled" in propagate_nodes.LanPaint_VideoMaskPropagate.DESCRIPTION
@@ -308,9 +273,3 @@ def test_visible_node_protocol_and_the_existing_propagate_nodes_are_untouched():
     if not torch.cuda.is_available():
         with pytest.raises(RuntimeError, match="no CPU fallback"):
             node().propagate(torch.zeros(4, 16, 16, 3), torch.zeros(16, 16), 0, 4, 2, 8, 16)
-
-
-def test_propagate_visible_modules_have_no_unbound_names():
-    files = [os.path.join(ROOT, "lanpaint_amd", f) for f in ("propagate_visible.py", "propagate_visible_nodes.py")]
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "scripts", "check_names.py"), *files], capture_output=True, text=True)
-    assert p.returncode == 0, p.stdout

@@ -1,12 +1,9 @@
 """The mask refine, the parts that need no device: the restatement (tests/refine_ref.py) checked on its own -- the properties the
 rule promises, as bits, the edge snap it exists for, grow_mask's rule against a brute-force disc --, the two C entries' argument
-checks (made before any HIP call), the descriptor's layout against the header as gcc reads it, lp_refine_ws_bytes against its
-Python mirror, the names' presence everywhere, the node's protocol and the no-fallback errors."""
+checks (made before any HIP call), lp_refine_ws_bytes against its Python mirror, the node's protocol and the no-fallback errors.
+Layouts, constants and names against the header are tests/test_cabi_mirror.py's, for the whole C ABI."""
 import ctypes
 import os
-import re
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -15,8 +12,6 @@ import torch
 from lanpaint_amd import _cabi, refine
 from tests import refine_ref as ref
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NEW_ENTRIES = ("lp_mask_refine", "lp_refine_ws_bytes")
 SHAPES = [(1, 1), (1, 7), (7, 1), (5, 9), (33, 65), (40, 70)]
 RADII = (1, 3, 8, 64)
 
@@ -222,37 +217,7 @@ def test_refine_ws_bytes_equals_its_mirror(hip_lib):
     assert hip_lib.lp_refine_ws_bytes(65536, 8, 8, 3, 8) == U
 
 
-def test_refine_descriptor_layout_matches_c(tmp_path):
-    py = _cabi.LpRefineDesc
-    prog = ['#include <stdio.h>', '#include <stddef.h>', '#include "lanpaint_hip.h"', "int main(void){"]
-    for f, _ in py._fields_:
-        prog.append(f'printf("%zu ", offsetof(lp_refine_desc, {f}));')
-    prog.append('printf("%zu\\n", sizeof(lp_refine_desc));')
-    prog.append('printf("%d %d\\n", LP_ABI_VERSION, LP_REFINE_MAX_RADIUS); return 0;}')
-    src = tmp_path / "layout.c"
-    src.write_text("\n".join(prog))
-    exe = tmp_path / "layout"
-    subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
-    lines = subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.strip().split("\n")
-    assert [int(v) for v in lines[0].split()] == [getattr(py, f).offset for f, _ in py._fields_] + [ctypes.sizeof(py)]
-    assert [f for f, _ in py._fields_] == ["batch", "height", "width", "channels", "mask_batch", "radius", "eps", "guide", "mask",
-                                           "out", "ws", "ws_bytes"]
-    assert [int(v) for v in lines[1].split()] == [25, _cabi.LP_REFINE_MAX_RADIUS] and _cabi.LP_REFINE_MAX_RADIUS == 64
-
-
-def test_abi_version_is_unchanged_and_the_refine_names_are_everywhere(hip_lib):
-    assert _cabi.ABI_VERSION == 25 and hip_lib.lp_abi_version() == 25
-    header = open(os.path.join(ROOT, "include", "lanpaint_hip.h")).read()
-    assert re.search(r"#define\s+LP_ABI_VERSION\s+25\b", header)
-    assert re.search(r"#define\s+LP_REFINE_MAX_RADIUS\s+64\b", header)
-    # the version script exports every lp_* name: the library's dynamic table is where a name shows
-    script = open(os.path.join(ROOT, "lanpaint_amd", "csrc", "exports.map")).read()
-    assert re.search(r"global:\s*lp_\*;", script)
-    dynamic = subprocess.run(["nm", "-D", "--defined-only", _cabi.LIB_PATH], capture_output=True, text=True, check=True).stdout
-    for name in NEW_ENTRIES:
-        assert re.search(r"LP_API\s+(int|int64_t)\s+%s\s*\(" % name, header), name
-        assert name in _cabi.EXPORTS and hasattr(hip_lib, name)
-        assert re.search(r"\bT %s$" % name, dynamic, flags=re.M), name
+def test_the_refine_kernels_are_a_source_of_the_build():
     from lanpaint_amd import build
     assert "refine_kernel.hip" in build.SOURCES and os.path.exists(os.path.join(build.CSRC, "refine_kernel.hip"))
 
@@ -271,15 +236,10 @@ def test_refine_refuses_cpu_tensors():
 
 
 def test_refine_node_protocol_and_own_mappings():
-    from lanpaint_amd import (detail_color_nodes, detail_nodes, detail_region_nodes, detail_subject_nodes, detail_track_nodes,
-                              fill_nodes, multiband_nodes, nodes, refine_nodes)
+    from lanpaint_amd import refine_nodes
     node = refine_nodes.LanPaint_MaskRefine
     assert refine_nodes.NODE_CLASS_MAPPINGS == {"LanPaint_MaskRefine": node}
     assert refine_nodes.NODE_DISPLAY_NAME_MAPPINGS == {"LanPaint_MaskRefine": "LanPaint Mask Refine"}
-    for other in (nodes, detail_nodes, detail_region_nodes, detail_track_nodes, detail_subject_nodes, detail_color_nodes, fill_nodes,
-                  multiband_nodes):
-        assert not set(refine_nodes.NODE_CLASS_MAPPINGS) & set(other.NODE_CLASS_MAPPINGS)
-        assert not set(refine_nodes.NODE_DISPLAY_NAME_MAPPINGS) & set(other.NODE_DISPLAY_NAME_MAPPINGS)
     types = node.INPUT_TYPES()
     req = types["required"]
     assert list(types) == ["required"] and list(req) == ["image", "mask", "grow", "radius", "eps"]
@@ -295,9 +255,3 @@ def test_refine_node_protocol_and_own_mappings():
     if not torch.cuda.is_available():
         with pytest.raises(RuntimeError, match="no CPU fallback"):
             node().refine(torch.zeros(2, 16, 16, 3), torch.zeros(2, 16, 16), 0, 8, 1e-3)
-
-
-def test_refine_modules_have_no_unbound_names():
-    files = [os.path.join(ROOT, "lanpaint_amd", f) for f in ("refine.py", "refine_nodes.py")]
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "scripts", "check_names.py"), *files], capture_output=True, text=True)
-    assert p.returncode == 0, p.stdout

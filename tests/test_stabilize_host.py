@@ -1,13 +1,10 @@
 """The video mask stabilize, the parts that need no device: the restatement (tests/stabilize_ref.py) checked on its own -- its
 distances against scipy, the properties the rule promises, as bits, and the flicker it exists to remove --, the two C entries'
-argument checks (made before any HIP call), the descriptor's layout against the header as gcc reads it, the names' presence
-everywhere, the node's protocol and the no-fallback errors."""
+argument checks (made before any HIP call), the node's protocol and the no-fallback errors.  Layouts, constants and names against
+the header are tests/test_cabi_mirror.py's, for the whole C ABI."""
 import ctypes
 import functools
 import os
-import re
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -16,8 +13,6 @@ import torch
 from lanpaint_amd import _cabi, stabilize
 from tests import stabilize_ref as ref
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NEW_ENTRIES = ("lp_mask_signed_d2", "lp_mask_stabilize")
 ONE = np.float32(1.0).view(np.uint32)
 
 
@@ -184,35 +179,7 @@ def test_stabilize_entries_reject_bad_arguments_without_a_device(hip_lib):
     assert hip_lib.lp_mask_stabilize(C.byref(M(**{**good, "frames": (1 << 30) + 1})), None) == _cabi.LP_E_UNSUPPORTED
 
 
-def test_stabilize_descriptor_layout_and_constants_match_c(tmp_path):
-    py = _cabi.LpStabilizeDesc
-    prog = ['#include <stdio.h>', '#include <stddef.h>', '#include "lanpaint_hip.h"', "int main(void){"]
-    for f, _ in py._fields_:
-        prog.append(f'printf("%zu ", offsetof(lp_stabilize_desc, {f}));')
-    prog.append('printf("%zu\\n", sizeof(lp_stabilize_desc));')
-    prog.append('printf("%d %d %d %d %d %d %d %.1f\\n", LP_ABI_VERSION, LP_STAB_Q_FAR, LP_STAB_MAX_MEDIAN, LP_STAB_MAX_SMOOTH, '
-                'LP_STAB_MAX_GROW, LP_STAB_MAX_FEATHER, LP_STAB_SEG_FRAMES, LP_STAB_SD_CAP); return 0;}')
-    src = tmp_path / "layout.c"
-    src.write_text("\n".join(prog))
-    exe = tmp_path / "layout"
-    subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
-    lines = subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.strip().split("\n")
-    assert [int(v) for v in lines[0].split()] == [getattr(py, f).offset for f, _ in py._fields_] + [ctypes.sizeof(py)]
-    assert [f for f, _ in py._fields_] == ["frames", "height", "width", "median_radius", "smooth_radius", "reserved0", "grow",
-                                           "feather", "q", "out"]
-    assert [float(v) for v in lines[1].split()] == [_cabi.ABI_VERSION, _cabi.LP_STAB_Q_FAR, _cabi.LP_STAB_MAX_MEDIAN,
-                                                    _cabi.LP_STAB_MAX_SMOOTH, _cabi.LP_STAB_MAX_GROW, _cabi.LP_STAB_MAX_FEATHER,
-                                                    _cabi.LP_STAB_SEG_FRAMES, _cabi.LP_STAB_SD_CAP]
-    assert (_cabi.LP_STAB_MAX_MEDIAN, _cabi.LP_STAB_MAX_SMOOTH, _cabi.LP_STAB_MAX_GROW, _cabi.LP_STAB_MAX_FEATHER) == (3, 8, 256, 64)
-
-
-def test_the_stabilize_names_are_everywhere(hip_lib):
-    header = open(os.path.join(ROOT, "include", "lanpaint_hip.h")).read()
-    dynamic = subprocess.run(["nm", "-D", "--defined-only", _cabi.LIB_PATH], capture_output=True, text=True, check=True).stdout
-    for name in NEW_ENTRIES:
-        assert re.search(r"LP_API\s+int\s+%s\s*\(" % name, header), name
-        assert name in _cabi.EXPORTS and hasattr(hip_lib, name)
-        assert re.search(r"\bT %s$" % name, dynamic, flags=re.M), name
+def test_the_stabilize_kernels_are_a_source_of_the_build():
     from lanpaint_amd import build
     assert "stabilize_kernel.hip" in build.SOURCES and os.path.exists(os.path.join(build.CSRC, "stabilize_kernel.hip"))
 
@@ -240,15 +207,10 @@ def test_stabilize_refuses_cpu_tensors_and_bad_arguments():
 
 
 def test_stabilize_node_protocol_and_own_mappings():
-    from lanpaint_amd import (detail_color_nodes, detail_nodes, detail_region_nodes, detail_subject_nodes, detail_track_nodes,
-                              fill_nodes, multiband_nodes, nodes, refine_nodes, stabilize_nodes)
+    from lanpaint_amd import stabilize_nodes
     node = stabilize_nodes.LanPaint_VideoMaskStabilize
     assert stabilize_nodes.NODE_CLASS_MAPPINGS == {"LanPaint_VideoMaskStabilize": node}
     assert stabilize_nodes.NODE_DISPLAY_NAME_MAPPINGS == {"LanPaint_VideoMaskStabilize": "LanPaint Video Mask Stabilize"}
-    for other in (nodes, detail_nodes, detail_region_nodes, detail_track_nodes, detail_subject_nodes, detail_color_nodes, fill_nodes,
-                  multiband_nodes, refine_nodes):
-        assert not set(stabilize_nodes.NODE_CLASS_MAPPINGS) & set(other.NODE_CLASS_MAPPINGS)
-        assert not set(stabilize_nodes.NODE_DISPLAY_NAME_MAPPINGS) & set(other.NODE_DISPLAY_NAME_MAPPINGS)
     types = node.INPUT_TYPES()
     req = types["required"]
     assert list(types) == ["required"] and list(req) == ["mask", "median_radius", "smooth_radius", "grow", "feather"]
@@ -267,9 +229,3 @@ def test_stabilize_node_protocol_and_own_mappings():
     if not torch.cuda.is_available():
         with pytest.raises(RuntimeError, match="no CPU fallback"):
             node().stabilize(torch.zeros(4, 16, 16), 1, 2, 0.0, 0.0)
-
-
-def test_stabilize_modules_have_no_unbound_names():
-    files = [os.path.join(ROOT, "lanpaint_amd", f) for f in ("stabilize.py", "stabilize_nodes.py")]
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "scripts", "check_names.py"), *files], capture_output=True, text=True)
-    assert p.returncode == 0, p.stdout

@@ -1,14 +1,11 @@
 """The checked video temporal fill, the parts that need no device: what the rule promises, on the two restatements
 (tests/temporal_fill_ref.py, tests/temporal_fill_checked_ref.py), as bits and counts; that the case of the device's stage test
-reaches every branch of the rule; the C entry's argument checks (made before any HIP call), the descriptor's layout against the
-header as gcc reads it, the names' presence everywhere, the wrappers' argument checks, the node's protocol and the no-fallback
-errors."""
+reaches every branch of the rule; the C entry's argument checks (made before any HIP call), the wrappers' argument checks, the
+node's protocol and the no-fallback errors.  Layouts, constants and names against the header are tests/test_cabi_mirror.py's, for
+the whole C ABI."""
 import ctypes
 import functools
 import os
-import re
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -22,7 +19,6 @@ from tests.test_gpu_propagate import _rng, _video, _wild_video
 from tests.test_temporal_fill_host import pan_clip, still_clip
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-ENTRY = "lp_tfill_carry_pair"
 F = 5                                                                  # the stage case: frame 2 of 5, its donor frame 3
 
 
@@ -266,29 +262,8 @@ def test_entry_rejects_bad_arguments_without_a_device(hip_lib):
     assert call(frames=65536) == U
 
 
-def test_descriptor_layout_and_constants_match_c(tmp_path):
-    py = _cabi.LpTfillCarryPairDesc
-    prog = ['#include <stdio.h>', '#include <stddef.h>', '#include "lanpaint_hip.h"', "int main(void){"]
-    prog += [f'printf("%zu ", offsetof(lp_tfill_carry_pair_desc, {f}));' for f, _ in py._fields_]
-    prog.append('printf("%zu\\n", sizeof(lp_tfill_carry_pair_desc));')
-    prog.append('printf("%d %d %d %d %d\\n", LP_TFILL_DISPUTED, LP_PROP_VIS_MAX_BIAS, LP_PROP_MIN_PIXELS, LP_PROP_BLOCK, LP_ABI_VERSION);'
-                ' return 0;}')
-    src, exe = tmp_path / "layout.c", tmp_path / "layout"
-    src.write_text("\n".join(prog))
-    subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
-    lines = subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.strip().split("\n")
-    assert [int(v) for v in lines[0].split()] == [getattr(py, f).offset for f, _ in py._fields_] + [ctypes.sizeof(py)]
-    assert [int(v) for v in lines[1].split()] == [_cabi.LP_TFILL_DISPUTED, _cabi.LP_PROP_VIS_MAX_BIAS, _cabi.LP_PROP_MIN_PIXELS,
-                                                  _cabi.LP_PROP_BLOCK, _cabi.ABI_VERSION]
-    assert [cref.DISPUTED, cref.MAX_BIAS, cref.MIN_PIXELS, cref.BLOCK] == [int(v) for v in lines[1].split()][:4]
-
-
-def test_the_name_is_everywhere_and_the_abi_version_stays(hip_lib):
+def test_the_header_says_the_checked_fill_words():
     header = open(os.path.join(ROOT, "include", "lanpaint_hip.h")).read()
-    dynamic = subprocess.run(["nm", "-D", "--defined-only", _cabi.LIB_PATH], capture_output=True, text=True, check=True).stdout
-    assert re.search(r"LP_API\s+int\s+%s\s*\(" % ENTRY, header)
-    assert ENTRY in _cabi.EXPORTS and hasattr(hip_lib, ENTRY) and re.search(r"\bT %s$" % ENTRY, dynamic, flags=re.M)
-    assert _cabi.ABI_VERSION == 25 and hip_lib.lp_abi_version() == 25
     for word in ("Checked temporal fill", "a dispute never alters", "mu = floor((2 D + n) / (2 n))", "R > agree * n", "source = -2",
                  "witnesses = 2 when n >= LP_PROP_MIN_PIXELS", "wherever source != -2", "Frame F - 1 has no backward step"):
         assert word in header, word
@@ -319,22 +294,10 @@ def test_the_wrappers_refuse_cpu_tensors_and_bad_arguments():
 
 
 def test_node_protocol_and_own_mappings():
-    import importlib
-    import pkgutil
-
-    import lanpaint_amd
     from lanpaint_amd import temporal_fill_checked_nodes as mod, temporal_fill_nodes
     node = mod.LanPaint_VideoTemporalFillChecked
     assert mod.NODE_CLASS_MAPPINGS == {"LanPaint_VideoTemporalFillChecked": node}
     assert list(mod.NODE_DISPLAY_NAME_MAPPINGS) == ["LanPaint_VideoTemporalFillChecked"]
-    others = [m.name for m in pkgutil.iter_modules(lanpaint_amd.__path__) if m.name.endswith("nodes") and m.name != "temporal_fill_checked_nodes"]
-    assert len(others) >= 13 and "temporal_fill_nodes" in others
-    for name in others:                                                # every other node module of the package
-        other = importlib.import_module("lanpaint_amd." + name)
-        if not hasattr(other, "NODE_CLASS_MAPPINGS"):                  # a module of parts that others assemble
-            continue
-        assert not set(mod.NODE_CLASS_MAPPINGS) & set(other.NODE_CLASS_MAPPINGS), name
-        assert not set(mod.NODE_DISPLAY_NAME_MAPPINGS.values()) & set(other.NODE_DISPLAY_NAME_MAPPINGS.values()), name
     types = node.INPUT_TYPES()
     req, plain = types["required"], temporal_fill_nodes.LanPaint_VideoTemporalFill.INPUT_TYPES()["required"]
     assert list(types) == ["required"] and list(req) == list(plain) + ["agree"] and all(req[k] == plain[k] for k in plain)
@@ -348,9 +311,3 @@ def test_node_protocol_and_own_mappings():
     if not torch.cuda.is_available():
         with pytest.raises(RuntimeError, match="no CPU fallback"):
             node().fill(torch.zeros(3, 16, 16, 3), torch.zeros(3, 16, 16))
-
-
-def test_modules_have_no_unbound_names():
-    files = [os.path.join(ROOT, "lanpaint_amd", f) for f in ("temporal_fill_checked.py", "temporal_fill_checked_nodes.py")]
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "scripts", "check_names.py"), *files], capture_output=True, text=True)
-    assert p.returncode == 0, p.stdout

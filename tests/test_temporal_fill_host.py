@@ -1,13 +1,10 @@
 """The video temporal fill, the parts that need no device: the properties the rule promises on the restatement
-(tests/temporal_fill_ref.py) as bits and counts, the C entries' argument checks (made before any HIP call), the descriptors'
-layout against the header as gcc reads it, the names' presence everywhere, the wrappers' argument checks, the node's protocol and
-the no-fallback errors."""
+(tests/temporal_fill_ref.py) as bits and counts, the C entries' argument checks (made before any HIP call), the wrappers' argument
+checks, the node's protocol and the no-fallback errors.  Layouts, constants and names against the header are
+tests/test_cabi_mirror.py's, for the whole C ABI."""
 import ctypes
 import functools
 import os
-import re
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -18,7 +15,6 @@ from tests import propagate_ref as ref
 from tests import temporal_fill_ref as tref
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NEW_ENTRIES = ("lp_tfill_known", "lp_tfill_carry")
 
 
 def _bits(a):
@@ -168,34 +164,8 @@ def test_entries_reject_bad_arguments_without_a_device(hip_lib):
     assert hip_lib.lp_tfill_carry(C.byref(_cabi.LpTfillCarryDesc(**{**good, "frames": 65536})), None) == U
 
 
-def test_descriptor_layouts_and_constants_match_c(tmp_path):
-    structs = (("lp_tfill_known_desc", _cabi.LpTfillKnownDesc), ("lp_tfill_carry_desc", _cabi.LpTfillCarryDesc))
-    prog = ['#include <stdio.h>', '#include <stddef.h>', '#include "lanpaint_hip.h"', "int main(void){"]
-    for cname, py in structs:
-        for f, _ in py._fields_:
-            prog.append(f'printf("%zu ", offsetof({cname}, {f}));')
-        prog.append(f'printf("%zu\\n", sizeof({cname}));')
-    prog.append('printf("%d %d\\n", LP_TFILL_MAX_REACH, LP_ABI_VERSION); return 0;}')
-    src = tmp_path / "layout.c"
-    src.write_text("\n".join(prog))
-    exe = tmp_path / "layout"
-    subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
-    lines = subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.strip().split("\n")
-    for line, (_, py) in zip(lines, structs):
-        assert [int(v) for v in line.split()] == [getattr(py, f).offset for f, _ in py._fields_] + [ctypes.sizeof(py)]
-    assert [int(v) for v in lines[-1].split()] == [_cabi.LP_TFILL_MAX_REACH, _cabi.ABI_VERSION]
-
-
-def test_the_names_are_everywhere_and_the_abi_version_stays(hip_lib):
+def test_the_header_says_the_temporal_fill_words():
     header = open(os.path.join(ROOT, "include", "lanpaint_hip.h")).read()
-    dynamic = subprocess.run(["nm", "-D", "--defined-only", _cabi.LIB_PATH], capture_output=True, text=True, check=True).stdout
-    exports = open(os.path.join(ROOT, "lanpaint_amd", "csrc", "exports.map")).read()
-    assert re.search(r"global:\s*lp_\*;", exports)                     # every lp_* entry, these two among them
-    for name in NEW_ENTRIES:
-        assert re.search(r"LP_API\s+int\s+%s\s*\(" % name, header), name
-        assert name in _cabi.EXPORTS and hasattr(hip_lib, name)
-        assert re.search(r"\bT %s$" % name, dynamic, flags=re.M), name
-    assert _cabi.ABI_VERSION == 25 and hip_lib.lp_abi_version() == 25
     for word in ("LP_TFILL_MAX_REACH", "a tie stays with the past", "A tap with weight 0 is not read", "no FMA", "known = 1 - m",
                  "r = q - 16 i", "for every chunking"):
         assert word in header, word
@@ -236,16 +206,10 @@ def test_temporal_fill_refuses_cpu_tensors_and_bad_arguments():
 
 
 def test_node_protocol_and_own_mappings():
-    from lanpaint_amd import (detail_nodes, fill_nodes, grain_nodes, multiband_nodes, nodes, propagate_keys_nodes,
-                              propagate_keys_visible_nodes, propagate_nodes, propagate_visible_nodes, refine_nodes, stabilize_nodes,
-                              temporal_fill_nodes, video_nodes)
+    from lanpaint_amd import temporal_fill_nodes
     node = temporal_fill_nodes.LanPaint_VideoTemporalFill
     assert temporal_fill_nodes.NODE_CLASS_MAPPINGS == {"LanPaint_VideoTemporalFill": node}
     assert list(temporal_fill_nodes.NODE_DISPLAY_NAME_MAPPINGS) == ["LanPaint_VideoTemporalFill"]
-    for other in (nodes, detail_nodes, fill_nodes, multiband_nodes, refine_nodes, stabilize_nodes, grain_nodes, video_nodes,
-                  propagate_nodes, propagate_keys_nodes, propagate_visible_nodes, propagate_keys_visible_nodes):
-        assert not set(temporal_fill_nodes.NODE_CLASS_MAPPINGS) & set(other.NODE_CLASS_MAPPINGS)
-        assert not set(temporal_fill_nodes.NODE_DISPLAY_NAME_MAPPINGS.values()) & set(other.NODE_DISPLAY_NAME_MAPPINGS.values())
     types = node.INPUT_TYPES()
     req = types["required"]
     assert list(types) == ["required"] and list(req) == ["image", "mask", "levels", "search", "smooth", "reach"]
@@ -263,9 +227,3 @@ def test_node_protocol_and_own_mappings():
     if not torch.cuda.is_available():
         with pytest.raises(RuntimeError, match="no CPU fallback"):
             node().fill(torch.zeros(3, 16, 16, 3), torch.zeros(3, 16, 16))
-
-
-def test_modules_have_no_unbound_names():
-    files = [os.path.join(ROOT, "lanpaint_amd", f) for f in ("temporal_fill.py", "temporal_fill_nodes.py")]
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "scripts", "check_names.py"), *files], capture_output=True, text=True)
-    assert p.returncode == 0, p.stdout

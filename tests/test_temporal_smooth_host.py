@@ -1,13 +1,11 @@
 """The video temporal smooth, the parts that need no device: the properties the rule promises on the restatement
-(tests/temporal_smooth_ref.py) as bits and counts, the C entry's argument checks (made before any HIP call), the descriptor's
-layout against the header as gcc reads it, the names' presence everywhere, the wrappers' argument checks, the node's protocol and
-the no-fallback errors."""
+(tests/temporal_smooth_ref.py) as bits and counts, the C entry's argument checks (made before any HIP call), the wrappers'
+argument checks, the node's protocol and the no-fallback errors.  Layouts, constants and names against the header are
+tests/test_cabi_mirror.py's, for the whole C ABI."""
 import ctypes
 import functools
 import os
 import re
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -222,31 +220,9 @@ def test_entry_rejects_bad_arguments_without_a_device(hip_lib):
     assert call(frames=65536) == U
 
 
-def test_descriptor_layout_and_constants_match_c(tmp_path):
-    py = _cabi.LpTsmoothDesc
-    prog = ['#include <stdio.h>', '#include <stddef.h>', '#include "lanpaint_hip.h"', "int main(void){"]
-    for f, _ in py._fields_:
-        prog.append(f'printf("%zu ", offsetof(lp_tsmooth_desc, {f}));')
-    prog.append('printf("%zu\\n", sizeof(lp_tsmooth_desc));')
-    prog.append('printf("%d %d\\n", LP_TSMOOTH_MAX_RADIUS, LP_ABI_VERSION); return 0;}')
-    src = tmp_path / "layout.c"
-    src.write_text("\n".join(prog))
-    exe = tmp_path / "layout"
-    subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
-    lines = subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.strip().split("\n")
-    assert [int(v) for v in lines[0].split()] == [getattr(py, f).offset for f, _ in py._fields_] + [ctypes.sizeof(py)]
-    assert [int(v) for v in lines[1].split()] == [_cabi.LP_TSMOOTH_MAX_RADIUS, _cabi.ABI_VERSION]
-
-
-def test_the_names_are_everywhere_and_the_abi_version_stays(hip_lib):
+def test_the_header_and_the_documents_say_the_smooth_words():
     read = lambda *path: open(os.path.join(ROOT, *path)).read()       # noqa: E731
     header = read("include", "lanpaint_hip.h")
-    dynamic = subprocess.run(["nm", "-D", "--defined-only", _cabi.LIB_PATH], capture_output=True, text=True, check=True).stdout
-    assert re.search(r"global:\s*lp_\*;", read("lanpaint_amd", "csrc", "exports.map"))     # every lp_* entry, this one among them
-    assert re.search(r"LP_API\s+int\s+lp_tsmooth\s*\(", header)
-    assert "lp_tsmooth" in _cabi.EXPORTS and hasattr(hip_lib, "lp_tsmooth")
-    assert re.search(r"\bT lp_tsmooth$", dynamic, flags=re.M)
-    assert _cabi.ABI_VERSION == 25 and hip_lib.lp_abi_version() == 25
     assert "temporal_smooth_kernel.hip" in read("lanpaint_amd", "build.py")
     for word in ("LP_TSMOOTH_MAX_RADIUS", "w_k = C(2R, R + k)", "keeps x bit for bit", "a tap with weight 0 is not", "no FMA",
                  "an accepted NaN sample makes that pixel NaN", "for every chunking", "a single outlier frame", "support = -1"):
@@ -286,17 +262,10 @@ def test_temporal_smooth_refuses_cpu_tensors_and_bad_arguments():
 
 
 def test_node_protocol_and_own_mappings():
-    from lanpaint_amd import (detail_nodes, fill_nodes, grain_nodes, multiband_nodes, nodes, propagate_keys_nodes,
-                              propagate_keys_visible_nodes, propagate_nodes, propagate_visible_nodes, refine_nodes, stabilize_nodes,
-                              temporal_fill_checked_nodes, temporal_fill_nodes, temporal_smooth_nodes, video_nodes)
+    from lanpaint_amd import temporal_smooth_nodes
     node = temporal_smooth_nodes.LanPaint_VideoTemporalSmooth
     assert temporal_smooth_nodes.NODE_CLASS_MAPPINGS == {"LanPaint_VideoTemporalSmooth": node}
     assert list(temporal_smooth_nodes.NODE_DISPLAY_NAME_MAPPINGS) == ["LanPaint_VideoTemporalSmooth"]
-    for other in (nodes, detail_nodes, fill_nodes, multiband_nodes, refine_nodes, stabilize_nodes, grain_nodes, video_nodes,
-                  propagate_nodes, propagate_keys_nodes, propagate_visible_nodes, propagate_keys_visible_nodes, temporal_fill_nodes,
-                  temporal_fill_checked_nodes):
-        assert not set(temporal_smooth_nodes.NODE_CLASS_MAPPINGS) & set(other.NODE_CLASS_MAPPINGS)
-        assert not set(temporal_smooth_nodes.NODE_DISPLAY_NAME_MAPPINGS.values()) & set(other.NODE_DISPLAY_NAME_MAPPINGS.values())
     types = node.INPUT_TYPES()
     req = types["required"]
     assert list(types) == ["required"]
@@ -317,9 +286,3 @@ def test_node_protocol_and_own_mappings():
     if not torch.cuda.is_available():
         with pytest.raises(RuntimeError, match="no CPU fallback"):
             node().smooth(torch.zeros(3, 16, 16, 3), torch.zeros(3, 16, 16))
-
-
-def test_modules_have_no_unbound_names():
-    files = [os.path.join(ROOT, "lanpaint_amd", f) for f in ("temporal_smooth.py", "temporal_smooth_nodes.py")]
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "scripts", "check_names.py"), *files], capture_output=True, text=True)
-    assert p.returncode == 0, p.stdout
