@@ -1142,6 +1142,78 @@ LP_API int lp_mask_fill(const lp_fill_desc* desc, void* stream);
  * refuses.                                                                                                                   */
 LP_API int64_t lp_fill_ws_bytes(int32_t batch, int32_t height, int32_t width, int32_t channels);
 
+/* ---- lp_mask_fill, the patch form: reserved0 = LP_FILL_PATCH(r, levels, iters, seed) ------------------------------------------------
+ * reserved0 == 0 is the push-pull fill above, unchanged.  The patch form first makes that fill and then replaces it, under the
+ * mask, by texture copied from the known part of the same image (a PatchMatch search and vote over a pyramid of 8-bit codes).
+ * Every image on its own; integers throughout except the pre-fill and the final division; the same bits on every run and for
+ * every split of a batch.  (csrc/patch_fill_kernel.hip.)
+ *
+ * Mode word: bit 0 = 1; bits 4..7 r, the patch radius (P = 2 r + 1), 1..LP_FILL_PATCH_MAX_RADIUS; bits 8..11 levels,
+ * 1..LP_FILL_PATCH_MAX_LEVELS; bits 12..15 iters, 1..LP_FILL_PATCH_MAX_ITERS; bits 16..31 seed, 0..65535; bits 1..3 zero.
+ * LP_E_INVALID: bit 0 clear with another bit set, bits 1..3, a field outside its range, ws_bytes below
+ * LP_FILL_PATCH_WS_BYTES(...);  LP_E_UNSUPPORTED: channels > LP_FILL_PATCH_MAX_CHANNELS.  All checked before any HIP call,
+ * next to the checks above.
+ *
+ * 1 codes    pp = the push-pull result (the rule above; `out` holds it first).  code(v) = clamp(floor(fl(fl(v * 255) + 0.5)), 0, 255)
+ *            in fp32, a NaN gives 0.  I_0 = code(pp) per channel, so a known pixel holds its own code; hole_0 = mask > 0.5 (a NaN
+ *            is not).  A pixel's codes are one 32-bit word, channel c in byte c, unused bytes 0.
+ * 2 pyramid  levels 0 .. levels - 1, (h_{l+1}, w_{l+1}) = (ceil(h_l / 2), ceil(w_l / 2)).  Per channel I_{l+1}(i, j) =
+ *            (sum + n / 2) / n (integer division) over the children (2 i + dy, 2 j + dx), dy, dx in {0, 1}, that lie inside level
+ *            l, n = their number (1, 2 or 4); hole_{l+1} = the OR of those children's hole_l.
+ * 3 sets     per level: p is a TARGET when a pixel p + d, d in [-r, r]^2, inside the picture is a hole (the hole dilated by r,
+ *            Chebyshev); s is a SOURCE when all of s + [-r, r]^2 lies inside the picture and none of it is a hole.  The field
+ *            NNF holds per target a source centre or INVALID.
+ * 4 distance T is the working image: I_l with the hole pixels at their current estimate.  D(p, s) = the sum over d in [-r, r]^2
+ *            with p + d inside the picture, and over the channels, of |T(p + d) - I_l(s + d)|.  A candidate must be a source;
+ *            candidates are ordered by the key (D, s_y, s_x) and the lowest key wins.
+ * 5 search   one round reads NNF_in and writes NNF_out for every target p (no order between pixels).  Candidates, in this order:
+ *            (a) NNF_in(p) if valid;  (b) for step in (1, 4) and e in ((0, -1), (-1, 0), (0, 1), (1, 0)) (e = (e_y, e_x)):
+ *            n = p + step * e; if n is inside the picture, a target and NNF_in(n) valid: NNF_in(n) - step * e;  (c) for
+ *            j = 0, 1, ... while R_j = max(h_l, w_l) >> j >= 1: centre + (u_y, u_x), centre = the best so far (p itself while
+ *            none is valid), u = (int)((word * (2 R_j + 1)) >> 32) - R_j with the product in 64 bits, word = word 0 for u_y and
+ *            word 1 for u_x of Philox4x32-10 (Random123) with counter (p_y * 65536 + p_x [64 bit], (level << 40 | round << 32 |
+ *            j) [64 bit]) and key `seed` [64 bit]; the best is updated after every j.  `round` counts the rounds of a level from
+ *            0.  A candidate outside the picture or no source is dropped.  NNF_out(p) = the best, INVALID while there is none.
+ *            Neither the counter nor the key holds the image's index.
+ * 6 vote     each hole pixel q, per channel: sum = the sum of I_l(NNF(p) + d) over d in [-r, r]^2 with p = q - d inside the
+ *            picture and NNF(p) valid, n = the number of such d; n > 0: T(q) = (sum + n / 2) / n; n = 0: T(q) stays.
+ * 7 schedule coarsest level: T = I_l, NNF all INVALID, then iters x (search, vote).  From level l + 1 to l: T = I_l, NNF_l(p) =
+ *            2 NNF_{l+1}(p >> 1) + (p & 1) (per coordinate) for a target p whose NNF_{l+1}(p >> 1) is valid, kept when it lies
+ *            inside level l and is a source of level l, else INVALID; then one vote, then iters x (search, vote).
+ * 8 out      a known pixel: the image's bits.  A hole pixel with n > 0 in the last vote of level 0: (float)code / 255.0f (IEEE
+ *            division) per channel.  A hole pixel with n = 0 there: pp.
+ * So an image with no hole comes back bit for bit, an image with no source is the push-pull result bit for bit, and no output
+ * depends on the image under the mask.
+ *
+ * Workspace: LP_FILL_PATCH_WS_BYTES(lp_fill_ws_bytes(batch, height, width, channels), batch, height, width, levels) bytes.  First
+ * the push-pull form's part, lp_fill_ws_bytes(...) bytes (a multiple of 16); then for level l = 0 .. levels - 1, with
+ * n_l = batch * h_l * w_l and each plane's bytes rounded up to 16, image b at element b * h_l * w_l of a plane, in this order:
+ *   codes  n_l uint32   I_l                          work   n_l uint32   T
+ *   nnf    n_l int32    the field a level ends with and the vote reads: s_y * 65536 + s_x, INVALID = -1 (also where p is no target)
+ *   nnf2   n_l int32    the other field of the rounds
+ *   hole   n_l uint8    hole_l                       sets   n_l uint8    bit 0 hole, bit 1 target, bit 2 source
+ * LP_FILL_PATCH_LEVEL_BYTES(n) is one level's share.  Contents need not be set: no byte is read before it is written.
+ * Launches on `stream`: the push-pull form's, then 2 * levels for codes, pyramid and sets, and per level one field launch and
+ * iters x (search, vote), one more vote below the coarsest level.  A search or vote block is a 16 x 16 tile (LP_FILL_PATCH_TILE)
+ * with its r-halo in LDS; a tile without target (search) or hole (vote) leaves after its flags.                                   */
+#define LP_FILL_PATCH_MAX_RADIUS   4
+#define LP_FILL_PATCH_MAX_LEVELS   6
+#define LP_FILL_PATCH_MAX_ITERS    8
+#define LP_FILL_PATCH_MAX_CHANNELS 4
+#define LP_FILL_PATCH_TILE         16
+#define LP_FILL_PATCH(r, levels, iters, seed)                                                                              \
+    ((int32_t)(1u | ((uint32_t)(r) << 4) | ((uint32_t)(levels) << 8) | ((uint32_t)(iters) << 12) | ((uint32_t)(seed) << 16)))
+#define LP_FILL_PATCH_LEVEL_BYTES(n) (4 * (((int64_t)(n) * 4 + 15) / 16 * 16) + 2 * (((int64_t)(n) + 15) / 16 * 16))
+/* `pull_bytes` = lp_fill_ws_bytes(batch, height, width, channels); h_l = ((height - 1) >> l) + 1, the side halved l times, rounded up */
+#define LP_FILL_PATCH_SIDE(s, l) ((((int64_t)(s) - 1) >> (l)) + 1)
+#define LP_FILL_PATCH_WS_LEVEL(batch, height, width, levels, l)                                                            \
+    ((l) < (levels) ? LP_FILL_PATCH_LEVEL_BYTES((int64_t)(batch) * LP_FILL_PATCH_SIDE(height, l) * LP_FILL_PATCH_SIDE(width, l)) : 0)
+#define LP_FILL_PATCH_WS_BYTES(pull_bytes, batch, height, width, levels)                                                   \
+    ((int64_t)(pull_bytes) + LP_FILL_PATCH_WS_LEVEL(batch, height, width, levels, 0) +                                     \
+     LP_FILL_PATCH_WS_LEVEL(batch, height, width, levels, 1) + LP_FILL_PATCH_WS_LEVEL(batch, height, width, levels, 2) +   \
+     LP_FILL_PATCH_WS_LEVEL(batch, height, width, levels, 3) + LP_FILL_PATCH_WS_LEVEL(batch, height, width, levels, 4) +   \
+     LP_FILL_PATCH_WS_LEVEL(batch, height, width, levels, 5))
+
 /* The outpaint canvas and its mask, one launch.  H' = top + height + bottom, W' = left + width + right.
  *   image      [batch, height, width, channels] fp32
  *   mask       [mask_batch, height, width] fp32, mask_batch 1 or batch; mask_batch 0: no mask (the pointer is not read)

@@ -298,6 +298,41 @@ def fill_ws_bytes(batch, height, width, channels):
     return max(16, (int(batch) * pix * (4 * int(channels) + 1) + 15) // 16 * 16)
 
 
+LP_FILL_PATCH_MAX_RADIUS, LP_FILL_PATCH_MAX_LEVELS, LP_FILL_PATCH_MAX_ITERS, LP_FILL_PATCH_MAX_CHANNELS = 4, 6, 8, 4
+LP_FILL_PATCH_TILE = 16
+FILL_PATCH_PLANES = (("codes", 4), ("work", 4), ("nnf", 4), ("nnf2", 4), ("hole", 1), ("sets", 1))     # a level's planes, bytes an element
+
+
+def LP_FILL_PATCH(r, levels, iters, seed):
+    """The header's macro: lp_mask_fill's patch form as the int32 mode word of reserved0."""
+    word = 1 | (r << 4) | (levels << 8) | (iters << 12) | (seed << 16)
+    return word - (1 << 32) if word >= 1 << 31 else word
+
+
+def fill_patch_levels(height, width, levels):
+    """The sides of the patch form's levels 0 .. levels - 1: halved and rounded up."""
+    return [(((int(height) - 1) >> l) + 1, ((int(width) - 1) >> l) + 1) for l in range(int(levels))]
+
+
+def fill_patch_ws_layout(batch, height, width, channels, levels):
+    """The patch form's workspace as the header lays it out: [{"h", "w", plane: byte offset of image 0's first element, ...}] for
+    level 0 .. levels - 1; image b of a plane starts b * h * w elements further.  "nnf" is the field a level ends with."""
+    at, out = fill_ws_bytes(batch, height, width, channels), []
+    for h, w in fill_patch_levels(height, width, levels):
+        level = {"h": h, "w": w}
+        for name, size in FILL_PATCH_PLANES:
+            level[name] = at
+            at += (int(batch) * h * w * size + 15) // 16 * 16
+        out.append(level)
+    return out
+
+
+def fill_patch_ws_bytes(batch, height, width, channels, levels):
+    """LP_FILL_PATCH_WS_BYTES of include/lanpaint_hip.h over lp_fill_ws_bytes: what lp_mask_fill's patch form needs."""
+    last = fill_patch_ws_layout(batch, height, width, channels, levels)[-1]
+    return last["sets"] + (int(batch) * last["h"] * last["w"] + 15) // 16 * 16
+
+
 class LpMultibandDesc(C.Structure):
     _fields_ = [("batch", C.c_int32), ("height", C.c_int32), ("width", C.c_int32), ("channels", C.c_int32),
                 ("mask_batch", C.c_int32), ("levels", C.c_int32),

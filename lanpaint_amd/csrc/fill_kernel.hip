@@ -12,6 +12,8 @@
 //                    masked pixel only copies; an image with no known pixel is recognised by the top level's flag, on the device.
 //                    Filled values of a level go into the workspace where that level's flag is 0 -- places no block reads in the
 //                    same launch -- so the next span finds its top level complete.
+//                    With a mode word in reserved0 (LP_FILL_PATCH) the same launches make the pre-fill of the patch form, whose
+//                    kernels are patch_fill_kernel.hip's.
 //   lp_outpaint_pad  one streaming launch over the canvas: a block row per canvas row writes the image (original or 0) and the
 //                    mask (max(band, incoming)).
 //
@@ -338,7 +340,12 @@ extern "C" int lp_mask_fill(const lp_fill_desc* dp, void* stream_) {
     if (d.mask_batch != 1 && d.mask_batch != d.batch) return LP_E_INVALID;
     if (d.batch > 65535) return LP_E_UNSUPPORTED;
     if (!aligned16(d.ws)) return LP_E_ALIGN;
-    if (d.ws_bytes < lp_fill_ws_bytes(d.batch, d.height, d.width, d.channels)) return LP_E_INVALID;
+    if (d.reserved0 != 0) {                                        // the patch form: its mode word, channels and larger workspace
+        const int rc = patch_fill_check(d);
+        if (rc != LP_OK) return rc;
+    } else if (d.ws_bytes < lp_fill_ws_bytes(d.batch, d.height, d.width, d.channels)) {
+        return LP_E_INVALID;
+    }
     int32_t h[17], w[17];
     int64_t off[17], pix;
     const int L = fill_levels(d.height, d.width, h, w, off, &pix);
@@ -363,7 +370,7 @@ extern "C" int lp_mask_fill(const lp_fill_desc* dp, void* stream_) {
             hipLaunchKernelGGL(lp_fill_push_kernel<false>, grid, dim3(256), 0, stream, d, g);
         if (hipGetLastError() != hipSuccess) return LP_E_LAUNCH;
     }
-    return LP_OK;
+    return d.reserved0 != 0 ? patch_fill_enqueue(d, stream) : LP_OK;   // `out` is the push-pull result: the patch form's pre-fill
 }
 
 extern "C" int lp_outpaint_pad(const lp_outpaint_desc* dp, void* stream_) {

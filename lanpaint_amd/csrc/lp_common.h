@@ -785,6 +785,12 @@ int sigma_times_rule_dispatch(const float* sigma, int rows, const float* schedul
                               float* times, float* scalars, int32_t* seq_out, int32_t seq, int32_t n_steps, int32_t early_stop,
                               int32_t total_steps, double min_step_frac, int32_t guess, uint64_t* valid_out, hipStream_t stream);
 
+// ---- what fill_kernel.hip's lp_mask_fill calls in patch_fill_kernel.hip: the patch form, reserved0 != 0 ----
+// LP_OK, or the refusal of the mode word, of the channel count or of a workspace below the patch form's need; no HIP call
+int patch_fill_check(const lp_fill_desc& d);
+// the patch form behind the push-pull launches: d.out holds the push-pull result, d.ws the push-pull part first
+int patch_fill_enqueue(const lp_fill_desc& d, hipStream_t stream);
+
 // The 8-bit code of a value in 0..1 (the propagate section's "1 luma"; the grain and refine sections' codes): clamped, times 255,
 // rounded half up; a NaN gives 0.  A site that packs codes into a word casts to its unsigned type.
 __device__ __forceinline__ int code_of(float v) {

@@ -16,6 +16,18 @@ fill_masked(image, mask) -> image
         Known pixels come back bit for bit; an image with no known pixel comes back unchanged; no output depends on the image
         under the mask.  include/lanpaint_hip.h (lp_mask_fill) states the rule in full.
 
+fill_masked_patch(image, mask, radius=3, levels=AUTO, iters=4, seed=0) -> image
+        The same pre-fill, then under the mask texture copied from the known part of the same image: a PatchMatch search (patches
+        of 2 * radius + 1 pixels a side on 8-bit codes, `iters` Jacobi rounds of propagation and seeded random search per pyramid
+        level, `levels` levels coarse to fine) and a vote that averages what the overlapping patches bring.  Where smooth
+        continuation blurs grass, brick, fabric or gravel, this repeats them.  Known pixels come back bit for bit; an image with no
+        hole comes back unchanged; one with no hole-free patch is fill_masked's result bit for bit; nothing depends on the image
+        under the mask; the bits are the same on every run and for every batch and chunk.  include/lanpaint_hip.h (LP_FILL_PATCH)
+        states the rule in full.  Not handled: smooth shading (an exemplar fill cannot extrapolate a gradient -- on a plain colour
+        ramp it is worse than fill_masked, which stays the choice there); temporal coherence (frames are filled independently:
+        temporal_fill goes in front, temporal_smooth behind); more than 4 channels.  The batch runs in chunks whose workspace stays
+        under WS_CAP_BYTES.
+
 plan_outpaint(H, W, left, top, right, bottom, overlap, multiple_of) -> OutpaintPlan
         The final pads and the canvas size.  Per axis with pads (p0, p1) and M = multiple_of: when the axis is padded and M > 1,
         the canvas is brought up to the next multiple of M by e = (-(p0 + N + p1)) mod M more pixels -- split e // 2 low and the
@@ -37,10 +49,12 @@ import dataclasses
 import torch
 
 from . import _cabi
-from ._hostcall import MAX_BATCH, image4, int_in, launch, mask_for, require_hip, workspace
+from ._hostcall import MAX_BATCH, chunks, image4, int_in, launch, mask_for, require_hip, workspace
 from ._util import _as_f32c
 
 MAX_SIDE = _cabi.LP_DETAIL_MAX_SIDE
+AUTO = 0                              # fill_masked_patch's `levels`: as many as leave room for four patches a side
+WS_CAP_BYTES = 1 << 30                # fill_masked_patch's workspace, about 28 bytes a pixel, per chunk of images
 
 
 @dataclasses.dataclass(frozen=True)
@@ -101,6 +115,39 @@ def fill_masked(image, mask):
     out = torch.empty_like(img)
     d = _cabi.LpFillDesc(b, h, w, c, m.shape[0], 0, img.data_ptr(), m.data_ptr(), out.data_ptr(), ws.data_ptr(), ws.numel())
     launch("lp_mask_fill", dev, ctypes.byref(d))
+    return out
+
+
+def patch_levels(h, w, radius):
+    """AUTO: the largest L in 1..6 whose coarsest level still has min(h_{L-1}, w_{L-1}) >= 4 * (2 * radius + 1); at least 1."""
+    fits = [L for L in range(1, _cabi.LP_FILL_PATCH_MAX_LEVELS + 1) if min(_cabi.fill_patch_levels(h, w, L)[-1]) >= 4 * (2 * radius + 1)]
+    return max(fits, default=1)
+
+
+def fill_masked_patch(image, mask, radius=3, levels=AUTO, iters=4, seed=0):
+    """`image` [B, H, W, C], C <= 4, with its masked pixels filled with texture from the known ones (module docstring).  `mask` is
+    [B, H, W], [1, H, W] or [H, W].  One lp_mask_fill call per chunk of images on the current stream and no device -> host read."""
+    img = image4(require_hip(image, "image", __name__), "image")
+    int_in(radius, 1, _cabi.LP_FILL_PATCH_MAX_RADIUS, "radius")
+    int_in(levels, AUTO, _cabi.LP_FILL_PATCH_MAX_LEVELS, "levels")
+    int_in(iters, 1, _cabi.LP_FILL_PATCH_MAX_ITERS, "iters")
+    int_in(seed, 0, 65535, "seed")
+    if img.shape[3] > _cabi.LP_FILL_PATCH_MAX_CHANNELS:
+        raise ValueError(f"image {tuple(img.shape)}: the patch fill takes at most {_cabi.LP_FILL_PATCH_MAX_CHANNELS} channels")
+    img = _as_f32c(img)
+    dev = img.device
+    m = _mask_for(mask, img, dev)
+    b, h, w, c = img.shape
+    L = levels if levels != AUTO else patch_levels(h, w, radius)
+    mode = _cabi.LP_FILL_PATCH(radius, L, iters, seed)
+    parts = list(chunks(b, _cabi.fill_patch_ws_bytes(1, h, w, c, L), WS_CAP_BYTES))
+    ws = workspace(_cabi.fill_patch_ws_bytes(parts[0][1], h, w, c, L), dev)
+    out = torch.empty_like(img)
+    for s, n in parts:
+        mc = m if m.shape[0] == 1 else m[s:s + n]
+        d = _cabi.LpFillDesc(n, h, w, c, mc.shape[0], mode, img[s:s + n].data_ptr(), mc.data_ptr(), out[s:s + n].data_ptr(),
+                             ws.data_ptr(), ws.numel())
+        launch("lp_mask_fill", dev, ctypes.byref(d))
     return out
 
 
