@@ -14,22 +14,13 @@ For each shape, three timings of the same merge:
     python scripts/bench_av_merge.py [--iters 30] [--warmup 5] [--host-iters 3] [--kernels 10s=A.db 60s=B.db]
     python scripts/bench_av_merge.py --shape 10s --iters 20      # the body of a rocprofv3 --kernel-trace run
 
-Wall time: host clock around one call ending in torch.cuda.synchronize(), median over --iters after --warmup.  Per-kernel
+Time: featurebench.wall per call, median over --iters after --warmup (torch_host without the device synchronise).  Per-kernel
 times come from a SEPARATE rocprofv3 --kernel-trace --stats run per shape (--kernels reads its results .db / CSV); the merge
 kernel's bytes (two fp32 reads and one write per sample and channel) over its median time are reported against 6.3 TB/s.
 """
 from __future__ import annotations
 
-import argparse
-import json
-import os
-import statistics
-import sys
-import time
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "scripts"))
+import featurebench as fb
 
 HBM_ACHIEVABLE = 6.3e12
 SR, FPS, CROSSFADE, CHANNELS = 48000, 25, 0.02, 2
@@ -60,18 +51,9 @@ def torch_sequence(orig, inp, am, crossfade, sr):
     return orig * (1 - w[None, None]) + inp * w[None, None]
 
 
-def timed(fn, iters, warmup, sync):
-    for _ in range(warmup):
-        fn()
-    sync()
-    times = []
-    for _ in range(iters):
-        t0 = time.perf_counter()
-        fn()
-        sync()
-        times.append(time.perf_counter() - t0)
-    return {"ms_median": round(statistics.median(times) * 1e3, 4), "ms_min": round(min(times) * 1e3, 4),
-            "ms_max": round(max(times) * 1e3, 4), "iters": iters}
+def wall_stats(fn, iters, warmup, sync=fb.synchronize):
+    ms, (low, high) = fb.summary(fb.series([("wall", fn)], iters, warmup, timer=lambda f: fb.wall(f, sync=sync), sync=sync)["wall"])
+    return {"ms_median": ms, "ms_min": low, "ms_max": high, "iters": iters}
 
 
 def kernel_stats(path):
@@ -82,37 +64,30 @@ def kernel_stats(path):
         for k in ("plan", "merge"):
             if f"lp_audio_{k}_kernel" in name:
                 per.setdefault(k, []).append((end - start) * 1e-3)
-    return {k: {"calls": len(v), "mean_us": round(statistics.mean(v), 2), "median_us": round(statistics.median(v), 2)}
+    return {k: {"calls": len(v), "mean_us": round(sum(v) / len(v), 2), "median_us": round(fb.median(v), 2)}
             for k, v in per.items()}
 
 
 def run_hip(seconds, iters, warmup):
-    import torch
     from lanpaint_amd import audio
-    orig, inp, mask = inputs(seconds, torch.device("cuda", 0))
-    return timed(lambda: audio.merge_audio_with_mask(orig, inp, mask, CROSSFADE, SR, SR), iters, warmup,
-                 torch.cuda.synchronize)
+    orig, inp, mask = inputs(seconds, fb.device())
+    return wall_stats(lambda: audio.merge_audio_with_mask(orig, inp, mask, CROSSFADE, SR, SR), iters, warmup)
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--iters", type=int, default=30)
-    ap.add_argument("--warmup", type=int, default=5)
+    ap = fb.parser(iters=30, warmup=5)
     ap.add_argument("--host-iters", type=int, default=3)
     ap.add_argument("--shape", choices=sorted(SHAPES))
     ap.add_argument("--kernels", nargs="*", default=[], help="SHAPE=rocprofv3 results .db or kernel-trace .csv")
     args = ap.parse_args()
+    dev = fb.device()
     import torch
-    if not torch.cuda.is_available():
-        raise SystemExit("bench_av_merge.py needs a HIP device")
     if args.shape:
         run_hip(SHAPES[args.shape], args.iters, args.warmup)
         return
     from lanpaint_amd import audio
     profiles = dict(kv.split("=", 1) for kv in args.kernels)
-    dev = torch.device("cuda", 0)
-    result = {"metric": "av_audio_merge", "unit": "ms", "sample_rate": SR, "channels": CHANNELS, "crossfade_s": CROSSFADE,
-              "device": torch.cuda.get_device_name(0), "torch_threads": torch.get_num_threads(), "shapes": {}}
+    shapes = {}
     for name in sorted(SHAPES, key=SHAPES.get):
         seconds = SHAPES[name]
         orig, inp, mask = inputs(seconds, dev)
@@ -122,10 +97,9 @@ def main():
         rec = {"n": n, "mask_frames": int(mask.numel()), "bytes": 3 * 4 * CHANNELS * n,
                "max_abs_diff_vs_torch_dev": float((got - want).abs().max()),
                "hip": run_hip(seconds, args.iters, args.warmup),
-               "torch_dev": timed(lambda: torch_sequence(orig, inp, mask.to(dev), CROSSFADE, SR), args.iters, args.warmup,
-                                  torch.cuda.synchronize)}
+               "torch_dev": wall_stats(lambda: torch_sequence(orig, inp, mask.to(dev), CROSSFADE, SR), args.iters, args.warmup)}
         o_h, i_h = orig.cpu(), inp.cpu()
-        rec["torch_host"] = timed(lambda: torch_sequence(o_h, i_h, mask, CROSSFADE, SR), args.host_iters, 1, lambda: None)
+        rec["torch_host"] = wall_stats(lambda: torch_sequence(o_h, i_h, mask, CROSSFADE, SR), args.host_iters, 1, sync=lambda: None)
         if name in profiles:
             ks = kernel_stats(profiles[name])
             rec["kernels"] = ks
@@ -133,10 +107,11 @@ def main():
                 rec["merge_kernel_hbm_frac"] = round(rec["bytes"] / (ks["merge"]["median_us"] * 1e-6) / HBM_ACHIEVABLE, 4)
         else:
             rec["kernels"] = "not measured"
-        result["shapes"][name] = rec
+        shapes[name] = rec
         del orig, inp, got, want
         torch.cuda.empty_cache()
-    print(json.dumps(result, separators=(",", ":")))
+    fb.emit("av_audio_merge", None, sample_rate=SR, channels=CHANNELS, crossfade_s=CROSSFADE, torch_threads=torch.get_num_threads(),
+            shapes=shapes)
 
 
 if __name__ == "__main__":

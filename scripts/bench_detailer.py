@@ -14,22 +14,13 @@ Jobs:
     python scripts/bench_detailer.py [--iters 30] [--warmup 5] [--filter bicubic] [--kernels still:crop=A.db clip:stitch=B.db]
     python scripts/bench_detailer.py --shape clip --job stitch --iters 5   # the body of a rocprofv3 --kernel-trace run (new path only)
 
-Time: device events around one call, per iteration.  Every iteration runs new, old, new, old: the two series of the SAME code
-give the spread (relative difference of their medians), which is what a new-vs-old difference has to exceed to mean
-anything.  Per-kernel times come from a SEPARATE rocprofv3 --kernel-trace --stats run per shape and job (--kernels reads its
-results .db / kernel-trace CSV); required bytes over kernel time are reported against 6.29 TB/s achievable copy rate.
+Time: featurebench.events per call; every iteration runs new, old, new, old.  Per-kernel times come from a SEPARATE
+rocprofv3 --kernel-trace --stats run per shape and job (--kernels reads its results .db / kernel-trace CSV); required bytes over
+kernel time are reported against 6.29 TB/s achievable copy rate.
 """
 from __future__ import annotations
 
-import argparse
-import json
-import os
-import statistics
-import sys
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "scripts"))
+import featurebench as fb
 
 COPY_ACHIEVABLE = 6.29e12
 # name: (B, H, W, C, mask box (y0, y1, x0, x1) inclusive, context, target)
@@ -84,17 +75,6 @@ def stitch_old(image, mask, r, det, filter):
 JOBS = {"crop": (crop_new, crop_old), "stitch": (stitch_new, stitch_old)}
 
 
-def timed(fn, args):
-    import torch
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    out = fn(*args)
-    e1.record()
-    e1.synchronize()
-    del out
-    return e0.elapsed_time(e1)
-
-
 def required_bytes(name, job, r):
     b, H, W, c = SHAPES[name][:4]
     if job == "crop":                                     # window in + working size out, image and the one-frame mask
@@ -104,23 +84,14 @@ def required_bytes(name, job, r):
 
 
 def run_shape(name, iters, warmup, filter, new_only=False, only=None):
-    import torch
-    dev = torch.device("cuda", 0)
-    args = make_job(name, filter, dev) + (filter,)
+    args = make_job(name, filter, fb.device()) + (filter,)
     series = {}
     for job, (new, old) in JOBS.items():
         if only and job != only:
             continue
+        new, old = (lambda f=f: f(*args) for f in (new, old))
         fns = [("new_a", new), ("new_b", new)] if new_only else [("new_a", new), ("old_a", old), ("new_b", new), ("old_b", old)]
-        for _ in range(warmup):
-            for _, fn in fns:
-                fn(*args)
-        torch.cuda.synchronize()
-        rec = {label: [] for label, _ in fns}
-        for _ in range(iters):
-            for label, fn in fns:
-                rec[label].append(timed(fn, args))
-        series[job] = rec
+        series[job] = fb.series(fns, iters, warmup)
     return args[2], series
 
 
@@ -134,7 +105,7 @@ def kernel_stats(path, job):
         for k in KERNELS:
             if f"lp_detail_{k}_kernel" in name:
                 per.setdefault(k, []).append((end - start) * 1e-3)
-    out = {k: {"calls": len(v), "total_us": round(sum(v), 2), "median_us": round(statistics.median(v), 2)} for k, v in per.items()}
+    out = {k: {"calls": len(v), "total_us": round(sum(v), 2), "median_us": round(fb.median(v), 2)} for k, v in per.items()}
     anchor = "stitch" if job == "stitch" else "resample"
     if anchor not in per:
         return out, None
@@ -143,24 +114,20 @@ def kernel_stats(path, job):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--iters", type=int, default=30)
-    ap.add_argument("--warmup", type=int, default=5)
+    ap = fb.parser(iters=30, warmup=5)
     ap.add_argument("--filter", choices=("bilinear", "bicubic"), default="bicubic")
     ap.add_argument("--shape", choices=sorted(SHAPES))
     ap.add_argument("--job", choices=sorted(JOBS), help="with --shape: run this job only")
     ap.add_argument("--kernels", nargs="*", default=[], help="SHAPE:JOB=rocprofv3 results .db or kernel-trace .csv")
     a = ap.parse_args()
+    fb.device()
     import torch
-    if not torch.cuda.is_available():
-        raise SystemExit("bench_detailer.py needs a HIP device")
     if a.shape:
         run_shape(a.shape, a.iters, a.warmup, a.filter, new_only=True, only=a.job)
         return
     profiles = dict(kv.split("=", 1) for kv in a.kernels)
-    result = {"metric": "detailer_crop_stitch", "unit": "ms", "iters": a.iters, "warmup": a.warmup, "filter": a.filter,
-              "blend_overlap": K, "device": torch.cuda.get_device_name(0), "shapes": {}}
-    med = statistics.median
+    shapes = {}
+    med = fb.median
     for name in sorted(SHAPES):
         region, series = run_shape(name, a.iters, a.warmup, a.filter)
         rec = {"image": list(SHAPES[name][:4]), "region": [region.y0, region.x0, region.h, region.w],
@@ -168,10 +135,10 @@ def main():
         for job, s in series.items():
             new, old = med(s["new_a"] + s["new_b"]), med(s["old_a"] + s["old_b"])
             rec[job] = {"new_ms": round(new, 4), "old_ms": round(old, 4), "old_over_new": round(old / new, 3),
-                        "new_min_max_ms": [round(min(s["new_a"] + s["new_b"]), 4), round(max(s["new_a"] + s["new_b"]), 4)],
-                        "old_min_max_ms": [round(min(s["old_a"] + s["old_b"]), 4), round(max(s["old_a"] + s["old_b"]), 4)],
-                        "spread_new": round(abs(med(s["new_a"]) - med(s["new_b"])) / new, 4),
-                        "spread_old": round(abs(med(s["old_a"]) - med(s["old_b"])) / old, 4),
+                        "new_min_max_ms": fb.summary(s["new_a"] + s["new_b"])[1],
+                        "old_min_max_ms": fb.summary(s["old_a"] + s["old_b"])[1],
+                        "spread_new": fb.spread(s["new_a"], s["new_b"]),
+                        "spread_old": fb.spread(s["old_a"], s["old_b"]),
                         "required_bytes": required_bytes(name, job, region)}
         for job in JOBS:
             if f"{name}:{job}" in profiles:
@@ -182,9 +149,9 @@ def main():
                     rec[job]["copy_rate_frac"] = round(rec[job]["required_bytes"] / (per_call_us * 1e-6) / COPY_ACHIEVABLE, 4)
             else:
                 rec[job]["kernels"] = "not measured"
-        result["shapes"][name] = rec
+        shapes[name] = rec
         torch.cuda.empty_cache()
-    print(json.dumps(result, separators=(",", ":")))
+    fb.emit("detailer_crop_stitch", a, filter=a.filter, blend_overlap=K, shapes=shapes)
 
 
 if __name__ == "__main__":

@@ -13,21 +13,14 @@ that drifts across the window), method mean_std, margin 8, smooth 9.  Everything
     python scripts/bench_detailer_color.py [--iters 20] [--warmup 3]
     python scripts/bench_detailer_color.py --job hip --iters 10          # the body of a rocprofv3 --kernel-trace run
 
-Time: device events around one call, per iteration.  Every iteration runs hip, eager, hip, eager, then the three HIP stages
-on their own and the clone: the two series of the SAME code give the run-to-run spread (relative difference of their medians).
+Time: featurebench.events per call; every iteration runs hip, eager, hip, eager, then the three HIP stages on their own and
+the clone.
 Bytes: what the algorithm has to move -- two image reads and one mask read for the statistics, one image read and one write
 for the map -- over the time, and that rate over the clone's (one read, one write).
 """
 from __future__ import annotations
 
-import argparse
-import json
-import os
-import statistics
-import sys
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import featurebench as fb
 
 FRAMES, H, W, C = 81, 576, 1024, 3
 RADIUS, MARGIN, SMOOTH, METHOD, STRENGTH = 150, 8, 9, "mean_std", 1.0
@@ -106,63 +99,34 @@ def eager_match(j):
     return d * gain[:, None, None, :] + bias[:, None, None, :]
 
 
-def timed(fn, job):
-    import torch
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    out = fn(job)
-    e1.record()
-    e1.synchronize()
-    del out
-    return e0.elapsed_time(e1)
-
-
 def run(job, iters, warmup, only=None):
-    import torch
-    fns = [("hip_a", hip_match), ("eager_a", eager_match), ("hip_b", hip_match), ("eager_b", eager_match),
-           ("stats", hip_stats), ("fit", hip_fit), ("apply", hip_apply), ("clone", clone)]
-    if only == "hip":
-        fns = [("hip_a", hip_match)]
-    elif only == "eager":
-        fns = [("eager_a", eager_match)]
-    for _ in range(warmup):
-        for _, fn in fns:
-            fn(job)
-    torch.cuda.synchronize()
-    rec = {tag: [] for tag, _ in fns}
-    for _ in range(iters):
-        for tag, fn in fns:
-            rec[tag].append(timed(fn, job))
-    return rec
+    hip, eager, stats, fit, apply, copy = (lambda f=f: f(job) for f in (hip_match, eager_match, hip_stats, hip_fit, hip_apply, clone))
+    fns = [("hip_a", hip), ("eager_a", eager), ("hip_b", hip), ("eager_b", eager), ("stats", stats), ("fit", fit), ("apply", apply),
+           ("clone", copy)]
+    if only:
+        fns = [(only + "_a", hip if only == "hip" else eager)]
+    return fb.series(fns, iters, warmup)
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--iters", type=int, default=20)
-    ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--job", choices=("hip", "eager"), help="run this side only and print nothing (a profiler run's body)")
-    a = ap.parse_args()
-    import torch
-    if not torch.cuda.is_available():
-        raise SystemExit("bench_detailer_color.py needs a HIP device")
-    job = make_job(torch.device("cuda", 0))
+    a = fb.parser(jobs=("hip", "eager"), iters=20, warmup=3).parse_args()
+    job = make_job(fb.device())
     if a.job:
         run(job, a.iters, a.warmup, only=a.job)
         return
     diff = float((hip_match(job) - eager_match(job)).abs().max())     # the two sides compute the same thing
     s = run(job, a.iters, a.warmup)
-    med = statistics.median
+    med = fb.median
     need = required_bytes()
     hip, eager = med(s["hip_a"] + s["hip_b"]), med(s["eager_a"] + s["eager_b"])
     clone_tbs = need["clone"] / (med(s["clone"]) * 1e-3) / 1e12
-    result = {"metric": "detailer_color_match", "unit": "ms", "iters": a.iters, "warmup": a.warmup,
-              "device": torch.cuda.get_device_name(0), "image": [FRAMES, H, W, C], "margin": MARGIN, "smooth": SMOOTH,
+    result = {"image": [FRAMES, H, W, C], "margin": MARGIN, "smooth": SMOOTH,
               "method": METHOD, "max_abs_hip_minus_eager": diff,
               "hip_ms": round(hip, 4), "eager_ms": round(eager, 4), "eager_over_hip": round(eager / hip, 3),
-              "hip_min_max_ms": [round(min(s["hip_a"] + s["hip_b"]), 4), round(max(s["hip_a"] + s["hip_b"]), 4)],
-              "eager_min_max_ms": [round(min(s["eager_a"] + s["eager_b"]), 4), round(max(s["eager_a"] + s["eager_b"]), 4)],
-              "hip_spread": round(abs(med(s["hip_a"]) - med(s["hip_b"])) / hip, 4),
-              "eager_spread": round(abs(med(s["eager_a"]) - med(s["eager_b"])) / eager, 4),
+              "hip_min_max_ms": fb.summary(s["hip_a"] + s["hip_b"])[1],
+              "eager_min_max_ms": fb.summary(s["eager_a"] + s["eager_b"])[1],
+              "hip_spread": fb.spread(s["hip_a"], s["hip_b"]),
+              "eager_spread": fb.spread(s["eager_a"], s["eager_b"]),
               "clone_ms": round(med(s["clone"]), 4), "clone_tb_per_s": round(clone_tbs, 3), "required_bytes": need}
     for tag, key in (("hip", "match"), ("stats", "stats"), ("apply", "apply")):
         t = hip if tag == "hip" else med(s[tag])
@@ -170,7 +134,7 @@ def main():
         result[f"{key}_required_tb_per_s"] = round(rate, 3)
         result[f"{key}_fraction_of_clone_rate"] = round(rate / clone_tbs, 3)
     result["stats_ms"], result["fit_ms"], result["apply_ms"] = (round(med(s[k]), 4) for k in ("stats", "fit", "apply"))
-    print(json.dumps(result, separators=(",", ":")))
+    fb.emit("detailer_color_match", a, **result)
 
 
 if __name__ == "__main__":

@@ -13,24 +13,15 @@ Jobs, new against what the tree had before for the same result:
     python scripts/bench_detailer_regions.py [--iters 30] [--warmup 5] [--filter bicubic] [--kernels clip=A.db still=B.db]
     python scripts/bench_detailer_regions.py --shape clip --job label --iters 10   # the body of a rocprofv3 --kernel-trace run
 
-Time: device events around one call, per iteration.  Every iteration runs new, old, new, old: the two series of the SAME code
-give the spread (relative difference of their medians), which is what a new-vs-old difference has to exceed to mean
-anything.  `label` includes the table's device -> host read on both sides (mask_bbox reads its four integers back too).
-Per-kernel times come from a SEPARATE rocprofv3 --kernel-trace --stats run of `--shape S --job label`, which runs
-mask_components and mask_bbox alternately (--kernels reads its results .db / kernel-trace CSV): per launch the median and
-min-max, the bytes the launch has to touch, and the union pass against lp_detail_bbox_kernel on the same input in that run.
+Time: featurebench.events per call; every iteration runs new, old, new, old.  `label` includes the table's device -> host
+read on both sides (mask_bbox reads its four integers back too).  Per-kernel times come from a SEPARATE rocprofv3 --kernel-trace
+--stats run of `--shape S --job label`, which runs mask_components and mask_bbox alternately (--kernels reads its results .db /
+kernel-trace CSV): per launch the median and min-max, the bytes the launch has to touch, and the union pass against
+lp_detail_bbox_kernel on the same input in that run.
 """
 from __future__ import annotations
 
-import argparse
-import json
-import os
-import statistics
-import sys
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "scripts"))
+import featurebench as fb
 
 COPY_ACHIEVABLE = 6.29e12
 # name: (B, mask frames, H, W, C, discs (cy, cx, r), context, padding, target)
@@ -100,34 +91,14 @@ def stitch_old(j):
 JOBS = {"label": (label_new, label_old), "crop": (crop_new, crop_old), "stitch": (stitch_new, stitch_old)}
 
 
-def timed(fn, job):
-    import torch
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    out = fn(job)
-    e1.record()
-    e1.synchronize()
-    del out
-    return e0.elapsed_time(e1)
-
-
 def run_shape(name, iters, warmup, filter, only=None):
-    import torch
-    job = make_job(name, filter, torch.device("cuda", 0))
+    job = make_job(name, filter, fb.device())
     series = {}
     for label, (new, old) in JOBS.items():
         if only and label != only:
             continue
-        fns = [("new_a", new), ("old_a", old), ("new_b", new), ("old_b", old)]
-        for _ in range(warmup):
-            for _, fn in fns:
-                fn(job)
-        torch.cuda.synchronize()
-        rec = {tag: [] for tag, _ in fns}
-        for _ in range(iters):
-            for tag, fn in fns:
-                rec[tag].append(timed(fn, job))
-        series[label] = rec
+        new, old = (lambda f=f: f(job) for f in (new, old))
+        series[label] = fb.series([("new_a", new), ("old_a", old), ("new_b", new), ("old_b", old)], iters, warmup)
     return job, series
 
 
@@ -152,7 +123,7 @@ def kernel_stats(path, name):
     need = label_launch_bytes(name)
     out = {}
     for k, v in per.items():
-        med = statistics.median(v)
+        med = fb.median(v)
         out[k] = {"calls": len(v), "median_us": round(med, 2), "min_max_us": [round(min(v), 2), round(max(v), 2)],
                   "bytes": int(need[k]), "copy_rate_frac": round(need[k] / (med * 1e-6) / COPY_ACHIEVABLE, 4)}
     if "union" in out and "bbox" in out:
@@ -163,24 +134,20 @@ def kernel_stats(path, name):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--iters", type=int, default=30)
-    ap.add_argument("--warmup", type=int, default=5)
+    ap = fb.parser(iters=30, warmup=5)
     ap.add_argument("--filter", choices=("bilinear", "bicubic"), default="bicubic")
     ap.add_argument("--shape", choices=sorted(SHAPES))
     ap.add_argument("--job", choices=sorted(JOBS), help="with --shape: run this job only")
     ap.add_argument("--kernels", nargs="*", default=[], help="SHAPE=rocprofv3 results .db or kernel-trace .csv of a label run")
     a = ap.parse_args()
+    fb.device()
     import torch
-    if not torch.cuda.is_available():
-        raise SystemExit("bench_detailer_regions.py needs a HIP device")
     if a.shape:
         run_shape(a.shape, a.iters, a.warmup, a.filter, only=a.job)
         return
     profiles = dict(kv.split("=", 1) for kv in a.kernels)
-    result = {"metric": "detailer_regions", "unit": "ms", "iters": a.iters, "warmup": a.warmup, "filter": a.filter,
-              "blend_overlap": K, "device": torch.cuda.get_device_name(0), "shapes": {}}
-    med = statistics.median
+    shapes = {}
+    med = fb.median
     for name in sorted(SHAPES):
         job, series = run_shape(name, a.iters, a.warmup, a.filter)
         g = job["regions"]
@@ -189,15 +156,15 @@ def main():
         for label, s in series.items():
             new, old = med(s["new_a"] + s["new_b"]), med(s["old_a"] + s["old_b"])
             rec[label] = {"new_ms": round(new, 4), "old_ms": round(old, 4), "old_over_new": round(old / new, 3),
-                          "new_min_max_ms": [round(min(s["new_a"] + s["new_b"]), 4), round(max(s["new_a"] + s["new_b"]), 4)],
-                          "old_min_max_ms": [round(min(s["old_a"] + s["old_b"]), 4), round(max(s["old_a"] + s["old_b"]), 4)],
-                          "spread_new": round(abs(med(s["new_a"]) - med(s["new_b"])) / new, 4),
-                          "spread_old": round(abs(med(s["old_a"]) - med(s["old_b"])) / old, 4)}
+                          "new_min_max_ms": fb.summary(s["new_a"] + s["new_b"])[1],
+                          "old_min_max_ms": fb.summary(s["old_a"] + s["old_b"])[1],
+                          "spread_new": fb.spread(s["new_a"], s["new_b"]),
+                          "spread_old": fb.spread(s["old_a"], s["old_b"])}
         rec["label"]["kernels"] = kernel_stats(profiles[name], name) if name in profiles else "not measured"
-        result["shapes"][name] = rec
+        shapes[name] = rec
         del job
         torch.cuda.empty_cache()
-    print(json.dumps(result, separators=(",", ":")))
+    fb.emit("detailer_regions", a, filter=a.filter, blend_overlap=K, shapes=shapes)
 
 
 if __name__ == "__main__":

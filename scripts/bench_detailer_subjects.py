@@ -9,8 +9,8 @@ detailed crops are already on the device.
 (a) Working pixels, host arithmetic only: the window and the working pixels per subject under plan_track (one box per frame,
     which spans every subject in it) against plan_subjects.  `--host-only` prints this part from numpy boxes without a device.
 (b) Kernel resources come from the library's metadata (scripts/instantiation_coverage.py kernel_resources), not from here.
-(c) Times against yardsticks in the same process, interleaved (every iteration runs new, yardstick, new, yardstick; the two
-    series of the SAME code give the run-to-run spread, and `yard_spread` is the margin a difference has to exceed):
+(c) Times against yardsticks in the same process, interleaved (featurebench.events per call; every iteration runs new,
+    yardstick, new, yardstick, and `yard_spread` is the margin a difference has to exceed):
         label   lp_mask_components_frames on the volume   vs  `frames` back-to-back lp_mask_components calls on single frames
                 (raw entries into preallocated buffers on both sides, no table read-back inside the timed span)
         crop    detail_subjects.crop_subjects             vs  detail.crop_track called S times, once per subject's path
@@ -27,14 +27,9 @@ detailed crops are already on the device.
 """
 from __future__ import annotations
 
-import argparse
 import json
-import os
-import statistics
-import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import featurebench as fb
 
 FRAMES, H, W, C = 81, 720, 1280, 3
 DISCS = ((60, 250, 240, 1040, 0), (60, 470, 1040, 240, 0), (20, 360, 600, 680, 60))   # radius, row, x from, x to, first frame
@@ -158,72 +153,45 @@ def stitch_yard(j):
 JOBS = {"label": (label_new, label_yard), "crop": (crop_new, crop_yard), "stitch": (stitch_new, stitch_yard)}
 
 
-def timed(fn, job):
-    import torch
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    out = fn(job)
-    e1.record()
-    e1.synchronize()
-    del out
-    return e0.elapsed_time(e1)
-
-
 def run(job, iters, warmup, only=None):
-    import torch
     series = {}
-    for label, (new, yard) in JOBS.items():
+    for label, pair in JOBS.items():
         if only and label != only:
             continue
-        fns = [("new_a", new), ("yard_a", yard), ("new_b", new), ("yard_b", yard)]
-        for _ in range(warmup):
-            for _, fn in fns:
-                fn(job)
-        torch.cuda.synchronize()
-        rec = {tag: [] for tag, _ in fns}
-        for _ in range(iters):
-            for tag, fn in fns:
-                rec[tag].append(timed(fn, job))
-        series[label] = rec
+        new, yard = (lambda f=f: f(job) for f in pair)
+        series[label] = fb.series([("new_a", new), ("yard_a", yard), ("new_b", new), ("yard_b", yard)], iters, warmup)
     return series
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--iters", type=int, default=20)
-    ap.add_argument("--warmup", type=int, default=3)
+    ap = fb.parser(jobs=sorted(JOBS), iters=20, warmup=3)
     ap.add_argument("--filter", choices=("bilinear", "bicubic"), default="bicubic")
-    ap.add_argument("--job", choices=sorted(JOBS), help="run this job only and print nothing (a profiler run's body)")
     ap.add_argument("--host-only", action="store_true", help="part (a) from numpy boxes; needs no device")
     a = ap.parse_args()
-    result = {"metric": "detailer_subjects", "unit": "ms", "filter": a.filter, "blend_overlap": K, "smooth": SMOOTH,
-              "image": [FRAMES, H, W, C], "expected_label_ratio_from_bytes": round(EXPECTED_LABEL_RATIO, 4)}
+    result = {"filter": a.filter, "blend_overlap": K, "smooth": SMOOTH, "image": [FRAMES, H, W, C],
+              "expected_label_ratio_from_bytes": round(EXPECTED_LABEL_RATIO, 4)}
     if a.host_only:
         import numpy as np
         vols = disc_masks()
         boxes = tuple(host_boxes(v) for v in vols)
         subjects, track = plans(boxes, host_boxes(np.logical_or.reduce(vols)))
         result["working_pixels"] = working_pixels(boxes, subjects, track)
-        print(json.dumps(result, separators=(",", ":")))
+        print(json.dumps({"metric": "detailer_subjects", "unit": "ms", **result}, separators=(",", ":")))
         return
-    import torch
-    if not torch.cuda.is_available():
-        raise SystemExit("bench_detailer_subjects.py needs a HIP device (or --host-only for part (a))")
-    job = make_job(a.filter, torch.device("cuda", 0))
+    job = make_job(a.filter, fb.device(hint=" (or --host-only for part (a))"))
     if a.job:
         run(job, a.iters, a.warmup, only=a.job)
         return
-    result.update({"iters": a.iters, "warmup": a.warmup, "device": torch.cuda.get_device_name(0),
-                   "working_pixels": working_pixels(job["boxes"], job["subjects"], job["track"])})
-    med = statistics.median
+    result["working_pixels"] = working_pixels(job["boxes"], job["subjects"], job["track"])
+    med = fb.median
     for label, s in run(job, a.iters, a.warmup).items():
         new, yard = med(s["new_a"] + s["new_b"]), med(s["yard_a"] + s["yard_b"])
         result[label] = {"new_ms": round(new, 4), "yard_ms": round(yard, 4), "new_over_yard": round(new / yard, 4),
-                         "new_min_max_ms": [round(min(s["new_a"] + s["new_b"]), 4), round(max(s["new_a"] + s["new_b"]), 4)],
-                         "yard_min_max_ms": [round(min(s["yard_a"] + s["yard_b"]), 4), round(max(s["yard_a"] + s["yard_b"]), 4)],
-                         "new_spread": round(abs(med(s["new_a"]) - med(s["new_b"])) / new, 4),
-                         "yard_spread": round(abs(med(s["yard_a"]) - med(s["yard_b"])) / yard, 4)}
-    print(json.dumps(result, separators=(",", ":")))
+                         "new_min_max_ms": fb.summary(s["new_a"] + s["new_b"])[1],
+                         "yard_min_max_ms": fb.summary(s["yard_a"] + s["yard_b"])[1],
+                         "new_spread": fb.spread(s["new_a"], s["new_b"]),
+                         "yard_spread": fb.spread(s["yard_a"], s["yard_b"])}
+    fb.emit("detailer_subjects", a, **result)
 
 
 if __name__ == "__main__":

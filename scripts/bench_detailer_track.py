@@ -16,20 +16,12 @@ already on the device.
     python scripts/bench_detailer_track.py [--iters 30] [--warmup 5] [--filter bicubic]
     python scripts/bench_detailer_track.py --job stitch --iters 10      # the body of a rocprofv3 --kernel-trace run
 
-Time: device events around one call, per iteration.  Every iteration runs track, fixed, track, fixed: the two series of the
-SAME code give the run-to-run spread (relative difference of their medians), and `fixed_spread` is the margin a track-vs-fixed
-difference has to exceed to mean anything.  `bbox` includes the table's device -> host read on both sides.
+Time: featurebench.events per call; every iteration runs track, fixed, track, fixed, and `fixed_spread` is the margin a
+track-vs-fixed difference has to exceed to mean anything.  `bbox` includes the table's device -> host read on both sides.
 """
 from __future__ import annotations
 
-import argparse
-import json
-import os
-import statistics
-import sys
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import featurebench as fb
 
 FRAMES, H, W, C = 81, 720, 1280, 3
 RADIUS, X_FROM, X_TO = 60, 240, 1040
@@ -108,62 +100,34 @@ def stitch_fixed(j):
 JOBS = {"bbox": (bbox_track, bbox_fixed), "crop": (crop_track, crop_fixed), "stitch": (stitch_track, stitch_fixed)}
 
 
-def timed(fn, job):
-    import torch
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    out = fn(job)
-    e1.record()
-    e1.synchronize()
-    del out
-    return e0.elapsed_time(e1)
-
-
 def run(job, iters, warmup, only=None):
-    import torch
     series = {}
-    for label, (track, fixed) in JOBS.items():
+    for label, pair in JOBS.items():
         if only and label != only:
             continue
-        fns = [("track_a", track), ("fixed_a", fixed), ("track_b", track), ("fixed_b", fixed)]
-        for _ in range(warmup):
-            for _, fn in fns:
-                fn(job)
-        torch.cuda.synchronize()
-        rec = {tag: [] for tag, _ in fns}
-        for _ in range(iters):
-            for tag, fn in fns:
-                rec[tag].append(timed(fn, job))
-        series[label] = rec
+        track, fixed = (lambda f=f: f(job) for f in pair)
+        series[label] = fb.series([("track_a", track), ("fixed_a", fixed), ("track_b", track), ("fixed_b", fixed)], iters, warmup)
     return series
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--iters", type=int, default=30)
-    ap.add_argument("--warmup", type=int, default=5)
+    ap = fb.parser(jobs=sorted(JOBS), iters=30, warmup=5)
     ap.add_argument("--filter", choices=("bilinear", "bicubic"), default="bicubic")
-    ap.add_argument("--job", choices=sorted(JOBS), help="run this job only and print nothing (a profiler run's body)")
     a = ap.parse_args()
-    import torch
-    if not torch.cuda.is_available():
-        raise SystemExit("bench_detailer_track.py needs a HIP device")
-    job = make_job(a.filter, torch.device("cuda", 0))
+    job = make_job(a.filter, fb.device())
     if a.job:
         run(job, a.iters, a.warmup, only=a.job)
         return
-    result = {"metric": "detailer_track", "unit": "ms", "iters": a.iters, "warmup": a.warmup, "filter": a.filter,
-              "blend_overlap": K, "smooth": SMOOTH, "device": torch.cuda.get_device_name(0), "image": [FRAMES, H, W, C],
-              "working_pixels": working_pixels(job)}
-    med = statistics.median
+    result = {"filter": a.filter, "blend_overlap": K, "smooth": SMOOTH, "image": [FRAMES, H, W, C], "working_pixels": working_pixels(job)}
+    med = fb.median
     for label, s in run(job, a.iters, a.warmup).items():
         track, fixed = med(s["track_a"] + s["track_b"]), med(s["fixed_a"] + s["fixed_b"])
         result[label] = {"track_ms": round(track, 4), "fixed_ms": round(fixed, 4), "track_over_fixed": round(track / fixed, 4),
-                         "track_min_max_ms": [round(min(s["track_a"] + s["track_b"]), 4), round(max(s["track_a"] + s["track_b"]), 4)],
-                         "fixed_min_max_ms": [round(min(s["fixed_a"] + s["fixed_b"]), 4), round(max(s["fixed_a"] + s["fixed_b"]), 4)],
-                         "track_spread": round(abs(med(s["track_a"]) - med(s["track_b"])) / track, 4),
-                         "fixed_spread": round(abs(med(s["fixed_a"]) - med(s["fixed_b"])) / fixed, 4)}
-    print(json.dumps(result, separators=(",", ":")))
+                         "track_min_max_ms": fb.summary(s["track_a"] + s["track_b"])[1],
+                         "fixed_min_max_ms": fb.summary(s["fixed_a"] + s["fixed_b"])[1],
+                         "track_spread": fb.spread(s["track_a"], s["track_b"]),
+                         "fixed_spread": fb.spread(s["fixed_a"], s["fixed_b"])}
+    fb.emit("detailer_track", a, **result)
 
 
 if __name__ == "__main__":

@@ -21,19 +21,11 @@ Two workloads, everything already on the device: a ramp with a 3 x 3 binomial gr
     python scripts/bench_grain.py [--iters 10] [--warmup 2] [--case still] [--torch-iters 3]
     python scripts/bench_grain.py --job apply --case clip --iters 10      # the body of a rocprofv3 --kernel-trace run
 
-Time: device events around one call, per iteration.  Every iteration runs apply, stats_in, apply, stats_in, stats_out, fit,
-clone, match: the two series of the SAME code give the run-to-run spread (relative difference of their medians).
+Time: featurebench.events per call; every iteration runs apply, stats_in, apply, stats_in, stats_out, fit, clone, match.
 """
 from __future__ import annotations
 
-import argparse
-import json
-import os
-import statistics
-import sys
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import featurebench as fb
 
 CASES = {"still": (1, 1024, 1024, 3), "clip": (81, 720, 1280, 3)}
 INFINITY_CACHE_BYTES = 256 << 20
@@ -173,29 +165,9 @@ def jobs():
             "torch_apply": lambda j: torch_apply(j["image"], j["mask"], j["amp"], j["sizes_host"], SEED)}
 
 
-def timed(fn, job):
-    import torch
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    out = fn(job)
-    e1.record()
-    e1.synchronize()
-    del out
-    return e0.elapsed_time(e1)
-
-
 def run(job, order, iters, warmup):
-    import torch
-    fn = jobs()
-    for _ in range(warmup):
-        for _, name in order:
-            fn[name](job)
-    torch.cuda.synchronize()
-    rec = {tag: [] for tag, _ in order}
-    for _ in range(iters):
-        for tag, name in order:
-            rec[tag].append(timed(fn[name], job))
-    return rec
+    fn = {name: (lambda f=f: f(job)) for name, f in jobs().items()}
+    return fb.series([(tag, fn[name]) for tag, name in order], iters, warmup)
 
 
 def measure(job, iters, warmup, torch_iters):
@@ -213,7 +185,7 @@ def measure(job, iters, warmup, torch_iters):
                   ("stats_out", "stats_out"), ("fit", "fit"), ("clone", "clone"), ("match", "match")], iters, warmup)
     t = run(job, [("torch_stats", "torch_stats"), ("torch_apply", "torch_apply")], torch_iters, 1)
     torch.cuda.empty_cache()
-    med = statistics.median
+    med = fb.median
     apply, stats_in = med(s["apply_a"] + s["apply_b"]), med(s["stats_in_a"] + s["stats_in_b"])
     clone = med(s["clone"])
     apply_bytes, stats_bytes, clone_bytes = B * H * W * (8 * C + 4), B * H * W * (4 * C + 4), B * H * W * C * 8
@@ -222,12 +194,12 @@ def measure(job, iters, warmup, torch_iters):
             "grain_std_codes_max": r3(float(job["amp"].max()) * 255.0 * (21845 * (1, 36, 4900)[job["sizes_host"][0]]) ** 0.5),
             "stats_elements_differing_from_torch": stats_diff, "apply_elements_differing_from_torch": apply_diff,
             "elements_changed_by_apply": changed,
-            "match_ms": r3(med(s["match"])), "match_min_max_ms": [r3(min(s["match"])), r3(max(s["match"]))],
+            "match_ms": r3(med(s["match"])), "match_min_max_ms": fb.summary(s["match"])[1],
             "stats_out_ms": r3(med(s["stats_out"])), "stats_in_ms": r3(stats_in), "fit_ms": r3(med(s["fit"])), "apply_ms": r3(apply),
-            "apply_min_max_ms": [r3(min(s["apply_a"] + s["apply_b"])), r3(max(s["apply_a"] + s["apply_b"]))],
-            "stats_in_min_max_ms": [r3(min(s["stats_in_a"] + s["stats_in_b"])), r3(max(s["stats_in_a"] + s["stats_in_b"]))],
-            "apply_spread": r3(abs(med(s["apply_a"]) - med(s["apply_b"])) / apply),
-            "stats_in_spread": r3(abs(med(s["stats_in_a"]) - med(s["stats_in_b"])) / stats_in),
+            "apply_min_max_ms": fb.summary(s["apply_a"] + s["apply_b"])[1],
+            "stats_in_min_max_ms": fb.summary(s["stats_in_a"] + s["stats_in_b"])[1],
+            "apply_spread": fb.spread(s["apply_a"], s["apply_b"]),
+            "stats_in_spread": fb.spread(s["stats_in_a"], s["stats_in_b"]),
             "clone_ms": r3(clone), "torch_stats_ms": r3(med(t["torch_stats"])), "torch_apply_ms": r3(med(t["torch_apply"])),
             "torch_stats_over_stats_in": round(med(t["torch_stats"]) / stats_in, 1),
             "torch_apply_over_apply": round(med(t["torch_apply"]) / apply, 1),
@@ -240,18 +212,11 @@ def measure(job, iters, warmup, torch_iters):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--iters", type=int, default=10)
-    ap.add_argument("--warmup", type=int, default=2)
+    ap = fb.parser(CASES, ("stats_out", "stats_in", "fit", "apply", "match"))
     ap.add_argument("--torch-iters", type=int, default=3)
-    ap.add_argument("--case", choices=tuple(CASES), help="this workload only")
-    ap.add_argument("--job", choices=("stats_out", "stats_in", "fit", "apply", "match"),
-                    help="run this side only and print nothing (a profiler run's body)")
     a = ap.parse_args()
+    dev = fb.device()
     import torch
-    if not torch.cuda.is_available():
-        raise SystemExit("bench_grain.py needs a HIP device")
-    dev = torch.device("cuda", 0)
     results = []
     for case in ((a.case,) if a.case else tuple(CASES)):
         job = make_job(case, dev)
@@ -262,8 +227,7 @@ def main():
         del job
         torch.cuda.empty_cache()
     if not a.job:
-        print(json.dumps({"metric": "grain_match", "unit": "ms", "iters": a.iters, "warmup": a.warmup, "torch_iters": a.torch_iters,
-                          "device": torch.cuda.get_device_name(0), "cases": results}, separators=(",", ":")))
+        fb.emit("grain_match", a, results, torch_iters=a.torch_iters)
 
 
 if __name__ == "__main__":

@@ -15,22 +15,14 @@ Two cases at levels = 5, everything already on the device:
     python scripts/bench_multiband.py [--iters 20] [--warmup 3]
     python scripts/bench_multiband.py --job hip --case frame --iters 10     # the body of a rocprofv3 --kernel-trace run
 
-Time: device events around one call, per iteration.  Every iteration runs hip, torch, hip, torch, clone: the two series of the
-SAME code give the run-to-run spread (relative difference of their medians).  Bytes: what the rule has to move -- image1, image2
+Time: featurebench.events per call; every iteration runs hip, torch, hip, torch, clone.  Bytes: what the rule has to move -- image1, image2
 and the mask read twice (to build the pyramid and to collapse onto level 0: level 0 is never stored), the result written once,
 and every stored level written once and read where the rule needs it -- over the time, and that rate over the clone's (one
 read, one write).
 """
 from __future__ import annotations
 
-import argparse
-import json
-import os
-import statistics
-import sys
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import featurebench as fb
 
 CASES = {"frame": (1, 1024, 1024, 3), "clip": (81, 720, 1280, 3)}
 LEVELS, RADIUS = 5, 150
@@ -125,31 +117,12 @@ def torch_job(j):
     return torch_blend(j["a"], j["b"], j["mask"], LEVELS)
 
 
-def timed(fn, job):
-    import torch
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    out = fn(job)
-    e1.record()
-    e1.synchronize()
-    del out
-    return e0.elapsed_time(e1)
-
-
 def run(job, iters, warmup, only=None):
-    import torch
-    fns = [("hip_a", hip_job), ("torch_a", torch_job), ("hip_b", hip_job), ("torch_b", torch_job), ("clone", clone)]
+    hip, eager, copy = (lambda f=f: f(job) for f in (hip_job, torch_job, clone))
+    fns = [("hip_a", hip), ("torch_a", eager), ("hip_b", hip), ("torch_b", eager), ("clone", copy)]
     if only:
-        fns = [(only + "_a", hip_job if only == "hip" else torch_job)]
-    for _ in range(warmup):
-        for _, fn in fns:
-            fn(job)
-    torch.cuda.synchronize()
-    rec = {tag: [] for tag, _ in fns}
-    for _ in range(iters):
-        for tag, fn in fns:
-            rec[tag].append(timed(fn, job))
-    return rec
+        fns = [(only + "_a", hip if only == "hip" else eager)]
+    return fb.series(fns, iters, warmup)
 
 
 def measure(case, dev, iters, warmup):
@@ -158,32 +131,25 @@ def measure(case, dev, iters, warmup):
     diff = float((hip_job(job) - torch_job(job)).abs().max())       # the two sides compute the same thing
     torch.cuda.empty_cache()
     s = run(job, iters, warmup)
-    med = statistics.median
+    med = fb.median
     need = required_bytes(case)
     hip, eager = med(s["hip_a"] + s["hip_b"]), med(s["torch_a"] + s["torch_b"])
     clone_tbs = need["clone"] / (med(s["clone"]) * 1e-3) / 1e12
     rate = need["job"] / (hip * 1e-3) / 1e12
     return {"case": case, "image": list(job["a"].shape), "levels": LEVELS, "max_abs_hip_minus_torch": diff,
             "hip_ms": round(hip, 4), "torch_ms": round(eager, 4), "torch_over_hip": round(eager / hip, 2),
-            "hip_min_max_ms": [round(min(s["hip_a"] + s["hip_b"]), 4), round(max(s["hip_a"] + s["hip_b"]), 4)],
-            "torch_min_max_ms": [round(min(s["torch_a"] + s["torch_b"]), 4), round(max(s["torch_a"] + s["torch_b"]), 4)],
-            "hip_spread": round(abs(med(s["hip_a"]) - med(s["hip_b"])) / hip, 4),
-            "torch_spread": round(abs(med(s["torch_a"]) - med(s["torch_b"])) / eager, 4),
+            "hip_min_max_ms": fb.summary(s["hip_a"] + s["hip_b"])[1],
+            "torch_min_max_ms": fb.summary(s["torch_a"] + s["torch_b"])[1],
+            "hip_spread": fb.spread(s["hip_a"], s["hip_b"]),
+            "torch_spread": fb.spread(s["torch_a"], s["torch_b"]),
             "clone_ms": round(med(s["clone"]), 4), "clone_tb_per_s": round(clone_tbs, 3), "required_bytes": need,
             "required_tb_per_s": round(rate, 3), "fraction_of_clone_rate": round(rate / clone_tbs, 3)}
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--iters", type=int, default=20)
-    ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--case", choices=tuple(CASES), help="this case only")
-    ap.add_argument("--job", choices=("hip", "torch"), help="run this side only and print nothing (a profiler run's body)")
-    a = ap.parse_args()
+    a = fb.parser(CASES, ("hip", "torch"), iters=20, warmup=3).parse_args()
+    dev = fb.device()
     import torch
-    if not torch.cuda.is_available():
-        raise SystemExit("bench_multiband.py needs a HIP device")
-    dev = torch.device("cuda", 0)
     cases = (a.case,) if a.case else tuple(CASES)
     if a.job:
         for case in cases:
@@ -193,9 +159,7 @@ def main():
     for case in cases:
         results.append(measure(case, dev, a.iters, a.warmup))
         torch.cuda.empty_cache()
-    print(json.dumps({"metric": "multiband_blend", "unit": "ms", "iters": a.iters, "warmup": a.warmup,
-                      "device": torch.cuda.get_device_name(0), "cases": results,
-                      "hip_faster_in_every_case": all(r["torch_over_hip"] > 1.0 for r in results)}, separators=(",", ":")))
+    fb.emit("multiband_blend", a, results, hip_faster_in_every_case=all(r["torch_over_hip"] > 1.0 for r in results))
 
 
 if __name__ == "__main__":

@@ -18,20 +18,13 @@ Two cases, everything already on the device, a textured image (a random 24 x 32 
     python scripts/bench_patch_fill.py [--iters 10] [--warmup 2] [--case frame] [--parent-lib PATH] [--no-eager]
     python scripts/bench_patch_fill.py --job patch --case frame --iters 3      # the body of a rocprofv3 --kernel-trace --stats run
 
-Time: device events around one call, per iteration; every iteration runs patch, smooth, patch, smooth: the two series of the same
-code give the run-to-run spread.
+Time: featurebench.events per call; every iteration runs patch, smooth, patch, smooth.
 """
 from __future__ import annotations
 
-import argparse
 import ctypes
-import json
-import os
-import statistics
-import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import featurebench as fb
 
 CASES = ("frame", "clip")
 RADIUS, ITERS, SEED = 3, 4, 0
@@ -225,70 +218,44 @@ def parent_series(job, parent_lib, iters, warmup):
     ws = torch.empty(_cabi.fill_ws_bytes(b, h, w, c), dtype=torch.uint8, device=dev)
     out = torch.empty_like(img)
     d = _cabi.LpFillDesc(b, h, w, c, mask.shape[0], 0, img.data_ptr(), mask.data_ptr(), out.data_ptr(), ws.data_ptr(), ws.numel())
-    order = ("this_a", "parent_a", "this_b", "parent_b")
-    rec = {k: [] for k in order}
-    for i in range(warmup + iters):
-        for k in order:
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            rc = libs[k[:-2]].lp_mask_fill(ctypes.byref(d), raw_stream(dev))
-            e1.record()
-            e1.synchronize()
-            assert rc == 0, rc
-            if i >= warmup:
-                rec[k].append(e0.elapsed_time(e1))
-    med = statistics.median
+
+    def entry(lib):
+        rc = lib.lp_mask_fill(ctypes.byref(d), raw_stream(dev))
+        assert rc == 0, rc
+    ours, theirs = (lambda lib=lib: entry(lib) for lib in (libs["this"], libs["parent"]))
+    rec = fb.series([("this_a", ours), ("parent_a", theirs), ("this_b", ours), ("parent_b", theirs)], iters, warmup)
+    med = fb.median
     this, parent = med(rec["this_a"] + rec["this_b"]), med(rec["parent_a"] + rec["parent_b"])
     return {"this_ms": round(this, 4), "parent_ms": round(parent, 4), "this_over_parent": round(this / parent, 4),
-            "this_spread": round(abs(med(rec["this_a"]) - med(rec["this_b"])) / this, 4),
-            "parent_spread": round(abs(med(rec["parent_a"]) - med(rec["parent_b"])) / parent, 4),
-            "this_min_max_ms": [round(min(rec["this_a"] + rec["this_b"]), 4), round(max(rec["this_a"] + rec["this_b"]), 4)],
-            "parent_min_max_ms": [round(min(rec["parent_a"] + rec["parent_b"]), 4), round(max(rec["parent_a"] + rec["parent_b"]), 4)]}
-
-
-def timed(fn, job):
-    import torch
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    out = fn(job)
-    e1.record()
-    e1.synchronize()
-    del out
-    return e0.elapsed_time(e1)
+            "this_spread": fb.spread(rec["this_a"], rec["this_b"]),
+            "parent_spread": fb.spread(rec["parent_a"], rec["parent_b"]),
+            "this_min_max_ms": fb.summary(rec["this_a"] + rec["this_b"])[1],
+            "parent_min_max_ms": fb.summary(rec["parent_a"] + rec["parent_b"])[1]}
 
 
 def measure(case, dev, iters, warmup, eager, parent_lib):
     import torch
     from lanpaint_amd import fill
     job = make_job(case, dev)
-    fns = [("patch_a", patch_job), ("smooth_a", smooth_job), ("patch_b", patch_job), ("smooth_b", smooth_job)]
-    for _ in range(warmup):
-        for _, fn in fns:
-            fn(job)
-    torch.cuda.synchronize()
-    rec = {tag: [] for tag, _ in fns}
-    for _ in range(iters):
-        for tag, fn in fns:
-            rec[tag].append(timed(fn, job))
-    med = statistics.median
+    run_patch, run_smooth, run_eager = (lambda f=f: f(job) for f in (patch_job, smooth_job, eager_job))
+    rec = fb.series([("patch_a", run_patch), ("smooth_a", run_smooth), ("patch_b", run_patch), ("smooth_b", run_smooth)], iters, warmup)
+    med = fb.median
     patch, smooth = med(rec["patch_a"] + rec["patch_b"]), med(rec["smooth_a"] + rec["smooth_b"])
     got = patch_job(job)
     hole = job["mask"] > 0.5
     res = {"case": case, "image": list(job["image"].shape), "levels": fill.patch_levels(*job["image"].shape[1:3], RADIUS),
            "hole_pixels": int(hole.sum()),
            "patch_ms": round(patch, 3), "smooth_ms": round(smooth, 4), "patch_over_smooth": round(patch / smooth, 1),
-           "patch_min_max_ms": [round(min(rec["patch_a"] + rec["patch_b"]), 3), round(max(rec["patch_a"] + rec["patch_b"]), 3)],
-           "patch_spread": round(abs(med(rec["patch_a"]) - med(rec["patch_b"])) / patch, 4),
-           "smooth_spread": round(abs(med(rec["smooth_a"]) - med(rec["smooth_b"])) / smooth, 4),
-           "changed_from_smooth": int((got != smooth_job(job)).sum())}
+           "patch_min_max_ms": fb.summary(rec["patch_a"] + rec["patch_b"], 3)[1],
+           "patch_spread": fb.spread(rec["patch_a"], rec["patch_b"]),
+           "smooth_spread": fb.spread(rec["smooth_a"], rec["smooth_b"]),
+           "changed_from_smooth": fb.differing(got, smooth_job(job))}
     if eager:
-        eager_job(job)
-        torch.cuda.synchronize()
-        times = [timed(eager_job, job) for _ in range(max(2, iters // 4))]
+        times = fb.series([("eager", run_eager)], max(2, iters // 4), 1)["eager"]
         want = eager_job(job)
         res.update({"eager_ms": round(med(times), 2), "eager_over_patch": round(med(times) / patch, 1),
-                    "elements_differing_from_eager": int((got.view(torch.int32) != want.view(torch.int32)).sum()),
-                    "codes_differing_from_eager": int((torch.floor(got * 255.0 + 0.5) != torch.floor(want * 255.0 + 0.5)).sum())})
+                    "elements_differing_from_eager": fb.differing(got.view(torch.int32), want.view(torch.int32)),
+                    "codes_differing_from_eager": fb.differing(torch.floor(got * 255.0 + 0.5), torch.floor(want * 255.0 + 0.5))})
         del want
     if parent_lib:
         res["push_pull_vs_parent"] = parent_series(job, parent_lib, max(iters, 20), warmup)
@@ -296,33 +263,24 @@ def measure(case, dev, iters, warmup, eager, parent_lib):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--iters", type=int, default=10)
-    ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--case", choices=CASES, help="this case only")
-    ap.add_argument("--job", choices=("patch", "smooth", "eager"), help="run this side only and print nothing (a profiler run's body)")
+    ap = fb.parser(CASES, ("patch", "smooth", "eager"))
     ap.add_argument("--no-eager", action="store_true", help="leave the torch-operator side out")
     ap.add_argument("--parent-lib", help="another build of liblanpaint_hip.so to time lp_mask_fill's push-pull form against")
     a = ap.parse_args()
+    dev = fb.device()
     import torch
-    if not torch.cuda.is_available():
-        raise SystemExit("bench_patch_fill.py needs a HIP device")
-    dev = torch.device("cuda", 0)
     cases = (a.case,) if a.case else CASES
     if a.job:
         fn = {"patch": patch_job, "smooth": smooth_job, "eager": eager_job}[a.job]
         for case in cases:
             job = make_job(case, dev)
-            for _ in range(a.warmup + a.iters):
-                fn(job)
-            torch.cuda.synchronize()
+            fb.untimed(lambda: fn(job), a.warmup + a.iters)
         return
     results = []
     for case in cases:
         results.append(measure(case, dev, a.iters, a.warmup, not a.no_eager, a.parent_lib))
         torch.cuda.empty_cache()
-    print(json.dumps({"metric": "patch_fill", "unit": "ms", "iters": a.iters, "warmup": a.warmup, "radius": RADIUS, "patch_iters": ITERS,
-                      "device": torch.cuda.get_device_name(0), "cases": results}, separators=(",", ":")))
+    fb.emit("patch_fill", a, results, radius=RADIUS, patch_iters=ITERS)
 
 
 if __name__ == "__main__":

@@ -7,7 +7,7 @@ Two workloads at the default parameters (levels 4, search 2, smooth 8), key fram
     square  16 frames of 1024 x 1024 x 3, the same
 
     whole     propagate.propagate_masks: the luma pyramids per chunk of frames, the key mask, then F - 1 dependent steps of
-              2 levels + 1 launches each.  Timed with a host clock around the call and a device synchronise, and with device events.
+              2 levels + 1 launches each.  Timed with featurebench.wall, and with featurebench.events.
     stages    every entry on its own, on the buffers of the clip's first step: lp_prop_luma (all frames), lp_prop_key_mask,
               lp_prop_match and lp_prop_fill per level, lp_prop_advance; `reps` back-to-back calls between two device events.
     launches  counted by wrapping the module's launch(): per call and per step.
@@ -22,15 +22,7 @@ Two workloads at the default parameters (levels 4, search 2, smooth 8), key fram
 """
 from __future__ import annotations
 
-import argparse
-import json
-import os
-import statistics
-import sys
-import time
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import featurebench as fb
 
 CASES = {"clip": (81, 720, 1280), "square": (16, 1024, 1024)}
 LEVELS, SEARCH, SMOOTH = 4, 2, 8
@@ -213,101 +205,58 @@ def torch_propagate(images, mask, levels=LEVELS, search=SEARCH, smooth=SMOOTH):
     return torch.stack(out)
 
 
-# ---- timing ------------------------------------------------------------------------------------------------------------------------------
-def events(fn, reps=1):
-    import torch
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(reps):
-        out = fn()
-    e1.record()
-    e1.synchronize()
-    del out
-    return e0.elapsed_time(e1) / reps
-
-
-def wall(fn):
-    import torch
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    out = fn()
-    torch.cuda.synchronize()
-    del out
-    return (time.perf_counter() - t0) * 1e3
-
-
-def count_launches(fn, *modules):
-    """The entry names `fn` launches from `modules` (lanpaint_amd.propagate when none is named) and from the motion layer they
-    share, in call order: every module binds `launch` by name, so each one's own name is wrapped."""
-    from lanpaint_amd import _motion, propagate
-    real = {m: m.launch for m in (*(modules or (propagate,)), _motion)}
-    names = []
-    for m, f in real.items():
-        m.launch = lambda entry, *a, f=f: (names.append(entry), f(entry, *a))[1]
-    try:
-        fn()
-    finally:
-        for m, f in real.items():
-            m.launch = f
-    return names
-
-
+# ---- measurements ------------------------------------------------------------------------------------------------------------------------
 def stage_times(job, reps):
     """Every entry alone on the first step's buffers: ms per call, and its count in a whole call."""
     import torch
     from lanpaint_amd import _cabi, propagate
     F, H, W = job["shape"]
-    med = statistics.median
+    med = fb.median
     out = {}
-    out["luma_all_frames"] = med([events(lambda: propagate.luma_pyramids(job["images"], LEVELS)) for _ in range(3)])
+    out["luma_all_frames"] = med([fb.events(lambda: propagate.luma_pyramids(job["images"], LEVELS)) for _ in range(3)])
     pyr = propagate.luma_pyramids(job["images"][:2], LEVELS)
-    out["key_mask"] = events(lambda: propagate.key_mask(job["mask"], LEVELS), reps)
+    out["key_mask"] = fb.events(lambda: propagate.key_mask(job["mask"], LEVELS), reps)
     mpyr, _ = propagate.key_mask(job["mask"], LEVELS)
     step = propagate.Step(H, W, LEVELS, SEARCH, SMOOTH, job["images"].device)
     step.field_of(pyr[0], pyr[1], mpyr)
     torch.cuda.synchronize()
     for lv in range(LEVELS - 1, -1, -1):
         parent = None if lv == LEVELS - 1 else step.field[lv + 1]
-        out[f"match_level{lv}"] = events(lambda: propagate.match_level(pyr[0], pyr[1], mpyr, H, W, LEVELS, lv, SEARCH, SMOOTH, parent,
-                                                                       step.raw[lv], step.valid[lv]), reps)
-        out[f"fill_level{lv}"] = events(lambda: propagate.fill_median(step.raw[lv], step.valid[lv], step.field[lv]), reps)
+        out[f"match_level{lv}"] = fb.events(lambda: propagate.match_level(pyr[0], pyr[1], mpyr, H, W, LEVELS, lv, SEARCH, SMOOTH, parent,
+                                                                          step.raw[lv], step.valid[lv]), reps)
+        out[f"fill_level{lv}"] = fb.events(lambda: propagate.fill_median(step.raw[lv], step.valid[lv], step.field[lv]), reps)
     key_bits = propagate.level_view(mpyr, H, W, 0)[0]
     o = torch.empty((H, W), dtype=torch.float32, device=key_bits.device)
-    out["advance"] = events(lambda: propagate.advance(step.field[0], step.pos[1], key_bits, LEVELS, step.pos[0], o, step.mpyr[0]), reps)
+    out["advance"] = fb.events(lambda: propagate.advance(step.field[0], step.pos[1], key_bits, LEVELS, step.pos[0], o, step.mpyr[0]), reps)
     per_step = sum(v for k, v in out.items() if k.startswith(("match", "fill", "advance")))
     chunks = -(-F * (_cabi.prop_pyramid_ws_bytes(1, H, W, LEVELS)) // propagate.WS_CAP_BYTES)
     return out, per_step, out["luma_all_frames"] + out["key_mask"] + (F - 1) * per_step, chunks
 
 
 def measure(job, iters, warmup, torch_frames, reps):
-    import torch
     from lanpaint_amd import propagate
     F, H, W = job["shape"]
     call = lambda: propagate.propagate_masks(job["images"], job["mask"], 0, LEVELS, SEARCH, SMOOTH)    # noqa: E731
-    names = count_launches(call)
+    names = fb.count_launches(call)
     got = call()
     inter = ((got[-1] >= 0.5) & job["truth"]).sum().item()
     union = ((got[-1] >= 0.5) | job["truth"]).sum().item()
-    again = int((call() != got).sum())
+    again = fb.differing(call(), got)
     n = min(torch_frames, F)
     eager = torch_propagate(job["images"][:n], job["mask"])
-    differing = int((eager != propagate.propagate_masks(job["images"][:n], job["mask"], 0, LEVELS, SEARCH, SMOOTH)).sum())
+    differing = fb.differing(eager, propagate.propagate_masks(job["images"][:n], job["mask"], 0, LEVELS, SEARCH, SMOOTH))
     del eager
-    for _ in range(warmup):
-        call()
-    torch.cuda.synchronize()
-    walls, evs, torch_ms, small_ms = [], [], [], []
-    for _ in range(iters):
-        walls.append(wall(call))
-        evs.append(events(call))
-        torch_ms.append(wall(lambda: torch_propagate(job["images"][:n], job["mask"])))
-        small_ms.append(wall(lambda: propagate.propagate_masks(job["images"][:n], job["mask"], 0, LEVELS, SEARCH, SMOOTH)))
+    fb.untimed(call, warmup)
+    s = fb.series([("wall", call, fb.wall), ("events", call),
+                   ("torch", lambda: torch_propagate(job["images"][:n], job["mask"]), fb.wall),
+                   ("small", lambda: propagate.propagate_masks(job["images"][:n], job["mask"], 0, LEVELS, SEARCH, SMOOTH), fb.wall)], iters, 0)
+    walls, evs, torch_ms, small_ms = s["wall"], s["events"], s["torch"], s["small"]
     stages, per_step, busy, chunks = stage_times(job, reps)
-    med = statistics.median
+    med = fb.median
     whole = med(walls)
     per = {k: names.count(k) for k in sorted(set(names))}
     return {"case": job["case"], "frames_height_width": [F, H, W], "levels": LEVELS, "search": SEARCH, "smooth": SMOOTH,
-            "whole_wall_ms": round(whole, 3), "whole_wall_min_max_ms": [round(min(walls), 3), round(max(walls), 3)],
+            "whole_wall_ms": round(whole, 3), "whole_wall_min_max_ms": fb.summary(walls, 3)[1],
             "whole_events_ms": round(med(evs), 3), "ms_per_frame": round(whole / F, 4),
             "launches_per_call": len(names), "launches_by_entry": per,
             "launches_per_step": (per.get("lp_prop_match", 0) + per.get("lp_prop_fill", 0) + per.get("lp_prop_advance", 0)) // max(F - 1, 1),
@@ -320,33 +269,24 @@ def measure(job, iters, warmup, torch_frames, reps):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--iters", type=int, default=5)
-    ap.add_argument("--warmup", type=int, default=1)
+    ap = fb.parser(CASES, ("whole",), iters=5, warmup=1)
     ap.add_argument("--reps", type=int, default=50, help="back-to-back calls per stage timing")
     ap.add_argument("--torch-frames", type=int, default=4)
-    ap.add_argument("--case", choices=tuple(CASES), help="this workload only")
-    ap.add_argument("--job", choices=("whole",), help="run the whole call only and print nothing (a profiler run's body)")
     a = ap.parse_args()
+    dev = fb.device()
     import torch
-    if not torch.cuda.is_available():
-        raise SystemExit("bench_propagate.py needs a HIP device")
     from lanpaint_amd import propagate
-    dev = torch.device("cuda", 0)
     results = []
     for case in ((a.case,) if a.case else tuple(CASES)):
         job = make_job(case, dev)
         if a.job:
-            for _ in range(a.warmup + a.iters):
-                propagate.propagate_masks(job["images"], job["mask"], 0, LEVELS, SEARCH, SMOOTH)
-            torch.cuda.synchronize()
+            fb.untimed(lambda: propagate.propagate_masks(job["images"], job["mask"], 0, LEVELS, SEARCH, SMOOTH), a.warmup + a.iters)
         else:
             results.append(measure(job, a.iters, a.warmup, a.torch_frames, a.reps))
         del job
         torch.cuda.empty_cache()
     if not a.job:
-        print(json.dumps({"metric": "mask_propagate", "unit": "ms", "iters": a.iters, "warmup": a.warmup,
-                          "device": torch.cuda.get_device_name(0), "cases": results}, separators=(",", ":")))
+        fb.emit("mask_propagate", a, results)
 
 
 if __name__ == "__main__":

@@ -8,11 +8,11 @@ everything already on the device:
     square  16 frames of 1024 x 1024 x 3
 
     whole     propagate_anchored.propagate_masks_anchored against propagate.propagate_masks on the same clip in the same process,
-              alternating, each with a host clock around the call and a device synchronise.  Their ratio is the figure that
+              alternating, each with featurebench.wall.  Their ratio is the figure that
               matters; from the launch counts (2 levels + 4 against 2 levels + 1 a step) one would guess 12 / 9.
     launches  the entry names of one step of either form, counted from the modules' own launches.
-    stages    lp_prop_anchor_match alone on the buffers of the clip's first step, `reps` back-to-back calls between two device
-              events, next to the step's other launches timed the same way.
+    stages    lp_prop_anchor_match alone on the buffers of the clip's first step, featurebench.events over `reps` back-to-back
+              calls, next to the step's other launches timed the same way.
     drift     the last frame's IoU of both forms against the truth on a clip of the same size built as tests/anchor_clips.py
               builds its own: a textured disc that moves (0.23, 0.61) pixel per frame over a still textured background, bilinear
               sampling, Gaussian noise of 0.01.  This is the clip the form is for; the timed clip's disc moves by whole pixels.
@@ -21,17 +21,9 @@ everything already on the device:
 """
 from __future__ import annotations
 
-import argparse
-import json
-import os
-import statistics
-import sys
+import featurebench as fb
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "scripts"))
-
-import bench_propagate as base                                        # noqa: E402  the clip and the timers
+import bench_propagate as base  # the clip
 
 LEVELS, SEARCH, SMOOTH, ANCHOR = base.LEVELS, base.SEARCH, base.SMOOTH, 2
 
@@ -95,53 +87,46 @@ def stage_times(job, reps):
     step.field_of(pyr[0], pyr[1], mpyr)
     for lv in range(LEVELS - 1, -1, -1):
         parent = None if lv == LEVELS - 1 else step.field[lv + 1]
-        out[f"match_level{lv}"] = base.events(lambda: propagate.match_level(pyr[0], pyr[1], mpyr, H, W, LEVELS, lv, SEARCH, SMOOTH, parent,
+        out[f"match_level{lv}"] = fb.events(lambda: propagate.match_level(pyr[0], pyr[1], mpyr, H, W, LEVELS, lv, SEARCH, SMOOTH, parent,
                                                                             step.raw[lv], step.valid[lv]), reps)
-        out[f"fill_level{lv}"] = base.events(lambda: propagate.fill_median(step.raw[lv], step.valid[lv], step.field[lv]), reps)
+        out[f"fill_level{lv}"] = fb.events(lambda: propagate.fill_median(step.raw[lv], step.valid[lv], step.field[lv]), reps)
     key_bits = propagate.level_view(mpyr, H, W, 0)[0]
-    out["advance"] = base.events(lambda: propagate.advance(step.field[0], None, key_bits, LEVELS, step.raw_pos, step.code, step.raw_mpyr), reps)
+    out["advance"] = fb.events(lambda: propagate.advance(step.field[0], None, key_bits, LEVELS, step.raw_pos, step.code, step.raw_mpyr), reps)
     luma_t, luma_k = (propagate.level_view(pyr[i:i + 1], H, W, 0)[0] for i in (1, 0))
     bits = propagate.level_view(step.raw_mpyr, H, W, 0)[0]
     vec, valid = (torch.empty_like(t) for t in (step.raw[0], step.valid[0]))
-    out["anchor_match"] = base.events(lambda: pa.anchor_field(step.raw_pos, luma_t, luma_k, bits, ANCHOR, SMOOTH, vec, valid), reps)
+    out["anchor_match"] = fb.events(lambda: pa.anchor_field(step.raw_pos, luma_t, luma_k, bits, ANCHOR, SMOOTH, vec, valid), reps)
     e = torch.empty_like(step.field[0])
-    out["anchor_fill"] = base.events(lambda: propagate.fill_median(vec, valid, e), reps)
+    out["anchor_fill"] = fb.events(lambda: propagate.fill_median(vec, valid, e), reps)
     o = torch.empty((H, W), dtype=torch.float32, device=bits.device)
-    out["anchor_advance"] = base.events(lambda: propagate.advance(e, step.raw_pos, key_bits, LEVELS, step.pos[0], o, step.mpyr[0]), reps)
+    out["anchor_advance"] = fb.events(lambda: propagate.advance(e, step.raw_pos, key_bits, LEVELS, step.pos[0], o, step.mpyr[0]), reps)
     torch.cuda.synchronize()
     return out, int(valid.sum()), valid.numel()
 
 
 def measure(job, iters, warmup, reps):
-    import torch
     from lanpaint_amd import propagate, propagate_anchored as pa
     F, H, W = job["shape"]
     new = lambda: pa.propagate_masks_anchored(job["images"], job["mask"], 0, LEVELS, SEARCH, SMOOTH, ANCHOR)      # noqa: E731
     old = lambda: propagate.propagate_masks(job["images"], job["mask"], 0, LEVELS, SEARCH, SMOOTH)               # noqa: E731
     got, plain = new(), old()
-    differing_again = int((new() != got).sum())
+    differing_again = fb.differing(new(), got)
     skip = ("lp_prop_luma", "lp_prop_key_mask")
     small = job["images"][:2]
-    step_new = [n for n in base.count_launches(lambda: pa.propagate_masks_anchored(small, job["mask"], 0, LEVELS, SEARCH, SMOOTH, ANCHOR),
+    step_new = [n for n in fb.count_launches(lambda: pa.propagate_masks_anchored(small, job["mask"], 0, LEVELS, SEARCH, SMOOTH, ANCHOR),
                                                pa, propagate) if n not in skip]
-    step_old = [n for n in base.count_launches(lambda: propagate.propagate_masks(small, job["mask"], 0, LEVELS, SEARCH, SMOOTH)) if n not in skip]
+    step_old = [n for n in fb.count_launches(lambda: propagate.propagate_masks(small, job["mask"], 0, LEVELS, SEARCH, SMOOTH)) if n not in skip]
     truth = job["truth"]
     ious = {"anchored_last_iou": round(iou(got[-1] >= 0.5, truth), 4), "plain_last_iou": round(iou(plain[-1] >= 0.5, truth), 4),
-            "elements_differing_from_plain": int((got != plain).sum())}
+            "elements_differing_from_plain": fb.differing(got, plain)}
     del got, plain
-    for _ in range(warmup):
-        new()
-        old()
-    torch.cuda.synchronize()
-    new_ms, old_ms = [], []
-    for _ in range(iters):                                            # alternating: the two share whatever else the host does
-        new_ms.append(base.wall(new))
-        old_ms.append(base.wall(old))
+    # alternating: the two share whatever else the host does
+    new_ms, old_ms = fb.series([("new", new), ("old", old)], iters, warmup, timer=fb.wall).values()
     stages, valid, blocks = stage_times(job, reps)
-    med = statistics.median
+    med = fb.median
     return {"case": job["case"], "frames_height_width": [F, H, W], "levels": LEVELS, "search": SEARCH, "smooth": SMOOTH, "anchor": ANCHOR,
-            "anchored_wall_ms": round(med(new_ms), 3), "anchored_wall_min_max_ms": [round(min(new_ms), 3), round(max(new_ms), 3)],
-            "plain_wall_ms": round(med(old_ms), 3), "plain_wall_min_max_ms": [round(min(old_ms), 3), round(max(old_ms), 3)],
+            "anchored_wall_ms": round(med(new_ms), 3), "anchored_wall_min_max_ms": fb.summary(new_ms, 3)[1],
+            "plain_wall_ms": round(med(old_ms), 3), "plain_wall_min_max_ms": fb.summary(old_ms, 3)[1],
             "anchored_over_plain": round(med(new_ms) / med(old_ms), 3),
             "launches_per_step": [len(step_new), len(step_old)], "step_entries": step_new,
             "stage_ms": {k: round(v, 5) for k, v in stages.items()}, "stage_reps": reps,
@@ -151,17 +136,12 @@ def measure(job, iters, warmup, reps):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--iters", type=int, default=5)
-    ap.add_argument("--warmup", type=int, default=1)
+    ap = fb.parser(base.CASES, iters=5, warmup=1)
     ap.add_argument("--reps", type=int, default=50, help="back-to-back calls per stage timing")
-    ap.add_argument("--case", choices=tuple(base.CASES), help="this workload only")
     ap.add_argument("--no-drift", action="store_true", help="skip the sub-pixel clip's IoU pair")
     a = ap.parse_args()
+    dev = fb.device()
     import torch
-    if not torch.cuda.is_available():
-        raise SystemExit("bench_propagate_anchored.py needs a HIP device")
-    dev = torch.device("cuda", 0)
     results = []
     for case in ((a.case,) if a.case else tuple(base.CASES)):
         job = base.make_job(case, dev)
@@ -172,8 +152,7 @@ def main():
             r["subpixel_clip"] = drift(case, dev)
             torch.cuda.empty_cache()
         results.append(r)
-    print(json.dumps({"metric": "mask_propagate_anchored", "unit": "ms", "iters": a.iters, "warmup": a.warmup,
-                      "device": torch.cuda.get_device_name(0), "cases": results}, separators=(",", ":")))
+    fb.emit("mask_propagate_anchored", a, results)
 
 
 if __name__ == "__main__":

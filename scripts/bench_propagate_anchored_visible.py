@@ -8,12 +8,12 @@ occlusion 16), key frame 0, everything already on the device:
     square  16 frames of 1024 x 1024 x 3
 
     whole     propagate_masks_anchored_visible against propagate_masks_anchored and propagate_masks_visible on the same clip in
-              the same process, alternating, each with a host clock around the call and a device synchronise, medians.  From the
+              the same process, alternating, each with featurebench.wall, medians.  From the
               launch counts (2 levels + 6 against 2 levels + 4 and 2 levels + 3 a step) one would guess the anchored call plus the
               visible form's two launches a step.
     launches  the entry names of one step, counted from the modules' own launches.
     gate      lp_prop_anchor_match_gated alone against lp_prop_anchor_match alone on the buffers of the clip's first step,
-              `reps` back-to-back calls between two device events, alternating `rounds` times, medians; the blocks the gate shut.
+              featurebench.events over `reps` back-to-back calls, alternating `rounds` times, medians; the blocks the gate shut.
               --launches-only makes these launches and nothing else to time, at anchor 2 and 7, for a kernel trace of its own.
     torch     the same rule in torch operators on the first `--torch-frames` frames: its time, the module's on the same frames,
               and the number of elements in which the two differ, which must be 0.
@@ -25,19 +25,13 @@ occlusion 16), key frame 0, everything already on the device:
 """
 from __future__ import annotations
 
-import argparse
 import json
-import os
-import statistics
-import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "scripts"))
+import featurebench as fb
 
-import bench_propagate as base                                        # noqa: E402  the clip, the plain rule in torch, the timers
-import bench_propagate_anchored as anchored                           # noqa: E402  the sub-pixel clip
-import bench_propagate_visible as visible                             # noqa: E402  the visible rule in torch
+import bench_propagate as base  # the clip, the plain rule in torch
+import bench_propagate_anchored as anchored  # the sub-pixel clip
+import bench_propagate_visible as visible  # the visible rule in torch
 
 LEVELS, SEARCH, SMOOTH, ANCHOR, OCCLUSION = base.LEVELS, base.SEARCH, base.SMOOTH, 2, 16
 
@@ -122,14 +116,9 @@ def gate_times(job, reps, rounds, anchor=ANCHOR):
     gated_fn = lambda: pav.gated_anchor_field(step.raw_pos, luma_t, luma_k, bits, anchor, SMOOTH, OCCLUSION, step.raw[0],   # noqa: E731
                                               step.valid[0], step.gated)
     plain_fn = lambda: pa.anchor_field(step.raw_pos, luma_t, luma_k, bits, anchor, SMOOTH, raw, valid)                      # noqa: E731
-    gated_fn(), plain_fn()
-    gated_ms, plain_ms = [], []
-    for _ in range(rounds):
-        gated_ms.append(base.events(gated_fn, reps))
-        plain_ms.append(base.events(plain_fn, reps))
-    torch.cuda.synchronize()
+    gated_ms, plain_ms = fb.series([("gated", gated_fn), ("plain", plain_fn)], rounds, 1, timer=lambda f: fb.events(f, reps)).values()
     same = bool(torch.equal(torch.where(step.gated != 0, 0, valid), step.valid[0]))
-    return statistics.median(gated_ms), statistics.median(plain_ms), [int(step.gated.sum()), int(valid.sum()), valid.numel()], same
+    return fb.median(gated_ms), fb.median(plain_ms), [int(step.gated.sum()), int(valid.sum()), valid.numel()], same
 
 
 def occluded(case, dev):
@@ -158,7 +147,6 @@ def occluded(case, dev):
 
 
 def measure(job, iters, warmup, torch_frames, reps, rounds):
-    import torch
     from lanpaint_amd import propagate, propagate_anchored as pa, propagate_anchored_visible as pav, propagate_visible as pv
     F, H, W = job["shape"]
     images, mask = job["images"], job["mask"]
@@ -166,37 +154,29 @@ def measure(job, iters, warmup, torch_frames, reps, rounds):
     anc = lambda: pa.propagate_masks_anchored(images, mask, 0, LEVELS, SEARCH, SMOOTH, ANCHOR)                        # noqa: E731
     vis = lambda: pv.propagate_masks_visible(images, mask, 0, LEVELS, SEARCH, SMOOTH, OCCLUSION)                      # noqa: E731
     got, hid = new()
-    again = new()
-    differing_again = int((again[0] != got).sum() + (again[1] != hid).sum())
+    differing_again = fb.differing(new(), (got, hid))
     timed = {"new_last_iou": round(anchored.iou((got[-1] + hid[-1]) >= 0.5, job["truth"]), 4), "hidden_mass": round(float(hid.sum()), 1),
-             "elements_differing_from_anchored": int((got != anc()).sum())}
+             "elements_differing_from_anchored": fb.differing(got, anc())}
     n = min(torch_frames, F)
     small = lambda: pav.propagate_masks_anchored_visible(images[:n], mask, 0, LEVELS, SEARCH, SMOOTH, ANCHOR, OCCLUSION)   # noqa: E731
     eager = lambda: torch_propagate_anchored_visible(images[:n], mask)                                                     # noqa: E731
-    a, b = eager(), small()
-    differing = int((a[0] != b[0]).sum() + (a[1] != b[1]).sum())
-    del a, b, again, got, hid
+    differing = fb.differing(eager(), small())
+    del got, hid
     skip = ("lp_prop_luma", "lp_prop_key_mask")
-    step_new = [e for e in base.count_launches(lambda: pav.propagate_masks_anchored_visible(images[:2], mask, 0, LEVELS, SEARCH, SMOOTH,
+    step_new = [e for e in fb.count_launches(lambda: pav.propagate_masks_anchored_visible(images[:2], mask, 0, LEVELS, SEARCH, SMOOTH,
                                                                                              ANCHOR, OCCLUSION), pav, pa, pv, propagate)
                 if e not in skip]
-    for _ in range(warmup):
-        new(), anc(), vis()
-    torch.cuda.synchronize()
-    new_ms, anc_ms, vis_ms, torch_ms, small_ms = [], [], [], [], []
-    for _ in range(iters):                                            # alternating: the three share whatever else the host does
-        new_ms.append(base.wall(new))
-        anc_ms.append(base.wall(anc))
-        vis_ms.append(base.wall(vis))
-        torch_ms.append(base.wall(eager))
-        small_ms.append(base.wall(small))
+    # alternating: the three share whatever else the host does
+    fb.untimed(lambda: (new(), anc(), vis()), warmup)
+    s = fb.series([("new", new), ("anchored", anc), ("visible", vis), ("torch", eager), ("small", small)], iters, 0, timer=fb.wall)
+    new_ms, anc_ms, vis_ms, torch_ms, small_ms = s.values()
     gated_ms, plain_ms, blocks, same = gate_times(job, reps, rounds)
-    med = statistics.median
+    med = fb.median
     return {"case": job["case"], "frames_height_width": [F, H, W], "levels": LEVELS, "search": SEARCH, "smooth": SMOOTH, "anchor": ANCHOR,
             "occlusion": OCCLUSION,
-            "new_wall_ms": round(med(new_ms), 3), "new_wall_min_max_ms": [round(min(new_ms), 3), round(max(new_ms), 3)],
-            "anchored_wall_ms": round(med(anc_ms), 3), "anchored_wall_min_max_ms": [round(min(anc_ms), 3), round(max(anc_ms), 3)],
-            "visible_wall_ms": round(med(vis_ms), 3), "visible_wall_min_max_ms": [round(min(vis_ms), 3), round(max(vis_ms), 3)],
+            "new_wall_ms": round(med(new_ms), 3), "new_wall_min_max_ms": fb.summary(new_ms, 3)[1],
+            "anchored_wall_ms": round(med(anc_ms), 3), "anchored_wall_min_max_ms": fb.summary(anc_ms, 3)[1],
+            "visible_wall_ms": round(med(vis_ms), 3), "visible_wall_min_max_ms": fb.summary(vis_ms, 3)[1],
             "new_over_anchored": round(med(new_ms) / med(anc_ms), 3), "new_over_visible": round(med(new_ms) / med(vis_ms), 3),
             "launches_per_step": len(step_new), "step_entries": step_new,
             "gated_launch_ms": round(gated_ms, 5), "ungated_launch_ms": round(plain_ms, 5), "gated_over_ungated": round(gated_ms / plain_ms, 3),
@@ -208,21 +188,16 @@ def measure(job, iters, warmup, torch_frames, reps, rounds):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--iters", type=int, default=5)
-    ap.add_argument("--warmup", type=int, default=1)
+    ap = fb.parser(base.CASES, iters=5, warmup=1)
     ap.add_argument("--reps", type=int, default=50, help="back-to-back calls per launch timing")
     ap.add_argument("--rounds", type=int, default=7, help="alternating launch timings, of which the median is taken")
     ap.add_argument("--torch-frames", type=int, default=4)
-    ap.add_argument("--case", choices=tuple(base.CASES), help="this workload only")
     ap.add_argument("--no-occluded", action="store_true", help="skip the occluded sub-pixel clip's IoU")
     ap.add_argument("--launches-only", action="store_true",
                     help="the two launches alone at anchor 2 and 7, for a kernel trace: rocprofv3 --kernel-trace --stats -- python ...")
     a = ap.parse_args()
+    dev = fb.device()
     import torch
-    if not torch.cuda.is_available():
-        raise SystemExit("bench_propagate_anchored_visible.py needs a HIP device")
-    dev = torch.device("cuda", 0)
     results = []
     if a.launches_only:
         for case in ((a.case,) if a.case else tuple(base.CASES)):
@@ -243,8 +218,7 @@ def main():
             r["occluded_subpixel_clip"] = occluded(case, dev)
             torch.cuda.empty_cache()
         results.append(r)
-    print(json.dumps({"metric": "mask_propagate_anchored_visible", "unit": "ms", "iters": a.iters, "warmup": a.warmup,
-                      "device": torch.cuda.get_device_name(0), "cases": results}, separators=(",", ":")))
+    fb.emit("mask_propagate_anchored_visible", a, results)
     if any(r["elements_differing_from_torch"] for r in results):
         raise SystemExit("the module differs from the same rule in torch operators")
 

@@ -5,11 +5,10 @@ The `clip` (81 frames of 1280 x 720 x 3) and `square` (16 frames of 1024 x 1024 
 the default parameters, the true disc painted on every key, with three sets of keys: the two ends, the two ends and the middle,
 every 10th frame.  Everything is already on the device.
 
-    whole      propagate_keys.propagate_keys, a host clock around the call and a device synchronise: the median of `iters`
-               runs and their min..max.
+    whole      propagate_keys.propagate_keys, featurebench.wall: the median of `iters` runs and their min..max.
     launches   counted by wrapping the module's launch(): the batched entry calls, the merges, and the dependent steps (the
                longest chain).
-    edt        stabilize.signed_d2 on every gap's two stacks alone, between two device events, and its share of the whole call.
+    edt        stabilize.signed_d2 on every gap's two stacks alone, featurebench.events, and its share of the whole call.
     composed   the same result from what the single-key module already has: one propagate.propagate_masks per key on the frames
                between its neighbouring keys, stabilize.signed_d2 on the two results of a gap, and the merge in torch fp64
                operators, on the same device.  Timed the same way and compared element by element.  This is the yardstick: the
@@ -20,17 +19,9 @@ every 10th frame.  Everything is already on the device.
 """
 from __future__ import annotations
 
-import argparse
-import json
-import os
-import statistics
-import sys
+import featurebench as fb
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "scripts"))
-
-import bench_propagate as single                                       # noqa: E402
+import bench_propagate as single
 
 LEVELS, SEARCH, SMOOTH = single.LEVELS, single.SEARCH, single.SMOOTH
 KEY_SETS = {"ends": lambda F: [0, F - 1], "ends and middle": lambda F: [0, F // 2, F - 1],
@@ -87,22 +78,16 @@ def composed(images, masks, keys):
     return out
 
 
-def count_launches(fn):
-    from lanpaint_amd import propagate_keys
-    return single.count_launches(fn, propagate_keys)
-
-
 def measure(job, name, keys, iters, warmup):
-    import torch
     from lanpaint_amd import propagate_keys, stabilize
     F, H, W = job["shape"]
     masks = painted(job, keys)
     call = lambda: propagate_keys.propagate_keys(job["images"], masks, keys, LEVELS, SEARCH, SMOOTH)    # noqa: E731
     other = lambda: composed(job["images"], masks, keys)              # noqa: E731
-    names = count_launches(call)
+    names = fb.count_launches(call, propagate_keys)
     got = call()
-    differing = int((other() != got).sum())
-    again = int((call() != got).sum())
+    differing = fb.differing(other(), got)
+    again = fb.differing(call(), got)
     truth = painted(job, list(range(F))) >= 0.5
     inter = ((got >= 0.5) & truth).flatten(1).sum(1).double()
     union = ((got >= 0.5) | truth).flatten(1).sum(1).clamp(min=1).double()
@@ -110,20 +95,14 @@ def measure(job, name, keys, iters, warmup):
     del truth
     gaps = [(a, b) for a, b in zip(keys, keys[1:]) if b - a > 1]
     edt_of = lambda: [stabilize.signed_d2(got[a + 1:b]) for a, b in gaps for _ in range(2)]    # noqa: E731
-    for _ in range(warmup):
-        call(), other()
-    torch.cuda.synchronize()
-    walls, others, edts = [], [], []
-    for _ in range(iters):
-        walls.append(single.wall(call))
-        others.append(single.wall(other))
-        edts.append(single.events(edt_of))
-    med = statistics.median
+    fb.untimed(lambda: (call(), other()), warmup)
+    walls, others, edts = fb.series([("whole", call, fb.wall), ("composed", other, fb.wall), ("edt", edt_of)], iters, 0).values()
+    med = fb.median
     plan = propagate_keys.chain_plan(F, keys)
     spread = max(walls) - min(walls)
     return {"case": job["case"], "keys": name, "key_frames": keys, "frames_height_width": [F, H, W],
-            "whole_wall_ms": round(med(walls), 3), "whole_wall_min_max_ms": [round(min(walls), 3), round(max(walls), 3)],
-            "composed_wall_ms": round(med(others), 3), "composed_wall_min_max_ms": [round(min(others), 3), round(max(others), 3)],
+            "whole_wall_ms": round(med(walls), 3), "whole_wall_min_max_ms": fb.summary(walls, 3)[1],
+            "composed_wall_ms": round(med(others), 3), "composed_wall_min_max_ms": fb.summary(others, 3)[1],
             "composed_over_batched": round(med(others) / med(walls), 3),
             "batched_not_slower_beyond_spread": bool(med(walls) <= med(others) + spread),
             "elements_differing_from_composed": differing, "elements_differing_between_two_calls": again,
@@ -135,18 +114,12 @@ def measure(job, name, keys, iters, warmup):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--iters", type=int, default=5)
-    ap.add_argument("--warmup", type=int, default=1)
-    ap.add_argument("--case", choices=tuple(single.CASES), help="this workload only")
+    ap = fb.parser(single.CASES, ("whole",), iters=5, warmup=1)
     ap.add_argument("--keys", choices=tuple(KEY_SETS), help="this set of keys only")
-    ap.add_argument("--job", choices=("whole",), help="run the whole call only and print nothing (a profiler run's body)")
     a = ap.parse_args()
+    dev = fb.device()
     import torch
-    if not torch.cuda.is_available():
-        raise SystemExit("bench_propagate_keys.py needs a HIP device")
     from lanpaint_amd import propagate_keys
-    dev = torch.device("cuda", 0)
     results = []
     for case in ((a.case,) if a.case else tuple(single.CASES)):
         job = single.make_job(case, dev)
@@ -155,17 +128,14 @@ def main():
             keys = KEY_SETS[name](F)
             if a.job:
                 masks = painted(job, keys)
-                for _ in range(a.warmup + a.iters):
-                    propagate_keys.propagate_keys(job["images"], masks, keys, LEVELS, SEARCH, SMOOTH)
-                torch.cuda.synchronize()
+                fb.untimed(lambda: propagate_keys.propagate_keys(job["images"], masks, keys, LEVELS, SEARCH, SMOOTH), a.warmup + a.iters)
             else:
                 results.append(measure(job, name, keys, a.iters, a.warmup))
                 torch.cuda.empty_cache()
         del job
         torch.cuda.empty_cache()
     if not a.job:
-        print(json.dumps({"metric": "mask_propagate_keys", "unit": "ms", "iters": a.iters, "warmup": a.warmup,
-                          "device": torch.cuda.get_device_name(0), "cases": results}, separators=(",", ":")))
+        fb.emit("mask_propagate_keys", a, results)
 
 
 if __name__ == "__main__":

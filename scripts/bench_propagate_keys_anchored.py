@@ -5,12 +5,12 @@ The `clip` (81 frames of 1280 x 720 x 3) and `square` (16 frames of 1024 x 1024 
 the default parameters and anchor 2, the true disc painted on the first and the last frame.  Everything is already on the device,
 and everything that is compared runs in this one process, alternating.
 
-    whole      propagate_keys_anchored.propagate_keys_anchored against propagate_keys.propagate_keys on the same input, a host
-               clock around the call and a device synchronise: the median of `iters` runs each, their min..max and the ratio.
+    whole      propagate_keys_anchored.propagate_keys_anchored against propagate_keys.propagate_keys on the same input,
+               featurebench.wall: the median of `iters` runs each, their min..max and the ratio.
     launches   counted by wrapping the modules' launch(): the batched entry calls of both, the dependent steps.
-    edt        stabilize.signed_d2 on the gap's two stacks alone, between two device events, and its share of the anchored call.
+    edt        stabilize.signed_d2 on the gap's two stacks alone, featurebench.events, and its share of the anchored call.
     batch      lp_prop_match_batch in its warped-key form with 2 and 32 jobs against as many single lp_prop_anchor_match launches
-               on the same buffers, `reps` calls back to back between two device events, alternating over `rounds`: the median
+               on the same buffers, featurebench.events over `reps` calls back to back, alternating over `rounds`: the median
                ms per call of each, and whether the two gave the same elements.
     drift      the lowest per-frame IoU with the true disc of both calls on scripts/bench_propagate_anchored.py's sub-pixel clip
                of the same size, keys on both ends (--no-drift skips it).
@@ -20,19 +20,11 @@ and everything that is compared runs in this one process, alternating.
 """
 from __future__ import annotations
 
-import argparse
-import json
-import os
-import statistics
-import sys
+import featurebench as fb
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "scripts"))
-
-import bench_propagate as single                                       # noqa: E402
-import bench_propagate_anchored as anchored                            # noqa: E402
-import bench_propagate_keys as keyed                                   # noqa: E402
+import bench_propagate as single
+import bench_propagate_anchored as anchored
+import bench_propagate_keys as keyed
 
 LEVELS, SEARCH, SMOOTH, ANCHOR = single.LEVELS, single.SEARCH, single.SMOOTH, anchored.ANCHOR
 
@@ -64,14 +56,9 @@ def batch_times(job, jobs, reps, rounds):
     d = _cabi.LpPropMatchBatchDesc(H, W, LEVELS, 0, ANCHOR, SMOOTH, jobs, _cabi.LP_PROP_MATCH_WARPED_KEY, table.ctypes.data)
     batched_fn = lambda: launch("lp_prop_match_batch", dev, ctypes.byref(d))                                # noqa: E731
     singles_fn = lambda: [pa.anchor_field(*p, ANCHOR, SMOOTH, *o) for p, o in zip(planes, outs)]           # noqa: E731
-    batched_fn(), singles_fn()
-    batched_ms, singles_ms = [], []
-    for _ in range(rounds):
-        batched_ms.append(single.events(batched_fn, reps))
-        singles_ms.append(single.events(singles_fn, reps))
-    torch.cuda.synchronize()
+    batched_ms, singles_ms = fb.series([("batched", batched_fn), ("singles", singles_fn)], rounds, 1, timer=lambda f: fb.events(f, reps)).values()
     same = all(torch.equal(a[0], b[0]) and torch.equal(a[1], b[1]) for a, b in zip(outs, b_outs))
-    return statistics.median(batched_ms), statistics.median(singles_ms), bool(same)
+    return fb.median(batched_ms), fb.median(singles_ms), bool(same)
 
 
 def drift(case, dev):
@@ -86,34 +73,28 @@ def drift(case, dev):
 
 
 def measure(job, iters, warmup, reps, rounds):
-    import torch
     from lanpaint_amd import propagate_keys as pk, propagate_keys_anchored as pka, stabilize
     F, H, W = job["shape"]
     keys = [0, F - 1]
     masks = keyed.painted(job, keys)
     new = lambda: pka.propagate_keys_anchored(job["images"], masks, keys, LEVELS, SEARCH, SMOOTH, ANCHOR)    # noqa: E731
     old = lambda: pk.propagate_keys(job["images"], masks, keys, LEVELS, SEARCH, SMOOTH)                     # noqa: E731
-    names_new, names_old = single.count_launches(new, pk), single.count_launches(old, pk)      # pka launches through pk's Chains
+    names_new, names_old = fb.count_launches(new, pk), fb.count_launches(old, pk)      # pka launches through pk's Chains
     got = new()
-    again = int((new() != got).sum())
-    off = int((pka.propagate_keys_anchored(job["images"], masks, keys, LEVELS, SEARCH, SMOOTH, 0) != old()).sum())
-    moved = int((got != old()).sum())
+    again = fb.differing(new(), got)
+    off = fb.differing(pka.propagate_keys_anchored(job["images"], masks, keys, LEVELS, SEARCH, SMOOTH, 0), old())
+    moved = fb.differing(got, old())
     edt_of = lambda: [stabilize.signed_d2(got[1:F - 1]) for _ in range(2)]                                   # noqa: E731
-    for _ in range(warmup):
-        new(), old()
-    torch.cuda.synchronize()
-    new_ms, old_ms, edts = [], [], []
-    for _ in range(iters):                                            # alternating: the two share whatever else the host does
-        new_ms.append(single.wall(new))
-        old_ms.append(single.wall(old))
-        edts.append(single.events(edt_of))
+    # alternating: the two share whatever else the host does
+    fb.untimed(lambda: (new(), old()), warmup)
+    new_ms, old_ms, edts = fb.series([("new", new, fb.wall), ("old", old, fb.wall), ("edt", edt_of)], iters, 0).values()
     del got
-    med = statistics.median
+    med = fb.median
     plan = pk.chain_plan(F, keys)
     out = {"case": job["case"], "key_frames": keys, "frames_height_width": [F, H, W], "levels": LEVELS, "search": SEARCH, "smooth": SMOOTH,
            "anchor": ANCHOR,
-           "anchored_wall_ms": round(med(new_ms), 3), "anchored_wall_min_max_ms": [round(min(new_ms), 3), round(max(new_ms), 3)],
-           "keys_wall_ms": round(med(old_ms), 3), "keys_wall_min_max_ms": [round(min(old_ms), 3), round(max(old_ms), 3)],
+           "anchored_wall_ms": round(med(new_ms), 3), "anchored_wall_min_max_ms": fb.summary(new_ms, 3)[1],
+           "keys_wall_ms": round(med(old_ms), 3), "keys_wall_min_max_ms": fb.summary(old_ms, 3)[1],
            "anchored_over_keys": round(med(new_ms) / med(old_ms), 3),
            "chains": len(plan), "dependent_steps": max(c[3] for c in plan),
            "batched_entry_calls": [sum(n.endswith("_batch") for n in names_new), sum(n.endswith("_batch") for n in names_old)],
@@ -129,29 +110,21 @@ def measure(job, iters, warmup, reps, rounds):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--iters", type=int, default=5)
-    ap.add_argument("--warmup", type=int, default=1)
+    ap = fb.parser(single.CASES, ("whole",), iters=5, warmup=1)
     ap.add_argument("--reps", type=int, default=50, help="back-to-back calls per launch timing")
     ap.add_argument("--rounds", type=int, default=7, help="alternating launch timings, of which the median is taken")
-    ap.add_argument("--case", choices=tuple(single.CASES), help="this workload only")
     ap.add_argument("--no-drift", action="store_true", help="skip the sub-pixel clip's IoU")
-    ap.add_argument("--job", choices=("whole",), help="run the whole call only and print nothing (a profiler run's body)")
     a = ap.parse_args()
+    dev = fb.device()
     import torch
-    if not torch.cuda.is_available():
-        raise SystemExit("bench_propagate_keys_anchored.py needs a HIP device")
     from lanpaint_amd import propagate_keys_anchored as pka
-    dev = torch.device("cuda", 0)
     results = []
     for case in ((a.case,) if a.case else tuple(single.CASES)):
         job = single.make_job(case, dev)
         F = job["shape"][0]
         if a.job:
             masks = keyed.painted(job, [0, F - 1])
-            for _ in range(a.warmup + a.iters):
-                pka.propagate_keys_anchored(job["images"], masks, [0, F - 1], LEVELS, SEARCH, SMOOTH, ANCHOR)
-            torch.cuda.synchronize()
+            fb.untimed(lambda: pka.propagate_keys_anchored(job["images"], masks, [0, F - 1], LEVELS, SEARCH, SMOOTH, ANCHOR), a.warmup + a.iters)
         else:
             results.append(measure(job, a.iters, a.warmup, a.reps, a.rounds))
             del job
@@ -160,8 +133,7 @@ def main():
                 results[-1]["subpixel_clip"] = drift(case, dev)
         torch.cuda.empty_cache()
     if not a.job:
-        print(json.dumps({"metric": "mask_propagate_keys_anchored", "unit": "ms", "iters": a.iters, "warmup": a.warmup,
-                          "device": torch.cuda.get_device_name(0), "cases": results}, separators=(",", ":")))
+        fb.emit("mask_propagate_keys_anchored", a, results)
 
 
 if __name__ == "__main__":

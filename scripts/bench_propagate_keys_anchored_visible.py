@@ -7,11 +7,10 @@ the default parameters, anchor 2 and occlusion 16, the true disc painted on the 
 on the device, and everything that is compared runs in this one process, alternating.
 
     whole      propagate_keys_anchored_visible against propagate_keys_visible, propagate_keys_anchored and propagate_keys on the
-               same input, a host clock around the call and a device synchronise: the median of `iters` runs each, their
-               min..max and the three ratios.
+               same input, featurebench.wall: the median of `iters` runs each, their min..max and the three ratios.
     launches   counted by wrapping the modules' launch(): the batched entry calls of the four, the dependent steps.
     batch      lp_prop_match_batch in its gated form with 2 and 32 jobs against as many single lp_prop_anchor_match_gated
-               launches on the same buffers, `reps` calls back to back between two device events, alternating over `rounds`:
+               launches on the same buffers, featurebench.events over `reps` calls back to back, alternating over `rounds`:
                the median ms per call of each, and whether the two gave the same elements.
     occluded   the whole-subject IoU (mask + hidden >= 0.5; worst frame and mean) of the new form, propagate_keys_visible and
                propagate_keys_anchored (hidden = 0) on scripts/bench_propagate_anchored.py's sub-pixel clip of the same size with
@@ -22,19 +21,11 @@ on the device, and everything that is compared runs in this one process, alterna
 """
 from __future__ import annotations
 
-import argparse
-import json
-import os
-import statistics
-import sys
+import featurebench as fb
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "scripts"))
-
-import bench_propagate as single                                       # noqa: E402
-import bench_propagate_anchored as anchored                            # noqa: E402
-import bench_propagate_keys as keyed                                   # noqa: E402
+import bench_propagate as single
+import bench_propagate_anchored as anchored
+import bench_propagate_keys as keyed
 
 LEVELS, SEARCH, SMOOTH, ANCHOR, OCCLUSION = single.LEVELS, single.SEARCH, single.SMOOTH, anchored.ANCHOR, 16
 
@@ -67,14 +58,9 @@ def batch_times(job, jobs, reps, rounds):
     d = _cabi.LpPropMatchBatchDesc(H, W, LEVELS, 0, ANCHOR, SMOOTH, jobs, _cabi.LP_PROP_MATCH_GATED(OCCLUSION), table.ctypes.data)
     batched_fn = lambda: launch("lp_prop_match_batch", dev, ctypes.byref(d))                                            # noqa: E731
     singles_fn = lambda: [pav.gated_anchor_field(*p, ANCHOR, SMOOTH, OCCLUSION, *o) for p, o in zip(planes, outs)]     # noqa: E731
-    batched_fn(), singles_fn()
-    batched_ms, singles_ms = [], []
-    for _ in range(rounds):
-        batched_ms.append(single.events(batched_fn, reps))
-        singles_ms.append(single.events(singles_fn, reps))
-    torch.cuda.synchronize()
+    batched_ms, singles_ms = fb.series([("batched", batched_fn), ("singles", singles_fn)], rounds, 1, timer=lambda f: fb.events(f, reps)).values()
     same = all(torch.equal(a[0], b[0]) and torch.equal(a[1], b[1]) for a, b in zip(outs, b_outs))
-    return statistics.median(batched_ms), statistics.median(singles_ms), bool(same), [int(outs[0][2].sum()), int(outs[0][1].sum())]
+    return fb.median(batched_ms), fb.median(singles_ms), bool(same), [int(outs[0][2].sum()), int(outs[0][1].sum())]
 
 
 def occluded(case, dev):
@@ -103,7 +89,6 @@ def occluded(case, dev):
 
 
 def measure(job, iters, warmup, reps, rounds):
-    import torch
     from lanpaint_amd import (propagate_keys as pk, propagate_keys_anchored as pka, propagate_keys_anchored_visible as pkav,
                               propagate_keys_visible as pkv)
     F, H, W = job["shape"]
@@ -114,29 +99,21 @@ def measure(job, iters, warmup, reps, rounds):
              "keys_visible": lambda: pkv.propagate_keys_visible(images, masks, keys, LEVELS, SEARCH, SMOOTH, OCCLUSION),
              "keys_anchored": lambda: pka.propagate_keys_anchored(images, masks, keys, LEVELS, SEARCH, SMOOTH, ANCHOR),
              "keys": lambda: pk.propagate_keys(images, masks, keys, LEVELS, SEARCH, SMOOTH)}
-    names = {k: single.count_launches(fn, pk) for k, fn in calls.items()}      # every form launches its steps through pk's Chains
+    names = {k: fb.count_launches(fn, pk) for k, fn in calls.items()}      # every form launches its steps through pk's Chains
     got = calls["new"]()
-    again = sum(int((a != b).sum()) for a, b in zip(calls["new"](), got))
-    off = {"anchor_0": sum(int((a != b).sum()) for a, b in zip(
-               pkav.propagate_keys_anchored_visible(images, masks, keys, LEVELS, SEARCH, SMOOTH, 0, OCCLUSION), calls["keys_visible"]())),
-           "occlusion_0": int((pkav.propagate_keys_anchored_visible(images, masks, keys, LEVELS, SEARCH, SMOOTH, ANCHOR, 0)[0]
-                               != calls["keys_anchored"]()).sum())}
+    again = fb.differing(calls["new"](), got)
+    off = {"anchor_0": fb.differing(pkav.propagate_keys_anchored_visible(images, masks, keys, LEVELS, SEARCH, SMOOTH, 0, OCCLUSION),
+                                    calls["keys_visible"]()),
+           "occlusion_0": fb.differing(pkav.propagate_keys_anchored_visible(images, masks, keys, LEVELS, SEARCH, SMOOTH, ANCHOR, 0)[0],
+                                       calls["keys_anchored"]())}
     del got
-    for _ in range(warmup):
-        for fn in calls.values():
-            fn()
-    torch.cuda.synchronize()
-    ms = {k: [] for k in calls}
-    for _ in range(iters):                                            # alternating: the four share whatever else the host does
-        for k, fn in calls.items():
-            ms[k].append(single.wall(fn))
-    med = statistics.median
+    ms = fb.series(list(calls.items()), iters, warmup, timer=fb.wall)    # alternating: the four share whatever else the host does
+    med = fb.median
     plan = pk.chain_plan(F, keys)
     out = {"case": job["case"], "key_frames": keys, "frames_height_width": [F, H, W], "levels": LEVELS, "search": SEARCH, "smooth": SMOOTH,
            "anchor": ANCHOR, "occlusion": OCCLUSION, "chains": len(plan), "dependent_steps": max(c[3] for c in plan)}
     for k in calls:
-        out[f"{k}_wall_ms"] = round(med(ms[k]), 3)
-        out[f"{k}_wall_min_max_ms"] = [round(min(ms[k]), 3), round(max(ms[k]), 3)]
+        out[f"{k}_wall_ms"], out[f"{k}_wall_min_max_ms"] = fb.summary(ms[k], 3)
         out[f"{k}_batched_entry_calls"] = sum(n.endswith("_batch") for n in names[k])
     for k in ("keys_visible", "keys_anchored", "keys"):
         out[f"new_over_{k}"] = round(med(ms["new"]) / med(ms[k]), 3)
@@ -152,29 +129,22 @@ def measure(job, iters, warmup, reps, rounds):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--iters", type=int, default=5)
-    ap.add_argument("--warmup", type=int, default=1)
+    ap = fb.parser(single.CASES, ("whole",), iters=5, warmup=1)
     ap.add_argument("--reps", type=int, default=50, help="back-to-back calls per launch timing")
     ap.add_argument("--rounds", type=int, default=7, help="alternating launch timings, of which the median is taken")
-    ap.add_argument("--case", choices=tuple(single.CASES), help="this workload only")
     ap.add_argument("--no-occluded", action="store_true", help="skip the occluded sub-pixel clip's IoU")
-    ap.add_argument("--job", choices=("whole",), help="run the whole call only and print nothing (a profiler run's body)")
     a = ap.parse_args()
+    dev = fb.device()
     import torch
-    if not torch.cuda.is_available():
-        raise SystemExit("bench_propagate_keys_anchored_visible.py needs a HIP device")
     from lanpaint_amd import propagate_keys_anchored_visible as pkav
-    dev = torch.device("cuda", 0)
     results = []
     for case in ((a.case,) if a.case else tuple(single.CASES)):
         job = single.make_job(case, dev)
         F = job["shape"][0]
         if a.job:
             masks = keyed.painted(job, [0, F - 1])
-            for _ in range(a.warmup + a.iters):
-                pkav.propagate_keys_anchored_visible(job["images"], masks, [0, F - 1], LEVELS, SEARCH, SMOOTH, ANCHOR, OCCLUSION)
-            torch.cuda.synchronize()
+            fb.untimed(lambda: pkav.propagate_keys_anchored_visible(job["images"], masks, [0, F - 1], LEVELS, SEARCH, SMOOTH, ANCHOR, OCCLUSION),
+                       a.warmup + a.iters)
         else:
             results.append(measure(job, a.iters, a.warmup, a.reps, a.rounds))
             del job
@@ -183,8 +153,7 @@ def main():
                 results[-1]["occluded_subpixel_clip"] = occluded(case, dev)
         torch.cuda.empty_cache()
     if not a.job:
-        print(json.dumps({"metric": "mask_propagate_keys_anchored_visible", "unit": "ms", "iters": a.iters, "warmup": a.warmup,
-                          "device": torch.cuda.get_device_name(0), "cases": results}, separators=(",", ":")))
+        fb.emit("mask_propagate_keys_anchored_visible", a, results)
 
 
 if __name__ == "__main__":

@@ -6,10 +6,10 @@ the bar of scripts/bench_propagate_visible.py drawn over them, at the default pa
 keys on both ends and with a third key in the middle.  Everything is already on the device.
 
     whole      propagate_keys_visible.propagate_keys_visible against propagate_keys.propagate_keys (the several-keys rule without
-               occlusion handling) on the same clip and keys in the same process, alternately: a host clock around the call and a
-               device synchronise, the median of `iters` runs and their min..max, and the ratio.
+               occlusion handling) on the same clip and keys in the same process, alternately: featurebench.wall, the median
+               of `iters` runs and their min..max, and the ratio.
     launches   counted by wrapping the modules' launch(): the entry calls by name and the dependent steps.
-    stages     the three new entries alone, between two device events, `reps` calls back to back: lp_prop_visible_batch and
+    stages     the three new entries alone, featurebench.events, `reps` calls back to back: lp_prop_visible_batch and
                lp_prop_occlude_batch with as many jobs as the call's first step has chains, on the call's own first-step buffers,
                and lp_prop_merge_visible on the first gap.  The two EDTs of the gaps alone, and their share of the call.
     checks     two calls give the same bits; the keys return their paintings; the mask pixels on the bar against the plain rule's.
@@ -19,27 +19,14 @@ keys on both ends and with a third key in the middle.  Everything is already on 
 """
 from __future__ import annotations
 
-import argparse
-import json
-import os
-import statistics
-import sys
+import featurebench as fb
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "scripts"))
-
-import bench_propagate as single                                       # noqa: E402  the timers
-import bench_propagate_keys as several                                 # noqa: E402  the paintings
-import bench_propagate_visible as visible                              # noqa: E402  the clip with the bar
+import bench_propagate as single  # the cases and parameters
+import bench_propagate_keys as several  # the paintings
+import bench_propagate_visible as visible  # the clip with the bar
 
 LEVELS, SEARCH, SMOOTH, OCCLUSION = single.LEVELS, single.SEARCH, single.SMOOTH, visible.OCCLUSION
 KEY_SETS = {"ends": lambda F: [0, F - 1], "ends and middle": lambda F: [0, F // 2, F - 1]}
-
-
-def count_launches(fn):
-    from lanpaint_amd import propagate_keys, propagate_keys_visible
-    return single.count_launches(fn, propagate_keys, propagate_keys_visible)
 
 
 def stage_times(job, masks, keys, reps):
@@ -60,10 +47,10 @@ def stage_times(job, masks, keys, reps):
     key_bits = propagate.level_view(mpyr, H, W, 0)[0]
     out = {"jobs": jobs}
     feed = [(pos, luma[1], luma[0], key_bits)] * jobs
-    out["visible_batch"] = single.events(lambda: kv.visible_flags_batch(feed, OCCLUSION), reps)
+    out["visible_batch"] = fb.events(lambda: kv.visible_flags_batch(feed, OCCLUSION), reps)
     flags = kv.visible_flags_batch(feed[:1], OCCLUSION)[0]
     counts = torch.zeros(jobs, dtype=torch.int32, device=dev)
-    out["occlude_batch"] = single.events(lambda: kv.occlude_batch([(bits, flags)] * jobs, LEVELS, counts), reps)
+    out["occlude_batch"] = fb.events(lambda: kv.occlude_batch([(bits, flags)] * jobs, LEVELS, counts), reps)
     a, b = next((a, b) for a, b in zip(keys, keys[1:]) if b - a > 1)
     n, span = b - a - 1, b - a
     code = bits[None].repeat(n, 1, 1)
@@ -71,26 +58,24 @@ def stage_times(job, masks, keys, reps):
     fl = torch.zeros((n, *_cabi.prop_grid(H, W)), dtype=torch.int32, device=dev)
     many = torch.from_numpy(np.full(span, 1000, np.int32)).to(dev)
     o, h = torch.empty_like(code), torch.empty_like(code)
-    out["merge_visible"] = single.events(lambda: kv.merge_gap_visible(q, q, code, code, code, code, fl, fl, many, many, span, 1, o, h), reps)
+    out["merge_visible"] = fb.events(lambda: kv.merge_gap_visible(q, q, code, code, code, code, fl, fl, many, many, span, 1, o, h), reps)
     out["merge_visible_frames"] = n
     lost = many.clone()
     lost[1] = 0                                                       # the forward chain lost on every frame: the pass-through branch
-    out["merge_visible_one_lost"] = single.events(lambda: kv.merge_gap_visible(q, q, code, code, code, code, fl, fl, lost, many, span, 1, o, h), reps)
+    out["merge_visible_one_lost"] = fb.events(lambda: kv.merge_gap_visible(q, q, code, code, code, code, fl, fl, lost, many, span, 1, o, h), reps)
     torch.cuda.synchronize()
     return out
 
 
 def measure(job, name, keys, iters, warmup, reps):
-    import torch
     from lanpaint_amd import propagate_keys, propagate_keys_visible as kv, stabilize
     F, H, W = job["shape"]
     masks = several.painted(job, keys)
     new = lambda: kv.propagate_keys_visible(job["images"], masks, keys, LEVELS, SEARCH, SMOOTH, OCCLUSION)    # noqa: E731
     old = lambda: propagate_keys.propagate_keys(job["images"], masks, keys, LEVELS, SEARCH, SMOOTH)          # noqa: E731
-    names = count_launches(new)
+    names = fb.count_launches(new, propagate_keys, kv)
     got, hid = new()
-    again = new()
-    differing_again = int((again[0] != got).sum() + (again[1] != hid).sum())
+    differing_again = fb.differing(new(), (got, hid))
     plain = old()
     x0, x1 = job["bar"]
     on_bar, on_bar_plain = int((got[:, :, x0:x1] >= 0.5).sum()), int((plain[:, :, x0:x1] >= 0.5).sum())
@@ -101,24 +86,19 @@ def measure(job, name, keys, iters, warmup, reps):
     union = (subject | truth).flatten(1).sum(1).clamp(min=1).double()
     iou = float((inter / union).min())
     hidden_mass = float(hid.sum())
-    del truth, subject, again, plain
+    del truth, subject, plain
     gaps = [(a, b) for a, b in zip(keys, keys[1:]) if b - a > 1]
     edt_of = lambda: [stabilize.signed_d2(got[a + 1:b]) for a, b in gaps for _ in range(2)]    # noqa: E731
-    for _ in range(warmup):
-        new(), old()
-    torch.cuda.synchronize()
-    new_ms, old_ms, edts = [], [], []
-    for _ in range(iters):                                            # alternating: the two share whatever else the host does
-        new_ms.append(single.wall(new))
-        old_ms.append(single.wall(old))
-        edts.append(single.events(edt_of))
+    # alternating: the two share whatever else the host does
+    fb.untimed(lambda: (new(), old()), warmup)
+    new_ms, old_ms, edts = fb.series([("new", new, fb.wall), ("old", old, fb.wall), ("edt", edt_of)], iters, 0).values()
     stages = stage_times(job, masks, keys, reps)
-    med = statistics.median
+    med = fb.median
     plan = propagate_keys.chain_plan(F, keys)
     steps = max((c[3] for c in plan), default=0)
     return {"case": job["case"], "keys": name, "key_frames": keys, "frames_height_width": [F, H, W], "levels": LEVELS, "occlusion": OCCLUSION,
-            "visible_wall_ms": round(med(new_ms), 3), "visible_wall_min_max_ms": [round(min(new_ms), 3), round(max(new_ms), 3)],
-            "keys_wall_ms": round(med(old_ms), 3), "keys_wall_min_max_ms": [round(min(old_ms), 3), round(max(old_ms), 3)],
+            "visible_wall_ms": round(med(new_ms), 3), "visible_wall_min_max_ms": fb.summary(new_ms, 3)[1],
+            "keys_wall_ms": round(med(old_ms), 3), "keys_wall_min_max_ms": fb.summary(old_ms, 3)[1],
             "visible_over_keys": round(med(new_ms) / med(old_ms), 3),
             "chains": len(plan), "dependent_steps": steps, "entry_calls": len(names),
             "entry_calls_by_name": {k: names.count(k) for k in sorted(set(names))},
@@ -131,19 +111,13 @@ def measure(job, name, keys, iters, warmup, reps):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--iters", type=int, default=5)
-    ap.add_argument("--warmup", type=int, default=1)
+    ap = fb.parser(single.CASES, ("whole",), iters=5, warmup=1)
     ap.add_argument("--reps", type=int, default=20, help="back-to-back calls per stage timing")
-    ap.add_argument("--case", choices=tuple(single.CASES), help="this workload only")
     ap.add_argument("--keys", choices=tuple(KEY_SETS), help="this set of keys only")
-    ap.add_argument("--job", choices=("whole",), help="run the whole call only and print nothing (a profiler run's body)")
     a = ap.parse_args()
+    dev = fb.device()
     import torch
-    if not torch.cuda.is_available():
-        raise SystemExit("bench_propagate_keys_visible.py needs a HIP device")
     from lanpaint_amd import propagate_keys_visible as kv
-    dev = torch.device("cuda", 0)
     results = []
     for case in ((a.case,) if a.case else tuple(single.CASES)):
         job = visible.make_job(case, dev)
@@ -152,17 +126,14 @@ def main():
             keys = KEY_SETS[name](F)
             if a.job:
                 masks = several.painted(job, keys)
-                for _ in range(a.warmup + a.iters):
-                    kv.propagate_keys_visible(job["images"], masks, keys, LEVELS, SEARCH, SMOOTH, OCCLUSION)
-                torch.cuda.synchronize()
+                fb.untimed(lambda: kv.propagate_keys_visible(job["images"], masks, keys, LEVELS, SEARCH, SMOOTH, OCCLUSION), a.warmup + a.iters)
             else:
                 results.append(measure(job, name, keys, a.iters, a.warmup, a.reps))
                 torch.cuda.empty_cache()
         del job
         torch.cuda.empty_cache()
     if not a.job:
-        print(json.dumps({"metric": "mask_propagate_keys_visible", "unit": "ms", "iters": a.iters, "warmup": a.warmup,
-                          "device": torch.cuda.get_device_name(0), "cases": results}, separators=(",", ":")))
+        fb.emit("mask_propagate_keys_visible", a, results)
 
 
 if __name__ == "__main__":

@@ -9,9 +9,9 @@ path, so that the occlusion test has something to find:
     square  16 frames of 1024 x 1024 x 3
 
     whole     propagate_visible.propagate_masks_visible against propagate.propagate_masks on the same clip in the same process,
-              alternating, each with a host clock around the call and a device synchronise.  Their ratio is the figure that matters.
-    stages    lp_prop_visible and lp_prop_occlude alone on the buffers of the clip's first step, `reps` back-to-back calls between
-              two device events, next to the step's other launches (match and fill per level, advance) timed the same way.
+              alternating, each with featurebench.wall.  Their ratio is the figure that matters.
+    stages    lp_prop_visible and lp_prop_occlude alone on the buffers of the clip's first step, featurebench.events over `reps`
+              back-to-back calls, next to the step's other launches (match and fill per level, advance) timed the same way.
     torch     the same rule in torch operators on the same device, compared element by element with the module's two outputs, on
               `--torch-frames` frames of the case.
 
@@ -19,17 +19,9 @@ path, so that the occlusion test has something to find:
 """
 from __future__ import annotations
 
-import argparse
-import json
-import os
-import statistics
-import sys
+import featurebench as fb
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "scripts"))
-
-import bench_propagate as base                                        # noqa: E402  the clip, the plain rule in torch, the timers
+import bench_propagate as base  # the clip, the plain rule in torch
 
 LEVELS, SEARCH, SMOOTH, OCCLUSION = base.LEVELS, base.SEARCH, base.SMOOTH, 16
 
@@ -118,23 +110,22 @@ def stage_times(job, reps):
     step.field_of(pyr[0], pyr[1], mpyr)
     for lv in range(LEVELS - 1, -1, -1):
         parent = None if lv == LEVELS - 1 else step.field[lv + 1]
-        out[f"match_level{lv}"] = base.events(lambda: propagate.match_level(pyr[0], pyr[1], mpyr, H, W, LEVELS, lv, SEARCH, SMOOTH, parent,
+        out[f"match_level{lv}"] = fb.events(lambda: propagate.match_level(pyr[0], pyr[1], mpyr, H, W, LEVELS, lv, SEARCH, SMOOTH, parent,
                                                                             step.raw[lv], step.valid[lv]), reps)
-        out[f"fill_level{lv}"] = base.events(lambda: propagate.fill_median(step.raw[lv], step.valid[lv], step.field[lv]), reps)
+        out[f"fill_level{lv}"] = fb.events(lambda: propagate.fill_median(step.raw[lv], step.valid[lv], step.field[lv]), reps)
     key_bits = propagate.level_view(mpyr, H, W, 0)[0]
     adv = lambda: propagate.advance(step.field[0], None, key_bits, LEVELS, step.pos[0], step.code, step.raw_mpyr)    # noqa: E731
-    out["advance"] = base.events(adv, reps)
+    out["advance"] = fb.events(adv, reps)
     luma_t, luma_k = (propagate.level_view(pyr[i:i + 1], H, W, 0)[0] for i in (1, 0))
     bits = propagate.level_view(step.raw_mpyr, H, W, 0)[0]
-    out["visible"] = base.events(lambda: pv.visible_flags(step.pos[0], luma_t, luma_k, bits, OCCLUSION, step.flags), reps)
+    out["visible"] = fb.events(lambda: pv.visible_flags(step.pos[0], luma_t, luma_k, bits, OCCLUSION, step.flags), reps)
     o, h = (torch.empty((H, W), dtype=torch.float32, device=bits.device) for _ in range(2))
-    out["occlude"] = base.events(lambda: pv.occlude(step.code, step.flags, LEVELS, o, h, step.mpyr[0]), reps)
+    out["occlude"] = fb.events(lambda: pv.occlude(step.code, step.flags, LEVELS, o, h, step.mpyr[0]), reps)
     torch.cuda.synchronize()
     return out, int(step.flags.sum()), step.flags.numel()
 
 
 def measure(job, iters, warmup, torch_frames, reps):
-    import torch
     from lanpaint_amd import propagate, propagate_visible as pv
     F, H, W = job["shape"]
     new = lambda: pv.propagate_masks_visible(job["images"], job["mask"], 0, LEVELS, SEARCH, SMOOTH, OCCLUSION)    # noqa: E731
@@ -143,30 +134,23 @@ def measure(job, iters, warmup, torch_frames, reps):
     plain = old()
     x0, x1 = job["bar"]
     on_bar, on_bar_plain = int((got[:, :, x0:x1] >= 0.5).sum()), int((plain[:, :, x0:x1] >= 0.5).sum())
-    again = new()
-    differing_again = int((again[0] != got).sum() + (again[1] != hid).sum())
+    differing_again = fb.differing(new(), (got, hid))
     n = min(torch_frames, F)
-    eager = torch_propagate_visible(job["images"][:n], job["mask"])
-    small = pv.propagate_masks_visible(job["images"][:n], job["mask"], 0, LEVELS, SEARCH, SMOOTH, OCCLUSION)
-    differing = int((eager[0] != small[0]).sum() + (eager[1] != small[1]).sum())
-    del eager, small, again, plain
-    for _ in range(warmup):
-        new()
-        old()
-    torch.cuda.synchronize()
-    new_ms, old_ms, torch_ms, small_ms = [], [], [], []
-    for _ in range(iters):                                            # alternating: the two share whatever else the host does
-        new_ms.append(base.wall(new))
-        old_ms.append(base.wall(old))
-        torch_ms.append(base.wall(lambda: torch_propagate_visible(job["images"][:n], job["mask"])))
-        small_ms.append(base.wall(lambda: pv.propagate_masks_visible(job["images"][:n], job["mask"], 0, LEVELS, SEARCH, SMOOTH, OCCLUSION)))
+    eager = lambda: torch_propagate_visible(job["images"][:n], job["mask"])                                                      # noqa: E731
+    small = lambda: pv.propagate_masks_visible(job["images"][:n], job["mask"], 0, LEVELS, SEARCH, SMOOTH, OCCLUSION)             # noqa: E731
+    differing = fb.differing(eager(), small())
+    del plain
+    # alternating: the two share whatever else the host does
+    fb.untimed(lambda: (new(), old()), warmup)
+    s = fb.series([("new", new), ("old", old), ("torch", eager), ("small", small)], iters, 0, timer=fb.wall)
+    new_ms, old_ms, torch_ms, small_ms = s.values()
     stages, flagged, blocks = stage_times(job, reps)
-    med = statistics.median
+    med = fb.median
     match_fill = sum(v for k, v in stages.items() if k.startswith(("match", "fill")))
     return {"case": job["case"], "frames_height_width": [F, H, W], "levels": LEVELS, "search": SEARCH, "smooth": SMOOTH,
             "occlusion": OCCLUSION, "visible_wall_ms": round(med(new_ms), 3),
-            "visible_wall_min_max_ms": [round(min(new_ms), 3), round(max(new_ms), 3)],
-            "plain_wall_ms": round(med(old_ms), 3), "plain_wall_min_max_ms": [round(min(old_ms), 3), round(max(old_ms), 3)],
+            "visible_wall_min_max_ms": fb.summary(new_ms, 3)[1],
+            "plain_wall_ms": round(med(old_ms), 3), "plain_wall_min_max_ms": fb.summary(old_ms, 3)[1],
             "visible_over_plain": round(med(new_ms) / med(old_ms), 3),
             "stage_ms": {k: round(v, 5) for k, v in stages.items()}, "stage_reps": reps,
             "new_launches_ms_per_step": round(stages["visible"] + stages["occlude"], 5),
@@ -179,25 +163,19 @@ def measure(job, iters, warmup, torch_frames, reps):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--iters", type=int, default=5)
-    ap.add_argument("--warmup", type=int, default=1)
+    ap = fb.parser(base.CASES, iters=5, warmup=1)
     ap.add_argument("--reps", type=int, default=50, help="back-to-back calls per stage timing")
     ap.add_argument("--torch-frames", type=int, default=4)
-    ap.add_argument("--case", choices=tuple(base.CASES), help="this workload only")
     a = ap.parse_args()
+    dev = fb.device()
     import torch
-    if not torch.cuda.is_available():
-        raise SystemExit("bench_propagate_visible.py needs a HIP device")
-    dev = torch.device("cuda", 0)
     results = []
     for case in ((a.case,) if a.case else tuple(base.CASES)):
         job = make_job(case, dev)
         results.append(measure(job, a.iters, a.warmup, a.torch_frames, a.reps))
         del job
         torch.cuda.empty_cache()
-    print(json.dumps({"metric": "mask_propagate_visible", "unit": "ms", "iters": a.iters, "warmup": a.warmup,
-                      "device": torch.cuda.get_device_name(0), "cases": results}, separators=(",", ":")))
+    fb.emit("mask_propagate_visible", a, results)
 
 
 if __name__ == "__main__":

@@ -17,21 +17,13 @@ Two cases at radius 8 and 32 (and the HIP side alone at 64), eps = 1e-3, everyth
     python scripts/bench_refine.py [--iters 10] [--warmup 2]
     python scripts/bench_refine.py --job hip --case frame --radius 8 --iters 10     # the body of a rocprofv3 --kernel-trace run
 
-Time: device events around one call, per iteration.  Every iteration runs hip, torch, hip, torch, clone: the two series of the
-SAME code give the run-to-run spread (relative difference of their medians).  Bytes: what the rule has to move -- the guide and
+Time: featurebench.events per call; every iteration runs hip, torch, hip, torch, clone.  Bytes: what the rule has to move -- the guide and
 the mask read, the result written, the 16 bytes per pixel of the workspace written once and read once -- over the time, and that
 rate over the clone's (one read, one write).
 """
 from __future__ import annotations
 
-import argparse
-import json
-import os
-import statistics
-import sys
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import featurebench as fb
 
 CASES = {"frame": (1, 1024, 1024, 3), "clip": (81, 720, 1280, 3)}
 RADII, HIP_ONLY_RADIUS = (8, 32), 64
@@ -115,31 +107,12 @@ def torch_job(j, r):
     return torch_refine(j["guide"], j["mask"], r, EPS)
 
 
-def timed(fn, job, r):
-    import torch
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    out = fn(job, r)
-    e1.record()
-    e1.synchronize()
-    del out
-    return e0.elapsed_time(e1)
-
-
 def run(job, r, iters, warmup, only=None):
-    import torch
-    fns = [("hip_a", hip_job), ("torch_a", torch_job), ("hip_b", hip_job), ("torch_b", torch_job), ("clone", clone)]
+    hip, eager, copy = (lambda f=f: f(job, r) for f in (hip_job, torch_job, clone))
+    fns = [("hip_a", hip), ("torch_a", eager), ("hip_b", hip), ("torch_b", eager), ("clone", copy)]
     if only:
-        fns = [(only + "_a", hip_job if only == "hip" else torch_job)]
-    for _ in range(warmup):
-        for _, fn in fns:
-            fn(job, r)
-    torch.cuda.synchronize()
-    rec = {tag: [] for tag, _ in fns}
-    for _ in range(iters):
-        for tag, fn in fns:
-            rec[tag].append(timed(fn, job, r))
-    return rec
+        fns = [(only + "_a", hip if only == "hip" else eager)]
+    return fb.series(fns, iters, warmup)
 
 
 def measure(job, r, iters, warmup):
@@ -153,7 +126,7 @@ def measure(job, r, iters, warmup):
     del got, eager, truth
     torch.cuda.empty_cache()
     s = run(job, r, iters, warmup)
-    med = statistics.median
+    med = fb.median
     need = required_bytes(case)
     hip, eager = med(s["hip_a"] + s["hip_b"]), med(s["torch_a"] + s["torch_b"])
     clone_tbs = need["clone"] / (med(s["clone"]) * 1e-3) / 1e12
@@ -161,31 +134,25 @@ def measure(job, r, iters, warmup):
     return {"case": case, "image": list(job["guide"].shape), "radius": r, "eps": EPS, "max_abs_hip_minus_torch": diff,
             "pixels_on_the_wrong_side": wrong,
             "hip_ms": round(hip, 4), "torch_ms": round(eager, 4), "torch_over_hip": round(eager / hip, 2),
-            "hip_min_max_ms": [round(min(s["hip_a"] + s["hip_b"]), 4), round(max(s["hip_a"] + s["hip_b"]), 4)],
-            "torch_min_max_ms": [round(min(s["torch_a"] + s["torch_b"]), 4), round(max(s["torch_a"] + s["torch_b"]), 4)],
-            "hip_spread": round(abs(med(s["hip_a"]) - med(s["hip_b"])) / hip, 4),
-            "torch_spread": round(abs(med(s["torch_a"]) - med(s["torch_b"])) / eager, 4),
+            "hip_min_max_ms": fb.summary(s["hip_a"] + s["hip_b"])[1],
+            "torch_min_max_ms": fb.summary(s["torch_a"] + s["torch_b"])[1],
+            "hip_spread": fb.spread(s["hip_a"], s["hip_b"]),
+            "torch_spread": fb.spread(s["torch_a"], s["torch_b"]),
             "clone_ms": round(med(s["clone"]), 4), "clone_tb_per_s": round(clone_tbs, 3), "required_bytes": need,
             "required_tb_per_s": round(rate, 3), "fraction_of_clone_rate": round(rate / clone_tbs, 3)}
 
 
 def measure_hip_only(job, r, iters, warmup):
-    s = run(job, r, iters, warmup, only="hip")["hip_a"]
-    return {"case": job["case"], "radius": r, "hip_ms": round(statistics.median(s), 4), "hip_min_max_ms": [round(min(s), 4), round(max(s), 4)]}
+    ms, low_high = fb.summary(run(job, r, iters, warmup, only="hip")["hip_a"])
+    return {"case": job["case"], "radius": r, "hip_ms": ms, "hip_min_max_ms": low_high}
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--iters", type=int, default=10)
-    ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--case", choices=tuple(CASES), help="this case only")
+    ap = fb.parser(CASES, ("hip", "torch"))
     ap.add_argument("--radius", type=int, help="this radius only")
-    ap.add_argument("--job", choices=("hip", "torch"), help="run this side only and print nothing (a profiler run's body)")
     a = ap.parse_args()
+    dev = fb.device()
     import torch
-    if not torch.cuda.is_available():
-        raise SystemExit("bench_refine.py needs a HIP device")
-    dev = torch.device("cuda", 0)
     cases = (a.case,) if a.case else tuple(CASES)
     radii = (a.radius,) if a.radius else RADII
     if a.job:
@@ -204,9 +171,7 @@ def main():
             largest.append(measure_hip_only(job, HIP_ONLY_RADIUS, a.iters, a.warmup))
         del job
         torch.cuda.empty_cache()
-    print(json.dumps({"metric": "mask_refine", "unit": "ms", "iters": a.iters, "warmup": a.warmup,
-                      "device": torch.cuda.get_device_name(0), "cases": results, "radius_64_hip_only": largest,
-                      "hip_faster_in_every_case": all(r["torch_over_hip"] > 1.0 for r in results)}, separators=(",", ":")))
+    fb.emit("mask_refine", a, results, radius_64_hip_only=largest, hip_faster_in_every_case=all(r["torch_over_hip"] > 1.0 for r in results))
 
 
 if __name__ == "__main__":

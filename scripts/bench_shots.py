@@ -7,8 +7,8 @@ with a hard cut put in: the second half of the clip is the first half's frames m
 
     whole      shots.detect_shots against three things on the same clip in the same process, alternately: propagate.luma_pyramids
                alone at the same level (the cost that was there before), temporal_fill.temporal_fill, and the same rule in torch
-               operators.  A host clock around the call and a device synchronise, the median of `iters` runs and their min..max,
-               and the ratios.  Device events around the call as well.
+               operators.  featurebench.wall, the median of `iters` runs and their min..max, and the ratios.
+               featurebench.events around the call as well.
     split      between two device events (`reps` calls back to back): the pyramids, the measuring entry (two clears, the launch for
                all frames, the fold), the deciding launch.
     torch      the same rule in torch operators on the same device, on the whole clip, compared element by element: the elements
@@ -20,18 +20,10 @@ with a hard cut put in: the second half of the clip is the first half's frames m
 """
 from __future__ import annotations
 
-import argparse
-import json
-import os
-import statistics
-import sys
+import featurebench as fb
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "scripts"))
-
-import bench_propagate as single                                       # noqa: E402  the timers, the luma and the pyramid in torch
-import bench_temporal_fill as fill                                     # noqa: E402  the workloads
+import bench_propagate as single  # the luma and the pyramid in torch
+import bench_temporal_fill as fill  # the workloads
 
 LEVEL, SEARCH, RATIO, WINDOW = 2, 2, 200, 4
 
@@ -93,9 +85,9 @@ def measure(job, iters, warmup, reps):
     old = lambda: tf.temporal_fill(images, masks, fill.LEVELS, fill.SEARCH, fill.SMOOTH, 0)              # noqa: E731
     eager = lambda: torch_detect(images, T, HI)                                                           # noqa: E731
     shot, score = new()
-    again = fill.differing(new(), (shot, score))
+    again = fb.differing(new(), (shot, score))
     t_shot, t_score = eager()
-    from_torch = {"score": int((t_score != score).sum()), "shot": int((t_shot != shot).sum())}
+    from_torch = {"score": fb.differing(t_score, score), "shot": fb.differing(t_shot, shot)}
     ranges = shots.shot_ranges(shot)
     h, w = _cabi.prop_level_shape(H, W, LEVEL)
     n = h * w
@@ -104,17 +96,12 @@ def measure(job, iters, warmup, reps):
     out = torch.empty((F - 1, 2), dtype=torch.int64, device=images.device)
     alone = lambda: shots.measure_planes(pyr[0, off:], stride, F, h, w, SEARCH, out)                      # noqa: E731
     decide = lambda: shots.shot_decide(score, n, T, HI, RATIO, WINDOW)                                   # noqa: E731
-    for _ in range(warmup):
-        new(), pyramids(), old(), eager(), alone(), decide()
-    torch.cuda.synchronize()
-    med = statistics.median
-    new_ms, pyr_ms, old_ms, torch_ms, evs = [], [], [], [], []
-    for _ in range(iters):                                            # alternating: they share whatever else the host does
-        new_ms.append(single.wall(new))
-        pyr_ms.append(single.wall(pyramids))
-        old_ms.append(single.wall(old))
-        torch_ms.append(single.wall(eager))
-        evs.append(single.events(new))
+    fb.untimed(lambda: (new(), pyramids(), old(), eager(), alone(), decide()), warmup)
+    med = fb.median
+    # alternating: they share whatever else the host does
+    s = fb.series([("new", new, fb.wall), ("pyramids", pyramids, fb.wall), ("old", old, fb.wall), ("torch", eager, fb.wall), ("events", new)],
+                  iters, 0)
+    new_ms, pyr_ms, old_ms, torch_ms, evs = s.values()
     A = score[:, 0].double() / n
     share = 50.0 * score[:, 1].double() / n
     others = torch.ones(F - 1, dtype=torch.bool, device=images.device)
@@ -123,46 +110,37 @@ def measure(job, iters, warmup, reps):
             "window": WINDOW, "level": LEVEL, "search": SEARCH, "cut_at": job["cut"], "ranges": ranges,
             "cut_pair": {"A_over_N": round(float(A[job["cut"] - 1]), 2), "share_percent": round(float(share[job["cut"] - 1]), 1)},
             "other_pairs_max": {"A_over_N": round(float(A[others].max()), 2), "share_percent": round(float(share[others].max()), 1)},
-            "detect_wall_ms": round(med(new_ms), 3), "detect_wall_min_max_ms": [round(min(new_ms), 3), round(max(new_ms), 3)],
+            "detect_wall_ms": round(med(new_ms), 3), "detect_wall_min_max_ms": fb.summary(new_ms, 3)[1],
             "detect_events_ms": round(med(evs), 3), "ms_per_frame": round(med(new_ms) / F, 4),
-            "pyramids_wall_ms": round(med(pyr_ms), 3), "pyramids_wall_min_max_ms": [round(min(pyr_ms), 3), round(max(pyr_ms), 3)],
+            "pyramids_wall_ms": round(med(pyr_ms), 3), "pyramids_wall_min_max_ms": fb.summary(pyr_ms, 3)[1],
             "detect_over_pyramids": round(med(new_ms) / med(pyr_ms), 2),
-            "fill_wall_ms": round(med(old_ms), 3), "fill_wall_min_max_ms": [round(min(old_ms), 3), round(max(old_ms), 3)],
+            "fill_wall_ms": round(med(old_ms), 3), "fill_wall_min_max_ms": fb.summary(old_ms, 3)[1],
             "detect_over_fill": round(med(new_ms) / med(old_ms), 3),
             "torch_wall_ms": round(med(torch_ms), 3), "torch_over_detect": round(med(torch_ms) / med(new_ms), 1),
             "elements_differing_from_torch": from_torch, "elements_differing_between_two_calls": again,
             "stage_reps": reps,
-            "split_ms": {"pyramids": round(single.events(pyramids, reps), 4), "measure_entry": round(single.events(alone, reps), 4),
-                         "decide_launch": round(single.events(decide, reps), 4)}}
+            "split_ms": {"pyramids": round(fb.events(pyramids, reps), 4), "measure_entry": round(fb.events(alone, reps), 4),
+                         "decide_launch": round(fb.events(decide, reps), 4)}}
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--iters", type=int, default=5)
-    ap.add_argument("--warmup", type=int, default=1)
+    ap = fb.parser(single.CASES, ("whole",), iters=5, warmup=1)
     ap.add_argument("--reps", type=int, default=50, help="back-to-back calls per stage timing")
-    ap.add_argument("--case", choices=tuple(single.CASES), help="this workload only")
-    ap.add_argument("--job", choices=("whole",), help="run the whole call only and print nothing (a profiler run's body)")
     a = ap.parse_args()
+    dev = fb.device()
     import torch
-    if not torch.cuda.is_available():
-        raise SystemExit("bench_shots.py needs a HIP device")
     from lanpaint_amd import shots
-    dev = torch.device("cuda", 0)
     results = []
     for case in ((a.case,) if a.case else tuple(single.CASES)):
         job = make_job(case, dev)
         if a.job:
-            for _ in range(a.warmup + a.iters):
-                shots.detect_shots(job["images"])
-            torch.cuda.synchronize()
+            fb.untimed(lambda: shots.detect_shots(job["images"]), a.warmup + a.iters)
         else:
             results.append(measure(job, a.iters, a.warmup, a.reps))
         del job
         torch.cuda.empty_cache()
     if not a.job:
-        print(json.dumps({"metric": "video_shot_detect", "unit": "ms", "iters": a.iters, "warmup": a.warmup,
-                          "device": torch.cuda.get_device_name(0), "cases": results}, separators=(",", ":")))
+        fb.emit("video_shot_detect", a, results)
 
 
 if __name__ == "__main__":

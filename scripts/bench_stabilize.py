@@ -18,21 +18,14 @@ Two workloads, everything already on the device, at the radius pairs (median, sm
     python scripts/bench_stabilize.py [--iters 10] [--warmup 2] [--case clip]
     python scripts/bench_stabilize.py --job temporal --case clip --iters 10      # the body of a rocprofv3 --kernel-trace run
 
-Time: device events around one call, per iteration.  Every iteration runs temporal, torch, temporal, torch, clone, edt, whole: the
-two series of the SAME code give the run-to-run spread (relative difference of their medians).  The clip's q and out together are
-597 MB and do not fit the 256 MiB Infinity Cache; the square's are 134 MB and do.
+Time: featurebench.events per call; every iteration runs temporal, torch, temporal, torch, clone, edt, whole.  The clip's q and
+out together are 597 MB and do not fit the 256 MiB Infinity Cache; the square's are 134 MB and do.
 """
 from __future__ import annotations
 
-import argparse
-import json
 import math
-import os
-import statistics
-import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import featurebench as fb
 
 CASES = {"clip": (81, 720, 1280), "square": (16, 1024, 1024)}
 PAIRS = ((1, 2), (3, 8))
@@ -83,45 +76,25 @@ def jobs(pair):
             "whole": lambda j: stabilize.stabilize_masks(j["mask"], median, smooth)}
 
 
-def timed(fn, job):
-    import torch
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    out = fn(job)
-    e1.record()
-    e1.synchronize()
-    del out
-    return e0.elapsed_time(e1)
-
-
 def run(job, pair, iters, warmup, only=None):
-    import torch
-    fn = jobs(pair)
+    fn = {name: (lambda f=f: f(job)) for name, f in jobs(pair).items()}
     order = [("temporal_a", "temporal"), ("torch_a", "torch"), ("temporal_b", "temporal"), ("torch_b", "torch"), ("clone", "clone"),
              ("edt", "edt"), ("whole", "whole")]
     if only:
         order = [(only, only)]
-    for _ in range(warmup):
-        for _, name in order:
-            fn[name](job)
-    torch.cuda.synchronize()
-    rec = {tag: [] for tag, _ in order}
-    for _ in range(iters):
-        for tag, name in order:
-            rec[tag].append(timed(fn[name], job))
-    return rec
+    return fb.series([(tag, fn[name]) for tag, name in order], iters, warmup)
 
 
 def measure(job, pair, iters, warmup):
     import torch
     fn = jobs(pair)
     got, eager = fn["temporal"](job), fn["torch"](job)
-    differing = int((got != eager).sum())
+    differing = fb.differing(got, eager)
     changed = int((got != (job["mask"] >= 0.5).float()).sum())
     del got, eager
     torch.cuda.empty_cache()
     s = run(job, pair, iters, warmup)
-    med = statistics.median
+    med = fb.median
     F, H, W = CASES[job["case"]]
     moved = F * H * W * 8
     temporal, eager = med(s["temporal_a"] + s["temporal_b"]), med(s["torch_a"] + s["torch_b"])
@@ -131,26 +104,17 @@ def measure(job, pair, iters, warmup):
             "whole_ms": round(whole, 4), "edt_ms": round(edt, 4), "edt_share_of_whole": round(edt / whole, 3),
             "temporal_ms": round(temporal, 4), "torch_ms": round(eager, 4), "clone_ms": round(clone, 4),
             "torch_over_temporal": round(eager / temporal, 2), "temporal_over_clone": round(temporal / clone, 2),
-            "temporal_min_max_ms": [round(min(s["temporal_a"] + s["temporal_b"]), 4), round(max(s["temporal_a"] + s["temporal_b"]), 4)],
-            "torch_min_max_ms": [round(min(s["torch_a"] + s["torch_b"]), 4), round(max(s["torch_a"] + s["torch_b"]), 4)],
-            "whole_min_max_ms": [round(min(s["whole"]), 4), round(max(s["whole"]), 4)],
-            "temporal_spread": round(abs(med(s["temporal_a"]) - med(s["temporal_b"])) / temporal, 4),
-            "torch_spread": round(abs(med(s["torch_a"]) - med(s["torch_b"])) / eager, 4),
+            "temporal_min_max_ms": fb.summary(s["temporal_a"] + s["temporal_b"])[1],
+            "torch_min_max_ms": fb.summary(s["torch_a"] + s["torch_b"])[1], "whole_min_max_ms": fb.summary(s["whole"])[1],
+            "temporal_spread": fb.spread(s["temporal_a"], s["temporal_b"]), "torch_spread": fb.spread(s["torch_a"], s["torch_b"]),
             "required_bytes": moved, "fits_infinity_cache": moved <= INFINITY_CACHE_BYTES,
             "temporal_tb_per_s": round(moved / (temporal * 1e-3) / 1e12, 3), "clone_tb_per_s": round(moved / (clone * 1e-3) / 1e12, 3)}
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--iters", type=int, default=10)
-    ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--case", choices=tuple(CASES), help="this workload only")
-    ap.add_argument("--job", choices=("temporal", "torch", "edt", "whole"), help="run this side only and print nothing (a profiler run's body)")
-    a = ap.parse_args()
+    a = fb.parser(CASES, ("temporal", "torch", "edt", "whole")).parse_args()
+    dev = fb.device()
     import torch
-    if not torch.cuda.is_available():
-        raise SystemExit("bench_stabilize.py needs a HIP device")
-    dev = torch.device("cuda", 0)
     results = []
     for case in ((a.case,) if a.case else tuple(CASES)):
         job = make_job(case, dev)
@@ -163,10 +127,8 @@ def main():
         del job
         torch.cuda.empty_cache()
     if not a.job:
-        print(json.dumps({"metric": "mask_stabilize", "unit": "ms", "iters": a.iters, "warmup": a.warmup,
-                          "device": torch.cuda.get_device_name(0), "cases": results,
-                          "temporal_faster_than_torch_in_every_case": all(r["torch_over_temporal"] > 1.0 for r in results)},
-                         separators=(",", ":")))
+        fb.emit("mask_stabilize", a, results,
+                temporal_faster_than_torch_in_every_case=all(r["torch_over_temporal"] > 1.0 for r in results))
 
 
 if __name__ == "__main__":

@@ -6,8 +6,8 @@ textured disc crossing a panning texture -- with the disc's own mask on every fr
 (levels 4, search 2, smooth 8, reach 0).  Everything is already on the device.
 
     whole      temporal_fill.temporal_fill against propagate.propagate_masks (key frame 0, the disc's mask) on the same clip in
-               the same process, alternately: a host clock around the call and a device synchronise, the median of `iters` runs
-               and their min..max, and the ratio.  Device events around the call as well.
+               the same process, alternately: featurebench.wall, the median of `iters` runs and their min..max, and the
+               ratio.  featurebench.events around the call as well.
     split      between two device events: the copy of the clip and the outputs' allocation; the two pyramids of all frames; the
                fields of all 2 (F - 1) steps; the carries are what is left of the whole call.
     launches   counted by wrapping the modules' launch(): the entry calls by name, next to what the rule says they must be.
@@ -23,17 +23,9 @@ textured disc crossing a panning texture -- with the disc's own mask on every fr
 """
 from __future__ import annotations
 
-import argparse
-import json
-import os
-import statistics
-import sys
+import featurebench as fb
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "scripts"))
-
-import bench_propagate as single                                       # noqa: E402  the workloads, the timers, the field in torch
+import bench_propagate as single  # the workloads, the field in torch
 
 LEVELS, SEARCH, SMOOTH, REACH, GROW = single.LEVELS, single.SEARCH, single.SMOOTH, 0, 2
 
@@ -120,21 +112,11 @@ def torch_temporal_fill(images, mask, levels=LEVELS, search=SEARCH, smooth=SMOOT
 
 
 # ---- measurements ---------------------------------------------------------------------------------------------------------------------------
-def count_launches(fn):
-    from lanpaint_amd import propagate, temporal_fill
-    return single.count_launches(fn, propagate, temporal_fill)
-
-
 def expected_launches(F, levels):
     """What the rule says a call in one chunk is made of."""
     groups = -(-(F - 1) // 32)
     return {"lp_prop_luma": 1, "lp_tfill_known": 1, "lp_prop_match_batch": 2 * levels * groups, "lp_prop_fill_batch": 2 * levels * groups,
             "lp_tfill_carry": 2 * (F - 1)}
-
-
-def differing(a, b):
-    """Elements of two results that differ, a NaN equal to a NaN."""
-    return int(sum(((x != y) & ~((x != x) & (y != y))).sum() for x, y in zip(a, b)))
 
 
 def carry_alone(job, reps):
@@ -157,12 +139,12 @@ def carry_alone(job, reps):
                                               indexing="ij"), dim=-1))
     run = lambda: tf.carry(vec, bits[1], bits[0], state, images, filled, source, remaining, t, t - 1, 0, False, out)    # noqa: E731
     run()
-    ms = single.events(run, reps)
+    ms = fb.events(run, reps)
     masked = int((bits[1] == 0).sum())
     moved = H * W + masked * (1 + 12 + 12 + 4 * C * 4 + C * 4 + 4 + 4)
     blob = torch.empty(moved, dtype=torch.uint8, device=images.device)
     blob.clone()
-    return ms, single.events(blob.clone, reps), moved, masked
+    return ms, fb.events(blob.clone, reps), moved, masked
 
 
 def measure(job, iters, warmup, torch_frames, reps):
@@ -172,9 +154,9 @@ def measure(job, iters, warmup, torch_frames, reps):
     images, masks = job["images"], job["masks"]
     new = lambda: tf.temporal_fill(images, masks, LEVELS, SEARCH, SMOOTH, REACH)                        # noqa: E731
     old = lambda: propagate.propagate_masks(images, job["mask"], 0, LEVELS, SEARCH, SMOOTH)           # noqa: E731
-    names = count_launches(new)
+    names = fb.count_launches(new, propagate, tf)
     got = new()
-    again = differing(new(), got)
+    again = fb.differing(new(), got)
     masked = int((masks >= 0.5).sum())
     left = int(got[1].sum())
     outside = int(((got[0] != images) & (masks < 0.5)[..., None]).sum())
@@ -183,7 +165,7 @@ def measure(job, iters, warmup, torch_frames, reps):
     del got, ages
     n = min(torch_frames, F)
     eager = torch_temporal_fill(images[:n], masks[:n])
-    from_torch = differing(eager, tf.temporal_fill(images[:n], masks[:n], LEVELS, SEARCH, SMOOTH, REACH))
+    from_torch = fb.differing(eager, tf.temporal_fill(images[:n], masks[:n], LEVELS, SEARCH, SMOOTH, REACH))
     del eager
     steps = [(t, t - 1) for t in range(1, F)] + [(t, t + 1) for t in range(F - 2, -1, -1)]
     both = lambda: (propagate.luma_pyramids(images, LEVELS), tf.known_pyramids(masks, F, LEVELS))    # noqa: E731
@@ -191,28 +173,21 @@ def measure(job, iters, warmup, torch_frames, reps):
     fields = lambda: [tf.step_fields(luma, known, part, H, W, LEVELS, SEARCH, SMOOTH) for part in (steps[:F - 1], steps[F - 1:])]    # noqa: E731
     copies = lambda: (images.clone(), torch.empty((F, H, W), dtype=torch.int32, device=images.device),    # noqa: E731
                       torch.empty((F, H, W), device=images.device))
-    for _ in range(warmup):
-        new(), old(), fields()
-    torch.cuda.synchronize()
-    new_ms, old_ms, evs, pyr_ms, field_ms, copy_ms, torch_ms, small_ms = [], [], [], [], [], [], [], []
-    for _ in range(iters):                                            # alternating: the two share whatever else the host does
-        new_ms.append(single.wall(new))
-        old_ms.append(single.wall(old))
-        evs.append(single.events(new))
-        pyr_ms.append(single.events(both))
-        field_ms.append(single.events(fields))
-        copy_ms.append(single.events(copies))
-        torch_ms.append(single.wall(lambda: torch_temporal_fill(images[:n], masks[:n])))
-        small_ms.append(single.wall(lambda: tf.temporal_fill(images[:n], masks[:n], LEVELS, SEARCH, SMOOTH, REACH)))
+    fb.untimed(lambda: (new(), old(), fields()), warmup)
+    s = fb.series([("new", new, fb.wall), ("old", old, fb.wall),      # alternating: the two share whatever else the host does
+                   ("events", new), ("pyramids", both), ("fields", fields), ("copies", copies),
+                   ("torch", lambda: torch_temporal_fill(images[:n], masks[:n]), fb.wall),
+                   ("small", lambda: tf.temporal_fill(images[:n], masks[:n], LEVELS, SEARCH, SMOOTH, REACH), fb.wall)], iters, 0)
+    new_ms, old_ms, evs, pyr_ms, field_ms, copy_ms, torch_ms, small_ms = s.values()
     del luma, known
     carry_ms, clone_ms, moved, carry_masked = carry_alone(job, reps)
-    med = statistics.median
+    med = fb.median
     per = {k: names.count(k) for k in sorted(set(names))}
     rest = med(evs) - med(pyr_ms) - med(field_ms) - med(copy_ms)
     return {"case": job["case"], "frames_height_width": [F, H, W], "levels": LEVELS, "search": SEARCH, "smooth": SMOOTH, "reach": REACH,
-            "fill_wall_ms": round(med(new_ms), 3), "fill_wall_min_max_ms": [round(min(new_ms), 3), round(max(new_ms), 3)],
+            "fill_wall_ms": round(med(new_ms), 3), "fill_wall_min_max_ms": fb.summary(new_ms, 3)[1],
             "fill_events_ms": round(med(evs), 3), "ms_per_frame": round(med(new_ms) / F, 4),
-            "propagate_wall_ms": round(med(old_ms), 3), "propagate_wall_min_max_ms": [round(min(old_ms), 3), round(max(old_ms), 3)],
+            "propagate_wall_ms": round(med(old_ms), 3), "propagate_wall_min_max_ms": fb.summary(old_ms, 3)[1],
             "fill_over_propagate": round(med(new_ms) / med(old_ms), 3),
             "split_ms": {"copy_and_outputs": round(med(copy_ms), 3), "pyramids": round(med(pyr_ms), 3), "fields": round(med(field_ms), 3),
                          "carries_by_difference": round(rest, 3)},
@@ -228,33 +203,24 @@ def measure(job, iters, warmup, torch_frames, reps):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--iters", type=int, default=5)
-    ap.add_argument("--warmup", type=int, default=1)
+    ap = fb.parser(single.CASES, ("whole",), iters=5, warmup=1)
     ap.add_argument("--reps", type=int, default=50, help="back-to-back calls per stage timing")
     ap.add_argument("--torch-frames", type=int, default=4)
-    ap.add_argument("--case", choices=tuple(single.CASES), help="this workload only")
-    ap.add_argument("--job", choices=("whole",), help="run the whole call only and print nothing (a profiler run's body)")
     a = ap.parse_args()
+    dev = fb.device()
     import torch
-    if not torch.cuda.is_available():
-        raise SystemExit("bench_temporal_fill.py needs a HIP device")
     from lanpaint_amd import temporal_fill as tf
-    dev = torch.device("cuda", 0)
     results = []
     for case in ((a.case,) if a.case else tuple(single.CASES)):
         job = make_job(case, dev)
         if a.job:
-            for _ in range(a.warmup + a.iters):
-                tf.temporal_fill(job["images"], job["masks"], LEVELS, SEARCH, SMOOTH, REACH)
-            torch.cuda.synchronize()
+            fb.untimed(lambda: tf.temporal_fill(job["images"], job["masks"], LEVELS, SEARCH, SMOOTH, REACH), a.warmup + a.iters)
         else:
             results.append(measure(job, a.iters, a.warmup, a.torch_frames, a.reps))
         del job
         torch.cuda.empty_cache()
     if not a.job:
-        print(json.dumps({"metric": "video_temporal_fill", "unit": "ms", "iters": a.iters, "warmup": a.warmup,
-                          "device": torch.cuda.get_device_name(0), "cases": results}, separators=(",", ":")))
+        fb.emit("video_temporal_fill", a, results)
 
 
 if __name__ == "__main__":

@@ -5,9 +5,9 @@ The two workloads of scripts/bench_temporal_fill.py -- `clip` (81 frames of 1280
 1024 x 1024 x 3), a textured disc crossing a panning texture under its own mask grown by 2 pixels -- at the default parameters
 (levels 4, search 2, smooth 8, reach 0, agree 8).  Everything is already on the device.
 
-    whole      temporal_fill_checked against the unchanged temporal_fill on the same clip in the same process, alternately: a
-               host clock around the call and a device synchronise, the median of `iters` runs and their min..max, and the
-               ratio.  Device events around each call as well.
+    whole      temporal_fill_checked against the unchanged temporal_fill on the same clip in the same process, alternately:
+               featurebench.wall, the median of `iters` runs and their min..max, and the ratio.  featurebench.events around
+               each call as well.
     backward   what a backward step costs more than the plain one: the difference of the two calls' event times over the
                F - 1 backward steps (everything else in the two calls is the same launches), next to one lp_tfill_carry_pair and
                one lp_tfill_carry (nearer = 1) launch on the middle frame, each timed between two events with the frame's planes
@@ -25,18 +25,10 @@ The two workloads of scripts/bench_temporal_fill.py -- `clip` (81 frames of 1280
 """
 from __future__ import annotations
 
-import argparse
-import json
-import os
-import statistics
-import sys
+import featurebench as fb
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "scripts"))
-
-import bench_propagate as single                                       # noqa: E402  the timers
-import bench_temporal_fill as plain                                    # noqa: E402  the workloads
+import bench_propagate as single  # the cases
+import bench_temporal_fill as plain  # the workloads
 
 LEVELS, SEARCH, SMOOTH, REACH, AGREE = plain.LEVELS, plain.SEARCH, plain.SMOOTH, plain.REACH, 8
 WRONG = 8 / 255
@@ -117,8 +109,8 @@ def backward_alone(job, reps):
         times = []
         for _ in range(reps + 1):
             filled[t], source[t], remaining[t] = keep
-            times.append(single.events(run))
-        ms[name] = statistics.median(times[1:])
+            times.append(fb.events(run))
+        ms[name] = fb.median(times[1:])
     return ms["pair"], ms["plain"]
 
 
@@ -129,25 +121,20 @@ def measure(job, iters, warmup, reps):
     new = lambda: tc.temporal_fill_checked(images, masks, LEVELS, SEARCH, SMOOTH, REACH, AGREE)     # noqa: E731
     old = lambda: tf.temporal_fill(images, masks, LEVELS, SEARCH, SMOOTH, REACH)                    # noqa: E731
     got, base = new(), old()
-    again = plain.differing(new(), got)
+    again = fb.differing(new(), got)
     disputed = int((got[2] == -2).sum())
-    from_plain = plain.differing(got[:3], base)
+    from_plain = fb.differing(got[:3], base)
     verified, one = int((got[3] == 2).sum()), int((got[3] == 1).sum())
     del got, base
-    for _ in range(warmup):
-        new(), old()
-    new_ms, old_ms, new_ev, old_ev = [], [], [], []
-    for _ in range(iters):                                            # alternating: the two share whatever else the host does
-        new_ms.append(single.wall(new))
-        old_ms.append(single.wall(old))
-        new_ev.append(single.events(new))
-        old_ev.append(single.events(old))
-    med = statistics.median
+    # alternating: the two share whatever else the host does
+    s = fb.series([("new", new, fb.wall), ("old", old, fb.wall), ("new_events", new), ("old_events", old)], iters, warmup)
+    new_ms, old_ms, new_ev, old_ev = s.values()
+    med = fb.median
     pair_ms, carry_ms = backward_alone(job, reps)
     return {"case": job["case"], "frames_height_width": [F, H, W], "levels": LEVELS, "search": SEARCH, "smooth": SMOOTH, "reach": REACH,
             "agree": AGREE,
-            "checked_wall_ms": round(med(new_ms), 3), "checked_wall_min_max_ms": [round(min(new_ms), 3), round(max(new_ms), 3)],
-            "plain_wall_ms": round(med(old_ms), 3), "plain_wall_min_max_ms": [round(min(old_ms), 3), round(max(old_ms), 3)],
+            "checked_wall_ms": round(med(new_ms), 3), "checked_wall_min_max_ms": fb.summary(new_ms, 3)[1],
+            "plain_wall_ms": round(med(old_ms), 3), "plain_wall_min_max_ms": fb.summary(old_ms, 3)[1],
             "checked_over_plain": round(med(new_ms) / med(old_ms), 3),
             "checked_events_ms": round(med(new_ev), 3), "plain_events_ms": round(med(old_ev), 3),
             "checked_over_plain_events": round(med(new_ev) / med(old_ev), 3),
@@ -159,35 +146,25 @@ def measure(job, iters, warmup, reps):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--iters", type=int, default=5)
-    ap.add_argument("--warmup", type=int, default=1)
+    ap = fb.parser(single.CASES, ("checked", "plain"), iters=5, warmup=1)
     ap.add_argument("--reps", type=int, default=20, help="launches per stage timing")
-    ap.add_argument("--case", choices=tuple(single.CASES), help="this workload only")
-    ap.add_argument("--job", choices=("checked", "plain"), help="run that call only and print nothing (a profiler run's body)")
     a = ap.parse_args()
+    dev = fb.device()
     import torch
-    if not torch.cuda.is_available():
-        raise SystemExit("bench_temporal_fill_checked.py needs a HIP device")
     from lanpaint_amd import temporal_fill as tf, temporal_fill_checked as tc
-    dev = torch.device("cuda", 0)
     results = []
     for case in ((a.case,) if a.case else tuple(single.CASES)):
         job = plain.make_job(case, dev)
         if a.job:
-            for _ in range(a.warmup + a.iters):
-                if a.job == "checked":
-                    tc.temporal_fill_checked(job["images"], job["masks"], LEVELS, SEARCH, SMOOTH, REACH, AGREE)
-                else:
-                    tf.temporal_fill(job["images"], job["masks"], LEVELS, SEARCH, SMOOTH, REACH)
-            torch.cuda.synchronize()
+            body = {"checked": lambda: tc.temporal_fill_checked(job["images"], job["masks"], LEVELS, SEARCH, SMOOTH, REACH, AGREE),
+                    "plain": lambda: tf.temporal_fill(job["images"], job["masks"], LEVELS, SEARCH, SMOOTH, REACH)}[a.job]
+            fb.untimed(body, a.warmup + a.iters)
         else:
             results.append(measure(job, a.iters, a.warmup, a.reps))
         del job
         torch.cuda.empty_cache()
     if not a.job:
-        print(json.dumps({"metric": "video_temporal_fill_checked", "unit": "ms", "iters": a.iters, "warmup": a.warmup,
-                          "device": torch.cuda.get_device_name(0), "cases": results}, separators=(",", ":")))
+        fb.emit("video_temporal_fill_checked", a, results)
 
 
 if __name__ == "__main__":

@@ -7,8 +7,8 @@ textured disc crossing a panning texture, the disc's own mask on every frame, gr
 the device.
 
     whole      temporal_smooth.temporal_smooth per radius against temporal_fill.temporal_fill on the same clip in the same process,
-               alternately: a host clock around the call and a device synchronise, the median of `iters` runs and their min..max,
-               and the ratio.  Device events around the call as well.
+               alternately: featurebench.wall, the median of `iters` runs and their min..max, and the ratio.
+               featurebench.events around the call as well.
     split      between two device events, per radius: the two pyramids of all frames, the fields of all 2 (F - 1) steps, and the one
                smooth launch for all frames (`reps` calls back to back).
     launch     that launch against a clone of a buffer of the bytes it must move: every frame read and written once, the known
@@ -26,19 +26,12 @@ the device.
 """
 from __future__ import annotations
 
-import argparse
-import json
-import os
-import statistics
-import sys
 from math import comb
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "scripts"))
+import featurebench as fb
 
-import bench_propagate as single                                       # noqa: E402  the timers, the field in torch
-import bench_temporal_fill as fill                                     # noqa: E402  the workloads, the vectors and the sample in torch
+import bench_propagate as single  # the field in torch
+import bench_temporal_fill as fill  # the workloads, the vectors and the sample in torch
 
 LEVELS, SEARCH, SMOOTH, TOLERANCE, MOTION, RADII = single.LEVELS, single.SEARCH, single.SMOOTH, 24, "background", (1, 2, 8)
 
@@ -101,11 +94,6 @@ def torch_temporal_smooth(images, mask, radius, tolerance=TOLERANCE, motion=MOTI
 
 
 # ---- measurements ---------------------------------------------------------------------------------------------------------------------------
-def count_launches(fn):
-    from lanpaint_amd import propagate, temporal_fill, temporal_smooth
-    return single.count_launches(fn, propagate, temporal_fill, temporal_smooth)
-
-
 def measure(job, iters, warmup, torch_frames, reps):
     import torch
     from lanpaint_amd import propagate, temporal_fill as tf, temporal_smooth as ts
@@ -113,7 +101,7 @@ def measure(job, iters, warmup, torch_frames, reps):
     images, masks = job["images"], job["masks"]
     C = images.shape[3]
     old = lambda: tf.temporal_fill(images, masks, LEVELS, SEARCH, SMOOTH, 0)                            # noqa: E731
-    med = statistics.median
+    med = fb.median
     masked = int((masks >= 0.5).sum())
     n = min(torch_frames, F)
     both = lambda: (propagate.luma_pyramids(images, LEVELS), tf.known_pyramids(masks, F, LEVELS))    # noqa: E731
@@ -121,15 +109,15 @@ def measure(job, iters, warmup, torch_frames, reps):
     per_radius = []
     for radius in RADII:
         new = lambda: ts.temporal_smooth(images, masks, radius, TOLERANCE, MOTION, LEVELS, SEARCH, SMOOTH)    # noqa: E731
-        names = count_launches(new)
+        names = fb.count_launches(new, propagate, tf, ts)
         got = new()
-        again = fill.differing(new(), got)
+        again = fb.differing(new(), got)
         outside = int(((got[0] != images) & (masks < 0.5)[..., None]).sum())
         changed = int(((got[0] != images).any(dim=-1) & (masks >= 0.5)).sum())
         share = float(got[1][masks >= 0.5].float().mean()) / (2 * radius)
         del got
         eager = torch_temporal_smooth(images[:n], masks[:n], radius)
-        from_torch = fill.differing(eager, ts.temporal_smooth(images[:n], masks[:n], radius, TOLERANCE, MOTION, LEVELS, SEARCH, SMOOTH))
+        from_torch = fb.differing(eager, ts.temporal_smooth(images[:n], masks[:n], radius, TOLERANCE, MOTION, LEVELS, SEARCH, SMOOTH))
         del eager
         fwd, bwd = ts.field_steps(0, F, F, radius)
         steps = [(u, u + 1) for u in fwd] + [(u, u - 1) for u in bwd]
@@ -138,34 +126,29 @@ def measure(job, iters, warmup, torch_frames, reps):
         out = torch.empty_like(images)
         support = torch.empty((F, H, W), dtype=torch.int32, device=images.device)
         alone = lambda: ts.smooth_frames(vec[:len(fwd)], vec[len(fwd):], known, images, radius, TOLERANCE, 0, F, 0, 1, out, support)    # noqa: E731
-        for _ in range(warmup):
-            new(), old(), fields(), alone()
-        torch.cuda.synchronize()
-        new_ms, old_ms, evs, pyr_ms, field_ms, torch_ms, small_ms = [], [], [], [], [], [], []
-        for _ in range(iters):                                        # alternating: the two share whatever else the host does
-            new_ms.append(single.wall(new))
-            old_ms.append(single.wall(old))
-            evs.append(single.events(new))
-            pyr_ms.append(single.events(both))
-            field_ms.append(single.events(fields))
-            torch_ms.append(single.wall(lambda: torch_temporal_smooth(images[:n], masks[:n], radius)))
-            small_ms.append(single.wall(lambda: ts.temporal_smooth(images[:n], masks[:n], radius, TOLERANCE, MOTION, LEVELS, SEARCH, SMOOTH)))
-        launch_ms = single.events(alone, reps)
+        fb.untimed(lambda: (new(), old(), fields(), alone()), warmup)
+        s = fb.series([("new", new, fb.wall), ("old", old, fb.wall),  # alternating: the two share whatever else the host does
+                       ("events", new), ("pyramids", both), ("fields", fields),
+                       ("torch", lambda: torch_temporal_smooth(images[:n], masks[:n], radius), fb.wall),
+                       ("small", lambda: ts.temporal_smooth(images[:n], masks[:n], radius, TOLERANCE, MOTION, LEVELS, SEARCH, SMOOTH), fb.wall)],
+                      iters, 0)
+        new_ms, old_ms, evs, pyr_ms, field_ms, torch_ms, small_ms = s.values()
+        launch_ms = fb.events(alone, reps)
         all_known = torch.ones((F, H, W), dtype=torch.uint8, device=images.device)
         copy_only = lambda: ts.smooth_frames(vec[:len(fwd)], vec[len(fwd):], all_known, images, radius, TOLERANCE, 0, F, 0, 1, out, support)    # noqa: E731
         copy_only()
-        copy_ms = single.events(copy_only, reps)
-        frames_clone_ms = single.events(lambda: out.copy_(images), reps)        # what torch.clone runs, without its allocation
+        copy_ms = fb.events(copy_only, reps)
+        frames_clone_ms = fb.events(lambda: out.copy_(images), reps)        # what torch.clone runs, without its allocation
         del all_known
         moved = F * H * W * (2 * C * 4 + 1 + 4) + masked * 2 * radius * (4 * 8 + 4 * C * 4)
         blob, twin = (torch.empty(moved, dtype=torch.uint8, device=images.device) for _ in range(2))
         twin.copy_(blob)
-        clone_ms = single.events(lambda: twin.copy_(blob), max(reps // 5, 1))
+        clone_ms = fb.events(lambda: twin.copy_(blob), max(reps // 5, 1))
         del blob, twin, vec, out, support
         per_radius.append({
-            "radius": radius, "smooth_wall_ms": round(med(new_ms), 3), "smooth_wall_min_max_ms": [round(min(new_ms), 3), round(max(new_ms), 3)],
+            "radius": radius, "smooth_wall_ms": round(med(new_ms), 3), "smooth_wall_min_max_ms": fb.summary(new_ms, 3)[1],
             "smooth_events_ms": round(med(evs), 3), "ms_per_frame": round(med(new_ms) / F, 4),
-            "fill_wall_ms": round(med(old_ms), 3), "fill_wall_min_max_ms": [round(min(old_ms), 3), round(max(old_ms), 3)],
+            "fill_wall_ms": round(med(old_ms), 3), "fill_wall_min_max_ms": fb.summary(old_ms, 3)[1],
             "smooth_over_fill": round(med(new_ms) / med(old_ms), 3),
             "split_ms": {"pyramids": round(med(pyr_ms), 3), "fields": round(med(field_ms), 3), "smooth_launch": round(launch_ms, 4),
                          "smooth_launch_with_an_empty_mask": round(copy_ms, 4), "clone_of_the_clip": round(frames_clone_ms, 4)},
@@ -181,33 +164,24 @@ def measure(job, iters, warmup, torch_frames, reps):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--iters", type=int, default=5)
-    ap.add_argument("--warmup", type=int, default=1)
+    ap = fb.parser(single.CASES, ("whole",), iters=5, warmup=1)
     ap.add_argument("--reps", type=int, default=50, help="back-to-back calls per stage timing")
     ap.add_argument("--torch-frames", type=int, default=4)
-    ap.add_argument("--case", choices=tuple(single.CASES), help="this workload only")
-    ap.add_argument("--job", choices=("whole",), help="run the whole call only and print nothing (a profiler run's body)")
     a = ap.parse_args()
+    dev = fb.device()
     import torch
-    if not torch.cuda.is_available():
-        raise SystemExit("bench_temporal_smooth.py needs a HIP device")
     from lanpaint_amd import temporal_smooth as ts
-    dev = torch.device("cuda", 0)
     results = []
     for case in ((a.case,) if a.case else tuple(single.CASES)):
         job = fill.make_job(case, dev)
         if a.job:
-            for _ in range(a.warmup + a.iters):
-                ts.temporal_smooth(job["images"], job["masks"], 2, TOLERANCE, MOTION, LEVELS, SEARCH, SMOOTH)
-            torch.cuda.synchronize()
+            fb.untimed(lambda: ts.temporal_smooth(job["images"], job["masks"], 2, TOLERANCE, MOTION, LEVELS, SEARCH, SMOOTH), a.warmup + a.iters)
         else:
             results.append(measure(job, a.iters, a.warmup, a.torch_frames, a.reps))
         del job
         torch.cuda.empty_cache()
     if not a.job:
-        print(json.dumps({"metric": "video_temporal_smooth", "unit": "ms", "iters": a.iters, "warmup": a.warmup,
-                          "device": torch.cuda.get_device_name(0), "cases": results}, separators=(",", ":")))
+        fb.emit("video_temporal_smooth", a, results)
 
 
 if __name__ == "__main__":

@@ -6,8 +6,8 @@ at its parameters (tolerance 24, motion "background", levels 4, search 2, smooth
 Everything is already on the device.
 
     whole      temporal_smooth_robust.temporal_smooth_robust per radius against temporal_smooth.temporal_smooth on the same clip in
-               the same process, alternately: a host clock around the call and a device synchronise, the median of `iters` runs
-               and their min..max, and the ratio.  Device events around the robust call as well.
+               the same process, alternately: featurebench.wall, the median of `iters` runs and their min..max, and the
+               ratio.  featurebench.events around the robust call as well.
     launch     the one launch alone (`robust_frames`) against the plain one (`smooth_frames`) on the same fields, `reps` calls back
                to back between two device events, and the ratio; both with an empty mask too -- the copy alone.
     resources  VGPRs, SGPRs, LDS and scratch of the two kernels, from the metadata of the library that ran.
@@ -22,19 +22,11 @@ Everything is already on the device.
 """
 from __future__ import annotations
 
-import argparse
-import json
-import os
-import statistics
-import sys
+import featurebench as fb
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "scripts"))
-
-import bench_propagate as single                                       # noqa: E402  the timers
-import bench_temporal_fill as fill                                     # noqa: E402  the workloads
-import bench_temporal_smooth as plain                                  # noqa: E402  the parameters
+import bench_propagate as single  # the cases
+import bench_temporal_fill as fill  # the workloads
+import bench_temporal_smooth as plain  # the parameters
 
 LEVELS, SEARCH, SMOOTH, TOLERANCE, MOTION, RADII = plain.LEVELS, plain.SEARCH, plain.SMOOTH, plain.TOLERANCE, plain.MOTION, plain.RADII
 POP = 64 / 256
@@ -86,7 +78,7 @@ def measure(job, iters, warmup, reps):
     from lanpaint_amd import propagate, temporal_fill as tf, temporal_smooth as ts, temporal_smooth_robust as tr
     F, H, W = job["shape"]
     images, masks = job["images"], job["masks"]
-    med = statistics.median
+    med = fb.median
     masked = int((masks >= 0.5).sum())
     luma, known = propagate.luma_pyramids(images, LEVELS), tf.known_pyramids(masks, F, LEVELS)
     per_radius = []
@@ -94,9 +86,9 @@ def measure(job, iters, warmup, reps):
         args = (radius, TOLERANCE, MOTION, LEVELS, SEARCH, SMOOTH)
         new = lambda: tr.temporal_smooth_robust(images, masks, *args)                                    # noqa: E731
         old = lambda: ts.temporal_smooth(images, masks, *args)                                           # noqa: E731
-        names = plain.count_launches(new)
+        names = fb.count_launches(new, propagate, tf, ts)
         got = new()
-        again = fill.differing(new(), got)
+        again = fb.differing(new(), got)
         outside = int(((got[0] != images) & (masks < 0.5)[..., None]).sum())
         replaced = int((got[2] == 1).sum())
         share = float(got[1][masks >= 0.5].float().mean()) / (2 * radius)
@@ -114,22 +106,15 @@ def measure(job, iters, warmup, reps):
                                                           out, support, flags),
             "plain_empty_mask": lambda: ts.smooth_frames(vec[:len(fwd)], vec[len(fwd):], all_known, images, radius, TOLERANCE, 0, F, 0, 1,
                                                          out, support)}
-        for _ in range(warmup):
-            new(), old()
-            for fn in launches.values():
-                fn()
-        torch.cuda.synchronize()
-        new_ms, old_ms, evs = [], [], []
-        for _ in range(iters):                                        # alternating: the two share whatever else the host does
-            new_ms.append(single.wall(new))
-            old_ms.append(single.wall(old))
-            evs.append(single.events(new))
-        launch_ms = {k: single.events(fn, reps) for k, fn in launches.items()}
+        fb.untimed(lambda: (new(), old(), [fn() for fn in launches.values()]), warmup)
+        # alternating: the two share whatever else the host does
+        new_ms, old_ms, evs = fb.series([("new", new, fb.wall), ("old", old, fb.wall), ("events", new)], iters, 0).values()
+        launch_ms = {k: fb.events(fn, reps) for k, fn in launches.items()}
         del vec, out, support, flags, all_known
         per_radius.append({
-            "radius": radius, "robust_wall_ms": round(med(new_ms), 3), "robust_wall_min_max_ms": [round(min(new_ms), 3), round(max(new_ms), 3)],
+            "radius": radius, "robust_wall_ms": round(med(new_ms), 3), "robust_wall_min_max_ms": fb.summary(new_ms, 3)[1],
             "robust_events_ms": round(med(evs), 3), "ms_per_frame": round(med(new_ms) / F, 4),
-            "plain_wall_ms": round(med(old_ms), 3), "plain_wall_min_max_ms": [round(min(old_ms), 3), round(max(old_ms), 3)],
+            "plain_wall_ms": round(med(old_ms), 3), "plain_wall_min_max_ms": fb.summary(old_ms, 3)[1],
             "robust_over_plain": round(med(new_ms) / med(old_ms), 3),
             "launch_ms": {k: round(v, 4) for k, v in launch_ms.items()},
             "launch_robust_over_plain": round(launch_ms["robust"] / launch_ms["plain"], 3),
@@ -145,33 +130,24 @@ def measure(job, iters, warmup, reps):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--iters", type=int, default=5)
-    ap.add_argument("--warmup", type=int, default=1)
+    ap = fb.parser(single.CASES, ("whole",), iters=5, warmup=1)
     ap.add_argument("--reps", type=int, default=20, help="back-to-back calls per launch timing")
-    ap.add_argument("--case", choices=tuple(single.CASES), help="this workload only")
-    ap.add_argument("--job", choices=("whole",), help="run the whole call only and print nothing (a profiler run's body)")
     a = ap.parse_args()
+    dev = fb.device()
     import torch
-    if not torch.cuda.is_available():
-        raise SystemExit("bench_temporal_smooth_robust.py needs a HIP device")
     from lanpaint_amd import temporal_smooth_robust as tr
-    dev = torch.device("cuda", 0)
     results = []
     for case in ((a.case,) if a.case else tuple(single.CASES)):
         job = fill.make_job(case, dev)
         job.setdefault("case", case)
         if a.job:
-            for _ in range(a.warmup + a.iters):
-                tr.temporal_smooth_robust(job["images"], job["masks"], 2, TOLERANCE, MOTION, LEVELS, SEARCH, SMOOTH)
-            torch.cuda.synchronize()
+            fb.untimed(lambda: tr.temporal_smooth_robust(job["images"], job["masks"], 2, TOLERANCE, MOTION, LEVELS, SEARCH, SMOOTH), a.warmup + a.iters)
         else:
             results.append(measure(job, a.iters, a.warmup, a.reps))
         del job
         torch.cuda.empty_cache()
     if not a.job:
-        print(json.dumps({"metric": "video_temporal_smooth_robust", "unit": "ms", "iters": a.iters, "warmup": a.warmup,
-                          "device": torch.cuda.get_device_name(0), "kernels": kernel_resources(), "cases": results}, separators=(",", ":")))
+        fb.emit("video_temporal_smooth_robust", a, results, kernels=kernel_resources())
 
 
 if __name__ == "__main__":

@@ -9,22 +9,13 @@ Shapes (keyframes already on the device, as a node that keeps them there would h
     python scripts/bench_videomask.py [--iters 30] [--warmup 5] [--kernels a=A.db b=B.db c=C.db]
     python scripts/bench_videomask.py --shape a --iters 5          # the body of a rocprofv3 --kernel-trace run
 
-Wall time: host clock around one call ending in torch.cuda.synchronize(), median over --iters after --warmup.  Per-kernel
+Time: featurebench.wall per call, median over --iters after --warmup.  Per-kernel
 times come from a SEPARATE rocprofv3 --kernel-trace --stats run per shape (--kernels reads its results .db / kernel-trace
 CSV); the resize kernel's output bytes over its mean time are reported against 6.3 TB/s achievable HBM bandwidth.
 """
 from __future__ import annotations
 
-import argparse
-import json
-import os
-import statistics
-import sys
-import time
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "scripts"))
+import featurebench as fb
 
 HBM_ACHIEVABLE = 6.3e12
 SHAPES = {"a": (2, 81, (1280, 720)), "b": (4, 121, (1920, 1080)), "c": (2, 81, None)}
@@ -46,21 +37,12 @@ def keyframes(n, count, dev):
 
 
 def run_shape(name, iters, warmup):
-    import torch
     from lanpaint_amd import videomask
-    dev = torch.device("cuda", 0)
+    dev = fb.device()
     n, count, size = SHAPES[name]
     keys = keyframes(n, count, dev)
-    for _ in range(warmup):
-        videomask.interpolate_masks(keys, count, size=size, device=dev)
-    torch.cuda.synchronize()
-    times = []
-    for _ in range(iters):
-        t0 = time.perf_counter()
-        out = videomask.interpolate_masks(keys, count, size=size, device=dev)
-        torch.cuda.synchronize()
-        times.append(time.perf_counter() - t0)
-    return out, times
+    call = lambda: videomask.interpolate_masks(keys, count, size=size, device=dev)    # noqa: E731
+    return fb.series([("wall", call)], iters, warmup, timer=fb.wall)["wall"]
 
 
 def kernel_stats(path):
@@ -71,33 +53,29 @@ def kernel_stats(path):
         for k in ("col", "row", "sdf", "morph", "resize"):
             if f"lp_vmask_{k}_kernel" in name:
                 per.setdefault(k, []).append((end - start) * 1e-3)
-    return {k: {"calls": len(v), "mean_us": round(statistics.mean(v), 2), "median_us": round(statistics.median(v), 2)}
+    return {k: {"calls": len(v), "mean_us": round(sum(v) / len(v), 2), "median_us": round(fb.median(v), 2)}
             for k, v in per.items()}
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--iters", type=int, default=30)
-    ap.add_argument("--warmup", type=int, default=5)
+    ap = fb.parser(iters=30, warmup=5)
     ap.add_argument("--shape", choices=sorted(SHAPES))
     ap.add_argument("--kernels", nargs="*", default=[], help="SHAPE=rocprofv3 results .db or kernel-trace .csv")
     args = ap.parse_args()
+    fb.device()
     import torch
-    if not torch.cuda.is_available():
-        raise SystemExit("bench_videomask.py needs a HIP device")
     if args.shape:
         run_shape(args.shape, args.iters, args.warmup)
         return
     profiles = dict(kv.split("=", 1) for kv in args.kernels)
-    result = {"metric": "videomask_interpolate_masks", "unit": "ms", "iters": args.iters, "warmup": args.warmup,
-              "device": torch.cuda.get_device_name(0), "shapes": {}}
+    shapes = {}
     for name in sorted(SHAPES):
         n, count, size = SHAPES[name]
-        out, times = run_shape(name, args.iters, args.warmup)
+        times = run_shape(name, args.iters, args.warmup)
         w, h = size or (KEY_W, KEY_H)
-        rec = {"keys": n, "frames": count, "out": [count, h, w], "out_bytes": out.numel() * 4,
-               "wall_ms_median": round(statistics.median(times) * 1e3, 4), "wall_ms_min": round(min(times) * 1e3, 4),
-               "wall_ms_max": round(max(times) * 1e3, 4)}
+        ms, (low, high) = fb.summary(times)
+        rec = {"keys": n, "frames": count, "out": [count, h, w], "out_bytes": count * h * w * 4,
+               "wall_ms_median": ms, "wall_ms_min": low, "wall_ms_max": high}
         if name in profiles:
             ks = kernel_stats(profiles[name])
             rec["kernels"] = ks
@@ -107,10 +85,9 @@ def main():
                 rec["big_kernel_hbm_frac"] = round(rec["out_bytes"] / (big["median_us"] * 1e-6) / HBM_ACHIEVABLE, 4)
         else:
             rec["kernels"] = "not measured"
-        result["shapes"][name] = rec
-        del out
+        shapes[name] = rec
         torch.cuda.empty_cache()
-    print(json.dumps(result, separators=(",", ":")))
+    fb.emit("videomask_interpolate_masks", args, shapes=shapes)
 
 
 if __name__ == "__main__":
