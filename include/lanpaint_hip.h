@@ -1287,6 +1287,85 @@ LP_API int lp_multiband_blend(const lp_multiband_desc* desc, void* stream);
  * Host arithmetic, no HIP call.  A negative LP_E_* for arguments lp_multiband_blend refuses.                                */
 LP_API int64_t lp_multiband_ws_bytes(int32_t batch, int32_t height, int32_t width, int32_t channels, int32_t levels);
 
+/* ---- lp_multiband_blend, the focus form: levels = LP_MULTIBAND_FOCUS(edge, ring, strength16, per_frame) -------------------------------
+ * Every levels >= 0 is the blend above, unchanged.  A negative `levels` is a mode word; the only form it names is focus match: measure
+ * how soft the edges of the footage around the mask are, measure how soft the edges under the mask are, and blur the masked area
+ * by the difference.  What a decoder returns under the mask is as sharp as the model draws; the footage around it is as soft as the
+ * lens, the motion, the codec or an upscale left it.  The form goes behind the stitch or decode (and the temporal smooth) and in
+ * front of the multiband blend and the grain match -- blur removes grain, so grain goes back after it.  (csrc/focus_kernel.hip.)
+ *   image1   the picture to correct (the stitched or decoded result); image2 where the reference sharpness is read: the same
+ *            tensor or the untouched original, same shape.  image1 == image2 is allowed; out != image1 and out != image2 stay.
+ * Mode word: bit 31 set; bits 0..7 edge, 1..255 grey levels; bits 8..11 ring, 1..LP_FOCUS_MAX_RING tiles; bits 12..16 strength16,
+ * 0..16 sixteenths; bit 17 per_frame; bits 18..30 zero (so levels = -1 stays LP_E_INVALID).  LP_E_INVALID: a field outside its range,
+ * a bit of 18..30, and everything the plain form refuses, in its order (LP_E_ALIGN is answered before a short workspace);
+ * LP_E_UNSUPPORTED: batch > 65535, or per_frame = 0 with batch * height * width > 2^30 (the pooled sums stay inside 64 bits).  All
+ * before any HIP call.  lp_multiband_ws_bytes(batch, height, width, channels, word) returns LP_FOCUS_WS_BYTES(...) or those codes.
+ *
+ * The rule.  Integers up to the fit; the fit in fp64 with + - * / only, each rounded on its own; the blur in fp32 with every product
+ * and sum rounded on its own.  No exp, log or pow.  The same bits on every run, for every tiling and every split of a batch
+ * (per_frame = 1; the pooled form measures the whole batch it is given).
+ * codes    code(v) = (int)(fl(fl(t * 255) + 0.5)) in fp32, t = v clamped to 0..1, a NaN gives 0.  Y = (77 c0 + 150 c1 + 29 c2 + 128)
+ *          >> 8 of the codes of a pixel's first three channels; with fewer than three channels Y = c0.
+ * scales   A = Y through the separable binomial (1, 2, 1) (variance 0.5), B = Y through the separable binomial
+ *          (1, 8, 28, 56, 70, 56, 28, 8, 1) (variance 2), unnormalised exact integers: A carries a factor 16, B a factor 65536.
+ *          A pixel takes part only if its whole 11 x 11 support (Chebyshev distance 5) lies inside the image.  Central
+ *          differences: gx = P(y, x + 1) - P(y, x - 1), gy = P(y + 1, x) - P(y - 1, x), gA^2 = gx^2 + gy^2 on A, gB^2 on B, int64.
+ *          An EDGE pixel has gB^2 >= (edge * 2 * 65536)^2 = (edge * 131072)^2.
+ * regions  masked(p) = mask(p) > 0.5 (a NaN is not masked).  Tiles are 32 x 32 from the origin (LP_FOCUS_TILE); a tile is MARKED
+ *          when it holds a masked pixel.  INSIDE: all 121 pixels of the support are masked; read on image1.  RING: none of the 121
+ *          is masked, and the pixel's tile lies within `ring` tiles (Chebyshev, in tiles) of a marked tile; read on image2.
+ * stats    per image and region, over the region's edge pixels: n, SA = sum of gA^2, SB = sum of floor(gB^2 / 65536) (the shift
+ *          keeps SB of a 32768 x 32768 image inside an int64), all int64.  Integer sums: any order gives the same bits.
+ * fit      per image (per_frame = 1) or on the sums over the batch.  A side with n < LP_FOCUS_MIN_COUNT fits nothing: K = 0, and
+ *          that side's variance is reported as LP_FOCUS_NO_FIT.  Else a = (double)SA / 256, b = (double)SB / 65536, r = a / b,
+ *          q = r * r (the squared ratio of the mean squared gradients (SA / 16^2) / (SB' / 65536^2), SB' the unshifted sum);
+ *          var = (2 - 0.5 * q) / (q - 1) for q > 1, LP_FOCUS_MAX_VAR for q <= 1 (a step edge of variance s^2 has
+ *          q = (s^2 + 2) / (s^2 + 0.5)).  d = var_ring - var_inside, 0 if that is not positive; v = (strength16 / 16) * d, limited to
+ *          LP_FOCUS_MAX_VAR (16 px^2, sigma 4); K = (int)(v * 32 + 0.5): the variance to add in thirty-seconds of a px^2.
+ * kernel   k = K >> 4, t = K & 15.  b_k(i) = C(2 k, k + i) / 4^k, the binomial of order 2 k and variance k / 2 exactly: the integer
+ *          coefficient (< 2^64 up to order 66) converted to fp64, round to nearest even, times the exact power of two; 0 for
+ *          |i| > k.  w(i) = (float)(((16 - t) * b_k(i) + t * b_{k+1}(i)) / 16) for |i| <= 33.  A mixture of zero-mean kernels has
+ *          the mixed variance, so w has variance K / 32 before the rounding to fp32.
+ * apply    separable, rows first (along x into a plane of the workspace), then columns.  r = k + 1 for t > 0, else k.  Along an
+ *          axis: s = w(-r) * v[-r]; s = s + w(i) * v[i] for i = -r + 1 .. r in that order, coordinates clamped to the image.
+ *          m = (mask > 0) ? min(mask, 1) : 0 (a NaN gives 0); out = image1 + m * (blur - image1), the difference, the product and
+ *          the sum in that order.  Where m == 0 or K == 0, out holds image1's bits.  A tile without m > 0 only copies; the rows pass
+ *          skips a tile no column pass reads.
+ * What follows: an all-zero mask gives image1 bit for bit; a masked area as soft as or softer than its surroundings gives image1
+ * bit for bit; so does an image with a side under 11 pixels; nothing further than 33 pixels from a pixel with m > 0 changes.
+ * NOT handled: sharpening (a generated side softer than the ring is left alone); focus that varies across the mask (one variance
+ * per frame or per clip); textures without edges (they fall under LP_FOCUS_MIN_COUNT and nothing happens).
+ *
+ * Workspace, LP_FOCUS_WS_BYTES(batch, height, width, channels) bytes, contents need not be set (no byte is read before it is
+ * written), at the offsets of the macros below, each a multiple of 16:
+ *   FLAGS  uint8 [batch][ceil(height / 32)][ceil(width / 32)], rows of mask_batch images used: bit 0 a masked pixel, bit 1 m > 0
+ *   STATS  int64 [batch][2][3]: region 0 ring, 1 inside; {n, SA, SB}
+ *   VAR    fp64  [batch][2]: var_ring, var_inside as fitted (pooled: the same pair in every row)
+ *   K      int32 [batch]                       TAPS   fp32 [batch][LP_FOCUS_TAPS]: w(i) at index 33 + i
+ *   PLANE  fp32  [batch][height][width][channels]: the rows pass
+ * Five launches on `stream`: flags (it also clears STATS), stats, fit (one block), rows, columns.  The blur is two launches through
+ * PLANE, not one launch with a 33-pixel halo in LDS: at four channels that tile is 98 x 98 x 16 bytes = 150 KB of the 160 KB a CU
+ * has, one block a CU.                                                                                                          */
+#define LP_FOCUS_MAX_RING  8
+#define LP_FOCUS_MIN_COUNT 64
+#define LP_FOCUS_MAX_VAR   16
+#define LP_FOCUS_NO_FIT    (-1.0)
+#define LP_FOCUS_TILE      32
+#define LP_FOCUS_TAPS      67
+#define LP_MULTIBAND_FOCUS(edge, ring, strength16, per_frame)                                                               \
+    ((int32_t)(0x80000000u | (uint32_t)(edge) | ((uint32_t)(ring) << 8) | ((uint32_t)(strength16) << 12) | ((uint32_t)(per_frame) << 17)))
+#define LP_FOCUS_R16(n) (((int64_t)(n) + 15) / 16 * 16)
+#define LP_FOCUS_TILES(s) (((int64_t)(s) + LP_FOCUS_TILE - 1) / LP_FOCUS_TILE)
+#define LP_FOCUS_WS_FLAGS(batch, height, width, channels) ((int64_t)0)
+#define LP_FOCUS_WS_STATS(batch, height, width, channels) LP_FOCUS_R16((int64_t)(batch) * LP_FOCUS_TILES(height) * LP_FOCUS_TILES(width))
+#define LP_FOCUS_WS_VAR(batch, height, width, channels) (LP_FOCUS_WS_STATS(batch, height, width, channels) + (int64_t)(batch) * 48)
+#define LP_FOCUS_WS_K(batch, height, width, channels) (LP_FOCUS_WS_VAR(batch, height, width, channels) + (int64_t)(batch) * 16)
+#define LP_FOCUS_WS_TAPS(batch, height, width, channels) (LP_FOCUS_WS_K(batch, height, width, channels) + LP_FOCUS_R16((int64_t)(batch) * 4))
+#define LP_FOCUS_WS_PLANE(batch, height, width, channels)                                                                   \
+    (LP_FOCUS_WS_TAPS(batch, height, width, channels) + LP_FOCUS_R16((int64_t)(batch) * LP_FOCUS_TAPS * 4))
+#define LP_FOCUS_WS_BYTES(batch, height, width, channels)                                                                   \
+    (LP_FOCUS_WS_PLANE(batch, height, width, channels) + LP_FOCUS_R16((int64_t)(batch) * (height) * (width) * (channels) * 4))
+
 /* ---- Mask refine (beyond the reference) ---------------------------------------------------------------------------------------
  * Every node after the sampler takes the mask as given, and the mask is what nobody helps the user with: a painted blob, or the
  * SDF morph of two blobs, follows the subject's centroid and not its outline.  lp_mask_refine is the colour guided filter (He,

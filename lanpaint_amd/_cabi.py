@@ -355,6 +355,36 @@ def multiband_ws_bytes(batch, height, width, channels, levels):
     return max(16, (int(batch) * pix * (2 * int(channels) + 1) * 4 + 15) // 16 * 16)
 
 
+LP_FOCUS_MAX_RING, LP_FOCUS_MIN_COUNT, LP_FOCUS_MAX_VAR, LP_FOCUS_NO_FIT, LP_FOCUS_TILE, LP_FOCUS_TAPS = 8, 64, 16, -1.0, 32, 67
+
+
+def LP_MULTIBAND_FOCUS(edge, ring, strength16, per_frame):
+    """The header's macro: lp_multiband_blend's focus form as the (negative) int32 mode word of `levels`."""
+    return ((0x80000000 | edge | (ring << 8) | (strength16 << 12) | (per_frame << 17)) & 0xFFFFFFFF) - (1 << 32)
+
+
+def focus_ws_layout(batch, height, width, channels):
+    """The focus form's workspace as the header's LP_FOCUS_WS_* macros lay it out: byte offsets of "flags" (uint8 [batch, th, tw]),
+    "stats" (int64 [batch, 2, 3]), "var" (fp64 [batch, 2]), "K" (int32 [batch]), "taps" (fp32 [batch, 67]), "plane" (fp32
+    [batch, height, width, channels]) and the total as "bytes"."""
+    r16 = lambda n: (n + 15) // 16 * 16                              # noqa: E731
+    b, h, w, c = int(batch), int(height), int(width), int(channels)
+    tile = LP_FOCUS_TILE
+    out = {"flags": 0}
+    out["stats"] = r16(b * ((h + tile - 1) // tile) * ((w + tile - 1) // tile))
+    out["var"] = out["stats"] + b * 48
+    out["K"] = out["var"] + b * 16
+    out["taps"] = out["K"] + r16(b * 4)
+    out["plane"] = out["taps"] + r16(b * LP_FOCUS_TAPS * 4)
+    out["bytes"] = out["plane"] + r16(b * h * w * c * 4)
+    return out
+
+
+def focus_ws_bytes(batch, height, width, channels):
+    """LP_FOCUS_WS_BYTES of include/lanpaint_hip.h: what lp_multiband_ws_bytes returns for a focus word inside the limits."""
+    return focus_ws_layout(batch, height, width, channels)["bytes"]
+
+
 LP_REFINE_MAX_RADIUS = 64
 
 

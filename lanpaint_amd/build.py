@@ -14,7 +14,7 @@ ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 SOURCES = ["step_kernel.hip", "aux_kernels.hip", "blend_kernel.hip", "videomask_kernel.hip", "audio_kernel.hip",
            "detail_kernel.hip", "label_kernel.hip", "color_kernel.hip", "fill_kernel.hip", "patch_fill_kernel.hip",
-           "multiband_kernel.hip", "refine_kernel.hip", "stabilize_kernel.hip", "grain_kernel.hip",
+           "multiband_kernel.hip", "focus_kernel.hip", "refine_kernel.hip", "stabilize_kernel.hip", "grain_kernel.hip",
            "propagate_kernel.hip", "temporal_fill_kernel.hip", "temporal_smooth_kernel.hip",
            "shot_kernel.hip", "cabi.hip"]
 HEADERS = [os.path.join(CSRC, "lp_common.h"), os.path.join(CSRC, "mask_tile.h"), os.path.join(CSRC, "resample_tile.h"),

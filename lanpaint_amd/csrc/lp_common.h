@@ -791,6 +791,13 @@ int patch_fill_check(const lp_fill_desc& d);
 // the patch form behind the push-pull launches: d.out holds the push-pull result, d.ws the push-pull part first
 int patch_fill_enqueue(const lp_fill_desc& d, hipStream_t stream);
 
+// ---- what multiband_kernel.hip's lp_multiband_blend and lp_multiband_ws_bytes call in focus_kernel.hip: the focus form, levels < 0 ----
+bool focus_word_ok(int32_t levels);
+// LP_OK, or the refusal of the mode word, of the batch or of a pooled clip above 2^30 pixels; no HIP call
+int focus_check(int32_t batch, int32_t height, int32_t width, int32_t levels);
+// the five launches; d has passed lp_multiband_blend's checks and d.ws holds LP_FOCUS_WS_BYTES(...) bytes
+int focus_enqueue(const lp_multiband_desc& d, hipStream_t stream);
+
 // The 8-bit code of a value in 0..1 (the propagate section's "1 luma"; the grain and refine sections' codes): clamped, times 255,
 // rounded half up; a NaN gives 0.  A site that packs codes into a word casts to its unsigned type.
 __device__ __forceinline__ int code_of(float v) {

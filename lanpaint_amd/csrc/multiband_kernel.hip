@@ -16,6 +16,7 @@
 // level below or above as the previous launch left it; nothing waits inside a launch.  The rule fixes every value and the
 // order of every operation, so tiling, halos and vector width cannot change a bit; every product, sum and difference below is
 // one __f*_rn call (the library is built with -ffp-contract=on).
+// A negative `levels` is the focus form's mode word: the entry's checks, then focus_kernel.hip's launches.
 // Entry points defined here: lp_multiband_blend, lp_multiband_ws_bytes.
 #include "lp_common.h"
 
@@ -247,7 +248,11 @@ int multiband_levels(int H, int W, int levels, int32_t* h, int32_t* w, int64_t* 
 }  // namespace
 
 extern "C" int64_t lp_multiband_ws_bytes(int32_t batch, int32_t height, int32_t width, int32_t channels, int32_t levels) {
-    if (batch <= 0 || !side_ok(height) || !side_ok(width) || !chan_ok(channels) || levels < 0) return LP_E_INVALID;
+    if (batch <= 0 || !side_ok(height) || !side_ok(width) || !chan_ok(channels)) return LP_E_INVALID;
+    if (levels < 0) {                                                // the focus form (focus_kernel.hip)
+        const int st = focus_check(batch, height, width, levels);
+        return st != LP_OK ? st : LP_FOCUS_WS_BYTES(batch, height, width, channels);
+    }
     if (batch > 65535) return LP_E_UNSUPPORTED;
     int32_t h[kMaxLevels + 1], w[kMaxLevels + 1];
     int64_t off[kMaxLevels + 1], pix;
@@ -260,12 +265,16 @@ extern "C" int lp_multiband_blend(const lp_multiband_desc* dp, void* stream_) {
     const hipStream_t stream = as_stream(stream_);
     if (!dp) return LP_E_INVALID;
     const lp_multiband_desc& d = *dp;
-    if (d.batch <= 0 || !side_ok(d.height) || !side_ok(d.width) || !chan_ok(d.channels) || d.levels < 0) return LP_E_INVALID;
+    if (d.batch <= 0 || !side_ok(d.height) || !side_ok(d.width) || !chan_ok(d.channels) || (d.levels < 0 && !focus_word_ok(d.levels)))
+        return LP_E_INVALID;
     if (!d.image1 || !d.image2 || !d.mask || !d.out || !d.ws || d.out == d.image1 || d.out == d.image2) return LP_E_INVALID;
     if (d.mask_batch != 1 && d.mask_batch != d.batch) return LP_E_INVALID;
     if (d.batch > 65535) return LP_E_UNSUPPORTED;
     if (!aligned16(d.ws)) return LP_E_ALIGN;
-    if (d.ws_bytes < lp_multiband_ws_bytes(d.batch, d.height, d.width, d.channels, d.levels)) return LP_E_INVALID;
+    const int64_t need = lp_multiband_ws_bytes(d.batch, d.height, d.width, d.channels, d.levels);
+    if (need < 0) return static_cast<int>(need);                     // (the focus form's pooled limit; never for levels >= 0 here)
+    if (d.ws_bytes < need) return LP_E_INVALID;
+    if (d.levels < 0) return focus_enqueue(d, stream);
     int32_t h[kMaxLevels + 1], w[kMaxLevels + 1];
     int64_t off[kMaxLevels + 1], pix;
     const int n = multiband_levels(d.height, d.width, d.levels, h, w, off, &pix);

@@ -1,0 +1,284 @@
+"""The focus form of lp_multiband_blend (LP_MULTIBAND_FOCUS), the parts that need no device: the mode macro and the workspace
+macros against their Python twins, the entry's refusals (made before any HIP call), levels >= 0 left alone, the wrapper's and the
+node's errors, and what the node promises -- measured on the restatement (tests/focus_ref.py), because the device is held to the
+restatement's bits by tests/test_gpu_focus.py.
+
+The quality claim: on the 192 x 192 Voronoi scene (60 random grey cells, seeds 0, 1, 2), blurred outside a sharp central 96 x 96
+mask by a Gaussian of sigma 1, 1.5 and 2, the sigma of the blur the fit applies, sqrt(K / 32), is held to the true sigma.  The
+restatement's relative errors (numpy on a CPU), seed by seed for sigma (1, 1.5, 2): 0.190 0.184 0.195 / 0.134 0.134 0.152 /
+0.116 0.134 0.157, worst 0.195 -- it reads low, because the edge pixels are picked by their gradient and lie at the centre of an edge,
+where the ratio of the two scales is larger than over the whole edge.  ALLOWANCE is 1.5 times that worst case."""
+import ctypes
+import os
+import subprocess
+
+import numpy as np
+import pytest
+import torch
+
+from lanpaint_amd import _cabi
+from tests import cabi_header
+from tests import focus_ref as fref
+from tests import focus_scenes as scenes
+
+WORST_MEASURED = 0.195
+ALLOWANCE = 1.5 * WORST_MEASURED
+WORDS = [(1, 1, 0, 0), (8, 2, 16, 0), (255, 8, 16, 1), (128, 3, 7, 1), (17, 5, 1, 0)]
+WS_CASES = [(1, 1, 1, 1), (2, 17, 33, 3), (3, 32, 32, 4), (1, 2049, 1, 1), (81, 720, 1280, 3), (7, 40, 150, 5), (65535, 32768, 32768, 64)]
+PARTS = ("FLAGS", "STATS", "VAR", "K", "TAPS", "PLANE", "BYTES")
+
+
+def _call(macro, args):
+    return "%s(%s)" % (macro, ", ".join(map(str, args)))
+
+
+@pytest.fixture(scope="module")
+def c_values(tmp_path_factory):
+    """What gcc makes of the header's focus macros at WORDS and WS_CASES, and of the limits."""
+    show = lambda key, expr: 'printf("%s\\t%lld\\n", "{}", (long long)({}));'.format(key, expr)       # noqa: E731
+    prog = ["#include <stdio.h>", '#include "lanpaint_hip.h"', "int main(void){"]
+    prog += [show(_call("LP_MULTIBAND_FOCUS", m), _call("LP_MULTIBAND_FOCUS", m)) for m in WORDS]
+    for case in WS_CASES:
+        prog += [show(_call(p, case), _call("LP_FOCUS_WS_" + p, case)) for p in PARTS]
+    prog += [show(n, n) for n in ("LP_FOCUS_MAX_RING", "LP_FOCUS_MIN_COUNT", "LP_FOCUS_MAX_VAR", "LP_FOCUS_TILE", "LP_FOCUS_TAPS",
+                                  "(int)LP_FOCUS_NO_FIT")]
+    prog.append("return 0;}")
+    tmp = tmp_path_factory.mktemp("focus")
+    (tmp / "m.c").write_text("\n".join(prog))
+    subprocess.run(["gcc", "-I", os.path.join(cabi_header.ROOT, "include"), str(tmp / "m.c"), "-o", str(tmp / "m")], check=True)
+    out = subprocess.run([str(tmp / "m")], check=True, capture_output=True, text=True).stdout
+    return {k: int(v) for k, v in (line.split("\t") for line in out.splitlines())}
+
+
+# ---- the macros -------------------------------------------------------------------------------------------------------------------------
+def test_the_mode_macro_and_the_limits_agree_with_their_python_twins(c_values):
+    for m in WORDS:
+        word = _cabi.LP_MULTIBAND_FOCUS(*m)
+        assert word == c_values[_call("LP_MULTIBAND_FOCUS", m)] == fref.mode_word(*m), m
+        assert -(1 << 31) <= word < 0 and _cabi.LpMultibandDesc(levels=word).levels == word
+        u = word & 0xFFFFFFFF
+        assert (u & 255, (u >> 8) & 15, (u >> 12) & 31, (u >> 17) & 1, (u >> 18) & 0x1FFF, u >> 31) == (*m, 0, 1)
+    assert _cabi.LP_MULTIBAND_FOCUS(8, 2, 16, 0) == 0x80010208 - (1 << 32)
+    assert (-1 & 0xFFFFFFFF) >> 18 & 0x1FFF                              # levels = -1 has bits 18..30 set: no focus word
+    for name in ("MAX_RING", "MIN_COUNT", "MAX_VAR", "TILE", "TAPS"):
+        assert getattr(_cabi, "LP_FOCUS_" + name) == c_values["LP_FOCUS_" + name]
+    assert c_values["(int)LP_FOCUS_NO_FIT"] == _cabi.LP_FOCUS_NO_FIT == fref.NO_FIT == -1
+    assert (fref.MAX_RING, fref.MIN_COUNT, fref.MAX_VAR, fref.TILE, fref.TAPS) == (8, 64, 16, 32, 67) == \
+        tuple(getattr(_cabi, "LP_FOCUS_" + n) for n in ("MAX_RING", "MIN_COUNT", "MAX_VAR", "TILE", "TAPS"))
+
+
+def test_the_workspace_macros_agree_with_the_mirror_and_the_layout(c_values, hip_lib):
+    for case in WS_CASES:
+        b, h, w, c = case
+        layout = _cabi.focus_ws_layout(*case)
+        for part in PARTS:
+            assert layout[part.replace("BYTES", "bytes") if part in ("BYTES", "K") else part.lower()] == c_values[_call(part, case)], (case, part)
+        th, tw = -(-h // 32), -(-w // 32)
+        at = 0
+        for name, size in (("flags", b * th * tw), ("stats", b * 48), ("var", b * 16), ("K", b * 4), ("taps", b * 67 * 4),
+                           ("plane", b * h * w * c * 4)):
+            assert layout[name] == at and at % 16 == 0, (case, name)
+            at += (size + 15) // 16 * 16
+        assert at == layout["bytes"] == _cabi.focus_ws_bytes(*case)
+    # the size function: per_frame takes any batch it accepts, the pooled form stops at 2^30 pixels
+    per_frame, pooled = _cabi.LP_MULTIBAND_FOCUS(8, 2, 16, 1), _cabi.LP_MULTIBAND_FOCUS(8, 2, 16, 0)
+    for case in WS_CASES[:-1]:
+        assert hip_lib.lp_multiband_ws_bytes(*case, per_frame) == hip_lib.lp_multiband_ws_bytes(*case, pooled) == _cabi.focus_ws_bytes(*case)
+    assert hip_lib.lp_multiband_ws_bytes(65535, 32768, 32768, 64, per_frame) == _cabi.focus_ws_bytes(65535, 32768, 32768, 64)
+    assert hip_lib.lp_multiband_ws_bytes(65535, 32768, 32768, 64, pooled) == _cabi.LP_E_UNSUPPORTED
+    assert hip_lib.lp_multiband_ws_bytes(1, 32768, 32768, 3, pooled) == _cabi.focus_ws_bytes(1, 32768, 32768, 3)      # 2^30 exactly
+    assert hip_lib.lp_multiband_ws_bytes(2, 32768, 32768, 3, pooled) == _cabi.LP_E_UNSUPPORTED
+    assert hip_lib.lp_multiband_ws_bytes(65536, 8, 8, 3, per_frame) == _cabi.LP_E_UNSUPPORTED
+    for bad in (-1, _cabi.LP_MULTIBAND_FOCUS(0, 2, 16, 0), _cabi.LP_MULTIBAND_FOCUS(8, 9, 16, 0)):
+        assert hip_lib.lp_multiband_ws_bytes(2, 40, 150, 3, bad) == _cabi.LP_E_INVALID
+    assert hip_lib.lp_multiband_ws_bytes(0, 40, 150, 3, pooled) == _cabi.LP_E_INVALID
+    # the plain form's sizes are what they were
+    for levels in (0, 1, 5, 16):
+        assert hip_lib.lp_multiband_ws_bytes(2, 40, 150, 3, levels) == _cabi.multiband_ws_bytes(2, 40, 150, 3, levels)
+    # 81 frames of 720p: the plane and little more, under the wrapper's 1 GiB
+    assert 81 * 720 * 1280 * 3 * 4 < _cabi.focus_ws_bytes(81, 720, 1280, 3) < 81 * 720 * 1280 * 3 * 4 + (1 << 20) < 1 << 30
+
+
+# ---- the entry's refusals ---------------------------------------------------------------------------------------------------------------
+def _good(hip_lib, word, **change):
+    p, q = ctypes.c_void_p(256), ctypes.c_void_p(512)                  # never dereferenced: validation comes before any HIP call
+    d = dict(batch=2, height=40, width=150, channels=3, mask_batch=1, levels=word, image1=p, image2=p, mask=p, out=q, ws=p,
+             ws_bytes=_cabi.focus_ws_bytes(2, 40, 150, 3))
+    d.update(change)
+    return hip_lib.lp_multiband_blend(ctypes.byref(_cabi.LpMultibandDesc(**d)), None)
+
+
+def _signed(u):
+    return u - (1 << 32) if u >= 1 << 31 else u
+
+
+def test_the_focus_form_refuses_a_bad_word_without_a_device(hip_lib):
+    E, U, A = _cabi.LP_E_INVALID, _cabi.LP_E_UNSUPPORTED, _cabi.LP_E_ALIGN
+    M = _cabi.LP_MULTIBAND_FOCUS
+    good = M(8, 2, 16, 0)
+    # a word that passes every check but the workspace's: the refusals below are the word's and nothing else's
+    assert _good(hip_lib, good, ws_bytes=_cabi.focus_ws_bytes(2, 40, 150, 3) - 1) == E
+    assert _good(hip_lib, good, ws=260) == A                           # reached only by a word that is accepted
+    for fine in (M(1, 1, 0, 0), M(255, 8, 16, 1), M(8, 2, 0, 1)):
+        assert _good(hip_lib, fine, ws=260) == A, hex(fine & 0xFFFFFFFF)
+    # every field at 0 and one above its limit (edge 256 does not fit its eight bits: it arrives as edge 0 with a ring bit;
+    # strength16 0 is allowed; per_frame 2 is bit 18)
+    for bad in (M(0, 2, 16, 0), M(256, 2, 16, 0), M(8, 0, 16, 0), M(8, 9, 16, 0), M(8, 15, 16, 0), M(8, 2, 17, 0), M(8, 2, 31, 0),
+                M(8, 2, 16, 2)):
+        assert _good(hip_lib, bad, ws=260) == E, hex(bad & 0xFFFFFFFF)
+    for bit in range(18, 31):
+        assert _good(hip_lib, _signed((good & 0xFFFFFFFF) | (1 << bit)), ws=260) == E, bit
+    assert _good(hip_lib, -1, ws=260) == E and _good(hip_lib, -1) == E
+    assert _good(hip_lib, _signed(0x80000000), ws=260) == E            # the bare sign: edge 0
+    # a workspace one byte short; the plain form's size is far too small
+    need = _cabi.focus_ws_bytes(2, 40, 150, 3)
+    assert _good(hip_lib, good, ws_bytes=need - 1) == E and _good(hip_lib, good, ws_bytes=_cabi.multiband_ws_bytes(2, 40, 150, 3, 5)) == E
+    # the checks of the plain form hold under the focus word, in its order: alignment is answered before a short workspace
+    for change in ({"batch": 0}, {"height": 0}, {"width": _cabi.LP_DETAIL_MAX_SIDE + 1}, {"channels": 0},
+                   {"channels": _cabi.LP_DETAIL_MAX_CHANNELS + 1}, {"mask_batch": 3}, {"image1": None}, {"image2": None}, {"mask": None},
+                   {"out": None}, {"ws": None}, {"out": ctypes.c_void_p(256)}):
+        assert _good(hip_lib, good, **change) == E, change
+    assert _good(hip_lib, good, image2=ctypes.c_void_p(512)) == E      # out == image2 stays a refusal
+    assert _good(hip_lib, good, ws=260, ws_bytes=1) == A
+    assert _good(hip_lib, good, batch=65536, ws_bytes=1 << 50) == U
+    assert _good(hip_lib, good, batch=2, height=32768, width=32768, ws_bytes=1 << 60) == U           # pooled above 2^30 pixels
+    assert _good(hip_lib, M(8, 2, 16, 1), batch=2, height=32768, width=32768, ws_bytes=1 << 60, ws=260) == A
+
+
+def test_levels_zero_and_up_keep_their_checks(hip_lib):
+    E, A = _cabi.LP_E_INVALID, _cabi.LP_E_ALIGN
+    for levels in (0, 5):
+        ws = _cabi.multiband_ws_bytes(2, 40, 150, 3, levels)
+        assert _good(hip_lib, levels, ws_bytes=ws - 1 if levels else 15) == E
+        assert _good(hip_lib, levels, ws_bytes=ws, ws=260) == A
+        assert _good(hip_lib, levels, ws_bytes=1, ws=260) == A
+
+
+# ---- the wrapper and the node -----------------------------------------------------------------------------------------------------------
+def test_the_wrapper_refuses_cpu_tensors_and_bad_arguments():
+    from lanpaint_amd import focus
+    img, mask = torch.zeros(2, 16, 16, 3), torch.zeros(2, 16, 16)
+    with pytest.raises(RuntimeError, match="no CPU fallback"):
+        focus.match_focus(img, mask)
+    with pytest.raises(RuntimeError, match="no CPU fallback"):
+        focus.focus_report(img, mask)
+
+    class OnDevice(torch.Tensor):                                      # passes require_hip; the checks below come before any device work
+        is_cuda = True
+
+    dev_img, dev_mask = img.as_subclass(OnDevice), mask.as_subclass(OnDevice)
+    with pytest.raises(RuntimeError, match="reference"):
+        focus.match_focus(dev_img, dev_mask, reference=img)
+    for bad in (dict(strength=-0.1), dict(strength=1.5), dict(strength=float("nan")), dict(strength=True), dict(edge=0), dict(edge=256),
+                dict(edge=8.0), dict(ring=0), dict(ring=9), dict(ring=True), dict(per_frame=2), dict(per_frame="yes")):
+        with pytest.raises(ValueError, match=next(iter(bad))):
+            focus.match_focus(dev_img, dev_mask, **bad)
+    with pytest.raises(ValueError, match="reference shape"):
+        focus.match_focus(dev_img, dev_mask, reference=torch.zeros(2, 16, 17, 3).as_subclass(OnDevice))
+    with pytest.raises(ValueError, match=r"\[B, H, W, C\]"):
+        focus.match_focus(torch.zeros(8, 8, 3).as_subclass(OnDevice), dev_mask)
+    assert focus.WS_CAP_BYTES == 1 << 30 and focus.NO_FIT == -1.0
+
+
+def test_the_node_keeps_the_protocol_and_has_no_cpu_fallback():
+    from lanpaint_amd import focus_nodes as mod
+    node = mod.LanPaint_FocusMatch
+    assert mod.NODE_CLASS_MAPPINGS == {"LanPaint_FocusMatch": node}
+    assert mod.NODE_DISPLAY_NAME_MAPPINGS == {"LanPaint_FocusMatch": "LanPaint Focus Match"}
+    types = node.INPUT_TYPES()
+    req = types["required"]
+    assert list(req) == ["image", "mask", "strength", "edge", "ring", "per_frame"] and list(types["optional"]) == ["reference"]
+    assert req["image"][0] == "IMAGE" and req["mask"][0] == "MASK" and types["optional"]["reference"][0] == "IMAGE"
+    assert req["strength"][0] == "FLOAT" and req["strength"][1] == {**req["strength"][1], "default": 1.0, "min": 0.0, "max": 1.0}
+    for name, default, lo, hi in (("edge", 8, 1, 255), ("ring", 2, 1, 8)):
+        assert req[name][0] == "INT" and req[name][1] == {**req[name][1], "default": default, "min": lo, "max": hi}, name
+    assert req["per_frame"][0] == "BOOLEAN" and req["per_frame"][1]["default"] is False
+    assert node.RETURN_TYPES == ("IMAGE",) and node.RETURN_NAMES == ("image",) and node.FUNCTION == "match"
+    for said in ("never sharpens", "one blur per frame or clip", "without edges"):      # what is not handled is said where the user reads it
+        assert said in node.DESCRIPTION, said
+    if not torch.cuda.is_available():
+        with pytest.raises(RuntimeError, match="no CPU fallback"):
+            node().match(torch.zeros(2, 16, 16, 3), torch.zeros(2, 16, 16))
+
+
+def test_the_focus_kernels_are_a_source_of_the_build():
+    from lanpaint_amd import build
+    assert "focus_kernel.hip" in build.SOURCES and os.path.exists(os.path.join(build.CSRC, "focus_kernel.hip"))
+
+
+# ---- the restatement: what the node promises --------------------------------------------------------------------------------------------
+def _sigma2(out, mask):
+    """(var_ring, var_inside) as the rule measures them on `out` itself"""
+    st = fref.stats_of(out, out, mask, 8, 2)[0]
+    return [float(fref.variance_of(*map(int, st[side]))) for side in (0, 1)]
+
+
+@pytest.mark.parametrize("seed", [0, 1, 2])
+@pytest.mark.parametrize("sigma_true", [1.0, 1.5, 2.0])
+def test_the_fitted_blur_is_the_blur_of_the_surroundings(seed, sigma_true):
+    img, mask = scenes.soft_around_sharp(seed, sigma_true)
+    out, stats, var, K, taps = fref.match_focus_ref(img, img, mask)
+    assert stats[0, 0, 0] >= 64 and stats[0, 1, 0] >= 64
+    fitted = float(np.sqrt(K[0] / 32.0))
+    rel = abs(fitted - sigma_true) / sigma_true
+    ring, inside = _sigma2(out, mask)
+    after = abs(inside - ring) / ring
+    print(f"FOCUS_FIT seed {seed} sigma {sigma_true}: var ring {var[0, 0]:.3f} inside {var[0, 1]:.3f} K {K[0]} fitted sigma {fitted:.3f} "
+          f"rel {rel:.3f}; after the apply var ring {ring:.3f} inside {inside:.3f} rel {after:.3f}")
+    assert rel <= ALLOWANCE
+    assert after <= ALLOWANCE                                          # the inside's own estimate now lies at the ring's
+    # the taps are a kernel of the variance K / 32, and the surroundings keep their bits
+    i = np.arange(-33, 34, dtype=np.float64)
+    w = taps[0].astype(np.float64)
+    assert abs(w.sum() - 1) < 1e-6 and abs((w * i).sum()) < 1e-9 and abs((w * i * i).sum() - K[0] / 32.0) < 1e-5
+    known = ~(mask[0] > 0)
+    assert (out.view(np.uint32)[0][known] == img.view(np.uint32)[0][known]).all()
+    assert (out[0][~known] != img[0][~known]).any()
+
+
+def test_a_scene_blurred_everywhere_and_a_flat_scene_come_back_bit_for_bit():
+    sharp = scenes.voronoi(0)
+    mask = scenes.soft_around_sharp(0, 1.0)[1]
+    soft = scenes.quantised(scenes.gauss(sharp, 1.5))[None, :, :, None]
+    out, stats, var, K, _ = fref.match_focus_ref(soft, soft, mask)
+    assert stats[0, 0, 0] >= 64 and stats[0, 1, 0] >= 64                # both sides measured ...
+    assert K[0] == 0 and abs(var[0, 0] - var[0, 1]) < 0.35 * var[0, 0]   # ... alike (the inside reads softer here), so nothing is added
+    assert var[0, 1] >= var[0, 0]
+    assert (out.view(np.uint32) == soft.view(np.uint32)).all()
+    flat = np.full((1, 192, 192, 3), 0.5, np.float32)
+    out, stats, var, K, taps = fref.match_focus_ref(flat, flat, mask)
+    assert (stats == 0).all() and K[0] == 0 and (var == fref.NO_FIT).all() and (out.view(np.uint32) == flat.view(np.uint32)).all()
+    assert taps[0, 33] == 1 and np.count_nonzero(taps) == 1
+    # an inpaint softer than its surroundings is left alone: no sharpening
+    softer = np.array(soft)
+    softer[0, 48:144, 48:144, 0] = scenes.quantised(scenes.gauss(sharp, 2.5))[48:144, 48:144]
+    out, _, var, K, _ = fref.match_focus_ref(softer, soft, mask)
+    assert var[0, 1] > var[0, 0] > 0 and K[0] == 0 and (out.view(np.uint32) == softer.view(np.uint32)).all()
+
+
+def test_the_restatements_consequences():
+    """An all-zero mask, a side under 11 pixels: bit for bit.  Nothing further than 33 pixels from the mask changes.  strength
+    scales K.  Pooled and per-frame differ only in whose sums are fitted."""
+    img1, img2, mask = scenes.stripes(4.03)
+    out, stats, var, K, taps = fref.match_focus_ref(img1, img2, mask, edge=1)
+    assert K[0] == 512 and np.count_nonzero(taps[0]) == 65                 # the cap: k 32, t 0
+    none = np.zeros_like(mask)
+    out0, stats0, _, K0, _ = fref.match_focus_ref(img1, img2, none, edge=1)
+    assert K0[0] == 0 and (stats0 == 0).all() and (out0.view(np.uint32) == img1.view(np.uint32)).all()
+    small = np.ascontiguousarray(img1[:, :10])
+    outs, statss, _, Ks, _ = fref.match_focus_ref(small, small, np.ones((1, 10, 128), np.float32), edge=1)
+    assert Ks[0] == 0 and (statss == 0).all() and (outs.view(np.uint32) == small.view(np.uint32)).all()
+    # a soft mask that reaches further than the hard one: the change stays within its m > 0 and its size follows m
+    soft_mask = np.array(mask)
+    soft_mask[0, 20:24, 24:104] = 0.25
+    out2 = fref.match_focus_ref(img1, img2, soft_mask, edge=1)[0]
+    changed = out2.view(np.uint32)[0, :, :, 0] != img1.view(np.uint32)[0, :, :, 0]
+    assert changed[20:24].any() and not changed[soft_mask[0] == 0].any()
+    half = fref.match_focus_ref(img1, img2, mask, edge=1, strength16=8)[3]
+    assert half[0] == int(np.floor((var[0, 0] - var[0, 1]) * 16 + 0.5)) and 256 <= half[0] < 272      # half the uncapped difference
+    sharp = scenes.stripes(0.0)[0]                                     # sharp on both sides: nothing to add
+    two1, two2 = np.concatenate([img1, sharp]), np.concatenate([img2, sharp])
+    pooled = fref.match_focus_ref(two1, two2, mask, edge=1, per_frame=0)
+    each = fref.match_focus_ref(two1, two2, mask, edge=1, per_frame=1)
+    assert each[3][0] == 512 and each[3][1] == 0 and pooled[3][0] == pooled[3][1] and 0 < pooled[3][0] < 512
+    assert (each[1] == pooled[1]).all() and (each[0][1].view(np.uint32) == sharp[0].view(np.uint32)).all()
