@@ -1,6 +1,6 @@
 """include/lanpaint_hip.h as data, for tests/test_cabi_mirror.py: its structs, its LP_API prototypes and its object-like LP_* macros,
 read with regular expressions that know exactly the declaration shapes the header uses.  A declaration of another shape raises
-with its text: nothing is skipped."""
+with its text: nothing is skipped.  `_call` and `_signed` serve the tests that hand the header's macros to a C compiler."""
 import collections
 import keyword
 import os
@@ -71,3 +71,11 @@ def class_name(c_name):
 def field_name(c_name):
     """The Python field is the C field, plus a trailing underscore where that is a keyword (lambda -> lambda_)."""
     return c_name + "_" if keyword.iskeyword(c_name) else c_name
+
+
+def _call(macro, args):
+    return "%s(%s)" % (macro, ", ".join(map(str, args)))
+
+
+def _signed(u):
+    return u - (1 << 32) if u >= 1 << 31 else u

@@ -357,3 +357,28 @@ def array_digest(a):
 def effective_steps_grid():
     """(n, frac, MinStepFrac) of the dense grid the inner-step rule (nodes.py:134-144) is compared on."""
     return [(n, float(frac), mf) for n in range(0, 12) for frac in np.linspace(0.0, 1.0, 41) for mf in (0.0, 0.05, 0.3, 1.0)]
+
+
+def _options_for_call(sc):
+    """A fresh copy of the schedule's model_options with a trace list, per sigma call -- what the fixture's generator handed the
+    reference (tests/golden/make_golden.py::run_schedule); None for schedules without the inner early stop."""
+    if sc.get("model_options") is None:
+        return None
+    mo = {k: dict(v) if isinstance(v, dict) else v for k, v in sc["model_options"].items()}
+    mo["lanpaint_semantic_trace"] = []
+    return mo
+
+
+def check_schedule_traces(g, iterations, traces, name, rtol=2e-5):
+    """Iterations run per sigma call and the stopper's records, call after call, against the reference's (fixture)."""
+    assert iterations == list(g["iterations"]), f"{name}: iterations per sigma call"
+    flat = [t for tr in traces for t in tr]
+    assert [k for k, tr in enumerate(traces) for _ in tr] == list(g["trace_call"]), (
+        "the sigma call of every trace record against the fixture's trace_call")
+    assert [t["patience_counter"] for t in flat] == list(g["trace_counter"]) and [t["stopped"] for t in flat] == list(g["trace_stopped"]), (
+        "the stopper's patience counters and stopped flags against the fixture's")
+    for key in ("dist", "dist_inpaint", "dist_ring", "dist_drift", "threshold_eff", "abt"):
+        want = g["trace_" + key]
+        got = np.asarray([np.nan if t[key] is None else t[key] for t in flat], dtype=np.float64)
+        assert np.array_equal(np.isnan(got), np.isnan(want)), f"{name}: {key}"
+        np.testing.assert_allclose(got[~np.isnan(got)], want[~np.isnan(want)], rtol=rtol, err_msg=f"{name}: {key}")

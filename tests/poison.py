@@ -2,7 +2,7 @@
 chosen byte in every position.  The caching allocator gives a call the block the last call of the same shape released, which very
 often holds the right answer already; a kernel that reads a cell before it writes it, skips an output element or lets padding reach
 a result passes on such a block.  Under a poison the element shows: 0x00 reads as integer 0, 0.0 and flag false, 0xFF as integer
--1, NaN, flag true and byte 255.  Not a conftest: a test asks for it by name."""
+-1, NaN, flag true and byte 255.  Not a conftest: a test asks for it by name.  POISONS and poison_id parametrise the scratch tests."""
 import torch
 
 
@@ -28,3 +28,7 @@ def poisoned_empty(monkeypatch, byte):
     monkeypatch.setattr(torch, "empty", poisoned(torch.empty))
     monkeypatch.setattr(torch, "empty_like", poisoned(torch.empty_like))
     return filled
+
+
+POISONS = [0x00, 0xFF]
+poison_id = lambda b: f"0x{b:02X}"                                   # noqa: E731

@@ -1,10 +1,14 @@
 """The clips of the shot detect tests, in plain numpy: low-pass canvases of different tone that pan by 2 pixels a frame under a
 little noise, joined by hard cuts, and the three things that must not be called a cut -- a flash frame, a large box that moves
 further than the search, and a plain pan.  White-noise canvases (tests/temporal_clips.py) are no use here: at pyramid level 2
-two of them are the same grey mush.  Every clip is (images fp32 [F, H, W, 3], the frames at which a new shot begins)."""
+two of them are the same grey mush.  Every clip is (images fp32 [F, H, W, 3], the frames at which a new shot begins).  At the end, the scores and the per-shot fill
+case that tests/test_shots_host.py and tests/test_gpu_shots.py both use."""
 import functools
 
 import numpy as np
+
+from tests import shots_ref as sref
+from tests import temporal_fill_ref as tref
 
 H, W = 96, 128
 PAN = 2                                # pixels a frame, along x
@@ -93,3 +97,37 @@ def box_mask(frames, at, height=H, width=W):
     mask = np.zeros((frames, height, width), np.float32)
     mask[at - 1:at + 1, height // 3:height // 3 + 20, width // 3:width // 3 + 24] = 1.0
     return mask
+
+
+@functools.lru_cache(maxsize=None)
+def scores(name, level=2, search=2):
+    images, starts = CLIPS[name]()
+    return (*sref.shot_scores(images, level, search), starts)
+
+
+def expected_shot(frames, starts):
+    return np.searchsorted(np.asarray(starts, dtype=np.int64), np.arange(frames), side="right").astype(np.int32)
+
+
+FILL_FRAMES, FILL_CUT, FILL_LEVELS = 6, 3, 3
+
+
+@functools.lru_cache(maxsize=None)
+def fill_case():
+    """(images, mask, ranges, the whole clip's fill, the per-shot composition): the two-shot clip, a box under the mask in the two
+    frames beside the cut.  tests/test_gpu_shots.py compares the device with both."""
+    images, starts = two_shots(FILL_FRAMES, FILL_CUT)
+    mask = box_mask(FILL_FRAMES, FILL_CUT)
+    ranges = [(0, FILL_CUT), (FILL_CUT, FILL_FRAMES)]
+    whole = tref.temporal_fill_ref(images, mask, levels=FILL_LEVELS)
+    parts = [tref.temporal_fill_ref(images[lo:hi], mask[lo:hi], levels=FILL_LEVELS) for lo, hi in ranges]
+    source = np.concatenate([np.where(p[2] >= 0, p[2] + lo, p[2]) for p, (lo, hi) in zip(parts, ranges)])
+    composed = (np.concatenate([p[0] for p in parts]), np.concatenate([p[1] for p in parts]), source)
+    return images, mask, ranges, whole, composed
+
+
+def foreign_sources(source, mask, ranges):
+    """The masked pixels whose source frame lies in another shot than the pixel."""
+    shot = expected_shot(source.shape[0], [lo for lo, _ in ranges[1:]])
+    of_source = shot[np.clip(source, 0, None)]
+    return int(((mask >= 0.5) & (source >= 0) & (of_source != shot[:, None, None])).sum())

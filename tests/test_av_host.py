@@ -15,66 +15,14 @@ import torch
 from lanpaint_amd import _cabi, audio, av_nodes, interp_rule
 from oracle import lanpaint_oracle as orc
 from tests import audio_ref, av_stubs
+from tests.audio_ref import RULE_NAMES, fixture_id, host_rule, load_fixture as load, restated_merge, weights_f64
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden")
 MERGE_FIXTURES = sorted(glob.glob(os.path.join(GOLDEN, "av_merge_*.npz")))
-RULE_NAMES = {_cabi.LP_NN_ATEN_SCALAR: "scalar", _cabi.LP_NN_ATEN_CPU_GENERIC_FMA: "generic_fma",
-              _cabi.LP_NN_ATEN_CPU_GENERIC: "generic"}
-
-
-def fixture_id(path):
-    return os.path.basename(path)[len("av_merge_"):-4]
-
-
-def load(path):
-    z = np.load(path)
-    return {k: z[k] for k in z.files}
 
 
 # ---------------------------------------------------------------- float64 restatement of what lp_audio_merge computes
-def weights_f64(am, n, cf, rule):
-    """w' of include/lanpaint_hip.h (lp_audio_desc): the up-sampled mask, then float(S * double(1.0f / cf)) with S the
-    replicate-clamped window sum, here from a plain float64 cumulative sum over the samples."""
-    am = np.asarray(am, np.float32)
-    w = am if am.shape[0] == n else am[orc.nearest_exact_src_index(n, am.shape[0], RULE_NAMES[rule])]
-    w = w.astype(np.float64)
-    if cf <= 1:
-        return w.astype(np.float32)
-    c = np.concatenate([[0.0], np.cumsum(w)])
-    i = np.arange(n, dtype=np.int64)
-    lo_raw = i - cf // 2
-    hi_raw = lo_raw + cf
-    lo, hi = np.maximum(lo_raw, 0), np.minimum(hi_raw, n)
-    s = (lo - lo_raw) * w[0] + (hi_raw - hi) * w[-1] + (c[hi] - c[lo])
-    return (s * np.float64(np.float32(1.0) / np.float32(cf))).astype(np.float32)
-
-
-def lerp_f32(o, p, w):
-    """o * (1 - w) + p * w in fp32, every operation rounded (what torch's separate ops do)."""
-    w = np.asarray(w, np.float32)
-    return (o.astype(np.float32) * (np.float32(1) - w) + p.astype(np.float32) * w).astype(np.float32)
-
-
-def restated_merge(rec, rule):
-    """The whole merge on equal-rate inputs, restated on numpy arrays with the reference's channel rule."""
-    o, p = rec["orig"], rec["inpainted"]
-    n = min(o.shape[-1], p.shape[-1])
-    o, p = o[..., :n], p[..., :n]
-    am = audio.normalize_mask(torch.from_numpy(rec["mask"])).numpy()
-    w = weights_f64(am, n, audio.crossfade_samples(float(rec["crossfade"]), int(rec["orig_sr"])), rule)
-    if o.shape[1] != p.shape[1] and o.shape[1] != 1 and p.shape[1] != 1:
-        o = o[:, :p.shape[1]]
-    return lerp_f32(o, p, w[None, None]), w
-
-
-def host_rule(rec):
-    """The index rule torch's CPU kernel takes for the fixtures' host masks (what the reference ran)."""
-    am = audio.normalize_mask(torch.from_numpy(rec["mask"]))
-    n = min(rec["orig"].shape[-1], rec["inpainted"].shape[-1])
-    return interp_rule.rule_for(am, am.reshape(1, 1, -1), (n,))
-
-
 def test_fixtures_are_present():
     names = {fixture_id(p) for p in MERGE_FIXTURES}
     assert len(names) >= 12 and {"hard_even_cf", "per_sample_odd_cf", "cf_ge_n", "tie_2_to_41", "err_channels"} <= names

@@ -18,6 +18,7 @@ import pytest
 
 from lanpaint_amd import _cabi
 from tests import cabi_header
+from tests.cabi_header import _call
 
 ROOT = cabi_header.ROOT
 HEADER = cabi_header.parse()
@@ -72,10 +73,6 @@ MACROS = [
     ("LP_COMPONENTS_FRAMES_WS_BYTES", _cabi.lp_components_frames_ws_bytes, [(1, 1, 1), (81, 720, 1280), (65535, 128, 128), (1, 720, 1280)]),
     ("LP_PROP_MATCH_GATED", _cabi.LP_PROP_MATCH_GATED, [(16,), (1,), (255,)]),
 ]
-
-
-def _call(macro, args):
-    return "%s(%s)" % (macro, ", ".join(map(str, args)))
 
 
 @pytest.fixture(scope="module")

@@ -20,16 +20,13 @@ from lanpaint_amd import _cabi
 from tests import cabi_header
 from tests import focus_ref as fref
 from tests import focus_scenes as scenes
+from tests.cabi_header import _call, _signed
 
 WORST_MEASURED = 0.195
 ALLOWANCE = 1.5 * WORST_MEASURED
 WORDS = [(1, 1, 0, 0), (8, 2, 16, 0), (255, 8, 16, 1), (128, 3, 7, 1), (17, 5, 1, 0)]
 WS_CASES = [(1, 1, 1, 1), (2, 17, 33, 3), (3, 32, 32, 4), (1, 2049, 1, 1), (81, 720, 1280, 3), (7, 40, 150, 5), (65535, 32768, 32768, 64)]
 PARTS = ("FLAGS", "STATS", "VAR", "K", "TAPS", "PLANE", "BYTES")
-
-
-def _call(macro, args):
-    return "%s(%s)" % (macro, ", ".join(map(str, args)))
 
 
 @pytest.fixture(scope="module")
@@ -106,10 +103,6 @@ def _good(hip_lib, word, **change):
              ws_bytes=_cabi.focus_ws_bytes(2, 40, 150, 3))
     d.update(change)
     return hip_lib.lp_multiband_blend(ctypes.byref(_cabi.LpMultibandDesc(**d)), None)
-
-
-def _signed(u):
-    return u - (1 << 32) if u >= 1 << 31 else u
 
 
 def test_the_focus_form_refuses_a_bad_word_without_a_device(hip_lib):

@@ -8,11 +8,13 @@ import pytest
 import torch
 
 from lanpaint_amd import propagate, propagate_anchored, propagate_anchored_visible, propagate_visible
+from tests import device, inputs, motion_checks
 from tests import propagate_anchored_visible_ref as avref
-from tests import test_gpu_propagate_anchored_visible as t_both
+from tests.compare import _same_bits, _same_ints as _same
+from tests.device import DELAY_MS, _spin_cycles_per_ms
 from tests.helpers import record_launches
-from tests.poison import poisoned_empty
-from tests.test_gpu_motion_scratch import DELAY_MS, POISONS, SMALL, _same, _same_bits, _spin_cycles_per_ms, poison_id
+from tests.inputs import SMALL
+from tests.poison import POISONS, poison_id, poisoned_empty
 
 pytestmark = pytest.mark.gpu
 FRAMES, KEY = 7, 3            # the key in the middle: three steps either way, so both buffers of every ping-pong pair are written and read
@@ -20,8 +22,8 @@ FRAMES, KEY = 7, 3            # the key in the middle: three steps either way, s
 
 def _call():
     """(the device's inputs, the restatement's (mask, hidden)) of the suite's 7-frame clip on (23, 33), at 3 levels."""
-    images, truth = t_both._clip(FRAMES, *SMALL, KEY)
-    return (t_both._dev(images), t_both._dev(truth[KEY].astype("float32"))), t_both._want(FRAMES, *SMALL, KEY)[0]
+    images, truth = inputs._anchored_visible_clip(FRAMES, *SMALL, KEY)
+    return (device._dev(images), device._dev(truth[KEY].astype("float32"))), inputs._anchored_visible_want(FRAMES, *SMALL, KEY)[0]
 
 
 def _compare(got, want, what):
@@ -36,10 +38,10 @@ def _compare(got, want, what):
 def test_the_call_under_poison_equals_the_restatement(mode, poison, monkeypatch):
     (images, mask), want = _call()
     if mode == "chunked":                                              # fp32 images need no copy: one frame's pyramid a chunk
-        monkeypatch.setattr(propagate, "WS_CAP_BYTES", propagate._cabi.prop_pyramid_ws_bytes(1, *SMALL, t_both.LEVELS) + 8)
+        monkeypatch.setattr(propagate, "WS_CAP_BYTES", propagate._cabi.prop_pyramid_ws_bytes(1, *SMALL, inputs.ANCHORED_VISIBLE_LEVELS) + 8)
     names = record_launches(monkeypatch, propagate_anchored_visible, propagate_anchored, propagate_visible, propagate)
     filled = poisoned_empty(monkeypatch, poison)
-    got = t_both._call(images, mask, KEY)
+    got = motion_checks._anchored_visible_call(images, mask, KEY)
     assert filled                                                      # the call's buffers did come through the poison
     lumas = names.count("lp_prop_luma")
     assert lumas <= 2 if mode == "whole" else lumas >= 5, (mode, lumas)
@@ -52,9 +54,9 @@ def test_gated_anchor_field_under_poison(poison, monkeypatch):
     filled = poisoned_empty(monkeypatch, poison)
     for positions, lumas, mask, occlusion in (("smooth", "noisy", "disc", 16), ("outside", "dark", "random", 1), ("key", "noisy", "full", 16),
                                               ("key", "noisy", "empty", 16)):
-        P, Yt, Yk, m = t_both._inputs(SMALL, positions, lumas, mask)
+        P, Yt, Yk, m = inputs._anchored_visible_inputs(SMALL, positions, lumas, mask)
         want_vec, want_valid, want_gated = avref.gated_anchor_field(P, Yt, Yk, m, 2, 8, occlusion)
-        vec, valid, gated = t_both._device_field(P, Yt, Yk, m, 2, 8, occlusion)
+        vec, valid, gated = motion_checks._anchored_visible_field(P, Yt, Yk, m, 2, 8, occlusion)
         _same(gated, want_gated, ("gated", positions, lumas, mask))
         _same(valid, want_valid, ("valid", positions, lumas, mask))
         _same(vec, want_vec, ("vec", positions, lumas, mask))
@@ -71,14 +73,14 @@ def test_the_call_on_a_held_back_side_stream_reads_nothing_back(monkeypatch):
     filled = poisoned_empty(monkeypatch, 0xFF)
     side = torch.cuda.Stream()
     with torch.cuda.stream(side):
-        t_both._call(images, mask, KEY)                                # the first call loads the kernels and fills the allocator's
+        motion_checks._anchored_visible_call(images, mask, KEY)                                # the first call loads the kernels and fills the allocator's
         side.synchronize()                                             # pool of this stream: no hipMalloc below
         del filled[:]
         done = torch.cuda.Event()
         torch.cuda._sleep(cycles)
         done.record(side)
         start = time.perf_counter()
-        got = t_both._call(images, mask, KEY)
+        got = motion_checks._anchored_visible_call(images, mask, KEY)
         held = not done.query()                                        # directly behind the call, before anything synchronises
         idle = torch.cuda.default_stream().query()
         call_ms = (time.perf_counter() - start) * 1e3

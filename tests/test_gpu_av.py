@@ -9,33 +9,11 @@ import pytest
 
 from oracle import lanpaint_oracle as orc
 from tests.helpers import assert_close
+from tests.port_checks import _case
 from tests.stubs import MODELS
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
-
-
-def _case(shape, split, seed, soft=False, rows_differ=False):
-    rng = np.random.default_rng(seed)
-    b = shape[0]
-    y = rng.standard_normal(shape, dtype=np.float32)
-    noise = rng.standard_normal(shape, dtype=np.float32)
-    ai = np.zeros(shape, dtype=np.float32)
-    ai[..., split:] = 1.0                                    # the audio part of the flat pack
-    mask = (rng.random(shape) > 0.45).astype(np.float32)
-    if soft:
-        mask = rng.random(shape, dtype=np.float32)
-    t_v = np.float32([0.55 + (0.1 * r if rows_differ else 0.0) for r in range(b)])
-    t_a = np.float32([0.30 + (0.05 * r if rows_differ else 0.0) for r in range(b)])
-    if b > 1:            # (the reference blends `times * (1 - ai)`: per-row times of a batch have to broadcast against the latent)
-        t_v, t_a = t_v.reshape((b,) + (1,) * (len(shape) - 1)), t_a.reshape((b,) + (1,) * (len(shape) - 1))
-    times_v = orc.times_from_sigma(t_v, True)
-    times_a = orc.times_from_sigma(t_a, True)
-    corr = ((1.0 - ai) + np.float32(0.7) * ai).astype(np.float32)
-    bs = (-1,) + (1,) * (len(shape) - 1)
-    x = (t_v.reshape(bs) * noise + (1 - t_v.reshape(bs)) * y).astype(np.float32)
-    t_v = np.ascontiguousarray(t_v)
-    return dict(x=x, y=y, noise=noise, mask=mask, ai=ai, sigma=t_v, times_v=times_v, times_a=times_a, corr=corr)
 
 
 def _run_oracle(c, n_steps, draws, model_options=None):

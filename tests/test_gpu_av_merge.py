@@ -11,20 +11,15 @@ import torch
 
 from lanpaint_amd import _cabi, audio, av_nodes, interp_rule
 from tests import av_stubs
-from tests.test_av_host import fixture_id, host_rule, lerp_f32, load, restated_merge, weights_f64
+from tests.audio_ref import _reference_sequence, fixture_id, host_rule, lerp_f32, load_fixture as load, restated_merge, weights_f64
+from tests.compare import ulps
+from tests.device import DEV, _lib
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden")
 FIXTURES = [p for p in sorted(glob.glob(os.path.join(GOLDEN, "av_merge_*.npz"))) if "err_" not in p]
-DEV = torch.device("cuda", 0)
-
-
-def ulps(a, b):
-    """Distance in fp32 units in the last place (of the larger magnitude)."""
-    a, b = np.asarray(a, np.float32), np.asarray(b, np.float32)
-    return np.abs(a.astype(np.float64) - b.astype(np.float64)) / np.spacing(np.maximum(np.abs(a), np.abs(b)))
 
 
 def kernel_weights(mask, n, crossfade, sr):
@@ -36,11 +31,6 @@ def run(rec, mask=None):
     t = torch.from_numpy
     return audio.merge_audio_with_mask(t(rec["orig"]), t(rec["inpainted"]), t(rec["mask"]) if mask is None else mask,
                                        float(rec["crossfade"]), int(rec["orig_sr"]), int(rec["result_sr"]))
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _lib():
-    return _cabi.load()
 
 
 @pytest.mark.parametrize("path", FIXTURES, ids=fixture_id)
@@ -90,16 +80,6 @@ def test_both_mask_devices(fm, n, crossfade, sr):
         np.testing.assert_array_equal(w_dev, ref(am.to(DEV)))
     if (fm, n) == (2, 41) and cf == 0:
         assert w_host[20] != w_dev[20]
-
-
-def _reference_sequence(orig, inp, am, crossfade, sr):
-    """The reference's merge_audio_with_mask as a torch sequence (equal rates), run wherever its tensors are."""
-    n = orig.shape[-1]
-    w = torch.nn.functional.interpolate(am[None, None], size=(n,), mode="nearest-exact")[0, 0]
-    cf = max(1, int(round(crossfade * sr)))
-    k = torch.ones(1, 1, cf, device=orig.device) / cf
-    w = torch.nn.functional.conv1d(torch.nn.functional.pad(w[None, None], (cf // 2, cf - 1 - cf // 2), mode="replicate"), k)[0, 0]
-    return orig * (1 - w[None, None]) + inp * w[None, None], w
 
 
 def _ten_seconds():

@@ -14,17 +14,13 @@ import torch
 from lanpaint_amd import _cabi, audio
 from oracle import lanpaint_oracle as orc
 from tests import audio_ref as ar
-from tests.test_gpu_av_merge import _reference_sequence, ulps
+from tests.audio_ref import _reference_sequence
+from tests.compare import ulps
+from tests.device import DEV, _lib
 
 pytestmark = pytest.mark.gpu
 
-DEV = torch.device("cuda", 0)
 PLAN_THREADS = 1024                      # kPlanThreads of csrc/audio_kernel.hip: thread t owns ceil(fm / 1024) segments
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _lib():
-    return _cabi.load()
 
 
 # ---------------------------------------------------------------- helpers

@@ -11,25 +11,15 @@ import torch.nn.functional as F
 
 from lanpaint_amd import blend, detail, detail_nodes
 from tests import detail_ref
+from tests.device import DEV, _gen
+from tests.image_checks import _bbox_ref, _outside_is_untouched, _rect_mask, _region
+from tests.image_inputs import STITCH_CASES
 
 pytestmark = pytest.mark.gpu
-DEV = torch.device("cuda", 0)
 SHAPES = [((300, 417), (1024, 1424)), ((1024, 1424), (300, 417)), ((731, 512), (736, 512)), ((97, 55), (41, 200))]
 
 
-def _gen(seed):
-    return torch.Generator().manual_seed(seed)
-
-
 # ---- lp_mask_bbox ----------------------------------------------------------------------------------------------------------------
-def _bbox_ref(mask):
-    m = mask if mask.ndim == 3 else mask.unsqueeze(0)
-    nz = torch.nonzero(m > 0.5)
-    if nz.shape[0] == 0:
-        return (m.shape[1], -1, m.shape[2], -1)
-    return (int(nz[:, 1].min()), int(nz[:, 1].max()), int(nz[:, 2].min()), int(nz[:, 2].max()))
-
-
 @pytest.mark.parametrize("shape", [(3, 70, 130), (1, 257, 1000), (2, 33, 77), (1, 16, 64), (5, 300, 1028), (130, 70)])
 def test_bbox_equals_torch_nonzero_on_random_sparse_masks(shape):
     g = _gen(shape[-1])
@@ -65,10 +55,6 @@ def test_bbox_is_the_union_over_frames_and_takes_2d_masks():
 
 
 # ---- lp_detail_resample ----------------------------------------------------------------------------------------------------------
-def _region(y0, x0, hw, out_hw, H, W):
-    return detail.Region(y0, x0, hw[0], hw[1], out_hw[0], out_hw[1], H, W)
-
-
 def _check_resample(image, region, filter, label):
     """image [B, H, W, C] on the CPU.  e_hip <= b over every output element; e_t32 (torch's own fp32 CPU operator) for the record."""
     r = region
@@ -133,32 +119,6 @@ def test_mask_is_cropped_by_the_same_job_bilinear_and_stays_soft(mask_b):
 
 
 # ---- lp_detail_stitch ------------------------------------------------------------------------------------------------------------
-def _rect_mask(shape, rects, soft_seed=None):
-    mask = torch.zeros(shape)
-    for f, y0, y1, x0, x1 in rects:
-        mask[f, y0:y1 + 1, x0:x1 + 1] = 1.0
-    if soft_seed is not None:                                              # soft values above 0.5 inside, below outside
-        noise = torch.rand(shape, generator=_gen(soft_seed))
-        mask = torch.where(mask > 0, 0.55 + 0.45 * noise, 0.3 * noise * (noise > 0.8))
-    return mask
-
-
-# (name, B, H, W, C, mask frames, rectangles (frame, y0, y1, x0, x1), soft seed, context, padding)
-STITCH_CASES = [
-    ("touching_region_edge", 2, 96, 128, 3, 2, [(0, 24, 55, 32, 63), (1, 24, 55, 32, 63)], None, 1.0, 0),
-    ("flush_with_corner", 1, 96, 128, 3, 1, [(0, 0, 15, 104, 127)], None, 1.0, 0),
-    ("flush_with_border_soft", 2, 90, 130, 4, 2, [(0, 30, 52, 0, 20), (1, 70, 89, 5, 30)], 3, 1.0, 0),
-    ("one_mask_for_three_frames", 3, 96, 128, 3, 1, [(0, 40, 60, 50, 90)], 4, 1.5, 4),
-    ("small_region", 1, 64, 64, 1, 1, [(0, 30, 33, 28, 35)], None, 1.0, 0),
-]
-
-
-def _outside_is_untouched(out, original, r):
-    probe = out.clone()
-    probe[:, r.y0:r.y0 + r.h, r.x0:r.x0 + r.w, :] = original[:, r.y0:r.y0 + r.h, r.x0:r.x0 + r.w, :]
-    return torch.equal(probe, original)
-
-
 @pytest.mark.parametrize("k", [1, 9, 51])
 @pytest.mark.parametrize("case", STITCH_CASES, ids=[c[0] for c in STITCH_CASES])
 def test_stitch_without_resample_matches_torch_restatement_and_mask_blend(case, k):

@@ -10,34 +10,13 @@ import torch
 
 from lanpaint_amd import detail_color, detail_color_nodes, detail_track_nodes
 from tests import color_ref
+from tests.device import DEV
+from tests.image_checks import _check_color_stats as _check_stats, _fit_bits
+from tests.image_inputs import _blob_mask, _images, _rng
 
 pytestmark = pytest.mark.gpu
-DEV = torch.device("cuda", 0)
 TOL = 8 * 2.0 ** -24
 ABOVE = np.nextafter(np.float32(0.5), np.float32(1.0))
-
-
-def _rng(*key):
-    return np.random.default_rng(list(key))
-
-
-def _images(B, H, W, C, seed):
-    rng = _rng(B, H, W, C, seed)
-    r = rng.random((B, H, W, C), dtype=np.float32)
-    d = (r * np.float32(0.9)).astype(np.float32) + rng.normal(0.03, 0.02, (B, H, W, C)).astype(np.float32)
-    return d, r
-
-
-def _blob_mask(Bm, H, W, seed):
-    """Soft blobs: values on both sides of 0.5 with a gradual edge, a little noise on top."""
-    rng = _rng(Bm, H, W, seed)
-    yy, xx = np.mgrid[0:H, 0:W].astype(np.float32)
-    m = np.zeros((Bm, H, W), dtype=np.float32)
-    for p in range(Bm):
-        for _ in range(2):
-            cy, cx, s = rng.uniform(0, H), rng.uniform(0, W), 1.0 + min(H, W) / 8.0 * rng.uniform(0.5, 1.5)
-            m[p] += np.float32(0.9) * np.exp(-((yy - cy) ** 2 + (xx - cx) ** 2) / np.float32(2 * s * s)).astype(np.float32)
-    return np.clip(m + rng.uniform(0, 0.05, m.shape).astype(np.float32), 0, 1).astype(np.float32)
 
 
 def _edge_mask(Bm, H, W, seed):
@@ -48,23 +27,6 @@ def _edge_mask(Bm, H, W, seed):
         for _ in range(3):
             m[p, rng.integers(H), rng.integers(W)] = ABOVE
     return m
-
-
-def _check_stats(d, r, mask, margin, what):
-    """Device stats of CPU arrays against the restatement; returns the device table."""
-    dt, rt = torch.from_numpy(d).to(DEV), torch.from_numpy(r).to(DEV)
-    mt = None if mask is None else torch.from_numpy(mask).to(DEV)
-    got_dev = detail_color.color_stats(dt, rt, mt, margin)
-    again = detail_color.color_stats(dt, rt, mt, margin)
-    assert got_dev.dtype == torch.float64 and tuple(got_dev.shape) == (d.shape[0], 1 + 4 * d.shape[3])
-    got = got_dev.cpu().numpy()
-    assert (got.view(np.uint64) == again.cpu().numpy().view(np.uint64)).all(), what          # two calls, equal bits
-    want, mag = color_ref.stats_ref(d, r, mask, margin)
-    assert (got[:, 0] == want[:, 0]).all(), (what, got[:, 0], want[:, 0])                   # n exactly
-    bound = want[:, :1] * 2.0 ** -52 * mag[:, 1:]
-    err = np.abs(got[:, 1:] - want[:, 1:])
-    assert (err <= bound).all(), (what, float((err / np.maximum(bound, 1e-300)).max()))
-    return got_dev
 
 
 # H, W, C, B, mask_batch, margin.  The tile is 32 x 128: sizes at it, one under, one over, three tiles each way; W % 4 != 0
@@ -136,14 +98,6 @@ def clip_stats():
     stats = detail_color.color_stats(torch.from_numpy(d).to(DEV), torch.from_numpy(r).to(DEV),
                                      torch.from_numpy(_blob_mask(B, H, W, 12)).to(DEV), 2)
     return stats
-
-
-def _fit_bits(stats, *args):
-    got = detail_color.color_fit(stats, *args).cpu().numpy()
-    want = color_ref.fit_ref(stats.cpu().numpy(), *args)
-    assert got.dtype == np.float32 and got.shape == want.shape
-    assert (got.view(np.uint32) == want.view(np.uint32)).all(), (args, got[got != want][:4], want[got != want][:4])
-    return got
 
 
 def test_fit_equals_the_restatement_bit_for_bit_over_the_parameter_grid(clip_stats):

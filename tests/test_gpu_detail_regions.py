@@ -10,18 +10,11 @@ import torch
 
 from lanpaint_amd import _cabi, detail, detail_nodes, detail_region_nodes
 from tests import detail_ref, regions_ref
+from tests.compare import _tensor_bits as _bits
+from tests.device import DEV, _gen
 
 pytestmark = pytest.mark.gpu
-DEV = torch.device("cuda", 0)
 CAP = _cabi.LP_DETAIL_MAX_COMPONENTS
-
-
-def _gen(seed):
-    return torch.Generator().manual_seed(seed)
-
-
-def _bits(t):
-    return t.detach().cpu().contiguous().numpy().view(np.uint32)
 
 
 # ---- lp_mask_components ------------------------------------------------------------------------------------------------------------

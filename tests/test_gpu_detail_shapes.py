@@ -13,25 +13,15 @@ from scipy import ndimage
 from lanpaint_amd import _cabi, detail, detail_subjects
 from lanpaint_amd._util import raw_stream
 from tests import detail_ref, regions_ref, subjects_ref
-from tests.test_gpu_detail import STITCH_CASES, _rect_mask
+from tests.compare import _tensor_bits as _bits
+from tests.device import DEV, _gen
+from tests.image_checks import _rect_mask, _region
+from tests.image_inputs import STITCH_CASES
 
 pytestmark = pytest.mark.gpu
-DEV = torch.device("cuda", 0)
 CAP = _cabi.LP_DETAIL_MAX_COMPONENTS
 SIDE = _cabi.LP_DETAIL_MAX_SIDE
 Y0, X0, AFTER_Y, AFTER_X = 3, 5, 2, 3               # every window: at an odd origin of a larger image, rows and columns after it
-
-
-def _gen(seed):
-    return torch.Generator().manual_seed(seed)
-
-
-def _bits(t):
-    return t.detach().cpu().contiguous().numpy().view(np.uint32)
-
-
-def _region(y0, x0, hw, out_hw, H, W):
-    return detail.Region(y0, x0, hw[0], hw[1], out_hw[0], out_hw[1], H, W)
 
 
 # ---- lp_detail_resample ----------------------------------------------------------------------------------------------------------

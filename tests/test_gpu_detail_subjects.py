@@ -13,18 +13,11 @@ import torch
 from lanpaint_amd import _cabi, detail, detail_color_nodes, detail_subject_nodes, detail_subjects, detail_track_nodes
 from lanpaint_amd._util import raw_stream
 from tests import detail_ref, subjects_ref
+from tests.compare import _tensor_bits as _bits
+from tests.device import DEV, _gen
 
 pytestmark = pytest.mark.gpu
-DEV = torch.device("cuda", 0)
 CAP = _cabi.LP_DETAIL_MAX_COMPONENTS
-
-
-def _gen(seed):
-    return torch.Generator().manual_seed(seed)
-
-
-def _bits(t):
-    return t.detach().cpu().contiguous().numpy().view(np.uint32)
 
 
 # ---- lp_mask_components_frames -----------------------------------------------------------------------------------------------------

@@ -9,32 +9,15 @@ import pytest
 import torch
 
 from lanpaint_amd import blend, detail, detail_nodes, detail_track_nodes
+from tests.compare import _tensor_bits as _bits
+from tests.device import DEV, _gen
+from tests.image_checks import _window_mask
+from tests.image_inputs import _boxes_ref
 
 pytestmark = pytest.mark.gpu
-DEV = torch.device("cuda", 0)
-
-
-def _gen(seed):
-    return torch.Generator().manual_seed(seed)
-
-
-def _bits(t):
-    return t.detach().cpu().contiguous().numpy().view(np.uint32)
 
 
 # ---- lp_mask_bbox_frames -----------------------------------------------------------------------------------------------------------
-def _boxes_ref(mask):
-    """Per plane, in numpy: inclusive bounds of mask > 0.5, (H, -1, W, -1) for an empty plane."""
-    m = mask.cpu().numpy()
-    m = m[None] if m.ndim == 2 else m
-    out = []
-    for plane in m:
-        ys, xs = np.nonzero(plane > np.float32(0.5))
-        out.append((plane.shape[0], -1, plane.shape[1], -1) if ys.size == 0 else
-                   (int(ys.min()), int(ys.max()), int(xs.min()), int(xs.max())))
-    return tuple(out)
-
-
 def _check_boxes(mask, what):
     """mask: CPU tensor, or a HIP tensor to be used as it is (its alignment matters)."""
     dev_mask = mask if mask.is_cuda else mask.to(DEV)
@@ -173,13 +156,6 @@ def test_crop_track_with_a_one_plane_mask(size):
     assert np.array_equal(_bits(cimg), _bits(want_img)) and np.array_equal(_bits(cmask), _bits(want_mask))
     _, cmask2 = detail.crop_track(image, mask[0], still, "bicubic")      # a 2-D mask
     assert np.array_equal(_bits(cmask2), _bits(want_mask))
-
-
-def _window_mask(track):
-    inside = torch.zeros(len(track), track.H, track.W, dtype=torch.bool)       # built on the CPU, frame by frame
-    for f, (y0, x0) in enumerate(track.origins):
-        inside[f, y0:y0 + track.h, x0:x0 + track.w] = True
-    return inside
 
 
 @pytest.mark.parametrize("size", ["copy", "up", "down"])

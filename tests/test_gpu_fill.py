@@ -11,26 +11,16 @@ import torch
 from lanpaint_amd import _cabi, fill, fill_nodes
 from lanpaint_amd._util import raw_stream
 from tests import fill_ref
+from tests.compare import _raw_bits as _bits
+from tests.device import DEV
+from tests.image_inputs import _band, _fill_speckle as _speckle, _image, _rng
 
 pytestmark = pytest.mark.gpu
-DEV = torch.device("cuda", 0)
 ABOVE = np.nextafter(np.float32(0.5), np.float32(1.0))
 # (H, W, C): one pixel, one row, one column; around the 32-pixel tile and two tiles; more than one block each way; a 140 x 150
 # hole; thin shapes of 13 and 14 levels (three spans each way) at a few KB.  W % 4 != 0 and C in {1, 2, 5}: the element-wise form.
 SHAPES = [(1, 1, 3), (1, 7, 1), (7, 1, 4), (31, 33, 3), (32, 32, 4), (63, 65, 3), (64, 64, 5), (65, 129, 2), (130, 200, 3),
           (160, 200, 3), (1, 2049, 3), (2049, 1, 1), (3, 4100, 4)]
-
-
-def _rng(*key):
-    return np.random.default_rng(list(key))
-
-
-def _image(B, H, W, C, seed=0):
-    return (np.float32(0.05) + np.float32(0.95) * _rng(B, H, W, C, seed).random((B, H, W, C), dtype=np.float32)).astype(np.float32)
-
-
-def _speckle(Bm, H, W, seed=1):
-    return (_rng(Bm, H, W, seed).random((Bm, H, W)) < 0.3).astype(np.float32)
 
 
 def _hole(Bm, H, W):
@@ -41,13 +31,6 @@ def _hole(Bm, H, W):
         return None
     m = np.zeros((Bm, H, W), dtype=np.float32)
     m[:, r[0]:r[1], c[0]:c[1]] = 1.0
-    return m
-
-
-def _band(Bm, H, W):
-    m = np.zeros((Bm, H, W), dtype=np.float32)
-    m[:, :H // 4] = 1.0
-    m[:, :, W - W // 3:] = 1.0
     return m
 
 
@@ -80,10 +63,6 @@ def _mask_forms(Bm, H, W):
     for which in range(4):
         forms[f"corner {which}"] = _corner(Bm, H, W, which)
     return {k: v for k, v in forms.items() if v is not None}
-
-
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
 
 
 def _fill(img, mask):

@@ -17,12 +17,11 @@ from lanpaint_amd._util import raw_stream
 from tests import focus_ref as fref
 from tests import focus_scenes as scenes
 from tests import multiband_ref
+from tests.device import DELAY_MS, DEV, _spin_cycles_per_ms
 from tests.helpers import record_launches
 from tests.poison import poisoned_empty
-from tests.test_gpu_motion_scratch import _spin_cycles_per_ms
 
 pytestmark = pytest.mark.gpu
-DEV = torch.device("cuda", 0)
 GUARD = 64                                                             # bytes behind the workspace and behind the output
 FORMS = ("left", "frame", "all", "none", "soft", "nan")
 SHAPES = [(1, 1), (10, 40), (40, 10), (11, 11), (12, 12), (37, 41), (40, 150), (65, 33)]
@@ -289,9 +288,6 @@ def test_blend_multiband_is_what_it_was():
 
 
 # ---- off the null stream, behind a delay; the launch record -----------------------------------------------------------------------------
-DELAY_MS = 100                                                         # tests/test_gpu_image_scratch.py's, for the same reasons
-
-
 def test_the_wrapper_on_a_held_back_side_stream_reads_nothing_back(monkeypatch):
     """As tests/test_gpu_patch_fill.py has it: made on a side stream that is still busy with a delay, the call returns before the
     delay is done (no device -> host read, no synchronisation), leaves nothing on the null stream, makes one lp_multiband_blend call,

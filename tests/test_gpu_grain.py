@@ -3,7 +3,6 @@ The rule is integers, then fp64 and fp32 with every operation rounded on its own
 whatever tile, block or chunk a launch uses: every comparison covers every element and has no tolerance."""
 import ctypes
 import functools
-import zlib
 
 import numpy as np
 import pytest
@@ -12,9 +11,12 @@ import torch
 from lanpaint_amd import _cabi, grain, grain_nodes
 from lanpaint_amd._util import raw_stream
 from tests import grain_ref as ref
+from tests.compare import _raw_bits as _bits, _same_typed as _same
+from tests.device import DEV, _dev
+from tests.image_checks import _check_fit, _check_grain_stats as _check_stats
+from tests.image_inputs import IMAGES, _box, _grain_wild as _wild, _m3, _named_rng as _rng, _random_table
 
 pytestmark = pytest.mark.gpu
-DEV = torch.device("cuda", 0)
 TH, TW = _cabi.LP_GRAIN_TILE_H, _cabi.LP_GRAIN_TILE_W                  # 16 x 64
 # (B, H, W, C): one pixel; no interior pixel; exactly one; odd sizes; one under, at and one over the tile's width and height
 # and the four channels of a group; 16 Philox blocks per pixel; several tiles each way
@@ -24,75 +26,7 @@ IDS = lambda s: "x".join(map(str, s))                                  # noqa: E
 BIG_SEED = (1 << 63) + 5
 
 
-def _rng(*key):
-    return np.random.default_rng([zlib.crc32(k.encode()) if isinstance(k, str) else int(k) for k in key])
-
-
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
-def _same(got, want, what):
-    assert got.dtype == want.dtype and got.shape == want.shape, (what, got.dtype, got.shape, want.dtype, want.shape)
-    bad = (_bits(got) != _bits(want)) if got.dtype == np.float32 else (got != want)
-    assert not bad.any(), (what, int(bad.sum()), np.argwhere(bad)[:4].tolist())
-
-
-def _dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
-
-
-# ---- images ---------------------------------------------------------------------------------------------------------------------------
-def _noisy(size):
-    def make(B, H, W, C, seed=1):
-        rng = _rng(B, H, W, C, size, seed)
-        ramp = np.linspace(0.2, 0.8, W)[None, None, :, None] + 0.02 * np.arange(C)[None, None, None, :] / max(C, 1)
-        n = rng.normal(0.0, 1.0, (B, H + 4, W + 4, C))
-        k = ref.KERNELS[size].astype(np.float64)
-        f = np.zeros((B, H, W, C))
-        for dy in range(-size, size + 1):
-            for dx in range(-size, size + 1):
-                f += k[dy + size, dx + size] * n[:, 2 + dy:2 + dy + H, 2 + dx:2 + dx + W]
-        return (ramp + 0.03 * f / np.sqrt(ref.SUM_K2[size])).astype(np.float32)
-    return make
-
-
-def _checker(B, H, W, C, seed=0):
-    yy, xx = np.mgrid[:H, :W]
-    return np.broadcast_to(((yy + xx) & 1).astype(np.float32)[None, :, :, None], (B, H, W, C)).copy()
-
-
-def _boundaries(B, H, W, C, seed=2):
-    """(k + 0.5) / 255 and its float neighbours, where the code changes."""
-    rng = _rng(B, H, W, C, seed)
-    v = ((rng.integers(0, 255, (B, H, W, C)) + 0.5) / 255.0).astype(np.float32)
-    step = rng.integers(-1, 2, (B, H, W, C))
-    return np.where(step < 0, np.nextafter(v, np.float32(0)), np.where(step > 0, np.nextafter(v, np.float32(1)), v)).astype(np.float32)
-
-
-def _wild(B, H, W, C, seed=3):
-    """NaN, infinities and values outside [0, 1]."""
-    rng = _rng(B, H, W, C, seed)
-    m = (1.6 * rng.random((B, H, W, C)) - 0.3).astype(np.float32)
-    pick = rng.random((B, H, W, C))
-    m[pick < 0.05] = np.nan
-    m[(pick >= 0.05) & (pick < 0.08)] = np.inf
-    m[(pick >= 0.08) & (pick < 0.11)] = -np.inf
-    return m
-
-
-IMAGES = {"white": _noisy(0), "medium": _noisy(1), "coarse": _noisy(2), "all 0": lambda *s: np.zeros(s, np.float32),
-          "all 1": lambda *s: np.ones(s, np.float32), "checker": _checker, "boundaries": _boundaries, "wild": _wild}
-
-
 # ---- masks ----------------------------------------------------------------------------------------------------------------------------
-def _box(B, H, W, per_image=True):
-    m = np.zeros((B if per_image else 1, H, W), np.float32)
-    for i in range(m.shape[0]):
-        m[i, H // 5 + i % 3:H - H // 5, W // 6 + i % 2:W - W // 4] = 1.0
-    return m
-
-
 def _soft(B, H, W, seed=4):
     rng = _rng(B, H, W, seed)
     yy, xx = np.mgrid[:H, :W]
@@ -109,21 +43,9 @@ MASKS = {"[H, W]": lambda B, H, W: _box(B, H, W, False)[0], "[1, H, W]": lambda 
          "wild": _wild_mask}
 
 
-def _m3(mask):
-    return mask[None] if mask.ndim == 2 else mask
-
-
 # ---- stats ----------------------------------------------------------------------------------------------------------------------------
 STATS_CASES = [("all", 0, 8), ("all", 1, 8), ("all", 64, 8), ("all", 255, 8), ("outside", 64, 0), ("outside", 255, 1),
                ("outside", 64, 25), ("outside", 255, 8), ("inside", 64, 8), ("inside", 255, 8), ("inside", 1, 8)]
-
-
-def _check_stats(image, mask, cases, what):
-    t_img, t_mask = _dev(image), _dev(mask)
-    got = torch.stack([grain.grain_stats(t_img, t_mask, r, f, m) for r, f, m in cases]).cpu().numpy()
-    for g, (r, f, m) in zip(got, cases):
-        _same(g, ref.grain_stats(image, _m3(mask), grain.REGIONS[r], f, m), (what, r, f, m))
-    return got
 
 
 @pytest.mark.parametrize("shape", SHAPES, ids=IDS)
@@ -207,25 +129,6 @@ def _table(B, C, rows):
     for (b, c, k), v in rows.items():
         t[b, c, k] = v
     return t
-
-
-def _random_table(B, C, seed, scale=400):
-    rng = _rng(B, C, seed)
-    n = rng.integers(0, 200, (B, C, ref.K))
-    n[rng.random((B, C, ref.K)) < 0.3] = 0
-    e1 = (n * rng.random((B, C, ref.K)) * scale).astype(np.int64)
-    e2 = (n * rng.random((B, C, ref.K)) * scale * rng.choice([1, 20, 50], (B, 1, 1))).astype(np.int64)
-    return np.stack([n, e1, e2], axis=-1).astype(np.int64)
-
-
-def _check_fit(gen, reft, cases, what):
-    for strength, size, clip in cases:
-        amp, sz = grain.grain_fit(_dev(gen), _dev(reft), strength, size, clip)
-        assert amp.is_cuda and sz.is_cuda and sz.dtype == torch.int32
-        want_amp, want_size = ref.grain_fit(gen, reft, strength, size, clip)
-        _same(sz.cpu().numpy(), want_size, (what, "size", strength, size, clip))
-        _same(amp.cpu().numpy(), want_amp, (what, "amp", strength, size, clip))
-    return want_amp, want_size
 
 
 def test_fit_branches_equal_the_restatement():

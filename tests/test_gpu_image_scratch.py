@@ -26,30 +26,20 @@ import torch
 from lanpaint_amd import (_cabi, _util, audio, blend, detail, detail_color, detail_subjects, fill, grain, multiband, refine,
                           resample, stabilize, videomask)
 from oracle import lanpaint_oracle as orc
-from tests import color_ref, detail_ref, fill_ref, regions_ref, subjects_ref
+from tests import color_ref, compare, detail_ref, device, fill_ref, image_checks, image_inputs, regions_ref, subjects_ref
 from tests import grain_ref as gref
 from tests import multiband_ref as mb_ref
 from tests import refine_ref as rref
 from tests import stabilize_ref as sref
-from tests import test_gpu_detail as t_detail
-from tests import test_gpu_detail_color as t_color
-from tests import test_gpu_detail_track as t_track
-from tests import test_gpu_fill as t_fill
-from tests import test_gpu_grain as t_grain
-from tests import test_gpu_multiband as t_mb
-from tests import test_gpu_refine as t_refine
-from tests import test_gpu_stabilize as t_stab
-from tests import test_gpu_videomask as t_vmask
-from tests import test_gpu_videomask_shapes as t_vshapes
 from tests import videomask_ref as vref
+from tests.audio_ref import lerp_f32, weights_f64
+from tests.compare import ulps
+from tests.device import DEV, _dev, _spin_cycles_per_ms
 from tests.helpers import record_launches
-from tests.poison import poisoned_empty
-from tests.test_av_host import lerp_f32, weights_f64
-from tests.test_gpu_av_merge import ulps
-from tests.test_gpu_motion_scratch import LARGE, POISONS, SMALL, _spin_cycles_per_ms, poison_id
+from tests.inputs import LARGE, SMALL
+from tests.poison import POISONS, poison_id, poisoned_empty
 
 pytestmark = pytest.mark.gpu
-DEV = torch.device("cuda", 0)
 # (23, 33) and (40, 70): odd, no multiple of a tile side (16, 32, 64), of the 16 x 64 grain and label tiles, of the 1024-element
 # label chunk or of the stabilize's 256-pixel block; (40, 70) takes several workgroups of every kernel and three label chunks.
 # B = 3 images; a config is (plane, channels, mask planes): C = 3 has W * C % 4 != 0, the element-wise forms, C = 4 on (40, 70) the
@@ -60,10 +50,6 @@ CONFIGS = [(SMALL, 3, 1), (LARGE, 3, B), (LARGE, 4, 1)]
 CHUNKED = [(SMALL, 3, B), (LARGE, 3, B)]
 MODULES = (audio, blend, detail, detail_color, detail_subjects, fill, grain, multiband, refine, resample, stabilize, videomask)
 K, K_WIDE, FILTER = 9, 17, "bicubic"                                   # blend_overlap: the 16 x 64 tile and, above 15, the 8 x 32 one
-
-
-def _dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
 
 
 def _bits(a):
@@ -116,7 +102,7 @@ def _only(names, **counts):
 @functools.lru_cache(maxsize=None)
 def _fill_masked(plane, C, Bm, mode):
     H, W = plane
-    img, mask = t_fill._image(B, H, W, C, 3), t_fill._speckle(Bm, H, W, 5)
+    img, mask = image_inputs._image(B, H, W, C, 3), image_inputs._fill_speckle(Bm, H, W, 5)
     if Bm == B:
         mask[1] = 1.0                                                  # one image with no known pixel: it comes back unchanged
         assert not (~(mask[1] > 0.5)).any() and (~(mask[0] > 0.5)).any() and (mask[0] > 0.5).any()
@@ -143,8 +129,8 @@ def _fill_masked(plane, C, Bm, mode):
 @functools.lru_cache(maxsize=None)
 def _outpaint_pad(plane, C, Bm, mode, do_fill, with_mask):
     H, W = plane
-    img = t_fill._image(B, H, W, C, 8)
-    mask = t_fill._speckle(Bm, H, W, 25) * np.float32(0.8) if with_mask else None
+    img = image_inputs._image(B, H, W, C, 8)
+    mask = image_inputs._fill_speckle(Bm, H, W, 25) * np.float32(0.8) if with_mask else None
     pads = dict(left=5, top=0, right=3, bottom=6, overlap=2, multiple_of=8)
     plan = fill.plan_outpaint(H, W, **pads)
     want_c, want_m = fill_ref.pad_ref(img, mask, plan.left, plan.top, plan.right, plan.bottom, plan.overlap)
@@ -172,8 +158,8 @@ LEVELS = 5
 @functools.lru_cache(maxsize=None)
 def _blend_multiband(plane, C, Bm, mode):
     H, W = plane
-    a, b = _half(t_mb._image(B, H, W, C, 11), mode), _half(t_mb._image(B, H, W, C, 12), mode)
-    mask = t_mb._soft(Bm, H, W, 13)
+    a, b = _half(image_inputs._image(B, H, W, C, 11), mode), _half(image_inputs._image(B, H, W, C, 12), mode)
+    mask = image_inputs._soft(Bm, H, W, 13)
     want = mb_ref.blend_ref(a, b, mask, LEVELS)
 
     def check(got, dev, what):
@@ -201,8 +187,9 @@ def _refine_caps(plane):
 
 def _soft_blobs(Bm, H, W, mode):
     """tests/test_gpu_refine.py's blobs with soft values: above 0.5 inside, below it outside."""
-    soft = t_refine._soft(Bm, H, W, 7)
-    m = np.where(t_refine._blobs(Bm, H, W) > 0, np.float32(0.5) + np.float32(0.5) * soft, np.float32(0.499) * soft).astype(np.float32)
+    soft = image_inputs._soft(Bm, H, W, 7)
+    m = np.where(image_inputs._refine_blobs(Bm, H, W) > 0, np.float32(0.5) + np.float32(0.5) * soft,
+                 np.float32(0.499) * soft).astype(np.float32)
     return _half(m, mode)
 
 
@@ -226,7 +213,7 @@ def _grow_mask(plane, C, Bm, mode, grow):
 @functools.lru_cache(maxsize=None)
 def _refine_mask(plane, C, Bm, mode, radius, grow):
     H, W = plane
-    guide, mask = _half(t_refine._guide(B, H, W, C, 11), mode), t_refine._soft(Bm, H, W, 13)
+    guide, mask = _half(image_inputs._guide(B, H, W, C, 11), mode), image_inputs._soft(Bm, H, W, 13)
     grown = mask if grow == 0 else np.stack([rref.grow_ref(m, grow) for m in mask])
     want = rref.refine_ref(guide, grown, radius, 1e-3) if radius else np.ascontiguousarray(np.broadcast_to(grown, (B, H, W)))
 
@@ -250,8 +237,8 @@ STAB = (1, 2, 0.5, 3.0)                                                # median,
 @functools.lru_cache(maxsize=None)
 def _stabilize_masks(plane, C, Bm, mode):
     H, W = plane
-    mask = t_stab._blobs(FRAMES, H, W, 15)
-    mask[1] = t_stab._soft(1, H, W, 3)[0]                              # a soft frame: the half rounding moves values across 0.5
+    mask = image_inputs._stabilize_blobs(FRAMES, H, W, 15)
+    mask[1] = image_inputs._stabilize_soft(1, H, W, 3)[0]                              # a soft frame: the half rounding moves values across 0.5
     mask = _half(mask, mode)
     want = sref.stabilize_ref(mask, *STAB)
     assert FRAMES > _cabi.LP_STAB_SEG_FRAMES and not mask[FRAMES // 3].any()
@@ -276,9 +263,9 @@ GRAIN = dict(margin=2, seed=3, frame0=5)                               # margin 
 def _grain_scene(plane, C, Bm, mode):
     """tests/test_gpu_grain.py's video: a noisy image that is clean under a box mask."""
     H, W = plane
-    mask = t_grain._box(B, H, W, Bm == B)
+    mask = image_inputs._box(B, H, W, Bm == B)
     clean = np.linspace(0.2, 0.8, W, dtype=np.float32)[None, None, :, None]
-    image = np.where(mask[..., None] > 0.5, clean, t_grain.IMAGES["medium"](B, H, W, C)).astype(np.float32)
+    image = np.where(mask[..., None] > 0.5, clean, image_inputs.IMAGES["medium"](B, H, W, C)).astype(np.float32)
     return _half(image, mode), mask
 
 
@@ -286,14 +273,14 @@ def _grain_scene(plane, C, Bm, mode):
 def _grain_match(plane, C, Bm, mode, with_plate, clip):
     H, W = plane
     image, mask = _grain_scene(plane, C, Bm, mode)
-    plate = _half(t_grain.IMAGES["coarse"](2, H + 3, W - 2, C, 9), mode) if with_plate else None
+    plate = _half(image_inputs.IMAGES["coarse"](2, H + 3, W - 2, C, 9), mode) if with_plate else None
     want = gref.match(image, mask, plate, clip_frames=clip, **GRAIN)
     # the poison has to matter: pixels are measured outside the mask, and a band that no pixel touches holds the memset's zero
     outside = gref.grain_stats(image, mask, grain.REGIONS["outside"], 64, GRAIN["margin"])[..., 0]
     assert outside.sum() > 0 and (outside == 0).any() and (want != image).any()
 
     def check(got, dev, what):
-        t_grain._same(got.cpu().numpy(), want, what)
+        compare._same_typed(got.cpu().numpy(), want, what)
 
     def caps(monkeypatch):                                             # one frame a chunk, of the image and of the larger plate
         monkeypatch.setattr(grain, "WS_CAP_BYTES", H * W * C * 4 + 8)
@@ -315,7 +302,7 @@ MARGIN, SMOOTH = 2, 3
 @functools.lru_cache(maxsize=None)
 def _color_match(plane, C, Bm, mode, method):
     H, W = plane
-    (d, r), mask = t_color._images(B, H, W, C, 1), t_color._blob_mask(Bm, H, W, 2)
+    (d, r), mask = image_inputs._images(B, H, W, C, 1), image_inputs._blob_mask(Bm, H, W, 2)
     want_stats, mag = color_ref.stats_ref(d, r, mask, MARGIN)
     assert (want_stats[:, 0] >= _cabi.LP_COLOR_MIN_COUNT).all() and (want_stats[:, 0] < H * W).all()
 
@@ -341,7 +328,7 @@ def _color_match(plane, C, Bm, mode, method):
 @functools.lru_cache(maxsize=None)
 def _mask_blend(plane, C, Bm, mode):
     H, W = plane
-    i1, i2, mask = t_fill._image(B, H, W, C, 1), t_fill._image(B, H, W, C, 2), t_mb._speckle(Bm, H, W, 4)
+    i1, i2, mask = image_inputs._image(B, H, W, C, 1), image_inputs._image(B, H, W, C, 2), image_inputs._multiband_speckle(Bm, H, W, 4)
     want = orc.mask_blend(i1, i2, np.ascontiguousarray(np.broadcast_to(mask, (B, H, W))), K)
 
     def check(got, dev, what):
@@ -354,8 +341,8 @@ def _mask_blend(plane, C, Bm, mode):
 @functools.lru_cache(maxsize=None)
 def _merge_video(plane, C, Bm, mode, half_res):
     H, W = plane
-    o, p = t_fill._image(B, H, W, C, 3), t_fill._image(B, H, W, C, 4)
-    mask = t_mb._speckle(Bm, H // 2, W // 2, 5) if half_res else t_mb._speckle(Bm, H, W, 6)
+    o, p = image_inputs._image(B, H, W, C, 3), image_inputs._image(B, H, W, C, 4)
+    mask = image_inputs._multiband_speckle(Bm, H // 2, W // 2, 5) if half_res else image_inputs._multiband_speckle(Bm, H, W, 6)
     want = orc.merge_video_with_mask(o, p, mask, K_WIDE, mask_on="gpu")   # the mask is on the device: torch's GPU index rule
 
     def check(got, dev, what):
@@ -400,7 +387,7 @@ def _interpolate_masks(plane, C, Bm, mode):
     """tests/test_gpu_videomask_shapes.py's end-to-end case on this plane, with a resize up on both axes."""
     h, w = plane
     rng = np.random.default_rng(h + w)
-    keys = np.stack([t_vshapes._blob(rng, h, w) for _ in INDICES])
+    keys = np.stack([image_inputs._blob(rng, h, w) for _ in INDICES])
     size = (w + 17, h + 9)
     centroids = []
     for k in keys:
@@ -474,7 +461,7 @@ def _stitch_bound(win, filter, det):
 def _single_scene(plane, C, Bm):
     H, W = plane
     image, mask = torch.rand(B, H, W, C, generator=_gen(H, W, C, 1)), _two_blobs(Bm, H, W)
-    bbox = t_detail._bbox_ref(mask)
+    bbox = image_checks._bbox_ref(mask)
     region = detail.plan_region(bbox, H, W, 1.0, 1, 8, 2 * TARGET)
     assert region.resampled and (region.h, region.w) != (H, W)
     det = torch.rand(B, region.oh, region.ow, C, generator=_gen(H, W, C, 2))
@@ -485,7 +472,7 @@ def _single_stitch_check(got, original, det, mask, region, what):
     out = got.cpu()
     err = float((out - detail_ref.stitch_ref(original, det, mask, region, K, FILTER)).abs().max())
     assert err <= _stitch_bound(region, FILTER, det), (what, err)
-    assert t_detail._outside_is_untouched(out, original, region), what
+    assert image_checks._outside_is_untouched(out, original, region), what
 
 
 @functools.lru_cache(maxsize=None)
@@ -564,7 +551,7 @@ def _detail_regions(plane, C, Bm, mode, call):
 def _track_scene(plane, C):
     H, W = plane
     image, mask = torch.rand(CLIP, H, W, C, generator=_gen(H, W, C, 5)), _two_subjects(H, W, empty=1)
-    boxes = t_track._boxes_ref(mask)
+    boxes = image_inputs._boxes_ref(mask)
     assert boxes[1] == (H, -1, W, -1) and all(b[1] >= 0 for f, b in enumerate(boxes) if f != 1)   # the empty frame's row is written
     track = detail.plan_track(boxes, H, W, 1.0, 1, 2, 2 * TARGET, smooth=3)
     assert track.resampled and len(set(track.origins)) > 1
@@ -577,7 +564,7 @@ def _track_stitch_check(got, dev_original, dev_det, dev_mask, original, track, w
     for f in range(CLIP):
         want = detail.stitch(dev_original[f:f + 1], dev_det[f:f + 1], dev_mask[f:f + 1], track.region(f), K, FILTER)
         assert np.array_equal(_bits(got[f:f + 1]), _bits(want)), (what, f)
-    outside = ~t_track._window_mask(track)
+    outside = ~image_checks._window_mask(track)
     assert bool(outside.flatten(1).any(dim=1).all()) and np.array_equal(_bits(got.cpu()[outside]), _bits(original[outside])), what
 
 
@@ -789,7 +776,7 @@ def test_keyframe_edt_under_poison(poison, monkeypatch):
     rng = np.random.default_rng(11)
     masks = [(rng.random((H, W)) < p).astype(np.float32) for p in (0.002, 0.05, 0.5, 0.97)]
     masks += [rng.random((H, W)).astype(np.float32), np.zeros((H, W), np.float32), np.ones((H, W), np.float32)]
-    t_vmask._check_edt(masks)                                          # d2 of both planes, the centroid sums and the SDF, exactly
+    image_checks._check_edt(masks)                                          # d2 of both planes, the centroid sums and the SDF, exactly
     assert filled
 
 
@@ -797,13 +784,13 @@ def test_keyframe_edt_under_poison(poison, monkeypatch):
 def test_morph_frames_and_resize_codes_under_poison(poison, monkeypatch):
     filled = poisoned_empty(monkeypatch, poison)
     rng = np.random.default_rng(100 * H + W)
-    keys = t_vshapes._keys(rng, H, W)
-    stack = t_vshapes._dev(keys)
+    keys = image_inputs._keys(rng, H, W)
+    stack = device._dev(keys)
     _, sdf, _ = videomask.keyframe_edt(stack)
-    plan, _, _ = t_vshapes._hand_plan(H, W, len(keys))
-    _, codes, _ = t_vshapes._check_morph("poison", keys, stack, sdf, plan)                    # the float form and the codes
+    plan, _, _ = image_checks._hand_plan(H, W, len(keys))
+    _, codes, _ = image_checks._check_morph("poison", keys, stack, sdf, plan)                    # the float form and the codes
     for size in ((W + 17, H + 9), (W - 10, H), (20, 50)):
-        got = videomask.resize_codes(t_vshapes._dev(codes), size).cpu().numpy()
+        got = videomask.resize_codes(device._dev(codes), size).cpu().numpy()
         assert np.array_equal(got, vref.pil_resize_ref(codes, size)), size
     assert filled
 
@@ -812,11 +799,11 @@ def test_morph_frames_and_resize_codes_under_poison(poison, monkeypatch):
 def test_color_stats_fit_and_apply_under_poison(poison, monkeypatch):
     filled = poisoned_empty(monkeypatch, poison)
     for C, Bm in ((3, B), (4, 1), (5, 1)):                             # 5: two channel groups
-        (d, r), mask = t_color._images(B, H, W, C, 1), t_color._blob_mask(Bm, H, W, 2)
-        stats = t_color._check_stats(d, r, mask, MARGIN, ("stats", C))
-        t_color._check_stats(d, r, None, 0, ("no mask", C))
+        (d, r), mask = image_inputs._images(B, H, W, C, 1), image_inputs._blob_mask(Bm, H, W, 2)
+        stats = image_checks._check_color_stats(d, r, mask, MARGIN, ("stats", C))
+        image_checks._check_color_stats(d, r, None, 0, ("no mask", C))
         for args in (("mean_std", 1.0, 1, 0), ("mean", 0.3, 3, 0), ("mean_std", 1.0, 0, 1), ("mean_std", 1.0, 3, 3)):
-            coef = t_color._fit_bits(stats, *args)
+            coef = image_checks._fit_bits(stats, *args)
         got = detail_color.color_apply(_dev(d), _dev(coef))
         _same_bits(got, color_ref.apply_ref(d, coef), ("apply", C))
     assert filled
@@ -826,11 +813,11 @@ def test_color_stats_fit_and_apply_under_poison(poison, monkeypatch):
 def test_signed_d2_and_stabilize_q_under_poison(poison, monkeypatch):
     filled = poisoned_empty(monkeypatch, poison)
     for name in ("soft", "blobs"):
-        mask = t_stab.FORMS[name](FRAMES, H, W)
+        mask = image_inputs.FORMS[name](FRAMES, H, W)
         q_ref = sref.signed_d2(mask)
-        q_dev = t_stab._device_q(mask)
+        q_dev = image_checks._device_q(mask)
         assert q_dev.dtype == torch.int32 and (q_dev.cpu().numpy() == q_ref).all(), name
-        t_stab._check_q(q_dev, q_ref, [(0, 0, 0.0, 0.0), (1, 2, 0.0, 0.0), (2, 1, 0.5, 3.0), (3, 8, -0.5, 0.5)], name)
+        image_checks._check_q(q_dev, q_ref, [(0, 0, 0.0, 0.0), (1, 2, 0.0, 0.0), (2, 1, 0.5, 3.0), (3, 8, -0.5, 0.5)], name)
     assert filled
 
 
@@ -840,19 +827,19 @@ def test_grain_stats_fit_field_and_apply_under_poison(poison, monkeypatch):
     C = 3
     image, mask = _grain_scene(SMALL, C, B, "whole")
     cases = [("all", 64, 8), ("outside", 64, 2), ("inside", 64, 8)]    # the three regions
-    got = t_grain._check_stats(image, mask, cases, "stats")
+    got = image_checks._check_grain_stats(image, mask, cases, "stats")
     assert all(g[..., 0].sum() > 0 and (g[..., 0] == 0).any() for g in got)        # measured, and bands that nothing touched
-    gen, plate = t_grain._random_table(B, C, 1, 100), t_grain._random_table(5, C, 3)
-    t_grain._check_fit(gen, t_grain._random_table(B, C, 2), [(1.0, -1, 0), (1.0, -1, 1), (0.8, -1, 3), (1.3, 1, 3)], "fit")
-    t_grain._check_fit(gen, plate, [(1.0, -1, 0), (1.0, 2, 3)], "fit, plate")
+    gen, plate = image_inputs._random_table(B, C, 1, 100), image_inputs._random_table(5, C, 3)
+    image_checks._check_fit(gen, image_inputs._random_table(B, C, 2), [(1.0, -1, 0), (1.0, -1, 1), (0.8, -1, 3), (1.3, 1, 3)], "fit")
+    image_checks._check_fit(gen, plate, [(1.0, -1, 0), (1.0, 2, 3)], "fit, plate")
     for size in (0, 1, 2):
         field = grain.grain_field((B, H, W, C), size, 21, size == 1, 7, DEV).cpu().numpy()
-        t_grain._same(field, gref.grain_field(B, H, W, C, size, 21, size == 1, 7), ("field", size))
-    amp = (t_grain._rng("poison", 7).random((B, C, gref.K)) * 3e-4).astype(np.float32)
+        compare._same_typed(field, gref.grain_field(B, H, W, C, size, 21, size == 1, 7), ("field", size))
+    amp = (image_inputs._named_rng("poison", 7).random((B, C, gref.K)) * 3e-4).astype(np.float32)
     amp[0, 0, 3] = 0.0
     sizes = np.array([0, 2, 1], np.int32)
     out = grain.grain_apply(_dev(image), _dev(mask), _dev(amp), _dev(sizes), seed=4, frame0=1000).cpu().numpy()
-    t_grain._same(out, gref.grain_apply(image, mask, amp, sizes, 4, False, 1000), "apply")
+    compare._same_typed(out, gref.grain_apply(image, mask, amp, sizes, 4, False, 1000), "apply")
     assert filled
 
 

@@ -13,8 +13,9 @@ import torch
 
 from lanpaint_amd import (_cabi, propagate, propagate_keys, propagate_keys_visible, propagate_visible, shots, temporal_fill,
                           temporal_fill_checked, temporal_smooth, temporal_smooth_robust)
+from tests.device import _dev
 from tests.helpers import GOLDEN_DIR, record_launches
-from tests.test_gpu_propagate import _dev, _disc, _video
+from tests.inputs import _disc, _video
 
 pytestmark = pytest.mark.gpu
 MODULES = (propagate, propagate_visible, propagate_keys, propagate_keys_visible, temporal_fill, temporal_fill_checked, temporal_smooth,

@@ -22,6 +22,7 @@ import torch
 
 from lanpaint_amd import (_cabi, propagate, propagate_anchored, propagate_anchored_visible, propagate_keys, propagate_keys_visible,
                           propagate_visible, shots, temporal_fill, temporal_fill_checked, temporal_smooth, temporal_smooth_robust)
+from tests import inputs, motion_checks
 from tests import propagate_anchored_ref as aref
 from tests import propagate_keys_ref as kref
 from tests import propagate_keys_visible_ref as kvref
@@ -32,20 +33,11 @@ from tests import temporal_fill_checked_ref as cref
 from tests import temporal_fill_ref as tref
 from tests import temporal_smooth_ref as sref
 from tests import temporal_smooth_robust_ref as rref
-from tests import test_gpu_propagate as t_prop
-from tests import test_gpu_propagate_anchored as t_anchored
-from tests import test_gpu_propagate_keys as t_keys
-from tests import test_gpu_propagate_keys_visible as t_keys_visible
-from tests import test_gpu_propagate_visible as t_visible
-from tests import test_gpu_shots as t_shots
-from tests import test_gpu_temporal_fill as t_fill
-from tests import test_gpu_temporal_fill_checked as t_checked
-from tests import test_gpu_temporal_smooth as t_smooth
-from tests import test_gpu_temporal_smooth_robust as t_robust
+from tests.compare import _same_bits, _same_ints as _same
+from tests.device import DELAY_MS, _dev, _levels_of, _spin_cycles_per_ms
 from tests.helpers import GOLDEN_DIR, record_launches
-from tests.poison import poisoned_empty
-from tests.test_gpu_propagate import _dev, _disc, _levels_of, _rng, _same, _same_bits, _video
-from tests.test_gpu_temporal_fill import _random_masks
+from tests.inputs import LARGE, SMALL, _disc, _random_masks, _rng, _video
+from tests.poison import POISONS, poison_id, poisoned_empty
 
 pytestmark = pytest.mark.gpu
 
@@ -58,14 +50,8 @@ F, KEY, KEYS, SEARCH, SMOOTH, RADIUS, TOLERANCE = 7, 3, (1, 4), 2, 8, 2, 24
 AGREE = 4
 # shot decision: every pair whose residual is a maximum among its two neighbours is a cut, so that `shot` is not all zero
 DECISION = dict(threshold=1, hist=0, ratio=100, window=1)
-# (23, 33) and (40, 70): odd at every pyramid level, no multiple of the 8-pixel block, the 16-pixel window or the 32-pixel tile;
-# (40, 70) takes several workgroups of every kernel.  Levels 1 has no parent field; with 6 the top levels of (23, 33) are 1 x 2.
-# "chunked": fp16 images and every WS_CAP_BYTES lowered, the restatement on the half-rounded values.
-SMALL, LARGE = (23, 33), (40, 70)
 CASES = [(SMALL, 3, "whole"), (SMALL, 3, "chunked"), (LARGE, 3, "whole"), (LARGE, 3, "chunked"), (SMALL, 1, "whole"), (SMALL, 6, "whole")]
-POISONS = [0x00, 0xFF]
 case_id = lambda c: c if isinstance(c, str) else "x".join(map(str, c)) if isinstance(c, tuple) else f"levels{c}"    # noqa: E731
-poison_id = lambda b: f"0x{b:02X}"                                   # noqa: E731
 
 
 # ---- inputs and restatements, once per plane and mode ----------------------------------------------------------------------------------
@@ -164,8 +150,8 @@ def _compare(call, got, want, what):
         _same(score.cpu().numpy(), want[1], (what, "score"))
         _same(shot.cpu().numpy(), want[0], (what, "shot"))
     else:
-        {"temporal_fill": t_fill._check_whole, "temporal_fill_checked": t_checked._check_whole, "temporal_smooth": t_smooth._check,
-         "temporal_smooth_robust": t_robust._check}[call](got, want, what)
+        {"temporal_fill": motion_checks._check_fill_whole, "temporal_fill_checked": motion_checks._check_checked_whole,
+         "temporal_smooth": motion_checks._check_smooth, "temporal_smooth_robust": motion_checks._check_robust_smooth}[call](got, want, what)
 
 
 MODULES = (propagate, propagate_visible, propagate_anchored, propagate_keys, propagate_keys_visible, temporal_fill,
@@ -277,7 +263,7 @@ stage = pytest.mark.parametrize("poison", POISONS, ids=poison_id)
 def test_key_mask_under_poison(poison, monkeypatch):
     filled = poisoned_empty(monkeypatch, poison)
     for form in ("disc", "soft", "wild"):
-        mask = t_prop.MASKS[form](H, W)
+        mask = inputs.MASKS[form](H, W)
         bits = ref.binarise(mask)
         for levels in (1, 3, 6):
             mpyr, out = propagate.key_mask(_dev(mask), levels)
@@ -291,14 +277,14 @@ def test_key_mask_under_poison(poison, monkeypatch):
 def test_match_level_and_fill_median_under_poison(poison, monkeypatch):
     filled = poisoned_empty(monkeypatch, poison)
     for levels in (1, 3, 6):
-        t_prop._check_match(H, W, levels, SEARCH, SMOOTH, "random", "disc", (poison, levels))
+        motion_checks._check_match(H, W, levels, SEARCH, SMOOTH, "random", "disc", (poison, levels))
     assert filled
 
 
 @stage
 def test_advance_under_poison(poison, monkeypatch):
     filled = poisoned_empty(monkeypatch, poison)
-    vec, vec2, bits, P1, c1, P2, c2 = t_prop._advance_case(H, W, 40)
+    vec, vec2, bits, P1, c1, P2, c2 = inputs._advance_case(H, W, 40)
     for levels in (1, 6):
         pos1, out1, mp1 = propagate.advance(_dev(vec), None, _dev(bits), levels)
         pos2, out2, mp2 = propagate.advance(_dev(vec2), pos1, _dev(bits), levels)
@@ -314,15 +300,15 @@ def test_advance_under_poison(poison, monkeypatch):
 @stage
 def test_visible_flags_and_occlude_under_poison(poison, monkeypatch):
     filled = poisoned_empty(monkeypatch, poison)
-    Yt, Yk = t_visible._lumas("noisy", H, W)
+    Yt, Yk = inputs._visible_lumas("noisy", H, W)
     for positions in ("smooth", "outside"):
-        P = t_visible._positions(positions, H, W)
+        P = inputs._positions(positions, H, W)
         for name in ("disc", "sparse"):
-            m = t_visible.MASKS[name](H, W)
+            m = inputs.VISIBLE_MASKS[name](H, W)
             want = vref.visible_flags(Yt, Yk, P, m, 16)
             got = propagate_visible.visible_flags(_dev(P.astype(np.int32)), _dev(Yt), _dev(Yk), _dev(m), 16)
             _same(got.cpu().numpy(), want, ("flags", positions, name))
-    flags = t_visible._flags("random", *ref.grid_of(H, W))
+    flags = inputs._flags("random", *ref.grid_of(H, W))
     c = _rng(H, W, 12).integers(0, 257, (H, W))
     cv = vref.occlude(c, flags)
     for levels in (1, 4):
@@ -339,9 +325,9 @@ def test_visible_flags_and_occlude_under_poison(poison, monkeypatch):
 def test_anchor_field_under_poison(poison, monkeypatch):
     filled = poisoned_empty(monkeypatch, poison)
     for positions, lumas, mask in (("smooth", "noisy", "disc"), ("outside", "flat", "random"), ("key", "noisy", "empty")):
-        P, Yt, Yk, m = t_anchored._inputs(SMALL, positions, lumas, mask)
+        P, Yt, Yk, m = inputs._anchored_inputs(SMALL, positions, lumas, mask)
         want_vec, want_valid = aref.anchor_field(P, Yt, Yk, m, 2, SMOOTH)
-        vec, valid = t_anchored._device_field(P, Yt, Yk, m, 2, SMOOTH)
+        vec, valid = motion_checks._anchored_field(P, Yt, Yk, m, 2, SMOOTH)
         _same(valid, want_valid, ("valid", positions, lumas, mask))
         _same(vec, want_vec, ("vec", positions, lumas, mask))
     assert filled
@@ -352,7 +338,7 @@ def test_the_batched_step_entries_under_poison(poison, monkeypatch):
     """match_level_batch, fill_median_batch and advance_batch against the single entries, which the test above holds to the
     restatement under the same poison: the suite's own test, on this plane."""
     filled = poisoned_empty(monkeypatch, poison)
-    t_keys.test_batched_entries_equal_the_single_entries(SMALL, 5)
+    motion_checks._check_batched_entries(SMALL, 5)
     assert filled
 
 
@@ -360,11 +346,11 @@ def test_the_batched_step_entries_under_poison(poison, monkeypatch):
 def test_visible_flags_batch_and_occlude_batch_under_poison(poison, monkeypatch):
     filled = poisoned_empty(monkeypatch, poison)
     jobs = 5
-    made = [t_keys_visible._visible_job(H, W, j) for j in range(jobs)]
+    made = [inputs._visible_job(H, W, j) for j in range(jobs)]
     got = propagate_keys_visible.visible_flags_batch([(_dev(P.astype(np.int32)), _dev(Yt), _dev(Yk), _dev(m)) for P, Yt, Yk, m in made], 16)
     for j, (P, Yt, Yk, m) in enumerate(made):
         _same(got[j].cpu().numpy(), vref.visible_flags(Yt, Yk, P, m, 16), ("flags", j))
-    made = [t_keys_visible._occlude_job(H, W, j) for j in range(jobs)]
+    made = [inputs._occlude_job(H, W, j) for j in range(jobs)]
     feed = [(_dev((c / 256).astype(np.float32)), _dev(flags.astype(np.int32))) for c, flags in made]
     counts = torch.arange(jobs, dtype=torch.int32, device=feed[0][0].device) * 3       # added to, not overwritten
     got = propagate_keys_visible.occlude_batch(feed, 4, counts)
@@ -384,7 +370,7 @@ def test_visible_flags_batch_and_occlude_batch_under_poison(poison, monkeypatch)
 def test_merge_gap_and_merge_gap_visible_under_poison(poison, monkeypatch):
     filled = poisoned_empty(monkeypatch, poison)
     span = 3
-    pairs = np.array([(a, b) for a in t_keys.SPECIAL for b in t_keys.SPECIAL], dtype=np.int64)
+    pairs = np.array([(a, b) for a in inputs.KEYS_SPECIAL for b in inputs.KEYS_SPECIAL], dtype=np.int64)
     rng = _rng(span, H, W, 2, 1)
     q = rng.integers(-5000, 5001, (2, 2, H, W))
     q[q == 0] = 1
@@ -393,12 +379,12 @@ def test_merge_gap_and_merge_gap_visible_under_poison(poison, monkeypatch):
     q[0][pick], q[1][pick] = chosen[..., 0][pick], chosen[..., 1][pick]
     got = propagate_keys.merge_gap(_dev(q[0].astype(np.int32)), _dev(q[1].astype(np.int32)), span, 1).cpu().numpy()
     _same_bits(got, np.stack([kref.merge(q[0][f], q[1][f], span, 1 + f) for f in range(2)]), "merge")
-    q, c, cv, f = t_keys_visible._merge_inputs(H, W, span, "random")
+    q, c, cv, f = motion_checks._merge_inputs(H, W, span, "random")
     dq, dc, dcv, df = (_dev(q.astype(np.int32)), _dev((c / 256).astype(np.float32)), _dev((cv / 256).astype(np.float32)),
                        _dev(f.astype(np.int32)))
     for kind in ("none_lost", "a_lost", "both_lost"):
-        na, nb = t_keys_visible._counts(kind, span)
-        want, want_hidden = t_keys_visible._merge_want(q, c, cv, f, na, nb, span)
+        na, nb = inputs._counts(kind, span)
+        want, want_hidden = inputs._merge_want(q, c, cv, f, na, nb, span)
         out, hidden = propagate_keys_visible.merge_gap_visible(dq[0], dq[1], dc[0], dcv[0], dc[1], dcv[1], df[0], df[1],
                                                                _dev(np.array(na, np.int32)), _dev(np.array(nb, np.int32)), span)
         _same_bits(out.cpu().numpy(), want, ("mask", kind))
@@ -410,7 +396,7 @@ def test_merge_gap_and_merge_gap_visible_under_poison(poison, monkeypatch):
 def test_step_fields_under_poison(poison, monkeypatch):
     """34 steps of 18 frames, two launches a level: against the single entries and the restatement, the suite's own test."""
     filled = poisoned_empty(monkeypatch, poison)
-    t_fill.test_batched_fields_equal_the_single_entries_and_the_restatement()
+    motion_checks._check_batched_fields()
     assert filled
 
 
@@ -419,8 +405,8 @@ def test_shot_scores_and_shot_decide_under_poison(poison, monkeypatch):
     filled = poisoned_empty(monkeypatch, poison)
     images = _video(F, H, W, 3)
     for level, search in ((0, 1), (2, 2), (5, 3)):
-        t_shots._check_scores(images, level, search, (level, search))
-    score = t_shots._random_scores(257, 1000, 0)
+        motion_checks._check_scores(images, level, search, (level, search))
+    score = inputs._random_scores(257, 1000, 0)
     for window, ratio, threshold, hist in ((1, 100, 16, 30), (4, 200, 1, 0)):
         want = shref.shot_decide(score, 1000, threshold, hist, ratio, window)
         assert want[-1] > 0
@@ -429,31 +415,6 @@ def test_shot_scores_and_shot_decide_under_poison(poison, monkeypatch):
 
 
 # ---- C: off the default stream, behind a delay ---------------------------------------------------------------------------------------------
-# How long the side stream is held back, in milliseconds.  It has to outlast the host's side of the call.  Measured on the MI355X
-# (the warm call of each of the ten on (23, 33), whole mode, poison 0xFF, host wall time in ms; the first call on a stream, which
-# loads kernels and fills the allocator's pool, is not the warm one: it took up to 208 ms):
-#     propagate_masks 0.68, propagate_masks_visible 0.86, propagate_masks_anchored 0.92, propagate_keys 0.57,
-#     propagate_keys_visible 0.76, temporal_fill 0.56, temporal_fill_checked 0.83, temporal_smooth 0.33,
-#     temporal_smooth_robust 0.29, detect_shots 0.11
-# The largest is 0.92 ms (0.87 in another run).  The host side of ~100 ctypes launches jitters and the test machine is shared, so the delay is not 4 x
-# but more than 100 x that, and still well under a second: the ten tests spend one second waiting in all.
-DELAY_MS = 100
-
-
-@functools.lru_cache(maxsize=None)
-def _spin_cycles_per_ms():
-    """What `torch.cuda._sleep` counts in a millisecond on this device, measured once with events on the default stream."""
-    torch.cuda._sleep(1000)                                            # the kernel's first launch loads it
-    torch.cuda.synchronize()
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    cycles = 20_000_000
-    a.record()
-    torch.cuda._sleep(cycles)
-    b.record()
-    b.synchronize()
-    return cycles / a.elapsed_time(b)
-
-
 @pytest.mark.parametrize("call", CALLS)
 def test_the_call_on_a_held_back_side_stream_reads_nothing_back(call, monkeypatch):
     """The call is made on a side stream that is still busy with a delay queued in front of it.  The delay's event is not done

@@ -12,30 +12,16 @@ import torch
 from lanpaint_amd import _cabi, multiband, multiband_nodes
 from lanpaint_amd._util import raw_stream
 from tests import multiband_ref as ref
+from tests.compare import _raw_bits as _bits
+from tests.device import DEV
+from tests.image_inputs import _band, _image, _multiband_speckle as _speckle, _rng, _soft
 
 pytestmark = pytest.mark.gpu
-DEV = torch.device("cuda", 0)
 # (H, W, C): degenerate axes and clamped taps; around one and two tiles (16 for the reduce, 32 for the collapse), odd sizes at
 # several levels; W * C % 4 != 0 or C = 5: the element-wise form, the others the float4 form at level 0
 SHAPES = [(1, 1, 3), (1, 7, 1), (7, 1, 4), (2, 2, 1), (3, 5, 2), (31, 33, 3), (32, 32, 4), (63, 65, 3), (64, 64, 5), (65, 129, 2),
           (130, 200, 3)]
 LEVELS = (0, 1, 2, 5, 12)
-
-
-def _rng(*key):
-    return np.random.default_rng(list(key))
-
-
-def _image(B, H, W, C, seed=0):
-    return (np.float32(0.05) + np.float32(0.95) * _rng(B, H, W, C, seed).random((B, H, W, C), dtype=np.float32)).astype(np.float32)
-
-
-def _soft(Bm, H, W, seed=1):
-    return _rng(Bm, H, W, seed).random((Bm, H, W), dtype=np.float32)
-
-
-def _speckle(Bm, H, W, seed=2):
-    return (_rng(Bm, H, W, seed).random((Bm, H, W)) < 0.3).astype(np.float32)
 
 
 def _hole(Bm, H, W):
@@ -44,13 +30,6 @@ def _hole(Bm, H, W):
     c = (25, W - 25) if W >= 115 else (10, W - 10) if W >= 85 else (0, W)
     m = np.zeros((Bm, H, W), dtype=np.float32)
     m[:, r[0]:r[1], c[0]:c[1]] = 1.0
-    return m
-
-
-def _band(Bm, H, W):
-    m = np.zeros((Bm, H, W), dtype=np.float32)
-    m[:, :H // 4] = 1.0
-    m[:, :, W - W // 3:] = 1.0
     return m
 
 
@@ -75,10 +54,6 @@ def _mask_forms(Bm, H, W):
     return {"soft": _soft(Bm, H, W), "speckle": _speckle(Bm, H, W), "hole": _hole(Bm, H, W), "band": _band(Bm, H, W),
             "all 0": np.zeros((Bm, H, W), dtype=np.float32), "all 1": np.ones((Bm, H, W), dtype=np.float32),
             "corner": _corner(Bm, H, W), "nan": _nan_mask(Bm, H, W), "wide": _wide(Bm, H, W)}
-
-
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
 
 
 def _blend(a, b, mask, levels):

@@ -56,7 +56,7 @@ def test_hip_matches_reference_schedule(name):
     are compared with the port under one torch seed in tests/test_gpu_port_on_device.py."""
     import torch
     from lanpaint_amd import LanPaint
-    from tests.test_oracle_golden import _options_for_call, check_schedule_traces
+    from tests.golden_cases import _options_for_call, check_schedule_traces
     sc = gc.build_schedule(name)
     g = load_golden(name)
     dev = "cuda"

@@ -14,20 +14,16 @@ import torch
 from lanpaint_amd import _cabi, fill, fill_patch_nodes
 from lanpaint_amd._util import raw_stream
 from tests import patch_fill_ref as pref
+from tests.compare import _raw_bits as _bits
+from tests.device import DELAY_MS, DEV, _spin_cycles_per_ms
 from tests.helpers import record_launches
 from tests.poison import poisoned_empty
-from tests.test_gpu_motion_scratch import _spin_cycles_per_ms
 
 pytestmark = pytest.mark.gpu
-DEV = torch.device("cuda", 0)
 GUARD = 64                                                             # bytes behind the workspace and behind the output
 FORMS = ("centre", "borders", "speckle30", "speckle2", "known", "masked", "corner", "nan", "half")
 SMALL_SHAPES = [(1, 1, 3), (1, 7, 1), (7, 1, 4), (5, 5, 3)]
 LARGE_SHAPES = [(31, 33, 3), (33, 65, 4), (64, 96, 1), (65, 129, 2)]
-
-
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
 
 
 @functools.lru_cache(maxsize=None)
@@ -274,9 +270,6 @@ def test_the_node_runs_end_to_end_from_host_tensors():
 
 
 # ---- off the null stream, behind a delay; the launch record -----------------------------------------------------------------------------------
-DELAY_MS = 100                                                         # tests/test_gpu_image_scratch.py's, for the same reasons
-
-
 def test_the_wrapper_on_a_held_back_side_stream_reads_nothing_back(monkeypatch):
     """As tests/test_gpu_image_scratch.py has it for fill_masked: made on a side stream that is still busy with a delay, the call
     returns before the delay is done (no device -> host read, no synchronisation), leaves nothing on the null stream, makes one

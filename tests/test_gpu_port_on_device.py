@@ -17,14 +17,13 @@ import sys
 
 import numpy as np
 import pytest
+from tests.port_checks import PortOnDevice, _compare
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 from tests.stubs import FlowSampling, VESampling      # noqa: E402
-
-REL, MSE = 2e-5, 1e-9
 
 
 class TwoHeads:
@@ -38,24 +37,6 @@ class TwoHeads:
     def __call__(self, x, t, model_options=None, seed=None):
         self.calls += 1
         return 0.9 * x, 0.8 * x
-
-
-class PortOnDevice:
-    """The port behind the reference's constructor / call signature (lanpaint.py:8,44): the replace step goes through the
-    model_sampling's own noise_scaling like the reference's does (lanpaint.py:84-92)."""
-
-    def __init__(self, Model, NSteps, Friction, Lambda, Beta, StepSize, IS_FLUX=False, IS_FLOW=False, EarlyStopThreshold=0.0,
-                 EarlyStopPatience=1, EarlyStopHook=None, MinStepFrac=0.0):
-        from oracle.lanpaint_oracle import OracleLanPaint, TorchBackend
-        ms = Model.inner_model.model_sampling
-        self.inner_model = Model
-        self.port = OracleLanPaint(Model, NSteps, Friction, Lambda, Beta, StepSize, is_flux=IS_FLUX, is_flow=IS_FLOW,
-                                   early_stop_threshold=EarlyStopThreshold, early_stop_patience=EarlyStopPatience,
-                                   min_step_frac=MinStepFrac, backend=TorchBackend(), noise_scaling=ms.noise_scaling,
-                                   noise_scale=float(getattr(ms, "noise_scale", 1.0)))
-
-    def __call__(self, x, latent_image, noise, sigma, latent_mask, current_times, model_options, seed, n_steps=None, **kw):
-        return self.port(x, latent_image, noise, sigma, latent_mask, current_times, model_options, seed, n_steps=n_steps, **kw)
 
 
 def _reference_class():
@@ -101,18 +82,6 @@ def _walk(engine, job, seed, inference=False):
                 x = torch.lerp(den, x, job["ratios"][i])
     torch.cuda.synchronize()
     return outs, xs, torch.cuda.get_rng_state(0).clone()
-
-
-def _compare(got, want, what):
-    import torch
-    g, w = got.double(), want.double()
-    assert torch.isfinite(g).all(), f"{what}: non-finite values"
-    scale = max(1.0, float(w.abs().max()))
-    err = float((g - w).abs().max())
-    mse = float(((g - w) ** 2).mean())
-    assert err <= REL * scale, f"{what}: max abs err {err:.3e} > {REL * scale:.3e}"
-    assert mse <= MSE * scale * scale, f"{what}: MSE {mse:.3e}"
-    return err / scale, mse
 
 
 def _engines(job, **product_kw):
@@ -273,7 +242,7 @@ def test_av_pack_port_on_gpu_vs_default_engine_same_seed(shape, split, rows_diff
     """The flat audio+video pack (lanpaint.py:60-74, 173-180: per-element blended times, the audio correction on the score)
     through the reference on the GPU and through the product's two-row table path, same seed, three calls with moving times."""
     import torch
-    from tests.test_gpu_av import _case
+    from tests.port_checks import _case
     from lanpaint_amd import LanPaint
     from oracle import lanpaint_oracle as orc
     c = _case(shape, split, seed=77, rows_differ=rows_differ)
@@ -345,7 +314,7 @@ def test_av_pack_with_inner_early_stop_port_on_gpu_vs_default_engine_same_seed(k
     earlystop.py:104-110) against the product on the two-row table -- watched eager launches (default engine, a fresh options
     dict per call) and the device-gated launches of a replayed graph (round 5)."""
     import torch
-    from tests.test_gpu_av import _case
+    from tests.port_checks import _case
     from lanpaint_amd import LanPaint
     shape, split, n_steps = (1, 8, 66000), 40001, 8
     c = _case(shape, split, seed=78)

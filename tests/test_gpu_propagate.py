@@ -2,7 +2,6 @@
 tests/propagate_ref.py.  The rule is integer arithmetic throughout, so the device must give the restatement's values whatever tile,
 block or chunk a launch uses: every comparison covers every element and has no tolerance.  Each stage is compared on its own (fed
 with the restatement's inputs for that stage) and the whole chain as well."""
-import functools
 
 import numpy as np
 import pytest
@@ -10,110 +9,13 @@ import torch
 
 from lanpaint_amd import _cabi, propagate, propagate_nodes
 from tests import propagate_ref as ref
+from tests.compare import _f32_bits as _bits, _same_bits, _same_ints as _same
+from tests.device import _dev, _levels_of
+from tests.inputs import BIG, MASKS, PLANES, VIDEOS, _advance_case, _disc, _rng, _soft, _video
+from tests.motion_checks import _check_match
 
 pytestmark = pytest.mark.gpu
-DEV = torch.device("cuda", 0)
-# one under, at and one over the block (8) and the window (16), odd sizes at every pyramid level; (70, 130): several workgroups of
-# every kernel (32 x 32 tiles, a 9 x 17 grid)
-PLANES = [(1, 1), (1, 7), (7, 1), (8, 8), (9, 15), (16, 17), (23, 33), (40, 70)]
-BIG = (70, 130)
 ONE = np.float32(1.0).view(np.uint32)
-
-
-def _rng(*key):
-    return np.random.default_rng([abs(int(k)) for k in key])
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
-
-
-def _dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
-
-
-# ---- inputs ---------------------------------------------------------------------------------------------------------------------------
-def _video(F, H, W, C=3, seed=0):
-    """Frames cut out of one random canvas, moving by (2, -3) pixels per frame, with a little noise of their own."""
-    rng = _rng(F, H, W, C, seed)
-    canvas = rng.random((H + 2 * F, W + 3 * F, C), dtype=np.float32)
-    frames = [canvas[2 * t:2 * t + H, 3 * (F - 1 - t):3 * (F - 1 - t) + W] for t in range(F)]
-    return (np.stack(frames) + rng.normal(0, 0.02, (F, H, W, C))).astype(np.float32)
-
-
-def _constant(F, H, W, C=3, seed=0):
-    return np.full((F, H, W, C), 0.375, np.float32)
-
-
-def _wild_video(F, H, W, C=3, seed=0):
-    """Values outside [0, 1], NaN and infinities."""
-    rng = _rng(F, H, W, C, seed, 1)
-    v = (3.0 * rng.random((F, H, W, C)) - 1.0).astype(np.float32)
-    pick = rng.random((F, H, W, C))
-    v[pick < 0.1] = np.nan
-    v[(pick >= 0.1) & (pick < 0.15)] = np.inf
-    v[(pick >= 0.15) & (pick < 0.2)] = -np.inf
-    return v
-
-
-VIDEOS = {"random": _video, "constant": _constant, "wild": _wild_video}
-
-
-def _disc(H, W, seed=0):
-    """A disc that touches the border."""
-    yy, xx = np.mgrid[:H, :W]
-    r = max(min(H, W) / 3, 1)
-    return ((yy - r + 1) ** 2 + (xx - W + r) ** 2 <= r * r).astype(np.float32)
-
-
-def _soft(H, W, seed=0):
-    return _rng(H, W, seed, 2).random((H, W), dtype=np.float32)
-
-
-def _threshold(H, W, seed=0):
-    v = np.float32(0.5)
-    return _rng(H, W, seed, 3).choice(np.array([np.nextafter(v, np.float32(0)), v, np.nextafter(v, np.float32(1))]), (H, W))
-
-
-def _wild_mask(H, W, seed=0):
-    rng = _rng(H, W, seed, 4)
-    m = (3.0 * rng.random((H, W)) - 1.0).astype(np.float32)
-    pick = rng.random((H, W))
-    m[pick < 0.15] = np.nan
-    m[(pick >= 0.15) & (pick < 0.2)] = np.inf
-    m[(pick >= 0.2) & (pick < 0.25)] = -np.inf
-    return m
-
-
-def _pixels(H, W, n):
-    """n mask pixels in the top left corner, all inside block (0, 0)'s window."""
-    m = np.zeros((H, W), np.float32)
-    m.reshape(-1)[[y * W + x for y in range(min(H, 4)) for x in range(min(W, 4))][:n]] = 1
-    return m
-
-
-MASKS = {"empty": lambda H, W, s=0: np.zeros((H, W), np.float32), "full": lambda H, W, s=0: np.ones((H, W), np.float32),
-         "one pixel": lambda H, W, s=0: _pixels(H, W, 1), "15 pixels": lambda H, W, s=0: _pixels(H, W, 15),
-         "16 pixels": lambda H, W, s=0: _pixels(H, W, 16), "disc": _disc, "soft": _soft, "threshold": _threshold, "wild": _wild_mask}
-
-
-def _levels_of(pyr, H, W, levels):
-    """The device's frame pyramids uint8 [n, stride] as one numpy array per level."""
-    host = pyr.cpu()
-    return [propagate.level_view(host, H, W, lv).numpy() for lv in range(levels)]
-
-
-def _same(got, want, what):
-    got, want = np.asarray(got), np.asarray(want)
-    assert got.shape == want.shape, (what, got.shape, want.shape)
-    bad = got.astype(np.int64) != want.astype(np.int64)
-    assert not bad.any(), (what, int(bad.sum()), np.argwhere(bad)[:4].tolist())
-
-
-def _same_bits(got, want, what):
-    assert got.dtype == np.float32 and got.shape == want.shape, what
-    bad = _bits(got) != _bits(want)
-    assert not bad.any(), (what, int(bad.sum()), np.argwhere(bad)[:4].tolist())
 
 
 # ---- stage 1 and 2: luma and pyramids ---------------------------------------------------------------------------------------------------
@@ -147,32 +49,6 @@ def test_key_mask_and_its_pyramid_equal_the_restatement(form):
 
 
 # ---- stage 3: the match, the fill and median, the advance, each fed with the restatement's inputs -------------------------------------------
-def _packed(planes, H, W, levels):
-    """numpy planes of one frame's pyramid -> the device's byte string."""
-    row = np.zeros(_cabi.prop_pyramid_ws_bytes(1, H, W, levels), np.uint8)
-    for lv, p in enumerate(planes):
-        off = _cabi.prop_level_offset(H, W, lv)
-        row[off:off + p.size] = p.reshape(-1)
-    return _dev(row)
-
-
-def _check_match(H, W, levels, search, smooth, video, mask, what):
-    images = VIDEOS[video](2, H, W, 3, seed=search)
-    Y = ref.luma(images)
-    ps, pt = (ref.pyramid(Y[f], levels, ref.down_luma) for f in range(2))
-    pm = ref.pyramid(ref.binarise(MASKS[mask](H, W)), levels, ref.down_mask)
-    src, tgt, mpyr = (_packed(p, H, W, levels) for p in (ps, pt, pm))
-    _, trace = ref.motion_field(ps, pt, pm, search, smooth)
-    for lv in range(levels - 1, -1, -1):
-        raw, valid, final = trace[lv]
-        parent = None if lv == levels - 1 else _dev(trace[lv + 1][2].astype(np.int32))
-        vec, ok = propagate.match_level(src, tgt, mpyr, H, W, levels, lv, search, smooth, parent)
-        _same(ok.cpu().numpy(), valid, (what, "valid", lv))
-        _same(vec.cpu().numpy(), raw, (what, "vec", lv))
-        _same(propagate.fill_median(vec, ok).cpu().numpy(), final, (what, "fill and median", lv))
-    return trace
-
-
 @pytest.mark.parametrize("search,smooth", [(1, 0), (2, 8), (7, 64)])
 def test_match_equals_the_restatement_on_every_plane(search, smooth):
     for H, W in PLANES:
@@ -207,18 +83,6 @@ def test_fill_and_median_equal_the_restatement(grid):
         valid = rng.random((gh, gw)) < density
         got = propagate.fill_median(_dev(vec), _dev(valid.astype(np.int32))).cpu().numpy()
         _same(got, ref.fill_median(vec, valid), (grid, density))
-
-
-@functools.lru_cache(maxsize=None)
-def _advance_case(H, W, scale):
-    rng = _rng(H, W, scale)
-    gh, gw = ref.grid_of(H, W)
-    vec = rng.integers(-scale, scale + 1, (gh, gw, 2)).astype(np.int32)
-    vec2 = rng.integers(-scale, scale + 1, (gh, gw, 2)).astype(np.int32)
-    bits = (rng.random((H, W)) < 0.5).astype(np.uint8)
-    P1, c1 = ref.advance(ref.key_positions(H, W), vec, bits)
-    P2, c2 = ref.advance(P1, vec2, bits)
-    return vec, vec2, bits, P1, c1, P2, c2
 
 
 @pytest.mark.parametrize("scale", [0, 40, 7100])

@@ -10,83 +10,19 @@ import torch
 
 from lanpaint_amd import _cabi, propagate, propagate_anchored, propagate_anchored_nodes, shots
 from tests import propagate_anchored_ref as aref
-from tests import propagate_ref as ref
 from tests.anchor_clips import subpixel_clip
+from tests.compare import _same_bits, _same_ints as _same
+from tests.device import DEV, _dev
 from tests.helpers import record_launches
-from tests.test_gpu_propagate_visible import PLANES, _positions
-from tests.test_propagate_anchored_host import assert_the_two_iou_lines, drift_case
+from tests.inputs import ANCHORED_MASKS as MASKS, VISIBLE_PLANES as PLANES, _anchored_inputs as _inputs
+from tests.motion_checks import _anchored_field as _device_field
+from tests.propagate_scenes import assert_the_two_drift_iou_lines as assert_the_two_iou_lines, drift_case
 
 pytestmark = pytest.mark.gpu
-DEV = torch.device("cuda", 0)
 ANCHORS, SMOOTHS, POSITIONS, LUMAS = (1, 2, 7), (0, 8, 64), ("key", "smooth", "outside"), ("noisy", "flat")
 
 
-def _rng(*key):
-    return np.random.default_rng([abs(int(k)) for k in key])
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
-
-
-def _dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
-
-
-def _same(got, want, what):
-    got, want = np.asarray(got), np.asarray(want)
-    assert got.shape == want.shape, (what, got.shape, want.shape)
-    bad = got.astype(np.int64) != want.astype(np.int64)
-    assert not bad.any(), (what, int(bad.sum()), np.argwhere(bad)[:4].tolist())
-
-
-def _same_bits(got, want, what):
-    assert got.dtype == np.float32 and got.shape == want.shape, what
-    bad = _bits(got) != _bits(want)
-    assert not bad.any(), (what, int(bad.sum()), np.argwhere(bad)[:4].tolist())
-
-
 # ---- inputs of the launch -------------------------------------------------------------------------------------------------------------
-def _lumas(kind, H, W):
-    """(Yt, Yk) uint8.  noisy: a random key plane and the same plane moved by (1, -1) plus noise, so the winner is mostly off the
-    centre and the sub-pixel step has work; flat: two values only, so candidates tie and the key order decides."""
-    rng = _rng(H, W, 19)
-    if kind == "noisy":
-        Yk = rng.integers(0, 256, (H, W))
-        Yt = np.roll(Yk, (1, -1), (0, 1)) + np.round(rng.normal(0, 12, (H, W)))
-    else:
-        Yk = 128 + rng.integers(0, 2, (H, W))
-        Yt = 128 + rng.integers(0, 2, (H, W))
-    return np.clip(Yt, 0, 255).astype(np.uint8), Yk.astype(np.uint8)
-
-
-def _disc(H, W):
-    """A disc that touches the border."""
-    yy, xx = np.mgrid[:H, :W]
-    r = max(min(H, W) / 3, 1)
-    return ((yy - r + 1) ** 2 + (xx - W + r) ** 2 <= r * r).astype(np.uint8)
-
-
-def _random(H, W):
-    """The density grows from 0.02 on the left to 0.5 on the right: windows under LP_PROP_MIN_PIXELS, at it and over it."""
-    density = 0.02 + 0.48 * np.arange(W)[None, :] / max(W - 1, 1)
-    return (_rng(H, W, 20).random((H, W)) < density).astype(np.uint8)
-
-
-MASKS = {"empty": lambda H, W: np.zeros((H, W), np.uint8), "full": lambda H, W: np.ones((H, W), np.uint8), "disc": _disc, "random": _random}
-
-
-def _inputs(plane, positions, lumas, mask):
-    H, W = plane
-    return _positions(positions, H, W), *_lumas(lumas, H, W), MASKS[mask](H, W)
-
-
-def _device_field(P, Yt, Yk, m, anchor, smooth):
-    vec, valid = propagate_anchored.anchor_field(_dev(P.astype(np.int32)), _dev(Yt), _dev(Yk), _dev(m), anchor, smooth)
-    assert vec.dtype == valid.dtype == torch.int32 and tuple(valid.shape) == ref.grid_of(*Yt.shape) and tuple(vec.shape) == (*valid.shape, 2)
-    return vec.cpu().numpy(), valid.cpu().numpy()
-
-
 def _restatement_cases():
     """Every plane with every mask; the anchors, smooths, positions and lumas turn with the plane and the mask, so that every value
     of each meets every plane size class and every mask.  anchor 7 (225 candidates, four passes of the lanes) costs the restatement

@@ -3,7 +3,6 @@ lp_prop_anchor_match_gated in csrc/propagate_kernel.hip) against the numpy resta
 against the ungated launch.  The rule is integer arithmetic, so every comparison covers every element and has no tolerance.  The
 new launch is compared on its own, fed with inputs made here, and the whole chain as well.  Without the feature this file fails at
 its imports."""
-import functools
 
 import numpy as np
 import pytest
@@ -12,76 +11,23 @@ import torch
 from lanpaint_amd import (_cabi, propagate, propagate_anchored, propagate_anchored_visible, propagate_anchored_visible_nodes,
                           propagate_visible, shots)
 from tests import propagate_anchored_visible_ref as avref
-from tests import propagate_ref as ref
 from tests.anchor_clips import subpixel_clip
+from tests.compare import _same_bits, _same_ints as _same
+from tests.device import DEV, _dev
 from tests.helpers import record_launches
-from tests.test_gpu_propagate_anchored import MASKS
-from tests.test_gpu_propagate_visible import PLANES, _positions
-from tests.test_gpu_propagate_visible import _lumas as _visible_lumas
-from tests.test_propagate_anchored_visible_host import assert_the_quality_lines, quality_case
+from tests.inputs import (ANCHORED_MASKS as MASKS, ANCHORED_VISIBLE_LEVELS as LEVELS, VISIBLE_PLANES as PLANES,
+                          _anchored_visible_clip as _clip, _anchored_visible_inputs as _inputs, _anchored_visible_want as _want)
+from tests.motion_checks import _anchored_visible_call as _call, _anchored_visible_field as _device_field
+from tests.propagate_scenes import anchored_quality_case as quality_case, assert_the_anchored_quality_lines as assert_the_quality_lines
 
 pytestmark = pytest.mark.gpu
-DEV = torch.device("cuda", 0)
 ANCHORS, SMOOTHS, OCCLUSIONS, POSITIONS, LUMAS = (1, 2, 7), (0, 8, 64), (1, 16, 255), ("key", "smooth", "outside"), ("noisy", "dark")
 # 1 x 1, 1 x 7, 8 x 8, 9 x 15: partial tiles and blocks; 33 x 64: the vector path; 70 x 132: several tiles
 LAUNCH_PLANES = [(1, 1), (1, 7), (8, 8), (9, 15), (33, 64), (70, 132)]
 assert set(LAUNCH_PLANES) <= set(PLANES)
 
 
-def _rng(*key):
-    return np.random.default_rng([abs(int(k)) for k in key])
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
-
-
-def _dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
-
-
-def _same(got, want, what):
-    got, want = np.asarray(got), np.asarray(want)
-    assert got.shape == want.shape, (what, got.shape, want.shape)
-    bad = got.astype(np.int64) != want.astype(np.int64)
-    assert not bad.any(), (what, int(bad.sum()), np.argwhere(bad)[:4].tolist())
-
-
-def _same_bits(got, want, what):
-    assert got.dtype == np.float32 and got.shape == want.shape, what
-    bad = _bits(got) != _bits(want)
-    assert not bad.any(), (what, int(bad.sum()), np.argwhere(bad)[:4].tolist())
-
-
 # ---- inputs of the launch -------------------------------------------------------------------------------------------------------------
-def _lumas(kind, H, W):
-    """(Yt, Yk) uint8.  noisy: a random key plane and the same plane moved by (1, -1) plus noise whose amplitude grows from 0 to 60
-    grey levels from left to right, so the winner is mostly off the centre and the gate's residual crosses every threshold
-    somewhere; dark: the visible test's kind, t darker than the key by 20 to 60, so mu runs into its clamp at -32."""
-    if kind == "dark":
-        return _visible_lumas("dark", H, W)
-    rng = _rng(H, W, 21)
-    xx = np.broadcast_to(np.arange(W)[None, :] / max(W - 1, 1), (H, W))
-    Yk = rng.integers(0, 256, (H, W))
-    Yt = np.roll(Yk, (1, -1), (0, 1)) + np.round(rng.normal(0, 1, (H, W)) * 60 * xx)
-    return np.clip(Yt, 0, 255).astype(np.uint8), Yk.astype(np.uint8)
-
-
-@functools.lru_cache(maxsize=None)
-def _inputs(plane, positions, lumas, mask):
-    """(P, Yt, Yk, m) in numpy, shared: not to be written to."""
-    H, W = plane
-    return _positions(positions, H, W), *_lumas(lumas, H, W), MASKS[mask](H, W)
-
-
-def _device_field(P, Yt, Yk, m, anchor, smooth, occlusion):
-    vec, valid, gated = propagate_anchored_visible.gated_anchor_field(_dev(P.astype(np.int32)), _dev(Yt), _dev(Yk), _dev(m), anchor,
-                                                                      smooth, occlusion)
-    assert vec.dtype == valid.dtype == gated.dtype == torch.int32
-    assert tuple(valid.shape) == tuple(gated.shape) == ref.grid_of(*Yt.shape) and tuple(vec.shape) == (*valid.shape, 2)
-    return vec.cpu().numpy(), valid.cpu().numpy(), gated.cpu().numpy()
-
-
 def _restatement_cases():
     """Every plane with every mask; the anchors, smooths, occlusions, positions and lumas turn with the plane and the mask, so
     that every value of each meets every mask.  anchor 7 (225 candidates, four passes of the lanes) costs the restatement the most:
@@ -172,35 +118,6 @@ def test_gated_anchor_field_on_unaligned_planes_takes_the_scalar_path_with_the_s
 
 
 # ---- the whole chain ------------------------------------------------------------------------------------------------------------------
-LEVELS = 3
-
-
-@functools.lru_cache(maxsize=None)
-def _clip(F, H, W, key, seed=0):
-    """The sub-pixel clip with something in front of the subject on every frame but the key: three columns of another texture
-    through the disc's right half, so that blocks are gated and flags fire from the first step on."""
-    images, truth = subpixel_clip(F, H, W, seed=seed)
-    x = int(0.3 * W + min(H, W) / 10)
-    bar = _rng(H, W, 22).random((H, 3, 1)).astype(np.float32)
-    for f in range(F):
-        if f != key:
-            images[f, :, x:x + 3, :] = bar
-    images.setflags(write=False)
-    return images, truth
-
-
-@functools.lru_cache(maxsize=None)
-def _want(F, H, W, key):
-    images, truth = _clip(F, H, W, key)
-    trace = {}
-    want = avref.propagate_anchored_visible_ref(images, truth[key].astype(np.float32), key, LEVELS, 2, 8, 2, 16, trace)
-    return want, trace
-
-
-def _call(images, mask, key, anchor=2, occlusion=16):
-    return propagate_anchored_visible.propagate_masks_anchored_visible(images, mask, key, LEVELS, 2, 8, anchor, occlusion)
-
-
 @pytest.mark.parametrize("plane", [(23, 33), (40, 56)], ids=lambda s: "x".join(map(str, s)))
 @pytest.mark.parametrize("frames,key", [(1, 0), (2, 1), (7, 3)])
 def test_the_chain_equals_the_restatement_bit_for_bit(plane, frames, key):

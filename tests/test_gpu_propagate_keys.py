@@ -12,20 +12,15 @@ import torch
 from lanpaint_amd import _cabi, propagate, propagate_keys, propagate_keys_nodes, stabilize
 from tests import propagate_keys_ref as kref
 from tests import propagate_ref as ref
-from tests import stabilize_ref as stab
+from tests.compare import _f32_bits as _bits, _same_bits
+from tests.device import DEV, _dev, _equal
 from tests.helpers import record_launches
-from tests.test_gpu_propagate import MASKS, _bits, _dev, _disc, _rng, _same_bits, _soft, _video
+from tests.inputs import KEYS_SPECIAL as SPECIAL, MASKS, _disc, _rng, _soft, _video
+from tests.motion_checks import _check_batched_entries
 
 pytestmark = pytest.mark.gpu
-DEV = torch.device("cuda", 0)
 ONE = np.float32(1.0).view(np.uint32)
 BIG = (70, 130)                                                       # several workgroups of every kernel
-PARAMS = [(1, 1, 0), (3, 2, 8), (6, 7, 64)]                           # levels, search, smooth
-JOB_MASKS = ("disc", "soft", "full", "16 pixels", "wild", "threshold", "empty")
-
-
-def _equal(got, want, what):
-    assert got.dtype == want.dtype and got.shape == want.shape and torch.equal(got, want), what
 
 
 # ---- the batched entries against the single entries --------------------------------------------------------------------------------------
@@ -34,39 +29,7 @@ def _equal(got, want, what):
 def test_batched_entries_equal_the_single_entries(plane, jobs):
     """Job i goes from frame i to frame i + 1 of one video under a mask of its own; odd jobs carry positions, even jobs start from
     the key's, in one launch."""
-    H, W = plane
-    images = _dev(_video(jobs + 1, H, W, 3, seed=jobs))
-    rng = _rng(H, W, jobs)
-    for levels, search, smooth in PARAMS:
-        pyr = propagate.luma_pyramids(images, levels)
-        keys = [propagate.key_mask(_dev(MASKS[JOB_MASKS[i % len(JOB_MASKS)]](H, W, i)), levels)[0] for i in range(jobs)]
-        pos = [None if i % 2 == 0 else _dev(np.maximum(ref.key_positions(H, W) + rng.integers(-40, 41, (H, W, 2)), 0).astype(np.int32))
-               for i in range(jobs)]
-        single, parents = [], [None] * jobs
-        for i in range(jobs):
-            trace, parent = [], None
-            for lv in range(levels - 1, -1, -1):
-                vec, valid = propagate.match_level(pyr[i], pyr[i + 1], keys[i], H, W, levels, lv, search, smooth, parent)
-                parent = propagate.fill_median(vec, valid)
-                trace.append((vec, valid, parent))
-            bits = propagate.level_view(keys[i], H, W, 0)[0]
-            single.append((trace, propagate.advance(parent, pos[i], bits, levels)))
-        for n, lv in enumerate(range(levels - 1, -1, -1)):
-            got = propagate_keys.match_level_batch([(pyr[i], pyr[i + 1], keys[i], parents[i]) for i in range(jobs)], H, W, levels, lv,
-                                                   search, smooth)
-            parents = propagate_keys.fill_median_batch(got)
-            for i in range(jobs):
-                what = (plane, jobs, levels, "level", lv, "job", i)
-                _equal(got[i][0], single[i][0][n][0], (*what, "vec"))
-                _equal(got[i][1], single[i][0][n][1], (*what, "valid"))
-                _equal(parents[i], single[i][0][n][2], (*what, "field"))
-        got = propagate_keys.advance_batch([(parents[i], pos[i], propagate.level_view(keys[i], H, W, 0)[0]) for i in range(jobs)], levels)
-        for i in range(jobs):
-            for g, w, name in zip(got[i][:2], single[i][1][:2], ("positions", "mask")):
-                _equal(g, w, (plane, jobs, levels, "job", i, name))
-            for lv in range(levels):                                  # the bytes between two levels belong to nobody
-                _equal(propagate.level_view(got[i][2], H, W, lv), propagate.level_view(single[i][1][2], H, W, lv),
-                       (plane, jobs, levels, "job", i, "pyramid level", lv))
+    _check_batched_entries(plane, jobs)
 
 
 def test_the_wrappers_refuse_more_jobs_than_a_launch_holds_and_mixed_planes():
@@ -81,9 +44,6 @@ def test_the_wrappers_refuse_more_jobs_than_a_launch_holds_and_mixed_planes():
 
 
 # ---- the merge ---------------------------------------------------------------------------------------------------------------------------
-SPECIAL = [1, -1, 2, -2, 3, -3, 4095, 4096, 4097, -4095, -4096, -4097, stab.Q_FAR, -stab.Q_FAR, 2 * 16383 ** 2, -2 * 16383 ** 2]
-
-
 @pytest.mark.parametrize("span", [2, 3, 7, 65535])
 def test_merge_equals_the_restatement(span):
     pairs = np.array([(a, b) for a in SPECIAL for b in SPECIAL], dtype=np.int64)        # every pair: equal and opposite signs

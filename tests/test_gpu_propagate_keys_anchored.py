@@ -11,74 +11,27 @@ import torch
 
 from lanpaint_amd import (_cabi, propagate, propagate_anchored, propagate_keys, propagate_keys_anchored,
                           propagate_keys_anchored_nodes)
-from tests import propagate_anchored_ref as aref
 from tests import propagate_keys_anchored_ref as karef
 from tests import propagate_keys_ref as kref
 from tests import propagate_ref as ref
-from tests.anchor_clips import subpixel_clip
+from tests.compare import _f32_bits as _bits, _same_bits, _same_ints as _same
+from tests.device import DELAY_MS, DEV, _dev, _equal, _spin_cycles_per_ms
 from tests.helpers import record_launches
+from tests.inputs import (BATCH_PLANES, JOB_MASKS, KEYS_ANCHORED_ANCHOR as ANCHOR, KEYS_ANCHORED_CLIPS as CLIPS,
+                          KEYS_ANCHORED_LEVELS as LEVELS, KEYS_ANCHORED_SEARCH as SEARCH, KEYS_ANCHORED_SMOOTH as SMOOTH, MASKS, _job,
+                          _job_field, _keys_anchored_clip as _clip, _soft, _video)
+from tests.motion_checks import _offset_view
 from tests.poison import poisoned_empty
-from tests.test_gpu_motion_scratch import DELAY_MS, _spin_cycles_per_ms
-from tests.test_gpu_propagate import MASKS, _bits, _dev, _rng, _same, _same_bits, _soft, _video
-from tests.test_gpu_propagate_visible import _positions
-from tests.test_propagate_keys_anchored_host import assert_the_two_iou_lines, gap_drift_case
+from tests.propagate_scenes import assert_the_two_gap_iou_lines as assert_the_two_iou_lines, gap_drift_case
 
 pytestmark = pytest.mark.gpu
-DEV = torch.device("cuda", 0)
 ONE = np.float32(1.0).view(np.uint32)
-LEVELS, SEARCH, SMOOTH, ANCHOR = 3, 2, 8, 2
 STEP = ["lp_prop_match_batch", "lp_prop_fill_batch"] * LEVELS + ["lp_prop_advance_batch", "lp_prop_match_batch", "lp_prop_fill_batch",
                                                                   "lp_prop_advance_batch"]
 
 
-def _equal(got, want, what):
-    assert got.dtype == want.dtype and got.shape == want.shape and torch.equal(got, want), what
-
-
 # ---- the batched warped match -----------------------------------------------------------------------------------------------------------
-# (1, 1), (7, 9), (33, 70): no side a multiple of 4 or 32, the scalar path; (40, 72): the vector path, several tiles
-BATCH_PLANES = [(1, 1), (7, 9), (33, 70), (40, 72)]
-JOB_POSITIONS = ("key", "smooth", "outside")
-JOB_MASKS = ("disc", "random", "15 pixels", "full", "empty")              # job 2 of a launch has 15 pixels: under LP_PROP_MIN_PIXELS
 NUMBERS = [(1, 0), (2, 8), (7, 64)]                                    # anchor, smooth
-
-
-def _random_mask(H, W, i):
-    density = 0.02 + 0.48 * np.arange(W)[None, :] / max(W - 1, 1)
-    return (_rng(H, W, i, 21).random((H, W)) < density).astype(np.float32)
-
-
-@functools.lru_cache(maxsize=None)
-def _job(H, W, i):
-    """Job i of a plane, the same in every launch that holds it: (P int32 [H, W, 2], Yt, Yk, m uint8 [H, W]).  The frame is the key
-    moved by (1, -1) plus noise, so the winner is mostly off the centre and the sub-pixel step has work."""
-    rng = _rng(H, W, i, 38)
-    Yk = rng.integers(0, 256, (H, W))
-    Yt = np.clip(np.roll(Yk, (1, -1), (0, 1)) + np.round(rng.normal(0, 12, (H, W))), 0, 255)
-    P = _positions(JOB_POSITIONS[i % 3], H, W) + (0 if i % 3 == 0 else rng.integers(-6, 7, (H, W, 2)))
-    kind = JOB_MASKS[i % len(JOB_MASKS)]
-    m = _random_mask(H, W, i) if kind == "random" else MASKS[kind](H, W, i)
-    out = (P.astype(np.int32), Yt.astype(np.uint8), Yk.astype(np.uint8), ref.binarise(m).astype(np.uint8))
-    for a in out:
-        a.setflags(write=False)
-    return out
-
-
-@functools.lru_cache(maxsize=None)
-def _job_field(H, W, i, anchor, smooth):
-    P, Yt, Yk, m = _job(H, W, i)
-    return aref.anchor_field(P.astype(np.int64), Yt, Yk, m, anchor, smooth)
-
-
-def _offset_view(a, offset, stride=None):
-    """`a` on the device as a view `offset` bytes into a buffer of its own, as one row of `stride` elements if given (the rest of
-    a pyramid row: 0xA5, which nobody may read)."""
-    t = torch.from_numpy(np.ascontiguousarray(a))
-    n = t.numel() if stride is None else stride
-    buf = torch.full((offset // t.element_size() + n,), 0xA5 if t.dtype == torch.uint8 else -1, dtype=t.dtype, device=DEV)
-    view = buf[offset // t.element_size():]
-    view[:t.numel()] = t.reshape(-1).to(DEV)
-    return view if stride is not None else view.view(a.shape)
 
 
 @pytest.mark.parametrize("plane", BATCH_PLANES, ids=lambda s: "x".join(map(str, s)))
@@ -150,28 +103,6 @@ def test_the_batched_warped_match_moves_and_refuses():
 
 
 # ---- the whole call ----------------------------------------------------------------------------------------------------------------------
-# per plane: the frames, then one key first, in the middle, last; two adjacent keys (no in-between frame); both ends; three keys
-CLIPS = {(9, 7): (6, [[0], [3], [5], [2, 3], [0, 5], [0, 2, 5]]), (40, 70): (7, [[0], [3], [6], [2, 3], [0, 6], [0, 3, 6]])}
-
-
-@functools.lru_cache(maxsize=None)
-def _clip(plane, half=False):
-    """(images, their luma planes, their luma pyramids, a painting per frame).  (40, 70): the disc that moves a fraction of a pixel
-    a frame, painted with the truth; (9, 7), too small for it: the moving canvas under random paintings."""
-    F = CLIPS[plane][0]
-    if plane == (9, 7):
-        images, painted = _video(F, *plane, 3, seed=38), np.stack([_soft(*plane, k) for k in range(F)])
-    else:
-        images, truth = subpixel_clip(F, *plane, vy=0.43, vx=0.71)
-        painted = truth.astype(np.float32)
-    if half:
-        images = images.astype(np.float16).astype(np.float32)
-    Y = ref.luma(images)
-    for a in (images, painted):
-        a.setflags(write=False)
-    return images, Y, [ref.pyramid(Y[f], LEVELS, ref.down_luma) for f in range(F)], painted
-
-
 @functools.lru_cache(maxsize=None)
 def _longest_chain(plane, half, k, d):
     """The longest anchored chain from key k in direction d; a shorter chain is its beginning."""

@@ -15,15 +15,16 @@ from lanpaint_amd import (_cabi, propagate_anchored_visible, propagate_keys, pro
 from tests import propagate_anchored_visible_ref as avref
 from tests import propagate_keys_anchored_visible_ref as kavref
 from tests import propagate_ref as ref
+from tests.compare import _same_bits, _same_ints as _same
+from tests.device import DELAY_MS, DEV, _dev, _equal, _spin_cycles_per_ms
 from tests.helpers import record_launches
+from tests.inputs import (BATCH_PLANES, JOB_MASKS, KEYS_ANCHORED_CLIPS as CLIPS, MASKS, _job, _job_field, _keys_anchored_clip as _clip,
+                          _soft, _video)
+from tests.motion_checks import _offset_view
 from tests.poison import poisoned_empty
-from tests.test_gpu_motion_scratch import DELAY_MS, _spin_cycles_per_ms
-from tests.test_gpu_propagate import MASKS, _dev, _same, _same_bits, _soft, _video
-from tests.test_gpu_propagate_keys_anchored import BATCH_PLANES, CLIPS, JOB_MASKS, _clip, _equal, _job, _job_field, _offset_view
-from tests.test_propagate_keys_anchored_visible_host import assert_the_quality_lines, quality_case
+from tests.propagate_scenes import assert_the_keys_quality_lines as assert_the_quality_lines, keys_quality_case as quality_case
 
 pytestmark = pytest.mark.gpu
-DEV = torch.device("cuda", 0)
 LEVELS, SEARCH, SMOOTH, ANCHOR, OCCLUSION = 3, 2, 8, 2, 16
 STEP = ["lp_prop_match_batch", "lp_prop_fill_batch"] * LEVELS + ["lp_prop_advance_batch", "lp_prop_match_batch", "lp_prop_fill_batch",
                                                                   "lp_prop_advance_batch", "lp_prop_visible_batch", "lp_prop_occlude_batch"]

@@ -15,12 +15,14 @@ from tests import propagate_keys_ref as kref
 from tests import propagate_keys_visible_ref as kvref
 from tests import propagate_ref as ref
 from tests import propagate_visible_ref as vref
+from tests.compare import _same_bits, _same_ints as _same
+from tests.device import DEV, _dev
 from tests.helpers import record_launches
-from tests.test_gpu_propagate_visible import MASKS, _dev, _flags, _lumas, _occluded_video, _positions, _rng, _same, _same_bits
-from tests.test_propagate_visible_host import occluded_disc_clip
+from tests.inputs import VISIBLE_MASKS as MASKS, _counts, _merge_want, _occlude_job, _occluded_video, _rng, _visible_job
+from tests.motion_checks import _merge_inputs
+from tests.propagate_scenes import occluded_disc_clip
 
 pytestmark = pytest.mark.gpu
-DEV = torch.device("cuda", 0)
 # under, at and over the block (8) and the window (16), several 32 x 32 tiles, and widths that are a multiple of 4 (the vector path)
 PLANES = [(1, 1), (1, 7), (8, 8), (9, 15), (16, 17), (23, 33), (40, 70), (33, 64), (70, 132)]
 LEVELS, SEARCH, SMOOTH = 3, 2, 8
@@ -36,15 +38,6 @@ def _shifted(a):
 
 
 # ---- the two batch entries -------------------------------------------------------------------------------------------------------------
-def _visible_job(H, W, job):
-    """Inputs of one job, different for every job: the positions' and the lumas' kinds and the mask's form cycle, and the planes
-    are rolled by the job's number."""
-    P = np.roll(_positions(("key", "smooth", "outside")[job % 3], H, W), job, axis=1)
-    Yt, Yk = _lumas(("noisy", "dark")[job % 2], H, W)
-    m = list(MASKS.values())[(job + 1) % len(MASKS)](H, W)
-    return P, np.roll(Yt, job, axis=0), Yk, np.roll(m, -job, axis=1)
-
-
 @pytest.mark.parametrize("jobs", [1, 2, 32])
 def test_visible_batch_equals_the_restatement_per_job(jobs):
     for H, W in PLANES:
@@ -55,13 +48,6 @@ def test_visible_batch_equals_the_restatement_per_job(jobs):
             for j, (P, Yt, Yk, m) in enumerate(made):
                 assert got[j].dtype == torch.int32 and tuple(got[j].shape) == ref.grid_of(H, W)
                 _same(got[j].cpu().numpy(), vref.visible_flags(Yt, Yk, P, m, occlusion), ("flags", (H, W), jobs, j, occlusion))
-
-
-def _occlude_job(H, W, job):
-    flags = np.roll(_flags(("random", "checkerboard", "none", "all")[job % 4], *ref.grid_of(H, W)), job, axis=1)
-    c = _rng(H, W, 12, job).integers(0, 257, (H, W))
-    c[_rng(H, W, 13, job).random((H, W)) < 0.3] = 256
-    return c, flags
 
 
 @pytest.mark.parametrize("jobs", [1, 2, 32])
@@ -126,47 +112,6 @@ def test_jobs_outside_1_to_32_are_invalid():
 
 
 # ---- the merge ---------------------------------------------------------------------------------------------------------------------------
-def _counts(kind, span):
-    """(N_A, N_B) by step.  The forward chain is at step j on frame j of the gap, the backward chain at step span - j."""
-    a, b = [200] * span, [300] * span
-    mid = (span + 1) // 2
-    if kind == "a_lost":
-        a[mid] = 15                                                    # lost from the middle frame on, sticky: later counts are high again
-    if kind == "b_lost":
-        b[mid] = 0                                                     # lost from its step `mid` on: the frames up to span - mid
-    if kind == "both_lost":                                            # either from its first step on: both on every frame
-        a[1], b[1] = 15, 0
-    if kind == "small_key":                                            # a key below 16 bits is never lost, whatever follows
-        a = [15] + [0] * (span - 1)
-        b = [16] + [16] * (span - 1)
-    return a, b
-
-
-def _merge_inputs(H, W, span, flag_kind):
-    n = span - 1
-    gh, gw = ref.grid_of(H, W)
-    rng = _rng(H, W, span, 31)
-    q = rng.integers(-12, 13, (2, n, H, W))
-    far = rng.random((2, n, H, W))
-    q = np.where(far < 0.2, rng.integers(-5000, 5001, (2, n, H, W)), q)
-    q = np.where(far > 0.95, np.where(q < 0, -_cabi.LP_STAB_Q_FAR, _cabi.LP_STAB_Q_FAR), q)
-    c = rng.integers(0, 257, (2, n, H, W))
-    c[rng.random((2, n, H, W)) < 0.3] = 256
-    if flag_kind == "random":
-        f = rng.integers(0, 2, (2, n, gh, gw))
-    else:                                                              # the forward chain's as named, the backward chain's the opposite
-        f = np.stack([np.stack([_flags(flag_kind, gh, gw)] * n), np.stack([1 - _flags(flag_kind, gh, gw)] * n)])
-    g = rng.integers(0, 2, (2, n, gh, gw))                             # any visible part c' <= c will do for the chains' own masks
-    cv = np.stack([np.stack([vref.occlude(c[x, i], g[x, i]) for i in range(n)]) for x in range(2)])
-    return q, c, cv, f
-
-
-def _merge_want(q, c, cv, f, na, nb, span):
-    out = [kvref.merge_frame(q[0, i], q[1, i], (c[0, i], cv[0, i], f[0, i]), (c[1, i], cv[1, i], f[1, i]), kvref.lost_at(na, i + 1),
-                             kvref.lost_at(nb, span - i - 1), span, i + 1) for i in range(span - 1)]
-    return np.stack([o[0] for o in out]), np.stack([o[1] for o in out])
-
-
 @pytest.mark.parametrize("plane", [(1, 1), (9, 15), (23, 33), (70, 132)], ids=lambda s: "x".join(map(str, s)))
 @pytest.mark.parametrize("span", [2, 3, 7])
 def test_merge_visible_equals_the_restatement(plane, span):

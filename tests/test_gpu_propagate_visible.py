@@ -11,80 +11,16 @@ import torch
 from lanpaint_amd import _cabi, propagate, propagate_visible, propagate_visible_nodes
 from tests import propagate_ref as ref
 from tests import propagate_visible_ref as vref
+from tests.compare import _same_bits, _same_ints as _same
+from tests.device import DEV, _dev
 from tests.helpers import record_launches
+from tests.inputs import (VISIBLE_MASKS as MASKS, VISIBLE_PLANES as PLANES, _border_disc as _disc, _flags, _occluded_video, _positions,
+                          _rng, _visible_lumas as _lumas)
 
 pytestmark = pytest.mark.gpu
-DEV = torch.device("cuda", 0)
-# one under, at and over the block (8) and the window (16), and several workgroups (32 x 32 tiles); the last two have a width that
-# is a multiple of 4, where the kernels read and write four pixels as one vector
-PLANES = [(1, 1), (1, 7), (7, 1), (8, 8), (9, 15), (16, 17), (23, 33), (40, 70), (70, 130), (33, 64), (70, 132)]
-
-
-def _rng(*key):
-    return np.random.default_rng([abs(int(k)) for k in key])
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
-
-
-def _dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
-
-
-def _same(got, want, what):
-    got, want = np.asarray(got), np.asarray(want)
-    assert got.shape == want.shape, (what, got.shape, want.shape)
-    bad = got.astype(np.int64) != want.astype(np.int64)
-    assert not bad.any(), (what, int(bad.sum()), np.argwhere(bad)[:4].tolist())
-
-
-def _same_bits(got, want, what):
-    assert got.dtype == np.float32 and got.shape == want.shape, what
-    bad = _bits(got) != _bits(want)
-    assert not bad.any(), (what, int(bad.sum()), np.argwhere(bad)[:4].tolist())
 
 
 # ---- inputs of the two launches -----------------------------------------------------------------------------------------------------------
-def _positions(kind, H, W):
-    """int64 [H, W, 2] in 1/16 px: the key map; the key map bent by a smooth field plus jitter; a map that leaves the plane."""
-    P = ref.key_positions(H, W)
-    if kind == "key":
-        return P
-    yy, xx = np.mgrid[:H, :W]
-    if kind == "smooth":
-        bend = np.stack([40 * np.sin(xx / 9.0) + 25 * np.cos(yy / 5.0), 55 * np.cos(xx / 7.0 + yy / 11.0)], axis=-1)
-        return P + np.round(bend).astype(np.int64) + _rng(H, W, 7).integers(-8, 9, (H, W, 2))
-    return (3 * P) // 2 - 16 * 5 + _rng(H, W, 8).integers(-300, 301, (H, W, 2))
-
-
-def _lumas(kind, H, W):
-    """(Yt, Yk) uint8.  noisy: the key's plane plus noise whose amplitude grows from 0 to 60 grey levels from left to right, so the
-    residual crosses every threshold somewhere; dark: t darker than the key by 20 on the left to 60 on the right, so D is strongly
-    negative, the floor of a negative mean is taken and mu runs into its clamp at -32."""
-    rng = _rng(H, W, 9)
-    xx = np.broadcast_to(np.arange(W)[None, :] / max(W - 1, 1), (H, W))
-    if kind == "noisy":
-        Yk = rng.integers(0, 256, (H, W))
-        Yt = Yk + np.round(rng.normal(0, 1, (H, W)) * 60 * xx)
-    else:
-        Yk = 190 + rng.integers(0, 60, (H, W))
-        Yt = Yk - np.round(20 + 40 * xx) - rng.integers(0, 3, (H, W))
-    return np.clip(Yt, 0, 255).astype(np.uint8), Yk.astype(np.uint8)
-
-
-def _disc(H, W):
-    """A disc that touches the border."""
-    yy, xx = np.mgrid[:H, :W]
-    r = max(min(H, W) / 3, 1)
-    return ((yy - r + 1) ** 2 + (xx - W + r) ** 2 <= r * r).astype(np.uint8)
-
-
-MASKS = {"empty": lambda H, W: np.zeros((H, W), np.uint8), "full": lambda H, W: np.ones((H, W), np.uint8), "disc": _disc,
-         # about 14 mask pixels per 16 x 16 window: some windows under LP_PROP_MIN_PIXELS, some at it, some over
-         "sparse": lambda H, W: (_rng(H, W, 10).random((H, W)) < 0.055).astype(np.uint8)}
-
-
 @pytest.mark.parametrize("positions", ["key", "smooth", "outside"])
 @pytest.mark.parametrize("lumas", ["noisy", "dark"])
 def test_visible_flags_equal_the_restatement(positions, lumas):
@@ -125,12 +61,6 @@ def test_visible_flags_on_unaligned_planes_take_the_scalar_path_with_the_same_bi
     _same_bits(hidden.cpu().numpy(), (c - cv).astype(np.float32) / np.float32(256), "unaligned hidden")
 
 
-def _flags(kind, gh, gw):
-    yy, xx = np.mgrid[:gh, :gw]
-    return {"none": np.zeros((gh, gw), np.int64), "all": np.ones((gh, gw), np.int64), "checkerboard": (yy + xx) % 2,
-            "random": _rng(gh, gw, 11).integers(0, 2, (gh, gw))}[kind]
-
-
 @pytest.mark.parametrize("kind", ["none", "all", "checkerboard", "random"])
 def test_occlude_equals_the_restatement(kind):
     for H, W in PLANES:
@@ -150,21 +80,6 @@ def test_occlude_equals_the_restatement(kind):
 
 
 # ---- the whole chain ------------------------------------------------------------------------------------------------------------------
-@functools.lru_cache(maxsize=None)
-def _occluded_video(F, H, W):
-    """Frames cut out of one random canvas, moving by (2, -3) pixels per frame, a little noise of their own, and a static bar of
-    another texture over the middle fifth of the width: (images fp32 [F, H, W, 3], a centred disc as the key mask)."""
-    rng = _rng(F, H, W, 14)
-    canvas = rng.random((H + 2 * F, W + 3 * F, 3), dtype=np.float32)
-    frames = np.stack([canvas[2 * t:2 * t + H, 3 * (F - 1 - t):3 * (F - 1 - t) + W] for t in range(F)])
-    frames = frames + rng.normal(0, 0.02, frames.shape)
-    x0, x1 = 2 * W // 5, 3 * W // 5
-    frames[:, :, x0:x1] = rng.random((H, x1 - x0, 3), dtype=np.float32)
-    yy, xx = np.mgrid[:H, :W]
-    mask = ((yy - H / 2) ** 2 + (xx - W / 2) ** 2 <= (min(H, W) / 2.5) ** 2).astype(np.float32)
-    return frames.astype(np.float32), mask
-
-
 @functools.lru_cache(maxsize=None)
 def _want(F, H, W, key, occlusion):
     images, mask = _occluded_video(F, H, W)

@@ -11,9 +11,11 @@ import torch
 from lanpaint_amd import _cabi, refine, refine_nodes, videomask
 from lanpaint_amd._util import raw_stream
 from tests import refine_ref as ref
+from tests.compare import _raw_bits as _bits
+from tests.device import DEV
+from tests.image_inputs import _guide, _refine_blobs as _blobs, _rng, _soft
 
 pytestmark = pytest.mark.gpu
-DEV = torch.device("cuda", 0)
 # (H, W, C, B, mask_batch, r): degenerate axes, windows wider than the image, several tiles and chunks, a grey guide, a fourth
 # channel that is not read, the largest radius; then one under, at and one over the tile sides (32 wide, 32 tall in the first
 # launch, 64 tall in the second) and the 16-row chunk
@@ -22,31 +24,6 @@ SHAPES = [(1, 1, 3, 1, 1, 1), (1, 7, 3, 1, 1, 64), (7, 1, 1, 2, 1, 3), (5, 9, 4,
           (31, 33, 3, 1, 1, 2), (32, 32, 3, 2, 2, 3), (33, 31, 1, 1, 1, 4), (63, 32, 3, 1, 1, 2), (64, 31, 3, 1, 1, 9),
           (65, 33, 3, 1, 1, 7), (15, 17, 3, 1, 1, 1), (16, 16, 3, 1, 1, 8), (17, 15, 3, 1, 1, 24)]
 EPS = (1e-6, 1e-3, 1.0)
-
-
-def _rng(*key):
-    return np.random.default_rng(list(key))
-
-
-def _guide(B, H, W, C, seed=0):
-    """Two flat regions with noise, so that windows see an edge; values run a little outside [0, 1]."""
-    rng = _rng(B, H, W, C, seed)
-    yy, xx = np.mgrid[:H, :W]
-    side = ((xx - W / 2) + 0.4 * (yy - H / 2) < 0)[None, :, :, None]
-    base = np.where(side, rng.random((B, 1, 1, C)), rng.random((B, 1, 1, C)))
-    return (base + rng.normal(0, 0.08, (B, H, W, C))).astype(np.float32)
-
-
-def _soft(Bm, H, W, seed=1):
-    return _rng(Bm, H, W, seed).random((Bm, H, W), dtype=np.float32)
-
-
-def _blobs(Bm, H, W, seed=2):
-    yy, xx = np.mgrid[:H, :W]
-    m = ((xx - W / 2 + 3 * np.sin(yy / 3.0)) + 0.4 * (yy - H / 2) < 2).astype(np.float32)
-    m = np.repeat(m[None], Bm, axis=0)
-    m[:, H // 3:H // 3 + 3, W // 4:W // 4 + 5] = 1.0 - m[:, H // 3:H // 3 + 3, W // 4:W // 4 + 5]
-    return m
 
 
 def _single(Bm, H, W):
@@ -77,10 +54,6 @@ def _wild(Bm, H, W, seed=4):
 
 FORMS = {"soft": _soft, "blobs": _blobs, "all 0": lambda *s: np.zeros(s, np.float32), "all 1": lambda *s: np.ones(s, np.float32),
          "single": _single, "boundaries": _boundaries, "wild": _wild}
-
-
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
 
 
 def _refine(guide, mask, r, eps, **kw):

@@ -13,22 +13,16 @@ from lanpaint_amd import propagate, stabilize, temporal_fill, temporal_fill_chec
 from lanpaint_amd import temporal_fill_nodes
 from tests import shot_clips as clips
 from tests import shots_ref as sref
-from tests.test_gpu_propagate import _dev, _rng, _same, _video, _wild_video
-from tests.test_gpu_temporal_fill import _same_values, plane_ids
-from tests.test_shots_host import FILL_LEVELS, expected_shot, fill_case, foreign_sources, scores
+from tests.compare import _same_ints as _same, _same_values
+from tests.device import _dev
+from tests.inputs import _random_scores, _rng, _video, _wild_video, plane_ids
+from tests.motion_checks import _check_scores
+from tests.shot_clips import FILL_LEVELS, expected_shot, fill_case, foreign_sources, scores
 
 pytestmark = pytest.mark.gpu
 F = 5
 PLANES = [(9, 15), (23, 33), (40, 70), (70, 130)]      # one block and a cut one; odd sizes; more than one tile; a 3 x 5 grid of tiles
 SMALL = [(1, 1), (5, 6), (3, 40), (8, 8)]              # smaller than one block, or one block wide
-
-
-def _check_scores(images, level, search, what):
-    score, n = shots.shot_scores(_dev(images), level, search)
-    want, want_n = sref.shot_scores(images, level, search)
-    assert n == want_n and score.is_cuda and score.dtype == torch.int64 and score.is_contiguous() and tuple(score.shape) == want.shape
-    _same(score.cpu().numpy(), want, what)
-    return want
 
 
 # ---- shot_scores ----------------------------------------------------------------------------------------------------------------------------
@@ -79,18 +73,6 @@ def test_the_histograms_of_a_chunk():
 
 
 # ---- shot_decide ----------------------------------------------------------------------------------------------------------------------------
-def _random_scores(frames, n, seed):
-    """Heavy-tailed residuals with runs of equal values, so that some pair stands out of every window and equal neighbours occur."""
-    rng = _rng(frames, seed, 9)
-    A = rng.integers(1, 255, frames - 1) ** 2 * n // 256
-    B = rng.integers(0, 2 * n + 1, frames - 1)
-    run = rng.random(frames - 1) < 0.3
-    for t in range(1, frames - 1):
-        if run[t]:
-            A[t] = A[t - 1]
-    return np.stack([A, B], axis=1).astype(np.int64)
-
-
 @pytest.mark.parametrize("frames", [2, 3, 255, 256, 257, 1025, 65535])
 def test_decide_equals_the_restatement(frames):
     found = 0

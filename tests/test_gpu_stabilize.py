@@ -12,9 +12,12 @@ import torch
 from lanpaint_amd import _cabi, stabilize, stabilize_nodes, videomask
 from lanpaint_amd._util import raw_stream
 from tests import stabilize_ref as ref
+from tests.compare import _raw_bits as _bits, _same_raw_bits as _same
+from tests.device import DEV
+from tests.image_checks import _check_q, _device_q
+from tests.image_inputs import FORMS, _rng, _stabilize_blobs as _blobs, _stabilize_soft as _soft
 
 pytestmark = pytest.mark.gpu
-DEV = torch.device("cuda", 0)
 SEG = _cabi.LP_STAB_SEG_FRAMES                                         # 16: the shortest time segment
 MEDIANS, SMOOTHS = (0, 1, 2, 3), (0, 1, 2, 8)                          # the four instantiations: Tm <= 1 or not, Ts <= 2 or not
 FEATHERS, GROWS = (0.0, 0.5, 3.0, 64.0), (0.0, 0.5, -0.5, 7.25, -7.25)
@@ -26,83 +29,6 @@ FRAMES = tuple(range(1, 25)) + (2 * SEG - 1, 2 * SEG, 2 * SEG + 1, 3 * SEG + 5)
 SHAPES = [(5, 1, 1), (6, 1, 7), (7, 7, 1), (4, 5, 9), (3, 2, 31), (3, 1, 32), (3, 3, 33), (3, 1, 63), (3, 1, 65), (3, 1, 255),
           (18, 16, 16), (3, 1, 257), (17, 3, 171), (40, 70, 130)]
 ONE = np.float32(1.0).view(np.uint32)
-
-
-def _rng(*key):
-    return np.random.default_rng(list(key))
-
-
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
-def _soft(F, H, W, seed=1):
-    return _rng(F, H, W, seed).random((F, H, W), dtype=np.float32)
-
-
-def _blobs(F, H, W, seed=2):
-    """A disc that drifts and jitters, an empty frame and a stray blob in it."""
-    rng = _rng(F, H, W, seed)
-    yy, xx = np.mgrid[:H, :W]
-    m = np.zeros((F, H, W), dtype=np.float32)
-    for t in range(F):
-        cy, cx = H / 2 + rng.normal(0, 1), W / 3 + 0.7 * t + rng.normal(0, 1)
-        m[t] = (yy - cy) ** 2 + (xx - cx) ** 2 <= (min(H, W) / 3 + rng.normal(0, 1)) ** 2
-    m[F // 3] = 0.0
-    m[F // 2, :2, -3:] = 1.0
-    return m
-
-
-def _alternating(F, H, W):
-    m = np.zeros((F, H, W), dtype=np.float32)
-    m[1::2] = 1.0
-    return m
-
-
-def _single(F, H, W):
-    m = np.zeros((F, H, W), dtype=np.float32)
-    m[F // 2, H // 2, W // 3] = 1.0
-    return m
-
-
-def _threshold(F, H, W, seed=3):
-    """0.5 and its float neighbours."""
-    v = np.float32(0.5)
-    return _rng(F, H, W, seed).choice(np.array([np.nextafter(v, np.float32(0)), v, np.nextafter(v, np.float32(1))]), (F, H, W))
-
-
-def _wild(F, H, W, seed=4):
-    """NaN, infinities and values outside [0, 1]."""
-    rng = _rng(F, H, W, seed)
-    m = (3.0 * rng.random((F, H, W)) - 1.0).astype(np.float32)
-    pick = rng.random((F, H, W))
-    m[pick < 0.15] = np.nan
-    m[(pick >= 0.15) & (pick < 0.2)] = np.inf
-    m[(pick >= 0.2) & (pick < 0.25)] = -np.inf
-    return m
-
-
-FORMS = {"soft": _soft, "blobs": _blobs, "all 0": lambda *s: np.zeros(s, np.float32), "all 1": lambda *s: np.ones(s, np.float32),
-         "alternating": _alternating, "single": _single, "threshold": _threshold, "wild": _wild}
-
-
-def _device_q(mask):
-    return stabilize.signed_d2(torch.from_numpy(mask).to(DEV))
-
-
-def _same(got, want, what):
-    assert got.dtype == np.float32 and got.shape == want.shape, what
-    bad = _bits(got) != _bits(want)
-    assert not bad.any(), (what, int(bad.sum()), np.argwhere(bad)[:4].tolist())
-
-
-def _check_q(q_dev, q_ref, cases, what):
-    """Every (median, smooth, grow, feather) of `cases` on the device's q against the restatement on its own q; the device's
-    results come back in one copy."""
-    got = torch.stack([stabilize.stabilize_q(q_dev, *c) for c in cases]).cpu().numpy()
-    for g, c in zip(got, cases):
-        _same(g, ref.stabilize_q_ref(q_ref, *c), (what, c))
-    return got
 
 
 def _random_q(F, H, W, seed=5):

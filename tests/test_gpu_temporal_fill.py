@@ -9,30 +9,18 @@ import numpy as np
 import pytest
 import torch
 
-from lanpaint_amd import _cabi, propagate, temporal_fill as tf, temporal_fill_nodes
+from lanpaint_amd import _cabi, temporal_fill as tf, temporal_fill_nodes
 from tests import propagate_ref as ref
 from tests import temporal_fill_ref as tref
-from tests.test_gpu_propagate import (BIG, PLANES, _bits, _dev, _levels_of, _rng, _same, _soft, _threshold, _video, _wild_mask,
-                                      _wild_video)
-from tests.test_temporal_fill_host import check_fixed, check_pan, check_still, pan_clip, still_clip
+from tests.compare import _f32_bits as _bits, _same_ints as _same, _same_values
+from tests.device import _dev, _levels_of
+from tests.inputs import (ALL_PLANES, FILL_FRAMES as F, FILL_LEVELS as LEVELS, THIN_PLANES, _carry_case, _random_masks, _soft, _threshold,
+                          _video, _wild_mask, _wild_video, plane_ids)
+from tests.motion_checks import _check_batched_fields, _check_carry, _check_fill_whole as _check_whole
+from tests.temporal_clips import (check_fill_fixed as check_fixed, check_fill_pan as check_pan, check_fill_still as check_still,
+                                  fill_pan_clip as pan_clip, fill_still_clip as still_clip)
 
 pytestmark = pytest.mark.gpu
-F, LEVELS = 5, 3
-ALL_PLANES = PLANES + [BIG]
-plane_ids = lambda s: "x".join(map(str, s))                          # noqa: E731
-
-
-def _same_values(got, want, what):
-    """fp32: NaN where the restatement has NaN, else the same bits."""
-    got, want = np.asarray(got), np.asarray(want)
-    assert got.dtype == np.float32 and got.shape == want.shape, (what, got.dtype, got.shape, want.shape)
-    nan = np.isnan(want)
-    bad = (np.isnan(got) != nan) | (~nan & (_bits(got) != _bits(want)))
-    assert not bad.any(), (what, int(bad.sum()), np.argwhere(bad)[:4].tolist())
-
-
-def _random_masks(frames, H, W, seed=0, share=0.3):
-    return (_rng(frames, H, W, seed, 5).random((frames, H, W)) < share).astype(np.float32)
 
 
 MASKS = {"empty": lambda n, H, W: np.zeros((n, H, W), np.float32), "full": lambda n, H, W: np.ones((n, H, W), np.float32),
@@ -70,71 +58,10 @@ def test_known_pyramids_equal_the_restatement(form):
 
 # ---- stage 2: the fields -------------------------------------------------------------------------------------------------------------------
 def test_batched_fields_equal_the_single_entries_and_the_restatement():
-    frames, H, W = 18, 23, 33
-    images, mask = _video(frames, H, W), _random_masks(frames, H, W)
-    luma = propagate.luma_pyramids(_dev(images), LEVELS)
-    known = tf.known_pyramids(_dev(mask), frames, LEVELS)
-    steps = [(t, t - 1) for t in range(1, frames)] + [(t, t + 1) for t in range(frames - 2, -1, -1)]
-    assert len(steps) == 34 and len(steps) % tf.MAX_JOBS == 2            # two launches per level, a remainder of 2
-    got = tf.step_fields(luma, known, steps, H, W, LEVELS, 2, 8)
-    assert got.dtype == torch.int32 and tuple(got.shape) == (34, *_cabi.prop_grid(H, W), 2)
-    Y = ref.luma(images)
-    pyr = [ref.pyramid(Y[f], LEVELS, ref.down_luma) for f in range(frames)]
-    kpyr = tref.known_pyramids(tref.known_bits(mask, frames), LEVELS)
-    host = got.cpu().numpy()
-    for j, (t, s) in enumerate(steps):
-        parent = None
-        for lv in range(LEVELS - 1, -1, -1):
-            vec, ok = propagate.match_level(luma[t], luma[s], known[t], H, W, LEVELS, lv, 2, 8, parent)
-            parent = propagate.fill_median(vec, ok)
-        assert torch.equal(got[j], parent), ("the single entries", j, t, s)
-        _same(host[j], tref.step_field(pyr[t], pyr[s], kpyr[t], 2, 8), ("the restatement", j, t, s))
+    _check_batched_fields()
 
 
 # ---- stages 3 and 4: one carry, fed with the restatement's inputs ---------------------------------------------------------------------------
-@functools.lru_cache(maxsize=None)
-def _carry_case(H, W, wild, channels=3):
-    """A frame 2 of 5 with random known bits, a random field of up to 2.5 pixels, a random state of both neighbours with origins
-    in every frame, and a random `source` under the mask from an earlier pass."""
-    rng = _rng(H, W, int(wild), 6)
-    images = (_wild_video if wild else _video)(F, H, W, channels)
-    gh, gw = ref.grid_of(H, W)
-    vec = rng.integers(-40, 41, (gh, gw, 2)).astype(np.int32)
-    known = (rng.random((3, H, W)) < 0.5).astype(np.uint8)            # of the frames 1, 2, 3
-    org = rng.integers(-1, F, (H, W)).astype(np.int32)
-    pos = np.stack([rng.integers(-40, 16 * H + 40, (H, W)), rng.integers(-40, 16 * W + 40, (H, W))], axis=-1).astype(np.int32)
-    source = np.where(known[1] != 0, 2, rng.choice([-1, 0, 1, 3, 4], (H, W))).astype(np.int32)
-    return images, vec, known, org, pos, source
-
-
-def _check_carry(H, W, wild, donor, state, reach, nearer, channels=3):
-    t = 2
-    images, vec, known, org, pos, source_t = _carry_case(H, W, wild, channels)
-    known_t, known_s = known[1], known[donor - 1]
-    want_org, want_pos = tref.carry(t, known_t, donor, known_s, vec, (org, pos) if state else None, reach)
-    write = tref.choose(t, known_t, want_org, source_t, nearer)
-    source = np.full((F, H, W), -7, np.int32)
-    source[t] = source_t
-    remaining = np.full((F, H, W), 0.25, np.float32)
-    remaining[t] = (known_t == 0) & (source_t == -1)
-    filled = images.copy()
-    want_filled, want_source, want_remaining = filled.copy(), source.copy(), remaining.copy()
-    want_filled[t][write] = tref.sample(images, want_org[write], want_pos[write][:, 0], want_pos[write][:, 1])
-    want_source[t][write] = want_org[write]
-    want_remaining[t][write] = 0
-    d_filled, d_source, d_remaining = _dev(filled), _dev(source), _dev(remaining)
-    got_org, got_pos = tf.carry(_dev(vec), _dev(known_t), _dev(known_s), (_dev(org), _dev(pos)) if state else None, _dev(images),
-                                d_filled, d_source, d_remaining, t, donor, reach, nearer)
-    what = ((H, W), wild, donor, state, reach, nearer, channels)
-    under = known_t == 0                                               # the state planes matter under the mask only
-    _same(got_org.cpu().numpy()[under], want_org[under], (what, "org"))
-    _same(got_pos.cpu().numpy()[under], want_pos[under], (what, "pos"))
-    _same_values(d_filled.cpu().numpy(), want_filled, (what, "filled"))
-    _same(d_source.cpu().numpy(), want_source, (what, "source"))
-    _same_values(d_remaining.cpu().numpy(), want_remaining, (what, "remaining"))
-    return want_org, write
-
-
 @pytest.mark.parametrize("plane", ALL_PLANES, ids=plane_ids)
 def test_carry_equals_the_restatement(plane):
     H, W = plane
@@ -144,12 +71,6 @@ def test_carry_equals_the_restatement(plane):
                 _check_carry(H, W, False, donor, state, reach, nearer)
     _check_carry(H, W, True, 1, True, 0, False)
     _check_carry(H, W, True, 3, True, 2, True)
-
-
-# One block high with several across, and the other way round: the grid is one block wide, so both blocks a pixel interpolates
-# between are the same clamped one.  The plane list's own thin planes (1 x 1, 1 x 7, 7 x 1) are thinner than the case's vectors are
-# long: there every masked pixel's vector leaves the plane and its value is never seen (counted on the restatement alone).
-THIN_PLANES = [(7, 33), (33, 5)]
 
 
 @pytest.mark.parametrize("plane", THIN_PLANES, ids=plane_ids)
@@ -182,14 +103,6 @@ def _reference(H, W, frames=F, channels=3, wild=False, levels=LEVELS, reach=0):
     images = (_wild_video if wild else _video)(frames, H, W, channels)
     mask = np.stack([_wild_mask(H, W, f) for f in range(frames)]) if wild else _random_masks(frames, H, W)
     return images, mask, tref.temporal_fill_ref(images, mask, levels, 2, 8, reach)
-
-
-def _check_whole(got, want, what):
-    for g, dtype in zip(got, (torch.float32, torch.float32, torch.int32)):
-        assert g.is_cuda and g.dtype == dtype and g.is_contiguous()
-    _same_values(got[0].cpu().numpy(), want[0], (what, "filled"))
-    _same_values(got[1].cpu().numpy(), want[1], (what, "remaining"))
-    _same(got[2].cpu().numpy(), want[2], (what, "source"))
 
 
 @pytest.mark.parametrize("plane", ALL_PLANES, ids=plane_ids)

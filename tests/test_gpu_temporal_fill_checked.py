@@ -11,39 +11,18 @@ import torch
 
 from lanpaint_amd import _cabi, temporal_fill as tf, temporal_fill_checked as tc, temporal_fill_checked_nodes
 from tests import temporal_fill_checked_ref as cref
-from tests.test_gpu_propagate import _dev, _same, _video, _wild_mask, _wild_video
-from tests.test_gpu_temporal_fill import ALL_PLANES, LEVELS, THIN_PLANES, F, _random_masks, _same_values, plane_ids
-from tests.test_temporal_fill_checked_host import (CLEAN_CLIPS, SECOND_OBJECT, check_clean, check_invariant, clean_clip, pair_case,
-                                                   pair_want, random_clip, second_object_clip, second_object_counts)
+from tests.compare import _same_values
+from tests.device import _dev
+from tests.inputs import (ALL_PLANES, FILL_FRAMES as F, FILL_LEVELS as LEVELS, THIN_PLANES, _random_masks, _video, _wild_mask,
+                          _wild_video, plane_ids)
+from tests.motion_checks import _check_checked_whole as _check_whole, _check_pair
+from tests.temporal_clips import (CLEAN_CLIPS, SECOND_OBJECT, check_clean, check_invariant, clean_clip, pair_case, pair_want, random_clip,
+                                  second_object_clip, second_object_counts)
 
 pytestmark = pytest.mark.gpu
 
 
 # ---- the backward step, fed with the restatement's inputs -----------------------------------------------------------------------------
-def _check_pair(H, W, wild, C, state, reach, agree):
-    t = 2
-    case = pair_case(H, W, wild, C)
-    images, vec, known, org, pos, source_t, filled_t = case
-    (want_org, want_pos), want = pair_want(case, state, reach, agree)
-    filled, source = images.copy(), np.full((F, H, W), -7, np.int32)
-    remaining, witnesses = np.full((F, H, W), 0.25, np.float32), np.full((F, H, W), 77, np.int32)
-    filled[t], source[t], remaining[t] = filled_t, source_t, (known[0] == 0) & (source_t == -1)
-    wants = [filled.copy(), source.copy(), remaining.copy(), witnesses.copy()]
-    for plane, w in zip(wants, want):
-        plane[t] = w
-    d_filled, d_source, d_remaining, d_witnesses = _dev(filled), _dev(source), _dev(remaining), _dev(witnesses)
-    got_org, got_pos = tc.carry_pair(_dev(vec), _dev(known[0]), _dev(known[1]), (_dev(org), _dev(pos)) if state else None,
-                                     _dev(images), d_filled, d_source, d_remaining, d_witnesses, t, reach, agree)
-    what = ((H, W), wild, C, state, reach, agree)
-    under = known[0] == 0                                              # the state planes matter under the mask only
-    _same(got_org.cpu().numpy()[under], want_org[under], (what, "org"))
-    _same(got_pos.cpu().numpy()[under], want_pos[under], (what, "pos"))
-    _same_values(d_filled.cpu().numpy(), wants[0], (what, "filled"))
-    _same(d_source.cpu().numpy(), wants[1], (what, "source"))
-    _same_values(d_remaining.cpu().numpy(), wants[2], (what, "remaining"))
-    _same(d_witnesses.cpu().numpy(), wants[3], (what, "witnesses"))
-
-
 @pytest.mark.parametrize("plane", ALL_PLANES, ids=plane_ids)
 def test_carry_pair_equals_the_restatement(plane):
     H, W = plane
@@ -86,15 +65,6 @@ def _reference(H, W, frames=F, wild=False, one_mask=False, reach=0, agree=8):
     mask = np.stack([_wild_mask(H, W, f) for f in range(frames)]) if wild else _random_masks(frames, H, W)
     mask = mask[0] if one_mask else mask
     return images, mask, cref.temporal_fill_checked_ref(images, mask, LEVELS, 2, 8, reach, agree)
-
-
-def _check_whole(got, want, what):
-    for g, dtype in zip(got, (torch.float32, torch.float32, torch.int32, torch.int32)):
-        assert g.is_cuda and g.dtype == dtype and g.is_contiguous()
-    _same_values(got[0].cpu().numpy(), want[0], (what, "filled"))
-    _same_values(got[1].cpu().numpy(), want[1], (what, "remaining"))
-    _same(got[2].cpu().numpy(), want[2], (what, "source"))
-    _same(got[3].cpu().numpy(), want[3], (what, "witnesses"))
 
 
 @pytest.mark.parametrize("plane", ALL_PLANES, ids=plane_ids)
@@ -185,7 +155,7 @@ def test_clean_geometry_is_never_disputed(name, noisy):
 
 
 def test_the_pan_clip_is_filled_with_the_true_background_and_verified():
-    from tests.test_temporal_fill_host import check_pan
+    from tests.temporal_clips import check_fill_pan as check_pan
     plain, checked = _both(*clean_clip("pan", False))
     check_clean(plain, checked)
     check_pan(*checked[:3])

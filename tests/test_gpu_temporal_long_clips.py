@@ -16,12 +16,15 @@ from lanpaint_amd._hostcall import chunks
 from tests import temporal_fill_checked_ref as cref
 from tests import temporal_fill_ref as tref
 from tests import temporal_smooth_ref as sref
-from tests.test_gpu_propagate import _bits, _dev, _video
-from tests.test_gpu_temporal_fill import _carry_case, _check_carry, _check_whole, _random_masks
-from tests.test_gpu_temporal_fill_checked import _check_pair, _check_whole as _check_whole_checked
-from tests.test_gpu_temporal_smooth import _check as _check_smooth
-from tests.test_temporal_long_clips_host import (FRAMES, LEVELS, PLANE, SEARCH, SMOOTH, SMOOTH_FRAMES, checked_clip, checked_want,
-                                                 fill_clip, fill_want, smooth_clip, smooth_want)
+from tests.compare import _f32_bits as _bits
+from tests.device import _dev
+from tests.inputs import _carry_case, _random_masks, _video
+from tests.motion_checks import (_check_carry, _check_checked_whole as _check_whole_checked, _check_fill_whole as _check_whole,
+                                 _check_pair, _check_smooth)
+from tests.temporal_clips import (LONG_FRAMES as FRAMES, LONG_LEVELS as LEVELS, LONG_PLANE as PLANE, LONG_SEARCH as SEARCH,
+                                  LONG_SMOOTH as SMOOTH, LONG_SMOOTH_FRAMES as SMOOTH_FRAMES, long_checked_clip as checked_clip,
+                                  long_checked_want as checked_want, long_fill_clip as fill_clip, long_fill_want as fill_want,
+                                  long_smooth_clip as smooth_clip, long_smooth_want as smooth_want)
 
 pytestmark = pytest.mark.gpu
 PARAMS = (LEVELS, SEARCH, SMOOTH)

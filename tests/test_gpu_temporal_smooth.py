@@ -13,19 +13,15 @@ from lanpaint_amd import _cabi, temporal_smooth as ts, temporal_smooth_nodes
 from tests import propagate_ref as ref
 from tests import temporal_fill_ref as tref
 from tests import temporal_smooth_ref as sref
-from tests.test_gpu_propagate import _dev, _rng, _same, _video, _wild_video
-from tests.test_gpu_temporal_fill import ALL_PLANES, THIN_PLANES, _random_masks, _same_values, plane_ids
-from tests.test_temporal_smooth_host import (RADII, check_ghost, check_noise, check_pan, ghost_clip, noise_clip, pan_clip)
+from tests.compare import _same_ints as _same, _same_values
+from tests.device import _dev
+from tests.inputs import ALL_PLANES, THIN_PLANES, _random_masks, _rng, _video, _wild_video, plane_ids
+from tests.motion_checks import _check_smooth as _check
+from tests.temporal_clips import (RADII, check_smooth_ghost as check_ghost, check_smooth_noise as check_noise,
+                                  check_smooth_pan as check_pan, ghost_clip, noise_clip, smooth_pan_clip as pan_clip)
 
 pytestmark = pytest.mark.gpu
 F, LEVELS = 5, 3
-
-
-def _check(got, want, what):
-    out, support = got
-    assert out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and support.dtype == torch.int32 and support.is_contiguous()
-    _same(support.cpu().numpy(), want[1], (what, "support"))
-    _same_values(out.cpu().numpy(), want[0], (what, "out"))
 
 
 # ---- the launch alone ---------------------------------------------------------------------------------------------------------------------

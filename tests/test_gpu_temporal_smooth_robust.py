@@ -16,25 +16,16 @@ from tests import propagate_ref as ref
 from tests import temporal_fill_ref as tref
 from tests import temporal_smooth_ref as sref
 from tests import temporal_smooth_robust_ref as rref
-from tests.test_gpu_propagate import _dev, _rng, _same, _video, _wild_video
-from tests.test_gpu_temporal_fill import ALL_PLANES, THIN_PLANES, _random_masks, _same_values, plane_ids
-from tests.test_temporal_smooth_host import RADII, ghost_clip, noise_clip, pan_clip
-from tests.test_temporal_smooth_robust_host import (check_ghost_removed, check_noise, check_pan_equals_plain, check_pop, check_two_frame_pop,
-                                                    pop_clip)
+from tests.compare import _same_ints as _same, _same_values
+from tests.device import _dev
+from tests.inputs import ALL_PLANES, THIN_PLANES, _random_masks, _rng, _video, _wild_video, plane_ids
+from tests.motion_checks import _check_robust_smooth as _check
+from tests.temporal_clips import (RADII, check_ghost_removed, check_pan_equals_plain, check_pop, check_robust_noise as check_noise,
+                                  check_two_frame_pop, ghost_clip, noise_clip, pop_clip, smooth_pan_clip as pan_clip)
 
 pytestmark = pytest.mark.gpu
 F, LEVELS = 5, 3
 NAMES = ("out", "support", "replaced")
-
-
-def _check(got, want, what):
-    out, support, replaced = got
-    assert out.is_cuda and out.dtype == torch.float32 and out.is_contiguous()
-    for plane in (support, replaced):
-        assert plane.dtype == torch.int32 and plane.is_contiguous() and plane.shape == out.shape[:3]
-    _same(support.cpu().numpy(), want[1], (what, "support"))
-    _same(replaced.cpu().numpy(), want[2], (what, "replaced"))
-    _same_values(out.cpu().numpy(), want[0], (what, "out"))
 
 
 def _popped(images, seed, share=0.12):

@@ -25,7 +25,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 from tests.stubs import FlowSampling, VESampling      # noqa: E402
-from tests.test_gpu_port_on_device import PortOnDevice, _compare      # noqa: E402
+from tests.port_checks import PortOnDevice, _compare      # noqa: E402
 
 SHAPES = {"252_one_partial_block": ((1, 4, 9, 7), (1.0,)),
           "1088_partial_last_block": ((1, 4, 17, 16), (1.0,)),

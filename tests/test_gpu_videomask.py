@@ -10,53 +10,17 @@ import numpy as np
 import pytest
 import torch
 
-from lanpaint_amd import _cabi, videomask
+from lanpaint_amd import videomask
+from tests.device import DEV
+from tests.image_checks import _check_edt, _edt
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FIXTURES = sorted(glob.glob(os.path.join(ROOT, "tests", "golden", "videomask_*.npz")))
-DEV = torch.device("cuda", 0)
-NONE = _cabi.LP_VMASK_D2_NONE
 
 
 def _ids(p):
     return os.path.basename(p)[len("videomask_"):-4]
-
-
-def _brute_d2(fg):
-    """Squared distance to the nearest True pixel by brute force, -1 where there is none."""
-    h, w = fg.shape
-    ys, xs = np.nonzero(fg)
-    if len(ys) == 0:
-        return np.full((h, w), NONE, np.int64)
-    yy, xx = np.mgrid[:h, :w]
-    out = np.full((h, w), np.iinfo(np.int64).max, np.int64)
-    for c in range(0, len(ys), 256):
-        d = (yy[..., None] - ys[c:c + 256]) ** 2 + (xx[..., None] - xs[c:c + 256]) ** 2
-        out = np.minimum(out, d.min(-1))
-    return out
-
-
-def _edt(masks):
-    keys = torch.from_numpy(np.ascontiguousarray(np.stack(masks)).astype(np.float32)).to(DEV)
-    d2, sdf, csum = videomask.keyframe_edt(keys)
-    torch.cuda.synchronize()
-    return d2.cpu().numpy(), sdf.cpu().numpy(), csum.cpu().numpy()
-
-
-def _check_edt(masks):
-    d2, sdf, csum = _edt(masks)
-    for k, m in enumerate(masks):
-        fg = np.asarray(m) >= 0.5
-        assert np.array_equal(d2[k, 0], _brute_d2(fg)), k
-        assert np.array_equal(d2[k, 1], _brute_d2(~fg)), k
-        ys, xs = np.nonzero(fg)
-        assert csum[k].tolist() == [len(ys), int(ys.sum()), int(xs.sum())]
-        h, w = fg.shape
-        if not fg.any() or fg.all():
-            assert (sdf[k] == (max(h, w) / 2.0) * (1 if fg.all() else -1)).all()
-        else:
-            assert np.array_equal(sdf[k], np.sqrt(d2[k, 1].astype(np.float64)) - np.sqrt(d2[k, 0].astype(np.float64)))
 
 
 def test_d2_is_exact_on_random_masks():

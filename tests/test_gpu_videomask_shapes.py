@@ -13,16 +13,12 @@ from lanpaint_amd import _cabi, videomask
 from lanpaint_amd._util import raw_stream
 from lanpaint_amd.videomask import FRAME_DTYPE, frame_plan
 from tests import videomask_ref as vref
-from tests.test_videomask_host import _apply, _pairs
+from tests.device import DEV, _dev
+from tests.image_checks import PLAN_INNER as INNER, PLAN_KEY as KEY, PLAN_ZERO as ZERO, _check_morph, _hand_plan
+from tests.image_inputs import _apply, _blob, _keys, _pairs, _row
 
 pytestmark = pytest.mark.gpu
-DEV = torch.device("cuda", 0)
 NONE = _cabi.LP_VMASK_D2_NONE
-ZERO, KEY, INNER = _cabi.LP_VMASK_ZERO, _cabi.LP_VMASK_KEY, _cabi.LP_VMASK_INNER
-
-
-def _dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
 
 
 # ---- resize: live Pillow, bit for bit ------------------------------------------------------------------------------------------
@@ -120,82 +116,6 @@ def test_resize_saturates_as_pillow_clip8_does():
     assert np.array_equal(out.cpu().numpy()[0], want.astype(np.float32) / np.float32(255))
 
 # ---- morph: the float64 arbiter ---------------------------------------------------------------------------------------------
-def _blob(rng, h, w):
-    """A soft mask in [0, 1]: two Gaussian bumps, the larger one deep enough inside the frame to have an interior."""
-    yy, xx = np.mgrid[:h, :w].astype(np.float64)
-    s = 0.25 * min(h, w) + 0.5
-    f = np.zeros((h, w))
-    for scale in (1.0, 0.5):
-        cy, cx = rng.uniform(0.35, 0.65) * h, rng.uniform(0.1, 0.9) * w
-        f += np.exp(-((yy - cy) ** 2 + (xx - cx) ** 2) / (2.0 * (s * scale) ** 2))
-    return np.clip(f, 0.0, 1.0).astype(np.float32)
-
-
-def _keys(rng, h, w):
-    """Five keys: two soft blobs, one whose foreground is exactly 0.5 next to nextafter(0.5, 0), one empty, one full."""
-    half, below = np.float32(0.5), np.nextafter(np.float32(0.5), np.float32(0))
-    edge = np.where(_blob(rng, h, w) >= 0.4, half, below).astype(np.float32)
-    edge[rng.random((h, w)) < 0.02] = 1.0
-    edge[rng.random((h, w)) < 0.02] = 0.0
-    return np.stack([_blob(rng, h, w), _blob(rng, h, w), edge, np.zeros((h, w), np.float32), np.ones((h, w), np.float32)])
-
-
-def _row(kind, lo=0, hi=0, sy1=0, sx1=0, sy2=0, sx2=0, wf=0.0):
-    return (kind, lo, hi, sx1, sy1, sx2, sy2, 0, wf, 1.0 - wf)
-
-
-def _hand_plan(h, w, n_keys):
-    """(plan, indices of the fully vacated INNER frames, indices of the entries naming a key out of range)."""
-    third, big = 1.0 / 3.0, 2 ** 31 - 1
-    rows = [
-        _row(INNER, 0, 1, wf=third),                                                          # 0: no shift
-        _row(INNER, 0, 1, sy1=1, sx1=-1, sy2=1, sx2=-1, wf=third),                            # 1, 2: one pixel
-        _row(INNER, 0, 1, sy1=-1, sx1=1, sy2=-1, sx2=1, wf=0.5),
-        _row(ZERO),
-        _row(INNER, 0, 1, sy1=h - 1, sx1=w - 1, sy2=h - 1, sx2=w - 1, wf=third),              # 4, 5: one row / column is left
-        _row(INNER, 0, 1, sy1=1 - h, sx1=1 - w, sy2=1 - h, sx2=1 - w, wf=third),
-        _row(INNER, 0, 1, sy1=h, sy2=h, wf=third),                                            # 6: past the frame in y only
-        _row(INNER, 0, 1, sx1=-w, sx2=-w, wf=third),                                          # 7: in x only
-        _row(INNER, 0, 1, sy1=h + 3, sx1=w, sy2=-h, sx2=-(w + 7), wf=third),                  # 8: in both
-        _row(INNER, 1, 0, sy1=big, sx1=-big - 1, sy2=-big - 1, sx2=big, wf=0.25),             # 9: the largest integers
-        _row(INNER, 0, 1, sy1=2, sx1=-2, sy2=-3, sx2=1, wf=third),                            # 10: both keys move the same way
-        _row(INNER, 0, 1, sy1=-1, sx1=5, sy2=4, sx2=-2, wf=0.75),                             # 11: mixed signs per axis
-        _row(INNER, 0, 1, wf=0.0), _row(INNER, 0, 1, wf=1.0),                                 # 12, 13: the end weights
-        _row(INNER, 0, 1, sy1=h, wf=third),                                                   # 14: only one key vacated
-        _row(KEY, 2),
-        _row(INNER, 0, 3, sx1=1, wf=third), _row(INNER, 2, 2, sy1=1, wf=third),               # 16, 17: not adjacent; equal
-        _row(INNER, 4, 1, sx2=1, wf=third), _row(INNER, 3, 4, wf=0.5),                        # 18, 19: hi < lo; empty to full
-        _row(ZERO),
-        _row(INNER, -1, 1, wf=third), _row(INNER, 0, n_keys, wf=third),                       # 21 .. 25: no such key
-        _row(KEY, -1), _row(KEY, n_keys), _row(INNER, n_keys, -1, wf=third),
-        _row(KEY, 0), _row(KEY, n_keys - 1), _row(ZERO),
-    ]
-    return np.array(rows, FRAME_DTYPE), [6, 7, 8, 9], [21, 22, 23, 24, 25]
-
-
-def _check_morph(tag, keys, stack, sdf, plan):
-    """The device's float and codes output of `plan` against the arbiter; returns (got, codes, want)."""
-    want = vref.morph_ref(keys, plan)
-    got = videomask.morph_frames(stack, plan, sdf).cpu().numpy()
-    codes = videomask.morph_frames(stack, plan, sdf, codes=True).cpu().numpy()
-    assert got.shape == want.shape and got.dtype == np.float32 and codes.dtype == np.uint8
-    ulp = vref.ulp_diff(got, want)
-    differing = int(np.count_nonzero(got.view(np.uint32) != want.view(np.uint32)))
-    h, w = keys.shape[1:]
-    print(f"VMASK_MORPH {h}x{w} {tag}: max ulp {int(ulp.max())}, differing {differing} of {got.size}")
-    assert ulp.max() <= 1, int(ulp.max())
-    assert 1.0 - differing / got.size >= 0.99999, (differing, got.size)
-    assert np.array_equal(codes, vref.codes_ref(got))                    # the conversion alone: the same fp32 multiply
-    want_codes = vref.codes_ref(want)
-    assert np.abs(codes.astype(np.int16) - want_codes.astype(np.int16)).max() <= 1
-    for t, p in enumerate(plan):                                         # what holds exactly
-        if p["kind"] == ZERO:
-            assert not got[t].any() and not codes[t].any(), t
-        elif p["kind"] == KEY and 0 <= p["key_lo"] < len(keys):
-            assert np.array_equal(got[t].view(np.uint32), keys[p["key_lo"]].view(np.uint32)), t
-    return got, codes, want
-
-
 @pytest.mark.parametrize("h,w", [(1, 1), (1, 300), (300, 1), (37, 53), (64, 64), (257, 1000), (480, 832)],
                          ids=lambda v: str(v))
 def test_morph_equals_the_arbiter(h, w):

@@ -12,12 +12,9 @@ import torch
 
 from lanpaint_amd import _cabi, grain, grain_nodes
 from tests import grain_ref as ref
+from tests.compare import _f32_bits as _bits
 
 NEW_ENTRIES = ("lp_grain_stats", "lp_grain_fit", "lp_grain_field", "lp_grain_apply")
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
 
 
 # ---- the restatement on its own -------------------------------------------------------------------------------------------------------

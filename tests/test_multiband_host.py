@@ -12,15 +12,12 @@ import torch.nn.functional as F
 
 from lanpaint_amd import _cabi, multiband
 from tests import multiband_ref as ref
+from tests.compare import _raw_bits as _bits
 
 LEVELS = (0, 1, 2, 3, 5, 12)
 SHAPES = [(1, 1), (1, 7), (7, 1), (2, 2), (3, 5), (63, 65), (64, 64), (130, 200), (300, 300)]
 WS_CASES = [(1, 1, 1, 1, 5), (1, 1, 2, 1, 1), (1, 1, 2, 1, 0), (2, 17, 33, 3, 2), (3, 32, 32, 4, 16), (1, 2049, 1, 5, 12),
             (81, 720, 1280, 3, 5), (65535, 32768, 32768, 64, 16), (4, 300, 300, 3, 0)]
-
-
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
 
 
 def _image(H, W, C=3, seed=0, B=1):

@@ -6,9 +6,10 @@ import pytest
 
 from oracle.lanpaint_oracle import OracleLanPaint
 from tests import golden_cases as gc
-from oracle import lanpaint_oracle as orc
+from tests.golden_cases import _options_for_call, check_schedule_traces
 from tests.helpers import assert_close, assert_digest, assert_matches_golden, load_golden, run_oracle_case, xi_list
 from tests.stubs import MODELS
+from oracle import lanpaint_oracle as orc
 
 
 @pytest.mark.parametrize("name", sorted(gc.CASES))
@@ -24,29 +25,6 @@ def test_oracle_matches_reference_golden(name):
         np.testing.assert_allclose([t["dist"] for t in tr], g["trace_dist"], rtol=2e-5)
         assert [t["counter"] for t in tr] == list(g["trace_counter"])
         assert [t["stopped"] for t in tr] == list(g["trace_stopped"])
-
-
-def _options_for_call(sc):
-    """A fresh copy of the schedule's model_options with a trace list, per sigma call -- what the fixture's generator handed the
-    reference (tests/golden/make_golden.py::run_schedule); None for schedules without the inner early stop."""
-    if sc.get("model_options") is None:
-        return None
-    mo = {k: dict(v) if isinstance(v, dict) else v for k, v in sc["model_options"].items()}
-    mo["lanpaint_semantic_trace"] = []
-    return mo
-
-
-def check_schedule_traces(g, iterations, traces, name, rtol=2e-5):
-    """Iterations run per sigma call and the stopper's records, call after call, against the reference's (fixture)."""
-    assert iterations == list(g["iterations"]), f"{name}: iterations per sigma call"
-    flat = [t for tr in traces for t in tr]
-    assert [k for k, tr in enumerate(traces) for _ in tr] == list(g["trace_call"])
-    assert [t["patience_counter"] for t in flat] == list(g["trace_counter"]) and [t["stopped"] for t in flat] == list(g["trace_stopped"])
-    for key in ("dist", "dist_inpaint", "dist_ring", "dist_drift", "threshold_eff", "abt"):
-        want = g["trace_" + key]
-        got = np.asarray([np.nan if t[key] is None else t[key] for t in flat], dtype=np.float64)
-        assert np.array_equal(np.isnan(got), np.isnan(want)), f"{name}: {key}"
-        np.testing.assert_allclose(got[~np.isnan(got)], want[~np.isnan(want)], rtol=rtol, err_msg=f"{name}: {key}")
 
 
 @pytest.mark.parametrize("name", sorted(gc.SCHEDULES))

@@ -13,14 +13,11 @@ import torch
 from lanpaint_amd import _cabi, fill
 from tests import cabi_header, fill_ref
 from tests import patch_fill_ref as pref
+from tests.cabi_header import _call, _signed
 
 MODES = [(1, 1, 1, 0), (3, 4, 4, 0), (4, 6, 8, 65535), (2, 3, 5, 32768), (2, 3, 5, 32767), (1, 6, 1, 12345)]
 WS_CASES = [(1, 1, 1, 1, 1), (1, 1, 1, 3, 6), (2, 17, 33, 3, 3), (3, 32, 32, 4, 2), (1, 2049, 1, 1, 6), (81, 720, 1280, 3, 4),
             (65535, 32768, 32768, 4, 6)]
-
-
-def _call(macro, args):
-    return "%s(%s)" % (macro, ", ".join(map(str, args)))
 
 
 @pytest.fixture(scope="module")
@@ -89,10 +86,6 @@ def _good(hip_lib, mode, **change):
              ws_bytes=_cabi.fill_patch_ws_bytes(2, 40, 150, 3, levels))
     d.update(change)
     return hip_lib.lp_mask_fill(ctypes.byref(_cabi.LpFillDesc(**d)), None)
-
-
-def _signed(u):
-    return u - (1 << 32) if u >= 1 << 31 else u
 
 
 def test_the_patch_form_refuses_a_bad_mode_word_without_a_device(hip_lib):

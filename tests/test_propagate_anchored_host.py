@@ -3,7 +3,6 @@ own -- that the rule does what it is for, on a clip with sub-pixel motion, and t
 entry's argument checks (made before any HIP call), the nodes' protocol, and that the existing propagate nodes are as they were.
 Layouts, constants and names against the header are tests/test_cabi_mirror.py's, for the whole C ABI."""
 import ctypes
-import functools
 import os
 
 import numpy as np
@@ -13,32 +12,11 @@ import torch
 from lanpaint_amd import _cabi
 from tests import propagate_anchored_ref as aref
 from tests import propagate_ref as ref
-from tests.anchor_clips import iou, subpixel_clip
+from tests.anchor_clips import subpixel_clip
+from tests.compare import _f32_bits as _bits
+from tests.propagate_scenes import assert_the_two_drift_iou_lines as assert_the_two_iou_lines, drift_case
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
-
-
-@functools.lru_cache(maxsize=None)
-def drift_case():
-    """subpixel_clip(33, 40, 56), the key on frame 0: (images, truth, the plain restatement's output, the anchored one's with the
-    defaults).  Shared with the GPU test, which compares the device's output with the last."""
-    images, truth = subpixel_clip(33, 40, 56)
-    key = truth[0].astype(np.float32)
-    return images, truth, ref.propagate_ref(images, key, 0, 4, 2, 8), aref.propagate_anchored_ref(images, key, 0, 4, 2, 8, 2)
-
-
-def assert_the_two_iou_lines(truth, plain, anchored):
-    """The proof that the rule does what it is for.  Measured on the restatement: 0.484 and a minimum of 0.868; the margins cover
-    nothing but a reader's rewording of the restatement."""
-    last = iou(plain[-1] >= 0.5, truth[-1])
-    worst = min(iou(anchored[t] >= 0.5, truth[t]) for t in range(len(truth)))
-    print("plain, last frame", last, "anchored, worst frame", worst)
-    assert last < 0.65
-    assert worst >= 0.80
 
 
 # ---- the restatement on its own ---------------------------------------------------------------------------------------------------------------

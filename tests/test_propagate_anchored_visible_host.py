@@ -4,7 +4,6 @@ and an occluder, and the properties it promises, as bits --, the C entry's argum
 protocol, and that the existing node modules are as they were.  Layouts, constants and names against the header are
 tests/test_cabi_mirror.py's, for the whole C ABI."""
 import ctypes
-import functools
 import os
 
 import numpy as np
@@ -16,68 +15,12 @@ from tests import propagate_anchored_ref as aref
 from tests import propagate_anchored_visible_ref as avref
 from tests import propagate_ref as ref
 from tests import propagate_visible_ref as vref
-from tests.anchor_clips import _tex, iou, subpixel_clip
+from tests.anchor_clips import subpixel_clip
+from tests.compare import _f32_bits as _bits
+from tests.propagate_scenes import (QUALITY_DEFAULTS as DEFAULTS, QUALITY_OCCLUSION as OCCLUSION, anchored_quality_case as quality_case,
+                                    assert_the_anchored_quality_lines as assert_the_quality_lines, whole_subject_iou)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-DEFAULTS = (0, 4, 2, 8)                                                 # key_frame, levels, search, smooth
-ANCHOR, OCCLUSION = 2, 16
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
-
-
-def occluded_clip(name):
-    """Clip A: subpixel_clip(33, 64, 96) with a static textured bar on columns 50..55 of every frame, at most 28 % of the subject
-    behind it on any frame.  Clip B: the same with rows 20..25, so the bar crosses the subject on every frame, the key frame
-    included.  (images, truth, bar bool [H, W])."""
-    images, truth = subpixel_clip(33, 64, 96)
-    bar = np.zeros((64, 96), bool)
-    if name == "A":
-        images[:, :, 50:56, :] = _tex(np.random.default_rng(99), 64, 6)[None, :, :, None]
-        bar[:, 50:56] = True
-    else:
-        images[:, 20:26, :, :] = _tex(np.random.default_rng(99), 6, 96)[None, :, :, None]
-        bar[20:26] = True
-    return images, truth, bar
-
-
-@functools.lru_cache(maxsize=None)
-def quality_case(name):
-    """(images, truth, the new restatement's (mask, hidden), the anchored restatement's mask, the visible one's (mask, hidden)) at
-    the defaults, the key truth[0] on frame 0.  "N": subpixel_clip(33, 40, 56), no occluder.  Shared with the GPU test, which
-    compares the device's output with the first."""
-    images, truth = subpixel_clip(33, 40, 56) if name == "N" else occluded_clip(name)[:2]
-    key = truth[0].astype(np.float32)
-    return (images, truth, avref.propagate_anchored_visible_ref(images, key, *DEFAULTS, ANCHOR, OCCLUSION),
-            aref.propagate_anchored_ref(images, key, *DEFAULTS, ANCHOR), vref.propagate_visible_ref(images, key, *DEFAULTS, OCCLUSION))
-
-
-def whole_subject_iou(mask, hidden, truth):
-    """(last frame, worst frame behind the key) of iou((mask + hidden)[t] >= 0.5, truth[t])."""
-    v = [iou((mask[t] + hidden[t]) >= 0.5, truth[t]) for t in range(1, len(truth))]
-    return v[-1], min(v)
-
-
-# the anchored and the visible form's last-frame whole-subject IoU may be at most this
-LINES = {"A": (0.70, 0.30), "B": (0.50, 0.50)}
-
-
-def assert_the_quality_lines(name, truth, new, anchored, visible):
-    """The proof that the rule does what it is for: whole-subject IoU, hidden = 0 for the anchored form.  Measured on the
-    restatements, last frame / worst frame:
-        A: new 0.917 / 0.914, anchored 0.621 / 0.621, visible 0.142 / 0.142   (without the gate 0.720 / 0.720)
-        B: new 0.964 / 0.914, anchored 0.386 / 0.381, visible 0.067 / 0.067   (without the gate 0.361 / 0.361)
-    The margins cover a reader's rewording of the restatement and nothing else.  IoU of `mask` alone against the visible part of
-    the subject on A: 0.604 on the last and on the worst frame (the block-wide flags hide up to a block beyond the bar); recorded,
-    nothing is asserted on it."""
-    new_last, new_worst = whole_subject_iou(*new, truth)
-    anchored_last, _ = whole_subject_iou(anchored, np.zeros_like(anchored), truth)
-    visible_last, _ = whole_subject_iou(*visible, truth)
-    print(name, "new, last and worst frame", new_last, new_worst, "anchored, last frame", anchored_last, "visible, last frame", visible_last)
-    assert new_worst >= 0.85
-    assert anchored_last <= LINES[name][0]
-    assert visible_last <= LINES[name][1]
 
 
 # ---- the restatement on its own ---------------------------------------------------------------------------------------------------------------

@@ -3,7 +3,6 @@ properties the rule promises, as bits, and the one quality condition it has to m
 argument checks (made before any HIP call), the node's protocol and the no-fallback errors.  Layouts, constants and names against
 the header are tests/test_cabi_mirror.py's, for the whole C ABI."""
 import ctypes
-import functools
 import os
 
 import numpy as np
@@ -12,53 +11,11 @@ import torch
 
 from lanpaint_amd import _cabi
 from tests import propagate_ref as ref
+from tests.compare import _f32_bits as _bits, _iou
+from tests.propagate_scenes import SCENES, disc_scene, texture
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ONE = np.float32(1.0).view(np.uint32)
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
-
-
-@functools.lru_cache(maxsize=None)
-def texture(seed, H=256, W=256, beta=1.2):
-    """A periodic random texture with a 1 / f^beta amplitude spectrum, scaled to [0, 1]."""
-    rng = np.random.default_rng(seed)
-    fy, fx = np.fft.fftfreq(H)[:, None], np.fft.fftfreq(W)[None, :]
-    f = np.sqrt(fy * fy + fx * fx)
-    f[0, 0] = 1.0
-    spec = (rng.normal(size=(H, W)) + 1j * rng.normal(size=(H, W))) / f ** beta
-    spec[0, 0] = 0
-    t = np.fft.ifft2(spec).real
-    return (t - t.min()) / (t.max() - t.min())
-
-
-def _sample(tex, yy, xx):
-    H, W = tex.shape
-    y0, x0 = np.floor(yy).astype(int), np.floor(xx).astype(int)
-    fy, fx = yy - y0, xx - x0
-    g = lambda y, x: tex[y % H, x % W]                                # noqa: E731
-    return (1 - fy) * ((1 - fx) * g(y0, x0) + fx * g(y0, x0 + 1)) + fy * ((1 - fx) * g(y0 + 1, x0) + fx * g(y0 + 1, x0 + 1))
-
-
-def disc_scene(F, v_obj, v_bg, radius, centre, seed=0, H=96, W=128, sigma=0.01):
-    """A disc carrying one texture moves by v_obj pixels per frame over a background texture that moves by v_bg, both sampled
-    bilinearly, Gaussian noise on every frame: (images fp32 [F, H, W, 1], the true disc per frame)."""
-    bg, ob = texture((seed, 1)), texture((seed, 2))
-    rng = np.random.default_rng([seed, 3])
-    yy, xx = np.mgrid[:H, :W].astype(np.float64)
-    frames, discs = [], []
-    for t in range(F):
-        disc = (yy - centre[0] - v_obj[0] * t) ** 2 + (xx - centre[1] - v_obj[1] * t) ** 2 <= radius ** 2
-        img = np.where(disc, _sample(ob, yy - v_obj[0] * t, xx - v_obj[1] * t), _sample(bg, yy - v_bg[0] * t, xx - v_bg[1] * t))
-        frames.append(img + rng.normal(0, sigma, img.shape))
-        discs.append(disc)
-    return np.stack(frames).astype(np.float32)[..., None], np.stack(discs)
-
-
-def _iou(a, b):
-    return float((a & b).sum()) / max(int((a | b).sum()), 1)
 
 
 # ---- the restatement on its own -------------------------------------------------------------------------------------------------------
@@ -125,10 +82,6 @@ def test_the_chains_before_and_after_a_middle_key_frame_are_independent():
     per_frame = np.zeros((7, 96, 128), np.float32)
     per_frame[3] = mask                                               # [F, H, W]: the key frame's mask is the one that is read
     assert (_bits(ref.propagate_ref(images, per_frame, 3, 3, 2, 8)) == _bits(whole)).all()
-
-
-SCENES = {"slow": (10, (1.3, -0.7), (0.3, -0.4), 18, (40, 70)), "still background": (12, (0.4, 0.3), (0.0, 0.0), 18, (40, 60)),
-          "fast": (8, (3.3, -2.6), (-0.5, 0.5), 14, (30, 85))}
 
 
 @pytest.mark.parametrize("name", list(SCENES))

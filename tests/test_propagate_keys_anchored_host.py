@@ -8,7 +8,6 @@ A descriptor that the library would accept is never handed over here: its addres
 the launch would follow them.  That both forms accept what they should is tests/test_gpu_propagate_keys_anchored.py's, on real
 buffers."""
 import ctypes
-import functools
 import os
 
 import numpy as np
@@ -20,39 +19,15 @@ from tests import propagate_anchored_ref as aref
 from tests import propagate_keys_anchored_ref as karef
 from tests import propagate_keys_ref as kref
 from tests.anchor_clips import iou, subpixel_clip
+from tests.compare import _f32_bits as _bits
+from tests.device import _match_jobs as _jobs
+from tests.propagate_scenes import assert_the_two_gap_iou_lines as assert_the_two_iou_lines, gap_drift_case, lowest_iou
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 WARPED = _cabi.LP_PROP_MATCH_WARPED_KEY
 
 
-def _bits(a):
-    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
-
-
 # ---- the restatement on its own ----------------------------------------------------------------------------------------------------------
-@functools.lru_cache(maxsize=None)
-def gap_drift_case():
-    """subpixel_clip(49, 40, 72) with the true discs painted on frames 8 and 40, levels 3: (images, truth, the several-keys
-    restatement's output, the anchored one's).  Shared with the GPU test, which compares the device's output with the last."""
-    images, truth = subpixel_clip(49, 40, 72)
-    masks = truth[[8, 40]].astype(np.float32)
-    return (images, truth, kref.propagate_keys_ref(images, masks, [8, 40], 3, 2, 8),
-            karef.propagate_keys_anchored_ref(images, masks, [8, 40], 3, 2, 8, 2))
-
-
-def lowest_iou(out, truth):
-    return min(iou(out[t] >= 0.5, truth[t]) for t in range(len(truth)))
-
-
-def assert_the_two_iou_lines(truth, plain, anchored):
-    """What the form is for: half way through the gap the plain chains have both fallen behind, the anchored ones have not.
-    The restatement gives 0.737 and 0.871; the bounds are the issue's."""
-    low_plain, low_anchored = lowest_iou(plain, truth), lowest_iou(anchored, truth)
-    print("several keys, lowest per-frame IoU", low_plain, "anchored", low_anchored)
-    assert low_anchored >= 0.85
-    assert low_plain <= 0.78
-
-
 def test_the_plain_chains_fall_behind_between_two_keys_and_the_anchored_chains_do_not():
     _, truth, plain, anchored = gap_drift_case()
     assert_the_two_iou_lines(truth, plain, anchored)
@@ -94,11 +69,6 @@ def test_still_video_empty_and_full():
 
 
 # ---- the C ABI ------------------------------------------------------------------------------------------------------------------------
-def _jobs(rows):
-    arr = (_cabi.LpPropMatchJob * len(rows))(*[_cabi.LpPropMatchJob(*r) for r in rows])
-    return arr, ctypes.cast(arr, ctypes.c_void_p)
-
-
 FIELDS = [f for f, _ in _cabi.LpPropMatchJob._fields_]
 
 

@@ -8,7 +8,6 @@ A descriptor that the library would accept is never handed over here: its addres
 the launch would follow them.  That the gated form accepts what it should is tests/test_gpu_propagate_keys_anchored_visible.py's,
 on real buffers."""
 import ctypes
-import functools
 import os
 
 import numpy as np
@@ -22,18 +21,14 @@ from tests import propagate_keys_anchored_visible_ref as kavref
 from tests import propagate_keys_ref as kref
 from tests import propagate_keys_visible_ref as kvref
 from tests import propagate_ref as ref
-from tests.anchor_clips import iou
-from tests.test_propagate_anchored_visible_host import occluded_clip
-from tests.test_propagate_keys_visible_host import _disc, _moving
-from tests.test_propagate_visible_host import occluded_disc_clip
+from tests.compare import _f32_bits as _bits
+from tests.device import _match_jobs as _jobs
+from tests.propagate_scenes import (_moving, _moving_disc as _disc, assert_the_keys_quality_lines as assert_the_quality_lines,
+                                    keys_quality_case as quality_case)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GATED = _cabi.LP_PROP_MATCH_GATED
 LEVELS, SEARCH, SMOOTH, ANCHOR, OCCLUSION = 3, 2, 8, 2, 16
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
 
 
 def _same(got, want, what):
@@ -104,53 +99,6 @@ def test_a_still_video_empty_keys_the_keys_themselves_and_the_codes():
 
 
 # ---- the quality lines ----------------------------------------------------------------------------------------------------------------------
-@functools.lru_cache(maxsize=None)
-def quality_case(name):
-    """(images, masks, keys, levels, truth, the new restatement's (mask, hidden), its trace, the keys-visible restatement's
-    (mask, hidden), the keys-anchored one's mask).  "A", "B": tests/test_propagate_anchored_visible_host.py's occluded clips with the
-    truth painted on the first and the last frame, the defaults.  "disc": occluded_disc_clip(0, 16, 64, 96, 12, (28, 44)), keys 0 and
-    15, levels 3.  Shared with the GPU test, which compares the device's outputs with the new restatement's."""
-    if name == "disc":
-        images, truth, _ = occluded_disc_clip(seed=0, F=16, H=64, W=96, radius=12, bar=(28, 44))
-        levels = 3
-    else:
-        images, truth, _ = occluded_clip(name)
-        levels = 4
-    keys = [0, len(truth) - 1]
-    masks = truth[keys].astype(np.float32)
-    trace = {}
-    new = kavref.propagate_keys_anchored_visible_ref(images, masks, keys, levels, 2, 8, 2, 16, trace=trace)
-    return (images, masks, keys, levels, truth, new, trace, kvref.propagate_keys_visible_ref(images, masks, keys, levels, 2, 8, 16),
-            karef.propagate_keys_anchored_ref(images, masks, keys, levels, 2, 8, 2))
-
-
-def whole_subject(mask, hidden, truth, frames):
-    """(worst, mean) over `frames` of iou((mask + hidden)[t] >= 0.5, truth[t])."""
-    v = [iou((mask[t] + hidden[t]) >= 0.5, truth[t]) for t in frames]
-    return min(v), sum(v) / len(v)
-
-
-def assert_the_quality_lines(name, truth, new, keys_visible, keys_anchored):
-    """What the form is for, whole-subject IoU with hidden = 0 for the keys-anchored form.  Measured on the restatements:
-        A, worst frame of all:      new 0.910, keys-visible 0.770, keys-anchored 0.781
-        B, worst frame of all:      new 0.894, keys-visible 0.669, keys-anchored 0.807
-        disc, mean / worst of 1..14: new 0.946 / 0.837, keys-visible 0.967 / 0.921, keys-anchored 0.243 / 0.000
-    The bounds are the issue's; the rule is integer arithmetic, so the margins cover a rewording of the restatement only."""
-    frames = range(1, len(truth) - 1) if name == "disc" else range(len(truth))
-    worst, mean = whole_subject(*new, truth, frames)
-    kv_worst, kv_mean = whole_subject(*keys_visible, truth, frames)
-    ka_worst, ka_mean = whole_subject(keys_anchored, np.zeros_like(keys_anchored), truth, frames)
-    print(name, "new worst / mean", worst, mean, "keys-visible", kv_worst, kv_mean, "keys-anchored", ka_worst, ka_mean)
-    if name == "disc":
-        assert mean >= 0.85
-        assert ka_mean <= 0.5
-    else:
-        assert worst >= 0.85
-        assert kv_worst <= {"A": 0.80, "B": 0.72}[name]
-        assert ka_worst <= 0.83
-    return worst, mean, kv_worst, kv_mean, ka_worst, ka_mean
-
-
 @pytest.mark.parametrize("name", ["A", "B", "disc"])
 def test_the_new_form_holds_where_either_several_keys_form_fails(name):
     _, masks, keys, _, truth, new, trace, keys_visible, keys_anchored = quality_case(name)
@@ -168,11 +116,6 @@ def test_the_new_form_holds_where_either_several_keys_form_fails(name):
 
 
 # ---- the C ABI ------------------------------------------------------------------------------------------------------------------------
-def _jobs(rows):
-    arr = (_cabi.LpPropMatchJob * len(rows))(*[_cabi.LpPropMatchJob(*r) for r in rows])
-    return arr, ctypes.cast(arr, ctypes.c_void_p)
-
-
 FIELDS = [f for f, _ in _cabi.LpPropMatchJob._fields_]
 
 

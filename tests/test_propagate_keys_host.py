@@ -14,7 +14,8 @@ import torch
 from lanpaint_amd import _cabi
 from tests import propagate_keys_ref as kref
 from tests import propagate_ref as ref
-from tests.test_propagate_host import SCENES, _bits, _iou, disc_scene, texture
+from tests.compare import _f32_bits as _bits, _iou
+from tests.propagate_scenes import SCENES, disc_scene, texture
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ONE = np.float32(1.0).view(np.uint32)

@@ -16,28 +16,11 @@ from tests import propagate_keys_ref as kref
 from tests import propagate_keys_visible_ref as kvref
 from tests import propagate_ref as ref
 from tests import propagate_visible_ref as vref
-from tests.test_propagate_visible_host import _iou, _texture, occluded_disc_clip
+from tests.compare import _f32_bits as _bits, _iou
+from tests.propagate_scenes import _moving, _moving_disc as _disc, _texture, occluded_disc_clip
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LEVELS, SEARCH, SMOOTH = 3, 2, 8
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
-
-
-def _moving(F, H, W, seed=21):
-    """Frames cut out of one canvas that moves by (1, -2) per frame, a little noise, and a static bar of another texture."""
-    rng = np.random.default_rng(seed)
-    canvas = rng.random((H + F, W + 2 * F, 3), dtype=np.float32)
-    frames = np.stack([canvas[t:t + H, 2 * (F - 1 - t):2 * (F - 1 - t) + W] for t in range(F)]) + rng.normal(0, 0.02, (F, H, W, 3))
-    frames[:, :, 2 * W // 5:3 * W // 5] = rng.random((H, 3 * W // 5 - 2 * W // 5, 3), dtype=np.float32)
-    return frames.astype(np.float32)
-
-
-def _disc(H, W, cy, cx, r):
-    yy, xx = np.mgrid[:H, :W]
-    return ((yy - cy) ** 2 + (xx - cx) ** 2 <= r * r).astype(np.float32)
 
 
 # ---- what follows from the rule, on the restatement alone -------------------------------------------------------------------------------

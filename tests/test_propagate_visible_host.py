@@ -13,46 +13,11 @@ import torch
 from lanpaint_amd import _cabi
 from tests import propagate_ref as ref
 from tests import propagate_visible_ref as vref
+from tests.compare import _f32_bits as _bits, _iou
+from tests.propagate_scenes import _texture, occluded_disc_clip
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DEFAULT_OCCLUSION = 16
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
-
-
-def _texture(rng, H, W, beta=1.2):
-    """A periodic random texture with a 1 / f^beta amplitude spectrum, scaled to [0, 1]."""
-    fy, fx = np.fft.fftfreq(H)[:, None], np.fft.fftfreq(W)[None, :]
-    f = np.sqrt(fy * fy + fx * fx)
-    f[0, 0] = 1.0
-    spec = (rng.normal(size=(H, W)) + 1j * rng.normal(size=(H, W))) / f ** beta
-    spec[0, 0] = 0
-    t = np.fft.ifft2(spec).real
-    return (t - t.min()) / (t.max() - t.min())
-
-
-def occluded_disc_clip(seed, F, H, W, radius, bar, speed=3, noise=0.01):
-    """A static random-texture background; a disc with a texture of its own that moves `speed` pixels per frame from the left
-    edge; a static bar over columns bar[0]..bar[1] - 1 with a third texture, drawn over everything; Gaussian noise per frame.
-    (images fp32 [F, H, W, 1], the whole disc per frame bool [F, H, W], the bar bool [H, W])."""
-    rng = np.random.default_rng(seed)
-    bg, ob, bt = (_texture(rng, 128, 256) for _ in range(3))
-    yy, xx = np.mgrid[:H, :W]
-    on_bar = (xx >= bar[0]) & (xx < bar[1])
-    frames, discs = [], []
-    for t in range(F):
-        disc = (yy - H // 2) ** 2 + (xx - (radius + 2 + speed * t)) ** 2 <= radius * radius
-        img = np.where(disc, ob[yy, (xx - speed * t) % 256], bg[:H, :W])
-        img = np.where(on_bar, bt[:H, :W], img)
-        frames.append(img + rng.normal(0, noise, img.shape))
-        discs.append(disc)
-    return np.stack(frames).astype(np.float32)[..., None], np.stack(discs), on_bar
-
-
-def _iou(a, b):
-    return float((a & b).sum()) / max(int((a | b).sum()), 1)
 
 
 @functools.lru_cache(maxsize=None)

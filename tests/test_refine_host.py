@@ -11,13 +11,10 @@ import torch
 
 from lanpaint_amd import _cabi, refine
 from tests import refine_ref as ref
+from tests.compare import _raw_bits as _bits
 
 SHAPES = [(1, 1), (1, 7), (7, 1), (5, 9), (33, 65), (40, 70)]
 RADII = (1, 3, 8, 64)
-
-
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
 
 
 def _guide(H, W, C=3, seed=0):

@@ -12,7 +12,6 @@ pass both absolute conditions and are rejected by `ratio` alone: neither residua
 search 2): quiet pairs A / N 3.5 .. 4.0 and share 4 .. 11 %, box pairs 9.6 .. 15.8 and 6 .. 9 %, cuts 40.1 .. 88.3 and
 85 .. 100 %, flash pairs 124 and 100 %."""
 import ctypes
-import functools
 import os
 
 import numpy as np
@@ -22,20 +21,10 @@ import torch
 from lanpaint_amd import _cabi, shots, shots_nodes
 from tests import shot_clips as clips
 from tests import shots_ref as sref
-from tests import temporal_fill_ref as tref
+from tests.shot_clips import expected_shot, fill_case, foreign_sources, scores
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 T, HI = shots.THRESHOLD, shots.HIST
-
-
-@functools.lru_cache(maxsize=None)
-def scores(name, level=2, search=2):
-    images, starts = clips.CLIPS[name]()
-    return (*sref.shot_scores(images, level, search), starts)
-
-
-def expected_shot(frames, starts):
-    return np.searchsorted(np.asarray(starts, dtype=np.int64), np.arange(frames), side="right").astype(np.int32)
 
 
 # ---- the rule on the clips --------------------------------------------------------------------------------------------------------------
@@ -199,30 +188,6 @@ def test_ranges_are_checked_and_read_from_a_shot_tensor():
 
 
 # ---- what the shot-aware fill rests on, by the temporal fill's restatement alone ------------------------------------------------------------
-FILL_FRAMES, FILL_CUT, FILL_LEVELS = 6, 3, 3
-
-
-@functools.lru_cache(maxsize=None)
-def fill_case():
-    """(images, mask, ranges, the whole clip's fill, the per-shot composition): the two-shot clip, a box under the mask in the two
-    frames beside the cut.  tests/test_gpu_shots.py compares the device with both."""
-    images, starts = clips.two_shots(FILL_FRAMES, FILL_CUT)
-    mask = clips.box_mask(FILL_FRAMES, FILL_CUT)
-    ranges = [(0, FILL_CUT), (FILL_CUT, FILL_FRAMES)]
-    whole = tref.temporal_fill_ref(images, mask, levels=FILL_LEVELS)
-    parts = [tref.temporal_fill_ref(images[lo:hi], mask[lo:hi], levels=FILL_LEVELS) for lo, hi in ranges]
-    source = np.concatenate([np.where(p[2] >= 0, p[2] + lo, p[2]) for p, (lo, hi) in zip(parts, ranges)])
-    composed = (np.concatenate([p[0] for p in parts]), np.concatenate([p[1] for p in parts]), source)
-    return images, mask, ranges, whole, composed
-
-
-def foreign_sources(source, mask, ranges):
-    """The masked pixels whose source frame lies in another shot than the pixel."""
-    shot = expected_shot(source.shape[0], [lo for lo, _ in ranges[1:]])
-    of_source = shot[np.clip(source, 0, None)]
-    return int(((mask >= 0.5) & (source >= 0) & (of_source != shot[:, None, None])).sum())
-
-
 def test_the_plain_fill_borrows_across_the_cut_and_the_per_shot_fill_does_not():
     images, mask, ranges, whole, composed = fill_case()
     assert sref.shot_ranges(sref.detect_shots(images, T, HI)[0]) == ranges         # the detector finds that cut

@@ -12,12 +12,9 @@ import torch
 
 from lanpaint_amd import _cabi, stabilize
 from tests import stabilize_ref as ref
+from tests.compare import _f32_bits as _bits
 
 ONE = np.float32(1.0).view(np.uint32)
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
 
 
 def _blobs(F, H, W, seed=0):

@@ -12,126 +12,16 @@ import pytest
 import torch
 
 from lanpaint_amd import _cabi
-from tests import propagate_ref as ref
 from tests import temporal_fill_checked_ref as cref
 from tests import temporal_fill_ref as tref
-from tests.test_gpu_propagate import _rng, _video, _wild_video
-from tests.test_temporal_fill_host import pan_clip, still_clip
+from tests.compare import _f32_bits as _bits
+from tests.temporal_clips import (CLEAN_CLIPS, SECOND_OBJECT, check_clean, check_invariant, clean_clip, pair_case, pair_want, random_clip,
+                                  second_object_clip, second_object_counts)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-F = 5                                                                  # the stage case: frame 2 of 5, its donor frame 3
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
-
-
-# ---- the scenes; tests/test_gpu_temporal_fill_checked.py runs the device on the same ones --------------------------------------------
-@functools.lru_cache(maxsize=None)
-def second_object_clip():
-    """(boxless clip, clip, mask): 10 frames of 64 x 96 x 3 on one still random canvas; a second object, a 40 x 40 texture, moves
-    2 px per frame down through the path of a 12 x 12 constant box that moves 5 px per frame to the right on top of it; the mask
-    is the box grown by 1.  The one-layer background field cannot hold both motions."""
-    frames, H, W = 10, 64, 96
-    rng = np.random.default_rng(11)
-    clean = np.repeat(rng.random((1, H, W, 3), dtype=np.float32), frames, axis=0)
-    tex = rng.random((40, 40, 3), dtype=np.float32)
-    for t in range(frames):
-        clean[t, 2 * t:2 * t + 40, 36:76] = tex
-    clip, mask = clean.copy(), np.zeros((frames, H, W), np.float32)
-    for t in range(frames):
-        y, x = 26, 6 + 5 * t
-        clip[t, y:y + 12, x:x + 12] = 0.5
-        mask[t, y - 1:y + 13, x - 1:x + 13] = 1
-    return clean, clip, mask
-
-
-# what the restatements give on it at the defaults and agree = 8; the conditions these satisfy are in the test below
-SECOND_OBJECT = dict(masked=1960, plain_wrong=556, filled=1169, wrong=67, disputed=791, verified=343, verified_wrong=14)
-
-
-def second_object_counts(plain, checked):
-    """The counts of SECOND_OBJECT from the outputs of the plain and the checked call on the clip.  Wrong: a borrowed pixel whose
-    bits differ from the clip drawn without the box."""
-    clean, _, mask = second_object_clip()
-    m = mask == 1
-    (pf, _, ps), (cf, cr, cs, cw) = plain, checked
-    plain_wrong = (_bits(pf) != _bits(clean)).any(-1) & m & (ps >= 0)
-    wrong = (_bits(cf) != _bits(clean)).any(-1) & m & (cs >= 0)
-    assert ((cr == 1) == (m & (cs < 0))).all()
-    return dict(masked=int(m.sum()), plain_wrong=int(plain_wrong.sum()), filled=int((m & (cs >= 0)).sum()), wrong=int(wrong.sum()),
-                disputed=int((cs == cref.DISPUTED).sum()), verified=int((cw == 2).sum()), verified_wrong=int((wrong & (cw == 2)).sum()))
-
-
-@functools.lru_cache(maxsize=None)
-def clean_clip(name, noisy):
-    """(clip, mask) of `pan_clip()` or `still_clip(2)`, with Gaussian noise of sigma 4 grey levels on every frame when `noisy`."""
-    _, clip, mask = pan_clip() if name == "pan" else still_clip(2)
-    if noisy:
-        clip = (clip + np.random.default_rng(3).normal(0, 4 / 255, clip.shape)).astype(np.float32)
-    return clip, mask
-
-
-CLEAN_CLIPS = [("pan", False), ("still", False), ("pan", True), ("still", True)]
-
-
-@functools.lru_cache(maxsize=None)
-def random_clip():
-    """A random moving video of 5 x 40 x 70 x 3 under random masks: every pixel class, disputes included."""
-    images = _video(F, 40, 70)
-    mask = (_rng(F, 40, 70, 0, 5).random((F, 40, 70)) < 0.3).astype(np.float32)
-    return images, mask
-
-
-def check_invariant(images, plain, checked, what):
-    """What follows from the rule, between a plain and a checked result on the same arguments."""
-    (pf, pr, ps), (cf, cr, cs, cw) = plain, checked
-    agreed, nan = cs != cref.DISPUTED, np.isnan(pf)
-    assert (cs[agreed] == ps[agreed]).all() and (_bits(cr)[agreed] == _bits(pr)[agreed]).all(), what
-    assert (((_bits(cf) == _bits(pf)) | (nan & np.isnan(cf)))[agreed]).all(), what
-    assert (ps[~agreed] >= 0).all(), what
-    assert ((_bits(cf) == _bits(images)) | np.isnan(images))[~agreed].all(), what
-    masked = pr.astype(bool) | (ps != np.arange(len(ps))[:, None, None])          # the plain call's mask bits
-    assert ((cr == 1) == (masked & (cs < 0))).all() and ((cr == 0) | (cr == 1)).all(), what
-    assert (cw[~masked] == 0).all() and (cw[cs < 0] == 0).all() and ((cw >= 1) == (masked & (cs >= 0))).all() and cw.max() <= 2, what
 
 
 # ---- the case of the device's stage test ----------------------------------------------------------------------------------------------
-@functools.lru_cache(maxsize=None)
-def pair_case(H, W, wild=False, C=3):
-    """Frame 2 of 5 with its donor 3: random known bits of both, of the frame a quarter to three quarters by block, a random field of up to 2.5 pixels, a random state of the donor
-    with origins in every frame, a random forward `source` under the mask and a forward `filled` that is, block by block, the
-    backward sample itself, that sample darker or brighter by 0.3 or by 0.05, or noise.
-    (images, vec, known [2, H, W], org, pos, source_t, filled_t)."""
-    rng = _rng(H, W, int(wild), C, 8)
-    images = (_wild_video if wild else _video)(F, H, W, C)
-    gh, gw = ref.grid_of(H, W)
-    vec = rng.integers(-40, 41, (gh, gw, 2)).astype(np.int32)
-    share = cref.per_pixel(rng.choice([0.25, 0.5, 0.75], (gh, gw)), H, W)   # so that a block holds few or many pixels to compare
-    known = (rng.random((2, H, W)) < np.stack([share, np.full((H, W), 0.5)])).astype(np.uint8)
-    org = rng.integers(-1, F, (H, W)).astype(np.int32)
-    pos = np.stack([rng.integers(-40, 16 * H + 40, (H, W)), rng.integers(-40, 16 * W + 40, (H, W))], axis=-1).astype(np.int32)
-    source = np.where(known[0] != 0, 2, rng.choice([-1, 0, 1, 3, 4], (H, W))).astype(np.int32)
-    b_org, b_pos = tref.carry(2, known[0], 3, known[1], vec, (org, pos), 0)
-    has_b = (known[0] == 0) & (b_org >= 0)
-    filled = images[2].copy()
-    filled[has_b] = tref.sample(images, b_org[has_b], b_pos[has_b][:, 0], b_pos[has_b][:, 1])
-    mode = cref.per_pixel(rng.integers(0, 5, (gh, gw)), H, W)
-    with np.errstate(invalid="ignore"):
-        filled = filled + np.choose(mode, [0, -0.3, 0.3, 0, 0.05]).astype(np.float32)[..., None] + rng.normal(0, 0.004, filled.shape)
-    filled = np.where((mode == 3)[..., None], rng.random(filled.shape), filled).astype(np.float32)
-    filled = np.where((known[0] != 0)[..., None], images[2], filled)
-    return images, vec, known, org, pos, source, filled
-
-
-def pair_want(case, state, reach, agree, stats=None):
-    """What the step must leave for `case`: the state (org, pos) and frame 2's (filled, source, remaining, witnesses)."""
-    images, vec, known, org, pos, source, filled = case
-    b_org, b_pos = tref.carry(2, known[0], 3, known[1], vec, (org, pos) if state else None, reach)
-    remaining = ((known[0] == 0) & (source == -1)).astype(np.float32)
-    return (b_org, b_pos), cref.pair(2, known[0], images, b_org, b_pos, filled, source, remaining, agree, stats)
-
-
 @pytest.mark.parametrize("plane", [(40, 70), (23, 33)], ids=lambda s: "x".join(map(str, s)))
 def test_the_stage_case_reaches_every_branch_of_the_rule(plane):
     H, W = plane
@@ -216,12 +106,6 @@ def test_clean_geometry_is_never_disputed_with_and_without_noise(name, noisy):
     clip, mask = clean_clip(name, noisy)
     plain, checked = tref.temporal_fill_ref(clip, mask), cref.temporal_fill_checked_ref(clip, mask)
     check_clean(plain, checked)
-
-
-def check_clean(plain, checked):
-    assert not (checked[2] == cref.DISPUTED).any() and (checked[3] == 2).any()
-    for p, c in zip(plain, checked):
-        assert (_bits(p) == _bits(c)).all() if p.dtype == np.float32 else (p == c).all()
 
 
 def test_one_and_two_frames_and_the_last_frame():

@@ -3,7 +3,6 @@
 checks, the node's protocol and the no-fallback errors.  Layouts, constants and names against the header are
 tests/test_cabi_mirror.py's, for the whole C ABI."""
 import ctypes
-import functools
 import os
 
 import numpy as np
@@ -13,66 +12,11 @@ import torch
 from lanpaint_amd import _cabi
 from tests import propagate_ref as ref
 from tests import temporal_fill_ref as tref
+from tests.compare import _f32_bits as _bits
+from tests.temporal_clips import (STILL_REMAINING, check_fill_fixed as check_fixed, check_fill_pan as check_pan,
+                                  check_fill_still as check_still, fill_pan_clip as pan_clip, fill_still_clip as still_clip)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
-
-
-# ---- the scenes of the three properties; tests/test_gpu_temporal_fill.py runs the device on the same ones ---------------------------------
-@functools.lru_cache(maxsize=None)
-def pan_clip():
-    """(boxless clip, clip, mask): 8 frames of 48 x 64 x 3 cut from one random canvas, panning (1, -2) px per frame; a 12 x 12
-    constant box moves 5 px per frame across it; the mask is the box grown by 1."""
-    rng = np.random.default_rng(5)
-    F, H, W = 8, 48, 64
-    canvas = rng.random((H + F, W + 2 * F, 3), dtype=np.float32)
-    clean = np.stack([canvas[t:t + H, 2 * (F - 1 - t):2 * (F - 1 - t) + W] for t in range(F)])
-    clip, mask = clean.copy(), np.zeros((F, H, W), np.float32)
-    for t in range(F):
-        y, x = 18, 4 + 5 * t
-        clip[t, y:y + 12, x:x + 12] = 0.5
-        mask[t, y - 1:y + 13, x - 1:x + 13] = 1
-    return clean, clip, mask
-
-
-@functools.lru_cache(maxsize=None)
-def still_clip(step):
-    """(still canvas, clip, mask): 8 equal frames of 32 x 48 x 3 with an 8 x 8 constant box that moves `step` px per frame."""
-    F, H, W = 8, 32, 48
-    still = np.repeat(np.random.default_rng(6).random((1, H, W, 3), dtype=np.float32), F, axis=0)
-    clip, mask = still.copy(), np.zeros((F, H, W), np.float32)
-    for t in range(F):
-        clip[t, 12:20, 10 + step * t:18 + step * t] = 0.25
-        mask[t, 12:20, 10 + step * t:18 + step * t] = 1
-    return still, clip, mask
-
-
-STILL_REMAINING = {1: 288, 2: 96, 8: 0}                               # reach -> pixels no frame within it shows
-
-
-def check_pan(filled, remaining, source):
-    clean, clip, mask = pan_clip()
-    assert int(mask.sum()) == 1568 and not remaining.any()
-    assert (_bits(filled) == _bits(clean)).all()                       # all 1568 masked pixels are the true background, bit for bit
-    assert ((source >= 0) & (source < 8)).all() and ((source == np.arange(8)[:, None, None]) == (mask == 0)).all()
-
-
-def check_still(reach, filled, remaining, source):
-    still, clip, mask = still_clip(2)
-    assert int(remaining.sum()) == STILL_REMAINING[reach]
-    assert ((remaining == 1) == ((mask == 1) & (source == -1))).all()
-    age = np.abs(source - np.arange(8)[:, None, None])
-    assert (age[source >= 0] <= reach).all()
-    assert (_bits(filled) == np.where((remaining == 1)[..., None], _bits(clip), _bits(still))).all()
-
-
-def check_fixed(filled, remaining, source):
-    _, clip, mask = still_clip(0)
-    assert (_bits(remaining) == _bits(mask)).all() and (_bits(filled) == _bits(clip)).all()
-    assert (source == np.where(mask == 1, -1, np.arange(8)[:, None, None])).all()
 
 
 # ---- the properties, on the restatement ---------------------------------------------------------------------------------------------------

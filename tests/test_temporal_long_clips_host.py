@@ -4,7 +4,6 @@ kernels with these results, and that says something about origins tens of frames
 occurs, about disputes on a long clip and about smooth chains of 8 steps only if the clips make the rule go there.  That they do is
 asserted here as conditions; the counts seen when this was written stand beside them in brackets.  The cases and their cached
 restatement results are shared with the device's tests."""
-import functools
 
 import numpy as np
 import pytest
@@ -13,17 +12,12 @@ from tests import temporal_clips as clips
 from tests import temporal_fill_checked_ref as cref
 from tests import temporal_fill_ref as tref
 from tests import temporal_smooth_ref as sref
-
-FRAMES, PLANE = 48, (23, 33)
-LEVELS, SEARCH, SMOOTH = 3, 2, 8
-LEAVES = 40                                                            # the big box is in the frames .. LEAVES - 1
-ARRIVES = 6                                                            # the checked clip: the big box is in ARRIVES .. LEAVES - 1
-CHANGE = 30                                                            # the checked clip: the scene changes in this frame
-SMOOTH_FRAMES = 20
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
+from tests.compare import _f32_bits as _bits
+from tests.temporal_clips import (LONG_ARRIVES as ARRIVES, LONG_CHANGE as CHANGE, LONG_FRAMES as FRAMES, LONG_LEAVES as LEAVES,
+                                  LONG_LEVELS as LEVELS, LONG_PLANE as PLANE, LONG_SEARCH as SEARCH, LONG_SMOOTH as SMOOTH,
+                                  LONG_SMOOTH_FRAMES as SMOOTH_FRAMES, long_checked_clip as checked_clip,
+                                  long_checked_want as checked_want, long_fill_clip as fill_clip, long_fill_want as fill_want,
+                                  long_smooth_clip as smooth_clip, long_smooth_want as smooth_want)
 
 
 def same_bits(a, b):
@@ -35,53 +29,6 @@ def ages(mask, source):
     """The ages |t - source| of the borrowed pixels: masked, with an origin."""
     m = (mask if mask.ndim == 3 else np.broadcast_to(mask, source.shape)) == 1
     return np.abs(np.arange(len(source))[:, None, None] - source)[m & (source >= 0)]
-
-
-# ---- the cases; tests/test_gpu_temporal_long_clips.py runs the device on the same ones -------------------------------------------------
-def fill_clip(one_mask=False):
-    """(images, mask): the drift clip, the big box until it leaves in frame LEAVES; `one_mask`: the big box in every frame."""
-    mask = clips.stay_then_leave_mask(FRAMES, *PLANE, 0, LEAVES)
-    return clips.drift_clip(FRAMES, *PLANE), mask[0] if one_mask else mask
-
-
-@functools.lru_cache(maxsize=None)
-def fill_want(reach, one_mask=False):
-    return tref.temporal_fill_ref(*fill_clip(one_mask), LEVELS, SEARCH, SMOOTH, reach)
-
-
-@functools.lru_cache(maxsize=None)
-def checked_clip(one_mask=False):
-    """(images, mask): the drift clip with a scene change in frame CHANGE, the big box in the frames ARRIVES .. LEAVES - 1."""
-    mask = clips.stay_then_leave_mask(FRAMES, *PLANE, ARRIVES, LEAVES)
-    images = clips.scene_change(clips.drift_clip(FRAMES, *PLANE), CHANGE)
-    images.setflags(write=False)
-    return images, mask[ARRIVES] if one_mask else mask
-
-
-@functools.lru_cache(maxsize=None)
-def checked_want(reach, agree, one_mask=False):
-    return cref.temporal_fill_checked_ref(*checked_clip(one_mask), LEVELS, SEARCH, SMOOTH, reach, agree)
-
-
-def smooth_clip(frames, channels=3, one_mask=False):
-    """(images, mask): the first `frames` frames of the drift clip under a random mask of 30 %."""
-    mask = clips.random_mask(frames, *PLANE)
-    return clips.drift_clip(FRAMES, *PLANE, channels)[:frames], mask[0] if one_mask else mask
-
-
-@functools.lru_cache(maxsize=None)
-def _smooth_fields(frames, motion, channels, one_mask):
-    images, mask = smooth_clip(frames, channels, one_mask)
-    known = tref.known_bits(mask, frames)
-    return known, sref.fields(images, known, motion, LEVELS, SEARCH, SMOOTH)
-
-
-@functools.lru_cache(maxsize=None)
-def smooth_want(frames, radius, tolerance, motion, channels=3, one_mask=False):
-    """`sref.temporal_smooth_ref` of the case, its two lines with the fields -- which know nothing of radius and tolerance --
-    computed once (test_the_shared_fields_give_the_whole_restatement)."""
-    known, (fwd, bwd) = _smooth_fields(frames, motion, channels, one_mask)
-    return sref.smooth_frames(smooth_clip(frames, channels, one_mask)[0], known, fwd, bwd, radius, tolerance)
 
 
 # ---- the plain fill ----------------------------------------------------------------------------------------------------------------------

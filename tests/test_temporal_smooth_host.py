@@ -3,7 +3,6 @@
 argument checks, the node's protocol and the no-fallback errors.  Layouts, constants and names against the header are
 tests/test_cabi_mirror.py's, for the whole C ABI."""
 import ctypes
-import functools
 import os
 import re
 
@@ -13,110 +12,12 @@ import torch
 
 from lanpaint_amd import _cabi
 from tests import temporal_smooth_ref as sref
+from tests.compare import _f32_bits as _bits
+from tests.temporal_clips import (NOISE_RATIO, RADII, check_outside, check_smooth_ghost as check_ghost, check_smooth_noise as check_noise,
+                                  check_smooth_pan as check_pan, ghost_clip, noise_clip, smooth_pan_clip as pan_clip,
+                                  smooth_still_clip as still_clip)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-RADII = (1, 2, 3)
-PAN_PIXELS = {1: 1344, 2: 896, 3: 448}                               # masked pixels of the frames R .. F - 1 - R: 224 a frame
-NOISE_RATIO = {1: 6 / 16, 2: 70 / 256, 3: 924 / 4096}                # sum w^2 / (sum w)^2: 0.375, 0.273, 0.226
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
-
-
-# ---- the scenes of the three properties; tests/test_gpu_temporal_smooth.py runs the device on the same ones -----------------------------
-@functools.lru_cache(maxsize=None)
-def pan_clip():
-    """(clean clip, flickering clip, mask): 8 frames of 48 x 64 x 3 cut from one canvas of 8-bit values, panning (1, -2) px per
-    frame; the mask is fixed to the canvas, and under it even frames are 8 / 256 too bright and odd frames as much too dark."""
-    rng = np.random.default_rng(6)
-    F, H, W = 8, 48, 64
-    canvas = (rng.integers(64, 192, (H + F, W + 2 * F, 3)) / 256).astype(np.float32)
-    cm = np.zeros((H + F, W + 2 * F), np.float32)
-    cm[26:40, 30:46] = 1
-
-    def cut(a, t):
-        return a[t:t + H, 2 * (F - 1 - t):2 * (F - 1 - t) + W]
-    clean = np.stack([cut(canvas, t) for t in range(F)])
-    mask = np.stack([cut(cm, t) for t in range(F)])
-    clip = clean.copy()
-    for t in range(F):
-        clip[t][mask[t] == 1] += np.float32(8 / 256 if t % 2 == 0 else -8 / 256)
-    return clean, clip, mask
-
-
-@functools.lru_cache(maxsize=None)
-def still_clip():
-    """(still clip, mask): 9 equal frames of 32 x 48 x 3 in 0.25 .. 0.75 and a static mask."""
-    F, H, W = 9, 32, 48
-    frame = (0.25 + 0.5 * np.random.default_rng(7).random((1, H, W, 3))).astype(np.float32)
-    mask = np.zeros((H, W), np.float32)
-    mask[10:22, 14:34] = 1
-    return np.repeat(frame, F, axis=0), mask
-
-
-@functools.lru_cache(maxsize=None)
-def noise_clip():
-    """(still clip, noisy clip, mask): iid normal noise of sigma 0.02 under the mask of the still clip."""
-    still, mask = still_clip()
-    clip = still.copy()
-    clip[:, mask == 1] += np.random.default_rng(8).normal(0, 0.02, (still.shape[0], int(mask.sum()), 3)).astype(np.float32)
-    return still, clip, mask
-
-
-GHOST_FRAME, GHOST = 4, (slice(13, 19), slice(20, 28))               # a 6 x 8 patch inside the hole
-
-
-@functools.lru_cache(maxsize=None)
-def ghost_clip():
-    """(clip, mask): the still clip with a patch of 1.0 in one frame, inside the hole: at least 64 grey levels from the canvas."""
-    still, mask = still_clip()
-    clip = still.copy()
-    clip[GHOST_FRAME][GHOST] = 1.0
-    return clip, mask
-
-
-def check_outside(images, mask, out, support):
-    """Everything outside the mask is bits of the input with support -1; under it support counts 0 .. 2R."""
-    under = np.broadcast_to(mask == 1, support.shape)
-    assert (_bits(out)[~under] == _bits(images)[~under]).all() and (support[~under] == -1).all() and (support[under] >= 0).all()
-
-
-def check_pan(radius, motion, out, support):
-    clean, clip, mask = pan_clip()
-    F = clip.shape[0]
-    under = mask == 1
-    assert (np.abs(clip - clean)[under] == np.float32(8 / 256)).all()   # the error of the input, everywhere under the mask
-    check_outside(clip, mask, out, support)
-    inner = np.zeros_like(under)
-    inner[radius:F - radius] = under[radius:F - radius]
-    assert int(inner.sum()) == PAN_PIXELS[radius]
-    if motion == "background":
-        assert (_bits(out)[inner] == _bits(clean)[inner]).all()        # every one of them is the clean canvas, bit for bit
-        assert (support[inner] == 2 * radius).all()
-    else:
-        assert np.abs(out - clean)[under].mean() < np.abs(clip - clean)[under].mean()
-
-
-def check_noise(radius, out, support):
-    still, clip, mask = noise_clip()
-    F = clip.shape[0]
-    check_outside(clip, mask, out, support)
-    inner = slice(radius, F - radius)
-    before, after = (clip - still)[inner][:, mask == 1], (out - still)[inner][:, mask == 1]
-    ratio = float(after.astype(np.float64).var() / before.astype(np.float64).var())
-    print(f"radius {radius}: variance ratio {ratio:.4f}, the weights give {NOISE_RATIO[radius]:.4f}")
-    assert abs(ratio / NOISE_RATIO[radius] - 1) <= 0.15, (radius, ratio)
-
-
-def check_ghost(out, support):
-    clip, mask = ghost_clip()
-    check_outside(clip, mask, out, support)
-    for t in range(GHOST_FRAME - 2, GHOST_FRAME + 3):                  # the patch's frame and its four neighbours
-        assert (_bits(out[t][GHOST]) == _bits(clip[t][GHOST])).all(), t
-    assert (support[GHOST_FRAME][GHOST] == 0).all()
-    assert (support[GHOST_FRAME - 1][GHOST] == 2).all() and (support[GHOST_FRAME + 2][GHOST] == 3).all()   # the chain ends at the patch
-    assert (_bits(out) == _bits(clip)).all()                           # and the rest of the clip is still
 
 
 # ---- the properties, on the restatement ---------------------------------------------------------------------------------------------------

@@ -4,7 +4,6 @@ checks (made before any HIP call), the wrappers' argument checks, the nodes' pro
 the plain smooth's (tests/test_temporal_smooth_host.py) and two pop clips made from its pan.  Layouts, constants and names against
 the header are tests/test_cabi_mirror.py's, for the whole C ABI."""
 import ctypes
-import functools
 import os
 import re
 
@@ -15,78 +14,12 @@ import torch
 from lanpaint_amd import _cabi
 from tests import temporal_smooth_ref as sref
 from tests import temporal_smooth_robust_ref as rref
-from tests.test_temporal_smooth_host import (NOISE_RATIO, RADII, _bits, check_outside, ghost_clip, noise_clip, pan_clip, still_clip)
+from tests.compare import _f32_bits as _bits
+from tests.temporal_clips import (POP, RADII, check_ghost_removed, check_pan_equals_plain, check_pop, check_robust_noise as check_noise,
+                                  check_two_frame_pop, ghost_clip, noise_clip, pop_clip, smooth_pan_clip as pan_clip,
+                                  smooth_still_clip as still_clip)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-POP = np.float32(64 / 256)
-
-
-# ---- the scenes; tests/test_gpu_temporal_smooth_robust.py runs the device on the same ones ---------------------------------------------
-@functools.lru_cache(maxsize=None)
-def pop_clip(frames):
-    """(clip, mask): the clean pan clip with 64 / 256 added under the mask of the frames `frames`."""
-    clean, _, mask = pan_clip()
-    clip = clean.copy()
-    for t in frames:
-        clip[t][mask[t] == 1] += POP
-    return clip, mask
-
-
-def check_planes(images, mask, out, support, replaced):
-    """Outside the mask: the input's bits and -1 in both planes; under it support counts and replaced is 0 or 1."""
-    check_outside(images, mask, out, support)
-    under = np.broadcast_to(mask == 1, replaced.shape)
-    assert (replaced[~under] == -1).all() and np.isin(replaced[under], (0, 1)).all()
-    assert (support[replaced == 1] >= rref.QUORUM).all()
-
-
-def check_pan_equals_plain(robust, plain):
-    _, clip, mask = pan_clip()
-    out, support, replaced = robust
-    check_planes(clip, mask, out, support, replaced)
-    assert (_bits(out) == _bits(plain[0])).all() and (support == plain[1]).all()
-    assert (replaced[mask == 1] == 0).all()                            # nothing is rejected under either reference
-
-
-def check_pop(robust, plain):
-    clean, _, mask = pan_clip()
-    clip, _ = pop_clip((3,))
-    out, support, replaced = robust
-    check_planes(clip, mask, out, support, replaced)
-    assert (_bits(out) == _bits(clean)).all()                          # the clean clip, in every frame
-    assert int((replaced == 1).sum()) == 224 and (replaced[3][mask[3] == 1] == 1).all()
-    assert (_bits(plain[0]) == _bits(clip)).all()                      # the plain rule keeps the pop
-
-
-def check_two_frame_pop(radius, robust):
-    clean, _, mask = pan_clip()
-    clip, _ = pop_clip((3, 4))
-    out, support, replaced = robust
-    check_planes(clip, mask, out, support, replaced)
-    if radius == 1:                                                    # what lasts longer than R frames stays
-        assert (_bits(out) == _bits(clip)).all() and not (replaced == 1).any()
-    else:
-        assert (_bits(out) == _bits(clean)).all() and int((replaced == 1).sum()) == 448
-        assert (replaced[3:5][mask[3:5] == 1] == 1).all()
-
-
-def check_ghost_removed(robust):
-    clip, mask = ghost_clip()
-    still, _ = still_clip()
-    out, support, replaced = robust
-    check_planes(clip, mask, out, support, replaced)
-    assert (_bits(out) == _bits(still)).all() and int((replaced == 1).sum()) == 48
-
-
-def check_noise(radius, out, support, replaced):
-    still, clip, mask = noise_clip()
-    check_planes(clip, mask, out, support, replaced)
-    assert not (replaced == 1).any()
-    inner = slice(radius, clip.shape[0] - radius)
-    before, after = (clip - still)[inner][:, mask == 1], (out - still)[inner][:, mask == 1]
-    ratio = float(after.astype(np.float64).var() / before.astype(np.float64).var())
-    print(f"radius {radius}: variance ratio {ratio:.4f}, the weights give {NOISE_RATIO[radius]:.4f}")
-    assert abs(ratio / NOISE_RATIO[radius] - 1) <= 0.15, (radius, ratio)
 
 
 # ---- what follows from the rule, on the restatement ---------------------------------------------------------------------------------------

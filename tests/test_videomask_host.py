@@ -16,6 +16,7 @@ import torch
 from lanpaint_amd import _cabi, videomask
 from lanpaint_amd.videomask import FRAME_DTYPE, frame_plan, parse_keyframes_widget, pillow_bilinear_coeffs
 from tests import videomask_ref as vref
+from tests.image_inputs import _apply, _pairs
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FIXTURES = sorted(glob.glob(os.path.join(ROOT, "tests", "golden", "videomask_*.npz")))
@@ -113,32 +114,6 @@ def test_frame_plan_edges():
 
 
 # ---- Pillow's BILINEAR -------------------------------------------------------------------------------------------------------
-def _apply(codes, bx, kx, by, ky):
-    """The two integer passes the kernel runs, one numpy loop per output index (Pillow's ImagingResampleHorizontal_8bpc /
-    ImagingResampleVertical_8bpc)."""
-    h, _ = codes.shape
-    tmp = np.empty((h, len(bx)), np.int64)
-    for xx, (x0, n) in enumerate(bx):
-        ss = (1 << 21) + codes[:, x0:x0 + n].astype(np.int64) @ kx[xx, :n].astype(np.int64)
-        tmp[:, xx] = np.clip(ss >> 22, 0, 255)
-    out = np.empty((len(by), len(bx)), np.int64)
-    for yy, (y0, n) in enumerate(by):
-        ss = (1 << 21) + ky[yy, :n].astype(np.int64) @ tmp[y0:y0 + n]
-        out[yy] = np.clip(ss >> 22, 0, 255)
-    return out.astype(np.uint8)
-
-
-def _pairs():
-    rng = np.random.default_rng(3)
-    pairs = [((832, 480), (1280, 720)), ((7, 9), (3, 400)), ((56, 40), (97, 61)), ((56, 40), (23, 17)), ((45, 31), (19, 53)),
-             ((10, 10), (10, 17)), ((13, 9), (40, 9)), ((1, 5), (7, 1)), ((300, 2), (1, 1))]
-    while len(pairs) < 32:
-        w, h = (int(v) for v in rng.integers(1, 200, 2))
-        ow, oh = (int(v) for v in rng.integers(1, 300, 2))
-        pairs.append(((w, h), (ow, oh)))
-    return pairs
-
-
 @pytest.mark.parametrize("src,dst", _pairs())
 def test_pillow_coefficients_equal_live_pil(src, dst):
     Image = pytest.importorskip("PIL.Image")
